@@ -7,20 +7,26 @@ rgbd_benchmark parameters with sparse VO / MOD / loop clo
 the reference's own early stop (icp_iter = 10).  A "step" is one frame.  Frames are rendered before
 the timed region and are resident in HBM when it starts.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1: launched by torch.distributed.run, one rank per GPU; the map is sharded by world-space
   tile, the frame is replicated, ICP / association are exchanged over RCCL ("strong" scaling:
   the total map size is fixed).
 
-Prints ONE JSON line (rank 0) with the contract keys plus "roofline" (dominant kernel, measured
-live with hipEvents on the library's stream) and "cpu_baseline" (the CPU oracle = a single-threaded
-port of the reference algorithm, timed on this box's host cores on a bounded sample)."""
+Prints ONE JSON line (rank 0) with the contract keys (metric, value, unit, ms_per_step, ...).  A plain
+run sets up, warms up, times the K steps and stops there.  --full adds everything else this script
+measures: "roofline" (dominant kernel, measured live with hipEvents on the library's stream), the
+sequential latency, the steady state, the extras (host frames, pre-filter, real frames, the other
+BASELINE configurations) and "cpu_baseline" (the CPU oracle = a single-threaded port of the reference
+algorithm, timed on this box's host cores on a bounded sample) with its parity check.
+--dump-outputs DIR writes what the timed path returned at its last step as .npy files (dump_outputs)."""
 import argparse
 import ctypes
 import json
 import os
+import subprocess
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -233,7 +239,7 @@ def real_frames_leg(lib, dev, model, nvis, cap):
     superpixel-row lookups whose label lay outside the tile's 7 x 7-cell LDS window (the exact global path)."""
     from supersurfel_fusion_amd import replay
     path = os.path.join(ROOT, "tests", "golden", "tum_fr1_xyz_8frames.npz")
-    if not os.path.exists(path):
+    if not replay.npz_parts(path):
         return dict(error="tests/golden/tum_fr1_xyz_8frames.npz is missing")
     fr = [(np.ascontiguousarray(rgb), np.ascontiguousarray(depth, np.float32)) for _, rgb, depth in replay.frames_from_npz(path)]
     nr = len(fr)
@@ -349,24 +355,47 @@ def pin_to_gpu_numa_node(local):
 
 def render_frames(n, tum_shaped=False):
     """tum_shaped (BASELINE config 5): ~25 % of the pixels holes, depth quantised to 16 bits at 5000 counts per metre and
-    converted back as the benchmark node does (depth_scale 0.0002)"""
-    frames = []
-    for k in range(n):
+    converted back as the benchmark node does (depth_scale 0.0002).  Frame k depends on k alone (its own seeded stream), so
+    the frames are rendered on a few threads (numpy releases the interpreter lock in its array loops): same frames, less set-up."""
+    def one(k):
         R, t = synthetic.orbit_pose(k)
         rgb, depth, _ = synthetic.render(R, t, W, H, noise=True, holes=0.25 if tum_shaped else 0.0, rng=np.random.default_rng(1000 + k))
         if tum_shaped:
             d16 = np.clip(np.rint(depth.astype(np.float64) * 5000.0), 0, 65535).astype(np.uint16)
             depth = (d16.astype(np.float64) * 0.0002).astype(np.float32)
-        frames.append((rgb, depth))
-    return frames
+        return rgb, depth
+    ncpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    with ThreadPoolExecutor(max(1, min(n, ncpu, 16))) as ex:
+        return list(ex.map(one, range(n)))
+
+
+# --dump-outputs: the frame result's counters, and the rows of the map sampled (fixed seed) when it holds more than DUMP_ROWS
+RESULT_COUNTERS = ("icp_valid", "icp_iters", "n_model", "n_visible", "n_removed", "n_inserted", "n_updated", "stamp")
+DUMP_ROWS = 1 << 18
+
+
+def dump_outputs(out_dir, f, last):
+    """What the timed path hands its caller at its last step, one .npy per array (float32 / float64; ~32 MB at the default
+    workload): pose (12 floats) and counters of the frame result, the frame's superpixel label map, and the map after the frame
+    (every field of up to DUMP_ROWS rows: a fixed, seeded sample of a larger map; model_rows holds the sampled row numbers)."""
+    os.makedirs(out_dir, exist_ok=True)
+    save = lambda name, arr: np.save(os.path.join(out_dir, name + ".npy"), arr)      # noqa: E731
+    save("pose", np.asarray(last["pose"], np.float32))
+    save("counters", np.array([last.get(k, np.nan) for k in RESULT_COUNTERS], np.float64))
+    save("index_map", f.index_map().astype(np.float64))
+    model = f.get_model()
+    n = len(model["confidences"])
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+    save("model_rows", rows.astype(np.float64))
+    for name, arr in model.items():
+        save("model_" + name, arr[rows].astype(np.float32 if arr.dtype == np.float32 else np.float64))
 
 
 def other_config(cfg_n, steps, pin):
     """bench.py --config <cfg_n> in a process of its own -> what the driver's line carries about it: frames/s, the dominant
     kernel with its roofline fraction and (when a PMC file stamped with the current kernel sources exists for that
     configuration) its HBM traffic, the whole-frame roofline fraction"""
-    import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", str(cfg_n), "--steps", str(steps), "--extras", "0",
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", str(cfg_n), "--steps", str(steps), "--full", "--extras", "0",
            "--cpu-frames", "0", "--pin", str(pin)]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     try:
@@ -387,6 +416,13 @@ def other_config(cfg_n, steps, pin):
                 per_kernel={k: dict(avg_us=v["avg_us"], achieved_GBs=v.get("achieved_GBs")) for k, v in (d.get("per_kernel") or {}).items()
                             if k in ("icp_accumulate", "match", "update_insert", "reorder_move_icp", "reorder_move", "update_pass_rgbd", "render_moments", "bilateral_prefilter", "apply_deformation")},
                 command=" ".join(["bench.py"] + cmd[2:]))
+
+
+def workload_text(cfg_n, gn, gv):
+    """the line's config.workload: what was timed, with the map's global live / visible row counts"""
+    return ("%dx%d synthetic RGB-D orbit (seed 1234), map seeded with %d supersurfels "
+            "(~%d live, ~%d visible), reference rgbd_benchmark parameters, extract+ICP+fuse per frame%s"
+            % (W, H, N_MODEL, gn, gv, " (BASELINE config 3: all seeded supersurfels visible, 10 forced ICP iterations)" if cfg_n == 3 else ""))
 
 
 def launch_plan(gpus, env, device_count, argv):
@@ -424,8 +460,13 @@ def error_line(text, gpus):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1200)
+    ap.add_argument("--steps", type=int, default=None, help="timed frames (default 1200; 64 at --config 3)")
     ap.add_argument("--warmup", type=int, default=48)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too (sequential latency, stage split, per-kernel roofline, steady state, "
+                         "the extras, the CPU baseline and its parity check); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned at its last step to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--rendered-frames", type=int, default=64,
                     help="distinct orbit frames rendered; the sequence sweeps them back and forth (consecutive frames stay 1 degree apart)")
     ap.add_argument("--seed-order", default="seeded", choices=["seeded", "image"],
@@ -469,7 +510,9 @@ def main():
     global W, H, P, N_MODEL
     if a.config == 3:
         W, H, a.force_icp = 1280, 960, True
-        a.steps, a.warmup, a.rendered_frames = min(a.steps, 64), min(a.warmup, 8), min(a.rendered_frames, 16)
+        a.steps = 64 if a.steps is None else a.steps
+        a.warmup, a.rendered_frames = min(a.warmup, 8), min(a.rendered_frames, 16)
+    a.steps = 1200 if a.steps is None else a.steps
     P = W * H
 
     # how was this started?  N > 1 without a launcher: start one (one rank per GPU); a box that cannot run it gets one
@@ -485,7 +528,8 @@ def main():
         os.dup2(saved_stdout, 1)                   # the ranks inherit the real stdout: rank 0 prints the line
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
         env.setdefault("OMP_NUM_THREADS", "16")     # torch.distributed.run would set 1 (and say so): the cpu_baseline leg of rank 0 uses OpenMP
-        os.execve(sys.executable, detail, env)
+        # the launcher runs as a fresh child process (this one has already asked the runtime for its devices)
+        sys.exit(subprocess.run(detail, env=env).returncode)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if a.config == 4:
@@ -678,7 +722,7 @@ def main():
     fill = None
     if native_seq:
         results = [r.as_dict() for r in results]
-        if K <= 64:
+        if K <= 64 and a.full:
             # where a short timed region goes: completion time of every frame inside ssf_process_sequence (the library's
             # own clock, from its entry), the call's return and the end of the closing barrier, all in microseconds
             tt_ = np.zeros(64)
@@ -695,6 +739,41 @@ def main():
                 fill["extract_batches_launched"] = [dict(at_us=round(float(mk[256 + 2 * i]), 1), frames=int(mk[257 + 2 * i]), host_us=round(1e4 * (mk[257 + 2 * i] % 1.0), 1)) for i in range(32) if mk[256 + 2 * i] >= 0]
     iters = [r["icp_iters"] for r in results]
     last = results[-1]
+    if world > 1:
+        tt = torch.tensor([dt], dtype=torch.float64, device=dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        dt = float(tt.item())
+    exchange_name = (a.comm if native_ok and drv is None else "torch.distributed") if exchange else "none"
+    out = None
+
+    def finish(out):
+        f.close()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        if rank == 0:
+            sys.stdout.flush()
+            ctypes.CDLL(None).fflush(None)             # C-level buffers of the runtime libraries (to stderr)
+            os.dup2(saved_stdout, 1)
+            print(json.dumps(out), flush=True)
+
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, f, last)
+    if not a.full:
+        # a plain run ends here: the headline and the configuration it was measured on; everything else is --full's
+        gcounts = f.global_counts() if drv is None else dict(n_model=last["global_n_model"], n_visible=last["global_n_visible"])
+        if rank == 0:
+            out = {
+                "metric": "frames_per_sec", "value": K / dt, "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": a.warmup,
+                "ms_per_step": 1000.0 * dt / K, "higher_is_better": True, "scaling": "weak" if a.config == 4 else "strong", "vs_baseline": None,
+                "dtype": "f32", "data": "synthetic",
+                "config": {"workload": workload_text(a.config, gcounts["n_model"], gcounts["n_visible"]),
+                           "width": W, "height": H, "n_model": int(gcounts["n_model"]), "n_visible": int(gcounts["n_visible"]), "superpixels": f.S,
+                           "icp_iter_max": 10, "icp_iters_mean": float(np.mean(iters)), "icp_forced": bool(a.force_icp), "baseline_config": a.config,
+                           "seed_order": a.seed_order, "exchange": exchange_name, "pipeline_depth": depth, "extract_batch": batch},
+                "pipeline_depth": depth, "extract_batch": batch, "warmup_extra_frames": Wm - a.warmup, "host_affinity": affinity,
+            }
+        finish(out)
+        return
     # strictly sequential latency (one frame in flight, pipeline_depth 0 / extract_batch 1): a second handle at
     # N = 1, the same handle through the one-frame entry point otherwise
     nseq = a.profile_frames
@@ -716,10 +795,6 @@ def main():
     if fseq is not None:
         fseq.close()
     base = Wm + K + (0 if fseq is not None else 4 + nseq)
-    if world > 1:
-        tt = torch.tensor([dt], dtype=torch.float64, device=dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt = float(tt.item())
 
     # ---- roofline of the dominant kernel: per-kernel hipEvent times on the library's stream ----
     # (same submission pattern as the timed region: batched / pipelined when configured)
@@ -1017,14 +1092,11 @@ def main():
             "metric": "frames_per_sec", "value": K / dt, "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": a.warmup,
             "ms_per_step": 1000.0 * dt / K, "higher_is_better": True, "scaling": "weak" if a.config == 4 else "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%dx%d synthetic RGB-D orbit (seed 1234), map seeded with %d supersurfels "
-                                   "(~%d live, ~%d visible), reference rgbd_benchmark parameters, extract+ICP+fuse per frame%s"
-                                   % (W, H, N_MODEL, gn, gv, " (BASELINE config 3: all seeded supersurfels visible, 10 forced ICP iterations)"
-                                      if a.config == 3 else ""),
+            "config": {"workload": workload_text(a.config, gn, gv),
                        "width": W, "height": H, "n_model": int(gn), "n_visible": int(gv), "superpixels": n_superpixels,
                        "icp_iter_max": 10, "icp_iters_mean": float(np.mean(iters)), "icp_forced": bool(a.force_icp), "baseline_config": a.config,
                        "seed_order": a.seed_order,      # "seeded": the BASELINE workload; "image": a measurement beside it (see --seed-order)
-                       "exchange": (a.comm if native_ok and drv is None else "torch.distributed") if exchange else "none",
+                       "exchange": exchange_name,
                        "exchange_note": (("native peer-to-peer exchange regions (no collective launches)" if a.comm == "p2p" else "native RCCL on the track stream") if native_ok and drv is None else "torch.distributed driver") if exchange else "none (1 rank)",
                        # what the attached exchange itself reports (ncclCommCount / opened regions): must equal n_gpus
                        "exchange_ranks_reported": comm_info["ranks"], "exchange_backend_attached": comm_info["backend"],
@@ -1053,14 +1125,7 @@ def main():
             "roofline": roofline, "frame_roofline": frame_roofline, "cpu_baseline": cpu, "extras": extras, "kernel_source_sha": kernel_source_sha(), "host_affinity": affinity,
             "per_kernel": per_kernel,
         }
-    f.close()
-    if dist.is_initialized():
-        dist.destroy_process_group()
-    if rank == 0:
-        sys.stdout.flush()
-        ctypes.CDLL(None).fflush(None)             # C-level buffers of the runtime libraries (to stderr)
-        os.dup2(saved_stdout, 1)
-        print(json.dumps(out), flush=True)
+    finish(out)
 
 
 if __name__ == "__main__":

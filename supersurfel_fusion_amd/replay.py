@@ -67,7 +67,43 @@ def pack_frames(dataset_dir, assoc_path, out_npz, n):
     for i, e in enumerate(ent):
         arrs["rgb%d" % i] = np.asarray(Image.open(os.path.join(dataset_dir, e["rgb"])).convert("RGB"), np.uint8)
         arrs["depth%d" % i] = np.asarray(Image.open(os.path.join(dataset_dir, e["depth"])), np.uint16)
-    np.savez_compressed(out_npz, **arrs)
+    save_npz_parts(out_npz, arrs)
+
+
+def npz_parts(path):
+    """the files of a frame archive: `path` itself, or its parts <stem>.part<k>.npz (save_npz_parts), in frame order"""
+    if os.path.exists(path):
+        return [path]
+    stem = path[:-4] if path.endswith(".npz") else path
+    parts, k = [], 0
+    while os.path.exists("%s.part%d.npz" % (stem, k)):
+        parts.append("%s.part%d.npz" % (stem, k)); k += 1
+    return parts
+
+
+def save_npz_parts(path, arrs):
+    """A frame archive (lines, rgb<k>, depth<k>) as one compressed file per frame, <stem>.part<k>.npz (part 0 also holds the
+    association lines): every file of a committed archive stays below 1 MiB.  load_npz reads it back whole."""
+    stem = path[:-4] if path.endswith(".npz") else path
+    k = 0
+    while "rgb%d" % k in arrs:
+        part = {"rgb%d" % k: arrs["rgb%d" % k], "depth%d" % k: arrs["depth%d" % k]}
+        if k == 0:
+            part["lines"] = arrs["lines"]
+        np.savez_compressed("%s.part%d.npz" % (stem, k), **part)
+        k += 1
+
+
+def load_npz(path):
+    """the arrays of a frame archive, whole or in parts (npz_parts), as one dict"""
+    parts = npz_parts(path)
+    if not parts:
+        raise FileNotFoundError(path)
+    out = {}
+    for p in parts:
+        with np.load(p) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def rot_to_quat_xyzw(R):
@@ -190,7 +226,7 @@ def frames_from_dataset(dataset_dir, depth_scale=0.0002, max_frames=None):
 
 
 def frames_from_npz(path, depth_scale=0.0002):
-    z = np.load(path)
+    z = load_npz(path)
     i = 0
     while "rgb%d" % i in z:
         stamp = str(z["lines"][i]).split()[0]

@@ -90,7 +90,7 @@ def main():
     for j, i in enumerate((20, 21, 60, 61)):
         arrs["rgb%d" % j] = np.asarray(Image.open(os.path.join(DATASET, all_ent[i]["rgb"])).convert("RGB"), np.uint8)
         arrs["depth%d" % j] = np.asarray(Image.open(os.path.join(DATASET, all_ent[i]["depth"])), np.uint16)
-    np.savez_compressed(os.path.join(GOLD, "tum_fr3_walking_4frames.npz"), **arrs)
+    replay.save_npz_parts(os.path.join(GOLD, "tum_fr3_walking_4frames.npz"), arrs)
 
     gt = np.array([e["gt"][0] for e in ent])
     est = np.array([r["pose"][9:] for r in res], np.float64)

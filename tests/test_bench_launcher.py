@@ -76,11 +76,12 @@ def test_two_gpus_on_a_one_gpu_box_is_the_error_record_not_a_traceback():
 
 @pytest.mark.gpu
 def test_the_bench_line_keeps_the_drivers_contract():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's form, with the slow legs shortened): ONE JSON line on stdout with
-    the contract's keys, the metric's configuration, `roofline` and `cpu_baseline` objects of the prescribed shape, and figures that
-    are consistent with each other (value = steps / time, the dominant kernel's share below the step time, achieved below peak)."""
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` (the driver's form with everything measured beside it, the slow legs
+    shortened): ONE JSON line on stdout with the contract's keys, the metric's configuration, `roofline` and `cpu_baseline` objects of
+    the prescribed shape, and figures that are consistent with each other (value = steps / time, the dominant kernel's share below the
+    step time, achieved below peak)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--extras", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--extras", "0",
                         "--cpu-frames", "4", "--profile-frames", "16"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -111,3 +112,89 @@ def test_the_bench_line_keeps_the_drivers_contract():
     par = cb["parity"]
     assert par == d["parity"] and "error" not in par, par
     assert par["frames"] == 4 and par["frames_bit_equal"] == 4 and par["frames_counters_equal"] == 4 and par["max_abs_pose_diff"] == 0.0 and par["within_tolerance"] is True
+
+
+def test_the_options_of_a_plain_and_a_full_run_are_there():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_threaded_rendering_gives_the_serial_frames():
+    import numpy as np
+    import bench
+    from supersurfel_fusion_amd import synthetic
+    for tum_shaped in (False, True):
+        frames = bench.render_frames(3, tum_shaped=tum_shaped)
+        for k, (rgb, depth) in enumerate(frames):
+            R, t = synthetic.orbit_pose(k)
+            rgb_s, depth_s, _ = synthetic.render(R, t, bench.W, bench.H, noise=True, holes=0.25 if tum_shaped else 0.0,
+                                                 rng=np.random.default_rng(1000 + k))
+            if tum_shaped:
+                d16 = np.clip(np.rint(depth_s.astype(np.float64) * 5000.0), 0, 65535).astype(np.uint16)
+                depth_s = (d16.astype(np.float64) * 0.0002).astype(np.float32)
+            assert np.array_equal(rgb, rgb_s) and np.array_equal(depth.view(np.uint32), depth_s.view(np.uint32)), k
+
+
+def test_dump_outputs_writes_the_frame_result_and_a_seeded_sample_of_the_map(oracle_lib, tmp_path, monkeypatch):
+    """bench.dump_outputs on the CPU checker: float32 / float64 arrays only, the result of the last frame, and a map larger than
+    DUMP_ROWS sampled by a fixed seed (two dumps of the same state are the same files)"""
+    import numpy as np
+    import bench
+    from supersurfel_fusion_amd import binding, synthetic
+    W, H = 160, 128
+    K = synthetic.intrinsics(W, H)
+    f = binding.Fusion(oracle_lib, oracle_lib.default_config(**{k: K[k] for k in ("width", "height", "fx", "fy", "cx", "cy")},
+                                                             nb_supersurfels_max=4096))
+    for k in range(2):
+        R, t = synthetic.orbit_pose(k)
+        rgb, depth, _ = synthetic.render(R, t, W, H, noise=True, rng=np.random.default_rng(k))
+        last = f.process_frame(rgb, depth)
+    n = f.counts()["n_model"]
+    assert n > 64
+    monkeypatch.setattr(bench, "DUMP_ROWS", 64)
+    bench.dump_outputs(str(tmp_path / "a"), f, last)
+    bench.dump_outputs(str(tmp_path / "b"), f, last)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(["pose.npy", "counters.npy", "index_map.npy", "model_rows.npy"] + ["model_%s.npy" % s for s, _, _ in binding.SURFEL_FIELDS])
+    got = {p[:-4]: np.load(str(tmp_path / "a" / p)) for p in names}
+    for name, arr in got.items():
+        assert arr.dtype in (np.float32, np.float64), name
+        assert np.array_equal(arr, np.load(str(tmp_path / "b" / (name + ".npy")))), name
+    assert np.array_equal(got["pose"], last["pose"]) and got["counters"][2] == last["n_model"] == n
+    assert np.array_equal(got["index_map"], f.index_map())
+    rows = got["model_rows"].astype(np.int64)
+    assert len(rows) == 64 and np.all(np.diff(rows) > 0) and rows[-1] < n
+    model = f.get_model()
+    for name, _, _ in binding.SURFEL_FIELDS:
+        assert np.array_equal(got["model_" + name], model[name][rows]), name
+    f.close()
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_steps_and_dumps_the_same_outputs_each_time(tmp_path):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR` (the plain form): the headline line without the legs of
+    --full, ms_per_step of exactly --steps timed frames, and outputs that are the same, array for array, from run to run"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                            "--dump-outputs", str(tmp_path / d)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines.append(json.loads(out[0]))
+    for d in lines:
+        assert d["metric"] == "frames_per_sec" and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["steps"] == 20 and d["warmup"] == 5 and abs(d["value"] * d["ms_per_step"] / 1000.0 - 1.0) < 1e-6 and d["value"] > 1000
+        for key in ("roofline", "cpu_baseline", "per_kernel", "extras", "parity", "stage_ms"):
+            assert key not in d, key
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert "pose.npy" in files and "index_map.npy" in files and "model_positions.npy" in files
+    assert sum((tmp_path / "a" / p).stat().st_size for p in files) < 64 << 20
+    for p in files:
+        x, y = np.load(str(tmp_path / "a" / p)), np.load(str(tmp_path / "b" / p))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), p
+    n_model = int(np.load(str(tmp_path / "a" / "counters.npy"))[2])
+    assert n_model == lines[0]["config"]["n_model"] and len(np.load(str(tmp_path / "a" / "model_rows.npy"))) == 1 << 18

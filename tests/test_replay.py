@@ -27,7 +27,7 @@ def tum_frames(n):
 
 
 def test_association_parsing(tmp_path):
-    z = np.load(TUM)
+    z = replay.load_npz(TUM)
     p = tmp_path / "associations_with_gt.txt"
     p.write_text("\n".join(str(l) for l in z["lines"]) + "\n\n")
     ent = replay.read_associations(str(p))
@@ -74,7 +74,7 @@ def test_real_tum_frames_through_the_oracle(oracle_lib, tmp_path):
     assert res[1]["icp_valid"] == 1 and res[2]["icp_valid"] == 1
     assert (f.inlier_map() > 0).mean() < 0.8            # holes are not inliers
     # frame-to-frame motion of fr1_xyz is centimetres: compare with the ground-truth displacement
-    z = np.load(TUM)
+    z = replay.load_npz(TUM)
     gt = np.array([[float(v) for v in str(l).split()[5:8]] for l in z["lines"][:3]])
     est = np.array([r["pose"][9:] for r in res])
     assert abs(np.linalg.norm(est[2] - est[0]) - np.linalg.norm(gt[2] - gt[0])) < 0.02

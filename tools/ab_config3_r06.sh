@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${1:?outdir}; mkdir -p $O; cd $R
 N=${2:-2}
 run() { # tag, env...
   local tag=$1; shift
-  env "$@" timeout 400 python bench.py --config 3 --extras 0 --cpu-frames 0 2> $O/$tag.err | tail -n 1 | python -c "
+  env "$@" timeout 400 python bench.py --full --config 3 --extras 0 --cpu-frames 0 2> $O/$tag.err | tail -n 1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['per_kernel']
 print('$tag', round(d['value'],1), 'frames/s  frame_frac', round(d['frame_roofline']['frac'],3), ' '.join('%s %.1f' % (n, k[n]['avg_us']) for n in ('icp_accumulate','match','bin_rows','update_insert','reorder_move_icp','reorder_move') if n in k))" >> $O/summary.txt
 }

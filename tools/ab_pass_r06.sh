@@ -12,7 +12,7 @@ done
 bash tools/kernel_ab.sh $OD $N update_pass_rgbd,update_pass_rgb,render_moments product "$@" > /dev/null 2>&1
 for r in $(seq 1 $N); do for V in product "$@"; do
   unset SSF_PRODUCT_VARIANT; [ $V != product ] && export SSF_PRODUCT_VARIANT=$V
-  timeout 300 python bench.py --extras 0 --cpu-frames 0 --steps 20 --warmup 5 2>/dev/null | tail -n 1 | python -c "
+  timeout 300 python bench.py --full --extras 0 --cpu-frames 0 --steps 20 --warmup 5 2>/dev/null | tail -n 1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$V driver-form run $r', round(d['value'],1), 'frac', d['roofline']['frac'], 'steady', d['config'].get('steady_state_frames_per_sec'))" >> $O/driver_form.txt
 done; done
 cat $O/summary.txt $O/kernel_ab.txt $O/driver_form.txt

@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${1:?outdir}; mkdir -p $O; cd $R
 export SSF_PRODUCT_VARIANT=lab
 for r in 1 2; do for m in 1 0; do
-  SSF_ICP_AHEAD=$m timeout 300 python bench.py --gpus 1 --steps 64 --warmup 5 --extras 0 --cpu-frames 0 > $O/k64_ahead${m}_$r.json 2> $O/k64_ahead${m}_$r.err
+  SSF_ICP_AHEAD=$m timeout 300 python bench.py --full --gpus 1 --steps 64 --warmup 5 --extras 0 --cpu-frames 0 > $O/k64_ahead${m}_$r.json 2> $O/k64_ahead${m}_$r.err
 done; done
 python - <<PY
 import json,glob

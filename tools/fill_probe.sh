@@ -15,9 +15,9 @@ if 'track_entered_us' in p:
     print('   first record->icp done:', ' '.join('%d' % (b-a) for a,b in zip(r1, ic)))
     print('   icp done->frame done:', ' '.join('%d' % (b-a) for a,b in zip(ic, t)))
     print('   iterations:', p['icp_iters'], ' batches launched (us, frames):', p['extract_batches_launched'])"; }
-for r in 1 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 --extras 0 --cpu-frames 0 --profile-frames 0 2>/dev/null | show pinned_$r; done
-for r in 1 2; do python bench.py --gpus 1 --steps 20 --warmup 5 --extras 0 --cpu-frames 0 --profile-frames 0 --pin 0 2>/dev/null | show unpinned_$r; done
+for r in 1 2 3; do python bench.py --full --gpus 1 --steps 20 --warmup 5 --extras 0 --cpu-frames 0 --profile-frames 0 2>/dev/null | show pinned_$r; done
+for r in 1 2; do python bench.py --full --gpus 1 --steps 20 --warmup 5 --extras 0 --cpu-frames 0 --profile-frames 0 --pin 0 2>/dev/null | show unpinned_$r; done
 for e in "$@"; do
-  for r in 1 2; do env $e python bench.py --gpus 1 --steps 20 --warmup 5 --extras 0 --cpu-frames 0 --profile-frames 0 2>/dev/null | show ${e}_$r; done
+  for r in 1 2; do env $e python bench.py --full --gpus 1 --steps 20 --warmup 5 --extras 0 --cpu-frames 0 --profile-frames 0 2>/dev/null | show ${e}_$r; done
 done
 python tools/startup_probe.py 2>/dev/null

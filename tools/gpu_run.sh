@@ -12,7 +12,7 @@
 #   prof3        the profile command of the trace / pmc steps that follow becomes BASELINE config 3 (1280x960, 1 M rows in view,
 #                10 forced ICP iterations; outputs tagged _config3)
 #   prof5 / prof2  the same for BASELINE config 5 / back to the default workload
-#   driver       the driver's exact command (python bench.py --gpus 1 --steps 20 --warmup 5, everything on)
+#   driver       the driver's command with everything on (python bench.py --full --gpus 1 --steps 20 --warmup 5)
 #   gpus2        python bench.py --gpus 2 ... on this one-GPU box: must end in the JSON error record
 #   sharded1     every multi-GPU exchange on one rank (RCCL, then the peer-to-peer regions)
 #   env:K=V      export K=V for the steps that follow (A/B of kernel variants on the same box)
@@ -23,22 +23,22 @@ O=$R/gpurun_out/${1:?outdir}; shift
 mkdir -p $O
 cd $R
 TAG=""
-PROF="python $R/bench.py --cpu-frames 0 --profile-frames 0 --extras 0 --steps 96 --warmup 8"
-PROFNOTE="bench.py --cpu-frames 0 --profile-frames 0 --extras 0 --steps 96 --warmup 8 (pipelined 2 x 8)"
+PROF="python $R/bench.py --full --cpu-frames 0 --profile-frames 0 --extras 0 --steps 96 --warmup 8"
+PROFNOTE="bench.py --full --cpu-frames 0 --profile-frames 0 --extras 0 --steps 96 --warmup 8 (pipelined 2 x 8)"
 lastline() { [ -s "$1" ] && tail -n 1 "$1" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$2', round(d['value'],1), d.get('unit'), 'frac', round(d['roofline']['frac'],4), d['roofline'].get('kernel'), 'seq_ms', d.get('sequential_ms_per_frame'))" 2>/dev/null >> $O/summary.txt; }
 for step in "$@"; do
   case $step in
-    prof3) PROF="python $R/bench.py --config 3 --cpu-frames 0 --profile-frames 0 --extras 0 --steps 32 --warmup 8"; PROFNOTE="bench.py --config 3 --cpu-frames 0 --profile-frames 0 --extras 0 --steps 32 --warmup 8 (1280x960, pipelined 2 x 4)"; export PMC_EXTRACT_BATCH=4; export PROFPIX=1228800; TAG="_config3";;
-    prof5) PROF="python $R/bench.py --config 5 --cpu-frames 0 --profile-frames 0 --extras 0 --steps 96 --warmup 8"; PROFNOTE="bench.py --config 5 --cpu-frames 0 --profile-frames 0 --extras 0 --steps 96 --warmup 8 (TUM-shaped frames, pre-filter in the frame, pipelined 2 x 12)"; export PMC_EXTRACT_BATCH=12; export PROFPIX=307200; TAG="_config5";;
-    prof2) PROF="python $R/bench.py --cpu-frames 0 --profile-frames 0 --extras 0 --steps 96 --warmup 8"; PROFNOTE="bench.py --cpu-frames 0 --profile-frames 0 --extras 0 --steps 96 --warmup 8 (pipelined 2 x 8)"; export PMC_EXTRACT_BATCH=8; export PROFPIX=307200; TAG="";;
+    prof3) PROF="python $R/bench.py --full --config 3 --cpu-frames 0 --profile-frames 0 --extras 0 --steps 32 --warmup 8"; PROFNOTE="bench.py --full --config 3 --cpu-frames 0 --profile-frames 0 --extras 0 --steps 32 --warmup 8 (1280x960, pipelined 2 x 4)"; export PMC_EXTRACT_BATCH=4; export PROFPIX=1228800; TAG="_config3";;
+    prof5) PROF="python $R/bench.py --full --config 5 --cpu-frames 0 --profile-frames 0 --extras 0 --steps 96 --warmup 8"; PROFNOTE="bench.py --full --config 5 --cpu-frames 0 --profile-frames 0 --extras 0 --steps 96 --warmup 8 (TUM-shaped frames, pre-filter in the frame, pipelined 2 x 12)"; export PMC_EXTRACT_BATCH=12; export PROFPIX=307200; TAG="_config5";;
+    prof2) PROF="python $R/bench.py --full --cpu-frames 0 --profile-frames 0 --extras 0 --steps 96 --warmup 8"; PROFNOTE="bench.py --full --cpu-frames 0 --profile-frames 0 --extras 0 --steps 96 --warmup 8 (pipelined 2 x 8)"; export PMC_EXTRACT_BATCH=8; export PROFPIX=307200; TAG="";;
     driver)
-      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver_command.err; lastline $O/bench_driver_command.json driver_command;;
+      timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver_command.err; lastline $O/bench_driver_command.json driver_command;;
     gpus2)
       timeout 300 python bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_gpus2.json 2> $O/bench_gpus2.err; echo "gpus2 rc=$? $(cat $O/bench_gpus2.json)" >> $O/summary.txt;;
     sharded1)
-      timeout 400 python bench.py --force-sharded --extras 0 --cpu-frames 0 --steps 240 > $O/bench_one_rank_rccl.json 2> $O/bench_one_rank_rccl.err; lastline $O/bench_one_rank_rccl.json one_rank_rccl
-      timeout 400 python bench.py --force-sharded --comm p2p --extras 0 --cpu-frames 0 --steps 240 > $O/bench_one_rank_p2p.json 2> $O/bench_one_rank_p2p.err; lastline $O/bench_one_rank_p2p.json one_rank_p2p
-      timeout 400 python bench.py --force-sharded --extract dealt --extras 0 --cpu-frames 0 --steps 240 > $O/bench_one_rank_rccl_dealt.json 2> $O/bench_one_rank_rccl_dealt.err; lastline $O/bench_one_rank_rccl_dealt.json one_rank_rccl_dealt;;
+      timeout 400 python bench.py --full --force-sharded --extras 0 --cpu-frames 0 --steps 240 > $O/bench_one_rank_rccl.json 2> $O/bench_one_rank_rccl.err; lastline $O/bench_one_rank_rccl.json one_rank_rccl
+      timeout 400 python bench.py --full --force-sharded --comm p2p --extras 0 --cpu-frames 0 --steps 240 > $O/bench_one_rank_p2p.json 2> $O/bench_one_rank_p2p.err; lastline $O/bench_one_rank_p2p.json one_rank_p2p
+      timeout 400 python bench.py --full --force-sharded --extract dealt --extras 0 --cpu-frames 0 --steps 240 > $O/bench_one_rank_rccl_dealt.json 2> $O/bench_one_rank_rccl_dealt.err; lastline $O/bench_one_rank_rccl_dealt.json one_rank_rccl_dealt;;
     env:*) export "${step#env:}"; case "${step#env:}" in SSF_*) export SSF_PRODUCT_VARIANT=${SSF_PRODUCT_VARIANT:-lab};; esac;    # (the switches live in the lab build)
             TAG="${TAG}_$(echo ${step#env:} | tr -c 'A-Za-z0-9=\n' '_')";;
     suite)
@@ -47,15 +47,15 @@ for step in "$@"; do
     quick)
       ( time timeout 1200 python -m pytest tests/test_parity_gpu.py -m gpu -x -q ) > $O/pytest_quick$TAG.log 2>&1; tail -n 3 $O/pytest_quick$TAG.log >> $O/summary.txt;;
     bench)
-      timeout 600 python bench.py > $O/bench_default$TAG.json 2> $O/bench_default$TAG.err; lastline $O/bench_default$TAG.json default$TAG
-      for r in a b; do timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --extras 0 --cpu-frames 0 > $O/bench_s20_$r$TAG.json 2> $O/bench_s20_$r$TAG.err; lastline $O/bench_s20_$r$TAG.json s20_$r$TAG; done;;
+      timeout 600 python bench.py --full > $O/bench_default$TAG.json 2> $O/bench_default$TAG.err; lastline $O/bench_default$TAG.json default$TAG
+      for r in a b; do timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --extras 0 --cpu-frames 0 > $O/bench_s20_$r$TAG.json 2> $O/bench_s20_$r$TAG.err; lastline $O/bench_s20_$r$TAG.json s20_$r$TAG; done;;
     fast)
-      timeout 300 python bench.py --extras 0 --cpu-frames 0 > $O/bench_fast$TAG.json 2> $O/bench_fast$TAG.err; lastline $O/bench_fast$TAG.json fast$TAG
-      timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --extras 0 --cpu-frames 0 > $O/bench_s20$TAG.json 2> $O/bench_s20$TAG.err; lastline $O/bench_s20$TAG.json s20$TAG;;
+      timeout 300 python bench.py --full --extras 0 --cpu-frames 0 > $O/bench_fast$TAG.json 2> $O/bench_fast$TAG.err; lastline $O/bench_fast$TAG.json fast$TAG
+      timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --extras 0 --cpu-frames 0 > $O/bench_s20$TAG.json 2> $O/bench_s20$TAG.err; lastline $O/bench_s20$TAG.json s20$TAG;;
     latency)
-      timeout 300 python bench.py --extras 0 --cpu-frames 0 --pipeline-depth 0 --extract-batch 1 --steps 200 > $O/bench_latency$TAG.json 2> $O/bench_latency$TAG.err; lastline $O/bench_latency$TAG.json latency$TAG;;
+      timeout 300 python bench.py --full --extras 0 --cpu-frames 0 --pipeline-depth 0 --extract-batch 1 --steps 200 > $O/bench_latency$TAG.json 2> $O/bench_latency$TAG.err; lastline $O/bench_latency$TAG.json latency$TAG;;
     config3|config4|config5)
-      timeout 400 python bench.py --config ${step#config} --extras 0 --cpu-frames 0 > $O/bench_$step$TAG.json 2> $O/bench_$step$TAG.err; lastline $O/bench_$step$TAG.json $step$TAG;;
+      timeout 400 python bench.py --full --config ${step#config} --extras 0 --cpu-frames 0 > $O/bench_$step$TAG.json 2> $O/bench_$step$TAG.err; lastline $O/bench_$step$TAG.json $step$TAG;;
     trace)
       ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace$TAG -o trace -- $PROF > $O/trace$TAG.log 2>&1 )
       DB=$(find $O/trace$TAG -name "*.db" | head -1)
