@@ -3,7 +3,8 @@
  * hot path: initialize / processFrame / getPose / getnbSupersurfels / getStamp / getModel / exportModel.
  * A node that owns a `supersurfel_fusion::SupersurfelFusion ssf;` member includes this header instead of the
  * reference's and links libssf_hip.so.  No OpenCV needed: processFrame takes raw pointers; the
- * cv::Mat overloads appear when <opencv2/core.hpp> has been included before this header.
+ * cv::Mat overloads appear when <opencv2/core.hpp> has been included before this header.  setInputFormat (ssf_input.h,
+ * libssf_hip.so only) lets processFrame take a sensor's frames as they come: BGR colour, uint16 depth counts.
  *
  * Sparse VO, MOD and loop closure stay with the caller; their outputs enter as `vo_pose` and `dynamic`.
  * Errors: the reference exits the process on a CUDA failure (cuda_error_check.h:30-66); this surface throws
@@ -14,6 +15,7 @@
 #include <string>
 #include <vector>
 #include "ssf.h"
+#include "ssf_input.h"
 
 /* The reference's pose / matrix types (core/include/supersurfel_fusion/matrix_types.h:26-42), at GLOBAL scope as there,
  * so that the nodes' lines compile as they stand:
@@ -188,7 +190,17 @@ public:
     void initialize(const ssf_config& c) {
         if (h_) { ssf_destroy(h_); h_ = nullptr; }
         if (ssf_create(&c, &h_) != SSF_OK) { h_ = nullptr; throw std::runtime_error(ssf_last_error(nullptr)); }
-        width_ = c.width; height_ = c.height;
+        width_ = c.width; height_ = c.height; depth_u16_ = false;
+    }
+    /* raw sensor frames (ssf_input.h; exported by libssf_hip.so only): after initialize(), which resets the handle to RGB8 +
+     * float metres.  color: SSF_COLOR_RGB8 / BGR8 / RGBA8 / BGRA8; depth: SSF_DEPTH_F32_METRES or SSF_DEPTH_U16_SCALED with
+     * depth_scale metres per count (the node's depthScale, 0.0002 for TUM).  Then
+     *     ssf.setInputFormat(SSF_COLOR_BGR8, SSF_DEPTH_U16_SCALED, depthScale);
+     *     ssf.processFrame(rgb_ptr, depth_u16_ptr);              // or the cv::Mat overload with CV_8UC3 (BGR) + CV_16UC1
+     * replace the node's cvtColor / convertTo. */
+    void setInputFormat(ssf_color_format color, ssf_depth_format depth, double depth_scale = 1.0) {
+        check(ssf_set_input_format(need(), color, depth, depth_scale));
+        depth_u16_ = depth == SSF_DEPTH_U16_SCALED;
     }
     bool isInitialized() const { return h_ != nullptr; }
 
@@ -197,13 +209,30 @@ public:
      * pose prior (supersurfel_fusion.cu:225-228; row-major R then t; nullptr = previous pose); dynamic: the MOD
      * mask, one byte per superpixel (motion_detection.cu:573-578; nullptr = none). */
     void processFrame(const uint8_t* rgb, const float* depth_m, const float* vo_pose = nullptr, const uint8_t* dynamic = nullptr) {
+        if (depth_u16_) throw std::logic_error("processFrame: the input format is uint16 depth; pass the counts as const uint16_t*");
         check(ssf_process_frame(need(), rgb, depth_m, vo_pose, dynamic, &last_));
+    }
+    /* the same with H x W uint16 depth counts: needs setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first; rgb in the
+     * colour format set there */
+    void processFrame(const uint8_t* rgb, const uint16_t* depth_counts, const float* vo_pose = nullptr, const uint8_t* dynamic = nullptr) {
+        if (!depth_u16_) throw std::logic_error("processFrame(uint16_t depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+        check(ssf_process_frame(need(), rgb, reinterpret_cast<const float*>(depth_counts), vo_pose, dynamic, &last_));
     }
     /* replay of a recorded sequence (SupersurfelFusionRGBDBenchmarkNode::run): host images of n frames, results in
      * order; with pipeline_depth / extract_batch > 0 / 1 the extract stage runs ahead (bit-identical results) */
     std::vector<ssf_frame_result> processSequence(const std::vector<const uint8_t*>& rgb, const std::vector<const float*>& depth_m) {
         if (rgb.size() != depth_m.size()) throw std::invalid_argument("processSequence: rgb / depth counts differ");
         std::vector<const void*> r(rgb.begin(), rgb.end()), d(depth_m.begin(), depth_m.end());
+        std::vector<ssf_frame_result> out(rgb.size());
+        if (depth_u16_) throw std::logic_error("processSequence: the input format is uint16 depth; pass the counts as const uint16_t*");
+        check(ssf_process_sequence(need(), r.data(), d.data(), (int)rgb.size(), 0, out.data()));
+        if (!out.empty()) last_ = out.back();
+        return out;
+    }
+    std::vector<ssf_frame_result> processSequence(const std::vector<const uint8_t*>& rgb, const std::vector<const uint16_t*>& depth_counts) {
+        if (rgb.size() != depth_counts.size()) throw std::invalid_argument("processSequence: rgb / depth counts differ");
+        if (!depth_u16_) throw std::logic_error("processSequence(uint16_t depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+        std::vector<const void*> r(rgb.begin(), rgb.end()), d(depth_counts.begin(), depth_counts.end());
         std::vector<ssf_frame_result> out(rgb.size());
         check(ssf_process_sequence(need(), r.data(), d.data(), (int)rgb.size(), 0, out.data()));
         if (!out.empty()) last_ = out.back();
@@ -214,6 +243,10 @@ public:
      * tests/test_cpp_wrapper.py (tests/cpp/cv_double.hpp) since OpenCV is not in the build image */
     void processFrame(const cv::Mat& rgb_h, const cv::Mat& depth_h, const float* vo_pose = nullptr, const uint8_t* dynamic = nullptr) {
         const cv::Mat rgb = rgb_h.isContinuous() ? rgb_h : rgb_h.clone(), d = depth_h.isContinuous() ? depth_h : depth_h.clone();
+#ifdef CV_16UC1
+        /* the sensor's CV_16UC1 depth (and its colour, BGR from cv_bridge) as they come, once setInputFormat has said so */
+        if (d.type() == CV_16UC1) { processFrame(rgb.ptr<uint8_t>(), d.ptr<uint16_t>(), vo_pose, dynamic); return; }
+#endif
         processFrame(rgb.ptr<uint8_t>(), d.ptr<float>(), vo_pose, dynamic);
     }
     void computeSuperpixelSegIm(cv::Mat& seg_im) {                     /* CV_8UC3, supersurfel_fusion.cu:635-640 */
@@ -321,6 +354,7 @@ private:
     Supersurfels model_view_, frame_view_;        /* always there (layout does not depend on the include order); bound by the thrust form's getModel() / getFrame() and by getModelView() / getFrameView() */
     int width_ = 0, height_ = 0;
     int pipeline_depth_ = 0, extract_batch_ = 1; bool depth_prefilter_ = true;
+    bool depth_u16_ = false;                       /* setInputFormat: depth arrives as uint16 counts */
 };
 
 }  /* inline namespace thrust_view / host_copy */

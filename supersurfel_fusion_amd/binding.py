@@ -70,6 +70,12 @@ ABI_SYMBOLS = [
     "ssf_sequence_times", "ssf_sequence_marks", "ssf_stream_copy_rate", "ssf_upload_stats", "ssf_pooled_streams", "ssf_waiter_matches", "ssf_waiter_match_repairs", "ssf_tuner_state", "ssf_submit_frame_tables", "ssf_comm_deal_extract",
 ]
 
+# the input-format entry points of include/ssf_input.h: exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
+INPUT_FORMAT_SYMBOLS = ["ssf_set_input_format", "ssf_get_input_format"]
+# ssf_color_format / ssf_depth_format: name -> (enum value, bytes per pixel)
+COLOR_FORMATS = {"rgb8": (0, 3), "bgr8": (1, 3), "rgba8": (2, 4), "bgra8": (3, 4)}
+DEPTH_FORMATS = {"f32": (0, 4), "u16": (1, 2)}
+
 SURFEL_FIELDS = (("positions", 3, np.float32), ("colors", 3, np.float32), ("stamps", 2, np.int32),
                  ("orientations", 9, np.float32), ("shapes", 6, np.float32),
                  ("dims", 2, np.float32), ("confidences", 1, np.float32))
@@ -154,6 +160,10 @@ class Library:
         L.ssf_stage_fuse_end.argtypes = [vp, vp, C.POINTER(SsfFrameResult)]
         L.ssf_stage_fuse_begin_device.argtypes = [vp, vp, vp, vp]
         L.ssf_stage_fuse_end_device.argtypes = [vp, vp, C.POINTER(SsfFrameResult)]
+        self.has_input_format = all(hasattr(L, nm) for nm in INPUT_FORMAT_SYMBOLS)
+        if self.has_input_format:
+            L.ssf_set_input_format.argtypes = [vp, C.c_int, C.c_int, C.c_double]
+            L.ssf_get_input_format.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]
 
     @property
     def backend(self):
@@ -210,6 +220,7 @@ class Fusion:
             raise SsfError("ssf_create failed (%d): %s" % (rc, library.lib.ssf_last_error(None).decode()))
         self.W, self.H = cfg.width, cfg.height
         self.S = self.counts()["n_superpixels"]
+        self.color_format, self.depth_format = "rgb8", "f32"      # set_input_format
         self._held = []          # host buffers of submitted frames: they must outlive the asynchronous copy (ssf.h)
 
     def close(self):
@@ -227,11 +238,58 @@ class Fusion:
         if rc != 0:
             raise SsfError("%s failed (%d): %s" % (what, rc, self.L.lib.ssf_last_error(self.h).decode()))
 
+    # ---- input format (include/ssf_input.h) ---------------------------------------------------
+    def set_input_format(self, color="rgb8", depth="f32", depth_scale=1.0):
+        """How every frame entry point reads its images from now on: colour 'rgb8' | 'bgr8' | 'rgba8' | 'bgra8' (H x W x 3 / 4
+        uint8, alpha ignored), depth 'f32' (H x W float32 metres) | 'u16' (H x W uint16 counts, metres = count * depth_scale
+        evaluated in double and rounded once to float32).  Not while frames are pending."""
+        if not self.L.has_input_format:
+            raise SsfError("%s does not export ssf_set_input_format: it reads RGB8 colour and float32 metres only" % self.L.path)
+        if color not in COLOR_FORMATS or depth not in DEPTH_FORMATS:
+            raise SsfError("unknown input format %r / %r (colour: %s; depth: %s)" % (color, depth, ", ".join(COLOR_FORMATS),
+                                                                                   ", ".join(DEPTH_FORMATS)))
+        self._ck(self.L.lib.ssf_set_input_format(self.h, COLOR_FORMATS[color][0], DEPTH_FORMATS[depth][0], float(depth_scale)),
+                 "ssf_set_input_format")
+        self.color_format, self.depth_format = color, depth
+
+    def input_format(self):
+        """dict(color, depth, depth_scale) as the library reports it"""
+        if not self.L.has_input_format:
+            raise SsfError("%s does not export ssf_get_input_format" % self.L.path)
+        c, d, sc = C.c_int(), C.c_int(), C.c_double()
+        self._ck(self.L.lib.ssf_get_input_format(self.h, C.byref(c), C.byref(d), C.byref(sc)), "ssf_get_input_format")
+        return dict(color={v[0]: k for k, v in COLOR_FORMATS.items()}[c.value],
+                    depth={v[0]: k for k, v in DEPTH_FORMATS.items()}[d.value], depth_scale=sc.value)
+
+    def _frame(self, rgb, depth):
+        """contiguous host arrays of one frame in the handle's input format.  The default format (RGB8 + float32 metres)
+        converts what it is given, as it always has; any other format refuses a dtype or shape that does not match it
+        (a cast would turn depth counts into 'metres')."""
+        if (self.color_format, self.depth_format) == ("rgb8", "f32"):
+            rgb, depth = np.ascontiguousarray(rgb, np.uint8), np.ascontiguousarray(depth, np.float32)
+            assert rgb.shape == (self.H, self.W, 3) and depth.shape == (self.H, self.W)
+            return rgb, depth
+        return self._color_array(rgb), self._depth_array(depth)
+
+    def _color_array(self, rgb):
+        ch = COLOR_FORMATS[self.color_format][1]
+        rgb = np.asarray(rgb)
+        if rgb.dtype != np.uint8 or rgb.shape != (self.H, self.W, ch):
+            raise SsfError("colour frame must be uint8 %dx%dx%d for input format %s, got %s %s" % (
+                self.H, self.W, ch, self.color_format, rgb.dtype, rgb.shape))
+        return np.ascontiguousarray(rgb)
+
+    def _depth_array(self, depth):
+        dt = np.uint16 if self.depth_format == "u16" else np.float32
+        depth = np.asarray(depth)
+        if depth.dtype != dt or depth.shape != (self.H, self.W):
+            raise SsfError("depth frame must be %s %dx%d for input format %s, got %s %s" % (
+                np.dtype(dt).name, self.H, self.W, self.depth_format, depth.dtype, depth.shape))
+        return np.ascontiguousarray(depth)
+
     # ---- whole frame -------------------------------------------------------------------------
     def process_frame(self, rgb, depth, prior_pose=None, dynamic_mask=None):
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        depth = np.ascontiguousarray(depth, np.float32)
-        assert rgb.shape == (self.H, self.W, 3) and depth.shape == (self.H, self.W)
+        rgb, depth = self._frame(rgb, depth)
         prior = None if prior_pose is None else np.ascontiguousarray(prior_pose, np.float32)
         mask = None if dynamic_mask is None else np.ascontiguousarray(dynamic_mask, np.uint8)
         res = SsfFrameResult()
@@ -254,9 +312,7 @@ class Fusion:
         if on_device:
             rp, dp = C.c_void_p(rgb), C.c_void_p(depth)
         else:
-            rgb = np.ascontiguousarray(rgb, np.uint8)
-            depth = np.ascontiguousarray(depth, np.float32)
-            assert rgb.shape == (self.H, self.W, 3) and depth.shape == (self.H, self.W)
+            rgb, depth = self._frame(rgb, depth)
             rp, dp = _ptr(rgb), _ptr(depth)
         mask = None if dynamic_mask is None else np.ascontiguousarray(dynamic_mask, np.uint8)
         self._ck(self.L.lib.ssf_submit_frame(self.h, rp, dp, 1 if on_device else 0, _ptr(mask)), "ssf_submit_frame")
@@ -287,6 +343,12 @@ class Fusion:
         (device pointers when on_device, else addresses of contiguous host arrays).  Returns a list of result dicts."""
         return [r.as_dict() for r in self.process_prepared(self.prepare_sequence(rgb_ptrs, depth_ptrs), on_device)]
 
+    def host_sequence(self, rgbs, depths):
+        """Host frames for prepare_sequence / process_sequence(on_device=False), checked against the input format like
+        process_frame's: returns (rgb_ptrs, depth_ptrs, keep) -- `keep` holds the arrays and must outlive the call."""
+        keep = [self._frame(r, d) for r, d in zip(rgbs, depths)]
+        return [a.ctypes.data for a, _ in keep], [b.ctypes.data for _, b in keep], keep
+
     def process_submitted(self, prior_pose=None):
         """ICP + association + fusion of the oldest submitted frame; returns its SsfFrameResult."""
         prior = None if prior_pose is None else np.ascontiguousarray(prior_pose, np.float32)
@@ -309,9 +371,12 @@ class Fusion:
     def stage_extract(self, rgb, depth, dynamic_mask=None, on_device=False):
         if on_device:
             rp, dp = C.c_void_p(rgb), C.c_void_p(depth)
-        else:
+        elif (self.color_format, self.depth_format) == ("rgb8", "f32"):
             rgb = np.ascontiguousarray(rgb, np.uint8)
             depth = np.ascontiguousarray(depth, np.float32)
+            rp, dp = _ptr(rgb), _ptr(depth)
+        else:
+            rgb, depth = self._frame(rgb, depth)
             rp, dp = _ptr(rgb), _ptr(depth)
         mask = None if dynamic_mask is None else np.ascontiguousarray(dynamic_mask, np.uint8)
         self._ck(self.L.lib.ssf_stage_extract(self.h, rp, dp, 1 if on_device else 0, _ptr(mask)), "ssf_stage_extract")
@@ -605,8 +670,9 @@ class Fusion:
         return rc
 
     def bilateral_filter(self, depth):
-        depth = np.ascontiguousarray(depth, np.float32)
-        out = np.zeros_like(depth)
+        """the depth pre-filter alone: input in the handle's depth format, output H x W float32 metres"""
+        depth = np.ascontiguousarray(depth, np.float32) if self.depth_format == "f32" else self._depth_array(depth)
+        out = np.zeros(depth.shape, np.float32)
         self._ck(self.L.lib.ssf_bilateral_filter(self.h, _ptr(depth), _ptr(out), 0), "ssf_bilateral_filter")
         return out
 

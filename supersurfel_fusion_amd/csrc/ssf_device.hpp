@@ -22,6 +22,7 @@
 #include <cstddef>
 #include "ssf_math.hpp"
 #include "../../include/ssf.h"
+#include "../../include/ssf_input.h"
 
 // SSF_EXPERIMENTS: the laboratory build (csrc/variants/lab/libssf_hip.so, `make lab`): the measurement arms and environment
 // switches behind DESIGN.md's A/B tables.  The PRODUCT library is built without it: it reads no environment variable and
@@ -168,10 +169,13 @@ SSF_HD SurfelSoA batch_slot(SurfelSoA s, size_t o) {
     s.dims = slab_shift(s.dims, o); s.conf = slab_shift(s.conf, o);
     return s;
 }
-// caller-side inputs of the frames of one batch
+// caller-side inputs of the frames of one batch, in the format of the buffers they point to (ssf_input.h): colour
+// SSF_COLOR_* (3 or 4 bytes per pixel), depth SSF_DEPTH_* (float metres, or uint16 counts x depth_scale)
 struct BatchIn {
     const uint8_t* rgb[SSF_MAX_BATCH];
-    const float* depth[SSF_MAX_BATCH];
+    const void* depth[SSF_MAX_BATCH];
+    int color_format, depth_format;
+    double depth_scale;
 };
 template <typename T> SSF_HD T batch_pick(const T* arr, int b) {     // uniform select chain (no dynamic kernarg indexing)
     T v = arr[0];
@@ -236,8 +240,9 @@ void launch_render_moments(hipStream_t st, const SegParams& p, const Cam& cam, F
 void launch_finalize_surfels(hipStream_t st, const SegParams& p, FrameMaps& m, int nb, SurfelSoA frame, float zmin,
                              float zmax, int stamp0, const uint8_t* dynamic_mask, unsigned mask_bits,
                              unsigned long long* best, uint8_t* matched);
-void launch_bilateral(hipStream_t st, const float* in, float* out, int W, int H, float sigma_color, float sigma_space);
-// the nb frames of a batch in ONE launch: frame b from in.depth[b] to out0 + b * slab bytes
+void launch_bilateral(hipStream_t st, const void* in, int depth_format, double depth_scale, float* out, int W, int H, float sigma_color,
+                      float sigma_space);
+// the nb frames of a batch in ONE launch: frame b from in.depth[b] (in.depth_format) to out0 + b * slab bytes (float metres)
 void launch_bilateral_batch(hipStream_t st, const BatchIn& in, float* out0, size_t slab, int nb, int W, int H, float sigma_color, float sigma_space);
 void launch_boundary_map(hipStream_t st, const SegParams& p, const int32_t* label, int32_t* out);
 void launch_preview(hipStream_t st, int W, int H, const int32_t* label, const uint32_t* rgba, uint8_t* out /* 3P */);

@@ -30,13 +30,32 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ void atomic_add_i64(long long* p, long long v) {
     atomicAdd(reinterpret_cast<unsigned long long*>(p), static_cast<unsigned long long>(v));
 }
+// ---- input formats (ssf_input.h) -------------------------------------------------------------------
+// Colour of pixel q as r | g << 8 | b << 16: the 3-byte layouts byte by byte, the 4-byte ones as one dword (alpha dropped).
+template <int CF> __device__ __forceinline__ uint32_t load_rgb(const uint8_t* __restrict__ p, size_t q) {
+    if (CF == SSF_COLOR_RGBA8 || CF == SSF_COLOR_BGRA8) {
+        const uint32_t v = reinterpret_cast<const uint32_t*>(p)[q];
+        return CF == SSF_COLOR_RGBA8 ? (v & 0xFFFFFFu) : (((v & 0xFFu) << 16) | (v & 0xFF00u) | ((v >> 16) & 0xFFu));
+    }
+    const uint32_t c0 = p[3 * q], c1 = p[3 * q + 1], c2 = p[3 * q + 2];
+    return CF == SSF_COLOR_BGR8 ? (c2 | (c1 << 8) | (c0 << 16)) : (c0 | (c1 << 8) | (c2 << 16));
+}
+// Depth of pixel q in metres: the float as stored, or the uint16 count times the scale evaluated in double and rounded ONCE to
+// float (the node's convertTo(CV_32FC1, depthScale), replay.convert_depth): the very floats the default format would carry.
+template <int DF> __device__ __forceinline__ float load_depth(const void* __restrict__ p, size_t q, double scale) {
+    if (DF == SSF_DEPTH_U16_SCALED) return (float)((double)reinterpret_cast<const uint16_t*>(p)[q] * scale);
+    return reinterpret_cast<const float*>(p)[q];
+}
+
 // ---- ingest ------------------------------------------------------------------------------------
 // One workgroup per grid cell: RGB->RGBA, disparity = 1/depth, label = cell id, and the cell's
 // initial sums by an in-block reduction (depth2disp32F_kernel TPS_RGBD_kernels.cu:278-296,
-// initSuperpixelsRGBD_kernel :61-110).
+// initSuperpixelsRGBD_kernel :61-110).  CF / DF: the formats of the buffers this launch reads (ssf_input.h) -- with the
+// pre-filter on, depth is its float output whatever the handle's input format.
+template <int CF, int DF>
 __global__ __launch_bounds__(256) void k_ingest(SegParams p, BatchIn in, FrameMaps m, uint32_t epoch0) {
     const uint8_t* __restrict__ rgb = batch_pick(in.rgb, (int)blockIdx.y);
-    const float* __restrict__ depth = batch_pick(in.depth, (int)blockIdx.y);
+    const void* __restrict__ depth = batch_pick(in.depth, (int)blockIdx.y);
     m = batch_slot(m, blockIdx.y);
     const int cell = blockIdx.x;
     if (cell == 0 && threadIdx.x == 0) m.epoch[0] = epoch0 + blockIdx.y;
@@ -49,9 +68,10 @@ __global__ __launch_bounds__(256) void k_ingest(SegParams p, BatchIn in, FrameMa
     for (int i = threadIdx.x; i < w * h; i += blockDim.x) {
         const int x = cx0 + i % w, y = cy0 + i / w;
         const size_t q = (size_t)y * p.W + x;
-        const uint32_t r = rgb[3 * q], g = rgb[3 * q + 1], b = rgb[3 * q + 2];
-        m.rgba[q] = r | (g << 8) | (b << 16) | (255u << 24);
-        m.disp[q] = 1.f / depth[q];
+        const uint32_t c = load_rgb<CF>(rgb, q);
+        const uint32_t r = c & 0xFFu, g = (c >> 8) & 0xFFu, b = c >> 16;
+        m.rgba[q] = c | (255u << 24);
+        m.disp[q] = 1.f / load_depth<DF>(depth, q, in.depth_scale);
         m.label[q] = cell;
         m.inlier[q] = 0;
         sx += x; sy += y; sr += (int)r; sg += (int)g; sb += (int)b; n += 1;
@@ -1409,9 +1429,13 @@ __device__ __forceinline__ int reflect101(int i, int n) {
 }
 // (every frame of an extract batch in one launch: frame = blockIdx.z, input = the caller's / the upload ring's buffer of that
 // frame, output = out0 + frame * slab bytes)
+// DF: the input's depth format, converted to metres where a pixel is staged (once per staged pixel, not per tap; only the
+// unstaged path of radii above BIL_RMAX converts per tap)
+template <int DF>
 __global__ __launch_bounds__(256) void k_bilateral(BatchIn bin, float* __restrict__ out0, size_t slab, int W, int H,
                                                    int radius, float ss, float sc) {
-    const float* __restrict__ in = batch_pick(bin.depth, (int)blockIdx.z);
+    const void* __restrict__ in = batch_pick(bin.depth, (int)blockIdx.z);
+    const double scale = bin.depth_scale;
     float* __restrict__ out = slab_shift(out0, (size_t)blockIdx.z * slab);
     __shared__ float tile[(BIL_TILE + 2 * BIL_RMAX) * (BIL_TILE + 2 * BIL_RMAX)];
     __shared__ int s_ext[2 * BIL_RMAX + 1];            // half-width of the circular support in row dy
@@ -1421,7 +1445,7 @@ __global__ __launch_bounds__(256) void k_bilateral(BatchIn bin, float* __restric
     if (staged) {
         for (int i = threadIdx.x; i < tw * tw; i += blockDim.x) {
             const int gx = reflect101(X0 - radius + i % tw, W), gy = reflect101(Y0 - radius + i / tw, H);
-            tile[i] = in[(size_t)gy * W + gx];
+            tile[i] = load_depth<DF>(in, (size_t)gy * W + gx, scale);
         }
         if ((int)threadIdx.x <= 2 * radius) {
             const int dy = (int)threadIdx.x - radius;
@@ -1453,12 +1477,12 @@ __global__ __launch_bounds__(256) void k_bilateral(BatchIn bin, float* __restric
             }
         }
     } else {
-        const float center = in[(size_t)y * W + x];
+        const float center = load_depth<DF>(in, (size_t)y * W + x, scale);
         for (int dy = -radius; dy <= radius; dy++)
             for (int dx = -radius; dx <= radius; dx++) {
                 const float space2 = (float)(dx * dx + dy * dy);
                 if (space2 > r2) continue;
-                const float v = in[(size_t)reflect101(y + dy, H) * W + reflect101(x + dx, W)];
+                const float v = load_depth<DF>(in, (size_t)reflect101(y + dy, H) * W + reflect101(x + dx, W), scale);
                 const float dv = fabsf(v - center);
                 const float w = exp_neg_spec(space2 * ss + (dv * dv) * sc);
                 sum1 = sum1 + w * v;
@@ -1549,16 +1573,17 @@ __device__ __forceinline__ void bilateral_row7(const float* __restrict__ row, fl
         }
     }
 }
-template <int WAVES>
+// DF: the input's depth format, converted to metres in the tile load (once per staged pixel; the tap loops see floats)
+template <int WAVES, int DF>
 __global__ __launch_bounds__(256, WAVES) void k_bilateral_r7(BatchIn bin, float* __restrict__ out0, size_t slab, int W, int H, float ss, float sc) {
-    const float* __restrict__ in = batch_pick(bin.depth, (int)blockIdx.z);
+    const void* __restrict__ in = batch_pick(bin.depth, (int)blockIdx.z);
     float* __restrict__ out = slab_shift(out0, (size_t)blockIdx.z * slab);
     constexpr int R = 7, BW = BIL_TILE + 2 * R;
     __shared__ float tile[BW * BW];
     const int X0 = blockIdx.x * BIL_TILE, Y0 = blockIdx.y * BIL_TILE;
     for (int i = threadIdx.x; i < BW * BW; i += blockDim.x) {
         const int gx = reflect101(X0 - R + i % BW, W), gy = reflect101(Y0 - R + i / BW, H);
-        tile[i] = in[(size_t)gy * W + gx];
+        tile[i] = load_depth<DF>(in, (size_t)gy * W + gx, bin.depth_scale);
     }
     __syncthreads();
     const int lx = threadIdx.x % BIL_TILE, ly = threadIdx.x / BIL_TILE;
@@ -1577,8 +1602,8 @@ __global__ __launch_bounds__(256, WAVES) void k_bilateral_r7(BatchIn bin, float*
     bilateral_row7<7>(c + 7 * BW, center, ss, sc, sum1, sum2);
     out[(size_t)y * W + x] = sum1 / sum2;
 }
-void launch_bilateral_batch(hipStream_t st, const BatchIn& in, float* out0, size_t slab, int nb, int W, int H, float sigma_color, float sigma_space) {
-    ScopedKernel sk("bilateral_prefilter", st);
+template <int DF>
+static void launch_bilateral_df(hipStream_t st, const BatchIn& in, float* out0, size_t slab, int nb, int W, int H, float sigma_color, float sigma_space) {
     int radius = (int)lrint((double)sigma_space * 1.5);
     if (radius < 1) radius = 1;
     const float ss = -0.5f / (sigma_space * sigma_space), sc = -0.5f / (sigma_color * sigma_color);
@@ -1587,24 +1612,40 @@ void launch_bilateral_batch(hipStream_t st, const BatchIn& in, float* out0, size
     if (radius == 7 && !generic_only) {
 #ifdef SSF_EXPERIMENTS
         static const int waves = SSF_ENV_INT("BIL_WAVES", 2);       // (3 and 4 waves per SIMD spill: measured slower)
-        if (waves == 3) { hipLaunchKernelGGL(k_bilateral_r7<3>, grid, dim3(256), 0, st, in, out0, slab, W, H, ss, sc); return; }
-        if (waves == 4) { hipLaunchKernelGGL(k_bilateral_r7<4>, grid, dim3(256), 0, st, in, out0, slab, W, H, ss, sc); return; }
+        if (waves == 3) { hipLaunchKernelGGL((k_bilateral_r7<3, DF>), grid, dim3(256), 0, st, in, out0, slab, W, H, ss, sc); return; }
+        if (waves == 4) { hipLaunchKernelGGL((k_bilateral_r7<4, DF>), grid, dim3(256), 0, st, in, out0, slab, W, H, ss, sc); return; }
 #endif
-        hipLaunchKernelGGL(k_bilateral_r7<2>, grid, dim3(256), 0, st, in, out0, slab, W, H, ss, sc);
+        hipLaunchKernelGGL((k_bilateral_r7<2, DF>), grid, dim3(256), 0, st, in, out0, slab, W, H, ss, sc);
         return;
     }
-    hipLaunchKernelGGL(k_bilateral, grid, dim3(256), 0, st, in, out0, slab, W, H, radius, ss, sc);
+    hipLaunchKernelGGL(k_bilateral<DF>, grid, dim3(256), 0, st, in, out0, slab, W, H, radius, ss, sc);
 }
-void launch_bilateral(hipStream_t st, const float* in, float* out, int W, int H, float sigma_color, float sigma_space) {
-    BatchIn b{}; b.depth[0] = in;
+void launch_bilateral_batch(hipStream_t st, const BatchIn& in, float* out0, size_t slab, int nb, int W, int H, float sigma_color, float sigma_space) {
+    ScopedKernel sk("bilateral_prefilter", st);
+    if (in.depth_format == SSF_DEPTH_U16_SCALED) launch_bilateral_df<SSF_DEPTH_U16_SCALED>(st, in, out0, slab, nb, W, H, sigma_color, sigma_space);
+    else launch_bilateral_df<SSF_DEPTH_F32_METRES>(st, in, out0, slab, nb, W, H, sigma_color, sigma_space);
+}
+void launch_bilateral(hipStream_t st, const void* in, int depth_format, double depth_scale, float* out, int W, int H, float sigma_color,
+                      float sigma_space) {
+    BatchIn b{}; b.depth[0] = in; b.depth_format = depth_format; b.depth_scale = depth_scale;
     launch_bilateral_batch(st, b, out, 0, 1, W, H, sigma_color, sigma_space);
 }
 
 // ---- launchers -----------------------------------------------------------------------------------
 
+template <int CF>
+static void launch_ingest_cf(hipStream_t st, const SegParams& p, const BatchIn& in, FrameMaps& m, int nb, uint32_t epoch0) {
+    if (in.depth_format == SSF_DEPTH_U16_SCALED) hipLaunchKernelGGL((k_ingest<CF, SSF_DEPTH_U16_SCALED>), dim3(p.S, nb), dim3(256), 0, st, p, in, m, epoch0);
+    else hipLaunchKernelGGL((k_ingest<CF, SSF_DEPTH_F32_METRES>), dim3(p.S, nb), dim3(256), 0, st, p, in, m, epoch0);
+}
 void launch_ingest(hipStream_t st, const SegParams& p, const BatchIn& in, FrameMaps& m, int nb, uint32_t epoch0) {
     ScopedKernel sk("ingest", st);
-    hipLaunchKernelGGL(k_ingest, dim3(p.S, nb), dim3(256), 0, st, p, in, m, epoch0);
+    switch (in.color_format) {
+    case SSF_COLOR_BGR8: launch_ingest_cf<SSF_COLOR_BGR8>(st, p, in, m, nb, epoch0); break;
+    case SSF_COLOR_RGBA8: launch_ingest_cf<SSF_COLOR_RGBA8>(st, p, in, m, nb, epoch0); break;
+    case SSF_COLOR_BGRA8: launch_ingest_cf<SSF_COLOR_BGRA8>(st, p, in, m, nb, epoch0); break;
+    default: launch_ingest_cf<SSF_COLOR_RGB8>(st, p, in, m, nb, epoch0); break;
+    }
 }
 // pass pixels per thread (tile width / 32) for a launch over nb frames; SSF_PASS_NPX = 1 / 2 forces it (measurement)
 int pass_tile_npx(int nb) {

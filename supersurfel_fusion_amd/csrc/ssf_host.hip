@@ -561,6 +561,9 @@ struct ssf_handle {
     int seq_batches = 0;                      // batches launched by the running ssf_process_sequence (see seq_batch_size)
     double us_wait_upload = 0.0;                          // the submitting thread's wait for uploads (ssf_upload_stats)
     Uploader* up = nullptr; bool seq_upload = false;   // host frames of a sequence are copied ahead by a worker thread
+    // the format every frame entry point reads its images in (ssf_set_input_format, ssf_input.h); the buffers that hold frames
+    // on the device (batch input slabs, upload ring, pre-filter input) are sized for the largest one, so a change allocates nothing
+    int in_color = SSF_COLOR_RGB8, in_depth = SSF_DEPTH_F32_METRES; double in_scale = 1.0;
     // multi-GPU: RCCL communicator over the ranks of cfg.nranks (ssf_comm_attach); the shard sizes of all ranks
     // are all-gathered at the end of every frame and read lazily at the start of the next one
     ncclComm_t comm = nullptr; int* d_all5 = nullptr;
@@ -824,9 +827,11 @@ static int launch_batch(ssf_handle* h, ExtractCtx& c) {
     const bool mine = !dealt || c.mine;
     int extract_rc = SSF_OK;
     if (mine) {
+        c.in.color_format = h->in_color; c.in.depth_format = h->in_depth; c.in.depth_scale = h->in_scale;
         if (h->cfg.depth_prefilter) {                                      // supersurfel_fusion.cu:180 -- the batch's frames in one launch
             launch_bilateral_batch(st, c.in, c.d_depth_filt, c.maps.slab, nb, h->cfg.width, h->cfg.height, h->cfg.prefilter_sigma_color, h->cfg.prefilter_sigma_space);
             for (int b = 0; b < nb; b++) c.in.depth[b] = slab_shift(c.d_depth_filt, (size_t)b * c.maps.slab);
+            c.in.depth_format = SSF_DEPTH_F32_METRES;                      // (ingest reads the filter's float output, the raw colour)
         }
         launch_ingest(st, h->seg, c.in, c.maps, nb, c.epoch0);
         extract_rc = run_segmentation(h, c);
@@ -867,10 +872,22 @@ static int launch_batch(ssf_handle* h, ExtractCtx& c) {
     }
     return SSF_OK;
 }
+// bytes per pixel of the handle's input format (ssf_input.h), and whether device frames are aligned for it
+static size_t color_bpp(const ssf_handle* h) { return (h->in_color == SSF_COLOR_RGBA8 || h->in_color == SSF_COLOR_BGRA8) ? 4 : 3; }
+static size_t depth_bpp(const ssf_handle* h) { return h->in_depth == SSF_DEPTH_U16_SCALED ? 2 : 4; }
+static bool device_input_aligned(ssf_handle* h, const void* rgb, const void* depth) {
+    const size_t ca = color_bpp(h) == 4 ? 4 : 1, da = depth_bpp(h);
+    if ((rgb && (uintptr_t)rgb % ca) || (depth && (uintptr_t)depth % da)) {
+        h->err = "device frame pointer not aligned for the input format (4-byte colour: 4 bytes; depth: its element size)";
+        return false;
+    }
+    return true;
+}
 // Add one frame to the open batch; the batch is launched when it is full (or when its first frame is needed).
 static int submit_extract(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask) {
     ExtractCtx& c = h->ctx[h->open_ctx];
     if (c.launched) { h->err = "extract pipeline is full: process a submitted frame first"; return SSF_ERR_STATE; }
+    if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
     const int b = c.count;
     if (b == 0) {
         c.stamp0 = h->stamp + h->stamp_bias + (int)h->pending.size(); c.mask_bits = 0; c.epoch0 = h->extract_ordinal;
@@ -879,11 +896,11 @@ static int submit_extract(ssf_handle* h, const void* rgb, const void* depth, int
     }
     h->extract_ordinal++;
     const size_t P = (size_t)h->cfg.width * h->cfg.height, off = (size_t)b * c.maps.slab;
-    c.in.rgb[b] = (const uint8_t*)rgb; c.in.depth[b] = (const float*)depth;
+    c.in.rgb[b] = (const uint8_t*)rgb; c.in.depth[b] = depth;
     if (!on_device && c.mine) {            // (a batch another rank extracts: its images are never looked at here)
         uint8_t* drgb = slab_shift(c.d_rgb_in, off); float* ddep = slab_shift(c.d_depth_in, off);
-        HCK(hipMemcpyAsync(drgb, rgb, 3 * P, hipMemcpyHostToDevice, c.stream));
-        HCK(hipMemcpyAsync(ddep, depth, 4 * P, hipMemcpyHostToDevice, c.stream));
+        HCK(hipMemcpyAsync(drgb, rgb, color_bpp(h) * P, hipMemcpyHostToDevice, c.stream));
+        HCK(hipMemcpyAsync(ddep, depth, depth_bpp(h) * P, hipMemcpyHostToDevice, c.stream));
         c.in.rgb[b] = drgb; c.in.depth[b] = ddep;
     }
     if (mask && c.mine) { HCK(hipMemcpyAsync(slab_shift(c.d_mask, off), mask, h->S, hipMemcpyHostToDevice, c.stream)); c.mask_bits |= 1u << b; }
@@ -1846,7 +1863,7 @@ int ssf_create(const ssf_config* cfg, ssf_handle** out) {
         SurfelSoA& f = c.frame;
         take(f.pos, 3 * S); take(f.col, 3 * S); take(f.lab, 3 * S); take(f.stamps, 2 * S); take(f.r0, 3 * S); take(f.r1, 3 * S);
         take(f.r2, 3 * S); take(f.shape, 6 * S); take(f.dims, 2 * S); take(f.conf, S);
-        take(c.d_best, S); take(c.d_matched, S); take(c.d_rgb_in, 3 * P); take(c.d_depth_in, P); take(c.d_depth_filt, P); take(c.d_mask, S);
+        take(c.d_best, S); take(c.d_matched, S); take(c.d_rgb_in, 4 * P); take(c.d_depth_in, P); take(c.d_depth_filt, P); take(c.d_mask, S);
         take(c.d_wire, 26 * S);
         return (off + 255) & ~(size_t)255;
     };
@@ -1954,12 +1971,14 @@ int ssf_process_frame(ssf_handle* h, const uint8_t* rgb, const float* depth, con
 }
 int ssf_process_frame_device(ssf_handle* h, const void* rgb, const void* depth, const float* prior, const uint8_t* mask, ssf_frame_result* out) {
     if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
+    if (!device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
     return process_frame_impl(h, rgb, depth, 1, prior, mask, out);
 }
 
 // pipelined form: extract of future frames runs ahead on its own stream(s)
 int ssf_submit_frame(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask) {
     if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
+    if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
     TimerScope ts(h);
     const double t0 = now_us();
     int rc = submit_extract(h, rgb, depth, on_device, mask);
@@ -1983,6 +2002,7 @@ int ssf_process_sequence(ssf_handle* h, const void* const* rgb, const void* cons
     if (!h || !rgb || !depth || n < 0) return SSF_ERR_INVALID_ARG;
     if (!h->pending.empty()) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
     for (int i = 0; i < n; i++) if (!rgb[i] || !depth[i]) return SSF_ERR_INVALID_ARG;
+    if (on_device) for (int i = 0; i < n; i++) if (!device_input_aligned(h, rgb[i], depth[i])) return SSF_ERR_INVALID_ARG;
     int rc = SSF_OK;
     // an empty pipeline: the sequence's first (small) batch goes to context 0, whose stream outranks the other contexts'
     // (ssf_create): the batch the track chain is waiting for is not slowed down by the larger ones launched right behind it
@@ -2008,18 +2028,18 @@ int ssf_process_sequence(ssf_handle* h, const void* const* rgb, const void* cons
             // SSF_UPLOAD_RING_BYTES of device buffers (and the same again page-locked), never fewer than the window the submitting
             // thread can run ahead by + 2 (below that the workers could not keep up at all).  INTEGRATION.md section 2b has the footprint.
             const int window = ((int)h->ctx.size() + 1) * h->batch + 2;
-            const int by_bytes = (int)(SSF_UPLOAD_RING_BYTES / (7 * P));
+            // (slots sized for the largest input format, ssf_input.h: 4 colour bytes per pixel; a format change reallocates nothing)
+            const int by_bytes = (int)(SSF_UPLOAD_RING_BYTES / (8 * P));
             u->ring = std::max(window, std::min(((int)h->ctx.size() + 3) * h->batch + 2, by_bytes));
-            u->rgb_bytes = 3 * P; u->depth_bytes = 4 * P;
             u->device = h->cfg.device_id;
             bool ok = true;
             u->d_rgb.assign(u->ring, nullptr); u->d_depth.assign(u->ring, nullptr);
-            for (int i = 0; i < u->ring && ok; i++) ok = dalloc(h, &u->d_rgb[i], 3 * P) && dalloc(h, &u->d_depth[i], P);
+            for (int i = 0; i < u->ring && ok; i++) ok = dalloc(h, &u->d_rgb[i], 4 * P) && dalloc(h, &u->d_depth[i], P);
             if (ok && !SSF_ENV_SET("UPLOAD_PAGEABLE")) {     // page-locked staging (optional: without it the copies go through the runtime's)
                 u->p_rgb.assign(u->ring, nullptr); u->p_depth.assign(u->ring, nullptr);
                 bool pin = true;
                 for (int i = 0; i < u->ring && pin; i++)
-                    pin = hipHostMalloc((void**)&u->p_rgb[i], 3 * P, hipHostMallocDefault) == hipSuccess &&
+                    pin = hipHostMalloc((void**)&u->p_rgb[i], 4 * P, hipHostMallocDefault) == hipSuccess &&
                           hipHostMalloc((void**)&u->p_depth[i], 4 * P, hipHostMallocDefault) == hipSuccess;
                 if (!pin) { for (auto q : u->p_rgb) if (q) (void)hipHostFree(q); for (auto q : u->p_depth) if (q) (void)hipHostFree(q); u->p_rgb.clear(); u->p_depth.clear(); (void)hipGetLastError(); }
             }
@@ -2030,6 +2050,7 @@ int ssf_process_sequence(ssf_handle* h, const void* const* rgb, const void* cons
         }
         Uploader& u = *h->up;
         u.n = n; u.rgb = rgb; u.depth = depth; u.ctx0 = h->open_ctx;
+        u.rgb_bytes = color_bpp(h) * P; u.depth_bytes = depth_bpp(h) * P;
         u.processed.store(0); u.failed.store(0); u.stop.store(0);
         u.start();
     }
@@ -2336,8 +2357,29 @@ int ssf_get_global_counts(ssf_handle* h, int64_t* out5) {
     return SSF_OK;
 }
 
+int ssf_set_input_format(ssf_handle* h, int color, int depth, double depth_scale) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    if (color < SSF_COLOR_RGB8 || color > SSF_COLOR_BGRA8 || (depth != SSF_DEPTH_F32_METRES && depth != SSF_DEPTH_U16_SCALED)) {
+        h->err = "ssf_set_input_format: unknown colour or depth format"; return SSF_ERR_INVALID_ARG;
+    }
+    if (depth == SSF_DEPTH_U16_SCALED && !(std::isfinite(depth_scale) && depth_scale > 0.0)) {
+        h->err = "ssf_set_input_format: depth_scale must be finite and > 0"; return SSF_ERR_INVALID_ARG;
+    }
+    if (!h->pending.empty() || h->seq_n > 0) { h->err = "ssf_set_input_format: frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
+    h->in_color = color; h->in_depth = depth; h->in_scale = depth == SSF_DEPTH_U16_SCALED ? depth_scale : 1.0;
+    return SSF_OK;
+}
+int ssf_get_input_format(const ssf_handle* h, int* color, int* depth, double* depth_scale) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    if (color) *color = h->in_color;
+    if (depth) *depth = h->in_depth;
+    if (depth_scale) *depth_scale = h->in_scale;
+    return SSF_OK;
+}
+
 int ssf_stage_extract(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask) {
     if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
+    if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
     TimerScope ts(h);
     return do_extract(h, rgb, depth, on_device, mask);
 }
@@ -2736,9 +2778,11 @@ int ssf_rehome_end(ssf_handle* h, const int32_t* table, int n_rec) {
 int ssf_bilateral_filter(ssf_handle* h, const void* in, void* out, int on_device) {
     if (!h || !in || !out) return SSF_ERR_INVALID_ARG;
     const size_t P = (size_t)h->cfg.width * h->cfg.height;
-    const float* d_in = (const float*)in; float* d_out = (float*)out;
-    if (!on_device) { HCK(hipMemcpyAsync(h->d_bf_in, in, 4 * P, hipMemcpyHostToDevice, h->stream)); d_in = h->d_bf_in; d_out = h->d_bf_out; }
-    { TimerScope ts(h); launch_bilateral(h->stream, d_in, d_out, h->cfg.width, h->cfg.height, h->cfg.prefilter_sigma_color, h->cfg.prefilter_sigma_space); }
+    const void* d_in = in; float* d_out = (float*)out;
+    if (on_device && (!device_input_aligned(h, nullptr, in) || (uintptr_t)out % 4)) return SSF_ERR_INVALID_ARG;
+    // (input in the handle's depth format, ssf_input.h: h->d_bf_in holds P floats, room for either; the output is float metres)
+    if (!on_device) { HCK(hipMemcpyAsync(h->d_bf_in, in, depth_bpp(h) * P, hipMemcpyHostToDevice, h->stream)); d_in = h->d_bf_in; d_out = h->d_bf_out; }
+    { TimerScope ts(h); launch_bilateral(h->stream, d_in, h->in_depth, h->in_scale, d_out, h->cfg.width, h->cfg.height, h->cfg.prefilter_sigma_color, h->cfg.prefilter_sigma_space); }
     if (!on_device) HCK(hipMemcpyAsync(out, d_out, 4 * P, hipMemcpyDeviceToHost, h->stream));
     HCK(hipStreamSynchronize(h->stream));
     if (h->cfg.profile == 1) timer_collect(&h->timer);

@@ -12,7 +12,10 @@ core/src/supersurfel_fusion.cu:595-633).
 The depth pre-filter of processFrame (cv::cuda::bilateralFilter(depth, -1, 0.03, 4.5), supersurfel_fusion.cu:180)
 is ON, as in the reference (BENCHMARK_LAUNCH below).  Sparse VO, MOD and loop closure of the reference are out of
 scope: the pose prior is the previous pose.  Pre-decoded frames (np.savez archives produced by `pack_frames`) replace the PNG files on
-boxes without the dataset."""
+boxes without the dataset.
+
+--raw-frames hands the decoded colour and the 16-bit depth to the handle as they are (Fusion.set_input_format, include/ssf_input.h):
+the conversion happens in the kernels that load the pixels, and estimated.txt is the same, bit for bit."""
 import argparse
 import os
 
@@ -47,11 +50,12 @@ def read_associations(path, max_frames=None):
     return out
 
 
-def decode_frame(dataset_dir, entry, depth_scale):
+def decode_frame(dataset_dir, entry, depth_scale, raw=False):
+    """(rgb u8 HxWx3, depth): float32 metres, or with raw the sensor's uint16 counts"""
     from PIL import Image
     rgb = np.asarray(Image.open(os.path.join(dataset_dir, entry["rgb"])).convert("RGB"), np.uint8)
     d16 = np.asarray(Image.open(os.path.join(dataset_dir, entry["depth"])), np.uint16)
-    return rgb, convert_depth(d16, depth_scale)
+    return rgb, (d16 if raw else convert_depth(d16, depth_scale))
 
 
 def convert_depth(d16, depth_scale):
@@ -133,7 +137,7 @@ def tum_line(stamp, pose12):
 
 
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False):
-    """frames: iterable of (stamp, rgb u8 HxWx3, depth f32 HxW).  Returns (lines, results).
+    """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
     same, bit for bit, as with one process_frame per line."""
@@ -153,7 +157,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False):
                 except StopIteration:
                     done = True
                     break
-                rgb, depth = np.ascontiguousarray(rgb, np.uint8), np.ascontiguousarray(depth, np.float32)
+                rgb, depth = fusion._frame(rgb, depth)
                 fusion.submit_frame(rgb, depth)           # (the copy is asynchronous: ssf.h, ssf_submit_frame)
                 held.append((rgb, depth))
                 stamps.append(stamp)
@@ -219,18 +223,20 @@ def prior_consistency(fusion, frames, prior_xyz, prior_quat):
                 correction_rotation_p90_deg=float(np.percentile(da, 90)) if da else None)
 
 
-def frames_from_dataset(dataset_dir, depth_scale=0.0002, max_frames=None):
+def frames_from_dataset(dataset_dir, depth_scale=0.0002, max_frames=None, raw=False):
     for e in read_associations(os.path.join(dataset_dir, "associations_with_gt.txt"), max_frames):
-        rgb, depth = decode_frame(dataset_dir, e, depth_scale)
+        rgb, depth = decode_frame(dataset_dir, e, depth_scale, raw)
         yield e["stamp"], rgb, depth
 
 
-def frames_from_npz(path, depth_scale=0.0002):
+def frames_from_npz(path, depth_scale=0.0002, raw=False):
+    """(stamp, rgb, depth) of a frame archive; depth in float32 metres, or with raw the stored uint16 counts"""
     z = load_npz(path)
     i = 0
     while "rgb%d" % i in z:
         stamp = str(z["lines"][i]).split()[0]
-        yield stamp, z["rgb%d" % i], convert_depth(z["depth%d" % i], depth_scale)
+        d16 = z["depth%d" % i]
+        yield stamp, z["rgb%d" % i], (d16 if raw else convert_depth(d16, depth_scale))
         i += 1
 
 
@@ -255,7 +261,7 @@ def ate_rmse(est_xyz, gt_xyz):
     return float(np.sqrt((err ** 2).sum(1).mean()))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--dataset", help="TUM sequence directory with associations_with_gt.txt")
     ap.add_argument("--npz", help="pre-decoded frames (pack_frames) instead of --dataset")
@@ -264,12 +270,21 @@ def main():
     ap.add_argument("--max-frames", type=int, default=None)
     ap.add_argument("--export-model", default=None)
     ap.add_argument("--pipelined", action="store_true", help="extract of later frames runs ahead (pipeline_depth 2, extract_batch 4)")
-    a = ap.parse_args()
+    ap.add_argument("--raw-frames", action="store_true",
+                    help="hand the decoded colour and the uint16 depth to the handle unconverted (input format rgb8 + u16 x --depth-scale)")
+    return ap.parse_args(argv)
+
+
+def main():
+    a = parse_args()
     from . import binding
     lib = binding.load_product()
     cfg = lib.default_config(pipeline_depth=2 if a.pipelined else 0, extract_batch=4 if a.pipelined else 1, **BENCHMARK_LAUNCH)
     f = binding.Fusion(lib, cfg)
-    frames = frames_from_npz(a.npz, a.depth_scale) if a.npz else frames_from_dataset(a.dataset, a.depth_scale, a.max_frames)
+    if a.raw_frames:
+        f.set_input_format("rgb8", "u16", a.depth_scale)
+    frames = (frames_from_npz(a.npz, a.depth_scale, a.raw_frames) if a.npz
+              else frames_from_dataset(a.dataset, a.depth_scale, a.max_frames, a.raw_frames))
     lines, res = replay(f, frames, a.out, a.export_model, pipelined=a.pipelined)
     print("%d frames -> %s ; %d supersurfels" % (len(lines), a.out, res[-1]["n_model"] if res else 0))
 
