@@ -4,7 +4,8 @@
  * A node that owns a `supersurfel_fusion::SupersurfelFusion ssf;` member includes this header instead of the
  * reference's and links libssf_hip.so.  No OpenCV needed: processFrame takes raw pointers; the
  * cv::Mat overloads appear when <opencv2/core.hpp> has been included before this header.  setInputFormat (ssf_input.h,
- * libssf_hip.so only) lets processFrame take a sensor's frames as they come: BGR colour, uint16 depth counts.
+ * libssf_hip.so only) lets processFrame take a sensor's frames as they come: BGR colour, uint16 depth counts.  processFrame with a
+ * PixelMask (ssf_dynamic.h, libssf_hip.so only) takes a detector's per-pixel mask of moving objects.
  *
  * Sparse VO, MOD and loop closure stay with the caller; their outputs enter as `vo_pose` and `dynamic`.
  * Errors: the reference exits the process on a CUDA failure (cuda_error_check.h:30-66); this surface throws
@@ -16,6 +17,7 @@
 #include <vector>
 #include "ssf.h"
 #include "ssf_input.h"
+#include "ssf_dynamic.h"
 
 /* The reference's pose / matrix types (core/include/supersurfel_fusion/matrix_types.h:26-42), at GLOBAL scope as there,
  * so that the nodes' lines compile as they stand:
@@ -144,6 +146,12 @@ struct Supersurfels {                                                    /* supe
 static_assert(sizeof(DeviceArray<float3>) == sizeof(void*) + sizeof(size_t) && sizeof(Supersurfels) == 7 * sizeof(DeviceArray<float>),
               "ssf.hpp: the device views are (pointer, count) pairs in every translation unit");
 
+/* a per-pixel mask of moving objects for processFrame (ssf_dynamic.h): H x W bytes, non-zero = dynamic; nullptr = none */
+struct PixelMask {
+    const uint8_t* data;
+    explicit PixelMask(const uint8_t* d) : data(d) {}
+};
+
 class SupersurfelFusion {
 public:
     SupersurfelFusion() = default;
@@ -218,6 +226,25 @@ public:
         if (!depth_u16_) throw std::logic_error("processFrame(uint16_t depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
         check(ssf_process_frame(need(), rgb, reinterpret_cast<const float*>(depth_counts), vo_pose, dynamic, &last_));
     }
+    /* a per-pixel mask of moving objects (ssf_dynamic.h; exported by libssf_hip.so only): H x W bytes, non-zero = dynamic, e.g. a
+     * detector's person boxes rasterised.  The superpixels of which at least half the pixels are masked get confidence -1, as
+     * with the reference's MOD.  The mask is wrapped so that processFrame(rgb, depth, nullptr) stays the pose-prior overload:
+     *     ssf.processFrame(rgb_ptr, depth_ptr, supersurfel_fusion::PixelMask(mask_ptr), vo_pose);
+     * PixelMask(nullptr) = no mask. */
+    void processFrame(const uint8_t* rgb, const float* depth_m, PixelMask pixel_mask, const float* vo_pose = nullptr) {
+        if (depth_u16_) throw std::logic_error("processFrame: the input format is uint16 depth; pass the counts as const uint16_t*");
+        check(ssf_process_frame_pixmask(need(), rgb, depth_m, 0, vo_pose, pixel_mask.data, &last_));
+    }
+    void processFrame(const uint8_t* rgb, const uint16_t* depth_counts, PixelMask pixel_mask, const float* vo_pose = nullptr) {
+        if (!depth_u16_) throw std::logic_error("processFrame(uint16_t depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+        check(ssf_process_frame_pixmask(need(), rgb, depth_counts, 0, vo_pose, pixel_mask.data, &last_));
+    }
+    /* the dynamic superpixels of the last frame by its pixel mask (S bytes, 1 = dynamic; all 0 without a mask) */
+    std::vector<uint8_t> getDynamicSuperpixels() {
+        std::vector<uint8_t> v((size_t)getnbSuperpixels());
+        check(ssf_get_dynamic_superpixels(need(), v.data(), nullptr));
+        return v;
+    }
     /* replay of a recorded sequence (SupersurfelFusionRGBDBenchmarkNode::run): host images of n frames, results in
      * order; with pipeline_depth / extract_batch > 0 / 1 the extract stage runs ahead (bit-identical results) */
     std::vector<ssf_frame_result> processSequence(const std::vector<const uint8_t*>& rgb, const std::vector<const float*>& depth_m) {
@@ -249,6 +276,21 @@ public:
 #endif
         processFrame(rgb.ptr<uint8_t>(), d.ptr<float>(), vo_pose, dynamic);
     }
+#ifdef CV_8UC1
+    /* ... with a CV_8UC1 pixel mask of the frame's size (non-zero = moving object; an empty Mat = no mask), e.g. the node's
+     * YOLO person boxes drawn filled into a zero image */
+    void processFrame(const cv::Mat& rgb_h, const cv::Mat& depth_h, const cv::Mat& pixel_mask, const float* vo_pose = nullptr) {
+        if (pixel_mask.rows == 0 && pixel_mask.cols == 0) { processFrame(rgb_h, depth_h, vo_pose); return; }
+        if (pixel_mask.type() != CV_8UC1 || pixel_mask.rows != height_ || pixel_mask.cols != width_)
+            throw std::invalid_argument("processFrame: the pixel mask must be CV_8UC1 of the frame's size");
+        const cv::Mat rgb = rgb_h.isContinuous() ? rgb_h : rgb_h.clone(), d = depth_h.isContinuous() ? depth_h : depth_h.clone();
+        const cv::Mat m = pixel_mask.isContinuous() ? pixel_mask : pixel_mask.clone();
+#ifdef CV_16UC1
+        if (d.type() == CV_16UC1) { processFrame(rgb.ptr<uint8_t>(), d.ptr<uint16_t>(), PixelMask(m.ptr<uint8_t>()), vo_pose); return; }
+#endif
+        processFrame(rgb.ptr<uint8_t>(), d.ptr<float>(), PixelMask(m.ptr<uint8_t>()), vo_pose);
+    }
+#endif
     void computeSuperpixelSegIm(cv::Mat& seg_im) {                     /* CV_8UC3, supersurfel_fusion.cu:635-640 */
         seg_im.create(height_, width_, CV_8UC3);
         check(ssf_get_preview_image(need(), seg_im.ptr<uint8_t>()));

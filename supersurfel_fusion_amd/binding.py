@@ -75,6 +75,9 @@ INPUT_FORMAT_SYMBOLS = ["ssf_set_input_format", "ssf_get_input_format"]
 # ssf_color_format / ssf_depth_format: name -> (enum value, bytes per pixel)
 COLOR_FORMATS = {"rgb8": (0, 3), "bgr8": (1, 3), "rgba8": (2, 4), "bgra8": (3, 4)}
 DEPTH_FORMATS = {"f32": (0, 4), "u16": (1, 2)}
+# the pixel-mask entry points of include/ssf_dynamic.h: exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
+DYNAMIC_MASK_SYMBOLS = ["ssf_process_frame_pixmask", "ssf_submit_frame_pixmask", "ssf_process_sequence_pixmask",
+                        "ssf_stage_extract_pixmask", "ssf_get_dynamic_superpixels"]
 
 SURFEL_FIELDS = (("positions", 3, np.float32), ("colors", 3, np.float32), ("stamps", 2, np.int32),
                  ("orientations", 9, np.float32), ("shapes", 6, np.float32),
@@ -164,6 +167,13 @@ class Library:
         if self.has_input_format:
             L.ssf_set_input_format.argtypes = [vp, C.c_int, C.c_int, C.c_double]
             L.ssf_get_input_format.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        self.has_dynamic_mask = all(hasattr(L, nm) for nm in DYNAMIC_MASK_SYMBOLS)
+        if self.has_dynamic_mask:
+            L.ssf_process_frame_pixmask.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.POINTER(SsfFrameResult)]
+            L.ssf_submit_frame_pixmask.argtypes = [vp, vp, vp, C.c_int, vp]
+            L.ssf_process_sequence_pixmask.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp]
+            L.ssf_stage_extract_pixmask.argtypes = [vp, vp, vp, C.c_int, vp]
+            L.ssf_get_dynamic_superpixels.argtypes = [vp, vp, C.POINTER(C.c_int)]
 
     @property
     def backend(self):
@@ -287,33 +297,88 @@ class Fusion:
                 np.dtype(dt).name, self.H, self.W, self.depth_format, depth.dtype, depth.shape))
         return np.ascontiguousarray(depth)
 
+    # ---- pixel masks (include/ssf_dynamic.h) --------------------------------------------------
+    def _need_pixmask(self, symbol):
+        if not self.L.has_dynamic_mask:
+            raise SsfError("%s does not export %s: it takes no pixel masks (include/ssf_dynamic.h)" % (self.L.path, symbol))
+
+    def _pixel_mask(self, pixel_mask, on_device=False):
+        """the ctypes argument of a pixel mask: None, a device address (int) when on_device, else an H x W uint8 host array
+        (bool is taken as is: one byte per pixel).  Anything else is refused, not cast."""
+        if pixel_mask is None:
+            return None, None
+        if on_device:
+            if not isinstance(pixel_mask, (int, np.integer)):
+                raise SsfError("a device pixel mask is a device address (int), got %s" % type(pixel_mask).__name__)
+            return C.c_void_p(int(pixel_mask)), None
+        m = np.asarray(pixel_mask)
+        if m.dtype not in (np.uint8, np.bool_) or m.shape != (self.H, self.W):
+            raise SsfError("pixel mask must be uint8 (or bool) %dx%d, got %s %s" % (self.H, self.W, m.dtype, m.shape))
+        m = np.ascontiguousarray(m).view(np.uint8)
+        return _ptr(m), m
+
+    def dynamic_superpixels(self):
+        """(S uint8 array, count): the pixel-mask vote of the current frame, 1 = dynamic (all 0 without a pixel mask)"""
+        self._need_pixmask("ssf_get_dynamic_superpixels")
+        out = np.zeros(self.S, np.uint8)
+        n = C.c_int()
+        self._ck(self.L.lib.ssf_get_dynamic_superpixels(self.h, _ptr(out), C.byref(n)), "ssf_get_dynamic_superpixels")
+        return out, n.value
+
     # ---- whole frame -------------------------------------------------------------------------
-    def process_frame(self, rgb, depth, prior_pose=None, dynamic_mask=None):
+    def process_frame(self, rgb, depth, prior_pose=None, dynamic_mask=None, pixel_mask=None):
+        """pixel_mask: H x W uint8 (non-zero = moving object), voted onto the frame's superpixels (ssf_dynamic.h);
+        not together with dynamic_mask (one byte per superpixel)."""
         rgb, depth = self._frame(rgb, depth)
         prior = None if prior_pose is None else np.ascontiguousarray(prior_pose, np.float32)
+        if pixel_mask is not None:
+            self._need_pixmask("ssf_process_frame_pixmask")
+            if dynamic_mask is not None:
+                raise SsfError("pixel_mask and dynamic_mask do not combine: the pixel-mask calls take no per-superpixel mask")
+            pm, keep = self._pixel_mask(pixel_mask)
+            res = SsfFrameResult()
+            self._ck(self.L.lib.ssf_process_frame_pixmask(self.h, _ptr(rgb), _ptr(depth), 0, _ptr(prior), pm, C.byref(res)),
+                     "ssf_process_frame_pixmask")
+            return res.as_dict()
         mask = None if dynamic_mask is None else np.ascontiguousarray(dynamic_mask, np.uint8)
         res = SsfFrameResult()
         self._ck(self.L.lib.ssf_process_frame(self.h, _ptr(rgb), _ptr(depth), _ptr(prior), _ptr(mask),
                                               C.byref(res)), "ssf_process_frame")
         return res.as_dict()
 
-    def process_frame_device(self, d_rgb_ptr, d_depth_ptr, prior_pose=None):
+    def process_frame_device(self, d_rgb_ptr, d_depth_ptr, prior_pose=None, pixel_mask=None):
+        """pixel_mask: None or the device address of an H x W uint8 pixel mask (ssf_dynamic.h)"""
         prior = None if prior_pose is None else np.ascontiguousarray(prior_pose, np.float32)
         res = SsfFrameResult()
+        if pixel_mask is not None:
+            self._need_pixmask("ssf_process_frame_pixmask")
+            pm, _ = self._pixel_mask(pixel_mask, on_device=True)
+            self._ck(self.L.lib.ssf_process_frame_pixmask(self.h, C.c_void_p(d_rgb_ptr), C.c_void_p(d_depth_ptr), 1, _ptr(prior), pm,
+                                                          C.byref(res)), "ssf_process_frame_pixmask")
+            return res
         self._ck(self.L.lib.ssf_process_frame_device(self.h, C.c_void_p(d_rgb_ptr), C.c_void_p(d_depth_ptr),
                                                      _ptr(prior), None, C.byref(res)),
                  "ssf_process_frame_device")
         return res
 
     # ---- pipelined form ----------------------------------------------------------------------
-    def submit_frame(self, rgb, depth, dynamic_mask=None, on_device=False):
+    def submit_frame(self, rgb, depth, dynamic_mask=None, on_device=False, pixel_mask=None):
         """Enqueue the extract stage of the next frame (asynchronous).  With on_device=True rgb and
-        depth are device addresses that must stay valid until the frame has been processed."""
+        depth are device addresses that must stay valid until the frame has been processed.
+        pixel_mask (ssf_dynamic.h): H x W uint8 host array, or a device address with on_device=True."""
         if on_device:
             rp, dp = C.c_void_p(rgb), C.c_void_p(depth)
         else:
             rgb, depth = self._frame(rgb, depth)
             rp, dp = _ptr(rgb), _ptr(depth)
+        if pixel_mask is not None:
+            self._need_pixmask("ssf_submit_frame_pixmask")
+            if dynamic_mask is not None:
+                raise SsfError("pixel_mask and dynamic_mask do not combine: the pixel-mask calls take no per-superpixel mask")
+            pm, keep = self._pixel_mask(pixel_mask, on_device)
+            self._ck(self.L.lib.ssf_submit_frame_pixmask(self.h, rp, dp, 1 if on_device else 0, pm), "ssf_submit_frame_pixmask")
+            self._held.append((rgb, depth, keep))
+            return
         mask = None if dynamic_mask is None else np.ascontiguousarray(dynamic_mask, np.uint8)
         self._ck(self.L.lib.ssf_submit_frame(self.h, rp, dp, 1 if on_device else 0, _ptr(mask)), "ssf_submit_frame")
         self._held.append((rgb, depth, mask))
@@ -332,16 +397,31 @@ class Fusion:
         n = len(rgb_ptrs)
         return (C.c_void_p * n)(*rgb_ptrs), (C.c_void_p * n)(*depth_ptrs), (SsfFrameResult * n)(), n
 
-    def process_prepared(self, prepared, on_device=True):
-        """ssf_process_sequence on arrays from prepare_sequence; returns the raw SsfFrameResult array (as_dict() each)."""
+    def process_prepared(self, prepared, on_device=True, mask_ptrs=None):
+        """ssf_process_sequence on arrays from prepare_sequence; returns the raw SsfFrameResult array (as_dict() each).
+        mask_ptrs: None, or one pixel-mask address (or None / 0) per frame: ssf_process_sequence_pixmask."""
         pr, pd, res, n = prepared
-        self._ck(self.L.lib.ssf_process_sequence(self.h, pr, pd, n, 1 if on_device else 0, res), "ssf_process_sequence")
+        if mask_ptrs is None:
+            self._ck(self.L.lib.ssf_process_sequence(self.h, pr, pd, n, 1 if on_device else 0, res), "ssf_process_sequence")
+            return res
+        self._need_pixmask("ssf_process_sequence_pixmask")
+        if len(mask_ptrs) != n:
+            raise SsfError("mask_ptrs has %d entries for %d frames" % (len(mask_ptrs), n))
+        pm = (C.c_void_p * n)(*[int(q) if q else None for q in mask_ptrs])
+        self._ck(self.L.lib.ssf_process_sequence_pixmask(self.h, pr, pd, pm, n, 1 if on_device else 0, res), "ssf_process_sequence_pixmask")
         return res
 
-    def process_sequence(self, rgb_ptrs, depth_ptrs, on_device=True):
+    def process_sequence(self, rgb_ptrs, depth_ptrs, on_device=True, mask_ptrs=None):
         """The whole submit-ahead / process-in-order loop in native code.  rgb_ptrs / depth_ptrs: raw addresses
-        (device pointers when on_device, else addresses of contiguous host arrays).  Returns a list of result dicts."""
-        return [r.as_dict() for r in self.process_prepared(self.prepare_sequence(rgb_ptrs, depth_ptrs), on_device)]
+        (device pointers when on_device, else addresses of contiguous host arrays).  mask_ptrs: None, or per frame the
+        address of its H x W uint8 pixel mask (same kind as the frames) or None (ssf_dynamic.h).  Returns a list of result dicts."""
+        return [r.as_dict() for r in self.process_prepared(self.prepare_sequence(rgb_ptrs, depth_ptrs), on_device, mask_ptrs)]
+
+    def host_masks(self, masks):
+        """Host pixel masks for process_sequence(mask_ptrs=...), checked like process_frame's: returns (mask_ptrs, keep) -- an
+        entry None stays None; `keep` holds the arrays and must outlive the call."""
+        keep = [None if m is None else self._pixel_mask(m)[1] for m in masks]
+        return [None if m is None else m.ctypes.data for m in keep], keep
 
     def host_sequence(self, rgbs, depths):
         """Host frames for prepare_sequence / process_sequence(on_device=False), checked against the input format like
@@ -368,7 +448,19 @@ class Fusion:
         return int(self.L.lib.ssf_pipeline_capacity(self.h))
 
     # ---- stage seams -------------------------------------------------------------------------
-    def stage_extract(self, rgb, depth, dynamic_mask=None, on_device=False):
+    def stage_extract(self, rgb, depth, dynamic_mask=None, on_device=False, pixel_mask=None):
+        if pixel_mask is not None:
+            self._need_pixmask("ssf_stage_extract_pixmask")
+            if dynamic_mask is not None:
+                raise SsfError("pixel_mask and dynamic_mask do not combine: the pixel-mask calls take no per-superpixel mask")
+            if on_device:
+                rp, dp = C.c_void_p(rgb), C.c_void_p(depth)
+            else:
+                rgb, depth = self._frame(rgb, depth)
+                rp, dp = _ptr(rgb), _ptr(depth)
+            pm, keep = self._pixel_mask(pixel_mask, on_device)
+            self._ck(self.L.lib.ssf_stage_extract_pixmask(self.h, rp, dp, 1 if on_device else 0, pm), "ssf_stage_extract_pixmask")
+            return
         if on_device:
             rp, dp = C.c_void_p(rgb), C.c_void_p(depth)
         elif (self.color_format, self.depth_format) == ("rgb8", "f32"):

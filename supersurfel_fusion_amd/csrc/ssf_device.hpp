@@ -23,6 +23,7 @@
 #include "ssf_math.hpp"
 #include "../../include/ssf.h"
 #include "../../include/ssf_input.h"
+#include "../../include/ssf_dynamic.h"
 
 // SSF_EXPERIMENTS: the laboratory build (csrc/variants/lab/libssf_hip.so, `make lab`): the measurement arms and environment
 // switches behind DESIGN.md's A/B tables.  The PRODUCT library is built without it: it reads no environment variable and
@@ -236,10 +237,18 @@ void launch_plane_filter(hipStream_t st, const SegParams& p, FrameMaps& m, int n
 void launch_import_frame(hipStream_t st, const SegParams& p, FrameMaps& m, int nb, SurfelSoA frame, const float* wire, unsigned long long* best, uint8_t* matched);
 void launch_export_rows(hipStream_t st, const SegParams& p, const FrameMaps& m, int nb, SurfelSoA frame, float* wire);      // the nb slots' supersurfels -> their wire buffers
 void launch_render_moments(hipStream_t st, const SegParams& p, const Cam& cam, FrameMaps& m, int nb);
+// ... for a batch with pixel masks (ssf_dynamic.h): also counts every slot's pixels per superpixel and those whose byte of
+// pixmask (P bytes per slot) is non-zero into pixcnt (2 S u32 per slot: total, masked; zeroed by the caller for the slots it votes)
+void launch_render_moments_pixmask(hipStream_t st, const SegParams& p, const Cam& cam, FrameMaps& m, int nb, const uint8_t* pixmask,
+                                   uint32_t* pixcnt);
 // frame k of the batch gets stamp stamp0 + k; bit k of mask_bits: dynamic_mask slot k is valid
 void launch_finalize_surfels(hipStream_t st, const SegParams& p, FrameMaps& m, int nb, SurfelSoA frame, float zmin,
                              float zmax, int stamp0, const uint8_t* dynamic_mask, unsigned mask_bits,
                              unsigned long long* best, uint8_t* matched);
+// ... + bit k of pixmask_bits: frame k votes its superpixels dynamic from the counts of launch_render_moments_pixmask
+void launch_finalize_surfels_pixmask(hipStream_t st, const SegParams& p, FrameMaps& m, int nb, SurfelSoA frame, float zmin, float zmax,
+                                     int stamp0, const uint8_t* dynamic_mask, unsigned mask_bits, unsigned long long* best, uint8_t* matched,
+                                     const uint32_t* pixcnt, unsigned pixmask_bits);
 void launch_bilateral(hipStream_t st, const void* in, int depth_format, double depth_scale, float* out, int W, int H, float sigma_color,
                       float sigma_space);
 // the nb frames of a batch in ONE launch: frame b from in.depth[b] (in.depth_format) to out0 + b * slab bytes (float metres)

@@ -1156,13 +1156,24 @@ __global__ __launch_bounds__(1024) void k_plane_filter_tiled(SegParams p, FrameM
 #ifndef MOM_REP
 #define MOM_REP(wcap) ((wcap) <= WIN_SMALL ? 8 : 4)
 #endif
-template <int WCAP>
-__global__ __launch_bounds__(256) void k_render_moments(SegParams p, Cam cam, FrameMaps m, TileOrder ord) {
+// PIXMASK (ssf_dynamic.h): the same tile also counts, per superpixel, its pixels and those of them whose pixel-mask byte is set --
+// total[s] and masked[s], as two u32 per superpixel at pixcnt[2 s] / [2 s + 1] (zeroed in front of the launch) -- with one
+// packed u32 LDS counter per window cell and replica (masked << 16 | total: a replica counts at most TILE * TILE pixels) and a
+// global atomic per pixel whose label is outside the window.  Integer sums over a partition of the image: exact and order-free.
+// The unmasked kernel is the PIXMASK = false instantiation, with not one instruction of this.
+static_assert(TILE * TILE < 65536, "packed window-cell pixel counters");
+// a batch in which at least one frame carries a pixel mask: pixmask / pixcnt are slot 0 of the context's P-byte mask and 2 S-word
+// count buffers (slot b at + b * m.slab bytes); every slot is counted, the vote (k_finalize_surfels<true>) reads only those flagged.
+template <int WCAP, bool PIXMASK>
+__global__ __launch_bounds__(256) void k_render_moments(SegParams p, Cam cam, FrameMaps m, TileOrder ord, const uint8_t* __restrict__ pixmask,
+                                                        uint32_t* __restrict__ pixcnt) {
     __shared__ int tile[TW * TW];
     __shared__ __attribute__((aligned(16))) SpRow w_row[WCAP];
     __shared__ unsigned long long w_acc[WCAP * 13 * MOM_REP(WCAP)];    // MOM_REP replicas (lane id) against same-address serialisation
+    __shared__ uint32_t w_pix[WCAP * MOM_REP(WCAP)];                   // (PIXMASK only: unreferenced, and not allocated, otherwise)
     const TileIdx ti = tile_index(ord);                // (XCD-aware tile order: see tile_index)
     m = batch_slot(m, ti.bz);
+    if constexpr (PIXMASK) { pixmask = slab_shift(pixmask, (size_t)ti.bz * m.slab); pixcnt = slab_shift(pixcnt, (size_t)ti.bz * m.slab); }
     const int X0 = ti.bx * TILE, Y0 = ti.by * TILE;
     CellWindow win; win.init(p, X0, Y0, WCAP);
     // Everything the workgroup needs from memory is requested first -- the window's rows, the gamma table, this thread's
@@ -1178,16 +1189,19 @@ __global__ __launch_bounds__(256) void k_render_moments(SegParams p, Cam cam, Fr
     const float lut = m.srgb_lut[threadIdx.x];
     // this thread's pixels: inlier flag and colour (clamped addresses, used only for pixels inside the image)
     constexpr int PX = TILE * TILE / 256;
-    unsigned char pin[PX]; uint32_t prgba[PX];
+    unsigned char pin[PX]; uint32_t prgba[PX]; unsigned char pmk[PX];
 #pragma unroll
     for (int k = 0; k < PX; k++) {
         const int i = threadIdx.x + 256 * k;
         const int x = min(X0 + i % TILE, p.W - 1), y = min(Y0 + i / TILE, p.H - 1);
         const unsigned int q = __umul24((unsigned int)y, (unsigned int)p.W) + (unsigned int)x;
         pin[k] = m.inlier[q]; prgba[k] = m.rgba[q];
+        if constexpr (PIXMASK) pmk[k] = pixmask[q];
     }
     const TileRegs treg = tile_request(m.label, X0, Y0, p.W, p.H);
     for (int i = threadIdx.x; i < win.size() * 13 * MOM_REP(WCAP); i += blockDim.x) w_acc[i] = 0ull;
+    if constexpr (PIXMASK)
+        for (int i = threadIdx.x; i < win.size() * MOM_REP(WCAP); i += blockDim.x) w_pix[i] = 0u;
     // the gamma table in LDS: three lookups per pixel would otherwise be global loads queued behind this thread's
     // stores (the maps may alias as far as the compiler knows)
     __shared__ float s_lut[256];
@@ -1210,6 +1224,13 @@ __global__ __launch_bounds__(256) void k_render_moments(SegParams p, Cam cam, Fr
         const float disp = ((float)x * sp.ta + (float)y * sp.tb) + sp.tc;
         const float depth = 1.f / disp;
         out_label[k] = label; out_depth[k] = depth;
+        if constexpr (PIXMASK) {                 // every pixel of the label map counts, inlier or not
+            if (ws >= 0) atomicAdd(&w_pix[ws * MOM_REP(WCAP) + (lane_id() & (MOM_REP(WCAP) - 1))], 1u + ((pmk[k] != 0 ? 1u : 0u) << 16));
+            else {
+                atomicAdd(&pixcnt[2 * (size_t)label], 1u);
+                if (pmk[k]) atomicAdd(&pixcnt[2 * (size_t)label + 1], 1u);
+            }
+        }
         const int bound = tile_boundary(tile, lx + 1, ly + 1);
         if (!(pin[k] && isfinite(depth) && depth > 0.0f && bound == 0)) continue;
         const V3 pos = v3(((float)x - cam.cx) * depth / cam.fx, ((float)y - cam.cy) * depth / cam.fy, depth);
@@ -1244,6 +1265,16 @@ __global__ __launch_bounds__(256) void k_render_moments(SegParams p, Cam cam, Fr
         for (int r = 0; r < MOM_REP(WCAP); r++) v += (long long)w_acc[((i / 13) * MOM_REP(WCAP) + r) * 13 + i % 13];
         if (v != 0) atomic_add_i64(&m.moments[(size_t)win.label_of(i / 13, p.gy) * 13 + i % 13], v);
     }
+    if constexpr (PIXMASK)
+        for (int i = threadIdx.x; i < win.size(); i += blockDim.x) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int r = 0; r < MOM_REP(WCAP); r++) v += w_pix[i * MOM_REP(WCAP) + r];      // (each field < 2^16: no carry)
+            if (v == 0) continue;
+            const size_t l = (size_t)win.label_of(i, p.gy);
+            atomicAdd(&pixcnt[2 * l], v & 0xFFFFu);
+            if (v >> 16) atomicAdd(&pixcnt[2 * l + 1], v >> 16);
+        }
 }
 
 // computeSupersurfels, supersurfel_fusion_kernels.cu:169-224 (+ the MOD mask hook).  64 superpixels per workgroup.  One
@@ -1252,9 +1283,13 @@ __global__ __launch_bounds__(256) void k_render_moments(SegParams p, Cam cam, Fr
 // they run side by side with identical arithmetic: waves 0-1, two lanes per superpixel, iterate towards the largest /
 // smallest axis; wave 2 converts the colour; wave 2 then assembles and stores the supersurfel.
 #define FIN_PER_WG 64
+// PIXMASK: the vote of ssf_dynamic.h for the frames whose bit is set in pixmask_bits, from the counts k_render_moments_pixmask
+// left at pixcnt (slot 0; + b * m.slab bytes for slot b): dynamic iff masked > 0 && 2 masked >= total.
+template <bool PIXMASK>
 __global__ __launch_bounds__(256) void k_finalize_surfels(SegParams p, FrameMaps m, SurfelSoA f, float zmin, float zmax, int stamp0,
                                                           const uint8_t* __restrict__ dyn_mask, unsigned mask_bits,
-                                                          unsigned long long* __restrict__ best, uint8_t* __restrict__ matched) {
+                                                          unsigned long long* __restrict__ best, uint8_t* __restrict__ matched,
+                                                          const uint32_t* __restrict__ pixcnt, unsigned pixmask_bits) {
     __shared__ float s_axis[2][FIN_PER_WG][3];
     const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
     const int kk = wv < 2 ? wv * 32 + (l >> 1) : l;
@@ -1308,6 +1343,13 @@ __global__ __launch_bounds__(256) void k_finalize_surfels(SegParams p, FrameMaps
     } else
         conf = -1.0f;
     if (dyn_mask && dyn_mask[k]) conf = -1.0f;
+    if constexpr (PIXMASK) {
+        if ((pixmask_bits >> fb) & 1u) {
+            const uint32_t* c = slab_shift(pixcnt, off);
+            const uint32_t total = c[2 * k], masked = c[2 * k + 1];
+            if (masked > 0u && 2ull * masked >= (unsigned long long)total) conf = -1.0f;
+        }
+    }
     f.pos[3 * k] = pos.x; f.pos[3 * k + 1] = pos.y; f.pos[3 * k + 2] = pos.z;
     f.col[3 * k] = col.x; f.col[3 * k + 1] = col.y; f.col[3 * k + 2] = col.z;
     f.lab[3 * k] = lab.x; f.lab[3 * k + 1] = lab.y; f.lab[3 * k + 2] = lab.z;
@@ -1795,8 +1837,16 @@ void launch_plane_filter(hipStream_t st, const SegParams& p, FrameMaps& m, int n
 void launch_render_moments(hipStream_t st, const SegParams& p, const Cam& cam, FrameMaps& m, int nb) {
     ScopedKernel sk("render_moments", st);
     const dim3 grid = batch_tile_grid(p, nb);
-    if (p.win_cells_max <= WIN_SMALL) hipLaunchKernelGGL(k_render_moments<WIN_SMALL>, grid, dim3(256), SSF_RENDER_DYN_LDS, st, p, cam, m, tile_order(grid));
-    else hipLaunchKernelGGL(k_render_moments<WIN_MAX>, grid, dim3(256), SSF_RENDER_DYN_LDS, st, p, cam, m, tile_order(grid));
+    if (p.win_cells_max <= WIN_SMALL) hipLaunchKernelGGL((k_render_moments<WIN_SMALL, false>), grid, dim3(256), SSF_RENDER_DYN_LDS, st, p, cam, m, tile_order(grid), nullptr, nullptr);
+    else hipLaunchKernelGGL((k_render_moments<WIN_MAX, false>), grid, dim3(256), SSF_RENDER_DYN_LDS, st, p, cam, m, tile_order(grid), nullptr, nullptr);
+}
+void launch_render_moments_pixmask(hipStream_t st, const SegParams& p, const Cam& cam, FrameMaps& m, int nb, const uint8_t* pixmask,
+                                   uint32_t* pixcnt) {
+    ScopedKernel sk("render_moments", st);
+    const dim3 grid = batch_tile_grid(p, nb);
+    if (p.win_cells_max <= WIN_SMALL)
+        hipLaunchKernelGGL((k_render_moments<WIN_SMALL, true>), grid, dim3(256), SSF_RENDER_DYN_LDS, st, p, cam, m, tile_order(grid), pixmask, pixcnt);
+    else hipLaunchKernelGGL((k_render_moments<WIN_MAX, true>), grid, dim3(256), SSF_RENDER_DYN_LDS, st, p, cam, m, tile_order(grid), pixmask, pixcnt);
 }
 void launch_import_frame(hipStream_t st, const SegParams& p, FrameMaps& m, int nb, SurfelSoA frame, const float* wire, unsigned long long* best, uint8_t* matched) {
     ScopedKernel sk("import_frame", st);
@@ -1811,8 +1861,15 @@ void launch_finalize_surfels(hipStream_t st, const SegParams& p, FrameMaps& m, i
                              float zmax, int stamp0, const uint8_t* dynamic_mask, unsigned mask_bits,
                              unsigned long long* best, uint8_t* matched) {
     ScopedKernel sk("finalize_surfels", st);
-    hipLaunchKernelGGL(k_finalize_surfels, dim3((p.S + FIN_PER_WG - 1) / FIN_PER_WG, nb), dim3(256), 0, st, p, m, frame, zmin, zmax, stamp0,
-                       dynamic_mask, mask_bits, best, matched);
+    hipLaunchKernelGGL(k_finalize_surfels<false>, dim3((p.S + FIN_PER_WG - 1) / FIN_PER_WG, nb), dim3(256), 0, st, p, m, frame, zmin, zmax, stamp0,
+                       dynamic_mask, mask_bits, best, matched, nullptr, 0u);
+}
+void launch_finalize_surfels_pixmask(hipStream_t st, const SegParams& p, FrameMaps& m, int nb, SurfelSoA frame, float zmin, float zmax,
+                                     int stamp0, const uint8_t* dynamic_mask, unsigned mask_bits, unsigned long long* best, uint8_t* matched,
+                                     const uint32_t* pixcnt, unsigned pixmask_bits) {
+    ScopedKernel sk("finalize_surfels", st);
+    hipLaunchKernelGGL(k_finalize_surfels<true>, dim3((p.S + FIN_PER_WG - 1) / FIN_PER_WG, nb), dim3(256), 0, st, p, m, frame, zmin, zmax,
+                       stamp0, dynamic_mask, mask_bits, best, matched, pixcnt, pixmask_bits);
 }
 void launch_boundary_map(hipStream_t st, const SegParams& p, const int32_t* label, int32_t* out) {
     hipLaunchKernelGGL(k_boundary_map, tile_grid(p), dim3(256), 0, st, p, label, out);

@@ -368,6 +368,9 @@ struct Uploader {
     // page-locked staging slots (one per ring slot): the worker copies the caller's pageable frame here itself and hands
     // the runtime a truly asynchronous DMA; left to the runtime, pageable copies of several threads serialise inside it
     std::vector<uint8_t*> p_rgb; std::vector<float*> p_depth;
+    // pixel masks of ssf_process_sequence_pixmask (ssf_dynamic.h): masks[i] == NULL or masks == NULL, no copy; P bytes per ring slot
+    const uint8_t* const* masks = nullptr; size_t mask_bytes = 0;
+    std::vector<uint8_t*> d_mask, p_mask;
     bool ready(int i) const { return done[i % NTH].load(std::memory_order_acquire) > i; }
     // where the workers' time went, microseconds summed over the workers since the handle was created (ssf_upload_stats):
     // waiting for a free ring slot | the staging memcpy | the two hipMemcpyAsync calls; frames
@@ -384,13 +387,16 @@ struct Uploader {
             const int sl = i % ring;
             hipStream_t st = ctx_stream[(size_t)(ctx0 + seq_batch_of(i, batch)) % ctx_stream.size()];
             const void* src_rgb = rgb[i]; const void* src_depth = depth[i];
+            const uint8_t* src_mask = masks ? masks[i] : nullptr;
             if (!p_rgb.empty()) {           // (slot sl was last used by frame i - ring, which has been processed: its DMA is done)
                 std::memcpy(p_rgb[sl], rgb[i], rgb_bytes); std::memcpy(p_depth[sl], depth[i], depth_bytes);
                 src_rgb = p_rgb[sl]; src_depth = p_depth[sl];
+                if (src_mask) { std::memcpy(p_mask[sl], src_mask, mask_bytes); src_mask = p_mask[sl]; }
             }
             const double t2 = now_us();
             if (hipMemcpyAsync(d_rgb[sl], src_rgb, rgb_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
-                hipMemcpyAsync(d_depth[sl], src_depth, depth_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { failed.store(1); return; }
+                hipMemcpyAsync(d_depth[sl], src_depth, depth_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+                (src_mask && hipMemcpyAsync(d_mask[sl], src_mask, mask_bytes, hipMemcpyHostToDevice, st) != hipSuccess)) { failed.store(1); return; }
             done[t].store(i + 1, std::memory_order_release);
             const double t3 = now_us();
             us_ring += (long long)(t1 - t0); us_memcpy += (long long)(t2 - t1); us_enqueue += (long long)(t3 - t2); frames_done++;
@@ -528,12 +534,18 @@ struct ExtractCtx {
     int count = 0, inflight = 0, stamp0 = 0, nb_launched = 1; bool launched = false, waited = false;
     uint32_t epoch0 = 0;
     BatchIn in = {}; unsigned mask_bits = 0;
+    // pixel masks (ssf_dynamic.h): P mask bytes and 2 S pixel counts (total, masked) per slot; bit b of pixmask_bits: slot b has
+    // a mask.  A batch with any bit set runs the counting instantiations (k_render_moments<., true>, k_finalize_surfels<true>),
+    // whose segmentation chain is captured in a graph of its own.
+    uint8_t* d_pixmask = nullptr; uint32_t* d_pixcnt = nullptr; unsigned pixmask_bits = 0;
+    hipGraph_t graph_pm[SSF_MAX_BATCH + 1] = {}; hipGraphExec_t exec_pm[SSF_MAX_BATCH + 1] = {};
 };
 // the frame the track/fuse chain works on: slot views into its context
 struct ActiveFrame {
     FrameMaps maps; SurfelSoA frame;
     unsigned long long* d_best = nullptr; uint8_t* d_matched = nullptr;
     ExtractCtx* ctx = nullptr; int slot = 0;
+    bool pixmask = false;                         // the frame was submitted with a pixel mask: ssf_get_dynamic_superpixels reads its counts
 };
 
 // Round 6: the tile-sorted copy (ssf_tile_rows.inc) in the product, for LARGE visible sets.  At BASELINE config 3 (940 k visible
@@ -555,7 +567,7 @@ struct ssf_handle {
     uint32_t extract_ordinal = 0;                 // frames submitted so far = RNG epoch of the next frame
     // ssf_process_sequence: frames still to be submitted; do_fuse submits them between its launches and its wait for
     // the counters (the ~40 us of host work of a batch launch hide behind the ~55 us fuse chain on the GPU)
-    const void* const* seq_rgb = nullptr; const void* const* seq_depth = nullptr; int seq_next = 0, seq_n = 0, seq_on_device = 0, stamp_bias = 0;
+    const void* const* seq_rgb = nullptr; const void* const* seq_depth = nullptr; const uint8_t* const* seq_pixmask = nullptr; int seq_next = 0, seq_n = 0, seq_on_device = 0, stamp_bias = 0;
     long long n_waiter_matches = 0;           // frames whose association ran in a waiting ICP launch (debug)
     int seq_k = 0;                            // frame of the sequence the track loop is working on (debug marks)
     int seq_batches = 0;                      // batches launched by the running ssf_process_sequence (see seq_batch_size)
@@ -746,7 +758,7 @@ struct TimerScope {
 // Pass k reads label/sums buffer k&1 and writes the other; no merge launch between passes (the pass
 // kernel rebuilds the rows it needs from the quiescent sums buffer).  The global superpixel table is
 // only materialised where a later stage wants it: before the plane filter.
-static void enqueue_segmentation(ssf_handle* h, ExtractCtx& c, hipStream_t st) {
+static void enqueue_segmentation(ssf_handle* h, ExtractCtx& c, hipStream_t st, bool pixmask) {
     const SegParams& p = h->seg;
     const int nb = c.count;
     const int limit = h->max_passes > 0 ? h->max_passes : (1 << 30);
@@ -773,14 +785,17 @@ static void enqueue_segmentation(ssf_handle* h, ExtractCtx& c, hipStream_t st) {
     } else
         for (; k < k2; k++) launch_update_pass(st, p, c.maps, nb, k, ox[k & 3], oy[k & 3], true, 0);
     launch_plane_filter(st, p, c.maps, nb, k & 1);             // final merge (table + planes) + smoothing sweeps
-    launch_render_moments(st, p, h->cam, c.maps, nb);
+    if (pixmask) launch_render_moments_pixmask(st, p, h->cam, c.maps, nb, c.d_pixmask, c.d_pixcnt);
+    else launch_render_moments(st, p, h->cam, c.maps, nb);
 }
 // ~45 short dependent kernels: replayed as one captured hipGraph (launch-bound inner loop), one graph per
 // batch size; eager when kernels are individually timed or the pass count is being bisected
 static int run_segmentation(ssf_handle* h, ExtractCtx& c) {
     const bool use_graph = h->cfg.profile != 1 && h->max_passes == 0 && !h->graph_failed;
+    const bool pm = c.pixmask_bits != 0;
     if (use_graph) {
-        hipGraphExec_t& ex = c.exec[c.count];
+        hipGraphExec_t& ex = pm ? c.exec_pm[c.count] : c.exec[c.count];
+        hipGraph_t& graph = pm ? c.graph_pm[c.count] : c.graph[c.count];
         if (!ex) {
             // captured on a stream of its own, not on the context's: the upload thread (Uploader) may be enqueueing
             // copies on the context's stream at this very moment
@@ -794,16 +809,16 @@ static int run_segmentation(ssf_handle* h, ExtractCtx& c) {
             bool ok = (h->capture_stream || (h->capture_stream = stream_pool().take(h->cfg.device_id, StreamPool::CAPTURE)) != nullptr) &&
                       hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
             if (ok) {
-                enqueue_segmentation(h, c, h->capture_stream);
-                ok = hipStreamEndCapture(h->capture_stream, &c.graph[c.count]) == hipSuccess && c.graph[c.count] != nullptr;
+                enqueue_segmentation(h, c, h->capture_stream, pm);
+                ok = hipStreamEndCapture(h->capture_stream, &graph) == hipSuccess && graph != nullptr;
             }
-            if (ok) ok = hipGraphInstantiate(&ex, c.graph[c.count], nullptr, nullptr, 0) == hipSuccess;
+            if (ok) ok = hipGraphInstantiate(&ex, graph, nullptr, nullptr, 0) == hipSuccess;
             if (!ok) { h->graph_failed = true; ex = nullptr; (void)hipGetLastError(); }
             if (ex) { HCK(hipGraphLaunch(ex, c.stream)); return SSF_OK; }       // (the first replay still under the lock)
         }
         if (ex) { HCK(hipGraphLaunch(ex, c.stream)); return SSF_OK; }
     }
-    enqueue_segmentation(h, c, c.stream);
+    enqueue_segmentation(h, c, c.stream, pm);
     return SSF_OK;
 }
 
@@ -834,10 +849,15 @@ static int launch_batch(ssf_handle* h, ExtractCtx& c) {
             c.in.depth_format = SSF_DEPTH_F32_METRES;                      // (ingest reads the filter's float output, the raw colour)
         }
         launch_ingest(st, h->seg, c.in, c.maps, nb, c.epoch0);
+        for (int b = 0; b < nb; b++)                                       // (the pixel counts of the frames that vote)
+            if ((c.pixmask_bits >> b) & 1u) HCK(hipMemsetAsync(slab_shift(c.d_pixcnt, (size_t)b * c.maps.slab), 0, 2 * sizeof(uint32_t) * h->S, st));
         extract_rc = run_segmentation(h, c);
         if (extract_rc && !dealt) return extract_rc;
-        if (!extract_rc) launch_finalize_surfels(st, h->seg, c.maps, nb, c.frame, h->cfg.range_min, h->cfg.range_max, c.stamp0, c.d_mask, c.mask_bits,
-                                                 c.d_best, c.d_matched);
+        if (!extract_rc && c.pixmask_bits)
+            launch_finalize_surfels_pixmask(st, h->seg, c.maps, nb, c.frame, h->cfg.range_min, h->cfg.range_max, c.stamp0, c.d_mask, c.mask_bits,
+                                            c.d_best, c.d_matched, c.d_pixcnt, c.pixmask_bits);
+        else if (!extract_rc) launch_finalize_surfels(st, h->seg, c.maps, nb, c.frame, h->cfg.range_min, h->cfg.range_max, c.stamp0, c.d_mask, c.mask_bits,
+                                                      c.d_best, c.d_matched);
     }
     if (dealt) {
         // (a local failure above must not leave the other ranks waiting in their broadcasts: the group is issued regardless -- what it
@@ -884,13 +904,15 @@ static bool device_input_aligned(ssf_handle* h, const void* rgb, const void* dep
     return true;
 }
 // Add one frame to the open batch; the batch is launched when it is full (or when its first frame is needed).
-static int submit_extract(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask) {
+// pixmask: the frame's pixel mask (ssf_dynamic.h), P bytes, a device pointer when pixmask_on_device, NULL = none.
+static int submit_extract(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask,
+                          const uint8_t* pixmask = nullptr, int pixmask_on_device = 0) {
     ExtractCtx& c = h->ctx[h->open_ctx];
     if (c.launched) { h->err = "extract pipeline is full: process a submitted frame first"; return SSF_ERR_STATE; }
     if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
     const int b = c.count;
     if (b == 0) {
-        c.stamp0 = h->stamp + h->stamp_bias + (int)h->pending.size(); c.mask_bits = 0; c.epoch0 = h->extract_ordinal;
+        c.stamp0 = h->stamp + h->stamp_bias + (int)h->pending.size(); c.mask_bits = 0; c.pixmask_bits = 0; c.epoch0 = h->extract_ordinal;
         if (h->deal && h->comm) { c.deal_batch = h->deal_batches++; c.mine = (int)(c.deal_batch % (long long)h->cfg.nranks) == h->cfg.rank; }
         else c.mine = true;
     }
@@ -904,6 +926,10 @@ static int submit_extract(ssf_handle* h, const void* rgb, const void* depth, int
         c.in.rgb[b] = drgb; c.in.depth[b] = ddep;
     }
     if (mask && c.mine) { HCK(hipMemcpyAsync(slab_shift(c.d_mask, off), mask, h->S, hipMemcpyHostToDevice, c.stream)); c.mask_bits |= 1u << b; }
+    if (pixmask && c.mine) {               // (only the extracting rank votes; the peers import the confidences)
+        HCK(hipMemcpyAsync(slab_shift(c.d_pixmask, off), pixmask, P, pixmask_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
+        c.pixmask_bits |= 1u << b;
+    }
     c.count = b + 1;
     h->pending.push_back(std::make_pair(h->open_ctx, b));
     // (inside ssf_process_sequence the first two batches are smaller: seq_batch_size)
@@ -922,7 +948,7 @@ static int submit_tables(ssf_handle* h, const int32_t* label, const float* plane
     hipStream_t st = c.stream;
     const bool multi = h->ctx.size() > 1;
     if (multi && c.consumed_valid) HCK(hipStreamWaitEvent(st, c.ev_consumed, 0));
-    c.stamp0 = h->stamp + h->stamp_bias + (int)h->pending.size(); c.mask_bits = 0; c.epoch0 = h->extract_ordinal;
+    c.stamp0 = h->stamp + h->stamp_bias + (int)h->pending.size(); c.mask_bits = 0; c.pixmask_bits = 0; c.epoch0 = h->extract_ordinal;
     h->extract_ordinal++;                          // (the RANSAC epoch advances as if the frame had been extracted here)
     const size_t P = (size_t)h->cfg.width * h->cfg.height, S = (size_t)h->S;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -973,7 +999,7 @@ static int activate_oldest(ssf_handle* h) {
     ActiveFrame& a = h->active;
     a.maps = batch_slot(c.maps, fr.second); a.frame = batch_slot(c.frame, off);
     a.d_best = slab_shift(c.d_best, off); a.d_matched = slab_shift(c.d_matched, off);
-    a.ctx = &c; a.slot = fr.second;
+    a.ctx = &c; a.slot = fr.second; a.pixmask = ((c.pixmask_bits >> fr.second) & 1u) != 0;
     h->have_frame = true;
     return SSF_OK;
 }
@@ -987,8 +1013,9 @@ static int seq_flush_tail(ssf_handle* h) {
 }
 static int seq_submit(ssf_handle* h) {
     const int i = h->seq_next;
+    const uint8_t* pixmask = h->seq_pixmask ? h->seq_pixmask[i] : nullptr;
     if (h->seq_on_device || !h->seq_upload) {
-        int rc = submit_extract(h, h->seq_rgb[i], h->seq_depth[i], h->seq_on_device, nullptr);
+        int rc = submit_extract(h, h->seq_rgb[i], h->seq_depth[i], h->seq_on_device, nullptr, pixmask, h->seq_on_device);
         if (!rc) { h->seq_next++; rc = seq_flush_tail(h); }
         return rc;
     }
@@ -1004,14 +1031,14 @@ static int seq_submit(ssf_handle* h) {
     }
     h->us_wait_upload += now_us() - w0;
     const int sl = i % u.ring;                    // (its copies are already in the stream of the context it goes to)
-    int rc = submit_extract(h, u.d_rgb[sl], u.d_depth[sl], 1, nullptr);
+    int rc = submit_extract(h, u.d_rgb[sl], u.d_depth[sl], 1, nullptr, pixmask ? u.d_mask[sl] : nullptr, 1);
     if (!rc) { h->seq_next++; rc = seq_flush_tail(h); }
     return rc;
 }
-static int do_extract(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask) {
+static int do_extract(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask, const uint8_t* pixmask = nullptr) {
     if (!h->pending.empty()) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
     int rc = retire_active(h);
-    if (!rc) rc = submit_extract(h, rgb, depth, on_device, mask);
+    if (!rc) rc = submit_extract(h, rgb, depth, on_device, mask, pixmask, on_device);
     return rc ? rc : activate_oldest(h);
 }
 
@@ -1689,10 +1716,10 @@ static int process_oldest(ssf_handle* h, const float* prior, ssf_frame_result* o
     return SSF_OK;
 }
 static int process_frame_impl(ssf_handle* h, const void* rgb, const void* depth, int on_device, const float* prior,
-                              const uint8_t* mask, ssf_frame_result* out) {
+                              const uint8_t* mask, ssf_frame_result* out, const uint8_t* pixmask = nullptr) {
     if (!h->pending.empty()) { h->err = "frames are pending in the extract pipeline: use ssf_process_submitted"; return SSF_ERR_STATE; }
     int rc;
-    { TimerScope ts(h); rc = submit_extract(h, rgb, depth, on_device, mask); }
+    { TimerScope ts(h); rc = submit_extract(h, rgb, depth, on_device, mask, pixmask, on_device); }
     return rc ? rc : process_oldest(h, prior, out);
 }
 
@@ -1753,6 +1780,7 @@ void ssf_destroy(ssf_handle* h) {
         h->up->shutdown();
         for (auto q : h->up->p_rgb) if (q) (void)hipHostFree(q);
         for (auto q : h->up->p_depth) if (q) (void)hipHostFree(q);
+        for (auto q : h->up->p_mask) if (q) (void)hipHostFree(q);
         delete h->up; h->up = nullptr;
     }
     for (auto& c : h->ctx) if (c.stream) (void)hipStreamSynchronize(c.stream);
@@ -1763,6 +1791,7 @@ void ssf_destroy(ssf_handle* h) {
     if (h->p2p.region) (void)hipFree(h->p2p.region);
     for (auto& c : h->ctx) {
         for (int n = 0; n <= SSF_MAX_BATCH; n++) { if (c.exec[n]) (void)hipGraphExecDestroy(c.exec[n]); if (c.graph[n]) (void)hipGraphDestroy(c.graph[n]); }
+        for (int n = 0; n <= SSF_MAX_BATCH; n++) { if (c.exec_pm[n]) (void)hipGraphExecDestroy(c.exec_pm[n]); if (c.graph_pm[n]) (void)hipGraphDestroy(c.graph_pm[n]); }
         hipEvent_t evs[4] = {c.ev_done, c.ev_consumed, c.ev_t0, c.ev_t1};
         for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
         if (c.own_stream && c.stream) stream_pool().give(c.stream, h->cfg.device_id, c.stream_prio);          // (synchronised above)
@@ -1865,6 +1894,7 @@ int ssf_create(const ssf_config* cfg, ssf_handle** out) {
         take(f.r2, 3 * S); take(f.shape, 6 * S); take(f.dims, 2 * S); take(f.conf, S);
         take(c.d_best, S); take(c.d_matched, S); take(c.d_rgb_in, 4 * P); take(c.d_depth_in, P); take(c.d_depth_filt, P); take(c.d_mask, S);
         take(c.d_wire, 26 * S);
+        take(c.d_pixmask, P); take(c.d_pixcnt, 2 * S);
         return (off + 255) & ~(size_t)255;
     };
     size_t slab_bytes = 0;
@@ -1998,7 +2028,8 @@ int ssf_process_submitted(ssf_handle* h, const float* prior, ssf_frame_result* o
     if (!h) return SSF_ERR_INVALID_ARG;
     return process_oldest(h, prior, out);
 }
-int ssf_process_sequence(ssf_handle* h, const void* const* rgb, const void* const* depth, int n, int on_device, ssf_frame_result* out) {
+static int process_sequence_impl(ssf_handle* h, const void* const* rgb, const void* const* depth, const uint8_t* const* pixmasks, int n,
+                                 int on_device, ssf_frame_result* out) {
     if (!h || !rgb || !depth || n < 0) return SSF_ERR_INVALID_ARG;
     if (!h->pending.empty()) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
     for (int i = 0; i < n; i++) if (!rgb[i] || !depth[i]) return SSF_ERR_INVALID_ARG;
@@ -2033,15 +2064,22 @@ int ssf_process_sequence(ssf_handle* h, const void* const* rgb, const void* cons
             u->ring = std::max(window, std::min(((int)h->ctx.size() + 3) * h->batch + 2, by_bytes));
             u->device = h->cfg.device_id;
             bool ok = true;
-            u->d_rgb.assign(u->ring, nullptr); u->d_depth.assign(u->ring, nullptr);
-            for (int i = 0; i < u->ring && ok; i++) ok = dalloc(h, &u->d_rgb[i], 4 * P) && dalloc(h, &u->d_depth[i], P);
+            // (and P bytes per slot for a pixel mask, ssf_process_sequence_pixmask: allocated with the ring, never mid-sequence)
+            u->d_rgb.assign(u->ring, nullptr); u->d_depth.assign(u->ring, nullptr); u->d_mask.assign(u->ring, nullptr);
+            for (int i = 0; i < u->ring && ok; i++) ok = dalloc(h, &u->d_rgb[i], 4 * P) && dalloc(h, &u->d_depth[i], P) && dalloc(h, &u->d_mask[i], P);
             if (ok && !SSF_ENV_SET("UPLOAD_PAGEABLE")) {     // page-locked staging (optional: without it the copies go through the runtime's)
-                u->p_rgb.assign(u->ring, nullptr); u->p_depth.assign(u->ring, nullptr);
+                u->p_rgb.assign(u->ring, nullptr); u->p_depth.assign(u->ring, nullptr); u->p_mask.assign(u->ring, nullptr);
                 bool pin = true;
                 for (int i = 0; i < u->ring && pin; i++)
                     pin = hipHostMalloc((void**)&u->p_rgb[i], 4 * P, hipHostMallocDefault) == hipSuccess &&
-                          hipHostMalloc((void**)&u->p_depth[i], 4 * P, hipHostMallocDefault) == hipSuccess;
-                if (!pin) { for (auto q : u->p_rgb) if (q) (void)hipHostFree(q); for (auto q : u->p_depth) if (q) (void)hipHostFree(q); u->p_rgb.clear(); u->p_depth.clear(); (void)hipGetLastError(); }
+                          hipHostMalloc((void**)&u->p_depth[i], 4 * P, hipHostMallocDefault) == hipSuccess &&
+                          hipHostMalloc((void**)&u->p_mask[i], P, hipHostMallocDefault) == hipSuccess;
+                if (!pin) {
+                    for (auto q : u->p_rgb) if (q) (void)hipHostFree(q);
+                    for (auto q : u->p_depth) if (q) (void)hipHostFree(q);
+                    for (auto q : u->p_mask) if (q) (void)hipHostFree(q);
+                    u->p_rgb.clear(); u->p_depth.clear(); u->p_mask.clear(); (void)hipGetLastError();
+                }
             }
             for (auto& c : h->ctx) u->ctx_stream.push_back(c.stream);
             u->batch = h->batch;
@@ -2051,10 +2089,11 @@ int ssf_process_sequence(ssf_handle* h, const void* const* rgb, const void* cons
         Uploader& u = *h->up;
         u.n = n; u.rgb = rgb; u.depth = depth; u.ctx0 = h->open_ctx;
         u.rgb_bytes = color_bpp(h) * P; u.depth_bytes = depth_bpp(h) * P;
+        u.masks = pixmasks; u.mask_bytes = P;
         u.processed.store(0); u.failed.store(0); u.stop.store(0);
         u.start();
     }
-    h->seq_rgb = rgb; h->seq_depth = depth; h->seq_next = 0; h->seq_n = n; h->seq_on_device = on_device; h->seq_upload = ahead;
+    h->seq_rgb = rgb; h->seq_depth = depth; h->seq_pixmask = pixmasks; h->seq_next = 0; h->seq_n = n; h->seq_on_device = on_device; h->seq_upload = ahead;
     h->seq_batches = 0; h->seq_launches = 0;
     h->seq_t0_us = now_us();
     for (int k = 0; k < n && !rc; k++) {
@@ -2074,8 +2113,12 @@ int ssf_process_sequence(ssf_handle* h, const void* const* rgb, const void* cons
         h->up->stop.store(1);
         h->up->join();
     }
-    h->seq_rgb = nullptr; h->seq_depth = nullptr; h->seq_n = 0; h->seq_next = 0; h->seq_upload = false;
+    h->seq_rgb = nullptr; h->seq_depth = nullptr; h->seq_pixmask = nullptr; h->seq_n = 0; h->seq_next = 0; h->seq_upload = false;
+    if (h->up) h->up->masks = nullptr;
     return rc;
+}
+int ssf_process_sequence(ssf_handle* h, const void* const* rgb, const void* const* depth, int n, int on_device, ssf_frame_result* out) {
+    return process_sequence_impl(h, rgb, depth, nullptr, n, on_device, out);
 }
 int ssf_pending_frames(const ssf_handle* h) { return h ? (int)h->pending.size() : 0; }
 int ssf_pipeline_capacity(const ssf_handle* h) { return h ? (int)h->ctx.size() * h->batch : 0; }
@@ -2382,6 +2425,53 @@ int ssf_stage_extract(ssf_handle* h, const void* rgb, const void* depth, int on_
     if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
     TimerScope ts(h);
     return do_extract(h, rgb, depth, on_device, mask);
+}
+
+// ---- pixel masks (ssf_dynamic.h) ----------------------------------------------------------------------
+static int copy_map(ssf_handle* h, void* dst, const void* src, size_t bytes);
+int ssf_process_frame_pixmask(ssf_handle* h, const void* rgb, const void* depth, int on_device, const float* prior, const uint8_t* pixel_mask,
+                              ssf_frame_result* out) {
+    if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
+    if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
+    return process_frame_impl(h, rgb, depth, on_device ? 1 : 0, prior, nullptr, out, pixel_mask);
+}
+int ssf_submit_frame_pixmask(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* pixel_mask) {
+    if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
+    if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
+    TimerScope ts(h);
+    const double t0 = now_us();
+    int rc = submit_extract(h, rgb, depth, on_device ? 1 : 0, nullptr, pixel_mask, on_device ? 1 : 0);
+    h->host_us[0] += now_us() - t0;
+    return rc;
+}
+int ssf_process_sequence_pixmask(ssf_handle* h, const void* const* rgb, const void* const* depth, const uint8_t* const* pixel_masks, int n,
+                                 int on_device, ssf_frame_result* out) {
+    return process_sequence_impl(h, rgb, depth, pixel_masks, n, on_device ? 1 : 0, out);
+}
+int ssf_stage_extract_pixmask(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* pixel_mask) {
+    if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
+    if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
+    TimerScope ts(h);
+    return do_extract(h, rgb, depth, on_device ? 1 : 0, nullptr, pixel_mask);
+}
+// the vote of the current frame, recomputed on the host from the counts k_finalize_surfels<true> voted on (same integer rule)
+int ssf_get_dynamic_superpixels(ssf_handle* h, uint8_t* out, int* n_dynamic) {
+    if (!h || !out) return SSF_ERR_INVALID_ARG;
+    const ActiveFrame& a = *h->cc;
+    const size_t S = (size_t)h->S;
+    int n = 0;
+    if (a.pixmask && a.ctx) {
+        std::vector<uint32_t> cnt(2 * S);
+        const int rc = copy_map(h, cnt.data(), slab_shift(a.ctx->d_pixcnt, (size_t)a.slot * a.ctx->maps.slab), 2 * S * sizeof(uint32_t));
+        if (rc) return rc;
+        for (size_t k = 0; k < S; k++) {
+            const uint32_t total = cnt[2 * k], masked = cnt[2 * k + 1];
+            out[k] = (masked > 0u && 2ull * masked >= (unsigned long long)total) ? 1 : 0;
+            n += out[k];
+        }
+    } else std::memset(out, 0, S);
+    if (n_dynamic) *n_dynamic = n;
+    return SSF_OK;
 }
 // test hook: compact / recentre the out-of-view store now (normally done when its span runs out of room or holes pile up)
 int ssf_debug_recentre(ssf_handle* h) {

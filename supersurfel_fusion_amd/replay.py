@@ -15,7 +15,12 @@ scope: the pose prior is the previous pose.  Pre-decoded frames (np.savez archiv
 boxes without the dataset.
 
 --raw-frames hands the decoded colour and the 16-bit depth to the handle as they are (Fusion.set_input_format, include/ssf_input.h):
-the conversion happens in the kernels that load the pixels, and estimated.txt is the same, bit for bit."""
+the conversion happens in the kernels that load the pixels, and estimated.txt is the same, bit for bit.
+
+--dynamic-masks DIR hands a detector's per-pixel mask of moving objects to the handle with each frame (include/ssf_dynamic.h):
+DIR/<rgb stamp>.png (any 8-bit image; a colour one counts a pixel as masked when any channel is non-zero) or DIR/<rgb stamp>.npy
+(H x W), non-zero = dynamic.  A frame without a file has no mask.  Superpixels of which at least half the pixels are masked get
+confidence -1 and take no part in tracking or fusion."""
 import argparse
 import os
 
@@ -136,15 +141,35 @@ def tum_line(stamp, pose12):
     return " ".join([stamp] + ["%g" % v for v in list(t) + list(q)])
 
 
-def replay(fusion, frames, out_path=None, export_model=None, pipelined=False):
+def read_pixel_mask(mask_dir, stamp, shape):
+    """the pixel mask of the frame with rgb stamp `stamp` (H x W uint8, non-zero = dynamic), or None without a file"""
+    npy, png = os.path.join(mask_dir, stamp + ".npy"), os.path.join(mask_dir, stamp + ".png")
+    if os.path.exists(npy):
+        m = np.load(npy)
+    elif os.path.exists(png):
+        from PIL import Image
+        m = np.asarray(Image.open(png))
+    else:
+        return None
+    if m.ndim == 3:
+        m = m.any(axis=2)
+    if m.shape != tuple(shape):
+        raise ValueError("mask of %s is %s, the frame is %s" % (stamp, m.shape, tuple(shape)))
+    return (np.asarray(m) != 0).astype(np.uint8)
+
+
+def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
-    same, bit for bit, as with one process_frame per line."""
+    same, bit for bit, as with one process_frame per line.
+    mask_dir: per-frame pixel masks (read_pixel_mask), handed over with their frames (include/ssf_dynamic.h)."""
     lines, results = [], []
+    mask_of = (lambda stamp, depth: read_pixel_mask(mask_dir, stamp, np.shape(depth))) if mask_dir else (lambda stamp, depth: None)
     if not pipelined:
         for stamp, rgb, depth in frames:
-            r = fusion.process_frame(rgb, depth)
+            m = mask_of(stamp, depth)
+            r = fusion.process_frame(rgb, depth) if m is None else fusion.process_frame(rgb, depth, pixel_mask=m)
             results.append(r)
             lines.append(tum_line(stamp, r["pose"]))
     else:
@@ -158,8 +183,12 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False):
                     done = True
                     break
                 rgb, depth = fusion._frame(rgb, depth)
-                fusion.submit_frame(rgb, depth)           # (the copy is asynchronous: ssf.h, ssf_submit_frame)
-                held.append((rgb, depth))
+                m = mask_of(stamp, depth)
+                if m is None:
+                    fusion.submit_frame(rgb, depth)       # (the copy is asynchronous: ssf.h, ssf_submit_frame)
+                else:
+                    fusion.submit_frame(rgb, depth, pixel_mask=m)
+                held.append((rgb, depth, m))
                 stamps.append(stamp)
             if fusion.pending_frames() == 0:
                 break
@@ -272,6 +301,8 @@ def parse_args(argv=None):
     ap.add_argument("--pipelined", action="store_true", help="extract of later frames runs ahead (pipeline_depth 2, extract_batch 4)")
     ap.add_argument("--raw-frames", action="store_true",
                     help="hand the decoded colour and the uint16 depth to the handle unconverted (input format rgb8 + u16 x --depth-scale)")
+    ap.add_argument("--dynamic-masks", default=None, metavar="DIR",
+                    help="per-frame pixel masks of moving objects: DIR/<rgb stamp>.png or .npy, non-zero = dynamic; no file = no mask")
     return ap.parse_args(argv)
 
 
@@ -285,7 +316,7 @@ def main():
         f.set_input_format("rgb8", "u16", a.depth_scale)
     frames = (frames_from_npz(a.npz, a.depth_scale, a.raw_frames) if a.npz
               else frames_from_dataset(a.dataset, a.depth_scale, a.max_frames, a.raw_frames))
-    lines, res = replay(f, frames, a.out, a.export_model, pipelined=a.pipelined)
+    lines, res = replay(f, frames, a.out, a.export_model, pipelined=a.pipelined, mask_dir=a.dynamic_masks)
     print("%d frames -> %s ; %d supersurfels" % (len(lines), a.out, res[-1]["n_model"] if res else 0))
 
 
