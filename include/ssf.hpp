@@ -18,6 +18,7 @@
 #include "ssf.h"
 #include "ssf_input.h"
 #include "ssf_dynamic.h"
+#include "ssf_render.h"
 
 /* The reference's pose / matrix types (core/include/supersurfel_fusion/matrix_types.h:26-42), at GLOBAL scope as there,
  * so that the nodes' lines compile as they stand:
@@ -150,6 +151,22 @@ static_assert(sizeof(DeviceArray<float3>) == sizeof(void*) + sizeof(size_t) && s
 struct PixelMask {
     const uint8_t* data;
     explicit PixelMask(const uint8_t* d) : data(d) {}
+};
+
+/* renderModel (ssf_render.h; exported by libssf_hip.so only): the map drawn into a pinhole camera on the device.  Defaults: the
+ * handle's camera (width 0), cfg.range_min / range_max (both 0), the reference node's marker size 3 */
+struct RenderOptions {
+    int width = 0, height = 0; float fx = 0.f, fy = 0.f, cx = 0.f, cy = 0.f;
+    float z_min = 0.f, z_max = 0.f, min_conf = 0.f, splat_scale = 3.f;
+    bool visible_only = false;
+};
+/* the images of renderModel, row-major H x W (x 3), and its statistics */
+struct RenderedView {
+    int width = 0, height = 0;
+    std::vector<float> depth, color, normal;       /* depth 0 / colour 0 / normal 0 where no disc is hit */
+    std::vector<int32_t> index;                    /* logical row index (getModelHost's order), -1 where no disc is hit */
+    std::vector<uint8_t> rgb8;
+    ssf_render_stats stats;
 };
 
 class SupersurfelFusion {
@@ -291,6 +308,19 @@ public:
         processFrame(rgb.ptr<uint8_t>(), d.ptr<float>(), PixelMask(m.ptr<uint8_t>()), vo_pose);
     }
 #endif
+#if defined(CV_8UC3) && defined(CV_32FC1)
+    /* ... as images of the handle's camera: rgb CV_8UC3, depth CV_32FC1 (metres, 0 = nothing) */
+    void renderModel(const Transform3& pose, cv::Mat& rgb, cv::Mat& depth) {
+        ssf_render_params p;
+        check(ssf_render_default_params(need(), &p));
+        float v[12];
+        transform3_to_rt(pose, v);
+        p.pose = v;
+        rgb.create(height_, width_, CV_8UC3);
+        depth.create(height_, width_, CV_32FC1);
+        check(ssf_render_model(need(), &p, depth.ptr<float>(), nullptr, rgb.ptr<uint8_t>(), nullptr, nullptr, nullptr));
+    }
+#endif
     void computeSuperpixelSegIm(cv::Mat& seg_im) {                     /* CV_8UC3, supersurfel_fusion.cu:635-640 */
         seg_im.create(height_, width_, CV_8UC3);
         check(ssf_get_preview_image(need(), seg_im.ptr<uint8_t>()));
@@ -300,6 +330,24 @@ public:
         check(ssf_get_plane_depth(need(), slanted_plane_im.ptr<float>()));
     }
 #endif
+    /* The model drawn into a pinhole camera at `pose` (camera-to-map) on the device (ssf_render.h): every supersurfel is the
+     * ellipse inscribed in the reference node's marker quad, the nearest one wins.  Replaces the node's getModelHost() copy-out
+     * for its markers. */
+    void renderModel(const Transform3& pose, RenderedView& out, const RenderOptions& o = RenderOptions()) {
+        ssf_render_params p;
+        check(ssf_render_default_params(need(), &p));
+        float v[12];
+        transform3_to_rt(pose, v);
+        p.pose = v;
+        if (o.width != 0) { p.width = o.width; p.height = o.height; p.fx = o.fx; p.fy = o.fy; p.cx = o.cx; p.cy = o.cy; }
+        if (o.z_min != 0.f || o.z_max != 0.f) { p.z_min = o.z_min; p.z_max = o.z_max; }
+        p.min_conf = o.min_conf; p.splat_scale = o.splat_scale; p.visible_only = o.visible_only ? 1 : 0; p.on_device = 0;
+        const size_t n = (p.width >= 1 && p.height >= 1) ? (size_t)p.width * (size_t)p.height : 1;
+        out.width = p.width; out.height = p.height;
+        out.depth.resize(n); out.index.resize(n); out.rgb8.resize(3 * n); out.color.resize(3 * n); out.normal.resize(3 * n);
+        check(ssf_render_model(need(), &p, out.depth.data(), out.index.data(), out.rgb8.data(), out.color.data(), out.normal.data(),
+                               &out.stats));
+    }
     /* the same two images without OpenCV */
     std::vector<uint8_t> getSuperpixelSegIm() {
         std::vector<uint8_t> v((size_t)3 * width_ * height_);

@@ -78,6 +78,12 @@ DEPTH_FORMATS = {"f32": (0, 4), "u16": (1, 2)}
 # the pixel-mask entry points of include/ssf_dynamic.h: exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 DYNAMIC_MASK_SYMBOLS = ["ssf_process_frame_pixmask", "ssf_submit_frame_pixmask", "ssf_process_sequence_pixmask",
                         "ssf_stage_extract_pixmask", "ssf_get_dynamic_superpixels"]
+# the model drawn into a virtual camera (include/ssf_render.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
+RENDER_SYMBOLS = ["ssf_render_default_params", "ssf_render_model"]
+# the images of ssf_render_model, in its argument order: name, dtype, per-pixel shape
+RENDER_OUTPUTS = (("depth", np.float32, ()), ("index", np.int32, ()), ("rgb8", np.uint8, (3,)), ("color", np.float32, (3,)),
+                  ("normal", np.float32, (3,)))
+RENDER_OUTPUT_NAMES = tuple(nm for nm, _, _ in RENDER_OUTPUTS)
 
 SURFEL_FIELDS = (("positions", 3, np.float32), ("colors", 3, np.float32), ("stamps", 2, np.int32),
                  ("orientations", 9, np.float32), ("shapes", 6, np.float32),
@@ -86,6 +92,21 @@ SURFEL_FIELDS = (("positions", 3, np.float32), ("colors", 3, np.float32), ("stam
 
 class SsfError(RuntimeError):
     pass
+
+
+class SsfRenderParams(C.Structure):
+    """ssf_render_params (include/ssf_render.h)"""
+    _fields_ = [("pose", C.c_void_p), ("width", C.c_int), ("height", C.c_int)] + \
+               [(nm, C.c_float) for nm in ("fx", "fy", "cx", "cy", "z_min", "z_max", "min_conf", "splat_scale")] + \
+               [("visible_only", C.c_int), ("on_device", C.c_int)]
+
+
+class SsfRenderStats(C.Structure):
+    """ssf_render_stats (include/ssf_render.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("fragments", "pixels_filled", "rows_shown", "list_entries")]
+
+    def as_dict(self):
+        return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
 
 
 class Library:
@@ -174,6 +195,10 @@ class Library:
             L.ssf_process_sequence_pixmask.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp]
             L.ssf_stage_extract_pixmask.argtypes = [vp, vp, vp, C.c_int, vp]
             L.ssf_get_dynamic_superpixels.argtypes = [vp, vp, C.POINTER(C.c_int)]
+        self.has_render = all(hasattr(L, nm) for nm in RENDER_SYMBOLS)
+        if self.has_render:
+            L.ssf_render_default_params.argtypes = [vp, C.POINTER(SsfRenderParams)]
+            L.ssf_render_model.argtypes = [vp, C.POINTER(SsfRenderParams), vp, vp, vp, vp, vp, C.POINTER(SsfRenderStats)]
 
     @property
     def backend(self):
@@ -324,6 +349,74 @@ class Fusion:
         n = C.c_int()
         self._ck(self.L.lib.ssf_get_dynamic_superpixels(self.h, _ptr(out), C.byref(n)), "ssf_get_dynamic_superpixels")
         return out, n.value
+
+    # ---- the model drawn into a virtual camera (include/ssf_render.h) ----------------------------
+    def _need_render(self, symbol):
+        if not self.L.has_render:
+            raise SsfError("%s does not export %s: it does not render the model (include/ssf_render.h)" % (self.L.path, symbol))
+
+    def _render_params(self, pose, camera, z_range, min_conf, splat_scale, visible_only, on_device):
+        """(SsfRenderParams, the pose array it points into, (W, H)).  pose: 12 floats or a 3 x 4 [R | t] camera-to-map (None =
+        the handle's pose); camera: dict(width, height, fx, fy, cx, cy) (None = the handle's camera); z_range: (z_min, z_max)
+        (None = cfg.range_min / range_max)."""
+        p = SsfRenderParams()
+        keep = None
+        if pose is not None:
+            pose = np.asarray(pose, np.float32)
+            if pose.shape == (3, 4):
+                pose = np.concatenate([pose[:, :3].ravel(), pose[:, 3]])
+            if pose.size != 12:
+                raise SsfError("a render pose is 12 floats (R row-major, then t) or 3 x 4 [R | t], got shape %s" % (pose.shape,))
+            keep = np.ascontiguousarray(pose.ravel(), np.float32)
+            p.pose = keep.ctypes.data
+        W, H = self.W, self.H
+        if camera is not None:
+            W, H = int(camera["width"]), int(camera["height"])
+            p.width, p.height = W, H
+            p.fx, p.fy, p.cx, p.cy = (float(camera[k]) for k in ("fx", "fy", "cx", "cy"))
+        if z_range is not None:
+            p.z_min, p.z_max = float(z_range[0]), float(z_range[1])
+        p.min_conf, p.splat_scale = float(min_conf), float(splat_scale)
+        p.visible_only, p.on_device = int(bool(visible_only)), int(bool(on_device))
+        return p, keep, (W, H)
+
+    def render_model(self, pose=None, camera=None, z_range=None, min_conf=0.0, splat_scale=3.0, visible_only=False,
+                     outputs=RENDER_OUTPUT_NAMES):
+        """The model drawn into a pinhole camera (ssf_render_model): dict of the requested images (depth H x W f32, index H x W
+        i32, rgb8 / color / normal H x W x 3) and 'stats' (fragments, pixels_filled, rows_shown, list_entries)."""
+        self._need_render("ssf_render_model")
+        bad = [nm for nm in outputs if nm not in RENDER_OUTPUT_NAMES]
+        if bad:
+            raise SsfError("unknown render outputs %s (known: %s)" % (bad, ", ".join(RENDER_OUTPUT_NAMES)))
+        p, keep, (W, H) = self._render_params(pose, camera, z_range, min_conf, splat_scale, visible_only, False)
+        if W == 0:
+            W, H = self.W, self.H            # (width 0: the handle's camera)
+        if not (1 <= W <= 4096 and 1 <= H <= 4096):
+            W = H = 1                        # (the library refuses the size and writes nothing)
+        out = {nm: np.empty((H, W) + tail, dt) for nm, dt, tail in RENDER_OUTPUTS if nm in outputs}
+        st = SsfRenderStats()
+        self._ck(self.L.lib.ssf_render_model(self.h, C.byref(p), *[_ptr(out.get(nm)) for nm in RENDER_OUTPUT_NAMES], C.byref(st)),
+                 "ssf_render_model")
+        out["stats"] = st.as_dict()
+        return out
+
+    def render_model_device(self, depth=None, index=None, rgb8=None, color=None, normal=None, pose=None, camera=None,
+                            z_range=None, min_conf=0.0, splat_scale=3.0, visible_only=False):
+        """ssf_render_model into device memory: each output is None or the device address (int) of a contiguous buffer of the
+        shape and dtype render_model returns (e.g. a torch tensor's data_ptr()).  Returns the stats dict."""
+        self._need_render("ssf_render_model")
+        p, keep, _ = self._render_params(pose, camera, z_range, min_conf, splat_scale, visible_only, True)
+        ptrs = [None if a is None else C.c_void_p(int(a)) for a in (depth, index, rgb8, color, normal)]
+        st = SsfRenderStats()
+        self._ck(self.L.lib.ssf_render_model(self.h, C.byref(p), *ptrs, C.byref(st)), "ssf_render_model")
+        return st.as_dict()
+
+    def render_default_params(self):
+        """ssf_render_default_params as a dict"""
+        self._need_render("ssf_render_default_params")
+        p = SsfRenderParams()
+        self._ck(self.L.lib.ssf_render_default_params(self.h, C.byref(p)), "ssf_render_default_params")
+        return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm != "pose"}
 
     # ---- whole frame -------------------------------------------------------------------------
     def process_frame(self, rgb, depth, prior_pose=None, dynamic_mask=None, pixel_mask=None):

@@ -24,6 +24,7 @@
 #include "../../include/ssf.h"
 #include "../../include/ssf_input.h"
 #include "../../include/ssf_dynamic.h"
+#include "../../include/ssf_render.h"
 
 // SSF_EXPERIMENTS: the laboratory build (csrc/variants/lab/libssf_hip.so, `make lab`): the measurement arms and environment
 // switches behind DESIGN.md's A/B tables.  The PRODUCT library is built without it: it reads no environment variable and
@@ -371,6 +372,22 @@ void launch_move_rows(hipStream_t st, const Cam& cam, SurfelSoA vis_src, SurfelS
 // new_head (dst.live must be zero where it matters); set_span != 0: cnt->oov_head / oov_tail := the new span
 void launch_oov_compact(hipStream_t st, OovStore src, OovStore dst, int span_upper, int new_head, uint32_t* bc_oov, Counters* cnt,
                         int set_span);
+// ---- the model drawn into a virtual camera (ssf_render.h; ssf_render.hip) ------------------------------------------------
+// R = 9 floats row-major and t (camera-to-map, ssf_get_pose's layout); ntx x nty tiles of 16 x 16 pixels; k = s * s
+struct RenderCam { float R[9], t[3]; float fx, fy, cx, cy; int W, H, ntx, nty; float zmin, zmax, min_conf, s, k; };
+// the rows drawn: slots [0, nvs = 256 nbv) = the visible array (rows < n_visible), then nbo blocks of 256 slots = the
+// out-of-view span [oov_head, oov_tail) of `oov` (live flags; nbo = 0: visible rows only); nslots = 256 (nbv + nbo)
+struct RenderView { RenderCam cam; SurfelSoA vis; OovStore oov; int n_visible, nbv, nvs, oov_head, oov_tail, nbo, nslots; };
+struct RenderOut { float* depth; int32_t* index; uint8_t* rgb8; float* color; float* normal; };      // nullptr = not produced
+// prep (+ the out-of-view live scan into bc[nbo + 1]) and the exclusive scan of the tile counts: tcnt[ntiles + 1] (zeroed by the
+// caller) becomes the list offsets, cursor[ntiles] a copy; *total = list entries (64 bits)
+void launch_render_prep(hipStream_t st, const RenderView& rv, uint32_t* bc, float4* rec, uint2* rbox, int32_t* logical, uint32_t* tcnt,
+                        uint32_t* cursor, unsigned long long* total);
+void launch_render_fill(hipStream_t st, const RenderView& rv, const uint2* rbox, uint32_t* cursor, uint32_t* list);
+// stats[0..2] += fragments, filled pixels, rows shown (seen[slot] != epoch before this render)
+void launch_render_tile(hipStream_t st, const RenderView& rv, const float4* rec, const uint2* rbox, const int32_t* logical,
+                        const uint32_t* list, const uint32_t* toff, const RenderOut& out, uint32_t* seen, uint32_t epoch,
+                        unsigned long long* stats);
 // one iteration of the loop-closure registration against a frame; out40: see k_align
 void launch_align(hipStream_t st, const Cam& cam, const float* spos, const float* slab, const float* snrm, const float* sconf,
                   int n, SurfelSoA frame, const int32_t* label, const float* plane_depth, Rt T, long long* out40);

@@ -555,6 +555,17 @@ struct ActiveFrame {
 #ifndef SSF_BIN_MIN_ROWS_DEFAULT
 #define SSF_BIN_MIN_ROWS_DEFAULT 400000
 #endif
+// working buffers of ssf_render_model (ssf_render.h): allocated on first use; each group (per slot / per tile / list / staged images)
+// is grown as a whole or not at all (render_grow), freed in ssf_destroy
+struct RenderWs {
+    float4* rec = nullptr; uint2* rbox = nullptr; int32_t* logical = nullptr; uint32_t* seen = nullptr; uint32_t* bc = nullptr;
+    size_t slots = 0;                                              // per slot: record, pixel box, logical index, `seen` epoch
+    uint32_t* tcnt = nullptr; uint32_t* cursor = nullptr; size_t tiles = 0;           // per tile (+ 1): counts -> offsets, cursors
+    uint32_t* list = nullptr; size_t list_cap = 0;                                    // (tile -> slot) lists
+    unsigned long long* stats = nullptr;                          // fragments, filled pixels, rows shown, list entries
+    unsigned char* img = nullptr; size_t img_bytes = 0;           // host outputs, staged on the device
+    uint32_t epoch = 0;                                           // of the last render: seen[slot] == epoch <=> shown by it
+};
 struct ssf_handle {
     ssf_config cfg;
     int S = 0, gx = 0, gy = 0;
@@ -645,6 +656,7 @@ struct ssf_handle {
     double seq_mark_us[4][64] = {{0}}, seq_launch_us[32] = {0}, seq_launch_host_us[32] = {0}; int seq_launch_n[32] = {0}, seq_launches = 0;   // debug: entry / first ICP record / ICP done / counters back per frame, batch launches
     double seq_t0_us = 0, seq_done_us[64] = {0};      // debug: completion time of the first frames of the last ssf_process_sequence
     double host_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // debug: submit | icp loop | match+fuse | frames | extract ready at activation | first icp iteration
+    RenderWs render;                              // ssf_render_model (ssf_render.h)
 };
 static std::string g_create_err;
 
@@ -1799,6 +1811,9 @@ void ssf_destroy(ssf_handle* h) {
     if (h->capture_stream) stream_pool().give(h->capture_stream, h->cfg.device_id, StreamPool::CAPTURE);
     if (!h->guarded.empty() && !SSF_ENV_SET("GUARD_ONLY")) check_guards(h);
     for (void* p : h->allocs) (void)hipFree(p);
+    { void* rw[] = {h->render.rec, h->render.rbox, h->render.logical, h->render.seen, h->render.bc, h->render.tcnt, h->render.cursor,
+                    h->render.list, h->render.stats, h->render.img};
+      for (void* q : rw) if (q) (void)hipFree(q); }
     if (h->mb_host) (void)hipHostFree(h->mb_host);
     for (int i = 0; i < 4; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     for (auto& r : h->timer.pool_free) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -2717,6 +2732,131 @@ int ssf_get_model_device(ssf_handle* h, ssf_surfels* o, int* n) {
     o->positions = s.pos; o->colors = s.col; o->stamps = s.stamps; o->orientations = h->d_orient9; o->shapes = s.shape;
     o->dims = s.dims; o->confidences = s.conf;
     if (n) *n = h->n_model;
+    return SSF_OK;
+}
+
+// ---- the model drawn into a virtual camera (ssf_render.h; kernels in ssf_render.hip) ------------------------------------
+// all or nothing: allocate every (pointer, bytes) of `want`; only when all succeeded free the old buffers and install the new
+// ones.  A failed hipMalloc leaves its error behind in the runtime: it is cleared, so that the next frame's launch checks do
+// not report it.
+static bool render_grow(std::initializer_list<std::pair<void**, size_t>> want) {
+    std::vector<void*> got;
+    for (const auto& w : want) {
+        void* q = nullptr;
+        if (hipMalloc(&q, std::max<size_t>(w.second, 1)) != hipSuccess) {
+            for (void* g : got) (void)hipFree(g);
+            (void)hipGetLastError();
+            return false;
+        }
+        got.push_back(q);
+    }
+    size_t i = 0;
+    for (const auto& w : want) { if (*w.first) (void)hipFree(*w.first); *w.first = got[i++]; }
+    return true;
+}
+static size_t render_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int ssf_render_default_params(const ssf_handle* h, ssf_render_params* p) {
+    if (!h || !p) return SSF_ERR_INVALID_ARG;
+    std::memset(p, 0, sizeof(*p));
+    p->width = h->cam.W; p->height = h->cam.H; p->fx = h->cam.fx; p->fy = h->cam.fy; p->cx = h->cam.cx; p->cy = h->cam.cy;
+    p->z_min = h->cfg.range_min; p->z_max = h->cfg.range_max; p->min_conf = 0.0f; p->splat_scale = 3.0f;
+    return SSF_OK;
+}
+
+int ssf_render_model(ssf_handle* h, const ssf_render_params* p, float* depth, int32_t* index, uint8_t* rgb8, float* color,
+                     float* normal, ssf_render_stats* stats) {
+    if (!h || !p) return SSF_ERR_INVALID_ARG;
+    if (!depth && !index && !rgb8 && !color && !normal) { h->err = "ssf_render_model: every output is NULL"; return SSF_ERR_INVALID_ARG; }
+    if (!h->pending.empty() || h->fusing) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
+    if (h->cfg.nranks > 1) { h->err = "ssf_render_model: a sharded handle (cfg.nranks > 1) is not rendered"; return SSF_ERR_STATE; }
+    RenderCam K;
+    const Rt T = p->pose ? pose_from12(p->pose) : h->pose;
+    const float R9[9] = {T.R.r0.x, T.R.r0.y, T.R.r0.z, T.R.r1.x, T.R.r1.y, T.R.r1.z, T.R.r2.x, T.R.r2.y, T.R.r2.z};
+    std::memcpy(K.R, R9, sizeof(R9)); K.t[0] = T.t.x; K.t[1] = T.t.y; K.t[2] = T.t.z;
+    if (p->width == 0) { K.W = h->cam.W; K.H = h->cam.H; K.fx = h->cam.fx; K.fy = h->cam.fy; K.cx = h->cam.cx; K.cy = h->cam.cy; }
+    else { K.W = p->width; K.H = p->height; K.fx = p->fx; K.fy = p->fy; K.cx = p->cx; K.cy = p->cy; }
+    if (K.W < 1 || K.W > 4096 || K.H < 1 || K.H > 4096) { h->err = "ssf_render_model: the camera size must be 1..4096 x 1..4096"; return SSF_ERR_INVALID_ARG; }
+    if (!std::isfinite(K.fx) || !std::isfinite(K.fy) || K.fx == 0.0f || K.fy == 0.0f) { h->err = "ssf_render_model: fx and fy must be finite and non-zero"; return SSF_ERR_INVALID_ARG; }
+    K.zmin = p->z_min; K.zmax = p->z_max;
+    if (K.zmin == 0.0f && K.zmax == 0.0f) { K.zmin = h->cfg.range_min; K.zmax = h->cfg.range_max; }
+    if (!(K.zmin > 0.0f) || !(K.zmax > K.zmin)) { h->err = "ssf_render_model: the depth range needs 0 < z_min < z_max"; return SSF_ERR_INVALID_ARG; }
+    K.s = p->splat_scale == 0.0f ? 3.0f : p->splat_scale;
+    if (!(K.s >= 0.0f) || !std::isfinite(K.s)) { h->err = "ssf_render_model: splat_scale must be finite and >= 0"; return SSF_ERR_INVALID_ARG; }
+    K.k = K.s * K.s; K.min_conf = p->min_conf;
+    K.ntx = (K.W + 15) / 16; K.nty = (K.H + 15) / 16;
+    const int ntiles = K.ntx * K.nty;
+
+    RenderView rv;
+    rv.cam = K; rv.vis = h->model[h->mcur]; rv.oov = h->oov[h->ocur];
+    rv.n_visible = h->n_visible; rv.nbv = (h->n_visible + 255) / 256; rv.nvs = 256 * rv.nbv;
+    rv.oov_head = h->oov_head; rv.oov_tail = h->oov_tail;
+    rv.nbo = p->visible_only ? 0 : (h->oov_tail - h->oov_head + 255) / 256;
+    rv.nslots = 256 * (rv.nbv + rv.nbo);
+
+    RenderWs& w = h->render;
+    const size_t P = (size_t)K.W * K.H;
+    const size_t img_need = p->on_device ? 0 : (depth ? render_align(4 * P) : 0) + (index ? render_align(4 * P) : 0) +
+                                               (rgb8 ? render_align(3 * P) : 0) + (color ? render_align(12 * P) : 0) + (normal ? render_align(12 * P) : 0);
+    const size_t slots = std::max<size_t>(rv.nslots, 256);
+    bool ok = true;
+    if (ok && slots > w.slots) {
+        ok = render_grow({{(void**)&w.rec, 64 * slots}, {(void**)&w.rbox, 8 * slots}, {(void**)&w.logical, 4 * slots},
+                          {(void**)&w.seen, 4 * slots}, {(void**)&w.bc, 4 * (slots / 256 + 1)}});
+        if (ok) { w.slots = slots; w.epoch = 0; HCK(hipMemsetAsync(w.seen, 0, 4 * slots, h->stream)); }
+    }
+    if (ok && (size_t)ntiles + 1 > w.tiles) {
+        ok = render_grow({{(void**)&w.tcnt, 4 * ((size_t)ntiles + 1)}, {(void**)&w.cursor, 4 * ((size_t)ntiles + 1)}});
+        if (ok) w.tiles = (size_t)ntiles + 1;
+    }
+    if (ok && !w.stats) ok = render_grow({{(void**)&w.stats, 4 * sizeof(unsigned long long)}});
+    if (ok && img_need > w.img_bytes) {
+        ok = render_grow({{(void**)&w.img, img_need}});
+        if (ok) w.img_bytes = img_need;
+    }
+    if (!ok) { h->err = "ssf_render_model: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
+    if (++w.epoch == 0) { HCK(hipMemsetAsync(w.seen, 0, 4 * w.slots, h->stream)); w.epoch = 1; }
+
+    TimerScope ts(h);
+    hipStream_t st = h->stream;
+    HCK(hipMemsetAsync(w.tcnt, 0, 4 * ((size_t)ntiles + 1), st));
+    HCK(hipMemsetAsync(w.stats, 0, 4 * sizeof(unsigned long long), st));
+    launch_render_prep(st, rv, w.bc, w.rec, w.rbox, w.logical, w.tcnt, w.cursor, w.stats + 3);
+    HCK(hipGetLastError());
+    unsigned long long total = 0;
+    HCK(hipMemcpyAsync(&total, w.stats + 3, sizeof(total), hipMemcpyDeviceToHost, st));
+    HCK(hipStreamSynchronize(st));
+    if (total > 0xFFFFFFFFull) { h->err = "ssf_render_model: more than 2^32 - 1 (tile, row) list entries"; return SSF_ERR_DEVICE; }
+    if (total > w.list_cap) {
+        const size_t cap = std::min<unsigned long long>(total + total / 4, 0xFFFFFFFFull);
+        if (!render_grow({{(void**)&w.list, 4 * cap}})) {
+            h->err = "ssf_render_model: allocation of " + std::to_string(4 * cap) + " bytes for the tile lists failed";
+            return SSF_ERR_DEVICE;
+        }
+        w.list_cap = cap;
+    }
+    if (total > 0) { launch_render_fill(st, rv, w.rbox, w.cursor, w.list); HCK(hipGetLastError()); }
+    RenderOut o{depth, index, rgb8, color, normal};
+    if (!p->on_device) {
+        unsigned char* q = w.img;
+        auto carve = [&](bool want, size_t bytes) { unsigned char* r = want ? q : nullptr; if (want) q += render_align(bytes); return r; };
+        o.depth = (float*)carve(depth != nullptr, 4 * P); o.index = (int32_t*)carve(index != nullptr, 4 * P);
+        o.rgb8 = carve(rgb8 != nullptr, 3 * P); o.color = (float*)carve(color != nullptr, 12 * P); o.normal = (float*)carve(normal != nullptr, 12 * P);
+    }
+    launch_render_tile(st, rv, w.rec, w.rbox, w.logical, w.list, w.tcnt, o, w.seen, w.epoch, w.stats);
+    HCK(hipGetLastError());
+    unsigned long long st3[3] = {0, 0, 0};
+    HCK(hipMemcpyAsync(st3, w.stats, sizeof(st3), hipMemcpyDeviceToHost, st));
+    if (!p->on_device) {
+        if (depth) HCK(hipMemcpyAsync(depth, o.depth, 4 * P, hipMemcpyDeviceToHost, st));
+        if (index) HCK(hipMemcpyAsync(index, o.index, 4 * P, hipMemcpyDeviceToHost, st));
+        if (rgb8) HCK(hipMemcpyAsync(rgb8, o.rgb8, 3 * P, hipMemcpyDeviceToHost, st));
+        if (color) HCK(hipMemcpyAsync(color, o.color, 12 * P, hipMemcpyDeviceToHost, st));
+        if (normal) HCK(hipMemcpyAsync(normal, o.normal, 12 * P, hipMemcpyDeviceToHost, st));
+    }
+    HCK(hipStreamSynchronize(st));
+    if (h->cfg.profile == 1) timer_collect(&h->timer);
+    if (stats) { stats->fragments = (int64_t)st3[0]; stats->pixels_filled = (int64_t)st3[1]; stats->rows_shown = (int64_t)st3[2]; stats->list_entries = (int64_t)total; }
     return SSF_OK;
 }
 int ssf_get_frame_device(ssf_handle* h, ssf_surfels* o, int* n) {

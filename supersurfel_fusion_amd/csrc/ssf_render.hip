@@ -1,0 +1,278 @@
+// ssf_render.hip -- the fused model drawn into a virtual pinhole camera (include/ssf_render.h) on gfx950.
+//
+// Every supersurfel is a flat two-sided elliptical disc; the nearest disc along a pixel's ray wins (no blending).  What is
+// computed is pinned, operation by operation, in include/ssf_render.h (the numpy restatement: tests/render_ref.py).  How:
+//   * prep   one thread per slot of [visible rows | out-of-view span] (the two stores are read in place, never materialised):
+//            live test, culling, the camera-frame record (C, E1, E2, N, num = N.C, dims, rhs = (k dims.x) dims.y) and a
+//            CONSERVATIVE pixel box of the disc; every 16 x 16 screen tile the box touches gets one integer atomic count.
+//            A slot's number orders like the logical index ([visible | out-of-view], ssf_get_model's order), so the slot
+//            number breaks depth ties in the key; the out-of-view rows' logical index comes from an exclusive scan of their
+//            live flags (own scratch: the handle's Counters and d_bc_oov are not touched).
+//   * scan   exclusive scan of the tile counts (one workgroup); the host reads the total once and sizes the list buffer.
+//   * fill   (tile -> slot) lists with one returning atomic per list entry; the order inside a list is arbitrary.
+//   * tile   one 256-thread workgroup per tile, one pixel per thread: the tile's records are staged through LDS 256 at a time,
+//            every thread keeps the minimum key (bits(z) << 32 | slot) in registers, then resolves its outputs (winner's
+//            normal from its record, its colour gathered from the store).  The result depends on the integer minimum only:
+//            no float atomics, bitwise reproducible for any list order.
+// Statistics are exact integers: fragments and filled pixels are summed per workgroup (one 64-bit atomic each); rows_shown
+// counts the slots whose `seen` word a winner exchanges from an older render epoch to the current one.
+#include "ssf_device.hpp"
+
+namespace ssf {
+
+__device__ __forceinline__ int rlane() { return threadIdx.x & 63; }
+__device__ __forceinline__ unsigned long long rsum_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ bool finite3(float a, float b, float c) { return isfinite(a) && isfinite(b) && isfinite(c); }
+
+// slot -> the row it reads: visible slots [0, nvs) are rows of the visible array, then 256-wide blocks of the out-of-view span
+__device__ __forceinline__ void slot_source(const RenderView& rv, uint32_t s, SurfelSoA& src, size_t& row) {
+    if (s < (uint32_t)rv.nvs) { src = rv.vis; row = s; }
+    else { src = rv.oov.rows; row = (size_t)rv.oov_head + (s - (uint32_t)rv.nvs); }
+}
+
+// ---- out-of-view rows: live counts per 256-slot block, then an exclusive scan (k_render_scan) --------------------------
+__global__ __launch_bounds__(256) void k_render_oov_count(RenderView rv, uint32_t* __restrict__ bc) {
+    __shared__ int part[4];
+    const long long phys = (long long)rv.oov_head + (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool lv = phys < rv.oov_tail && rv.oov.live[phys];
+    const int k = __popcll(__ballot(lv));
+    if (rlane() == 0) part[threadIdx.x >> 6] = k;
+    __syncthreads();
+    if (threadIdx.x == 0) bc[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// exclusive scan of n counts in place (one workgroup of 1024); out[n] = the total (low 32 bits), cursor (nullable) = a copy of
+// the offsets, *total = the 64-bit total (a list longer than 2^32 - 1 entries is refused by the host, never wrapped)
+__global__ __launch_bounds__(1024) void k_render_scan(uint32_t* __restrict__ a, int n, uint32_t* __restrict__ cursor,
+                                                      unsigned long long* __restrict__ total) {
+    __shared__ unsigned long long wtot[16];
+    __shared__ unsigned long long base;
+    if (threadIdx.x == 0) base = 0;
+    __syncthreads();
+    for (int i0 = 0; i0 < n; i0 += 1024) {
+        const int i = i0 + threadIdx.x;
+        const unsigned long long c = i < n ? a[i] : 0u;
+        unsigned long long v = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const unsigned long long up = __shfl_up(v, o, 64); if (rlane() >= o) v += up; }
+        if (rlane() == 63) wtot[threadIdx.x >> 6] = v;
+        __syncthreads();
+        unsigned long long before = 0, all = 0;
+        for (int w = 0; w < 16; w++) { const unsigned long long t = wtot[w]; if (w < (int)(threadIdx.x >> 6)) before += t; all += t; }
+        const unsigned long long ex = base + before + v - c;
+        if (i < n) { a[i] = (uint32_t)ex; if (cursor) cursor[i] = (uint32_t)ex; }
+        __syncthreads();
+        if (threadIdx.x == 0) base += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { a[n] = (uint32_t)base; *total = base; }
+}
+
+// ---- prep: one thread per slot ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_render_prep(RenderView rv, const uint32_t* __restrict__ bc, float4* __restrict__ rec,
+                                                     uint2* __restrict__ rbox, int32_t* __restrict__ logical,
+                                                     uint32_t* __restrict__ tcnt) {
+    __shared__ int part[4];
+    const RenderCam& K = rv.cam;
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+    bool have; int lg = 0;
+    SurfelSoA src; size_t row;
+    slot_source(rv, s, src, row);
+    if ((int)blockIdx.x < rv.nbv) {                       // (block-uniform branch)
+        have = (int)s < rv.n_visible;
+        lg = (int)s;
+    } else {
+        have = (long long)row < (long long)rv.oov_tail && rv.oov.live[row];
+        const unsigned long long m = __ballot(have);
+        const int wv = threadIdx.x >> 6;
+        if (rlane() == 0) part[wv] = __popcll(m);
+        __syncthreads();
+        int before = 0;
+        for (int w = 0; w < wv; w++) before += part[w];
+        lg = rv.n_visible + (int)bc[blockIdx.x - rv.nbv] + before + __popcll(m & ((1ull << rlane()) - 1ull));
+    }
+    uint2 box = make_uint2(1u, 1u);                       // empty: u0 = 1 > u1 = 0
+    if (have) {
+        const float conf = src.conf[row], dx = src.dims[2 * row], dy = src.dims[2 * row + 1];
+        if (conf > K.min_conf && dx > 0.0f && dy > 0.0f && isfinite(dx) && isfinite(dy)) {
+            const float* R = K.R;
+            const float px = src.pos[3 * row] - K.t[0], py = src.pos[3 * row + 1] - K.t[1], pz = src.pos[3 * row + 2] - K.t[2];
+            // C_j = (R0j d.x + R1j d.y) + R2j d.z (contraction off: one IEEE operation each, in this order)
+            const float Cx = (R[0] * px + R[3] * py) + R[6] * pz, Cy = (R[1] * px + R[4] * py) + R[7] * pz, Cz = (R[2] * px + R[5] * py) + R[8] * pz;
+            const float* r0 = src.r0 + 3 * row; const float* r1 = src.r1 + 3 * row; const float* r2 = src.r2 + 3 * row;
+            const float a0 = r0[0], a1 = r0[1], a2 = r0[2], b0 = r1[0], b1 = r1[1], b2 = r1[2], n0 = r2[0], n1 = r2[1], n2 = r2[2];
+            const float E1x = (R[0] * a0 + R[3] * a1) + R[6] * a2, E1y = (R[1] * a0 + R[4] * a1) + R[7] * a2, E1z = (R[2] * a0 + R[5] * a1) + R[8] * a2;
+            const float E2x = (R[0] * b0 + R[3] * b1) + R[6] * b2, E2y = (R[1] * b0 + R[4] * b1) + R[7] * b2, E2z = (R[2] * b0 + R[5] * b1) + R[8] * b2;
+            const float Nx = (R[0] * n0 + R[3] * n1) + R[6] * n2, Ny = (R[1] * n0 + R[4] * n1) + R[7] * n2, Nz = (R[2] * n0 + R[5] * n1) + R[8] * n2;
+            // a non-finite C or N gives no candidate pixel at all (z is then NaN, infinite or 0: include/ssf_render.h)
+            if (finite3(Cx, Cy, Cz) && finite3(Nx, Ny, Nz)) {
+                int u0 = 0, u1 = K.W - 1, v0 = 0, v1 = K.H - 1;
+                bool cull = false;
+                if (finite3(E1x, E1y, E1z) && finite3(E2x, E2y, E2z)) {
+                    // Conservative box.  A candidate's hit point P = (z qx, z qy, z) has z_min <= P.z <= z_max, lies in the
+                    // disc's plane up to ~1e-7 z (rounding of z = num / den) and inside its ellipse up to the rounding of the
+                    // inside test: the disc's axis-aligned extent widened by 1e-3 relative + 1e-5 of |C| + hx + hy covers it,
+                    // and the projection of that box (clipped to [z_min, z_max]) plus 2 pixels covers its pixels.
+                    const float hx = K.s * sqrtf(dx), hy = K.s * sqrtf(dy);
+                    const float slack = 1e-5f * (fabsf(Cx) + fabsf(Cy) + fabsf(Cz) + hx + hy) + 1e-6f;
+                    const float ex = sqrtf((E1x * hx) * (E1x * hx) + (E2x * hy) * (E2x * hy)) * 1.001f + slack;
+                    const float ey = sqrtf((E1y * hx) * (E1y * hx) + (E2y * hy) * (E2y * hy)) * 1.001f + slack;
+                    const float ez = sqrtf((E1z * hx) * (E1z * hx) + (E2z * hy) * (E2z * hy)) * 1.001f + slack;
+                    const float z0 = fmaxf(Cz - ez, K.zmin), z1 = fminf(Cz + ez, K.zmax);
+                    if (!(z0 <= z1)) cull = true;
+                    else {
+                        const float xl = Cx - ex, xh = Cx + ex, yl = Cy - ey, yh = Cy + ey;
+                        const float sxl = fminf(xl / z0, xl / z1), sxh = fmaxf(xh / z0, xh / z1);
+                        const float syl = fminf(yl / z0, yl / z1), syh = fmaxf(yh / z0, yh / z1);
+                        const float ua = K.fx * sxl + K.cx, ub = K.fx * sxh + K.cx, va = K.fy * syl + K.cy, vb = K.fy * syh + K.cy;
+                        const float ulo = fminf(ua, ub) - 2.0f, uhi = fmaxf(ua, ub) + 2.0f, vlo = fminf(va, vb) - 2.0f, vhi = fmaxf(va, vb) + 2.0f;
+                        if (!(uhi >= 0.0f) || !(ulo <= (float)(K.W - 1)) || !(vhi >= 0.0f) || !(vlo <= (float)(K.H - 1))) cull = true;
+                        else {
+                            u0 = (int)floorf(fmaxf(ulo, 0.0f)); u1 = (int)ceilf(fminf(uhi, (float)(K.W - 1)));
+                            v0 = (int)floorf(fmaxf(vlo, 0.0f)); v1 = (int)ceilf(fminf(vhi, (float)(K.H - 1)));
+                        }
+                    }
+                }   // (a non-finite in-plane axis: the whole image, the tile pass decides)
+                if (!cull) {
+                    const float num = (Nx * Cx + Ny * Cy) + Nz * Cz;
+                    const float rhs = (K.k * dx) * dy;
+                    float4* o = rec + 4 * (size_t)s;
+                    o[0] = make_float4(Cx, Cy, Cz, num);
+                    o[1] = make_float4(E1x, E1y, E1z, dy);
+                    o[2] = make_float4(E2x, E2y, E2z, dx);
+                    o[3] = make_float4(Nx, Ny, Nz, rhs);
+                    logical[s] = lg;
+                    box = make_uint2((uint32_t)u0 | ((uint32_t)u1 << 16), (uint32_t)v0 | ((uint32_t)v1 << 16));
+                    for (int ty = v0 >> 4; ty <= (v1 >> 4); ty++)
+                        for (int tx = u0 >> 4; tx <= (u1 >> 4); tx++) atomicAdd(&tcnt[ty * K.ntx + tx], 1u);
+                }
+            }
+        }
+    }
+    if ((int)s < rv.nslots) rbox[s] = box;
+}
+
+// ---- fill: the (tile -> slot) lists -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_render_fill(RenderView rv, const uint2* __restrict__ rbox, uint32_t* __restrict__ cursor,
+                                                     uint32_t* __restrict__ list) {
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+    if ((int)s >= rv.nslots) return;
+    const uint2 b = rbox[s];
+    const int u0 = b.x & 0xFFFF, u1 = b.x >> 16, v0 = b.y & 0xFFFF, v1 = b.y >> 16;
+    if (u0 > u1 || v0 > v1) return;
+    for (int ty = v0 >> 4; ty <= (v1 >> 4); ty++)
+        for (int tx = u0 >> 4; tx <= (u1 >> 4); tx++) list[atomicAdd(&cursor[ty * rv.cam.ntx + tx], 1u)] = s;
+}
+
+// ---- tile: one workgroup per 16 x 16 tile, one pixel per thread -------------------------------------------------------
+__global__ __launch_bounds__(256) void k_render_tile(RenderView rv, const float4* __restrict__ rec, const uint2* __restrict__ rbox,
+                                                     const int32_t* __restrict__ logical, const uint32_t* __restrict__ list,
+                                                     const uint32_t* __restrict__ toff, RenderOut out, uint32_t* __restrict__ seen,
+                                                     uint32_t epoch, unsigned long long* __restrict__ stats) {
+    __shared__ float4 sr[4 * 256];
+    __shared__ uint2 sb[256];
+    __shared__ uint32_t ss[256];
+    __shared__ unsigned long long red[3][4];
+    const RenderCam& K = rv.cam;
+    const int t = blockIdx.x, tx = t % K.ntx, ty = t / K.ntx;
+    const int u = tx * 16 + (threadIdx.x & 15), v = ty * 16 + (threadIdx.x >> 4);
+    const bool inimg = u < K.W && v < K.H;
+    const float qx = ((float)u - K.cx) / K.fx, qy = ((float)v - K.cy) / K.fy;
+    const uint32_t uv = (uint32_t)u | ((uint32_t)v << 16);
+    unsigned long long best = ~0ull;
+    uint32_t frag = 0;
+    const uint32_t beg = toff[t], end = toff[t + 1];
+    for (uint32_t c0 = beg; c0 < end; c0 += 256) {
+        const int n = (int)min(256u, end - c0);
+        if ((int)threadIdx.x < n) {
+            const uint32_t s = list[c0 + threadIdx.x];
+            const float4* r = rec + 4 * (size_t)s;
+            sr[4 * threadIdx.x] = r[0]; sr[4 * threadIdx.x + 1] = r[1]; sr[4 * threadIdx.x + 2] = r[2]; sr[4 * threadIdx.x + 3] = r[3];
+            sb[threadIdx.x] = rbox[s]; ss[threadIdx.x] = s;
+        }
+        __syncthreads();
+        for (int j = 0; j < n; j++) {
+            const uint2 b = sb[j];
+            // inside the record's pixel box: u0 <= u <= u1 and v0 <= v <= v1 (16-bit fields, no borrow across them)
+            if ((uv & 0xFFFF) < (b.x & 0xFFFF) || (uv & 0xFFFF) > (b.x >> 16) || (uv >> 16) < (b.y & 0xFFFF) || (uv >> 16) > (b.y >> 16)) continue;
+            const float4 A = sr[4 * j], B = sr[4 * j + 1], Cc = sr[4 * j + 2], D = sr[4 * j + 3];
+            const float den = (D.x * qx + D.y * qy) + D.z;
+            const float z = A.w / den;
+            if (!(den != 0.0f) || !isfinite(z) || !(z >= K.zmin) || !(z <= K.zmax)) continue;
+            const float Px = z * qx, Py = z * qy;
+            const float dx = Px - A.x, dy = Py - A.y, dz = z - A.z;
+            const float a = (dx * B.x + dy * B.y) + dz * B.z;
+            const float bb = (dx * Cc.x + dy * Cc.y) + dz * Cc.z;
+            if (!((a * a) * B.w + (bb * bb) * Cc.w <= D.w)) continue;
+            frag++;
+            const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | ss[j];
+            best = key < best ? key : best;
+        }
+        __syncthreads();
+    }
+    uint32_t filled = 0, shown = 0;
+    if (inimg) {
+        const size_t p = (size_t)v * K.W + u;
+        float z = 0.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, m0 = 0.0f, m1 = 0.0f, m2 = 0.0f;
+        int32_t lg = -1;
+        if (best != ~0ull) {
+            const uint32_t s = (uint32_t)best;
+            z = __uint_as_float((uint32_t)(best >> 32));
+            const float4 D = rec[4 * (size_t)s + 3];
+            const float den = (D.x * qx + D.y * qy) + D.z;
+            m0 = den > 0.0f ? -D.x : D.x; m1 = den > 0.0f ? -D.y : D.y; m2 = den > 0.0f ? -D.z : D.z;
+            lg = logical[s];
+            SurfelSoA src; size_t row;
+            slot_source(rv, s, src, row);
+            c0 = src.col[3 * row]; c1 = src.col[3 * row + 1]; c2 = src.col[3 * row + 2];
+            filled = 1;
+            if (atomicExch(&seen[s], epoch) != epoch) shown = 1;
+        }
+        if (out.depth) out.depth[p] = z;
+        if (out.index) out.index[p] = lg;
+        if (out.color) { out.color[3 * p] = c0; out.color[3 * p + 1] = c1; out.color[3 * p + 2] = c2; }
+        if (out.rgb8) {
+            out.rgb8[3 * p] = (uint8_t)fminf(255.0f, fmaxf(0.0f, rintf(c0)));
+            out.rgb8[3 * p + 1] = (uint8_t)fminf(255.0f, fmaxf(0.0f, rintf(c1)));
+            out.rgb8[3 * p + 2] = (uint8_t)fminf(255.0f, fmaxf(0.0f, rintf(c2)));
+        }
+        if (out.normal) { out.normal[3 * p] = m0; out.normal[3 * p + 1] = m1; out.normal[3 * p + 2] = m2; }
+    }
+    const unsigned long long f = rsum_u64(frag), fl = rsum_u64(filled), sh = rsum_u64(shown);
+    if (rlane() == 0) { red[0][threadIdx.x >> 6] = f; red[1][threadIdx.x >> 6] = fl; red[2][threadIdx.x >> 6] = sh; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const unsigned long long sum = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+        if (sum) atomicAdd(&stats[threadIdx.x], sum);
+    }
+}
+
+// ---- launches -------------------------------------------------------------------------------------------------------
+void launch_render_prep(hipStream_t st, const RenderView& rv, uint32_t* bc, float4* rec, uint2* rbox, int32_t* logical, uint32_t* tcnt,
+                        uint32_t* cursor, unsigned long long* total) {
+    ScopedKernel sk("render_prep", st);
+    if (rv.nbo > 0) {
+        hipLaunchKernelGGL(k_render_oov_count, dim3(rv.nbo), dim3(256), 0, st, rv, bc);
+        hipLaunchKernelGGL(k_render_scan, dim3(1), dim3(1024), 0, st, bc, rv.nbo, (uint32_t*)nullptr, total);
+    }
+    if (rv.nbv + rv.nbo > 0)
+        hipLaunchKernelGGL(k_render_prep, dim3(rv.nbv + rv.nbo), dim3(256), 0, st, rv, bc, rec, rbox, logical, tcnt);
+    hipLaunchKernelGGL(k_render_scan, dim3(1), dim3(1024), 0, st, tcnt, rv.cam.ntx * rv.cam.nty, cursor, total);
+}
+void launch_render_fill(hipStream_t st, const RenderView& rv, const uint2* rbox, uint32_t* cursor, uint32_t* list) {
+    ScopedKernel sk("render_fill", st);
+    if (rv.nslots > 0) hipLaunchKernelGGL(k_render_fill, dim3(rv.nslots / 256), dim3(256), 0, st, rv, rbox, cursor, list);
+}
+void launch_render_tile(hipStream_t st, const RenderView& rv, const float4* rec, const uint2* rbox, const int32_t* logical,
+                        const uint32_t* list, const uint32_t* toff, const RenderOut& out, uint32_t* seen, uint32_t epoch,
+                        unsigned long long* stats) {
+    ScopedKernel sk("render_tile", st);
+    hipLaunchKernelGGL(k_render_tile, dim3(rv.cam.ntx * rv.cam.nty), dim3(256), 0, st, rv, rec, rbox, logical, list, toff, out, seen,
+                       epoch, stats);
+}
+
+}  // namespace ssf

@@ -158,13 +158,27 @@ def read_pixel_mask(mask_dir, stamp, shape):
     return (np.asarray(m) != 0).astype(np.uint8)
 
 
-def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None):
+def write_render(fusion, render_dir, stamp):
+    """the model drawn at the tracked pose with the handle's camera (include/ssf_render.h): render_dir/<stamp>_rgb.png and
+    render_dir/<stamp>_depth.npy (float32 metres, 0 = no supersurfel)"""
+    from PIL import Image
+    out = fusion.render_model(outputs=("depth", "rgb8"))
+    os.makedirs(render_dir, exist_ok=True)
+    Image.fromarray(out["rgb8"]).save(os.path.join(render_dir, stamp + "_rgb.png"))
+    np.save(os.path.join(render_dir, stamp + "_depth.npy"), out["depth"])
+    return out["stats"]
+
+
+def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
     same, bit for bit, as with one process_frame per line.
-    mask_dir: per-frame pixel masks (read_pixel_mask), handed over with their frames (include/ssf_dynamic.h)."""
+    mask_dir: per-frame pixel masks (read_pixel_mask), handed over with their frames (include/ssf_dynamic.h).
+    render_dir: after frames 0, render_every, 2 render_every, ... the model is drawn at the tracked pose (write_render); pipelined,
+    submission pauses at such a frame until it has been processed (a render needs no frame pending)."""
     lines, results = [], []
+    render_every = max(1, int(render_every))
     mask_of = (lambda stamp, depth: read_pixel_mask(mask_dir, stamp, np.shape(depth))) if mask_dir else (lambda stamp, depth: None)
     if not pipelined:
         for stamp, rgb, depth in frames:
@@ -172,11 +186,13 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             r = fusion.process_frame(rgb, depth) if m is None else fusion.process_frame(rgb, depth, pixel_mask=m)
             results.append(r)
             lines.append(tum_line(stamp, r["pose"]))
+            if render_dir and (len(lines) - 1) % render_every == 0:
+                write_render(fusion, render_dir, stamp)
     else:
         it, stamps, done = iter(frames), [], False
         held = []                                         # submitted host buffers stay alive until their frame is processed
         while True:
-            while not done and fusion.can_submit():
+            while not done and fusion.can_submit() and not (render_dir and len(stamps) > len(lines) and (len(stamps) - 1) % render_every == 0):
                 try:
                     stamp, rgb, depth = next(it)
                 except StopIteration:
@@ -196,6 +212,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             held.pop(0)
             results.append(r)
             lines.append(tum_line(stamps[len(lines)], r["pose"]))
+            if render_dir and (len(lines) - 1) % render_every == 0:
+                write_render(fusion, render_dir, stamps[len(lines) - 1])
     if out_path:
         with open(out_path, "w") as f:
             f.write("\n".join(lines) + "\n")
@@ -303,6 +321,9 @@ def parse_args(argv=None):
                     help="hand the decoded colour and the uint16 depth to the handle unconverted (input format rgb8 + u16 x --depth-scale)")
     ap.add_argument("--dynamic-masks", default=None, metavar="DIR",
                     help="per-frame pixel masks of moving objects: DIR/<rgb stamp>.png or .npy, non-zero = dynamic; no file = no mask")
+    ap.add_argument("--render-dir", default=None, metavar="DIR",
+                    help="every --render-every frames, the model drawn at the tracked pose: DIR/<stamp>_rgb.png and DIR/<stamp>_depth.npy")
+    ap.add_argument("--render-every", type=int, default=30, metavar="K")
     return ap.parse_args(argv)
 
 
@@ -316,7 +337,8 @@ def main():
         f.set_input_format("rgb8", "u16", a.depth_scale)
     frames = (frames_from_npz(a.npz, a.depth_scale, a.raw_frames) if a.npz
               else frames_from_dataset(a.dataset, a.depth_scale, a.max_frames, a.raw_frames))
-    lines, res = replay(f, frames, a.out, a.export_model, pipelined=a.pipelined, mask_dir=a.dynamic_masks)
+    lines, res = replay(f, frames, a.out, a.export_model, pipelined=a.pipelined, mask_dir=a.dynamic_masks,
+                        render_dir=a.render_dir, render_every=a.render_every)
     print("%d frames -> %s ; %d supersurfels" % (len(lines), a.out, res[-1]["n_model"] if res else 0))
 
 
