@@ -19,6 +19,7 @@
 #include "ssf_input.h"
 #include "ssf_dynamic.h"
 #include "ssf_render.h"
+#include "ssf_graph.h"
 
 /* The reference's pose / matrix types (core/include/supersurfel_fusion/matrix_types.h:26-42), at GLOBAL scope as there,
  * so that the nodes' lines compile as they stand:
@@ -167,6 +168,13 @@ struct RenderedView {
     std::vector<int32_t> index;                    /* logical row index (getModelHost's order), -1 where no disc is hit */
     std::vector<uint8_t> rgb8;
     ssf_render_stats stats;
+};
+
+/* the deformation graph's binding (ssf_graph.h): four node indices and four weights per row, in getModelHost()'s row order */
+struct GraphBinding {
+    std::vector<float> weights4;
+    std::vector<int32_t> idx4;
+    size_t size() const { return idx4.size() / 4; }
 };
 
 class SupersurfelFusion {
@@ -347,6 +355,55 @@ public:
         out.depth.resize(n); out.index.resize(n); out.rgb8.resize(3 * n); out.color.resize(3 * n); out.normal.resize(3 * n);
         check(ssf_render_model(need(), &p, out.depth.data(), out.index.data(), out.rgb8.data(), out.color.data(), out.normal.data(),
                                &out.stats));
+    }
+    /* The deformation graph of a loop closure, built and kept on the device (ssf_graph.h; exported by libssf_hip.so only): every
+     * stride-th confident row in birth order is a node, every row is bound to its four nearest nodes among the 2 * look born
+     * around its own birth.  Returns the number of nodes.  INTEGRATION.md section 2 has the call sequence. */
+    int buildDeformationGraph(int stride = 50, int look = 20, float min_conf = 0.f) {
+        ssf_graph_params p;
+        check(ssf_graph_default_params(&p));
+        p.stride = stride; p.look = look; p.min_conf = min_conf;
+        int m = 0;
+        check(ssf_graph_build(need(), &p, &m));
+        return m;
+    }
+    /* the reference's member name: the node positions in time order, for the caller's optimiser; t_init / rows (optional) get
+     * the nodes' birth stamps and model rows */
+    std::vector<float3> getNodesPositions(std::vector<int32_t>* t_init = nullptr, std::vector<int32_t>* rows = nullptr) {
+        int m = 0;
+        check(ssf_graph_info(need(), &m, nullptr, nullptr));
+        std::vector<float3> pos((size_t)m);
+        if (t_init) t_init->resize((size_t)m);
+        if (rows) rows->resize((size_t)m);
+        if (m > 0)
+            check(ssf_graph_get_nodes(need(), reinterpret_cast<float*>(pos.data()), t_init ? t_init->data() : nullptr,
+                                      rows ? rows->data() : nullptr, m));
+        return pos;
+    }
+    GraphBinding getGraphBinding() {
+        int n = 0;
+        check(ssf_graph_info(need(), nullptr, &n, nullptr));
+        GraphBinding b;
+        b.weights4.resize(4 * (size_t)n); b.idx4.resize(4 * (size_t)n);
+        check(ssf_graph_get_binding(need(), b.weights4.data(), b.idx4.data(), 0));
+        return b;
+    }
+    /* the same rule for a loop closure's constraint points (their birth stamps in t_init) */
+    GraphBinding bindPoints(const std::vector<float3>& points, const std::vector<int32_t>& t_init) {
+        if (points.size() != t_init.size()) throw std::runtime_error("bindPoints: one birth stamp per point");
+        GraphBinding b;
+        b.weights4.resize(4 * points.size()); b.idx4.resize(4 * points.size());
+        check(ssf_graph_bind_points(need(), reinterpret_cast<const float*>(points.data()), t_init.data(), (int)points.size(),
+                                    b.weights4.data(), b.idx4.data()));
+        return b;
+    }
+    /* deform the model with the optimised node transforms (one Mat33 and one translation per node, in node order) */
+    void applyGraph(const std::vector<Mat33>& rotations, const std::vector<float3>& translations) {
+        int m = 0;
+        check(ssf_graph_info(need(), &m, nullptr, nullptr));
+        if (rotations.size() != (size_t)m || translations.size() != (size_t)m)
+            throw std::runtime_error("applyGraph: one rotation and one translation per node");
+        check(ssf_graph_apply(need(), reinterpret_cast<const float*>(rotations.data()), reinterpret_cast<const float*>(translations.data())));
     }
     /* the same two images without OpenCV */
     std::vector<uint8_t> getSuperpixelSegIm() {

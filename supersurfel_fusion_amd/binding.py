@@ -80,6 +80,9 @@ DYNAMIC_MASK_SYMBOLS = ["ssf_process_frame_pixmask", "ssf_submit_frame_pixmask",
                         "ssf_stage_extract_pixmask", "ssf_get_dynamic_superpixels"]
 # the model drawn into a virtual camera (include/ssf_render.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 RENDER_SYMBOLS = ["ssf_render_default_params", "ssf_render_model"]
+# the deformation graph's nodes and per-row binding (include/ssf_graph.h): exported by the HIP product only, not part of ssf.h
+GRAPH_SYMBOLS = ["ssf_graph_default_params", "ssf_graph_build", "ssf_graph_get_nodes", "ssf_graph_get_binding",
+                 "ssf_graph_bind_points", "ssf_graph_apply", "ssf_graph_info"]
 # the images of ssf_render_model, in its argument order: name, dtype, per-pixel shape
 RENDER_OUTPUTS = (("depth", np.float32, ()), ("index", np.int32, ()), ("rgb8", np.uint8, (3,)), ("color", np.float32, (3,)),
                   ("normal", np.float32, (3,)))
@@ -107,6 +110,11 @@ class SsfRenderStats(C.Structure):
 
     def as_dict(self):
         return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
+
+
+class SsfGraphParams(C.Structure):
+    """ssf_graph_params (include/ssf_graph.h)"""
+    _fields_ = [("stride", C.c_int), ("look", C.c_int), ("min_conf", C.c_float)]
 
 
 class Library:
@@ -199,6 +207,16 @@ class Library:
         if self.has_render:
             L.ssf_render_default_params.argtypes = [vp, C.POINTER(SsfRenderParams)]
             L.ssf_render_model.argtypes = [vp, C.POINTER(SsfRenderParams), vp, vp, vp, vp, vp, C.POINTER(SsfRenderStats)]
+        self.has_graph = all(hasattr(L, nm) for nm in GRAPH_SYMBOLS)
+        if self.has_graph:
+            ip = C.POINTER(C.c_int)
+            L.ssf_graph_default_params.argtypes = [C.POINTER(SsfGraphParams)]
+            L.ssf_graph_build.argtypes = [vp, C.POINTER(SsfGraphParams), ip]
+            L.ssf_graph_get_nodes.argtypes = [vp, vp, vp, vp, C.c_int]
+            L.ssf_graph_get_binding.argtypes = [vp, vp, vp, C.c_int]
+            L.ssf_graph_bind_points.argtypes = [vp, vp, vp, C.c_int, vp, vp]
+            L.ssf_graph_apply.argtypes = [vp, vp, vp]
+            L.ssf_graph_info.argtypes = [vp, ip, ip, ip]
 
     @property
     def backend(self):
@@ -417,6 +435,80 @@ class Fusion:
         p = SsfRenderParams()
         self._ck(self.L.lib.ssf_render_default_params(self.h, C.byref(p)), "ssf_render_default_params")
         return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm != "pose"}
+
+    # ---- the deformation graph's nodes and per-row binding (include/ssf_graph.h) ------------------
+    def _need_graph(self, symbol):
+        if not self.L.has_graph:
+            raise SsfError("%s does not export %s: it does not build the deformation graph (include/ssf_graph.h, HIP product only)"
+                           % (self.L.path, symbol))
+
+    def graph_default_params(self):
+        """ssf_graph_default_params as a dict"""
+        self._need_graph("ssf_graph_default_params")
+        p = SsfGraphParams()
+        rc = self.L.lib.ssf_graph_default_params(C.byref(p))
+        if rc != 0:
+            raise SsfError("ssf_graph_default_params failed (%d)" % rc)
+        return {nm: getattr(p, nm) for nm, _ in p._fields_}
+
+    def graph_build(self, stride=50, look=20, min_conf=0.0):
+        """Sample the nodes from the model and bind every row to them on the device (ssf_graph_build); returns n_nodes."""
+        self._need_graph("ssf_graph_build")
+        p = SsfGraphParams(int(stride), int(look), float(min_conf))
+        m = C.c_int(0)
+        self._ck(self.L.lib.ssf_graph_build(self.h, C.byref(p), C.byref(m)), "ssf_graph_build")
+        return m.value
+
+    def graph_info(self):
+        """dict(n_nodes, n_rows, valid) of the resident graph"""
+        self._need_graph("ssf_graph_info")
+        m, n, v = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._ck(self.L.lib.ssf_graph_info(self.h, C.byref(m), C.byref(n), C.byref(v)), "ssf_graph_info")
+        return {"n_nodes": m.value, "n_rows": n.value, "valid": bool(v.value)}
+
+    def graph_nodes(self, capacity=None):
+        """(positions m x 3 f32, t_init m i32, rows m i32): the node table in time order (ssf_graph_get_nodes)"""
+        self._need_graph("ssf_graph_get_nodes")
+        m = self.graph_info()["n_nodes"] if capacity is None else int(capacity)
+        pos, t0, rows = np.empty((max(m, 0), 3), np.float32), np.empty(max(m, 0), np.int32), np.empty(max(m, 0), np.int32)
+        self._ck(self.L.lib.ssf_graph_get_nodes(self.h, _ptr(pos), _ptr(t0), _ptr(rows), m), "ssf_graph_get_nodes")
+        k = self.graph_info()["n_nodes"]
+        return pos[:k], t0[:k], rows[:k]
+
+    def graph_binding(self):
+        """(weights4 n x 4 f32, idx4 n x 4 i32): the resident binding of every logical row (ssf_graph_get_binding)"""
+        self._need_graph("ssf_graph_get_binding")
+        n = self.graph_info()["n_rows"]
+        w, i = np.empty((n, 4), np.float32), np.empty((n, 4), np.int32)
+        self._ck(self.L.lib.ssf_graph_get_binding(self.h, _ptr(w), _ptr(i), 0), "ssf_graph_get_binding")
+        return w, i
+
+    def graph_binding_device(self, weights4, idx4):
+        """ssf_graph_get_binding into device memory: the device addresses (int, or None) of n x 4 f32 / n x 4 i32 buffers"""
+        self._need_graph("ssf_graph_get_binding")
+        ptrs = [None if a is None else C.c_void_p(int(a)) for a in (weights4, idx4)]
+        self._ck(self.L.lib.ssf_graph_get_binding(self.h, ptrs[0], ptrs[1], 1), "ssf_graph_get_binding")
+
+    def graph_bind_points(self, points, t_init):
+        """(weights4, idx4) of n caller points (n x 3 f32, birth stamps n i32) against the resident nodes (ssf_graph_bind_points)"""
+        self._need_graph("ssf_graph_bind_points")
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        t0 = np.ascontiguousarray(t_init, np.int32).ravel()
+        if len(t0) != len(pts):
+            raise SsfError("graph_bind_points: %d points but %d stamps" % (len(pts), len(t0)))
+        n = len(pts)
+        w, i = np.empty((n, 4), np.float32), np.empty((n, 4), np.int32)
+        self._ck(self.L.lib.ssf_graph_bind_points(self.h, _ptr(pts), _ptr(t0), n, _ptr(w), _ptr(i)), "ssf_graph_bind_points")
+        return w, i
+
+    def graph_apply(self, node_rot, node_trans):
+        """Deform the model through the resident nodes and binding (ssf_graph_apply): node_rot m x 9 (or m x 3 x 3), node_trans m x 3"""
+        self._need_graph("ssf_graph_apply")
+        m = self.graph_info()["n_nodes"]
+        R, t = np.ascontiguousarray(node_rot, np.float32), np.ascontiguousarray(node_trans, np.float32)
+        if R.size != 9 * m or t.size != 3 * m:
+            raise SsfError("graph_apply: the graph has %d nodes; got %d rotation and %d translation floats" % (m, R.size, t.size))
+        self._ck(self.L.lib.ssf_graph_apply(self.h, _ptr(R), _ptr(t)), "ssf_graph_apply")
 
     # ---- whole frame -------------------------------------------------------------------------
     def process_frame(self, rgb, depth, prior_pose=None, dynamic_mask=None, pixel_mask=None):

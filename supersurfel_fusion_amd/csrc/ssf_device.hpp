@@ -25,6 +25,7 @@
 #include "../../include/ssf_input.h"
 #include "../../include/ssf_dynamic.h"
 #include "../../include/ssf_render.h"
+#include "../../include/ssf_graph.h"
 
 // SSF_EXPERIMENTS: the laboratory build (csrc/variants/lab/libssf_hip.so, `make lab`): the measurement arms and environment
 // switches behind DESIGN.md's A/B tables.  The PRODUCT library is built without it: it reads no environment variable and
@@ -388,6 +389,24 @@ void launch_render_fill(hipStream_t st, const RenderView& rv, const uint2* rbox,
 void launch_render_tile(hipStream_t st, const RenderView& rv, const float4* rec, const uint2* rbox, const int32_t* logical,
                         const uint32_t* list, const uint32_t* toff, const RenderOut& out, uint32_t* seen, uint32_t epoch,
                         unsigned long long* stats);
+// ---- the deformation graph's nodes and per-row binding (ssf_graph.h; ssf_graph.hip) ---------------------------------------
+// the rows read in place: slots [0, nvs = 256 nbv) = the visible array (rows < n_visible), then nbo blocks of 256 slots = the
+// out-of-view span [oov_head, oov_tail) of `oov` (live flags); nslots = 256 (nbv + nbo).  Slot order = logical order.
+struct GraphView { SurfelSoA vis; OovStore oov; int n_visible, nbv, nvs, oov_head, oov_tail, nbo, nslots; };
+#define GRAPH_SORT_ITEMS 2048                     // items of one workgroup of the counting sort
+// stamp[nslots], elig[nslots]; bc[nbo + 1] = exclusive scan of the out-of-view blocks' live counts; mm[4] (preset INT_MAX, INT_MIN,
+// 0, 0) = min / max stamp of the eligible rows, their number, the live rows
+void launch_graph_keys(hipStream_t st, const GraphView& gv, float min_conf, int32_t* stamp, uint8_t* elig, uint32_t* bc, int* mm);
+// stable sort of the eligible slots by (stamp - lo), `passes` 8-bit digits; cnt[256 ceil(nslots / GRAPH_SORT_ITEMS) + 1]; returns
+// which of the pairs (key_a, slot_a) = 0 / (key_b, slot_b) = 1 holds the n_elig sorted (stamp, slot) entries
+int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes, const int32_t* stamp, const uint8_t* elig, uint32_t* cnt,
+                      int32_t* key_a, uint32_t* slot_a, int32_t* key_b, uint32_t* slot_b);
+// node k = the slot order[k stride]: nodes[k] = (x, y, z, bits(t_init)), npos3 = the packed positions, nrow = the logical row
+void launch_graph_sample(hipStream_t st, const GraphView& gv, const uint32_t* bc, const uint32_t* order, int m, int stride, float4* nodes,
+                         float* npos3, int32_t* nrow);
+void launch_graph_bind(hipStream_t st, const GraphView& gv, const uint32_t* bc, const float4* nodes, int m, int look, float* w4, int32_t* i4);
+void launch_graph_bind_points(hipStream_t st, const float* pts, const int32_t* t0, int n, const float4* nodes, int m, int look, float* w4,
+                              int32_t* i4);
 // one iteration of the loop-closure registration against a frame; out40: see k_align
 void launch_align(hipStream_t st, const Cam& cam, const float* spos, const float* slab, const float* snrm, const float* sconf,
                   int n, SurfelSoA frame, const int32_t* label, const float* plane_depth, Rt T, long long* out40);

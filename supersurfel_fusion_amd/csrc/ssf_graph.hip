@@ -1,0 +1,281 @@
+// ssf_graph.hip -- the deformation graph's nodes and the per-row binding (include/ssf_graph.h) on gfx950.
+//
+// What is computed is pinned, operation by operation, in include/ssf_graph.h (the numpy restatement: tests/graph_ref.py).  How:
+//   * rows   both model stores are read in place (never materialised), one thread per SLOT of [visible rows | out-of-view
+//            span], as the render kernels do.  Slot order = logical order, so a sort that is stable over slots is stable over
+//            logical indices; an out-of-view slot's logical index = n_visible + (live rows before it): a per-256-block count,
+//            an exclusive scan (own scratch: the handle's Counters and d_bc_oov are not touched) and a ballot inside the block.
+//   * rank   k_graph_keys: per slot the birth stamp and an eligibility byte, the out-of-view live counts, and min / max /
+//            count of the eligible stamps with exact integer atomics (the result does not depend on their order).  Then a
+//            stable least-significant-digit counting sort of (stamp - min) over 8-bit digits, 1..3 passes for a span of up to
+//            2^24 (the header admits 2^20): per pass a per-workgroup digit histogram, one exclusive scan over (digit, workgroup)
+//            and a scatter whose position inside a workgroup comes from wave ballots, never from the arrival order of an
+//            atomic.  Pass 0 drops the ineligible slots, so the sorted list is dense: rank -> slot.
+//   * sample node k = the slot of rank k * stride: its position bits, stamp and logical index, as one 16-byte record
+//            (x, y, z, bits(t_init)) per node in time order plus a packed position (what k_pack_nodes reads) and the row.
+//   * bind   one thread per slot (or per caller point): lower bound over the records' stamps (from L2: 16 steps at 64 k nodes),
+//            then the window's records, the five smallest (bits(d2) << 32 | k) kept sorted in ten registers by a min / max
+//            chain, the weights, one 16-byte store each for weights4 and idx4 at the logical index.
+// No float atomics anywhere; every count is an integer.
+#include <climits>
+#include "ssf_device.hpp"
+
+namespace ssf {
+
+__device__ __forceinline__ int glane() { return threadIdx.x & 63; }
+__device__ __forceinline__ bool gfinite3(float a, float b, float c) { return isfinite(a) && isfinite(b) && isfinite(c); }
+
+// slot -> the row it reads and whether it holds a row of the model
+__device__ __forceinline__ bool graph_slot(const GraphView& gv, uint32_t s, SurfelSoA& src, size_t& row) {
+    if (s < (uint32_t)gv.nvs) { src = gv.vis; row = s; return s < (uint32_t)gv.n_visible; }
+    const long long phys = (long long)gv.oov_head + (s - (uint32_t)gv.nvs);
+    src = gv.oov.rows; row = (size_t)phys;
+    return s < (uint32_t)gv.nslots && phys < gv.oov_tail && gv.oov.live[phys] != 0;
+}
+
+// ---- keys: stamp + eligibility per slot, live counts of the out-of-view blocks, min / max / count of the eligible stamps ----
+// mm[0] = min (starts INT_MAX), mm[1] = max (starts INT_MIN), mm[2] = eligible rows, mm[3] = live rows
+__global__ __launch_bounds__(256) void k_graph_keys(GraphView gv, float min_conf, int32_t* __restrict__ stamp, uint8_t* __restrict__ elig,
+                                                    uint32_t* __restrict__ bc, int* __restrict__ mm) {
+    __shared__ int part[4][4];
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    SurfelSoA src; size_t row;
+    const bool lv = graph_slot(gv, s, src, row);
+    int t = 0; bool el = false;
+    if (lv) {
+        t = src.stamps[2 * row];
+        el = src.conf[row] > min_conf && gfinite3(src.pos[3 * row], src.pos[3 * row + 1], src.pos[3 * row + 2]);
+    }
+    stamp[s] = t; elig[s] = el ? 1 : 0;
+    int lo = el ? t : INT_MAX, hi = el ? t : INT_MIN;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o, 64)); hi = max(hi, __shfl_xor(hi, o, 64)); }
+    const int ne = __popcll(__ballot(el)), nl = __popcll(__ballot(lv));
+    if (glane() == 0) { int* p = part[threadIdx.x >> 6]; p[0] = lo; p[1] = hi; p[2] = ne; p[3] = nl; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int e = part[0][2] + part[1][2] + part[2][2] + part[3][2], l = part[0][3] + part[1][3] + part[2][3] + part[3][3];
+        if ((int)blockIdx.x >= gv.nbv) bc[blockIdx.x - gv.nbv] = (uint32_t)l;
+        if (e > 0) {
+            atomicMin(&mm[0], min(min(part[0][0], part[1][0]), min(part[2][0], part[3][0])));
+            atomicMax(&mm[1], max(max(part[0][1], part[1][1]), max(part[2][1], part[3][1])));
+            atomicAdd(&mm[2], e);
+        }
+        if (l > 0) atomicAdd(&mm[3], l);
+    }
+}
+
+// exclusive scan of n counts in place (one workgroup of 1024); a[n] = the total
+__global__ __launch_bounds__(1024) void k_graph_scan(uint32_t* __restrict__ a, int n) {
+    __shared__ uint32_t wtot[16];
+    __shared__ uint32_t base;
+    if (threadIdx.x == 0) base = 0;
+    __syncthreads();
+    for (int i0 = 0; i0 < n; i0 += 1024) {
+        const int i = i0 + threadIdx.x;
+        const uint32_t c = i < n ? a[i] : 0u;
+        uint32_t v = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(v, o, 64); if (glane() >= o) v += up; }
+        if (glane() == 63) wtot[threadIdx.x >> 6] = v;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (int w = 0; w < 16; w++) { const uint32_t t = wtot[w]; if (w < (int)(threadIdx.x >> 6)) before += t; all += t; }
+        if (i < n) a[i] = base + before + v - c;
+        __syncthreads();
+        if (threadIdx.x == 0) base += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a[n] = base;
+}
+
+// ---- one pass of the stable counting sort: GRAPH_SORT_ITEMS items per workgroup, digit = ((key - lo) >> shift) & 255 ----------
+// elig (pass 0 only): items with elig == 0 take no part; slot_in == nullptr (pass 0): the item's own index
+__global__ __launch_bounds__(256) void k_graph_hist(const int32_t* __restrict__ key, const uint8_t* __restrict__ elig, int n, int lo, int shift,
+                                                    uint32_t* __restrict__ cnt, int nb) {
+    __shared__ uint32_t hist[256];
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    const int base = blockIdx.x * GRAPH_SORT_ITEMS;
+    for (int r = 0; r < GRAPH_SORT_ITEMS / 256; r++) {
+        const int i = base + r * 256 + threadIdx.x;
+        if (i < n && (!elig || elig[i])) atomicAdd(&hist[(((uint32_t)key[i] - (uint32_t)lo) >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    cnt[(size_t)threadIdx.x * nb + blockIdx.x] = hist[threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void k_graph_scatter(const int32_t* __restrict__ key, const uint8_t* __restrict__ elig,
+                                                       const uint32_t* __restrict__ slot_in, int n, int lo, int shift,
+                                                       const uint32_t* __restrict__ cnt, int nb, int32_t* __restrict__ key_out,
+                                                       uint32_t* __restrict__ slot_out) {
+    __shared__ uint32_t run[256];
+    __shared__ uint32_t wc[4][256];
+    run[threadIdx.x] = cnt[(size_t)threadIdx.x * nb + blockIdx.x];
+#pragma unroll
+    for (int w = 0; w < 4; w++) wc[w][threadIdx.x] = 0;
+    __syncthreads();
+    const int base = blockIdx.x * GRAPH_SORT_ITEMS, wave = threadIdx.x >> 6;
+    for (int r = 0; r < GRAPH_SORT_ITEMS / 256; r++) {
+        const int i = base + r * 256 + threadIdx.x;
+        const bool on = i < n && (!elig || elig[i]);
+        const int32_t k = on ? key[i] : 0;
+        const uint32_t d = (((uint32_t)k - (uint32_t)lo) >> shift) & 255u;
+        // the lanes of this wave that hold the same digit: eight ballots; the rank inside the wave is the lanes before this one
+        unsigned long long same = __ballot(on);
+#pragma unroll
+        for (int b = 0; b < 8; b++) {
+            const bool bit = (d >> b) & 1u;
+            const unsigned long long v = __ballot(bit);
+            same &= bit ? v : ~v;
+        }
+        const uint32_t rank = (uint32_t)__popcll(same & ((1ull << glane()) - 1ull));
+        if (on && rank == 0) wc[wave][d] = (uint32_t)__popcll(same);
+        __syncthreads();
+        if (on) {
+            uint32_t off = run[d] + rank;
+            for (int w = 0; w < wave; w++) off += wc[w][d];
+            key_out[off] = k;
+            slot_out[off] = slot_in ? slot_in[i] : (uint32_t)i;
+        }
+        __syncthreads();
+        run[threadIdx.x] += (wc[0][threadIdx.x] + wc[1][threadIdx.x]) + (wc[2][threadIdx.x] + wc[3][threadIdx.x]);
+#pragma unroll
+        for (int w = 0; w < 4; w++) wc[w][threadIdx.x] = 0;
+        __syncthreads();
+    }
+}
+
+// ---- sample: node k = the slot of rank k * stride ------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_graph_sample(GraphView gv, const uint32_t* __restrict__ bc, const uint32_t* __restrict__ order,
+                                                      int m, int stride, float4* __restrict__ nodes, float* __restrict__ npos3,
+                                                      int32_t* __restrict__ nrow) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= m) return;
+    const uint32_t s = order[(size_t)k * stride];
+    SurfelSoA src; size_t row;
+    (void)graph_slot(gv, s, src, row);
+    int logical = (int)s;
+    if (s >= (uint32_t)gv.nvs) {                  // live rows of the span in front of this one
+        const uint32_t b = (s - (uint32_t)gv.nvs) >> 8;
+        const size_t first = (size_t)gv.oov_head + ((size_t)b << 8);
+        int before = 0;
+        for (size_t q = first; q < row; q++) before += gv.oov.live[q] ? 1 : 0;
+        logical = gv.n_visible + (int)bc[b] + before;
+    }
+    const float x = src.pos[3 * row], y = src.pos[3 * row + 1], z = src.pos[3 * row + 2];
+    nodes[k] = make_float4(x, y, z, __int_as_float(src.stamps[2 * row]));
+    npos3[3 * k] = x; npos3[3 * k + 1] = y; npos3[3 * k + 2] = z;
+    nrow[k] = logical;
+}
+
+// ---- bind: steps 1-6 of ssf_graph.h for one point ------------------------------------------------------------------------
+__device__ __forceinline__ void graph_bind_one(const float4* __restrict__ nodes, int m, int L, float px, float py, float pz, int t,
+                                               float4& w4, int4& i4) {
+    int a = 0, b = m;                             // the first node whose stamp >= t
+    while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (__float_as_int(nodes[mid].w) < t) a = mid + 1; else b = mid;
+    }
+    const int W = min(m, 2 * L);
+    const int lo = max(0, min(a - L, max(0, m - 2 * L)));
+    unsigned long long k0 = ~0ull, k1 = ~0ull, k2 = ~0ull, k3 = ~0ull, k4 = ~0ull;
+    for (int j = 0; j < W; j++) {
+        const float4 g = nodes[lo + j];
+        const float dx = px - g.x, dy = py - g.y, dz = pz - g.z;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        unsigned long long x = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)(lo + j), lo_k;
+        lo_k = min(k0, x); x = max(k0, x); k0 = lo_k;
+        lo_k = min(k1, x); x = max(k1, x); k1 = lo_k;
+        lo_k = min(k2, x); x = max(k2, x); k2 = lo_k;
+        lo_k = min(k3, x); x = max(k3, x); k3 = lo_k;
+        k4 = min(k4, x);
+    }
+    i4 = make_int4((int)(uint32_t)k0, (int)(uint32_t)k1, (int)(uint32_t)k2, (int)(uint32_t)k3);
+    const float e0 = sqrtf(__uint_as_float((uint32_t)(k0 >> 32))), e1 = sqrtf(__uint_as_float((uint32_t)(k1 >> 32)));
+    const float e2 = sqrtf(__uint_as_float((uint32_t)(k2 >> 32))), e3 = sqrtf(__uint_as_float((uint32_t)(k3 >> 32)));
+    const float dmax = sqrtf(__uint_as_float((uint32_t)(k4 >> 32)));
+    const float r0 = 1.0f - e0 / dmax, r1 = 1.0f - e1 / dmax, r2 = 1.0f - e2 / dmax, r3 = 1.0f - e3 / dmax;
+    const float w0 = r0 * r0, w1 = r1 * r1, w2 = r2 * r2, w3 = r3 * r3;
+    const float s = ((w0 + w1) + w2) + w3;
+    const bool fin = gfinite3(px, py, pz);
+    if (dmax == 0.0f || !(s > 0.0f) || !fin) {
+        w4 = make_float4(0.25f, 0.25f, 0.25f, 0.25f);
+        if (!fin) i4 = make_int4(lo, lo + 1, lo + 2, lo + 3);
+    } else {
+        w4 = make_float4(w0 / s, w1 / s, w2 / s, w3 / s);
+    }
+}
+
+// every logical row of the model: one thread per slot; bc = the exclusive scan of the out-of-view blocks' live counts
+__global__ __launch_bounds__(256) void k_graph_bind(GraphView gv, const uint32_t* __restrict__ bc, const float4* __restrict__ nodes, int m,
+                                                    int L, float4* __restrict__ w4, int4* __restrict__ i4) {
+    __shared__ int wl[4];
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    SurfelSoA src; size_t row;
+    const bool lv = graph_slot(gv, s, src, row);
+    int logical = (int)s;
+    if ((int)blockIdx.x >= gv.nbv) {              // (uniform per workgroup)
+        const unsigned long long bal = __ballot(lv);
+        if (glane() == 0) wl[threadIdx.x >> 6] = __popcll(bal);
+        __syncthreads();
+        int before = __popcll(bal & ((1ull << glane()) - 1ull));
+        for (int w = 0; w < (int)(threadIdx.x >> 6); w++) before += wl[w];
+        logical = gv.n_visible + (int)bc[blockIdx.x - gv.nbv] + before;
+    }
+    if (!lv) return;
+    float4 w; int4 i;
+    graph_bind_one(nodes, m, L, src.pos[3 * row], src.pos[3 * row + 1], src.pos[3 * row + 2], src.stamps[2 * row], w, i);
+    w4[logical] = w; i4[logical] = i;
+}
+
+// n caller points against the same nodes
+__global__ __launch_bounds__(256) void k_graph_bind_points(const float* __restrict__ pts, const int32_t* __restrict__ t0, int n,
+                                                           const float4* __restrict__ nodes, int m, int L, float4* __restrict__ w4,
+                                                           int4* __restrict__ i4) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    float4 w; int4 i;
+    graph_bind_one(nodes, m, L, pts[3 * (size_t)p], pts[3 * (size_t)p + 1], pts[3 * (size_t)p + 2], t0[p], w, i);
+    w4[p] = w; i4[p] = i;
+}
+
+// ---- launches ----------------------------------------------------------------------------------------------------------
+void launch_graph_keys(hipStream_t st, const GraphView& gv, float min_conf, int32_t* stamp, uint8_t* elig, uint32_t* bc, int* mm) {
+    ScopedKernel sk("graph_rank", st);
+    hipLaunchKernelGGL(k_graph_keys, dim3(gv.nbv + gv.nbo), dim3(256), 0, st, gv, min_conf, stamp, elig, bc, mm);
+    if (gv.nbo > 0) hipLaunchKernelGGL(k_graph_scan, dim3(1), dim3(1024), 0, st, bc, gv.nbo);
+}
+int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes, const int32_t* stamp, const uint8_t* elig, uint32_t* cnt,
+                      int32_t* key_a, uint32_t* slot_a, int32_t* key_b, uint32_t* slot_b) {
+    ScopedKernel sk("graph_rank", st);
+    const int32_t* kin = stamp; const uint32_t* sin = nullptr; const uint8_t* el = elig;
+    int n = nslots, out = 0;
+    for (int p = 0; p < passes; p++) {
+        const int nb = (n + GRAPH_SORT_ITEMS - 1) / GRAPH_SORT_ITEMS;
+        int32_t* kout = out == 0 ? key_a : key_b; uint32_t* sout = out == 0 ? slot_a : slot_b;
+        hipLaunchKernelGGL(k_graph_hist, dim3(nb), dim3(256), 0, st, kin, el, n, lo, 8 * p, cnt, nb);
+        hipLaunchKernelGGL(k_graph_scan, dim3(1), dim3(1024), 0, st, cnt, 256 * nb);
+        hipLaunchKernelGGL(k_graph_scatter, dim3(nb), dim3(256), 0, st, kin, el, sin, n, lo, 8 * p, cnt, nb, kout, sout);
+        kin = kout; sin = sout; el = nullptr; n = n_elig; out ^= 1;
+    }
+    return out ^ 1;                               // which pair holds the sorted list: 0 = a, 1 = b
+}
+void launch_graph_sample(hipStream_t st, const GraphView& gv, const uint32_t* bc, const uint32_t* order, int m, int stride, float4* nodes,
+                         float* npos3, int32_t* nrow) {
+    ScopedKernel sk("graph_sample", st);
+    hipLaunchKernelGGL(k_graph_sample, dim3((m + 255) / 256), dim3(256), 0, st, gv, bc, order, m, stride, nodes, npos3, nrow);
+}
+void launch_graph_bind(hipStream_t st, const GraphView& gv, const uint32_t* bc, const float4* nodes, int m, int look, float* w4, int32_t* i4) {
+    ScopedKernel sk("graph_bind", st);
+    hipLaunchKernelGGL(k_graph_bind, dim3(gv.nbv + gv.nbo), dim3(256), 0, st, gv, bc, nodes, m, look, reinterpret_cast<float4*>(w4),
+                       reinterpret_cast<int4*>(i4));
+}
+void launch_graph_bind_points(hipStream_t st, const float* pts, const int32_t* t0, int n, const float4* nodes, int m, int look, float* w4,
+                              int32_t* i4) {
+    ScopedKernel sk("graph_bind", st);
+    hipLaunchKernelGGL(k_graph_bind_points, dim3((n + 255) / 256), dim3(256), 0, st, pts, t0, n, nodes, m, look,
+                       reinterpret_cast<float4*>(w4), reinterpret_cast<int4*>(i4));
+}
+
+}  // namespace ssf

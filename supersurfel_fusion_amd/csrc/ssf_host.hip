@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
+#include <climits>
 #include <chrono>
 #include <deque>
 #include <cmath>
@@ -566,6 +567,15 @@ struct RenderWs {
     unsigned char* img = nullptr; size_t img_bytes = 0;           // host outputs, staged on the device
     uint32_t epoch = 0;                                           // of the last render: seen[slot] == epoch <=> shown by it
 };
+// ssf_graph_build (ssf_graph.h): the resident node table and binding, and the working buffers of the time-order sort.  Allocated
+// on first use; each group (per slot / per node) is grown as a whole or not at all (render_grow), freed in ssf_destroy
+struct GraphWs {
+    int32_t* stamp = nullptr; uint8_t* elig = nullptr; int32_t* key_a = nullptr; int32_t* key_b = nullptr;
+    uint32_t* slot_a = nullptr; uint32_t* slot_b = nullptr; uint32_t* cnt = nullptr; uint32_t* bc = nullptr;
+    float* w4 = nullptr; int32_t* idx4 = nullptr; int* mm = nullptr; size_t slots = 0;       // per slot; w4 / idx4 per logical row
+    float4* nodes = nullptr; float* npos3 = nullptr; int32_t* nrow = nullptr; size_t node_cap = 0;   // per node, in time order
+    int m = 0, rows = 0, look = 0; bool built = false; unsigned long long gen = 0;          // valid <=> built && gen == h->model_gen
+};
 struct ssf_handle {
     ssf_config cfg;
     int S = 0, gx = 0, gy = 0;
@@ -657,6 +667,8 @@ struct ssf_handle {
     double seq_t0_us = 0, seq_done_us[64] = {0};      // debug: completion time of the first frames of the last ssf_process_sequence
     double host_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // debug: submit | icp loop | match+fuse | frames | extract ready at activation | first icp iteration
     RenderWs render;                              // ssf_render_model (ssf_render.h)
+    GraphWs graph;                                // ssf_graph_* (ssf_graph.h)
+    unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense)
 };
 static std::string g_create_err;
 
@@ -1244,6 +1256,7 @@ static int materialise(ssf_handle* h) {
 // the stores <- h->dense (n rows, the first n_visible of them visible); also resets the device counters
 static int store_from_dense(ssf_handle* h, int n, int n_visible) {
     h->ahead.valid = false;                       // the model is replaced: a record accumulated ahead is stale
+    h->model_gen++;
     int rc = copy_soa(h, h->model[h->mcur], h->dense, (size_t)n_visible);
     if (rc) return rc;
     OovStore& o = h->oov[h->ocur];
@@ -1335,6 +1348,7 @@ static int fuse_begin(ssf_handle* h, int migrate) {
     }
     HCK(hipGetLastError());
     h->fusing = true;
+    h->model_gen++;
     return SSF_OK;
 }
 static int fuse_end(ssf_handle* h, const int32_t* d_table, ssf_frame_result* out) {
@@ -1814,6 +1828,9 @@ void ssf_destroy(ssf_handle* h) {
     { void* rw[] = {h->render.rec, h->render.rbox, h->render.logical, h->render.seen, h->render.bc, h->render.tcnt, h->render.cursor,
                     h->render.list, h->render.stats, h->render.img};
       for (void* q : rw) if (q) (void)hipFree(q); }
+    { GraphWs& g = h->graph;
+      void* gw[] = {g.stamp, g.elig, g.key_a, g.key_b, g.slot_a, g.slot_b, g.cnt, g.bc, g.w4, g.idx4, g.mm, g.nodes, g.npos3, g.nrow};
+      for (void* q : gw) if (q) (void)hipFree(q); }
     if (h->mb_host) (void)hipHostFree(h->mb_host);
     for (int i = 0; i < 4; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     for (auto& r : h->timer.pool_free) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -2908,6 +2925,18 @@ int ssf_export_model_txt(ssf_handle* h, const char* path) {
     return SSF_OK;
 }
 
+// the shared part of ssf_apply_deformation and ssf_graph_apply: k_pack_nodes + k_deformation on the dense logical view (weights are
+// per logical row) with device arrays, then the split back into the two stores
+static int deform_dense(ssf_handle* h, int m, const float* d_np, const float* d_nr, const float* d_nt, float* d_nodes, const float* d_w,
+                        const int32_t* d_i) {
+    hipStream_t st = h->stream;
+    { int rc = materialise(h); if (rc) return rc; }
+    { TimerScope ts(h); launch_deformation(st, h->dense, h->n_model, m, d_np, d_nr, d_nt, d_nodes, d_w, d_i); }
+    { int rc = store_from_dense(h, h->n_model, h->n_visible); if (rc) return rc; }
+    HCK(hipStreamSynchronize(st));
+    if (h->cfg.profile == 1) timer_collect(&h->timer);
+    return SSF_OK;
+}
 int ssf_apply_deformation(ssf_handle* h, const float* np, const float* nr, const float* nt, int m, const float* w4, const int32_t* idx4) {
     if (!h || !np || !nr || !nt || !w4 || !idx4 || m <= 0) return SSF_ERR_INVALID_ARG;
     drop_shard_sizes(h);
@@ -2925,13 +2954,162 @@ int ssf_apply_deformation(ssf_handle* h, const float* np, const float* nr, const
     HCK(hipMemcpyAsync(d_nt, nt, 12 * (size_t)m, hipMemcpyHostToDevice, st));
     HCK(hipMemcpyAsync(d_w, w4, 16 * n, hipMemcpyHostToDevice, st));
     HCK(hipMemcpyAsync(d_i, idx4, 16 * n, hipMemcpyHostToDevice, st));
-    // applied to the dense logical view (weights are per logical row), then split back into the two stores
-    { int rc = materialise(h); if (rc) return rc; }
-    { TimerScope ts(h); launch_deformation(st, h->dense, (int)n, m, d_np, d_nr, d_nt, d_nodes, d_w, d_i); }
-    { int rc = store_from_dense(h, h->n_model, h->n_visible); if (rc) return rc; }
+    return deform_dense(h, m, d_np, d_nr, d_nt, d_nodes, d_w, d_i);
+}
+
+// ---- the deformation graph's nodes and per-row binding (ssf_graph.h; kernels in ssf_graph.hip) ----------------------------
+int ssf_graph_default_params(ssf_graph_params* p) {
+    if (!p) return SSF_ERR_INVALID_ARG;
+    p->stride = 50; p->look = 20; p->min_conf = 0.0f;
+    return SSF_OK;
+}
+static bool graph_valid(const ssf_handle* h) { return h->graph.built && h->graph.gen == h->model_gen; }
+// the refusals every call that uses the resident graph shares
+static int graph_usable(ssf_handle* h, const char* who) {
+    if (!h->pending.empty() || h->fusing) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
+    if (h->cfg.nranks > 1) { h->err = std::string(who) + ": a sharded handle (cfg.nranks > 1) has no deformation graph"; return SSF_ERR_STATE; }
+    if (!h->graph.built) { h->err = std::string(who) + ": no graph has been built (ssf_graph_build)"; return SSF_ERR_STATE; }
+    if (!graph_valid(h)) { h->err = std::string(who) + ": graph is stale: build it again"; return SSF_ERR_STATE; }
+    return SSF_OK;
+}
+int ssf_graph_build(ssf_handle* h, const ssf_graph_params* p, int* n_nodes) {
+    if (!h || !p) return SSF_ERR_INVALID_ARG;
+    if (p->stride < 1 || p->look < 3 || !std::isfinite(p->min_conf)) {
+        h->err = "ssf_graph_build: needs stride >= 1, look >= 3 and a finite min_conf"; return SSF_ERR_INVALID_ARG;
+    }
+    if (!h->pending.empty() || h->fusing) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
+    if (h->cfg.nranks > 1) { h->err = "ssf_graph_build: a sharded handle (cfg.nranks > 1) has no deformation graph"; return SSF_ERR_STATE; }
+    GraphWs& g = h->graph;
+    g.built = false;                              // whatever happens below, no half-built graph is kept
+    if (h->n_model <= 0) { h->err = "ssf_graph_build: the model is empty"; return SSF_ERR_STATE; }
+
+    GraphView gv;
+    gv.vis = h->model[h->mcur]; gv.oov = h->oov[h->ocur];
+    gv.n_visible = h->n_visible; gv.nbv = (h->n_visible + 255) / 256; gv.nvs = 256 * gv.nbv;
+    gv.oov_head = h->oov_head; gv.oov_tail = h->oov_tail;
+    gv.nbo = (h->oov_tail - h->oov_head + 255) / 256;
+    gv.nslots = 256 * (gv.nbv + gv.nbo);
+    const size_t slots = (size_t)gv.nslots;       // (>= n_model > 0: every row has a slot)
+    if (slots > g.slots) {
+        const size_t nb = (slots + GRAPH_SORT_ITEMS - 1) / GRAPH_SORT_ITEMS;
+        if (!render_grow({{(void**)&g.stamp, 4 * slots}, {(void**)&g.elig, slots}, {(void**)&g.key_a, 4 * slots}, {(void**)&g.key_b, 4 * slots},
+                          {(void**)&g.slot_a, 4 * slots}, {(void**)&g.slot_b, 4 * slots}, {(void**)&g.cnt, 4 * (256 * nb + 1)},
+                          {(void**)&g.bc, 4 * (slots / 256 + 1)}, {(void**)&g.w4, 16 * slots}, {(void**)&g.idx4, 16 * slots},
+                          {(void**)&g.mm, 4 * sizeof(int)}})) {
+            h->err = "ssf_graph_build: allocation of the working buffers failed"; return SSF_ERR_DEVICE;
+        }
+        g.slots = slots;
+    }
+    TimerScope ts(h);
+    hipStream_t st = h->stream;
+    const int mm0[4] = {INT_MAX, INT_MIN, 0, 0};
+    int mm[4] = {0, 0, 0, 0};
+    HCK(hipMemcpyAsync(g.mm, mm0, sizeof(mm0), hipMemcpyHostToDevice, st));
+    launch_graph_keys(st, gv, p->min_conf, g.stamp, g.elig, g.bc, g.mm);
+    HCK(hipGetLastError());
+    HCK(hipMemcpyAsync(mm, g.mm, sizeof(mm), hipMemcpyDeviceToHost, st));
+    HCK(hipStreamSynchronize(st));
+    if (mm[3] != h->n_model) { h->err = "ssf_graph_build: the stores hold " + std::to_string(mm[3]) + " rows, the handle counts " + std::to_string(h->n_model); return SSF_ERR_DEVICE; }
+    const int n_elig = mm[2];
+    const long long m64 = ((long long)n_elig + p->stride - 1) / p->stride;
+    if (m64 < 5) {
+        h->err = "ssf_graph_build: " + std::to_string(m64) + " nodes (" + std::to_string(n_elig) + " eligible rows, stride " +
+                 std::to_string(p->stride) + "); a graph needs at least 5";
+        if (h->cfg.profile == 1) timer_collect(&h->timer);
+        return SSF_ERR_STATE;
+    }
+    const long long span = (long long)mm[1] - (long long)mm[0];
+    if (span >= SSF_GRAPH_MAX_STAMP_SPAN) {
+        h->err = "ssf_graph_build: the eligible rows' birth stamps span " + std::to_string(span) + " frames; at most " +
+                 std::to_string(SSF_GRAPH_MAX_STAMP_SPAN - 1) + " are sorted";
+        if (h->cfg.profile == 1) timer_collect(&h->timer);
+        return SSF_ERR_STATE;
+    }
+    const int m = (int)m64;
+    if ((size_t)m > g.node_cap) {
+        const size_t cap = (size_t)m + (size_t)m / 4;
+        if (!render_grow({{(void**)&g.nodes, 16 * cap}, {(void**)&g.npos3, 12 * cap}, {(void**)&g.nrow, 4 * cap}})) {
+            h->err = "ssf_graph_build: allocation of the node table failed"; return SSF_ERR_DEVICE;
+        }
+        g.node_cap = cap;
+    }
+    const int passes = span < 256 ? 1 : span < 65536 ? 2 : 3;
+    const int which = launch_graph_sort(st, gv.nslots, n_elig, mm[0], passes, g.stamp, g.elig, g.cnt, g.key_a, g.slot_a, g.key_b, g.slot_b);
+    HCK(hipGetLastError());
+    launch_graph_sample(st, gv, g.bc, which == 0 ? g.slot_a : g.slot_b, m, p->stride, g.nodes, g.npos3, g.nrow);
+    HCK(hipGetLastError());
+    launch_graph_bind(st, gv, g.bc, g.nodes, m, p->look, g.w4, g.idx4);
+    HCK(hipGetLastError());
+    HCK(hipStreamSynchronize(st));
+    if (h->cfg.profile == 1) timer_collect(&h->timer);
+    g.m = m; g.rows = h->n_model; g.look = p->look; g.gen = h->model_gen; g.built = true;
+    if (n_nodes) *n_nodes = m;
+    return SSF_OK;
+}
+int ssf_graph_info(ssf_handle* h, int* n_nodes, int* n_rows, int* valid) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    if (n_nodes) *n_nodes = h->graph.built ? h->graph.m : 0;
+    if (n_rows) *n_rows = h->graph.built ? h->graph.rows : 0;
+    if (valid) *valid = graph_valid(h) ? 1 : 0;
+    return SSF_OK;
+}
+int ssf_graph_get_nodes(ssf_handle* h, float* positions, int32_t* t_init, int32_t* rows, int capacity) {
+    if (!h || (!positions && !t_init && !rows)) return SSF_ERR_INVALID_ARG;
+    const GraphWs& g = h->graph;
+    if (!g.built) { h->err = "ssf_graph_get_nodes: no graph has been built (ssf_graph_build)"; return SSF_ERR_STATE; }
+    if (capacity < g.m) { h->err = "ssf_graph_get_nodes: " + std::to_string(g.m) + " nodes, room for " + std::to_string(capacity); return SSF_ERR_CAPACITY; }
+    hipStream_t st = h->stream;
+    const size_t m = g.m;
+    std::vector<float> rec;
+    if (positions) HCK(hipMemcpyAsync(positions, g.npos3, 12 * m, hipMemcpyDeviceToHost, st));
+    if (rows) HCK(hipMemcpyAsync(rows, g.nrow, 4 * m, hipMemcpyDeviceToHost, st));
+    if (t_init) { rec.resize(4 * m); HCK(hipMemcpyAsync(rec.data(), g.nodes, 16 * m, hipMemcpyDeviceToHost, st)); }
+    HCK(hipStreamSynchronize(st));
+    if (t_init) for (size_t k = 0; k < m; k++) std::memcpy(&t_init[k], &rec[4 * k + 3], 4);
+    return SSF_OK;
+}
+int ssf_graph_get_binding(ssf_handle* h, float* weights4, int32_t* idx4, int on_device) {
+    if (!h || (!weights4 && !idx4)) return SSF_ERR_INVALID_ARG;
+    { int rc = graph_usable(h, "ssf_graph_get_binding"); if (rc) return rc; }
+    const GraphWs& g = h->graph;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (weights4) HCK(hipMemcpyAsync(weights4, g.w4, 16 * (size_t)g.rows, kind, h->stream));
+    if (idx4) HCK(hipMemcpyAsync(idx4, g.idx4, 16 * (size_t)g.rows, kind, h->stream));
+    HCK(hipStreamSynchronize(h->stream));
+    return SSF_OK;
+}
+int ssf_graph_bind_points(ssf_handle* h, const float* points, const int32_t* t_init, int n, float* weights4, int32_t* idx4) {
+    if (!h || !points || !t_init || !weights4 || !idx4 || n < 0) return SSF_ERR_INVALID_ARG;
+    { int rc = graph_usable(h, "ssf_graph_bind_points"); if (rc) return rc; }
+    if (n == 0) return SSF_OK;
+    const GraphWs& g = h->graph;
+    float *d_p, *d_w; int32_t *d_t, *d_i;
+    DevTemps tmp;
+    HCK(tmp.take(&d_p, 12 * (size_t)n)); HCK(tmp.take(&d_t, 4 * (size_t)n)); HCK(tmp.take(&d_w, 16 * (size_t)n)); HCK(tmp.take(&d_i, 16 * (size_t)n));
+    hipStream_t st = h->stream;
+    HCK(hipMemcpyAsync(d_p, points, 12 * (size_t)n, hipMemcpyHostToDevice, st));
+    HCK(hipMemcpyAsync(d_t, t_init, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    { TimerScope ts(h); launch_graph_bind_points(st, d_p, d_t, n, g.nodes, g.m, g.look, d_w, d_i); }
+    HCK(hipGetLastError());
+    HCK(hipMemcpyAsync(weights4, d_w, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HCK(hipMemcpyAsync(idx4, d_i, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
     HCK(hipStreamSynchronize(st));
     if (h->cfg.profile == 1) timer_collect(&h->timer);
     return SSF_OK;
+}
+int ssf_graph_apply(ssf_handle* h, const float* nr, const float* nt) {
+    if (!h || !nr || !nt) return SSF_ERR_INVALID_ARG;
+    { int rc = graph_usable(h, "ssf_graph_apply"); if (rc) return rc; }
+    drop_shard_sizes(h);
+    h->ahead.valid = false;
+    const GraphWs& g = h->graph;
+    const size_t m = g.m;
+    float *d_nr, *d_nt, *d_nodes;
+    DevTemps tmp;
+    HCK(tmp.take(&d_nr, 36 * m)); HCK(tmp.take(&d_nt, 12 * m)); HCK(tmp.take(&d_nodes, 64 * m));
+    HCK(hipMemcpyAsync(d_nr, nr, 36 * m, hipMemcpyHostToDevice, h->stream));
+    HCK(hipMemcpyAsync(d_nt, nt, 12 * m, hipMemcpyHostToDevice, h->stream));
+    return deform_dense(h, g.m, g.npos3, d_nr, d_nt, d_nodes, g.w4, g.idx4);
 }
 
 // ---- re-homing of a sharded map (see ssf.h): rows moved by ssf_apply_deformation go to the rank that owns their tile ----

@@ -1,0 +1,178 @@
+"""The deformation graph's nodes and binding (include/ssf_graph.h) without a GPU: who exports the entry points, the header on its
+own, the C++ surface, and properties of the numpy restatement the GPU tests compare against (tests/graph_ref.py)."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import graph_ref as gr
+from conftest import ROOT
+from supersurfel_fusion_amd import binding, synthetic
+
+INCLUDE = os.path.join(ROOT, "include")
+CPP = os.path.join(ROOT, "tests", "cpp")
+f32 = np.float32
+
+
+def exported(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", path], stdout=subprocess.PIPE, text=True, check=True).stdout
+    return {l.split()[-1] for l in out.splitlines() if l.strip()}
+
+
+def room(n=60000, seed=3, frames=600, dead=0.05):
+    """seeded rows of the synthetic room, born along a sweep over `frames` stamps, a share of them not eligible"""
+    m = synthetic.seed_model(n)
+    pos = np.ascontiguousarray(m["positions"], f32).reshape(n, 3)
+    rng = np.random.default_rng(seed)
+    az = np.arctan2(pos[:, 2], pos[:, 0])
+    t0 = ((az + np.pi) / (2 * np.pi) * frames + rng.integers(0, 30, n)).astype(np.int32)
+    conf = np.where(rng.random(n) > dead, f32(3000), f32(0)).astype(f32)
+    return pos, t0, conf
+
+
+def test_the_header_declares_exactly_the_symbols_the_binding_lists():
+    txt = open(os.path.join(INCLUDE, "ssf_graph.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    declared = set(re.findall(r"\b(ssf_graph_[a-z_]+)\s*\(", code))
+    assert declared == set(binding.GRAPH_SYMBOLS)
+
+
+def test_the_graph_symbols_stay_out_of_ssf_h():
+    for nm in binding.GRAPH_SYMBOLS:
+        assert nm not in binding.ABI_SYMBOLS
+        assert nm not in open(os.path.join(INCLUDE, "ssf.h")).read()
+        assert nm not in open(os.path.join(INCLUDE, "ssf_testing.h")).read()
+    assert "#define SSF_ABI_VERSION 3" in open(os.path.join(INCLUDE, "ssf.h")).read()
+
+
+def test_the_product_exports_the_graph_entry_points(product_lib):
+    assert set(binding.GRAPH_SYMBOLS) <= exported(product_lib.path)
+    assert product_lib.has_graph
+    assert product_lib.lib.ssf_abi_version() == 3
+
+
+def test_the_checker_does_not_and_the_binding_says_so(oracle_lib):
+    assert not set(binding.GRAPH_SYMBOLS) & exported(oracle_lib.path)
+    assert not oracle_lib.has_graph
+    f = binding.Fusion(oracle_lib, oracle_lib.default_config(width=64, height=48, fx=60.0, fy=60.0, cx=31.5, cy=23.5))
+    z = np.zeros((5, 3), f32)
+    for call, symbol in ((f.graph_build, "ssf_graph_build"), (f.graph_nodes, "ssf_graph_get_nodes"), (f.graph_binding, "ssf_graph_get_binding"),
+                         (lambda: f.graph_bind_points(z, np.zeros(5, np.int32)), "ssf_graph_bind_points"),
+                         (lambda: f.graph_apply(np.zeros((5, 9), f32), z), "ssf_graph_apply"), (f.graph_info, "ssf_graph_info"),
+                         (f.graph_default_params, "ssf_graph_default_params")):
+        with pytest.raises(binding.SsfError, match=symbol + ".*HIP product only"):
+            call()
+
+
+def test_the_graph_kernels_read_no_environment_and_use_no_float_atomics():
+    txt = open(os.path.join(ROOT, "supersurfel_fusion_amd", "csrc", "ssf_graph.hip")).read()
+    assert "getenv(" not in txt and "SSF_ENV" not in txt
+    for m in re.finditer(r"atomic\w+\(&(\w+)", txt):
+        assert m.group(1) in ("mm", "hist"), m.group(0)           # int / uint32 counters only
+
+
+@pytest.mark.parametrize("lang", ["c", "c++"])
+def test_the_header_compiles_on_its_own(lang, tmp_path):
+    src = tmp_path / ("t.c" if lang == "c" else "t.cpp")
+    src.write_text('#include "ssf_graph.h"\n'
+                   "int f(ssf_handle* h, float* p, int32_t* t, int32_t* r, float* w, int32_t* i) {\n"
+                   "    ssf_graph_params q; int m = 0, n = 0, v = 0;\n"
+                   "    if (ssf_graph_default_params(&q) != SSF_OK) return -1;\n"
+                   "    q.stride = 10; q.look = SSF_GRAPH_MAX_STAMP_SPAN > 3 ? 3 : 4; q.min_conf = 0.5f;\n"
+                   "    return ssf_graph_build(h, &q, &m) + ssf_graph_get_nodes(h, p, t, r, m) + ssf_graph_get_binding(h, w, i, 0) +\n"
+                   "           ssf_graph_bind_points(h, p, t, m, w, i) + ssf_graph_apply(h, p, p) + ssf_graph_info(h, &m, &n, &v); }\n")
+    cc, std = ("gcc", "-std=c99") if lang == "c" else ("g++", "-std=c++11")
+    r = subprocess.run([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", INCLUDE, "-c", str(src), "-o", str(tmp_path / "t.o")],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+
+
+def test_ssf_hpp_graph_surface_compiles_and_links_against_the_product(product_lib, tmp_path):
+    libdir = os.path.dirname(product_lib.path)
+    cmd = ["g++", "-std=c++11", "-O1", "-Wall", "-Wextra", "-Werror", "-I", INCLUDE, "-I", CPP, os.path.join(CPP, "graph_smoke.cpp"),
+           "-o", str(tmp_path / "graph_smoke"), "-L", libdir, "-lssf_hip", "-Wl,-rpath," + libdir]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+
+
+def test_the_default_parameters():
+    txt = open(os.path.join(ROOT, "supersurfel_fusion_amd", "csrc", "ssf_host.hip")).read()
+    assert "p->stride = 50; p->look = 20; p->min_conf = 0.0f;" in txt
+
+
+# ---- properties of the restatement itself ------------------------------------------------------------------------------------
+def test_ref_nodes_are_in_time_order_and_sampled_by_rank():
+    pos, t0, conf = room()
+    rows = gr.sample(pos, t0, conf, stride=50)
+    el = np.flatnonzero(gr.eligible(pos, conf))
+    assert len(rows) == -(-len(el) // 50)
+    assert conf[rows].min() > 0
+    key = t0[rows].astype(np.int64) * (1 << 32) + rows
+    assert (np.diff(key) > 0).all()                                  # (t_init, row) strictly ascending
+    order = sorted(el.tolist(), key=lambda i: (int(t0[i]), i))       # the definition, the slow way
+    assert rows.tolist() == order[::50]
+    assert gr.sample(pos, t0, conf, stride=1).tolist() == order
+    pos[rows[3]] = np.nan                                            # a non-finite row is not eligible
+    assert rows[3] not in gr.sample(pos, t0, conf, stride=50)
+
+
+def test_ref_binding_properties_on_the_room():
+    pos, t0, conf = room()
+    rows = gr.sample(pos, t0, conf, stride=50)
+    npos, nt0 = pos[rows], t0[rows]
+    m, L = len(rows), 20
+    w4, idx4, bad, lo, W = gr.bind(pos, t0, npos, nt0, look=L)
+    assert W == 2 * L and not bad.any()                              # no fallback row in the room
+    assert np.isfinite(w4).all() and (w4 >= 0).all()
+    s = w4.astype(np.float64).sum(axis=1)
+    assert np.abs(s - 1).max() <= 4 * np.finfo(f32).eps
+    srt = np.sort(idx4, axis=1)
+    assert (np.diff(srt, axis=1) > 0).all()                          # distinct
+    assert (idx4 >= lo[:, None]).all() and (idx4 < lo[:, None] + W).all() and idx4.min() >= 0 and idx4.max() < m
+    assert (idx4[rows, 0] == np.arange(m)).all()                     # a node row binds to itself first ...
+    d = pos[rows] - npos[idx4[rows, 0]]
+    assert (d == 0).all()                                            # ... at distance 0
+    assert (np.diff(w4, axis=1) <= 0).all()                          # nearest first: weights descend
+    # the window is the 2 L nodes around the row's birth
+    c = np.searchsorted(nt0, t0, side="left")
+    assert (lo == np.clip(c - L, 0, m - 2 * L)).all()
+
+
+def test_ref_against_a_scalar_restatement():
+    rng = np.random.default_rng(11)
+    n, m, L = 300, 23, 4
+    npos = rng.uniform(-1, 1, (m, 3)).astype(f32); nt0 = np.sort(rng.integers(-5, 12, m)).astype(np.int32)
+    pos = rng.uniform(-1, 1, (n, 3)).astype(f32); t0 = rng.integers(-9, 16, n).astype(np.int32)
+    pos[:m:2] = npos[:m:2]
+    w4, idx4 = gr.bind(pos, t0, npos, nt0, look=L)[:2]
+    for i in range(n):
+        c = next((k for k in range(m) if nt0[k] >= t0[i]), m)
+        lo = min(max(c - L, 0), max(0, m - 2 * L))
+        cand = []
+        for k in range(lo, lo + min(m, 2 * L)):
+            d = pos[i] - npos[k]
+            d2 = f32(f32(d[0] * d[0]) + f32(d[1] * d[1])) + f32(d[2] * d[2])
+            cand.append((int(np.array(d2, f32).view(np.uint32)) << 32 | k, d2))
+        cand.sort(key=lambda e: e[0])
+        dist = [np.sqrt(f32(e[1])) for e in cand[:5]]
+        r = [f32(1) - dist[j] / dist[4] for j in range(4)]
+        w = [x * x for x in r]
+        s = f32(f32(w[0] + w[1]) + w[2]) + w[3]
+        assert [e[0] & 0xFFFFFFFF for e in cand[:4]] == idx4[i].tolist()
+        assert np.array_equal(np.array([x / s for x in w], f32).view(np.uint32), w4[i].view(np.uint32))
+
+
+def test_ref_fallbacks():
+    # five nodes at one point: dmax == 0 for a row at that point; a far row still gets weights (dmax > 0 there? no: all five
+    # distances are equal, every r is 0, s is 0 -> fallback as well)
+    npos = np.tile(np.array([[0.5, 0.25, 2.0]], f32), (5, 1)); nt0 = np.arange(5, dtype=np.int32)
+    pts = np.array([[0.5, 0.25, 2.0], [1.0, 1.0, 1.0], [np.nan, 0.0, 0.0], [0.0, np.inf, 0.0]], f32)
+    w4, idx4, bad, lo, W = gr.bind(pts, np.array([2, 2, 9, -3], np.int32), npos, nt0, look=3)
+    assert W == 5 and bad.all() and (w4 == f32(0.25)).all()
+    assert (idx4 == np.arange(4)).all()                              # ties go to the smaller node index; non-finite: lo .. lo + 3
+    # clipped window (m < 2 L) and stamps outside the nodes' range
+    npos = np.random.default_rng(2).uniform(-1, 1, (7, 3)).astype(f32)
+    w4, idx4, bad, lo, W = gr.bind(npos[:3] + f32(0.01), np.array([-100, 3, 100], np.int32), npos, np.arange(7, dtype=np.int32), look=20)
+    assert W == 7 and (lo == 0).all() and not bad.any() and (idx4[:, 0] == np.arange(3)).all()
