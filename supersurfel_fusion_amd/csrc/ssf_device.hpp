@@ -373,12 +373,14 @@ void launch_move_rows(hipStream_t st, const Cam& cam, SurfelSoA vis_src, SurfelS
 // new_head (dst.live must be zero where it matters); set_span != 0: cnt->oov_head / oov_tail := the new span
 void launch_oov_compact(hipStream_t st, OovStore src, OovStore dst, int span_upper, int new_head, uint32_t* bc_oov, Counters* cnt,
                         int set_span);
+// ---- the model read in place, one thread per slot (helpers: ssf_slots.hpp) ---------------------------------------------------
+// slots [0, nvs = 256 nbv) = the visible array (rows < n_visible), then nbo blocks of 256 slots = the out-of-view span
+// [oov_head, oov_tail) of `oov` (live flags; nbo = 0: visible rows only); nslots = 256 (nbv + nbo).  Slot order = logical order.
+struct ModelView { SurfelSoA vis; OovStore oov; int n_visible, nbv, nvs, oov_head, oov_tail, nbo, nslots; };
 // ---- the model drawn into a virtual camera (ssf_render.h; ssf_render.hip) ------------------------------------------------
 // R = 9 floats row-major and t (camera-to-map, ssf_get_pose's layout); ntx x nty tiles of 16 x 16 pixels; k = s * s
 struct RenderCam { float R[9], t[3]; float fx, fy, cx, cy; int W, H, ntx, nty; float zmin, zmax, min_conf, s, k; };
-// the rows drawn: slots [0, nvs = 256 nbv) = the visible array (rows < n_visible), then nbo blocks of 256 slots = the
-// out-of-view span [oov_head, oov_tail) of `oov` (live flags; nbo = 0: visible rows only); nslots = 256 (nbv + nbo)
-struct RenderView { RenderCam cam; SurfelSoA vis; OovStore oov; int n_visible, nbv, nvs, oov_head, oov_tail, nbo, nslots; };
+struct RenderView { RenderCam cam; ModelView model; };           // one kernel argument: the camera and the rows drawn
 struct RenderOut { float* depth; int32_t* index; uint8_t* rgb8; float* color; float* normal; };      // nullptr = not produced
 // prep (+ the out-of-view live scan into bc[nbo + 1]) and the exclusive scan of the tile counts: tcnt[ntiles + 1] (zeroed by the
 // caller) becomes the list offsets, cursor[ntiles] a copy; *total = list entries (64 bits)
@@ -390,21 +392,18 @@ void launch_render_tile(hipStream_t st, const RenderView& rv, const float4* rec,
                         const uint32_t* list, const uint32_t* toff, const RenderOut& out, uint32_t* seen, uint32_t epoch,
                         unsigned long long* stats);
 // ---- the deformation graph's nodes and per-row binding (ssf_graph.h; ssf_graph.hip) ---------------------------------------
-// the rows read in place: slots [0, nvs = 256 nbv) = the visible array (rows < n_visible), then nbo blocks of 256 slots = the
-// out-of-view span [oov_head, oov_tail) of `oov` (live flags); nslots = 256 (nbv + nbo).  Slot order = logical order.
-struct GraphView { SurfelSoA vis; OovStore oov; int n_visible, nbv, nvs, oov_head, oov_tail, nbo, nslots; };
 #define GRAPH_SORT_ITEMS 2048                     // items of one workgroup of the counting sort
 // stamp[nslots], elig[nslots]; bc[nbo + 1] = exclusive scan of the out-of-view blocks' live counts; mm[4] (preset INT_MAX, INT_MIN,
 // 0, 0) = min / max stamp of the eligible rows, their number, the live rows
-void launch_graph_keys(hipStream_t st, const GraphView& gv, float min_conf, int32_t* stamp, uint8_t* elig, uint32_t* bc, int* mm);
+void launch_graph_keys(hipStream_t st, const ModelView& mv, float min_conf, int32_t* stamp, uint8_t* elig, uint32_t* bc, int* mm);
 // stable sort of the eligible slots by (stamp - lo), `passes` 8-bit digits; cnt[256 ceil(nslots / GRAPH_SORT_ITEMS) + 1]; returns
 // which of the pairs (key_a, slot_a) = 0 / (key_b, slot_b) = 1 holds the n_elig sorted (stamp, slot) entries
 int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes, const int32_t* stamp, const uint8_t* elig, uint32_t* cnt,
                       int32_t* key_a, uint32_t* slot_a, int32_t* key_b, uint32_t* slot_b);
 // node k = the slot order[k stride]: nodes[k] = (x, y, z, bits(t_init)), npos3 = the packed positions, nrow = the logical row
-void launch_graph_sample(hipStream_t st, const GraphView& gv, const uint32_t* bc, const uint32_t* order, int m, int stride, float4* nodes,
+void launch_graph_sample(hipStream_t st, const ModelView& mv, const uint32_t* bc, const uint32_t* order, int m, int stride, float4* nodes,
                          float* npos3, int32_t* nrow);
-void launch_graph_bind(hipStream_t st, const GraphView& gv, const uint32_t* bc, const float4* nodes, int m, int look, float* w4, int32_t* i4);
+void launch_graph_bind(hipStream_t st, const ModelView& mv, const uint32_t* bc, const float4* nodes, int m, int look, float* w4, int32_t* i4);
 void launch_graph_bind_points(hipStream_t st, const float* pts, const int32_t* t0, int n, const float4* nodes, int m, int look, float* w4,
                               int32_t* i4);
 // one iteration of the loop-closure registration against a frame; out40: see k_align

@@ -3,62 +3,51 @@
 // What is computed is pinned, operation by operation, in include/ssf_graph.h (the numpy restatement: tests/graph_ref.py).  How:
 //   * rows   both model stores are read in place (never materialised), one thread per SLOT of [visible rows | out-of-view
 //            span], as the render kernels do.  Slot order = logical order, so a sort that is stable over slots is stable over
-//            logical indices; an out-of-view slot's logical index = n_visible + (live rows before it): a per-256-block count,
-//            an exclusive scan (own scratch: the handle's Counters and d_bc_oov are not touched) and a ballot inside the block.
+//            logical indices; an out-of-view slot's logical index = n_visible + (live rows before it): a per-256-block count
+//            (k_graph_keys), an exclusive scan (k_graph_scan into own scratch: the handle's Counters and d_bc_oov are not
+//            touched) and a rank inside the block -- the view and these helpers are ssf_slots.hpp's, shared with the render.
 //   * rank   k_graph_keys: per slot the birth stamp and an eligibility byte, the out-of-view live counts, and min / max /
 //            count of the eligible stamps with exact integer atomics (the result does not depend on their order).  Then a
 //            stable least-significant-digit counting sort of (stamp - min) over 8-bit digits, 1..3 passes for a span of up to
-//            2^24 (the header admits 2^20): per pass a per-workgroup digit histogram, one exclusive scan over (digit, workgroup)
-//            and a scatter whose position inside a workgroup comes from wave ballots, never from the arrival order of an
-//            atomic.  Pass 0 drops the ineligible slots, so the sorted list is dense: rank -> slot.
-//   * sample node k = the slot of rank k * stride: its position bits, stamp and logical index, as one 16-byte record
-//            (x, y, z, bits(t_init)) per node in time order plus a packed position (what k_pack_nodes reads) and the row.
-//   * bind   one thread per slot (or per caller point): lower bound over the records' stamps (from L2: 16 steps at 64 k nodes),
-//            then the window's records, the five smallest (bits(d2) << 32 | k) kept sorted in ten registers by a min / max
+//            2^24 (the header admits 2^20): per pass a per-workgroup digit histogram (k_graph_hist), one k_graph_scan over
+//            (digit, workgroup) and a scatter (k_graph_scatter) whose position inside a workgroup comes from wave ballots,
+//            never from the arrival order of an atomic.  Pass 0 drops the ineligible slots, so the sorted list is dense:
+//            rank -> slot.
+//   * sample k_graph_sample: node k = the slot of rank k * stride: its position bits, stamp and logical index, as one 16-byte
+//            record (x, y, z, bits(t_init)) per node in time order plus a packed position (what k_pack_nodes reads) and the row.
+//   * bind   k_graph_bind / k_graph_bind_points: one thread per slot (or per caller point): lower bound over the records'
+//            stamps (from L2: 16 steps at 64 k nodes), then the window's records, the five smallest (bits(d2) << 32 | k) kept sorted in ten registers by a min / max
 //            chain, the weights, one 16-byte store each for weights4 and idx4 at the logical index.
 // No float atomics anywhere; every count is an integer.
 #include <climits>
-#include "ssf_device.hpp"
+#include "ssf_slots.hpp"
 
 namespace ssf {
 
-__device__ __forceinline__ int glane() { return threadIdx.x & 63; }
-__device__ __forceinline__ bool gfinite3(float a, float b, float c) { return isfinite(a) && isfinite(b) && isfinite(c); }
-
-// slot -> the row it reads and whether it holds a row of the model
-__device__ __forceinline__ bool graph_slot(const GraphView& gv, uint32_t s, SurfelSoA& src, size_t& row) {
-    if (s < (uint32_t)gv.nvs) { src = gv.vis; row = s; return s < (uint32_t)gv.n_visible; }
-    const long long phys = (long long)gv.oov_head + (s - (uint32_t)gv.nvs);
-    src = gv.oov.rows; row = (size_t)phys;
-    return s < (uint32_t)gv.nslots && phys < gv.oov_tail && gv.oov.live[phys] != 0;
-}
-
 // ---- keys: stamp + eligibility per slot, live counts of the out-of-view blocks, min / max / count of the eligible stamps ----
 // mm[0] = min (starts INT_MAX), mm[1] = max (starts INT_MIN), mm[2] = eligible rows, mm[3] = live rows
-__global__ __launch_bounds__(256) void k_graph_keys(GraphView gv, float min_conf, int32_t* __restrict__ stamp, uint8_t* __restrict__ elig,
+__global__ __launch_bounds__(256) void k_graph_keys(ModelView mv, float min_conf, int32_t* __restrict__ stamp, uint8_t* __restrict__ elig,
                                                     uint32_t* __restrict__ bc, int* __restrict__ mm) {
-    __shared__ int part[4][4];
+    __shared__ int mmw[4][2], ce[4], cl[4];
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     SurfelSoA src; size_t row;
-    const bool lv = graph_slot(gv, s, src, row);
+    const bool lv = slot_row(mv, s, src, row);
     int t = 0; bool el = false;
     if (lv) {
         t = src.stamps[2 * row];
-        el = src.conf[row] > min_conf && gfinite3(src.pos[3 * row], src.pos[3 * row + 1], src.pos[3 * row + 2]);
+        el = src.conf[row] > min_conf && finite3(src.pos[3 * row], src.pos[3 * row + 1], src.pos[3 * row + 2]);
     }
     stamp[s] = t; elig[s] = el ? 1 : 0;
     int lo = el ? t : INT_MAX, hi = el ? t : INT_MIN;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o, 64)); hi = max(hi, __shfl_xor(hi, o, 64)); }
-    const int ne = __popcll(__ballot(el)), nl = __popcll(__ballot(lv));
-    if (glane() == 0) { int* p = part[threadIdx.x >> 6]; p[0] = lo; p[1] = hi; p[2] = ne; p[3] = nl; }
-    __syncthreads();
+    if (lane() == 0) { mmw[threadIdx.x >> 6][0] = lo; mmw[threadIdx.x >> 6][1] = hi; }
+    const int e = block_count256(el, ce), l = block_count256(lv, cl);      // (their barrier also publishes mmw)
     if (threadIdx.x == 0) {
-        const int e = part[0][2] + part[1][2] + part[2][2] + part[3][2], l = part[0][3] + part[1][3] + part[2][3] + part[3][3];
-        if ((int)blockIdx.x >= gv.nbv) bc[blockIdx.x - gv.nbv] = (uint32_t)l;
+        if ((int)blockIdx.x >= mv.nbv) bc[blockIdx.x - mv.nbv] = (uint32_t)l;
         if (e > 0) {
-            atomicMin(&mm[0], min(min(part[0][0], part[1][0]), min(part[2][0], part[3][0])));
-            atomicMax(&mm[1], max(max(part[0][1], part[1][1]), max(part[2][1], part[3][1])));
+            atomicMin(&mm[0], min(min(mmw[0][0], mmw[1][0]), min(mmw[2][0], mmw[3][0])));
+            atomicMax(&mm[1], max(max(mmw[0][1], mmw[1][1]), max(mmw[2][1], mmw[3][1])));
             atomicAdd(&mm[2], e);
         }
         if (l > 0) atomicAdd(&mm[3], l);
@@ -67,26 +56,9 @@ __global__ __launch_bounds__(256) void k_graph_keys(GraphView gv, float min_conf
 
 // exclusive scan of n counts in place (one workgroup of 1024); a[n] = the total
 __global__ __launch_bounds__(1024) void k_graph_scan(uint32_t* __restrict__ a, int n) {
-    __shared__ uint32_t wtot[16];
-    __shared__ uint32_t base;
-    if (threadIdx.x == 0) base = 0;
-    __syncthreads();
-    for (int i0 = 0; i0 < n; i0 += 1024) {
-        const int i = i0 + threadIdx.x;
-        const uint32_t c = i < n ? a[i] : 0u;
-        uint32_t v = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(v, o, 64); if (glane() >= o) v += up; }
-        if (glane() == 63) wtot[threadIdx.x >> 6] = v;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (int w = 0; w < 16; w++) { const uint32_t t = wtot[w]; if (w < (int)(threadIdx.x >> 6)) before += t; all += t; }
-        if (i < n) a[i] = base + before + v - c;
-        __syncthreads();
-        if (threadIdx.x == 0) base += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) a[n] = base;
+    __shared__ uint32_t tot[1];
+    workgroup_scan<1, uint32_t>(a, n, nullptr, tot);
+    if (threadIdx.x == 0) a[n] = tot[0];
 }
 
 // ---- one pass of the stable counting sort: GRAPH_SORT_ITEMS items per workgroup, digit = ((key - lo) >> shift) & 255 ----------
@@ -129,7 +101,7 @@ __global__ __launch_bounds__(256) void k_graph_scatter(const int32_t* __restrict
             const unsigned long long v = __ballot(bit);
             same &= bit ? v : ~v;
         }
-        const uint32_t rank = (uint32_t)__popcll(same & ((1ull << glane()) - 1ull));
+        const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane()) - 1ull));
         if (on && rank == 0) wc[wave][d] = (uint32_t)__popcll(same);
         __syncthreads();
         if (on) {
@@ -147,21 +119,20 @@ __global__ __launch_bounds__(256) void k_graph_scatter(const int32_t* __restrict
 }
 
 // ---- sample: node k = the slot of rank k * stride ------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_graph_sample(GraphView gv, const uint32_t* __restrict__ bc, const uint32_t* __restrict__ order,
+__global__ __launch_bounds__(256) void k_graph_sample(ModelView mv, const uint32_t* __restrict__ bc, const uint32_t* __restrict__ order,
                                                       int m, int stride, float4* __restrict__ nodes, float* __restrict__ npos3,
                                                       int32_t* __restrict__ nrow) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= m) return;
     const uint32_t s = order[(size_t)k * stride];
     SurfelSoA src; size_t row;
-    (void)graph_slot(gv, s, src, row);
+    (void)slot_row(mv, s, src, row);
     int logical = (int)s;
-    if (s >= (uint32_t)gv.nvs) {                  // live rows of the span in front of this one
-        const uint32_t b = (s - (uint32_t)gv.nvs) >> 8;
-        const size_t first = (size_t)gv.oov_head + ((size_t)b << 8);
+    if (s >= (uint32_t)mv.nvs) {                  // live rows of the span in front of this one: bc[its block] + a walk over the block
+        const uint32_t b = (s - (uint32_t)mv.nvs) >> 8;
         int before = 0;
-        for (size_t q = first; q < row; q++) before += gv.oov.live[q] ? 1 : 0;
-        logical = gv.n_visible + (int)bc[b] + before;
+        for (size_t q = (size_t)mv.oov_head + ((size_t)b << 8); q < row; q++) before += mv.oov.live[q] ? 1 : 0;
+        logical = mv.n_visible + (int)bc[b] + before;
     }
     const float x = src.pos[3 * row], y = src.pos[3 * row + 1], z = src.pos[3 * row + 2];
     nodes[k] = make_float4(x, y, z, __int_as_float(src.stamps[2 * row]));
@@ -198,7 +169,7 @@ __device__ __forceinline__ void graph_bind_one(const float4* __restrict__ nodes,
     const float r0 = 1.0f - e0 / dmax, r1 = 1.0f - e1 / dmax, r2 = 1.0f - e2 / dmax, r3 = 1.0f - e3 / dmax;
     const float w0 = r0 * r0, w1 = r1 * r1, w2 = r2 * r2, w3 = r3 * r3;
     const float s = ((w0 + w1) + w2) + w3;
-    const bool fin = gfinite3(px, py, pz);
+    const bool fin = finite3(px, py, pz);
     if (dmax == 0.0f || !(s > 0.0f) || !fin) {
         w4 = make_float4(0.25f, 0.25f, 0.25f, 0.25f);
         if (!fin) i4 = make_int4(lo, lo + 1, lo + 2, lo + 3);
@@ -208,21 +179,13 @@ __device__ __forceinline__ void graph_bind_one(const float4* __restrict__ nodes,
 }
 
 // every logical row of the model: one thread per slot; bc = the exclusive scan of the out-of-view blocks' live counts
-__global__ __launch_bounds__(256) void k_graph_bind(GraphView gv, const uint32_t* __restrict__ bc, const float4* __restrict__ nodes, int m,
+__global__ __launch_bounds__(256) void k_graph_bind(ModelView mv, const uint32_t* __restrict__ bc, const float4* __restrict__ nodes, int m,
                                                     int L, float4* __restrict__ w4, int4* __restrict__ i4) {
-    __shared__ int wl[4];
+    __shared__ int part[4];
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     SurfelSoA src; size_t row;
-    const bool lv = graph_slot(gv, s, src, row);
-    int logical = (int)s;
-    if ((int)blockIdx.x >= gv.nbv) {              // (uniform per workgroup)
-        const unsigned long long bal = __ballot(lv);
-        if (glane() == 0) wl[threadIdx.x >> 6] = __popcll(bal);
-        __syncthreads();
-        int before = __popcll(bal & ((1ull << glane()) - 1ull));
-        for (int w = 0; w < (int)(threadIdx.x >> 6); w++) before += wl[w];
-        logical = gv.n_visible + (int)bc[blockIdx.x - gv.nbv] + before;
-    }
+    const bool lv = slot_row(mv, s, src, row);
+    const int logical = slot_logical256(mv, lv, bc, part);
     if (!lv) return;
     float4 w; int4 i;
     graph_bind_one(nodes, m, L, src.pos[3 * row], src.pos[3 * row + 1], src.pos[3 * row + 2], src.stamps[2 * row], w, i);
@@ -241,10 +204,10 @@ __global__ __launch_bounds__(256) void k_graph_bind_points(const float* __restri
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------
-void launch_graph_keys(hipStream_t st, const GraphView& gv, float min_conf, int32_t* stamp, uint8_t* elig, uint32_t* bc, int* mm) {
+void launch_graph_keys(hipStream_t st, const ModelView& mv, float min_conf, int32_t* stamp, uint8_t* elig, uint32_t* bc, int* mm) {
     ScopedKernel sk("graph_rank", st);
-    hipLaunchKernelGGL(k_graph_keys, dim3(gv.nbv + gv.nbo), dim3(256), 0, st, gv, min_conf, stamp, elig, bc, mm);
-    if (gv.nbo > 0) hipLaunchKernelGGL(k_graph_scan, dim3(1), dim3(1024), 0, st, bc, gv.nbo);
+    hipLaunchKernelGGL(k_graph_keys, dim3(mv.nbv + mv.nbo), dim3(256), 0, st, mv, min_conf, stamp, elig, bc, mm);
+    if (mv.nbo > 0) hipLaunchKernelGGL(k_graph_scan, dim3(1), dim3(1024), 0, st, bc, mv.nbo);
 }
 int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes, const int32_t* stamp, const uint8_t* elig, uint32_t* cnt,
                       int32_t* key_a, uint32_t* slot_a, int32_t* key_b, uint32_t* slot_b) {
@@ -261,14 +224,14 @@ int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes
     }
     return out ^ 1;                               // which pair holds the sorted list: 0 = a, 1 = b
 }
-void launch_graph_sample(hipStream_t st, const GraphView& gv, const uint32_t* bc, const uint32_t* order, int m, int stride, float4* nodes,
+void launch_graph_sample(hipStream_t st, const ModelView& mv, const uint32_t* bc, const uint32_t* order, int m, int stride, float4* nodes,
                          float* npos3, int32_t* nrow) {
     ScopedKernel sk("graph_sample", st);
-    hipLaunchKernelGGL(k_graph_sample, dim3((m + 255) / 256), dim3(256), 0, st, gv, bc, order, m, stride, nodes, npos3, nrow);
+    hipLaunchKernelGGL(k_graph_sample, dim3((m + 255) / 256), dim3(256), 0, st, mv, bc, order, m, stride, nodes, npos3, nrow);
 }
-void launch_graph_bind(hipStream_t st, const GraphView& gv, const uint32_t* bc, const float4* nodes, int m, int look, float* w4, int32_t* i4) {
+void launch_graph_bind(hipStream_t st, const ModelView& mv, const uint32_t* bc, const float4* nodes, int m, int look, float* w4, int32_t* i4) {
     ScopedKernel sk("graph_bind", st);
-    hipLaunchKernelGGL(k_graph_bind, dim3(gv.nbv + gv.nbo), dim3(256), 0, st, gv, bc, nodes, m, look, reinterpret_cast<float4*>(w4),
+    hipLaunchKernelGGL(k_graph_bind, dim3(mv.nbv + mv.nbo), dim3(256), 0, st, mv, bc, nodes, m, look, reinterpret_cast<float4*>(w4),
                        reinterpret_cast<int4*>(i4));
 }
 void launch_graph_bind_points(hipStream_t st, const float* pts, const int32_t* t0, int n, const float4* nodes, int m, int look, float* w4,

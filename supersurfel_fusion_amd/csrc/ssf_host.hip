@@ -556,9 +556,33 @@ struct ActiveFrame {
 #ifndef SSF_BIN_MIN_ROWS_DEFAULT
 #define SSF_BIN_MIN_ROWS_DEFAULT 400000
 #endif
+// The device buffers a workspace owns.  grow is all or nothing: allocate every (pointer, bytes) of `want`; only when all succeeded
+// free the old buffers and install the new ones.  A failed hipMalloc leaves its error behind in the runtime: it is cleared, so
+// that the next frame's launch checks do not report it.  release frees whatever grow installed (ssf_destroy): a pointer that a
+// workspace gains is named in its grow call and nowhere else.
+struct DevBufs {
+    std::vector<void**> owned;                                    // the workspace's members that hold a buffer
+    bool grow(std::initializer_list<std::pair<void**, size_t>> want) {
+        std::vector<void*> got;
+        for (const auto& w : want) {
+            void* q = nullptr;
+            if (hipMalloc(&q, std::max<size_t>(w.second, 1)) != hipSuccess) {
+                for (void* g : got) (void)hipFree(g);
+                (void)hipGetLastError();
+                return false;
+            }
+            got.push_back(q);
+        }
+        size_t i = 0;
+        for (const auto& w : want) { if (*w.first) (void)hipFree(*w.first); else owned.push_back(w.first); *w.first = got[i++]; }
+        return true;
+    }
+    void release() { for (void** q : owned) { (void)hipFree(*q); *q = nullptr; } owned.clear(); }
+};
 // working buffers of ssf_render_model (ssf_render.h): allocated on first use; each group (per slot / per tile / list / staged images)
-// is grown as a whole or not at all (render_grow), freed in ssf_destroy
+// is grown as a whole or not at all (DevBufs::grow)
 struct RenderWs {
+    DevBufs bufs;
     float4* rec = nullptr; uint2* rbox = nullptr; int32_t* logical = nullptr; uint32_t* seen = nullptr; uint32_t* bc = nullptr;
     size_t slots = 0;                                              // per slot: record, pixel box, logical index, `seen` epoch
     uint32_t* tcnt = nullptr; uint32_t* cursor = nullptr; size_t tiles = 0;           // per tile (+ 1): counts -> offsets, cursors
@@ -568,8 +592,9 @@ struct RenderWs {
     uint32_t epoch = 0;                                           // of the last render: seen[slot] == epoch <=> shown by it
 };
 // ssf_graph_build (ssf_graph.h): the resident node table and binding, and the working buffers of the time-order sort.  Allocated
-// on first use; each group (per slot / per node) is grown as a whole or not at all (render_grow), freed in ssf_destroy
+// on first use; each group (per slot / per node) is grown as a whole or not at all (DevBufs::grow)
 struct GraphWs {
+    DevBufs bufs;
     int32_t* stamp = nullptr; uint8_t* elig = nullptr; int32_t* key_a = nullptr; int32_t* key_b = nullptr;
     uint32_t* slot_a = nullptr; uint32_t* slot_b = nullptr; uint32_t* cnt = nullptr; uint32_t* bc = nullptr;
     float* w4 = nullptr; int32_t* idx4 = nullptr; int* mm = nullptr; size_t slots = 0;       // per slot; w4 / idx4 per logical row
@@ -1825,12 +1850,8 @@ void ssf_destroy(ssf_handle* h) {
     if (h->capture_stream) stream_pool().give(h->capture_stream, h->cfg.device_id, StreamPool::CAPTURE);
     if (!h->guarded.empty() && !SSF_ENV_SET("GUARD_ONLY")) check_guards(h);
     for (void* p : h->allocs) (void)hipFree(p);
-    { void* rw[] = {h->render.rec, h->render.rbox, h->render.logical, h->render.seen, h->render.bc, h->render.tcnt, h->render.cursor,
-                    h->render.list, h->render.stats, h->render.img};
-      for (void* q : rw) if (q) (void)hipFree(q); }
-    { GraphWs& g = h->graph;
-      void* gw[] = {g.stamp, g.elig, g.key_a, g.key_b, g.slot_a, g.slot_b, g.cnt, g.bc, g.w4, g.idx4, g.mm, g.nodes, g.npos3, g.nrow};
-      for (void* q : gw) if (q) (void)hipFree(q); }
+    h->render.bufs.release();
+    h->graph.bufs.release();
     if (h->mb_host) (void)hipHostFree(h->mb_host);
     for (int i = 0; i < 4; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     for (auto& r : h->timer.pool_free) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -2753,23 +2774,22 @@ int ssf_get_model_device(ssf_handle* h, ssf_surfels* o, int* n) {
 }
 
 // ---- the model drawn into a virtual camera (ssf_render.h; kernels in ssf_render.hip) ------------------------------------
-// all or nothing: allocate every (pointer, bytes) of `want`; only when all succeeded free the old buffers and install the new
-// ones.  A failed hipMalloc leaves its error behind in the runtime: it is cleared, so that the next frame's launch checks do
-// not report it.
-static bool render_grow(std::initializer_list<std::pair<void**, size_t>> want) {
-    std::vector<void*> got;
-    for (const auto& w : want) {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(w.second, 1)) != hipSuccess) {
-            for (void* g : got) (void)hipFree(g);
-            (void)hipGetLastError();
-            return false;
-        }
-        got.push_back(q);
-    }
-    size_t i = 0;
-    for (const auto& w : want) { if (*w.first) (void)hipFree(*w.first); *w.first = got[i++]; }
-    return true;
+// what ssf_render_model and ssf_graph_build read: both stores of the handle in place (visible_only: without the out-of-view span)
+static ModelView model_view(const ssf_handle* h, bool visible_only) {
+    ModelView mv;
+    mv.vis = h->model[h->mcur]; mv.oov = h->oov[h->ocur];
+    mv.n_visible = h->n_visible; mv.nbv = (h->n_visible + 255) / 256; mv.nvs = 256 * mv.nbv;
+    mv.oov_head = h->oov_head; mv.oov_tail = h->oov_tail;
+    mv.nbo = visible_only ? 0 : (h->oov_tail - h->oov_head + 255) / 256;
+    mv.nslots = 256 * (mv.nbv + mv.nbo);
+    return mv;
+}
+// the refusals of the calls that work on the model between frames: frames in flight and, for a call that does not serve a
+// sharded handle (who != nullptr), such a handle: "<who>: a sharded handle (cfg.nranks > 1) <lacks>"
+static int model_at_rest(ssf_handle* h, const char* who = nullptr, const char* lacks = nullptr) {
+    if (!h->pending.empty() || h->fusing) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
+    if (who && h->cfg.nranks > 1) { h->err = std::string(who) + ": a sharded handle (cfg.nranks > 1) " + lacks; return SSF_ERR_STATE; }
+    return SSF_OK;
 }
 static size_t render_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -2785,8 +2805,7 @@ int ssf_render_model(ssf_handle* h, const ssf_render_params* p, float* depth, in
                      float* normal, ssf_render_stats* stats) {
     if (!h || !p) return SSF_ERR_INVALID_ARG;
     if (!depth && !index && !rgb8 && !color && !normal) { h->err = "ssf_render_model: every output is NULL"; return SSF_ERR_INVALID_ARG; }
-    if (!h->pending.empty() || h->fusing) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
-    if (h->cfg.nranks > 1) { h->err = "ssf_render_model: a sharded handle (cfg.nranks > 1) is not rendered"; return SSF_ERR_STATE; }
+    { int rc = model_at_rest(h, "ssf_render_model", "is not rendered"); if (rc) return rc; }
     RenderCam K;
     const Rt T = p->pose ? pose_from12(p->pose) : h->pose;
     const float R9[9] = {T.R.r0.x, T.R.r0.y, T.R.r0.z, T.R.r1.x, T.R.r1.y, T.R.r1.z, T.R.r2.x, T.R.r2.y, T.R.r2.z};
@@ -2804,31 +2823,26 @@ int ssf_render_model(ssf_handle* h, const ssf_render_params* p, float* depth, in
     K.ntx = (K.W + 15) / 16; K.nty = (K.H + 15) / 16;
     const int ntiles = K.ntx * K.nty;
 
-    RenderView rv;
-    rv.cam = K; rv.vis = h->model[h->mcur]; rv.oov = h->oov[h->ocur];
-    rv.n_visible = h->n_visible; rv.nbv = (h->n_visible + 255) / 256; rv.nvs = 256 * rv.nbv;
-    rv.oov_head = h->oov_head; rv.oov_tail = h->oov_tail;
-    rv.nbo = p->visible_only ? 0 : (h->oov_tail - h->oov_head + 255) / 256;
-    rv.nslots = 256 * (rv.nbv + rv.nbo);
+    const RenderView rv{K, model_view(h, p->visible_only != 0)};
 
     RenderWs& w = h->render;
     const size_t P = (size_t)K.W * K.H;
     const size_t img_need = p->on_device ? 0 : (depth ? render_align(4 * P) : 0) + (index ? render_align(4 * P) : 0) +
                                                (rgb8 ? render_align(3 * P) : 0) + (color ? render_align(12 * P) : 0) + (normal ? render_align(12 * P) : 0);
-    const size_t slots = std::max<size_t>(rv.nslots, 256);
+    const size_t slots = std::max<size_t>(rv.model.nslots, 256);
     bool ok = true;
     if (ok && slots > w.slots) {
-        ok = render_grow({{(void**)&w.rec, 64 * slots}, {(void**)&w.rbox, 8 * slots}, {(void**)&w.logical, 4 * slots},
+        ok = w.bufs.grow({{(void**)&w.rec, 64 * slots}, {(void**)&w.rbox, 8 * slots}, {(void**)&w.logical, 4 * slots},
                           {(void**)&w.seen, 4 * slots}, {(void**)&w.bc, 4 * (slots / 256 + 1)}});
         if (ok) { w.slots = slots; w.epoch = 0; HCK(hipMemsetAsync(w.seen, 0, 4 * slots, h->stream)); }
     }
     if (ok && (size_t)ntiles + 1 > w.tiles) {
-        ok = render_grow({{(void**)&w.tcnt, 4 * ((size_t)ntiles + 1)}, {(void**)&w.cursor, 4 * ((size_t)ntiles + 1)}});
+        ok = w.bufs.grow({{(void**)&w.tcnt, 4 * ((size_t)ntiles + 1)}, {(void**)&w.cursor, 4 * ((size_t)ntiles + 1)}});
         if (ok) w.tiles = (size_t)ntiles + 1;
     }
-    if (ok && !w.stats) ok = render_grow({{(void**)&w.stats, 4 * sizeof(unsigned long long)}});
+    if (ok && !w.stats) ok = w.bufs.grow({{(void**)&w.stats, 4 * sizeof(unsigned long long)}});
     if (ok && img_need > w.img_bytes) {
-        ok = render_grow({{(void**)&w.img, img_need}});
+        ok = w.bufs.grow({{(void**)&w.img, img_need}});
         if (ok) w.img_bytes = img_need;
     }
     if (!ok) { h->err = "ssf_render_model: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
@@ -2846,7 +2860,7 @@ int ssf_render_model(ssf_handle* h, const ssf_render_params* p, float* depth, in
     if (total > 0xFFFFFFFFull) { h->err = "ssf_render_model: more than 2^32 - 1 (tile, row) list entries"; return SSF_ERR_DEVICE; }
     if (total > w.list_cap) {
         const size_t cap = std::min<unsigned long long>(total + total / 4, 0xFFFFFFFFull);
-        if (!render_grow({{(void**)&w.list, 4 * cap}})) {
+        if (!w.bufs.grow({{(void**)&w.list, 4 * cap}})) {
             h->err = "ssf_render_model: allocation of " + std::to_string(4 * cap) + " bytes for the tile lists failed";
             return SSF_ERR_DEVICE;
         }
@@ -2966,8 +2980,7 @@ int ssf_graph_default_params(ssf_graph_params* p) {
 static bool graph_valid(const ssf_handle* h) { return h->graph.built && h->graph.gen == h->model_gen; }
 // the refusals every call that uses the resident graph shares
 static int graph_usable(ssf_handle* h, const char* who) {
-    if (!h->pending.empty() || h->fusing) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
-    if (h->cfg.nranks > 1) { h->err = std::string(who) + ": a sharded handle (cfg.nranks > 1) has no deformation graph"; return SSF_ERR_STATE; }
+    { int rc = model_at_rest(h, who, "has no deformation graph"); if (rc) return rc; }
     if (!h->graph.built) { h->err = std::string(who) + ": no graph has been built (ssf_graph_build)"; return SSF_ERR_STATE; }
     if (!graph_valid(h)) { h->err = std::string(who) + ": graph is stale: build it again"; return SSF_ERR_STATE; }
     return SSF_OK;
@@ -2977,22 +2990,16 @@ int ssf_graph_build(ssf_handle* h, const ssf_graph_params* p, int* n_nodes) {
     if (p->stride < 1 || p->look < 3 || !std::isfinite(p->min_conf)) {
         h->err = "ssf_graph_build: needs stride >= 1, look >= 3 and a finite min_conf"; return SSF_ERR_INVALID_ARG;
     }
-    if (!h->pending.empty() || h->fusing) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
-    if (h->cfg.nranks > 1) { h->err = "ssf_graph_build: a sharded handle (cfg.nranks > 1) has no deformation graph"; return SSF_ERR_STATE; }
+    { int rc = model_at_rest(h, "ssf_graph_build", "has no deformation graph"); if (rc) return rc; }
     GraphWs& g = h->graph;
     g.built = false;                              // whatever happens below, no half-built graph is kept
     if (h->n_model <= 0) { h->err = "ssf_graph_build: the model is empty"; return SSF_ERR_STATE; }
 
-    GraphView gv;
-    gv.vis = h->model[h->mcur]; gv.oov = h->oov[h->ocur];
-    gv.n_visible = h->n_visible; gv.nbv = (h->n_visible + 255) / 256; gv.nvs = 256 * gv.nbv;
-    gv.oov_head = h->oov_head; gv.oov_tail = h->oov_tail;
-    gv.nbo = (h->oov_tail - h->oov_head + 255) / 256;
-    gv.nslots = 256 * (gv.nbv + gv.nbo);
-    const size_t slots = (size_t)gv.nslots;       // (>= n_model > 0: every row has a slot)
+    const ModelView mv = model_view(h, false);
+    const size_t slots = (size_t)mv.nslots;       // (>= n_model > 0: every row has a slot)
     if (slots > g.slots) {
         const size_t nb = (slots + GRAPH_SORT_ITEMS - 1) / GRAPH_SORT_ITEMS;
-        if (!render_grow({{(void**)&g.stamp, 4 * slots}, {(void**)&g.elig, slots}, {(void**)&g.key_a, 4 * slots}, {(void**)&g.key_b, 4 * slots},
+        if (!g.bufs.grow({{(void**)&g.stamp, 4 * slots}, {(void**)&g.elig, slots}, {(void**)&g.key_a, 4 * slots}, {(void**)&g.key_b, 4 * slots},
                           {(void**)&g.slot_a, 4 * slots}, {(void**)&g.slot_b, 4 * slots}, {(void**)&g.cnt, 4 * (256 * nb + 1)},
                           {(void**)&g.bc, 4 * (slots / 256 + 1)}, {(void**)&g.w4, 16 * slots}, {(void**)&g.idx4, 16 * slots},
                           {(void**)&g.mm, 4 * sizeof(int)}})) {
@@ -3005,7 +3012,7 @@ int ssf_graph_build(ssf_handle* h, const ssf_graph_params* p, int* n_nodes) {
     const int mm0[4] = {INT_MAX, INT_MIN, 0, 0};
     int mm[4] = {0, 0, 0, 0};
     HCK(hipMemcpyAsync(g.mm, mm0, sizeof(mm0), hipMemcpyHostToDevice, st));
-    launch_graph_keys(st, gv, p->min_conf, g.stamp, g.elig, g.bc, g.mm);
+    launch_graph_keys(st, mv, p->min_conf, g.stamp, g.elig, g.bc, g.mm);
     HCK(hipGetLastError());
     HCK(hipMemcpyAsync(mm, g.mm, sizeof(mm), hipMemcpyDeviceToHost, st));
     HCK(hipStreamSynchronize(st));
@@ -3028,17 +3035,17 @@ int ssf_graph_build(ssf_handle* h, const ssf_graph_params* p, int* n_nodes) {
     const int m = (int)m64;
     if ((size_t)m > g.node_cap) {
         const size_t cap = (size_t)m + (size_t)m / 4;
-        if (!render_grow({{(void**)&g.nodes, 16 * cap}, {(void**)&g.npos3, 12 * cap}, {(void**)&g.nrow, 4 * cap}})) {
+        if (!g.bufs.grow({{(void**)&g.nodes, 16 * cap}, {(void**)&g.npos3, 12 * cap}, {(void**)&g.nrow, 4 * cap}})) {
             h->err = "ssf_graph_build: allocation of the node table failed"; return SSF_ERR_DEVICE;
         }
         g.node_cap = cap;
     }
     const int passes = span < 256 ? 1 : span < 65536 ? 2 : 3;
-    const int which = launch_graph_sort(st, gv.nslots, n_elig, mm[0], passes, g.stamp, g.elig, g.cnt, g.key_a, g.slot_a, g.key_b, g.slot_b);
+    const int which = launch_graph_sort(st, mv.nslots, n_elig, mm[0], passes, g.stamp, g.elig, g.cnt, g.key_a, g.slot_a, g.key_b, g.slot_b);
     HCK(hipGetLastError());
-    launch_graph_sample(st, gv, g.bc, which == 0 ? g.slot_a : g.slot_b, m, p->stride, g.nodes, g.npos3, g.nrow);
+    launch_graph_sample(st, mv, g.bc, which == 0 ? g.slot_a : g.slot_b, m, p->stride, g.nodes, g.npos3, g.nrow);
     HCK(hipGetLastError());
-    launch_graph_bind(st, gv, g.bc, g.nodes, m, p->look, g.w4, g.idx4);
+    launch_graph_bind(st, mv, g.bc, g.nodes, m, p->look, g.w4, g.idx4);
     HCK(hipGetLastError());
     HCK(hipStreamSynchronize(st));
     if (h->cfg.profile == 1) timer_collect(&h->timer);
@@ -3117,7 +3124,7 @@ int ssf_graph_apply(ssf_handle* h, const float* nr, const float* nt) {
 // the ranks is the caller's (supersurfel_fusion_amd/sharded.py: torch.distributed; the tests: files / memory).
 int ssf_rehome_begin(ssf_handle* h, int32_t* table, int table_rows, int* n_out) {
     if (!h || !n_out || table_rows < 0 || (!table && table_rows > 0)) return SSF_ERR_INVALID_ARG;
-    if (!h->pending.empty() || h->fusing) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
+    { int rc = model_at_rest(h); if (rc) return rc; }
     *n_out = 0;
     drop_shard_sizes(h);
     const int n = h->n_model;
@@ -3144,7 +3151,7 @@ int ssf_rehome_begin(ssf_handle* h, int32_t* table, int table_rows, int* n_out) 
 }
 int ssf_rehome_end(ssf_handle* h, const int32_t* table, int n_rec) {
     if (!h || n_rec < 0 || (!table && n_rec > 0)) return SSF_ERR_INVALID_ARG;
-    if (!h->pending.empty() || h->fusing) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
+    { int rc = model_at_rest(h); if (rc) return rc; }
     drop_shard_sizes(h);
     // the records addressed to this rank, split by the block they arrive in (table order kept).  A full shard turns the
     // surplus away, in table order, as a frame's migration does (k_migrate_in): their source shards have already let them

@@ -7,69 +7,42 @@
 //            CONSERVATIVE pixel box of the disc; every 16 x 16 screen tile the box touches gets one integer atomic count.
 //            A slot's number orders like the logical index ([visible | out-of-view], ssf_get_model's order), so the slot
 //            number breaks depth ties in the key; the out-of-view rows' logical index comes from an exclusive scan of their
-//            live flags (own scratch: the handle's Counters and d_bc_oov are not touched).
-//   * scan   exclusive scan of the tile counts (one workgroup); the host reads the total once and sizes the list buffer.
-//   * fill   (tile -> slot) lists with one returning atomic per list entry; the order inside a list is arbitrary.
-//   * tile   one 256-thread workgroup per tile, one pixel per thread: the tile's records are staged through LDS 256 at a time,
-//            every thread keeps the minimum key (bits(z) << 32 | slot) in registers, then resolves its outputs (winner's
+//            live flags (k_render_oov_count + k_render_scan into own scratch: the handle's Counters and d_bc_oov are not
+//            touched).  Slot -> row, the rank inside a block and the scan are the helpers of ssf_slots.hpp (k_render_prep).
+//   * scan   k_render_scan again: exclusive scan of the tile counts (one workgroup, 64-bit total); the host reads the total
+//            once and sizes the list buffer.
+//   * fill   k_render_fill: (tile -> slot) lists with one returning atomic per list entry; the order inside a list is arbitrary.
+//   * tile   k_render_tile: one 256-thread workgroup per tile, one pixel per thread: the tile's records are staged through
+//            LDS 256 at a time, every thread keeps the minimum key (bits(z) << 32 | slot) in registers, then resolves its outputs (winner's
 //            normal from its record, its colour gathered from the store).  The result depends on the integer minimum only:
 //            no float atomics, bitwise reproducible for any list order.
 // Statistics are exact integers: fragments and filled pixels are summed per workgroup (one 64-bit atomic each); rows_shown
 // counts the slots whose `seen` word a winner exchanges from an older render epoch to the current one.
-#include "ssf_device.hpp"
+#include "ssf_slots.hpp"
 
 namespace ssf {
 
-__device__ __forceinline__ int rlane() { return threadIdx.x & 63; }
 __device__ __forceinline__ unsigned long long rsum_u64(unsigned long long v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-__device__ __forceinline__ bool finite3(float a, float b, float c) { return isfinite(a) && isfinite(b) && isfinite(c); }
-
-// slot -> the row it reads: visible slots [0, nvs) are rows of the visible array, then 256-wide blocks of the out-of-view span
-__device__ __forceinline__ void slot_source(const RenderView& rv, uint32_t s, SurfelSoA& src, size_t& row) {
-    if (s < (uint32_t)rv.nvs) { src = rv.vis; row = s; }
-    else { src = rv.oov.rows; row = (size_t)rv.oov_head + (s - (uint32_t)rv.nvs); }
-}
 
 // ---- out-of-view rows: live counts per 256-slot block, then an exclusive scan (k_render_scan) --------------------------
-__global__ __launch_bounds__(256) void k_render_oov_count(RenderView rv, uint32_t* __restrict__ bc) {
+__global__ __launch_bounds__(256) void k_render_oov_count(ModelView mv, uint32_t* __restrict__ bc) {
     __shared__ int part[4];
-    const long long phys = (long long)rv.oov_head + (long long)blockIdx.x * 256 + threadIdx.x;
-    const bool lv = phys < rv.oov_tail && rv.oov.live[phys];
-    const int k = __popcll(__ballot(lv));
-    if (rlane() == 0) part[threadIdx.x >> 6] = k;
-    __syncthreads();
-    if (threadIdx.x == 0) bc[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+    size_t phys;
+    const int k = block_count256(span_live(mv.oov.live, mv.oov_head, mv.oov_tail, blockIdx.x * 256u + threadIdx.x, phys), part);
+    if (threadIdx.x == 0) bc[blockIdx.x] = k;
 }
 
-// exclusive scan of n counts in place (one workgroup of 1024); out[n] = the total (low 32 bits), cursor (nullable) = a copy of
+// exclusive scan of n counts in place (one workgroup of 1024); a[n] = the total (low 32 bits), cursor (nullable) = a copy of
 // the offsets, *total = the 64-bit total (a list longer than 2^32 - 1 entries is refused by the host, never wrapped)
 __global__ __launch_bounds__(1024) void k_render_scan(uint32_t* __restrict__ a, int n, uint32_t* __restrict__ cursor,
                                                       unsigned long long* __restrict__ total) {
-    __shared__ unsigned long long wtot[16];
-    __shared__ unsigned long long base;
-    if (threadIdx.x == 0) base = 0;
-    __syncthreads();
-    for (int i0 = 0; i0 < n; i0 += 1024) {
-        const int i = i0 + threadIdx.x;
-        const unsigned long long c = i < n ? a[i] : 0u;
-        unsigned long long v = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const unsigned long long up = __shfl_up(v, o, 64); if (rlane() >= o) v += up; }
-        if (rlane() == 63) wtot[threadIdx.x >> 6] = v;
-        __syncthreads();
-        unsigned long long before = 0, all = 0;
-        for (int w = 0; w < 16; w++) { const unsigned long long t = wtot[w]; if (w < (int)(threadIdx.x >> 6)) before += t; all += t; }
-        const unsigned long long ex = base + before + v - c;
-        if (i < n) { a[i] = (uint32_t)ex; if (cursor) cursor[i] = (uint32_t)ex; }
-        __syncthreads();
-        if (threadIdx.x == 0) base += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { a[n] = (uint32_t)base; *total = base; }
+    __shared__ unsigned long long tot[1];
+    workgroup_scan<1, unsigned long long>(a, n, cursor, tot);
+    if (threadIdx.x == 0) { a[n] = (uint32_t)tot[0]; *total = tot[0]; }
 }
 
 // ---- prep: one thread per slot ---------------------------------------------------------------------------------------
@@ -79,22 +52,9 @@ __global__ __launch_bounds__(256) void k_render_prep(RenderView rv, const uint32
     __shared__ int part[4];
     const RenderCam& K = rv.cam;
     const uint32_t s = blockIdx.x * 256 + threadIdx.x;
-    bool have; int lg = 0;
     SurfelSoA src; size_t row;
-    slot_source(rv, s, src, row);
-    if ((int)blockIdx.x < rv.nbv) {                       // (block-uniform branch)
-        have = (int)s < rv.n_visible;
-        lg = (int)s;
-    } else {
-        have = (long long)row < (long long)rv.oov_tail && rv.oov.live[row];
-        const unsigned long long m = __ballot(have);
-        const int wv = threadIdx.x >> 6;
-        if (rlane() == 0) part[wv] = __popcll(m);
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wv; w++) before += part[w];
-        lg = rv.n_visible + (int)bc[blockIdx.x - rv.nbv] + before + __popcll(m & ((1ull << rlane()) - 1ull));
-    }
+    const bool have = slot_row(rv.model, s, src, row);
+    const int lg = slot_logical256(rv.model, have, bc, part);
     uint2 box = make_uint2(1u, 1u);                       // empty: u0 = 1 > u1 = 0
     if (have) {
         const float conf = src.conf[row], dx = src.dims[2 * row], dy = src.dims[2 * row + 1];
@@ -153,14 +113,14 @@ __global__ __launch_bounds__(256) void k_render_prep(RenderView rv, const uint32
             }
         }
     }
-    if ((int)s < rv.nslots) rbox[s] = box;
+    if ((int)s < rv.model.nslots) rbox[s] = box;
 }
 
 // ---- fill: the (tile -> slot) lists -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_render_fill(RenderView rv, const uint2* __restrict__ rbox, uint32_t* __restrict__ cursor,
                                                      uint32_t* __restrict__ list) {
     const uint32_t s = blockIdx.x * 256 + threadIdx.x;
-    if ((int)s >= rv.nslots) return;
+    if ((int)s >= rv.model.nslots) return;
     const uint2 b = rbox[s];
     const int u0 = b.x & 0xFFFF, u1 = b.x >> 16, v0 = b.y & 0xFFFF, v1 = b.y >> 16;
     if (u0 > u1 || v0 > v1) return;
@@ -227,7 +187,7 @@ __global__ __launch_bounds__(256) void k_render_tile(RenderView rv, const float4
             m0 = den > 0.0f ? -D.x : D.x; m1 = den > 0.0f ? -D.y : D.y; m2 = den > 0.0f ? -D.z : D.z;
             lg = logical[s];
             SurfelSoA src; size_t row;
-            slot_source(rv, s, src, row);
+            (void)slot_row(rv.model, s, src, row);
             c0 = src.col[3 * row]; c1 = src.col[3 * row + 1]; c2 = src.col[3 * row + 2];
             filled = 1;
             if (atomicExch(&seen[s], epoch) != epoch) shown = 1;
@@ -243,7 +203,7 @@ __global__ __launch_bounds__(256) void k_render_tile(RenderView rv, const float4
         if (out.normal) { out.normal[3 * p] = m0; out.normal[3 * p + 1] = m1; out.normal[3 * p + 2] = m2; }
     }
     const unsigned long long f = rsum_u64(frag), fl = rsum_u64(filled), sh = rsum_u64(shown);
-    if (rlane() == 0) { red[0][threadIdx.x >> 6] = f; red[1][threadIdx.x >> 6] = fl; red[2][threadIdx.x >> 6] = sh; }
+    if (lane() == 0) { red[0][threadIdx.x >> 6] = f; red[1][threadIdx.x >> 6] = fl; red[2][threadIdx.x >> 6] = sh; }
     __syncthreads();
     if (threadIdx.x < 3) {
         const unsigned long long sum = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
@@ -255,17 +215,18 @@ __global__ __launch_bounds__(256) void k_render_tile(RenderView rv, const float4
 void launch_render_prep(hipStream_t st, const RenderView& rv, uint32_t* bc, float4* rec, uint2* rbox, int32_t* logical, uint32_t* tcnt,
                         uint32_t* cursor, unsigned long long* total) {
     ScopedKernel sk("render_prep", st);
-    if (rv.nbo > 0) {
-        hipLaunchKernelGGL(k_render_oov_count, dim3(rv.nbo), dim3(256), 0, st, rv, bc);
-        hipLaunchKernelGGL(k_render_scan, dim3(1), dim3(1024), 0, st, bc, rv.nbo, (uint32_t*)nullptr, total);
+    const ModelView& mv = rv.model;
+    if (mv.nbo > 0) {
+        hipLaunchKernelGGL(k_render_oov_count, dim3(mv.nbo), dim3(256), 0, st, mv, bc);
+        hipLaunchKernelGGL(k_render_scan, dim3(1), dim3(1024), 0, st, bc, mv.nbo, (uint32_t*)nullptr, total);
     }
-    if (rv.nbv + rv.nbo > 0)
-        hipLaunchKernelGGL(k_render_prep, dim3(rv.nbv + rv.nbo), dim3(256), 0, st, rv, bc, rec, rbox, logical, tcnt);
+    if (mv.nbv + mv.nbo > 0)
+        hipLaunchKernelGGL(k_render_prep, dim3(mv.nbv + mv.nbo), dim3(256), 0, st, rv, bc, rec, rbox, logical, tcnt);
     hipLaunchKernelGGL(k_render_scan, dim3(1), dim3(1024), 0, st, tcnt, rv.cam.ntx * rv.cam.nty, cursor, total);
 }
 void launch_render_fill(hipStream_t st, const RenderView& rv, const uint2* rbox, uint32_t* cursor, uint32_t* list) {
     ScopedKernel sk("render_fill", st);
-    if (rv.nslots > 0) hipLaunchKernelGGL(k_render_fill, dim3(rv.nslots / 256), dim3(256), 0, st, rv, rbox, cursor, list);
+    if (rv.model.nslots > 0) hipLaunchKernelGGL(k_render_fill, dim3(rv.model.nslots / 256), dim3(256), 0, st, rv, rbox, cursor, list);
 }
 void launch_render_tile(hipStream_t st, const RenderView& rv, const float4* rec, const uint2* rbox, const int32_t* logical,
                         const uint32_t* list, const uint32_t* toff, const RenderOut& out, uint32_t* seen, uint32_t epoch,

@@ -21,11 +21,10 @@
 //     iteration with exact sums; fern codes are a gather.
 #include <stdlib.h>
 #include <algorithm>
-#include "ssf_device.hpp"
+#include "ssf_slots.hpp"
 
 namespace ssf {
 
-__device__ __forceinline__ int lane() { return threadIdx.x & 63; }
 __device__ __forceinline__ long long wsum64(long long v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -1284,42 +1283,6 @@ __global__ __launch_bounds__(1024) void k_first_frame(SurfelSoA M, SurfelSoA F, 
 }
 
 // ---- stable partition over the model store (see OovStore in ssf_device.hpp) ----------------------------------------
-// exclusive scan of NC counters per block over nblocks blocks by one 1024-thread workgroup (one block per thread
-// and round: coalesced loads); totals -> tot[NC].  (Out-of-view store compaction only.)
-template <int NC>
-__device__ __forceinline__ void block_scan_counts(uint32_t* __restrict__ bc, int nblocks, uint32_t* tot /* LDS, NC */,
-                                                  uint32_t (*wtot)[6] /* LDS, 16 x 6 */) {
-    if (threadIdx.x < NC) tot[threadIdx.x] = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nblocks; b0 += 1024) {
-        const int b = b0 + threadIdx.x;
-        uint32_t c[NC], incl[NC];
-#pragma unroll
-        for (int s = 0; s < NC; s++) c[s] = (b < nblocks) ? bc[NC * b + s] : 0u;
-#pragma unroll
-        for (int s = 0; s < NC; s++) {
-            uint32_t v = c[s];
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(v, o, 64); if (lane() >= o) v += up; }
-            incl[s] = v;
-            if (lane() == 63) wtot[threadIdx.x >> 6][s] = v;
-        }
-        __syncthreads();
-        uint32_t before[NC], total[NC];
-#pragma unroll
-        for (int s = 0; s < NC; s++) { before[s] = 0; total[s] = 0; }
-        for (int w = 0; w < 16; w++)
-#pragma unroll
-            for (int s = 0; s < NC; s++) { const uint32_t t = wtot[w][s]; if (w < (int)(threadIdx.x >> 6)) before[s] += t; total[s] += t; }
-        if (b < nblocks)
-#pragma unroll
-            for (int s = 0; s < NC; s++) bc[NC * b + s] = tot[s] + before[s] + incl[s] - c[s];
-        __syncthreads();
-        if (threadIdx.x < NC) tot[threadIdx.x] += total[threadIdx.x];
-        __syncthreads();
-    }
-}
-
 // one model row in registers: all loads are issued before the first store (source and destination arrays may alias as
 // far as the compiler knows, so a field-by-field copy is a chain of dependent round trips)
 struct RowRegs { V3 pos, col, lab, r0, r1, r2; Sym3 shape; int s0, s1; float d0, d1, conf; };
@@ -1683,23 +1646,18 @@ __global__ __launch_bounds__(256) void k_rehome_count(SurfelSoA D, int n, int n_
     if (threadIdx.x < 3) bc[3 * blockIdx.x + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
 }
 __global__ __launch_bounds__(1024) void k_rehome_scan(uint32_t* __restrict__ bc, int nblocks, int* __restrict__ tot3) {
-    __shared__ uint32_t wtot[16][6];
     __shared__ uint32_t tot[3];
-    block_scan_counts<3>(bc, nblocks, tot, wtot);
+    workgroup_scan<3, uint32_t>(bc, nblocks, nullptr, tot);
     if (threadIdx.x < 3) tot3[threadIdx.x] = (int)tot[threadIdx.x];
 }
 __global__ __launch_bounds__(256) void k_rehome_scatter(SurfelSoA D, int n, int n_visible, int rank, int nranks, float tile,
                                                         const uint32_t* __restrict__ bc, SurfelSoA stay, int32_t* __restrict__ table, int table_rows) {
-    __shared__ int part[4][2];
-    const int i = blockIdx.x * blockDim.x + threadIdx.x, wv = threadIdx.x >> 6;
+    __shared__ int part[2][4];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int c = rehome_class(D, i, n, rank, nranks, tile);
-    const unsigned long long m0 = __ballot(c == 0), m1 = __ballot(c == 1);
-    if (lane() == 0) { part[wv][0] = __popcll(m0); part[wv][1] = __popcll(m1); }
-    __syncthreads();
+    const int r0 = block_rank256(c == 0, part[0]), r1 = block_rank256(c == 1, part[1]);      // (before any thread leaves)
     if (c > 1) return;
-    int before = 0;
-    for (int w = 0; w < wv; w++) before += part[w][c];
-    const size_t j = (size_t)bc[3 * blockIdx.x + c] + before + __popcll((c == 0 ? m0 : m1) & ((1ull << lane()) - 1ull));
+    const size_t j = (size_t)bc[3 * blockIdx.x + c] + (c == 0 ? r0 : r1);
     if (c == 0) { copy_row(D, (size_t)i, stay, j); return; }
     if (j >= (size_t)table_rows) return;                               // (the host sees the total and reports SSF_ERR_CAPACITY)
     const RowRegs r = load_row(D, (size_t)i);
@@ -1739,35 +1697,26 @@ void launch_rehome_unpack(hipStream_t st, const int32_t* table, int n, SurfelSoA
 }
 
 // ---- out-of-view store maintenance: stable compaction of the live rows into the other store -------------------
+// (head and tail come from the device counters: the launches are enqueued before the host knows them)
 __global__ __launch_bounds__(256) void k_oov_count(OovStore O, uint32_t* __restrict__ bc, const Counters* __restrict__ cnt) {
     __shared__ int part[4];
-    const long long phys = (long long)cnt->oov_head + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool lv = phys < cnt->oov_tail && O.live[phys];
-    const int k = __popcll(__ballot(lv));
-    if (lane() == 0) part[threadIdx.x >> 6] = k;
-    __syncthreads();
-    if (threadIdx.x == 0) bc[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+    size_t phys;
+    const int k = block_count256(span_live(O.live, cnt->oov_head, cnt->oov_tail, blockIdx.x * 256u + threadIdx.x, phys), part);
+    if (threadIdx.x == 0) bc[blockIdx.x] = k;
 }
 __global__ __launch_bounds__(1024) void k_oov_scan(uint32_t* __restrict__ bc, int nb_upper, const Counters* __restrict__ cnt) {
-    __shared__ uint32_t wtot[16][6];
     __shared__ uint32_t tot[1];
-    const int nb = min(nb_upper, (cnt->oov_tail - cnt->oov_head + 255) / 256);
-    block_scan_counts<1>(bc, nb, tot, wtot);
+    workgroup_scan<1, uint32_t>(bc, min(nb_upper, (cnt->oov_tail - cnt->oov_head + 255) / 256), nullptr, tot);
 }
 __global__ __launch_bounds__(256) void k_oov_compact(OovStore A, OovStore B, const uint32_t* __restrict__ bc, int new_head,
                                                      const Counters* __restrict__ cnt) {
     __shared__ int part[4];
-    const long long phys = (long long)cnt->oov_head + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool lv = phys < cnt->oov_tail && A.live[phys];
-    const unsigned long long mask = __ballot(lv);
-    const int wv = threadIdx.x >> 6;
-    if (lane() == 0) part[wv] = __popcll(mask);
-    __syncthreads();
+    size_t phys;
+    const bool lv = span_live(A.live, cnt->oov_head, cnt->oov_tail, blockIdx.x * 256u + threadIdx.x, phys);
+    const int before = block_rank256(lv, part);
     if (lv) {
-        int before = 0;
-        for (int w = 0; w < wv; w++) before += part[w];
-        const size_t j = (size_t)new_head + bc[blockIdx.x] + before + __popcll(mask & ((1ull << lane()) - 1ull));
-        copy_row(A.rows, (size_t)phys, B.rows, j);
+        const size_t j = (size_t)new_head + bc[blockIdx.x] + before;
+        copy_row(A.rows, phys, B.rows, j);
         B.live[j] = 1;
     }
 }
