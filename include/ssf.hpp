@@ -20,6 +20,7 @@
 #include "ssf_dynamic.h"
 #include "ssf_render.h"
 #include "ssf_graph.h"
+#include "ssf_keyframes.h"
 
 /* The reference's pose / matrix types (core/include/supersurfel_fusion/matrix_types.h:26-42), at GLOBAL scope as there,
  * so that the nodes' lines compile as they stand:
@@ -176,6 +177,16 @@ struct GraphBinding {
     std::vector<int32_t> idx4;
     size_t size() const { return idx4.size() / 4; }
 };
+
+/* one stored keyframe (ssf_keyframes.h): its rows, pose (12 floats, ssf_get_pose's layout), stamp and codes (one byte per fern) */
+struct Keyframe {
+    HostSupersurfels rows;
+    float pose[12];
+    int stamp = 0;
+    std::vector<uint8_t> codes;
+};
+/* what ssf_align / ssf_keyframes_align report */
+struct KeyframeAlignment { float rel_pose[12]; bool valid = false; int iters = 0, pairs = 0; };
 
 class SupersurfelFusion {
 public:
@@ -405,6 +416,60 @@ public:
             throw std::runtime_error("applyGraph: one rotation and one translation per node");
         check(ssf_graph_apply(need(), reinterpret_cast<const float*>(rotations.data()), reinterpret_cast<const float*>(translations.data())));
     }
+    /* The keyframe database of loop detection, kept on the device (ssf_keyframes.h; exported by libssf_hip.so only):
+     * configureKeyframes once, considerKeyframe after every frame, alignKeyframe for a loop candidate of its record.
+     * INTEGRATION.md section 2 has the call sequence. */
+    static ssf_keyframes_params defaultKeyframesParams() { ssf_keyframes_params p; ssf_keyframes_default_params(&p); return p; }
+    void configureKeyframes(const ssf_keyframes_params& p) { check(ssf_keyframes_configure(need(), &p)); }
+    void configureKeyframes() { configureKeyframes(defaultKeyframesParams()); }
+    void clearKeyframes() { check(ssf_keyframes_clear(need())); }
+    int nbKeyframes() { int n = 0; check(ssf_keyframes_info(need(), nullptr, &n, nullptr, nullptr)); return n; }
+    void setFerns(const std::vector<ssf_fern>& ferns) { check(ssf_keyframes_set_ferns(need(), ferns.data(), (int)ferns.size())); }
+    std::vector<ssf_fern> getFerns() {
+        std::vector<ssf_fern> f((size_t)keyframeFerns());
+        check(ssf_keyframes_get_ferns(need(), f.data(), (int)f.size()));
+        return f;
+    }
+    /* the current frame's codes, one byte per fern */
+    std::vector<uint8_t> encodeKeyframe() {
+        std::vector<uint8_t> c((size_t)keyframeFerns());
+        check(ssf_keyframes_encode(need(), c.data(), (int)c.size()));
+        return c;
+    }
+    /* encode the current frame, search, add it when the view is new: the per-frame call */
+    ssf_keyframe_result considerKeyframe() { ssf_keyframe_result r; check(ssf_keyframes_consider(need(), &r)); return r; }
+    /* search only: the current frame's codes ... */
+    ssf_keyframe_result queryKeyframes(int min_gap = -1, int k = SSF_KEYFRAMES_MAX_CANDIDATES) {
+        ssf_keyframe_result r; check(ssf_keyframes_query(need(), nullptr, 0, min_gap, k, &r)); return r;
+    }
+    /* ... or the caller's, with the caller's stamp */
+    ssf_keyframe_result queryKeyframes(const std::vector<uint8_t>& codes, int stamp, int min_gap = -1, int k = SSF_KEYFRAMES_MAX_CANDIDATES) {
+        if (codes.size() != (size_t)keyframeFerns()) throw std::runtime_error("queryKeyframes: one code per fern");
+        ssf_keyframe_result r; check(ssf_keyframes_query(need(), codes.data(), stamp, min_gap, k, &r)); return r;
+    }
+    int addKeyframe() { int id = -1; check(ssf_keyframes_add(need(), &id)); return id; }
+    int putKeyframe(Keyframe& kf) {
+        if (kf.codes.size() != (size_t)keyframeFerns()) throw std::runtime_error("putKeyframe: one code per fern");
+        ssf_surfels v = kf.rows.view(); int id = -1;
+        check(ssf_keyframes_put(need(), kf.codes.data(), &v, kf.rows.size, kf.pose, kf.stamp, &id));
+        return id;
+    }
+    Keyframe getKeyframe(int id) {
+        Keyframe kf; int n = 0;
+        check(ssf_keyframes_get(need(), id, nullptr, 0, &n, nullptr, nullptr, nullptr));
+        kf.rows.resize(n); kf.codes.resize((size_t)keyframeFerns());
+        ssf_surfels v = kf.rows.view();
+        check(ssf_keyframes_get(need(), id, &v, n, &n, kf.pose, &kf.stamp, kf.codes.data()));
+        return kf;
+    }
+    void setKeyframePose(int id, const float* pose12) { check(ssf_keyframes_set_pose(need(), id, pose12)); }
+    /* register stored keyframe id against the current frame (ssf_align's outputs); init_pose12 may be null */
+    KeyframeAlignment alignKeyframe(int id, const float* init_pose12 = nullptr, bool use_conf = false) {
+        KeyframeAlignment a; int valid = 0;
+        check(ssf_keyframes_align(need(), id, init_pose12, use_conf ? 1 : 0, a.rel_pose, &valid, &a.iters, &a.pairs));
+        a.valid = valid != 0;
+        return a;
+    }
     /* the same two images without OpenCV */
     std::vector<uint8_t> getSuperpixelSegIm() {
         std::vector<uint8_t> v((size_t)3 * width_ * height_);
@@ -416,6 +481,7 @@ public:
         check(ssf_get_plane_depth(need(), v.data()));
         return v;
     }
+    int keyframeFerns() { ssf_keyframes_params p; check(ssf_keyframes_info(need(), nullptr, nullptr, nullptr, &p)); return p.n_ferns; }
     /* getPose(): supersurfel_fusion.hpp:89 -- `const Transform3&`, camera-to-map, valid until the next call on this
      * object (the reference returns a reference to its member; so does this, refreshed from the library) */
     const Transform3& getPose() const {

@@ -83,6 +83,15 @@ RENDER_SYMBOLS = ["ssf_render_default_params", "ssf_render_model"]
 # the deformation graph's nodes and per-row binding (include/ssf_graph.h): exported by the HIP product only, not part of ssf.h
 GRAPH_SYMBOLS = ["ssf_graph_default_params", "ssf_graph_build", "ssf_graph_get_nodes", "ssf_graph_get_binding",
                  "ssf_graph_bind_points", "ssf_graph_apply", "ssf_graph_info"]
+# the fern-coded keyframe database (include/ssf_keyframes.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
+KEYFRAME_SYMBOLS = ["ssf_keyframes_default_params", "ssf_keyframes_configure", "ssf_keyframes_set_ferns", "ssf_keyframes_get_ferns",
+                    "ssf_keyframes_encode", "ssf_keyframes_query", "ssf_keyframes_add", "ssf_keyframes_consider", "ssf_keyframes_put",
+                    "ssf_keyframes_get", "ssf_keyframes_set_pose", "ssf_keyframes_align", "ssf_keyframes_info", "ssf_keyframes_clear"]
+KEYFRAMES_MAX_FERNS = 4096
+KEYFRAMES_MAX_CANDIDATES = 8
+# ssf_fern as a numpy record (12 bytes)
+FERN_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("pad", np.uint8),
+                       ("depth_mm", np.uint32)])
 # the images of ssf_render_model, in its argument order: name, dtype, per-pixel shape
 RENDER_OUTPUTS = (("depth", np.float32, ()), ("index", np.int32, ()), ("rgb8", np.uint8, (3,)), ("color", np.float32, (3,)),
                   ("normal", np.float32, (3,)))
@@ -115,6 +124,30 @@ class SsfRenderStats(C.Structure):
 class SsfGraphParams(C.Structure):
     """ssf_graph_params (include/ssf_graph.h)"""
     _fields_ = [("stride", C.c_int), ("look", C.c_int), ("min_conf", C.c_float)]
+
+
+class SsfKeyframesParams(C.Structure):
+    """ssf_keyframes_params (include/ssf_keyframes.h)"""
+    _fields_ = [("cell", C.c_int), ("n_ferns", C.c_int), ("seed", C.c_uint64), ("max_keyframes", C.c_int), ("min_gap", C.c_int),
+                ("max_rows", C.c_int64), ("new_ratio", C.c_float), ("loop_ratio", C.c_float)]
+
+    def as_dict(self):
+        return {nm: getattr(self, nm) for nm, _ in self._fields_}
+
+
+class SsfKeyframeCandidate(C.Structure):
+    _fields_ = [(nm, C.c_int32) for nm in ("id", "diff", "stamp", "loop")]
+
+
+class SsfKeyframeResult(C.Structure):
+    """ssf_keyframe_result (include/ssf_keyframes.h)"""
+    _fields_ = [(nm, C.c_int32) for nm in ("added", "id", "full", "min_diff_all", "n_keyframes", "n_candidates")] + \
+               [("candidates", SsfKeyframeCandidate * KEYFRAMES_MAX_CANDIDATES)]
+
+    def as_dict(self):
+        c = [dict(id=int(e.id), diff=int(e.diff), stamp=int(e.stamp), loop=bool(e.loop)) for e in self.candidates[:self.n_candidates]]
+        return dict(added=bool(self.added), id=int(self.id), full=bool(self.full), min_diff_all=int(self.min_diff_all),
+                    n_keyframes=int(self.n_keyframes), candidates=c)
 
 
 class Library:
@@ -217,6 +250,23 @@ class Library:
             L.ssf_graph_bind_points.argtypes = [vp, vp, vp, C.c_int, vp, vp]
             L.ssf_graph_apply.argtypes = [vp, vp, vp]
             L.ssf_graph_info.argtypes = [vp, ip, ip, ip]
+        self.has_keyframes = all(hasattr(L, nm) for nm in KEYFRAME_SYMBOLS)
+        if self.has_keyframes:
+            ip, kp, kr = C.POINTER(C.c_int), C.POINTER(SsfKeyframesParams), C.POINTER(SsfKeyframeResult)
+            L.ssf_keyframes_default_params.argtypes = [kp]
+            L.ssf_keyframes_configure.argtypes = [vp, kp]
+            L.ssf_keyframes_set_ferns.argtypes = [vp, vp, C.c_int]
+            L.ssf_keyframes_get_ferns.argtypes = [vp, vp, C.c_int]
+            L.ssf_keyframes_encode.argtypes = [vp, vp, C.c_int]
+            L.ssf_keyframes_query.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, kr]
+            L.ssf_keyframes_add.argtypes = [vp, ip]
+            L.ssf_keyframes_consider.argtypes = [vp, kr]
+            L.ssf_keyframes_put.argtypes = [vp, vp, C.POINTER(SsfSurfels), C.c_int, vp, C.c_int, ip]
+            L.ssf_keyframes_get.argtypes = [vp, C.c_int, C.POINTER(SsfSurfels), C.c_int, ip, vp, ip, vp]
+            L.ssf_keyframes_set_pose.argtypes = [vp, C.c_int, vp]
+            L.ssf_keyframes_align.argtypes = [vp, C.c_int, vp, C.c_int, vp, ip, ip, ip]
+            L.ssf_keyframes_info.argtypes = [vp, ip, ip, C.POINTER(C.c_int64), kp]
+            L.ssf_keyframes_clear.argtypes = [vp]
 
     @property
     def backend(self):
@@ -730,6 +780,146 @@ class Fusion:
         res = SsfFrameResult()
         self._ck(self.L.lib.ssf_stage_fuse_end_device(self.h, C.c_void_p(d_table_ptr), C.byref(res)), "ssf_stage_fuse_end_device")
         return res.as_dict()
+
+    # ---- the fern-coded keyframe database (include/ssf_keyframes.h) ---------------------------------
+    def _need_keyframes(self, symbol):
+        if not self.L.has_keyframes:
+            raise SsfError("%s does not export %s: it keeps no keyframe database (include/ssf_keyframes.h, HIP product only)"
+                           % (self.L.path, symbol))
+
+    def keyframes_default_params(self):
+        """ssf_keyframes_default_params as a dict"""
+        self._need_keyframes("ssf_keyframes_default_params")
+        p = SsfKeyframesParams()
+        rc = self.L.lib.ssf_keyframes_default_params(C.byref(p))
+        if rc != 0:
+            raise SsfError("ssf_keyframes_default_params failed (%d)" % rc)
+        return p.as_dict()
+
+    def keyframes_configure(self, **kw):
+        """Allocate the database on the device and generate the fern table (ssf_keyframes_configure); keywords: the fields of
+        ssf_keyframes_params (cell, n_ferns, seed, max_keyframes, min_gap, max_rows, new_ratio, loop_ratio)"""
+        self._need_keyframes("ssf_keyframes_configure")
+        p = SsfKeyframesParams()
+        self.L.lib.ssf_keyframes_default_params(C.byref(p))
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise AttributeError("ssf_keyframes_params has no field %r" % k)
+            setattr(p, k, v)
+        self._ck(self.L.lib.ssf_keyframes_configure(self.h, C.byref(p)), "ssf_keyframes_configure")
+
+    def keyframes_info(self):
+        """dict(configured, n_keyframes, rows_used, params) (ssf_keyframes_info)"""
+        self._need_keyframes("ssf_keyframes_info")
+        c, n, r, p = C.c_int(0), C.c_int(0), C.c_int64(0), SsfKeyframesParams()
+        self._ck(self.L.lib.ssf_keyframes_info(self.h, C.byref(c), C.byref(n), C.byref(r), C.byref(p)), "ssf_keyframes_info")
+        return dict(configured=bool(c.value), n_keyframes=n.value, rows_used=r.value, params=p.as_dict())
+
+    def _kf_n(self):
+        return self.keyframes_info()["params"]["n_ferns"]
+
+    def keyframes_set_ferns(self, ferns):
+        """Replace the fern table: a FERN_DTYPE record array of n_ferns entries (ssf_keyframes_set_ferns)"""
+        self._need_keyframes("ssf_keyframes_set_ferns")
+        f = np.ascontiguousarray(ferns, FERN_DTYPE)
+        self._ck(self.L.lib.ssf_keyframes_set_ferns(self.h, _ptr(f), len(f)), "ssf_keyframes_set_ferns")
+
+    def keyframes_get_ferns(self):
+        """The fern table in force as a FERN_DTYPE record array (ssf_keyframes_get_ferns)"""
+        self._need_keyframes("ssf_keyframes_get_ferns")
+        f = np.zeros(KEYFRAMES_MAX_FERNS, FERN_DTYPE)
+        self._ck(self.L.lib.ssf_keyframes_get_ferns(self.h, _ptr(f), len(f)), "ssf_keyframes_get_ferns")
+        return f[:self._kf_n()].copy()
+
+    def keyframes_encode(self):
+        """The current frame's codes, one byte per fern (ssf_keyframes_encode)"""
+        self._need_keyframes("ssf_keyframes_encode")
+        codes = np.zeros(KEYFRAMES_MAX_FERNS, np.uint8)
+        self._ck(self.L.lib.ssf_keyframes_encode(self.h, _ptr(codes), len(codes)), "ssf_keyframes_encode")
+        return codes[:self._kf_n()].copy()
+
+    def keyframes_query(self, codes=None, stamp=0, min_gap=-1, k=KEYFRAMES_MAX_CANDIDATES):
+        """Search the stored keyframes (ssf_keyframes_query): codes None = the current frame's (with the handle's stamp), else
+        n_ferns bytes with `stamp`; min_gap < 0 = the configured one.  Returns the record as a dict."""
+        self._need_keyframes("ssf_keyframes_query")
+        if codes is not None:
+            codes = np.ascontiguousarray(codes, np.uint8)
+            if len(codes) != self._kf_n():
+                raise SsfError("keyframes_query: %d codes, the database has %d ferns" % (len(codes), self._kf_n()))
+        res = SsfKeyframeResult()
+        self._ck(self.L.lib.ssf_keyframes_query(self.h, _ptr(codes), int(stamp), int(min_gap), int(k), C.byref(res)), "ssf_keyframes_query")
+        return res.as_dict()
+
+    def keyframes_add(self):
+        """The current frame becomes a keyframe (ssf_keyframes_add); returns its id"""
+        self._need_keyframes("ssf_keyframes_add")
+        i = C.c_int(-1)
+        self._ck(self.L.lib.ssf_keyframes_add(self.h, C.byref(i)), "ssf_keyframes_add")
+        return i.value
+
+    def keyframes_consider(self):
+        """Encode the current frame, search, add it when the view is new (ssf_keyframes_consider); returns the record as a dict"""
+        self._need_keyframes("ssf_keyframes_consider")
+        res = SsfKeyframeResult()
+        self._ck(self.L.lib.ssf_keyframes_consider(self.h, C.byref(res)), "ssf_keyframes_consider")
+        return res.as_dict()
+
+    def keyframes_put(self, codes, rows, pose, stamp):
+        """A keyframe from host data (ssf_keyframes_put): codes n_ferns bytes, rows a dict of the SURFEL_FIELDS arrays (or None for
+        no rows), pose 12 floats; returns its id"""
+        self._need_keyframes("ssf_keyframes_put")
+        codes = np.ascontiguousarray(codes, np.uint8)
+        if len(codes) != self._kf_n():
+            raise SsfError("keyframes_put: %d codes, the database has %d ferns" % (len(codes), self._kf_n()))
+        pose = np.ascontiguousarray(pose, np.float32)
+        if pose.size != 12:
+            raise SsfError("keyframes_put: a pose is 12 floats")
+        n, st, keep = 0, None, []
+        if rows is not None and len(rows["confidences"]) > 0:
+            n = len(rows["confidences"])
+            keep = [np.ascontiguousarray(rows[name], dt) for name, _, dt in SURFEL_FIELDS]
+            for a, (name, k, _) in zip(keep, SURFEL_FIELDS):
+                if a.size != n * k:
+                    raise SsfError("keyframes_put: rows[%r] has %d values for %d rows" % (name, a.size, n))
+            st = C.byref(SsfSurfels(*[a.ctypes.data_as(C.c_void_p) for a in keep]))
+        i = C.c_int(-1)
+        self._ck(self.L.lib.ssf_keyframes_put(self.h, _ptr(codes), st, n, _ptr(pose), int(stamp), C.byref(i)), "ssf_keyframes_put")
+        return i.value
+
+    def keyframes_get(self, kf_id):
+        """dict(rows (the SURFEL_FIELDS arrays), pose, stamp, codes) of one stored keyframe (ssf_keyframes_get)"""
+        self._need_keyframes("ssf_keyframes_get")
+        n, stamp = C.c_int(0), C.c_int(0)
+        self._ck(self.L.lib.ssf_keyframes_get(self.h, int(kf_id), None, 0, C.byref(n), None, None, None), "ssf_keyframes_get")
+        arrs, st = _alloc_surfels(n.value)
+        pose, codes = np.zeros(12, np.float32), np.zeros(KEYFRAMES_MAX_FERNS, np.uint8)
+        self._ck(self.L.lib.ssf_keyframes_get(self.h, int(kf_id), C.byref(st), n.value, C.byref(n), _ptr(pose), C.byref(stamp), _ptr(codes)),
+                 "ssf_keyframes_get")
+        return dict(rows=arrs, pose=pose, stamp=stamp.value, codes=codes[:self._kf_n()].copy())
+
+    def keyframes_set_pose(self, kf_id, pose):
+        """Move a stored keyframe's pose (ssf_keyframes_set_pose)"""
+        self._need_keyframes("ssf_keyframes_set_pose")
+        pose = np.ascontiguousarray(pose, np.float32)
+        if pose.size != 12:
+            raise SsfError("keyframes_set_pose: a pose is 12 floats")
+        self._ck(self.L.lib.ssf_keyframes_set_pose(self.h, int(kf_id), _ptr(pose)), "ssf_keyframes_set_pose")
+
+    def keyframes_align(self, kf_id, init_pose=None, use_conf=False):
+        """align() with the stored rows of keyframe kf_id as sources, nothing row-sized crossing the bus (ssf_keyframes_align).
+        Returns dict(rel_pose (12,), valid, iters, pairs)."""
+        self._need_keyframes("ssf_keyframes_align")
+        init = None if init_pose is None else np.ascontiguousarray(init_pose, np.float32)
+        rel = np.zeros(12, np.float32)
+        valid, iters, pairs = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._ck(self.L.lib.ssf_keyframes_align(self.h, int(kf_id), _ptr(init), 1 if use_conf else 0, _ptr(rel), C.byref(valid),
+                                                C.byref(iters), C.byref(pairs)), "ssf_keyframes_align")
+        return dict(rel_pose=rel, valid=bool(valid.value), iters=iters.value, pairs=pairs.value)
+
+    def keyframes_clear(self):
+        """Free the database (ssf_keyframes_clear); keyframes_configure may be called again"""
+        self._need_keyframes("ssf_keyframes_clear")
+        self._ck(self.L.lib.ssf_keyframes_clear(self.h), "ssf_keyframes_clear")
 
     # ---- loop closure: registration of a keyframe's supersurfels against the current frame ---------
     def align(self, source, init_pose=None):

@@ -26,6 +26,7 @@
 #include "../../include/ssf_dynamic.h"
 #include "../../include/ssf_render.h"
 #include "../../include/ssf_graph.h"
+#include "../../include/ssf_keyframes.h"
 
 // SSF_EXPERIMENTS: the laboratory build (csrc/variants/lab/libssf_hip.so, `make lab`): the measurement arms and environment
 // switches behind DESIGN.md's A/B tables.  The PRODUCT library is built without it: it reads no environment variable and
@@ -406,6 +407,20 @@ void launch_graph_sample(hipStream_t st, const ModelView& mv, const uint32_t* bc
 void launch_graph_bind(hipStream_t st, const ModelView& mv, const uint32_t* bc, const float4* nodes, int m, int look, float* w4, int32_t* i4);
 void launch_graph_bind_points(hipStream_t st, const float* pts, const int32_t* t0, int n, const float4* nodes, int m, int look, float* w4,
                               int32_t* i4);
+// ---- the fern-coded keyframe database (ssf_keyframes.h; ssf_keyframes.hip) ----------------------------------------------
+// the row pool: a keyframe's rows are consecutive, in ssf_surfels' layout (what ssf_keyframes_get / _put copy as they are)
+struct KfPool { float* pos; float* col; int32_t* stamps; float* orient; float* shape; float* dims; float* conf; };
+#define SSF_KF_REC_WORDS 40                       // ssf_keyframe_result (38 words), the rows stored, one spare
+// one query: n ferns in `words` packed words, K stored keyframes; mode 0 query, 1 consider, 2 add (see k_kf_select)
+struct KfQuery { int words, n, K, max_keyframes, mode, kmax, stamp, min_gap; long long rows_used, max_rows; float new_ratio, loop_ratio; };
+// ferns[i] = (x | y << 16, r | g << 8 | b << 16, depth_mm, 0); codes: `words` packed words of the frame (rgba, plane_depth)
+void launch_kf_encode(hipStream_t st, const uint32_t* rgba, const float* plane_depth, int W, int B, float zmin, float zmax,
+                      const uint4* ferns, int n, int words, uint32_t* codes);
+void launch_kf_unpack(hipStream_t st, const uint32_t* codes, int n, uint8_t* out);
+void launch_kf_search(hipStream_t st, const uint32_t* q, const uint32_t* table, int words, int K, uint32_t* diff);
+void launch_kf_select(hipStream_t st, const KfQuery& qy, const uint32_t* q, uint32_t* table, int32_t* stamps, const uint32_t* diff,
+                      const SurfelSoA& frame, int S, const KfPool& pool, int32_t* rec);
+void launch_kf_align_prep(hipStream_t st, const float* col, const float* orient, int n, float* lab, float* nrm);
 // one iteration of the loop-closure registration against a frame; out40: see k_align
 void launch_align(hipStream_t st, const Cam& cam, const float* spos, const float* slab, const float* snrm, const float* sconf,
                   int n, SurfelSoA frame, const int32_t* label, const float* plane_depth, Rt T, long long* out40);

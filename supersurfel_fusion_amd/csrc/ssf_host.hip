@@ -539,6 +539,7 @@ struct ExtractCtx {
     // a mask.  A batch with any bit set runs the counting instantiations (k_render_moments<., true>, k_finalize_surfels<true>),
     // whose segmentation chain is captured in a graph of its own.
     uint8_t* d_pixmask = nullptr; uint32_t* d_pixcnt = nullptr; unsigned pixmask_bits = 0;
+    bool from_tables = false;                     // the batch came in through ssf_submit_frame_tables: its slot has no colour map
     hipGraph_t graph_pm[SSF_MAX_BATCH + 1] = {}; hipGraphExec_t exec_pm[SSF_MAX_BATCH + 1] = {};
 };
 // the frame the track/fuse chain works on: slot views into its context
@@ -547,6 +548,8 @@ struct ActiveFrame {
     unsigned long long* d_best = nullptr; uint8_t* d_matched = nullptr;
     ExtractCtx* ctx = nullptr; int slot = 0;
     bool pixmask = false;                         // the frame was submitted with a pixel mask: ssf_get_dynamic_superpixels reads its counts
+    bool has_rgba = false;                        // the frame was extracted here: maps.rgba is its colour map (ssf_keyframes.h reads it)
+    bool activated = false;                       // a submitted frame has been made the current one (ssf_create only points at slot 0)
 };
 
 // Round 6: the tile-sorted copy (ssf_tile_rows.inc) in the product, for LARGE visible sets.  At BASELINE config 3 (940 k visible
@@ -600,6 +603,19 @@ struct GraphWs {
     float* w4 = nullptr; int32_t* idx4 = nullptr; int* mm = nullptr; size_t slots = 0;       // per slot; w4 / idx4 per logical row
     float4* nodes = nullptr; float* npos3 = nullptr; int32_t* nrow = nullptr; size_t node_cap = 0;   // per node, in time order
     int m = 0, rows = 0, look = 0; bool built = false; unsigned long long gen = 0;          // valid <=> built && gen == h->model_gen
+};
+// the keyframe database of ssf_keyframes.h: everything is allocated by ssf_keyframes_configure, as a whole or not at all
+// (DevBufs::grow), and freed by ssf_keyframes_clear / ssf_destroy.  The host mirrors what it needs to address a keyframe (its
+// first pool row, row count, stamp, pose); codes, stamps and rows live on the device.
+struct KeyframeMeta { long long first; int rows; int stamp; float pose[12]; };
+struct KeyframeWs {
+    DevBufs bufs;
+    ssf_keyframes_params p{}; bool on = false;
+    int words = 0, gw = 0, gh = 0;
+    uint4* ferns = nullptr; uint32_t* q = nullptr; uint32_t* table = nullptr; int32_t* stamps = nullptr; uint32_t* diff = nullptr;
+    int32_t* rec = nullptr; uint8_t* bytes = nullptr;
+    KfPool pool{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    std::vector<ssf_fern> host_ferns; std::vector<KeyframeMeta> kfs; long long rows_used = 0;
 };
 struct ssf_handle {
     ssf_config cfg;
@@ -693,6 +709,7 @@ struct ssf_handle {
     double host_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // debug: submit | icp loop | match+fuse | frames | extract ready at activation | first icp iteration
     RenderWs render;                              // ssf_render_model (ssf_render.h)
     GraphWs graph;                                // ssf_graph_* (ssf_graph.h)
+    KeyframeWs kf;                                // ssf_keyframes_* (ssf_keyframes.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense)
 };
 static std::string g_create_err;
@@ -962,6 +979,7 @@ static int submit_extract(ssf_handle* h, const void* rgb, const void* depth, int
     const int b = c.count;
     if (b == 0) {
         c.stamp0 = h->stamp + h->stamp_bias + (int)h->pending.size(); c.mask_bits = 0; c.pixmask_bits = 0; c.epoch0 = h->extract_ordinal;
+        c.from_tables = false;
         if (h->deal && h->comm) { c.deal_batch = h->deal_batches++; c.mine = (int)(c.deal_batch % (long long)h->cfg.nranks) == h->cfg.rank; }
         else c.mine = true;
     }
@@ -999,6 +1017,7 @@ static int submit_tables(ssf_handle* h, const int32_t* label, const float* plane
     if (multi && c.consumed_valid) HCK(hipStreamWaitEvent(st, c.ev_consumed, 0));
     c.stamp0 = h->stamp + h->stamp_bias + (int)h->pending.size(); c.mask_bits = 0; c.pixmask_bits = 0; c.epoch0 = h->extract_ordinal;
     h->extract_ordinal++;                          // (the RANSAC epoch advances as if the frame had been extracted here)
+    c.from_tables = true;
     const size_t P = (size_t)h->cfg.width * h->cfg.height, S = (size_t)h->S;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     c.timed = false;
@@ -1049,6 +1068,7 @@ static int activate_oldest(ssf_handle* h) {
     a.maps = batch_slot(c.maps, fr.second); a.frame = batch_slot(c.frame, off);
     a.d_best = slab_shift(c.d_best, off); a.d_matched = slab_shift(c.d_matched, off);
     a.ctx = &c; a.slot = fr.second; a.pixmask = ((c.pixmask_bits >> fr.second) & 1u) != 0;
+    a.has_rgba = !c.from_tables && c.mine; a.activated = true;
     h->have_frame = true;
     return SSF_OK;
 }
@@ -1852,6 +1872,7 @@ void ssf_destroy(ssf_handle* h) {
     for (void* p : h->allocs) (void)hipFree(p);
     h->render.bufs.release();
     h->graph.bufs.release();
+    h->kf.bufs.release();
     if (h->mb_host) (void)hipHostFree(h->mb_host);
     for (int i = 0; i < 4; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     for (auto& r : h->timer.pool_free) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -2178,34 +2199,11 @@ int ssf_pipeline_capacity(const ssf_handle* h) { return h ? (int)h->ctx.size() *
 int ssf_can_submit(const ssf_handle* h) { return (h && !h->ctx[h->open_ctx].launched) ? 1 : 0; }
 
 // ---- loop-closure registration + fern codes -------------------------------------
-int ssf_align(ssf_handle* h, const ssf_surfels* src, int n, const float* init_pose, float* rel_pose, int* valid, int* iters,
-              int* pairs_last) {
-    if (!h || !src || n < 0 || !rel_pose || !valid || !src->positions || !src->colors || !src->orientations) return SSF_ERR_INVALID_ARG;
-    TimerScope ts(h);
-    // sources: positions, Lab of the colours (same inline function as the kernels), normals = rows[2]
-    const size_t N = (size_t)std::max(n, 1);
-    std::vector<float> lab(3 * N), nrm(3 * N);
-    for (int i = 0; i < n; i++) {
-        const V3 l = rgb_to_lab(v3(src->colors[3 * i], src->colors[3 * i + 1], src->colors[3 * i + 2]));
-        lab[3 * i] = l.x; lab[3 * i + 1] = l.y; lab[3 * i + 2] = l.z;
-        for (int c = 0; c < 3; c++) nrm[3 * i + c] = src->orientations[9 * i + 6 + c];
-    }
-    float *d_pos = nullptr, *d_lab = nullptr, *d_nrm = nullptr, *d_conf = nullptr; long long* d_out = nullptr;
-    DevTemps tmp;
-    HCK(tmp.take(&d_pos, 12 * N)); HCK(tmp.take(&d_lab, 12 * N)); HCK(tmp.take(&d_nrm, 12 * N));
-    HCK(tmp.take(&d_out, 40 * sizeof(long long)));
-    if (src->confidences) HCK(tmp.take(&d_conf, 4 * N));
+// the iterations of align on device sources (ssf_align: uploaded; ssf_keyframes_align: derived from the stored rows); d_out: 40 i64
+static int align_loop(ssf_handle* h, const float* d_pos, const float* d_lab, const float* d_nrm, const float* d_conf, int n, long long* d_out,
+                      const float* init_pose, float* rel_pose, int* valid, int* iters, int* pairs_last) {
     hipStream_t st = h->stream;
     int rc = SSF_OK;
-    auto cleanup = [&]() {};
-    if (n > 0) {
-        if (hipMemcpyAsync(d_pos, src->positions, 12 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(d_lab, lab.data(), 12 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(d_nrm, nrm.data(), 12 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess ||
-            (d_conf && hipMemcpyAsync(d_conf, src->confidences, 4 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess)) {
-            cleanup(); h->err = "upload of the source supersurfels failed"; return SSF_ERR_DEVICE;
-        }
-    }
     M3 R_init = m3_identity(); V3 t_init = v3(0, 0, 0);
     if (init_pose) { const Rt p0 = pose_from12(init_pose); R_init = p0.R; t_init = p0.t; }
     double tf_inc[16], JtJ[36];
@@ -2241,7 +2239,6 @@ int ssf_align(ssf_handle* h, const ssf_surfels* src, int n, const float* init_po
         align_increment(JtJ, Jtr, scale, cs, ct, tf_iter);
         mat4_lmul(tf_iter, tf_inc);
     }
-    cleanup();
     if (rc) return rc;
     double cov[36];
     mat6_inverse_lu(JtJ, cov);
@@ -2257,6 +2254,34 @@ int ssf_align(ssf_handle* h, const ssf_surfels* src, int n, const float* init_po
     if (pairs_last) *pairs_last = pairs;
     if (h->cfg.profile == 1) timer_collect(&h->timer);
     return SSF_OK;
+}
+int ssf_align(ssf_handle* h, const ssf_surfels* src, int n, const float* init_pose, float* rel_pose, int* valid, int* iters,
+              int* pairs_last) {
+    if (!h || !src || n < 0 || !rel_pose || !valid || !src->positions || !src->colors || !src->orientations) return SSF_ERR_INVALID_ARG;
+    TimerScope ts(h);
+    // sources: positions, Lab of the colours (same inline function as the kernels), normals = rows[2]
+    const size_t N = (size_t)std::max(n, 1);
+    std::vector<float> lab(3 * N), nrm(3 * N);
+    for (int i = 0; i < n; i++) {
+        const V3 l = rgb_to_lab(v3(src->colors[3 * i], src->colors[3 * i + 1], src->colors[3 * i + 2]));
+        lab[3 * i] = l.x; lab[3 * i + 1] = l.y; lab[3 * i + 2] = l.z;
+        for (int c = 0; c < 3; c++) nrm[3 * i + c] = src->orientations[9 * i + 6 + c];
+    }
+    float *d_pos = nullptr, *d_lab = nullptr, *d_nrm = nullptr, *d_conf = nullptr; long long* d_out = nullptr;
+    DevTemps tmp;
+    HCK(tmp.take(&d_pos, 12 * N)); HCK(tmp.take(&d_lab, 12 * N)); HCK(tmp.take(&d_nrm, 12 * N));
+    HCK(tmp.take(&d_out, 40 * sizeof(long long)));
+    if (src->confidences) HCK(tmp.take(&d_conf, 4 * N));
+    hipStream_t st = h->stream;
+    if (n > 0) {
+        if (hipMemcpyAsync(d_pos, src->positions, 12 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(d_lab, lab.data(), 12 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(d_nrm, nrm.data(), 12 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess ||
+            (d_conf && hipMemcpyAsync(d_conf, src->confidences, 4 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess)) {
+            h->err = "upload of the source supersurfels failed"; return SSF_ERR_DEVICE;
+        }
+    }
+    return align_loop(h, d_pos, d_lab, d_nrm, d_conf, n, d_out, init_pose, rel_pose, valid, iters, pairs_last);
 }
 int ssf_fern_codes(ssf_handle* h, const uint8_t* rgb, const float* depth, int width, int height, const uint32_t* fern_pos,
                    const uint8_t* fern_rgb, const float* fern_depth, int n, uint8_t* codes) {
@@ -3117,6 +3142,315 @@ int ssf_graph_apply(ssf_handle* h, const float* nr, const float* nt) {
     HCK(hipMemcpyAsync(d_nr, nr, 36 * m, hipMemcpyHostToDevice, h->stream));
     HCK(hipMemcpyAsync(d_nt, nt, 12 * m, hipMemcpyHostToDevice, h->stream));
     return deform_dense(h, g.m, g.npos3, d_nr, d_nt, d_nodes, g.w4, g.idx4);
+}
+
+// ---- the fern-coded keyframe database (ssf_keyframes.h; kernels in ssf_keyframes.hip) -------------------------------------
+int ssf_keyframes_default_params(ssf_keyframes_params* p) {
+    if (!p) return SSF_ERR_INVALID_ARG;
+    std::memset(p, 0, sizeof(*p));
+    p->cell = 8; p->n_ferns = 500; p->seed = 1234; p->max_keyframes = 256; p->min_gap = 30; p->max_rows = 0;
+    p->new_ratio = 0.3f; p->loop_ratio = 0.2f;
+    return SSF_OK;
+}
+static uint64_t kf_splitmix64(uint64_t& s) {
+    s += 0x9E3779B97F4A7C15ull;
+    uint64_t z = s;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// the refusals the calls share: a sharded handle, no database, a model that is not at rest and (needs_frame: 1 = a current
+// frame, 2 = one with a colour map) no frame to read
+static int kf_usable(ssf_handle* h, const char* who, int needs_frame) {
+    if (h->cfg.nranks > 1) { h->err = std::string(who) + ": a sharded handle (cfg.nranks > 1) keeps no keyframe database"; return SSF_ERR_STATE; }
+    if (!h->kf.on) { h->err = std::string(who) + ": no keyframe database (ssf_keyframes_configure)"; return SSF_ERR_STATE; }
+    if (!h->pending.empty() || h->fusing) { h->err = std::string(who) + ": frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
+    if (needs_frame && !(h->active.ctx && h->active.activated)) { h->err = std::string(who) + ": no frame has been processed yet"; return SSF_ERR_STATE; }
+    if (needs_frame == 2 && !h->active.has_rgba) {
+        h->err = std::string(who) + ": the current frame came in as tables (ssf_submit_frame_tables): it has no colour map"; return SSF_ERR_STATE;
+    }
+    return SSF_OK;
+}
+static void kf_pack_ferns(const std::vector<ssf_fern>& f, std::vector<uint32_t>& out) {
+    out.resize(4 * f.size());
+    for (size_t i = 0; i < f.size(); i++) {
+        out[4 * i] = (uint32_t)f[i].x | ((uint32_t)f[i].y << 16);
+        out[4 * i + 1] = (uint32_t)f[i].r | ((uint32_t)f[i].g << 8) | ((uint32_t)f[i].b << 16);
+        out[4 * i + 2] = f[i].depth_mm; out[4 * i + 3] = 0;
+    }
+}
+static int kf_upload_ferns(ssf_handle* h) {
+    std::vector<uint32_t> w;
+    kf_pack_ferns(h->kf.host_ferns, w);
+    HCK(hipMemcpyAsync(h->kf.ferns, w.data(), 4 * w.size(), hipMemcpyHostToDevice, h->stream));
+    HCK(hipStreamSynchronize(h->stream));
+    return SSF_OK;
+}
+int ssf_keyframes_configure(ssf_handle* h, const ssf_keyframes_params* p) {
+    if (!h || !p) return SSF_ERR_INVALID_ARG;
+    const int W = h->cfg.width, H = h->cfg.height;
+    if ((p->cell != 4 && p->cell != 8 && p->cell != 16) || W < p->cell || H < p->cell || p->n_ferns < 1 || p->n_ferns > SSF_KEYFRAMES_MAX_FERNS ||
+        p->max_keyframes < 1 || p->min_gap < 0 || p->max_rows < 0 || !std::isfinite(p->new_ratio) || !std::isfinite(p->loop_ratio)) {
+        h->err = "ssf_keyframes_configure: needs cell 4 / 8 / 16 (<= the image), 1 .. 4096 ferns, max_keyframes >= 1, min_gap >= 0, max_rows >= 0 and finite ratios";
+        return SSF_ERR_INVALID_ARG;
+    }
+    // the depth range in mm: the sum of a cell's 256 depths must fit 31 bits
+    if (!(h->cfg.range_min >= 0.0f) || !(h->cfg.range_max <= 8000.0f) || !(lrintf(h->cfg.range_max * 1000.0f) > lrintf(h->cfg.range_min * 1000.0f))) {
+        h->err = "ssf_keyframes_configure: needs 0 <= range_min < range_max <= 8000 m (whole millimetres apart)"; return SSF_ERR_INVALID_ARG;
+    }
+    if (h->cfg.nranks > 1) { h->err = "ssf_keyframes_configure: a sharded handle (cfg.nranks > 1) keeps no keyframe database"; return SSF_ERR_STATE; }
+    KeyframeWs& k = h->kf;
+    if (k.on) { h->err = "ssf_keyframes_configure: a database is live (ssf_keyframes_clear first)"; return SSF_ERR_STATE; }
+    const size_t words = (((size_t)p->n_ferns + 7) / 8 + 63) / 64 * 64, K = (size_t)p->max_keyframes;
+    const size_t rows = p->max_rows > 0 ? (size_t)p->max_rows : K * (size_t)h->S;
+    if (!k.bufs.grow({{(void**)&k.ferns, 16 * (size_t)p->n_ferns}, {(void**)&k.q, 4 * words}, {(void**)&k.table, 4 * words * K},
+                      {(void**)&k.stamps, 4 * K}, {(void**)&k.diff, 4 * K}, {(void**)&k.rec, 4 * SSF_KF_REC_WORDS},
+                      {(void**)&k.bytes, (size_t)SSF_KEYFRAMES_MAX_FERNS},
+                      {(void**)&k.pool.pos, 12 * rows}, {(void**)&k.pool.col, 12 * rows}, {(void**)&k.pool.stamps, 8 * rows},
+                      {(void**)&k.pool.orient, 36 * rows}, {(void**)&k.pool.shape, 24 * rows}, {(void**)&k.pool.dims, 8 * rows},
+                      {(void**)&k.pool.conf, 4 * rows}})) {
+        k.bufs.release();
+        h->err = "ssf_keyframes_configure: allocation of the database failed"; return SSF_ERR_DEVICE;
+    }
+    k.p = *p; k.p.max_rows = (int64_t)rows;
+    k.words = (int)words; k.gw = W / p->cell; k.gh = H / p->cell;
+    k.kfs.clear(); k.rows_used = 0;
+    const uint32_t dlo = (uint32_t)lrintf(h->cfg.range_min * 1000.0f), dhi = (uint32_t)lrintf(h->cfg.range_max * 1000.0f);
+    k.host_ferns.assign((size_t)p->n_ferns, ssf_fern());
+    uint64_t s = p->seed;
+    for (auto& f : k.host_ferns) {
+        f.x = (uint16_t)(kf_splitmix64(s) % (uint64_t)k.gw); f.y = (uint16_t)(kf_splitmix64(s) % (uint64_t)k.gh);
+        f.r = (uint8_t)(kf_splitmix64(s) % 256u); f.g = (uint8_t)(kf_splitmix64(s) % 256u); f.b = (uint8_t)(kf_splitmix64(s) % 256u);
+        f.pad = 0; f.depth_mm = dlo + (uint32_t)(kf_splitmix64(s) % (uint64_t)(dhi - dlo));
+    }
+    { int rc = kf_upload_ferns(h); if (rc) { k.bufs.release(); return rc; } }
+    k.on = true;
+    return SSF_OK;
+}
+int ssf_keyframes_clear(ssf_handle* h) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    KeyframeWs& k = h->kf;
+    k.bufs.release();
+    k.on = false; k.kfs.clear(); k.host_ferns.clear(); k.rows_used = 0; k.words = 0;
+    return SSF_OK;
+}
+int ssf_keyframes_info(ssf_handle* h, int* configured, int* n_keyframes, int64_t* rows_used, ssf_keyframes_params* p) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    const KeyframeWs& k = h->kf;
+    if (configured) *configured = k.on ? 1 : 0;
+    if (n_keyframes) *n_keyframes = k.on ? (int)k.kfs.size() : 0;
+    if (rows_used) *rows_used = k.on ? (int64_t)k.rows_used : 0;
+    if (p) { if (k.on) *p = k.p; else std::memset(p, 0, sizeof(*p)); }
+    return SSF_OK;
+}
+int ssf_keyframes_set_ferns(ssf_handle* h, const ssf_fern* ferns, int n) {
+    if (!h || !ferns) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_set_ferns", 0); if (rc) return rc; }
+    KeyframeWs& k = h->kf;
+    if (n != k.p.n_ferns) { h->err = "ssf_keyframes_set_ferns: the database is configured for " + std::to_string(k.p.n_ferns) + " ferns"; return SSF_ERR_INVALID_ARG; }
+    if (!k.kfs.empty()) { h->err = "ssf_keyframes_set_ferns: keyframes are stored under the present table"; return SSF_ERR_STATE; }
+    for (int i = 0; i < n; i++)
+        if ((int)ferns[i].x >= k.gw || (int)ferns[i].y >= k.gh) {
+            h->err = "ssf_keyframes_set_ferns: fern " + std::to_string(i) + " names a cell outside the " + std::to_string(k.gw) + " x " + std::to_string(k.gh) + " grid";
+            return SSF_ERR_INVALID_ARG;
+        }
+    k.host_ferns.assign(ferns, ferns + n);
+    for (auto& f : k.host_ferns) f.pad = 0;
+    return kf_upload_ferns(h);
+}
+int ssf_keyframes_get_ferns(ssf_handle* h, ssf_fern* ferns, int capacity) {
+    if (!h || !ferns) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_get_ferns", 0); if (rc) return rc; }
+    const KeyframeWs& k = h->kf;
+    if (capacity < k.p.n_ferns) { h->err = "ssf_keyframes_get_ferns: " + std::to_string(k.p.n_ferns) + " ferns, room for " + std::to_string(capacity); return SSF_ERR_CAPACITY; }
+    std::memcpy(ferns, k.host_ferns.data(), sizeof(ssf_fern) * k.host_ferns.size());
+    return SSF_OK;
+}
+// the current frame's packed codes into kf.q (enqueued only)
+static void kf_encode_current(ssf_handle* h) {
+    const KeyframeWs& k = h->kf;
+    launch_kf_encode(h->stream, h->cc->maps.rgba, h->cc->maps.plane_depth, h->cfg.width, k.p.cell, h->cfg.range_min, h->cfg.range_max,
+                     k.ferns, k.p.n_ferns, k.words, k.q);
+}
+// n code bytes -> the packed words; false: a code > 15
+static bool kf_pack_codes(const uint8_t* codes, int n, int words, std::vector<uint32_t>& out) {
+    out.assign((size_t)words, 0u);
+    for (int i = 0; i < n; i++) {
+        if (codes[i] > 15) return false;
+        out[i >> 3] |= (uint32_t)codes[i] << (4 * (i & 7));
+    }
+    return true;
+}
+// search + select (+ the add) of kf.q; rec: SSF_KF_REC_WORDS words.  The host takes the keyframe the device added into its mirror
+static int kf_run(ssf_handle* h, const char* who, int mode, int kmax, int stamp, int min_gap, bool with_frame, int32_t* rec) {
+    KeyframeWs& k = h->kf;
+    hipStream_t st = h->stream;
+    KfQuery q;
+    q.words = k.words; q.n = k.p.n_ferns; q.K = (int)k.kfs.size(); q.max_keyframes = k.p.max_keyframes; q.mode = mode; q.kmax = kmax;
+    q.stamp = stamp; q.min_gap = min_gap; q.rows_used = k.rows_used; q.max_rows = (long long)k.p.max_rows;
+    q.new_ratio = k.p.new_ratio; q.loop_ratio = k.p.loop_ratio;
+    launch_kf_search(st, k.q, k.table, k.words, q.K, k.diff);
+    HCK(hipGetLastError());
+    SurfelSoA none; std::memset(&none, 0, sizeof(none));
+    launch_kf_select(st, q, k.q, k.table, k.stamps, k.diff, with_frame ? h->cc->frame : none, with_frame ? h->S : 0, k.pool, k.rec);
+    HCK(hipGetLastError());
+    HCK(hipMemcpyAsync(rec, k.rec, 4 * SSF_KF_REC_WORDS, hipMemcpyDeviceToHost, st));
+    HCK(hipStreamSynchronize(st));
+    if (h->cfg.profile == 1) timer_collect(&h->timer);
+    const bool added = rec[0] != 0;
+    // the decision was taken on the device; the host checks what it can from the record
+    if (rec[4] != q.K + (added ? 1 : 0) || (added && (rec[1] != q.K || mode == 0 || rec[38] < 0 || k.rows_used + rec[38] > (long long)k.p.max_rows)) ||
+        rec[5] < 0 || rec[5] > kmax) {
+        h->err = std::string(who) + ": the device's record contradicts the host's view of the database"; return SSF_ERR_DEVICE;
+    }
+    if (added) {
+        KeyframeMeta m; m.first = k.rows_used; m.rows = rec[38]; m.stamp = stamp; pose_to12(h->pose, m.pose);
+        k.kfs.push_back(m); k.rows_used += m.rows;
+    }
+    return SSF_OK;
+}
+int ssf_keyframes_encode(ssf_handle* h, uint8_t* codes, int capacity) {
+    if (!h || !codes) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_encode", 2); if (rc) return rc; }
+    KeyframeWs& k = h->kf;
+    if (capacity < k.p.n_ferns) { h->err = "ssf_keyframes_encode: " + std::to_string(k.p.n_ferns) + " codes, room for " + std::to_string(capacity); return SSF_ERR_CAPACITY; }
+    { TimerScope ts(h); kf_encode_current(h); }
+    HCK(hipGetLastError());
+    launch_kf_unpack(h->stream, k.q, k.p.n_ferns, k.bytes);
+    HCK(hipGetLastError());
+    HCK(hipMemcpyAsync(codes, k.bytes, (size_t)k.p.n_ferns, hipMemcpyDeviceToHost, h->stream));
+    HCK(hipStreamSynchronize(h->stream));
+    if (h->cfg.profile == 1) timer_collect(&h->timer);
+    return SSF_OK;
+}
+int ssf_keyframes_query(ssf_handle* h, const uint8_t* codes, int stamp, int min_gap, int kmax, ssf_keyframe_result* out) {
+    if (!h || !out || kmax < 0 || kmax > SSF_KEYFRAMES_MAX_CANDIDATES) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_query", codes ? 0 : 2); if (rc) return rc; }
+    KeyframeWs& k = h->kf;
+    std::vector<uint32_t> packed;
+    TimerScope ts(h);
+    if (codes) {
+        if (!kf_pack_codes(codes, k.p.n_ferns, k.words, packed)) { h->err = "ssf_keyframes_query: a code is a value 0 .. 15"; return SSF_ERR_INVALID_ARG; }
+        HCK(hipMemcpyAsync(k.q, packed.data(), 4 * packed.size(), hipMemcpyHostToDevice, h->stream));
+    } else {
+        kf_encode_current(h);
+        HCK(hipGetLastError());
+        stamp = h->stamp;
+    }
+    int32_t rec[SSF_KF_REC_WORDS];
+    { int rc = kf_run(h, "ssf_keyframes_query", 0, kmax, stamp, min_gap < 0 ? k.p.min_gap : min_gap, false, rec); if (rc) return rc; }
+    std::memcpy(out, rec, sizeof(*out));
+    return SSF_OK;
+}
+int ssf_keyframes_consider(ssf_handle* h, ssf_keyframe_result* out) {
+    if (!h || !out) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_consider", 2); if (rc) return rc; }
+    TimerScope ts(h);
+    kf_encode_current(h);
+    HCK(hipGetLastError());
+    int32_t rec[SSF_KF_REC_WORDS];
+    { int rc = kf_run(h, "ssf_keyframes_consider", 1, SSF_KEYFRAMES_MAX_CANDIDATES, h->stamp, h->kf.p.min_gap, true, rec); if (rc) return rc; }
+    std::memcpy(out, rec, sizeof(*out));
+    return SSF_OK;
+}
+int ssf_keyframes_add(ssf_handle* h, int* id) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_add", 2); if (rc) return rc; }
+    TimerScope ts(h);
+    kf_encode_current(h);
+    HCK(hipGetLastError());
+    int32_t rec[SSF_KF_REC_WORDS];
+    { int rc = kf_run(h, "ssf_keyframes_add", 2, 0, h->stamp, h->kf.p.min_gap, true, rec); if (rc) return rc; }
+    if (!rec[0]) { h->err = "ssf_keyframes_add: the store is full"; return SSF_ERR_CAPACITY; }
+    if (id) *id = rec[1];
+    return SSF_OK;
+}
+int ssf_keyframes_put(ssf_handle* h, const uint8_t* codes, const ssf_surfels* rows, int n_rows, const float* pose, int stamp, int* id) {
+    if (!h || !codes || !pose || n_rows < 0 || (n_rows > 0 && (!rows || !rows->positions || !rows->colors || !rows->stamps || !rows->orientations ||
+                                                              !rows->shapes || !rows->dims || !rows->confidences))) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_put", 0); if (rc) return rc; }
+    KeyframeWs& k = h->kf;
+    const size_t K = k.kfs.size(), n = (size_t)n_rows, o = (size_t)k.rows_used;
+    if ((int)K >= k.p.max_keyframes || k.rows_used + n_rows > (long long)k.p.max_rows) { h->err = "ssf_keyframes_put: the store is full"; return SSF_ERR_CAPACITY; }
+    std::vector<uint32_t> packed;
+    if (!kf_pack_codes(codes, k.p.n_ferns, k.words, packed)) { h->err = "ssf_keyframes_put: a code is a value 0 .. 15"; return SSF_ERR_INVALID_ARG; }
+    hipStream_t st = h->stream;
+    const int32_t stamp32 = stamp;
+    HCK(hipMemcpyAsync(k.table + K * (size_t)k.words, packed.data(), 4 * packed.size(), hipMemcpyHostToDevice, st));
+    HCK(hipMemcpyAsync(k.stamps + K, &stamp32, 4, hipMemcpyHostToDevice, st));
+    if (n > 0) {
+        HCK(hipMemcpyAsync(k.pool.pos + 3 * o, rows->positions, 12 * n, hipMemcpyHostToDevice, st));
+        HCK(hipMemcpyAsync(k.pool.col + 3 * o, rows->colors, 12 * n, hipMemcpyHostToDevice, st));
+        HCK(hipMemcpyAsync(k.pool.stamps + 2 * o, rows->stamps, 8 * n, hipMemcpyHostToDevice, st));
+        HCK(hipMemcpyAsync(k.pool.orient + 9 * o, rows->orientations, 36 * n, hipMemcpyHostToDevice, st));
+        HCK(hipMemcpyAsync(k.pool.shape + 6 * o, rows->shapes, 24 * n, hipMemcpyHostToDevice, st));
+        HCK(hipMemcpyAsync(k.pool.dims + 2 * o, rows->dims, 8 * n, hipMemcpyHostToDevice, st));
+        HCK(hipMemcpyAsync(k.pool.conf + o, rows->confidences, 4 * n, hipMemcpyHostToDevice, st));
+    }
+    HCK(hipStreamSynchronize(st));
+    KeyframeMeta m; m.first = k.rows_used; m.rows = n_rows; m.stamp = stamp; std::memcpy(m.pose, pose, sizeof(m.pose));
+    k.kfs.push_back(m); k.rows_used += n_rows;
+    if (id) *id = (int)K;
+    return SSF_OK;
+}
+static int kf_lookup(ssf_handle* h, const char* who, int id) {
+    if (id < 0 || (size_t)id >= h->kf.kfs.size()) {
+        h->err = std::string(who) + ": no keyframe " + std::to_string(id) + " (" + std::to_string(h->kf.kfs.size()) + " stored)"; return SSF_ERR_INVALID_ARG;
+    }
+    return SSF_OK;
+}
+int ssf_keyframes_get(ssf_handle* h, int id, ssf_surfels* rows, int capacity, int* n_rows, float* pose, int* stamp, uint8_t* codes) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_get", 0); if (rc) return rc; }
+    { int rc = kf_lookup(h, "ssf_keyframes_get", id); if (rc) return rc; }
+    KeyframeWs& k = h->kf;
+    const KeyframeMeta& m = k.kfs[(size_t)id];
+    if (rows && capacity < m.rows) { h->err = "ssf_keyframes_get: " + std::to_string(m.rows) + " rows, room for " + std::to_string(capacity); return SSF_ERR_CAPACITY; }
+    hipStream_t st = h->stream;
+    const size_t n = (size_t)m.rows, o = (size_t)m.first;
+    if (rows && n > 0) {
+        if (rows->positions) HCK(hipMemcpyAsync(rows->positions, k.pool.pos + 3 * o, 12 * n, hipMemcpyDeviceToHost, st));
+        if (rows->colors) HCK(hipMemcpyAsync(rows->colors, k.pool.col + 3 * o, 12 * n, hipMemcpyDeviceToHost, st));
+        if (rows->stamps) HCK(hipMemcpyAsync(rows->stamps, k.pool.stamps + 2 * o, 8 * n, hipMemcpyDeviceToHost, st));
+        if (rows->orientations) HCK(hipMemcpyAsync(rows->orientations, k.pool.orient + 9 * o, 36 * n, hipMemcpyDeviceToHost, st));
+        if (rows->shapes) HCK(hipMemcpyAsync(rows->shapes, k.pool.shape + 6 * o, 24 * n, hipMemcpyDeviceToHost, st));
+        if (rows->dims) HCK(hipMemcpyAsync(rows->dims, k.pool.dims + 2 * o, 8 * n, hipMemcpyDeviceToHost, st));
+        if (rows->confidences) HCK(hipMemcpyAsync(rows->confidences, k.pool.conf + o, 4 * n, hipMemcpyDeviceToHost, st));
+    }
+    if (codes) {
+        launch_kf_unpack(st, k.table + (size_t)id * k.words, k.p.n_ferns, k.bytes);
+        HCK(hipGetLastError());
+        HCK(hipMemcpyAsync(codes, k.bytes, (size_t)k.p.n_ferns, hipMemcpyDeviceToHost, st));
+    }
+    HCK(hipStreamSynchronize(st));
+    if (n_rows) *n_rows = m.rows;
+    if (pose) std::memcpy(pose, m.pose, sizeof(m.pose));
+    if (stamp) *stamp = m.stamp;
+    return SSF_OK;
+}
+int ssf_keyframes_set_pose(ssf_handle* h, int id, const float* pose) {
+    if (!h || !pose) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_set_pose", 0); if (rc) return rc; }
+    { int rc = kf_lookup(h, "ssf_keyframes_set_pose", id); if (rc) return rc; }
+    std::memcpy(h->kf.kfs[(size_t)id].pose, pose, 12 * sizeof(float));
+    return SSF_OK;
+}
+int ssf_keyframes_align(ssf_handle* h, int id, const float* init_pose, int use_conf, float* rel_pose, int* valid, int* iters, int* pairs_last) {
+    if (!h || !rel_pose || !valid) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_align", 1); if (rc) return rc; }
+    { int rc = kf_lookup(h, "ssf_keyframes_align", id); if (rc) return rc; }
+    const KeyframeWs& k = h->kf;
+    const KeyframeMeta& m = k.kfs[(size_t)id];
+    const size_t N = (size_t)std::max(m.rows, 1), o = (size_t)m.first;
+    float *d_lab = nullptr, *d_nrm = nullptr; long long* d_out = nullptr;
+    DevTemps tmp;
+    HCK(tmp.take(&d_lab, 12 * N)); HCK(tmp.take(&d_nrm, 12 * N)); HCK(tmp.take(&d_out, 40 * sizeof(long long)));
+    TimerScope ts(h);
+    launch_kf_align_prep(h->stream, k.pool.col + 3 * o, k.pool.orient + 9 * o, m.rows, d_lab, d_nrm);
+    HCK(hipGetLastError());
+    return align_loop(h, k.pool.pos + 3 * o, d_lab, d_nrm, use_conf ? k.pool.conf + o : nullptr, m.rows, d_out, init_pose, rel_pose, valid, iters,
+                      pairs_last);
 }
 
 // ---- re-homing of a sharded map (see ssf.h): rows moved by ssf_apply_deformation go to the rank that owns their tile ----

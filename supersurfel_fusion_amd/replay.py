@@ -169,15 +169,36 @@ def write_render(fusion, render_dir, stamp):
     return out["stats"]
 
 
-def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30):
+def keyframe_line(fusion, stamp, rec):
+    """one line of the keyframe log: stamp, the id the frame was stored under (or -; "full" when the store had no room),
+    min_diff_all, then every loop candidate as id:diff with the verdict of aligning it against the frame (include/ssf_keyframes.h;
+    no prior: the identity, so a verdict is only expected to be valid for a near revisit)"""
+    parts = [stamp, "full" if rec["full"] else (str(rec["id"]) if rec["added"] else "-"), str(rec["min_diff_all"])]
+    for c in rec["candidates"]:
+        if c["loop"]:
+            a = fusion.keyframes_align(c["id"])
+            parts.append("%d:%d:%s:pairs=%d" % (c["id"], c["diff"], "valid" if a["valid"] else "invalid", a["pairs"]))
+    return " ".join(parts)
+
+
+def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
+           keyframes=None, keyframe_log=None):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
     same, bit for bit, as with one process_frame per line.
     mask_dir: per-frame pixel masks (read_pixel_mask), handed over with their frames (include/ssf_dynamic.h).
     render_dir: after frames 0, render_every, 2 render_every, ... the model is drawn at the tracked pose (write_render); pipelined,
-    submission pauses at such a frame until it has been processed (a render needs no frame pending)."""
+    submission pauses at such a frame until it has been processed (a render needs no frame pending).
+    keyframes: a dict of ssf_keyframes_params fields ({} = the defaults): the keyframe database is configured and
+    keyframes_consider runs after every frame (not pipelined: it needs no frame pending); keyframe_log: where keyframe_line's
+    lines go (they are also kept in fusion.keyframe_lines)."""
     lines, results = [], []
+    if keyframes is not None:
+        if pipelined:
+            raise ValueError("the keyframe database is consulted between frames: replay it without pipelined")
+        fusion.keyframes_configure(**keyframes)
+        fusion.keyframe_lines = []
     render_every = max(1, int(render_every))
     mask_of = (lambda stamp, depth: read_pixel_mask(mask_dir, stamp, np.shape(depth))) if mask_dir else (lambda stamp, depth: None)
     if not pipelined:
@@ -186,6 +207,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             r = fusion.process_frame(rgb, depth) if m is None else fusion.process_frame(rgb, depth, pixel_mask=m)
             results.append(r)
             lines.append(tum_line(stamp, r["pose"]))
+            if keyframes is not None:
+                fusion.keyframe_lines.append(keyframe_line(fusion, stamp, fusion.keyframes_consider()))
             if render_dir and (len(lines) - 1) % render_every == 0:
                 write_render(fusion, render_dir, stamp)
     else:
@@ -217,6 +240,9 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     if out_path:
         with open(out_path, "w") as f:
             f.write("\n".join(lines) + "\n")
+    if keyframes is not None and keyframe_log:
+        with open(keyframe_log, "w") as f:
+            f.write("".join(l + "\n" for l in fusion.keyframe_lines))
     if export_model:
         fusion.export_model_txt(export_model)
     return lines, results
@@ -324,6 +350,10 @@ def parse_args(argv=None):
     ap.add_argument("--render-dir", default=None, metavar="DIR",
                     help="every --render-every frames, the model drawn at the tracked pose: DIR/<stamp>_rgb.png and DIR/<stamp>_depth.npy")
     ap.add_argument("--render-every", type=int, default=30, metavar="K")
+    ap.add_argument("--keyframes", action="store_true",
+                    help="keep the fern-coded keyframe database: after every frame one line (stamp, stored id or -, min_diff_all, loop candidates "
+                         "with their alignment verdict); not with --pipelined")
+    ap.add_argument("--keyframe-log", default=None, metavar="FILE", help="write those lines to FILE instead of the terminal")
     return ap.parse_args(argv)
 
 
@@ -338,7 +368,10 @@ def main():
     frames = (frames_from_npz(a.npz, a.depth_scale, a.raw_frames) if a.npz
               else frames_from_dataset(a.dataset, a.depth_scale, a.max_frames, a.raw_frames))
     lines, res = replay(f, frames, a.out, a.export_model, pipelined=a.pipelined, mask_dir=a.dynamic_masks,
-                        render_dir=a.render_dir, render_every=a.render_every)
+                        render_dir=a.render_dir, render_every=a.render_every, keyframes={} if a.keyframes else None,
+                        keyframe_log=a.keyframe_log)
+    if a.keyframes and not a.keyframe_log:
+        print("\n".join(f.keyframe_lines))
     print("%d frames -> %s ; %d supersurfels" % (len(lines), a.out, res[-1]["n_model"] if res else 0))
 
 
