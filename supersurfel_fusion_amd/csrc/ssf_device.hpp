@@ -24,9 +24,6 @@
 #include "../../include/ssf.h"
 #include "../../include/ssf_input.h"
 #include "../../include/ssf_dynamic.h"
-#include "../../include/ssf_render.h"
-#include "../../include/ssf_graph.h"
-#include "../../include/ssf_keyframes.h"
 
 // SSF_EXPERIMENTS: the laboratory build (csrc/variants/lab/libssf_hip.so, `make lab`): the measurement arms and environment
 // switches behind DESIGN.md's A/B tables.  The PRODUCT library is built without it: it reads no environment variable and
@@ -374,53 +371,11 @@ void launch_move_rows(hipStream_t st, const Cam& cam, SurfelSoA vis_src, SurfelS
 // new_head (dst.live must be zero where it matters); set_span != 0: cnt->oov_head / oov_tail := the new span
 void launch_oov_compact(hipStream_t st, OovStore src, OovStore dst, int span_upper, int new_head, uint32_t* bc_oov, Counters* cnt,
                         int set_span);
-// ---- the model read in place, one thread per slot (helpers: ssf_slots.hpp) ---------------------------------------------------
+// ---- the model read in place, one thread per slot (helpers: ssf_slots.hpp; the render, graph and keyframe kernels) ------------
 // slots [0, nvs = 256 nbv) = the visible array (rows < n_visible), then nbo blocks of 256 slots = the out-of-view span
 // [oov_head, oov_tail) of `oov` (live flags; nbo = 0: visible rows only); nslots = 256 (nbv + nbo).  Slot order = logical order.
 struct ModelView { SurfelSoA vis; OovStore oov; int n_visible, nbv, nvs, oov_head, oov_tail, nbo, nslots; };
-// ---- the model drawn into a virtual camera (ssf_render.h; ssf_render.hip) ------------------------------------------------
-// R = 9 floats row-major and t (camera-to-map, ssf_get_pose's layout); ntx x nty tiles of 16 x 16 pixels; k = s * s
-struct RenderCam { float R[9], t[3]; float fx, fy, cx, cy; int W, H, ntx, nty; float zmin, zmax, min_conf, s, k; };
-struct RenderView { RenderCam cam; ModelView model; };           // one kernel argument: the camera and the rows drawn
-struct RenderOut { float* depth; int32_t* index; uint8_t* rgb8; float* color; float* normal; };      // nullptr = not produced
-// prep (+ the out-of-view live scan into bc[nbo + 1]) and the exclusive scan of the tile counts: tcnt[ntiles + 1] (zeroed by the
-// caller) becomes the list offsets, cursor[ntiles] a copy; *total = list entries (64 bits)
-void launch_render_prep(hipStream_t st, const RenderView& rv, uint32_t* bc, float4* rec, uint2* rbox, int32_t* logical, uint32_t* tcnt,
-                        uint32_t* cursor, unsigned long long* total);
-void launch_render_fill(hipStream_t st, const RenderView& rv, const uint2* rbox, uint32_t* cursor, uint32_t* list);
-// stats[0..2] += fragments, filled pixels, rows shown (seen[slot] != epoch before this render)
-void launch_render_tile(hipStream_t st, const RenderView& rv, const float4* rec, const uint2* rbox, const int32_t* logical,
-                        const uint32_t* list, const uint32_t* toff, const RenderOut& out, uint32_t* seen, uint32_t epoch,
-                        unsigned long long* stats);
-// ---- the deformation graph's nodes and per-row binding (ssf_graph.h; ssf_graph.hip) ---------------------------------------
-#define GRAPH_SORT_ITEMS 2048                     // items of one workgroup of the counting sort
-// stamp[nslots], elig[nslots]; bc[nbo + 1] = exclusive scan of the out-of-view blocks' live counts; mm[4] (preset INT_MAX, INT_MIN,
-// 0, 0) = min / max stamp of the eligible rows, their number, the live rows
-void launch_graph_keys(hipStream_t st, const ModelView& mv, float min_conf, int32_t* stamp, uint8_t* elig, uint32_t* bc, int* mm);
-// stable sort of the eligible slots by (stamp - lo), `passes` 8-bit digits; cnt[256 ceil(nslots / GRAPH_SORT_ITEMS) + 1]; returns
-// which of the pairs (key_a, slot_a) = 0 / (key_b, slot_b) = 1 holds the n_elig sorted (stamp, slot) entries
-int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes, const int32_t* stamp, const uint8_t* elig, uint32_t* cnt,
-                      int32_t* key_a, uint32_t* slot_a, int32_t* key_b, uint32_t* slot_b);
-// node k = the slot order[k stride]: nodes[k] = (x, y, z, bits(t_init)), npos3 = the packed positions, nrow = the logical row
-void launch_graph_sample(hipStream_t st, const ModelView& mv, const uint32_t* bc, const uint32_t* order, int m, int stride, float4* nodes,
-                         float* npos3, int32_t* nrow);
-void launch_graph_bind(hipStream_t st, const ModelView& mv, const uint32_t* bc, const float4* nodes, int m, int look, float* w4, int32_t* i4);
-void launch_graph_bind_points(hipStream_t st, const float* pts, const int32_t* t0, int n, const float4* nodes, int m, int look, float* w4,
-                              int32_t* i4);
-// ---- the fern-coded keyframe database (ssf_keyframes.h; ssf_keyframes.hip) ----------------------------------------------
-// the row pool: a keyframe's rows are consecutive, in ssf_surfels' layout (what ssf_keyframes_get / _put copy as they are)
-struct KfPool { float* pos; float* col; int32_t* stamps; float* orient; float* shape; float* dims; float* conf; };
-#define SSF_KF_REC_WORDS 40                       // ssf_keyframe_result (38 words), the rows stored, one spare
-// one query: n ferns in `words` packed words, K stored keyframes; mode 0 query, 1 consider, 2 add (see k_kf_select)
-struct KfQuery { int words, n, K, max_keyframes, mode, kmax, stamp, min_gap; long long rows_used, max_rows; float new_ratio, loop_ratio; };
-// ferns[i] = (x | y << 16, r | g << 8 | b << 16, depth_mm, 0); codes: `words` packed words of the frame (rgba, plane_depth)
-void launch_kf_encode(hipStream_t st, const uint32_t* rgba, const float* plane_depth, int W, int B, float zmin, float zmax,
-                      const uint4* ferns, int n, int words, uint32_t* codes);
-void launch_kf_unpack(hipStream_t st, const uint32_t* codes, int n, uint8_t* out);
-void launch_kf_search(hipStream_t st, const uint32_t* q, const uint32_t* table, int words, int K, uint32_t* diff);
-void launch_kf_select(hipStream_t st, const KfQuery& qy, const uint32_t* q, uint32_t* table, int32_t* stamps, const uint32_t* diff,
-                      const SurfelSoA& frame, int S, const KfPool& pool, int32_t* rec);
-void launch_kf_align_prep(hipStream_t st, const float* col, const float* orient, int n, float* lab, float* nrm);
+// ---- loop-closure registration and the caller's fern codes (ssf_align, ssf_fern_codes; ssf_track_fuse.hip) --------------------
 // one iteration of the loop-closure registration against a frame; out40: see k_align
 void launch_align(hipStream_t st, const Cam& cam, const float* spos, const float* slab, const float* snrm, const float* sconf,
                   int n, SurfelSoA frame, const int32_t* label, const float* plane_depth, Rt T, long long* out40);

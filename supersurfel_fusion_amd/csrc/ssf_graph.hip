@@ -21,8 +21,11 @@
 // No float atomics anywhere; every count is an integer.
 #include <climits>
 #include "ssf_slots.hpp"
+#include "ssf_handle.hpp"
 
 namespace ssf {
+
+#define GRAPH_SORT_ITEMS 2048                     // items of one workgroup of the counting sort
 
 // ---- keys: stamp + eligibility per slot, live counts of the out-of-view blocks, min / max / count of the eligible stamps ----
 // mm[0] = min (starts INT_MAX), mm[1] = max (starts INT_MIN), mm[2] = eligible rows, mm[3] = live rows
@@ -204,13 +207,17 @@ __global__ __launch_bounds__(256) void k_graph_bind_points(const float* __restri
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------
-void launch_graph_keys(hipStream_t st, const ModelView& mv, float min_conf, int32_t* stamp, uint8_t* elig, uint32_t* bc, int* mm) {
+// stamp[nslots], elig[nslots]; bc[nbo + 1] = exclusive scan of the out-of-view blocks' live counts; mm[4] (preset INT_MAX, INT_MIN,
+// 0, 0) = min / max stamp of the eligible rows, their number, the live rows
+static void launch_graph_keys(hipStream_t st, const ModelView& mv, float min_conf, int32_t* stamp, uint8_t* elig, uint32_t* bc, int* mm) {
     ScopedKernel sk("graph_rank", st);
     hipLaunchKernelGGL(k_graph_keys, dim3(mv.nbv + mv.nbo), dim3(256), 0, st, mv, min_conf, stamp, elig, bc, mm);
     if (mv.nbo > 0) hipLaunchKernelGGL(k_graph_scan, dim3(1), dim3(1024), 0, st, bc, mv.nbo);
 }
-int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes, const int32_t* stamp, const uint8_t* elig, uint32_t* cnt,
-                      int32_t* key_a, uint32_t* slot_a, int32_t* key_b, uint32_t* slot_b) {
+// stable sort of the eligible slots by (stamp - lo), `passes` 8-bit digits; cnt[256 ceil(nslots / GRAPH_SORT_ITEMS) + 1]; returns
+// which of the pairs (key_a, slot_a) = 0 / (key_b, slot_b) = 1 holds the n_elig sorted (stamp, slot) entries
+static int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes, const int32_t* stamp, const uint8_t* elig,
+                             uint32_t* cnt, int32_t* key_a, uint32_t* slot_a, int32_t* key_b, uint32_t* slot_b) {
     ScopedKernel sk("graph_rank", st);
     const int32_t* kin = stamp; const uint32_t* sin = nullptr; const uint8_t* el = elig;
     int n = nslots, out = 0;
@@ -224,21 +231,168 @@ int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes
     }
     return out ^ 1;                               // which pair holds the sorted list: 0 = a, 1 = b
 }
-void launch_graph_sample(hipStream_t st, const ModelView& mv, const uint32_t* bc, const uint32_t* order, int m, int stride, float4* nodes,
-                         float* npos3, int32_t* nrow) {
+// node k = the slot order[k stride]: nodes[k] = (x, y, z, bits(t_init)), npos3 = the packed positions, nrow = the logical row
+static void launch_graph_sample(hipStream_t st, const ModelView& mv, const uint32_t* bc, const uint32_t* order, int m, int stride,
+                                float4* nodes, float* npos3, int32_t* nrow) {
     ScopedKernel sk("graph_sample", st);
     hipLaunchKernelGGL(k_graph_sample, dim3((m + 255) / 256), dim3(256), 0, st, mv, bc, order, m, stride, nodes, npos3, nrow);
 }
-void launch_graph_bind(hipStream_t st, const ModelView& mv, const uint32_t* bc, const float4* nodes, int m, int look, float* w4, int32_t* i4) {
+static void launch_graph_bind(hipStream_t st, const ModelView& mv, const uint32_t* bc, const float4* nodes, int m, int look, float* w4, int32_t* i4) {
     ScopedKernel sk("graph_bind", st);
     hipLaunchKernelGGL(k_graph_bind, dim3(mv.nbv + mv.nbo), dim3(256), 0, st, mv, bc, nodes, m, look, reinterpret_cast<float4*>(w4),
                        reinterpret_cast<int4*>(i4));
 }
-void launch_graph_bind_points(hipStream_t st, const float* pts, const int32_t* t0, int n, const float4* nodes, int m, int look, float* w4,
-                              int32_t* i4) {
+static void launch_graph_bind_points(hipStream_t st, const float* pts, const int32_t* t0, int n, const float4* nodes, int m, int look,
+                                     float* w4, int32_t* i4) {
     ScopedKernel sk("graph_bind", st);
     hipLaunchKernelGGL(k_graph_bind_points, dim3((n + 255) / 256), dim3(256), 0, st, pts, t0, n, nodes, m, look,
                        reinterpret_cast<float4*>(w4), reinterpret_cast<int4*>(i4));
 }
 
 }  // namespace ssf
+
+// ---- host: the entry points of include/ssf_graph.h -------------------------------------------------------------------------
+extern "C" {
+int ssf_graph_default_params(ssf_graph_params* p) {
+    if (!p) return SSF_ERR_INVALID_ARG;
+    p->stride = 50; p->look = 20; p->min_conf = 0.0f;
+    return SSF_OK;
+}
+static bool graph_valid(const ssf_handle* h) { return h->graph.built && h->graph.gen == h->model_gen; }
+// the refusals every call that uses the resident graph shares
+static int graph_usable(ssf_handle* h, const char* who) {
+    { int rc = model_at_rest(h, who, "has no deformation graph"); if (rc) return rc; }
+    if (!h->graph.built) { h->err = std::string(who) + ": no graph has been built (ssf_graph_build)"; return SSF_ERR_STATE; }
+    if (!graph_valid(h)) { h->err = std::string(who) + ": graph is stale: build it again"; return SSF_ERR_STATE; }
+    return SSF_OK;
+}
+int ssf_graph_build(ssf_handle* h, const ssf_graph_params* p, int* n_nodes) {
+    if (!h || !p) return SSF_ERR_INVALID_ARG;
+    if (p->stride < 1 || p->look < 3 || !std::isfinite(p->min_conf)) {
+        h->err = "ssf_graph_build: needs stride >= 1, look >= 3 and a finite min_conf"; return SSF_ERR_INVALID_ARG;
+    }
+    { int rc = model_at_rest(h, "ssf_graph_build", "has no deformation graph"); if (rc) return rc; }
+    GraphWs& g = h->graph;
+    g.built = false;                              // whatever happens below, no half-built graph is kept
+    if (h->n_model <= 0) { h->err = "ssf_graph_build: the model is empty"; return SSF_ERR_STATE; }
+
+    const ModelView mv = model_view(h, false);
+    const size_t slots = (size_t)mv.nslots;       // (>= n_model > 0: every row has a slot)
+    if (slots > g.slots) {
+        const size_t nb = (slots + GRAPH_SORT_ITEMS - 1) / GRAPH_SORT_ITEMS;
+        if (!g.bufs.grow({{(void**)&g.stamp, 4 * slots}, {(void**)&g.elig, slots}, {(void**)&g.key_a, 4 * slots}, {(void**)&g.key_b, 4 * slots},
+                          {(void**)&g.slot_a, 4 * slots}, {(void**)&g.slot_b, 4 * slots}, {(void**)&g.cnt, 4 * (256 * nb + 1)},
+                          {(void**)&g.bc, 4 * (slots / 256 + 1)}, {(void**)&g.w4, 16 * slots}, {(void**)&g.idx4, 16 * slots},
+                          {(void**)&g.mm, 4 * sizeof(int)}})) {
+            h->err = "ssf_graph_build: allocation of the working buffers failed"; return SSF_ERR_DEVICE;
+        }
+        g.slots = slots;
+    }
+    TimerScope ts(h);
+    hipStream_t st = h->stream;
+    const int mm0[4] = {INT_MAX, INT_MIN, 0, 0};
+    int mm[4] = {0, 0, 0, 0};
+    HCK(hipMemcpyAsync(g.mm, mm0, sizeof(mm0), hipMemcpyHostToDevice, st));
+    launch_graph_keys(st, mv, p->min_conf, g.stamp, g.elig, g.bc, g.mm);
+    HCK(hipGetLastError());
+    HCK(hipMemcpyAsync(mm, g.mm, sizeof(mm), hipMemcpyDeviceToHost, st));
+    { int rc = sync_collect(h); if (rc) return rc; }          // (here, so that the refusals below have nothing left to book)
+    if (mm[3] != h->n_model) { h->err = "ssf_graph_build: the stores hold " + std::to_string(mm[3]) + " rows, the handle counts " + std::to_string(h->n_model); return SSF_ERR_DEVICE; }
+    const int n_elig = mm[2];
+    const long long m64 = ((long long)n_elig + p->stride - 1) / p->stride;
+    if (m64 < 5) {
+        h->err = "ssf_graph_build: " + std::to_string(m64) + " nodes (" + std::to_string(n_elig) + " eligible rows, stride " +
+                 std::to_string(p->stride) + "); a graph needs at least 5";
+        return SSF_ERR_STATE;
+    }
+    const long long span = (long long)mm[1] - (long long)mm[0];
+    if (span >= SSF_GRAPH_MAX_STAMP_SPAN) {
+        h->err = "ssf_graph_build: the eligible rows' birth stamps span " + std::to_string(span) + " frames; at most " +
+                 std::to_string(SSF_GRAPH_MAX_STAMP_SPAN - 1) + " are sorted";
+        return SSF_ERR_STATE;
+    }
+    const int m = (int)m64;
+    if ((size_t)m > g.node_cap) {
+        const size_t cap = (size_t)m + (size_t)m / 4;
+        if (!g.bufs.grow({{(void**)&g.nodes, 16 * cap}, {(void**)&g.npos3, 12 * cap}, {(void**)&g.nrow, 4 * cap}})) {
+            h->err = "ssf_graph_build: allocation of the node table failed"; return SSF_ERR_DEVICE;
+        }
+        g.node_cap = cap;
+    }
+    const int passes = span < 256 ? 1 : span < 65536 ? 2 : 3;
+    const int which = launch_graph_sort(st, mv.nslots, n_elig, mm[0], passes, g.stamp, g.elig, g.cnt, g.key_a, g.slot_a, g.key_b, g.slot_b);
+    HCK(hipGetLastError());
+    launch_graph_sample(st, mv, g.bc, which == 0 ? g.slot_a : g.slot_b, m, p->stride, g.nodes, g.npos3, g.nrow);
+    HCK(hipGetLastError());
+    launch_graph_bind(st, mv, g.bc, g.nodes, m, p->look, g.w4, g.idx4);
+    HCK(hipGetLastError());
+    { int rc = sync_collect(h); if (rc) return rc; }
+    g.m = m; g.rows = h->n_model; g.look = p->look; g.gen = h->model_gen; g.built = true;
+    if (n_nodes) *n_nodes = m;
+    return SSF_OK;
+}
+int ssf_graph_info(ssf_handle* h, int* n_nodes, int* n_rows, int* valid) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    if (n_nodes) *n_nodes = h->graph.built ? h->graph.m : 0;
+    if (n_rows) *n_rows = h->graph.built ? h->graph.rows : 0;
+    if (valid) *valid = graph_valid(h) ? 1 : 0;
+    return SSF_OK;
+}
+int ssf_graph_get_nodes(ssf_handle* h, float* positions, int32_t* t_init, int32_t* rows, int capacity) {
+    if (!h || (!positions && !t_init && !rows)) return SSF_ERR_INVALID_ARG;
+    const GraphWs& g = h->graph;
+    if (!g.built) { h->err = "ssf_graph_get_nodes: no graph has been built (ssf_graph_build)"; return SSF_ERR_STATE; }
+    if (capacity < g.m) { h->err = "ssf_graph_get_nodes: " + std::to_string(g.m) + " nodes, room for " + std::to_string(capacity); return SSF_ERR_CAPACITY; }
+    hipStream_t st = h->stream;
+    const size_t m = g.m;
+    std::vector<float> rec;
+    if (positions) HCK(hipMemcpyAsync(positions, g.npos3, 12 * m, hipMemcpyDeviceToHost, st));
+    if (rows) HCK(hipMemcpyAsync(rows, g.nrow, 4 * m, hipMemcpyDeviceToHost, st));
+    if (t_init) { rec.resize(4 * m); HCK(hipMemcpyAsync(rec.data(), g.nodes, 16 * m, hipMemcpyDeviceToHost, st)); }
+    HCK(hipStreamSynchronize(st));
+    if (t_init) for (size_t k = 0; k < m; k++) std::memcpy(&t_init[k], &rec[4 * k + 3], 4);
+    return SSF_OK;
+}
+int ssf_graph_get_binding(ssf_handle* h, float* weights4, int32_t* idx4, int on_device) {
+    if (!h || (!weights4 && !idx4)) return SSF_ERR_INVALID_ARG;
+    { int rc = graph_usable(h, "ssf_graph_get_binding"); if (rc) return rc; }
+    const GraphWs& g = h->graph;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (weights4) HCK(hipMemcpyAsync(weights4, g.w4, 16 * (size_t)g.rows, kind, h->stream));
+    if (idx4) HCK(hipMemcpyAsync(idx4, g.idx4, 16 * (size_t)g.rows, kind, h->stream));
+    HCK(hipStreamSynchronize(h->stream));
+    return SSF_OK;
+}
+int ssf_graph_bind_points(ssf_handle* h, const float* points, const int32_t* t_init, int n, float* weights4, int32_t* idx4) {
+    if (!h || !points || !t_init || !weights4 || !idx4 || n < 0) return SSF_ERR_INVALID_ARG;
+    { int rc = graph_usable(h, "ssf_graph_bind_points"); if (rc) return rc; }
+    if (n == 0) return SSF_OK;
+    const GraphWs& g = h->graph;
+    float *d_p, *d_w; int32_t *d_t, *d_i;
+    DevTemps tmp;
+    HCK(tmp.take(&d_p, 12 * (size_t)n)); HCK(tmp.take(&d_t, 4 * (size_t)n)); HCK(tmp.take(&d_w, 16 * (size_t)n)); HCK(tmp.take(&d_i, 16 * (size_t)n));
+    hipStream_t st = h->stream;
+    HCK(hipMemcpyAsync(d_p, points, 12 * (size_t)n, hipMemcpyHostToDevice, st));
+    HCK(hipMemcpyAsync(d_t, t_init, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    { TimerScope ts(h); launch_graph_bind_points(st, d_p, d_t, n, g.nodes, g.m, g.look, d_w, d_i); }
+    HCK(hipGetLastError());
+    HCK(hipMemcpyAsync(weights4, d_w, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HCK(hipMemcpyAsync(idx4, d_i, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
+    { int rc = sync_collect(h); if (rc) return rc; }
+    return SSF_OK;
+}
+int ssf_graph_apply(ssf_handle* h, const float* nr, const float* nt) {
+    if (!h || !nr || !nt) return SSF_ERR_INVALID_ARG;
+    { int rc = graph_usable(h, "ssf_graph_apply"); if (rc) return rc; }
+    drop_shard_sizes(h);
+    h->ahead.valid = false;
+    const GraphWs& g = h->graph;
+    const size_t m = g.m;
+    float *d_nr, *d_nt, *d_nodes;
+    DevTemps tmp;
+    HCK(tmp.take(&d_nr, 36 * m)); HCK(tmp.take(&d_nt, 12 * m)); HCK(tmp.take(&d_nodes, 64 * m));
+    HCK(hipMemcpyAsync(d_nr, nr, 36 * m, hipMemcpyHostToDevice, h->stream));
+    HCK(hipMemcpyAsync(d_nt, nt, 12 * m, hipMemcpyHostToDevice, h->stream));
+    return deform_dense(h, g.m, g.npos3, d_nr, d_nt, d_nodes, g.w4, g.idx4);
+}
+}  // extern "C"

@@ -1,0 +1,329 @@
+// ssf_handle.hpp -- the handle (ssf_handle, the types it holds by value, HCK) and the few host helpers that the entry points
+// outside ssf_host.hip call.  Private to the library's host code: included by ssf_host.hip (the core ABI, where the helpers are
+// defined) and by ssf_render.hip, ssf_graph.hip and ssf_keyframes.hip, whose entry points sit next to their kernels.  Nothing
+// here is part of the frame path's device interface (ssf_device.hpp).
+#pragma once
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <deque>
+#include <initializer_list>
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+#include "ssf_device.hpp"
+#include "../../include/ssf_render.h"
+#include "../../include/ssf_graph.h"
+#include "../../include/ssf_keyframes.h"
+
+struct ncclComm; typedef struct ncclComm* ncclComm_t;      // (as <rccl/rccl.h> declares it: the handle only holds communicators)
+struct Uploader;                                            // the handle only points to it (ssf_host.hip)
+namespace ssf {
+struct KernelTimer {
+    struct Rec { const char* name; hipEvent_t e0, e1; };
+    std::vector<Rec> open, pool_free;
+    std::vector<Rec> pending;
+    std::map<std::string, std::pair<double, long long>> acc;
+    const char* cur_name = nullptr; hipEvent_t cur_e0 = nullptr, cur_e1 = nullptr;
+    // what an EMPTY (e0, e1) bracket measures on this device: the two event packets themselves (~5 us).  Part of it
+    // overlaps with the dispatch when a kernel sits in between: 0.7 x the empty bracket is what makes back-to-back
+    // launches agree with rocprofv3's kernel durations (relabelling pass: 14.3 us live vs 14.4 us rocprofv3).
+    double bracket_bias_ms = -1.0;
+};
+}  // namespace ssf
+using namespace ssf;          // (as every file that includes this header does: the handle's members are ssf:: types)
+
+// ---- the first ICP iteration of the next frame: inside the row-move kernel, or as a launch of its own? ------------------------
+// Both forms give the same record bit for bit (exact integer sums).  Which one is FASTER depends on what else the part is doing,
+// and flipped sign between measurements of round 5 (profiles/track_chain_r05.txt): alone on the part the fused form saves a launch
+// and a trip (first record 11 us after the frame's entry against 15); next to the extract launches of a filling pipeline its
+// 3900-workgroup launch finishes late (36 us against 27) -- the driver's 20-frame form ran 4-7 % faster WITHOUT the fusion, a
+// 1200-frame steady state 3-5 % faster WITH it.  So the handle measures: the period between consecutive frame completions of a
+// pipelined sequence is attributed to the form that was in effect, the two forms take turns of PROBE frames, and the better mean
+// holds for HOLD frames before the next probe.  A handle starts WITHOUT the fusion (short sequences are fill-bound and never leave
+// that phase).  Results do not depend on any of it.
+struct AheadTuner {
+    static const int START = 48, PROBE = 16, ROUNDS = 3, HOLD = 1024, SKIP = 2;
+    int forced = -1;                 // lab: SSF_ICP_AHEAD = 0 / 1 / 2 pins the form (2: fused and the track stream waits for the next batch)
+    int mode = 0, frames = 0, left = START, round = 0, since_switch = 0;
+    bool probing = false;
+    double sum[2] = {0, 0}; int n[2] = {0, 0};
+    double last_done_us = -1.0; int last_mode = 0;
+    int current() const { return forced >= 0 ? (forced ? 1 : 0) : mode; }
+    void sequence_break() { last_done_us = -1.0; }                       // (the period across a drained pipeline says nothing)
+    void frame_done(double t_us, int iters) {
+        if (forced >= 0) return;
+        if (last_done_us >= 0.0 && since_switch >= SKIP && probing && iters > 0) { sum[last_mode] += (t_us - last_done_us) / (double)(iters + 4); n[last_mode]++; }   // (per unit of chain work: iterations + the fixed part)
+        last_done_us = t_us; last_mode = mode; frames++; since_switch++;
+        if (--left > 0) return;
+        if (!probing) { probing = true; round = 0; sum[0] = sum[1] = 0; n[0] = n[1] = 0; mode ^= 1; left = PROBE; since_switch = 0; return; }
+        if (++round < 2 * ROUNDS) { mode ^= 1; left = PROBE; since_switch = 0; return; }
+        probing = false;
+        if (n[0] > 0 && n[1] > 0) mode = (sum[1] / n[1] < sum[0] / n[0]) ? 1 : 0;
+        left = HOLD; since_switch = 0;
+    }
+};
+
+// ---- handle -----------------------------------------------------------------------------------------
+struct IcpLoop {
+    bool active = false, valid = true, done = true;
+    int iter = 0;
+    unsigned long long ahead_seq = 0;         // != 0: the first iteration's record was accumulated ahead (ssf_handle::ahead)
+    double tf_inc[16], prev_error, JtJ[36];
+    M3 R_init; V3 t_init, t_inc_stale;
+};
+
+// Everything the extract stage of one BATCH of frames owns (cfg.extract_batch frames, slot b of every
+// buffer at + b * slab bytes).  With pipeline_depth > 0 there are pipeline_depth + 1 of these, each on
+// its own stream: the extract of later batches runs while the track/fuse chain (h->stream) consumes the
+// frames of an earlier one.  Extract has no cross-frame state (the RANSAC draws are keyed by the frame
+// number), so batches are independent of one another.
+struct ExtractCtx {
+    FrameMaps maps;                               // slot 0; maps.slab = bytes to the next slot
+    SurfelSoA frame;
+    unsigned long long* d_best = nullptr; uint8_t* d_matched = nullptr;
+    uint8_t* d_rgb_in = nullptr; float* d_depth_in = nullptr; float* d_depth_filt = nullptr; uint8_t* d_mask = nullptr;
+    float* d_wire = nullptr;                      // 26 S words: the frame supersurfels of a frame extracted elsewhere (ssf_submit_frame_tables)
+    char* d_pas = nullptr; char* d_team_ws = nullptr;      // relabelling passes in one launch per phase (k_passes_team): per-pass arguments, team workspace
+    ncclComm_t deal_comm = nullptr;               // dealt extract stage: this context's own communicator (a collective per batch on ITS stream)
+    bool mine = true; long long deal_batch = 0;   // ... whether the open batch is this rank's to extract, and its number in the frame stream
+    hipStream_t stream = nullptr; bool own_stream = false; int stream_prio = 0;
+    hipEvent_t ev_done = nullptr, ev_consumed = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
+    bool consumed_valid = false, timed = false;
+    hipGraph_t graph[SSF_MAX_BATCH + 1] = {}; hipGraphExec_t exec[SSF_MAX_BATCH + 1] = {};
+    // batch state: open (count > 0, !launched) -> in flight (launched, inflight > 0) -> free
+    int count = 0, inflight = 0, stamp0 = 0, nb_launched = 1; bool launched = false, waited = false;
+    uint32_t epoch0 = 0;
+    BatchIn in = {}; unsigned mask_bits = 0;
+    // pixel masks (ssf_dynamic.h): P mask bytes and 2 S pixel counts (total, masked) per slot; bit b of pixmask_bits: slot b has
+    // a mask.  A batch with any bit set runs the counting instantiations (k_render_moments<., true>, k_finalize_surfels<true>),
+    // whose segmentation chain is captured in a graph of its own.
+    uint8_t* d_pixmask = nullptr; uint32_t* d_pixcnt = nullptr; unsigned pixmask_bits = 0;
+    bool from_tables = false;                     // the batch came in through ssf_submit_frame_tables: its slot has no colour map
+    hipGraph_t graph_pm[SSF_MAX_BATCH + 1] = {}; hipGraphExec_t exec_pm[SSF_MAX_BATCH + 1] = {};
+};
+// the frame the track/fuse chain works on: slot views into its context
+struct ActiveFrame {
+    FrameMaps maps; SurfelSoA frame;
+    unsigned long long* d_best = nullptr; uint8_t* d_matched = nullptr;
+    ExtractCtx* ctx = nullptr; int slot = 0;
+    bool pixmask = false;                         // the frame was submitted with a pixel mask: ssf_get_dynamic_superpixels reads its counts
+    bool has_rgba = false;                        // the frame was extracted here: maps.rgba is its colour map (ssf_keyframes.h reads it)
+    bool activated = false;                       // a submitted frame has been made the current one (ssf_create only points at slot 0)
+};
+
+// Round 6: the tile-sorted copy (ssf_tile_rows.inc) in the product, for LARGE visible sets.  At BASELINE config 3 (940 k visible
+// rows, ten iterations) it takes k_icp from 23.0 to 18.8 us per iteration and the association from 55.6 to 29.9 us for a 35 us sort
+// (profiles/config3_sorted_rows_r06.txt); at the metric's 120 k visible rows and four iterations the sort costs more than it saves,
+// hence the threshold.  -DSSF_BIN_MIN_ROWS_DEFAULT=-1 builds a product without it (the A/B).
+#ifndef SSF_BIN_MIN_ROWS_DEFAULT
+#define SSF_BIN_MIN_ROWS_DEFAULT 400000
+#endif
+// The device buffers a workspace owns.  grow is all or nothing: allocate every (pointer, bytes) of `want`; only when all succeeded
+// free the old buffers and install the new ones.  A failed hipMalloc leaves its error behind in the runtime: it is cleared, so
+// that the next frame's launch checks do not report it.  release frees whatever grow installed, and so does the destructor (a
+// workspace is a member of the handle: ssf_destroy's `delete h` frees it): a pointer that a workspace gains is named in its grow
+// call and nowhere else.
+struct DevBufs {
+    std::vector<void**> owned;                                    // the workspace's members that hold a buffer
+    bool grow(std::initializer_list<std::pair<void**, size_t>> want) {
+        std::vector<void*> got;
+        for (const auto& w : want) {
+            void* q = nullptr;
+            if (hipMalloc(&q, std::max<size_t>(w.second, 1)) != hipSuccess) {
+                for (void* g : got) (void)hipFree(g);
+                (void)hipGetLastError();
+                return false;
+            }
+            got.push_back(q);
+        }
+        size_t i = 0;
+        for (const auto& w : want) { if (*w.first) (void)hipFree(*w.first); else owned.push_back(w.first); *w.first = got[i++]; }
+        return true;
+    }
+    void release() { for (void** q : owned) { (void)hipFree(*q); *q = nullptr; } owned.clear(); }
+    DevBufs() = default; DevBufs(const DevBufs&) = delete; ~DevBufs() { release(); }       // (owned points into the workspace that holds this)
+};
+// working buffers of ssf_render_model (ssf_render.h): allocated on first use; each group (per slot / per tile / list / staged images)
+// is grown as a whole or not at all (DevBufs::grow)
+struct RenderWs {
+    DevBufs bufs;
+    float4* rec = nullptr; uint2* rbox = nullptr; int32_t* logical = nullptr; uint32_t* seen = nullptr; uint32_t* bc = nullptr;
+    size_t slots = 0;                                              // per slot: record, pixel box, logical index, `seen` epoch
+    uint32_t* tcnt = nullptr; uint32_t* cursor = nullptr; size_t tiles = 0;           // per tile (+ 1): counts -> offsets, cursors
+    uint32_t* list = nullptr; size_t list_cap = 0;                                    // (tile -> slot) lists
+    unsigned long long* stats = nullptr;                          // fragments, filled pixels, rows shown, list entries
+    unsigned char* img = nullptr; size_t img_bytes = 0;           // host outputs, staged on the device
+    uint32_t epoch = 0;                                           // of the last render: seen[slot] == epoch <=> shown by it
+};
+// ssf_graph_build (ssf_graph.h): the resident node table and binding, and the working buffers of the time-order sort.  Allocated
+// on first use; each group (per slot / per node) is grown as a whole or not at all (DevBufs::grow)
+struct GraphWs {
+    DevBufs bufs;
+    int32_t* stamp = nullptr; uint8_t* elig = nullptr; int32_t* key_a = nullptr; int32_t* key_b = nullptr;
+    uint32_t* slot_a = nullptr; uint32_t* slot_b = nullptr; uint32_t* cnt = nullptr; uint32_t* bc = nullptr;
+    float* w4 = nullptr; int32_t* idx4 = nullptr; int* mm = nullptr; size_t slots = 0;       // per slot; w4 / idx4 per logical row
+    float4* nodes = nullptr; float* npos3 = nullptr; int32_t* nrow = nullptr; size_t node_cap = 0;   // per node, in time order
+    int m = 0, rows = 0, look = 0; bool built = false; unsigned long long gen = 0;          // valid <=> built && gen == h->model_gen
+};
+// the keyframe database of ssf_keyframes.h: everything is allocated by ssf_keyframes_configure, as a whole or not at all
+// (DevBufs::grow), and freed by ssf_keyframes_clear / ssf_destroy.  The host mirrors what it needs to address a keyframe (its
+// first pool row, row count, stamp, pose); codes, stamps and rows live on the device.
+struct KeyframeMeta { long long first; int rows; int stamp; float pose[12]; };
+struct KeyframeWs {
+    DevBufs bufs;
+    ssf_keyframes_params p{}; bool on = false;
+    int words = 0, gw = 0, gh = 0;
+    uint4* ferns = nullptr; uint32_t* q = nullptr; uint32_t* table = nullptr; int32_t* stamps = nullptr; uint32_t* diff = nullptr;
+    int32_t* rec = nullptr; uint8_t* bytes = nullptr;
+    ssf_surfels pool{};                           // the row pool: device arrays, a keyframe's rows consecutive (what _get / _put copy as they are)
+    std::vector<ssf_fern> host_ferns; std::vector<KeyframeMeta> kfs; long long rows_used = 0;
+};
+struct ssf_handle {
+    ssf_config cfg;
+    int S = 0, gx = 0, gy = 0;
+    std::string err;
+    hipStream_t stream = nullptr; bool own_stream = false; int stream_prio = 0;
+    SegParams seg; Cam cam;
+    std::vector<ExtractCtx> ctx; int open_ctx = 0, batch = 1;
+    std::deque<std::pair<int, int>> pending;      // (context, slot) submitted, not yet processed (oldest first)
+    ActiveFrame active; ActiveFrame* cc = &active; // the frame the track/fuse chain is working on (or last worked on)
+    uint32_t extract_ordinal = 0;                 // frames submitted so far = RNG epoch of the next frame
+    // ssf_process_sequence: frames still to be submitted; do_fuse submits them between its launches and its wait for
+    // the counters (the ~40 us of host work of a batch launch hide behind the ~55 us fuse chain on the GPU)
+    const void* const* seq_rgb = nullptr; const void* const* seq_depth = nullptr; const uint8_t* const* seq_pixmask = nullptr; int seq_next = 0, seq_n = 0, seq_on_device = 0, stamp_bias = 0;
+    long long n_waiter_matches = 0;           // frames whose association ran in a waiting ICP launch (debug)
+    int seq_k = 0;                            // frame of the sequence the track loop is working on (debug marks)
+    int seq_batches = 0;                      // batches launched by the running ssf_process_sequence (see seq_batch_size)
+    double us_wait_upload = 0.0;                          // the submitting thread's wait for uploads (ssf_upload_stats)
+    Uploader* up = nullptr; bool seq_upload = false;   // host frames of a sequence are copied ahead by a worker thread
+    // the format every frame entry point reads its images in (ssf_set_input_format, ssf_input.h); the buffers that hold frames
+    // on the device (batch input slabs, upload ring, pre-filter input) are sized for the largest one, so a change allocates nothing
+    int in_color = SSF_COLOR_RGB8, in_depth = SSF_DEPTH_F32_METRES; double in_scale = 1.0;
+    // multi-GPU: RCCL communicator over the ranks of cfg.nranks (ssf_comm_attach); the shard sizes of all ranks
+    // are all-gathered at the end of every frame and read lazily at the start of the next one
+    ncclComm_t comm = nullptr; int* d_all5 = nullptr;
+    int deal = 0; long long deal_batches = 0;     // ssf_comm_deal_extract: 0 replicated, 1 dealt, 2 dealt + the extracting rank re-imports its own tables (self-check)
+    // ... or the peer-to-peer exchange region of ssf_p2p_* (one node; no collective launches): own region, the peers'
+    // regions as mapped into this process, and one sequence number per exchange kind (identical on every rank)
+    struct P2P {
+        unsigned char* region = nullptr; size_t bytes = 0; bool fine = false;
+        bool same_device = false; double timeout_s = 30.0;       // ssf_p2p_configure
+        P2PView view{}; bool on = false; std::vector<void*> opened;
+        unsigned long long seq_icp = 0, seq_cnt = 0, seq_assoc = 0, seq_migr = 0;
+    } p2p;
+    unsigned long long all_seq = 0; bool all_pending = false, all_valid = false;
+    long long all_cnt[5 * SSF_MAX_RANKS];
+    SurfelSoA model[2]; int mcur = 0;
+    std::vector<void*> allocs;
+    struct Guarded { void* base; size_t bytes, guard; };
+    std::vector<Guarded> guarded;         // SSF_ALLOC_GUARD (debug): see dalloc
+    float* d_bf_in = nullptr; float* d_bf_out = nullptr; float* d_orient9 = nullptr; float* d_frame_orient9 = nullptr;
+    long long* d_icp = nullptr;
+    uint8_t* d_state = nullptr; int32_t* d_cand = nullptr; Counters* d_cnt = nullptr;
+    // multi-GPU migration: this shard's migrant table (SSF_MIGRANT_WORDS x S int32), state between the two fuse halves
+    int32_t* d_migrants = nullptr; PartitionWs fuse_ws{}; bool fuse_first = false, fuse_migrate = false, fusing = false;
+    MoveTotals fuse_totals{0, 0, 0, 0}; bool move_totals_on = true;      // (lab: SSF_MOVE_TOTALS=0 keeps the fuse launch's tail)
+    // model store: model[mcur] = dense array of the visible rows (ping-pong), oov[ocur] = out-of-view rows (deque
+    // with live flags, host mirror of the span below), dense = materialised [visible | out-of-view] view for the
+    // consumers of the whole model (get/set model, export, deformation)
+    OovStore oov[2]; int ocur = 0; int oov_head = 0, oov_tail = 0, oov_live = 0; long long n_recentres = 0;
+    uint8_t* d_state_oov = nullptr; uint32_t* d_bc_oov = nullptr;
+    // sums of the per-frame partition (PartitionWs): two sets of part_words, used alternately; 128 arrival counters
+    uint32_t* d_part = nullptr; uint32_t* d_part_ticket = nullptr; int part_words = 0, part_sup_vis = 0, part_sup_oov = 0, part_set = 0;
+    SurfelSoA dense; uint8_t* d_live_scratch = nullptr;
+    int32_t* d_scratch_map = nullptr;
+    long long* d_icp_replicas = nullptr; unsigned int* d_tickets = nullptr; float* d_srgb_lut = nullptr;
+    // host-mapped mailbox (fine-grained): results the host waits for are polled, not synchronised on
+    Mailbox* mb_host = nullptr; Mailbox* mb_dev = nullptr;
+    unsigned long long icp_seq = 0, cnt_seq = 0;
+    // first ICP iteration of the next submitted frame, accumulated ahead by the row-move kernel of the frame just
+    // fused (do_fuse): valid for exactly that frame, that pose and that model; anything else drops it
+    struct { bool valid = false; unsigned long long seq = 0; ExtractCtx* ctx = nullptr; int slot = 0; int stamp = 0; Rt pose; } ahead;
+    double wait_launched_us = 0.0; long long n_waiter_match_repairs = 0; long long dbg_stall_before_match_us = 0;     // see process_oldest: SSF_ICP_GO_MATCH has no acknowledgement
+    bool icp_ahead = true; int icp_ahead_mode = 1;         // 1: when the next frame's extract has finished (the product); 2 (lab): always, the track stream waits for it
+    AheadTuner ahead_tuner;
+    // chained ICP launches: iteration i + 1 is launched while iteration i runs and waits on the device for the host's
+    // word (launch_icp, IcpGo): slots in fine-grained device memory the host stores into directly
+    IcpGo* go = nullptr; bool icp_chain = true; unsigned long long go_count = 0;
+    bool graph_failed = false; hipStream_t capture_stream = nullptr;
+    // tile-sorted copy of the visible rows' ICP / association fields (launch_bin_rows), made at the start of a frame's
+    // tracking when the visible set is large (bin_min_rows); valid for that frame only
+    SurfelSoA bins{}; int32_t* d_bin_idx = nullptr; uint32_t* d_bin_count = nullptr; uint32_t* d_bin_cursor = nullptr;
+    bool bins_valid = false; int bin_min_rows = SSF_BIN_MIN_ROWS_DEFAULT;      // visible rows from which a frame's tracking streams the tile-sorted copy (< 0: never)
+    // pass_team: the relabelling passes of a phase as ONE launch with a frame per XCD (k_passes_team) instead of a launch per pass.
+    // Its workgroups must all be on the chip at once, so whole batches take turns across the contexts (launch_batch: a batch's
+    // chain waits for the previous batch's ev_done).
+    bool pass_team = false; ExtractCtx* team_prev = nullptr;
+    long long h_icp_local[SSF_ICP_RECORD];
+    long long* h_icp = nullptr; Counters* h_cnt = nullptr;
+    int n_model = 0, n_visible = 0, stamp = 0, max_passes = 0;
+    Rt pose;
+    IcpLoop icp;
+    long long id_offset = 0, global_n_model = -1, global_n_visible = -1;
+    bool have_frame = false;
+    int last_icp_valid = 0, last_icp_iters = 0;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    KernelTimer timer;
+    std::vector<std::string> timer_names;
+    double seq_mark_us[4][64] = {{0}}, seq_launch_us[32] = {0}, seq_launch_host_us[32] = {0}; int seq_launch_n[32] = {0}, seq_launches = 0;   // debug: entry / first ICP record / ICP done / counters back per frame, batch launches
+    double seq_t0_us = 0, seq_done_us[64] = {0};      // debug: completion time of the first frames of the last ssf_process_sequence
+    double host_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // debug: submit | icp loop | match+fuse | frames | extract ready at activation | first icp iteration
+    RenderWs render;                              // ssf_render_model (ssf_render.h)
+    GraphWs graph;                                // ssf_graph_* (ssf_graph.h)
+    KeyframeWs kf;                                // ssf_keyframes_* (ssf_keyframes.h)
+    unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense)
+};
+
+#define HCK(call)                                                                                    \
+    do {                                                                                             \
+        hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess) {                                                                      \
+            h->err = std::string(#call) + ": " + hipGetErrorString(e_);                              \
+            return SSF_ERR_DEVICE;                                                                   \
+        }                                                                                            \
+    } while (0)
+
+// ---- helpers of ssf_host.hip that the render, graph and keyframe entry points call -------------------------------------------
+#pragma GCC visibility push(hidden)       // (shared by the library's own files, no part of what it exports)
+namespace ssf {
+// device temporaries of one call: freed on every exit path
+struct DevTemps {
+    std::vector<void*> p;
+    template <typename T> hipError_t take(T** out, size_t bytes) {
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, bytes ? bytes : 1);
+        if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
+        return e;
+    }
+    ~DevTemps() { for (void* q : p) (void)hipFree(q); }
+};
+// while one lives, the calling thread's launches are timed into h->timer (cfg.profile == 1)
+struct TimerScope { ssf_handle* h; explicit TimerScope(ssf_handle* hh); ~TimerScope(); };
+void timer_collect(KernelTimer* t);                 // call after a stream sync
+// the end of a call that launched under a TimerScope: wait for the handle's stream, then book the brackets it recorded
+inline int sync_collect(ssf_handle* h) {
+    HCK(hipStreamSynchronize(h->stream)); if (h->cfg.profile == 1) timer_collect(&h->timer); return SSF_OK;
+}
+ModelView model_view(const ssf_handle* h, bool visible_only);
+int model_at_rest(ssf_handle* h, const char* who = nullptr, const char* lacks = nullptr);
+int materialise(ssf_handle* h);
+int store_from_dense(ssf_handle* h, int n, int n_visible);
+void drop_shard_sizes(ssf_handle* h);
+inline Rt pose_from12(const float* p) {
+    Rt r; r.R = m3(v3(p[0], p[1], p[2]), v3(p[3], p[4], p[5]), v3(p[6], p[7], p[8])); r.t = v3(p[9], p[10], p[11]); return r;
+}
+inline void pose_to12(const Rt& r, float* p) {
+    p[0] = r.R.r0.x; p[1] = r.R.r0.y; p[2] = r.R.r0.z; p[3] = r.R.r1.x; p[4] = r.R.r1.y; p[5] = r.R.r1.z;
+    p[6] = r.R.r2.x; p[7] = r.R.r2.y; p[8] = r.R.r2.z; p[9] = r.t.x; p[10] = r.t.y; p[11] = r.t.z;
+}
+int align_loop(ssf_handle* h, const float* d_pos, const float* d_lab, const float* d_nrm, const float* d_conf, int n, long long* d_out,
+               const float* init_pose, float* rel_pose, int* valid, int* iters, int* pairs_last);
+int deform_dense(ssf_handle* h, int m, const float* d_np, const float* d_nr, const float* d_nt, float* d_nodes, const float* d_w,
+                 const int32_t* d_i);
+// rows [s0, s0 + n) of src -> rows [d0, d0 + n) of dst on the handle's stream (enqueued only); a NULL array of dst is skipped
+int copy_rows(ssf_handle* h, const ssf_surfels& dst, size_t d0, const ssf_surfels& src, size_t s0, size_t n, hipMemcpyKind kind);
+}  // namespace ssf
+#pragma GCC visibility pop

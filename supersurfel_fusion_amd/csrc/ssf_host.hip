@@ -3,49 +3,30 @@
 // hot-path parts only): extract contexts (pipelined / batched extract on their own streams and graphs),
 // the track chain (ICP loop with the host Gauss-Newton step of core/src/dense_registration.cu:324-421,
 // association, fusion, model-store upkeep), the RCCL exchanges of the multi-GPU mode, the loop-closure
-// registration, and the C ABI of include/ssf.h.
+// registration, and the C ABI of include/ssf.h.  The handle itself and the helpers shared with the entry points of ssf_render.h,
+// ssf_graph.h and ssf_keyframes.h -- which sit next to their kernels in ssf_render.hip, ssf_graph.hip, ssf_keyframes.hip -- are
+// declared in ssf_handle.hpp.
 //
 // There is NO CPU fallback here: without a gfx950 device ssf_create fails with SSF_ERR_NO_DEVICE.
-#include <algorithm>
 #include <atomic>
 #include <cfloat>
-#include <climits>
 #include <chrono>
-#include <deque>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <map>
 #include <new>
-#include <string>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
 #include <type_traits>
-#include <utility>
-#include <vector>
 #include <dlfcn.h>
 #include <unistd.h>
 #include <rccl/rccl.h>          // types only: the library is resolved at run time (dlopen), never linked
-#include "../../include/ssf.h"
-#include "ssf_device.hpp"
+#include "ssf_handle.hpp"          // (the handle; with it ssf_device.hpp, include/ssf*.h and the containers it holds)
 
 using namespace ssf;
 
 // ---- kernel timer (cfg.profile) -------------------------------------------------------------------
 namespace ssf {
-struct KernelTimer {
-    struct Rec { const char* name; hipEvent_t e0, e1; };
-    std::vector<Rec> open, pool_free;
-    std::vector<Rec> pending;
-    std::map<std::string, std::pair<double, long long>> acc;
-    const char* cur_name = nullptr; hipEvent_t cur_e0 = nullptr, cur_e1 = nullptr;
-    // what an EMPTY (e0, e1) bracket measures on this device: the two event packets themselves (~5 us).  Part of it
-    // overlaps with the dispatch when a kernel sits in between: 0.7 x the empty bracket is what makes back-to-back
-    // launches agree with rocprofv3's kernel durations (relabelling pass: 14.3 us live vs 14.4 us rocprofv3).
-    double bracket_bias_ms = -1.0;
-};
 static thread_local KernelTimer* g_timer = nullptr;
 KernelTimer* current_timer() { return g_timer; }
 void set_current_timer(KernelTimer* t) { g_timer = t; }
@@ -73,7 +54,7 @@ static void timer_calibrate(KernelTimer* t, hipStream_t st) {
     for (auto& x : e) (void)hipEventDestroy(x);
     t->bracket_bias_ms = n ? 0.7 * sum / n : 0.0;
 }
-static void timer_collect(KernelTimer* t) {     // call after a stream sync
+void timer_collect(KernelTimer* t) {     // call after a stream sync
     const double bias = t->bracket_bias_ms > 0.0 ? t->bracket_bias_ms : 0.0;
     for (auto& r : t->pending) {
         float ms = 0.f;
@@ -82,6 +63,11 @@ static void timer_collect(KernelTimer* t) {     // call after a stream sync
     }
     t->pending.clear();
 }
+TimerScope::TimerScope(ssf_handle* hh) : h(hh) {
+    if (hh->cfg.profile == 1) timer_calibrate(&hh->timer, hh->stream);       // first use only
+    set_current_timer(hh->cfg.profile == 1 ? &hh->timer : nullptr);
+}
+TimerScope::~TimerScope() { set_current_timer(nullptr); }
 }  // namespace ssf
 
 // ---- host solvers: dependency-free counterparts of the reference's Eigen calls ---------------------
@@ -473,255 +459,7 @@ struct StreamPool {
 };
 static StreamPool& stream_pool() { static StreamPool* p = new StreamPool(); return *p; }      // (never destroyed: the runtime may be gone by then)
 
-// ---- the first ICP iteration of the next frame: inside the row-move kernel, or as a launch of its own? ------------------------
-// Both forms give the same record bit for bit (exact integer sums).  Which one is FASTER depends on what else the part is doing,
-// and flipped sign between measurements of round 5 (profiles/track_chain_r05.txt): alone on the part the fused form saves a launch
-// and a trip (first record 11 us after the frame's entry against 15); next to the extract launches of a filling pipeline its
-// 3900-workgroup launch finishes late (36 us against 27) -- the driver's 20-frame form ran 4-7 % faster WITHOUT the fusion, a
-// 1200-frame steady state 3-5 % faster WITH it.  So the handle measures: the period between consecutive frame completions of a
-// pipelined sequence is attributed to the form that was in effect, the two forms take turns of PROBE frames, and the better mean
-// holds for HOLD frames before the next probe.  A handle starts WITHOUT the fusion (short sequences are fill-bound and never leave
-// that phase).  Results do not depend on any of it.
-struct AheadTuner {
-    static const int START = 48, PROBE = 16, ROUNDS = 3, HOLD = 1024, SKIP = 2;
-    int forced = -1;                 // lab: SSF_ICP_AHEAD = 0 / 1 / 2 pins the form (2: fused and the track stream waits for the next batch)
-    int mode = 0, frames = 0, left = START, round = 0, since_switch = 0;
-    bool probing = false;
-    double sum[2] = {0, 0}; int n[2] = {0, 0};
-    double last_done_us = -1.0; int last_mode = 0;
-    int current() const { return forced >= 0 ? (forced ? 1 : 0) : mode; }
-    void sequence_break() { last_done_us = -1.0; }                       // (the period across a drained pipeline says nothing)
-    void frame_done(double t_us, int iters) {
-        if (forced >= 0) return;
-        if (last_done_us >= 0.0 && since_switch >= SKIP && probing && iters > 0) { sum[last_mode] += (t_us - last_done_us) / (double)(iters + 4); n[last_mode]++; }   // (per unit of chain work: iterations + the fixed part)
-        last_done_us = t_us; last_mode = mode; frames++; since_switch++;
-        if (--left > 0) return;
-        if (!probing) { probing = true; round = 0; sum[0] = sum[1] = 0; n[0] = n[1] = 0; mode ^= 1; left = PROBE; since_switch = 0; return; }
-        if (++round < 2 * ROUNDS) { mode ^= 1; left = PROBE; since_switch = 0; return; }
-        probing = false;
-        if (n[0] > 0 && n[1] > 0) mode = (sum[1] / n[1] < sum[0] / n[0]) ? 1 : 0;
-        left = HOLD; since_switch = 0;
-    }
-};
-
-// ---- handle -----------------------------------------------------------------------------------------
-struct IcpLoop {
-    bool active = false, valid = true, done = true;
-    int iter = 0;
-    unsigned long long ahead_seq = 0;         // != 0: the first iteration's record was accumulated ahead (ssf_handle::ahead)
-    double tf_inc[16], prev_error, JtJ[36];
-    M3 R_init; V3 t_init, t_inc_stale;
-};
-
-// Everything the extract stage of one BATCH of frames owns (cfg.extract_batch frames, slot b of every
-// buffer at + b * slab bytes).  With pipeline_depth > 0 there are pipeline_depth + 1 of these, each on
-// its own stream: the extract of later batches runs while the track/fuse chain (h->stream) consumes the
-// frames of an earlier one.  Extract has no cross-frame state (the RANSAC draws are keyed by the frame
-// number), so batches are independent of one another.
-struct ExtractCtx {
-    FrameMaps maps;                               // slot 0; maps.slab = bytes to the next slot
-    SurfelSoA frame;
-    unsigned long long* d_best = nullptr; uint8_t* d_matched = nullptr;
-    uint8_t* d_rgb_in = nullptr; float* d_depth_in = nullptr; float* d_depth_filt = nullptr; uint8_t* d_mask = nullptr;
-    float* d_wire = nullptr;                      // 26 S words: the frame supersurfels of a frame extracted elsewhere (ssf_submit_frame_tables)
-    char* d_pas = nullptr; char* d_team_ws = nullptr;      // relabelling passes in one launch per phase (k_passes_team): per-pass arguments, team workspace
-    ncclComm_t deal_comm = nullptr;               // dealt extract stage: this context's own communicator (a collective per batch on ITS stream)
-    bool mine = true; long long deal_batch = 0;   // ... whether the open batch is this rank's to extract, and its number in the frame stream
-    hipStream_t stream = nullptr; bool own_stream = false; int stream_prio = 0;
-    hipEvent_t ev_done = nullptr, ev_consumed = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
-    bool consumed_valid = false, timed = false;
-    hipGraph_t graph[SSF_MAX_BATCH + 1] = {}; hipGraphExec_t exec[SSF_MAX_BATCH + 1] = {};
-    // batch state: open (count > 0, !launched) -> in flight (launched, inflight > 0) -> free
-    int count = 0, inflight = 0, stamp0 = 0, nb_launched = 1; bool launched = false, waited = false;
-    uint32_t epoch0 = 0;
-    BatchIn in = {}; unsigned mask_bits = 0;
-    // pixel masks (ssf_dynamic.h): P mask bytes and 2 S pixel counts (total, masked) per slot; bit b of pixmask_bits: slot b has
-    // a mask.  A batch with any bit set runs the counting instantiations (k_render_moments<., true>, k_finalize_surfels<true>),
-    // whose segmentation chain is captured in a graph of its own.
-    uint8_t* d_pixmask = nullptr; uint32_t* d_pixcnt = nullptr; unsigned pixmask_bits = 0;
-    bool from_tables = false;                     // the batch came in through ssf_submit_frame_tables: its slot has no colour map
-    hipGraph_t graph_pm[SSF_MAX_BATCH + 1] = {}; hipGraphExec_t exec_pm[SSF_MAX_BATCH + 1] = {};
-};
-// the frame the track/fuse chain works on: slot views into its context
-struct ActiveFrame {
-    FrameMaps maps; SurfelSoA frame;
-    unsigned long long* d_best = nullptr; uint8_t* d_matched = nullptr;
-    ExtractCtx* ctx = nullptr; int slot = 0;
-    bool pixmask = false;                         // the frame was submitted with a pixel mask: ssf_get_dynamic_superpixels reads its counts
-    bool has_rgba = false;                        // the frame was extracted here: maps.rgba is its colour map (ssf_keyframes.h reads it)
-    bool activated = false;                       // a submitted frame has been made the current one (ssf_create only points at slot 0)
-};
-
-// Round 6: the tile-sorted copy (ssf_tile_rows.inc) in the product, for LARGE visible sets.  At BASELINE config 3 (940 k visible
-// rows, ten iterations) it takes k_icp from 23.0 to 18.8 us per iteration and the association from 55.6 to 29.9 us for a 35 us sort
-// (profiles/config3_sorted_rows_r06.txt); at the metric's 120 k visible rows and four iterations the sort costs more than it saves,
-// hence the threshold.  -DSSF_BIN_MIN_ROWS_DEFAULT=-1 builds a product without it (the A/B).
-#ifndef SSF_BIN_MIN_ROWS_DEFAULT
-#define SSF_BIN_MIN_ROWS_DEFAULT 400000
-#endif
-// The device buffers a workspace owns.  grow is all or nothing: allocate every (pointer, bytes) of `want`; only when all succeeded
-// free the old buffers and install the new ones.  A failed hipMalloc leaves its error behind in the runtime: it is cleared, so
-// that the next frame's launch checks do not report it.  release frees whatever grow installed (ssf_destroy): a pointer that a
-// workspace gains is named in its grow call and nowhere else.
-struct DevBufs {
-    std::vector<void**> owned;                                    // the workspace's members that hold a buffer
-    bool grow(std::initializer_list<std::pair<void**, size_t>> want) {
-        std::vector<void*> got;
-        for (const auto& w : want) {
-            void* q = nullptr;
-            if (hipMalloc(&q, std::max<size_t>(w.second, 1)) != hipSuccess) {
-                for (void* g : got) (void)hipFree(g);
-                (void)hipGetLastError();
-                return false;
-            }
-            got.push_back(q);
-        }
-        size_t i = 0;
-        for (const auto& w : want) { if (*w.first) (void)hipFree(*w.first); else owned.push_back(w.first); *w.first = got[i++]; }
-        return true;
-    }
-    void release() { for (void** q : owned) { (void)hipFree(*q); *q = nullptr; } owned.clear(); }
-};
-// working buffers of ssf_render_model (ssf_render.h): allocated on first use; each group (per slot / per tile / list / staged images)
-// is grown as a whole or not at all (DevBufs::grow)
-struct RenderWs {
-    DevBufs bufs;
-    float4* rec = nullptr; uint2* rbox = nullptr; int32_t* logical = nullptr; uint32_t* seen = nullptr; uint32_t* bc = nullptr;
-    size_t slots = 0;                                              // per slot: record, pixel box, logical index, `seen` epoch
-    uint32_t* tcnt = nullptr; uint32_t* cursor = nullptr; size_t tiles = 0;           // per tile (+ 1): counts -> offsets, cursors
-    uint32_t* list = nullptr; size_t list_cap = 0;                                    // (tile -> slot) lists
-    unsigned long long* stats = nullptr;                          // fragments, filled pixels, rows shown, list entries
-    unsigned char* img = nullptr; size_t img_bytes = 0;           // host outputs, staged on the device
-    uint32_t epoch = 0;                                           // of the last render: seen[slot] == epoch <=> shown by it
-};
-// ssf_graph_build (ssf_graph.h): the resident node table and binding, and the working buffers of the time-order sort.  Allocated
-// on first use; each group (per slot / per node) is grown as a whole or not at all (DevBufs::grow)
-struct GraphWs {
-    DevBufs bufs;
-    int32_t* stamp = nullptr; uint8_t* elig = nullptr; int32_t* key_a = nullptr; int32_t* key_b = nullptr;
-    uint32_t* slot_a = nullptr; uint32_t* slot_b = nullptr; uint32_t* cnt = nullptr; uint32_t* bc = nullptr;
-    float* w4 = nullptr; int32_t* idx4 = nullptr; int* mm = nullptr; size_t slots = 0;       // per slot; w4 / idx4 per logical row
-    float4* nodes = nullptr; float* npos3 = nullptr; int32_t* nrow = nullptr; size_t node_cap = 0;   // per node, in time order
-    int m = 0, rows = 0, look = 0; bool built = false; unsigned long long gen = 0;          // valid <=> built && gen == h->model_gen
-};
-// the keyframe database of ssf_keyframes.h: everything is allocated by ssf_keyframes_configure, as a whole or not at all
-// (DevBufs::grow), and freed by ssf_keyframes_clear / ssf_destroy.  The host mirrors what it needs to address a keyframe (its
-// first pool row, row count, stamp, pose); codes, stamps and rows live on the device.
-struct KeyframeMeta { long long first; int rows; int stamp; float pose[12]; };
-struct KeyframeWs {
-    DevBufs bufs;
-    ssf_keyframes_params p{}; bool on = false;
-    int words = 0, gw = 0, gh = 0;
-    uint4* ferns = nullptr; uint32_t* q = nullptr; uint32_t* table = nullptr; int32_t* stamps = nullptr; uint32_t* diff = nullptr;
-    int32_t* rec = nullptr; uint8_t* bytes = nullptr;
-    KfPool pool{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    std::vector<ssf_fern> host_ferns; std::vector<KeyframeMeta> kfs; long long rows_used = 0;
-};
-struct ssf_handle {
-    ssf_config cfg;
-    int S = 0, gx = 0, gy = 0;
-    std::string err;
-    hipStream_t stream = nullptr; bool own_stream = false; int stream_prio = 0;
-    SegParams seg; Cam cam;
-    std::vector<ExtractCtx> ctx; int open_ctx = 0, batch = 1;
-    std::deque<std::pair<int, int>> pending;      // (context, slot) submitted, not yet processed (oldest first)
-    ActiveFrame active; ActiveFrame* cc = &active; // the frame the track/fuse chain is working on (or last worked on)
-    uint32_t extract_ordinal = 0;                 // frames submitted so far = RNG epoch of the next frame
-    // ssf_process_sequence: frames still to be submitted; do_fuse submits them between its launches and its wait for
-    // the counters (the ~40 us of host work of a batch launch hide behind the ~55 us fuse chain on the GPU)
-    const void* const* seq_rgb = nullptr; const void* const* seq_depth = nullptr; const uint8_t* const* seq_pixmask = nullptr; int seq_next = 0, seq_n = 0, seq_on_device = 0, stamp_bias = 0;
-    long long n_waiter_matches = 0;           // frames whose association ran in a waiting ICP launch (debug)
-    int seq_k = 0;                            // frame of the sequence the track loop is working on (debug marks)
-    int seq_batches = 0;                      // batches launched by the running ssf_process_sequence (see seq_batch_size)
-    double us_wait_upload = 0.0;                          // the submitting thread's wait for uploads (ssf_upload_stats)
-    Uploader* up = nullptr; bool seq_upload = false;   // host frames of a sequence are copied ahead by a worker thread
-    // the format every frame entry point reads its images in (ssf_set_input_format, ssf_input.h); the buffers that hold frames
-    // on the device (batch input slabs, upload ring, pre-filter input) are sized for the largest one, so a change allocates nothing
-    int in_color = SSF_COLOR_RGB8, in_depth = SSF_DEPTH_F32_METRES; double in_scale = 1.0;
-    // multi-GPU: RCCL communicator over the ranks of cfg.nranks (ssf_comm_attach); the shard sizes of all ranks
-    // are all-gathered at the end of every frame and read lazily at the start of the next one
-    ncclComm_t comm = nullptr; int* d_all5 = nullptr;
-    int deal = 0; long long deal_batches = 0;     // ssf_comm_deal_extract: 0 replicated, 1 dealt, 2 dealt + the extracting rank re-imports its own tables (self-check)
-    // ... or the peer-to-peer exchange region of ssf_p2p_* (one node; no collective launches): own region, the peers'
-    // regions as mapped into this process, and one sequence number per exchange kind (identical on every rank)
-    struct P2P {
-        unsigned char* region = nullptr; size_t bytes = 0; bool fine = false;
-        bool same_device = false; double timeout_s = 30.0;       // ssf_p2p_configure
-        P2PView view{}; bool on = false; std::vector<void*> opened;
-        unsigned long long seq_icp = 0, seq_cnt = 0, seq_assoc = 0, seq_migr = 0;
-    } p2p;
-    unsigned long long all_seq = 0; bool all_pending = false, all_valid = false;
-    long long all_cnt[5 * SSF_MAX_RANKS];
-    SurfelSoA model[2]; int mcur = 0;
-    std::vector<void*> allocs;
-    struct Guarded { void* base; size_t bytes, guard; };
-    std::vector<Guarded> guarded;         // SSF_ALLOC_GUARD (debug): see dalloc
-    float* d_bf_in = nullptr; float* d_bf_out = nullptr; float* d_orient9 = nullptr; float* d_frame_orient9 = nullptr;
-    long long* d_icp = nullptr;
-    uint8_t* d_state = nullptr; int32_t* d_cand = nullptr; Counters* d_cnt = nullptr;
-    // multi-GPU migration: this shard's migrant table (SSF_MIGRANT_WORDS x S int32), state between the two fuse halves
-    int32_t* d_migrants = nullptr; PartitionWs fuse_ws{}; bool fuse_first = false, fuse_migrate = false, fusing = false;
-    MoveTotals fuse_totals{0, 0, 0, 0}; bool move_totals_on = true;      // (lab: SSF_MOVE_TOTALS=0 keeps the fuse launch's tail)
-    // model store: model[mcur] = dense array of the visible rows (ping-pong), oov[ocur] = out-of-view rows (deque
-    // with live flags, host mirror of the span below), dense = materialised [visible | out-of-view] view for the
-    // consumers of the whole model (get/set model, export, deformation)
-    OovStore oov[2]; int ocur = 0; int oov_head = 0, oov_tail = 0, oov_live = 0; long long n_recentres = 0;
-    uint8_t* d_state_oov = nullptr; uint32_t* d_bc_oov = nullptr;
-    // sums of the per-frame partition (PartitionWs): two sets of part_words, used alternately; 128 arrival counters
-    uint32_t* d_part = nullptr; uint32_t* d_part_ticket = nullptr; int part_words = 0, part_sup_vis = 0, part_sup_oov = 0, part_set = 0;
-    SurfelSoA dense; uint8_t* d_live_scratch = nullptr;
-    int32_t* d_scratch_map = nullptr;
-    long long* d_icp_replicas = nullptr; unsigned int* d_tickets = nullptr; float* d_srgb_lut = nullptr;
-    // host-mapped mailbox (fine-grained): results the host waits for are polled, not synchronised on
-    Mailbox* mb_host = nullptr; Mailbox* mb_dev = nullptr;
-    unsigned long long icp_seq = 0, cnt_seq = 0;
-    // first ICP iteration of the next submitted frame, accumulated ahead by the row-move kernel of the frame just
-    // fused (do_fuse): valid for exactly that frame, that pose and that model; anything else drops it
-    struct { bool valid = false; unsigned long long seq = 0; ExtractCtx* ctx = nullptr; int slot = 0; int stamp = 0; Rt pose; } ahead;
-    double wait_launched_us = 0.0; long long n_waiter_match_repairs = 0; long long dbg_stall_before_match_us = 0;     // see process_oldest: SSF_ICP_GO_MATCH has no acknowledgement
-    bool icp_ahead = true; int icp_ahead_mode = 1;         // 1: when the next frame's extract has finished (the product); 2 (lab): always, the track stream waits for it
-    AheadTuner ahead_tuner;
-    // chained ICP launches: iteration i + 1 is launched while iteration i runs and waits on the device for the host's
-    // word (launch_icp, IcpGo): slots in fine-grained device memory the host stores into directly
-    IcpGo* go = nullptr; bool icp_chain = true; unsigned long long go_count = 0;
-    bool graph_failed = false; hipStream_t capture_stream = nullptr;
-    // tile-sorted copy of the visible rows' ICP / association fields (launch_bin_rows), made at the start of a frame's
-    // tracking when the visible set is large (bin_min_rows); valid for that frame only
-    SurfelSoA bins{}; int32_t* d_bin_idx = nullptr; uint32_t* d_bin_count = nullptr; uint32_t* d_bin_cursor = nullptr;
-    bool bins_valid = false; int bin_min_rows = SSF_BIN_MIN_ROWS_DEFAULT;      // visible rows from which a frame's tracking streams the tile-sorted copy (< 0: never)
-    // pass_team: the relabelling passes of a phase as ONE launch with a frame per XCD (k_passes_team) instead of a launch per pass.
-    // Its workgroups must all be on the chip at once, so whole batches take turns across the contexts (launch_batch: a batch's
-    // chain waits for the previous batch's ev_done).
-    bool pass_team = false; ExtractCtx* team_prev = nullptr;
-    long long h_icp_local[SSF_ICP_RECORD];
-    long long* h_icp = nullptr; Counters* h_cnt = nullptr;
-    int n_model = 0, n_visible = 0, stamp = 0, max_passes = 0;
-    Rt pose;
-    IcpLoop icp;
-    long long id_offset = 0, global_n_model = -1, global_n_visible = -1;
-    bool have_frame = false;
-    int last_icp_valid = 0, last_icp_iters = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    KernelTimer timer;
-    std::vector<std::string> timer_names;
-    double seq_mark_us[4][64] = {{0}}, seq_launch_us[32] = {0}, seq_launch_host_us[32] = {0}; int seq_launch_n[32] = {0}, seq_launches = 0;   // debug: entry / first ICP record / ICP done / counters back per frame, batch launches
-    double seq_t0_us = 0, seq_done_us[64] = {0};      // debug: completion time of the first frames of the last ssf_process_sequence
-    double host_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // debug: submit | icp loop | match+fuse | frames | extract ready at activation | first icp iteration
-    RenderWs render;                              // ssf_render_model (ssf_render.h)
-    GraphWs graph;                                // ssf_graph_* (ssf_graph.h)
-    KeyframeWs kf;                                // ssf_keyframes_* (ssf_keyframes.h)
-    unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense)
-};
 static std::string g_create_err;
-
-#define HCK(call)                                                                                    \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            h->err = std::string(#call) + ": " + hipGetErrorString(e_);                              \
-            return SSF_ERR_DEVICE;                                                                   \
-        }                                                                                            \
-    } while (0)
 
 #define NCK(call)                                                                                    \
     do {                                                                                             \
@@ -791,33 +529,19 @@ static void check_guards(ssf_handle* h) {
         idx++;
     }
 }
+// the ten streams of a supersurfel row set, stated once: f(the stream's member, its 4-byte words per row)
+template <typename F> static void each_stream(F&& f) {
+    f(&SurfelSoA::pos, 3); f(&SurfelSoA::col, 3); f(&SurfelSoA::lab, 3); f(&SurfelSoA::stamps, 2); f(&SurfelSoA::r0, 3);
+    f(&SurfelSoA::r1, 3); f(&SurfelSoA::r2, 3); f(&SurfelSoA::shape, 6); f(&SurfelSoA::dims, 2); f(&SurfelSoA::conf, 1);
+}
 static bool alloc_surfels(ssf_handle* h, SurfelSoA& s, size_t n) {
-    return dalloc(h, &s.pos, 3 * n) && dalloc(h, &s.col, 3 * n) && dalloc(h, &s.lab, 3 * n) && dalloc(h, &s.stamps, 2 * n) &&
-           dalloc(h, &s.r0, 3 * n) && dalloc(h, &s.r1, 3 * n) && dalloc(h, &s.r2, 3 * n) && dalloc(h, &s.shape, 6 * n) &&
-           dalloc(h, &s.dims, 2 * n) && dalloc(h, &s.conf, n);
+    bool ok = true;
+    each_stream([&](auto m, size_t w) { ok = ok && dalloc(h, &(s.*m), w * n); });
+    return ok;
 }
 static void zero_surfels(ssf_handle* h, SurfelSoA& s, size_t n) {
-    (void)hipMemsetAsync(s.pos, 0, 12 * n, h->stream); (void)hipMemsetAsync(s.col, 0, 12 * n, h->stream);
-    (void)hipMemsetAsync(s.lab, 0, 12 * n, h->stream); (void)hipMemsetAsync(s.stamps, 0, 8 * n, h->stream);
-    (void)hipMemsetAsync(s.r0, 0, 12 * n, h->stream); (void)hipMemsetAsync(s.r1, 0, 12 * n, h->stream);
-    (void)hipMemsetAsync(s.r2, 0, 12 * n, h->stream); (void)hipMemsetAsync(s.shape, 0, 24 * n, h->stream);
-    (void)hipMemsetAsync(s.dims, 0, 8 * n, h->stream); (void)hipMemsetAsync(s.conf, 0, 4 * n, h->stream);
+    each_stream([&](auto m, size_t w) { (void)hipMemsetAsync(s.*m, 0, 4 * w * n, h->stream); });
 }
-static Rt pose_from12(const float* p) {
-    Rt r; r.R = m3(v3(p[0], p[1], p[2]), v3(p[3], p[4], p[5]), v3(p[6], p[7], p[8])); r.t = v3(p[9], p[10], p[11]); return r;
-}
-static void pose_to12(const Rt& r, float* p) {
-    p[0] = r.R.r0.x; p[1] = r.R.r0.y; p[2] = r.R.r0.z; p[3] = r.R.r1.x; p[4] = r.R.r1.y; p[5] = r.R.r1.z;
-    p[6] = r.R.r2.x; p[7] = r.R.r2.y; p[8] = r.R.r2.z; p[9] = r.t.x; p[10] = r.t.y; p[11] = r.t.z;
-}
-struct TimerScope {
-    ssf_handle* h;
-    explicit TimerScope(ssf_handle* hh) : h(hh) {
-        if (hh->cfg.profile == 1) timer_calibrate(&hh->timer, hh->stream);       // first use only
-        set_current_timer(hh->cfg.profile == 1 ? &hh->timer : nullptr);
-    }
-    ~TimerScope() { set_current_timer(nullptr); }
-};
 
 // ---- stages -----------------------------------------------------------------------------------------
 // the segmentation chain between ingest and finalize: fixed topology and arguments per context.
@@ -1261,18 +985,14 @@ static void icp_end(ssf_handle* h, int* valid) {
 // ---- model store upkeep -----------------------------------------------------------------------------------
 static SurfelSoA soa_rows(const SurfelSoA& s, size_t r) {       // view starting at row r
     SurfelSoA v = s;
-    v.pos += 3 * r; v.col += 3 * r; v.lab += 3 * r; v.stamps += 2 * r; v.r0 += 3 * r; v.r1 += 3 * r; v.r2 += 3 * r;
-    v.shape += 6 * r; v.dims += 2 * r; v.conf += r;
+    each_stream([&](auto m, size_t w) { v.*m += w * r; });
     return v;
 }
 static int copy_soa(ssf_handle* h, const SurfelSoA& d, const SurfelSoA& s, size_t n) {      // device -> device, n rows
     if (n == 0) return SSF_OK;
-    hipStream_t st = h->stream;
-    HCK(hipMemcpyAsync(d.pos, s.pos, 12 * n, hipMemcpyDeviceToDevice, st)); HCK(hipMemcpyAsync(d.col, s.col, 12 * n, hipMemcpyDeviceToDevice, st));
-    HCK(hipMemcpyAsync(d.lab, s.lab, 12 * n, hipMemcpyDeviceToDevice, st)); HCK(hipMemcpyAsync(d.stamps, s.stamps, 8 * n, hipMemcpyDeviceToDevice, st));
-    HCK(hipMemcpyAsync(d.r0, s.r0, 12 * n, hipMemcpyDeviceToDevice, st)); HCK(hipMemcpyAsync(d.r1, s.r1, 12 * n, hipMemcpyDeviceToDevice, st));
-    HCK(hipMemcpyAsync(d.r2, s.r2, 12 * n, hipMemcpyDeviceToDevice, st)); HCK(hipMemcpyAsync(d.shape, s.shape, 24 * n, hipMemcpyDeviceToDevice, st));
-    HCK(hipMemcpyAsync(d.dims, s.dims, 8 * n, hipMemcpyDeviceToDevice, st)); HCK(hipMemcpyAsync(d.conf, s.conf, 4 * n, hipMemcpyDeviceToDevice, st));
+    hipError_t copy_of_a_stream = hipSuccess;                   // (the first failure ends the copies)
+    each_stream([&](auto m, size_t w) { if (!copy_of_a_stream) copy_of_a_stream = hipMemcpyAsync(d.*m, s.*m, 4 * w * n, hipMemcpyDeviceToDevice, h->stream); });
+    HCK(copy_of_a_stream);
     return SSF_OK;
 }
 static int oov_home(const ssf_handle* h) { return h->cfg.nb_supersurfels_max + h->S + 256; }   // head after a recentre
@@ -1287,8 +1007,9 @@ static int oov_recentre(ssf_handle* h) {
     h->n_recentres++;
     return SSF_OK;
 }
+namespace ssf {
 // dense [visible | out-of-view] copy of the model in h->dense (stream ordered)
-static int materialise(ssf_handle* h) {
+int materialise(ssf_handle* h) {
     int rc = copy_soa(h, h->dense, h->model[h->mcur], (size_t)h->n_visible);
     if (rc) return rc;
     if (h->oov_live > 0) {
@@ -1299,7 +1020,7 @@ static int materialise(ssf_handle* h) {
     return SSF_OK;
 }
 // the stores <- h->dense (n rows, the first n_visible of them visible); also resets the device counters
-static int store_from_dense(ssf_handle* h, int n, int n_visible) {
+int store_from_dense(ssf_handle* h, int n, int n_visible) {
     h->ahead.valid = false;                       // the model is replaced: a record accumulated ahead is stale
     h->model_gen++;
     int rc = copy_soa(h, h->model[h->mcur], h->dense, (size_t)n_visible);
@@ -1324,7 +1045,8 @@ static int store_from_dense(ssf_handle* h, int n, int n_visible) {
 // actually rewrites its shard depends on the rank (an empty shard, nothing leaving, nothing arriving), but all ranks make
 // the same call sequence, and every rank must enter the next frame in the same state -- a rank that kept the old record
 // would skip an exchange its peers perform (their exchange numbers / the RCCL collective order would go out of step).
-static inline void drop_shard_sizes(ssf_handle* h) { h->all_valid = false; h->all_pending = false; }
+void drop_shard_sizes(ssf_handle* h) { h->all_valid = false; h->all_pending = false; }
+}  // namespace ssf
 
 static inline P2PView p2p_view(ssf_handle* h, unsigned long long seq) { P2PView v = h->p2p.view; v.seq = seq; return v; }
 // exchange != 0 (native multi-rank frame calls with the peer-to-peer backend): the association tables are traded with
@@ -1794,17 +1516,102 @@ static int process_frame_impl(ssf_handle* h, const void* rgb, const void* depth,
     return rc ? rc : process_oldest(h, prior, out);
 }
 
-// device temporaries of one call: freed on every exit path
-struct DevTemps {
-    std::vector<void*> p;
-    template <typename T> hipError_t take(T** out, size_t bytes) {
-        void* q = nullptr;
-        const hipError_t e = hipMalloc(&q, bytes ? bytes : 1);
-        if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
-        return e;
+// ---- what the entry points of ssf_render.hip, ssf_graph.hip and ssf_keyframes.hip share with the ones here (ssf_handle.hpp) ----
+namespace ssf {
+int copy_rows(ssf_handle* h, const ssf_surfels& dst, size_t d0, const ssf_surfels& src, size_t s0, size_t n, hipMemcpyKind kind) {
+    if (n == 0) return SSF_OK;
+    auto one = [&](auto* d, const auto* s, size_t w) { return d ? hipMemcpyAsync(d + w * d0, s + w * s0, 4 * w * n, kind, h->stream) : hipSuccess; };
+    HCK(one(dst.positions, src.positions, 3)); HCK(one(dst.colors, src.colors, 3)); HCK(one(dst.stamps, src.stamps, 2));
+    HCK(one(dst.orientations, src.orientations, 9)); HCK(one(dst.shapes, src.shapes, 6)); HCK(one(dst.dims, src.dims, 2));
+    HCK(one(dst.confidences, src.confidences, 1));
+    return SSF_OK;
+}
+// the six arrays a row set in streams shares with ssf_surfels (its orientations are three streams: transposed where they cross)
+static ssf_surfels soa_surfels(const SurfelSoA& s) { return ssf_surfels{s.pos, s.col, s.stamps, nullptr, s.shape, s.dims, s.conf}; }
+// what ssf_render_model and ssf_graph_build read: both stores of the handle in place (visible_only: without the out-of-view span)
+ModelView model_view(const ssf_handle* h, bool visible_only) {
+    ModelView mv;
+    mv.vis = h->model[h->mcur]; mv.oov = h->oov[h->ocur];
+    mv.n_visible = h->n_visible; mv.nbv = (h->n_visible + 255) / 256; mv.nvs = 256 * mv.nbv;
+    mv.oov_head = h->oov_head; mv.oov_tail = h->oov_tail;
+    mv.nbo = visible_only ? 0 : (h->oov_tail - h->oov_head + 255) / 256;
+    mv.nslots = 256 * (mv.nbv + mv.nbo);
+    return mv;
+}
+// the refusals of the calls that work on the model between frames: frames in flight and, for a call that does not serve a
+// sharded handle (who != nullptr), such a handle: "<who>: a sharded handle (cfg.nranks > 1) <lacks>"
+int model_at_rest(ssf_handle* h, const char* who, const char* lacks) {
+    if (!h->pending.empty() || h->fusing) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
+    if (who && h->cfg.nranks > 1) { h->err = std::string(who) + ": a sharded handle (cfg.nranks > 1) " + lacks; return SSF_ERR_STATE; }
+    return SSF_OK;
+}
+// the iterations of align on device sources (ssf_align: uploaded; ssf_keyframes_align: derived from the stored rows); d_out: 40 i64
+int align_loop(ssf_handle* h, const float* d_pos, const float* d_lab, const float* d_nrm, const float* d_conf, int n, long long* d_out,
+               const float* init_pose, float* rel_pose, int* valid, int* iters, int* pairs_last) {
+    hipStream_t st = h->stream;
+    int rc = SSF_OK;
+    M3 R_init = m3_identity(); V3 t_init = v3(0, 0, 0);
+    if (init_pose) { const Rt p0 = pose_from12(init_pose); R_init = p0.R; t_init = p0.t; }
+    double tf_inc[16], JtJ[36];
+    for (int i = 0; i < 16; i++) tf_inc[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    for (int i = 0; i < 36; i++) JtJ[i] = 0.0;
+    M3 R_inc = m3_identity(); V3 t_inc = v3(0, 0, 0);
+    bool ok = true;
+    int it = 0, pairs = 0;
+    static const int tri[6][6] = {{0, 1, 2, 3, 4, 5}, {1, 6, 7, 8, 9, 10}, {2, 7, 11, 12, 13, 14},
+                                  {3, 8, 12, 15, 16, 17}, {4, 9, 13, 16, 18, 19}, {5, 10, 14, 17, 19, 20}};
+    while (it < h->cfg.icp_iter) {
+        it++;
+        inc_to_float(tf_inc, R_inc, t_inc);
+        Rt T; T.R = m3_mul(R_inc, R_init); T.t = add(m3_mulv(R_inc, t_init), t_inc);
+        launch_align(st, h->cam, d_pos, d_lab, d_nrm, d_conf, n, h->cc->frame, h->cc->maps.label, h->cc->maps.plane_depth, T, d_out);
+        long long rec[40];
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(rec, d_out, 37 * sizeof(long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) { rc = SSF_ERR_DEVICE; h->err = "align iteration failed on the device"; break; }
+        pairs = (int)rec[29];
+        if (pairs < 100) { ok = false; break; }
+        float cs[3], ct[3], scale;
+        for (int i = 0; i < 3; i++) {
+            const uint32_t a = (uint32_t)rec[30 + i], b = (uint32_t)rec[33 + i];
+            std::memcpy(&cs[i], &a, 4); std::memcpy(&ct[i], &b, 4);
+        }
+        { const uint32_t a = (uint32_t)rec[36]; std::memcpy(&scale, &a, 4); }
+        double Jtr[6];
+        for (int i = 0; i < 6; i++) {
+            for (int j = 0; j < 6; j++) JtJ[i * 6 + j] = (double)rec[tri[i][j]] / SSF_ICP_SCALE_JTJ;
+            Jtr[i] = (double)rec[21 + i] / SSF_ICP_SCALE_JTR;
+        }
+        double tf_iter[16];
+        align_increment(JtJ, Jtr, scale, cs, ct, tf_iter);
+        mat4_lmul(tf_iter, tf_inc);
     }
-    ~DevTemps() { for (void* q : p) (void)hipFree(q); }
-};
+    if (rc) return rc;
+    double cov[36];
+    mat6_inverse_lu(JtJ, cov);
+    for (int i = 0; i < 6; i++) if (cov[i * 6 + i] > h->cfg.icp_cov_thresh) { ok = false; break; }
+    Rt rel; rel.R = m3_identity(); rel.t = v3(0, 0, 0);
+    if (ok) {
+        if (len3(t_inc) > 0.3f) ok = false;                      // stale t_inc (start of the last iteration), :226
+        else { rel.R = m3_transpose(R_inc); rel.t = negate(m3_mulv(rel.R, t_inc)); }
+    }
+    pose_to12(rel, rel_pose);
+    *valid = ok ? 1 : 0;
+    if (iters) *iters = it;
+    if (pairs_last) *pairs_last = pairs;
+    if (h->cfg.profile == 1) timer_collect(&h->timer);
+    return SSF_OK;
+}
+// the shared part of ssf_apply_deformation and ssf_graph_apply: k_pack_nodes + k_deformation on the dense logical view (weights are
+// per logical row) with device arrays, then the split back into the two stores
+int deform_dense(ssf_handle* h, int m, const float* d_np, const float* d_nr, const float* d_nt, float* d_nodes, const float* d_w,
+                 const int32_t* d_i) {
+    hipStream_t st = h->stream;
+    { int rc = materialise(h); if (rc) return rc; }
+    { TimerScope ts(h); launch_deformation(st, h->dense, h->n_model, m, d_np, d_nr, d_nt, d_nodes, d_w, d_i); }
+    { int rc = store_from_dense(h, h->n_model, h->n_visible); if (rc) return rc; }
+    return sync_collect(h);
+}
+}  // namespace ssf
 
 // ---- C ABI ----------------------------------------------------------------------------------------------
 // (kernels of ssf_stream_copy_rate, further down)
@@ -1870,9 +1677,7 @@ void ssf_destroy(ssf_handle* h) {
     if (h->capture_stream) stream_pool().give(h->capture_stream, h->cfg.device_id, StreamPool::CAPTURE);
     if (!h->guarded.empty() && !SSF_ENV_SET("GUARD_ONLY")) check_guards(h);
     for (void* p : h->allocs) (void)hipFree(p);
-    h->render.bufs.release();
-    h->graph.bufs.release();
-    h->kf.bufs.release();
+    // (the workspaces -- render, graph, keyframes and any later one -- free their buffers with the handle below: ~DevBufs)
     if (h->mb_host) (void)hipHostFree(h->mb_host);
     for (int i = 0; i < 4; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     for (auto& r : h->timer.pool_free) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -2199,62 +2004,6 @@ int ssf_pipeline_capacity(const ssf_handle* h) { return h ? (int)h->ctx.size() *
 int ssf_can_submit(const ssf_handle* h) { return (h && !h->ctx[h->open_ctx].launched) ? 1 : 0; }
 
 // ---- loop-closure registration + fern codes -------------------------------------
-// the iterations of align on device sources (ssf_align: uploaded; ssf_keyframes_align: derived from the stored rows); d_out: 40 i64
-static int align_loop(ssf_handle* h, const float* d_pos, const float* d_lab, const float* d_nrm, const float* d_conf, int n, long long* d_out,
-                      const float* init_pose, float* rel_pose, int* valid, int* iters, int* pairs_last) {
-    hipStream_t st = h->stream;
-    int rc = SSF_OK;
-    M3 R_init = m3_identity(); V3 t_init = v3(0, 0, 0);
-    if (init_pose) { const Rt p0 = pose_from12(init_pose); R_init = p0.R; t_init = p0.t; }
-    double tf_inc[16], JtJ[36];
-    for (int i = 0; i < 16; i++) tf_inc[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    for (int i = 0; i < 36; i++) JtJ[i] = 0.0;
-    M3 R_inc = m3_identity(); V3 t_inc = v3(0, 0, 0);
-    bool ok = true;
-    int it = 0, pairs = 0;
-    static const int tri[6][6] = {{0, 1, 2, 3, 4, 5}, {1, 6, 7, 8, 9, 10}, {2, 7, 11, 12, 13, 14},
-                                  {3, 8, 12, 15, 16, 17}, {4, 9, 13, 16, 18, 19}, {5, 10, 14, 17, 19, 20}};
-    while (it < h->cfg.icp_iter) {
-        it++;
-        inc_to_float(tf_inc, R_inc, t_inc);
-        Rt T; T.R = m3_mul(R_inc, R_init); T.t = add(m3_mulv(R_inc, t_init), t_inc);
-        launch_align(st, h->cam, d_pos, d_lab, d_nrm, d_conf, n, h->cc->frame, h->cc->maps.label, h->cc->maps.plane_depth, T, d_out);
-        long long rec[40];
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(rec, d_out, 37 * sizeof(long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = SSF_ERR_DEVICE; h->err = "align iteration failed on the device"; break; }
-        pairs = (int)rec[29];
-        if (pairs < 100) { ok = false; break; }
-        float cs[3], ct[3], scale;
-        for (int i = 0; i < 3; i++) {
-            const uint32_t a = (uint32_t)rec[30 + i], b = (uint32_t)rec[33 + i];
-            std::memcpy(&cs[i], &a, 4); std::memcpy(&ct[i], &b, 4);
-        }
-        { const uint32_t a = (uint32_t)rec[36]; std::memcpy(&scale, &a, 4); }
-        double Jtr[6];
-        for (int i = 0; i < 6; i++) {
-            for (int j = 0; j < 6; j++) JtJ[i * 6 + j] = (double)rec[tri[i][j]] / SSF_ICP_SCALE_JTJ;
-            Jtr[i] = (double)rec[21 + i] / SSF_ICP_SCALE_JTR;
-        }
-        double tf_iter[16];
-        align_increment(JtJ, Jtr, scale, cs, ct, tf_iter);
-        mat4_lmul(tf_iter, tf_inc);
-    }
-    if (rc) return rc;
-    double cov[36];
-    mat6_inverse_lu(JtJ, cov);
-    for (int i = 0; i < 6; i++) if (cov[i * 6 + i] > h->cfg.icp_cov_thresh) { ok = false; break; }
-    Rt rel; rel.R = m3_identity(); rel.t = v3(0, 0, 0);
-    if (ok) {
-        if (len3(t_inc) > 0.3f) ok = false;                      // stale t_inc (start of the last iteration), :226
-        else { rel.R = m3_transpose(R_inc); rel.t = negate(m3_mulv(rel.R, t_inc)); }
-    }
-    pose_to12(rel, rel_pose);
-    *valid = ok ? 1 : 0;
-    if (iters) *iters = it;
-    if (pairs_last) *pairs_last = pairs;
-    if (h->cfg.profile == 1) timer_collect(&h->timer);
-    return SSF_OK;
-}
 int ssf_align(ssf_handle* h, const ssf_surfels* src, int n, const float* init_pose, float* rel_pose, int* valid, int* iters,
               int* pairs_last) {
     if (!h || !src || n < 0 || !rel_pose || !valid || !src->positions || !src->colors || !src->orientations) return SSF_ERR_INVALID_ARG;
@@ -2704,12 +2453,8 @@ static int copy_out(ssf_handle* h, const SurfelSoA& s, int first, int count, ssf
     if (count <= 0) return SSF_OK;
     const size_t n = count, f = first;
     hipStream_t st = h->stream;
-    if (o->positions) HCK(hipMemcpyAsync(o->positions, s.pos + 3 * f, 12 * n, hipMemcpyDeviceToHost, st));
-    if (o->colors) HCK(hipMemcpyAsync(o->colors, s.col + 3 * f, 12 * n, hipMemcpyDeviceToHost, st));
-    if (o->stamps) HCK(hipMemcpyAsync(o->stamps, s.stamps + 2 * f, 8 * n, hipMemcpyDeviceToHost, st));
-    if (o->shapes) HCK(hipMemcpyAsync(o->shapes, s.shape + 6 * f, 24 * n, hipMemcpyDeviceToHost, st));
-    if (o->dims) HCK(hipMemcpyAsync(o->dims, s.dims + 2 * f, 8 * n, hipMemcpyDeviceToHost, st));
-    if (o->confidences) HCK(hipMemcpyAsync(o->confidences, s.conf + f, 4 * n, hipMemcpyDeviceToHost, st));
+    ssf_surfels flat = *o; flat.orientations = nullptr;
+    { int rc = copy_rows(h, flat, 0, soa_surfels(s), f, n, hipMemcpyDeviceToHost); if (rc) return rc; }
     std::vector<float> rows;
     if (o->orientations) {
         rows.resize(9 * n);
@@ -2743,12 +2488,7 @@ int ssf_set_model(ssf_handle* h, const ssf_surfels* in, int n, int n_visible, in
         for (size_t i = 0; i < N; i++)
             for (int r = 0; r < 3; r++)
                 for (int c = 0; c < 3; c++) rows[(size_t)r * 3 * N + 3 * i + c] = in->orientations[9 * i + 3 * r + c];
-        HCK(hipMemcpyAsync(s.pos, in->positions, 12 * N, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(s.col, in->colors, 12 * N, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(s.stamps, in->stamps, 8 * N, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(s.shape, in->shapes, 24 * N, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(s.dims, in->dims, 8 * N, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(s.conf, in->confidences, 4 * N, hipMemcpyHostToDevice, st));
+        { int rc = copy_rows(h, soa_surfels(s), 0, *in, 0, N, hipMemcpyHostToDevice); if (rc) return rc; }
         HCK(hipMemcpyAsync(s.r0, rows.data(), 12 * N, hipMemcpyHostToDevice, st));
         HCK(hipMemcpyAsync(s.r1, rows.data() + 3 * N, 12 * N, hipMemcpyHostToDevice, st));
         HCK(hipMemcpyAsync(s.r2, rows.data() + 6 * N, 12 * N, hipMemcpyHostToDevice, st));
@@ -2756,8 +2496,7 @@ int ssf_set_model(ssf_handle* h, const ssf_surfels* in, int n, int n_visible, in
         HCK(hipStreamSynchronize(st));
     }
     h->stamp = stamp;
-    { int rc = store_from_dense(h, n, n_visible); if (rc) return rc; }
-    return SSF_OK;
+    return store_from_dense(h, n, n_visible);
 }
 static int copy_map(ssf_handle* h, void* dst, const void* src, size_t bytes) {
     HCK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
@@ -2792,129 +2531,11 @@ int ssf_get_model_device(ssf_handle* h, ssf_surfels* o, int* n) {
     launch_pack_orient(h->stream, s, h->n_model, h->d_orient9);
     HCK(hipGetLastError());
     HCK(hipStreamSynchronize(h->stream));
-    o->positions = s.pos; o->colors = s.col; o->stamps = s.stamps; o->orientations = h->d_orient9; o->shapes = s.shape;
-    o->dims = s.dims; o->confidences = s.conf;
+    *o = soa_surfels(s); o->orientations = h->d_orient9;
     if (n) *n = h->n_model;
     return SSF_OK;
 }
 
-// ---- the model drawn into a virtual camera (ssf_render.h; kernels in ssf_render.hip) ------------------------------------
-// what ssf_render_model and ssf_graph_build read: both stores of the handle in place (visible_only: without the out-of-view span)
-static ModelView model_view(const ssf_handle* h, bool visible_only) {
-    ModelView mv;
-    mv.vis = h->model[h->mcur]; mv.oov = h->oov[h->ocur];
-    mv.n_visible = h->n_visible; mv.nbv = (h->n_visible + 255) / 256; mv.nvs = 256 * mv.nbv;
-    mv.oov_head = h->oov_head; mv.oov_tail = h->oov_tail;
-    mv.nbo = visible_only ? 0 : (h->oov_tail - h->oov_head + 255) / 256;
-    mv.nslots = 256 * (mv.nbv + mv.nbo);
-    return mv;
-}
-// the refusals of the calls that work on the model between frames: frames in flight and, for a call that does not serve a
-// sharded handle (who != nullptr), such a handle: "<who>: a sharded handle (cfg.nranks > 1) <lacks>"
-static int model_at_rest(ssf_handle* h, const char* who = nullptr, const char* lacks = nullptr) {
-    if (!h->pending.empty() || h->fusing) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
-    if (who && h->cfg.nranks > 1) { h->err = std::string(who) + ": a sharded handle (cfg.nranks > 1) " + lacks; return SSF_ERR_STATE; }
-    return SSF_OK;
-}
-static size_t render_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int ssf_render_default_params(const ssf_handle* h, ssf_render_params* p) {
-    if (!h || !p) return SSF_ERR_INVALID_ARG;
-    std::memset(p, 0, sizeof(*p));
-    p->width = h->cam.W; p->height = h->cam.H; p->fx = h->cam.fx; p->fy = h->cam.fy; p->cx = h->cam.cx; p->cy = h->cam.cy;
-    p->z_min = h->cfg.range_min; p->z_max = h->cfg.range_max; p->min_conf = 0.0f; p->splat_scale = 3.0f;
-    return SSF_OK;
-}
-
-int ssf_render_model(ssf_handle* h, const ssf_render_params* p, float* depth, int32_t* index, uint8_t* rgb8, float* color,
-                     float* normal, ssf_render_stats* stats) {
-    if (!h || !p) return SSF_ERR_INVALID_ARG;
-    if (!depth && !index && !rgb8 && !color && !normal) { h->err = "ssf_render_model: every output is NULL"; return SSF_ERR_INVALID_ARG; }
-    { int rc = model_at_rest(h, "ssf_render_model", "is not rendered"); if (rc) return rc; }
-    RenderCam K;
-    const Rt T = p->pose ? pose_from12(p->pose) : h->pose;
-    const float R9[9] = {T.R.r0.x, T.R.r0.y, T.R.r0.z, T.R.r1.x, T.R.r1.y, T.R.r1.z, T.R.r2.x, T.R.r2.y, T.R.r2.z};
-    std::memcpy(K.R, R9, sizeof(R9)); K.t[0] = T.t.x; K.t[1] = T.t.y; K.t[2] = T.t.z;
-    if (p->width == 0) { K.W = h->cam.W; K.H = h->cam.H; K.fx = h->cam.fx; K.fy = h->cam.fy; K.cx = h->cam.cx; K.cy = h->cam.cy; }
-    else { K.W = p->width; K.H = p->height; K.fx = p->fx; K.fy = p->fy; K.cx = p->cx; K.cy = p->cy; }
-    if (K.W < 1 || K.W > 4096 || K.H < 1 || K.H > 4096) { h->err = "ssf_render_model: the camera size must be 1..4096 x 1..4096"; return SSF_ERR_INVALID_ARG; }
-    if (!std::isfinite(K.fx) || !std::isfinite(K.fy) || K.fx == 0.0f || K.fy == 0.0f) { h->err = "ssf_render_model: fx and fy must be finite and non-zero"; return SSF_ERR_INVALID_ARG; }
-    K.zmin = p->z_min; K.zmax = p->z_max;
-    if (K.zmin == 0.0f && K.zmax == 0.0f) { K.zmin = h->cfg.range_min; K.zmax = h->cfg.range_max; }
-    if (!(K.zmin > 0.0f) || !(K.zmax > K.zmin)) { h->err = "ssf_render_model: the depth range needs 0 < z_min < z_max"; return SSF_ERR_INVALID_ARG; }
-    K.s = p->splat_scale == 0.0f ? 3.0f : p->splat_scale;
-    if (!(K.s >= 0.0f) || !std::isfinite(K.s)) { h->err = "ssf_render_model: splat_scale must be finite and >= 0"; return SSF_ERR_INVALID_ARG; }
-    K.k = K.s * K.s; K.min_conf = p->min_conf;
-    K.ntx = (K.W + 15) / 16; K.nty = (K.H + 15) / 16;
-    const int ntiles = K.ntx * K.nty;
-
-    const RenderView rv{K, model_view(h, p->visible_only != 0)};
-
-    RenderWs& w = h->render;
-    const size_t P = (size_t)K.W * K.H;
-    const size_t img_need = p->on_device ? 0 : (depth ? render_align(4 * P) : 0) + (index ? render_align(4 * P) : 0) +
-                                               (rgb8 ? render_align(3 * P) : 0) + (color ? render_align(12 * P) : 0) + (normal ? render_align(12 * P) : 0);
-    const size_t slots = std::max<size_t>(rv.model.nslots, 256);
-    bool ok = true;
-    if (ok && slots > w.slots) {
-        ok = w.bufs.grow({{(void**)&w.rec, 64 * slots}, {(void**)&w.rbox, 8 * slots}, {(void**)&w.logical, 4 * slots},
-                          {(void**)&w.seen, 4 * slots}, {(void**)&w.bc, 4 * (slots / 256 + 1)}});
-        if (ok) { w.slots = slots; w.epoch = 0; HCK(hipMemsetAsync(w.seen, 0, 4 * slots, h->stream)); }
-    }
-    if (ok && (size_t)ntiles + 1 > w.tiles) {
-        ok = w.bufs.grow({{(void**)&w.tcnt, 4 * ((size_t)ntiles + 1)}, {(void**)&w.cursor, 4 * ((size_t)ntiles + 1)}});
-        if (ok) w.tiles = (size_t)ntiles + 1;
-    }
-    if (ok && !w.stats) ok = w.bufs.grow({{(void**)&w.stats, 4 * sizeof(unsigned long long)}});
-    if (ok && img_need > w.img_bytes) {
-        ok = w.bufs.grow({{(void**)&w.img, img_need}});
-        if (ok) w.img_bytes = img_need;
-    }
-    if (!ok) { h->err = "ssf_render_model: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
-    if (++w.epoch == 0) { HCK(hipMemsetAsync(w.seen, 0, 4 * w.slots, h->stream)); w.epoch = 1; }
-
-    TimerScope ts(h);
-    hipStream_t st = h->stream;
-    HCK(hipMemsetAsync(w.tcnt, 0, 4 * ((size_t)ntiles + 1), st));
-    HCK(hipMemsetAsync(w.stats, 0, 4 * sizeof(unsigned long long), st));
-    launch_render_prep(st, rv, w.bc, w.rec, w.rbox, w.logical, w.tcnt, w.cursor, w.stats + 3);
-    HCK(hipGetLastError());
-    unsigned long long total = 0;
-    HCK(hipMemcpyAsync(&total, w.stats + 3, sizeof(total), hipMemcpyDeviceToHost, st));
-    HCK(hipStreamSynchronize(st));
-    if (total > 0xFFFFFFFFull) { h->err = "ssf_render_model: more than 2^32 - 1 (tile, row) list entries"; return SSF_ERR_DEVICE; }
-    if (total > w.list_cap) {
-        const size_t cap = std::min<unsigned long long>(total + total / 4, 0xFFFFFFFFull);
-        if (!w.bufs.grow({{(void**)&w.list, 4 * cap}})) {
-            h->err = "ssf_render_model: allocation of " + std::to_string(4 * cap) + " bytes for the tile lists failed";
-            return SSF_ERR_DEVICE;
-        }
-        w.list_cap = cap;
-    }
-    if (total > 0) { launch_render_fill(st, rv, w.rbox, w.cursor, w.list); HCK(hipGetLastError()); }
-    RenderOut o{depth, index, rgb8, color, normal};
-    if (!p->on_device) {
-        unsigned char* q = w.img;
-        auto carve = [&](bool want, size_t bytes) { unsigned char* r = want ? q : nullptr; if (want) q += render_align(bytes); return r; };
-        o.depth = (float*)carve(depth != nullptr, 4 * P); o.index = (int32_t*)carve(index != nullptr, 4 * P);
-        o.rgb8 = carve(rgb8 != nullptr, 3 * P); o.color = (float*)carve(color != nullptr, 12 * P); o.normal = (float*)carve(normal != nullptr, 12 * P);
-    }
-    launch_render_tile(st, rv, w.rec, w.rbox, w.logical, w.list, w.tcnt, o, w.seen, w.epoch, w.stats);
-    HCK(hipGetLastError());
-    unsigned long long st3[3] = {0, 0, 0};
-    HCK(hipMemcpyAsync(st3, w.stats, sizeof(st3), hipMemcpyDeviceToHost, st));
-    if (!p->on_device) {
-        if (depth) HCK(hipMemcpyAsync(depth, o.depth, 4 * P, hipMemcpyDeviceToHost, st));
-        if (index) HCK(hipMemcpyAsync(index, o.index, 4 * P, hipMemcpyDeviceToHost, st));
-        if (rgb8) HCK(hipMemcpyAsync(rgb8, o.rgb8, 3 * P, hipMemcpyDeviceToHost, st));
-        if (color) HCK(hipMemcpyAsync(color, o.color, 12 * P, hipMemcpyDeviceToHost, st));
-        if (normal) HCK(hipMemcpyAsync(normal, o.normal, 12 * P, hipMemcpyDeviceToHost, st));
-    }
-    HCK(hipStreamSynchronize(st));
-    if (h->cfg.profile == 1) timer_collect(&h->timer);
-    if (stats) { stats->fragments = (int64_t)st3[0]; stats->pixels_filled = (int64_t)st3[1]; stats->rows_shown = (int64_t)st3[2]; stats->list_entries = (int64_t)total; }
-    return SSF_OK;
-}
 int ssf_get_frame_device(ssf_handle* h, ssf_surfels* o, int* n) {
     if (!h || !o) return SSF_ERR_INVALID_ARG;
     if (!h->cc || !h->cc->frame.pos) { h->err = "no frame has been processed yet"; return SSF_ERR_STATE; }
@@ -2923,8 +2544,7 @@ int ssf_get_frame_device(ssf_handle* h, ssf_surfels* o, int* n) {
     launch_pack_orient(h->stream, s, h->S, h->d_frame_orient9);
     HCK(hipGetLastError());
     HCK(hipStreamSynchronize(h->stream));
-    o->positions = s.pos; o->colors = s.col; o->stamps = s.stamps; o->orientations = h->d_frame_orient9; o->shapes = s.shape;
-    o->dims = s.dims; o->confidences = s.conf;
+    *o = soa_surfels(s); o->orientations = h->d_frame_orient9;
     if (n) *n = h->S;
     return SSF_OK;
 }
@@ -2964,18 +2584,6 @@ int ssf_export_model_txt(ssf_handle* h, const char* path) {
     return SSF_OK;
 }
 
-// the shared part of ssf_apply_deformation and ssf_graph_apply: k_pack_nodes + k_deformation on the dense logical view (weights are
-// per logical row) with device arrays, then the split back into the two stores
-static int deform_dense(ssf_handle* h, int m, const float* d_np, const float* d_nr, const float* d_nt, float* d_nodes, const float* d_w,
-                        const int32_t* d_i) {
-    hipStream_t st = h->stream;
-    { int rc = materialise(h); if (rc) return rc; }
-    { TimerScope ts(h); launch_deformation(st, h->dense, h->n_model, m, d_np, d_nr, d_nt, d_nodes, d_w, d_i); }
-    { int rc = store_from_dense(h, h->n_model, h->n_visible); if (rc) return rc; }
-    HCK(hipStreamSynchronize(st));
-    if (h->cfg.profile == 1) timer_collect(&h->timer);
-    return SSF_OK;
-}
 int ssf_apply_deformation(ssf_handle* h, const float* np, const float* nr, const float* nt, int m, const float* w4, const int32_t* idx4) {
     if (!h || !np || !nr || !nt || !w4 || !idx4 || m <= 0) return SSF_ERR_INVALID_ARG;
     drop_shard_sizes(h);
@@ -2994,463 +2602,6 @@ int ssf_apply_deformation(ssf_handle* h, const float* np, const float* nr, const
     HCK(hipMemcpyAsync(d_w, w4, 16 * n, hipMemcpyHostToDevice, st));
     HCK(hipMemcpyAsync(d_i, idx4, 16 * n, hipMemcpyHostToDevice, st));
     return deform_dense(h, m, d_np, d_nr, d_nt, d_nodes, d_w, d_i);
-}
-
-// ---- the deformation graph's nodes and per-row binding (ssf_graph.h; kernels in ssf_graph.hip) ----------------------------
-int ssf_graph_default_params(ssf_graph_params* p) {
-    if (!p) return SSF_ERR_INVALID_ARG;
-    p->stride = 50; p->look = 20; p->min_conf = 0.0f;
-    return SSF_OK;
-}
-static bool graph_valid(const ssf_handle* h) { return h->graph.built && h->graph.gen == h->model_gen; }
-// the refusals every call that uses the resident graph shares
-static int graph_usable(ssf_handle* h, const char* who) {
-    { int rc = model_at_rest(h, who, "has no deformation graph"); if (rc) return rc; }
-    if (!h->graph.built) { h->err = std::string(who) + ": no graph has been built (ssf_graph_build)"; return SSF_ERR_STATE; }
-    if (!graph_valid(h)) { h->err = std::string(who) + ": graph is stale: build it again"; return SSF_ERR_STATE; }
-    return SSF_OK;
-}
-int ssf_graph_build(ssf_handle* h, const ssf_graph_params* p, int* n_nodes) {
-    if (!h || !p) return SSF_ERR_INVALID_ARG;
-    if (p->stride < 1 || p->look < 3 || !std::isfinite(p->min_conf)) {
-        h->err = "ssf_graph_build: needs stride >= 1, look >= 3 and a finite min_conf"; return SSF_ERR_INVALID_ARG;
-    }
-    { int rc = model_at_rest(h, "ssf_graph_build", "has no deformation graph"); if (rc) return rc; }
-    GraphWs& g = h->graph;
-    g.built = false;                              // whatever happens below, no half-built graph is kept
-    if (h->n_model <= 0) { h->err = "ssf_graph_build: the model is empty"; return SSF_ERR_STATE; }
-
-    const ModelView mv = model_view(h, false);
-    const size_t slots = (size_t)mv.nslots;       // (>= n_model > 0: every row has a slot)
-    if (slots > g.slots) {
-        const size_t nb = (slots + GRAPH_SORT_ITEMS - 1) / GRAPH_SORT_ITEMS;
-        if (!g.bufs.grow({{(void**)&g.stamp, 4 * slots}, {(void**)&g.elig, slots}, {(void**)&g.key_a, 4 * slots}, {(void**)&g.key_b, 4 * slots},
-                          {(void**)&g.slot_a, 4 * slots}, {(void**)&g.slot_b, 4 * slots}, {(void**)&g.cnt, 4 * (256 * nb + 1)},
-                          {(void**)&g.bc, 4 * (slots / 256 + 1)}, {(void**)&g.w4, 16 * slots}, {(void**)&g.idx4, 16 * slots},
-                          {(void**)&g.mm, 4 * sizeof(int)}})) {
-            h->err = "ssf_graph_build: allocation of the working buffers failed"; return SSF_ERR_DEVICE;
-        }
-        g.slots = slots;
-    }
-    TimerScope ts(h);
-    hipStream_t st = h->stream;
-    const int mm0[4] = {INT_MAX, INT_MIN, 0, 0};
-    int mm[4] = {0, 0, 0, 0};
-    HCK(hipMemcpyAsync(g.mm, mm0, sizeof(mm0), hipMemcpyHostToDevice, st));
-    launch_graph_keys(st, mv, p->min_conf, g.stamp, g.elig, g.bc, g.mm);
-    HCK(hipGetLastError());
-    HCK(hipMemcpyAsync(mm, g.mm, sizeof(mm), hipMemcpyDeviceToHost, st));
-    HCK(hipStreamSynchronize(st));
-    if (mm[3] != h->n_model) { h->err = "ssf_graph_build: the stores hold " + std::to_string(mm[3]) + " rows, the handle counts " + std::to_string(h->n_model); return SSF_ERR_DEVICE; }
-    const int n_elig = mm[2];
-    const long long m64 = ((long long)n_elig + p->stride - 1) / p->stride;
-    if (m64 < 5) {
-        h->err = "ssf_graph_build: " + std::to_string(m64) + " nodes (" + std::to_string(n_elig) + " eligible rows, stride " +
-                 std::to_string(p->stride) + "); a graph needs at least 5";
-        if (h->cfg.profile == 1) timer_collect(&h->timer);
-        return SSF_ERR_STATE;
-    }
-    const long long span = (long long)mm[1] - (long long)mm[0];
-    if (span >= SSF_GRAPH_MAX_STAMP_SPAN) {
-        h->err = "ssf_graph_build: the eligible rows' birth stamps span " + std::to_string(span) + " frames; at most " +
-                 std::to_string(SSF_GRAPH_MAX_STAMP_SPAN - 1) + " are sorted";
-        if (h->cfg.profile == 1) timer_collect(&h->timer);
-        return SSF_ERR_STATE;
-    }
-    const int m = (int)m64;
-    if ((size_t)m > g.node_cap) {
-        const size_t cap = (size_t)m + (size_t)m / 4;
-        if (!g.bufs.grow({{(void**)&g.nodes, 16 * cap}, {(void**)&g.npos3, 12 * cap}, {(void**)&g.nrow, 4 * cap}})) {
-            h->err = "ssf_graph_build: allocation of the node table failed"; return SSF_ERR_DEVICE;
-        }
-        g.node_cap = cap;
-    }
-    const int passes = span < 256 ? 1 : span < 65536 ? 2 : 3;
-    const int which = launch_graph_sort(st, mv.nslots, n_elig, mm[0], passes, g.stamp, g.elig, g.cnt, g.key_a, g.slot_a, g.key_b, g.slot_b);
-    HCK(hipGetLastError());
-    launch_graph_sample(st, mv, g.bc, which == 0 ? g.slot_a : g.slot_b, m, p->stride, g.nodes, g.npos3, g.nrow);
-    HCK(hipGetLastError());
-    launch_graph_bind(st, mv, g.bc, g.nodes, m, p->look, g.w4, g.idx4);
-    HCK(hipGetLastError());
-    HCK(hipStreamSynchronize(st));
-    if (h->cfg.profile == 1) timer_collect(&h->timer);
-    g.m = m; g.rows = h->n_model; g.look = p->look; g.gen = h->model_gen; g.built = true;
-    if (n_nodes) *n_nodes = m;
-    return SSF_OK;
-}
-int ssf_graph_info(ssf_handle* h, int* n_nodes, int* n_rows, int* valid) {
-    if (!h) return SSF_ERR_INVALID_ARG;
-    if (n_nodes) *n_nodes = h->graph.built ? h->graph.m : 0;
-    if (n_rows) *n_rows = h->graph.built ? h->graph.rows : 0;
-    if (valid) *valid = graph_valid(h) ? 1 : 0;
-    return SSF_OK;
-}
-int ssf_graph_get_nodes(ssf_handle* h, float* positions, int32_t* t_init, int32_t* rows, int capacity) {
-    if (!h || (!positions && !t_init && !rows)) return SSF_ERR_INVALID_ARG;
-    const GraphWs& g = h->graph;
-    if (!g.built) { h->err = "ssf_graph_get_nodes: no graph has been built (ssf_graph_build)"; return SSF_ERR_STATE; }
-    if (capacity < g.m) { h->err = "ssf_graph_get_nodes: " + std::to_string(g.m) + " nodes, room for " + std::to_string(capacity); return SSF_ERR_CAPACITY; }
-    hipStream_t st = h->stream;
-    const size_t m = g.m;
-    std::vector<float> rec;
-    if (positions) HCK(hipMemcpyAsync(positions, g.npos3, 12 * m, hipMemcpyDeviceToHost, st));
-    if (rows) HCK(hipMemcpyAsync(rows, g.nrow, 4 * m, hipMemcpyDeviceToHost, st));
-    if (t_init) { rec.resize(4 * m); HCK(hipMemcpyAsync(rec.data(), g.nodes, 16 * m, hipMemcpyDeviceToHost, st)); }
-    HCK(hipStreamSynchronize(st));
-    if (t_init) for (size_t k = 0; k < m; k++) std::memcpy(&t_init[k], &rec[4 * k + 3], 4);
-    return SSF_OK;
-}
-int ssf_graph_get_binding(ssf_handle* h, float* weights4, int32_t* idx4, int on_device) {
-    if (!h || (!weights4 && !idx4)) return SSF_ERR_INVALID_ARG;
-    { int rc = graph_usable(h, "ssf_graph_get_binding"); if (rc) return rc; }
-    const GraphWs& g = h->graph;
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (weights4) HCK(hipMemcpyAsync(weights4, g.w4, 16 * (size_t)g.rows, kind, h->stream));
-    if (idx4) HCK(hipMemcpyAsync(idx4, g.idx4, 16 * (size_t)g.rows, kind, h->stream));
-    HCK(hipStreamSynchronize(h->stream));
-    return SSF_OK;
-}
-int ssf_graph_bind_points(ssf_handle* h, const float* points, const int32_t* t_init, int n, float* weights4, int32_t* idx4) {
-    if (!h || !points || !t_init || !weights4 || !idx4 || n < 0) return SSF_ERR_INVALID_ARG;
-    { int rc = graph_usable(h, "ssf_graph_bind_points"); if (rc) return rc; }
-    if (n == 0) return SSF_OK;
-    const GraphWs& g = h->graph;
-    float *d_p, *d_w; int32_t *d_t, *d_i;
-    DevTemps tmp;
-    HCK(tmp.take(&d_p, 12 * (size_t)n)); HCK(tmp.take(&d_t, 4 * (size_t)n)); HCK(tmp.take(&d_w, 16 * (size_t)n)); HCK(tmp.take(&d_i, 16 * (size_t)n));
-    hipStream_t st = h->stream;
-    HCK(hipMemcpyAsync(d_p, points, 12 * (size_t)n, hipMemcpyHostToDevice, st));
-    HCK(hipMemcpyAsync(d_t, t_init, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-    { TimerScope ts(h); launch_graph_bind_points(st, d_p, d_t, n, g.nodes, g.m, g.look, d_w, d_i); }
-    HCK(hipGetLastError());
-    HCK(hipMemcpyAsync(weights4, d_w, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
-    HCK(hipMemcpyAsync(idx4, d_i, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
-    HCK(hipStreamSynchronize(st));
-    if (h->cfg.profile == 1) timer_collect(&h->timer);
-    return SSF_OK;
-}
-int ssf_graph_apply(ssf_handle* h, const float* nr, const float* nt) {
-    if (!h || !nr || !nt) return SSF_ERR_INVALID_ARG;
-    { int rc = graph_usable(h, "ssf_graph_apply"); if (rc) return rc; }
-    drop_shard_sizes(h);
-    h->ahead.valid = false;
-    const GraphWs& g = h->graph;
-    const size_t m = g.m;
-    float *d_nr, *d_nt, *d_nodes;
-    DevTemps tmp;
-    HCK(tmp.take(&d_nr, 36 * m)); HCK(tmp.take(&d_nt, 12 * m)); HCK(tmp.take(&d_nodes, 64 * m));
-    HCK(hipMemcpyAsync(d_nr, nr, 36 * m, hipMemcpyHostToDevice, h->stream));
-    HCK(hipMemcpyAsync(d_nt, nt, 12 * m, hipMemcpyHostToDevice, h->stream));
-    return deform_dense(h, g.m, g.npos3, d_nr, d_nt, d_nodes, g.w4, g.idx4);
-}
-
-// ---- the fern-coded keyframe database (ssf_keyframes.h; kernels in ssf_keyframes.hip) -------------------------------------
-int ssf_keyframes_default_params(ssf_keyframes_params* p) {
-    if (!p) return SSF_ERR_INVALID_ARG;
-    std::memset(p, 0, sizeof(*p));
-    p->cell = 8; p->n_ferns = 500; p->seed = 1234; p->max_keyframes = 256; p->min_gap = 30; p->max_rows = 0;
-    p->new_ratio = 0.3f; p->loop_ratio = 0.2f;
-    return SSF_OK;
-}
-static uint64_t kf_splitmix64(uint64_t& s) {
-    s += 0x9E3779B97F4A7C15ull;
-    uint64_t z = s;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// the refusals the calls share: a sharded handle, no database, a model that is not at rest and (needs_frame: 1 = a current
-// frame, 2 = one with a colour map) no frame to read
-static int kf_usable(ssf_handle* h, const char* who, int needs_frame) {
-    if (h->cfg.nranks > 1) { h->err = std::string(who) + ": a sharded handle (cfg.nranks > 1) keeps no keyframe database"; return SSF_ERR_STATE; }
-    if (!h->kf.on) { h->err = std::string(who) + ": no keyframe database (ssf_keyframes_configure)"; return SSF_ERR_STATE; }
-    if (!h->pending.empty() || h->fusing) { h->err = std::string(who) + ": frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
-    if (needs_frame && !(h->active.ctx && h->active.activated)) { h->err = std::string(who) + ": no frame has been processed yet"; return SSF_ERR_STATE; }
-    if (needs_frame == 2 && !h->active.has_rgba) {
-        h->err = std::string(who) + ": the current frame came in as tables (ssf_submit_frame_tables): it has no colour map"; return SSF_ERR_STATE;
-    }
-    return SSF_OK;
-}
-static void kf_pack_ferns(const std::vector<ssf_fern>& f, std::vector<uint32_t>& out) {
-    out.resize(4 * f.size());
-    for (size_t i = 0; i < f.size(); i++) {
-        out[4 * i] = (uint32_t)f[i].x | ((uint32_t)f[i].y << 16);
-        out[4 * i + 1] = (uint32_t)f[i].r | ((uint32_t)f[i].g << 8) | ((uint32_t)f[i].b << 16);
-        out[4 * i + 2] = f[i].depth_mm; out[4 * i + 3] = 0;
-    }
-}
-static int kf_upload_ferns(ssf_handle* h) {
-    std::vector<uint32_t> w;
-    kf_pack_ferns(h->kf.host_ferns, w);
-    HCK(hipMemcpyAsync(h->kf.ferns, w.data(), 4 * w.size(), hipMemcpyHostToDevice, h->stream));
-    HCK(hipStreamSynchronize(h->stream));
-    return SSF_OK;
-}
-int ssf_keyframes_configure(ssf_handle* h, const ssf_keyframes_params* p) {
-    if (!h || !p) return SSF_ERR_INVALID_ARG;
-    const int W = h->cfg.width, H = h->cfg.height;
-    if ((p->cell != 4 && p->cell != 8 && p->cell != 16) || W < p->cell || H < p->cell || p->n_ferns < 1 || p->n_ferns > SSF_KEYFRAMES_MAX_FERNS ||
-        p->max_keyframes < 1 || p->min_gap < 0 || p->max_rows < 0 || !std::isfinite(p->new_ratio) || !std::isfinite(p->loop_ratio)) {
-        h->err = "ssf_keyframes_configure: needs cell 4 / 8 / 16 (<= the image), 1 .. 4096 ferns, max_keyframes >= 1, min_gap >= 0, max_rows >= 0 and finite ratios";
-        return SSF_ERR_INVALID_ARG;
-    }
-    // the depth range in mm: the sum of a cell's 256 depths must fit 31 bits
-    if (!(h->cfg.range_min >= 0.0f) || !(h->cfg.range_max <= 8000.0f) || !(lrintf(h->cfg.range_max * 1000.0f) > lrintf(h->cfg.range_min * 1000.0f))) {
-        h->err = "ssf_keyframes_configure: needs 0 <= range_min < range_max <= 8000 m (whole millimetres apart)"; return SSF_ERR_INVALID_ARG;
-    }
-    if (h->cfg.nranks > 1) { h->err = "ssf_keyframes_configure: a sharded handle (cfg.nranks > 1) keeps no keyframe database"; return SSF_ERR_STATE; }
-    KeyframeWs& k = h->kf;
-    if (k.on) { h->err = "ssf_keyframes_configure: a database is live (ssf_keyframes_clear first)"; return SSF_ERR_STATE; }
-    const size_t words = (((size_t)p->n_ferns + 7) / 8 + 63) / 64 * 64, K = (size_t)p->max_keyframes;
-    const size_t rows = p->max_rows > 0 ? (size_t)p->max_rows : K * (size_t)h->S;
-    if (!k.bufs.grow({{(void**)&k.ferns, 16 * (size_t)p->n_ferns}, {(void**)&k.q, 4 * words}, {(void**)&k.table, 4 * words * K},
-                      {(void**)&k.stamps, 4 * K}, {(void**)&k.diff, 4 * K}, {(void**)&k.rec, 4 * SSF_KF_REC_WORDS},
-                      {(void**)&k.bytes, (size_t)SSF_KEYFRAMES_MAX_FERNS},
-                      {(void**)&k.pool.pos, 12 * rows}, {(void**)&k.pool.col, 12 * rows}, {(void**)&k.pool.stamps, 8 * rows},
-                      {(void**)&k.pool.orient, 36 * rows}, {(void**)&k.pool.shape, 24 * rows}, {(void**)&k.pool.dims, 8 * rows},
-                      {(void**)&k.pool.conf, 4 * rows}})) {
-        k.bufs.release();
-        h->err = "ssf_keyframes_configure: allocation of the database failed"; return SSF_ERR_DEVICE;
-    }
-    k.p = *p; k.p.max_rows = (int64_t)rows;
-    k.words = (int)words; k.gw = W / p->cell; k.gh = H / p->cell;
-    k.kfs.clear(); k.rows_used = 0;
-    const uint32_t dlo = (uint32_t)lrintf(h->cfg.range_min * 1000.0f), dhi = (uint32_t)lrintf(h->cfg.range_max * 1000.0f);
-    k.host_ferns.assign((size_t)p->n_ferns, ssf_fern());
-    uint64_t s = p->seed;
-    for (auto& f : k.host_ferns) {
-        f.x = (uint16_t)(kf_splitmix64(s) % (uint64_t)k.gw); f.y = (uint16_t)(kf_splitmix64(s) % (uint64_t)k.gh);
-        f.r = (uint8_t)(kf_splitmix64(s) % 256u); f.g = (uint8_t)(kf_splitmix64(s) % 256u); f.b = (uint8_t)(kf_splitmix64(s) % 256u);
-        f.pad = 0; f.depth_mm = dlo + (uint32_t)(kf_splitmix64(s) % (uint64_t)(dhi - dlo));
-    }
-    { int rc = kf_upload_ferns(h); if (rc) { k.bufs.release(); return rc; } }
-    k.on = true;
-    return SSF_OK;
-}
-int ssf_keyframes_clear(ssf_handle* h) {
-    if (!h) return SSF_ERR_INVALID_ARG;
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    KeyframeWs& k = h->kf;
-    k.bufs.release();
-    k.on = false; k.kfs.clear(); k.host_ferns.clear(); k.rows_used = 0; k.words = 0;
-    return SSF_OK;
-}
-int ssf_keyframes_info(ssf_handle* h, int* configured, int* n_keyframes, int64_t* rows_used, ssf_keyframes_params* p) {
-    if (!h) return SSF_ERR_INVALID_ARG;
-    const KeyframeWs& k = h->kf;
-    if (configured) *configured = k.on ? 1 : 0;
-    if (n_keyframes) *n_keyframes = k.on ? (int)k.kfs.size() : 0;
-    if (rows_used) *rows_used = k.on ? (int64_t)k.rows_used : 0;
-    if (p) { if (k.on) *p = k.p; else std::memset(p, 0, sizeof(*p)); }
-    return SSF_OK;
-}
-int ssf_keyframes_set_ferns(ssf_handle* h, const ssf_fern* ferns, int n) {
-    if (!h || !ferns) return SSF_ERR_INVALID_ARG;
-    { int rc = kf_usable(h, "ssf_keyframes_set_ferns", 0); if (rc) return rc; }
-    KeyframeWs& k = h->kf;
-    if (n != k.p.n_ferns) { h->err = "ssf_keyframes_set_ferns: the database is configured for " + std::to_string(k.p.n_ferns) + " ferns"; return SSF_ERR_INVALID_ARG; }
-    if (!k.kfs.empty()) { h->err = "ssf_keyframes_set_ferns: keyframes are stored under the present table"; return SSF_ERR_STATE; }
-    for (int i = 0; i < n; i++)
-        if ((int)ferns[i].x >= k.gw || (int)ferns[i].y >= k.gh) {
-            h->err = "ssf_keyframes_set_ferns: fern " + std::to_string(i) + " names a cell outside the " + std::to_string(k.gw) + " x " + std::to_string(k.gh) + " grid";
-            return SSF_ERR_INVALID_ARG;
-        }
-    k.host_ferns.assign(ferns, ferns + n);
-    for (auto& f : k.host_ferns) f.pad = 0;
-    return kf_upload_ferns(h);
-}
-int ssf_keyframes_get_ferns(ssf_handle* h, ssf_fern* ferns, int capacity) {
-    if (!h || !ferns) return SSF_ERR_INVALID_ARG;
-    { int rc = kf_usable(h, "ssf_keyframes_get_ferns", 0); if (rc) return rc; }
-    const KeyframeWs& k = h->kf;
-    if (capacity < k.p.n_ferns) { h->err = "ssf_keyframes_get_ferns: " + std::to_string(k.p.n_ferns) + " ferns, room for " + std::to_string(capacity); return SSF_ERR_CAPACITY; }
-    std::memcpy(ferns, k.host_ferns.data(), sizeof(ssf_fern) * k.host_ferns.size());
-    return SSF_OK;
-}
-// the current frame's packed codes into kf.q (enqueued only)
-static void kf_encode_current(ssf_handle* h) {
-    const KeyframeWs& k = h->kf;
-    launch_kf_encode(h->stream, h->cc->maps.rgba, h->cc->maps.plane_depth, h->cfg.width, k.p.cell, h->cfg.range_min, h->cfg.range_max,
-                     k.ferns, k.p.n_ferns, k.words, k.q);
-}
-// n code bytes -> the packed words; false: a code > 15
-static bool kf_pack_codes(const uint8_t* codes, int n, int words, std::vector<uint32_t>& out) {
-    out.assign((size_t)words, 0u);
-    for (int i = 0; i < n; i++) {
-        if (codes[i] > 15) return false;
-        out[i >> 3] |= (uint32_t)codes[i] << (4 * (i & 7));
-    }
-    return true;
-}
-// search + select (+ the add) of kf.q; rec: SSF_KF_REC_WORDS words.  The host takes the keyframe the device added into its mirror
-static int kf_run(ssf_handle* h, const char* who, int mode, int kmax, int stamp, int min_gap, bool with_frame, int32_t* rec) {
-    KeyframeWs& k = h->kf;
-    hipStream_t st = h->stream;
-    KfQuery q;
-    q.words = k.words; q.n = k.p.n_ferns; q.K = (int)k.kfs.size(); q.max_keyframes = k.p.max_keyframes; q.mode = mode; q.kmax = kmax;
-    q.stamp = stamp; q.min_gap = min_gap; q.rows_used = k.rows_used; q.max_rows = (long long)k.p.max_rows;
-    q.new_ratio = k.p.new_ratio; q.loop_ratio = k.p.loop_ratio;
-    launch_kf_search(st, k.q, k.table, k.words, q.K, k.diff);
-    HCK(hipGetLastError());
-    SurfelSoA none; std::memset(&none, 0, sizeof(none));
-    launch_kf_select(st, q, k.q, k.table, k.stamps, k.diff, with_frame ? h->cc->frame : none, with_frame ? h->S : 0, k.pool, k.rec);
-    HCK(hipGetLastError());
-    HCK(hipMemcpyAsync(rec, k.rec, 4 * SSF_KF_REC_WORDS, hipMemcpyDeviceToHost, st));
-    HCK(hipStreamSynchronize(st));
-    if (h->cfg.profile == 1) timer_collect(&h->timer);
-    const bool added = rec[0] != 0;
-    // the decision was taken on the device; the host checks what it can from the record
-    if (rec[4] != q.K + (added ? 1 : 0) || (added && (rec[1] != q.K || mode == 0 || rec[38] < 0 || k.rows_used + rec[38] > (long long)k.p.max_rows)) ||
-        rec[5] < 0 || rec[5] > kmax) {
-        h->err = std::string(who) + ": the device's record contradicts the host's view of the database"; return SSF_ERR_DEVICE;
-    }
-    if (added) {
-        KeyframeMeta m; m.first = k.rows_used; m.rows = rec[38]; m.stamp = stamp; pose_to12(h->pose, m.pose);
-        k.kfs.push_back(m); k.rows_used += m.rows;
-    }
-    return SSF_OK;
-}
-int ssf_keyframes_encode(ssf_handle* h, uint8_t* codes, int capacity) {
-    if (!h || !codes) return SSF_ERR_INVALID_ARG;
-    { int rc = kf_usable(h, "ssf_keyframes_encode", 2); if (rc) return rc; }
-    KeyframeWs& k = h->kf;
-    if (capacity < k.p.n_ferns) { h->err = "ssf_keyframes_encode: " + std::to_string(k.p.n_ferns) + " codes, room for " + std::to_string(capacity); return SSF_ERR_CAPACITY; }
-    { TimerScope ts(h); kf_encode_current(h); }
-    HCK(hipGetLastError());
-    launch_kf_unpack(h->stream, k.q, k.p.n_ferns, k.bytes);
-    HCK(hipGetLastError());
-    HCK(hipMemcpyAsync(codes, k.bytes, (size_t)k.p.n_ferns, hipMemcpyDeviceToHost, h->stream));
-    HCK(hipStreamSynchronize(h->stream));
-    if (h->cfg.profile == 1) timer_collect(&h->timer);
-    return SSF_OK;
-}
-int ssf_keyframes_query(ssf_handle* h, const uint8_t* codes, int stamp, int min_gap, int kmax, ssf_keyframe_result* out) {
-    if (!h || !out || kmax < 0 || kmax > SSF_KEYFRAMES_MAX_CANDIDATES) return SSF_ERR_INVALID_ARG;
-    { int rc = kf_usable(h, "ssf_keyframes_query", codes ? 0 : 2); if (rc) return rc; }
-    KeyframeWs& k = h->kf;
-    std::vector<uint32_t> packed;
-    TimerScope ts(h);
-    if (codes) {
-        if (!kf_pack_codes(codes, k.p.n_ferns, k.words, packed)) { h->err = "ssf_keyframes_query: a code is a value 0 .. 15"; return SSF_ERR_INVALID_ARG; }
-        HCK(hipMemcpyAsync(k.q, packed.data(), 4 * packed.size(), hipMemcpyHostToDevice, h->stream));
-    } else {
-        kf_encode_current(h);
-        HCK(hipGetLastError());
-        stamp = h->stamp;
-    }
-    int32_t rec[SSF_KF_REC_WORDS];
-    { int rc = kf_run(h, "ssf_keyframes_query", 0, kmax, stamp, min_gap < 0 ? k.p.min_gap : min_gap, false, rec); if (rc) return rc; }
-    std::memcpy(out, rec, sizeof(*out));
-    return SSF_OK;
-}
-int ssf_keyframes_consider(ssf_handle* h, ssf_keyframe_result* out) {
-    if (!h || !out) return SSF_ERR_INVALID_ARG;
-    { int rc = kf_usable(h, "ssf_keyframes_consider", 2); if (rc) return rc; }
-    TimerScope ts(h);
-    kf_encode_current(h);
-    HCK(hipGetLastError());
-    int32_t rec[SSF_KF_REC_WORDS];
-    { int rc = kf_run(h, "ssf_keyframes_consider", 1, SSF_KEYFRAMES_MAX_CANDIDATES, h->stamp, h->kf.p.min_gap, true, rec); if (rc) return rc; }
-    std::memcpy(out, rec, sizeof(*out));
-    return SSF_OK;
-}
-int ssf_keyframes_add(ssf_handle* h, int* id) {
-    if (!h) return SSF_ERR_INVALID_ARG;
-    { int rc = kf_usable(h, "ssf_keyframes_add", 2); if (rc) return rc; }
-    TimerScope ts(h);
-    kf_encode_current(h);
-    HCK(hipGetLastError());
-    int32_t rec[SSF_KF_REC_WORDS];
-    { int rc = kf_run(h, "ssf_keyframes_add", 2, 0, h->stamp, h->kf.p.min_gap, true, rec); if (rc) return rc; }
-    if (!rec[0]) { h->err = "ssf_keyframes_add: the store is full"; return SSF_ERR_CAPACITY; }
-    if (id) *id = rec[1];
-    return SSF_OK;
-}
-int ssf_keyframes_put(ssf_handle* h, const uint8_t* codes, const ssf_surfels* rows, int n_rows, const float* pose, int stamp, int* id) {
-    if (!h || !codes || !pose || n_rows < 0 || (n_rows > 0 && (!rows || !rows->positions || !rows->colors || !rows->stamps || !rows->orientations ||
-                                                              !rows->shapes || !rows->dims || !rows->confidences))) return SSF_ERR_INVALID_ARG;
-    { int rc = kf_usable(h, "ssf_keyframes_put", 0); if (rc) return rc; }
-    KeyframeWs& k = h->kf;
-    const size_t K = k.kfs.size(), n = (size_t)n_rows, o = (size_t)k.rows_used;
-    if ((int)K >= k.p.max_keyframes || k.rows_used + n_rows > (long long)k.p.max_rows) { h->err = "ssf_keyframes_put: the store is full"; return SSF_ERR_CAPACITY; }
-    std::vector<uint32_t> packed;
-    if (!kf_pack_codes(codes, k.p.n_ferns, k.words, packed)) { h->err = "ssf_keyframes_put: a code is a value 0 .. 15"; return SSF_ERR_INVALID_ARG; }
-    hipStream_t st = h->stream;
-    const int32_t stamp32 = stamp;
-    HCK(hipMemcpyAsync(k.table + K * (size_t)k.words, packed.data(), 4 * packed.size(), hipMemcpyHostToDevice, st));
-    HCK(hipMemcpyAsync(k.stamps + K, &stamp32, 4, hipMemcpyHostToDevice, st));
-    if (n > 0) {
-        HCK(hipMemcpyAsync(k.pool.pos + 3 * o, rows->positions, 12 * n, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(k.pool.col + 3 * o, rows->colors, 12 * n, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(k.pool.stamps + 2 * o, rows->stamps, 8 * n, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(k.pool.orient + 9 * o, rows->orientations, 36 * n, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(k.pool.shape + 6 * o, rows->shapes, 24 * n, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(k.pool.dims + 2 * o, rows->dims, 8 * n, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(k.pool.conf + o, rows->confidences, 4 * n, hipMemcpyHostToDevice, st));
-    }
-    HCK(hipStreamSynchronize(st));
-    KeyframeMeta m; m.first = k.rows_used; m.rows = n_rows; m.stamp = stamp; std::memcpy(m.pose, pose, sizeof(m.pose));
-    k.kfs.push_back(m); k.rows_used += n_rows;
-    if (id) *id = (int)K;
-    return SSF_OK;
-}
-static int kf_lookup(ssf_handle* h, const char* who, int id) {
-    if (id < 0 || (size_t)id >= h->kf.kfs.size()) {
-        h->err = std::string(who) + ": no keyframe " + std::to_string(id) + " (" + std::to_string(h->kf.kfs.size()) + " stored)"; return SSF_ERR_INVALID_ARG;
-    }
-    return SSF_OK;
-}
-int ssf_keyframes_get(ssf_handle* h, int id, ssf_surfels* rows, int capacity, int* n_rows, float* pose, int* stamp, uint8_t* codes) {
-    if (!h) return SSF_ERR_INVALID_ARG;
-    { int rc = kf_usable(h, "ssf_keyframes_get", 0); if (rc) return rc; }
-    { int rc = kf_lookup(h, "ssf_keyframes_get", id); if (rc) return rc; }
-    KeyframeWs& k = h->kf;
-    const KeyframeMeta& m = k.kfs[(size_t)id];
-    if (rows && capacity < m.rows) { h->err = "ssf_keyframes_get: " + std::to_string(m.rows) + " rows, room for " + std::to_string(capacity); return SSF_ERR_CAPACITY; }
-    hipStream_t st = h->stream;
-    const size_t n = (size_t)m.rows, o = (size_t)m.first;
-    if (rows && n > 0) {
-        if (rows->positions) HCK(hipMemcpyAsync(rows->positions, k.pool.pos + 3 * o, 12 * n, hipMemcpyDeviceToHost, st));
-        if (rows->colors) HCK(hipMemcpyAsync(rows->colors, k.pool.col + 3 * o, 12 * n, hipMemcpyDeviceToHost, st));
-        if (rows->stamps) HCK(hipMemcpyAsync(rows->stamps, k.pool.stamps + 2 * o, 8 * n, hipMemcpyDeviceToHost, st));
-        if (rows->orientations) HCK(hipMemcpyAsync(rows->orientations, k.pool.orient + 9 * o, 36 * n, hipMemcpyDeviceToHost, st));
-        if (rows->shapes) HCK(hipMemcpyAsync(rows->shapes, k.pool.shape + 6 * o, 24 * n, hipMemcpyDeviceToHost, st));
-        if (rows->dims) HCK(hipMemcpyAsync(rows->dims, k.pool.dims + 2 * o, 8 * n, hipMemcpyDeviceToHost, st));
-        if (rows->confidences) HCK(hipMemcpyAsync(rows->confidences, k.pool.conf + o, 4 * n, hipMemcpyDeviceToHost, st));
-    }
-    if (codes) {
-        launch_kf_unpack(st, k.table + (size_t)id * k.words, k.p.n_ferns, k.bytes);
-        HCK(hipGetLastError());
-        HCK(hipMemcpyAsync(codes, k.bytes, (size_t)k.p.n_ferns, hipMemcpyDeviceToHost, st));
-    }
-    HCK(hipStreamSynchronize(st));
-    if (n_rows) *n_rows = m.rows;
-    if (pose) std::memcpy(pose, m.pose, sizeof(m.pose));
-    if (stamp) *stamp = m.stamp;
-    return SSF_OK;
-}
-int ssf_keyframes_set_pose(ssf_handle* h, int id, const float* pose) {
-    if (!h || !pose) return SSF_ERR_INVALID_ARG;
-    { int rc = kf_usable(h, "ssf_keyframes_set_pose", 0); if (rc) return rc; }
-    { int rc = kf_lookup(h, "ssf_keyframes_set_pose", id); if (rc) return rc; }
-    std::memcpy(h->kf.kfs[(size_t)id].pose, pose, 12 * sizeof(float));
-    return SSF_OK;
-}
-int ssf_keyframes_align(ssf_handle* h, int id, const float* init_pose, int use_conf, float* rel_pose, int* valid, int* iters, int* pairs_last) {
-    if (!h || !rel_pose || !valid) return SSF_ERR_INVALID_ARG;
-    { int rc = kf_usable(h, "ssf_keyframes_align", 1); if (rc) return rc; }
-    { int rc = kf_lookup(h, "ssf_keyframes_align", id); if (rc) return rc; }
-    const KeyframeWs& k = h->kf;
-    const KeyframeMeta& m = k.kfs[(size_t)id];
-    const size_t N = (size_t)std::max(m.rows, 1), o = (size_t)m.first;
-    float *d_lab = nullptr, *d_nrm = nullptr; long long* d_out = nullptr;
-    DevTemps tmp;
-    HCK(tmp.take(&d_lab, 12 * N)); HCK(tmp.take(&d_nrm, 12 * N)); HCK(tmp.take(&d_out, 40 * sizeof(long long)));
-    TimerScope ts(h);
-    launch_kf_align_prep(h->stream, k.pool.col + 3 * o, k.pool.orient + 9 * o, m.rows, d_lab, d_nrm);
-    HCK(hipGetLastError());
-    return align_loop(h, k.pool.pos + 3 * o, d_lab, d_nrm, use_conf ? k.pool.conf + o : nullptr, m.rows, d_out, init_pose, rel_pose, valid, iters,
-                      pairs_last);
 }
 
 // ---- re-homing of a sharded map (see ssf.h): rows moved by ssf_apply_deformation go to the rank that owns their tile ----

@@ -17,8 +17,13 @@
 //   * align   k_kf_align_prep: stored rows -> Lab and normals for k_align (positions and confidences are read in place).
 // Every count is an integer; there is no atomic in this file.
 #include "ssf_slots.hpp"
+#include "ssf_handle.hpp"
 
 namespace ssf {
+
+#define SSF_KF_REC_WORDS 40                       // ssf_keyframe_result (38 words), the rows stored, one spare
+// one query: n ferns in `words` packed words, K stored keyframes; mode 0 query, 1 consider, 2 add (see k_kf_select)
+struct KfQuery { int words, n, K, max_keyframes, mode, kmax, stamp, min_gap; long long rows_used, max_rows; float new_ratio, loop_ratio; };
 
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
@@ -104,7 +109,7 @@ struct KfSelect {
     long long rows_used, max_rows;
     float new_ratio, loop_ratio;
     SurfelSoA frame; int S;
-    KfPool pool;
+    ssf_surfels pool;                             // device arrays: a keyframe's rows are consecutive, in ssf_surfels' layout
     int32_t* rec;
 };
 __global__ __launch_bounds__(1024) void k_kf_select(KfSelect a) {
@@ -176,15 +181,15 @@ __global__ __launch_bounds__(1024) void k_kf_select(KfSelect a) {
             const SurfelSoA& f = a.frame;
 #pragma unroll
             for (int c = 0; c < 3; c++) {
-                a.pool.pos[3 * o + c] = f.pos[3 * r + c]; a.pool.col[3 * o + c] = f.col[3 * r + c];
-                a.pool.orient[9 * o + c] = f.r0[3 * r + c]; a.pool.orient[9 * o + 3 + c] = f.r1[3 * r + c];
-                a.pool.orient[9 * o + 6 + c] = f.r2[3 * r + c];
+                a.pool.positions[3 * o + c] = f.pos[3 * r + c]; a.pool.colors[3 * o + c] = f.col[3 * r + c];
+                a.pool.orientations[9 * o + c] = f.r0[3 * r + c]; a.pool.orientations[9 * o + 3 + c] = f.r1[3 * r + c];
+                a.pool.orientations[9 * o + 6 + c] = f.r2[3 * r + c];
             }
 #pragma unroll
-            for (int c = 0; c < 6; c++) a.pool.shape[6 * o + c] = f.shape[6 * r + c];
+            for (int c = 0; c < 6; c++) a.pool.shapes[6 * o + c] = f.shape[6 * r + c];
             a.pool.stamps[2 * o] = f.stamps[2 * r]; a.pool.stamps[2 * o + 1] = f.stamps[2 * r + 1];
             a.pool.dims[2 * o] = f.dims[2 * r]; a.pool.dims[2 * o + 1] = f.dims[2 * r + 1];
-            a.pool.conf[o] = f.conf[r];
+            a.pool.confidences[o] = f.conf[r];
         }
         base += all;
     }
@@ -202,21 +207,22 @@ __global__ __launch_bounds__(256) void k_kf_align_prep(const float* __restrict__
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------
-void launch_kf_encode(hipStream_t st, const uint32_t* rgba, const float* plane_depth, int W, int B, float zmin, float zmax,
-                      const uint4* ferns, int n, int words, uint32_t* codes) {
+// ferns[i] = (x | y << 16, r | g << 8 | b << 16, depth_mm, 0); codes: `words` packed words of the frame (rgba, plane_depth)
+static void launch_kf_encode(hipStream_t st, const uint32_t* rgba, const float* plane_depth, int W, int B, float zmin, float zmax,
+                             const uint4* ferns, int n, int words, uint32_t* codes) {
     ScopedKernel sk("kf_encode", st);
     hipLaunchKernelGGL(k_kf_encode, dim3(words), dim3(512), 0, st, rgba, plane_depth, W, B, zmin, zmax, ferns, n, codes);
 }
-void launch_kf_unpack(hipStream_t st, const uint32_t* codes, int n, uint8_t* out) {
+static void launch_kf_unpack(hipStream_t st, const uint32_t* codes, int n, uint8_t* out) {
     hipLaunchKernelGGL(k_kf_unpack, dim3((n + 255) / 256), dim3(256), 0, st, codes, n, out);
 }
-void launch_kf_search(hipStream_t st, const uint32_t* q, const uint32_t* table, int words, int K, uint32_t* diff) {
+static void launch_kf_search(hipStream_t st, const uint32_t* q, const uint32_t* table, int words, int K, uint32_t* diff) {
     if (K <= 0) return;
     ScopedKernel sk("kf_search", st);
     hipLaunchKernelGGL(k_kf_search, dim3((K + 3) / 4), dim3(256), 0, st, q, table, words, K, diff);
 }
-void launch_kf_select(hipStream_t st, const KfQuery& qy, const uint32_t* q, uint32_t* table, int32_t* stamps, const uint32_t* diff,
-                      const SurfelSoA& frame, int S, const KfPool& pool, int32_t* rec) {
+static void launch_kf_select(hipStream_t st, const KfQuery& qy, const uint32_t* q, uint32_t* table, int32_t* stamps, const uint32_t* diff,
+                             const SurfelSoA& frame, int S, const ssf_surfels& pool, int32_t* rec) {
     ScopedKernel sk("kf_select", st);
     KfSelect a;
     a.q = q; a.table = table; a.stamps = stamps; a.diff = diff;
@@ -225,10 +231,303 @@ void launch_kf_select(hipStream_t st, const KfQuery& qy, const uint32_t* q, uint
     a.new_ratio = qy.new_ratio; a.loop_ratio = qy.loop_ratio; a.frame = frame; a.S = S; a.pool = pool; a.rec = rec;
     hipLaunchKernelGGL(k_kf_select, dim3(1), dim3(1024), 0, st, a);
 }
-void launch_kf_align_prep(hipStream_t st, const float* col, const float* orient, int n, float* lab, float* nrm) {
+static void launch_kf_align_prep(hipStream_t st, const float* col, const float* orient, int n, float* lab, float* nrm) {
     if (n <= 0) return;
     ScopedKernel sk("kf_align_prep", st);
     hipLaunchKernelGGL(k_kf_align_prep, dim3((n + 255) / 256), dim3(256), 0, st, col, orient, n, lab, nrm);
 }
 
 }  // namespace ssf
+
+// ---- host: the entry points of include/ssf_keyframes.h ---------------------------------------------------------------------
+extern "C" {
+int ssf_keyframes_default_params(ssf_keyframes_params* p) {
+    if (!p) return SSF_ERR_INVALID_ARG;
+    std::memset(p, 0, sizeof(*p));
+    p->cell = 8; p->n_ferns = 500; p->seed = 1234; p->max_keyframes = 256; p->min_gap = 30; p->max_rows = 0;
+    p->new_ratio = 0.3f; p->loop_ratio = 0.2f;
+    return SSF_OK;
+}
+static uint64_t kf_splitmix64(uint64_t& s) {
+    s += 0x9E3779B97F4A7C15ull;
+    uint64_t z = s;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// the refusals the calls share: a sharded handle, no database, a model that is not at rest and (needs_frame: 1 = a current
+// frame, 2 = one with a colour map) no frame to read
+static int kf_usable(ssf_handle* h, const char* who, int needs_frame) {
+    if (h->cfg.nranks > 1) { h->err = std::string(who) + ": a sharded handle (cfg.nranks > 1) keeps no keyframe database"; return SSF_ERR_STATE; }
+    if (!h->kf.on) { h->err = std::string(who) + ": no keyframe database (ssf_keyframes_configure)"; return SSF_ERR_STATE; }
+    if (!h->pending.empty() || h->fusing) { h->err = std::string(who) + ": frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
+    if (needs_frame && !(h->active.ctx && h->active.activated)) { h->err = std::string(who) + ": no frame has been processed yet"; return SSF_ERR_STATE; }
+    if (needs_frame == 2 && !h->active.has_rgba) {
+        h->err = std::string(who) + ": the current frame came in as tables (ssf_submit_frame_tables): it has no colour map"; return SSF_ERR_STATE;
+    }
+    return SSF_OK;
+}
+static void kf_pack_ferns(const std::vector<ssf_fern>& f, std::vector<uint32_t>& out) {
+    out.resize(4 * f.size());
+    for (size_t i = 0; i < f.size(); i++) {
+        out[4 * i] = (uint32_t)f[i].x | ((uint32_t)f[i].y << 16);
+        out[4 * i + 1] = (uint32_t)f[i].r | ((uint32_t)f[i].g << 8) | ((uint32_t)f[i].b << 16);
+        out[4 * i + 2] = f[i].depth_mm; out[4 * i + 3] = 0;
+    }
+}
+static int kf_upload_ferns(ssf_handle* h) {
+    std::vector<uint32_t> w;
+    kf_pack_ferns(h->kf.host_ferns, w);
+    HCK(hipMemcpyAsync(h->kf.ferns, w.data(), 4 * w.size(), hipMemcpyHostToDevice, h->stream));
+    HCK(hipStreamSynchronize(h->stream));
+    return SSF_OK;
+}
+int ssf_keyframes_configure(ssf_handle* h, const ssf_keyframes_params* p) {
+    if (!h || !p) return SSF_ERR_INVALID_ARG;
+    const int W = h->cfg.width, H = h->cfg.height;
+    if ((p->cell != 4 && p->cell != 8 && p->cell != 16) || W < p->cell || H < p->cell || p->n_ferns < 1 || p->n_ferns > SSF_KEYFRAMES_MAX_FERNS ||
+        p->max_keyframes < 1 || p->min_gap < 0 || p->max_rows < 0 || !std::isfinite(p->new_ratio) || !std::isfinite(p->loop_ratio)) {
+        h->err = "ssf_keyframes_configure: needs cell 4 / 8 / 16 (<= the image), 1 .. 4096 ferns, max_keyframes >= 1, min_gap >= 0, max_rows >= 0 and finite ratios";
+        return SSF_ERR_INVALID_ARG;
+    }
+    // the depth range in mm: the sum of a cell's 256 depths must fit 31 bits
+    if (!(h->cfg.range_min >= 0.0f) || !(h->cfg.range_max <= 8000.0f) || !(lrintf(h->cfg.range_max * 1000.0f) > lrintf(h->cfg.range_min * 1000.0f))) {
+        h->err = "ssf_keyframes_configure: needs 0 <= range_min < range_max <= 8000 m (whole millimetres apart)"; return SSF_ERR_INVALID_ARG;
+    }
+    if (h->cfg.nranks > 1) { h->err = "ssf_keyframes_configure: a sharded handle (cfg.nranks > 1) keeps no keyframe database"; return SSF_ERR_STATE; }
+    KeyframeWs& k = h->kf;
+    if (k.on) { h->err = "ssf_keyframes_configure: a database is live (ssf_keyframes_clear first)"; return SSF_ERR_STATE; }
+    const size_t words = (((size_t)p->n_ferns + 7) / 8 + 63) / 64 * 64, K = (size_t)p->max_keyframes;
+    const size_t rows = p->max_rows > 0 ? (size_t)p->max_rows : K * (size_t)h->S;
+    if (!k.bufs.grow({{(void**)&k.ferns, 16 * (size_t)p->n_ferns}, {(void**)&k.q, 4 * words}, {(void**)&k.table, 4 * words * K},
+                      {(void**)&k.stamps, 4 * K}, {(void**)&k.diff, 4 * K}, {(void**)&k.rec, 4 * SSF_KF_REC_WORDS},
+                      {(void**)&k.bytes, (size_t)SSF_KEYFRAMES_MAX_FERNS},
+                      {(void**)&k.pool.positions, 12 * rows}, {(void**)&k.pool.colors, 12 * rows}, {(void**)&k.pool.stamps, 8 * rows},
+                      {(void**)&k.pool.orientations, 36 * rows}, {(void**)&k.pool.shapes, 24 * rows}, {(void**)&k.pool.dims, 8 * rows},
+                      {(void**)&k.pool.confidences, 4 * rows}})) {
+        k.bufs.release();
+        h->err = "ssf_keyframes_configure: allocation of the database failed"; return SSF_ERR_DEVICE;
+    }
+    k.p = *p; k.p.max_rows = (int64_t)rows;
+    k.words = (int)words; k.gw = W / p->cell; k.gh = H / p->cell;
+    k.kfs.clear(); k.rows_used = 0;
+    const uint32_t dlo = (uint32_t)lrintf(h->cfg.range_min * 1000.0f), dhi = (uint32_t)lrintf(h->cfg.range_max * 1000.0f);
+    k.host_ferns.assign((size_t)p->n_ferns, ssf_fern());
+    uint64_t s = p->seed;
+    for (auto& f : k.host_ferns) {
+        f.x = (uint16_t)(kf_splitmix64(s) % (uint64_t)k.gw); f.y = (uint16_t)(kf_splitmix64(s) % (uint64_t)k.gh);
+        f.r = (uint8_t)(kf_splitmix64(s) % 256u); f.g = (uint8_t)(kf_splitmix64(s) % 256u); f.b = (uint8_t)(kf_splitmix64(s) % 256u);
+        f.pad = 0; f.depth_mm = dlo + (uint32_t)(kf_splitmix64(s) % (uint64_t)(dhi - dlo));
+    }
+    { int rc = kf_upload_ferns(h); if (rc) { k.bufs.release(); return rc; } }
+    k.on = true;
+    return SSF_OK;
+}
+int ssf_keyframes_clear(ssf_handle* h) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    KeyframeWs& k = h->kf;
+    k.bufs.release();
+    k.on = false; k.kfs.clear(); k.host_ferns.clear(); k.rows_used = 0; k.words = 0;
+    return SSF_OK;
+}
+int ssf_keyframes_info(ssf_handle* h, int* configured, int* n_keyframes, int64_t* rows_used, ssf_keyframes_params* p) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    const KeyframeWs& k = h->kf;
+    if (configured) *configured = k.on ? 1 : 0;
+    if (n_keyframes) *n_keyframes = k.on ? (int)k.kfs.size() : 0;
+    if (rows_used) *rows_used = k.on ? (int64_t)k.rows_used : 0;
+    if (p) { if (k.on) *p = k.p; else std::memset(p, 0, sizeof(*p)); }
+    return SSF_OK;
+}
+int ssf_keyframes_set_ferns(ssf_handle* h, const ssf_fern* ferns, int n) {
+    if (!h || !ferns) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_set_ferns", 0); if (rc) return rc; }
+    KeyframeWs& k = h->kf;
+    if (n != k.p.n_ferns) { h->err = "ssf_keyframes_set_ferns: the database is configured for " + std::to_string(k.p.n_ferns) + " ferns"; return SSF_ERR_INVALID_ARG; }
+    if (!k.kfs.empty()) { h->err = "ssf_keyframes_set_ferns: keyframes are stored under the present table"; return SSF_ERR_STATE; }
+    for (int i = 0; i < n; i++)
+        if ((int)ferns[i].x >= k.gw || (int)ferns[i].y >= k.gh) {
+            h->err = "ssf_keyframes_set_ferns: fern " + std::to_string(i) + " names a cell outside the " + std::to_string(k.gw) + " x " + std::to_string(k.gh) + " grid";
+            return SSF_ERR_INVALID_ARG;
+        }
+    k.host_ferns.assign(ferns, ferns + n);
+    for (auto& f : k.host_ferns) f.pad = 0;
+    return kf_upload_ferns(h);
+}
+int ssf_keyframes_get_ferns(ssf_handle* h, ssf_fern* ferns, int capacity) {
+    if (!h || !ferns) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_get_ferns", 0); if (rc) return rc; }
+    const KeyframeWs& k = h->kf;
+    if (capacity < k.p.n_ferns) { h->err = "ssf_keyframes_get_ferns: " + std::to_string(k.p.n_ferns) + " ferns, room for " + std::to_string(capacity); return SSF_ERR_CAPACITY; }
+    std::memcpy(ferns, k.host_ferns.data(), sizeof(ssf_fern) * k.host_ferns.size());
+    return SSF_OK;
+}
+// the current frame's packed codes into kf.q (enqueued only)
+static void kf_encode_current(ssf_handle* h) {
+    const KeyframeWs& k = h->kf;
+    launch_kf_encode(h->stream, h->cc->maps.rgba, h->cc->maps.plane_depth, h->cfg.width, k.p.cell, h->cfg.range_min, h->cfg.range_max,
+                     k.ferns, k.p.n_ferns, k.words, k.q);
+}
+// n code bytes -> the packed words; false: a code > 15
+static bool kf_pack_codes(const uint8_t* codes, int n, int words, std::vector<uint32_t>& out) {
+    out.assign((size_t)words, 0u);
+    for (int i = 0; i < n; i++) {
+        if (codes[i] > 15) return false;
+        out[i >> 3] |= (uint32_t)codes[i] << (4 * (i & 7));
+    }
+    return true;
+}
+// search + select (+ the add) of kf.q; rec: SSF_KF_REC_WORDS words.  The host takes the keyframe the device added into its mirror
+static int kf_run(ssf_handle* h, const char* who, int mode, int kmax, int stamp, int min_gap, bool with_frame, int32_t* rec) {
+    KeyframeWs& k = h->kf;
+    hipStream_t st = h->stream;
+    KfQuery q;
+    q.words = k.words; q.n = k.p.n_ferns; q.K = (int)k.kfs.size(); q.max_keyframes = k.p.max_keyframes; q.mode = mode; q.kmax = kmax;
+    q.stamp = stamp; q.min_gap = min_gap; q.rows_used = k.rows_used; q.max_rows = (long long)k.p.max_rows;
+    q.new_ratio = k.p.new_ratio; q.loop_ratio = k.p.loop_ratio;
+    launch_kf_search(st, k.q, k.table, k.words, q.K, k.diff);
+    HCK(hipGetLastError());
+    SurfelSoA none; std::memset(&none, 0, sizeof(none));
+    launch_kf_select(st, q, k.q, k.table, k.stamps, k.diff, with_frame ? h->cc->frame : none, with_frame ? h->S : 0, k.pool, k.rec);
+    HCK(hipGetLastError());
+    HCK(hipMemcpyAsync(rec, k.rec, 4 * SSF_KF_REC_WORDS, hipMemcpyDeviceToHost, st));
+    { int rc = sync_collect(h); if (rc) return rc; }
+    const bool added = rec[0] != 0;
+    // the decision was taken on the device; the host checks what it can from the record
+    if (rec[4] != q.K + (added ? 1 : 0) || (added && (rec[1] != q.K || mode == 0 || rec[38] < 0 || k.rows_used + rec[38] > (long long)k.p.max_rows)) ||
+        rec[5] < 0 || rec[5] > kmax) {
+        h->err = std::string(who) + ": the device's record contradicts the host's view of the database"; return SSF_ERR_DEVICE;
+    }
+    if (added) {
+        KeyframeMeta m; m.first = k.rows_used; m.rows = rec[38]; m.stamp = stamp; pose_to12(h->pose, m.pose);
+        k.kfs.push_back(m); k.rows_used += m.rows;
+    }
+    return SSF_OK;
+}
+int ssf_keyframes_encode(ssf_handle* h, uint8_t* codes, int capacity) {
+    if (!h || !codes) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_encode", 2); if (rc) return rc; }
+    KeyframeWs& k = h->kf;
+    if (capacity < k.p.n_ferns) { h->err = "ssf_keyframes_encode: " + std::to_string(k.p.n_ferns) + " codes, room for " + std::to_string(capacity); return SSF_ERR_CAPACITY; }
+    { TimerScope ts(h); kf_encode_current(h); }
+    HCK(hipGetLastError());
+    launch_kf_unpack(h->stream, k.q, k.p.n_ferns, k.bytes);
+    HCK(hipGetLastError());
+    HCK(hipMemcpyAsync(codes, k.bytes, (size_t)k.p.n_ferns, hipMemcpyDeviceToHost, h->stream));
+    { int rc = sync_collect(h); if (rc) return rc; }
+    return SSF_OK;
+}
+int ssf_keyframes_query(ssf_handle* h, const uint8_t* codes, int stamp, int min_gap, int kmax, ssf_keyframe_result* out) {
+    if (!h || !out || kmax < 0 || kmax > SSF_KEYFRAMES_MAX_CANDIDATES) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_query", codes ? 0 : 2); if (rc) return rc; }
+    KeyframeWs& k = h->kf;
+    std::vector<uint32_t> packed;
+    TimerScope ts(h);
+    if (codes) {
+        if (!kf_pack_codes(codes, k.p.n_ferns, k.words, packed)) { h->err = "ssf_keyframes_query: a code is a value 0 .. 15"; return SSF_ERR_INVALID_ARG; }
+        HCK(hipMemcpyAsync(k.q, packed.data(), 4 * packed.size(), hipMemcpyHostToDevice, h->stream));
+    } else {
+        kf_encode_current(h);
+        HCK(hipGetLastError());
+        stamp = h->stamp;
+    }
+    int32_t rec[SSF_KF_REC_WORDS];
+    { int rc = kf_run(h, "ssf_keyframes_query", 0, kmax, stamp, min_gap < 0 ? k.p.min_gap : min_gap, false, rec); if (rc) return rc; }
+    std::memcpy(out, rec, sizeof(*out));
+    return SSF_OK;
+}
+int ssf_keyframes_consider(ssf_handle* h, ssf_keyframe_result* out) {
+    if (!h || !out) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_consider", 2); if (rc) return rc; }
+    TimerScope ts(h);
+    kf_encode_current(h);
+    HCK(hipGetLastError());
+    int32_t rec[SSF_KF_REC_WORDS];
+    { int rc = kf_run(h, "ssf_keyframes_consider", 1, SSF_KEYFRAMES_MAX_CANDIDATES, h->stamp, h->kf.p.min_gap, true, rec); if (rc) return rc; }
+    std::memcpy(out, rec, sizeof(*out));
+    return SSF_OK;
+}
+int ssf_keyframes_add(ssf_handle* h, int* id) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_add", 2); if (rc) return rc; }
+    TimerScope ts(h);
+    kf_encode_current(h);
+    HCK(hipGetLastError());
+    int32_t rec[SSF_KF_REC_WORDS];
+    { int rc = kf_run(h, "ssf_keyframes_add", 2, 0, h->stamp, h->kf.p.min_gap, true, rec); if (rc) return rc; }
+    if (!rec[0]) { h->err = "ssf_keyframes_add: the store is full"; return SSF_ERR_CAPACITY; }
+    if (id) *id = rec[1];
+    return SSF_OK;
+}
+int ssf_keyframes_put(ssf_handle* h, const uint8_t* codes, const ssf_surfels* rows, int n_rows, const float* pose, int stamp, int* id) {
+    if (!h || !codes || !pose || n_rows < 0 || (n_rows > 0 && (!rows || !rows->positions || !rows->colors || !rows->stamps || !rows->orientations ||
+                                                              !rows->shapes || !rows->dims || !rows->confidences))) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_put", 0); if (rc) return rc; }
+    KeyframeWs& k = h->kf;
+    const size_t K = k.kfs.size(), n = (size_t)n_rows, o = (size_t)k.rows_used;
+    if ((int)K >= k.p.max_keyframes || k.rows_used + n_rows > (long long)k.p.max_rows) { h->err = "ssf_keyframes_put: the store is full"; return SSF_ERR_CAPACITY; }
+    std::vector<uint32_t> packed;
+    if (!kf_pack_codes(codes, k.p.n_ferns, k.words, packed)) { h->err = "ssf_keyframes_put: a code is a value 0 .. 15"; return SSF_ERR_INVALID_ARG; }
+    hipStream_t st = h->stream;
+    const int32_t stamp32 = stamp;
+    HCK(hipMemcpyAsync(k.table + K * (size_t)k.words, packed.data(), 4 * packed.size(), hipMemcpyHostToDevice, st));
+    HCK(hipMemcpyAsync(k.stamps + K, &stamp32, 4, hipMemcpyHostToDevice, st));
+    if (n > 0) { int rc = copy_rows(h, k.pool, o, *rows, 0, n, hipMemcpyHostToDevice); if (rc) return rc; }
+    HCK(hipStreamSynchronize(st));
+    KeyframeMeta m; m.first = k.rows_used; m.rows = n_rows; m.stamp = stamp; std::memcpy(m.pose, pose, sizeof(m.pose));
+    k.kfs.push_back(m); k.rows_used += n_rows;
+    if (id) *id = (int)K;
+    return SSF_OK;
+}
+static int kf_lookup(ssf_handle* h, const char* who, int id) {
+    if (id < 0 || (size_t)id >= h->kf.kfs.size()) {
+        h->err = std::string(who) + ": no keyframe " + std::to_string(id) + " (" + std::to_string(h->kf.kfs.size()) + " stored)"; return SSF_ERR_INVALID_ARG;
+    }
+    return SSF_OK;
+}
+int ssf_keyframes_get(ssf_handle* h, int id, ssf_surfels* rows, int capacity, int* n_rows, float* pose, int* stamp, uint8_t* codes) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_get", 0); if (rc) return rc; }
+    { int rc = kf_lookup(h, "ssf_keyframes_get", id); if (rc) return rc; }
+    KeyframeWs& k = h->kf;
+    const KeyframeMeta& m = k.kfs[(size_t)id];
+    if (rows && capacity < m.rows) { h->err = "ssf_keyframes_get: " + std::to_string(m.rows) + " rows, room for " + std::to_string(capacity); return SSF_ERR_CAPACITY; }
+    hipStream_t st = h->stream;
+    const size_t n = (size_t)m.rows, o = (size_t)m.first;
+    if (rows) { int rc = copy_rows(h, *rows, 0, k.pool, o, n, hipMemcpyDeviceToHost); if (rc) return rc; }
+    if (codes) {
+        launch_kf_unpack(st, k.table + (size_t)id * k.words, k.p.n_ferns, k.bytes);
+        HCK(hipGetLastError());
+        HCK(hipMemcpyAsync(codes, k.bytes, (size_t)k.p.n_ferns, hipMemcpyDeviceToHost, st));
+    }
+    HCK(hipStreamSynchronize(st));
+    if (n_rows) *n_rows = m.rows;
+    if (pose) std::memcpy(pose, m.pose, sizeof(m.pose));
+    if (stamp) *stamp = m.stamp;
+    return SSF_OK;
+}
+int ssf_keyframes_set_pose(ssf_handle* h, int id, const float* pose) {
+    if (!h || !pose) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_set_pose", 0); if (rc) return rc; }
+    { int rc = kf_lookup(h, "ssf_keyframes_set_pose", id); if (rc) return rc; }
+    std::memcpy(h->kf.kfs[(size_t)id].pose, pose, 12 * sizeof(float));
+    return SSF_OK;
+}
+int ssf_keyframes_align(ssf_handle* h, int id, const float* init_pose, int use_conf, float* rel_pose, int* valid, int* iters, int* pairs_last) {
+    if (!h || !rel_pose || !valid) return SSF_ERR_INVALID_ARG;
+    { int rc = kf_usable(h, "ssf_keyframes_align", 1); if (rc) return rc; }
+    { int rc = kf_lookup(h, "ssf_keyframes_align", id); if (rc) return rc; }
+    const KeyframeWs& k = h->kf;
+    const KeyframeMeta& m = k.kfs[(size_t)id];
+    const size_t N = (size_t)std::max(m.rows, 1), o = (size_t)m.first;
+    float *d_lab = nullptr, *d_nrm = nullptr; long long* d_out = nullptr;
+    DevTemps tmp;
+    HCK(tmp.take(&d_lab, 12 * N)); HCK(tmp.take(&d_nrm, 12 * N)); HCK(tmp.take(&d_out, 40 * sizeof(long long)));
+    TimerScope ts(h);
+    launch_kf_align_prep(h->stream, k.pool.colors + 3 * o, k.pool.orientations + 9 * o, m.rows, d_lab, d_nrm);
+    HCK(hipGetLastError());
+    return align_loop(h, k.pool.positions + 3 * o, d_lab, d_nrm, use_conf ? k.pool.confidences + o : nullptr, m.rows, d_out, init_pose, rel_pose, valid, iters,
+                      pairs_last);
+}
+}  // extern "C"

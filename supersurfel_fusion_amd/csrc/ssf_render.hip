@@ -19,8 +19,14 @@
 // Statistics are exact integers: fragments and filled pixels are summed per workgroup (one 64-bit atomic each); rows_shown
 // counts the slots whose `seen` word a winner exchanges from an older render epoch to the current one.
 #include "ssf_slots.hpp"
+#include "ssf_handle.hpp"
 
 namespace ssf {
+
+// R = 9 floats row-major and t (camera-to-map, ssf_get_pose's layout); ntx x nty tiles of 16 x 16 pixels; k = s * s
+struct RenderCam { float R[9], t[3]; float fx, fy, cx, cy; int W, H, ntx, nty; float zmin, zmax, min_conf, s, k; };
+struct RenderView { RenderCam cam; ModelView model; };           // one kernel argument: the camera and the rows drawn
+struct RenderOut { float* depth; int32_t* index; uint8_t* rgb8; float* color; float* normal; };      // nullptr = not produced
 
 __device__ __forceinline__ unsigned long long rsum_u64(unsigned long long v) {
 #pragma unroll
@@ -212,8 +218,10 @@ __global__ __launch_bounds__(256) void k_render_tile(RenderView rv, const float4
 }
 
 // ---- launches -------------------------------------------------------------------------------------------------------
-void launch_render_prep(hipStream_t st, const RenderView& rv, uint32_t* bc, float4* rec, uint2* rbox, int32_t* logical, uint32_t* tcnt,
-                        uint32_t* cursor, unsigned long long* total) {
+// prep (+ the out-of-view live scan into bc[nbo + 1]) and the exclusive scan of the tile counts: tcnt[ntiles + 1] (zeroed by the
+// caller) becomes the list offsets, cursor[ntiles] a copy; *total = list entries (64 bits)
+static void launch_render_prep(hipStream_t st, const RenderView& rv, uint32_t* bc, float4* rec, uint2* rbox, int32_t* logical, uint32_t* tcnt,
+                               uint32_t* cursor, unsigned long long* total) {
     ScopedKernel sk("render_prep", st);
     const ModelView& mv = rv.model;
     if (mv.nbo > 0) {
@@ -224,16 +232,119 @@ void launch_render_prep(hipStream_t st, const RenderView& rv, uint32_t* bc, floa
         hipLaunchKernelGGL(k_render_prep, dim3(mv.nbv + mv.nbo), dim3(256), 0, st, rv, bc, rec, rbox, logical, tcnt);
     hipLaunchKernelGGL(k_render_scan, dim3(1), dim3(1024), 0, st, tcnt, rv.cam.ntx * rv.cam.nty, cursor, total);
 }
-void launch_render_fill(hipStream_t st, const RenderView& rv, const uint2* rbox, uint32_t* cursor, uint32_t* list) {
+static void launch_render_fill(hipStream_t st, const RenderView& rv, const uint2* rbox, uint32_t* cursor, uint32_t* list) {
     ScopedKernel sk("render_fill", st);
     if (rv.model.nslots > 0) hipLaunchKernelGGL(k_render_fill, dim3(rv.model.nslots / 256), dim3(256), 0, st, rv, rbox, cursor, list);
 }
-void launch_render_tile(hipStream_t st, const RenderView& rv, const float4* rec, const uint2* rbox, const int32_t* logical,
-                        const uint32_t* list, const uint32_t* toff, const RenderOut& out, uint32_t* seen, uint32_t epoch,
-                        unsigned long long* stats) {
+// stats[0..2] += fragments, filled pixels, rows shown (seen[slot] != epoch before this render)
+static void launch_render_tile(hipStream_t st, const RenderView& rv, const float4* rec, const uint2* rbox, const int32_t* logical,
+                               const uint32_t* list, const uint32_t* toff, const RenderOut& out, uint32_t* seen, uint32_t epoch,
+                               unsigned long long* stats) {
     ScopedKernel sk("render_tile", st);
     hipLaunchKernelGGL(k_render_tile, dim3(rv.cam.ntx * rv.cam.nty), dim3(256), 0, st, rv, rec, rbox, logical, list, toff, out, seen,
                        epoch, stats);
 }
 
 }  // namespace ssf
+
+// ---- host: the entry points of include/ssf_render.h ------------------------------------------------------------------------
+extern "C" {
+static size_t render_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int ssf_render_default_params(const ssf_handle* h, ssf_render_params* p) {
+    if (!h || !p) return SSF_ERR_INVALID_ARG;
+    std::memset(p, 0, sizeof(*p));
+    p->width = h->cam.W; p->height = h->cam.H; p->fx = h->cam.fx; p->fy = h->cam.fy; p->cx = h->cam.cx; p->cy = h->cam.cy;
+    p->z_min = h->cfg.range_min; p->z_max = h->cfg.range_max; p->min_conf = 0.0f; p->splat_scale = 3.0f;
+    return SSF_OK;
+}
+
+int ssf_render_model(ssf_handle* h, const ssf_render_params* p, float* depth, int32_t* index, uint8_t* rgb8, float* color,
+                     float* normal, ssf_render_stats* stats) {
+    if (!h || !p) return SSF_ERR_INVALID_ARG;
+    if (!depth && !index && !rgb8 && !color && !normal) { h->err = "ssf_render_model: every output is NULL"; return SSF_ERR_INVALID_ARG; }
+    { int rc = model_at_rest(h, "ssf_render_model", "is not rendered"); if (rc) return rc; }
+    RenderCam K;
+    const Rt T = p->pose ? pose_from12(p->pose) : h->pose;
+    const float R9[9] = {T.R.r0.x, T.R.r0.y, T.R.r0.z, T.R.r1.x, T.R.r1.y, T.R.r1.z, T.R.r2.x, T.R.r2.y, T.R.r2.z};
+    std::memcpy(K.R, R9, sizeof(R9)); K.t[0] = T.t.x; K.t[1] = T.t.y; K.t[2] = T.t.z;
+    if (p->width == 0) { K.W = h->cam.W; K.H = h->cam.H; K.fx = h->cam.fx; K.fy = h->cam.fy; K.cx = h->cam.cx; K.cy = h->cam.cy; }
+    else { K.W = p->width; K.H = p->height; K.fx = p->fx; K.fy = p->fy; K.cx = p->cx; K.cy = p->cy; }
+    if (K.W < 1 || K.W > 4096 || K.H < 1 || K.H > 4096) { h->err = "ssf_render_model: the camera size must be 1..4096 x 1..4096"; return SSF_ERR_INVALID_ARG; }
+    if (!std::isfinite(K.fx) || !std::isfinite(K.fy) || K.fx == 0.0f || K.fy == 0.0f) { h->err = "ssf_render_model: fx and fy must be finite and non-zero"; return SSF_ERR_INVALID_ARG; }
+    K.zmin = p->z_min; K.zmax = p->z_max;
+    if (K.zmin == 0.0f && K.zmax == 0.0f) { K.zmin = h->cfg.range_min; K.zmax = h->cfg.range_max; }
+    if (!(K.zmin > 0.0f) || !(K.zmax > K.zmin)) { h->err = "ssf_render_model: the depth range needs 0 < z_min < z_max"; return SSF_ERR_INVALID_ARG; }
+    K.s = p->splat_scale == 0.0f ? 3.0f : p->splat_scale;
+    if (!(K.s >= 0.0f) || !std::isfinite(K.s)) { h->err = "ssf_render_model: splat_scale must be finite and >= 0"; return SSF_ERR_INVALID_ARG; }
+    K.k = K.s * K.s; K.min_conf = p->min_conf;
+    K.ntx = (K.W + 15) / 16; K.nty = (K.H + 15) / 16;
+    const int ntiles = K.ntx * K.nty;
+
+    const RenderView rv{K, model_view(h, p->visible_only != 0)};
+
+    RenderWs& w = h->render;
+    const size_t P = (size_t)K.W * K.H;
+    const size_t img_need = p->on_device ? 0 : (depth ? render_align(4 * P) : 0) + (index ? render_align(4 * P) : 0) +
+                                               (rgb8 ? render_align(3 * P) : 0) + (color ? render_align(12 * P) : 0) + (normal ? render_align(12 * P) : 0);
+    const size_t slots = std::max<size_t>(rv.model.nslots, 256);
+    bool ok = true;
+    if (ok && slots > w.slots) {
+        ok = w.bufs.grow({{(void**)&w.rec, 64 * slots}, {(void**)&w.rbox, 8 * slots}, {(void**)&w.logical, 4 * slots},
+                          {(void**)&w.seen, 4 * slots}, {(void**)&w.bc, 4 * (slots / 256 + 1)}});
+        if (ok) { w.slots = slots; w.epoch = 0; HCK(hipMemsetAsync(w.seen, 0, 4 * slots, h->stream)); }
+    }
+    if (ok && (size_t)ntiles + 1 > w.tiles) {
+        ok = w.bufs.grow({{(void**)&w.tcnt, 4 * ((size_t)ntiles + 1)}, {(void**)&w.cursor, 4 * ((size_t)ntiles + 1)}});
+        if (ok) w.tiles = (size_t)ntiles + 1;
+    }
+    if (ok && !w.stats) ok = w.bufs.grow({{(void**)&w.stats, 4 * sizeof(unsigned long long)}});
+    if (ok && img_need > w.img_bytes) {
+        ok = w.bufs.grow({{(void**)&w.img, img_need}});
+        if (ok) w.img_bytes = img_need;
+    }
+    if (!ok) { h->err = "ssf_render_model: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
+    if (++w.epoch == 0) { HCK(hipMemsetAsync(w.seen, 0, 4 * w.slots, h->stream)); w.epoch = 1; }
+
+    TimerScope ts(h);
+    hipStream_t st = h->stream;
+    HCK(hipMemsetAsync(w.tcnt, 0, 4 * ((size_t)ntiles + 1), st));
+    HCK(hipMemsetAsync(w.stats, 0, 4 * sizeof(unsigned long long), st));
+    launch_render_prep(st, rv, w.bc, w.rec, w.rbox, w.logical, w.tcnt, w.cursor, w.stats + 3);
+    HCK(hipGetLastError());
+    unsigned long long total = 0;
+    HCK(hipMemcpyAsync(&total, w.stats + 3, sizeof(total), hipMemcpyDeviceToHost, st));
+    HCK(hipStreamSynchronize(st));
+    if (total > 0xFFFFFFFFull) { h->err = "ssf_render_model: more than 2^32 - 1 (tile, row) list entries"; return SSF_ERR_DEVICE; }
+    if (total > w.list_cap) {
+        const size_t cap = std::min<unsigned long long>(total + total / 4, 0xFFFFFFFFull);
+        if (!w.bufs.grow({{(void**)&w.list, 4 * cap}})) {
+            h->err = "ssf_render_model: allocation of " + std::to_string(4 * cap) + " bytes for the tile lists failed";
+            return SSF_ERR_DEVICE;
+        }
+        w.list_cap = cap;
+    }
+    if (total > 0) { launch_render_fill(st, rv, w.rbox, w.cursor, w.list); HCK(hipGetLastError()); }
+    RenderOut o{depth, index, rgb8, color, normal};
+    if (!p->on_device) {
+        unsigned char* q = w.img;
+        auto carve = [&](bool want, size_t bytes) { unsigned char* r = want ? q : nullptr; if (want) q += render_align(bytes); return r; };
+        o.depth = (float*)carve(depth != nullptr, 4 * P); o.index = (int32_t*)carve(index != nullptr, 4 * P);
+        o.rgb8 = carve(rgb8 != nullptr, 3 * P); o.color = (float*)carve(color != nullptr, 12 * P); o.normal = (float*)carve(normal != nullptr, 12 * P);
+    }
+    launch_render_tile(st, rv, w.rec, w.rbox, w.logical, w.list, w.tcnt, o, w.seen, w.epoch, w.stats);
+    HCK(hipGetLastError());
+    unsigned long long st3[3] = {0, 0, 0};
+    HCK(hipMemcpyAsync(st3, w.stats, sizeof(st3), hipMemcpyDeviceToHost, st));
+    if (!p->on_device) {
+        if (depth) HCK(hipMemcpyAsync(depth, o.depth, 4 * P, hipMemcpyDeviceToHost, st));
+        if (index) HCK(hipMemcpyAsync(index, o.index, 4 * P, hipMemcpyDeviceToHost, st));
+        if (rgb8) HCK(hipMemcpyAsync(rgb8, o.rgb8, 3 * P, hipMemcpyDeviceToHost, st));
+        if (color) HCK(hipMemcpyAsync(color, o.color, 12 * P, hipMemcpyDeviceToHost, st));
+        if (normal) HCK(hipMemcpyAsync(normal, o.normal, 12 * P, hipMemcpyDeviceToHost, st));
+    }
+    { int rc = sync_collect(h); if (rc) return rc; }
+    if (stats) { stats->fragments = (int64_t)st3[0]; stats->pixels_filled = (int64_t)st3[1]; stats->rows_shown = (int64_t)st3[2]; stats->list_entries = (int64_t)total; }
+    return SSF_OK;
+}
+}  // extern "C"

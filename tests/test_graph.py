@@ -98,7 +98,7 @@ def test_ssf_hpp_graph_surface_compiles_and_links_against_the_product(product_li
 
 
 def test_the_default_parameters():
-    txt = open(os.path.join(ROOT, "supersurfel_fusion_amd", "csrc", "ssf_host.hip")).read()
+    txt = open(os.path.join(ROOT, "supersurfel_fusion_amd", "csrc", "ssf_graph.hip")).read()
     assert "p->stride = 50; p->look = 20; p->min_conf = 0.0f;" in txt
 
 

@@ -156,7 +156,7 @@ def test_ssf_hpp_keyframe_surface_compiles_and_links_against_the_product(product
 
 
 def test_the_default_parameters():
-    txt = open(os.path.join(ROOT, "supersurfel_fusion_amd", "csrc", "ssf_host.hip")).read()
+    txt = open(os.path.join(ROOT, "supersurfel_fusion_amd", "csrc", "ssf_keyframes.hip")).read()
     assert "p->cell = 8; p->n_ferns = 500; p->seed = 1234; p->max_keyframes = 256; p->min_gap = 30; p->max_rows = 0;" in txt
     assert "p->new_ratio = 0.3f; p->loop_ratio = 0.2f;" in txt
 
