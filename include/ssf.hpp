@@ -20,6 +20,7 @@
 #include "ssf_dynamic.h"
 #include "ssf_render.h"
 #include "ssf_graph.h"
+#include "ssf_graph_solve.h"
 #include "ssf_keyframes.h"
 
 /* The reference's pose / matrix types (core/include/supersurfel_fusion/matrix_types.h:26-42), at GLOBAL scope as there,
@@ -416,6 +417,37 @@ public:
             throw std::runtime_error("applyGraph: one rotation and one translation per node");
         check(ssf_graph_apply(need(), reinterpret_cast<const float*>(rotations.data()), reinterpret_cast<const float*>(translations.data())));
     }
+    /* The graph's optimisation on the device (ssf_graph_solve.h; exported by libssf_hip.so only): node transforms that take the
+     * constraint points src (birth stamps in t_init) to dst, a pin being dst == src.  The names follow the reference's
+     * DeformationGraph (optimiseGraphSparse, applyGraphToModel) where it has the step.  The transforms stay on the device. */
+    static ssf_graph_solve_params defaultGraphSolveParams() { ssf_graph_solve_params p; ssf_graph_solve_default_params(&p); return p; }
+    ssf_graph_solve_result optimiseGraphSparse(const std::vector<float3>& src, const std::vector<int32_t>& t_init,
+                                               const std::vector<float3>& dst,
+                                               const ssf_graph_solve_params& p = defaultGraphSolveParams()) {
+        if (src.size() != t_init.size() || src.size() != dst.size())
+            throw std::runtime_error("optimiseGraphSparse: one birth stamp and one target per source point");
+        ssf_graph_solve_result r;
+        check(ssf_graph_solve(need(), &p, reinterpret_cast<const float*>(src.data()), t_init.data(),
+                              reinterpret_cast<const float*>(dst.data()), (int)src.size(), &r));
+        return r;
+    }
+    /* the four neighbours of every node, 4 per node in node order */
+    std::vector<int32_t> getGraphEdges() {
+        int m = 0;
+        check(ssf_graph_info(need(), &m, nullptr, nullptr));
+        std::vector<int32_t> e(4 * (size_t)m);
+        check(ssf_graph_get_edges(need(), e.data(), m));
+        return e;
+    }
+    /* the solved transforms, as applyGraph takes them */
+    void getGraphTransforms(std::vector<Mat33>& rotations, std::vector<float3>& translations) {
+        int m = 0;
+        check(ssf_graph_info(need(), &m, nullptr, nullptr));
+        rotations.resize((size_t)m); translations.resize((size_t)m);
+        check(ssf_graph_get_transforms(need(), reinterpret_cast<float*>(rotations.data()), reinterpret_cast<float*>(translations.data()), m));
+    }
+    /* deform the model with the resident solved transforms (nothing is uploaded); the graph is stale afterwards */
+    void applyGraphToModel() { check(ssf_graph_apply_solved(need())); }
     /* The keyframe database of loop detection, kept on the device (ssf_keyframes.h; exported by libssf_hip.so only):
      * configureKeyframes once, considerKeyframe after every frame, alignKeyframe for a loop candidate of its record.
      * INTEGRATION.md section 2 has the call sequence. */

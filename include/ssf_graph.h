@@ -4,7 +4,8 @@
  * After a loop closure the caller bends the whole map: ssf_apply_deformation wants four node indices and four weights per model
  * row.  Everything that is O(model rows) is done here, where the model lives: sampling the nodes from the model, binding every
  * row to its nodes, keeping that binding resident, and applying the optimised node transforms through it.  Only the node table
- * (16 B per node out, 48 B per node in) crosses to the host; the graph OPTIMISATION (a few thousand nodes) stays with the caller.
+ * (16 B per node out, 48 B per node in) crosses to the host.  The graph OPTIMISATION between ssf_graph_bind_points and
+ * ssf_graph_apply is ssf_graph_solve.h's (on the device, over the same resident nodes); a caller may still run its own.
  *
  * The rule is this library's own, deterministic, in the ElasticFusion shape (nodes in time order, a row looks at the nodes born
  * around its own birth, the k + 1-th nearest sets the support radius); it claims no bit parity with any other implementation.

@@ -83,6 +83,9 @@ RENDER_SYMBOLS = ["ssf_render_default_params", "ssf_render_model"]
 # the deformation graph's nodes and per-row binding (include/ssf_graph.h): exported by the HIP product only, not part of ssf.h
 GRAPH_SYMBOLS = ["ssf_graph_default_params", "ssf_graph_build", "ssf_graph_get_nodes", "ssf_graph_get_binding",
                  "ssf_graph_bind_points", "ssf_graph_apply", "ssf_graph_info"]
+# the graph's optimisation (include/ssf_graph_solve.h): HIP product only
+GRAPH_SOLVE_SYMBOLS = ["ssf_graph_solve_default_params", "ssf_graph_get_edges", "ssf_graph_solve", "ssf_graph_get_transforms",
+                       "ssf_graph_apply_solved"]
 # the fern-coded keyframe database (include/ssf_keyframes.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 KEYFRAME_SYMBOLS = ["ssf_keyframes_default_params", "ssf_keyframes_configure", "ssf_keyframes_set_ferns", "ssf_keyframes_get_ferns",
                     "ssf_keyframes_encode", "ssf_keyframes_query", "ssf_keyframes_add", "ssf_keyframes_consider", "ssf_keyframes_put",
@@ -124,6 +127,27 @@ class SsfRenderStats(C.Structure):
 class SsfGraphParams(C.Structure):
     """ssf_graph_params (include/ssf_graph.h)"""
     _fields_ = [("stride", C.c_int), ("look", C.c_int), ("min_conf", C.c_float)]
+
+
+GRAPH_SOLVE_MAX_OUTER = 64
+GRAPH_SOLVE_ENDS = ("tolerance", "max_inner", "breakdown", "zero")
+
+
+class SsfGraphSolveParams(C.Structure):
+    """ssf_graph_solve_params (include/ssf_graph_solve.h)"""
+    _fields_ = [(nm, C.c_double) for nm in ("w_rot", "w_reg", "w_con", "inner_tol", "outer_tol", "damping")] + \
+               [(nm, C.c_int) for nm in ("max_outer", "max_inner", "inner_check")]
+
+
+class SsfGraphSolveResult(C.Structure):
+    """ssf_graph_solve_result (include/ssf_graph_solve.h)"""
+    _fields_ = [(nm, C.c_double) for nm in ("e_before", "e_after", "e_rot", "e_reg", "e_con")] + \
+               [("outer", C.c_int), ("inner_end", C.c_int), ("inner", C.c_int * GRAPH_SOLVE_MAX_OUTER)]
+
+    def as_dict(self):
+        d = {nm: getattr(self, nm) for nm in ("e_before", "e_after", "e_rot", "e_reg", "e_con", "outer", "inner_end")}
+        d["inner"] = [int(v) for v in self.inner[:self.outer]]
+        return d
 
 
 class SsfKeyframesParams(C.Structure):
@@ -250,6 +274,13 @@ class Library:
             L.ssf_graph_bind_points.argtypes = [vp, vp, vp, C.c_int, vp, vp]
             L.ssf_graph_apply.argtypes = [vp, vp, vp]
             L.ssf_graph_info.argtypes = [vp, ip, ip, ip]
+        self.has_graph_solve = all(hasattr(L, nm) for nm in GRAPH_SOLVE_SYMBOLS)
+        if self.has_graph_solve:
+            L.ssf_graph_solve_default_params.argtypes = [C.POINTER(SsfGraphSolveParams)]
+            L.ssf_graph_get_edges.argtypes = [vp, vp, C.c_int]
+            L.ssf_graph_solve.argtypes = [vp, C.POINTER(SsfGraphSolveParams), vp, vp, vp, C.c_int, C.POINTER(SsfGraphSolveResult)]
+            L.ssf_graph_get_transforms.argtypes = [vp, vp, vp, C.c_int]
+            L.ssf_graph_apply_solved.argtypes = [vp]
         self.has_keyframes = all(hasattr(L, nm) for nm in KEYFRAME_SYMBOLS)
         if self.has_keyframes:
             ip, kp, kr = C.POINTER(C.c_int), C.POINTER(SsfKeyframesParams), C.POINTER(SsfKeyframeResult)
@@ -559,6 +590,64 @@ class Fusion:
         if R.size != 9 * m or t.size != 3 * m:
             raise SsfError("graph_apply: the graph has %d nodes; got %d rotation and %d translation floats" % (m, R.size, t.size))
         self._ck(self.L.lib.ssf_graph_apply(self.h, _ptr(R), _ptr(t)), "ssf_graph_apply")
+
+    # ---- the graph's optimisation (include/ssf_graph_solve.h) ----------------------------------------
+    def _need_graph_solve(self, symbol):
+        if not self.L.has_graph_solve:
+            raise SsfError("%s does not export %s: it does not solve the deformation graph (include/ssf_graph_solve.h, HIP product only)"
+                           % (self.L.path, symbol))
+
+    def graph_solve_default_params(self):
+        """ssf_graph_solve_default_params as a dict"""
+        self._need_graph_solve("ssf_graph_solve_default_params")
+        p = SsfGraphSolveParams()
+        rc = self.L.lib.ssf_graph_solve_default_params(C.byref(p))
+        if rc != 0:
+            raise SsfError("ssf_graph_solve_default_params failed (%d)" % rc)
+        return {nm: getattr(p, nm) for nm, _ in p._fields_}
+
+    def graph_edges(self, capacity=None):
+        """m x 4 i32: the four neighbours N(j) of every node (ssf_graph_get_edges)"""
+        self._need_graph_solve("ssf_graph_get_edges")
+        m = self.graph_info()["n_nodes"] if capacity is None else int(capacity)
+        e = np.empty((max(m, 0), 4), np.int32)
+        self._ck(self.L.lib.ssf_graph_get_edges(self.h, _ptr(e), m), "ssf_graph_get_edges")
+        return e[:self.graph_info()["n_nodes"]]
+
+    def graph_solve(self, src, t_init, dst, **params):
+        """Solve the node transforms that take the points src (n x 3 f32, birth stamps t_init n i32) to dst (ssf_graph_solve);
+        params override ssf_graph_solve_default_params.  Returns the result record as a dict; the transforms stay on the device
+        (graph_transforms, graph_apply_solved)."""
+        self._need_graph_solve("ssf_graph_solve")
+        p = SsfGraphSolveParams()
+        rc = self.L.lib.ssf_graph_solve_default_params(C.byref(p))
+        if rc != 0:
+            raise SsfError("ssf_graph_solve_default_params failed (%d)" % rc)
+        for k, v in params.items():
+            if k not in dict(p._fields_):
+                raise SsfError("graph_solve: unknown parameter %s" % k)
+            setattr(p, k, v)
+        s, d = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (src, dst))
+        t0 = np.ascontiguousarray(t_init, np.int32).ravel()
+        if len(t0) != len(s) or len(d) != len(s):
+            raise SsfError("graph_solve: %d sources, %d stamps, %d targets" % (len(s), len(t0), len(d)))
+        res = SsfGraphSolveResult()
+        self._ck(self.L.lib.ssf_graph_solve(self.h, C.byref(p), _ptr(s), _ptr(t0), _ptr(d), len(s), C.byref(res)), "ssf_graph_solve")
+        return res.as_dict()
+
+    def graph_transforms(self, capacity=None):
+        """(node_rotations m x 9 f32, node_translations m x 3 f32) of the last solve (ssf_graph_get_transforms)"""
+        self._need_graph_solve("ssf_graph_get_transforms")
+        m = self.graph_info()["n_nodes"] if capacity is None else int(capacity)
+        R, t = np.empty((max(m, 0), 9), np.float32), np.empty((max(m, 0), 3), np.float32)
+        self._ck(self.L.lib.ssf_graph_get_transforms(self.h, _ptr(R), _ptr(t), m), "ssf_graph_get_transforms")
+        k = self.graph_info()["n_nodes"]
+        return R[:k], t[:k]
+
+    def graph_apply_solved(self):
+        """Deform the model by the resident solved transforms (ssf_graph_apply_solved); the graph is stale afterwards"""
+        self._need_graph_solve("ssf_graph_apply_solved")
+        self._ck(self.L.lib.ssf_graph_apply_solved(self.h), "ssf_graph_apply_solved")
 
     # ---- whole frame -------------------------------------------------------------------------
     def process_frame(self, rgb, depth, prior_pose=None, dynamic_mask=None, pixel_mask=None):

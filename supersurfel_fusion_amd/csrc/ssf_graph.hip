@@ -18,6 +18,7 @@
 //   * bind   k_graph_bind / k_graph_bind_points: one thread per slot (or per caller point): lower bound over the records'
 //            stamps (from L2: 16 steps at 64 k nodes), then the window's records, the five smallest (bits(d2) << 32 | k) kept sorted in ten registers by a min / max
 //            chain, the weights, one 16-byte store each for weights4 and idx4 at the logical index.
+//   * edges  k_graph_edges: the same five nearest for every node itself, for the solve (ssf_graph_solve.hip).
 // No float atomics anywhere; every count is an integer.
 #include <climits>
 #include "ssf_slots.hpp"
@@ -144,16 +145,18 @@ __global__ __launch_bounds__(256) void k_graph_sample(ModelView mv, const uint32
 }
 
 // ---- bind: steps 1-6 of ssf_graph.h for one point ------------------------------------------------------------------------
-__device__ __forceinline__ void graph_bind_one(const float4* __restrict__ nodes, int m, int L, float px, float py, float pz, int t,
-                                               float4& w4, int4& i4) {
+// steps 1-4: the five smallest keys (bits(d2) << 32 | k) in ascending order, and the window's first node
+__device__ __forceinline__ void graph_nearest5(const float4* __restrict__ nodes, int m, int L, float px, float py, float pz, int t,
+                                               unsigned long long& k0, unsigned long long& k1, unsigned long long& k2,
+                                               unsigned long long& k3, unsigned long long& k4, int& lo) {
     int a = 0, b = m;                             // the first node whose stamp >= t
     while (a < b) {
         const int mid = (a + b) >> 1;
         if (__float_as_int(nodes[mid].w) < t) a = mid + 1; else b = mid;
     }
     const int W = min(m, 2 * L);
-    const int lo = max(0, min(a - L, max(0, m - 2 * L)));
-    unsigned long long k0 = ~0ull, k1 = ~0ull, k2 = ~0ull, k3 = ~0ull, k4 = ~0ull;
+    lo = max(0, min(a - L, max(0, m - 2 * L)));
+    k0 = k1 = k2 = k3 = k4 = ~0ull;
     for (int j = 0; j < W; j++) {
         const float4 g = nodes[lo + j];
         const float dx = px - g.x, dy = py - g.y, dz = pz - g.z;
@@ -165,6 +168,11 @@ __device__ __forceinline__ void graph_bind_one(const float4* __restrict__ nodes,
         lo_k = min(k3, x); x = max(k3, x); k3 = lo_k;
         k4 = min(k4, x);
     }
+}
+__device__ __forceinline__ void graph_bind_one(const float4* __restrict__ nodes, int m, int L, float px, float py, float pz, int t,
+                                               float4& w4, int4& i4) {
+    unsigned long long k0, k1, k2, k3, k4; int lo;
+    graph_nearest5(nodes, m, L, px, py, pz, t, k0, k1, k2, k3, k4, lo);
     i4 = make_int4((int)(uint32_t)k0, (int)(uint32_t)k1, (int)(uint32_t)k2, (int)(uint32_t)k3);
     const float e0 = sqrtf(__uint_as_float((uint32_t)(k0 >> 32))), e1 = sqrtf(__uint_as_float((uint32_t)(k1 >> 32)));
     const float e2 = sqrtf(__uint_as_float((uint32_t)(k2 >> 32))), e3 = sqrtf(__uint_as_float((uint32_t)(k3 >> 32)));
@@ -206,6 +214,19 @@ __global__ __launch_bounds__(256) void k_graph_bind_points(const float* __restri
     w4[p] = w; i4[p] = i;
 }
 
+// the solve's edges (ssf_graph_solve.h): node j's own steps 1-4, then the first four of k_0 ... k_4 that are not j
+__global__ __launch_bounds__(256) void k_graph_edges(const float4* __restrict__ nodes, int m, int L, int4* __restrict__ edges) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const float4 g = nodes[j];
+    unsigned long long k0, k1, k2, k3, k4; int lo;
+    graph_nearest5(nodes, m, L, g.x, g.y, g.z, __float_as_int(g.w), k0, k1, k2, k3, k4, lo);
+    const int a = (int)(uint32_t)k0, b = (int)(uint32_t)k1, c = (int)(uint32_t)k2, d = (int)(uint32_t)k3, e = (int)(uint32_t)k4;
+    // (the five are distinct: at most one is j, and everything after it moves up by one)
+    edges[j] = make_int4(a == j ? b : a, (a == j || b == j) ? c : b, (a == j || b == j || c == j) ? d : c,
+                         (a == j || b == j || c == j || d == j) ? e : d);
+}
+
 // ---- launches ----------------------------------------------------------------------------------------------------------
 // stamp[nslots], elig[nslots]; bc[nbo + 1] = exclusive scan of the out-of-view blocks' live counts; mm[4] (preset INT_MAX, INT_MIN,
 // 0, 0) = min / max stamp of the eligible rows, their number, the live rows
@@ -216,9 +237,11 @@ static void launch_graph_keys(hipStream_t st, const ModelView& mv, float min_con
 }
 // stable sort of the eligible slots by (stamp - lo), `passes` 8-bit digits; cnt[256 ceil(nslots / GRAPH_SORT_ITEMS) + 1]; returns
 // which of the pairs (key_a, slot_a) = 0 / (key_b, slot_b) = 1 holds the n_elig sorted (stamp, slot) entries
-static int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes, const int32_t* stamp, const uint8_t* elig,
-                             uint32_t* cnt, int32_t* key_a, uint32_t* slot_a, int32_t* key_b, uint32_t* slot_b) {
-    ScopedKernel sk("graph_rank", st);
+// (any int32 key with key - lo below 2^(8 passes); elig == nullptr: every item takes part and n_elig == nslots.  The solve's two
+// transposed lists use it with lo = 0 and keys below 2^20, booked under their own name)
+int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes, const int32_t* stamp, const uint8_t* elig,
+                      uint32_t* cnt, int32_t* key_a, uint32_t* slot_a, int32_t* key_b, uint32_t* slot_b, const char* name) {
+    ScopedKernel sk(name, st);
     const int32_t* kin = stamp; const uint32_t* sin = nullptr; const uint8_t* el = elig;
     int n = nslots, out = 0;
     for (int p = 0; p < passes; p++) {
@@ -242,9 +265,13 @@ static void launch_graph_bind(hipStream_t st, const ModelView& mv, const uint32_
     hipLaunchKernelGGL(k_graph_bind, dim3(mv.nbv + mv.nbo), dim3(256), 0, st, mv, bc, nodes, m, look, reinterpret_cast<float4*>(w4),
                        reinterpret_cast<int4*>(i4));
 }
-static void launch_graph_bind_points(hipStream_t st, const float* pts, const int32_t* t0, int n, const float4* nodes, int m, int look,
-                                     float* w4, int32_t* i4) {
-    ScopedKernel sk("graph_bind", st);
+void launch_graph_edges(hipStream_t st, const float4* nodes, int m, int look, int32_t* edges, const char* name) {
+    ScopedKernel sk(name, st);
+    hipLaunchKernelGGL(k_graph_edges, dim3((m + 255) / 256), dim3(256), 0, st, nodes, m, look, reinterpret_cast<int4*>(edges));
+}
+void launch_graph_bind_points(hipStream_t st, const float* pts, const int32_t* t0, int n, const float4* nodes, int m, int look,
+                              float* w4, int32_t* i4, const char* name) {
+    ScopedKernel sk(name, st);
     hipLaunchKernelGGL(k_graph_bind_points, dim3((n + 255) / 256), dim3(256), 0, st, pts, t0, n, nodes, m, look,
                        reinterpret_cast<float4*>(w4), reinterpret_cast<int4*>(i4));
 }
@@ -259,13 +286,15 @@ int ssf_graph_default_params(ssf_graph_params* p) {
     return SSF_OK;
 }
 static bool graph_valid(const ssf_handle* h) { return h->graph.built && h->graph.gen == h->model_gen; }
-// the refusals every call that uses the resident graph shares
-static int graph_usable(ssf_handle* h, const char* who) {
+}  // extern "C"
+// the refusals every call that uses the resident graph shares (ssf_graph_solve.hip's too)
+int ssf::graph_usable(ssf_handle* h, const char* who) {
     { int rc = model_at_rest(h, who, "has no deformation graph"); if (rc) return rc; }
     if (!h->graph.built) { h->err = std::string(who) + ": no graph has been built (ssf_graph_build)"; return SSF_ERR_STATE; }
     if (!graph_valid(h)) { h->err = std::string(who) + ": graph is stale: build it again"; return SSF_ERR_STATE; }
     return SSF_OK;
 }
+extern "C" {
 int ssf_graph_build(ssf_handle* h, const ssf_graph_params* p, int* n_nodes) {
     if (!h || !p) return SSF_ERR_INVALID_ARG;
     if (p->stride < 1 || p->look < 3 || !std::isfinite(p->min_conf)) {
@@ -274,6 +303,7 @@ int ssf_graph_build(ssf_handle* h, const ssf_graph_params* p, int* n_nodes) {
     { int rc = model_at_rest(h, "ssf_graph_build", "has no deformation graph"); if (rc) return rc; }
     GraphWs& g = h->graph;
     g.built = false;                              // whatever happens below, no half-built graph is kept
+    h->solve.solved = false;                      // (solved transforms die with the graph they belong to)
     if (h->n_model <= 0) { h->err = "ssf_graph_build: the model is empty"; return SSF_ERR_STATE; }
 
     const ModelView mv = model_view(h, false);
@@ -320,7 +350,7 @@ int ssf_graph_build(ssf_handle* h, const ssf_graph_params* p, int* n_nodes) {
         g.node_cap = cap;
     }
     const int passes = span < 256 ? 1 : span < 65536 ? 2 : 3;
-    const int which = launch_graph_sort(st, mv.nslots, n_elig, mm[0], passes, g.stamp, g.elig, g.cnt, g.key_a, g.slot_a, g.key_b, g.slot_b);
+    const int which = launch_graph_sort(st, mv.nslots, n_elig, mm[0], passes, g.stamp, g.elig, g.cnt, g.key_a, g.slot_a, g.key_b, g.slot_b, "graph_rank");
     HCK(hipGetLastError());
     launch_graph_sample(st, mv, g.bc, which == 0 ? g.slot_a : g.slot_b, m, p->stride, g.nodes, g.npos3, g.nrow);
     HCK(hipGetLastError());
@@ -374,7 +404,7 @@ int ssf_graph_bind_points(ssf_handle* h, const float* points, const int32_t* t_i
     hipStream_t st = h->stream;
     HCK(hipMemcpyAsync(d_p, points, 12 * (size_t)n, hipMemcpyHostToDevice, st));
     HCK(hipMemcpyAsync(d_t, t_init, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-    { TimerScope ts(h); launch_graph_bind_points(st, d_p, d_t, n, g.nodes, g.m, g.look, d_w, d_i); }
+    { TimerScope ts(h); launch_graph_bind_points(st, d_p, d_t, n, g.nodes, g.m, g.look, d_w, d_i, "graph_bind"); }
     HCK(hipGetLastError());
     HCK(hipMemcpyAsync(weights4, d_w, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
     HCK(hipMemcpyAsync(idx4, d_i, 16 * (size_t)n, hipMemcpyDeviceToHost, st));

@@ -1,6 +1,6 @@
 // ssf_handle.hpp -- the handle (ssf_handle, the types it holds by value, HCK) and the few host helpers that the entry points
 // outside ssf_host.hip call.  Private to the library's host code: included by ssf_host.hip (the core ABI, where the helpers are
-// defined) and by ssf_render.hip, ssf_graph.hip and ssf_keyframes.hip, whose entry points sit next to their kernels.  Nothing
+// defined) and by ssf_render.hip, ssf_graph.hip, ssf_graph_solve.hip and ssf_keyframes.hip, whose entry points sit next to their kernels.  Nothing
 // here is part of the frame path's device interface (ssf_device.hpp).
 #pragma once
 #include <algorithm>
@@ -16,6 +16,7 @@
 #include "ssf_device.hpp"
 #include "../../include/ssf_render.h"
 #include "../../include/ssf_graph.h"
+#include "../../include/ssf_graph_solve.h"
 #include "../../include/ssf_keyframes.h"
 
 struct ncclComm; typedef struct ncclComm* ncclComm_t;      // (as <rccl/rccl.h> declares it: the handle only holds communicators)
@@ -168,6 +169,24 @@ struct GraphWs {
     float4* nodes = nullptr; float* npos3 = nullptr; int32_t* nrow = nullptr; size_t node_cap = 0;   // per node, in time order
     int m = 0, rows = 0, look = 0; bool built = false; unsigned long long gen = 0;          // valid <=> built && gen == h->model_gen
 };
+// ssf_graph_solve (ssf_graph_solve.h): the solver's vectors (f64, 12 per node), the residual-space vectors, the two transposed
+// lists and the solved transforms.  Allocated on first use; each group (per node / per constraint) is grown as a whole or not at
+// all (DevBufs::grow).  Nothing here is read or written by the frame path.
+struct SolveWs {
+    DevBufs bufs;
+    // per node
+    int32_t* edges = nullptr; uint32_t* in_off = nullptr; uint32_t* con_off = nullptr;
+    double *x = nullptr, *b = nullptr, *D = nullptr, *delta = nullptr, *r = nullptr, *z = nullptr, *p0 = nullptr, *p1 = nullptr, *q = nullptr;
+    double *y_rot = nullptr, *y_reg = nullptr;                       // 6 / 12 per node: residuals, then J p
+    double* part = nullptr;                                          // block partials: see ssf_graph_solve.hip
+    float *rot = nullptr, *trans = nullptr; size_t node_cap = 0;
+    // per constraint
+    float *src = nullptr, *dst = nullptr, *w4 = nullptr; int32_t *t0 = nullptr, *idx4 = nullptr; double *y_con = nullptr, *e_con = nullptr; size_t con_cap = 0;
+    // the counting sorts' working set, for max(4 m, 4 n_con) items
+    int32_t *key_a = nullptr, *key_b = nullptr; uint32_t *slot_a = nullptr, *slot_b = nullptr, *cnt = nullptr, *in_list = nullptr, *con_list = nullptr;
+    size_t item_cap = 0;
+    bool solved = false; unsigned long long gen = 0;                 // the transforms belong to the graph of that generation
+};
 // the keyframe database of ssf_keyframes.h: everything is allocated by ssf_keyframes_configure, as a whole or not at all
 // (DevBufs::grow), and freed by ssf_keyframes_clear / ssf_destroy.  The host mirrors what it needs to address a keyframe (its
 // first pool row, row count, stamp, pose); codes, stamps and rows live on the device.
@@ -274,6 +293,7 @@ struct ssf_handle {
     RenderWs render;                              // ssf_render_model (ssf_render.h)
     GraphWs graph;                                // ssf_graph_* (ssf_graph.h)
     KeyframeWs kf;                                // ssf_keyframes_* (ssf_keyframes.h)
+    SolveWs solve;                                // ssf_graph_solve (ssf_graph_solve.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense)
 };
 
@@ -323,6 +343,14 @@ int align_loop(ssf_handle* h, const float* d_pos, const float* d_lab, const floa
                const float* init_pose, float* rel_pose, int* valid, int* iters, int* pairs_last);
 int deform_dense(ssf_handle* h, int m, const float* d_np, const float* d_nr, const float* d_nt, float* d_nodes, const float* d_w,
                  const int32_t* d_i);
+// ssf_graph.hip's pieces that ssf_graph_solve.hip uses: the refusals of a call on the resident graph, node j's four neighbours,
+// the binding of device points, and the stable counting sort (returns which pair, a = 0 / b = 1, holds the sorted list)
+int graph_usable(ssf_handle* h, const char* who);
+void launch_graph_edges(hipStream_t st, const float4* nodes, int m, int look, int32_t* edges, const char* name);
+void launch_graph_bind_points(hipStream_t st, const float* pts, const int32_t* t0, int n, const float4* nodes, int m, int look,
+                              float* w4, int32_t* i4, const char* name);
+int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes, const int32_t* stamp, const uint8_t* elig,
+                      uint32_t* cnt, int32_t* key_a, uint32_t* slot_a, int32_t* key_b, uint32_t* slot_b, const char* name);
 // rows [s0, s0 + n) of src -> rows [d0, d0 + n) of dst on the handle's stream (enqueued only); a NULL array of dst is skipped
 int copy_rows(ssf_handle* h, const ssf_surfels& dst, size_t d0, const ssf_surfels& src, size_t s0, size_t n, hipMemcpyKind kind);
 }  // namespace ssf
