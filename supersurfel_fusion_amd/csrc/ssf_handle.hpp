@@ -1,7 +1,7 @@
 // ssf_handle.hpp -- the handle (ssf_handle, the types it holds by value, HCK) and the few host helpers that the entry points
 // outside ssf_host.hip call.  Private to the library's host code: included by ssf_host.hip (the core ABI, where the helpers are
-// defined) and by ssf_render.hip, ssf_graph.hip, ssf_graph_solve.hip and ssf_keyframes.hip, whose entry points sit next to their kernels.  Nothing
-// here is part of the frame path's device interface (ssf_device.hpp).
+// defined), by ssf_render.hip, ssf_graph.hip, ssf_graph_solve.hip and ssf_keyframes.hip, whose entry points sit next to their kernels,
+// and through ssf_exchange.hpp by ssf_exchange.hip.  Nothing here is part of the frame path's device interface (ssf_device.hpp).
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -306,7 +306,7 @@ struct ssf_handle {
         }                                                                                            \
     } while (0)
 
-// ---- helpers of ssf_host.hip that the render, graph and keyframe entry points call -------------------------------------------
+// ---- helpers of ssf_host.hip that the render, graph, keyframe and exchange entry points call ----------------------------------
 #pragma GCC visibility push(hidden)       // (shared by the library's own files, no part of what it exports)
 namespace ssf {
 // device temporaries of one call: freed on every exit path
@@ -332,6 +332,14 @@ int model_at_rest(ssf_handle* h, const char* who = nullptr, const char* lacks = 
 int materialise(ssf_handle* h);
 int store_from_dense(ssf_handle* h, int n, int n_visible);
 void drop_shard_sizes(ssf_handle* h);
+// for ssf_exchange.hip: ssf_last_error(NULL)'s text, a buffer the handle owns, the wait for a mailbox word, row views and copies.
+// dalloc is defined in ssf_host.hip, which instantiates it for that file (<int>): another element type there needs its own line.
+void set_create_error(const char* what);
+template <typename T> bool dalloc(ssf_handle* h, T** p, size_t count);
+int wait_seq(ssf_handle* h, const volatile unsigned long long* word, unsigned long long want);
+SurfelSoA soa_rows(const SurfelSoA& s, size_t r);
+int copy_soa(ssf_handle* h, const SurfelSoA& d, const SurfelSoA& s, size_t n);
+inline P2PView p2p_view(ssf_handle* h, unsigned long long seq) { P2PView v = h->p2p.view; v.seq = seq; return v; }
 inline Rt pose_from12(const float* p) {
     Rt r; r.R = m3(v3(p[0], p[1], p[2]), v3(p[3], p[4], p[5]), v3(p[6], p[7], p[8])); r.t = v3(p[9], p[10], p[11]); return r;
 }

@@ -2,14 +2,14 @@
 // (the C++ counterpart of SupersurfelFusion::processFrame, core/src/supersurfel_fusion.cu:166-530,
 // hot-path parts only): extract contexts (pipelined / batched extract on their own streams and graphs),
 // the track chain (ICP loop with the host Gauss-Newton step of core/src/dense_registration.cu:324-421,
-// association, fusion, model-store upkeep), the RCCL exchanges of the multi-GPU mode, the loop-closure
-// registration, and the C ABI of include/ssf.h.  The handle itself and the helpers shared with the entry points of ssf_render.h,
-// ssf_graph.h and ssf_keyframes.h -- which sit next to their kernels in ssf_render.hip, ssf_graph.hip, ssf_keyframes.hip -- are
-// declared in ssf_handle.hpp.
+// association, fusion, model-store upkeep) with its exchanges in the multi-GPU mode, the loop-closure
+// registration, and the core of the C ABI of include/ssf.h: the handle's life cycle, the frame entry points, the stage seams, the
+// getters.  The handle and the helpers shared with the library's other host files are declared in ssf_handle.hpp: the entry points of
+// ssf_render.h, ssf_graph*.h and ssf_keyframes.h sit next to their kernels, attaching an exchange and re-homing a sharded map are in
+// ssf_exchange.hip, the host solvers in ssf_solvers.hpp, the hooks of ssf_testing.h in ssf_testing.hip.
 //
 // There is NO CPU fallback here: without a gfx950 device ssf_create fails with SSF_ERR_NO_DEVICE.
 #include <atomic>
-#include <cfloat>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -18,10 +18,9 @@
 #include <mutex>
 #include <thread>
 #include <type_traits>
-#include <dlfcn.h>
 #include <unistd.h>
-#include <rccl/rccl.h>          // types only: the library is resolved at run time (dlopen), never linked
-#include "ssf_handle.hpp"          // (the handle; with it ssf_device.hpp, include/ssf*.h and the containers it holds)
+#include "ssf_exchange.hpp"          // (RcclApi, NCK; with it ssf_handle.hpp: the handle, ssf_device.hpp, include/ssf*.h and the containers it holds)
+#include "ssf_solvers.hpp"
 
 using namespace ssf;
 
@@ -69,221 +68,6 @@ TimerScope::TimerScope(ssf_handle* hh) : h(hh) {
 }
 TimerScope::~TimerScope() { set_current_timer(nullptr); }
 }  // namespace ssf
-
-// ---- host solvers: dependency-free counterparts of the reference's Eigen calls ---------------------
-// (LDLT with diagonal pivoting as Eigen::LDLT, partial-pivot LU inverse, Shoemake quaternion
-// re-normalisation, Rodrigues rotation; pinned against the reference's vendored Eigen by
-// tests/test_solvers.py through the ssf_dbg_* exports below.)
-namespace {
-
-void sym6_ldlt_solve(const double* A, const double* b, double* x) {
-    const int n = 6;
-    double L[36]; int piv[6]; double w[6];
-    std::memcpy(L, A, sizeof(L));
-    bool all_zero = false;
-    for (int k = 0; k < n; k++) {
-        int p = k; double pm = std::fabs(L[k * n + k]);
-        for (int i = k + 1; i < n; i++) if (std::fabs(L[i * n + i]) > pm) { pm = std::fabs(L[i * n + i]); p = i; }
-        piv[k] = p;
-        if (p != k) {                       // symmetric row/column exchange on the lower triangle
-            for (int j = 0; j < k; j++) std::swap(L[k * n + j], L[p * n + j]);
-            for (int i = p + 1; i < n; i++) std::swap(L[i * n + k], L[i * n + p]);
-            std::swap(L[k * n + k], L[p * n + p]);
-            for (int i = k + 1; i < p; i++) std::swap(L[i * n + k], L[p * n + i]);
-        }
-        if (k > 0) {
-            for (int j = 0; j < k; j++) w[j] = L[j * n + j] * L[k * n + j];
-            double s = 0.0;
-            for (int j = 0; j < k; j++) s += L[k * n + j] * w[j];
-            L[k * n + k] -= s;
-            for (int i = k + 1; i < n; i++) {
-                double s2 = 0.0;
-                for (int j = 0; j < k; j++) s2 += L[i * n + j] * w[j];
-                L[i * n + k] -= s2;
-            }
-        }
-        const double d = L[k * n + k];
-        const bool ok = std::fabs(d) > 0.0;
-        if (k == 0 && !ok) { for (int j = 0; j < n; j++) piv[j] = j; all_zero = true; break; }
-        if (ok) for (int i = k + 1; i < n; i++) L[i * n + k] /= d;
-    }
-    double y[6];
-    for (int i = 0; i < n; i++) y[i] = b[i];
-    for (int k = 0; k < n; k++) std::swap(y[k], y[piv[k]]);
-    if (!all_zero) for (int i = 0; i < n; i++) for (int j = 0; j < i; j++) y[i] -= L[i * n + j] * y[j];
-    for (int i = 0; i < n; i++) { const double d = L[i * n + i]; y[i] = (std::fabs(d) > DBL_MIN) ? y[i] / d : 0.0; }
-    if (!all_zero) for (int i = n - 1; i >= 0; i--) for (int j = i + 1; j < n; j++) y[i] -= L[j * n + i] * y[j];
-    for (int k = n - 1; k >= 0; k--) std::swap(y[k], y[piv[k]]);
-    for (int i = 0; i < n; i++) x[i] = y[i];
-}
-
-void mat6_inverse_lu(const double* A, double* Ainv) {
-    const int n = 6;
-    double U[36]; int perm[6];
-    std::memcpy(U, A, sizeof(U));
-    for (int i = 0; i < n; i++) perm[i] = i;
-    for (int k = 0; k < n; k++) {
-        int p = k; double pm = std::fabs(U[k * n + k]);
-        for (int i = k + 1; i < n; i++) if (std::fabs(U[i * n + k]) > pm) { pm = std::fabs(U[i * n + k]); p = i; }
-        if (p != k) { for (int j = 0; j < n; j++) std::swap(U[k * n + j], U[p * n + j]); std::swap(perm[k], perm[p]); }
-        for (int i = k + 1; i < n; i++) {
-            U[i * n + k] /= U[k * n + k];
-            for (int j = k + 1; j < n; j++) U[i * n + j] -= U[i * n + k] * U[k * n + j];
-        }
-    }
-    for (int c = 0; c < n; c++) {
-        double y[6];
-        for (int i = 0; i < n; i++) y[i] = (perm[i] == c) ? 1.0 : 0.0;
-        for (int i = 0; i < n; i++) for (int j = 0; j < i; j++) y[i] -= U[i * n + j] * y[j];
-        for (int i = n - 1; i >= 0; i--) { for (int j = i + 1; j < n; j++) y[i] -= U[i * n + j] * y[j]; y[i] /= U[i * n + i]; }
-        for (int i = 0; i < n; i++) Ainv[i * n + c] = y[i];
-    }
-}
-
-template <typename T>
-void renormalise_rotation(T* R) {       // Quaternion(R).normalized().toRotationMatrix()
-    T q[4];
-    T t = (R[0] + R[4]) + R[8];
-    if (t > T(0)) {
-        t = std::sqrt(t + T(1.0)); q[3] = T(0.5) * t; t = T(0.5) / t;
-        q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
-    } else {
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > R[i * 4]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = std::sqrt(((R[i * 4] - R[j * 4]) - R[k * 4]) + T(1.0));
-        q[i] = T(0.5) * t; t = T(0.5) / t;
-        q[3] = (R[k * 3 + j] - R[j * 3 + k]) * t;
-        q[j] = (R[j * 3 + i] + R[i * 3 + j]) * t;
-        q[k] = (R[k * 3 + i] + R[i * 3 + k]) * t;
-    }
-    const T z = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
-    if (z > T(0)) { const T nrm = std::sqrt(z); for (int a = 0; a < 4; a++) q[a] = q[a] / nrm; }
-    const T tx = T(2) * q[0], ty = T(2) * q[1], tz = T(2) * q[2];
-    const T twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const T txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const T tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0] = T(1) - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = T(1) - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = T(1) - (txx + tyy);
-}
-
-void rodrigues(double angle, const double* ax, double* R) {     // AngleAxisd::toRotationMatrix
-    const double s = std::sin(angle), c = std::cos(angle);
-    const double sx = s * ax[0], sy = s * ax[1], sz = s * ax[2];
-    const double ox = (1.0 - c) * ax[0], oy = (1.0 - c) * ax[1], oz = (1.0 - c) * ax[2];
-    double m;
-    m = ox * ax[1]; R[1] = m - sz; R[3] = m + sz;
-    m = ox * ax[2]; R[2] = m + sy; R[6] = m - sy;
-    m = oy * ax[2]; R[5] = m - sx; R[7] = m + sx;
-    R[0] = ox * ax[0] + c; R[4] = oy * ax[1] + c; R[8] = oz * ax[2] + c;
-}
-
-// one Gauss-Newton increment from the solved 6-vector: tf_iter (4x4, row-major)
-void gn_increment(const double* X, double* tf_iter) {
-    double tran[3] = {X[3], X[4], X[5]}, axis[3] = {X[0], X[1], X[2]};
-    const double nrm = std::sqrt((axis[0] * axis[0] + axis[1] * axis[1]) + axis[2] * axis[2]);
-    const double angle = 0.5 * std::atan(nrm);
-    double Rr[9];
-    if (nrm == 0.0) { for (int i = 0; i < 9; i++) Rr[i] = (i % 4 == 0) ? 1.0 : 0.0; }
-    else { for (int i = 0; i < 3; i++) axis[i] /= nrm; rodrigues(angle, axis, Rr); }
-    const double ca = std::cos(angle);
-    for (int i = 0; i < 3; i++) tran[i] *= ca;
-    for (int i = 0; i < 16; i++) tf_iter[i] = 0.0;
-    double R9[9];
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) R9[i * 3 + j] = (Rr[i * 3] * Rr[j] + Rr[i * 3 + 1] * Rr[3 + j]) + Rr[i * 3 + 2] * Rr[6 + j];
-        tf_iter[i * 4 + 3] = (Rr[i * 3] * tran[0] + Rr[i * 3 + 1] * tran[1]) + Rr[i * 3 + 2] * tran[2];
-    }
-    renormalise_rotation<double>(R9);
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) tf_iter[i * 4 + j] = R9[i * 3 + j];
-    tf_iter[15] = 1.0;
-}
-
-// host step of one align iteration (DenseRegistration::align, dense_registration.cu:168-210): as gn_increment, with
-// the translation un-scaled and the increment conjugated by the centroid translations:
-// T(ct) * Rot * T(tran) * Rot * T(-cs), Eigen Isometry products left to right
-void align_increment(const double* JtJ, const double* Jtr, float scale, const float* cs, const float* ct, double* tf_iter) {
-    double X[6];
-    sym6_ldlt_solve(JtJ, Jtr, X);
-    double tran[3] = {X[3], X[4], X[5]}, axis[3] = {X[0], X[1], X[2]};
-    const double nrm = std::sqrt((axis[0] * axis[0] + axis[1] * axis[1]) + axis[2] * axis[2]);
-    const double angle = 0.5 * std::atan(nrm);
-    double Rr[9];
-    if (nrm == 0.0) { for (int i = 0; i < 9; i++) Rr[i] = (i % 4 == 0) ? 1.0 : 0.0; }
-    else { for (int i = 0; i < 3; i++) axis[i] /= nrm; rodrigues(angle, axis, Rr); }
-    const double ca = std::cos(angle);
-    for (int i = 0; i < 3; i++) { tran[i] /= (double)scale; tran[i] *= ca; }
-    double RR[9], t2[3], t4[3];
-    for (int i = 0; i < 3; i++) {
-        t2[i] = ((Rr[i * 3] * tran[0] + Rr[i * 3 + 1] * tran[1]) + Rr[i * 3 + 2] * tran[2]) + (double)ct[i];
-        for (int j = 0; j < 3; j++) RR[i * 3 + j] = (Rr[i * 3] * Rr[j] + Rr[i * 3 + 1] * Rr[3 + j]) + Rr[i * 3 + 2] * Rr[6 + j];
-    }
-    const double ncs[3] = {-1.0 * (double)cs[0], -1.0 * (double)cs[1], -1.0 * (double)cs[2]};
-    for (int i = 0; i < 3; i++) t4[i] = ((RR[i * 3] * ncs[0] + RR[i * 3 + 1] * ncs[1]) + RR[i * 3 + 2] * ncs[2]) + t2[i];
-    renormalise_rotation<double>(RR);
-    for (int i = 0; i < 16; i++) tf_iter[i] = 0.0;
-    for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) tf_iter[i * 4 + j] = RR[i * 3 + j]; tf_iter[i * 4 + 3] = t4[i]; }
-    tf_iter[15] = 1.0;
-}
-
-void mat4_lmul(const double* a, double* b) {      // b <- a * b
-    double r[16];
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++)
-            r[i * 4 + j] = ((a[i * 4] * b[j] + a[i * 4 + 1] * b[4 + j]) + a[i * 4 + 2] * b[8 + j]) + a[i * 4 + 3] * b[12 + j];
-    std::memcpy(b, r, sizeof(r));
-}
-
-}  // namespace
-
-// ---- RCCL, resolved at run time -------------------------------------------------------------------------
-// The multi-GPU exchanges (ssf_comm_attach) call RCCL directly on the track stream.  The symbols come from
-// the librccl the process already holds (torch ships one, SONAME librccl.so.1) or from /opt/rocm; a box
-// without RCCL still loads libssf_hip.so and runs single-GPU.
-struct RcclApi {
-    void* lib = nullptr;
-    decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-    decltype(&ncclCommInitRank) CommInitRank = nullptr;
-    decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclAllReduce) AllReduce = nullptr;
-    decltype(&ncclAllGather) AllGather = nullptr;
-    decltype(&ncclGetErrorString) GetErrorString = nullptr;
-    decltype(&ncclCommCount) CommCount = nullptr;
-    decltype(&ncclCommUserRank) CommUserRank = nullptr;
-    decltype(&ncclBroadcast) Broadcast = nullptr;           // the three below: only the dealt extract stage needs them (ssf_comm_deal_extract)
-    decltype(&ncclCommSplit) CommSplit = nullptr;
-    decltype(&ncclGroupStart) GroupStart = nullptr;
-    decltype(&ncclGroupEnd) GroupEnd = nullptr;
-    std::string err;
-};
-static RcclApi* rccl_api() {
-    static RcclApi api;
-    static bool tried = false;
-    if (tried) return api.lib ? &api : nullptr;
-    tried = true;
-    const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    for (const char* n : names) { api.lib = dlopen(n, RTLD_NOW | RTLD_NOLOAD); if (api.lib) break; }   // already in the process?
-    if (!api.lib) for (const char* n : names) { api.lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL); if (api.lib) break; }
-    if (!api.lib) { api.err = "librccl.so.1 not found"; return nullptr; }
-    api.GetUniqueId = (decltype(api.GetUniqueId))dlsym(api.lib, "ncclGetUniqueId");
-    api.CommInitRank = (decltype(api.CommInitRank))dlsym(api.lib, "ncclCommInitRank");
-    api.CommDestroy = (decltype(api.CommDestroy))dlsym(api.lib, "ncclCommDestroy");
-    api.AllReduce = (decltype(api.AllReduce))dlsym(api.lib, "ncclAllReduce");
-    api.AllGather = (decltype(api.AllGather))dlsym(api.lib, "ncclAllGather");
-    api.GetErrorString = (decltype(api.GetErrorString))dlsym(api.lib, "ncclGetErrorString");
-    api.CommCount = (decltype(api.CommCount))dlsym(api.lib, "ncclCommCount");
-    api.CommUserRank = (decltype(api.CommUserRank))dlsym(api.lib, "ncclCommUserRank");
-    api.Broadcast = (decltype(api.Broadcast))dlsym(api.lib, "ncclBroadcast");
-    api.CommSplit = (decltype(api.CommSplit))dlsym(api.lib, "ncclCommSplit");
-    api.GroupStart = (decltype(api.GroupStart))dlsym(api.lib, "ncclGroupStart");
-    api.GroupEnd = (decltype(api.GroupEnd))dlsym(api.lib, "ncclGroupEnd");
-    if (!api.GetUniqueId || !api.CommInitRank || !api.CommDestroy || !api.AllReduce || !api.AllGather) {
-        api.err = "librccl lacks a required symbol"; api.lib = nullptr; return nullptr;
-    }
-    return &api;
-}
 
 static inline double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // ---- upload of host frames ahead of the pipeline (ssf_process_sequence with host buffers) --------------------------
@@ -460,20 +244,12 @@ struct StreamPool {
 static StreamPool& stream_pool() { static StreamPool* p = new StreamPool(); return *p; }      // (never destroyed: the runtime may be gone by then)
 
 static std::string g_create_err;
-
-#define NCK(call)                                                                                    \
-    do {                                                                                             \
-        ncclResult_t r_ = (call);                                                                    \
-        if (r_ != ncclSuccess) {                                                                     \
-            RcclApi* a_ = rccl_api();                                                                \
-            h->err = std::string(#call) + ": " + ((a_ && a_->GetErrorString) ? a_->GetErrorString(r_) : "RCCL error"); \
-            return SSF_ERR_DEVICE;                                                                   \
-        }                                                                                            \
-    } while (0)
+namespace ssf {
+void set_create_error(const char* what) { g_create_err = what; }
 
 // Wait until the device has published sequence number `want` into the host-mapped mailbox word.
 // Bounded: falls back to a stream synchronise (and reports a device error) after ~5 s.
-static int wait_seq(ssf_handle* h, const volatile unsigned long long* word, unsigned long long want) {
+int wait_seq(ssf_handle* h, const volatile unsigned long long* word, unsigned long long want) {
     const auto t0 = std::chrono::steady_clock::now();
     unsigned long long spins = 0;
     while (__atomic_load_n(word, __ATOMIC_ACQUIRE) != want) {
@@ -493,7 +269,7 @@ static int wait_seq(ssf_handle* h, const volatile unsigned long long* word, unsi
 }
 
 template <typename T>
-static bool dalloc(ssf_handle* h, T** p, size_t count) {
+bool dalloc(ssf_handle* h, T** p, size_t count) {
     void* q = nullptr;
     // (SSF_ALLOC_GUARD=bytes: that much unused memory on both sides of every buffer -- a probe for out-of-bounds accesses
     // between the small buffers of handles that live side by side, tools/p2p_first_frame_stress.py)
@@ -512,6 +288,8 @@ static bool dalloc(ssf_handle* h, T** p, size_t count) {
     *p = (T*)((char*)q + guard);
     return true;
 }
+template bool dalloc<int>(ssf_handle*, int**, size_t);          // (ssf_exchange.hip's one allocation: the shard sizes of all ranks)
+}  // namespace ssf
 static void check_guards(ssf_handle* h) {
     int idx = 0;
     for (auto& g : h->guarded) {
@@ -693,6 +471,10 @@ static bool device_input_aligned(ssf_handle* h, const void* rgb, const void* dep
     }
     return true;
 }
+// what every entry point that takes a frame asks of its arguments first (false: SSF_ERR_INVALID_ARG)
+static bool frame_args_ok(ssf_handle* h, const void* rgb, const void* depth, int on_device) {
+    return h && rgb && depth && (!on_device || device_input_aligned(h, rgb, depth));
+}
 // Add one frame to the open batch; the batch is launched when it is full (or when its first frame is needed).
 // pixmask: the frame's pixel mask (ssf_dynamic.h), P bytes, a device pointer when pixmask_on_device, NULL = none.
 static int submit_extract(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask,
@@ -829,6 +611,8 @@ static int seq_submit(ssf_handle* h) {
     return rc;
 }
 static int do_extract(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask, const uint8_t* pixmask = nullptr) {
+    if (!frame_args_ok(h, rgb, depth, on_device)) return SSF_ERR_INVALID_ARG;
+    TimerScope ts(h);
     if (!h->pending.empty()) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
     int rc = retire_active(h);
     if (!rc) rc = submit_extract(h, rgb, depth, on_device, mask, pixmask, on_device);
@@ -983,12 +767,13 @@ static void icp_end(ssf_handle* h, int* valid) {
 }
 
 // ---- model store upkeep -----------------------------------------------------------------------------------
-static SurfelSoA soa_rows(const SurfelSoA& s, size_t r) {       // view starting at row r
+namespace ssf {
+SurfelSoA soa_rows(const SurfelSoA& s, size_t r) {       // view starting at row r
     SurfelSoA v = s;
     each_stream([&](auto m, size_t w) { v.*m += w * r; });
     return v;
 }
-static int copy_soa(ssf_handle* h, const SurfelSoA& d, const SurfelSoA& s, size_t n) {      // device -> device, n rows
+int copy_soa(ssf_handle* h, const SurfelSoA& d, const SurfelSoA& s, size_t n) {      // device -> device, n rows
     if (n == 0) return SSF_OK;
     hipError_t copy_of_a_stream = hipSuccess;                   // (the first failure ends the copies)
     each_stream([&](auto m, size_t w) { if (!copy_of_a_stream) copy_of_a_stream = hipMemcpyAsync(d.*m, s.*m, 4 * w * n, hipMemcpyDeviceToDevice, h->stream); });
@@ -1007,7 +792,6 @@ static int oov_recentre(ssf_handle* h) {
     h->n_recentres++;
     return SSF_OK;
 }
-namespace ssf {
 // dense [visible | out-of-view] copy of the model in h->dense (stream ordered)
 int materialise(ssf_handle* h) {
     int rc = copy_soa(h, h->dense, h->model[h->mcur], (size_t)h->n_visible);
@@ -1048,7 +832,6 @@ int store_from_dense(ssf_handle* h, int n, int n_visible) {
 void drop_shard_sizes(ssf_handle* h) { h->all_valid = false; h->all_pending = false; }
 }  // namespace ssf
 
-static inline P2PView p2p_view(ssf_handle* h, unsigned long long seq) { P2PView v = h->p2p.view; v.seq = seq; return v; }
 // exchange != 0 (native multi-rank frame calls with the peer-to-peer backend): the association tables are traded with
 // the peers by the match launch's last workgroup -- or, when no rank has anything to match, by a launch of its own
 static int do_match(ssf_handle* h, int exchange = 0) {
@@ -1076,7 +859,6 @@ static int do_match(ssf_handle* h, int exchange = 0) {
 // final counters come back through the mailbox (no D2H copy, no stream synchronise).  In two halves: between them a
 // sharded map exchanges the rows that crossed a tile edge (migrate: fuse_begin leaves this shard's migrant table in
 // h->d_migrants; fuse_end takes the rank-reduced table, or nullptr when nothing can arrive).
-static int comm_gather_counts(ssf_handle* h);
 static int fuse_begin(ssf_handle* h, int migrate) {
     const long long nmodel_g = (h->cfg.nranks > 1 && h->global_n_model >= 0) ? h->global_n_model : h->n_model;
     const long long nvis_g = (h->cfg.nranks > 1 && h->global_n_visible >= 0) ? h->global_n_visible : h->n_visible;
@@ -1233,48 +1015,6 @@ static int fuse_end(ssf_handle* h, const int32_t* d_table, ssf_frame_result* out
 static int do_fuse(ssf_handle* h, ssf_frame_result* out) {          // no exchange of rows (single shard, or ssf_stage_fuse)
     int rc = fuse_begin(h, 0);
     return rc ? rc : fuse_end(h, nullptr, out);
-}
-
-// ---- multi-GPU exchanges (native RCCL on the track stream) -------------------------------------------------
-// enqueue the all-gather of every rank's Counters::last and its publication to the mailbox
-static int comm_gather_counts(ssf_handle* h) {
-    const unsigned long long seq = ++h->all_seq;
-    if (h->p2p.on) launch_p2p_counts(h->stream, p2p_view(h, ++h->p2p.seq_cnt), h->d_cnt, h->mb_dev, seq);
-    else {
-        RcclApi* api = rccl_api();
-        { ScopedKernel sk("exchange_counts", h->stream);      // (cfg.profile = 1: the collective's time on the track stream, bench.py's exchange_us_per_frame)
-          NCK(api->AllGather(h->d_cnt->last, h->d_all5, 5, ncclInt32, h->comm, h->stream)); }
-        launch_publish_all_counts(h->stream, h->d_all5, h->cfg.nranks, h->mb_dev, seq);
-    }
-    HCK(hipGetLastError());
-    h->all_pending = true;
-    return SSF_OK;
-}
-// the shard sizes of all ranks after the previous frame -> global counts and this shard's id offset
-static int comm_counts(ssf_handle* h) {
-    if (!h->all_valid && !h->all_pending) { int rc = comm_gather_counts(h); if (rc) return rc; }
-    if (h->all_pending) {
-        int rc = wait_seq(h, &h->mb_host->all_seq, h->all_seq);
-        if (rc) return rc;
-        const int n = 5 * h->cfg.nranks;
-        for (int attempt = 0;; attempt++) {
-            unsigned long long check = h->all_seq;
-            for (int i = 0; i < n; i++) {
-                const int v = __atomic_load_n(&h->mb_host->all_cnt[i], __ATOMIC_RELAXED);
-                h->all_cnt[i] = v; check += (unsigned long long)(unsigned int)v;
-            }
-            if (check == __atomic_load_n(&h->mb_host->all_check, __ATOMIC_ACQUIRE)) break;
-            if (attempt > 100000) { h->err = "shard-size mailbox record failed its checksum"; return SSF_ERR_DEVICE; }
-        }
-        h->all_pending = false; h->all_valid = true;
-    }
-    long long gm = 0, gv = 0, off = 0;
-    for (int r = 0; r < h->cfg.nranks; r++) {
-        gm += h->all_cnt[5 * r]; gv += h->all_cnt[5 * r + 1];
-        if (r < h->cfg.rank) off += h->all_cnt[5 * r + 1];
-    }
-    h->global_n_model = gm; h->global_n_visible = gv; h->id_offset = off;
-    return SSF_OK;
 }
 
 // ---- chained ICP launches --------------------------------------------------------------------------------
@@ -1510,6 +1250,7 @@ static int process_oldest(ssf_handle* h, const float* prior, ssf_frame_result* o
 }
 static int process_frame_impl(ssf_handle* h, const void* rgb, const void* depth, int on_device, const float* prior,
                               const uint8_t* mask, ssf_frame_result* out, const uint8_t* pixmask = nullptr) {
+    if (!frame_args_ok(h, rgb, depth, on_device)) return SSF_ERR_INVALID_ARG;
     if (!h->pending.empty()) { h->err = "frames are pending in the extract pipeline: use ssf_process_submitted"; return SSF_ERR_STATE; }
     int rc;
     { TimerScope ts(h); rc = submit_extract(h, rgb, depth, on_device, mask, pixmask, on_device); }
@@ -1874,26 +1615,19 @@ int ssf_create(const ssf_config* cfg, ssf_handle** out) {
 }
 const char* ssf_last_error(const ssf_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
-int ssf_process_frame(ssf_handle* h, const uint8_t* rgb, const float* depth, const float* prior, const uint8_t* mask, ssf_frame_result* out) {
-    if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
-    return process_frame_impl(h, rgb, depth, 0, prior, mask, out);
-}
-int ssf_process_frame_device(ssf_handle* h, const void* rgb, const void* depth, const float* prior, const uint8_t* mask, ssf_frame_result* out) {
-    if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
-    if (!device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
-    return process_frame_impl(h, rgb, depth, 1, prior, mask, out);
-}
+int ssf_process_frame(ssf_handle* h, const uint8_t* rgb, const float* depth, const float* prior, const uint8_t* mask, ssf_frame_result* out) { return process_frame_impl(h, rgb, depth, 0, prior, mask, out); }
+int ssf_process_frame_device(ssf_handle* h, const void* rgb, const void* depth, const float* prior, const uint8_t* mask, ssf_frame_result* out) { return process_frame_impl(h, rgb, depth, 1, prior, mask, out); }
 
 // pipelined form: extract of future frames runs ahead on its own stream(s)
-int ssf_submit_frame(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask) {
-    if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
-    if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
+static int submit_frame(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask, const uint8_t* pixmask) {
+    if (!frame_args_ok(h, rgb, depth, on_device)) return SSF_ERR_INVALID_ARG;
     TimerScope ts(h);
     const double t0 = now_us();
-    int rc = submit_extract(h, rgb, depth, on_device, mask);
+    int rc = submit_extract(h, rgb, depth, on_device, mask, pixmask, on_device);
     h->host_us[0] += now_us() - t0;
     return rc;
 }
+int ssf_submit_frame(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask) { return submit_frame(h, rgb, depth, on_device, mask, nullptr); }
 int ssf_submit_frame_tables(ssf_handle* h, const int32_t* label, const float* plane_depth, const ssf_surfels* frame, int on_device) {
     if (!h || !label || !plane_depth || !frame) return SSF_ERR_INVALID_ARG;
     if (!frame->positions || !frame->colors || !frame->stamps || !frame->orientations || !frame->shapes || !frame->dims || !frame->confidences) return SSF_ERR_INVALID_ARG;
@@ -2056,177 +1790,6 @@ int ssf_fern_codes(ssf_handle* h, const uint8_t* rgb, const float* depth, int wi
     return SSF_OK;
 }
 
-// ---- multi-GPU (native RCCL) ------------------------------------------------------------------------------
-int ssf_comm_unique_id(uint8_t* id128) {
-    if (!id128) return SSF_ERR_INVALID_ARG;
-    RcclApi* api = rccl_api();
-    if (!api) { g_create_err = "RCCL is not available in this process"; return SSF_ERR_DEVICE; }
-    static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
-    ncclUniqueId id;
-    if (api->GetUniqueId(&id) != ncclSuccess) { g_create_err = "ncclGetUniqueId failed"; return SSF_ERR_DEVICE; }
-    std::memcpy(id128, &id, 128);
-    return SSF_OK;
-}
-int ssf_comm_attach(ssf_handle* h, const uint8_t* id128) {
-    if (!h || !id128) return SSF_ERR_INVALID_ARG;
-    if (h->comm) { h->err = "a communicator is already attached"; return SSF_ERR_STATE; }
-    if (h->cfg.nranks > SSF_MAX_RANKS) { h->err = "too many ranks"; return SSF_ERR_INVALID_ARG; }
-    RcclApi* api = rccl_api();
-    if (!api) { h->err = "RCCL is not available in this process"; return SSF_ERR_DEVICE; }
-    HCK(hipSetDevice(h->cfg.device_id));
-    if (!h->d_all5 && !dalloc(h, &h->d_all5, 5 * SSF_MAX_RANKS)) { h->err = "allocation failed"; return SSF_ERR_DEVICE; }
-    ncclUniqueId id;
-    std::memcpy(&id, id128, 128);
-    NCK(api->CommInitRank(&h->comm, h->cfg.nranks, id, h->cfg.rank));
-    h->all_valid = false; h->all_pending = false;
-    return SSF_OK;
-}
-// The extract stage dealt over the ranks (see launch_batch): one communicator per batch context, split off the attached one --
-// a collective call, made by every rank after ssf_comm_attach and with an empty pipeline.  mode 0: back to the replicated form.
-int ssf_comm_deal_extract(ssf_handle* h, int mode) {
-    if (!h || mode < 0 || mode > 2) return SSF_ERR_INVALID_ARG;
-    if (!h->comm) { h->err = "ssf_comm_deal_extract: attach an RCCL communicator first (the peer-to-peer backend keeps the extract stage replicated)"; return SSF_ERR_STATE; }
-    if (!h->pending.empty()) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
-    for (auto& c : h->ctx) if (c.count > 0 || c.launched) { h->err = "a batch is open in the extract pipeline"; return SSF_ERR_STATE; }
-    RcclApi* api = rccl_api();
-    if (!api || !api->Broadcast || !api->CommSplit || !api->GroupStart || !api->GroupEnd) { h->err = "this RCCL has no ncclCommSplit / ncclBroadcast"; return SSF_ERR_DEVICE; }
-    HCK(hipSetDevice(h->cfg.device_id));
-    if (mode != 0)
-        for (auto& c : h->ctx)
-            if (!c.deal_comm) NCK(api->CommSplit(h->comm, 0, h->cfg.rank, &c.deal_comm, nullptr));
-    h->deal = mode; h->deal_batches = 0;
-    return SSF_OK;
-}
-int ssf_comm_info(ssf_handle* h, int* backend, int* ranks, int* my_rank) {
-    if (!h) return SSF_ERR_INVALID_ARG;
-    int b = 0, n = 1, r = 0;
-    if (h->comm) {
-        b = 1; n = h->cfg.nranks; r = h->cfg.rank;
-        RcclApi* api = rccl_api();
-        if (api && api->CommCount && api->CommUserRank) { NCK(api->CommCount(h->comm, &n)); NCK(api->CommUserRank(h->comm, &r)); }
-    } else if (h->p2p.on) {
-        b = 2; n = (int)h->p2p.opened.size() + 1; r = h->cfg.rank;
-        if (h->p2p.opened.empty()) n = h->cfg.nranks;        // ranks of one process (ssf_p2p_attach_local): nothing was opened through IPC
-    }
-    if (backend) *backend = b;
-    if (ranks) *ranks = n;
-    if (my_rank) *my_rank = r;
-    return SSF_OK;
-}
-// ---- multi-GPU (native, peer to peer: no collective launches) ---------------------------------------------------
-// the bound of every in-kernel wait for a peer, in ticks of the device's constant-rate wall clock (wall_clock64)
-static int p2p_set_timeout(ssf_handle* h) {
-    int khz = 0;
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->cfg.device_id) != hipSuccess || khz <= 0) { (void)hipGetLastError(); khz = 100000; }
-    h->p2p.view.timeout_ticks = (unsigned long long)(h->p2p.timeout_s * 1000.0 * (double)khz);
-    return SSF_OK;
-}
-static int p2p_region(ssf_handle* h) {
-    if (h->p2p.region) return SSF_OK;
-    if (h->cfg.nranks > SSF_P2P_MAX_RANKS) { h->err = "the peer-to-peer exchange serves at most 8 ranks (one node)"; return SSF_ERR_INVALID_ARG; }
-    HCK(hipSetDevice(h->cfg.device_id));
-    const size_t bytes = p2p_region_bytes(h->S);
-    void* q = nullptr;
-    // Which memory: peers store into this region and this rank's kernels poll it WHILE THEY RUN.  HIP guarantees coherence
-    // of ordinary (coarse-grained) device memory across devices only at kernel boundaries -- the owner's L2 may serve its
-    // polling loads stale lines while another GPU writes over xGMI -- so the region is FINE-GRAINED device memory
-    // (hipDeviceMallocFinegrained) unless the caller has declared, through ssf_p2p_configure, that every rank of the map
-    // lives on this handle's device (several shards on one GPU: the one arrangement this build could be run in).  There
-    // plain memory is used: all accesses to a region are system-scope atomics that meet in the same memory, and round 2's
-    // campaigns (profiles/p2p_campaigns_r02.txt) ran 2600 create-attach-run cycles clean with it against 211 bad ones with
-    // an UNCACHED region (hipDeviceMallocUncached; SSF_P2P_REGION_UNCACHED=1 brings that mapping back for experiments).
-    static const bool uncached = SSF_ENV_SET("P2P_REGION_UNCACHED");
-    if (uncached && hipExtMallocWithFlags(&q, bytes, hipDeviceMallocUncached) == hipSuccess) h->p2p.fine = true;
-    else if (!uncached && !h->p2p.same_device && hipExtMallocWithFlags(&q, bytes, hipDeviceMallocFinegrained) == hipSuccess) h->p2p.fine = true;
-    else {
-        (void)hipGetLastError();
-        if (!h->p2p.same_device && !uncached) { h->err = "fine-grained device memory for the exchange region is not available"; return SSF_ERR_DEVICE; }
-        HCK(hipMalloc(&q, bytes));
-    }
-    HCK(hipMemset(q, 0, bytes));
-    HCK(hipDeviceSynchronize());
-    h->p2p.region = (unsigned char*)q; h->p2p.bytes = bytes;
-    return SSF_OK;
-}
-int ssf_p2p_configure(ssf_handle* h, int all_ranks_on_this_device, double timeout_s) {
-    if (!h || !(timeout_s > 0.0)) return SSF_ERR_INVALID_ARG;
-    if (h->p2p.region && (all_ranks_on_this_device != 0) != h->p2p.same_device) {
-        h->err = "ssf_p2p_configure: the exchange region is already allocated (call before ssf_p2p_export / ssf_p2p_region)"; return SSF_ERR_STATE;
-    }
-    h->p2p.same_device = all_ranks_on_this_device != 0;
-    h->p2p.timeout_s = timeout_s;
-    if (h->p2p.on) { int rc = p2p_set_timeout(h); if (rc) return rc; }
-    return SSF_OK;
-}
-int ssf_p2p_region(ssf_handle* h, void** region, size_t* bytes) {
-    if (!h || !region) return SSF_ERR_INVALID_ARG;
-    int rc = p2p_region(h);
-    if (rc) return rc;
-    *region = h->p2p.region; if (bytes) *bytes = h->p2p.bytes;
-    return SSF_OK;
-}
-int ssf_p2p_export(ssf_handle* h, uint8_t* handle64) {
-    if (!h || !handle64) return SSF_ERR_INVALID_ARG;
-    int rc = p2p_region(h);
-    if (rc) return rc;
-    static_assert(sizeof(hipIpcMemHandle_t) == SSF_P2P_HANDLE_BYTES, "hipIpcMemHandle_t is 64 bytes");
-    hipIpcMemHandle_t ih;
-    HCK(hipIpcGetMemHandle(&ih, h->p2p.region));
-    std::memcpy(handle64, &ih, sizeof(ih));
-    return SSF_OK;
-}
-static int p2p_finish_attach(ssf_handle* h) {
-    { int rc = p2p_set_timeout(h); if (rc) return rc; }
-    h->p2p.view.me = h->cfg.rank; h->p2p.view.nranks = h->cfg.nranks; h->p2p.view.S = h->S; h->p2p.view.seq = 0;
-    h->p2p.on = true;
-    h->all_valid = false; h->all_pending = false;
-    return SSF_OK;
-}
-static int p2p_attach_check(ssf_handle* h) {
-    if (h->comm || h->p2p.on) { h->err = "an exchange backend is already attached"; return SSF_ERR_STATE; }
-    if (h->stamp != 0 && h->cfg.nranks > 1) { /* joining later is fine as long as every rank does so at the same frame */ }
-    return p2p_region(h);
-}
-int ssf_p2p_attach(ssf_handle* h, const uint8_t* handles) {
-    if (!h || !handles) return SSF_ERR_INVALID_ARG;
-    int rc = p2p_attach_check(h);
-    if (rc) return rc;
-    for (int r = 0; r < h->cfg.nranks; r++) {
-        if (r == h->cfg.rank) { h->p2p.view.peer[r] = h->p2p.region; continue; }
-        hipIpcMemHandle_t ih;
-        std::memcpy(&ih, handles + (size_t)SSF_P2P_HANDLE_BYTES * r, sizeof(ih));
-        void* q = nullptr;
-        HCK(hipIpcOpenMemHandle(&q, ih, hipIpcMemLazyEnablePeerAccess));
-        h->p2p.opened.push_back(q);
-        h->p2p.view.peer[r] = (unsigned char*)q;
-    }
-    return p2p_finish_attach(h);
-}
-int ssf_p2p_attach_local(ssf_handle* h, void* const* regions) {
-    if (!h || !regions) return SSF_ERR_INVALID_ARG;
-    int rc = p2p_attach_check(h);
-    if (rc) return rc;
-    for (int r = 0; r < h->cfg.nranks; r++) {
-        if (r != h->cfg.rank && !regions[r]) { h->err = "a peer region is missing"; return SSF_ERR_INVALID_ARG; }
-        h->p2p.view.peer[r] = r == h->cfg.rank ? h->p2p.region : (unsigned char*)regions[r];
-    }
-    return p2p_finish_attach(h);
-}
-int ssf_get_global_counts(ssf_handle* h, int64_t* out5) {
-    if (!h || !out5) return SSF_ERR_INVALID_ARG;
-    if (!h->comm && !h->p2p.on) {
-        int rc = hipStreamSynchronize(h->stream) == hipSuccess ? SSF_OK : SSF_ERR_DEVICE;
-        Counters c;
-        if (rc || hipMemcpy(&c, h->d_cnt, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess) { h->err = "device error"; return SSF_ERR_DEVICE; }
-        for (int i = 0; i < 5; i++) out5[i] = c.last[i];
-        return SSF_OK;
-    }
-    int rc = comm_counts(h);
-    if (rc) return rc;
-    for (int i = 0; i < 5; i++) { out5[i] = 0; for (int r = 0; r < h->cfg.nranks; r++) out5[i] += h->all_cnt[5 * r + i]; }
-    return SSF_OK;
-}
-
 int ssf_set_input_format(ssf_handle* h, int color, int depth, double depth_scale) {
     if (!h) return SSF_ERR_INVALID_ARG;
     if (color < SSF_COLOR_RGB8 || color > SSF_COLOR_BGRA8 || (depth != SSF_DEPTH_F32_METRES && depth != SSF_DEPTH_U16_SCALED)) {
@@ -2247,40 +1810,20 @@ int ssf_get_input_format(const ssf_handle* h, int* color, int* depth, double* de
     return SSF_OK;
 }
 
-int ssf_stage_extract(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask) {
-    if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
-    if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
-    TimerScope ts(h);
-    return do_extract(h, rgb, depth, on_device, mask);
-}
+int ssf_stage_extract(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* mask) { return do_extract(h, rgb, depth, on_device, mask); }
 
 // ---- pixel masks (ssf_dynamic.h) ----------------------------------------------------------------------
 static int copy_map(ssf_handle* h, void* dst, const void* src, size_t bytes);
 int ssf_process_frame_pixmask(ssf_handle* h, const void* rgb, const void* depth, int on_device, const float* prior, const uint8_t* pixel_mask,
                               ssf_frame_result* out) {
-    if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
-    if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
     return process_frame_impl(h, rgb, depth, on_device ? 1 : 0, prior, nullptr, out, pixel_mask);
 }
-int ssf_submit_frame_pixmask(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* pixel_mask) {
-    if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
-    if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
-    TimerScope ts(h);
-    const double t0 = now_us();
-    int rc = submit_extract(h, rgb, depth, on_device ? 1 : 0, nullptr, pixel_mask, on_device ? 1 : 0);
-    h->host_us[0] += now_us() - t0;
-    return rc;
-}
+int ssf_submit_frame_pixmask(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* pixel_mask) { return submit_frame(h, rgb, depth, on_device ? 1 : 0, nullptr, pixel_mask); }
 int ssf_process_sequence_pixmask(ssf_handle* h, const void* const* rgb, const void* const* depth, const uint8_t* const* pixel_masks, int n,
                                  int on_device, ssf_frame_result* out) {
     return process_sequence_impl(h, rgb, depth, pixel_masks, n, on_device ? 1 : 0, out);
 }
-int ssf_stage_extract_pixmask(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* pixel_mask) {
-    if (!h || !rgb || !depth) return SSF_ERR_INVALID_ARG;
-    if (on_device && !device_input_aligned(h, rgb, depth)) return SSF_ERR_INVALID_ARG;
-    TimerScope ts(h);
-    return do_extract(h, rgb, depth, on_device ? 1 : 0, nullptr, pixel_mask);
-}
+int ssf_stage_extract_pixmask(ssf_handle* h, const void* rgb, const void* depth, int on_device, const uint8_t* pixel_mask) { return do_extract(h, rgb, depth, on_device ? 1 : 0, nullptr, pixel_mask); }
 // the vote of the current frame, recomputed on the host from the counts k_finalize_surfels<true> voted on (same integer rule)
 int ssf_get_dynamic_superpixels(ssf_handle* h, uint8_t* out, int* n_dynamic) {
     if (!h || !out) return SSF_ERR_INVALID_ARG;
@@ -2338,17 +1881,19 @@ int ssf_stage_icp_end(ssf_handle* h, int* valid) {
     if (!h || !valid) return SSF_ERR_INVALID_ARG;
     icp_end(h, valid); return SSF_OK;
 }
-int ssf_stage_match(ssf_handle* h, uint64_t* best, uint8_t* matched) {
+// the association of the current frame, run and copied out: to the host (and waited for) or to device tables (enqueued only)
+static int stage_match(ssf_handle* h, uint64_t* best, uint8_t* matched, hipMemcpyKind kind) {
     if (!h || !best || !matched) return SSF_ERR_INVALID_ARG;
     if (!h->have_frame) return SSF_ERR_STATE;
     TimerScope ts(h);
     int rc = do_match(h);
     if (rc) return rc;
-    HCK(hipMemcpyAsync(best, h->cc->d_best, (size_t)h->S * 8, hipMemcpyDeviceToHost, h->stream));
-    HCK(hipMemcpyAsync(matched, h->cc->d_matched, (size_t)h->S, hipMemcpyDeviceToHost, h->stream));
-    HCK(hipStreamSynchronize(h->stream));
+    HCK(hipMemcpyAsync(best, h->cc->d_best, (size_t)h->S * 8, kind, h->stream));
+    HCK(hipMemcpyAsync(matched, h->cc->d_matched, (size_t)h->S, kind, h->stream));
+    if (kind == hipMemcpyDeviceToHost) HCK(hipStreamSynchronize(h->stream));
     return SSF_OK;
 }
+int ssf_stage_match(ssf_handle* h, uint64_t* best, uint8_t* matched) { return stage_match(h, best, matched, hipMemcpyDeviceToHost); }
 int ssf_stage_begin_submitted(ssf_handle* h) {
     if (!h) return SSF_ERR_INVALID_ARG;
     return activate_oldest(h);
@@ -2369,59 +1914,48 @@ int ssf_stage_icp_fetch(ssf_handle* h, const int64_t* d_sums, int64_t* sums) {
     std::memcpy(sums, h->h_icp, SSF_ICP_RECORD * sizeof(int64_t));
     return SSF_OK;
 }
-int ssf_stage_match_device(ssf_handle* h, uint64_t* d_best, uint8_t* d_matched) {
-    if (!h || !d_best || !d_matched) return SSF_ERR_INVALID_ARG;
-    if (!h->have_frame) return SSF_ERR_STATE;
-    TimerScope ts(h);
-    int rc = do_match(h);
-    if (rc) return rc;
-    HCK(hipMemcpyAsync(d_best, h->cc->d_best, (size_t)h->S * 8, hipMemcpyDeviceToDevice, h->stream));
-    HCK(hipMemcpyAsync(d_matched, h->cc->d_matched, (size_t)h->S, hipMemcpyDeviceToDevice, h->stream));
+int ssf_stage_match_device(ssf_handle* h, uint64_t* d_best, uint8_t* d_matched) { return stage_match(h, d_best, d_matched, hipMemcpyDeviceToDevice); }
+// the caller's association tables -> the current frame's (enqueued on the track stream)
+static int assoc_in(ssf_handle* h, const uint64_t* best, const uint8_t* matched, hipMemcpyKind kind) {
+    HCK(hipMemcpyAsync(h->cc->d_best, best, (size_t)h->S * 8, kind, h->stream));
+    HCK(hipMemcpyAsync(h->cc->d_matched, matched, (size_t)h->S, kind, h->stream));
     return SSF_OK;
 }
-int ssf_stage_fuse_device(ssf_handle* h, const uint64_t* d_best, const uint8_t* d_matched, ssf_frame_result* out) {
-    if (!h || !d_best || !d_matched) return SSF_ERR_INVALID_ARG;
-    if (!h->have_frame || h->fusing) return SSF_ERR_STATE;
-    TimerScope ts(h);
-    HCK(hipMemcpyAsync(h->cc->d_best, d_best, (size_t)h->S * 8, hipMemcpyDeviceToDevice, h->stream));
-    HCK(hipMemcpyAsync(h->cc->d_matched, d_matched, (size_t)h->S, hipMemcpyDeviceToDevice, h->stream));
-    return do_fuse(h, out);
-}
-int ssf_stage_fuse_begin_device(ssf_handle* h, const uint64_t* d_best, const uint8_t* d_matched, int32_t* d_table) {
-    if (!h || !d_best || !d_matched || !d_table) return SSF_ERR_INVALID_ARG;
-    if (!h->have_frame || h->fusing) return SSF_ERR_STATE;
-    TimerScope ts(h);
-    HCK(hipMemcpyAsync(h->cc->d_best, d_best, (size_t)h->S * 8, hipMemcpyDeviceToDevice, h->stream));
-    HCK(hipMemcpyAsync(h->cc->d_matched, d_matched, (size_t)h->S, hipMemcpyDeviceToDevice, h->stream));
-    int rc = fuse_begin(h, 1);
-    if (rc) return rc;
-    const hipError_t e = h->fuse_migrate ? hipMemcpyAsync(d_table, h->d_migrants, (size_t)SSF_MIGRANT_WORDS * h->S * 4, hipMemcpyDeviceToDevice, h->stream)
-                                         : hipMemsetAsync(d_table, 0, (size_t)SSF_MIGRANT_WORDS * h->S * 4, h->stream);
+// this shard's migrant table -> the caller's (zeros when the frame migrates nothing); a host table is waited for
+static int migrants_out(ssf_handle* h, int32_t* table, hipMemcpyKind kind) {
+    const size_t bytes = (size_t)SSF_MIGRANT_WORDS * h->S * 4;
+    const bool host = kind == hipMemcpyDeviceToHost;
+    hipError_t e = hipSuccess;
+    if (h->fuse_migrate) { e = hipMemcpyAsync(table, h->d_migrants, bytes, kind, h->stream); if (host && e == hipSuccess) e = hipStreamSynchronize(h->stream); }
+    else if (host) std::memset(table, 0, bytes);
+    else e = hipMemsetAsync(table, 0, bytes, h->stream);
     if (e != hipSuccess) { h->fusing = false; h->err = std::string("migrant table copy: ") + hipGetErrorString(e); return SSF_ERR_DEVICE; }
     return SSF_OK;
 }
+static int stage_fuse(ssf_handle* h, const uint64_t* best, const uint8_t* matched, ssf_frame_result* out, hipMemcpyKind in) {
+    if (!h || !best || !matched) return SSF_ERR_INVALID_ARG;
+    if (!h->have_frame || h->fusing) return SSF_ERR_STATE;
+    TimerScope ts(h);
+    int rc = assoc_in(h, best, matched, in);
+    return rc ? rc : do_fuse(h, out);
+}
+static int stage_fuse_begin(ssf_handle* h, const uint64_t* best, const uint8_t* matched, int32_t* table, hipMemcpyKind in, hipMemcpyKind out) {
+    if (!h || !best || !matched || !table) return SSF_ERR_INVALID_ARG;
+    if (!h->have_frame || h->fusing) return SSF_ERR_STATE;
+    TimerScope ts(h);
+    int rc = assoc_in(h, best, matched, in);
+    if (!rc) rc = fuse_begin(h, 1);
+    return rc ? rc : migrants_out(h, table, out);
+}
+int ssf_stage_fuse_device(ssf_handle* h, const uint64_t* d_best, const uint8_t* d_matched, ssf_frame_result* out) { return stage_fuse(h, d_best, d_matched, out, hipMemcpyDeviceToDevice); }
+int ssf_stage_fuse_begin_device(ssf_handle* h, const uint64_t* d_best, const uint8_t* d_matched, int32_t* d_table) { return stage_fuse_begin(h, d_best, d_matched, d_table, hipMemcpyDeviceToDevice, hipMemcpyDeviceToDevice); }
 int ssf_stage_fuse_end_device(ssf_handle* h, const int32_t* d_table, ssf_frame_result* out) {
     if (!h) return SSF_ERR_INVALID_ARG;
     if (!h->fusing) return SSF_ERR_STATE;
     TimerScope ts(h);
     return fuse_end(h, d_table, out);
 }
-int ssf_stage_fuse_begin(ssf_handle* h, const uint64_t* best, const uint8_t* matched, int32_t* table) {
-    if (!h || !best || !matched || !table) return SSF_ERR_INVALID_ARG;
-    if (!h->have_frame || h->fusing) return SSF_ERR_STATE;
-    TimerScope ts(h);
-    HCK(hipMemcpyAsync(h->cc->d_best, best, (size_t)h->S * 8, hipMemcpyHostToDevice, h->stream));
-    HCK(hipMemcpyAsync(h->cc->d_matched, matched, (size_t)h->S, hipMemcpyHostToDevice, h->stream));
-    int rc = fuse_begin(h, 1);
-    if (rc) return rc;
-    const size_t bytes = (size_t)SSF_MIGRANT_WORDS * h->S * 4;
-    if (h->fuse_migrate) {
-        hipError_t e = hipMemcpyAsync(table, h->d_migrants, bytes, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) { h->fusing = false; h->err = std::string("migrant table copy: ") + hipGetErrorString(e); return SSF_ERR_DEVICE; }
-    } else std::memset(table, 0, bytes);
-    return SSF_OK;
-}
+int ssf_stage_fuse_begin(ssf_handle* h, const uint64_t* best, const uint8_t* matched, int32_t* table) { return stage_fuse_begin(h, best, matched, table, hipMemcpyHostToDevice, hipMemcpyDeviceToHost); }
 int ssf_stage_fuse_end(ssf_handle* h, const int32_t* table, ssf_frame_result* out) {
     if (!h) return SSF_ERR_INVALID_ARG;
     if (!h->fusing) return SSF_ERR_STATE;
@@ -2429,14 +1963,7 @@ int ssf_stage_fuse_end(ssf_handle* h, const int32_t* table, ssf_frame_result* ou
     if (table && h->fuse_migrate) HCK(hipMemcpyAsync(h->d_migrants, table, (size_t)SSF_MIGRANT_WORDS * h->S * 4, hipMemcpyHostToDevice, h->stream));
     return fuse_end(h, (table && h->fuse_migrate) ? h->d_migrants : nullptr, out);
 }
-int ssf_stage_fuse(ssf_handle* h, const uint64_t* best, const uint8_t* matched, ssf_frame_result* out) {
-    if (!h || !best || !matched) return SSF_ERR_INVALID_ARG;
-    if (!h->have_frame || h->fusing) return SSF_ERR_STATE;
-    TimerScope ts(h);
-    HCK(hipMemcpyAsync(h->cc->d_best, best, (size_t)h->S * 8, hipMemcpyHostToDevice, h->stream));
-    HCK(hipMemcpyAsync(h->cc->d_matched, matched, (size_t)h->S, hipMemcpyHostToDevice, h->stream));
-    return do_fuse(h, out);
-}
+int ssf_stage_fuse(ssf_handle* h, const uint64_t* best, const uint8_t* matched, ssf_frame_result* out) { return stage_fuse(h, best, matched, out, hipMemcpyHostToDevice); }
 
 int ssf_get_pose(const ssf_handle* h, float* p) { if (!h || !p) return SSF_ERR_INVALID_ARG; pose_to12(h->pose, p); return SSF_OK; }
 int ssf_set_pose(ssf_handle* h, const float* p) { if (!h || !p) return SSF_ERR_INVALID_ARG; h->pose = pose_from12(p); return SSF_OK; }
@@ -2449,6 +1976,15 @@ int ssf_get_counts(const ssf_handle* h, int* nm, int* nv, int* st, int* ns) {
     return SSF_OK;
 }
 
+// orientations: 9 floats per row at the ABI (3 x 3, row-major), the three matrix rows as three streams of 3 n floats in the stores
+static void orient_to_streams(const float* o9, float* rows, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) rows[(size_t)r * 3 * n + 3 * i + c] = o9[9 * i + 3 * r + c];
+}
+static void orient_from_streams(const float* rows, float* o9, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) o9[9 * i + 3 * r + c] = rows[(size_t)r * 3 * n + 3 * i + c];
+}
 static int copy_out(ssf_handle* h, const SurfelSoA& s, int first, int count, ssf_surfels* o) {
     if (count <= 0) return SSF_OK;
     const size_t n = count, f = first;
@@ -2463,10 +1999,7 @@ static int copy_out(ssf_handle* h, const SurfelSoA& s, int first, int count, ssf
         HCK(hipMemcpyAsync(rows.data() + 6 * n, s.r2 + 3 * f, 12 * n, hipMemcpyDeviceToHost, st));
     }
     HCK(hipStreamSynchronize(st));
-    if (o->orientations)
-        for (size_t i = 0; i < n; i++)
-            for (int r = 0; r < 3; r++)
-                for (int c = 0; c < 3; c++) o->orientations[9 * i + 3 * r + c] = rows[(size_t)r * 3 * n + 3 * i + c];
+    if (o->orientations) orient_from_streams(rows.data(), o->orientations, n);
     return SSF_OK;
 }
 int ssf_get_model(ssf_handle* h, int first, int count, ssf_surfels* o) {
@@ -2485,9 +2018,7 @@ int ssf_set_model(ssf_handle* h, const ssf_surfels* in, int n, int n_visible, in
     const size_t N = n;
     if (n > 0) {
         std::vector<float> rows(9 * N);
-        for (size_t i = 0; i < N; i++)
-            for (int r = 0; r < 3; r++)
-                for (int c = 0; c < 3; c++) rows[(size_t)r * 3 * N + 3 * i + c] = in->orientations[9 * i + 3 * r + c];
+        orient_to_streams(in->orientations, rows.data(), N);
         { int rc = copy_rows(h, soa_surfels(s), 0, *in, 0, N, hipMemcpyHostToDevice); if (rc) return rc; }
         HCK(hipMemcpyAsync(s.r0, rows.data(), 12 * N, hipMemcpyHostToDevice, st));
         HCK(hipMemcpyAsync(s.r1, rows.data() + 3 * N, 12 * N, hipMemcpyHostToDevice, st));
@@ -2604,77 +2135,6 @@ int ssf_apply_deformation(ssf_handle* h, const float* np, const float* nr, const
     return deform_dense(h, m, d_np, d_nr, d_nt, d_nodes, d_w, d_i);
 }
 
-// ---- re-homing of a sharded map (see ssf.h): rows moved by ssf_apply_deformation go to the rank that owns their tile ----
-// A rare, bulk operation (a loop closure): worked on the dense logical view with full-model copies; the transport between
-// the ranks is the caller's (supersurfel_fusion_amd/sharded.py: torch.distributed; the tests: files / memory).
-int ssf_rehome_begin(ssf_handle* h, int32_t* table, int table_rows, int* n_out) {
-    if (!h || !n_out || table_rows < 0 || (!table && table_rows > 0)) return SSF_ERR_INVALID_ARG;
-    { int rc = model_at_rest(h); if (rc) return rc; }
-    *n_out = 0;
-    drop_shard_sizes(h);
-    const int n = h->n_model;
-    if (h->cfg.nranks <= 1 || n == 0) return SSF_OK;
-    hipStream_t st = h->stream;
-    { int rc = materialise(h); if (rc) return rc; }
-    int32_t* d_table = nullptr; int* d_tot = nullptr;
-    DevTemps tmp;
-    HCK(tmp.take(&d_table, (size_t)std::max(table_rows, 1) * SSF_MIGRANT_WORDS * 4)); HCK(tmp.take(&d_tot, 16));
-    SurfelSoA scratch = h->oov[h->ocur ^ 1].rows;          // (the other out-of-view store is scratch between recentres)
-    launch_rehome_split(st, h->dense, n, h->n_visible, h->cfg.rank, h->cfg.nranks, h->cfg.shard_tile, h->d_bc_oov, d_tot, scratch, d_table, table_rows);
-    HCK(hipGetLastError());
-    int tot[3] = {0, 0, 0};
-    HCK(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
-    HCK(hipStreamSynchronize(st));
-    if (tot[1] > table_rows) { h->err = "ssf_rehome_begin: the table is too small for the rows that leave"; return SSF_ERR_CAPACITY; }   // (stores untouched)
-    if (tot[1] == 0) return SSF_OK;
-    HCK(hipMemcpyAsync(table, d_table, (size_t)tot[1] * SSF_MIGRANT_WORDS * 4, hipMemcpyDeviceToHost, st));
-    { int rc = copy_soa(h, h->dense, scratch, (size_t)tot[0]); if (rc) return rc; }
-    { int rc = store_from_dense(h, tot[0], tot[2]); if (rc) return rc; }
-    HCK(hipStreamSynchronize(st));
-    *n_out = tot[1];
-    return SSF_OK;
-}
-int ssf_rehome_end(ssf_handle* h, const int32_t* table, int n_rec) {
-    if (!h || n_rec < 0 || (!table && n_rec > 0)) return SSF_ERR_INVALID_ARG;
-    { int rc = model_at_rest(h); if (rc) return rc; }
-    drop_shard_sizes(h);
-    // the records addressed to this rank, split by the block they arrive in (table order kept).  A full shard turns the
-    // surplus away, in table order, as a frame's migration does (k_migrate_in): their source shards have already let them
-    // go, so they are lost to the map -- the call still succeeds on every rank (an error here would leave the ranks in
-    // different states with nothing to roll back) and returns their number
-    std::vector<int32_t> vis, oov;
-    const int n = h->n_model, nv = h->n_visible;
-    int room = h->cfg.nb_supersurfels_max - n, turned_away = 0;
-    for (int j = 0; j < n_rec; j++) {
-        const int32_t* w = table + (size_t)SSF_MIGRANT_WORDS * j;
-        if (w[0] - 1 != h->cfg.rank) continue;
-        if (room <= 0) { turned_away++; continue; }
-        room--;
-        std::vector<int32_t>& dst = w[1] ? vis : oov;
-        dst.insert(dst.end(), w, w + SSF_MIGRANT_WORDS);
-    }
-    const int av = (int)(vis.size() / SSF_MIGRANT_WORDS), ao = (int)(oov.size() / SSF_MIGRANT_WORDS);
-    if (av + ao == 0) return turned_away;
-    hipStream_t st = h->stream;
-    { int rc = materialise(h); if (rc) return rc; }
-    int32_t* d_rec = nullptr;
-    DevTemps tmp;
-    HCK(tmp.take(&d_rec, (size_t)(av + ao) * SSF_MIGRANT_WORDS * 4));
-    if (av) HCK(hipMemcpyAsync(d_rec, vis.data(), vis.size() * 4, hipMemcpyHostToDevice, st));
-    if (ao) HCK(hipMemcpyAsync(d_rec + vis.size(), oov.data(), oov.size() * 4, hipMemcpyHostToDevice, st));
-    // [visible | arrivals flagged visible | out of view | the other arrivals], assembled in the scratch store
-    SurfelSoA scratch = h->oov[h->ocur ^ 1].rows;
-    { int rc = copy_soa(h, scratch, h->dense, (size_t)nv); if (rc) return rc; }
-    launch_rehome_unpack(st, d_rec, av, scratch, nv);
-    { int rc = copy_soa(h, soa_rows(scratch, (size_t)nv + av), soa_rows(h->dense, (size_t)nv), (size_t)(n - nv)); if (rc) return rc; }
-    launch_rehome_unpack(st, d_rec + vis.size(), ao, scratch, n + av);
-    HCK(hipGetLastError());
-    { int rc = copy_soa(h, h->dense, scratch, (size_t)n + av + ao); if (rc) return rc; }
-    { int rc = store_from_dense(h, n + av + ao, nv + av); if (rc) return rc; }
-    HCK(hipStreamSynchronize(st));
-    return turned_away;
-}
-
 int ssf_bilateral_filter(ssf_handle* h, const void* in, void* out, int on_device) {
     if (!h || !in || !out) return SSF_ERR_INVALID_ARG;
     const size_t P = (size_t)h->cfg.width * h->cfg.height;
@@ -2707,22 +2167,6 @@ int ssf_set_profile(ssf_handle* h, int enable) {
     return SSF_OK;
 }
 
-// completion times (us since the call started) of the first 64 frames of the last ssf_process_sequence (tools/startup_probe.py)
-#ifdef SSF_EXPERIMENTS          // (laboratory build only: probes of tools/, not part of the product)
-// the record of the last ICP iteration the host fetched (after the exchange of a sharded map: the SUM over the ranks)
-int ssf_dbg_last_icp_record(ssf_handle* h, int64_t* out29) {
-    if (!h || !out29) return SSF_ERR_INVALID_ARG;
-    for (int i = 0; i < 29; i++) out29[i] = h->h_icp_local[i];
-    return SSF_OK;
-}
-// device copy of the last record [0..28] and, with the peer-to-peer exchange, of this shard's own record before it [32..60]
-int ssf_dbg_device_icp_records(ssf_handle* h, int64_t* out64) {
-    if (!h || !out64) return SSF_ERR_INVALID_ARG;
-    HCK(hipStreamSynchronize(h->stream));
-    HCK(hipMemcpy(out64, h->d_icp, 64 * sizeof(int64_t), hipMemcpyDeviceToHost));
-    return SSF_OK;
-}
-#endif
 // per frame of the last sequence (first 64): entry of the track loop, first ICP record back, ICP loop done, counters
 // back [us from the call's entry]; then 32 x (time, frames) of the extract batches launched
 int ssf_sequence_marks(ssf_handle* h, double* out320) {
@@ -2742,46 +2186,14 @@ int ssf_tuner_state(ssf_handle* h, double* out4) {
     return SSF_OK;
 }
 // ... and the frames whose association was run again as a launch of its own because the host's word to the waiting launch came
-// too late to be trusted; the test hook that makes it late (a stall of the calling thread in front of the word)
+// too late to be trusted
 long long ssf_waiter_match_repairs(ssf_handle* h) { return h ? h->n_waiter_match_repairs : -1; }
-#ifdef SSF_EXPERIMENTS
-void ssf_dbg_stall_before_match_us(ssf_handle* h, long long us) { if (h) h->dbg_stall_before_match_us = us; }      // (fault injection: lab build only)
-#endif
+// completion times (us since the call started) of the first 64 frames of the last ssf_process_sequence (tools/startup_probe.py)
 int ssf_sequence_times(ssf_handle* h, double* out64) {
     if (!h || !out64) return SSF_ERR_INVALID_ARG;
     for (int i = 0; i < 64; i++) out64[i] = h->seq_done_us[i];
     return SSF_OK;
 }
-#ifdef SSF_EXPERIMENTS          // (laboratory build only: probes of tools/, not part of the product)
-// host-side time split of the pipelined loop (tools/pipeline_probe.py); reset on read
-int ssf_dbg_host_times(ssf_handle* h, double* out8) {
-    if (!h || !out8) return SSF_ERR_INVALID_ARG;
-    for (int i = 0; i < 8; i++) { out8[i] = h->host_us[i]; h->host_us[i] = 0; }
-    return SSF_OK;
-}
-
-// throughput of the extract stage alone (tools/extract_only_probe.py): frames (device pointers, `nlist` of them,
-// cycled) go through the batch contexts and are retired unread; returns microseconds per frame.  The handle's
-// frame stamp advances as if the frames had been fused.
-double ssf_dbg_extract_only(ssf_handle* h, const void* const* rgb, const void* const* depth, int nlist, int n) {
-    if (!h || !rgb || !depth || nlist <= 0 || !h->pending.empty()) return -1.0;
-    int nsub = 0;
-    double t0 = 0;
-    for (int i = 0; i < n; i++) {
-        if (i == n / 4) { for (auto& c : h->ctx) (void)hipStreamSynchronize(c.stream); (void)hipStreamSynchronize(h->stream); t0 = now_us(); }
-        while (nsub < n && !h->ctx[h->open_ctx].launched) {
-            if (submit_extract(h, rgb[nsub % nlist], depth[nsub % nlist], 1, nullptr)) return -1.0;
-            nsub++;
-        }
-        if (activate_oldest(h) || retire_active(h)) return -1.0;
-        h->stamp++;
-    }
-    for (auto& c : h->ctx) (void)hipStreamSynchronize(c.stream);
-    (void)hipStreamSynchronize(h->stream);
-    return (now_us() - t0) / (double)(n - n / 4);
-}
-
-#endif
 
 // What a stream copy reaches on THIS box (nominal AND measured-achievable peak): 16 bytes per lane, `mib` MiB
 // read + the same written, best of `reps` over four forms of the same copy -- MI355X_MICROARCH.md quotes 6.29 TB/s (79 % of the
@@ -2824,87 +2236,6 @@ double ssf_stream_copy_rate(int mib, int reps) {
     return best;
 }
 
-#ifdef SSF_EXPERIMENTS          // (laboratory build only: probes of tools/, not part of the product)
-// ablation timer for the ICP kernel (tools/icp_probe.py): `reps` back-to-back launches in mode `dbg`
-// (bit0: skip the per-surfel math, bit1: skip the LDS accumulation, bit2: skip arrival counting + tail)
-double ssf_dbg_time_icp(ssf_handle* h, int reps, int dbg) {
-    if (!h || !h->have_frame) return -1.0;
-    Rt T; T.R = m3_transpose(h->pose.R); T.t = negate(m3_mulv(T.R, h->pose.t));
-    hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    for (int i = 0; i < 3; i++) launch_icp(h->stream, h->cam, h->model[h->mcur], h->n_visible, h->cc->maps.pix2, h->cc->maps.fpack, T, h->d_icp_replicas, h->d_tickets + 8, h->d_icp, h->mb_dev, ++h->icp_seq, dbg);
-    (void)hipEventRecord(e0, h->stream);
-    for (int i = 0; i < reps; i++) launch_icp(h->stream, h->cam, h->model[h->mcur], h->n_visible, h->cc->maps.pix2, h->cc->maps.fpack, T, h->d_icp_replicas, h->d_tickets + 8, h->d_icp, h->mb_dev, ++h->icp_seq, dbg);
-    (void)hipEventRecord(e1, h->stream);
-    (void)hipStreamSynchronize(h->stream);
-    float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipMemsetAsync(h->d_icp_replicas, 0, 2 * SSF_ICP_REPLICAS * 32 * sizeof(long long), h->stream);
-    (void)hipMemsetAsync(h->d_tickets, 0, 512 * sizeof(unsigned int), h->stream);
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return 1000.0 * ms / reps;
-}
-
-// ablation timer for the fuse launch (tools/fuse_probe.py; lab build; leaves model and partition sums garbage): `reps` back-to-back
-// k_update_insert launches on the current frame.  mode bit 0: without the out-of-view arm, bit 1: without update + insert,
-// bit 2: without the classification of the visible rows (and then without the update, which needs them)
-double ssf_dbg_time_fuse(ssf_handle* h, int reps, int mode, long long* blocks2 /* out-of-view blocks of 256 slots | those with rows that move; may be null */) {
-    if (!h || !h->have_frame || !h->cc) return -1.0;
-    SurfelSoA& M = h->model[h->mcur];
-    PartitionWs ws;
-    uint32_t* set = h->d_part + (size_t)h->part_set * h->part_words;
-    ws.sup_vis = set; ws.sup_oov = set + h->part_sup_vis; ws.tot = ws.sup_oov + h->part_sup_oov;
-    ws.ticket = h->d_part_ticket; ws.other = h->d_part + (size_t)(h->part_set ^ 1) * h->part_words; ws.words = h->part_words;
-    const int S = (mode & 2) ? 0 : h->S, nvis = (mode & 4) ? 0 : h->n_visible, span = (mode & 1) ? 0 : h->oov_tail - h->oov_head;
-    auto launch = [&] {
-        launch_fuse(h->stream, M, h->cc->frame, h->pose, h->stamp, h->id_offset, nvis, h->cc->d_best, h->cc->d_matched, h->d_cand,
-                    S, (nvis > 0 && S > 0) ? 1 : 0, h->cfg.nb_supersurfels_max, 0, 1, h->cfg.shard_tile, h->d_cnt,
-                    h->cam, h->oov[h->ocur], span, h->cc->maps.plane_depth, h->cfg.delta_t,
-                    h->cfg.conf_thresh, h->cfg.range_min, h->cfg.range_max, h->d_state, h->d_state_oov, h->d_bc_oov, ws, 0, 1);
-    };
-    hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    for (int i = 0; i < 3 && reps > 0; i++) launch();              // (reps <= 0: only the block census of the last real frame)
-    (void)hipEventRecord(e0, h->stream);
-    for (int i = 0; i < reps; i++) launch();
-    (void)hipEventRecord(e1, h->stream);
-    (void)hipStreamSynchronize(h->stream);
-    float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (blocks2) {
-        const int nb = (span + 255) / 256;
-        std::vector<uint32_t> bc((size_t)std::max(nb, 1));
-        if (nb > 0) (void)hipMemcpy(bc.data(), h->d_bc_oov, (size_t)nb * 4, hipMemcpyDeviceToHost);
-        blocks2[0] = nb; blocks2[1] = 0;
-        for (int i = 0; i < nb; i++) blocks2[1] += bc[i] != 0u;
-    }
-    return reps > 0 ? 1000.0 * ms / reps : 0.0;
-}
-// one fuse launch on the current frame with every workgroup leaving its three ticks (g_fuse_trace in ssf_track_fuse.hip): out =
-// 3 x workgroups words, arms4 = workgroups of update | insertion | visible rows | out-of-view span.  Returns the workgroups, < 0: n/a.
-int ssf_dbg_trace_fuse(ssf_handle* h, unsigned long long* out, int cap_wgs, int* arms4, int mode /* as ssf_dbg_time_fuse */) {
-    if (!h || !h->have_frame || !h->cc || !out || !arms4) return -1;
-    arms4[0] = (mode & 2) ? 0 : (h->S + 31) / 32; arms4[1] = (mode & 2) ? 0 : (h->S + 255) / 256; arms4[2] = (mode & 4) ? 0 : (h->n_visible + 255) / 256;
-    long long b2[2];
-    unsigned long long* d = nullptr;
-    const size_t words = (size_t)3 * 65536;
-    if (hipMalloc((void**)&d, words * 8) != hipSuccess) return -2;
-    (void)hipMemset(d, 0, words * 8);
-    set_fuse_trace(d);
-    (void)ssf_dbg_time_fuse(h, 1, mode, b2);         // (3 warm launches with the trace on, then the one whose ticks stay)
-    set_fuse_trace(nullptr);
-    std::vector<unsigned long long> all(words);
-    (void)hipMemcpy(all.data(), d, words * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    int n = 0;
-    for (int i = 0; i < 65536; i++) if (all[3 * (size_t)i]) n = i + 1;
-    arms4[3] = n - arms4[0] - arms4[1] - arms4[2];
-    const int m = n < cap_wgs ? n : cap_wgs;
-    std::memcpy(out, all.data(), (size_t)m * 24);
-    return m;
-}
-#endif
-// ablation timer for the relabelling pass (tools/pass_probe.py); leaves the segmentation state garbage
-// lab build: tiles of the last extracted frame (slot 0 of the active context) that proved themselves clean, per pass
-// (FrameMaps::epoch[1 + pass], counted by k_update_pass under SSF_EXPERIMENTS; tools/skip_probe.py)
 // streams waiting in the process-wide pool for the next handle (StreamPool)
 int ssf_pooled_streams(void) {
     StreamPool& sp = stream_pool();
@@ -2926,95 +2257,6 @@ int ssf_upload_stats(ssf_handle* h, double* out6) {
     return SSF_OK;
 }
 #ifdef SSF_EXPERIMENTS          // (laboratory build only: probes of tools/, not part of the product)
-// the relabelling statistics of the frame just processed (FrameMaps::epoch, SSF_PASS_STAT_* in ssf_extract.hip): out64[8 .. 12];
-// collected only after ssf_dbg_pass_stats_enable(1)
-int ssf_dbg_pass_stats_enable(int on) { set_pass_stats(on ? 1 : 0); return SSF_OK; }
-int ssf_dbg_pass_stats(ssf_handle* h, uint32_t* out64) {
-    if (!h || !h->active.ctx || !out64) return SSF_ERR_INVALID_ARG;
-    HCK(hipStreamSynchronize(h->active.ctx->stream));
-    HCK(hipMemcpy(out64, h->active.maps.epoch, 64 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return SSF_OK;
-}
-double ssf_dbg_time_pass(ssf_handle* h, int reps, int rgbd, int dbg, int nb) {
-    if (!h || !h->active.ctx) return -1.0;
-    ExtractCtx& c = *h->active.ctx;                   // all slots of the batch context (nb <= extract_batch)
-    nb = std::max(1, std::min(nb, h->batch));
-    hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    const int ox[4] = {0, 1, 0, 1}, oy[4] = {0, 1, 1, 0};
-    for (int i = 0; i < 4; i++) launch_update_pass(h->stream, h->seg, c.maps, nb, 20 + i, ox[i & 3], oy[i & 3], rgbd != 0, dbg);
-    (void)hipEventRecord(e0, h->stream);
-    for (int i = 0; i < reps; i++) launch_update_pass(h->stream, h->seg, c.maps, nb, 24 + i, ox[i & 3], oy[i & 3], rgbd != 0, dbg);
-    (void)hipEventRecord(e1, h->stream);
-    (void)hipStreamSynchronize(h->stream);
-    float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return 1000.0 * ms / reps;
-}
-// one pass launch over nb frames of the active context with every workgroup leaving its five ticks (g_pass_trace, ssf_extract.hip);
-// `k` = the pass number (>= 20 with rgbd: the frames' state is that of a finished extract, a late pass' workload).  out: 5 words per
-// workgroup, grid3 = the launch's grid.  Returns the workgroups copied, < 0: n/a.  Leaves the segmentation state advanced by five passes.
-int ssf_dbg_trace_pass(ssf_handle* h, int rgbd, int nb, unsigned long long* out, int cap_wgs, int* grid3) {
-    if (!h || !h->active.ctx || !out || !grid3) return -1;
-    ExtractCtx& c = *h->active.ctx;
-    nb = std::max(1, std::min(nb, h->batch));
-    const int ox[4] = {0, 1, 0, 1}, oy[4] = {0, 1, 1, 0};
-    grid3[0] = (h->cfg.width + 30 + 31) / 32; grid3[1] = (h->cfg.height + 31) / 32; grid3[2] = nb;
-    const int n = grid3[0] * grid3[1] * grid3[2];
-    unsigned long long* d = nullptr;
-    if (hipMalloc((void**)&d, (size_t)n * 40) != hipSuccess) return -2;
-    (void)hipMemset(d, 0, (size_t)n * 40);
-    for (int i = 0; i < 4; i++) launch_update_pass(h->stream, h->seg, c.maps, nb, 20 + i, ox[i & 3], oy[i & 3], rgbd != 0, 0);
-    (void)hipStreamSynchronize(h->stream);
-    set_pass_trace(d);
-    launch_update_pass(h->stream, h->seg, c.maps, nb, 24, ox[0], oy[0], rgbd != 0, 0);
-    (void)hipStreamSynchronize(h->stream);
-    set_pass_trace(nullptr);
-    const int m = std::min(n, cap_wgs);
-    (void)hipMemcpy(out, d, (size_t)m * 40, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    return m;
-}
-
+#include "lab/host_probes.inc"
 #endif
-// ---- test hooks (include/ssf_testing.h): the host solvers, so they can be pinned on a CPU box ----------
-int ssf_dbg_ldlt_solve6(const double* A, const double* b, double* x) { sym6_ldlt_solve(A, b, x); return 0; }
-int ssf_dbg_lu_inverse6(const double* A, double* Ainv) { mat6_inverse_lu(A, Ainv); return 0; }
-int ssf_dbg_renormalise_d(double* R9) { renormalise_rotation<double>(R9); return 0; }
-int ssf_dbg_renormalise_f(float* R9) { renormalise_rotation<float>(R9); return 0; }
-int ssf_dbg_gn_increment(const double* X6, double* tf16) { gn_increment(X6, tf16); return 0; }
-int ssf_dbg_align_increment(const double* JtJ, const double* Jtr, float scale, const float* cs, const float* ct, double* tf16) {
-    align_increment(JtJ, Jtr, scale, cs, ct, tf16); return 0;
-}
-
-int ssf_dbg_rgb_to_lab(const float* c, float* o) { V3 r = rgb_to_lab(v3(c[0], c[1], c[2])); o[0] = r.x; o[1] = r.y; o[2] = r.z; return 0; }
-int ssf_dbg_lab_to_rgb(const float* c, float* o) { V3 r = lab_to_rgb(v3(c[0], c[1], c[2])); o[0] = r.x; o[1] = r.y; o[2] = r.z; return 0; }
-int ssf_dbg_sym_inverse(const float* c, float* o) {
-    Sym3 out; const bool ok = sym_inverse(sym3(c[0], c[1], c[2], c[3], c[4], c[5]), out);
-    o[0] = out.xx; o[1] = out.xy; o[2] = out.xz; o[3] = out.yy; o[4] = out.yz; o[5] = out.zz; return ok ? 1 : 0;
-}
-int ssf_dbg_principal_frame(const float* c, float* vecs, float* vals) {
-    M3 m; V3 v; principal_frame(sym3(c[0], c[1], c[2], c[3], c[4], c[5]), m, v);
-    const float o[9] = {m.r0.x, m.r0.y, m.r0.z, m.r1.x, m.r1.y, m.r1.z, m.r2.x, m.r2.y, m.r2.z};
-    std::memcpy(vecs, o, sizeof(o)); vals[0] = v.x; vals[1] = v.y; vals[2] = v.z; return 0;
-}
-// img9: a 3 x 3 label patch, row-major; returns 1 when the centre pixel is a bridge (its label may not change)
-int ssf_dbg_connectivity_guard(const int32_t* g) { return guard_unchangeable(guard_ring(g[4], g[0], g[1], g[2], g[5], g[8], g[7], g[6], g[3])) ? 1 : 0; }
-int ssf_dbg_plane_solve(const float* r, float* th) {
-    float a = 0, b = 0, c = 0;
-    const bool ok = plane_solve(a, b, c, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], r[10], r[11]);
-    th[0] = a; th[1] = b; th[2] = c; return ok ? 1 : 0;
-}
-
-static M3 m3_from9(const float* a) { return m3(v3(a[0], a[1], a[2]), v3(a[3], a[4], a[5]), v3(a[6], a[7], a[8])); }
-static void m3_to9(const M3& m, float* o) { o[0] = m.r0.x; o[1] = m.r0.y; o[2] = m.r0.z; o[3] = m.r1.x; o[4] = m.r1.y; o[5] = m.r1.z; o[6] = m.r2.x; o[7] = m.r2.y; o[8] = m.r2.z; }
-static void sym_to6(const Sym3& s, float* o) { o[0] = s.xx; o[1] = s.xy; o[2] = s.xz; o[3] = s.yy; o[4] = s.yz; o[5] = s.zz; }
-int ssf_dbg_sym_square(const float* c, float* o) { sym_to6(sym_square(sym3(c[0], c[1], c[2], c[3], c[4], c[5])), o); return 0; }
-int ssf_dbg_sym_mulv(const float* c, const float* v, float* o) { V3 r = sym_mul(sym3(c[0], c[1], c[2], c[3], c[4], c[5]), v3(v[0], v[1], v[2])); o[0] = r.x; o[1] = r.y; o[2] = r.z; return 0; }
-int ssf_dbg_mult_abat(const float* R9, const float* c, float* o) { sym_to6(rot_sym(m3_from9(R9), sym3(c[0], c[1], c[2], c[3], c[4], c[5])), o); return 0; }
-int ssf_dbg_m3_mul(const float* A9, const float* B9, float* o) { m3_to9(m3_mul(m3_from9(A9), m3_from9(B9)), o); return 0; }
-int ssf_dbg_m3_mulv(const float* A9, const float* v, float* o) { V3 r = m3_mulv(m3_from9(A9), v3(v[0], v[1], v[2])); o[0] = r.x; o[1] = r.y; o[2] = r.z; return 0; }
-int ssf_dbg_row_mul(const float* v, const float* A9, float* o) { V3 r = row_mul(v3(v[0], v[1], v[2]), m3_from9(A9)); o[0] = r.x; o[1] = r.y; o[2] = r.z; return 0; }
-int ssf_dbg_rot_to_quat(const float* R9, float* q4) { rot_to_quat(m3_from9(R9), q4); return 0; }
-int ssf_dbg_quat_to_rot(const float* q4, float* R9) { m3_to9(quat_to_rot_quirk(q4), R9); return 0; }
-
 }  // extern "C"
