@@ -807,7 +807,7 @@ class Fusion:
         self._ck(self.L.lib.ssf_debug_set_max_passes(self.h, n), "ssf_debug_set_max_passes")
 
     def set_bin_min_rows(self, n):
-        """visible rows from which a frame's tracking streams a tile-sorted copy of them (product default: never; 0 = always)"""
+        """visible rows from which a frame's tracking streams a tile-sorted copy of them (product default: 400 000; 0 = always, < 0 = never)"""
         self._ck(self.L.lib.ssf_debug_set_bin_min_rows(self.h, int(n)), "ssf_debug_set_bin_min_rows")
 
     def set_shard(self, id_offset, global_n_model, global_n_visible):

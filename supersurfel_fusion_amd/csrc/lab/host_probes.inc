@@ -73,10 +73,10 @@ double ssf_dbg_time_fuse(ssf_handle* h, int reps, int mode, long long* blocks2 /
     ws.ticket = h->d_part_ticket; ws.other = h->d_part + (size_t)(h->part_set ^ 1) * h->part_words; ws.words = h->part_words;
     const int S = (mode & 2) ? 0 : h->S, nvis = (mode & 4) ? 0 : h->n_visible, span = (mode & 1) ? 0 : h->oov_tail - h->oov_head;
     auto launch = [&] {
-        launch_fuse(h->stream, M, h->cc->frame, h->pose, h->stamp, h->id_offset, nvis, h->cc->d_best, h->cc->d_matched, h->d_cand,
-                    S, (nvis > 0 && S > 0) ? 1 : 0, h->cfg.nb_supersurfels_max, 0, 1, h->cfg.shard_tile, h->d_cnt,
-                    h->cam, h->oov[h->ocur], span, h->cc->maps.plane_depth, h->cfg.delta_t,
-                    h->cfg.conf_thresh, h->cfg.range_min, h->cfg.range_max, h->d_state, h->d_state_oov, h->d_bc_oov, ws, 0, 1);
+        ClassifyArgs ca = h->classify; ca.plane_depth = h->cc->maps.plane_depth;
+        launch_fuse(h->stream, M, h->cc->frame, h->pose, h->stamp, h->id_offset, nvis, AssocTables{h->cc->d_best, h->cc->d_matched, h->d_cand, S},
+                    (nvis > 0 && S > 0) ? 1 : 0, h->cfg.nb_supersurfels_max, ShardArgs{0, 1, 0, h->cfg.shard_tile}, h->d_cnt,
+                    h->oov[h->ocur], span, ca, h->d_state, h->d_state_oov, h->d_bc_oov, ws, 1);
     };
     hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     for (int i = 0; i < 3 && reps > 0; i++) launch();              // (reps <= 0: only the block census of the last real frame)

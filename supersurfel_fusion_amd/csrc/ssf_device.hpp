@@ -286,6 +286,11 @@ SSF_HD unsigned int icp_go_word_weight(unsigned int dword) {      // dword 0..11
 SSF_HD unsigned int icp_go_abort_check(unsigned int want) { return ((want * 0x9E3779B1u) >> 2) & SSF_ICP_GO_CHECK_MASK; }
 #define SSF_ICP_GO_SLOTS 4
 struct MatchArgs { float zmin, zmax; long long id_offset; unsigned long long* best; uint8_t* matched; int32_t* cand; };    // launch_match's arguments
+// what the fuse launches take in groups: the classification of a row (filterModel) | this shard's place among the ranks (migrate:
+// updated rows that cross a tile edge leave) | the frame's association tables (launch_match's output; S frame supersurfels)
+struct ClassifyArgs { Cam cam; const float* plane_depth; int delta_t; float conf_thresh, zmin, zmax; };
+struct ShardArgs { int rank, nranks, migrate; float tile; };
+struct AssocTables { const unsigned long long* best; const uint8_t* matched; const int32_t* cand; int S; };
 int icp_variant_mode();              // 0: the product's k_icp; other values: measurement arms that cannot take SSF_ICP_GO_MATCH
 void launch_icp(hipStream_t st, const Cam& cam, SurfelSoA model, int n_visible, const uint2* pix2, const float4* fpack,
                 Rt T, long long* replicas, unsigned int* ticket,
@@ -315,10 +320,8 @@ struct PartitionWs { uint32_t* sup_vis; uint32_t* sup_oov; uint32_t* tot; uint32
 // launch_move_rows sends to the host: sequence number cnt_seq there).  do_update = 0 skips the update (no visible rows anywhere);
 // span_upper = host upper bound of the out-of-view span; cand = launch_match's per-row candidate.
 void launch_fuse(hipStream_t st, SurfelSoA model /* visible array */, SurfelSoA frame, Rt pose, int stamp, long long id_offset,
-                 int n_visible, const unsigned long long* best, const uint8_t* matched, const int32_t* cand, int S, int do_update,
-                 int capacity, int rank, int nranks, float tile, Counters* cnt, const Cam& cam, OovStore oov,
-                 int span_upper, const float* plane_depth, int delta_t, float conf_thresh, float zmin, float zmax,
-                 uint8_t* state_vis, uint8_t* state_oov, uint32_t* bc_oov, const PartitionWs& ws, int migrate = 0,
+                 int n_visible, const AssocTables& at, int do_update, int capacity, const ShardArgs& sh, Counters* cnt, OovStore oov,
+                 int span_upper, const ClassifyArgs& ca, uint8_t* state_vis, uint8_t* state_oov, uint32_t* bc_oov, const PartitionWs& ws,
                  int tail_in_move = 0 /* the launch ends without turning the class totals into counters: launch_move_rows(totals) does */);
 // launch_move_rows(totals != nullptr): the fuse launch ended without its tail; every block of the move kernel takes the old
 // counts from here (the host mirrors them) and the class totals from the partition's replicas, block 0 finalises the counters
@@ -334,25 +337,22 @@ struct MoveTotals { int from_tot, nv /* visible rows before the frame */, head_o
 // slots zero); after the tables of all ranks have been summed, launch_migrate_in appends the rows addressed to this
 // rank behind this frame's insertions (ascending f), classifies them and corrects the partition sums and both
 // counter sets; launch_move_rows then treats them like inserted rows.
-void launch_pack_emigrants(hipStream_t st, SurfelSoA model, const unsigned long long* best, const uint8_t* matched, long long id_offset,
-                           int n_visible, const uint8_t* state_vis, int S, int do_update, int nranks, float tile, int32_t* table);
-void launch_migrate_in(hipStream_t st, SurfelSoA model, const int32_t* table, int S, int rank, int capacity, Counters* cnt,
-                       const Cam& cam, Rt pose, int stamp, const float* plane_depth, int delta_t, float conf_thresh, float zmin,
-                       float zmax, uint8_t* state_vis, const PartitionWs& ws);
+void launch_pack_emigrants(hipStream_t st, SurfelSoA model, const AssocTables& at, long long id_offset, int n_visible,
+                           const uint8_t* state_vis, int do_update, const ShardArgs& sh, int32_t* table);
+void launch_migrate_in(hipStream_t st, SurfelSoA model, const int32_t* table, int S, int capacity, Counters* cnt, const ShardArgs& sh,
+                       const ClassifyArgs& ca, Rt pose, int stamp, uint8_t* state_vis, const PartitionWs& ws);
 // re-homing of a sharded map (ssf_rehome_begin / _end): split the dense view into the rows that stay (-> stay, ranks closed,
 // visible block first) and the rows that leave (-> migrant-table records); bc: 3 words per block of 256 rows, tot3: totals
 // (staying, leaving, staying rows of the visible block); unpack: records -> rows [base, base + n) of dst
 void launch_rehome_split(hipStream_t st, SurfelSoA dense, int n, int n_visible, int rank, int nranks, float tile, uint32_t* bc, int* tot3,
                          SurfelSoA stay, int32_t* table, int table_rows);
 void launch_rehome_unpack(hipStream_t st, const int32_t* table, int n, SurfelSoA dst, int base);
-void launch_first_frame(hipStream_t st, SurfelSoA model, SurfelSoA frame, Rt pose, int S, int capacity, int rank,
-                        int nranks, float tile, Counters* cnt);
-// first ICP iteration of the next frame, accumulated by the row-move kernel of this one (launch_classify_reorder)
-struct NextFrameIcp {
-    const uint2* pix2; const float4* fpack;   // packed tables of the next frame
-    Rt T;                                     // model -> camera transform of that iteration
-    long long* replicas; unsigned int* ticket; long long* sums; unsigned long long seq;
-    const struct P2PView* pv;                 // non-null: the record is traded with the peers (see P2PView below)
+void launch_first_frame(hipStream_t st, SurfelSoA model, SurfelSoA frame, Rt pose, int S, int capacity, const ShardArgs& sh, Counters* cnt);
+// first ICP iteration of the next frame, accumulated by the row-move kernel of this one (k_move_rows<true, .> takes this record as it is)
+struct NextIcp {
+    Cam cam; const uint2* pix2; const float4* fpack;   // packed tables of the next frame
+    Rt T;                                               // model -> camera transform of that iteration
+    long long* replicas; unsigned int* ticket; long long* sums; Mailbox* mb; unsigned long long seq;
 };
 // Model store: the visible rows are a dense array (two of them, ping-pong); the out-of-view
 // rows live in a deque-like store with a live flag per row.  The per-frame stable partition
@@ -362,11 +362,11 @@ struct NextFrameIcp {
 // behind it and clears the live flag of B0/B2: the (large) B1 block is never touched.
 // launch_move_rows moves the rows accordingly (after launch_fuse); nv_upper / span_upper = host upper bounds of the
 // visible rows (incl. insertions) and of the out-of-view span; next != nullptr: also accumulate the next frame's
-// first ICP iteration
-void launch_move_rows(hipStream_t st, const Cam& cam, SurfelSoA vis_src, SurfelSoA vis_dst, OovStore oov, int nv_upper, int span_upper,
+// first ICP iteration (next_pv != nullptr: and trade its record with the peers, see P2PView below)
+void launch_move_rows(hipStream_t st, SurfelSoA vis_src, SurfelSoA vis_dst, OovStore oov, int nv_upper, int span_upper,
                       const uint8_t* state_vis, const uint8_t* state_oov, const uint32_t* bc_oov, const PartitionWs& ws,
-                      Counters* cnt /* [2]: see launch_fuse */, Mailbox* mb, unsigned long long cnt_seq, const NextFrameIcp* next,
-                      const MoveTotals* totals = nullptr);
+                      Counters* cnt /* [2]: see launch_fuse */, Mailbox* mb, unsigned long long cnt_seq, const NextIcp* next,
+                      const struct P2PView* next_pv = nullptr, const MoveTotals* totals = nullptr);
 // stable compaction of the live out-of-view rows of src (span from the device counters) into dst starting at
 // new_head (dst.live must be zero where it matters); set_span != 0: cnt->oov_head / oov_tail := the new span
 void launch_oov_compact(hipStream_t st, OovStore src, OovStore dst, int span_upper, int new_head, uint32_t* bc_oov, Counters* cnt,

@@ -116,12 +116,24 @@ struct ActiveFrame {
 };
 
 // Round 6: the tile-sorted copy (ssf_tile_rows.inc) in the product, for LARGE visible sets.  At BASELINE config 3 (940 k visible
-// rows, ten iterations) it takes k_icp from 23.0 to 18.8 us per iteration and the association from 55.6 to 29.9 us for a 35 us sort
+// rows, ten iterations) it takes k_icp from 23.0 to 19.1 us per iteration and k_match from 55.3 to 31.7 us for a 35 us sort
 // (profiles/config3_sorted_rows_r06.txt); at the metric's 120 k visible rows and four iterations the sort costs more than it saves,
 // hence the threshold.  -DSSF_BIN_MIN_ROWS_DEFAULT=-1 builds a product without it (the A/B).
 #ifndef SSF_BIN_MIN_ROWS_DEFAULT
 #define SSF_BIN_MIN_ROWS_DEFAULT 400000
 #endif
+// The copy has ONE rule.  It is valid from the launch_bin_rows that made it (make_if_large, at the start of a frame's tracking) until the first
+// of icp_begin (another frame, or another pose to sort by), fuse_begin (which EVERY frame passes before its rows are rewritten and
+// n_visible changes -- also the frame whose association ran inside the waiting k_icp launch and never entered do_match) and
+// store_from_dense (the visible array replaced outside a frame: ssf_set_model, deformation, re-homing).  Each of the three calls
+// drop; nothing else writes `valid`.  While it is valid the ICP and association launches stream `rows` (icp_rows).
+struct TileCopy {
+    SurfelSoA rows{};                             // rows.pos: one 48-byte record per row (k_bin_scatter); the other streams stay null
+    int32_t* d_idx = nullptr; uint32_t* d_count = nullptr; uint32_t* d_cursor = nullptr;       // launch_match's flag "sorted records" | bin_buffer_words each
+    bool valid = false; int min_rows = SSF_BIN_MIN_ROWS_DEFAULT;      // min_rows: visible rows from which a frame's tracking makes the copy (< 0: never)
+    int make_if_large(ssf_handle* h);             // (ssf_host.hip) the frame's copy, if it wants one: on first use the buffers, then launch_bin_rows
+    void drop() { valid = false; }
+};
 // The device buffers a workspace owns.  grow is all or nothing: allocate every (pointer, bytes) of `want`; only when all succeeded
 // free the old buffers and install the new ones.  A failed hipMalloc leaves its error behind in the runtime: it is cleared, so
 // that the next frame's launch checks do not report it.  release frees whatever grow installed, and so does the destructor (a
@@ -268,10 +280,9 @@ struct ssf_handle {
     // word (launch_icp, IcpGo): slots in fine-grained device memory the host stores into directly
     IcpGo* go = nullptr; bool icp_chain = true; unsigned long long go_count = 0;
     bool graph_failed = false; hipStream_t capture_stream = nullptr;
-    // tile-sorted copy of the visible rows' ICP / association fields (launch_bin_rows), made at the start of a frame's
-    // tracking when the visible set is large (bin_min_rows); valid for that frame only
-    SurfelSoA bins{}; int32_t* d_bin_idx = nullptr; uint32_t* d_bin_count = nullptr; uint32_t* d_bin_cursor = nullptr;
-    bool bins_valid = false; int bin_min_rows = SSF_BIN_MIN_ROWS_DEFAULT;      // visible rows from which a frame's tracking streams the tile-sorted copy (< 0: never)
+    TileCopy bins;                                // tile-sorted copy of the visible rows' ICP / association fields, for large visible sets
+    // what the fuse launches take as groups: built by ssf_create; plane_depth and migrate are the frame's (fuse_begin)
+    ClassifyArgs classify{}; ShardArgs shard{};
     // pass_team: the relabelling passes of a phase as ONE launch with a frame per XCD (k_passes_team) instead of a launch per pass.
     // Its workgroups must all be on the chip at once, so whole batches take turns across the contexts (launch_batch: a batch's
     // chain waits for the previous batch's ev_done).

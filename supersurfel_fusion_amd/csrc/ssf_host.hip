@@ -619,13 +619,21 @@ static int do_extract(ssf_handle* h, const void* rgb, const void* depth, int on_
     return rc ? rc : activate_oldest(h);
 }
 
+// a single shard with no exchange of any kind | a shard of a map that runs its exchanges natively (RCCL or peer-to-peer) | an ICP
+// iteration is ONE launch (also on peer-to-peer shards: its last workgroup trades the record), as chained launches and the record made ahead need
+static inline bool single_shard_alone(const ssf_handle* h) { return h->cfg.nranks == 1 && !h->comm && !h->p2p.on; }
+static inline bool exchanges_natively(const ssf_handle* h) { return h->comm || h->p2p.on; }
+static inline bool icp_is_one_launch(const ssf_handle* h) { return single_shard_alone(h) || (h->p2p.on && !h->comm); }
+// rows of the whole map (the sum over the shards once it is known, ssf_stage_set_shard / comm_counts): the same decision on every rank
+static inline long long total_model(const ssf_handle* h) { return (h->cfg.nranks > 1 && h->global_n_model >= 0) ? h->global_n_model : h->n_model; }
+static inline long long total_visible(const ssf_handle* h) { return (h->cfg.nranks > 1 && h->global_n_visible >= 0) ? h->global_n_visible : h->n_visible; }
 static void icp_start_from(IcpLoop& I, const Rt& pose) {
     I.R_init = m3_transpose(pose.R);
     I.t_init = negate(m3_mulv(I.R_init, pose.t));
     for (int i = 0; i < 16; i++) I.tf_inc[i] = (i % 5 == 0) ? 1.0 : 0.0;
 }
 static void icp_begin(ssf_handle* h, const float* prior) {
-    h->bins_valid = false;                        // (process_oldest makes this frame's tile-sorted copy after this call)
+    h->bins.drop();                               // (process_oldest makes this frame's tile-sorted copy after this call)
     if (prior) h->pose = pose_from12(prior);
     IcpLoop& I = h->icp;
     // a record accumulated ahead is this frame's first iteration only if nothing it was computed from has changed
@@ -633,8 +641,7 @@ static void icp_begin(ssf_handle* h, const float* prior) {
     if (h->ahead.valid && !prior && h->have_frame && h->active.ctx == h->ahead.ctx && h->active.slot == h->ahead.slot &&
         h->stamp == h->ahead.stamp && std::memcmp(&h->pose, &h->ahead.pose, sizeof(Rt)) == 0) I.ahead_seq = h->ahead.seq;
     h->ahead.valid = false;
-    const long long nvis = (h->cfg.nranks > 1 && h->global_n_visible >= 0) ? h->global_n_visible : h->n_visible;
-    I.active = nvis > 0 && h->cfg.icp_iter > 0;
+    I.active = total_visible(h) > 0 && h->cfg.icp_iter > 0;
     I.valid = true; I.done = !I.active; I.iter = 0;
     icp_start_from(I, h->pose);
     for (int i = 0; i < 36; i++) I.JtJ[i] = 0.0;
@@ -647,8 +654,6 @@ static void inc_to_float(const double* tf, M3& R, V3& t) {
            v3((float)tf[8], (float)tf[9], (float)tf[10]));
     t = v3((float)tf[3], (float)tf[7], (float)tf[11]);
 }
-// device accumulate; the record lands in d_icp and in the mailbox (h_icp points at the mailbox copy)
-static int icp_fetch(ssf_handle* h, unsigned long long seq, IcpGo* waiter = nullptr, unsigned long long waiter_go_seq = 0, bool* waiter_dismissed = nullptr);
 // model -> camera transform of the coming iteration
 static Rt icp_transform(IcpLoop& I) {
     M3 R_inc; V3 t_inc;
@@ -657,22 +662,40 @@ static Rt icp_transform(IcpLoop& I) {
     Rt T; T.R = m3_mul(R_inc, I.R_init); T.t = add(m3_mulv(R_inc, I.t_init), t_inc);
     return T;
 }
-// the rows an ICP / association launch streams: the visible array, or its tile-sorted copy when this frame has one
-static inline const SurfelSoA& icp_rows(const ssf_handle* h) { return h->bins_valid ? h->bins : h->model[h->mcur]; }
-static int icp_accumulate(ssf_handle* h, bool to_host, long long* d_out = nullptr) {
-    IcpLoop& I = h->icp;
-    const Rt T = icp_transform(I);
-    const unsigned long long seq = ++h->icp_seq;
-    launch_icp(h->stream, h->cam, icp_rows(h), h->n_visible, h->cc->maps.pix2, h->cc->maps.fpack, T,
-               h->d_icp_replicas, h->d_tickets + 8, d_out ? d_out : h->d_icp, h->mb_dev, seq, -1, nullptr, 0, nullptr, h->bins_valid ? 1 : 0);
-    HCK(hipGetLastError());
-    return to_host ? icp_fetch(h, seq) : SSF_OK;
+// drain the write-combining buffers: the stores above become visible to the device in order, now
+static inline void store_fence() {
+#if defined(__x86_64__)
+    __builtin_ia32_sfence();
+#else
+    __atomic_thread_fence(__ATOMIC_SEQ_CST);
+#endif
 }
-// wait for mailbox record `seq` and copy it to h->h_icp_local
-static void icp_release_waiting(IcpGo* slot, unsigned long long go_seq, const Rt* T, unsigned long long p2p_seq = 0, bool match = false);
-// waiter: a launch made ahead that is waiting on the device for the host's word (chained ICP launches).  Before the stream
-// is drained it is told to leave (*waiter_dismissed = true): it would otherwise hold the stream until its own bound expires.
-static int icp_fetch(ssf_handle* h, unsigned long long seq, IcpGo* waiter, unsigned long long waiter_go_seq, bool* waiter_dismissed) {
+// the host's word to a waiting launch: its transform and "go", or "no further iteration"
+static void icp_release_waiting(IcpGo* slot, unsigned long long go_seq, const Rt* T, unsigned long long p2p_seq = 0, bool match = false) {
+    volatile IcpGo* s = slot;
+    const unsigned long long want = go_seq & 0xFFFFFFFFull;
+    if (T) {
+        const float v[12] = {T->R.r0.x, T->R.r0.y, T->R.r0.z, T->R.r1.x, T->R.r1.y, T->R.r1.z, T->R.r2.x, T->R.r2.y, T->R.r2.z,
+                             T->t.x, T->t.y, T->t.z};
+        uint32_t w[12]; memcpy(w, v, sizeof w);
+        uint32_t sum = (uint32_t)p2p_seq * icp_go_word_weight(14) + (uint32_t)(p2p_seq >> 32) * icp_go_word_weight(15);
+        for (unsigned int i = 0; i < 12; i++) sum += w[i] * icp_go_word_weight(i);
+        // the whole line, then ONE fence: the write-combining buffer goes out as one 64-byte write (were it ever split, the
+        // checksum in the flag word keeps the kernel polling until the rest has landed)
+        for (int i = 0; i < 12; i++) s->T[i] = v[i];
+        s->x = p2p_seq;
+        s->flag = want | ((unsigned long long)((sum >> 2) & SSF_ICP_GO_CHECK_MASK) << 32) | (match ? SSF_ICP_GO_MATCH : 0ull);
+    } else s->flag = want | ((unsigned long long)icp_go_abort_check((unsigned int)want) << 32) | SSF_ICP_GO_ABORT;
+    store_fence();
+}
+
+// a launch made ahead that is waiting on the device for the host's word: the slot the word goes to, the number the word
+// carries and the sequence number of the record the launch will publish
+struct IcpWaiter { bool waiting = false; IcpGo* slot = nullptr; unsigned long long go_seq = 0, seq_rec = 0; };
+// wait for mailbox record `seq` and copy it to h->h_icp_local (h_icp then points at that copy).  waiter: the launch made ahead, if one
+// is waiting.  Before the stream is drained it is told to leave (waiter->waiting = false: the next iteration, if any, is launched
+// afresh): it would otherwise hold the stream until its own bound expires.
+static int icp_fetch(ssf_handle* h, unsigned long long seq, IcpWaiter* waiter = nullptr) {
     // the record is five 64-byte lines that each end in the sequence number (Mailbox::icp_rec): accept it when all
     // five carry `seq` and the checksum over the payload matches; anything else is a record still in flight
     const volatile unsigned long long* rec = h->mb_host->icp_rec;
@@ -701,7 +724,7 @@ static int icp_fetch(ssf_handle* h, unsigned long long seq, IcpGo* waiter, unsig
                               h->cfg.nranks, h->stamp, h->icp.iter, seq, h->p2p.seq_icp, h->n_visible);
                 h->err = std::string("ICP mailbox record never arrived") + where; return SSF_ERR_DEVICE;
             }
-            if (waiter) { icp_release_waiting(waiter, waiter_go_seq, nullptr); if (waiter_dismissed) *waiter_dismissed = true; waiter = nullptr; }
+            if (waiter) { icp_release_waiting(waiter->slot, waiter->go_seq, nullptr); waiter->waiting = false; waiter = nullptr; }
             hipError_t e = hipStreamSynchronize(h->stream);
             if (e != hipSuccess) { h->err = std::string("device error while waiting for the ICP record: ") + hipGetErrorString(e); return SSF_ERR_DEVICE; }
             drained = true; t0 = std::chrono::steady_clock::now();
@@ -712,6 +735,24 @@ static int icp_fetch(ssf_handle* h, unsigned long long seq, IcpGo* waiter, unsig
     }
     h->h_icp = h->h_icp_local;
     return SSF_OK;
+}
+// the rows an ICP / association launch streams: the visible array, or its tile-sorted copy when this frame has one
+static inline const SurfelSoA& icp_rows(const ssf_handle* h) { return h->bins.valid ? h->bins.rows : h->model[h->mcur]; }
+// THE k_icp launch of the frame path: the current frame's tables, the rows above, the handle's reduction buffers and mailbox
+// (sums_out: the record's place on the device, nullptr = h->d_icp; go, go_seq, pv, match: as launch_icp's)
+static int icp_issue(ssf_handle* h, const Rt& T, unsigned long long seq, long long* sums_out = nullptr, IcpGo* go = nullptr,
+                     unsigned long long go_seq = 0, const P2PView* pv = nullptr, const MatchArgs* match = nullptr) {
+    launch_icp(h->stream, h->cam, icp_rows(h), h->n_visible, h->cc->maps.pix2, h->cc->maps.fpack, T, h->d_icp_replicas, h->d_tickets + 8,
+               sums_out ? sums_out : h->d_icp, h->mb_dev, seq, -1, go, go_seq, pv, h->bins.valid ? 1 : 0, match);
+    HCK(hipGetLastError());
+    return SSF_OK;
+}
+// one iteration's record under the loop's current transform (pv: summed over the peers by the launch itself)
+static int icp_accumulate(ssf_handle* h, bool to_host, long long* d_out = nullptr, const P2PView* pv = nullptr) {
+    const Rt T = icp_transform(h->icp);
+    const unsigned long long seq = ++h->icp_seq;
+    const int rc = icp_issue(h, T, seq, d_out, nullptr, 0, pv);
+    return (rc || !to_host) ? rc : icp_fetch(h, seq);
 }
 static void icp_update(ssf_handle* h, const int64_t* sums, int* again) {
     IcpLoop& I = h->icp;
@@ -806,6 +847,7 @@ int materialise(ssf_handle* h) {
 // the stores <- h->dense (n rows, the first n_visible of them visible); also resets the device counters
 int store_from_dense(ssf_handle* h, int n, int n_visible) {
     h->ahead.valid = false;                       // the model is replaced: a record accumulated ahead is stale
+    h->bins.drop();                               // ... and so is a tile-sorted copy of its visible rows (TileCopy's rule)
     h->model_gen++;
     int rc = copy_soa(h, h->model[h->mcur], h->dense, (size_t)n_visible);
     if (rc) return rc;
@@ -835,23 +877,12 @@ void drop_shard_sizes(ssf_handle* h) { h->all_valid = false; h->all_pending = fa
 // exchange != 0 (native multi-rank frame calls with the peer-to-peer backend): the association tables are traded with
 // the peers by the match launch's last workgroup -- or, when no rank has anything to match, by a launch of its own
 static int do_match(ssf_handle* h, int exchange = 0) {
-    const long long nmodel = (h->cfg.nranks > 1 && h->global_n_model >= 0) ? h->global_n_model : h->n_model;
-    const long long nvis = (h->cfg.nranks > 1 && h->global_n_visible >= 0) ? h->global_n_visible : h->n_visible;
-    const bool any = nmodel > 0 && nvis > 0;               // (global quantities: the same decision on every rank)
+    const bool any = total_model(h) > 0 && total_visible(h) > 0;               // (global quantities: the same decision on every rank)
     const int n = any ? h->n_visible : 0;
-    if (exchange && h->p2p.on) {
-        const P2PView pv = p2p_view(h, ++h->p2p.seq_assoc);
-        launch_match(h->stream, h->cam, icp_rows(h), n, h->cc->maps.pix2, h->cc->maps.fpack, h->pose, h->cfg.range_min,
-                     h->cfg.range_max, h->id_offset, h->cc->d_best, h->cc->d_matched, h->d_cand, h->S, h->bins_valid ? h->d_bin_idx : nullptr);
-        launch_p2p_assoc(h->stream, pv, h->cc->d_best, h->cc->d_matched, h->mb_dev);
-        HCK(hipGetLastError());
-        h->bins_valid = false;
-        return SSF_OK;
-    }
     launch_match(h->stream, h->cam, icp_rows(h), n, h->cc->maps.pix2, h->cc->maps.fpack, h->pose, h->cfg.range_min,
-                 h->cfg.range_max, h->id_offset, h->cc->d_best, h->cc->d_matched, h->d_cand, h->S, h->bins_valid ? h->d_bin_idx : nullptr);
+                 h->cfg.range_max, h->id_offset, h->cc->d_best, h->cc->d_matched, h->d_cand, h->S, h->bins.valid ? h->bins.d_idx : nullptr);
+    if (exchange && h->p2p.on) launch_p2p_assoc(h->stream, p2p_view(h, ++h->p2p.seq_assoc), h->cc->d_best, h->cc->d_matched, h->mb_dev);
     HCK(hipGetLastError());
-    h->bins_valid = false;                        // (the fuse launch that follows rewrites the rows the copy was made from)
     return SSF_OK;
 }
 
@@ -860,11 +891,12 @@ static int do_match(ssf_handle* h, int exchange = 0) {
 // sharded map exchanges the rows that crossed a tile edge (migrate: fuse_begin leaves this shard's migrant table in
 // h->d_migrants; fuse_end takes the rank-reduced table, or nullptr when nothing can arrive).
 static int fuse_begin(ssf_handle* h, int migrate) {
-    const long long nmodel_g = (h->cfg.nranks > 1 && h->global_n_model >= 0) ? h->global_n_model : h->n_model;
-    const long long nvis_g = (h->cfg.nranks > 1 && h->global_n_visible >= 0) ? h->global_n_visible : h->n_visible;
+    const long long nmodel_g = total_model(h), nvis_g = total_visible(h);
     SurfelSoA& M = h->model[h->mcur];
+    h->bins.drop();                               // (TileCopy's rule: from here on the frame rewrites the rows the copy was made from)
     h->fuse_first = !(nmodel_g > 0);
     h->fuse_migrate = migrate && h->cfg.nranks > 1 && !h->fuse_first;
+    h->classify.plane_depth = h->cc->maps.plane_depth; h->shard.migrate = h->fuse_migrate ? 1 : 0;
     if (nmodel_g > 0) {
         // out-of-view store upkeep before the frame's launches: room in front for the rows that leave the view (at
         // most all visible rows), room behind for out-of-view insertions, and not too many dead slots in the span
@@ -876,7 +908,7 @@ static int fuse_begin(ssf_handle* h, int migrate) {
         // a single shard: the fuse launch ends without its three-trip tail, the move kernel works the counters out from the class
         // totals (MoveTotals: the counts the frame starts from are mirrored here).  A sharded map keeps the tail: arrivals from
         // other ranks change the counters between the two launches (launch_migrate_in).
-        h->fuse_totals.from_tot = (h->cfg.nranks == 1 && !h->comm && !h->p2p.on && !h->fuse_migrate && h->move_totals_on) ? 1 : 0;
+        h->fuse_totals.from_tot = (single_shard_alone(h) && !h->fuse_migrate && h->move_totals_on) ? 1 : 0;
         h->fuse_totals.nv = h->n_visible; h->fuse_totals.head_old = h->oov_head; h->fuse_totals.tail_old = h->oov_tail;
         PartitionWs& ws = h->fuse_ws;
         {
@@ -886,14 +918,12 @@ static int fuse_begin(ssf_handle* h, int migrate) {
             h->part_set ^= 1;
         }
         // update | insert | classification of every row | publication of the counters: one launch
-        launch_fuse(h->stream, M, h->cc->frame, h->pose, h->stamp, h->id_offset, h->n_visible, h->cc->d_best, h->cc->d_matched, h->d_cand,
-                    h->S, nvis_g > 0 ? 1 : 0, h->cfg.nb_supersurfels_max, h->cfg.rank, h->cfg.nranks, h->cfg.shard_tile, h->d_cnt,
-                    h->cam, h->oov[h->ocur], h->oov_tail - h->oov_head, h->cc->maps.plane_depth, h->cfg.delta_t,
-                    h->cfg.conf_thresh, h->cfg.range_min, h->cfg.range_max, h->d_state, h->d_state_oov, h->d_bc_oov, ws,
-                    h->fuse_migrate ? 1 : 0, h->fuse_totals.from_tot);
+        const AssocTables at{h->cc->d_best, h->cc->d_matched, h->d_cand, h->S};
+        launch_fuse(h->stream, M, h->cc->frame, h->pose, h->stamp, h->id_offset, h->n_visible, at, nvis_g > 0 ? 1 : 0,
+                    h->cfg.nb_supersurfels_max, h->shard, h->d_cnt, h->oov[h->ocur], h->oov_tail - h->oov_head, h->classify,
+                    h->d_state, h->d_state_oov, h->d_bc_oov, ws, h->fuse_totals.from_tot);
         if (h->fuse_migrate)
-            launch_pack_emigrants(h->stream, M, h->cc->d_best, h->cc->d_matched, h->id_offset, h->n_visible, h->d_state, h->S,
-                                  nvis_g > 0 ? 1 : 0, h->cfg.nranks, h->cfg.shard_tile, h->d_migrants);
+            launch_pack_emigrants(h->stream, M, at, h->id_offset, h->n_visible, h->d_state, nvis_g > 0 ? 1 : 0, h->shard, h->d_migrants);
     }
     HCK(hipGetLastError());
     h->fusing = true;
@@ -907,16 +937,15 @@ static int fuse_end(ssf_handle* h, const int32_t* d_table, ssf_frame_result* out
     if (!h->fuse_first) {
         const PartitionWs& ws = h->fuse_ws;
         if (h->fuse_migrate && d_table)
-            launch_migrate_in(h->stream, M, d_table, h->S, h->cfg.rank, h->cfg.nb_supersurfels_max, h->d_cnt, h->cam, h->pose, h->stamp,
-                              h->cc->maps.plane_depth, h->cfg.delta_t, h->cfg.conf_thresh, h->cfg.range_min, h->cfg.range_max,
+            launch_migrate_in(h->stream, M, d_table, h->S, h->cfg.nb_supersurfels_max, h->d_cnt, h->shard, h->classify, h->pose, h->stamp,
                               h->d_state, ws);
         // The rows the move kernel writes to the new visible array are the rows the next frame's first ICP iteration
         // reads, under a transform that is known now (the pose just estimated, when the caller supplies no prior):
         // if that frame's extract has finished, the move kernel accumulates the record on the way (k_move_rows<true>).
-        NextFrameIcp next{};
+        NextIcp next{};
         P2PView next_pv{};
         bool have_next = false;
-        if (h->icp_ahead && (h->p2p.on || h->ahead_tuner.current() == 1) && !h->comm && (h->cfg.nranks == 1 || h->p2p.on) && h->cfg.icp_iter > 0 && !h->pending.empty()) {
+        if (h->icp_ahead && (h->p2p.on || h->ahead_tuner.current() == 1) && icp_is_one_launch(h) && h->cfg.icp_iter > 0 && !h->pending.empty()) {
             ExtractCtx& nc = h->ctx[h->pending.front().first];
             const int nslot = h->pending.front().second;
             const bool multi = h->ctx.size() > 1;         // one context: extract ran on the track stream itself
@@ -936,10 +965,8 @@ static int fuse_end(ssf_handle* h, const int32_t* d_table, ssf_frame_result* out
                 const FrameMaps nm = batch_slot(nc.maps, nslot);
                 IcpLoop first;
                 icp_start_from(first, h->pose);
-                next.pix2 = nm.pix2; next.fpack = nm.fpack; next.T = icp_transform(first);
-                next.replicas = h->d_icp_replicas; next.ticket = h->d_tickets + 8; next.sums = h->d_icp;
-                next.seq = ++h->icp_seq;
-                if (h->p2p.on) { next_pv = p2p_view(h, ++h->p2p.seq_icp); next.pv = &next_pv; }
+                next = NextIcp{h->cam, nm.pix2, nm.fpack, icp_transform(first), h->d_icp_replicas, h->d_tickets + 8, h->d_icp, h->mb_dev, ++h->icp_seq};
+                if (h->p2p.on) next_pv = p2p_view(h, ++h->p2p.seq_icp);
                 h->ahead.valid = true; h->ahead.seq = next.seq; h->ahead.ctx = &nc; h->ahead.slot = nslot;
                 h->ahead.stamp = h->stamp + 1; h->ahead.pose = h->pose;
                 have_next = true;
@@ -950,16 +977,15 @@ static int fuse_end(ssf_handle* h, const int32_t* d_table, ssf_frame_result* out
         // model behind them)
         // (a sharded map: the shard sizes of all ranks are exchanged now -- the counters are final -- so that the next
         // frame does not have to wait for the row moves to learn them)
-        if (h->comm || h->p2p.on) { int rg = comm_gather_counts(h); if (rg) return rg; }
-        launch_move_rows(h->stream, h->cam, M, h->model[h->mcur ^ 1], h->oov[h->ocur], h->n_visible + (h->fuse_migrate ? 2 : 1) * h->S, h->oov_tail - h->oov_head,
+        if (exchanges_natively(h)) { int rg = comm_gather_counts(h); if (rg) return rg; }
+        launch_move_rows(h->stream, M, h->model[h->mcur ^ 1], h->oov[h->ocur], h->n_visible + (h->fuse_migrate ? 2 : 1) * h->S, h->oov_tail - h->oov_head,
                          h->d_state, h->d_state_oov, h->d_bc_oov, ws, h->d_cnt, h->mb_dev, seq, have_next ? &next : nullptr,
-                         h->fuse_totals.from_tot ? &h->fuse_totals : nullptr);
+                         have_next && h->p2p.on ? &next_pv : nullptr, h->fuse_totals.from_tot ? &h->fuse_totals : nullptr);
         h->mcur ^= 1;
     } else {
-        launch_first_frame(h->stream, M, h->cc->frame, h->pose, h->S, h->cfg.nb_supersurfels_max, h->cfg.rank, h->cfg.nranks,
-                           h->cfg.shard_tile, h->d_cnt);
+        launch_first_frame(h->stream, M, h->cc->frame, h->pose, h->S, h->cfg.nb_supersurfels_max, h->shard, h->d_cnt);
         launch_publish_counts(h->stream, h->d_cnt, 0, h->mb_dev, seq);
-        if (h->comm || h->p2p.on) { int rg = comm_gather_counts(h); if (rg) return rg; }
+        if (exchanges_natively(h)) { int rg = comm_gather_counts(h); if (rg) return rg; }
     }
     HCK(hipGetLastError());
     { int rr = retire_active(h); if (rr) return rr; }     // last reader of this frame's buffers is enqueued
@@ -1018,34 +1044,23 @@ static int do_fuse(ssf_handle* h, ssf_frame_result* out) {          // no exchan
 }
 
 // ---- chained ICP launches --------------------------------------------------------------------------------
-// launch the NEXT iteration now, to wait on the device for its transform; returns the sequence number of its record
-// (match_capable: the launch can be told to do the frame's association instead of an iteration -- SSF_ICP_GO_MATCH)
+// launch the NEXT iteration now, to wait on the device for its transform (icp_waiter_can_match: the launch can be told to do the
+// frame's association instead of an iteration -- SSF_ICP_GO_MATCH)
 static bool icp_waiter_can_match(const ssf_handle* h) {
     static const bool off = SSF_ENV_SET("NO_MATCH_IN_WAITER");          // (measurement switch)
-    return !off && !h->p2p.on && !h->comm && h->cfg.nranks == 1 && h->cfg.profile == 0 && icp_variant_mode() == 0;
+    return !off && single_shard_alone(h) && h->cfg.profile == 0 && icp_variant_mode() == 0;
 }
-static int icp_launch_waiting(ssf_handle* h, unsigned long long* seq_out, IcpGo** slot_out, unsigned long long* go_seq_out) {
-    const unsigned long long seq = ++h->icp_seq;
-    const unsigned long long go_seq = ++h->go_count;
-    IcpGo* slot = h->go + (go_seq % SSF_ICP_GO_SLOTS);
+static int icp_launch_waiting(ssf_handle* h, IcpWaiter& w) {
+    w.seq_rec = ++h->icp_seq;
+    w.go_seq = ++h->go_count;
+    w.slot = h->go + (w.go_seq % SSF_ICP_GO_SLOTS);
     h->wait_launched_us = now_us();               // (before the launch call: no workgroup of it can have started waiting earlier)
     Rt none; none.R = m3_identity(); none.t = v3(0, 0, 0);
     const P2PView pv = h->p2p.view;               // (the number of the peer exchange arrives with the go word)
     const MatchArgs ma{h->cfg.range_min, h->cfg.range_max, h->id_offset, h->cc->d_best, h->cc->d_matched, h->d_cand};
-    launch_icp(h->stream, h->cam, icp_rows(h), h->n_visible, h->cc->maps.pix2, h->cc->maps.fpack, none,
-               h->d_icp_replicas, h->d_tickets + 8, h->d_icp, h->mb_dev, seq, -1, slot, go_seq, h->p2p.on ? &pv : nullptr, h->bins_valid ? 1 : 0,
-               icp_waiter_can_match(h) ? &ma : nullptr);
-    HCK(hipGetLastError());
-    *seq_out = seq; *slot_out = slot; *go_seq_out = go_seq;
-    return SSF_OK;
-}
-// drain the write-combining buffers: the stores above become visible to the device in order, now
-static inline void store_fence() {
-#if defined(__x86_64__)
-    __builtin_ia32_sfence();
-#else
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);
-#endif
+    const int rc = icp_issue(h, none, w.seq_rec, nullptr, w.slot, w.go_seq, h->p2p.on ? &pv : nullptr, icp_waiter_can_match(h) ? &ma : nullptr);
+    w.waiting = rc == SSF_OK;
+    return rc;
 }
 // A chained launch that never got its word (host stalled past the kernel's bound, or the record never arrived) may
 // have left the arrival counters / replica records of the ICP reduction half filled: drain the stream, put them back
@@ -1057,116 +1072,81 @@ static void icp_chain_reset(ssf_handle* h) {
     (void)hipStreamSynchronize(h->stream);
     h->icp_chain = false; h->ahead.valid = false;
 }
-// the host's word to a waiting launch: its transform and "go", or "no further iteration"
-static void icp_release_waiting(IcpGo* slot, unsigned long long go_seq, const Rt* T, unsigned long long p2p_seq, bool match) {
-    volatile IcpGo* s = slot;
-    const unsigned long long want = go_seq & 0xFFFFFFFFull;
-    if (T) {
-        const float v[12] = {T->R.r0.x, T->R.r0.y, T->R.r0.z, T->R.r1.x, T->R.r1.y, T->R.r1.z, T->R.r2.x, T->R.r2.y, T->R.r2.z,
-                             T->t.x, T->t.y, T->t.z};
-        uint32_t w[12]; memcpy(w, v, sizeof w);
-        uint32_t sum = (uint32_t)p2p_seq * icp_go_word_weight(14) + (uint32_t)(p2p_seq >> 32) * icp_go_word_weight(15);
-        for (unsigned int i = 0; i < 12; i++) sum += w[i] * icp_go_word_weight(i);
-        // the whole line, then ONE fence: the write-combining buffer goes out as one 64-byte write (were it ever split, the
-        // checksum in the flag word keeps the kernel polling until the rest has landed)
-        for (int i = 0; i < 12; i++) s->T[i] = v[i];
-        s->x = p2p_seq;
-        s->flag = want | ((unsigned long long)((sum >> 2) & SSF_ICP_GO_CHECK_MASK) << 32) | (match ? SSF_ICP_GO_MATCH : 0ull);
-    } else s->flag = want | ((unsigned long long)icp_go_abort_check((unsigned int)want) << 32) | SSF_ICP_GO_ABORT;
-    store_fence();
-}
-
-// ICP + association + fusion of the oldest submitted frame, on the track stream
-static int process_oldest(ssf_handle* h, const float* prior, ssf_frame_result* out) {
-    TimerScope ts(h);
-    int rc = activate_oldest(h);
-    if (rc) return rc;
-    const double t_a = now_us();
-    const int kf = h->seq_n > 0 ? h->seq_k : -1;          // frame number inside a sequence (debug marks)
-    if (kf >= 0 && kf < 64) { h->seq_mark_us[0][kf] = t_a - h->seq_t0_us; h->seq_mark_us[1][kf] = 0; }
-    if (h->ctx.size() > 1 && hipEventQuery(h->cc->ctx->ev_done) == hipSuccess) h->host_us[4] += 1;
-    bool first_it = true;
-    const bool timing = h->cfg.profile != 0 && h->cc->ctx->timed;     // stage split costs an event synchronise: opt-in
-    if (timing) HCK(hipEventRecord(h->ev[1], h->stream));
-    RcclApi* api = h->comm ? rccl_api() : nullptr;
-    const bool exchanging = h->comm || h->p2p.on;          // a shard of a map that runs its exchanges natively
-    if (exchanging) { rc = comm_counts(h); if (rc) return rc; }
-    icp_begin(h, prior);
-    // a large visible set: its ICP / association fields once more, sorted by the image tile they project to under the
-    // frame's initial transform (ssf_track_fuse.hip, k_bin_*): the iterations and the association stream that copy
-    h->bins_valid = false;
-    // chained launches (single GPU, kernels not individually timed): while iteration i runs, iteration i + 1 is
-    // already launched and waits on the device for its transform
-    // (with the peer-to-peer exchange too: there an iteration is one launch as well; every rank takes the same decisions)
-    const bool chain = h->icp_chain && h->go && !h->comm && (h->cfg.nranks == 1 || h->p2p.on) && h->cfg.profile != 1;
-    if (h->icp.active && h->bin_min_rows >= 0 && h->n_visible >= h->bin_min_rows && h->n_visible > 0 && !exchanging && h->cfg.nranks == 1 &&
-        bin_buffer_words(h->cam, 1) != 0) {
-        if (!h->d_bin_idx) {                       // first use: the copy's buffers (48 B per row of capacity; d_bin_idx: only the flag "this is the sorted copy" of launch_match)
-            const size_t N = (size_t)h->cfg.nb_supersurfels_max, bw = bin_buffer_words(h->cam, N);
-            const bool ok = bw && dalloc(h, &h->bins.pos, 12 * N) && dalloc(h, &h->d_bin_idx, 1) && dalloc(h, &h->d_bin_count, bw) && dalloc(h, &h->d_bin_cursor, bw);
-            if (!ok) { h->err = "allocation of the tile-sorted copy failed"; return SSF_ERR_DEVICE; }
-        }
-        Rt T0; T0.R = h->icp.R_init; T0.t = h->icp.t_init;
-        // In front of the loop, on the track stream.  (Measured and removed, round 6: the sort on a stream of its own beside the
-        // frame's first two iterations, the launch made ahead for iteration 3 the first to wait for it -- 2 003-2 026 frames/s at
-        // BASELINE config 3 against 2 351-2 366 in front and 2 286-2 301 without the copy: launches made ahead hold their workgroups'
-        // places while they wait for the host's word, and the sort's three launches queue behind them.  profiles/config3_sorted_rows_r06.txt)
-        launch_bin_rows(h->stream, h->cam, h->model[h->mcur], h->n_visible, T0, h->d_bin_count, h->d_bin_cursor, h->bins);
-        HCK(hipGetLastError());
-        h->bins_valid = true;
+// ---- the track stage of one frame, step by step (process_oldest below is the list) -------------------------------------------------
+// what the steps share: entry time, end of the ICP loop, the frame's number inside a sequence (debug marks) | the stage split is
+// timed (costs an event synchronise: opt-in) | no record has come back yet | the launch made ahead
+struct TrackFrame { double t_a = 0.0, t_b = 0.0; int kf = -1; bool timing = false, first_it = true; IcpWaiter w; };
+// The tile-copy step of a frame (after icp_begin, which dropped the last copy).  A large visible set: its ICP / association fields
+// once more, sorted by the image tile they project to under the frame's initial transform (ssf_track_fuse.hip, k_bin_*): the
+// iterations and the association stream that copy.  The decision: a frame that iterates, on a single shard, min_rows visible rows or more.
+int TileCopy::make_if_large(ssf_handle* h) {
+    if (!(h->icp.active && min_rows >= 0 && h->n_visible >= min_rows && h->n_visible > 0 && single_shard_alone(h) && bin_buffer_words(h->cam, 1) != 0)) return SSF_OK;
+    if (!d_idx) {                              // first use: the copy's buffers (48 B per row of capacity; d_idx: only the flag "this is the sorted copy" of launch_match)
+        const size_t N = (size_t)h->cfg.nb_supersurfels_max, bw = bin_buffer_words(h->cam, N);
+        const bool ok = bw && dalloc(h, &rows.pos, 12 * N) && dalloc(h, &d_idx, 1) && dalloc(h, &d_count, bw) && dalloc(h, &d_cursor, bw);
+        if (!ok) { h->err = "allocation of the tile-sorted copy failed"; return SSF_ERR_DEVICE; }
     }
-    int again = h->icp.active ? 1 : 0, valid = 0;
-    bool waiting = false; unsigned long long wait_seq_rec = 0, wait_go_seq = 0; IcpGo* wait_slot = nullptr;
+    Rt T0; T0.R = h->icp.R_init; T0.t = h->icp.t_init;
+    // In front of the loop, on the track stream.  (Measured and removed, round 6: the sort on a stream of its own beside the
+    // frame's first two iterations, the launch made ahead for iteration 3 the first to wait for it -- 2 003-2 026 frames/s at
+    // BASELINE config 3 against 2 351-2 366 in front and 2 286-2 301 without the copy: launches made ahead hold their workgroups'
+    // places while they wait for the host's word, and the sort's three launches queue behind them.  profiles/config3_sorted_rows_r06.txt)
+    launch_bin_rows(h->stream, h->cam, h->model[h->mcur], h->n_visible, T0, d_count, d_cursor, rows);
+    HCK(hipGetLastError());
+    valid = true;
+    return SSF_OK;
+}
+// chained launches (single GPU, kernels not individually timed): while iteration i runs, iteration i + 1 is
+// already launched and waits on the device for its transform
+// (with the peer-to-peer exchange too: there an iteration is one launch as well; every rank takes the same decisions)
+static inline bool icp_chains(const ssf_handle* h) { return h->icp_chain && h->go && icp_is_one_launch(h) && h->cfg.profile != 1; }
+static int icp_loop_chained(ssf_handle* h, TrackFrame& f) {
+    IcpWaiter& w = f.w;
+    int again = h->icp.active ? 1 : 0, rc;
     while (again) {
-        if (chain) {
-            unsigned long long seq_rec;
-            if (h->icp.ahead_seq) { seq_rec = h->icp.ahead_seq; h->icp.ahead_seq = 0; }     // iteration 1 came from the move kernel
-            else if (waiting) {                                                                 // this iteration is already on the device
-                const Rt T = icp_transform(h->icp);
-                icp_release_waiting(wait_slot, wait_go_seq, &T, h->p2p.on ? ++h->p2p.seq_icp : 0);
-                seq_rec = wait_seq_rec; waiting = false;
-            } else {
-                const Rt T = icp_transform(h->icp);
+        unsigned long long seq_rec;
+        if (h->icp.ahead_seq) { seq_rec = h->icp.ahead_seq; h->icp.ahead_seq = 0; }     // iteration 1 came from the move kernel
+        else {
+            const Rt T = icp_transform(h->icp);
+            const unsigned long long xseq = h->p2p.on ? ++h->p2p.seq_icp : 0;             // (the number of this iteration's peer exchange)
+            if (w.waiting) { icp_release_waiting(w.slot, w.go_seq, &T, xseq); seq_rec = w.seq_rec; w.waiting = false; }   // already on the device
+            else {
+                const P2PView pv = p2p_view(h, xseq);
                 seq_rec = ++h->icp_seq;
-                P2PView pv{};
-                if (h->p2p.on) pv = p2p_view(h, ++h->p2p.seq_icp);
-                launch_icp(h->stream, h->cam, icp_rows(h), h->n_visible, h->cc->maps.pix2, h->cc->maps.fpack, T,
-                           h->d_icp_replicas, h->d_tickets + 8, h->d_icp, h->mb_dev, seq_rec, -1, nullptr, 0, h->p2p.on ? &pv : nullptr, h->bins_valid ? 1 : 0);
-                HCK(hipGetLastError());
-            }
-            // the next iteration, should there be one (the loop may run cfg.icp_iter iterations at most) -- and behind the LAST
-            // iteration the loop allows, a launch that can only be told to do the association: a loop that ends at the cap
-            // (BASELINE config 3: ten forced iterations) then starts its association ~1 us after the host's last step instead of
-            // a launch latency later (11-13 us between the tenth k_icp and k_match in the round-4 traces), like one that converges
-            if (h->icp.iter + 1 < h->cfg.icp_iter || (!timing && icp_waiter_can_match(h))) {
-                rc = icp_launch_waiting(h, &wait_seq_rec, &wait_slot, &wait_go_seq);
+                rc = icp_issue(h, T, seq_rec, nullptr, nullptr, 0, h->p2p.on ? &pv : nullptr);
                 if (rc) return rc;
-                waiting = true;
             }
-            bool dismissed = false;
-            rc = icp_fetch(h, seq_rec, waiting ? wait_slot : nullptr, wait_go_seq, &dismissed);
-            if (dismissed) waiting = false;           // (the next iteration, if any, is launched afresh)
-            if (rc) { if (waiting) icp_release_waiting(wait_slot, wait_go_seq, nullptr); icp_chain_reset(h); return rc; }
-            if (first_it) { h->host_us[5] += now_us() - t_a; first_it = false; if (kf >= 0 && kf < 64) h->seq_mark_us[1][kf] = now_us() - h->seq_t0_us; }
-            icp_update(h, (const int64_t*)h->h_icp, &again);
-            continue;
         }
+        // the next iteration, should there be one (the loop may run cfg.icp_iter iterations at most) -- and behind the LAST
+        // iteration the loop allows, a launch that can only be told to do the association: a loop that ends at the cap
+        // (BASELINE config 3: ten forced iterations) then starts its association ~1 us after the host's last step instead of
+        // a launch latency later (11-13 us between the tenth k_icp and k_match in the round-4 traces), like one that converges
+        if (h->icp.iter + 1 < h->cfg.icp_iter || (!f.timing && icp_waiter_can_match(h))) {
+            rc = icp_launch_waiting(h, w);
+            if (rc) return rc;
+        }
+        rc = icp_fetch(h, seq_rec, w.waiting ? &w : nullptr);
+        if (rc) { if (w.waiting) icp_release_waiting(w.slot, w.go_seq, nullptr); icp_chain_reset(h); return rc; }
+        if (f.first_it) { h->host_us[5] += now_us() - f.t_a; f.first_it = false; if (f.kf >= 0 && f.kf < 64) h->seq_mark_us[1][f.kf] = now_us() - h->seq_t0_us; }
+        icp_update(h, (const int64_t*)h->h_icp, &again);
+    }
+    return SSF_OK;
+}
+// one launch (or launch + collective) per iteration, waited for before the next is made
+static int icp_loop_plain(ssf_handle* h, TrackFrame& f) {
+    int again = h->icp.active ? 1 : 0, rc;
+    while (again) {
         if (h->p2p.on) {
             // one launch: its last workgroup trades the shard record with the peers through the exchange regions and
             // publishes the SUM over the ranks (exact: int64)
-            const Rt T = icp_transform(h->icp);
-            const unsigned long long seq = ++h->icp_seq;
             const P2PView pv = p2p_view(h, ++h->p2p.seq_icp);
-            launch_icp(h->stream, h->cam, icp_rows(h), h->n_visible, h->cc->maps.pix2, h->cc->maps.fpack, T,
-                       h->d_icp_replicas, h->d_tickets + 8, h->d_icp, h->mb_dev, seq, -1, nullptr, 0, &pv, h->bins_valid ? 1 : 0);
-            HCK(hipGetLastError());
-            rc = icp_fetch(h, seq);
+            rc = icp_accumulate(h, true, nullptr, &pv);
         } else if (h->comm) {
             // shard record -> SUM over the ranks in HBM (exact: int64) -> mailbox -> host solve
             rc = icp_accumulate(h, false);
             if (rc) return rc;
             { ScopedKernel sk("exchange_icp_record", h->stream);
-              NCK(api->AllReduce(h->d_icp, h->d_icp, SSF_ICP_RECORD, ncclInt64, ncclSum, h->comm, h->stream)); }
+              NCK(rccl_api()->AllReduce(h->d_icp, h->d_icp, SSF_ICP_RECORD, ncclInt64, ncclSum, h->comm, h->stream)); }
             const unsigned long long seq = ++h->icp_seq;
             launch_publish_icp(h->stream, h->d_icp, h->mb_dev, seq);
             HCK(hipGetLastError());
@@ -1178,18 +1158,23 @@ static int process_oldest(ssf_handle* h, const float* prior, ssf_frame_result* o
         } else
             rc = icp_accumulate(h, true);
         if (rc) return rc;
-        if (first_it) { h->host_us[5] += now_us() - t_a; first_it = false; }
+        if (f.first_it) { h->host_us[5] += now_us() - f.t_a; f.first_it = false; }
         icp_update(h, (const int64_t*)h->h_icp, &again);
     }
-    // no further iteration: the launch made ahead leaves -- or, told the frame's final pose, does the association on its way
-    // out (the rows, tables and frame it was launched with are the ones the association reads)
-    bool matched_by_waiter = false;
-    if (waiting && !timing && icp_waiter_can_match(h)) {
+    return SSF_OK;
+}
+// The end of the loop.  No further iteration: the launch made ahead leaves -- or, told the frame's final pose, does the association
+// on its way out (the rows, tables and frame it was launched with are the ones the association reads); otherwise the association is
+// a launch of its own.  Then its reduction over the ranks of an RCCL communicator.
+static int icp_loop_end(ssf_handle* h, TrackFrame& f) {
+    IcpWaiter& w = f.w;
+    int valid = 0; bool matched_by_waiter = false;
+    if (w.waiting && !f.timing && icp_waiter_can_match(h)) {
         icp_end(h, &valid);
 #ifdef SSF_EXPERIMENTS
         if (h->dbg_stall_before_match_us > 0) usleep((useconds_t)h->dbg_stall_before_match_us);      // (test hook of the lab build: a stalled host thread)
 #endif
-        icp_release_waiting(wait_slot, wait_go_seq, &h->pose, 0, true);
+        icp_release_waiting(w.slot, w.go_seq, &h->pose, 0, true);
         matched_by_waiter = true;
         // The word has no acknowledgement.  A waiting workgroup gives up after SSF_ICP_GO_WAIT_TICKS (0.25 s) and tells the rest
         // of its launch to leave; if this thread was stalled that long (descheduled, a debugger, SIGSTOP) between the launch and
@@ -1199,52 +1184,78 @@ static int process_oldest(ssf_handle* h, const float* prior, ssf_frame_result* o
         // of its own: match_row only takes minima and sets flags, so a partial pass followed by a full one is the full one.
         if (now_us() - h->wait_launched_us > 100000.0) { matched_by_waiter = false; h->n_waiter_match_repairs++; }
     } else {
-        if (waiting) icp_release_waiting(wait_slot, wait_go_seq, nullptr);
+        if (w.waiting) icp_release_waiting(w.slot, w.go_seq, nullptr);
         icp_end(h, &valid);
     }
-    const double t_b = now_us();
-    if (kf >= 0 && kf < 64) h->seq_mark_us[2][kf] = t_b - h->seq_t0_us;
-    if (timing) HCK(hipEventRecord(h->ev[2], h->stream));
+    f.t_b = now_us();
+    if (f.kf >= 0 && f.kf < 64) h->seq_mark_us[2][f.kf] = f.t_b - h->seq_t0_us;
+    if (f.timing) HCK(hipEventRecord(h->ev[2], h->stream));
     if (matched_by_waiter) h->n_waiter_matches++;
-    else { rc = do_match(h, 1); if (rc) return rc; }
+    else { const int rc = do_match(h, 1); if (rc) return rc; }
     if (h->comm) {
         // best key over the ranks (keys < 2^63: signed MIN == unsigned MIN), matched = OR over the ranks
+        RcclApi* api = rccl_api();
         ScopedKernel sk("exchange_association", h->stream);
         NCK(api->AllReduce(h->cc->d_best, h->cc->d_best, h->S, ncclInt64, ncclMin, h->comm, h->stream));
         NCK(api->AllReduce(h->cc->d_matched, h->cc->d_matched, h->S, ncclUint8, ncclMax, h->comm, h->stream));
     }
-    ssf_frame_result r;
-    if (exchanging) {
-        // rows whose fused position crossed a tile edge move to the rank that owns their new tile: every rank's
-        // migrant table (one slot per frame supersurfel, at most one rank fills a slot) is summed in HBM
-        static const int migrate = SSF_ENV_SET("NO_MIGRATE") ? 0 : 1;                  // (bisecting switch of tools/p2p_first_frame_stress.py)
-        rc = fuse_begin(h, migrate);
-        if (rc) { h->fusing = false; return rc; }
-        if (h->fuse_migrate && h->p2p.on) launch_p2p_migrants(h->stream, p2p_view(h, ++h->p2p.seq_migr), h->d_migrants, h->d_tickets + 320, h->mb_dev);
-        else if (h->fuse_migrate) {
-            ScopedKernel sk("exchange_migrants", h->stream);
-            const ncclResult_t nr = api->AllReduce(h->d_migrants, h->d_migrants, (size_t)SSF_MIGRANT_WORDS * h->S, ncclInt32, ncclSum, h->comm, h->stream);
-            if (nr != ncclSuccess) {          // the frame cannot be completed: the handle must not stay "between the two halves"
-                h->fusing = false;
-                h->err = std::string("ncclAllReduce (migrant table): ") + (api->GetErrorString ? api->GetErrorString(nr) : "RCCL error");
-                return SSF_ERR_DEVICE;
-            }
+    return SSF_OK;
+}
+// the two fuse halves, and between them -- a shard that exchanges natively -- the migrant tables of all ranks summed in HBM: rows whose
+// fused position crossed a tile edge move to the rank that owns their new tile (one slot per frame supersurfel, at most one rank fills it)
+static int exchange_and_fuse(ssf_handle* h, ssf_frame_result* r) {
+    if (!exchanges_natively(h)) return do_fuse(h, r);
+    static const int migrate = SSF_ENV_SET("NO_MIGRATE") ? 0 : 1;                  // (bisecting switch of tools/p2p_first_frame_stress.py)
+    const int rc = fuse_begin(h, migrate);
+    if (rc) { h->fusing = false; return rc; }
+    if (h->fuse_migrate && h->p2p.on) launch_p2p_migrants(h->stream, p2p_view(h, ++h->p2p.seq_migr), h->d_migrants, h->d_tickets + 320, h->mb_dev);
+    else if (h->fuse_migrate) {
+        RcclApi* api = rccl_api();
+        ScopedKernel sk("exchange_migrants", h->stream);
+        const ncclResult_t nr = api->AllReduce(h->d_migrants, h->d_migrants, (size_t)SSF_MIGRANT_WORDS * h->S, ncclInt32, ncclSum, h->comm, h->stream);
+        if (nr != ncclSuccess) {          // the frame cannot be completed: the handle must not stay "between the two halves"
+            h->fusing = false;
+            h->err = std::string("ncclAllReduce (migrant table): ") + (api->GetErrorString ? api->GetErrorString(nr) : "RCCL error");
+            return SSF_ERR_DEVICE;
         }
-        rc = fuse_end(h, h->d_migrants, &r);
-    } else
-        rc = do_fuse(h, &r);
+    }
+    return fuse_end(h, h->d_migrants, r);
+}
+// the stage split of a timed frame (ev[1] entry, ev[2] ICP done, ev[3] here): waits for the frame
+static int stage_times(ssf_handle* h, ssf_frame_result* r) {
+    HCK(hipEventRecord(h->ev[3], h->stream));
+    HCK(hipEventSynchronize(h->ev[3]));
+    float ms;
+    ExtractCtx* ec = h->cc->ctx;      // extract time of the batch this frame came in, per frame
+    if (hipEventElapsedTime(&ms, ec->ev_t0, ec->ev_t1) == hipSuccess) r->stage_ms[0] = ms / (float)ec->nb_launched;
+    if (hipEventElapsedTime(&ms, h->ev[1], h->ev[2]) == hipSuccess) r->stage_ms[1] = ms;
+    if (hipEventElapsedTime(&ms, h->ev[2], h->ev[3]) == hipSuccess) r->stage_ms[2] = ms;
+    return SSF_OK;
+}
+
+// ICP + association + fusion of the oldest submitted frame, on the track stream
+static int process_oldest(ssf_handle* h, const float* prior, ssf_frame_result* out) {
+    TimerScope ts(h);
+    int rc = activate_oldest(h);
+    if (rc) return rc;
+    TrackFrame f;
+    f.t_a = now_us();
+    f.kf = h->seq_n > 0 ? h->seq_k : -1;
+    if (f.kf >= 0 && f.kf < 64) { h->seq_mark_us[0][f.kf] = f.t_a - h->seq_t0_us; h->seq_mark_us[1][f.kf] = 0; }
+    if (h->ctx.size() > 1 && hipEventQuery(h->cc->ctx->ev_done) == hipSuccess) h->host_us[4] += 1;
+    f.timing = h->cfg.profile != 0 && h->cc->ctx->timed;
+    if (f.timing) HCK(hipEventRecord(h->ev[1], h->stream));
+    if (exchanges_natively(h)) { rc = comm_counts(h); if (rc) return rc; }
+    icp_begin(h, prior);
+    rc = h->bins.make_if_large(h);
+    if (!rc) rc = icp_chains(h) ? icp_loop_chained(h, f) : icp_loop_plain(h, f);
+    if (!rc) rc = icp_loop_end(h, f);
+    ssf_frame_result r;
+    if (!rc) rc = exchange_and_fuse(h, &r);
     if (rc) return rc;
     if (h->pending.empty()) h->ahead_tuner.sequence_break(); else h->ahead_tuner.frame_done(now_us(), r.icp_iters);
-    h->host_us[1] += t_b - t_a; h->host_us[2] += now_us() - t_b; h->host_us[3] += 1;
-    if (timing) {
-        HCK(hipEventRecord(h->ev[3], h->stream));
-        HCK(hipEventSynchronize(h->ev[3]));
-        float ms;
-        ExtractCtx* ec = h->cc->ctx;      // extract time of the batch this frame came in, per frame
-        if (hipEventElapsedTime(&ms, ec->ev_t0, ec->ev_t1) == hipSuccess) r.stage_ms[0] = ms / (float)ec->nb_launched;
-        if (hipEventElapsedTime(&ms, h->ev[1], h->ev[2]) == hipSuccess) r.stage_ms[1] = ms;
-        if (hipEventElapsedTime(&ms, h->ev[2], h->ev[3]) == hipSuccess) r.stage_ms[2] = ms;
-    }
+    h->host_us[1] += f.t_b - f.t_a; h->host_us[2] += now_us() - f.t_b; h->host_us[3] += 1;
+    if (f.timing) { rc = stage_times(h, &r); if (rc) return rc; }
     if (out) *out = r;
     return SSF_OK;
 }
@@ -1476,6 +1487,8 @@ int ssf_create(const ssf_config* cfg, ssf_handle** out) {
     p.cell_magic = c > 1 ? (uint32_t)((0x100000000ull + (uint64_t)c - 1) / (uint64_t)c) : 0u;
     p.win_cells_max = tile_window_cells_max(p);          // (selects the LDS footprint of the tile kernels: ssf_extract.hip, WCAP)
     h->cam.fx = cfg->fx; h->cam.fy = cfg->fy; h->cam.cx = cfg->cx; h->cam.cy = cfg->cy; h->cam.W = W; h->cam.H = H;
+    h->classify = ClassifyArgs{h->cam, nullptr, cfg->delta_t, cfg->conf_thresh, cfg->range_min, cfg->range_max};
+    h->shard = ShardArgs{cfg->rank, cfg->nranks, 0, cfg->shard_tile};
     const size_t P = (size_t)W * H, S = h->S, N = cfg->nb_supersurfels_max, NS = S * cfg->nb_samples;
     // relabelling tiles (the shifted grid has one more column): 32-wide tiles with 256 log entries each, or 64-wide
     // ones with 512 (ssf_extract.hip, k_update_pass<., NPX>); the log regions are sized for whichever needs more
@@ -1576,7 +1589,7 @@ int ssf_create(const ssf_config* cfg, ssf_handle** out) {
          dalloc(h, &h->d_icp, 64) && dalloc(h, &h->d_state, N + 16) && dalloc(h, &h->d_cand, N) &&
          dalloc(h, &h->d_cnt, 2) && dalloc(h, &h->d_migrants, (size_t)SSF_MIGRANT_WORDS * S) && dalloc(h, &h->d_scratch_map, P) && dalloc(h, &h->d_icp_replicas, 2 * SSF_ICP_REPLICAS * 32)     /* second half: the counted record of k_icp */;
 #ifdef SSF_EXPERIMENTS
-    h->bin_min_rows = SSF_ENV_INT("BIN_MIN_ROWS", SSF_BIN_MIN_ROWS_DEFAULT);          // (lab: the threshold by environment; < 0 never.  The copy's buffers are allocated on first use)
+    h->bins.min_rows = SSF_ENV_INT("BIN_MIN_ROWS", SSF_BIN_MIN_ROWS_DEFAULT);          // (lab: the threshold by environment; < 0 never.  The copy's buffers are allocated on first use)
 #endif
     if (ok) {
         ok = hipHostMalloc((void**)&h->mb_host, sizeof(Mailbox), hipHostMallocCoherent) == hipSuccess ||
@@ -1851,10 +1864,10 @@ int ssf_debug_recentre(ssf_handle* h) {
 }
 long long ssf_debug_recentre_count(const ssf_handle* h) { return h ? h->n_recentres : -1; }
 int ssf_debug_set_max_passes(ssf_handle* h, int n) { if (!h) return SSF_ERR_INVALID_ARG; h->max_passes = n; return SSF_OK; }
-// visible rows from which a frame's tracking streams a tile-sorted copy of them (default: never; 0: always)
+// visible rows from which a frame's tracking streams a tile-sorted copy of them (default: SSF_BIN_MIN_ROWS_DEFAULT, 400 000; 0: always; < 0: never)
 int ssf_debug_set_bin_min_rows(ssf_handle* h, int n) {
     if (!h) return SSF_ERR_INVALID_ARG;
-    h->bin_min_rows = bin_buffer_words(h->cam, 1) == 0 ? -1 : n;
+    h->bins.min_rows = bin_buffer_words(h->cam, 1) == 0 ? -1 : n;
     return SSF_OK;
 }
 int ssf_stage_set_shard(ssf_handle* h, int64_t off, int64_t gm, int64_t gv) {

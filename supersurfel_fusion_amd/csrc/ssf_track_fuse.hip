@@ -937,8 +937,6 @@ __device__ __forceinline__ void classify_oov_block(const Cam& cam, const OovStor
 //               exchanged with shuffles inside the group; the first lane stores colour and Lab
 // (the two kinds of work sit in different waves, so neither waits for the other's instruction stream)
 #define UPD_PER_WG 32
-struct ClassifyArgs { Cam cam; const float* plane_depth; int delta_t; float conf_thresh, zmin, zmax; };
-struct ShardArgs { int rank, nranks, migrate; float tile; };
 __device__ __forceinline__ int tile_owner(const V3& pw, int nranks, float tile);
 __device__ __forceinline__ float pick3(const V3& v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
 __device__ __forceinline__ void update_group(SurfelSoA M, SurfelSoA F, Rt pose, int stamp, long long id_offset, int n_visible,
@@ -1311,11 +1309,6 @@ __device__ __forceinline__ void copy_row_keep(const SurfelSoA& A, size_t i, cons
     pos = r.pos; lab = r.lab; nrm = r.r2;
     store_row(B, j, r);
 }
-// what the fused form of k_move_rows needs to accumulate the first ICP iteration of the NEXT frame
-struct NextIcp {
-    Cam cam; const uint2* pix2; const float4* fpack; Rt T;
-    long long* replicas; unsigned int* ticket; long long* sums; Mailbox* mb; unsigned long long seq;
-};
 // move the rows whose place changes (stable within each class): A0, C0 -> new visible array, A1 -> in front of the
 // out-of-view span, C1 -> behind it, B0 -> new visible array (slot freed), B2 -> slot freed.  B1 stays where it is.
 // ICP = true: the rows written to the new visible array (A0, B0, C0) are exactly the rows the next frame's first ICP
@@ -2080,60 +2073,43 @@ void launch_match(hipStream_t st, const Cam& cam, SurfelSoA model, int n_visible
     else hipLaunchKernelGGL(k_match<false>, dim3((n_visible + 255) / 256), dim3(256), 0, st, cam, model, n_visible, pix2, fpack,
                             pose, zmin, zmax, id_offset, best, matched, cand, orig);
 }
-void launch_fuse(hipStream_t st, SurfelSoA model, SurfelSoA frame, Rt pose, int stamp, long long id_offset,
-                 int n_visible, const unsigned long long* best, const uint8_t* matched, const int32_t* cand, int S, int do_update,
-                 int capacity, int rank, int nranks, float tile, Counters* cnt, const Cam& cam, OovStore oov,
-                 int span_upper, const float* plane_depth, int delta_t, float conf_thresh, float zmin, float zmax,
-                 uint8_t* state_vis, uint8_t* state_oov, uint32_t* bc_oov, const PartitionWs& ws, int migrate, int tail_in_move) {
+void launch_fuse(hipStream_t st, SurfelSoA model, SurfelSoA frame, Rt pose, int stamp, long long id_offset, int n_visible,
+                 const AssocTables& at, int do_update, int capacity, const ShardArgs& sh, Counters* cnt, OovStore oov, int span_upper,
+                 const ClassifyArgs& ca, uint8_t* state_vis, uint8_t* state_oov, uint32_t* bc_oov, const PartitionWs& ws, int tail_in_move) {
     ScopedKernel sk("update_insert", st);
-    const int nchunks = (S + 255) / 256, nb_oov = (span_upper + 255) / 256, nb_vis = (n_visible + 255) / 256;
-    ClassifyArgs ca; ca.cam = cam; ca.plane_depth = plane_depth; ca.delta_t = delta_t; ca.conf_thresh = conf_thresh; ca.zmin = zmin; ca.zmax = zmax;
+    const int S = at.S, nchunks = (S + 255) / 256, nb_oov = (span_upper + 255) / 256, nb_vis = (n_visible + 255) / 256;
     const int nupd = (S + UPD_PER_WG - 1) / UPD_PER_WG;
     hipLaunchKernelGGL(k_update_insert, dim3(nupd + nchunks + nb_vis + (nb_oov + OOV_PER_WG - 1) / OOV_PER_WG), dim3(256), 0, st, model,
                        frame, pose, stamp, id_offset,
-                       n_visible, best, matched, cand, S, do_update, capacity, rank, nranks, tile, cnt, nupd, nchunks, nb_vis, nb_oov, oov, ca,
-                       state_vis, state_oov, bc_oov, ws, migrate, tail_in_move);
+                       n_visible, at.best, at.matched, at.cand, S, do_update, capacity, sh.rank, sh.nranks, sh.tile, cnt, nupd, nchunks, nb_vis,
+                       nb_oov, oov, ca, state_vis, state_oov, bc_oov, ws, sh.migrate, tail_in_move);
 }
-void launch_pack_emigrants(hipStream_t st, SurfelSoA model, const unsigned long long* best, const uint8_t* matched, long long id_offset,
-                           int n_visible, const uint8_t* state_vis, int S, int do_update, int nranks, float tile, int32_t* table) {
+void launch_pack_emigrants(hipStream_t st, SurfelSoA model, const AssocTables& at, long long id_offset, int n_visible,
+                           const uint8_t* state_vis, int do_update, const ShardArgs& sh, int32_t* table) {
     ScopedKernel sk("pack_emigrants", st);
-    hipLaunchKernelGGL(k_pack_emigrants, dim3((S + 255) / 256), dim3(256), 0, st, model, best, matched, id_offset, n_visible, state_vis, S,
-                       do_update, nranks, tile, table);
+    hipLaunchKernelGGL(k_pack_emigrants, dim3((at.S + 255) / 256), dim3(256), 0, st, model, at.best, at.matched, id_offset, n_visible,
+                       state_vis, at.S, do_update, sh.nranks, sh.tile, table);
 }
-void launch_migrate_in(hipStream_t st, SurfelSoA model, const int32_t* table, int S, int rank, int capacity, Counters* cnt,
-                       const Cam& cam, Rt pose, int stamp, const float* plane_depth, int delta_t, float conf_thresh, float zmin,
-                       float zmax, uint8_t* state_vis, const PartitionWs& ws) {
+void launch_migrate_in(hipStream_t st, SurfelSoA model, const int32_t* table, int S, int capacity, Counters* cnt, const ShardArgs& sh,
+                       const ClassifyArgs& ca, Rt pose, int stamp, uint8_t* state_vis, const PartitionWs& ws) {
     ScopedKernel sk("migrate_in", st);
-    ClassifyArgs ca; ca.cam = cam; ca.plane_depth = plane_depth; ca.delta_t = delta_t; ca.conf_thresh = conf_thresh; ca.zmin = zmin; ca.zmax = zmax;
-    hipLaunchKernelGGL(k_migrate_in, dim3(1), dim3(1024), 0, st, model, table, S, rank, capacity, cnt, ca, pose, stamp, state_vis, ws);
+    hipLaunchKernelGGL(k_migrate_in, dim3(1), dim3(1024), 0, st, model, table, S, sh.rank, capacity, cnt, ca, pose, stamp, state_vis, ws);
 }
-void launch_first_frame(hipStream_t st, SurfelSoA model, SurfelSoA frame, Rt pose, int S, int capacity, int rank,
-                        int nranks, float tile, Counters* cnt) {
+void launch_first_frame(hipStream_t st, SurfelSoA model, SurfelSoA frame, Rt pose, int S, int capacity, const ShardArgs& sh, Counters* cnt) {
     ScopedKernel sk("first_frame", st);
-    hipLaunchKernelGGL(k_first_frame, dim3(1), dim3(1024), 0, st, model, frame, pose, S, capacity, rank, nranks, tile, cnt);
+    hipLaunchKernelGGL(k_first_frame, dim3(1), dim3(1024), 0, st, model, frame, pose, S, capacity, sh.rank, sh.nranks, sh.tile, cnt);
 }
-void launch_move_rows(hipStream_t st, const Cam& cam, SurfelSoA vis_src, SurfelSoA vis_dst, OovStore oov, int nv_upper, int span_upper,
+void launch_move_rows(hipStream_t st, SurfelSoA vis_src, SurfelSoA vis_dst, OovStore oov, int nv_upper, int span_upper,
                       const uint8_t* state_vis, const uint8_t* state_oov, const uint32_t* bc_oov, const PartitionWs& ws,
-                      Counters* cnt, Mailbox* mb, unsigned long long cnt_seq, const NextFrameIcp* next, const MoveTotals* totals) {
+                      Counters* cnt, Mailbox* mb, unsigned long long cnt_seq, const NextIcp* next, const P2PView* next_pv,
+                      const MoveTotals* totals) {
     const int nb_vis = std::max(1, (nv_upper + 255) / 256), nb_oov = (span_upper + 255) / 256;
     const MoveTotals mt = totals ? *totals : MoveTotals{0, 0, 0, 0};
-    NextIcp nx{};
-    const dim3 grid(nb_vis + nb_oov);
-    if (next) {
-        nx.cam = cam; nx.pix2 = next->pix2; nx.fpack = next->fpack; nx.T = next->T; nx.replicas = next->replicas;
-        nx.ticket = next->ticket; nx.sums = next->sums; nx.mb = mb; nx.seq = next->seq;
-        ScopedKernel sk("reorder_move_icp", st);
-        if (next->pv)
-            hipLaunchKernelGGL((k_move_rows<true, true>), grid, dim3(256), 0, st, vis_src, vis_dst, oov, state_vis, state_oov,
-                               bc_oov, ws, cnt, nb_vis, nx, mb, cnt_seq, *next->pv, mt);
-        else
-            hipLaunchKernelGGL((k_move_rows<true, false>), grid, dim3(256), 0, st, vis_src, vis_dst, oov, state_vis, state_oov,
-                               bc_oov, ws, cnt, nb_vis, nx, mb, cnt_seq, P2PView{}, mt);
-    } else {
-        ScopedKernel sk("reorder_move", st);
-        hipLaunchKernelGGL((k_move_rows<false, false>), grid, dim3(256), 0, st, vis_src, vis_dst, oov, state_vis, state_oov,
-                           bc_oov, ws, cnt, nb_vis, nx, mb, cnt_seq, P2PView{}, mt);
-    }
+    // (next: k_move_rows<true, .> also accumulates the next frame's first ICP iteration; next_pv: ... and trades the record with the peers)
+    auto kernel = !next ? k_move_rows<false, false> : (next_pv ? k_move_rows<true, true> : k_move_rows<true, false>);
+    ScopedKernel sk(next ? "reorder_move_icp" : "reorder_move", st);
+    hipLaunchKernelGGL(kernel, dim3(nb_vis + nb_oov), dim3(256), 0, st, vis_src, vis_dst, oov, state_vis, state_oov, bc_oov, ws, cnt, nb_vis,
+                       next ? *next : NextIcp{}, mb, cnt_seq, next_pv ? *next_pv : P2PView{}, mt);
 }
 void launch_oov_compact(hipStream_t st, OovStore src, OovStore dst, int span_upper, int new_head, uint32_t* bc_oov, Counters* cnt,
                         int set_span) {

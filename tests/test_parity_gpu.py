@@ -641,9 +641,9 @@ def test_an_arrival_at_a_full_shard_is_counted_as_removed(oracle_lib, product_li
 @pytest.mark.parametrize("pipelined", [False, True])
 def test_tile_sorted_rows_bit_exact(pipelined, oracle_lib, product_lib):
     """ICP and association streaming the TILE-SORTED copy of the visible rows (csrc/ssf_tile_rows.inc, launch_icp(by_tile) /
-    launch_match(orig); in the product since round 6 for visible sets of 400 k rows and more -- forced for every frame here, with the
-    copy made on its own stream beside the first two iterations): exact integer sums and atomicMin keys that carry the row's own
-    index make every result independent of the order of the rows."""
+    launch_match(orig); in the product since round 6 for visible sets of 400 k rows and more -- forced for every frame here; the
+    copy is made on the track stream in front of the frame's first iteration): exact integer sums and atomicMin keys that carry the
+    row's own index make every result independent of the order of the rows."""
     fo, nv = seeded(oracle_lib, 50000, 640, 480)
     kw = dict(pipeline_depth=2, extract_batch=2) if pipelined else {}
     fh, _ = seeded(product_lib, 50000, 640, 480, **kw)
@@ -663,6 +663,28 @@ def test_tile_sorted_rows_bit_exact(pipelined, oracle_lib, product_lib):
     for k in range(4):
         util.same_result(fo2.process_frame(*util.frame(k, 320, 240)), fh2.process_frame(*util.frame(k, 320, 240)))
     util.compare_state(fo2, fh2)
+
+
+def test_a_staged_call_after_a_waiter_matched_frame_reads_the_rows_not_a_stale_copy(product_lib):
+    """The tile-sorted copy ends at the frame's fuse launch, also when the waiting k_icp launch did the association and the frame
+    never entered the association's own launch: a staged association that follows without ssf_stage_icp_begin streams the visible
+    array as the frame left it.  Two product handles, one sorting every frame and one never, must agree on it to the bit."""
+    import ctypes as C
+    fa, _ = seeded(product_lib, 50000, 640, 480)
+    fb, _ = seeded(product_lib, 50000, 640, 480)
+    fa.set_bin_min_rows(0); fb.set_bin_min_rows(-1)
+    frames = [util.frame(k, 640, 480, noise=True, holes=0.02) for k in range(4)]
+    for rgb, depth in frames[:3]:
+        util.same_result(fa.process_frame(rgb, depth), fb.process_frame(rgb, depth))
+    product_lib.lib.ssf_waiter_matches.restype = C.c_longlong
+    product_lib.lib.ssf_waiter_matches.argtypes = [C.c_void_p]
+    assert product_lib.lib.ssf_waiter_matches(fa.h) >= 1, "no frame's association ran in a waiting launch: the path was not taken"
+    fa.stage_extract(*frames[3]); fb.stage_extract(*frames[3])
+    best_a, matched_a = fa.match()
+    best_b, matched_b = fb.match()
+    assert (best_a == best_b).all() and (matched_a == matched_b).all()
+    assert matched_b.any(), "the fourth frame matched nothing: the comparison is empty"
+    util.compare_state(fa, fb)
 
 
 def test_association_inside_the_waiting_icp_launch(oracle_lib, product_lib):
