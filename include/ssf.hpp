@@ -19,6 +19,7 @@
 #include "ssf_input.h"
 #include "ssf_dynamic.h"
 #include "ssf_render.h"
+#include "ssf_query.h"
 #include "ssf_graph.h"
 #include "ssf_graph_solve.h"
 #include "ssf_keyframes.h"
@@ -170,6 +171,27 @@ struct RenderedView {
     std::vector<int32_t> index;                    /* logical row index (getModelHost's order), -1 where no disc is hit */
     std::vector<uint8_t> rgb8;
     ssf_render_stats stats;
+};
+
+/* queryModel / countModel (ssf_query.h; exported by libssf_hip.so only): rows of the map selected on the device.  Defaults: every
+ * live row (min_conf 0, any stamps, SSF_REGION_ALL); pose nullptr = the current pose; width 0 = the handle's camera; z_min = z_max
+ * = 0 = cfg.range_min / range_max */
+struct QueryParams {
+    float min_conf = 0.f;
+    int32_t t_init_min = -2147483647 - 1, t_init_max = 2147483647, t_last_min = -2147483647 - 1, t_last_max = 2147483647;
+    bool visible_only = false;
+    int region = SSF_REGION_ALL;                   /* ssf_region_kind */
+    const Transform3* pose = nullptr;              /* frame-to-map: the sphere's centre (t) / the box's frame / the frustum's camera */
+    float radius = 0.f;
+    float half[3] = {0.f, 0.f, 0.f};
+    int width = 0, height = 0; float fx = 0.f, fy = 0.f, cx = 0.f, cy = 0.f;
+    float z_min = 0.f, z_max = 0.f;
+};
+/* the rows queryModel selects, in getModelHost()'s layout and order; index[j] = the row's position in getModelHost() */
+struct QueryResult {
+    HostSupersurfels rows;
+    std::vector<int32_t> index;
+    ssf_query_stats stats;
 };
 
 /* the deformation graph's binding (ssf_graph.h): four node indices and four weights per row, in getModelHost()'s row order */
@@ -367,6 +389,54 @@ public:
         out.depth.resize(n); out.index.resize(n); out.rgb8.resize(3 * n); out.color.resize(3 * n); out.normal.resize(3 * n);
         check(ssf_render_model(need(), &p, out.depth.data(), out.index.data(), out.rgb8.data(), out.color.data(), out.normal.data(),
                                &out.stats));
+    }
+    /* Rows of the map selected on the device by region, age and confidence (ssf_query.h): how many there are and their bounding
+     * box (countModel), or the rows themselves (queryModel) -- without the copy of the whole map that getModelHost() makes. */
+    ssf_query_stats countModel(const QueryParams& q) {
+        ssf_query_params p; float v[12];
+        query_params(q, p, v);
+        ssf_query_stats s;
+        check(ssf_query_count(need(), &p, &s));
+        return s;
+    }
+    void queryModel(const QueryParams& q, QueryResult& out) {
+        ssf_query_params p; float v[12];
+        query_params(q, p, v);
+        check(ssf_query_count(need(), &p, &out.stats));
+        for (int attempt = 0;; attempt++) {             /* sized from the count; repeated once should the call name another size */
+            const int n = (int)out.stats.n_selected;
+            out.rows.resize(n); out.index.resize((size_t)(n > 0 ? n : 1));
+            ssf_surfels view = out.rows.view();
+            const int rc = ssf_query_rows(need(), &p, &view, out.index.data(), n, &out.stats);
+            if (rc == SSF_ERR_CAPACITY && attempt == 0) continue;
+            check(rc);
+            break;
+        }
+        out.rows.resize((int)out.stats.n_selected); out.index.resize((size_t)out.stats.n_selected);
+    }
+    /* extractLocalPointCloud (supersurfel_fusion.hpp; extractLocalPointCloud kernel, supersurfel_fusion_kernels.cu:490): the part of
+     * the map within `radius` of the current pose's position, for a planner or a local visualiser -- positions, colours (sRGB
+     * 0..255) and normals (orientation row 2) of the rows selected by a SSF_REGION_SPHERE query, in getModelHost()'s order. */
+    void extractLocalPointCloud(float radius, std::vector<float3>& positions, std::vector<float3>& colors, std::vector<float3>& normals) {
+        ssf_query_params p;
+        check(ssf_query_default_params(need(), &p));
+        p.region = SSF_REGION_SPHERE; p.radius = radius;
+        ssf_query_stats s;
+        check(ssf_query_count(need(), &p, &s));
+        std::vector<float> ori;
+        for (int attempt = 0;; attempt++) {
+            const size_t n = (size_t)s.n_selected, m = n > 0 ? n : 1;
+            positions.resize(m); colors.resize(m); ori.resize(9 * m);
+            ssf_surfels view = {reinterpret_cast<float*>(positions.data()), reinterpret_cast<float*>(colors.data()), nullptr, ori.data(),
+                                nullptr, nullptr, nullptr};
+            const int rc = ssf_query_rows(need(), &p, &view, nullptr, (int)n, &s);
+            if (rc == SSF_ERR_CAPACITY && attempt == 0) continue;
+            check(rc);
+            break;
+        }
+        const size_t n = (size_t)s.n_selected;
+        positions.resize(n); colors.resize(n); normals.resize(n);
+        for (size_t i = 0; i < n; i++) { normals[i].x = ori[9 * i + 6]; normals[i].y = ori[9 * i + 7]; normals[i].z = ori[9 * i + 8]; }
     }
     /* The deformation graph of a loop closure, built and kept on the device (ssf_graph.h; exported by libssf_hip.so only): every
      * stride-th confident row in birth order is a node, every row is bound to its four nearest nodes among the 2 * look born
@@ -591,6 +661,15 @@ public:
     ssf_handle* handle() { return h_; }
 
 private:
+    void query_params(const QueryParams& q, ssf_query_params& p, float v[12]) const {
+        check(ssf_query_default_params(need(), &p));
+        p.min_conf = q.min_conf; p.t_init_min = q.t_init_min; p.t_init_max = q.t_init_max; p.t_last_min = q.t_last_min; p.t_last_max = q.t_last_max;
+        p.visible_only = q.visible_only ? 1 : 0; p.region = q.region;
+        if (q.pose) { transform3_to_rt(*q.pose, v); p.pose = v; }
+        p.radius = q.radius; p.half[0] = q.half[0]; p.half[1] = q.half[1]; p.half[2] = q.half[2];
+        p.width = q.width; p.height = q.height; p.fx = q.fx; p.fy = q.fy; p.cx = q.cx; p.cy = q.cy; p.z_min = q.z_min; p.z_max = q.z_max;
+        p.on_device = 0;
+    }
     ssf_handle* need() const { if (!h_) throw std::logic_error("SupersurfelFusion: initialize() first"); return h_; }
     void check(int rc) const { if (rc != SSF_OK) throw std::runtime_error(std::string(ssf_last_error(h_))); }
     ssf_handle* h_ = nullptr;

@@ -95,6 +95,9 @@ KEYFRAMES_MAX_CANDIDATES = 8
 # ssf_fern as a numpy record (12 bytes)
 FERN_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("pad", np.uint8),
                        ("depth_mm", np.uint32)])
+# rows of the model selected on the device (include/ssf_query.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
+QUERY_SYMBOLS = ["ssf_query_default_params", "ssf_query_count", "ssf_query_rows"]
+QUERY_REGIONS = {"all": 0, "sphere": 1, "box": 2, "frustum": 3}
 # the images of ssf_render_model, in its argument order: name, dtype, per-pixel shape
 RENDER_OUTPUTS = (("depth", np.float32, ()), ("index", np.int32, ()), ("rgb8", np.uint8, (3,)), ("color", np.float32, (3,)),
                   ("normal", np.float32, (3,)))
@@ -122,6 +125,24 @@ class SsfRenderStats(C.Structure):
 
     def as_dict(self):
         return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
+
+
+class SsfQueryParams(C.Structure):
+    """ssf_query_params (include/ssf_query.h)"""
+    _fields_ = [("min_conf", C.c_float), ("t_init_min", C.c_int32), ("t_init_max", C.c_int32), ("t_last_min", C.c_int32),
+                ("t_last_max", C.c_int32), ("visible_only", C.c_int), ("region", C.c_int), ("pose", C.c_void_p),
+                ("radius", C.c_float), ("half", C.c_float * 3), ("width", C.c_int), ("height", C.c_int)] + \
+               [(nm, C.c_float) for nm in ("fx", "fy", "cx", "cy", "z_min", "z_max")] + [("on_device", C.c_int)]
+
+
+class SsfQueryStats(C.Structure):
+    """ssf_query_stats (include/ssf_query.h)"""
+    _fields_ = [("n_scanned", C.c_int64), ("n_selected", C.c_int64), ("n_selected_visible", C.c_int64),
+                ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+    def as_dict(self):
+        return dict(n_scanned=int(self.n_scanned), n_selected=int(self.n_selected), n_selected_visible=int(self.n_selected_visible),
+                    lo=np.array(self.lo[:], np.float32), hi=np.array(self.hi[:], np.float32))
 
 
 class SsfGraphParams(C.Structure):
@@ -264,6 +285,11 @@ class Library:
         if self.has_render:
             L.ssf_render_default_params.argtypes = [vp, C.POINTER(SsfRenderParams)]
             L.ssf_render_model.argtypes = [vp, C.POINTER(SsfRenderParams), vp, vp, vp, vp, vp, C.POINTER(SsfRenderStats)]
+        self.has_query = all(hasattr(L, nm) for nm in QUERY_SYMBOLS)
+        if self.has_query:
+            L.ssf_query_default_params.argtypes = [vp, C.POINTER(SsfQueryParams)]
+            L.ssf_query_count.argtypes = [vp, C.POINTER(SsfQueryParams), C.POINTER(SsfQueryStats)]
+            L.ssf_query_rows.argtypes = [vp, C.POINTER(SsfQueryParams), C.POINTER(SsfSurfels), vp, C.c_int, C.POINTER(SsfQueryStats)]
         self.has_graph = all(hasattr(L, nm) for nm in GRAPH_SYMBOLS)
         if self.has_graph:
             ip = C.POINTER(C.c_int)
@@ -516,6 +542,123 @@ class Fusion:
         p = SsfRenderParams()
         self._ck(self.L.lib.ssf_render_default_params(self.h, C.byref(p)), "ssf_render_default_params")
         return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm != "pose"}
+
+    # ---- rows selected on the device by region, age and confidence (include/ssf_query.h) ----------
+    def _need_query(self, symbol):
+        if not self.L.has_query:
+            raise SsfError("%s does not export %s: it does not query the model (include/ssf_query.h, HIP product only)"
+                           % (self.L.path, symbol))
+
+    def _query_params(self, on_device, min_conf=0.0, t_init=None, t_last=None, visible_only=False, region="all", pose=None,
+                      radius=0.0, half=(0.0, 0.0, 0.0), camera=None, z_range=None):
+        """(SsfQueryParams, the pose array it points into).  t_init / t_last: (min, max) of stamps.x / stamps.y (None = any);
+        region: "all", "sphere" (radius about the pose's t), "box" (half extents in the pose's frame) or "frustum" (camera:
+        dict(width, height, fx, fy, cx, cy), None = the handle's; z_range: (z_min, z_max), None = cfg.range_min / range_max);
+        pose: 12 floats or a 3 x 4 [R | t] frame-to-map (None = the handle's pose)."""
+        p = SsfQueryParams()
+        self._ck(self.L.lib.ssf_query_default_params(self.h, C.byref(p)), "ssf_query_default_params")
+        keep = None
+        if pose is not None:
+            pose = np.asarray(pose, np.float32)
+            if pose.shape == (3, 4):
+                pose = np.concatenate([pose[:, :3].ravel(), pose[:, 3]])
+            if pose.size != 12:
+                raise SsfError("a query pose is 12 floats (R row-major, then t) or 3 x 4 [R | t], got shape %s" % (pose.shape,))
+            keep = np.ascontiguousarray(pose.ravel(), np.float32)
+            p.pose = keep.ctypes.data
+        p.min_conf = float(min_conf)
+        if t_init is not None:
+            p.t_init_min, p.t_init_max = int(t_init[0]), int(t_init[1])
+        if t_last is not None:
+            p.t_last_min, p.t_last_max = int(t_last[0]), int(t_last[1])
+        if isinstance(region, str) and region not in QUERY_REGIONS:
+            raise SsfError("unknown query region %r (known: %s)" % (region, ", ".join(QUERY_REGIONS)))
+        p.region = QUERY_REGIONS[region] if isinstance(region, str) else int(region)
+        p.radius = float(radius)
+        p.half[0], p.half[1], p.half[2] = (float(v) for v in half)
+        if camera is not None:
+            p.width, p.height = int(camera["width"]), int(camera["height"])
+            p.fx, p.fy, p.cx, p.cy = (float(camera[k]) for k in ("fx", "fy", "cx", "cy"))
+        if z_range is not None:
+            p.z_min, p.z_max = float(z_range[0]), float(z_range[1])
+        p.visible_only, p.on_device = int(bool(visible_only)), int(bool(on_device))
+        return p, keep
+
+    def _query_rows(self, p, ptrs, index_ptr, capacity):
+        """ssf_query_rows with raw pointers (field name -> address or None); returns the stats dict.  An SsfError raised here
+        carries .rc and .stats (filled for SSF_ERR_CAPACITY: -4)"""
+        st = SsfQueryStats()
+        surf = SsfSurfels(*[ptrs.get(name) for name, _, _ in SURFEL_FIELDS])
+        rc = self.L.lib.ssf_query_rows(self.h, C.byref(p), C.byref(surf) if any(ptrs.get(name) for name, _, _ in SURFEL_FIELDS) else None,
+                                       index_ptr, int(capacity), C.byref(st))
+        if rc != 0:
+            e = SsfError("ssf_query_rows failed (%d): %s" % (rc, self.L.lib.ssf_last_error(self.h).decode()))
+            e.rc, e.stats = rc, st.as_dict()
+            raise e
+        return st.as_dict()
+
+    def query_default_params(self):
+        """ssf_query_default_params as a dict"""
+        self._need_query("ssf_query_default_params")
+        p = SsfQueryParams()
+        self._ck(self.L.lib.ssf_query_default_params(self.h, C.byref(p)), "ssf_query_default_params")
+        return {nm: (list(getattr(p, nm)) if nm == "half" else getattr(p, nm)) for nm, _ in p._fields_ if nm != "pose"}
+
+    def query_count(self, **kw):
+        """How many rows a query selects, and their bounding box (ssf_query_count): the stats dict (n_scanned, n_selected,
+        n_selected_visible, lo, hi).  Keywords: _query_params."""
+        self._need_query("ssf_query_count")
+        p, keep = self._query_params(False, **kw)
+        st = SsfQueryStats()
+        self._ck(self.L.lib.ssf_query_count(self.h, C.byref(p), C.byref(st)), "ssf_query_count")
+        return st.as_dict()
+
+    def query_rows_into(self, arrays, index, capacity, **kw):
+        """ssf_query_rows into the caller's numpy arrays (dict: field name -> array, missing = not produced; index: int32 array
+        or None), at most `capacity` rows.  Returns the stats dict."""
+        self._need_query("ssf_query_rows")
+        p, keep = self._query_params(False, **kw)
+        return self._query_rows(p, {name: _ptr(a) for name, a in arrays.items()}, _ptr(index), capacity)
+
+    def query_model(self, fields=tuple(name for name, _, _ in SURFEL_FIELDS), **kw):
+        """The rows a query selects (ssf_query_rows): dict of the requested fields (arrays of n_selected rows, in get_model's
+        layout and order), 'index' (their logical indices: get_model()[name][index] are the same rows) and 'stats'.  The
+        buffers are sized from a count; should the call still report SSF_ERR_CAPACITY, it is repeated once with the size it names."""
+        self._need_query("ssf_query_rows")
+        known = {name: (k, dt) for name, k, dt in SURFEL_FIELDS}
+        bad = [nm for nm in fields if nm not in known]
+        if bad:
+            raise SsfError("unknown model fields %s (known: %s)" % (bad, ", ".join(known)))
+        p, keep = self._query_params(False, **kw)
+        st = SsfQueryStats()
+        self._ck(self.L.lib.ssf_query_count(self.h, C.byref(p), C.byref(st)), "ssf_query_count")
+        n = int(st.n_selected)
+        for attempt in (0, 1):
+            out = {nm: np.zeros((n, known[nm][0]) if known[nm][0] > 1 else (n,), known[nm][1]) for nm in fields}
+            index = np.zeros(n, np.int32)
+            try:
+                stats = self._query_rows(p, {nm: _ptr(a) for nm, a in out.items()}, _ptr(index), n)
+                break
+            except SsfError as e:
+                if attempt or getattr(e, "rc", 0) != -4:
+                    raise
+                n = e.stats["n_selected"]
+        m = stats["n_selected"]
+        out = {nm: a[:m] for nm, a in out.items()}
+        out["index"], out["stats"] = index[:m], stats
+        return out
+
+    def query_model_device(self, tensors, index=None, capacity=None, **kw):
+        """ssf_query_rows into device memory: tensors maps field names to contiguous torch tensors on the device (rows x
+        get_model's per-row shape and dtype; a device address as int also works, then give capacity), index an int32 tensor or
+        None.  capacity: rows the outputs hold (default: the smallest first dimension).  Returns the stats dict."""
+        self._need_query("ssf_query_rows")
+        p, keep = self._query_params(True, **kw)
+        outs = dict(tensors)
+        if capacity is None:
+            capacity = min(int(t.shape[0]) for t in list(outs.values()) + ([index] if index is not None else []))
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        return self._query_rows(p, {nm: addr(t) for nm, t in outs.items()}, addr(index), capacity)
 
     # ---- the deformation graph's nodes and per-row binding (include/ssf_graph.h) ------------------
     def _need_graph(self, symbol):

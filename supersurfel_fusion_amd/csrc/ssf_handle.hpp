@@ -1,6 +1,6 @@
 // ssf_handle.hpp -- the handle (ssf_handle, the types it holds by value, HCK) and the few host helpers that the entry points
 // outside ssf_host.hip call.  Private to the library's host code: included by ssf_host.hip (the core ABI, where the helpers are
-// defined), by ssf_render.hip, ssf_graph.hip, ssf_graph_solve.hip and ssf_keyframes.hip, whose entry points sit next to their kernels,
+// defined), by ssf_render.hip, ssf_query.hip, ssf_graph.hip, ssf_graph_solve.hip and ssf_keyframes.hip, whose entry points sit next to their kernels,
 // and through ssf_exchange.hpp by ssf_exchange.hip.  Nothing here is part of the frame path's device interface (ssf_device.hpp).
 #pragma once
 #include <algorithm>
@@ -212,6 +212,15 @@ struct KeyframeWs {
     ssf_surfels pool{};                           // the row pool: device arrays, a keyframe's rows consecutive (what _get / _put copy as they are)
     std::vector<ssf_fern> host_ferns; std::vector<KeyframeMeta> kfs; long long rows_used = 0;
 };
+// ssf_query_count / ssf_query_rows (ssf_query.h): the ballot mask (one word per 64 slots), the interleaved block counts (selected,
+// live out-of-view) that the scan turns into offsets, the out-of-view blocks' live offsets, the record the host reads, and the
+// staging buffer of host outputs.  Allocated on first use; each group is grown as a whole or not at all (DevBufs::grow)
+struct QueryWs {
+    DevBufs bufs;
+    unsigned long long* mask = nullptr; uint32_t* cnt = nullptr; uint32_t* bc = nullptr; size_t slots = 0;
+    uint32_t* rec = nullptr;
+    unsigned char* rows = nullptr; size_t rows_bytes = 0;
+};
 struct ssf_handle {
     ssf_config cfg;
     int S = 0, gx = 0, gy = 0;
@@ -305,6 +314,7 @@ struct ssf_handle {
     GraphWs graph;                                // ssf_graph_* (ssf_graph.h)
     KeyframeWs kf;                                // ssf_keyframes_* (ssf_keyframes.h)
     SolveWs solve;                                // ssf_graph_solve (ssf_graph_solve.h)
+    QueryWs query;                                // ssf_query_* (ssf_query.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense)
 };
 

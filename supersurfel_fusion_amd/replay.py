@@ -169,6 +169,17 @@ def write_render(fusion, render_dir, stamp):
     return out["stats"]
 
 
+def write_local_cloud(fusion, cloud_dir, k, radius):
+    """the part of the map within `radius` of the tracked pose's position, selected on the device (include/ssf_query.h, a sphere
+    query: the reference's extractLocalPointCloud): cloud_dir/<k as %06d>.npz with positions, colors, normals (orientation row 2)
+    and index (the rows' logical indices in get_model's order)"""
+    out = fusion.query_model(fields=("positions", "colors", "orientations"), region="sphere", radius=radius)
+    os.makedirs(cloud_dir, exist_ok=True)
+    np.savez(os.path.join(cloud_dir, "%06d.npz" % k), positions=out["positions"], colors=out["colors"],
+             normals=np.ascontiguousarray(out["orientations"][:, 6:9]), index=out["index"])
+    return out["stats"]
+
+
 def keyframe_line(fusion, stamp, rec):
     """one line of the keyframe log: stamp, the id the frame was stored under (or -; "full" when the store had no room),
     min_diff_all, then every loop candidate as id:diff with the verdict of aligning it against the frame (include/ssf_keyframes.h;
@@ -182,7 +193,7 @@ def keyframe_line(fusion, stamp, rec):
 
 
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
-           keyframes=None, keyframe_log=None):
+           keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
@@ -190,6 +201,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     mask_dir: per-frame pixel masks (read_pixel_mask), handed over with their frames (include/ssf_dynamic.h).
     render_dir: after frames 0, render_every, 2 render_every, ... the model is drawn at the tracked pose (write_render); pipelined,
     submission pauses at such a frame until it has been processed (a render needs no frame pending).
+    local_cloud_dir: after frames 0, local_cloud_every, 2 local_cloud_every, ... the rows within local_cloud_radius of the tracked
+    pose are written (write_local_cloud, numbered by frame); pipelined, submission pauses as for a render.
     keyframes: a dict of ssf_keyframes_params fields ({} = the defaults): the keyframe database is configured and
     keyframes_consider runs after every frame (not pipelined: it needs no frame pending); keyframe_log: where keyframe_line's
     lines go (they are also kept in fusion.keyframe_lines)."""
@@ -200,6 +213,9 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
         fusion.keyframes_configure(**keyframes)
         fusion.keyframe_lines = []
     render_every = max(1, int(render_every))
+    local_cloud_every = max(1, int(local_cloud_every))
+    # a frame after which the model is looked at (a render, a local cloud): nothing may be pending then
+    looks = lambda k: bool((render_dir and k % render_every == 0) or (local_cloud_dir and k % local_cloud_every == 0))
     mask_of = (lambda stamp, depth: read_pixel_mask(mask_dir, stamp, np.shape(depth))) if mask_dir else (lambda stamp, depth: None)
     if not pipelined:
         for stamp, rgb, depth in frames:
@@ -211,11 +227,13 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
                 fusion.keyframe_lines.append(keyframe_line(fusion, stamp, fusion.keyframes_consider()))
             if render_dir and (len(lines) - 1) % render_every == 0:
                 write_render(fusion, render_dir, stamp)
+            if local_cloud_dir and (len(lines) - 1) % local_cloud_every == 0:
+                write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
     else:
         it, stamps, done = iter(frames), [], False
         held = []                                         # submitted host buffers stay alive until their frame is processed
         while True:
-            while not done and fusion.can_submit() and not (render_dir and len(stamps) > len(lines) and (len(stamps) - 1) % render_every == 0):
+            while not done and fusion.can_submit() and not (len(stamps) > len(lines) and looks(len(stamps) - 1)):
                 try:
                     stamp, rgb, depth = next(it)
                 except StopIteration:
@@ -237,6 +255,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             lines.append(tum_line(stamps[len(lines)], r["pose"]))
             if render_dir and (len(lines) - 1) % render_every == 0:
                 write_render(fusion, render_dir, stamps[len(lines) - 1])
+            if local_cloud_dir and (len(lines) - 1) % local_cloud_every == 0:
+                write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
     if out_path:
         with open(out_path, "w") as f:
             f.write("\n".join(lines) + "\n")
@@ -350,6 +370,11 @@ def parse_args(argv=None):
     ap.add_argument("--render-dir", default=None, metavar="DIR",
                     help="every --render-every frames, the model drawn at the tracked pose: DIR/<stamp>_rgb.png and DIR/<stamp>_depth.npy")
     ap.add_argument("--render-every", type=int, default=30, metavar="K")
+    ap.add_argument("--local-cloud-dir", default=None, metavar="DIR",
+                    help="every --local-cloud-every frames, the rows within --local-cloud-radius of the tracked pose, selected on the "
+                         "device: DIR/<frame number as %%06d>.npz (positions, colors, normals, index)")
+    ap.add_argument("--local-cloud-radius", type=float, default=2.0, metavar="R", help="metres (default 2)")
+    ap.add_argument("--local-cloud-every", type=int, default=30, metavar="K")
     ap.add_argument("--keyframes", action="store_true",
                     help="keep the fern-coded keyframe database: after every frame one line (stamp, stored id or -, min_diff_all, loop candidates "
                          "with their alignment verdict); not with --pipelined")
@@ -368,7 +393,8 @@ def main():
     frames = (frames_from_npz(a.npz, a.depth_scale, a.raw_frames) if a.npz
               else frames_from_dataset(a.dataset, a.depth_scale, a.max_frames, a.raw_frames))
     lines, res = replay(f, frames, a.out, a.export_model, pipelined=a.pipelined, mask_dir=a.dynamic_masks,
-                        render_dir=a.render_dir, render_every=a.render_every, keyframes={} if a.keyframes else None,
+                        render_dir=a.render_dir, render_every=a.render_every, local_cloud_dir=a.local_cloud_dir,
+                        local_cloud_radius=a.local_cloud_radius, local_cloud_every=a.local_cloud_every, keyframes={} if a.keyframes else None,
                         keyframe_log=a.keyframe_log)
     if a.keyframes and not a.keyframe_log:
         print("\n".join(f.keyframe_lines))
