@@ -12,6 +12,7 @@
  * std::runtime_error with the library's message. */
 #ifndef SSF_HPP
 #define SSF_HPP
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -20,6 +21,7 @@
 #include "ssf_dynamic.h"
 #include "ssf_render.h"
 #include "ssf_query.h"
+#include "ssf_motion.h"
 #include "ssf_graph.h"
 #include "ssf_graph_solve.h"
 #include "ssf_keyframes.h"
@@ -155,6 +157,21 @@ static_assert(sizeof(DeviceArray<float3>) == sizeof(void*) + sizeof(size_t) && s
 struct PixelMask {
     const uint8_t* data;
     explicit PixelMask(const uint8_t* d) : data(d) {}
+};
+
+/* detectMotion / processFrame(rgb, depth, MotionParams) (ssf_motion.h; exported by libssf_hip.so only): the geometric moving-object
+ * detector.  The defaults are ssf_motion_default_params' (design choices, not tuned values); min_seeds 0 = max(1, W * H / 1024);
+ * pose nullptr = the pose prior of the call, else the current pose */
+struct MotionParams {
+    const float* pose = nullptr;
+    float min_conf = 0.f, splat_scale = 3.f, front_abs = 0.05f, front_quad = 0.01f, link_abs = 0.02f, link_rel = 0.01f;
+    int min_seeds = 0, unknown_per_seed = 2;
+};
+/* the mask of detectMotion / getMotionMask, row-major H x W (1 = moving object), and its statistics */
+struct MotionMask {
+    int width = 0, height = 0;
+    std::vector<uint8_t> mask;
+    ssf_motion_stats stats{};
 };
 
 /* renderModel (ssf_render.h; exported by libssf_hip.so only): the map drawn into a pinhole camera on the device.  Defaults: the
@@ -304,6 +321,39 @@ public:
         check(ssf_get_dynamic_superpixels(need(), v.data(), nullptr));
         return v;
     }
+    /* Moving objects from the depth frame and the map (ssf_motion.h; exported by libssf_hip.so only): pixels clearly in front of
+     * a surface the map knows, grown over depth-continuous pixels the map says nothing about.  detectMotion only looks (no state
+     * changes); processFrame(rgb, depth, MotionParams()) detects on the device and processes the frame with that pixel mask, which
+     * getMotionMask() returns afterwards. */
+    MotionMask detectMotion(const float* depth_m, const MotionParams& mp = MotionParams()) {
+        if (depth_u16_) throw std::logic_error("detectMotion: the input format is uint16 depth; pass the counts as const uint16_t*");
+        return detect_motion(depth_m, mp);
+    }
+    MotionMask detectMotion(const uint16_t* depth_counts, const MotionParams& mp = MotionParams()) {
+        if (!depth_u16_) throw std::logic_error("detectMotion(uint16_t depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+        return detect_motion(depth_counts, mp);
+    }
+    MotionMask detectMotion(const std::vector<float>& depth_m, const MotionParams& mp = MotionParams()) {
+        if (depth_m.size() != (size_t)width_ * (size_t)height_) throw std::invalid_argument("detectMotion: the depth image must be width x height");
+        return detectMotion(depth_m.data(), mp);
+    }
+    void processFrame(const uint8_t* rgb, const float* depth_m, const MotionParams& mp, const float* vo_pose = nullptr) {
+        if (depth_u16_) throw std::logic_error("processFrame: the input format is uint16 depth; pass the counts as const uint16_t*");
+        const ssf_motion_params p = motion_params(mp);
+        check(ssf_process_frame_motion(need(), rgb, depth_m, 0, vo_pose, &p, &last_));
+    }
+    void processFrame(const uint8_t* rgb, const uint16_t* depth_counts, const MotionParams& mp, const float* vo_pose = nullptr) {
+        if (!depth_u16_) throw std::logic_error("processFrame(uint16_t depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+        const ssf_motion_params p = motion_params(mp);
+        check(ssf_process_frame_motion(need(), rgb, depth_counts, 0, vo_pose, &p, &last_));
+    }
+    /* the mask of the last processFrame(rgb, depth, MotionParams) */
+    MotionMask getMotionMask() {
+        MotionMask m;
+        m.width = width_; m.height = height_; m.mask.resize((size_t)width_ * (size_t)height_);
+        check(ssf_get_motion_mask(need(), m.mask.data(), &m.stats));
+        return m;
+    }
     /* replay of a recorded sequence (SupersurfelFusionRGBDBenchmarkNode::run): host images of n frames, results in
      * order; with pipeline_depth / extract_batch > 0 / 1 the extract stage runs ahead (bit-identical results) */
     std::vector<ssf_frame_result> processSequence(const std::vector<const uint8_t*>& rgb, const std::vector<const float*>& depth_m) {
@@ -348,6 +398,29 @@ public:
         if (d.type() == CV_16UC1) { processFrame(rgb.ptr<uint8_t>(), d.ptr<uint16_t>(), PixelMask(m.ptr<uint8_t>()), vo_pose); return; }
 #endif
         processFrame(rgb.ptr<uint8_t>(), d.ptr<float>(), PixelMask(m.ptr<uint8_t>()), vo_pose);
+    }
+    /* ... the detector on a CV_32FC1 (or, after setInputFormat, CV_16UC1) depth image: the mask as CV_8UC1, 1 = moving object */
+    cv::Mat detectMotion(const cv::Mat& depth_h, const MotionParams& mp = MotionParams()) {
+        if (depth_h.rows != height_ || depth_h.cols != width_) throw std::invalid_argument("detectMotion: the depth image must be of the frame's size");
+        const cv::Mat d = depth_h.isContinuous() ? depth_h : depth_h.clone();
+#ifdef CV_16UC1
+        const MotionMask m = d.type() == CV_16UC1 ? detectMotion(d.ptr<uint16_t>(), mp) : detectMotion(d.ptr<float>(), mp);
+#else
+        const MotionMask m = detectMotion(d.ptr<float>(), mp);
+#endif
+        cv::Mat out;
+        out.create(height_, width_, CV_8UC1);
+        std::copy(m.mask.begin(), m.mask.end(), out.ptr<uint8_t>());
+        return out;
+    }
+    void processFrame(const cv::Mat& rgb_h, const cv::Mat& depth_h, const MotionParams& mp, const float* vo_pose = nullptr) {
+        if (rgb_h.rows != height_ || rgb_h.cols != width_ || depth_h.rows != height_ || depth_h.cols != width_)
+            throw std::invalid_argument("processFrame: the colour and depth images must be of the frame's size");
+        const cv::Mat rgb = rgb_h.isContinuous() ? rgb_h : rgb_h.clone(), d = depth_h.isContinuous() ? depth_h : depth_h.clone();
+#ifdef CV_16UC1
+        if (d.type() == CV_16UC1) { processFrame(rgb.ptr<uint8_t>(), d.ptr<uint16_t>(), mp, vo_pose); return; }
+#endif
+        processFrame(rgb.ptr<uint8_t>(), d.ptr<float>(), mp, vo_pose);
     }
 #endif
 #if defined(CV_8UC3) && defined(CV_32FC1)
@@ -671,6 +744,22 @@ private:
         p.on_device = 0;
     }
     ssf_handle* need() const { if (!h_) throw std::logic_error("SupersurfelFusion: initialize() first"); return h_; }
+    ssf_motion_params motion_params(const MotionParams& mp) {
+        ssf_motion_params p;
+        check(ssf_motion_default_params(need(), &p));
+        p.pose = mp.pose; p.min_conf = mp.min_conf; p.splat_scale = mp.splat_scale;
+        p.front_abs = mp.front_abs; p.front_quad = mp.front_quad; p.link_abs = mp.link_abs; p.link_rel = mp.link_rel;
+        if (mp.min_seeds != 0) p.min_seeds = mp.min_seeds;
+        p.unknown_per_seed = mp.unknown_per_seed; p.on_device = 0;
+        return p;
+    }
+    MotionMask detect_motion(const void* depth, const MotionParams& mp) {
+        const ssf_motion_params p = motion_params(mp);
+        MotionMask m;
+        m.width = width_; m.height = height_; m.mask.resize((size_t)width_ * (size_t)height_);
+        check(ssf_motion_mask(need(), &p, depth, m.mask.data(), nullptr, nullptr, nullptr, &m.stats));
+        return m;
+    }
     void check(int rc) const { if (rc != SSF_OK) throw std::runtime_error(std::string(ssf_last_error(h_))); }
     ssf_handle* h_ = nullptr;
     ssf_frame_result last_{};

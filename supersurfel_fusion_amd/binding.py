@@ -98,6 +98,12 @@ FERN_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("r", np.uint8), ("g"
 # rows of the model selected on the device (include/ssf_query.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 QUERY_SYMBOLS = ["ssf_query_default_params", "ssf_query_count", "ssf_query_rows"]
 QUERY_REGIONS = {"all": 0, "sphere": 1, "box": 2, "frustum": 3}
+# the geometric moving-object detector (include/ssf_motion.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
+MOTION_SYMBOLS = ["ssf_motion_default_params", "ssf_motion_segment", "ssf_motion_mask", "ssf_process_frame_motion", "ssf_get_motion_mask"]
+MOTION_CLASSES = {"invalid": 0, "static": 1, "seed": 2, "unknown": 3}
+# the images of ssf_motion_segment / ssf_motion_mask, in their argument order: name, dtype
+MOTION_OUTPUTS = (("mask", np.uint8), ("label", np.int32), ("cls", np.uint8))
+MOTION_OUTPUT_NAMES = tuple(nm for nm, _ in MOTION_OUTPUTS)
 # the images of ssf_render_model, in its argument order: name, dtype, per-pixel shape
 RENDER_OUTPUTS = (("depth", np.float32, ()), ("index", np.int32, ()), ("rgb8", np.uint8, (3,)), ("color", np.float32, (3,)),
                   ("normal", np.float32, (3,)))
@@ -122,6 +128,21 @@ class SsfRenderParams(C.Structure):
 class SsfRenderStats(C.Structure):
     """ssf_render_stats (include/ssf_render.h)"""
     _fields_ = [(nm, C.c_int64) for nm in ("fragments", "pixels_filled", "rows_shown", "list_entries")]
+
+    def as_dict(self):
+        return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
+
+
+class SsfMotionParams(C.Structure):
+    """ssf_motion_params (include/ssf_motion.h)"""
+    _fields_ = [("pose", C.c_void_p)] + \
+               [(nm, C.c_float) for nm in ("min_conf", "splat_scale", "front_abs", "front_quad", "link_abs", "link_rel")] + \
+               [("min_seeds", C.c_int), ("unknown_per_seed", C.c_int), ("on_device", C.c_int)]
+
+
+class SsfMotionStats(C.Structure):
+    """ssf_motion_stats (include/ssf_motion.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("n_seed", "n_unknown", "n_components", "n_dynamic_components", "pixels_masked")]
 
     def as_dict(self):
         return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
@@ -290,6 +311,14 @@ class Library:
             L.ssf_query_default_params.argtypes = [vp, C.POINTER(SsfQueryParams)]
             L.ssf_query_count.argtypes = [vp, C.POINTER(SsfQueryParams), C.POINTER(SsfQueryStats)]
             L.ssf_query_rows.argtypes = [vp, C.POINTER(SsfQueryParams), C.POINTER(SsfSurfels), vp, C.c_int, C.POINTER(SsfQueryStats)]
+        self.has_motion = all(hasattr(L, nm) for nm in MOTION_SYMBOLS)
+        if self.has_motion:
+            mp, ms = C.POINTER(SsfMotionParams), C.POINTER(SsfMotionStats)
+            L.ssf_motion_default_params.argtypes = [vp, mp]
+            L.ssf_motion_segment.argtypes = [vp, mp, vp, vp, vp, vp, vp, ms]
+            L.ssf_motion_mask.argtypes = [vp, mp, vp, vp, vp, vp, vp, ms]
+            L.ssf_process_frame_motion.argtypes = [vp, vp, vp, C.c_int, vp, mp, C.POINTER(SsfFrameResult)]
+            L.ssf_get_motion_mask.argtypes = [vp, vp, ms]
         self.has_graph = all(hasattr(L, nm) for nm in GRAPH_SYMBOLS)
         if self.has_graph:
             ip = C.POINTER(C.c_int)
@@ -543,6 +572,122 @@ class Fusion:
         self._ck(self.L.lib.ssf_render_default_params(self.h, C.byref(p)), "ssf_render_default_params")
         return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm != "pose"}
 
+    # ---- moving objects from the depth frame and the map (include/ssf_motion.h) --------------------
+    def _need_motion(self, symbol):
+        if not self.L.has_motion:
+            raise SsfError("%s does not export %s: it does not detect motion (include/ssf_motion.h, HIP product only)"
+                           % (self.L.path, symbol))
+
+    def _motion_params(self, params, on_device):
+        """(SsfMotionParams, the pose array it points into): the library's defaults overridden by the dict `params`; its
+        'pose' is 12 floats or a 3 x 4 [R | t] camera-to-map (None = the handle's pose)."""
+        p = SsfMotionParams()
+        self._ck(self.L.lib.ssf_motion_default_params(self.h, C.byref(p)), "ssf_motion_default_params")
+        keep = None
+        for k, v in dict(params or {}).items():
+            if k == "pose":
+                if v is not None:
+                    pose = np.asarray(v, np.float32)
+                    if pose.shape == (3, 4):
+                        pose = np.concatenate([pose[:, :3].ravel(), pose[:, 3]])
+                    if pose.size != 12:
+                        raise SsfError("a motion pose is 12 floats (R row-major, then t) or 3 x 4 [R | t], got shape %s" % (pose.shape,))
+                    keep = np.ascontiguousarray(pose.ravel(), np.float32)
+                    p.pose = keep.ctypes.data
+            elif k == "on_device" or k not in [nm for nm, _ in p._fields_]:
+                raise SsfError("ssf_motion_params has no settable field %r" % k)
+            else:
+                setattr(p, k, v)
+        p.on_device = int(bool(on_device))
+        return p, keep
+
+    def motion_default_params(self):
+        """ssf_motion_default_params as a dict (design choices, not tuned values: include/ssf_motion.h)"""
+        self._need_motion("ssf_motion_default_params")
+        p = SsfMotionParams()
+        self._ck(self.L.lib.ssf_motion_default_params(self.h, C.byref(p)), "ssf_motion_default_params")
+        return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm not in ("pose", "on_device")}
+
+    def _motion_outputs(self, outputs):
+        bad = [nm for nm in outputs if nm not in MOTION_OUTPUT_NAMES]
+        if bad:
+            raise SsfError("unknown motion outputs %s (known: %s)" % (bad, ", ".join(MOTION_OUTPUT_NAMES)))
+        return {nm: np.empty((self.H, self.W), dt) for nm, dt in MOTION_OUTPUTS if nm in outputs}
+
+    def motion_segment(self, depth, model_depth, params=None, outputs=MOTION_OUTPUT_NAMES):
+        """ssf_motion_segment on two host images (depth in the handle's input format, model_depth H x W float32): dict of the
+        requested images (mask u8, label i32, cls u8) and 'stats'."""
+        self._need_motion("ssf_motion_segment")
+        depth = self._depth_array(depth)
+        model_depth = np.asarray(model_depth)
+        if model_depth.dtype != np.float32 or model_depth.shape != (self.H, self.W):
+            raise SsfError("model depth must be float32 %dx%d, got %s %s" % (self.H, self.W, model_depth.dtype, model_depth.shape))
+        model_depth = np.ascontiguousarray(model_depth)
+        p, keep = self._motion_params(params, False)
+        out = self._motion_outputs(outputs)
+        st = SsfMotionStats()
+        self._ck(self.L.lib.ssf_motion_segment(self.h, C.byref(p), _ptr(depth), _ptr(model_depth),
+                                               *[_ptr(out.get(nm)) for nm in MOTION_OUTPUT_NAMES], C.byref(st)), "ssf_motion_segment")
+        out["stats"] = st.as_dict()
+        return out
+
+    def motion_mask(self, depth, params=None, outputs=MOTION_OUTPUT_NAMES, model_depth=False):
+        """ssf_motion_mask on a host depth image: dict of the requested images, 'stats' and, with model_depth=True, the
+        rendered 'model_depth'."""
+        self._need_motion("ssf_motion_mask")
+        depth = self._depth_array(depth)
+        p, keep = self._motion_params(params, False)
+        out = self._motion_outputs(outputs)
+        md = np.empty((self.H, self.W), np.float32) if model_depth else None
+        st = SsfMotionStats()
+        self._ck(self.L.lib.ssf_motion_mask(self.h, C.byref(p), _ptr(depth), *[_ptr(out.get(nm)) for nm in MOTION_OUTPUT_NAMES],
+                                            _ptr(md), C.byref(st)), "ssf_motion_mask")
+        if model_depth:
+            out["model_depth"] = md
+        out["stats"] = st.as_dict()
+        return out
+
+    @staticmethod
+    def _dev_addr(a):
+        """a device address: None, an int, or anything with data_ptr() (a torch tensor)"""
+        if a is None:
+            return None
+        return C.c_void_p(int(a.data_ptr() if hasattr(a, "data_ptr") else a))
+
+    def motion_mask_device(self, depth, mask=None, label=None, cls=None, model_depth_out=None, params=None, model_depth=None):
+        """ssf_motion_mask (or, with model_depth given, ssf_motion_segment) on device memory: every image is None, a device
+        address (int) or a tensor (data_ptr()) of the shape and dtype motion_mask returns.  `mask` is what
+        process_frame_device(pixel_mask=...) takes.  Returns the stats dict."""
+        self._need_motion("ssf_motion_segment" if model_depth is not None else "ssf_motion_mask")
+        p, keep = self._motion_params(params, True)
+        st = SsfMotionStats()
+        outs = [self._dev_addr(a) for a in (mask, label, cls)]
+        if model_depth is not None:
+            self._ck(self.L.lib.ssf_motion_segment(self.h, C.byref(p), self._dev_addr(depth), self._dev_addr(model_depth), *outs, C.byref(st)),
+                     "ssf_motion_segment")
+        else:
+            self._ck(self.L.lib.ssf_motion_mask(self.h, C.byref(p), self._dev_addr(depth), *outs, self._dev_addr(model_depth_out),
+                                                C.byref(st)), "ssf_motion_mask")
+        return st.as_dict()
+
+    def last_motion_mask(self):
+        """(H x W uint8 mask, stats dict) of the last process_frame(..., motion=...) (ssf_get_motion_mask)"""
+        self._need_motion("ssf_get_motion_mask")
+        mask = np.empty((self.H, self.W), np.uint8)
+        st = SsfMotionStats()
+        self._ck(self.L.lib.ssf_get_motion_mask(self.h, _ptr(mask), C.byref(st)), "ssf_get_motion_mask")
+        return mask, st.as_dict()
+
+    def _process_frame_motion(self, rgb_ptr, depth_ptr, on_device, prior, motion):
+        self._need_motion("ssf_process_frame_motion")
+        if not (motion is True or isinstance(motion, dict)):
+            raise SsfError("motion is None, True or a dict of ssf_motion_params fields, got %r" % (motion,))
+        p, keep = self._motion_params(None if motion is True else motion, on_device)
+        res = SsfFrameResult()
+        self._ck(self.L.lib.ssf_process_frame_motion(self.h, rgb_ptr, depth_ptr, int(bool(on_device)), _ptr(prior), C.byref(p), C.byref(res)),
+                 "ssf_process_frame_motion")
+        return res
+
     # ---- rows selected on the device by region, age and confidence (include/ssf_query.h) ----------
     def _need_query(self, symbol):
         if not self.L.has_query:
@@ -793,11 +938,16 @@ class Fusion:
         self._ck(self.L.lib.ssf_graph_apply_solved(self.h), "ssf_graph_apply_solved")
 
     # ---- whole frame -------------------------------------------------------------------------
-    def process_frame(self, rgb, depth, prior_pose=None, dynamic_mask=None, pixel_mask=None):
+    def process_frame(self, rgb, depth, prior_pose=None, dynamic_mask=None, pixel_mask=None, motion=None):
         """pixel_mask: H x W uint8 (non-zero = moving object), voted onto the frame's superpixels (ssf_dynamic.h);
-        not together with dynamic_mask (one byte per superpixel)."""
+        not together with dynamic_mask (one byte per superpixel).  motion: None, or True / a dict of ssf_motion_params fields:
+        the pixel mask is detected on the device from this depth and the map (ssf_process_frame_motion, ssf_motion.h)."""
         rgb, depth = self._frame(rgb, depth)
         prior = None if prior_pose is None else np.ascontiguousarray(prior_pose, np.float32)
+        if motion is not None:
+            if pixel_mask is not None or dynamic_mask is not None:
+                raise SsfError("motion does not combine with pixel_mask or dynamic_mask: it makes the frame's pixel mask itself")
+            return self._process_frame_motion(_ptr(rgb), _ptr(depth), False, prior, motion).as_dict()
         if pixel_mask is not None:
             self._need_pixmask("ssf_process_frame_pixmask")
             if dynamic_mask is not None:
@@ -813,9 +963,13 @@ class Fusion:
                                               C.byref(res)), "ssf_process_frame")
         return res.as_dict()
 
-    def process_frame_device(self, d_rgb_ptr, d_depth_ptr, prior_pose=None, pixel_mask=None):
-        """pixel_mask: None or the device address of an H x W uint8 pixel mask (ssf_dynamic.h)"""
+    def process_frame_device(self, d_rgb_ptr, d_depth_ptr, prior_pose=None, pixel_mask=None, motion=None):
+        """pixel_mask: None or the device address of an H x W uint8 pixel mask (ssf_dynamic.h); motion: as process_frame"""
         prior = None if prior_pose is None else np.ascontiguousarray(prior_pose, np.float32)
+        if motion is not None:
+            if pixel_mask is not None:
+                raise SsfError("motion does not combine with pixel_mask: it makes the frame's pixel mask itself")
+            return self._process_frame_motion(C.c_void_p(d_rgb_ptr), C.c_void_p(d_depth_ptr), True, prior, motion)
         res = SsfFrameResult()
         if pixel_mask is not None:
             self._need_pixmask("ssf_process_frame_pixmask")

@@ -1,6 +1,6 @@
 // ssf_handle.hpp -- the handle (ssf_handle, the types it holds by value, HCK) and the few host helpers that the entry points
 // outside ssf_host.hip call.  Private to the library's host code: included by ssf_host.hip (the core ABI, where the helpers are
-// defined), by ssf_render.hip, ssf_query.hip, ssf_graph.hip, ssf_graph_solve.hip and ssf_keyframes.hip, whose entry points sit next to their kernels,
+// defined), by ssf_render.hip, ssf_query.hip, ssf_motion.hip, ssf_graph.hip, ssf_graph_solve.hip and ssf_keyframes.hip, whose entry points sit next to their kernels,
 // and through ssf_exchange.hpp by ssf_exchange.hip.  Nothing here is part of the frame path's device interface (ssf_device.hpp).
 #pragma once
 #include <algorithm>
@@ -18,6 +18,7 @@
 #include "../../include/ssf_graph.h"
 #include "../../include/ssf_graph_solve.h"
 #include "../../include/ssf_keyframes.h"
+#include "../../include/ssf_motion.h"
 
 struct ncclComm; typedef struct ncclComm* ncclComm_t;      // (as <rccl/rccl.h> declares it: the handle only holds communicators)
 struct Uploader;                                            // the handle only points to it (ssf_host.hip)
@@ -171,6 +172,20 @@ struct RenderWs {
     unsigned char* img = nullptr; size_t img_bytes = 0;           // host outputs, staged on the device
     uint32_t epoch = 0;                                           // of the last render: seen[slot] == epoch <=> shown by it
 };
+// working buffers of ssf_motion_* (ssf_motion.h), P = W * H of the handle's camera: allocated on first use as a whole or not at
+// all (DevBufs::grow), 31 bytes per pixel.  `last` and last_stats keep the mask of the last ssf_process_frame_motion: the frame's
+// extract context copies from it, and later ssf_motion_mask calls do not touch it.
+struct MotionWs {
+    DevBufs bufs;
+    unsigned char* din = nullptr;                                 // a host depth image, uploaded in the input format (4 P)
+    float* m = nullptr; float* d32 = nullptr;                     // model depth (rendered or uploaded); the frame's depth in metres
+    uint8_t* cls = nullptr; int32_t* parent = nullptr; int32_t* label = nullptr;
+    uint2* cnt = nullptr;                                         // (seed, unknown) pixels: of a tile's component at its local root, then of the component at its root
+    uint8_t* mask = nullptr; uint8_t* last = nullptr;
+    unsigned long long* stats = nullptr;                          // ssf_motion_stats' five counts
+    size_t pixels = 0;
+    bool have_last = false; ssf_motion_stats last_stats{};
+};
 // ssf_graph_build (ssf_graph.h): the resident node table and binding, and the working buffers of the time-order sort.  Allocated
 // on first use; each group (per slot / per node) is grown as a whole or not at all (DevBufs::grow)
 struct GraphWs {
@@ -315,6 +330,7 @@ struct ssf_handle {
     KeyframeWs kf;                                // ssf_keyframes_* (ssf_keyframes.h)
     SolveWs solve;                                // ssf_graph_solve (ssf_graph_solve.h)
     QueryWs query;                                // ssf_query_* (ssf_query.h)
+    MotionWs motion;                              // ssf_motion_* (ssf_motion.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense)
 };
 
@@ -351,6 +367,11 @@ inline int sync_collect(ssf_handle* h) {
 ModelView model_view(const ssf_handle* h, bool visible_only);
 int model_at_rest(ssf_handle* h, const char* who = nullptr, const char* lacks = nullptr);
 int materialise(ssf_handle* h);
+// for ssf_motion.hip: what every frame entry point asks of its arguments first (false: SSF_ERR_INVALID_ARG), and
+// ssf_process_frame_pixmask with the pixel mask in device memory whatever on_device says of the frame
+bool frame_inputs_ok(ssf_handle* h, const void* rgb, const void* depth, int on_device);
+int process_frame_devmask(ssf_handle* h, const void* rgb, const void* depth, int on_device, const float* prior, const uint8_t* d_pixmask,
+                          ssf_frame_result* out);
 int store_from_dense(ssf_handle* h, int n, int n_visible);
 void drop_shard_sizes(ssf_handle* h);
 // for ssf_exchange.hip: ssf_last_error(NULL)'s text, a buffer the handle owns, the wait for a mailbox word, row views and copies.

@@ -1260,16 +1260,21 @@ static int process_oldest(ssf_handle* h, const float* prior, ssf_frame_result* o
     return SSF_OK;
 }
 static int process_frame_impl(ssf_handle* h, const void* rgb, const void* depth, int on_device, const float* prior,
-                              const uint8_t* mask, ssf_frame_result* out, const uint8_t* pixmask = nullptr) {
+                              const uint8_t* mask, ssf_frame_result* out, const uint8_t* pixmask = nullptr, int pixmask_on_device = -1) {
     if (!frame_args_ok(h, rgb, depth, on_device)) return SSF_ERR_INVALID_ARG;
     if (!h->pending.empty()) { h->err = "frames are pending in the extract pipeline: use ssf_process_submitted"; return SSF_ERR_STATE; }
     int rc;
-    { TimerScope ts(h); rc = submit_extract(h, rgb, depth, on_device, mask, pixmask, on_device); }
+    { TimerScope ts(h); rc = submit_extract(h, rgb, depth, on_device, mask, pixmask, pixmask_on_device < 0 ? on_device : pixmask_on_device); }
     return rc ? rc : process_oldest(h, prior, out);
 }
 
 // ---- what the entry points of ssf_render.hip, ssf_graph.hip and ssf_keyframes.hip share with the ones here (ssf_handle.hpp) ----
 namespace ssf {
+bool frame_inputs_ok(ssf_handle* h, const void* rgb, const void* depth, int on_device) { return frame_args_ok(h, rgb, depth, on_device); }
+int process_frame_devmask(ssf_handle* h, const void* rgb, const void* depth, int on_device, const float* prior, const uint8_t* d_pixmask,
+                          ssf_frame_result* out) {
+    return process_frame_impl(h, rgb, depth, on_device ? 1 : 0, prior, nullptr, out, d_pixmask, 1);
+}
 int copy_rows(ssf_handle* h, const ssf_surfels& dst, size_t d0, const ssf_surfels& src, size_t s0, size_t n, hipMemcpyKind kind) {
     if (n == 0) return SSF_OK;
     auto one = [&](auto* d, const auto* s, size_t w) { return d ? hipMemcpyAsync(d + w * d0, s + w * s0, 4 * w * n, kind, h->stream) : hipSuccess; };

@@ -20,7 +20,12 @@ the conversion happens in the kernels that load the pixels, and estimated.txt is
 --dynamic-masks DIR hands a detector's per-pixel mask of moving objects to the handle with each frame (include/ssf_dynamic.h):
 DIR/<rgb stamp>.png (any 8-bit image; a colour one counts a pixel as masked when any channel is non-zero) or DIR/<rgb stamp>.npy
 (H x W), non-zero = dynamic.  A frame without a file has no mask.  Superpixels of which at least half the pixels are masked get
-confidence -1 and take no part in tracking or fusion."""
+confidence -1 and take no part in tracking or fusion.
+
+--detect-motion lets the library make that mask itself from each depth frame and the map as it stands after the frame before
+(include/ssf_motion.h: pixels clearly in front of the map, grown over depth-continuous pixels the map does not show).  The mask of
+frame k needs the map after frame k - 1, so the run is sequential: not with --pipelined, and not with --dynamic-masks.
+--motion-mask-dir DIR writes every frame's mask to DIR/<rgb stamp>.png (0 / 255)."""
 import argparse
 import os
 
@@ -158,6 +163,15 @@ def read_pixel_mask(mask_dir, stamp, shape):
     return (np.asarray(m) != 0).astype(np.uint8)
 
 
+def write_motion_mask(fusion, mask_dir, stamp):
+    """the mask the library detected for the frame just processed (include/ssf_motion.h): mask_dir/<stamp>.png, 0 / 255 -- the form
+    read_pixel_mask reads back"""
+    from PIL import Image
+    mask, _ = fusion.last_motion_mask()
+    os.makedirs(mask_dir, exist_ok=True)
+    Image.fromarray(mask * np.uint8(255)).save(os.path.join(mask_dir, stamp + ".png"))
+
+
 def write_render(fusion, render_dir, stamp):
     """the model drawn at the tracked pose with the handle's camera (include/ssf_render.h): render_dir/<stamp>_rgb.png and
     render_dir/<stamp>_depth.npy (float32 metres, 0 = no supersurfel)"""
@@ -193,7 +207,8 @@ def keyframe_line(fusion, stamp, rec):
 
 
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
-           keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30):
+           keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30, detect_motion=False,
+           motion_mask_dir=None):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
@@ -205,8 +220,19 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     pose are written (write_local_cloud, numbered by frame); pipelined, submission pauses as for a render.
     keyframes: a dict of ssf_keyframes_params fields ({} = the defaults): the keyframe database is configured and
     keyframes_consider runs after every frame (not pipelined: it needs no frame pending); keyframe_log: where keyframe_line's
-    lines go (they are also kept in fusion.keyframe_lines)."""
+    lines go (they are also kept in fusion.keyframe_lines).
+    detect_motion: True or a dict of ssf_motion_params fields: every frame is processed with the pixel mask the library detects
+    from its depth and the map (include/ssf_motion.h); sequential only, and not together with mask_dir.  motion_mask_dir: where
+    write_motion_mask puts each of those masks."""
     lines, results = [], []
+    if detect_motion:
+        if pipelined:
+            raise ValueError("motion detection needs sequential processing (the mask of frame k is taken against the map after frame "
+                             "k - 1): replay it without pipelined")
+        if mask_dir:
+            raise ValueError("detect_motion makes the pixel masks itself: not together with mask_dir")
+    elif motion_mask_dir:
+        raise ValueError("motion_mask_dir needs detect_motion")
     if keyframes is not None:
         if pipelined:
             raise ValueError("the keyframe database is consulted between frames: replay it without pipelined")
@@ -220,7 +246,12 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     if not pipelined:
         for stamp, rgb, depth in frames:
             m = mask_of(stamp, depth)
-            r = fusion.process_frame(rgb, depth) if m is None else fusion.process_frame(rgb, depth, pixel_mask=m)
+            if detect_motion:
+                r = fusion.process_frame(rgb, depth, motion=detect_motion)
+                if motion_mask_dir:
+                    write_motion_mask(fusion, motion_mask_dir, stamp)
+            else:
+                r = fusion.process_frame(rgb, depth) if m is None else fusion.process_frame(rgb, depth, pixel_mask=m)
             results.append(r)
             lines.append(tum_line(stamp, r["pose"]))
             if keyframes is not None:
@@ -367,6 +398,10 @@ def parse_args(argv=None):
                     help="hand the decoded colour and the uint16 depth to the handle unconverted (input format rgb8 + u16 x --depth-scale)")
     ap.add_argument("--dynamic-masks", default=None, metavar="DIR",
                     help="per-frame pixel masks of moving objects: DIR/<rgb stamp>.png or .npy, non-zero = dynamic; no file = no mask")
+    ap.add_argument("--detect-motion", action="store_true",
+                    help="the library detects the moving objects itself from each depth frame and the map (sequential: not with "
+                         "--pipelined; not with --dynamic-masks)")
+    ap.add_argument("--motion-mask-dir", default=None, metavar="DIR", help="with --detect-motion: every frame's mask as DIR/<rgb stamp>.png")
     ap.add_argument("--render-dir", default=None, metavar="DIR",
                     help="every --render-every frames, the model drawn at the tracked pose: DIR/<stamp>_rgb.png and DIR/<stamp>_depth.npy")
     ap.add_argument("--render-every", type=int, default=30, metavar="K")
@@ -379,7 +414,15 @@ def parse_args(argv=None):
                     help="keep the fern-coded keyframe database: after every frame one line (stamp, stored id or -, min_diff_all, loop candidates "
                          "with their alignment verdict); not with --pipelined")
     ap.add_argument("--keyframe-log", default=None, metavar="FILE", help="write those lines to FILE instead of the terminal")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.detect_motion and a.dynamic_masks:
+        ap.error("--detect-motion and --dynamic-masks exclude each other: the library makes the masks, or a detector does")
+    if a.detect_motion and a.pipelined:
+        ap.error("--detect-motion needs sequential processing (the mask of frame k is taken against the map after frame k - 1): "
+                 "not with --pipelined")
+    if a.motion_mask_dir and not a.detect_motion:
+        ap.error("--motion-mask-dir needs --detect-motion")
+    return a
 
 
 def main():
@@ -395,7 +438,7 @@ def main():
     lines, res = replay(f, frames, a.out, a.export_model, pipelined=a.pipelined, mask_dir=a.dynamic_masks,
                         render_dir=a.render_dir, render_every=a.render_every, local_cloud_dir=a.local_cloud_dir,
                         local_cloud_radius=a.local_cloud_radius, local_cloud_every=a.local_cloud_every, keyframes={} if a.keyframes else None,
-                        keyframe_log=a.keyframe_log)
+                        keyframe_log=a.keyframe_log, detect_motion=a.detect_motion, motion_mask_dir=a.motion_mask_dir)
     if a.keyframes and not a.keyframe_log:
         print("\n".join(f.keyframe_lines))
     print("%d frames -> %s ; %d supersurfels" % (len(lines), a.out, res[-1]["n_model"] if res else 0))
