@@ -22,6 +22,7 @@
 #include "ssf_render.h"
 #include "ssf_query.h"
 #include "ssf_motion.h"
+#include "ssf_odometry.h"
 #include "ssf_graph.h"
 #include "ssf_graph_solve.h"
 #include "ssf_keyframes.h"
@@ -172,6 +173,23 @@ struct MotionMask {
     int width = 0, height = 0;
     std::vector<uint8_t> mask;
     ssf_motion_stats stats{};
+};
+
+/* estimateOdometry / trackOdometry / processFrame(rgb, depth, OdometryParams) (ssf_odometry.h; exported by libssf_hip.so only): the
+ * dense RGB-D odometry that makes a frame's pose prior.  The defaults are ssf_odometry_default_params' (design choices, not tuned
+ * values); iters[l] belongs to pyramid level l, 0 = the full image */
+struct OdometryParams {
+    int levels = 4;
+    int iters[SSF_ODO_MAX_LEVELS] = {4, 6, 8, 10, 10, 10};
+    float r_max = 0.5f, huber = 0.2f, min_pixel_share = 0.05f, tol_rot = 1e-4f, tol_trans = 1e-4f, max_translation = 0.3f, max_rotation = 0.35f;
+};
+/* what estimateOdometry / trackOdometry / getOdometry return: rel = current camera -> reference camera, prior = the pose prior
+ * (camera-to-map), both in getPose's 12-float layout; prior is meaningful when has_prior (trackOdometry with a valid estimate) */
+struct OdometryEstimate {
+    float rel[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    float prior[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    bool has_prior = false;
+    ssf_odometry_result result{};
 };
 
 /* renderModel (ssf_render.h; exported by libssf_hip.so only): the map drawn into a pinhole camera on the device.  Defaults: the
@@ -353,6 +371,58 @@ public:
         m.width = width_; m.height = height_; m.mask.resize((size_t)width_ * (size_t)height_);
         check(ssf_get_motion_mask(need(), m.mask.data(), &m.stats));
         return m;
+    }
+    /* Dense RGB-D odometry, the pose prior of the library's own (ssf_odometry.h; exported by libssf_hip.so only).
+     * setOdometryReference keeps a frame's pyramid (ref_mask: H x W, non-zero = ignore, or nullptr); estimateOdometry aligns a frame
+     * to it (init: 12 floats current camera -> reference camera, or nullptr) and leaves it; trackOdometry also makes the frame the
+     * next reference and returns the prior; processFrame(rgb, depth, OdometryParams()) tracks, then processes the frame with that
+     * prior (the first frame, and a frame whose estimate is invalid, without one); getOdometry returns the last track. */
+    void setOdometryReference(const uint8_t* rgb, const float* depth_m, const uint8_t* ref_mask = nullptr) {
+        if (depth_u16_) throw std::logic_error("setOdometryReference: the input format is uint16 depth; pass the counts as const uint16_t*");
+        check(ssf_odometry_set_reference(need(), rgb, depth_m, 0, ref_mask));
+    }
+    void setOdometryReference(const uint8_t* rgb, const uint16_t* depth_counts, const uint8_t* ref_mask = nullptr) {
+        if (!depth_u16_) throw std::logic_error("setOdometryReference(uint16_t depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+        check(ssf_odometry_set_reference(need(), rgb, depth_counts, 0, ref_mask));
+    }
+    OdometryEstimate estimateOdometry(const uint8_t* rgb, const float* depth_m, const OdometryParams& op = OdometryParams(), const float* init = nullptr) {
+        if (depth_u16_) throw std::logic_error("estimateOdometry: the input format is uint16 depth; pass the counts as const uint16_t*");
+        return estimate_odometry(rgb, depth_m, op, init);
+    }
+    OdometryEstimate estimateOdometry(const uint8_t* rgb, const uint16_t* depth_counts, const OdometryParams& op = OdometryParams(), const float* init = nullptr) {
+        if (!depth_u16_) throw std::logic_error("estimateOdometry(uint16_t depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+        return estimate_odometry(rgb, depth_counts, op, init);
+    }
+    OdometryEstimate trackOdometry(const uint8_t* rgb, const float* depth_m, const OdometryParams& op = OdometryParams()) {
+        if (depth_u16_) throw std::logic_error("trackOdometry: the input format is uint16 depth; pass the counts as const uint16_t*");
+        return track_odometry(rgb, depth_m, op);
+    }
+    OdometryEstimate trackOdometry(const uint8_t* rgb, const uint16_t* depth_counts, const OdometryParams& op = OdometryParams()) {
+        if (!depth_u16_) throw std::logic_error("trackOdometry(uint16_t depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+        return track_odometry(rgb, depth_counts, op);
+    }
+    void processFrame(const uint8_t* rgb, const float* depth_m, const OdometryParams& op) {
+        if (depth_u16_) throw std::logic_error("processFrame: the input format is uint16 depth; pass the counts as const uint16_t*");
+        const ssf_odometry_params p = odometry_params(op);
+        check(ssf_process_frame_odometry(need(), rgb, depth_m, 0, &p, nullptr, &last_));
+    }
+    void processFrame(const uint8_t* rgb, const uint16_t* depth_counts, const OdometryParams& op) {
+        if (!depth_u16_) throw std::logic_error("processFrame(uint16_t depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+        const ssf_odometry_params p = odometry_params(op);
+        check(ssf_process_frame_odometry(need(), rgb, depth_counts, 0, &p, nullptr, &last_));
+    }
+    /* ... with the moving-object detector on top: its mask is rendered at the odometry prior */
+    void processFrame(const uint8_t* rgb, const float* depth_m, const OdometryParams& op, const MotionParams& mp) {
+        if (depth_u16_) throw std::logic_error("processFrame: the input format is uint16 depth; pass the counts as const uint16_t*");
+        const ssf_odometry_params p = odometry_params(op);
+        const ssf_motion_params m = motion_params(mp);
+        check(ssf_process_frame_odometry(need(), rgb, depth_m, 0, &p, &m, &last_));
+    }
+    OdometryEstimate getOdometry() {
+        OdometryEstimate e;
+        check(ssf_get_odometry(need(), e.rel, e.prior, &e.result));
+        e.has_prior = e.result.valid != 0;
+        return e;
     }
     /* replay of a recorded sequence (SupersurfelFusionRGBDBenchmarkNode::run): host images of n frames, results in
      * order; with pipeline_depth / extract_batch > 0 / 1 the extract stage runs ahead (bit-identical results) */
@@ -752,6 +822,29 @@ private:
         if (mp.min_seeds != 0) p.min_seeds = mp.min_seeds;
         p.unknown_per_seed = mp.unknown_per_seed; p.on_device = 0;
         return p;
+    }
+    ssf_odometry_params odometry_params(const OdometryParams& op) {
+        ssf_odometry_params p;
+        check(ssf_odometry_default_params(need(), &p));
+        p.levels = op.levels;
+        for (int l = 0; l < SSF_ODO_MAX_LEVELS; l++) p.iters[l] = op.iters[l];
+        p.r_max = op.r_max; p.huber = op.huber; p.min_pixel_share = op.min_pixel_share; p.tol_rot = op.tol_rot; p.tol_trans = op.tol_trans;
+        p.max_translation = op.max_translation; p.max_rotation = op.max_rotation;
+        return p;
+    }
+    OdometryEstimate estimate_odometry(const uint8_t* rgb, const void* depth, const OdometryParams& op, const float* init) {
+        const ssf_odometry_params p = odometry_params(op);
+        OdometryEstimate e;
+        check(ssf_odometry_estimate(need(), &p, rgb, depth, 0, init, e.rel, &e.result));
+        return e;
+    }
+    OdometryEstimate track_odometry(const uint8_t* rgb, const void* depth, const OdometryParams& op) {
+        const ssf_odometry_params p = odometry_params(op);
+        OdometryEstimate e;
+        check(ssf_odometry_track(need(), &p, rgb, depth, 0, e.prior, &e.result));
+        e.has_prior = e.result.valid != 0;
+        check(ssf_get_odometry(need(), e.rel, nullptr, nullptr));
+        return e;
     }
     MotionMask detect_motion(const void* depth, const MotionParams& mp) {
         const ssf_motion_params p = motion_params(mp);

@@ -100,6 +100,11 @@ QUERY_SYMBOLS = ["ssf_query_default_params", "ssf_query_count", "ssf_query_rows"
 QUERY_REGIONS = {"all": 0, "sphere": 1, "box": 2, "frustum": 3}
 # the geometric moving-object detector (include/ssf_motion.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 MOTION_SYMBOLS = ["ssf_motion_default_params", "ssf_motion_segment", "ssf_motion_mask", "ssf_process_frame_motion", "ssf_get_motion_mask"]
+# dense RGB-D odometry, the pose prior of the library's own (include/ssf_odometry.h): HIP product only, not part of ssf.h
+ODOMETRY_SYMBOLS = ["ssf_odometry_default_params", "ssf_odometry_set_reference", "ssf_odometry_linearise", "ssf_odometry_estimate",
+                    "ssf_odometry_track", "ssf_process_frame_odometry", "ssf_get_odometry"]
+ODOMETRY_REASONS = ("converged", "max_iterations", "too_few_pixels", "degenerate", "motion_gate")
+ODO_MAX_LEVELS, ODO_RECORD = 6, 29
 MOTION_CLASSES = {"invalid": 0, "static": 1, "seed": 2, "unknown": 3}
 # the images of ssf_motion_segment / ssf_motion_mask, in their argument order: name, dtype
 MOTION_OUTPUTS = (("mask", np.uint8), ("label", np.int32), ("cls", np.uint8))
@@ -146,6 +151,25 @@ class SsfMotionStats(C.Structure):
 
     def as_dict(self):
         return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
+
+
+class SsfOdometryParams(C.Structure):
+    """ssf_odometry_params (include/ssf_odometry.h)"""
+    _fields_ = [("levels", C.c_int), ("iters", C.c_int * ODO_MAX_LEVELS)] + \
+               [(nm, C.c_float) for nm in ("r_max", "huber", "min_pixel_share", "tol_rot", "tol_trans", "max_translation", "max_rotation")]
+
+    def as_dict(self):
+        return {nm: (list(self.iters) if nm == "iters" else getattr(self, nm)) for nm, _ in self._fields_}
+
+
+class SsfOdometryResult(C.Structure):
+    """ssf_odometry_result (include/ssf_odometry.h)"""
+    _fields_ = [("valid", C.c_int), ("reason", C.c_int), ("levels", C.c_int), ("iters", C.c_int * ODO_MAX_LEVELS), ("pixels", C.c_int64),
+                ("mean_sq_residual", C.c_double)]
+
+    def as_dict(self):
+        return dict(valid=int(self.valid), reason=ODOMETRY_REASONS[self.reason], levels=int(self.levels), iters=list(self.iters),
+                    pixels=int(self.pixels), mean_sq_residual=float(self.mean_sq_residual))
 
 
 class SsfQueryParams(C.Structure):
@@ -319,6 +343,17 @@ class Library:
             L.ssf_motion_mask.argtypes = [vp, mp, vp, vp, vp, vp, vp, ms]
             L.ssf_process_frame_motion.argtypes = [vp, vp, vp, C.c_int, vp, mp, C.POINTER(SsfFrameResult)]
             L.ssf_get_motion_mask.argtypes = [vp, vp, ms]
+        self.has_odometry = all(hasattr(L, nm) for nm in ODOMETRY_SYMBOLS)
+        if self.has_odometry:
+            op, orr = C.POINTER(SsfOdometryParams), C.POINTER(SsfOdometryResult)
+            L.ssf_odometry_default_params.argtypes = [vp, op]
+            L.ssf_odometry_set_reference.argtypes = [vp, vp, vp, C.c_int, vp]
+            L.ssf_odometry_linearise.argtypes = [vp, op, C.c_int, vp, vp]
+            L.ssf_odometry_estimate.argtypes = [vp, op, vp, vp, C.c_int, vp, vp, orr]
+            L.ssf_odometry_track.argtypes = [vp, op, vp, vp, C.c_int, vp, orr]
+            L.ssf_process_frame_odometry.argtypes = [vp, vp, vp, C.c_int, op, C.POINTER(SsfMotionParams), C.POINTER(SsfFrameResult)]
+            L.ssf_get_odometry.argtypes = [vp, vp, vp, orr]
+            L.ssf_odometry_get_pyramid.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
         self.has_graph = all(hasattr(L, nm) for nm in GRAPH_SYMBOLS)
         if self.has_graph:
             ip = C.POINTER(C.c_int)
@@ -688,6 +723,144 @@ class Fusion:
                  "ssf_process_frame_motion")
         return res
 
+    # ---- dense RGB-D odometry: the pose prior of the library's own (include/ssf_odometry.h) ---------
+    def _need_odometry(self, symbol):
+        if not self.L.has_odometry:
+            raise SsfError("%s does not export %s: it has no dense odometry (include/ssf_odometry.h, HIP product only)"
+                           % (self.L.path, symbol))
+
+    def _odometry_params(self, params):
+        """SsfOdometryParams: the library's defaults overridden by the dict `params` ('iters': a list, level 0 first)"""
+        p = SsfOdometryParams()
+        self._ck(self.L.lib.ssf_odometry_default_params(self.h, C.byref(p)), "ssf_odometry_default_params")
+        for k, v in dict(params or {}).items():
+            if k not in [nm for nm, _ in p._fields_]:
+                raise SsfError("ssf_odometry_params has no field %r" % k)
+            if k == "iters":
+                v = list(v)
+                if len(v) > ODO_MAX_LEVELS:
+                    raise SsfError("iters has at most %d entries" % ODO_MAX_LEVELS)
+                for l, n in enumerate(v):
+                    p.iters[l] = int(n)
+            else:
+                setattr(p, k, v)
+        return p
+
+    @staticmethod
+    def _pose12(pose, what):
+        if pose is None:
+            return None
+        pose = np.asarray(pose, np.float32)
+        if pose.shape == (3, 4):
+            pose = np.concatenate([pose[:, :3].ravel(), pose[:, 3]])
+        if pose.size != 12:
+            raise SsfError("%s is 12 floats (R row-major, then t) or 3 x 4 [R | t], got shape %s" % (what, pose.shape))
+        return np.ascontiguousarray(pose.ravel(), np.float32)
+
+    def odometry_default_params(self):
+        """ssf_odometry_default_params as a dict (design choices, not tuned values: include/ssf_odometry.h)"""
+        self._need_odometry("ssf_odometry_default_params")
+        return self._odometry_params(None).as_dict()
+
+    def odometry_set_reference(self, rgb, depth, ref_mask=None):
+        """the pyramid of a host frame becomes the resident reference, with the handle's pose; ref_mask: H x W, non-zero = ignore"""
+        self._need_odometry("ssf_odometry_set_reference")
+        rgb, depth = self._frame(rgb, depth)
+        m = None
+        if ref_mask is not None:
+            m = np.ascontiguousarray(np.asarray(ref_mask) != 0, np.uint8)
+            if m.shape != (self.H, self.W):
+                raise SsfError("ref_mask must be %dx%d, got %s" % (self.H, self.W, m.shape))
+        self._ck(self.L.lib.ssf_odometry_set_reference(self.h, _ptr(rgb), _ptr(depth), 0, _ptr(m)), "ssf_odometry_set_reference")
+
+    def odometry_set_reference_device(self, d_rgb, d_depth, ref_mask=None):
+        """... on device memory (addresses or tensors; ref_mask a device H x W uint8 image or None)"""
+        self._need_odometry("ssf_odometry_set_reference")
+        self._ck(self.L.lib.ssf_odometry_set_reference(self.h, self._dev_addr(d_rgb), self._dev_addr(d_depth), 1, self._dev_addr(ref_mask)),
+                 "ssf_odometry_set_reference")
+
+    def odometry_linearise(self, level, T12, params=None):
+        """the 29 int64 words of the normal equations of the current pyramid against the reference at T (reference camera ->
+        current camera), level `level`"""
+        self._need_odometry("ssf_odometry_linearise")
+        p = self._odometry_params(params)
+        T = self._pose12(T12, "T12")
+        rec = np.zeros(ODO_RECORD, np.int64)
+        self._ck(self.L.lib.ssf_odometry_linearise(self.h, C.byref(p), int(level), _ptr(T), _ptr(rec)), "ssf_odometry_linearise")
+        return rec
+
+    def _odometry_estimate(self, rgb_ptr, depth_ptr, on_device, init, params):
+        p = self._odometry_params(params)
+        init = self._pose12(init, "init12")
+        rel, res = np.zeros(12, np.float32), SsfOdometryResult()
+        self._ck(self.L.lib.ssf_odometry_estimate(self.h, C.byref(p), rgb_ptr, depth_ptr, int(on_device), _ptr(init), _ptr(rel), C.byref(res)),
+                 "ssf_odometry_estimate")
+        return rel, res.as_dict()
+
+    def odometry_estimate(self, rgb, depth, init12=None, params=None):
+        """(rel, result): rel = current camera -> reference camera, 12 floats; the reference stays"""
+        self._need_odometry("ssf_odometry_estimate")
+        rgb, depth = self._frame(rgb, depth)
+        return self._odometry_estimate(_ptr(rgb), _ptr(depth), 0, init12, params)
+
+    def odometry_estimate_device(self, d_rgb, d_depth, init12=None, params=None):
+        self._need_odometry("ssf_odometry_estimate")
+        return self._odometry_estimate(self._dev_addr(d_rgb), self._dev_addr(d_depth), 1, init12, params)
+
+    def _odometry_track(self, rgb_ptr, depth_ptr, on_device, params):
+        p = self._odometry_params(params)
+        prior, res = np.zeros(12, np.float32), SsfOdometryResult()
+        self._ck(self.L.lib.ssf_odometry_track(self.h, C.byref(p), rgb_ptr, depth_ptr, int(on_device), _ptr(prior), C.byref(res)),
+                 "ssf_odometry_track")
+        return (prior if res.valid else None), res.as_dict()
+
+    def odometry_track(self, rgb, depth, params=None):
+        """(prior, result): prior = the pose prior of this frame (12 floats, what process_frame(prior_pose=...) takes), None when
+        the estimate is invalid; the frame becomes the reference"""
+        self._need_odometry("ssf_odometry_track")
+        rgb, depth = self._frame(rgb, depth)
+        return self._odometry_track(_ptr(rgb), _ptr(depth), 0, params)
+
+    def odometry_track_device(self, d_rgb, d_depth, params=None):
+        self._need_odometry("ssf_odometry_track")
+        return self._odometry_track(self._dev_addr(d_rgb), self._dev_addr(d_depth), 1, params)
+
+    def odometry_last(self):
+        """dict(rel, prior (None when invalid), result) of the last track (ssf_get_odometry)"""
+        self._need_odometry("ssf_get_odometry")
+        rel, prior, res = np.zeros(12, np.float32), np.zeros(12, np.float32), SsfOdometryResult()
+        self._ck(self.L.lib.ssf_get_odometry(self.h, _ptr(rel), _ptr(prior), C.byref(res)), "ssf_get_odometry")
+        return dict(rel=rel, prior=prior if res.valid else None, result=res.as_dict())
+
+    def odometry_pyramid(self, which, level):
+        """level `level` of the reference (which = 0) or current (1) pyramid: dict(I, D, gx, gy, intrinsics (fx, fy, cx, cy))"""
+        self._need_odometry("ssf_odometry_get_pyramid")
+        w, h, k = C.c_int(), C.c_int(), np.zeros(4, np.float32)
+        self._ck(self.L.lib.ssf_odometry_get_pyramid(self.h, int(which), int(level), None, None, None, None, C.byref(w), C.byref(h), _ptr(k)),
+                 "ssf_odometry_get_pyramid")
+        out = {nm: np.empty((h.value, w.value), np.float32) for nm in ("I", "D", "gx", "gy")}
+        self._ck(self.L.lib.ssf_odometry_get_pyramid(self.h, int(which), int(level), *[_ptr(out[nm]) for nm in ("I", "D", "gx", "gy")],
+                                                     None, None, None), "ssf_odometry_get_pyramid")
+        out["intrinsics"] = k
+        return out
+
+    def _process_frame_odometry(self, rgb_ptr, depth_ptr, on_device, odometry, motion):
+        self._need_odometry("ssf_process_frame_odometry")
+        if not (odometry is True or isinstance(odometry, dict)):
+            raise SsfError("odometry is None, True or a dict of ssf_odometry_params fields, got %r" % (odometry,))
+        p = self._odometry_params(None if odometry is True else odometry)
+        mp, keep = None, None
+        if motion is not None:
+            self._need_motion("ssf_process_frame_motion")
+            if not (motion is True or isinstance(motion, dict)):
+                raise SsfError("motion is None, True or a dict of ssf_motion_params fields, got %r" % (motion,))
+            m, keep = self._motion_params(None if motion is True else motion, on_device)
+            mp = C.byref(m)
+        res = SsfFrameResult()
+        self._ck(self.L.lib.ssf_process_frame_odometry(self.h, rgb_ptr, depth_ptr, int(bool(on_device)), C.byref(p), mp, C.byref(res)),
+                 "ssf_process_frame_odometry")
+        return res
+
     # ---- rows selected on the device by region, age and confidence (include/ssf_query.h) ----------
     def _need_query(self, symbol):
         if not self.L.has_query:
@@ -938,12 +1111,19 @@ class Fusion:
         self._ck(self.L.lib.ssf_graph_apply_solved(self.h), "ssf_graph_apply_solved")
 
     # ---- whole frame -------------------------------------------------------------------------
-    def process_frame(self, rgb, depth, prior_pose=None, dynamic_mask=None, pixel_mask=None, motion=None):
-        """pixel_mask: H x W uint8 (non-zero = moving object), voted onto the frame's superpixels (ssf_dynamic.h);
+    def process_frame(self, rgb, depth, prior_pose=None, dynamic_mask=None, pixel_mask=None, motion=None, odometry=None):
+        """odometry: None, or True / a dict of ssf_odometry_params fields: the pose prior comes from the library's dense odometry
+        against the frame before (ssf_process_frame_odometry, ssf_odometry.h; combines with motion, whose mask is then rendered at
+        that prior; not with prior_pose or the masks).
+        pixel_mask: H x W uint8 (non-zero = moving object), voted onto the frame's superpixels (ssf_dynamic.h);
         not together with dynamic_mask (one byte per superpixel).  motion: None, or True / a dict of ssf_motion_params fields:
         the pixel mask is detected on the device from this depth and the map (ssf_process_frame_motion, ssf_motion.h)."""
         rgb, depth = self._frame(rgb, depth)
         prior = None if prior_pose is None else np.ascontiguousarray(prior_pose, np.float32)
+        if odometry is not None:
+            if prior is not None or pixel_mask is not None or dynamic_mask is not None:
+                raise SsfError("odometry makes the pose prior itself and combines only with motion: not with prior_pose, pixel_mask or dynamic_mask")
+            return self._process_frame_odometry(_ptr(rgb), _ptr(depth), False, odometry, motion).as_dict()
         if motion is not None:
             if pixel_mask is not None or dynamic_mask is not None:
                 raise SsfError("motion does not combine with pixel_mask or dynamic_mask: it makes the frame's pixel mask itself")
@@ -963,9 +1143,13 @@ class Fusion:
                                               C.byref(res)), "ssf_process_frame")
         return res.as_dict()
 
-    def process_frame_device(self, d_rgb_ptr, d_depth_ptr, prior_pose=None, pixel_mask=None, motion=None):
-        """pixel_mask: None or the device address of an H x W uint8 pixel mask (ssf_dynamic.h); motion: as process_frame"""
+    def process_frame_device(self, d_rgb_ptr, d_depth_ptr, prior_pose=None, pixel_mask=None, motion=None, odometry=None):
+        """pixel_mask: None or the device address of an H x W uint8 pixel mask (ssf_dynamic.h); motion, odometry: as process_frame"""
         prior = None if prior_pose is None else np.ascontiguousarray(prior_pose, np.float32)
+        if odometry is not None:
+            if prior is not None or pixel_mask is not None:
+                raise SsfError("odometry makes the pose prior itself and combines only with motion: not with prior_pose or pixel_mask")
+            return self._process_frame_odometry(C.c_void_p(d_rgb_ptr), C.c_void_p(d_depth_ptr), True, odometry, motion)
         if motion is not None:
             if pixel_mask is not None:
                 raise SsfError("motion does not combine with pixel_mask: it makes the frame's pixel mask itself")

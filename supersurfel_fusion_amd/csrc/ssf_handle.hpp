@@ -1,6 +1,6 @@
 // ssf_handle.hpp -- the handle (ssf_handle, the types it holds by value, HCK) and the few host helpers that the entry points
 // outside ssf_host.hip call.  Private to the library's host code: included by ssf_host.hip (the core ABI, where the helpers are
-// defined), by ssf_render.hip, ssf_query.hip, ssf_motion.hip, ssf_graph.hip, ssf_graph_solve.hip and ssf_keyframes.hip, whose entry points sit next to their kernels,
+// defined), by ssf_render.hip, ssf_query.hip, ssf_motion.hip, ssf_odometry.hip, ssf_graph.hip, ssf_graph_solve.hip and ssf_keyframes.hip, whose entry points sit next to their kernels,
 // and through ssf_exchange.hpp by ssf_exchange.hip.  Nothing here is part of the frame path's device interface (ssf_device.hpp).
 #pragma once
 #include <algorithm>
@@ -19,6 +19,7 @@
 #include "../../include/ssf_graph_solve.h"
 #include "../../include/ssf_keyframes.h"
 #include "../../include/ssf_motion.h"
+#include "../../include/ssf_odometry.h"
 
 struct ncclComm; typedef struct ncclComm* ncclComm_t;      // (as <rccl/rccl.h> declares it: the handle only holds communicators)
 struct Uploader;                                            // the handle only points to it (ssf_host.hip)
@@ -186,6 +187,22 @@ struct MotionWs {
     size_t pixels = 0;
     bool have_last = false; ssf_motion_stats last_stats{};
 };
+// ssf_odometry_* (ssf_odometry.h): two pyramids (I, D, gx, gy; every level in one buffer each, level l at off[l]) that swap the
+// roles of reference and current, the staged host images, the record.  Allocated on first use as a whole or not at all
+// (DevBufs::grow).  Nothing here is read or written by the frame path.
+struct OdoPyramid { float* I = nullptr; float* D = nullptr; float* gx = nullptr; float* gy = nullptr; };
+struct OdoWs {
+    DevBufs bufs;
+    OdoPyramid pyr[2]; int ref = 0;                               // pyr[ref] is the reference, pyr[1 - ref] the current frame
+    unsigned char* rgb_in = nullptr; unsigned char* depth_in = nullptr; uint8_t* mask_in = nullptr;     // host images, uploaded (4 P, 4 P, P)
+    unsigned long long* rec = nullptr;                            // the 29-word record
+    size_t pixels = 0;
+    int levels = 0, lw[SSF_ODO_MAX_LEVELS] = {}, lh[SSF_ODO_MAX_LEVELS] = {}; size_t off[SSF_ODO_MAX_LEVELS + 1] = {};
+    float lfx[SSF_ODO_MAX_LEVELS] = {}, lfy[SSF_ODO_MAX_LEVELS] = {}, lcx[SSF_ODO_MAX_LEVELS] = {}, lcy[SSF_ODO_MAX_LEVELS] = {};
+    bool have_ref = false, have_cur = false, ref_pose_pending = false, have_last = false;
+    Rt ref_pose;
+    float last_rel[12] = {}, last_prior[12] = {}; ssf_odometry_result last_result{};
+};
 // ssf_graph_build (ssf_graph.h): the resident node table and binding, and the working buffers of the time-order sort.  Allocated
 // on first use; each group (per slot / per node) is grown as a whole or not at all (DevBufs::grow)
 struct GraphWs {
@@ -331,6 +348,7 @@ struct ssf_handle {
     SolveWs solve;                                // ssf_graph_solve (ssf_graph_solve.h)
     QueryWs query;                                // ssf_query_* (ssf_query.h)
     MotionWs motion;                              // ssf_motion_* (ssf_motion.h)
+    OdoWs odo;                                    // ssf_odometry_* (ssf_odometry.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense)
 };
 

@@ -25,7 +25,12 @@ confidence -1 and take no part in tracking or fusion.
 --detect-motion lets the library make that mask itself from each depth frame and the map as it stands after the frame before
 (include/ssf_motion.h: pixels clearly in front of the map, grown over depth-continuous pixels the map does not show).  The mask of
 frame k needs the map after frame k - 1, so the run is sequential: not with --pipelined, and not with --dynamic-masks.
---motion-mask-dir DIR writes every frame's mask to DIR/<rgb stamp>.png (0 / 255)."""
+--motion-mask-dir DIR writes every frame's mask to DIR/<rgb stamp>.png (0 / 255).
+
+--odometry-prior gives every frame but the first a pose prior from the library's dense RGB-D odometry against the frame before
+(include/ssf_odometry.h); a frame whose estimate is invalid is tracked from the previous pose as without the option.  The prior of
+frame k needs the pose of frame k - 1, so the run is sequential: not with --pipelined.  Together with --detect-motion the mask is
+rendered at the odometry prior."""
 import argparse
 import os
 
@@ -208,7 +213,7 @@ def keyframe_line(fusion, stamp, rec):
 
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
            keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30, detect_motion=False,
-           motion_mask_dir=None):
+           motion_mask_dir=None, odometry_prior=False):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
@@ -223,8 +228,17 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     lines go (they are also kept in fusion.keyframe_lines).
     detect_motion: True or a dict of ssf_motion_params fields: every frame is processed with the pixel mask the library detects
     from its depth and the map (include/ssf_motion.h); sequential only, and not together with mask_dir.  motion_mask_dir: where
-    write_motion_mask puts each of those masks."""
+    write_motion_mask puts each of those masks.
+    odometry_prior: True or a dict of ssf_odometry_params fields: every frame's pose prior comes from the library's dense odometry
+    against the frame before (include/ssf_odometry.h); sequential only, not together with mask_dir; with detect_motion the mask
+    is rendered at that prior."""
     lines, results = [], []
+    if odometry_prior:
+        if pipelined:
+            raise ValueError("the odometry prior needs sequential processing (the prior of frame k is composed with the pose of frame "
+                             "k - 1): replay it without pipelined")
+        if mask_dir:
+            raise ValueError("odometry_prior combines with detect_motion, not with mask_dir")
     if detect_motion:
         if pipelined:
             raise ValueError("motion detection needs sequential processing (the mask of frame k is taken against the map after frame "
@@ -246,7 +260,11 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     if not pipelined:
         for stamp, rgb, depth in frames:
             m = mask_of(stamp, depth)
-            if detect_motion:
+            if odometry_prior:
+                r = fusion.process_frame(rgb, depth, odometry=odometry_prior, motion=detect_motion or None)
+                if detect_motion and motion_mask_dir:
+                    write_motion_mask(fusion, motion_mask_dir, stamp)
+            elif detect_motion:
                 r = fusion.process_frame(rgb, depth, motion=detect_motion)
                 if motion_mask_dir:
                     write_motion_mask(fusion, motion_mask_dir, stamp)
@@ -402,6 +420,9 @@ def parse_args(argv=None):
                     help="the library detects the moving objects itself from each depth frame and the map (sequential: not with "
                          "--pipelined; not with --dynamic-masks)")
     ap.add_argument("--motion-mask-dir", default=None, metavar="DIR", help="with --detect-motion: every frame's mask as DIR/<rgb stamp>.png")
+    ap.add_argument("--odometry-prior", action="store_true",
+                    help="the pose prior of every frame comes from the library's dense RGB-D odometry against the frame before "
+                         "(sequential: not with --pipelined; not with --dynamic-masks; combines with --detect-motion)")
     ap.add_argument("--render-dir", default=None, metavar="DIR",
                     help="every --render-every frames, the model drawn at the tracked pose: DIR/<stamp>_rgb.png and DIR/<stamp>_depth.npy")
     ap.add_argument("--render-every", type=int, default=30, metavar="K")
@@ -420,6 +441,11 @@ def parse_args(argv=None):
     if a.detect_motion and a.pipelined:
         ap.error("--detect-motion needs sequential processing (the mask of frame k is taken against the map after frame k - 1): "
                  "not with --pipelined")
+    if a.odometry_prior and a.pipelined:
+        ap.error("--odometry-prior needs sequential processing (the prior of frame k is composed with the pose of frame k - 1): "
+                 "not with --pipelined")
+    if a.odometry_prior and a.dynamic_masks:
+        ap.error("--odometry-prior combines with --detect-motion, not with --dynamic-masks")
     if a.motion_mask_dir and not a.detect_motion:
         ap.error("--motion-mask-dir needs --detect-motion")
     return a
@@ -438,7 +464,8 @@ def main():
     lines, res = replay(f, frames, a.out, a.export_model, pipelined=a.pipelined, mask_dir=a.dynamic_masks,
                         render_dir=a.render_dir, render_every=a.render_every, local_cloud_dir=a.local_cloud_dir,
                         local_cloud_radius=a.local_cloud_radius, local_cloud_every=a.local_cloud_every, keyframes={} if a.keyframes else None,
-                        keyframe_log=a.keyframe_log, detect_motion=a.detect_motion, motion_mask_dir=a.motion_mask_dir)
+                        keyframe_log=a.keyframe_log, detect_motion=a.detect_motion, motion_mask_dir=a.motion_mask_dir,
+                        odometry_prior=a.odometry_prior)
     if a.keyframes and not a.keyframe_log:
         print("\n".join(f.keyframe_lines))
     print("%d frames -> %s ; %d supersurfels" % (len(lines), a.out, res[-1]["n_model"] if res else 0))
