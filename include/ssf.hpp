@@ -13,6 +13,7 @@
 #ifndef SSF_HPP
 #define SSF_HPP
 #include <algorithm>
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -21,6 +22,7 @@
 #include "ssf_dynamic.h"
 #include "ssf_render.h"
 #include "ssf_query.h"
+#include "ssf_navgrid.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
 #include "ssf_graph.h"
@@ -227,6 +229,30 @@ struct QueryResult {
     HostSupersurfels rows;
     std::vector<int32_t> index;
     ssf_query_stats stats;
+};
+
+/* buildNavGrid (ssf_navgrid.h; exported by libssf_hip.so only): the floor-plane navigation grid of the map.  The members start at
+ * ssf_navgrid_default_params' values (design choices, see the header); pose nullptr = floor-aligned about the camera with heights
+ * measured from the first camera -- a node that knows how its camera is mounted passes its own frame and bands */
+struct NavGridParams {
+    const Transform3* pose = nullptr;              /* grid-to-map: x, y span the floor, z up */
+    int width = 512, height = 512; float res = 0.05f;
+    float z_min = -1.5f, z_max = 0.5f, floor_max = -0.8f, floor_cos = 0.8f, min_conf = 0.f;
+    int32_t t_init_min = -2147483647 - 1, t_init_max = 2147483647, t_last_min = -2147483647 - 1, t_last_max = 2147483647;
+    bool visible_only = false;
+    float splat_scale = 2.f; int max_steps = 8, min_hits = 1, max_dist_cells = 40;
+    bool unknown_is_obstacle = false;
+    bool want_heights = true, want_hits = true, want_state = true, want_dist2 = true;      /* false: not produced (its vector stays empty) */
+};
+/* the grid buildNavGrid makes, row-major height x width (cell (ix, iy) at iy * width + ix), and its statistics; stats.pose is the
+ * grid frame that was used */
+struct NavGrid {
+    int width = 0, height = 0; float res = 0.f;
+    std::vector<float> zmin, zmax;                 /* +inf / -inf where nothing was seen */
+    std::vector<uint32_t> hits;                    /* x 2: floor samples, obstacle samples */
+    std::vector<int8_t> state;                     /* nav_msgs/OccupancyGrid's values: 100 occupied, 0 free, -1 unknown */
+    std::vector<int32_t> dist2;                    /* squared distance in cells to the nearest obstacle cell, capped at max_dist_cells^2 */
+    ssf_navgrid_stats stats;
 };
 
 /* the deformation graph's binding (ssf_graph.h): four node indices and four weights per row, in getModelHost()'s row order */
@@ -580,6 +606,46 @@ public:
         const size_t n = (size_t)s.n_selected;
         positions.resize(n); colors.resize(n); normals.resize(n);
         for (size_t i = 0; i < n; i++) { normals[i].x = ori[9 * i + 6]; normals[i].y = ori[9 * i + 7]; normals[i].z = ori[9 * i + 8]; }
+    }
+    /* The floor-plane navigation grid of the map, built on the device (ssf_navgrid.h): per cell the height range, the floor and
+     * obstacle hit counts, the occupancy state and the squared clearance -- without the copy of the whole map, the host
+     * rasteriser and the host distance transform a node would otherwise need.  INTEGRATION.md section 2 has the publishing side. */
+    void buildNavGrid(const NavGridParams& g, NavGrid& out) {
+        ssf_navgrid_params p; float v[12];
+        check(ssf_navgrid_default_params(need(), &p));
+        if (g.pose) { transform3_to_rt(*g.pose, v); p.pose = v; }
+        p.width = g.width; p.height = g.height; p.res = g.res;
+        p.z_min = g.z_min; p.z_max = g.z_max; p.floor_max = g.floor_max; p.floor_cos = g.floor_cos; p.min_conf = g.min_conf;
+        p.t_init_min = g.t_init_min; p.t_init_max = g.t_init_max; p.t_last_min = g.t_last_min; p.t_last_max = g.t_last_max;
+        p.visible_only = g.visible_only ? 1 : 0; p.splat_scale = g.splat_scale; p.max_steps = g.max_steps; p.min_hits = g.min_hits;
+        p.max_dist_cells = g.max_dist_cells; p.unknown_is_obstacle = g.unknown_is_obstacle ? 1 : 0; p.on_device = 0;
+        const size_t n = (p.width >= 1 && p.height >= 1) ? (size_t)p.width * (size_t)p.height : 1;
+        out.width = p.width; out.height = p.height; out.res = p.res;
+        out.zmin.resize(g.want_heights ? n : 0); out.zmax.resize(g.want_heights ? n : 0); out.hits.resize(g.want_hits ? 2 * n : 0);
+        out.state.resize(g.want_state ? n : 0); out.dist2.resize(g.want_dist2 ? n : 0);
+        const ssf_navgrid_out o = {g.want_heights ? out.zmin.data() : nullptr, g.want_heights ? out.zmax.data() : nullptr,
+                                   g.want_hits ? out.hits.data() : nullptr, g.want_state ? out.state.data() : nullptr,
+                                   g.want_dist2 ? out.dist2.data() : nullptr};
+        check(ssf_navgrid_build(need(), &p, &o, &out.stats));
+    }
+    /* The fields of a nav_msgs::OccupancyGrid that the grid determines: data, info.resolution, info.width, info.height and
+     * info.origin (the map-frame pose of cell (0, 0)'s corner: the grid frame's t, and its rotation as a quaternion).  header and
+     * info.map_load_time are the node's.  Any message type with these members works (tests use a double). */
+    template <typename OccupancyGridT> static void fillOccupancyGrid(const NavGrid& g, OccupancyGridT& msg) {
+        if (g.state.size() != (size_t)g.width * (size_t)g.height) throw std::logic_error("fillOccupancyGrid: the grid has no state (want_state)");
+        msg.info.resolution = g.res; msg.info.width = (unsigned)g.width; msg.info.height = (unsigned)g.height;
+        msg.data.assign(g.state.begin(), g.state.end());
+        const float* R = g.stats.pose;
+        msg.info.origin.position.x = R[9]; msg.info.origin.position.y = R[10]; msg.info.origin.position.z = R[11];
+        /* rotation matrix (row-major) -> unit quaternion, the branch with the largest divisor */
+        const double m00 = R[0], m01 = R[1], m02 = R[2], m10 = R[3], m11 = R[4], m12 = R[5], m20 = R[6], m21 = R[7], m22 = R[8];
+        const double tr = m00 + m11 + m22;
+        double qw, qx, qy, qz;
+        if (tr > 0.0) { const double s = 2.0 * std::sqrt(tr + 1.0); qw = 0.25 * s; qx = (m21 - m12) / s; qy = (m02 - m20) / s; qz = (m10 - m01) / s; }
+        else if (m00 > m11 && m00 > m22) { const double s = 2.0 * std::sqrt(1.0 + m00 - m11 - m22); qw = (m21 - m12) / s; qx = 0.25 * s; qy = (m01 + m10) / s; qz = (m02 + m20) / s; }
+        else if (m11 > m22) { const double s = 2.0 * std::sqrt(1.0 + m11 - m00 - m22); qw = (m02 - m20) / s; qx = (m01 + m10) / s; qy = 0.25 * s; qz = (m12 + m21) / s; }
+        else { const double s = 2.0 * std::sqrt(1.0 + m22 - m00 - m11); qw = (m10 - m01) / s; qx = (m02 + m20) / s; qy = (m12 + m21) / s; qz = 0.25 * s; }
+        msg.info.origin.orientation.x = qx; msg.info.origin.orientation.y = qy; msg.info.origin.orientation.z = qz; msg.info.origin.orientation.w = qw;
     }
     /* The deformation graph of a loop closure, built and kept on the device (ssf_graph.h; exported by libssf_hip.so only): every
      * stride-th confident row in birth order is a node, every row is bound to its four nearest nodes among the 2 * look born

@@ -98,6 +98,12 @@ FERN_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("r", np.uint8), ("g"
 # rows of the model selected on the device (include/ssf_query.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 QUERY_SYMBOLS = ["ssf_query_default_params", "ssf_query_count", "ssf_query_rows"]
 QUERY_REGIONS = {"all": 0, "sphere": 1, "box": 2, "frustum": 3}
+# the floor-plane navigation grid (include/ssf_navgrid.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
+NAVGRID_SYMBOLS = ["ssf_navgrid_default_params", "ssf_navgrid_default_pose", "ssf_navgrid_build"]
+# the arrays of ssf_navgrid_out, in its field order: name, dtype, per-cell shape
+NAVGRID_OUTPUTS = (("zmin", np.float32, ()), ("zmax", np.float32, ()), ("hits", np.uint32, (2,)), ("state", np.int8, ()),
+                   ("dist2", np.int32, ()))
+NAVGRID_OUTPUT_NAMES = tuple(nm for nm, _, _ in NAVGRID_OUTPUTS)
 # the geometric moving-object detector (include/ssf_motion.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 MOTION_SYMBOLS = ["ssf_motion_default_params", "ssf_motion_segment", "ssf_motion_mask", "ssf_process_frame_motion", "ssf_get_motion_mask"]
 # dense RGB-D odometry, the pose prior of the library's own (include/ssf_odometry.h): HIP product only, not part of ssf.h
@@ -188,6 +194,31 @@ class SsfQueryStats(C.Structure):
     def as_dict(self):
         return dict(n_scanned=int(self.n_scanned), n_selected=int(self.n_selected), n_selected_visible=int(self.n_selected_visible),
                     lo=np.array(self.lo[:], np.float32), hi=np.array(self.hi[:], np.float32))
+
+
+class SsfNavGridParams(C.Structure):
+    """ssf_navgrid_params (include/ssf_navgrid.h)"""
+    _fields_ = [("pose", C.c_void_p), ("width", C.c_int), ("height", C.c_int)] + \
+               [(nm, C.c_float) for nm in ("res", "z_min", "z_max", "floor_max", "floor_cos", "min_conf")] + \
+               [(nm, C.c_int32) for nm in ("t_init_min", "t_init_max", "t_last_min", "t_last_max")] + \
+               [("visible_only", C.c_int), ("splat_scale", C.c_float)] + \
+               [(nm, C.c_int) for nm in ("max_steps", "min_hits", "max_dist_cells", "unknown_is_obstacle", "on_device")]
+
+
+class SsfNavGridOut(C.Structure):
+    """ssf_navgrid_out (include/ssf_navgrid.h)"""
+    _fields_ = [(nm, C.c_void_p) for nm in ("zmin", "zmax", "hits", "state", "dist2")]
+
+
+class SsfNavGridStats(C.Structure):
+    """ssf_navgrid_stats (include/ssf_navgrid.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("rows_used", "samples", "samples_in_grid", "cells_free", "cells_occupied", "cells_unknown",
+                                           "list_entries")] + [("pose", C.c_float * 12)]
+
+    def as_dict(self):
+        d = {nm: int(getattr(self, nm)) for nm, _ in self._fields_ if nm != "pose"}
+        d["pose"] = np.array(self.pose[:], np.float32)
+        return d
 
 
 class SsfGraphParams(C.Structure):
@@ -335,6 +366,11 @@ class Library:
             L.ssf_query_default_params.argtypes = [vp, C.POINTER(SsfQueryParams)]
             L.ssf_query_count.argtypes = [vp, C.POINTER(SsfQueryParams), C.POINTER(SsfQueryStats)]
             L.ssf_query_rows.argtypes = [vp, C.POINTER(SsfQueryParams), C.POINTER(SsfSurfels), vp, C.c_int, C.POINTER(SsfQueryStats)]
+        self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
+        if self.has_navgrid:
+            L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
+            L.ssf_navgrid_default_pose.argtypes = [vp, C.POINTER(SsfNavGridParams), vp]
+            L.ssf_navgrid_build.argtypes = [vp, C.POINTER(SsfNavGridParams), C.POINTER(SsfNavGridOut), C.POINTER(SsfNavGridStats)]
         self.has_motion = all(hasattr(L, nm) for nm in MOTION_SYMBOLS)
         if self.has_motion:
             mp, ms = C.POINTER(SsfMotionParams), C.POINTER(SsfMotionStats)
@@ -977,6 +1013,86 @@ class Fusion:
             capacity = min(int(t.shape[0]) for t in list(outs.values()) + ([index] if index is not None else []))
         addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
         return self._query_rows(p, {nm: addr(t) for nm, t in outs.items()}, addr(index), capacity)
+
+    # ---- the floor-plane navigation grid: height, occupancy, clearance (include/ssf_navgrid.h) ------
+    def _need_navgrid(self, symbol):
+        if not self.L.has_navgrid:
+            raise SsfError("%s does not export %s: it builds no navigation grid (include/ssf_navgrid.h, HIP product only)"
+                           % (self.L.path, symbol))
+
+    def _navgrid_params(self, on_device, pose=None, t_init=None, t_last=None, visible_only=False, unknown_is_obstacle=False, **kw):
+        """(SsfNavGridParams, the pose array it points into).  pose: 12 floats or a 3 x 4 [R | t] grid-to-map (None = floor-aligned
+        about the camera: include/ssf_navgrid.h); t_init / t_last: (min, max) of stamps.x / stamps.y (None = any); the other
+        keywords are fields of ssf_navgrid_params (width, height, res, z_min, z_max, floor_max, floor_cos, min_conf, splat_scale,
+        max_steps, min_hits, max_dist_cells), each at ssf_navgrid_default_params' value when missing."""
+        p = SsfNavGridParams()
+        self._ck(self.L.lib.ssf_navgrid_default_params(self.h, C.byref(p)), "ssf_navgrid_default_params")
+        keep = None
+        if pose is not None:
+            pose = np.asarray(pose, np.float32)
+            if pose.shape == (3, 4):
+                pose = np.concatenate([pose[:, :3].ravel(), pose[:, 3]])
+            if pose.size != 12:
+                raise SsfError("a grid pose is 12 floats (R row-major, then t) or 3 x 4 [R | t], got shape %s" % (pose.shape,))
+            keep = np.ascontiguousarray(pose.ravel(), np.float32)
+            p.pose = keep.ctypes.data
+        if t_init is not None:
+            p.t_init_min, p.t_init_max = int(t_init[0]), int(t_init[1])
+        if t_last is not None:
+            p.t_last_min, p.t_last_max = int(t_last[0]), int(t_last[1])
+        kinds = dict(p._fields_)
+        for nm, v in kw.items():
+            if nm not in kinds or nm in ("pose", "on_device") or nm.startswith("t_"):
+                raise SsfError("unknown navigation grid parameter %r" % nm)
+            setattr(p, nm, float(v) if kinds[nm] is C.c_float else int(v))
+        p.visible_only, p.unknown_is_obstacle, p.on_device = int(bool(visible_only)), int(bool(unknown_is_obstacle)), int(bool(on_device))
+        return p, keep
+
+    def _navgrid_build(self, p, ptrs):
+        st = SsfNavGridStats()
+        out = SsfNavGridOut(*[ptrs.get(nm) for nm in NAVGRID_OUTPUT_NAMES])
+        self._ck(self.L.lib.ssf_navgrid_build(self.h, C.byref(p), C.byref(out), C.byref(st)), "ssf_navgrid_build")
+        return st.as_dict()
+
+    def nav_grid(self, outputs=NAVGRID_OUTPUT_NAMES, **kw):
+        """The navigation grid of the model (ssf_navgrid_build): dict of the requested arrays (zmin / zmax H x W f32, hits H x W x 2
+        u32 (floor, obstacle), state H x W i8 (100 occupied, 0 free, -1 unknown), dist2 H x W i32: squared cells to the nearest
+        obstacle cell, capped) and 'stats' (the counts, and 'pose': the grid frame used).  Keywords: _navgrid_params."""
+        self._need_navgrid("ssf_navgrid_build")
+        bad = [nm for nm in outputs if nm not in NAVGRID_OUTPUT_NAMES]
+        if bad:
+            raise SsfError("unknown navigation grid outputs %s (known: %s)" % (bad, ", ".join(NAVGRID_OUTPUT_NAMES)))
+        p, keep = self._navgrid_params(False, **kw)
+        W, H = p.width, p.height
+        if not (1 <= W <= 4096 and 1 <= H <= 4096):
+            W = H = 1                        # (the library refuses the size and writes nothing)
+        out = {nm: np.empty((H, W) + tail, dt) for nm, dt, tail in NAVGRID_OUTPUTS if nm in outputs}
+        stats = self._navgrid_build(p, {nm: _ptr(a) for nm, a in out.items()})
+        out["stats"] = stats
+        return out
+
+    def nav_grid_device(self, zmin=None, zmax=None, hits=None, state=None, dist2=None, **kw):
+        """ssf_navgrid_build into device memory: each output is None, a contiguous torch tensor on the device or the device address
+        (int) of a buffer of the shape and dtype nav_grid returns.  Returns the stats dict."""
+        self._need_navgrid("ssf_navgrid_build")
+        p, keep = self._navgrid_params(True, **kw)
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        return self._navgrid_build(p, dict(zmin=addr(zmin), zmax=addr(zmax), hits=addr(hits), state=addr(state), dist2=addr(dist2)))
+
+    def nav_grid_default_params(self):
+        """ssf_navgrid_default_params as a dict"""
+        self._need_navgrid("ssf_navgrid_default_params")
+        p = SsfNavGridParams()
+        self._ck(self.L.lib.ssf_navgrid_default_params(self.h, C.byref(p)), "ssf_navgrid_default_params")
+        return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm != "pose"}
+
+    def nav_grid_default_pose(self, **kw):
+        """the grid frame that pose=None means now (ssf_navgrid_default_pose): 12 floats, grid-to-map"""
+        self._need_navgrid("ssf_navgrid_default_pose")
+        p, keep = self._navgrid_params(False, **kw)
+        pose = np.zeros(12, np.float32)
+        self._ck(self.L.lib.ssf_navgrid_default_pose(self.h, C.byref(p), _ptr(pose)), "ssf_navgrid_default_pose")
+        return pose
 
     # ---- the deformation graph's nodes and per-row binding (include/ssf_graph.h) ------------------
     def _need_graph(self, symbol):

@@ -1,6 +1,6 @@
 // ssf_handle.hpp -- the handle (ssf_handle, the types it holds by value, HCK) and the few host helpers that the entry points
 // outside ssf_host.hip call.  Private to the library's host code: included by ssf_host.hip (the core ABI, where the helpers are
-// defined), by ssf_render.hip, ssf_query.hip, ssf_motion.hip, ssf_odometry.hip, ssf_graph.hip, ssf_graph_solve.hip and ssf_keyframes.hip, whose entry points sit next to their kernels,
+// defined), by ssf_render.hip, ssf_query.hip, ssf_navgrid.hip, ssf_motion.hip, ssf_odometry.hip, ssf_graph.hip, ssf_graph_solve.hip and ssf_keyframes.hip, whose entry points sit next to their kernels,
 // and through ssf_exchange.hpp by ssf_exchange.hip.  Nothing here is part of the frame path's device interface (ssf_device.hpp).
 #pragma once
 #include <algorithm>
@@ -20,6 +20,7 @@
 #include "../../include/ssf_keyframes.h"
 #include "../../include/ssf_motion.h"
 #include "../../include/ssf_odometry.h"
+#include "../../include/ssf_navgrid.h"
 
 struct ncclComm; typedef struct ncclComm* ncclComm_t;      // (as <rccl/rccl.h> declares it: the handle only holds communicators)
 struct Uploader;                                            // the handle only points to it (ssf_host.hip)
@@ -253,6 +254,19 @@ struct QueryWs {
     uint32_t* rec = nullptr;
     unsigned char* rows = nullptr; size_t rows_bytes = 0;
 };
+// ssf_navgrid_build (ssf_navgrid.h): per slot the grid-frame record and the cell box, per 32 x 32-cell tile (+ 1) the counts that
+// the scan turns into list offsets and the fill's cursors, the (tile -> slot) lists, per cell the four accumulator words, the column distances and
+// the state when the caller did not ask for it, the seven 64-bit sums, and the staging buffer of host outputs.  Allocated on first use;
+// each group is grown as a whole or not at all (DevBufs::grow).  Nothing here is read or written by the frame path.
+struct NavGridWs {
+    DevBufs bufs;
+    float4* rec = nullptr; uint2* rbox = nullptr; size_t slots = 0;
+    uint32_t* tcnt = nullptr; uint32_t* cursor = nullptr; size_t tiles = 0;
+    uint32_t* list = nullptr; size_t list_cap = 0;
+    uint32_t* acc = nullptr; uint16_t* colg = nullptr; int8_t* state = nullptr; size_t cells = 0;
+    unsigned long long* stats = nullptr;
+    unsigned char* img = nullptr; size_t img_bytes = 0;
+};
 struct ssf_handle {
     ssf_config cfg;
     int S = 0, gx = 0, gy = 0;
@@ -349,6 +363,7 @@ struct ssf_handle {
     QueryWs query;                                // ssf_query_* (ssf_query.h)
     MotionWs motion;                              // ssf_motion_* (ssf_motion.h)
     OdoWs odo;                                    // ssf_odometry_* (ssf_odometry.h)
+    NavGridWs navgrid;                            // ssf_navgrid_build (ssf_navgrid.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense)
 };
 

@@ -36,10 +36,6 @@ struct QueryOut { float *pos, *col; int32_t* stamps; float *ori, *shape, *dims, 
 // the record the host reads: [0] n_selected, [1] live out-of-view rows, [2] n_selected_visible, [3..5] lo, [6..8] hi (encoded)
 enum { QREC_WORDS = 9, QREC_LO = 3, QREC_HI = 6 };
 
-// the order-preserving unsigned image of a float (no NaN comes here): a < b <=> enc(a) < enc(b)
-__host__ __device__ __forceinline__ uint32_t float_order_bits(uint32_t u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__host__ __device__ __forceinline__ uint32_t float_order_bits_inv(uint32_t e) { return (e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e; }
-
 // the region test of include/ssf_query.h, steps 2 and 3 (contraction off: one IEEE operation each, in this order)
 __device__ __forceinline__ bool query_inside(const QueryArgs& q, float px, float py, float pz) {
     if (q.region == SSF_REGION_ALL) return true;

@@ -1,7 +1,7 @@
 // ssf_slots.hpp -- device helpers of the kernels that walk the model one thread per SLOT (ModelView, ssf_device.hpp) and of the
 // store upkeep (out-of-view compaction, re-homing): the slot -> row map, live counts and ranks inside a 256-thread block, and
 // the one-workgroup exclusive scan that turns per-block counts into offsets.  Device-only; included by ssf_render.hip,
-// ssf_graph.hip and ssf_track_fuse.hip.  (The per-frame kernels -- ICP, association, fuse, partition, row move, k_bin_* -- keep
+// ssf_query.hip, ssf_navgrid.hip, ssf_graph.hip and ssf_track_fuse.hip.  (The per-frame kernels -- ICP, association, fuse, partition, row move, k_bin_* -- keep
 // their own ballots and scans, tuned to the instruction; they do not go through these.)
 #pragma once
 #include "ssf_device.hpp"
@@ -10,6 +10,10 @@ namespace ssf {
 
 __device__ __forceinline__ int lane() { return threadIdx.x & 63; }
 __device__ __forceinline__ bool finite3(float a, float b, float c) { return isfinite(a) && isfinite(b) && isfinite(c); }
+
+// the order-preserving unsigned image of a float (no NaN comes here): a < b <=> enc(a) < enc(b)
+__host__ __device__ __forceinline__ uint32_t float_order_bits(uint32_t u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__host__ __device__ __forceinline__ uint32_t float_order_bits_inv(uint32_t e) { return (e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e; }
 
 // row head + i of an out-of-view span [head, tail): its physical index, and whether it holds a row (the span has holes, and its
 // last 256-block reaches past the tail: the bound comes first, the flag behind the tail is never read)

@@ -199,6 +199,29 @@ def write_local_cloud(fusion, cloud_dir, k, radius):
     return out["stats"]
 
 
+def write_nav_grid(fusion, grid_dir, k, res):
+    """the navigation grid of the map, built on the device (include/ssf_navgrid.h) at the default size and frame (floor-aligned
+    about the tracked camera) with cells of `res` metres: grid_dir/<k as %06d>.pgm -- the state in map_server's convention (205
+    unknown, 254 free, 0 occupied; the image's top row is the grid's last) --, <k>.yaml beside it (map_server's keys; origin = the
+    grid's corner along its own x and y axes; grid_to_map = the grid frame's 12 floats) and <k>_dist2.npy (squared clearance in
+    cells)"""
+    out = fusion.nav_grid(outputs=("state", "dist2"), res=res)
+    state, pose = out["state"], out["stats"]["pose"]
+    os.makedirs(grid_dir, exist_ok=True)
+    name = "%06d" % k
+    img = np.where(state == 100, 0, np.where(state == 0, 254, 205)).astype(np.uint8)[::-1]
+    with open(os.path.join(grid_dir, name + ".pgm"), "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
+        f.write(np.ascontiguousarray(img).tobytes())
+    R, t = pose[:9].reshape(3, 3).astype(np.float64), pose[9:].astype(np.float64)
+    with open(os.path.join(grid_dir, name + ".yaml"), "w") as f:
+        f.write("image: %s.pgm\nresolution: %.9g\norigin: [%.9g, %.9g, 0.0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n"
+                % (name, res, float(R[:, 0] @ t), float(R[:, 1] @ t)))
+        f.write("grid_to_map: [%s]\n" % ", ".join("%.9g" % v for v in pose))
+    np.save(os.path.join(grid_dir, name + "_dist2.npy"), out["dist2"])
+    return out["stats"]
+
+
 def keyframe_line(fusion, stamp, rec):
     """one line of the keyframe log: stamp, the id the frame was stored under (or -; "full" when the store had no room),
     min_diff_all, then every loop candidate as id:diff with the verdict of aligning it against the frame (include/ssf_keyframes.h;
@@ -213,7 +236,7 @@ def keyframe_line(fusion, stamp, rec):
 
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
            keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30, detect_motion=False,
-           motion_mask_dir=None, odometry_prior=False):
+           motion_mask_dir=None, odometry_prior=False, nav_grid_dir=None, nav_grid_every=30, nav_grid_res=0.05):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
@@ -223,6 +246,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     submission pauses at such a frame until it has been processed (a render needs no frame pending).
     local_cloud_dir: after frames 0, local_cloud_every, 2 local_cloud_every, ... the rows within local_cloud_radius of the tracked
     pose are written (write_local_cloud, numbered by frame); pipelined, submission pauses as for a render.
+    nav_grid_dir: after frames 0, nav_grid_every, 2 nav_grid_every, ... the navigation grid of the map with cells of nav_grid_res
+    metres is written (write_nav_grid, numbered by frame); pipelined, submission pauses as for a render.
     keyframes: a dict of ssf_keyframes_params fields ({} = the defaults): the keyframe database is configured and
     keyframes_consider runs after every frame (not pipelined: it needs no frame pending); keyframe_log: where keyframe_line's
     lines go (they are also kept in fusion.keyframe_lines).
@@ -254,8 +279,10 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
         fusion.keyframe_lines = []
     render_every = max(1, int(render_every))
     local_cloud_every = max(1, int(local_cloud_every))
+    nav_grid_every = max(1, int(nav_grid_every))
     # a frame after which the model is looked at (a render, a local cloud): nothing may be pending then
-    looks = lambda k: bool((render_dir and k % render_every == 0) or (local_cloud_dir and k % local_cloud_every == 0))
+    looks = lambda k: bool((render_dir and k % render_every == 0) or (local_cloud_dir and k % local_cloud_every == 0) or
+                           (nav_grid_dir and k % nav_grid_every == 0))
     mask_of = (lambda stamp, depth: read_pixel_mask(mask_dir, stamp, np.shape(depth))) if mask_dir else (lambda stamp, depth: None)
     if not pipelined:
         for stamp, rgb, depth in frames:
@@ -278,6 +305,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
                 write_render(fusion, render_dir, stamp)
             if local_cloud_dir and (len(lines) - 1) % local_cloud_every == 0:
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
+            if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
+                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res)
     else:
         it, stamps, done = iter(frames), [], False
         held = []                                         # submitted host buffers stay alive until their frame is processed
@@ -306,6 +335,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
                 write_render(fusion, render_dir, stamps[len(lines) - 1])
             if local_cloud_dir and (len(lines) - 1) % local_cloud_every == 0:
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
+            if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
+                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res)
     if out_path:
         with open(out_path, "w") as f:
             f.write("\n".join(lines) + "\n")
@@ -431,6 +462,11 @@ def parse_args(argv=None):
                          "device: DIR/<frame number as %%06d>.npz (positions, colors, normals, index)")
     ap.add_argument("--local-cloud-radius", type=float, default=2.0, metavar="R", help="metres (default 2)")
     ap.add_argument("--local-cloud-every", type=int, default=30, metavar="K")
+    ap.add_argument("--nav-grid-dir", default=None, metavar="DIR",
+                    help="every --nav-grid-every frames, the navigation grid of the map built on the device: DIR/<frame number as %%06d>.pgm "
+                         "(map_server's convention), .yaml and _dist2.npy (squared clearance in cells)")
+    ap.add_argument("--nav-grid-every", type=int, default=30, metavar="K")
+    ap.add_argument("--nav-grid-res", type=float, default=0.05, metavar="R", help="metres per cell (default 0.05)")
     ap.add_argument("--keyframes", action="store_true",
                     help="keep the fern-coded keyframe database: after every frame one line (stamp, stored id or -, min_diff_all, loop candidates "
                          "with their alignment verdict); not with --pipelined")
@@ -465,7 +501,8 @@ def main():
                         render_dir=a.render_dir, render_every=a.render_every, local_cloud_dir=a.local_cloud_dir,
                         local_cloud_radius=a.local_cloud_radius, local_cloud_every=a.local_cloud_every, keyframes={} if a.keyframes else None,
                         keyframe_log=a.keyframe_log, detect_motion=a.detect_motion, motion_mask_dir=a.motion_mask_dir,
-                        odometry_prior=a.odometry_prior)
+                        odometry_prior=a.odometry_prior, nav_grid_dir=a.nav_grid_dir, nav_grid_every=a.nav_grid_every,
+                        nav_grid_res=a.nav_grid_res)
     if a.keyframes and not a.keyframe_log:
         print("\n".join(f.keyframe_lines))
     print("%d frames -> %s ; %d supersurfels" % (len(lines), a.out, res[-1]["n_model"] if res else 0))
