@@ -104,6 +104,8 @@ NAVGRID_SYMBOLS = ["ssf_navgrid_default_params", "ssf_navgrid_default_pose", "ss
 NAVGRID_OUTPUTS = (("zmin", np.float32, ()), ("zmax", np.float32, ()), ("hits", np.uint32, (2,)), ("state", np.int8, ()),
                    ("dist2", np.int32, ()))
 NAVGRID_OUTPUT_NAMES = tuple(nm for nm, _, _ in NAVGRID_OUTPUTS)
+# the track stage's test hook and counter of the resident ICP launch (include/ssf_track.h): HIP product only, not part of ssf.h
+TRACK_SYMBOLS = ["ssf_debug_set_resident_icp_max_rows", "ssf_resident_icp_frames", "ssf_resident_icp_ahead_frames"]
 # the geometric moving-object detector (include/ssf_motion.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 MOTION_SYMBOLS = ["ssf_motion_default_params", "ssf_motion_segment", "ssf_motion_mask", "ssf_process_frame_motion", "ssf_get_motion_mask"]
 # dense RGB-D odometry, the pose prior of the library's own (include/ssf_odometry.h): HIP product only, not part of ssf.h
@@ -371,6 +373,13 @@ class Library:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
             L.ssf_navgrid_default_pose.argtypes = [vp, C.POINTER(SsfNavGridParams), vp]
             L.ssf_navgrid_build.argtypes = [vp, C.POINTER(SsfNavGridParams), C.POINTER(SsfNavGridOut), C.POINTER(SsfNavGridStats)]
+        self.has_track = all(hasattr(L, nm) for nm in TRACK_SYMBOLS)
+        if self.has_track:
+            L.ssf_debug_set_resident_icp_max_rows.argtypes = [vp, C.c_int]
+            L.ssf_resident_icp_frames.argtypes = [vp]
+            L.ssf_resident_icp_frames.restype = C.c_longlong
+            L.ssf_resident_icp_ahead_frames.argtypes = [vp]
+            L.ssf_resident_icp_ahead_frames.restype = C.c_longlong
         self.has_motion = all(hasattr(L, nm) for nm in MOTION_SYMBOLS)
         if self.has_motion:
             mp, ms = C.POINTER(SsfMotionParams), C.POINTER(SsfMotionStats)
@@ -1406,6 +1415,25 @@ class Fusion:
     def set_bin_min_rows(self, n):
         """visible rows from which a frame's tracking streams a tile-sorted copy of them (product default: 400 000; 0 = always, < 0 = never)"""
         self._ck(self.L.lib.ssf_debug_set_bin_min_rows(self.h, int(n)), "ssf_debug_set_bin_min_rows")
+
+    def set_resident_icp_max_rows(self, n):
+        """visible rows up to which a frame's ICP iterations and association run in one resident launch (product default and ceiling:
+        262 144; 0 = never)"""
+        if not self.L.has_track:
+            raise SsfError("this library has no resident ICP launch (include/ssf_track.h: HIP product only)")
+        self._ck(self.L.lib.ssf_debug_set_resident_icp_max_rows(self.h, int(n)), "ssf_debug_set_resident_icp_max_rows")
+
+    def resident_icp_frames(self):
+        """frames whose ICP iterations ran in a resident launch since the handle was created"""
+        if not self.L.has_track:
+            raise SsfError("this library has no resident ICP launch (include/ssf_track.h: HIP product only)")
+        return int(self.L.lib.ssf_resident_icp_frames(self.h))
+
+    def resident_icp_ahead_frames(self):
+        """... and those of them whose launch started behind a first record made by the frame before"""
+        if not self.L.has_track:
+            raise SsfError("this library has no resident ICP launch (include/ssf_track.h: HIP product only)")
+        return int(self.L.lib.ssf_resident_icp_ahead_frames(self.h))
 
     def set_shard(self, id_offset, global_n_model, global_n_visible):
         self._ck(self.L.lib.ssf_stage_set_shard(self.h, id_offset, global_n_model, global_n_visible), "ssf_stage_set_shard")

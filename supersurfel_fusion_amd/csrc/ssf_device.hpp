@@ -296,6 +296,16 @@ void launch_icp(hipStream_t st, const Cam& cam, SurfelSoA model, int n_visible, 
                 Rt T, long long* replicas, unsigned int* ticket,
                 long long* sums29, Mailbox* mb, unsigned long long seq, int dbg = -1, IcpGo* go = nullptr,
                 unsigned long long go_seq = 0, const struct P2PView* pv = nullptr, int by_tile = 0, const MatchArgs* match = nullptr);
+// The resident form: ONE launch for a frame's iterations and its association (k_icp_resident in ssf_track_fuse.hip).  Every lane
+// keeps its row in registers; the host sends one word per iteration into a line of its own -- go[idx] carries number go_base + idx,
+// the transform and, in IcpGo::x, the sequence number of the record that iteration publishes -- for idx = 1 .. last_idx; a word with
+// SSF_ICP_GO_MATCH (the final pose) or "leave" ends the launch.  The lines of a frame are never reused inside it, so a workgroup
+// that gets its place late finds every word it missed.  T0 != nullptr: iteration 0 runs at once under *T0 and publishes seq0.
+// One row per lane and every workgroup must hold a place until the launch ends: n_visible <= 256 * icp_resident_max_wgs().
+int icp_resident_max_wgs();
+void launch_icp_resident(hipStream_t st, const Cam& cam, SurfelSoA model, int n_visible, const uint2* pix2, const float4* fpack, const Rt* T0,
+                         long long* replicas, long long* sums29, Mailbox* mb, unsigned long long seq0, IcpGo* go, unsigned int go_base,
+                         int last_idx, const MatchArgs* match);
 // Tile-sorted copy of the ICP / association fields of the n visible rows of `model` (pos, lab, r2, conf -> the same
 // streams of `out`; out_idx[j] = the row's index in the visible array) under transform T (model -> camera): see k_bin_* in
 // ssf_track_fuse.hip.  count / cursor: bin_buffer_words(cam, capacity) words each.  launch_icp(by_tile = 1) /

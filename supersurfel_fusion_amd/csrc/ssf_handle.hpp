@@ -21,6 +21,7 @@
 #include "../../include/ssf_motion.h"
 #include "../../include/ssf_odometry.h"
 #include "../../include/ssf_navgrid.h"
+#include "../../include/ssf_track.h"
 
 struct ncclComm; typedef struct ncclComm* ncclComm_t;      // (as <rccl/rccl.h> declares it: the handle only holds communicators)
 struct Uploader;                                            // the handle only points to it (ssf_host.hip)
@@ -334,6 +335,11 @@ struct ssf_handle {
     // chained ICP launches: iteration i + 1 is launched while iteration i runs and waits on the device for the host's
     // word (launch_icp, IcpGo): slots in fine-grained device memory the host stores into directly
     IcpGo* go = nullptr; bool icp_chain = true; unsigned long long go_count = 0;
+    // the resident ICP launch (launch_icp_resident): two sets (frame parity) of cfg.icp_iter + 1 lines behind the SSF_ICP_GO_SLOTS
+    // of `go`, one per iteration index | visible rows up to which a frame takes it (a safety condition: every workgroup of the
+    // launch must hold a place at once; tests lower it) | frames that took it, those of them that started behind a record made ahead,
+    // launches made (picks the set of lines)
+    IcpGo* go_res = nullptr; int resident_max_rows = 0; long long n_resident_frames = 0, n_resident_ahead_frames = 0, n_resident_launches = 0;
     bool graph_failed = false; hipStream_t capture_stream = nullptr;
     TileCopy bins;                                // tile-sorted copy of the visible rows' ICP / association fields, for large visible sets
     // what the fuse launches take as groups: built by ssf_create; plane_depth and migrate are the frame's (fuse_begin)

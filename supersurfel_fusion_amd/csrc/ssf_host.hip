@@ -691,7 +691,9 @@ static void icp_release_waiting(IcpGo* slot, unsigned long long go_seq, const Rt
 
 // a launch made ahead that is waiting on the device for the host's word: the slot the word goes to, the number the word
 // carries and the sequence number of the record the launch will publish
-struct IcpWaiter { bool waiting = false; IcpGo* slot = nullptr; unsigned long long go_seq = 0, seq_rec = 0; };
+// (resident: the frame's resident launch, launch_icp_resident -- it stays `waiting` from its launch to the end of the loop, slot / go_seq are
+// the line and the number of the NEXT word it will wait for)
+struct IcpWaiter { bool waiting = false; IcpGo* slot = nullptr; unsigned long long go_seq = 0, seq_rec = 0; bool resident = false, resident_counted = false; };
 // wait for mailbox record `seq` and copy it to h->h_icp_local (h_icp then points at that copy).  waiter: the launch made ahead, if one
 // is waiting.  Before the stream is drained it is told to leave (waiter->waiting = false: the next iteration, if any, is launched
 // afresh): it would otherwise hold the stream until its own bound expires.
@@ -1062,6 +1064,45 @@ static int icp_launch_waiting(ssf_handle* h, IcpWaiter& w) {
     w.waiting = rc == SSF_OK;
     return rc;
 }
+// ---- the resident launch: one per frame, an iteration is one word -----------------------------------------------------------------
+// When a frame takes it: a single shard alone, rows streamed from the visible array (no tile-sorted copy), the product's kernel, and
+// few enough visible rows that every workgroup of the launch holds a place at once (resident_max_rows: 256 x icp_resident_max_wgs()
+// = 1024 workgroups of the 1792 places the kernel's registers leave on the part, 7 per compute unit -- a safety condition, not a
+// tuning knob.  It assumes ONE handle tracking on the GPU: resident grids of several handles or processes add up, and past 1792
+// places each waits for workgroups that cannot get one until the bounded waits end the launches in SSF_ERR_DEVICE.  Callers that
+// share a GPU among handles with large maps lower the limit, ssf_debug_set_resident_icp_max_rows).
+// Not with the depth pre-filter in the frame (cfg.depth_prefilter): that pipeline is bound by its extract stage, not by this
+// chain, and the workgroups that stay slow the relabelling launches beside them (k_update_pass 12.8 -> 13.6 us per launch in
+// the kernel traces) -- with the pre-filter in the frame the resident launch ran 3.3 % SLOWER, the same build with the limit at 0 as fast
+// as before (profiles/icp_resident.txt).  Everything else takes the launches above.
+static bool icp_resident_ok(const ssf_handle* h) {
+    return h->go_res && single_shard_alone(h) && !h->bins.valid && !h->cfg.depth_prefilter && icp_variant_mode() == 0 && h->n_visible > 0 &&
+           h->n_visible <= h->resident_max_rows;
+}
+// T0: the first iteration's transform, record seq0 (nullptr: the first record came from the row-move kernel, the launch starts at word 1)
+static int icp_launch_resident(ssf_handle* h, IcpWaiter& w, const Rt* T0, unsigned long long seq0) {
+    const int last = h->cfg.icp_iter;             // words 1 .. last: at most icp_iter - 1 iterations and the word that ends the launch
+    IcpGo* lines = h->go_res + (size_t)(h->n_resident_launches++ & 1) * (size_t)(last + 1);
+    const unsigned long long go_base = h->go_count;
+    h->go_count += (unsigned long long)last;
+    w.resident = true; w.slot = lines + 1; w.go_seq = go_base + 1;
+    h->wait_launched_us = now_us();               // (before the launch call: no workgroup of it can have started waiting earlier)
+    const MatchArgs ma{h->cfg.range_min, h->cfg.range_max, h->id_offset, h->cc->d_best, h->cc->d_matched, h->d_cand};
+    launch_icp_resident(h->stream, h->cam, h->model[h->mcur], h->n_visible, h->cc->maps.pix2, h->cc->maps.fpack, T0, h->d_icp_replicas, h->d_icp, h->mb_dev,
+                        seq0, lines, (unsigned int)go_base, last, icp_waiter_can_match(h) ? &ma : nullptr);
+    HCK(hipGetLastError());
+    w.waiting = true;
+    if (!w.resident_counted) { w.resident_counted = true; h->n_resident_frames++; if (!T0) h->n_resident_ahead_frames++; }    // (per frame, not per launch: icp_fetch may have dismissed one)
+    return SSF_OK;
+}
+// the next iteration of the resident launch: ONE store of the word (transform, number, record number), no launch call.  A workgroup
+// can start waiting for the word behind this one only once this one is stored: the clock of the host's repair rule (icp_loop_end)
+// restarts here.
+static void icp_resident_iterate(ssf_handle* h, IcpWaiter& w, const Rt& T, unsigned long long seq_rec) {
+    h->wait_launched_us = now_us();
+    icp_release_waiting(w.slot, w.go_seq, &T, seq_rec);
+    w.slot++; w.go_seq++;
+}
 // A chained launch that never got its word (host stalled past the kernel's bound, or the record never arrived) may
 // have left the arrival counters / replica records of the ICP reduction half filled: drain the stream, put them back
 // to rest and stop chaining launches on this handle.
@@ -1103,13 +1144,18 @@ static inline bool icp_chains(const ssf_handle* h) { return h->icp_chain && h->g
 static int icp_loop_chained(ssf_handle* h, TrackFrame& f) {
     IcpWaiter& w = f.w;
     int again = h->icp.active ? 1 : 0, rc;
+    const bool resident = again && icp_resident_ok(h);
     while (again) {
         unsigned long long seq_rec;
         if (h->icp.ahead_seq) { seq_rec = h->icp.ahead_seq; h->icp.ahead_seq = 0; }     // iteration 1 came from the move kernel
         else {
             const Rt T = icp_transform(h->icp);
             const unsigned long long xseq = h->p2p.on ? ++h->p2p.seq_icp : 0;             // (the number of this iteration's peer exchange)
-            if (w.waiting) { icp_release_waiting(w.slot, w.go_seq, &T, xseq); seq_rec = w.seq_rec; w.waiting = false; }   // already on the device
+            if (resident) {                            // one launch for the frame: up already -> one store; else it starts with this iteration
+                seq_rec = ++h->icp_seq;
+                if (w.waiting) icp_resident_iterate(h, w, T, seq_rec);
+                else { rc = icp_launch_resident(h, w, &T, seq_rec); if (rc) return rc; }
+            } else if (w.waiting) { icp_release_waiting(w.slot, w.go_seq, &T, xseq); seq_rec = w.seq_rec; w.waiting = false; }   // already on the device
             else {
                 const P2PView pv = p2p_view(h, xseq);
                 seq_rec = ++h->icp_seq;
@@ -1121,7 +1167,9 @@ static int icp_loop_chained(ssf_handle* h, TrackFrame& f) {
         // iteration the loop allows, a launch that can only be told to do the association: a loop that ends at the cap
         // (BASELINE config 3: ten forced iterations) then starts its association ~1 us after the host's last step instead of
         // a launch latency later (11-13 us between the tenth k_icp and k_match in the round-4 traces), like one that converges
-        if (h->icp.iter + 1 < h->cfg.icp_iter || (!f.timing && icp_waiter_can_match(h))) {
+        // (the resident launch is up from the first iteration on: behind a first record that came from the move kernel it starts here)
+        if (resident) { if (!w.waiting) { rc = icp_launch_resident(h, w, nullptr, 0); if (rc) return rc; } }
+        else if (h->icp.iter + 1 < h->cfg.icp_iter || (!f.timing && icp_waiter_can_match(h))) {
             rc = icp_launch_waiting(h, w);
             if (rc) return rc;
         }
@@ -1582,9 +1630,12 @@ int ssf_create(const ssf_config* cfg, ssf_handle** out) {
         void* q = nullptr;
         int large_bar = 0;
         (void)hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, cfg->device_id);
-        if (large_bar && hipExtMallocWithFlags(&q, SSF_ICP_GO_SLOTS * sizeof(IcpGo), hipDeviceMallocFinegrained) == hipSuccess) {
+        // (behind the SSF_ICP_GO_SLOTS lines of the launches made ahead: the resident launch's, two sets of icp_iter + 1 -- ssf_handle.hpp)
+        const size_t n_res = cfg->icp_iter > 0 && cfg->icp_iter < 4096 ? 2 * ((size_t)cfg->icp_iter + 1) : 0;
+        if (large_bar && hipExtMallocWithFlags(&q, (SSF_ICP_GO_SLOTS + n_res) * sizeof(IcpGo), hipDeviceMallocFinegrained) == hipSuccess) {
             h->allocs.push_back(q); h->go = (IcpGo*)q;
-            (void)hipMemset(q, 0, SSF_ICP_GO_SLOTS * sizeof(IcpGo));
+            (void)hipMemset(q, 0, (SSF_ICP_GO_SLOTS + n_res) * sizeof(IcpGo));
+            if (n_res) { h->go_res = h->go + SSF_ICP_GO_SLOTS; h->resident_max_rows = 256 * icp_resident_max_wgs(); }
         } else { (void)hipGetLastError(); h->go = nullptr; }
     }
     ok = ok && alloc_surfels(h, h->model[0], N) && alloc_surfels(h, h->model[1], N) && alloc_surfels(h, h->dense, N) &&
@@ -1873,6 +1924,13 @@ int ssf_debug_set_max_passes(ssf_handle* h, int n) { if (!h) return SSF_ERR_INVA
 int ssf_debug_set_bin_min_rows(ssf_handle* h, int n) {
     if (!h) return SSF_ERR_INVALID_ARG;
     h->bins.min_rows = bin_buffer_words(h->cam, 1) == 0 ? -1 : n;
+    return SSF_OK;
+}
+// visible rows up to which a frame's ICP loop and association run in ONE resident launch (default and ceiling: 262 144, every
+// workgroup of it must hold a place at once; 0: never)
+int ssf_debug_set_resident_icp_max_rows(ssf_handle* h, int n) {
+    if (!h) return SSF_ERR_INVALID_ARG;
+    h->resident_max_rows = h->go_res ? std::max(0, std::min(n, 256 * icp_resident_max_wgs())) : 0;
     return SSF_OK;
 }
 int ssf_stage_set_shard(ssf_handle* h, int64_t off, int64_t gm, int64_t gv) {
@@ -2195,6 +2253,10 @@ int ssf_sequence_marks(ssf_handle* h, double* out320) {
 }
 // frames whose association ran inside a waiting ICP launch (SSF_ICP_GO_MATCH) since the handle was created
 long long ssf_waiter_matches(ssf_handle* h) { return h ? h->n_waiter_matches : -1; }
+// frames whose ICP iterations ran in one resident launch (launch_icp_resident)
+long long ssf_resident_icp_frames(ssf_handle* h) { return h ? h->n_resident_frames : -1; }
+// ... and those of them whose launch started at its second word: the first record had been made by the frame before (k_move_rows<true>)
+long long ssf_resident_icp_ahead_frames(ssf_handle* h) { return h ? h->n_resident_ahead_frames : -1; }
 // the self-tuned choice of AheadTuner: [0] form in effect (1: first ICP iteration inside the row-move kernel), [1] pipelined frames
 // seen, [2] / [3] mean chain period per unit of work measured in the last probe without / with the fusion (0: not probed yet)
 int ssf_tuner_state(ssf_handle* h, double* out4) {

@@ -321,8 +321,10 @@ __device__ __forceinline__ void icp_fold_counted(const unsigned long long* red, 
         (void)__hip_atomic_fetch_add(&rep[threadIdx.x], ((unsigned long long)v << ICP_CNT_BITS) + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-__device__ __forceinline__ void icp_collect_counted(unsigned long long* __restrict__ counted, long long* __restrict__ sums, Mailbox* mb,
-                                                    unsigned long long seq, unsigned int n_wg) {
+// (returns false when the wait ran out: nothing was published; tid: threadIdx.x -- an argument so that a caller inside a loop can keep
+// the per-thread tables below from being hoisted out of it and held in registers by every workgroup for the whole launch)
+__device__ __forceinline__ bool icp_collect_counted(unsigned long long* __restrict__ counted, long long* __restrict__ sums, Mailbox* mb,
+                                                    unsigned long long seq, unsigned int n_wg, const unsigned int tid) {
     __shared__ long long part[SSF_ICP_REPLICAS * 32];
     __shared__ int s_expired;
     // word w = 256 j + thread of the SSF_ICP_REPLICAS x 30 counted words: replica w / 30, word w % 30
@@ -331,14 +333,14 @@ __device__ __forceinline__ void icp_collect_counted(unsigned long long* __restri
     int wr[WPT], wk[WPT]; bool mine[WPT]; unsigned int expect[WPT]; unsigned long long acc[WPT];
 #pragma unroll
     for (int j = 0; j < WPT; j++) {
-        const int w = 256 * j + (int)threadIdx.x;
+        const int w = 256 * j + (int)tid;
         wr[j] = w / ICP_CNT_WORDS; wk[j] = w - wr[j] * ICP_CNT_WORDS;
         mine[j] = w < NW;
         // workgroups b with b % SSF_ICP_REPLICAS == replica
         expect[j] = mine[j] ? (n_wg + SSF_ICP_REPLICAS - 1u - (unsigned int)wr[j]) / SSF_ICP_REPLICAS : 0u;
         acc[j] = 0ull;
     }
-    if (threadIdx.x == 0) s_expired = 0;
+    if (tid == 0) s_expired = 0;
     __syncthreads();
     const unsigned long long t0 = wall_clock64();
     for (unsigned int round = 0;; round++) {
@@ -355,34 +357,35 @@ __device__ __forceinline__ void icp_collect_counted(unsigned long long* __restri
             done = done && (!mine[j] || (unsigned int)(acc[j] & CNT_MASK) == expect[j]);
         }
         if (__syncthreads_and(done ? 1 : 0)) break;
-        if (threadIdx.x == 0 && (round & 15u) == 15u && wall_clock64() - t0 > SSF_ICP_COLLECT_WAIT_TICKS) s_expired = 1;
+        if (tid == 0 && (round & 15u) == 15u && wall_clock64() - t0 > SSF_ICP_COLLECT_WAIT_TICKS) s_expired = 1;
         __syncthreads();
-        if (s_expired) return;                   // (no record: the host's own bounded wait reports it and puts the buffers back to rest)
+        if (s_expired) return false;             // (no record: the host's own bounded wait reports it and puts the buffers back to rest)
         __builtin_amdgcn_s_sleep(1);
     }
 #pragma unroll
     for (int j = 0; j < WPT; j++)
         if (mine[j]) part[wr[j] * 32 + wk[j]] = (long long)(acc[j] - (acc[j] & CNT_MASK)) >> ICP_CNT_BITS;
     __syncthreads();
-    if (threadIdx.x < 64) {
+    if (tid < 64) {
         __shared__ unsigned long long pay[30];
         long long tot = 0;
-        if (threadIdx.x < ICP_CNT_WORDS)
-            for (int q = 0; q < SSF_ICP_REPLICAS; q++) tot += part[q * 32 + threadIdx.x];
+        if (tid < ICP_CNT_WORDS)
+            for (int q = 0; q < SSF_ICP_REPLICAS; q++) tot += part[q * 32 + tid];
         // term 27 = (word 29 << 40) + word 27
         const long long hi27 = (long long)shfl_u64((unsigned long long)tot, 29);
-        if (threadIdx.x == 27) tot = (long long)(((unsigned long long)hi27 << 40) + (unsigned long long)tot);
-        if (threadIdx.x >= 29) tot = 0;
-        if (threadIdx.x < 29) {
-            sums[threadIdx.x] = tot;
-            pay[threadIdx.x] = (unsigned long long)tot;
+        if (tid == 27) tot = (long long)(((unsigned long long)hi27 << 40) + (unsigned long long)tot);
+        if (tid >= 29) tot = 0;
+        if (tid < 29) {
+            sums[tid] = tot;
+            pay[tid] = (unsigned long long)tot;
         }
         const unsigned long long check = (unsigned long long)wsum64(tot) + seq;
-        if (threadIdx.x == 0) pay[29] = check;
+        if (tid == 0) pay[29] = check;
         __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0): the LDS writes have landed
-        if (threadIdx.x < 40)
-            __hip_atomic_store(&mb->icp_rec[threadIdx.x], SSF_ICP_REC_WORD(threadIdx.x, pay, seq), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (tid < 40)
+            __hip_atomic_store(&mb->icp_rec[tid], SSF_ICP_REC_WORD(tid, pay, seq), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+    return true;
 }
 // ---- rows in image-tile order (ssf_tile_rows.inc, further down): helpers of the launches that stream the tile-sorted copy ------------
 // Rows sorted by image tile (k_bin_* below) are handed to the launch's workgroups so that ONE XCD works on one contiguous
@@ -451,6 +454,46 @@ __device__ __forceinline__ void match_sorted_rows(const Cam& cam, const SurfelSo
 #ifndef SSF_ICP_NUM_SGPR
 #define SSF_ICP_NUM_SGPR 80
 #endif
+// Wave 0 of a workgroup (all 64 lanes) waits for the host's word `want` in the line `go`: 0 = leave (told to, or gave up), 1 = iterate,
+// 2 = associate (SSF_ICP_GO_MATCH).  w: this lane's dword of the line as it was when the word was accepted (lanes 0-11 the transform,
+// 14-15 IcpGo::x; lanes >= 16: 0).
+__device__ __forceinline__ int icp_wait_word(IcpGo* go, unsigned int want, unsigned int& w) {
+    int ok = 0, told = 0;
+    const unsigned int l = threadIdx.x;
+    const unsigned int* gw = reinterpret_cast<const unsigned int*>(go);
+    const unsigned int weight = icp_go_word_weight(l);
+    w = 0u;
+    // (the bound is WALL-CLOCK time -- the constant-rate counter behind wall_clock64(), 100 MHz on this part --, looked
+    // at every 64 polls: a quarter of a second, not a spin count whose length in seconds depends on how long a poll
+    // of fine-grained memory takes under load.  The host's own round trip is 3-5 us.)
+    const unsigned long long t0 = wall_clock64();
+    for (unsigned int spin = 0; spin < (1u << 24); spin++) {
+        w = l < 16u ? __hip_atomic_load(&gw[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
+        const unsigned int flo = (unsigned int)__builtin_amdgcn_readlane((int)w, 12), fhi = (unsigned int)__builtin_amdgcn_readlane((int)w, 13);
+        if (flo == want) {
+            if (fhi & 0x80000000u) {                                                     // SSF_ICP_GO_ABORT, valid only with this go_seq's hash beside it
+                if ((fhi & SSF_ICP_GO_CHECK_MASK) == icp_go_abort_check(want)) { told = 1; break; }      // (else: a stale high half -- keep polling)
+            } else {
+                unsigned int sum = w * weight;                                           // (lanes >= 16: 0)
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, 64);
+                sum = (unsigned int)__builtin_amdgcn_readfirstlane((int)sum);
+                if (((sum >> 2) & SSF_ICP_GO_CHECK_MASK) == (fhi & SSF_ICP_GO_CHECK_MASK)) {
+                    ok = (fhi & 0x40000000u) ? 2 : 1; told = 1;                          // SSF_ICP_GO_MATCH: the loop is over, associate under the pose in the line
+                    break;
+                }
+            }
+        }
+        if ((spin & 63u) == 63u && wall_clock64() - t0 > SSF_ICP_GO_WAIT_TICKS) break;
+        __builtin_amdgcn_s_sleep(1);
+    }
+    // gave up waiting (the host stalled for seconds): make that the decision of the whole launch -- workgroups
+    // dispatched later must not find a word that arrives after all and start accumulating into a record nobody
+    // completes.  (Only then: the normal "leave" word is the host's, and hundreds of workgroups echoing it
+    // through the BAR cost the launch behind this one 3 us per frame.)
+    if (!told && l == 0u) __hip_atomic_store(&go->flag, (unsigned long long)want | ((unsigned long long)icp_go_abort_check(want) << 32) | SSF_ICP_GO_ABORT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return ok;
+}
 template <bool P2P, int MODE>          // MODE 0: rows from the visible array; 3: rows from the tile-sorted copy (by_tile launches, large visible sets); lab: 1 = rows' terms summed in registers (SSF_ICP_PER_LANE), 2 = DPP row reduction (SSF_ICP_WRED)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(SSF_ICP_NUM_SGPR))) void k_icp(Cam cam, SurfelSoA model, int n_visible,
                                              const uint2* __restrict__ pix2, const float4* __restrict__ fpack,
@@ -477,40 +520,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(SSF_ICP_NUM_SGP
         // the polling lane read the transform word by word -- twelve dependent trips to fine-grained memory at the head of every
         // chained iteration --, then twelve lanes fetched it in one trip behind the flag; now it needs no trip of its own.)
         if (threadIdx.x < 64) {
-            int ok = 0, told = 0;
-            const unsigned int l = threadIdx.x, want = (unsigned int)go_seq;
-            const unsigned int* gw = reinterpret_cast<const unsigned int*>(go);
-            const unsigned int weight = icp_go_word_weight(l);
-            unsigned int w = 0u;
-            // (the bound is WALL-CLOCK time -- the constant-rate counter behind wall_clock64(), 100 MHz on this part --, looked
-            // at every 64 polls: a quarter of a second, not a spin count whose length in seconds depends on how long a poll
-            // of fine-grained memory takes under load.  The host's own round trip is 3-5 us.)
-            const unsigned long long t0 = wall_clock64();
-            for (unsigned int spin = 0; spin < (1u << 24); spin++) {
-                w = l < 16u ? __hip_atomic_load(&gw[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
-                const unsigned int flo = (unsigned int)__builtin_amdgcn_readlane((int)w, 12), fhi = (unsigned int)__builtin_amdgcn_readlane((int)w, 13);
-                if (flo == want) {
-                    if (fhi & 0x80000000u) {                                                     // SSF_ICP_GO_ABORT, valid only with this go_seq's hash beside it
-                        if ((fhi & SSF_ICP_GO_CHECK_MASK) == icp_go_abort_check(want)) { told = 1; break; }      // (else: a stale high half -- keep polling)
-                    } else {
-                        unsigned int sum = w * weight;                                           // (lanes >= 16: 0)
-#pragma unroll
-                        for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, 64);
-                        sum = (unsigned int)__builtin_amdgcn_readfirstlane((int)sum);
-                        if (((sum >> 2) & SSF_ICP_GO_CHECK_MASK) == (fhi & SSF_ICP_GO_CHECK_MASK)) {
-                            ok = (fhi & 0x40000000u) ? 2 : 1; told = 1;                          // SSF_ICP_GO_MATCH: the loop is over, associate under the pose in the line
-                            break;
-                        }
-                    }
-                }
-                if ((spin & 63u) == 63u && wall_clock64() - t0 > SSF_ICP_GO_WAIT_TICKS) break;
-                __builtin_amdgcn_s_sleep(1);
-            }
-            // gave up waiting (the host stalled for seconds): make that the decision of the whole launch -- workgroups
-            // dispatched later must not find a word that arrives after all and start accumulating into a record nobody
-            // completes.  (Only then: the normal "leave" word is the host's, and hundreds of workgroups echoing it
-            // through the BAR cost the launch behind this one 3 us per frame.)
-            if (!told && l == 0u) __hip_atomic_store(&go->flag, (unsigned long long)want | ((unsigned long long)icp_go_abort_check(want) << 32) | SSF_ICP_GO_ABORT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            const unsigned int l = threadIdx.x;
+            unsigned int w;
+            const int ok = icp_wait_word(go, (unsigned int)go_seq, w);
             if (ok) {
                 if (l < 12u) s_T[l] = __uint_as_float(w);
                 // (a launch made ahead learns the number of its peer exchange with its transform: a dismissed launch must
@@ -584,7 +596,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(SSF_ICP_NUM_SGP
         if (dbg & SSF_ICP_DBG_COUNTED) {            // the counted record (second half of the replica buffer): see icp_fold_counted
             unsigned long long* counted = reinterpret_cast<unsigned long long*>(replicas) + SSF_ICP_REPLICAS * 32;
             icp_fold_counted(red, counted);
-            if (blockIdx.x == n_wg - 1) icp_collect_counted(counted, sums, mb, seq, n_wg);
+            if (blockIdx.x == n_wg - 1) icp_collect_counted(counted, sums, mb, seq, n_wg, threadIdx.x);
             return;
         }
     }
@@ -592,6 +604,99 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(SSF_ICP_NUM_SGP
     if (threadIdx.x == 0) s_last = grid_arrive(ticket);
     __syncthreads();
     if (s_last) icp_publish<P2P>(replicas, sums, mb, seq, pv, p2p_seq);
+}
+
+// ---- the resident form: ONE launch for a frame's iterations and its association -------------------------------------------------
+// Across the iterations of a frame, and its association, the rows do not change: only the transform does.  Here every lane loads
+// its row ONCE (position, Lab, normal row, confidence: one row per lane, the grid is ceil(n_visible / 256) workgroups) and the
+// workgroups stay: iteration by iteration they wait for the host's word, accumulate the 29 terms from registers, fold them into
+// the counted record, and the last workgroup of the grid collects and publishes it under the sequence number the word carried
+// (IcpGo::x).  The words of a frame persist, one line per iteration index (go[idx], number go_base + idx): a workgroup that got its
+// place late finds every word it has missed -- at most one in practice, the host sends word i + 1 only behind record i, and record
+// i needs every workgroup's terms.  That also keeps the iterations apart in the counted record: no term of iteration i + 1 can
+// be added before the collector has taken the last of iteration i out.  A word with SSF_ICP_GO_MATCH carries the frame's final
+// pose: the association (k_match's arithmetic, from the same registers) and the end of the launch; "leave" ends it too.
+// have_first: iteration 0 runs at once under the argument T and publishes record `seq` (otherwise the frame's first record came
+// from the previous frame's row-move kernel and the launch starts at word 1).  Arithmetic, record and words are k_icp's: exact
+// integer sums, the results are the same bit for bit.
+// Every wait is bounded by wall-clock time (icp_wait_word, icp_collect_counted); a workgroup that gives up posts "leave" for the
+// index it was waiting at -- the collector for the next one --, so the whole launch ends and the host's own wait reports it.
+// The only wait on another workgroup is the collector's, so all workgroups must be able to hold a place at once: the host
+// launches at most 1024 of them (launch_icp_resident) where the kernel's registers leave 7 per compute unit, 1792 on the part
+// (tests/test_kernel_resources.py holds the register figures to that).
+__global__ __launch_bounds__(256, 7) __attribute__((amdgpu_num_sgpr(SSF_ICP_NUM_SGPR))) void k_icp_resident(Cam cam, SurfelSoA model, int n_visible,
+                                             const uint2* __restrict__ pix2, const float4* __restrict__ fpack,
+                                             Rt T, unsigned long long* __restrict__ counted, long long* __restrict__ sums, Mailbox* mb,
+                                             unsigned long long seq, IcpGo* go, unsigned int go_base, int have_first, int last_idx,
+                                             MatchArgs ma) {
+    __builtin_amdgcn_s_setprio(3);            // the track chain is the critical path (k_icp)
+    unsigned int n_wg = gridDim.x;
+    asm volatile("" : "+s"(n_visible), "+s"(n_wg), "+s"(last_idx), "+s"(go_base));          // (fetched now, not behind a wait: see k_icp)
+    __shared__ unsigned long long red[29 * ICP_SLOTS];
+    __shared__ float s_T[12];
+    __shared__ int s_go;
+    __shared__ unsigned long long s_seq;
+    const int id = (int)(blockIdx.x * 256u + threadIdx.x);
+    const bool live = id < n_visible;
+    // the row, once, in one round trip
+    float m_conf = 0.0f;
+    V3 mpos = v3(0, 0, 0), mlab = v3(0, 0, 0), mnrm = v3(0, 0, 0);
+    if (live) { m_conf = model.conf[id]; mpos = ld3(model.pos, id); mlab = ld3(model.lab, id); mnrm = ld3(model.r2, id); }
+    asm volatile("" : "+v"(m_conf), "+v"(mpos.x), "+v"(mlab.x), "+v"(mnrm.x));
+    const int slot = lane() & (ICP_SLOTS - 1);
+    // (the transform and the record's number of EVERY round come from LDS, the first round's put there now: carried through the loop
+    // in registers, the argument's twelve words and the next round's twelve are live side by side)
+    if (threadIdx.x == 0) {
+        const float t12[12] = {T.R.r0.x, T.R.r0.y, T.R.r0.z, T.R.r1.x, T.R.r1.y, T.R.r1.z, T.R.r2.x, T.R.r2.y, T.R.r2.z, T.t.x, T.t.y, T.t.z};
+#pragma unroll
+        for (int i = 0; i < 12; i++) s_T[i] = t12[i];
+        s_seq = seq; s_go = 1;
+    }
+    for (int idx = have_first ? 0 : 1; idx <= last_idx; idx++) {
+        // (Every round starts from the row and the camera as they stand in their registers: left alone, the compiler lifts whatever
+        // of a round depends on them alone out of the loop -- vector copies of the scalars, products, addresses -- and keeps it
+        // in registers for the whole launch)
+        asm volatile("" : "+v"(m_conf), "+v"(mpos.x), "+v"(mpos.y), "+v"(mpos.z), "+v"(mlab.x), "+v"(mlab.y), "+v"(mlab.z), "+v"(mnrm.x), "+v"(mnrm.y), "+v"(mnrm.z));
+        asm volatile("" : "+s"(cam.fx), "+s"(cam.fy), "+s"(cam.cx), "+s"(cam.cy), "+s"(cam.W), "+s"(cam.H));
+        for (int i = threadIdx.x; i < 29 * ICP_SLOTS; i += 256) red[i] = 0ull;
+        if (idx > 0 && threadIdx.x < 64) {
+            const unsigned int l = threadIdx.x;
+            unsigned int w;
+            const int ok = icp_wait_word(go + idx, go_base + (unsigned int)idx, w);
+            if (ok) {
+                if (l < 12u) s_T[l] = __uint_as_float(w);
+                const unsigned int xlo = (unsigned int)__builtin_amdgcn_readlane((int)w, 14), xhi = (unsigned int)__builtin_amdgcn_readlane((int)w, 15);
+                if (l == 0u) s_seq = ((unsigned long long)xhi << 32) | xlo;
+            }
+            if (l == 0u) s_go = ok;
+        }
+        __syncthreads();
+        if (!s_go) return;
+        if (s_go == 2) {
+            // findBestMatches on the way out (the pose is uniform, and said so: see k_icp)
+            auto sT = [&](int i) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_T[i]))); };
+            Rt P; P.R = m3(v3(sT(0), sT(1), sT(2)), v3(sT(3), sT(4), sT(5)), v3(sT(6), sT(7), sT(8)));
+            P.t = v3(sT(9), sT(10), sT(11));
+            if (ma.best && live) ma.cand[id] = match_values(cam, m_conf, mpos, mnrm, mlab, id, pix2, fpack, P, ma.zmin, ma.zmax, ma.id_offset, ma.best, ma.matched, false);
+            return;
+        }
+        T.R = m3(v3(s_T[0], s_T[1], s_T[2]), v3(s_T[3], s_T[4], s_T[5]), v3(s_T[6], s_T[7], s_T[8]));
+        T.t = v3(s_T[9], s_T[10], s_T[11]);
+        seq = s_seq;
+        if (live) icp_row(cam, pix2, fpack, T.R, T.t, mpos, mlab, mnrm, red, slot, 0);
+        __syncthreads();
+        icp_fold_counted(red, counted);
+        unsigned int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));         // (the collector's per-thread tables are made here, every round: see icp_collect_counted)
+        if (blockIdx.x == n_wg - 1 && !icp_collect_counted(counted, sums, mb, seq, n_wg, tid)) {
+            // the terms of some workgroup never came: nobody will be sent a further word -- tell the launch to leave
+            const unsigned int want = go_base + (unsigned int)idx + 1u;
+            if (threadIdx.x == 0 && idx < last_idx)
+                __hip_atomic_store(&go[idx + 1].flag, (unsigned long long)want | ((unsigned long long)icp_go_abort_check(want) << 32) | SSF_ICP_GO_ABORT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            return;
+        }
+        __syncthreads();                      // (the fold has read the table the next round clears)
+    }
 }
 
 // ---- loop-closure registration (DenseRegistration::align) -----------------------------------------------------
@@ -2061,6 +2166,19 @@ void launch_icp(hipStream_t st, const Cam& cam, SurfelSoA model, int n_visible, 
 #endif
     if (pv) hipLaunchKernelGGL((k_icp<true, 0>), dim3(grid), dim3(256), 0, st, cam, model, n_visible, pix2, fpack, T, replicas, ticket, sums29, mb, seq, dbg, go, go_seq, v, by_tile, ma);
     else hipLaunchKernelGGL((k_icp<false, 0>), dim3(grid), dim3(256), 0, st, cam, model, n_visible, pix2, fpack, T, replicas, ticket, sums29, mb, seq, dbg, go, go_seq, v, by_tile, ma);
+}
+// The resident form (k_icp_resident): one launch for the frame.  replicas: launch_icp's (the counted record is its second half);
+// go: the frame's lines, go[idx] for word go_base + idx, idx = 1 .. last_idx; T0 != nullptr: iteration 0 at once, record seq0.
+int icp_resident_max_wgs() { return 1024; }
+void launch_icp_resident(hipStream_t st, const Cam& cam, SurfelSoA model, int n_visible, const uint2* pix2, const float4* fpack, const Rt* T0,
+                         long long* replicas, long long* sums29, Mailbox* mb, unsigned long long seq0, IcpGo* go, unsigned int go_base,
+                         int last_idx, const MatchArgs* match) {
+    ScopedKernel sk("icp_resident", st);
+    const MatchArgs ma = match ? *match : MatchArgs{0.f, 0.f, 0, nullptr, nullptr, nullptr};
+    Rt none; none.R = m3_identity(); none.t = v3(0, 0, 0);
+    unsigned long long* counted = reinterpret_cast<unsigned long long*>(replicas) + SSF_ICP_REPLICAS * 32;
+    hipLaunchKernelGGL(k_icp_resident, dim3((n_visible + 255) / 256), dim3(256), 0, st, cam, model, n_visible, pix2, fpack, T0 ? *T0 : none, counted, sums29,
+                       mb, seq0, go, go_base, T0 ? 1 : 0, last_idx, ma);
 }
 void launch_match(hipStream_t st, const Cam& cam, SurfelSoA model, int n_visible, const uint2* pix2, const float4* fpack,
                   Rt pose, float zmin, float zmax, long long id_offset,
