@@ -14,6 +14,7 @@
 #define SSF_HPP
 #include <algorithm>
 #include <cmath>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -23,6 +24,7 @@
 #include "ssf_render.h"
 #include "ssf_query.h"
 #include "ssf_navgrid.h"
+#include "ssf_raycast.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
 #include "ssf_graph.h"
@@ -253,6 +255,25 @@ struct NavGrid {
     std::vector<int8_t> state;                     /* nav_msgs/OccupancyGrid's values: 100 occupied, 0 free, -1 unknown */
     std::vector<int32_t> dist2;                    /* squared distance in cells to the nearest obstacle cell, capped at max_dist_cells^2 */
     ssf_navgrid_stats stats;
+};
+
+/* castRays (ssf_raycast.h; exported by libssf_hip.so only): the first disc of the map that each ray hits.  The members start at
+ * ssf_raycast_default_params' values: pose nullptr = the tracked pose, t_min = t_max = 0 = the configured depth range, splat_scale
+ * 0 = 3, cell 0 = 0.125 m, hash_bits 0 = chosen by the library */
+struct RaycastParams {
+    const Transform3* pose = nullptr;              /* ray-frame-to-map */
+    float t_min = 0.f, t_max = 0.f, min_conf = 0.f, splat_scale = 0.f;
+    bool visible_only = false;
+    float cell = 0.f; int hash_bits = 0;
+    bool want_t = true, want_index = true, want_point = true, want_normal = true, want_color = true;   /* false: its vector stays empty */
+};
+/* per ray: t (a multiple of the direction; 0 on a miss), index into getModelHost() (-1 on a miss), hit point, normal facing the
+ * ray's origin and colour (all 0 on a miss), map frame */
+struct RaycastResult {
+    std::vector<float> t;
+    std::vector<int32_t> index;
+    std::vector<float3> point, normal, color;
+    ssf_raycast_stats stats;
 };
 
 /* the deformation graph's binding (ssf_graph.h): four node indices and four weights per row, in getModelHost()'s row order */
@@ -646,6 +667,63 @@ public:
         else if (m11 > m22) { const double s = 2.0 * std::sqrt(1.0 + m11 - m00 - m22); qw = (m02 - m20) / s; qx = (m01 + m10) / s; qy = 0.25 * s; qz = (m12 + m21) / s; }
         else { const double s = 2.0 * std::sqrt(1.0 + m22 - m00 - m11); qw = (m10 - m01) / s; qx = (m02 + m20) / s; qy = (m12 + m21) / s; qz = 0.25 * s; }
         msg.info.origin.orientation.x = qx; msg.info.origin.orientation.y = qy; msg.info.origin.orientation.z = qz; msg.info.origin.orientation.w = qw;
+    }
+    /* Rays cast through the map on the device (ssf_raycast.h): rays6 holds n rays of six floats (origin, direction) in the frame of
+     * r.pose.  The library keeps a spatial index of the map between calls and rebuilds it when the map has changed.  INTEGRATION.md
+     * section 2 has the uses (a simulated lidar scan, line of sight, picking). */
+    void castRays(const float* rays6, int n, const RaycastParams& r, RaycastResult& out) {
+        ssf_raycast_params p; float v[12];
+        check(ssf_raycast_default_params(need(), &p));
+        if (r.pose) { transform3_to_rt(*r.pose, v); p.pose = v; }
+        p.t_min = r.t_min; p.t_max = r.t_max; p.min_conf = r.min_conf; p.splat_scale = r.splat_scale;
+        p.visible_only = r.visible_only ? 1 : 0; p.on_device = 0; p.cell = r.cell; p.hash_bits = r.hash_bits;
+        const size_t m = n > 0 ? (size_t)n : 0;
+        out.t.resize(r.want_t ? m : 0); out.index.resize(r.want_index ? m : 0); out.point.resize(r.want_point ? m : 0);
+        out.normal.resize(r.want_normal ? m : 0); out.color.resize(r.want_color ? m : 0);
+        std::vector<float> pt(r.want_point ? 3 * m : 0), nr(r.want_normal ? 3 * m : 0), cl(r.want_color ? 3 * m : 0);
+        float dummy_t = 0.f;                           /* n == 0: the library still wants one output named */
+        check(ssf_raycast(need(), &p, rays6, n, m == 0 ? &dummy_t : (r.want_t ? out.t.data() : nullptr), r.want_index ? out.index.data() : nullptr,
+                          r.want_point ? pt.data() : nullptr, r.want_normal ? nr.data() : nullptr, r.want_color ? cl.data() : nullptr, &out.stats));
+        for (size_t i = 0; i < pt.size() / 3; i++) { out.point[i].x = pt[3 * i]; out.point[i].y = pt[3 * i + 1]; out.point[i].z = pt[3 * i + 2]; }
+        for (size_t i = 0; i < nr.size() / 3; i++) { out.normal[i].x = nr[3 * i]; out.normal[i].y = nr[3 * i + 1]; out.normal[i].z = nr[3 * i + 2]; }
+        for (size_t i = 0; i < cl.size() / 3; i++) { out.color[i].x = cl[3 * i]; out.color[i].y = cl[3 * i + 1]; out.color[i].z = cl[3 * i + 2]; }
+    }
+    void castRays(const std::vector<float>& rays6, const RaycastParams& r, RaycastResult& out) {
+        if (rays6.size() % 6 != 0) throw std::invalid_argument("castRays: rays6 holds six floats per ray");
+        castRays(rays6.data(), (int)(rays6.size() / 6), r, out);
+    }
+    /* the first hit of every ray only: t per ray, 0 on a miss */
+    std::vector<float> castRays(const std::vector<float>& rays6, const RaycastParams& r = RaycastParams()) {
+        RaycastParams q = r; q.want_index = q.want_point = q.want_normal = q.want_color = false; q.want_t = true;
+        RaycastResult out;
+        castRays(rays6, q, out);
+        return out.t;
+    }
+    /* A planar laser scan simulated from the map: n_beams unit rays in the x-y plane of `pose` (nullptr = the tracked pose; a node
+     * passes its laser frame), beam i at angle_min + i * angle_increment about z, angle_increment = (angle_max - angle_min) /
+     * (n_beams - 1).  Fills the members of a sensor_msgs::LaserScan that the scan determines: angle_min, angle_max, angle_increment,
+     * range_min, range_max, ranges (metres; +inf where nothing is hit within [range_min, range_max], as REP 117) and an empty
+     * intensities; time_increment and scan_time are set to 0, header is the node's.  Any message type with these members works. */
+    template <typename ScanT> void laserScan(const Transform3* pose, float angle_min, float angle_max, int n_beams, float range_min, float range_max,
+                                             ScanT& scan, const RaycastParams& r = RaycastParams()) {
+        if (n_beams < 1) throw std::invalid_argument("laserScan: n_beams < 1");
+        const float inc = n_beams > 1 ? (angle_max - angle_min) / (float)(n_beams - 1) : 0.f;
+        std::vector<float> rays(6 * (size_t)n_beams, 0.f);
+        for (int i = 0; i < n_beams; i++) {
+            const float a = angle_min + (float)i * inc;
+            rays[6 * (size_t)i + 3] = std::cos(a); rays[6 * (size_t)i + 4] = std::sin(a);
+        }
+        RaycastParams q = r;
+        q.pose = pose; q.t_min = range_min; q.t_max = range_max;
+        q.want_t = true; q.want_index = q.want_point = q.want_normal = q.want_color = false;
+        RaycastResult out;
+        castRays(rays, q, out);
+        scan.angle_min = angle_min; scan.angle_max = angle_max; scan.angle_increment = inc; scan.time_increment = 0.f; scan.scan_time = 0.f;
+        scan.range_min = range_min; scan.range_max = range_max;
+        scan.ranges.assign(out.t.begin(), out.t.end());
+        for (size_t i = 0; i < scan.ranges.size(); i++)
+            if (!(scan.ranges[i] > 0.f)) scan.ranges[i] = std::numeric_limits<float>::infinity();
+        scan.intensities.clear();
     }
     /* The deformation graph of a loop closure, built and kept on the device (ssf_graph.h; exported by libssf_hip.so only): every
      * stride-th confident row in birth order is a node, every row is bound to its four nearest nodes among the 2 * look born

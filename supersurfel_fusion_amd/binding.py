@@ -104,6 +104,12 @@ NAVGRID_SYMBOLS = ["ssf_navgrid_default_params", "ssf_navgrid_default_pose", "ss
 NAVGRID_OUTPUTS = (("zmin", np.float32, ()), ("zmax", np.float32, ()), ("hits", np.uint32, (2,)), ("state", np.int8, ()),
                    ("dist2", np.int32, ()))
 NAVGRID_OUTPUT_NAMES = tuple(nm for nm, _, _ in NAVGRID_OUTPUTS)
+# rays cast through the model (include/ssf_raycast.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
+RAYCAST_SYMBOLS = ["ssf_raycast_default_params", "ssf_raycast"]
+# the output arrays of ssf_raycast, in its argument order: name, dtype, per-ray shape
+RAYCAST_OUTPUTS = (("t", np.float32, ()), ("index", np.int32, ()), ("point", np.float32, (3,)), ("normal", np.float32, (3,)),
+                   ("color", np.float32, (3,)))
+RAYCAST_OUTPUT_NAMES = tuple(nm for nm, _, _ in RAYCAST_OUTPUTS)
 # the track stage's test hook and counter of the resident ICP launch (include/ssf_track.h): HIP product only, not part of ssf.h
 TRACK_SYMBOLS = ["ssf_debug_set_resident_icp_max_rows", "ssf_resident_icp_frames", "ssf_resident_icp_ahead_frames"]
 # the geometric moving-object detector (include/ssf_motion.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
@@ -221,6 +227,21 @@ class SsfNavGridStats(C.Structure):
         d = {nm: int(getattr(self, nm)) for nm, _ in self._fields_ if nm != "pose"}
         d["pose"] = np.array(self.pose[:], np.float32)
         return d
+
+
+class SsfRaycastParams(C.Structure):
+    """ssf_raycast_params (include/ssf_raycast.h)"""
+    _fields_ = [("pose", C.c_void_p), ("t_min", C.c_float), ("t_max", C.c_float), ("min_conf", C.c_float), ("splat_scale", C.c_float),
+                ("visible_only", C.c_int), ("on_device", C.c_int), ("cell", C.c_float), ("hash_bits", C.c_int)]
+
+
+class SsfRaycastStats(C.Structure):
+    """ssf_raycast_stats (include/ssf_raycast.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("rays", "rays_hit", "rays_invalid", "rows_indexed", "rows_oversize", "index_entries",
+                                           "cells_visited", "candidates_tested", "index_rebuilt")]
+
+    def as_dict(self):
+        return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
 
 
 class SsfGraphParams(C.Structure):
@@ -368,6 +389,10 @@ class Library:
             L.ssf_query_default_params.argtypes = [vp, C.POINTER(SsfQueryParams)]
             L.ssf_query_count.argtypes = [vp, C.POINTER(SsfQueryParams), C.POINTER(SsfQueryStats)]
             L.ssf_query_rows.argtypes = [vp, C.POINTER(SsfQueryParams), C.POINTER(SsfSurfels), vp, C.c_int, C.POINTER(SsfQueryStats)]
+        self.has_raycast = all(hasattr(L, nm) for nm in RAYCAST_SYMBOLS)
+        if self.has_raycast:
+            L.ssf_raycast_default_params.argtypes = [vp, C.POINTER(SsfRaycastParams)]
+            L.ssf_raycast.argtypes = [vp, C.POINTER(SsfRaycastParams), vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(SsfRaycastStats)]
         self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
         if self.has_navgrid:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
@@ -1102,6 +1127,73 @@ class Fusion:
         pose = np.zeros(12, np.float32)
         self._ck(self.L.lib.ssf_navgrid_default_pose(self.h, C.byref(p), _ptr(pose)), "ssf_navgrid_default_pose")
         return pose
+
+    # ---- rays cast through the model: the first disc each ray hits (include/ssf_raycast.h) ------------
+    def _need_raycast(self, symbol):
+        if not self.L.has_raycast:
+            raise SsfError("%s does not export %s: it casts no rays (include/ssf_raycast.h, HIP product only)" % (self.L.path, symbol))
+
+    def _raycast_params(self, on_device, pose=None, visible_only=False, **kw):
+        """(SsfRaycastParams, the pose array it points into).  pose: 12 floats or a 3 x 4 [R | t] ray-frame-to-map (None = the
+        handle's pose); the other keywords are fields of ssf_raycast_params (t_min, t_max, min_conf, splat_scale, cell,
+        hash_bits), each at ssf_raycast_default_params' value when missing."""
+        p = SsfRaycastParams()
+        self._ck(self.L.lib.ssf_raycast_default_params(self.h, C.byref(p)), "ssf_raycast_default_params")
+        keep = None
+        if pose is not None:
+            pose = np.asarray(pose, np.float32)
+            if pose.shape == (3, 4):
+                pose = np.concatenate([pose[:, :3].ravel(), pose[:, 3]])
+            if pose.size != 12:
+                raise SsfError("a ray pose is 12 floats (R row-major, then t) or 3 x 4 [R | t], got shape %s" % (pose.shape,))
+            keep = np.ascontiguousarray(pose.ravel(), np.float32)
+            p.pose = keep.ctypes.data
+        kinds = dict(p._fields_)
+        for nm, v in kw.items():
+            if nm not in kinds or nm in ("pose", "on_device", "visible_only"):
+                raise SsfError("unknown ray cast parameter %r" % nm)
+            setattr(p, nm, float(v) if kinds[nm] is C.c_float else int(v))
+        p.visible_only, p.on_device = int(bool(visible_only)), int(bool(on_device))
+        return p, keep
+
+    def _raycast(self, p, rays, n, ptrs):
+        st = SsfRaycastStats()
+        self._ck(self.L.lib.ssf_raycast(self.h, C.byref(p), rays, n, *([ptrs.get(nm) for nm in RAYCAST_OUTPUT_NAMES] + [C.byref(st)])),
+                 "ssf_raycast")
+        return st.as_dict()
+
+    def raycast(self, rays, outputs=RAYCAST_OUTPUT_NAMES, pose=None, **kw):
+        """The first disc of the model that each ray hits (ssf_raycast).  rays: n x 6 (origin, direction) in the pose's frame.
+        Returns a dict of the requested arrays (t n f32, index n i32, point / normal / color n x 3 f32; a miss: 0, -1, 0) and
+        'stats'.  Keywords: _raycast_params."""
+        self._need_raycast("ssf_raycast")
+        bad = [nm for nm in outputs if nm not in RAYCAST_OUTPUT_NAMES]
+        if bad:
+            raise SsfError("unknown ray cast outputs %s (known: %s)" % (bad, ", ".join(RAYCAST_OUTPUT_NAMES)))
+        rays = np.ascontiguousarray(rays, np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise SsfError("rays are n x 6 floats (origin, direction), got shape %s" % (rays.shape,))
+        n = len(rays)
+        p, keep = self._raycast_params(False, pose=pose, **kw)
+        out = {nm: np.empty((n,) + tail, dt) for nm, dt, tail in RAYCAST_OUTPUTS if nm in outputs}
+        stats = self._raycast(p, _ptr(rays) if n else None, n, {nm: _ptr(a) for nm, a in out.items()})
+        out["stats"] = stats
+        return out
+
+    def raycast_device(self, rays, n, t=None, index=None, point=None, normal=None, color=None, pose=None, **kw):
+        """ssf_raycast on device memory: rays and each output are a contiguous torch tensor on the device or the device address (int)
+        of a buffer of the shape and dtype raycast takes and returns (an output may be None).  Returns the stats dict."""
+        self._need_raycast("ssf_raycast")
+        p, keep = self._raycast_params(True, pose=pose, **kw)
+        addr = lambda a: None if a is None else C.c_void_p(int(a) if isinstance(a, int) else a.data_ptr())
+        return self._raycast(p, addr(rays), int(n), dict(t=addr(t), index=addr(index), point=addr(point), normal=addr(normal), color=addr(color)))
+
+    def raycast_default_params(self):
+        """ssf_raycast_default_params as a dict"""
+        self._need_raycast("ssf_raycast_default_params")
+        p = SsfRaycastParams()
+        self._ck(self.L.lib.ssf_raycast_default_params(self.h, C.byref(p)), "ssf_raycast_default_params")
+        return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm != "pose"}
 
     # ---- the deformation graph's nodes and per-row binding (include/ssf_graph.h) ------------------
     def _need_graph(self, symbol):

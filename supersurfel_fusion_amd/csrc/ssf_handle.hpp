@@ -268,6 +268,30 @@ struct NavGridWs {
     unsigned long long* stats = nullptr;
     unsigned char* img = nullptr; size_t img_bytes = 0;
 };
+// ssf_raycast (ssf_raycast.h): the resident index -- per slot the 64-byte record and the box of cells with the row's class, the
+// out-of-view blocks' live offsets, the oversize list; per bucket (+ 1) the list offsets and the fill's cursors; the (bucket -> slot)
+// lists; the sums and the box of indexed cells -- and the staging buffer of a call's host rays and outputs.  The index is valid
+// <=> built && gen == h->model_gen && recentres == h->n_recentres (a compaction moves rows to other slots) && (cell, s, hash_bits)
+// are the call's.  Allocated on first use; each group is grown as a whole or not at all (DevBufs::grow).  Nothing here is read or
+// written by the frame path.
+struct RayIndex {                                   // what the march needs of the index
+    float cell, s, k;
+    uint32_t mask;
+    int cmin[3], cmax[3];                           // the box of indexed cells (cmin > cmax: the grid is empty)
+    int n_over, nvs;                                // oversize list length; slots below nvs are visible rows
+    float cabs;                                     // the largest |coordinate| of the indexed cells' box, metres
+};
+struct RaycastWs {
+    DevBufs bufs;
+    float4* rec = nullptr; uint4* rbox = nullptr; uint32_t* bc = nullptr; uint32_t* over = nullptr; size_t slots = 0;
+    uint32_t* off = nullptr; uint32_t* cursor = nullptr; size_t buckets = 0;
+    uint32_t* list = nullptr; size_t list_cap = 0;
+    unsigned long long* stats = nullptr; int* cbox = nullptr;
+    unsigned char* io = nullptr; size_t io_bytes = 0;
+    RayIndex ix{};
+    bool built = false; unsigned long long gen = 0; long long recentres = 0; float cell = 0, s = 0; int hash_bits = 0;
+    long long rows_indexed = 0, rows_oversize = 0, entries = 0;
+};
 struct ssf_handle {
     ssf_config cfg;
     int S = 0, gx = 0, gy = 0;
@@ -370,7 +394,9 @@ struct ssf_handle {
     MotionWs motion;                              // ssf_motion_* (ssf_motion.h)
     OdoWs odo;                                    // ssf_odometry_* (ssf_odometry.h)
     NavGridWs navgrid;                            // ssf_navgrid_build (ssf_navgrid.h)
-    unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense)
+    RaycastWs raycast;                            // ssf_raycast (ssf_raycast.h)
+    unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense); the out-of-view
+                                                  // compaction keeps rows and order but moves slots: who keeps slot numbers also watches n_recentres (RaycastWs)
 };
 
 #define HCK(call)                                                                                    \

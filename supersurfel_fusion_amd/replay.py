@@ -234,9 +234,28 @@ def keyframe_line(fusion, stamp, rec):
     return " ".join(parts)
 
 
+def laser_scan_rays(beams):
+    """beams unit rays from the origin in the x-z plane of the camera frame (the plane of a level camera; y is down), beam i at
+    angle -pi + i * 2 pi / beams about -y from the viewing direction z: n x 6 f32"""
+    a = -np.pi + np.arange(int(beams)) * (2.0 * np.pi / int(beams))
+    rays = np.zeros((int(beams), 6), np.float32)
+    rays[:, 3], rays[:, 5] = np.sin(a), np.cos(a)
+    return rays
+
+
+def write_laser_scan(fusion, scan_dir, k, beams):
+    """a planar laser scan simulated from the map on the device (include/ssf_raycast.h): `beams` rays from the tracked pose over the
+    full circle in the camera's x-z plane (laser_scan_rays), within the configured depth range: scan_dir/<k as %06d>.npy, the
+    ranges in metres as f32, +inf where nothing is hit (REP 117)"""
+    t = fusion.raycast(laser_scan_rays(beams), outputs=("t",))["t"]
+    os.makedirs(scan_dir, exist_ok=True)
+    np.save(os.path.join(scan_dir, "%06d.npy" % k), np.where(t > 0, t, np.float32(np.inf)).astype(np.float32))
+
+
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
            keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30, detect_motion=False,
-           motion_mask_dir=None, odometry_prior=False, nav_grid_dir=None, nav_grid_every=30, nav_grid_res=0.05):
+           motion_mask_dir=None, odometry_prior=False, nav_grid_dir=None, nav_grid_every=30, nav_grid_res=0.05,
+           laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
@@ -248,6 +267,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     pose are written (write_local_cloud, numbered by frame); pipelined, submission pauses as for a render.
     nav_grid_dir: after frames 0, nav_grid_every, 2 nav_grid_every, ... the navigation grid of the map with cells of nav_grid_res
     metres is written (write_nav_grid, numbered by frame); pipelined, submission pauses as for a render.
+    laser_scan_dir: after frames 0, laser_scan_every, 2 laser_scan_every, ... a planar scan of laser_scan_beams beams from the tracked
+    pose is written (write_laser_scan, numbered by frame); pipelined, submission pauses as for a render.
     keyframes: a dict of ssf_keyframes_params fields ({} = the defaults): the keyframe database is configured and
     keyframes_consider runs after every frame (not pipelined: it needs no frame pending); keyframe_log: where keyframe_line's
     lines go (they are also kept in fusion.keyframe_lines).
@@ -280,9 +301,10 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     render_every = max(1, int(render_every))
     local_cloud_every = max(1, int(local_cloud_every))
     nav_grid_every = max(1, int(nav_grid_every))
+    laser_scan_every = max(1, int(laser_scan_every))
     # a frame after which the model is looked at (a render, a local cloud): nothing may be pending then
     looks = lambda k: bool((render_dir and k % render_every == 0) or (local_cloud_dir and k % local_cloud_every == 0) or
-                           (nav_grid_dir and k % nav_grid_every == 0))
+                           (nav_grid_dir and k % nav_grid_every == 0) or (laser_scan_dir and k % laser_scan_every == 0))
     mask_of = (lambda stamp, depth: read_pixel_mask(mask_dir, stamp, np.shape(depth))) if mask_dir else (lambda stamp, depth: None)
     if not pipelined:
         for stamp, rgb, depth in frames:
@@ -307,6 +329,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
                 write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res)
+            if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
+                write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     else:
         it, stamps, done = iter(frames), [], False
         held = []                                         # submitted host buffers stay alive until their frame is processed
@@ -337,6 +361,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
                 write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res)
+            if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
+                write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     if out_path:
         with open(out_path, "w") as f:
             f.write("\n".join(lines) + "\n")
@@ -467,6 +493,11 @@ def parse_args(argv=None):
                          "(map_server's convention), .yaml and _dist2.npy (squared clearance in cells)")
     ap.add_argument("--nav-grid-every", type=int, default=30, metavar="K")
     ap.add_argument("--nav-grid-res", type=float, default=0.05, metavar="R", help="metres per cell (default 0.05)")
+    ap.add_argument("--laser-scan-dir", default=None, metavar="DIR",
+                    help="every --laser-scan-every frames, a planar laser scan simulated from the map on the device, from the tracked pose: "
+                         "DIR/<frame number as %%06d>.npy (ranges in metres, +inf where nothing is hit)")
+    ap.add_argument("--laser-scan-every", type=int, default=30, metavar="K")
+    ap.add_argument("--laser-scan-beams", type=int, default=360, metavar="N", help="beams over the full circle (default 360)")
     ap.add_argument("--keyframes", action="store_true",
                     help="keep the fern-coded keyframe database: after every frame one line (stamp, stored id or -, min_diff_all, loop candidates "
                          "with their alignment verdict); not with --pipelined")
@@ -502,7 +533,8 @@ def main():
                         local_cloud_radius=a.local_cloud_radius, local_cloud_every=a.local_cloud_every, keyframes={} if a.keyframes else None,
                         keyframe_log=a.keyframe_log, detect_motion=a.detect_motion, motion_mask_dir=a.motion_mask_dir,
                         odometry_prior=a.odometry_prior, nav_grid_dir=a.nav_grid_dir, nav_grid_every=a.nav_grid_every,
-                        nav_grid_res=a.nav_grid_res)
+                        nav_grid_res=a.nav_grid_res, laser_scan_dir=a.laser_scan_dir, laser_scan_every=a.laser_scan_every,
+                        laser_scan_beams=a.laser_scan_beams)
     if a.keyframes and not a.keyframe_log:
         print("\n".join(f.keyframe_lines))
     print("%d frames -> %s ; %d supersurfels" % (len(lines), a.out, res[-1]["n_model"] if res else 0))
