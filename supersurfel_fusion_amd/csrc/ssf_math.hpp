@@ -128,7 +128,8 @@ SSF_HD uint64_t f64_to_bits(double d) { uint64_t b; memcpy(&b, &d, 8); return b;
 // operation; q + e c = x / 3 + e (c - 1/3) differs from the true quotient by less than 2^-53 ulp, while x / 3 cannot lie
 // closer than ulp / 6 to a midpoint between two doubles (x is an even multiple of ulp / 2, three times a midpoint an odd
 // one): the final rounding returns RN(x / 3).  For normal x away from the ends of the exponent range -- the specified
-// cube root works on [0.008, 1.2].  (tools/probe/div3_check.c: 1.5e9 values against the division, no difference.)
+// cube root works on [0.008, 1.2].  (tools/probe/div3_check.c: 1.5e9 values against the division, no difference; on the device:
+// tests/test_math_device_gpu.py::test_div3_exact_is_the_division, every binade from 2^-959 to 2^960.)
 // Twelve of these per pixel in k_render_moments, whose time is this conversion's double-precision arithmetic.
 SSF_HD double div3_exact(double x) {
     const double c = 0x1.5555555555555p-2;
@@ -137,7 +138,8 @@ SSF_HD double div3_exact(double x) {
 }
 // b / 3 for a 64-bit pattern from 32-bit pieces: two multiply-high and a handful of adds instead of the compiler's 64 x 64
 // multiply-high (four quarter-rate 64-bit multiply-adds).  hi = 3 qh + r, lo = 3 t + s, 2^32 = 3 * 0x55555555 + 1:
-// r 2^32 + lo = 3 (r * 0x55555555 + t) + (r + s).  (tools/probe/div3_check.c: 2e9 patterns.)
+// r 2^32 + lo = 3 (r * 0x55555555 + t) + (r + s).  (tools/probe/div3_check.c: 2e9 patterns; the device branch with its register
+// barrier: tests/test_math_device_gpu.py::test_div3_u64_is_the_division.)
 SSF_HD uint64_t div3_u64(uint64_t b) {
     const uint32_t hi = (uint32_t)(b >> 32), lo = (uint32_t)b;
     const uint32_t qh = (uint32_t)(((uint64_t)hi * 0xAAAAAAABull) >> 33), t = (uint32_t)(((uint64_t)lo * 0xAAAAAAABull) >> 33);
@@ -154,7 +156,10 @@ SSF_HD uint64_t div3_u64(uint64_t b) {
 // IEEE division the compiler emits for gfx950 is v_div_scale x 2, v_rcp_f64, two Newton steps on the reciprocal, the
 // quotient, one correction (v_div_fmas) and v_div_fixup; for such operands the scaling is the identity, v_div_fmas is a
 // plain fused multiply-add and the fix-up returns its input -- the eight operations below are the same operations on the
-// same values.  (Host code divides.)
+// same values.  (Host code divides.)  Pinned on the device by tests/test_math_device_gpu.py::test_div_inrange_is_the_division: 2^24
+// pairs of those ranges and 2^17 whose quotient lies 2^-54 ulp beside a rounding boundary (one Newton step fewer fails there
+// and nowhere else); outside the ranges -- zero, denormal, huge operands -- it is NOT the quotient, and no caller gets there
+// (lab_f / srgb_compress guard the cube root; test_outside_the_stated_domains).
 SSF_HD double div_inrange(double n, double d) {
 #if defined(__HIP_DEVICE_COMPILE__)
     double r = __builtin_amdgcn_rcp(d);
@@ -321,7 +326,8 @@ SSF_HD long long fx64(double v, double scale, double lim) {
     // magic-number addition -- t + 1.5 * 2^52 is rounded to an integer by the addition itself (default rounding mode) and lies
     // in the binade whose unit is 1, so the integer is the difference of the bit patterns; there is no hardware
     // double -> int64 conversion, the general sequence is ~8 double-precision instructions.  With a compile-time `lim`
-    // below 2^50 the general sequence is not even emitted.
+    // below 2^50 the general sequence is not even emitted.  (Each (scale, lim) pair a kernel passes, on every binade, at the rounding
+    // and clamp edges and against exact integer arithmetic: tests/test_math_device_gpu.py::test_fx64_pair.)
     const double t0 = v * scale;
     const double t = __builtin_fmin(__builtin_fmax(t0, -lim), lim);
     long long r;
@@ -338,7 +344,8 @@ SSF_HD long long fx64(double v, double scale, double lim) {
 #endif
 }
 // 32-bit fixed point of an already scaled value: round to nearest even, then convert SATURATING exactly as the hardware's
-// v_cvt_i32_f32 does (ISA manual; checked on the part by tools/probe/cvt_i32_f32.hip): NaN -> 0, t >= 2^31 -> INT_MAX,
+// v_cvt_i32_f32 does (ISA manual; checked on the part by tools/probe/cvt_i32_f32.hip and, on every binade, by
+// tests/test_math_device_gpu.py::test_f32_helpers_on_every_binade): NaN -> 0, t >= 2^31 -> INT_MAX,
 // t <= -2^31 -> INT_MIN, anything else is exact -- two instructions per term, no compare / select (27 terms per row in k_icp).
 // (Until round 3 the specification also sent 2^31 - 128, the largest float below 2^31, to INT_MAX: one compare and one
 // select per term for a value no term can take; oracle and product changed together.)

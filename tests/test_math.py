@@ -257,3 +257,150 @@ def test_principal_frame_bit_exact_against_the_references_text(which, oracle_lib
     generic = np.arange(len(V)) % 128 > 1
     assert np.abs(np.linalg.norm(V[generic][:, 0], axis=1) - 1).max() < 1e-5 and np.abs(np.linalg.norm(V[generic][:, 2], axis=1) - 1).max() < 1e-5
     assert (vals[generic][:, 0] >= vals[generic][:, 2]).all()
+
+
+# ---- the element-wise batch evaluators (csrc/probe/ssf_math_ops.h) ----------------------------------------------------------------
+# tests/test_math_device_gpu.py runs ssf_math.hpp on the DEVICE, element by element, against the oracle's batch entry
+# (oracle/oracle_mathbatch.cpp).  What can be checked without a GPU is checked here: the batch entry is the oracle's per-element
+# hooks, its fixed point is exact integer arithmetic, the probe library is built like the product and lists every operation, its
+# HOST branches equal the oracle too, and the product library gained nothing.
+import mathops as mo
+
+
+@pytest.fixture(scope="module")
+def orc_batch(oracle_lib):
+    fn = oracle_lib.lib.ssf_oracle_mathbatch
+    fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]; fn.restype = C.c_int
+    return fn
+
+
+@pytest.fixture(scope="module")
+def probe_lib():
+    return mo.load_probe()
+
+
+def _hook_inputs(rng, n):
+    """n seeded elements per operation that has an ssf_dbg_* hook: {name: (float32 / int32 array (n, in_words))}"""
+    M = rng.standard_normal((n, 3, 3)) * rng.uniform(1e-3, 1.0, (n, 1, 1))
+    Cm = M @ M.transpose(0, 2, 1) + np.eye(3) * 1e-7
+    cov = np.float32(np.stack([Cm[:, 0, 0], Cm[:, 0, 1], Cm[:, 0, 2], Cm[:, 1, 1], Cm[:, 1, 2], Cm[:, 2, 2]], 1))
+    cov[::7] *= np.float32(1e-3)                       # (both sides of sym_inverse's |det| > 1e-9 gate)
+    q = rng.standard_normal((n, 4)); q /= np.linalg.norm(q, axis=1, keepdims=True)
+    x, y, z, w = q.T
+    R = np.float32(np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z),
+                             2 * (y * z - w * x), 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], 1))
+    A = np.float32(rng.uniform(-2, 2, (n, 9))); v = np.float32(rng.uniform(-3, 3, (n, 3)))
+    labels = rng.integers(0, 3, (n, 9)).astype(np.int32)
+    return {
+        "rgb_to_lab": np.float32(rng.uniform(-5, 260, (n, 3))), "lab_to_rgb": np.float32(rng.uniform([0, -120, -120], [100, 120, 120], (n, 3))),
+        "sym_inverse": cov, "principal_frame": cov, "plane_solve": np.float32(rng.uniform(-50, 50, (n, 12))), "guard": labels,
+        "sym_square": cov, "sym_mul": np.hstack([cov, v]), "rot_sym": np.hstack([R, cov]), "m3_mul": np.hstack([R, A]),
+        "m3_mulv": np.hstack([A, v]), "row_mul": np.hstack([v, A]), "rot_to_quat": R, "quat_to_rot_quirk": np.float32(q),
+    }
+
+
+def _hook_result(L, name, row):
+    """one element through the library's per-element ssf_dbg_* hook, in the batch entry's output layout (uint32 words)"""
+    f32 = lambda k: np.zeros(k, np.float32)
+    def run(fn, *args):
+        getattr(L, fn).argtypes = [C.c_void_p] * len(args); getattr(L, fn).restype = C.c_int
+        return getattr(L, fn)(*[fptr(a) for a in args])
+    r = np.ascontiguousarray(row)
+    if name in ("rgb_to_lab", "lab_to_rgb", "sym_square", "rot_to_quat"):
+        o = f32({"sym_square": 6, "rot_to_quat": 4}.get(name, 3)); run("ssf_dbg_" + name, r, o); return o.view(np.uint32)
+    if name == "quat_to_rot_quirk":
+        o = f32(9); run("ssf_dbg_quat_to_rot", r, o); return o.view(np.uint32)
+    if name in ("sym_inverse", "plane_solve"):
+        o = f32(6 if name == "sym_inverse" else 3); rc = run("ssf_dbg_" + name, r, o); return np.concatenate([np.uint32([rc]), o.view(np.uint32)])
+    if name == "principal_frame":
+        v, w = f32(9), f32(3); run("ssf_dbg_principal_frame", r, v, w); return np.concatenate([v, w]).view(np.uint32)
+    if name == "guard":
+        return np.uint32([run("ssf_dbg_connectivity_guard", r)])
+    split, fn, nout = {"sym_mul": (6, "ssf_dbg_sym_mulv", 3), "rot_sym": (9, "ssf_dbg_mult_abat", 6), "m3_mul": (9, "ssf_dbg_m3_mul", 9),
+                       "m3_mulv": (9, "ssf_dbg_m3_mulv", 3), "row_mul": (3, "ssf_dbg_row_mul", 3)}[name]
+    o = f32(nout); run(fn, np.ascontiguousarray(r[:split]), np.ascontiguousarray(r[split:]), o); return o.view(np.uint32)
+
+
+def test_oracle_batch_entry_equals_its_per_element_hooks(oracle_lib, orc_batch):
+    """2048 seeded elements per operation that include/ssf_testing.h exposes: the batch loop returns what the hook returns, bit for
+    bit (no NaN allowance needed: it is the same code in the same library)"""
+    ins = _hook_inputs(np.random.default_rng(31), 2048)
+    for name, x in ins.items():
+        got = mo.evaluate(orc_batch, name, x)
+        want = np.stack([_hook_result(oracle_lib.lib, name, row) for row in x])
+        assert np.array_equal(got, want), (name, int(np.flatnonzero((got != want).any(axis=1))[0]))
+    assert orc_batch(9999, None, None, 0) == -1
+    assert oracle_lib.lib.ssf_oracle_mathbatch_num_ops() == len(mo.OPS)
+
+
+@pytest.mark.parametrize("name", sorted(mo.FX64_PAIRS))
+def test_fx_quant_is_exact_integer_rounding(name, orc_batch):
+    """the oracle's fx_quant against round_half_even(Fraction(v) * scale) clamped to +-limit in Python integers, on 20 000 values that
+    hold every edge of the pair: all k + 0.5 for |k| <= 2^12, the neighbours of +-limit, +-2^50 .. +-2^62 after scaling, +-0, +-inf, NaN"""
+    v = mo.fx_exact_subset(name)
+    assert len(v) == 20000
+    got = mo.evaluate(orc_batch, name, v).view(np.int64).reshape(-1)
+    want = mo.fx_exact(v, *mo.FX64_PAIRS[name])
+    bad = np.flatnonzero(got != want)
+    assert bad.size == 0, (name, float(v[bad[0]]).hex(), int(got[bad[0]]), int(want[bad[0]]))
+
+
+def test_probe_library_is_built_like_the_product_and_lists_every_operation(probe_lib):
+    """csrc/Makefile compiles probe/ssf_math_probe.hip with the product's FLAGS, unchanged; the library's table is the shared
+    header's list (number, name, element sizes)"""
+    import subprocess
+    def command(target, touched):
+        out = subprocess.run(["make", "-C", mo.CSRC, "-n", "-W", touched, target], stdout=subprocess.PIPE, text=True, check=True).stdout
+        line = [l for l in out.splitlines() if "hipcc" in l and touched in l][0].split()
+        return [t for t in line if not t.endswith((".hip", ".o", ".so")) and t not in ("-c", "-o", "-shared")]
+    assert command("mathprobe", "probe/ssf_math_probe.hip") == command("ssf_testing.o", "ssf_testing.hip")
+    assert probe_lib.ssf_mathprobe_num_ops() == len(mo.OPS)
+    listed = {}
+    for k in range(len(mo.OPS)):
+        i, nm, iw, ow = C.c_int(), C.c_char_p(), C.c_int(), C.c_int()
+        assert probe_lib.ssf_mathprobe_op_info(k, C.byref(i), C.byref(nm), C.byref(iw), C.byref(ow)) == 0
+        listed[nm.value.decode()] = (i.value, iw.value, ow.value)
+    assert listed == mo.OPS
+    assert sorted(v[0] for v in mo.OPS.values()) == list(range(len(mo.OPS)))
+    assert set(mo.FX64_PAIRS) == {n for n in mo.OPS if n.startswith("fx64_")}
+
+
+def test_probe_host_branches_equal_the_oracle(probe_lib, orc_batch):
+    """the probe's operations through the HOST branches of ssf_math.hpp (what the product's ssf_dbg_* hooks evaluate) against the
+    oracle's batch entry: every f32 helper on the binade set, fx64 on each pair's edges, the matrix helpers on seeded elements.
+    This checks the probe's layouts without a GPU; the device branches are tests/test_math_device_gpu.py's."""
+    host = probe_lib.ssf_mathprobe_eval_host
+    b32 = mo.f32_binade_set()[::16]
+    pos = b32[(b32 >> 31) == 0]
+    for name in ("fx32r", "fx32_s20", "fx32_s24", "pixel_round", "exp_neg_spec", "srgb_expand", "srgb_compress", "lab_f", "rng_unit"):
+        mo.assert_same(name, b32, mo.evaluate(host, name, b32), mo.evaluate(orc_batch, name, b32), ("product host", "oracle"))
+    for name in ("cbrtf_spec", "pow24_spec", "pow_inv24_spec"):
+        mo.assert_same(name, pos, mo.evaluate(host, name, pos), mo.evaluate(orc_batch, name, pos), ("product host", "oracle"))
+    for name, (sb, lb) in mo.FX64_PAIRS.items():
+        v = mo.fx_exact_subset(name)
+        mo.assert_same(name, v, mo.evaluate(host, name, v), mo.evaluate(orc_batch, name, v), ("product host", "oracle"))
+    rng = np.random.default_rng(32)
+    d = rng.uniform(0.008, 1.2, 4096)
+    for name, x in (("div3_exact", d), ("cbrt_spec", d), ("root5_spec", d), ("div_inrange", np.stack([d, rng.uniform(0.04, 1.2, 4096)], 1)),
+                    ("div3_u64", rng.integers(0, 1 << 63, 4096, dtype=np.uint64)), ("rng_draw", rng.integers(0, 1 << 32, (4096, 4), dtype=np.uint32)),
+                    ("rgb8_to_lab", rng.integers(0, 1 << 24, 4096, dtype=np.uint32)), ("len3", np.float32(rng.uniform(-3, 3, (4096, 3)))),
+                    ("unit3", np.float32(rng.uniform(-3, 3, (4096, 3))))):
+        mo.assert_same(name, x, mo.evaluate(host, name, x), mo.evaluate(orc_batch, name, x), ("product host", "oracle"))
+    for name, x in _hook_inputs(np.random.default_rng(33), 1024).items():
+        mo.assert_same(name, x, mo.evaluate(host, name, x), mo.evaluate(orc_batch, name, x), ("product host", "oracle"))
+    lut = np.zeros(256, np.float32)
+    probe_lib.ssf_mathprobe_expand_lut(fptr(lut))
+    c = np.float32(np.arange(256, dtype=np.float32) / np.float32(255.0))
+    assert np.array_equal(lut.view(np.uint32), mo.evaluate(orc_batch, "srgb_expand", c).reshape(-1))
+
+
+def test_product_library_exports_what_the_parent_build_exported(product_lib):
+    """the arithmetic probe is a library of its own: libssf_hip.so's dynamic symbol table is the list recorded from the build
+    before the probe existed (tests/golden/libssf_hip_dynsyms.txt: `nm -D --defined-only | awk '{print $3}' | sort`; a change
+    that adds or removes a kernel or an entry point regenerates it) and holds no probe symbol"""
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", product_lib.path], stdout=subprocess.PIPE, text=True, check=True).stdout
+    have = sorted(l.split()[2] for l in out.splitlines() if len(l.split()) == 3)
+    want = open(os.path.join(os.path.dirname(GOLD), "libssf_hip_dynsyms.txt")).read().split()
+    assert have == sorted(want), sorted(set(have) ^ set(want))
+    assert not [s for s in have if "probe_" in s or "mathprobe" in s]
