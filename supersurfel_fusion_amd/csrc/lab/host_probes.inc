@@ -17,6 +17,8 @@ int ssf_dbg_device_icp_records(ssf_handle* h, int64_t* out64) {
 }
 // fault injection: a stall of the calling thread in front of the host's word to the waiting launch (ssf_waiter_match_repairs)
 void ssf_dbg_stall_before_match_us(ssf_handle* h, long long us) { if (h) h->dbg_stall_before_match_us = us; }
+// frames whose in-launch association bid into the replicas of the association table (SSF_ASSOC_REPLICAS=0 switches them off)
+long long ssf_dbg_assoc_replica_frames(ssf_handle* h) { return h ? h->n_assoc_replica_frames : -1; }
 // host-side time split of the pipelined loop (tools/pipeline_probe.py); reset on read
 int ssf_dbg_host_times(ssf_handle* h, double* out8) {
     if (!h || !out8) return SSF_ERR_INVALID_ARG;
@@ -74,7 +76,7 @@ double ssf_dbg_time_fuse(ssf_handle* h, int reps, int mode, long long* blocks2 /
     const int S = (mode & 2) ? 0 : h->S, nvis = (mode & 4) ? 0 : h->n_visible, span = (mode & 1) ? 0 : h->oov_tail - h->oov_head;
     auto launch = [&] {
         ClassifyArgs ca = h->classify; ca.plane_depth = h->cc->maps.plane_depth;
-        launch_fuse(h->stream, M, h->cc->frame, h->pose, h->stamp, h->id_offset, nvis, AssocTables{h->cc->d_best, h->cc->d_matched, h->d_cand, S},
+        launch_fuse(h->stream, M, h->cc->frame, h->pose, h->stamp, h->id_offset, nvis, AssocTables{h->cc->d_best, h->cc->d_matched, h->d_cand, S, 0},
                     (nvis > 0 && S > 0) ? 1 : 0, h->cfg.nb_supersurfels_max, ShardArgs{0, 1, 0, h->cfg.shard_tile}, h->d_cnt,
                     h->oov[h->ocur], span, ca, h->d_state, h->d_state_oov, h->d_bc_oov, ws, 1);
     };

@@ -285,12 +285,20 @@ SSF_HD unsigned int icp_go_word_weight(unsigned int dword) {      // dword 0..11
 }
 SSF_HD unsigned int icp_go_abort_check(unsigned int want) { return ((want * 0x9E3779B1u) >> 2) & SSF_ICP_GO_CHECK_MASK; }
 #define SSF_ICP_GO_SLOTS 4
-struct MatchArgs { float zmin, zmax; long long id_offset; unsigned long long* best; uint8_t* matched; int32_t* cand; };    // launch_match's arguments
+// The association table of a frame slot is a slab of nine: table 0 (S words: what k_match, the tile-sorted path, the exchanges and the
+// stage seams write, read and ship) and SSF_ASSOC_REPLICAS replicas behind it, table 1 + x at (1 + x) * assoc_stride(S) words -- whole
+// 128-byte lines, so no two tables share one.  A frame of a single shard alone bids into the replica of the XCD its workgroup runs
+// on (rstride != 0: MatchArgs, AssocTables, ClassifyArgs); the readers of the fuse launch take the minimum over the nine (assoc_best,
+// ssf_track_fuse.hip).  All nine are put to SSF_NO_MATCH where the frame's supersurfels are made (k_finalize_surfels, k_import_frame).
+#define SSF_ASSOC_REPLICAS 8
+SSF_HD int assoc_stride(int S) { return (S + 15) & ~15; }
+SSF_HD size_t assoc_table_words(int S) { return (size_t)(1 + SSF_ASSOC_REPLICAS) * (size_t)assoc_stride(S); }
+struct MatchArgs { float zmin, zmax; long long id_offset; unsigned long long* best; uint8_t* matched; int32_t* cand; int rstride; };    // launch_match's arguments; rstride != 0: the in-launch association bids into the replicas
 // what the fuse launches take in groups: the classification of a row (filterModel) | this shard's place among the ranks (migrate:
 // updated rows that cross a tile edge leave) | the frame's association tables (launch_match's output; S frame supersurfels)
-struct ClassifyArgs { Cam cam; const float* plane_depth; int delta_t; float conf_thresh, zmin, zmax; };
+struct ClassifyArgs { Cam cam; const float* plane_depth; int delta_t; float conf_thresh, zmin, zmax; int assoc_rstride; };     // assoc_rstride: AssocTables::rstride on its way into the fuse launch (launch_fuse sets it)
 struct ShardArgs { int rank, nranks, migrate; float tile; };
-struct AssocTables { const unsigned long long* best; const uint8_t* matched; const int32_t* cand; int S; };
+struct AssocTables { const unsigned long long* best; const uint8_t* matched; const int32_t* cand; int S; int rstride; };       // rstride != 0: this frame bid into the replicas
 int icp_variant_mode();              // 0: the product's k_icp; other values: measurement arms that cannot take SSF_ICP_GO_MATCH
 void launch_icp(hipStream_t st, const Cam& cam, SurfelSoA model, int n_visible, const uint2* pix2, const float4* fpack,
                 Rt T, long long* replicas, unsigned int* ticket,

@@ -1332,6 +1332,8 @@ __global__ __launch_bounds__(256) void k_finalize_surfels(SegParams p, FrameMaps
     __syncthreads();
     if (wv != 2 || !active) return;
     best[k] = SSF_NO_MATCH; matched[k] = 0;         // association tables of this frame (findBestMatches init)
+#pragma unroll
+    for (int x = 1; x <= SSF_ASSOC_REPLICAS; x++) best[(size_t)x * assoc_stride(p.S) + k] = SSF_NO_MATCH;          // ... and its replicas (ssf_device.hpp)
     M3 vecs = m3(v3(0, 0, 0), v3(0, 0, 0), v3(0, 0, 0));
     float d0 = 0.f, d1 = 0.f; int s0 = 0, s1 = 0;
     if (valid) {
@@ -1404,6 +1406,8 @@ __global__ __launch_bounds__(256) void k_import_frame(int P, int S, FrameMaps m,
     m.fpack[4 * k + 1] = make_float4(r2.x, r2.y, r2.z, 0.f);
     m.fpack[4 * k + 2] = make_float4(pos.x, pos.y, pos.z, 0.f);
     best[k] = SSF_NO_MATCH; matched[k] = 0;
+#pragma unroll
+    for (int x = 1; x <= SSF_ASSOC_REPLICAS; x++) best[(size_t)x * assoc_stride(S) + k] = SSF_NO_MATCH;
 }
 
 // the S frame supersurfels of slot blockIdx.y in the wire layout of k_import_frame (what the rank that extracted a batch ships)

@@ -353,6 +353,10 @@ struct ssf_handle {
     // first ICP iteration of the next submitted frame, accumulated ahead by the row-move kernel of the frame just
     // fused (do_fuse): valid for exactly that frame, that pose and that model; anything else drops it
     struct { bool valid = false; unsigned long long seq = 0; ExtractCtx* ctx = nullptr; int slot = 0; int stamp = 0; Rt pose; } ahead;
+    int assoc_rstride = 0;                // the frame in process_oldest bids into the replicas of its association table (0: table 0 alone)
+#ifdef SSF_EXPERIMENTS
+    long long n_assoc_replica_frames = 0; // frames that did (ssf_dbg_assoc_replica_frames)
+#endif
     double wait_launched_us = 0.0; long long n_waiter_match_repairs = 0; long long dbg_stall_before_match_us = 0;     // see process_oldest: SSF_ICP_GO_MATCH has no acknowledgement
     bool icp_ahead = true; int icp_ahead_mode = 1;         // 1: when the next frame's extract has finished (the product); 2 (lab): always, the track stream waits for it
     AheadTuner ahead_tuner;

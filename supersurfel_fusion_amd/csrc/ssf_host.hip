@@ -920,7 +920,7 @@ static int fuse_begin(ssf_handle* h, int migrate) {
             h->part_set ^= 1;
         }
         // update | insert | classification of every row | publication of the counters: one launch
-        const AssocTables at{h->cc->d_best, h->cc->d_matched, h->d_cand, h->S};
+        const AssocTables at{h->cc->d_best, h->cc->d_matched, h->d_cand, h->S, h->assoc_rstride};
         launch_fuse(h->stream, M, h->cc->frame, h->pose, h->stamp, h->id_offset, h->n_visible, at, nvis_g > 0 ? 1 : 0,
                     h->cfg.nb_supersurfels_max, h->shard, h->d_cnt, h->oov[h->ocur], h->oov_tail - h->oov_head, h->classify,
                     h->d_state, h->d_state_oov, h->d_bc_oov, ws, h->fuse_totals.from_tot);
@@ -1052,6 +1052,16 @@ static bool icp_waiter_can_match(const ssf_handle* h) {
     static const bool off = SSF_ENV_SET("NO_MATCH_IN_WAITER");          // (measurement switch)
     return !off && single_shard_alone(h) && h->cfg.profile == 0 && icp_variant_mode() == 0;
 }
+// Which frames bid into the replicas of the association table (ssf_device.hpp): those whose association runs inside an ICP launch
+// over the visible array -- a single shard alone.  The tile-sorted copy (its XCDs already bid for disjoint frame supersurfels),
+// k_match as a launch of its own, sharded handles and the stage seams stay on table 0: rstride 0, and the readers read one word.
+static int assoc_replica_stride(const ssf_handle* h) {
+#ifdef SSF_EXPERIMENTS
+    static const bool off = SSF_ENV_INT("ASSOC_REPLICAS", 1) == 0;          // (measurement switch: A/B runs of one build)
+    if (off) return 0;
+#endif
+    return (icp_waiter_can_match(h) && !h->bins.valid) ? assoc_stride(h->S) : 0;
+}
 static int icp_launch_waiting(ssf_handle* h, IcpWaiter& w) {
     w.seq_rec = ++h->icp_seq;
     w.go_seq = ++h->go_count;
@@ -1059,7 +1069,7 @@ static int icp_launch_waiting(ssf_handle* h, IcpWaiter& w) {
     h->wait_launched_us = now_us();               // (before the launch call: no workgroup of it can have started waiting earlier)
     Rt none; none.R = m3_identity(); none.t = v3(0, 0, 0);
     const P2PView pv = h->p2p.view;               // (the number of the peer exchange arrives with the go word)
-    const MatchArgs ma{h->cfg.range_min, h->cfg.range_max, h->id_offset, h->cc->d_best, h->cc->d_matched, h->d_cand};
+    const MatchArgs ma{h->cfg.range_min, h->cfg.range_max, h->id_offset, h->cc->d_best, h->cc->d_matched, h->d_cand, h->assoc_rstride};
     const int rc = icp_issue(h, none, w.seq_rec, nullptr, w.slot, w.go_seq, h->p2p.on ? &pv : nullptr, icp_waiter_can_match(h) ? &ma : nullptr);
     w.waiting = rc == SSF_OK;
     return rc;
@@ -1087,7 +1097,7 @@ static int icp_launch_resident(ssf_handle* h, IcpWaiter& w, const Rt* T0, unsign
     h->go_count += (unsigned long long)last;
     w.resident = true; w.slot = lines + 1; w.go_seq = go_base + 1;
     h->wait_launched_us = now_us();               // (before the launch call: no workgroup of it can have started waiting earlier)
-    const MatchArgs ma{h->cfg.range_min, h->cfg.range_max, h->id_offset, h->cc->d_best, h->cc->d_matched, h->d_cand};
+    const MatchArgs ma{h->cfg.range_min, h->cfg.range_max, h->id_offset, h->cc->d_best, h->cc->d_matched, h->d_cand, h->assoc_rstride};
     launch_icp_resident(h->stream, h->cam, h->model[h->mcur], h->n_visible, h->cc->maps.pix2, h->cc->maps.fpack, T0, h->d_icp_replicas, h->d_icp, h->mb_dev,
                         seq0, lines, (unsigned int)go_base, last, icp_waiter_can_match(h) ? &ma : nullptr);
     HCK(hipGetLastError());
@@ -1224,6 +1234,9 @@ static int icp_loop_end(ssf_handle* h, TrackFrame& f) {
 #endif
         icp_release_waiting(w.slot, w.go_seq, &h->pose, 0, true);
         matched_by_waiter = true;
+#ifdef SSF_EXPERIMENTS
+        if (h->assoc_rstride) h->n_assoc_replica_frames++;          // (a frame the rule below repairs has bid into the replicas too, with whatever part of its grid was left)
+#endif
         // The word has no acknowledgement.  A waiting workgroup gives up after SSF_ICP_GO_WAIT_TICKS (0.25 s) and tells the rest
         // of its launch to leave; if this thread was stalled that long (descheduled, a debugger, SIGSTOP) between the launch and
         // the store above, the word may have found only the late-dispatched part of the grid and the association would cover a
@@ -1296,10 +1309,12 @@ static int process_oldest(ssf_handle* h, const float* prior, ssf_frame_result* o
     if (exchanges_natively(h)) { rc = comm_counts(h); if (rc) return rc; }
     icp_begin(h, prior);
     rc = h->bins.make_if_large(h);
+    h->assoc_rstride = rc ? 0 : assoc_replica_stride(h);
     if (!rc) rc = icp_chains(h) ? icp_loop_chained(h, f) : icp_loop_plain(h, f);
     if (!rc) rc = icp_loop_end(h, f);
     ssf_frame_result r;
     if (!rc) rc = exchange_and_fuse(h, &r);
+    h->assoc_rstride = 0;                         // (the frame's: a stage seam that fuses next reads table 0 alone)
     if (rc) return rc;
     if (h->pending.empty()) h->ahead_tuner.sequence_break(); else h->ahead_tuner.frame_done(now_us(), r.icp_iters);
     h->host_us[1] += f.t_b - f.t_a; h->host_us[2] += now_us() - f.t_b; h->host_us[3] += 1;
@@ -1578,7 +1593,7 @@ int ssf_create(const ssf_config* cfg, ssf_handle** out) {
         SurfelSoA& f = c.frame;
         take(f.pos, 3 * S); take(f.col, 3 * S); take(f.lab, 3 * S); take(f.stamps, 2 * S); take(f.r0, 3 * S); take(f.r1, 3 * S);
         take(f.r2, 3 * S); take(f.shape, 6 * S); take(f.dims, 2 * S); take(f.conf, S);
-        take(c.d_best, S); take(c.d_matched, S); take(c.d_rgb_in, 4 * P); take(c.d_depth_in, P); take(c.d_depth_filt, P); take(c.d_mask, S);
+        take(c.d_best, assoc_table_words(S)); take(c.d_matched, S); take(c.d_rgb_in, 4 * P); take(c.d_depth_in, P); take(c.d_depth_filt, P); take(c.d_mask, S);
         take(c.d_wire, 26 * S);
         take(c.d_pixmask, P); take(c.d_pixcnt, 2 * S);
         return (off + 255) & ~(size_t)255;

@@ -443,6 +443,28 @@ __device__ __forceinline__ void match_sorted_rows(const Cam& cam, const SurfelSo
         ma.cand[oid] = match_values(cam, a.w, v3(a.x, a.y, a.z), v3(c.x, c.y, c.z), v3(b.x, b.y, b.z), oid, pix2, fpack, pose, ma.zmin, ma.zmax, ma.id_offset, ma.best, ma.matched, true);
     }
 }
+// Where the in-launch association of a frame that uses the replicas bids (MatchArgs::rstride != 0): the replica of the XCD this
+// workgroup runs on (HW_REG_XCC_ID).  The atomic stays agent-scope, so WHICH table a workgroup picks changes the number of bids
+// that meet on one word -- an eighth -- and never the result.  Uniform, and evaluated only behind the wait, in the branch that
+// associates, so nothing of it is live across the waits: k_icp offsets the pointer once in front of its row loop, k_icp_resident
+// (one row per lane, no loop) where it calls match_values.
+__device__ __forceinline__ unsigned long long* assoc_bid_table(const MatchArgs& ma) {
+    const unsigned int xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u;      // HW_REG_XCC_ID[3:0]
+    return ma.rstride ? ma.best + (size_t)(1u + xcc) * (size_t)ma.rstride : ma.best;
+}
+// What the association left for frame supersurfel f: the minimum over table 0 and, when the frame bid into the replicas, tables
+// 1-8 -- nine loads in one trip.  Keys are unique (the row's id is the low half), so this is the word one table would hold.
+__device__ __forceinline__ unsigned long long assoc_best(const unsigned long long* __restrict__ best, int f, int rstride) {
+    unsigned long long v = best[f];
+    if (rstride) {
+        unsigned long long r[SSF_ASSOC_REPLICAS];
+#pragma unroll
+        for (int x = 0; x < SSF_ASSOC_REPLICAS; x++) r[x] = best[(size_t)(1 + x) * (size_t)rstride + f];
+#pragma unroll
+        for (int x = 0; x < SSF_ASSOC_REPLICAS; x++) v = r[x] < v ? r[x] : v;
+    }
+    return v;
+}
 #define SSF_ICP_DBG_COUNTED 0x40000000          // bit of k_icp's `dbg` argument: end the launch with the counted record
 #ifndef SSF_ICP_GO_WAIT_TICKS
 #define SSF_ICP_GO_WAIT_TICKS 25000000ull     // 0.25 s of the 100 MHz wall clock: how long a launch made ahead waits for the host's word
@@ -547,9 +569,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(SSF_ICP_NUM_SGP
                 T.R = m3(v3(sT(0), sT(1), sT(2)), v3(sT(3), sT(4), sT(5)), v3(sT(6), sT(7), sT(8)));
                 T.t = v3(sT(9), sT(10), sT(11));
                 if constexpr (MODE == 3) { if (ma.best) match_sorted_rows(cam, model, n_visible, pix2, fpack, T, ma); return; }
-                if (ma.best && !by_tile)
+                if (ma.best && !by_tile) {
+                    unsigned long long* const bid = assoc_bid_table(ma);
                     for (int id = blockIdx.x * WG + threadIdx.x; id < n_visible; id += n_wg * WG)
-                        ma.cand[id] = match_row(cam, model, id, id, pix2, fpack, T, ma.zmin, ma.zmax, ma.id_offset, ma.best, ma.matched);
+                        ma.cand[id] = match_row(cam, model, id, id, pix2, fpack, T, ma.zmin, ma.zmax, ma.id_offset, bid, ma.matched);
+                }
                 return;
             }
         }
@@ -677,7 +701,7 @@ __global__ __launch_bounds__(256, 7) __attribute__((amdgpu_num_sgpr(SSF_ICP_NUM_
             auto sT = [&](int i) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_T[i]))); };
             Rt P; P.R = m3(v3(sT(0), sT(1), sT(2)), v3(sT(3), sT(4), sT(5)), v3(sT(6), sT(7), sT(8)));
             P.t = v3(sT(9), sT(10), sT(11));
-            if (ma.best && live) ma.cand[id] = match_values(cam, m_conf, mpos, mnrm, mlab, id, pix2, fpack, P, ma.zmin, ma.zmax, ma.id_offset, ma.best, ma.matched, false);
+            if (ma.best && live) ma.cand[id] = match_values(cam, m_conf, mpos, mnrm, mlab, id, pix2, fpack, P, ma.zmin, ma.zmax, ma.id_offset, assoc_bid_table(ma), ma.matched, false);
             return;
         }
         T.R = m3(v3(s_T[0], s_T[1], s_T[2]), v3(s_T[3], s_T[4], s_T[5]), v3(s_T[6], s_T[7], s_T[8]));
@@ -900,7 +924,7 @@ __global__ __launch_bounds__(256) void k_match(Cam cam, SurfelSoA model, int n_v
     // in contiguous shares -- see xcd_block)
     if constexpr (SORTED) {                       // (the copy's 48-byte records: ssf_tile_rows.inc)
         (void)orig;
-        const MatchArgs ma{zmin, zmax, id_offset, best, matched, cand};
+        const MatchArgs ma{zmin, zmax, id_offset, best, matched, cand, 0};
         match_sorted_rows(cam, model, n_visible, pix2, fpack, pose, ma);
         return;
     } else {
@@ -1055,7 +1079,7 @@ __device__ __forceinline__ void update_group(SurfelSoA M, SurfelSoA F, Rt pose, 
     // Two dependent round trips instead of four: everything that hangs on the frame supersurfel alone is requested at
     // once (association result and the frame row), then everything that hangs on the model row it won.
     unsigned int mt = matched[f];
-    unsigned long long bk = best[f];
+    unsigned long long bk = assoc_best(best, f, ca.assoc_rstride);
     float f_conf = F.conf[f];
     V3 f_pos = v3(0.f, 0.f, 0.f), f_lab = v3(0.f, 0.f, 0.f);
     Sym3 f_shape = sym3(0.f, 0.f, 0.f, 0.f, 0.f, 0.f);
@@ -1292,7 +1316,7 @@ __global__ __launch_bounds__(256) void k_update_insert(SurfelSoA M, SurfelSoA F,
             int f = cand[i];
             float conf = M.conf[i]; int seen = M.stamps[2 * (size_t)i + 1]; V3 pos = ld3(M.pos, (size_t)i);
             asm volatile("" : "+v"(f), "+v"(conf), "+v"(seen), "+v"(pos.x));
-            const bool rewritten = do_update && f >= 0 && (uint32_t)(best[f] & 0xFFFFFFFFull) == (uint32_t)(id_offset + i);
+            const bool rewritten = do_update && f >= 0 && (uint32_t)(assoc_best(best, f, ca.assoc_rstride) & 0xFFFFFFFFull) == (uint32_t)(id_offset + i);
             if (!rewritten) {
                 cls = classify_values(ca.cam, conf, seen, pos, pose, ca.plane_depth, stamp, ca.delta_t, ca.conf_thresh, ca.zmin, ca.zmax);
                 if (cls == 2) M.conf[i] = -1.0f;
@@ -1647,8 +1671,9 @@ __global__ __launch_bounds__(256) void k_pack_emigrants(SurfelSoA M, const unsig
     int32_t w[SSF_MIGRANT_WORDS];
 #pragma unroll
     for (int i = 0; i < SSF_MIGRANT_WORDS; i++) w[i] = 0;
-    if (do_update && matched[f] && best[f] != SSF_NO_MATCH) {
-        const long long local = (long long)(uint32_t)(best[f] & 0xFFFFFFFFull) - id_offset;
+    const unsigned long long bk = assoc_best(best, f, 0);        // (a sharded frame never bids into the replicas)
+    if (do_update && matched[f] && bk != SSF_NO_MATCH) {
+        const long long local = (long long)(uint32_t)(bk & 0xFFFFFFFFull) - id_offset;
         if (local >= 0 && local < n_visible) {
             const size_t m = (size_t)local;
             const float conf = M.conf[m];
@@ -2144,7 +2169,7 @@ void launch_icp(hipStream_t st, const Cam& cam, SurfelSoA model, int n_visible, 
                 long long* sums29, Mailbox* mb, unsigned long long seq, int dbg_arg, IcpGo* go, unsigned long long go_seq,
                 const P2PView* pv, int by_tile, const MatchArgs* match) {
     ScopedKernel sk("icp_accumulate", st);
-    const MatchArgs ma = match ? *match : MatchArgs{0.f, 0.f, 0, nullptr, nullptr, nullptr};
+    const MatchArgs ma = match ? *match : MatchArgs{0.f, 0.f, 0, nullptr, nullptr, nullptr, 0};
     // one row per thread, <= 4096 workgroups (grid-stride beyond).  (lab: SSF_ICP_PER_LANE=n rows per thread with register sums,
     // SSF_ICP_WRED=1 the DPP row reduction -- lab/icp_arms.inc, both measured slower: DESIGN.md section 4.3)
     const int mode = dbg_arg > 0 && dbg_arg != 4 ? 0 : icp_variant_mode();      // (the probe switches live in the one-row-per-thread form)
@@ -2174,7 +2199,7 @@ void launch_icp_resident(hipStream_t st, const Cam& cam, SurfelSoA model, int n_
                          long long* replicas, long long* sums29, Mailbox* mb, unsigned long long seq0, IcpGo* go, unsigned int go_base,
                          int last_idx, const MatchArgs* match) {
     ScopedKernel sk("icp_resident", st);
-    const MatchArgs ma = match ? *match : MatchArgs{0.f, 0.f, 0, nullptr, nullptr, nullptr};
+    const MatchArgs ma = match ? *match : MatchArgs{0.f, 0.f, 0, nullptr, nullptr, nullptr, 0};
     Rt none; none.R = m3_identity(); none.t = v3(0, 0, 0);
     unsigned long long* counted = reinterpret_cast<unsigned long long*>(replicas) + SSF_ICP_REPLICAS * 32;
     hipLaunchKernelGGL(k_icp_resident, dim3((n_visible + 255) / 256), dim3(256), 0, st, cam, model, n_visible, pix2, fpack, T0 ? *T0 : none, counted, sums29,
@@ -2197,10 +2222,11 @@ void launch_fuse(hipStream_t st, SurfelSoA model, SurfelSoA frame, Rt pose, int 
     ScopedKernel sk("update_insert", st);
     const int S = at.S, nchunks = (S + 255) / 256, nb_oov = (span_upper + 255) / 256, nb_vis = (n_visible + 255) / 256;
     const int nupd = (S + UPD_PER_WG - 1) / UPD_PER_WG;
+    ClassifyArgs cr = ca; cr.assoc_rstride = at.rstride;
     hipLaunchKernelGGL(k_update_insert, dim3(nupd + nchunks + nb_vis + (nb_oov + OOV_PER_WG - 1) / OOV_PER_WG), dim3(256), 0, st, model,
                        frame, pose, stamp, id_offset,
                        n_visible, at.best, at.matched, at.cand, S, do_update, capacity, sh.rank, sh.nranks, sh.tile, cnt, nupd, nchunks, nb_vis,
-                       nb_oov, oov, ca, state_vis, state_oov, bc_oov, ws, sh.migrate, tail_in_move);
+                       nb_oov, oov, cr, state_vis, state_oov, bc_oov, ws, sh.migrate, tail_in_move);
 }
 void launch_pack_emigrants(hipStream_t st, SurfelSoA model, const AssocTables& at, long long id_offset, int n_visible,
                            const uint8_t* state_vis, int do_update, const ShardArgs& sh, int32_t* table) {
