@@ -4,12 +4,12 @@
 //   * rows   both model stores are read in place (never materialised), one thread per SLOT of [visible rows | out-of-view
 //            span], as the render kernels do.  Slot order = logical order, so a sort that is stable over slots is stable over
 //            logical indices; an out-of-view slot's logical index = n_visible + (live rows before it): a per-256-block count
-//            (k_graph_keys), an exclusive scan (k_graph_scan into own scratch: the handle's Counters and d_bc_oov are not
+//            (k_graph_keys), an exclusive scan (launch_slots_scan32 into own scratch: the handle's Counters and d_bc_oov are not
 //            touched) and a rank inside the block -- the view and these helpers are ssf_slots.hpp's, shared with the render.
 //   * rank   k_graph_keys: per slot the birth stamp and an eligibility byte, the out-of-view live counts, and min / max /
 //            count of the eligible stamps with exact integer atomics (the result does not depend on their order).  Then a
 //            stable least-significant-digit counting sort of (stamp - min) over 8-bit digits, 1..3 passes for a span of up to
-//            2^24 (the header admits 2^20): per pass a per-workgroup digit histogram (k_graph_hist), one k_graph_scan over
+//            2^24 (the header admits 2^20): per pass a per-workgroup digit histogram (k_graph_hist), one launch_slots_scan32 over
 //            (digit, workgroup) and a scatter (k_graph_scatter) whose position inside a workgroup comes from wave ballots,
 //            never from the arrival order of an atomic.  Pass 0 drops the ineligible slots, so the sorted list is dense:
 //            rank -> slot.
@@ -56,13 +56,6 @@ __global__ __launch_bounds__(256) void k_graph_keys(ModelView mv, float min_conf
         }
         if (l > 0) atomicAdd(&mm[3], l);
     }
-}
-
-// exclusive scan of n counts in place (one workgroup of 1024); a[n] = the total
-__global__ __launch_bounds__(1024) void k_graph_scan(uint32_t* __restrict__ a, int n) {
-    __shared__ uint32_t tot[1];
-    workgroup_scan<1, uint32_t>(a, n, nullptr, tot);
-    if (threadIdx.x == 0) a[n] = tot[0];
 }
 
 // ---- one pass of the stable counting sort: GRAPH_SORT_ITEMS items per workgroup, digit = ((key - lo) >> shift) & 255 ----------
@@ -233,7 +226,7 @@ __global__ __launch_bounds__(256) void k_graph_edges(const float4* __restrict__ 
 static void launch_graph_keys(hipStream_t st, const ModelView& mv, float min_conf, int32_t* stamp, uint8_t* elig, uint32_t* bc, int* mm) {
     ScopedKernel sk("graph_rank", st);
     hipLaunchKernelGGL(k_graph_keys, dim3(mv.nbv + mv.nbo), dim3(256), 0, st, mv, min_conf, stamp, elig, bc, mm);
-    if (mv.nbo > 0) hipLaunchKernelGGL(k_graph_scan, dim3(1), dim3(1024), 0, st, bc, mv.nbo);
+    if (mv.nbo > 0) launch_slots_scan32(st, bc, mv.nbo);
 }
 // stable sort of the eligible slots by (stamp - lo), `passes` 8-bit digits; cnt[256 ceil(nslots / GRAPH_SORT_ITEMS) + 1]; returns
 // which of the pairs (key_a, slot_a) = 0 / (key_b, slot_b) = 1 holds the n_elig sorted (stamp, slot) entries
@@ -248,7 +241,7 @@ int launch_graph_sort(hipStream_t st, int nslots, int n_elig, int lo, int passes
         const int nb = (n + GRAPH_SORT_ITEMS - 1) / GRAPH_SORT_ITEMS;
         int32_t* kout = out == 0 ? key_a : key_b; uint32_t* sout = out == 0 ? slot_a : slot_b;
         hipLaunchKernelGGL(k_graph_hist, dim3(nb), dim3(256), 0, st, kin, el, n, lo, 8 * p, cnt, nb);
-        hipLaunchKernelGGL(k_graph_scan, dim3(1), dim3(1024), 0, st, cnt, 256 * nb);
+        launch_slots_scan32(st, cnt, 256 * nb);
         hipLaunchKernelGGL(k_graph_scatter, dim3(nb), dim3(256), 0, st, kin, el, sin, n, lo, 8 * p, cnt, nb, kout, sout);
         kin = kout; sin = sout; el = nullptr; n = n_elig; out ^= 1;
     }

@@ -4,6 +4,7 @@
 // and through ssf_exchange.hpp by ssf_exchange.hip.  Nothing here is part of the frame path's device interface (ssf_device.hpp).
 #pragma once
 #include <algorithm>
+#include <cassert>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -14,6 +15,7 @@
 #include <utility>
 #include <vector>
 #include "ssf_device.hpp"
+#include "ssf_stage_layout.hpp"
 #include "../../include/ssf_render.h"
 #include "../../include/ssf_graph.h"
 #include "../../include/ssf_graph_solve.h"
@@ -163,14 +165,75 @@ struct DevBufs {
     void release() { for (void** q : owned) { (void)hipFree(*q); *q = nullptr; } owned.clear(); }
     DevBufs() = default; DevBufs(const DevBufs&) = delete; ~DevBufs() { release(); }       // (owned points into the workspace that holds this)
 };
+#pragma GCC visibility push(hidden)       // (StagedIo, BinnedList: the library's own, no part of what it exports)
+// The host arrays of one call, carried through a staging buffer on the device: every array is declared ONCE, with its bytes and
+// the kernel argument that points at it (on declaration: the caller's own pointer).  reserve grows the buffer when the call needs
+// more and points every argument at its item's place (nullptr for a NULL array: not produced); copy_in / copy_out enqueue the
+// copies of the inputs / outputs.  The offsets are StageLayout's (ssf_stage_layout.hpp).
+struct StagedIo {
+    StageLayout lay;
+    void** arg[StageLayout::MAX_ITEMS];
+    unsigned inputs = 0;                                          // bit i: item i is read by the device (host -> device)
+    void add(const void* host, size_t bytes, void** dev, bool in) {
+        const int i = lay.add(host, bytes);
+        assert(i >= 0);                                           // (more items than StageLayout::MAX_ITEMS: raise it)
+        arg[i] = dev; if (in) inputs |= 1u << i;
+    }
+    template <typename T> void out(T* host, size_t bytes, T** dev) { add(host, bytes, (void**)dev, false); }
+    template <typename T> void in(const T* host, size_t bytes, const T** dev) { add(host, bytes, (void**)dev, true); }
+    size_t need() const { return lay.total; }
+    // *buf holds *have bytes: grown to cap (>= need(), the caller's growth rule) when need() does not fit
+    bool reserve(DevBufs& bufs, unsigned char** buf, size_t* have, size_t cap) {
+        if (need() > *have) { if (!bufs.grow({{(void**)buf, cap}})) return false; *have = cap; }
+        for (int i = 0; i < lay.n; i++) *arg[i] = lay.at(*buf, i);
+        return true;
+    }
+    hipError_t copy(hipStream_t st, bool in) const {
+        for (int i = 0; i < lay.n; i++) {
+            const StageLayout::Item& it = lay.item[i];
+            if (!it.host || ((inputs >> i) & 1u) != (in ? 1u : 0u)) continue;
+            const hipError_t e = in ? hipMemcpyAsync(*arg[i], it.host, it.bytes, hipMemcpyHostToDevice, st)
+                                    : hipMemcpyAsync(const_cast<void*>(it.host), *arg[i], it.bytes, hipMemcpyDeviceToHost, st);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    hipError_t copy_in(hipStream_t st) const { return copy(st, true); }
+    hipError_t copy_out(hipStream_t st) const { return copy(st, false); }
+};
+// (bin -> slot) lists: per bin (+ 1) the counts that launch_slots_scan turns into offsets and a copy of them, the fill's cursors,
+// and the list.  The caller zeroes off[0 .. bins], counts, scans and reads the 64-bit total; then reserve_list; then fills.
+struct BinnedList {
+    uint32_t* off = nullptr; uint32_t* cursor = nullptr; size_t bin_cap = 0;          // bin_cap words each (bins + 1)
+    uint32_t* list = nullptr; size_t list_cap = 0;
+    bool reserve_bins(DevBufs& bufs, size_t bins) {
+        if (bins + 1 <= bin_cap) return true;
+        if (!bufs.grow({{(void**)&off, 4 * (bins + 1)}, {(void**)&cursor, 4 * (bins + 1)}})) return false;
+        bin_cap = bins + 1;
+        return true;
+    }
+    // room for `total` entries: more than 2^32 - 1 are refused, a list that grows takes a quarter more (capped there).  On a
+    // failure (SSF_ERR_DEVICE) err is the caller's wording: too_many, or alloc_a [+ the bytes asked for + alloc_b]
+    int reserve_list(DevBufs& bufs, unsigned long long total, std::string& err, const char* too_many, const char* alloc_a, const char* alloc_b = nullptr) {
+        if (total > 0xFFFFFFFFull) { err = too_many; return SSF_ERR_DEVICE; }
+        if (total <= list_cap) return SSF_OK;
+        const size_t cap = std::min<unsigned long long>(total + total / 4, 0xFFFFFFFFull);
+        if (!bufs.grow({{(void**)&list, 4 * cap}})) {
+            err = alloc_b ? alloc_a + std::to_string(4 * cap) + alloc_b : std::string(alloc_a);
+            return SSF_ERR_DEVICE;
+        }
+        list_cap = cap;
+        return SSF_OK;
+    }
+};
+#pragma GCC visibility pop
 // working buffers of ssf_render_model (ssf_render.h): allocated on first use; each group (per slot / per tile / list / staged images)
 // is grown as a whole or not at all (DevBufs::grow)
 struct RenderWs {
     DevBufs bufs;
     float4* rec = nullptr; uint2* rbox = nullptr; int32_t* logical = nullptr; uint32_t* seen = nullptr; uint32_t* bc = nullptr;
     size_t slots = 0;                                              // per slot: record, pixel box, logical index, `seen` epoch
-    uint32_t* tcnt = nullptr; uint32_t* cursor = nullptr; size_t tiles = 0;           // per tile (+ 1): counts -> offsets, cursors
-    uint32_t* list = nullptr; size_t list_cap = 0;                                    // (tile -> slot) lists
+    BinnedList tl;                                                // (tile -> slot) lists, a bin per 16 x 16 tile
     unsigned long long* stats = nullptr;                          // fragments, filled pixels, rows shown, list entries
     unsigned char* img = nullptr; size_t img_bytes = 0;           // host outputs, staged on the device
     uint32_t epoch = 0;                                           // of the last render: seen[slot] == epoch <=> shown by it
@@ -262,8 +325,7 @@ struct QueryWs {
 struct NavGridWs {
     DevBufs bufs;
     float4* rec = nullptr; uint2* rbox = nullptr; size_t slots = 0;
-    uint32_t* tcnt = nullptr; uint32_t* cursor = nullptr; size_t tiles = 0;
-    uint32_t* list = nullptr; size_t list_cap = 0;
+    BinnedList tl;                                                // (tile -> slot) lists, a bin per 32 x 32-cell tile
     uint32_t* acc = nullptr; uint16_t* colg = nullptr; int8_t* state = nullptr; size_t cells = 0;
     unsigned long long* stats = nullptr;
     unsigned char* img = nullptr; size_t img_bytes = 0;
@@ -284,8 +346,7 @@ struct RayIndex {                                   // what the march needs of t
 struct RaycastWs {
     DevBufs bufs;
     float4* rec = nullptr; uint4* rbox = nullptr; uint32_t* bc = nullptr; uint32_t* over = nullptr; size_t slots = 0;
-    uint32_t* off = nullptr; uint32_t* cursor = nullptr; size_t buckets = 0;
-    uint32_t* list = nullptr; size_t list_cap = 0;
+    BinnedList bl;                                  // (bucket -> slot) lists, a bin per bucket of the table
     unsigned long long* stats = nullptr; int* cbox = nullptr;
     unsigned char* io = nullptr; size_t io_bytes = 0;
     RayIndex ix{};

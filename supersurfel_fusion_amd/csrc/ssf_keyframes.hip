@@ -25,12 +25,6 @@ namespace ssf {
 // one query: n ferns in `words` packed words, K stored keyframes; mode 0 query, 1 consider, 2 add (see k_kf_select)
 struct KfQuery { int words, n, K, max_keyframes, mode, kmax, stamp, min_gap; long long rows_used, max_rows; float new_ratio, loop_ratio; };
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- encode: grid = words of the packed code vector, 512 threads = eight waves = eight ferns ---------------------------------
 // ferns[i] = (x | y << 16, r | g << 8 | b << 16, depth_mm, 0); the words past ceil(n / 8) are the zero padding
 __global__ __launch_bounds__(512) void k_kf_encode(const uint32_t* __restrict__ rgba, const float* __restrict__ plane_depth, int W, int B,
@@ -86,11 +80,7 @@ __global__ __launch_bounds__(256) void k_kf_search(const uint32_t* __restrict__ 
 
 // ---- select (+ the add): one workgroup of 1024 -----------------------------------------------------------------------------
 __device__ __forceinline__ unsigned long long workgroup_min64(unsigned long long v, unsigned long long* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long u = __shfl_xor(v, o, 64);
-        v = u < v ? u : v;
-    }
+    v = wave_min64(v);
     __syncthreads();                                                 // (red may still be read from the previous round)
     if (lane() == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();

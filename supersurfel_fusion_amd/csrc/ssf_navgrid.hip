@@ -9,7 +9,7 @@
 //              of a workgroup are first taken in an LDS histogram (grids of up to NAV_HIST tiles) and reach the tile's global
 //              counter as one atomic per workgroup and tile.  rows_used and the number of lattice samples that exist are
 //              summed here (a row can sit in several tiles' lists, but is prepared once).
-//   * scan     k_navgrid_scan: workgroup_scan over the tile counts (64-bit total); the host reads the total once and sizes the list.
+//   * scan     launch_slots_scan (ssf_slots.hpp) over the tile counts (64-bit total); the host reads the total once and sizes the list.
 //   * fill     k_navgrid_fill: (tile -> slot) lists; a workgroup reserves its entries of a list with one returning atomic and
 //              ranks them in LDS (same histogram).  The order inside a list is arbitrary.
 //   * tile     k_navgrid_tile: workgroups of 16 waves; a tile's list is dealt in chunks of 256 records to `split` workgroups
@@ -49,12 +49,6 @@ struct NavGrid {
 struct NavView { NavGrid grid; ModelView model; };               // one kernel argument: the grid and the rows put into it
 struct NavOut { float* zmin; float* zmax; uint32_t* hits; int8_t* state; };       // nullptr = not produced
 
-__device__ __forceinline__ unsigned long long nav_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // steps per half-axis (include/ssf_navgrid.h step 3): q = ceilf(h / step)
 __device__ __forceinline__ int nav_steps(float h, float step, int max_steps) {
     const float q = ceilf(h / step);
@@ -72,13 +66,6 @@ __device__ __forceinline__ int nav_lattice_count(int n1, int n2) {
         total += (i ? 2 : 1) * (2 * j + 1);
     }
     return total;
-}
-
-__global__ __launch_bounds__(1024) void k_navgrid_scan(uint32_t* __restrict__ a, int n, uint32_t* __restrict__ cursor,
-                                                       unsigned long long* __restrict__ total) {
-    __shared__ unsigned long long tot[1];
-    workgroup_scan<1, unsigned long long>(a, n, cursor, tot);
-    if (threadIdx.x == 0) { a[n] = (uint32_t)tot[0]; *total = tot[0]; }
 }
 
 // ---- prep: one thread per slot ---------------------------------------------------------------------------------------
@@ -148,7 +135,7 @@ __global__ __launch_bounds__(256) void k_navgrid_prep(NavView nv, float4* __rest
         }
     }
     if ((int)s < nv.model.nslots) rbox[s] = box;
-    used = nav_wave_sum(used); nsamp = nav_wave_sum(nsamp);
+    used = wave_sum(used); nsamp = wave_sum(nsamp);
     if (lane() == 0) { red[0][threadIdx.x >> 6] = used; red[1][threadIdx.x >> 6] = nsamp; }
     __syncthreads();
     if (use_hist)
@@ -251,7 +238,7 @@ __global__ __launch_bounds__(1024) void k_navgrid_tile(NavGrid G, int split, con
         if (nfloor) atomicAdd(&acc.nfloor[p], nfloor);
         if (nobst) atomicAdd(&acc.nobst[p], nobst);
     }
-    accepted = nav_wave_sum(accepted);
+    accepted = wave_sum(accepted);
     if (lane() == 0) red[wv] = accepted;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -275,7 +262,7 @@ __global__ __launch_bounds__(256) void k_navgrid_cells(NavAcc acc, size_t P, int
         if (out.hits) { out.hits[2 * p] = nfloor; out.hits[2 * p + 1] = nobst; }
         if (out.state) out.state[p] = st;
     }
-    nfree = nav_wave_sum(nfree); nocc = nav_wave_sum(nocc); nunk = nav_wave_sum(nunk);
+    nfree = wave_sum(nfree); nocc = wave_sum(nocc); nunk = wave_sum(nunk);
     if (lane() == 0) { red[0][threadIdx.x >> 6] = nfree; red[1][threadIdx.x >> 6] = nocc; red[2][threadIdx.x >> 6] = nunk; }
     __syncthreads();
     if (threadIdx.x < 3) {
@@ -325,7 +312,7 @@ static void launch_navgrid_prep(hipStream_t st, const NavView& nv, float4* rec, 
     ScopedKernel sk("navgrid_prep", st);
     const int nb = nv.model.nbv + nv.model.nbo;
     if (nb > 0) hipLaunchKernelGGL(k_navgrid_prep, dim3(nb), dim3(256), 0, st, nv, rec, rbox, tcnt, stats);
-    hipLaunchKernelGGL(k_navgrid_scan, dim3(1), dim3(1024), 0, st, tcnt, nv.grid.ntx * nv.grid.nty, cursor, stats + NAV_LIST);
+    launch_slots_scan(st, tcnt, nv.grid.ntx * nv.grid.nty, cursor, stats + NAV_LIST);
 }
 static void launch_navgrid_fill(hipStream_t st, const NavView& nv, const uint2* rbox, uint32_t* cursor, uint32_t* list) {
     ScopedKernel sk("navgrid_fill", st);
@@ -351,8 +338,6 @@ static void launch_navgrid_clearance(hipStream_t st, const int8_t* state, int W,
 }  // namespace ssf
 
 // ---- host: the entry points of include/ssf_navgrid.h -----------------------------------------------------------------------
-static size_t navgrid_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // what pose NULL means (include/ssf_navgrid.h): floor-aligned, centred on the camera, snapped to the cell size
 static void navgrid_default_pose(const ssf_handle* h, float res, int W, int H, float* pose) {
     const float R9[9] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1.0f, 0.0f, 1.0f, 0.0f};
@@ -415,65 +400,47 @@ int ssf_navgrid_build(ssf_handle* h, const ssf_navgrid_params* p, const ssf_navg
     NavGridWs& w = h->navgrid;
     const size_t P = (size_t)G.W * G.H;
     const bool want_dist = out->dist2 != nullptr;
-    const size_t img_need = p->on_device ? 0 : (out->zmin ? navgrid_align(4 * P) : 0) + (out->zmax ? navgrid_align(4 * P) : 0) +
-                                               (out->hits ? navgrid_align(8 * P) : 0) + (out->state ? navgrid_align(P) : 0) +
-                                               (out->dist2 ? navgrid_align(4 * P) : 0);
+    NavOut o{out->zmin, out->zmax, out->hits, out->state};
+    int32_t* d2 = out->dist2;
+    StagedIo io;                                                     // host outputs are staged on the device
+    if (!p->on_device) {
+        io.out(out->zmin, 4 * P, &o.zmin); io.out(out->zmax, 4 * P, &o.zmax); io.out(out->hits, 8 * P, &o.hits);
+        io.out(out->state, P, &o.state); io.out(out->dist2, 4 * P, &d2);
+    }
     const size_t slots = std::max<size_t>(nv.model.nslots, 256);
     bool ok = true;
     if (slots > w.slots) {
         ok = w.bufs.grow({{(void**)&w.rec, 64 * slots}, {(void**)&w.rbox, 8 * slots}});
         if (ok) w.slots = slots;
     }
-    if (ok && (size_t)ntiles + 1 > w.tiles) {
-        ok = w.bufs.grow({{(void**)&w.tcnt, 4 * ((size_t)ntiles + 1)}, {(void**)&w.cursor, 4 * ((size_t)ntiles + 1)}});
-        if (ok) w.tiles = (size_t)ntiles + 1;
-    }
+    if (ok) ok = w.tl.reserve_bins(w.bufs, (size_t)ntiles);
     if (ok && P > w.cells) {
         ok = w.bufs.grow({{(void**)&w.acc, 16 * P}, {(void**)&w.colg, 2 * P}, {(void**)&w.state, P}});
         if (ok) w.cells = P;
     }
     if (ok && !w.stats) ok = w.bufs.grow({{(void**)&w.stats, NAV_STATS * sizeof(unsigned long long)}});
-    if (ok && img_need > w.img_bytes) {
-        ok = w.bufs.grow({{(void**)&w.img, img_need}});
-        if (ok) w.img_bytes = img_need;
-    }
+    if (ok) ok = io.reserve(w.bufs, &w.img, &w.img_bytes, io.need());
     if (!ok) { h->err = "ssf_navgrid_build: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
 
     TimerScope ts(h);
     hipStream_t st = h->stream;
-    HCK(hipMemsetAsync(w.tcnt, 0, 4 * ((size_t)ntiles + 1), st));
+    HCK(hipMemsetAsync(w.tl.off, 0, 4 * ((size_t)ntiles + 1), st));
     HCK(hipMemsetAsync(w.stats, 0, NAV_STATS * sizeof(unsigned long long), st));
-    launch_navgrid_prep(st, nv, w.rec, w.rbox, w.tcnt, w.cursor, w.stats);
+    launch_navgrid_prep(st, nv, w.rec, w.rbox, w.tl.off, w.tl.cursor, w.stats);
     HCK(hipGetLastError());
     unsigned long long total = 0;
     HCK(hipMemcpyAsync(&total, w.stats + NAV_LIST, sizeof(total), hipMemcpyDeviceToHost, st));
     HCK(hipStreamSynchronize(st));
-    if (total > 0xFFFFFFFFull) { h->err = "ssf_navgrid_build: more than 2^32 - 1 (tile, row) list entries"; return SSF_ERR_DEVICE; }
-    if (total > w.list_cap) {
-        const size_t cap = std::min<unsigned long long>(total + total / 4, 0xFFFFFFFFull);
-        if (!w.bufs.grow({{(void**)&w.list, 4 * cap}})) {
-            h->err = "ssf_navgrid_build: allocation of " + std::to_string(4 * cap) + " bytes for the tile lists failed";
-            return SSF_ERR_DEVICE;
-        }
-        w.list_cap = cap;
-    }
-    if (total > 0) { launch_navgrid_fill(st, nv, w.rbox, w.cursor, w.list); HCK(hipGetLastError()); }
+    { int rc = w.tl.reserve_list(w.bufs, total, h->err, "ssf_navgrid_build: more than 2^32 - 1 (tile, row) list entries",
+                                 "ssf_navgrid_build: allocation of ", " bytes for the tile lists failed"); if (rc) return rc; }
+    if (total > 0) { launch_navgrid_fill(st, nv, w.rbox, w.tl.cursor, w.tl.list); HCK(hipGetLastError()); }
     const NavAcc acc{w.acc, w.acc + P, w.acc + 2 * P, w.acc + 3 * P};
     HCK(hipMemsetAsync(acc.zmin, 0xFF, 4 * P, st));
     HCK(hipMemsetAsync(acc.zmax, 0, 12 * P, st));
     // parts per tile: enough workgroups for the chip when the lists are long, one when they are short
     const int split = (int)std::min<unsigned long long>(NAV_MAX_SPLIT, std::max<unsigned long long>(1, total / (16 * NAV_CHUNK)));
-    NavOut o{out->zmin, out->zmax, out->hits, out->state};
-    int32_t* d2 = out->dist2;
-    if (!p->on_device) {
-        unsigned char* q = w.img;
-        auto carve = [&](bool want, size_t bytes) { unsigned char* r = want ? q : nullptr; if (want) q += navgrid_align(bytes); return r; };
-        o.zmin = (float*)carve(out->zmin != nullptr, 4 * P); o.zmax = (float*)carve(out->zmax != nullptr, 4 * P);
-        o.hits = (uint32_t*)carve(out->hits != nullptr, 8 * P); o.state = (int8_t*)carve(out->state != nullptr, P);
-        d2 = (int32_t*)carve(out->dist2 != nullptr, 4 * P);
-    }
     if (want_dist && !o.state) o.state = w.state;                    // dist2 alone: the state is still computed, internally
-    launch_navgrid_tile(st, G, split, w.rec, w.list, w.tcnt, acc, o, w.stats);
+    launch_navgrid_tile(st, G, split, w.rec, w.tl.list, w.tl.off, acc, o, w.stats);
     HCK(hipGetLastError());
     if (want_dist) {
         launch_navgrid_clearance(st, o.state, G.W, G.H, p->max_dist_cells, p->unknown_is_obstacle != 0, w.colg, d2);
@@ -481,13 +448,7 @@ int ssf_navgrid_build(ssf_handle* h, const ssf_navgrid_params* p, const ssf_navg
     }
     unsigned long long s7[NAV_LIST] = {0, 0, 0, 0, 0, 0};
     HCK(hipMemcpyAsync(s7, w.stats, sizeof(s7), hipMemcpyDeviceToHost, st));
-    if (!p->on_device) {
-        if (out->zmin) HCK(hipMemcpyAsync(out->zmin, o.zmin, 4 * P, hipMemcpyDeviceToHost, st));
-        if (out->zmax) HCK(hipMemcpyAsync(out->zmax, o.zmax, 4 * P, hipMemcpyDeviceToHost, st));
-        if (out->hits) HCK(hipMemcpyAsync(out->hits, o.hits, 8 * P, hipMemcpyDeviceToHost, st));
-        if (out->state) HCK(hipMemcpyAsync(out->state, o.state, P, hipMemcpyDeviceToHost, st));
-        if (out->dist2) HCK(hipMemcpyAsync(out->dist2, d2, 4 * P, hipMemcpyDeviceToHost, st));
-    }
+    HCK(io.copy_out(st));
     { int rc = sync_collect(h); if (rc) return rc; }
     if (stats) {
         stats->rows_used = (int64_t)s7[NAV_ROWS]; stats->samples = (int64_t)s7[NAV_SAMPLES]; stats->samples_in_grid = (int64_t)s7[NAV_ACCEPTED];

@@ -4,7 +4,7 @@
 //   * select  k_query_select: one thread per slot of [visible rows | out-of-view span] (the two stores are read in place, never
 //             materialised).  The predicate reads the live flag, position, confidence and stamps of a slot (25 B).  Every wave
 //             stores its 64-bit ballot as one word of the MASK (nslots / 64 words); every workgroup stores two counts for its
-//             256-slot block -- selected rows and, in the out-of-view span, live rows (the count of k_render_oov_count) -- and
+//             256-slot block -- selected rows and, in the out-of-view span, live rows (the count of k_slots_oov_count) -- and
 //             reduces its selected positions to a per-block box (wave shuffles, then four LDS words per bound), which at most
 //             six integer atomicMin / atomicMax per block fold into the call's box: the order-preserving integer image of
 //             the floats makes the result exact and independent of any order.
@@ -167,7 +167,6 @@ static void launch_query_gather(hipStream_t st, const ModelView& mv, const unsig
 }  // namespace ssf
 
 // ---- host: the entry points of include/ssf_query.h -------------------------------------------------------------------------
-static size_t query_align(size_t b) { return (b + 255) & ~(size_t)255; }
 static bool query_extent_ok(float v) { return std::isfinite(v) && v >= 0.0f; }
 
 // the checks of include/ssf_query.h (every parameter, whatever the region) and the kernels' argument
@@ -273,38 +272,21 @@ int ssf_query_rows(ssf_handle* h, const ssf_query_params* p, ssf_surfels* out, i
     const size_t n = (size_t)s.n_selected;
     hipStream_t st = h->stream;
     QueryOut o{u.positions, u.colors, u.stamps, u.orientations, u.shapes, u.dims, u.confidences, out_index};
+    StagedIo io;
     if (!p->on_device) {
         // host outputs: gathered into the staging buffer, then the n selected rows are copied out
-        const size_t need = (u.positions ? query_align(12 * n) : 0) + (u.colors ? query_align(12 * n) : 0) + (u.stamps ? query_align(8 * n) : 0) +
-                            (u.orientations ? query_align(36 * n) : 0) + (u.shapes ? query_align(24 * n) : 0) + (u.dims ? query_align(8 * n) : 0) +
-                            (u.confidences ? query_align(4 * n) : 0) + (out_index ? query_align(4 * n) : 0);
-        if (need > w.rows_bytes) {
-            const size_t cap = need + need / 4;
-            if (!w.bufs.grow({{(void**)&w.rows, cap}})) {
-                h->err = "ssf_query_rows: allocation of " + std::to_string(cap) + " bytes for the selected rows failed";
-                return SSF_ERR_DEVICE;
-            }
-            w.rows_bytes = cap;
+        io.out(u.positions, 12 * n, &o.pos); io.out(u.colors, 12 * n, &o.col); io.out(u.stamps, 8 * n, &o.stamps);
+        io.out(u.orientations, 36 * n, &o.ori); io.out(u.shapes, 24 * n, &o.shape); io.out(u.dims, 8 * n, &o.dims);
+        io.out(u.confidences, 4 * n, &o.conf); io.out(out_index, 4 * n, &o.index);
+        const size_t cap = io.need() + io.need() / 4;
+        if (!io.reserve(w.bufs, &w.rows, &w.rows_bytes, cap)) {
+            h->err = "ssf_query_rows: allocation of " + std::to_string(cap) + " bytes for the selected rows failed";
+            return SSF_ERR_DEVICE;
         }
-        unsigned char* q = w.rows;
-        auto carve = [&](bool want, size_t bytes) { unsigned char* r = want ? q : nullptr; if (want) q += query_align(bytes); return r; };
-        o.pos = (float*)carve(u.positions != nullptr, 12 * n); o.col = (float*)carve(u.colors != nullptr, 12 * n);
-        o.stamps = (int32_t*)carve(u.stamps != nullptr, 8 * n); o.ori = (float*)carve(u.orientations != nullptr, 36 * n);
-        o.shape = (float*)carve(u.shapes != nullptr, 24 * n); o.dims = (float*)carve(u.dims != nullptr, 8 * n);
-        o.conf = (float*)carve(u.confidences != nullptr, 4 * n); o.index = (int32_t*)carve(out_index != nullptr, 4 * n);
     }
     launch_query_gather(st, qv.model, w.mask, w.cnt, w.bc, o);
     HCK(hipGetLastError());
-    if (!p->on_device) {
-        if (u.positions) HCK(hipMemcpyAsync(u.positions, o.pos, 12 * n, hipMemcpyDeviceToHost, st));
-        if (u.colors) HCK(hipMemcpyAsync(u.colors, o.col, 12 * n, hipMemcpyDeviceToHost, st));
-        if (u.stamps) HCK(hipMemcpyAsync(u.stamps, o.stamps, 8 * n, hipMemcpyDeviceToHost, st));
-        if (u.orientations) HCK(hipMemcpyAsync(u.orientations, o.ori, 36 * n, hipMemcpyDeviceToHost, st));
-        if (u.shapes) HCK(hipMemcpyAsync(u.shapes, o.shape, 24 * n, hipMemcpyDeviceToHost, st));
-        if (u.dims) HCK(hipMemcpyAsync(u.dims, o.dims, 8 * n, hipMemcpyDeviceToHost, st));
-        if (u.confidences) HCK(hipMemcpyAsync(u.confidences, o.conf, 4 * n, hipMemcpyDeviceToHost, st));
-        if (out_index) HCK(hipMemcpyAsync(out_index, o.index, 4 * n, hipMemcpyDeviceToHost, st));
-    }
+    HCK(io.copy_out(st));
     return sync_collect(h);
 }
 }  // extern "C"

@@ -4,14 +4,14 @@
 // What is computed is pinned, operation by operation, in include/ssf_raycast.h (the numpy restatement, a brute force over
 // rays x rows: tests/raycast_ref.py).  The winner of a ray is an integer minimum, so the order inside a bucket does not matter.  How:
 //   * prep   k_raycast_prep: one thread per slot of [visible rows | out-of-view span] (slot_row / slot_logical256; the out-of-view
-//            blocks' live offsets by k_raycast_oov_count + k_raycast_scan into own scratch).  Every slot that holds a row gets one
+//            blocks' live offsets by launch_slots_oov_offsets into own scratch).  Every slot that holds a row gets one
 //            aligned 64-byte record (c, dims.x | n, dims.y | e1, conf | e2, logical index) -- all a candidate test reads -- and a
 //            class: not indexed, grid (with its box of cells), oversize.  Rows, oversize rows and entries are summed per workgroup;
 //            the box of all indexed cells is taken by integer atomicMin / atomicMax.  The host reads these once, sizes the table
 //            (hash_bits 0: from the entry count) and the lists.
 //            k_raycast_count (booked under raycast_prep as well): the entries per bucket, through a per-workgroup LDS histogram
 //            when the table fits one (RC_HIST buckets), else by global integer atomics.
-//   * scan   k_raycast_scan: workgroup_scan over the bucket counts.
+//   * scan   launch_slots_scan (ssf_slots.hpp) over the bucket counts.
 //   * fill   k_raycast_fill: (bucket -> slot) lists, reserved per workgroup and bucket through the same histogram; oversize slots
 //            are appended to their list.
 //   * march  k_raycast_march: ONE RAY PER WAVE.  The walk's state is the same in every lane (wave-uniform); the 64 lanes test 64
@@ -39,16 +39,6 @@ enum { RC_NONE = 0u, RC_GRID = 1u, RC_OVERSIZE = 2u };
 struct RayCast { float R[9], t0[3]; float tmin, tmax, min_conf; int visible_only, n; };
 struct RayOut { float* t; int32_t* index; float* point; float* normal; float* color; };
 
-__device__ __forceinline__ unsigned long long rc_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned long long rc_wave_min(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long u = __shfl_xor(v, o, 64); v = u < v ? u : v; }
-    return v;
-}
 // the cell of a coordinate: monotone (non-decreasing) in x; clamped so that it fits 16 bits (no row is entered beyond +-RC_COORD)
 __device__ __forceinline__ int rc_cell(float x, float cell) {
     const float g = floorf(x / cell);
@@ -58,19 +48,6 @@ __device__ __forceinline__ uint32_t rc_hash(int x, int y, int z) {
     return ((uint32_t)x * 73856093u) ^ ((uint32_t)y * 19349663u) ^ ((uint32_t)z * 83492791u);
 }
 __device__ __forceinline__ float rc_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
-
-__global__ __launch_bounds__(256) void k_raycast_oov_count(ModelView mv, uint32_t* __restrict__ bc) {
-    __shared__ int part[4];
-    size_t phys;
-    const int k = block_count256(span_live(mv.oov.live, mv.oov_head, mv.oov_tail, blockIdx.x * 256u + threadIdx.x, phys), part);
-    if (threadIdx.x == 0) bc[blockIdx.x] = k;
-}
-__global__ __launch_bounds__(1024) void k_raycast_scan(uint32_t* __restrict__ a, int n, uint32_t* __restrict__ cursor,
-                                                       unsigned long long* __restrict__ total) {
-    __shared__ unsigned long long tot[1];
-    workgroup_scan<1, unsigned long long>(a, n, cursor, tot);
-    if (threadIdx.x == 0) { a[n] = (uint32_t)tot[0]; if (total) *total = tot[0]; }
-}
 
 // ---- prep: one thread per slot ---------------------------------------------------------------------------------------
 // rbox[s] = (x0 | x1 << 16, y0 | y1 << 16, z0 | z1 << 16, class), cells biased by RC_BIAS; cbox[0..2] = min, [3..5] = max cell
@@ -134,7 +111,7 @@ __global__ __launch_bounds__(256) void k_raycast_prep(ModelView mv, float cell, 
         }
     }
     if ((int)slot < mv.nslots) rbox[slot] = box;
-    n_rows = rc_wave_sum(n_rows); n_over = rc_wave_sum(n_over); n_ent = rc_wave_sum(n_ent);
+    n_rows = wave_sum(n_rows); n_over = wave_sum(n_over); n_ent = wave_sum(n_ent);
     if (lane() == 0) { red[0][threadIdx.x >> 6] = n_rows; red[1][threadIdx.x >> 6] = n_over; red[2][threadIdx.x >> 6] = n_ent; }
     __syncthreads();
     if (threadIdx.x < 3) {
@@ -260,7 +237,7 @@ __global__ __launch_bounds__(256) void k_raycast_march(RayCast q, RayIndex ix, M
             // the oversize list, in full
             for (int e = ln; e < ix.n_over; e += width) rc_test(rec, over[e], r, q, ix, best, best_slot);
             n_tested += (unsigned long long)ix.n_over;
-            unsigned long long wbest = LANE ? best : rc_wave_min(best);
+            unsigned long long wbest = LANE ? best : wave_min64(best);
             // the grid.  A non-finite O or D (an overflow of step 1) gives no candidate among the grid's rows: tt is 0, infinite or a NaN
             const float O[3] = {r.Ox, r.Oy, r.Oz}, D[3] = {r.Dx, r.Dy, r.Dz};
             bool walk = ix.cmin[0] <= ix.cmax[0] && finite3(O[0], O[1], O[2]) && finite3(D[0], D[1], D[2]);
@@ -347,7 +324,7 @@ __global__ __launch_bounds__(256) void k_raycast_march(RayCast q, RayIndex ix, M
                         for (int j = 0; j < 3; j++) { plo[j] = lo[j]; phi[j] = hi[j]; }
                     } else { plo[0] = 1; phi[0] = 0; }
                     if (LANE) wbest = best;
-                    else if (__ballot(found)) wbest = rc_wave_min(best);
+                    else if (__ballot(found)) wbest = wave_min64(best);
                     // every candidate with tt <= tb has been seen: a later one cannot be smaller, nor tie
                     if (wbest != ~0ull && __uint_as_float((uint32_t)(wbest >> 32)) <= tb) break;
                     if (!(tb < thi) || after(tb)) break;                 // (after: the ray has left the indexed cells for good)
@@ -355,7 +332,7 @@ __global__ __launch_bounds__(256) void k_raycast_march(RayCast q, RayIndex ix, M
                 }
             }
             if (!LANE) {
-                wbest = rc_wave_min(best);
+                wbest = wave_min64(best);
                 best_slot = (uint32_t)__shfl((int)best_slot, (int)(__ffsll((long long)__ballot(best == wbest)) - 1), 64);
                 best = wbest;
             }
@@ -392,7 +369,7 @@ __global__ __launch_bounds__(256) void k_raycast_march(RayCast q, RayIndex ix, M
             }
         }
     }
-    if (LANE) { n_hit = rc_wave_sum(n_hit); n_invalid = rc_wave_sum(n_invalid); n_cells = rc_wave_sum(n_cells); n_tested = rc_wave_sum(n_tested); }
+    if (LANE) { n_hit = wave_sum(n_hit); n_invalid = wave_sum(n_invalid); n_cells = wave_sum(n_cells); n_tested = wave_sum(n_tested); }
     if (lane() == 0) {
         if (n_hit) atomicAdd(&stats[RC_HIT], n_hit);
         if (n_invalid) atomicAdd(&stats[RC_INVALID], n_invalid);
@@ -405,7 +382,6 @@ __global__ __launch_bounds__(256) void k_raycast_march(RayCast q, RayIndex ix, M
 
 // ---- host: the entry points of include/ssf_raycast.h ---------------------------------------------------------------------
 using namespace ssf;
-static size_t raycast_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // (re)builds the resident index for (cell, s, hash_bits) from the model as it stands
 static int raycast_build(ssf_handle* h, float cell, float s, int hash_bits) {
@@ -426,10 +402,7 @@ static int raycast_build(ssf_handle* h, float cell, float s, int hash_bits) {
     HCK(hipMemcpyAsync(w.cbox, cbox0, sizeof(cbox0), hipMemcpyHostToDevice, st));
     {
         ScopedKernel sk("raycast_prep", st);
-        if (mv.nbo > 0) {
-            hipLaunchKernelGGL(k_raycast_oov_count, dim3(mv.nbo), dim3(256), 0, st, mv, w.bc);
-            hipLaunchKernelGGL(k_raycast_scan, dim3(1), dim3(1024), 0, st, w.bc, mv.nbo, (uint32_t*)nullptr, (unsigned long long*)nullptr);
-        }
+        launch_slots_oov_offsets(st, mv, w.bc);
         if (mv.nbv + mv.nbo > 0)
             hipLaunchKernelGGL(k_raycast_prep, dim3(mv.nbv + mv.nbo), dim3(256), 0, st, mv, cell, s, w.bc, w.rec, w.rbox, w.cbox, w.stats);
     }
@@ -440,35 +413,26 @@ static int raycast_build(ssf_handle* h, float cell, float s, int hash_bits) {
     HCK(hipMemcpyAsync(cbox, w.cbox, sizeof(cbox), hipMemcpyDeviceToHost, st));
     HCK(hipStreamSynchronize(st));
     const unsigned long long entries = s3[RC_ENTRIES];
-    if (entries > 0xFFFFFFFFull) { h->err = "ssf_raycast: more than 2^32 - 1 (cell, row) index entries"; return SSF_ERR_DEVICE; }
+    { int rc = w.bl.reserve_list(w.bufs, entries, h->err, "ssf_raycast: more than 2^32 - 1 (cell, row) index entries",
+                                 "ssf_raycast: allocation of the index's lists failed"); if (rc) return rc; }
     int bits = hash_bits;
     if (bits == 0) { bits = 10; while (bits < 24 && (1ull << bits) < entries / 32) bits++; }
     const size_t nb = (size_t)1 << bits;
-    if (nb + 1 > w.buckets) {
-        if (!w.bufs.grow({{(void**)&w.off, 4 * (nb + 1)}, {(void**)&w.cursor, 4 * (nb + 1)}})) {
-            h->err = "ssf_raycast: allocation of the index's table failed"; return SSF_ERR_DEVICE;
-        }
-        w.buckets = nb + 1;
-    }
-    if (entries > w.list_cap) {
-        const size_t cap = std::min<unsigned long long>(entries + entries / 4, 0xFFFFFFFFull);
-        if (!w.bufs.grow({{(void**)&w.list, 4 * cap}})) { h->err = "ssf_raycast: allocation of the index's lists failed"; return SSF_ERR_DEVICE; }
-        w.list_cap = cap;
-    }
+    if (!w.bl.reserve_bins(w.bufs, nb)) { h->err = "ssf_raycast: allocation of the index's table failed"; return SSF_ERR_DEVICE; }
     const uint32_t mask = (uint32_t)(nb - 1);
-    HCK(hipMemsetAsync(w.off, 0, 4 * (nb + 1), st));
+    HCK(hipMemsetAsync(w.bl.off, 0, 4 * (nb + 1), st));
     HCK(hipMemsetAsync(w.cbox + 6, 0, 4, st));                          // the oversize list's cursor
     if (entries > 0) {
         ScopedKernel sk("raycast_prep", st);
-        hipLaunchKernelGGL(k_raycast_count, dim3(mv.nslots / 256), dim3(256), 0, st, mv.nslots, mask, w.rbox, w.off);
+        hipLaunchKernelGGL(k_raycast_count, dim3(mv.nslots / 256), dim3(256), 0, st, mv.nslots, mask, w.rbox, w.bl.off);
     }
     {
         ScopedKernel sk("raycast_scan", st);
-        hipLaunchKernelGGL(k_raycast_scan, dim3(1), dim3(1024), 0, st, w.off, (int)nb, w.cursor, (unsigned long long*)nullptr);
+        launch_slots_scan(st, w.bl.off, (int)nb, w.bl.cursor, nullptr);
     }
     if (entries > 0 || s3[RC_OVER] > 0) {
         ScopedKernel sk("raycast_fill", st);
-        hipLaunchKernelGGL(k_raycast_fill, dim3(mv.nslots / 256), dim3(256), 0, st, mv.nslots, mask, w.rbox, w.cursor, w.list, w.over, (uint32_t*)(w.cbox + 6));
+        hipLaunchKernelGGL(k_raycast_fill, dim3(mv.nslots / 256), dim3(256), 0, st, mv.nslots, mask, w.rbox, w.bl.cursor, w.bl.list, w.over, (uint32_t*)(w.cbox + 6));
     }
     HCK(hipGetLastError());
     RayIndex& ix = w.ix;
@@ -528,20 +492,13 @@ int ssf_raycast(ssf_handle* h, const ssf_raycast_params* p, const float* rays, i
     const size_t N = (size_t)n;
     RayOut o{t, index, point, normal, color};
     const float* d_rays = rays;
+    StagedIo io;
     if (!p->on_device && n > 0) {
-        const size_t need = raycast_align(24 * N) + (t ? raycast_align(4 * N) : 0) + (index ? raycast_align(4 * N) : 0) +
-                            (point ? raycast_align(12 * N) : 0) + (normal ? raycast_align(12 * N) : 0) + (color ? raycast_align(12 * N) : 0);
-        if (need > w.io_bytes) {
-            if (!w.bufs.grow({{(void**)&w.io, need}})) { h->err = "ssf_raycast: allocation of the staging buffer failed"; (void)sync_collect(h); return SSF_ERR_DEVICE; }
-            w.io_bytes = need;
-        }
-        unsigned char* qd = w.io;
-        auto carve = [&](bool want, size_t bytes) { unsigned char* r = want ? qd : nullptr; if (want) qd += raycast_align(bytes); return r; };
-        d_rays = (const float*)carve(true, 24 * N);
-        o.t = (float*)carve(t != nullptr, 4 * N); o.index = (int32_t*)carve(index != nullptr, 4 * N);
-        o.point = (float*)carve(point != nullptr, 12 * N); o.normal = (float*)carve(normal != nullptr, 12 * N);
-        o.color = (float*)carve(color != nullptr, 12 * N);
-        HCK(hipMemcpyAsync((void*)d_rays, rays, 24 * N, hipMemcpyHostToDevice, st));
+        io.in(rays, 24 * N, &d_rays);
+        io.out(t, 4 * N, &o.t); io.out(index, 4 * N, &o.index); io.out(point, 12 * N, &o.point); io.out(normal, 12 * N, &o.normal);
+        io.out(color, 12 * N, &o.color);
+        if (!io.reserve(w.bufs, &w.io, &w.io_bytes, io.need())) { h->err = "ssf_raycast: allocation of the staging buffer failed"; (void)sync_collect(h); return SSF_ERR_DEVICE; }
+        HCK(io.copy_in(st));
     }
     HCK(hipMemsetAsync(w.stats + RC_HIT, 0, 4 * sizeof(unsigned long long), st));
     if (n > 0) {
@@ -549,22 +506,16 @@ int ssf_raycast(ssf_handle* h, const ssf_raycast_params* p, const float* rays, i
 #ifdef SSF_EXPERIMENTS
         if (SSF_ENV_INT("RAYCAST_LANE", 0) != 0)                        // the other arm: one ray per lane
             hipLaunchKernelGGL(k_raycast_march<true>, dim3((unsigned)std::min<size_t>((N + 255) / 256, 16384)), dim3(256), 0, st, q, w.ix, model_view(h, false),
-                               d_rays, w.rec, w.off, w.list, w.over, o, w.stats);
+                               d_rays, w.rec, w.bl.off, w.bl.list, w.over, o, w.stats);
         else
 #endif
         hipLaunchKernelGGL(k_raycast_march<false>, dim3((unsigned)std::min<size_t>((N + RC_RAYS_PER_WG - 1) / RC_RAYS_PER_WG, 16384)), dim3(256), 0, st, q, w.ix,
-                           model_view(h, false), d_rays, w.rec, w.off, w.list, w.over, o, w.stats);
+                           model_view(h, false), d_rays, w.rec, w.bl.off, w.bl.list, w.over, o, w.stats);
     }
     HCK(hipGetLastError());
     unsigned long long s4[4] = {0, 0, 0, 0};
     HCK(hipMemcpyAsync(s4, w.stats + RC_HIT, sizeof(s4), hipMemcpyDeviceToHost, st));
-    if (!p->on_device && n > 0) {
-        if (t) HCK(hipMemcpyAsync(t, o.t, 4 * N, hipMemcpyDeviceToHost, st));
-        if (index) HCK(hipMemcpyAsync(index, o.index, 4 * N, hipMemcpyDeviceToHost, st));
-        if (point) HCK(hipMemcpyAsync(point, o.point, 12 * N, hipMemcpyDeviceToHost, st));
-        if (normal) HCK(hipMemcpyAsync(normal, o.normal, 12 * N, hipMemcpyDeviceToHost, st));
-        if (color) HCK(hipMemcpyAsync(color, o.color, 12 * N, hipMemcpyDeviceToHost, st));
-    }
+    HCK(io.copy_out(st));
     { int rc = sync_collect(h); if (rc) return rc; }
     if (stats) {
         stats->rays = n; stats->rays_hit = (int64_t)s4[0]; stats->rays_invalid = (int64_t)s4[1];

@@ -7,9 +7,9 @@
 //            CONSERVATIVE pixel box of the disc; every 16 x 16 screen tile the box touches gets one integer atomic count.
 //            A slot's number orders like the logical index ([visible | out-of-view], ssf_get_model's order), so the slot
 //            number breaks depth ties in the key; the out-of-view rows' logical index comes from an exclusive scan of their
-//            live flags (k_render_oov_count + k_render_scan into own scratch: the handle's Counters and d_bc_oov are not
+//            live flags (launch_slots_oov_offsets into own scratch: the handle's Counters and d_bc_oov are not
 //            touched).  Slot -> row, the rank inside a block and the scan are the helpers of ssf_slots.hpp (k_render_prep).
-//   * scan   k_render_scan again: exclusive scan of the tile counts (one workgroup, 64-bit total); the host reads the total
+//   * scan   launch_slots_scan: exclusive scan of the tile counts (one workgroup, 64-bit total); the host reads the total
 //            once and sizes the list buffer.
 //   * fill   k_render_fill: (tile -> slot) lists with one returning atomic per list entry; the order inside a list is arbitrary.
 //   * tile   k_render_tile: one 256-thread workgroup per tile, one pixel per thread: the tile's records are staged through
@@ -27,29 +27,6 @@ namespace ssf {
 struct RenderCam { float R[9], t[3]; float fx, fy, cx, cy; int W, H, ntx, nty; float zmin, zmax, min_conf, s, k; };
 struct RenderView { RenderCam cam; ModelView model; };           // one kernel argument: the camera and the rows drawn
 struct RenderOut { float* depth; int32_t* index; uint8_t* rgb8; float* color; float* normal; };      // nullptr = not produced
-
-__device__ __forceinline__ unsigned long long rsum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// ---- out-of-view rows: live counts per 256-slot block, then an exclusive scan (k_render_scan) --------------------------
-__global__ __launch_bounds__(256) void k_render_oov_count(ModelView mv, uint32_t* __restrict__ bc) {
-    __shared__ int part[4];
-    size_t phys;
-    const int k = block_count256(span_live(mv.oov.live, mv.oov_head, mv.oov_tail, blockIdx.x * 256u + threadIdx.x, phys), part);
-    if (threadIdx.x == 0) bc[blockIdx.x] = k;
-}
-
-// exclusive scan of n counts in place (one workgroup of 1024); a[n] = the total (low 32 bits), cursor (nullable) = a copy of
-// the offsets, *total = the 64-bit total (a list longer than 2^32 - 1 entries is refused by the host, never wrapped)
-__global__ __launch_bounds__(1024) void k_render_scan(uint32_t* __restrict__ a, int n, uint32_t* __restrict__ cursor,
-                                                      unsigned long long* __restrict__ total) {
-    __shared__ unsigned long long tot[1];
-    workgroup_scan<1, unsigned long long>(a, n, cursor, tot);
-    if (threadIdx.x == 0) { a[n] = (uint32_t)tot[0]; *total = tot[0]; }
-}
 
 // ---- prep: one thread per slot ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_render_prep(RenderView rv, const uint32_t* __restrict__ bc, float4* __restrict__ rec,
@@ -208,7 +185,7 @@ __global__ __launch_bounds__(256) void k_render_tile(RenderView rv, const float4
         }
         if (out.normal) { out.normal[3 * p] = m0; out.normal[3 * p + 1] = m1; out.normal[3 * p + 2] = m2; }
     }
-    const unsigned long long f = rsum_u64(frag), fl = rsum_u64(filled), sh = rsum_u64(shown);
+    const unsigned long long f = wave_sum<unsigned long long>(frag), fl = wave_sum<unsigned long long>(filled), sh = wave_sum<unsigned long long>(shown);
     if (lane() == 0) { red[0][threadIdx.x >> 6] = f; red[1][threadIdx.x >> 6] = fl; red[2][threadIdx.x >> 6] = sh; }
     __syncthreads();
     if (threadIdx.x < 3) {
@@ -224,13 +201,10 @@ static void launch_render_prep(hipStream_t st, const RenderView& rv, uint32_t* b
                                uint32_t* cursor, unsigned long long* total) {
     ScopedKernel sk("render_prep", st);
     const ModelView& mv = rv.model;
-    if (mv.nbo > 0) {
-        hipLaunchKernelGGL(k_render_oov_count, dim3(mv.nbo), dim3(256), 0, st, mv, bc);
-        hipLaunchKernelGGL(k_render_scan, dim3(1), dim3(1024), 0, st, bc, mv.nbo, (uint32_t*)nullptr, total);
-    }
+    launch_slots_oov_offsets(st, mv, bc);
     if (mv.nbv + mv.nbo > 0)
         hipLaunchKernelGGL(k_render_prep, dim3(mv.nbv + mv.nbo), dim3(256), 0, st, rv, bc, rec, rbox, logical, tcnt);
-    hipLaunchKernelGGL(k_render_scan, dim3(1), dim3(1024), 0, st, tcnt, rv.cam.ntx * rv.cam.nty, cursor, total);
+    launch_slots_scan(st, tcnt, rv.cam.ntx * rv.cam.nty, cursor, total);
 }
 static void launch_render_fill(hipStream_t st, const RenderView& rv, const uint2* rbox, uint32_t* cursor, uint32_t* list) {
     ScopedKernel sk("render_fill", st);
@@ -249,8 +223,6 @@ static void launch_render_tile(hipStream_t st, const RenderView& rv, const float
 
 // ---- host: the entry points of include/ssf_render.h ------------------------------------------------------------------------
 extern "C" {
-static size_t render_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int ssf_render_default_params(const ssf_handle* h, ssf_render_params* p) {
     if (!h || !p) return SSF_ERR_INVALID_ARG;
     std::memset(p, 0, sizeof(*p));
@@ -285,8 +257,12 @@ int ssf_render_model(ssf_handle* h, const ssf_render_params* p, float* depth, in
 
     RenderWs& w = h->render;
     const size_t P = (size_t)K.W * K.H;
-    const size_t img_need = p->on_device ? 0 : (depth ? render_align(4 * P) : 0) + (index ? render_align(4 * P) : 0) +
-                                               (rgb8 ? render_align(3 * P) : 0) + (color ? render_align(12 * P) : 0) + (normal ? render_align(12 * P) : 0);
+    RenderOut o{depth, index, rgb8, color, normal};
+    StagedIo io;                                                     // host outputs are staged on the device
+    if (!p->on_device) {
+        io.out(depth, 4 * P, &o.depth); io.out(index, 4 * P, &o.index); io.out(rgb8, 3 * P, &o.rgb8);
+        io.out(color, 12 * P, &o.color); io.out(normal, 12 * P, &o.normal);
+    }
     const size_t slots = std::max<size_t>(rv.model.nslots, 256);
     bool ok = true;
     if (ok && slots > w.slots) {
@@ -294,55 +270,29 @@ int ssf_render_model(ssf_handle* h, const ssf_render_params* p, float* depth, in
                           {(void**)&w.seen, 4 * slots}, {(void**)&w.bc, 4 * (slots / 256 + 1)}});
         if (ok) { w.slots = slots; w.epoch = 0; HCK(hipMemsetAsync(w.seen, 0, 4 * slots, h->stream)); }
     }
-    if (ok && (size_t)ntiles + 1 > w.tiles) {
-        ok = w.bufs.grow({{(void**)&w.tcnt, 4 * ((size_t)ntiles + 1)}, {(void**)&w.cursor, 4 * ((size_t)ntiles + 1)}});
-        if (ok) w.tiles = (size_t)ntiles + 1;
-    }
+    if (ok) ok = w.tl.reserve_bins(w.bufs, (size_t)ntiles);
     if (ok && !w.stats) ok = w.bufs.grow({{(void**)&w.stats, 4 * sizeof(unsigned long long)}});
-    if (ok && img_need > w.img_bytes) {
-        ok = w.bufs.grow({{(void**)&w.img, img_need}});
-        if (ok) w.img_bytes = img_need;
-    }
+    if (ok) ok = io.reserve(w.bufs, &w.img, &w.img_bytes, io.need());
     if (!ok) { h->err = "ssf_render_model: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
     if (++w.epoch == 0) { HCK(hipMemsetAsync(w.seen, 0, 4 * w.slots, h->stream)); w.epoch = 1; }
 
     TimerScope ts(h);
     hipStream_t st = h->stream;
-    HCK(hipMemsetAsync(w.tcnt, 0, 4 * ((size_t)ntiles + 1), st));
+    HCK(hipMemsetAsync(w.tl.off, 0, 4 * ((size_t)ntiles + 1), st));
     HCK(hipMemsetAsync(w.stats, 0, 4 * sizeof(unsigned long long), st));
-    launch_render_prep(st, rv, w.bc, w.rec, w.rbox, w.logical, w.tcnt, w.cursor, w.stats + 3);
+    launch_render_prep(st, rv, w.bc, w.rec, w.rbox, w.logical, w.tl.off, w.tl.cursor, w.stats + 3);
     HCK(hipGetLastError());
     unsigned long long total = 0;
     HCK(hipMemcpyAsync(&total, w.stats + 3, sizeof(total), hipMemcpyDeviceToHost, st));
     HCK(hipStreamSynchronize(st));
-    if (total > 0xFFFFFFFFull) { h->err = "ssf_render_model: more than 2^32 - 1 (tile, row) list entries"; return SSF_ERR_DEVICE; }
-    if (total > w.list_cap) {
-        const size_t cap = std::min<unsigned long long>(total + total / 4, 0xFFFFFFFFull);
-        if (!w.bufs.grow({{(void**)&w.list, 4 * cap}})) {
-            h->err = "ssf_render_model: allocation of " + std::to_string(4 * cap) + " bytes for the tile lists failed";
-            return SSF_ERR_DEVICE;
-        }
-        w.list_cap = cap;
-    }
-    if (total > 0) { launch_render_fill(st, rv, w.rbox, w.cursor, w.list); HCK(hipGetLastError()); }
-    RenderOut o{depth, index, rgb8, color, normal};
-    if (!p->on_device) {
-        unsigned char* q = w.img;
-        auto carve = [&](bool want, size_t bytes) { unsigned char* r = want ? q : nullptr; if (want) q += render_align(bytes); return r; };
-        o.depth = (float*)carve(depth != nullptr, 4 * P); o.index = (int32_t*)carve(index != nullptr, 4 * P);
-        o.rgb8 = carve(rgb8 != nullptr, 3 * P); o.color = (float*)carve(color != nullptr, 12 * P); o.normal = (float*)carve(normal != nullptr, 12 * P);
-    }
-    launch_render_tile(st, rv, w.rec, w.rbox, w.logical, w.list, w.tcnt, o, w.seen, w.epoch, w.stats);
+    { int rc = w.tl.reserve_list(w.bufs, total, h->err, "ssf_render_model: more than 2^32 - 1 (tile, row) list entries",
+                                 "ssf_render_model: allocation of ", " bytes for the tile lists failed"); if (rc) return rc; }
+    if (total > 0) { launch_render_fill(st, rv, w.rbox, w.tl.cursor, w.tl.list); HCK(hipGetLastError()); }
+    launch_render_tile(st, rv, w.rec, w.rbox, w.logical, w.tl.list, w.tl.off, o, w.seen, w.epoch, w.stats);
     HCK(hipGetLastError());
     unsigned long long st3[3] = {0, 0, 0};
     HCK(hipMemcpyAsync(st3, w.stats, sizeof(st3), hipMemcpyDeviceToHost, st));
-    if (!p->on_device) {
-        if (depth) HCK(hipMemcpyAsync(depth, o.depth, 4 * P, hipMemcpyDeviceToHost, st));
-        if (index) HCK(hipMemcpyAsync(index, o.index, 4 * P, hipMemcpyDeviceToHost, st));
-        if (rgb8) HCK(hipMemcpyAsync(rgb8, o.rgb8, 3 * P, hipMemcpyDeviceToHost, st));
-        if (color) HCK(hipMemcpyAsync(color, o.color, 12 * P, hipMemcpyDeviceToHost, st));
-        if (normal) HCK(hipMemcpyAsync(normal, o.normal, 12 * P, hipMemcpyDeviceToHost, st));
-    }
+    HCK(io.copy_out(st));
     { int rc = sync_collect(h); if (rc) return rc; }
     if (stats) { stats->fragments = (int64_t)st3[0]; stats->pixels_filled = (int64_t)st3[1]; stats->rows_shown = (int64_t)st3[2]; stats->list_entries = (int64_t)total; }
     return SSF_OK;

@@ -1,8 +1,14 @@
 // ssf_slots.hpp -- device helpers of the kernels that walk the model one thread per SLOT (ModelView, ssf_device.hpp) and of the
-// store upkeep (out-of-view compaction, re-homing): the slot -> row map, live counts and ranks inside a 256-thread block, and
-// the one-workgroup exclusive scan that turns per-block counts into offsets.  Device-only; included by ssf_render.hip,
-// ssf_query.hip, ssf_navgrid.hip, ssf_graph.hip and ssf_track_fuse.hip.  (The per-frame kernels -- ICP, association, fuse, partition, row move, k_bin_* -- keep
-// their own ballots and scans, tuned to the instruction; they do not go through these.)
+// store upkeep (out-of-view compaction, re-homing): the slot -> row map, live counts and ranks inside a 256-thread block, the
+// integer wave reductions, and the one-workgroup exclusive scan that turns per-block counts into offsets.  Included by
+// ssf_render.hip, ssf_query.hip, ssf_navgrid.hip, ssf_raycast.hip, ssf_graph.hip, ssf_keyframes.hip and ssf_track_fuse.hip.
+// The kernels shared by several of these files live in ssf_slots.hip (the library is built without relocatable device
+// code), reached through the host launchers declared at the end: k_slots_scan -- the scan of render's and the navigation grid's
+// tile counts, the ray cast's bucket counts and of every out-of-view live count; k_slots_scan32, the same body with 32-bit sums
+// for the graph's sort histograms -- and k_slots_oov_count.  What does NOT go through them: k_query_scan (two counters plus the record), k_oov_scan and k_rehome_scan
+// (a device-side n, store upkeep), k_bin_scan, everything of the per-frame kernels (ICP, association, fuse, partition, row move,
+// k_bin_*: their own ballots and scans, tuned to the instruction) and of ssf_extract.hip, and the fill kernels (render's plain
+// one, the LDS-histogram ones of the navigation grid and the ray cast with their different bin functions: measured choices).
 #pragma once
 #include "ssf_device.hpp"
 
@@ -10,6 +16,19 @@ namespace ssf {
 
 __device__ __forceinline__ int lane() { return threadIdx.x & 63; }
 __device__ __forceinline__ bool finite3(float a, float b, float c) { return isfinite(a) && isfinite(b) && isfinite(c); }
+
+// the wave's sum of an integer, and its 64-bit minimum, told to every lane (integers: no order can change the result)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long u = __shfl_xor(v, o, 64); v = u < v ? u : v; }
+    return v;
+}
 
 // the order-preserving unsigned image of a float (no NaN comes here): a < b <=> enc(a) < enc(b)
 __host__ __device__ __forceinline__ uint32_t float_order_bits(uint32_t u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
@@ -100,5 +119,16 @@ __device__ __forceinline__ void workgroup_scan(uint32_t* __restrict__ a, int n, 
         __syncthreads();
     }
 }
+
+// ---- the shared kernels' launchers (ssf_slots.hip).  They open no ScopedKernel: the caller's scope books them ---------------
+#pragma GCC visibility push(hidden)
+// exclusive scan of n counts in place by one workgroup; a[n] = the total's low 32 bits, cursor (nullable) = a copy of the
+// offsets, *total (nullable) = the 64-bit total (a list longer than 2^32 - 1 entries is refused by the host, never wrapped)
+void launch_slots_scan(hipStream_t st, uint32_t* a, int n, uint32_t* cursor, unsigned long long* total);
+// the same with 32-bit running sums, for a total that is known to fit (the graph's sort: ssf_slots.hip says why it is kept)
+void launch_slots_scan32(hipStream_t st, uint32_t* a, int n);
+// bc[nbo + 1] = the out-of-view blocks' live offsets (slot_logical256's bc): the live counts, then their scan; nothing for nbo == 0
+void launch_slots_oov_offsets(hipStream_t st, const ModelView& mv, uint32_t* bc);
+#pragma GCC visibility pop
 
 }  // namespace ssf

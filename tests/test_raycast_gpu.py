@@ -311,6 +311,30 @@ def test_the_working_buffers_grow(product_lib):
     check(f, "small again", rr.scene_rays(m, 64, 0), pose=rr.scene_pose(0), model=m, **rr.scene_kw(0))
 
 
+def test_more_out_of_view_blocks_than_one_round_of_the_scan(product_lib):
+    """270 000 rows, 256 of them visible: 1054 out-of-view blocks, so the one-workgroup scan of their live counts (1024 a round) takes
+    a second round, and the logical index of a row of the last blocks comes from the second round's offsets.  The rows are 250 copies
+    of a hand-built model of 1080, each copy 4 m further along z; eight rays come down the normals of rows of the last copy.  Then
+    513 rows on the same handle: offsets beyond the new block count are stale and must not be read."""
+    n, tile, nv = 270000, 1080, 256
+    base = rr.hand_model(tile, 3)
+    m = {name: np.ascontiguousarray(np.tile(a, (n // tile,) + (1,) * (a.ndim - 1))) for name, a in base.items()}
+    m["positions"][:, 2] += np.repeat(np.arange(n // tile, dtype=np.float32) * np.float32(4.0), tile)
+    f = handle(product_lib, nb_supersurfels_max=n)
+    f.set_model(m, nv, 100)
+    first_of_round_two = nv + 1024 * 256
+    targets = [k for k in range(n - 1, n - 400, -1) if abs(m["positions"][k, 0]) < 1e3][:8]
+    assert len(targets) == 8 and min(targets) >= first_of_round_two
+    c, nrm = m["positions"][targets].astype(np.float64), m["orientations"][targets, 6:9].astype(np.float64)
+    rays = np.concatenate([c + 0.4 * nrm, -nrm], axis=1).astype(np.float32)
+    got = check(f, "270 000 rows", rays, pose=rr.IDENTITY, model=m, t_min=0.05, t_max=8.0)
+    assert got["stats"]["rays_hit"] == 8 and got["stats"]["rows_indexed"] == n and (got["index"] >= first_of_round_two).all(), got["index"]
+    m2 = rr.hand_model(513, 0)
+    f.set_model(m2, 257, 100)
+    check(f, "513 rows after 270 000", rr.scene_rays(m2, 257, 0), pose=rr.scene_pose(0), model=m2, **rr.scene_kw(0))
+    f.close()
+
+
 # ---- a store with holes; a real map --------------------------------------------------------------------------------------------
 def test_a_store_with_holes_and_its_compaction(product_lib):
     """30 frames of a camera that pans 3 degrees per frame for 15 frames and back (true pose as the prior): rows leave the view and
