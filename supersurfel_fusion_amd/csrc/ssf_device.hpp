@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include <cstddef>
 #include "ssf_math.hpp"
+#include "ssf_mailbox.hpp"
 #include "../../include/ssf.h"
 #include "../../include/ssf_input.h"
 #include "../../include/ssf_dynamic.h"
@@ -87,7 +88,7 @@ struct Counters {
     // the source of the per-frame RCCL all-gather of the shard sizes
     int last[5];
 };
-#define SSF_MAX_RANKS 64
+static_assert(sizeof(Counters) == 4 * MAILBOX_COUNTER_WORDS, "the counter record of the mailbox (ssf_mailbox.hpp)");
 
 struct Cam { float fx, fy, cx, cy; int W, H; };
 struct Rt { M3 R; V3 t; };
@@ -211,8 +212,6 @@ struct Mailbox {
 #ifndef SSF_ICP_REPLICAS
 #define SSF_ICP_REPLICAS 8
 #endif
-// word w of Mailbox::icp_rec for payload p[0..29] (29 sums + checksum) and sequence number seq
-#define SSF_ICP_REC_WORD(w, p, seq) ((((w) & 7) == 7) ? (unsigned long long)(seq) : ((7 * ((w) >> 3) + ((w) & 7)) < 30 ? (unsigned long long)(p)[7 * ((w) >> 3) + ((w) & 7)] : 0ull))
 
 // ---- extract stage (ssf_extract.hip) -----------------------------------------------------------
 // every extract launch processes the nb frames of a batch (m, frame, best, matched, dynamic_mask = slot 0)

@@ -57,15 +57,10 @@ int comm_counts(ssf_handle* h) {
         int rc = wait_seq(h, &h->mb_host->all_seq, h->all_seq);
         if (rc) return rc;
         const int n = 5 * h->cfg.nranks;
-        for (int attempt = 0;; attempt++) {
-            unsigned long long check = h->all_seq;
-            for (int i = 0; i < n; i++) {
-                const int v = __atomic_load_n(&h->mb_host->all_cnt[i], __ATOMIC_RELAXED);
-                h->all_cnt[i] = v; check += (unsigned long long)(unsigned int)v;
-            }
-            if (check == __atomic_load_n(&h->mb_host->all_check, __ATOMIC_ACQUIRE)) break;
+        int w[MAILBOX_SHARD_WORDS];
+        for (int attempt = 0; !int_record_read(h->mb_host->all_cnt, n, &h->mb_host->all_check, h->all_seq, w); attempt++)
             if (attempt > 100000) { h->err = "shard-size mailbox record failed its checksum"; return SSF_ERR_DEVICE; }
-        }
+        for (int i = 0; i < n; i++) h->all_cnt[i] = w[i];
         h->all_pending = false; h->all_valid = true;
     }
     long long gm = 0, gv = 0, off = 0;

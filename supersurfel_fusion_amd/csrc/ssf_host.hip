@@ -698,24 +698,12 @@ struct IcpWaiter { bool waiting = false; IcpGo* slot = nullptr; unsigned long lo
 // is waiting.  Before the stream is drained it is told to leave (waiter->waiting = false: the next iteration, if any, is launched
 // afresh): it would otherwise hold the stream until its own bound expires.
 static int icp_fetch(ssf_handle* h, unsigned long long seq, IcpWaiter* waiter = nullptr) {
-    // the record is five 64-byte lines that each end in the sequence number (Mailbox::icp_rec): accept it when all
-    // five carry `seq` and the checksum over the payload matches; anything else is a record still in flight
+    // (icp_record_read, ssf_mailbox.hpp: anything but a whole record `seq` is a record still in flight)
     const volatile unsigned long long* rec = h->mb_host->icp_rec;
     auto t0 = std::chrono::steady_clock::now();
     bool drained = false;                     // the stream has been synchronised once after a timeout
     for (unsigned long long spins = 0;; spins++) {
-        bool ok = true;
-        for (int j = 0; j < 5 && ok; j++) ok = __atomic_load_n(&rec[8 * j + 7], __ATOMIC_ACQUIRE) == seq;
-        if (ok) {
-            unsigned long long check = seq, w29 = 0;
-            for (int p = 0; p < 30; p++) {
-                const unsigned long long v = __atomic_load_n(&rec[8 * (p / 7) + p % 7], __ATOMIC_RELAXED);
-                if (p < 29) { h->h_icp_local[p] = (long long)v; check += v; } else w29 = v;
-            }
-            bool still = true;                          // the lines must not have been overwritten while we read them
-            for (int j = 0; j < 5 && still; j++) still = __atomic_load_n(&rec[8 * j + 7], __ATOMIC_ACQUIRE) == seq;
-            if (still && check == w29) break;
-        }
+        if (icp_record_read(rec, seq, h->h_icp_local)) break;
         if ((spins & 0xFFFF) == 0xFFFF && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > (drained ? 1.0 : 5.0)) {
             // Nothing for 5 s.  The device may simply be slow or stalled (a cold box, a debugger, another tenant): drain the
             // stream -- however long that takes -- and look again before calling it an error; only a record that is
@@ -932,87 +920,83 @@ static int fuse_begin(ssf_handle* h, int migrate) {
     h->model_gen++;
     return SSF_OK;
 }
-static int fuse_end(ssf_handle* h, const int32_t* d_table, ssf_frame_result* out) {
+// ---- the end of the fuse stage, step by step (fuse_end below) ---------------------------------------------------------------
+// The rows the move kernel writes to the new visible array are the rows the next frame's first ICP iteration reads, under a
+// transform that is known now (the pose just estimated, when the caller supplies no prior): if that frame's extract has
+// finished, the move kernel accumulates the record on the way (k_move_rows<true>).  have_next: it does, with next / next_pv.
+static int fuse_next_icp(ssf_handle* h, NextIcp& next, P2PView& next_pv, bool& have_next) {
+    have_next = false;
+    if (!(h->icp_ahead && (h->p2p.on || h->ahead_tuner.current() == 1) && icp_is_one_launch(h) && h->cfg.icp_iter > 0 && !h->pending.empty()))
+        return SSF_OK;
+    ExtractCtx& nc = h->ctx[h->pending.front().first];
+    const int nslot = h->pending.front().second;
+    const bool multi = h->ctx.size() > 1;         // one context: extract ran on the track stream itself
+    // Only when that frame's extract HAS finished (round 5).  Frames of the batch being consumed are ready by construction;
+    // at a batch boundary the next context's event is asked.  Until round 4 the track stream was made to wait for it here --
+    // in a sequence's fill phase that parked the row moves behind a batch that was still 100-200 us from done, and the
+    // driver's 20-frame form ran 4 % slower with the fusion than without (7680-7730 against 8030-8060 frames/s, same box,
+    // alternated twice: profiles/track_chain_r05.txt); in the steady state the next batch is ready and nothing changes.
+    bool ready = nc.launched && (!multi || nc.waited);
+    // (peer-to-peer shards: every rank must take the SAME form for a frame -- a rank that fused would spin in the exchange until
+    //  its peer's later launch publishes -- so there the decision stays host-deterministic: wait for the event, as until round 4)
+    if (nc.launched && !ready && (h->icp_ahead_mode == 2 || h->p2p.on || hipEventQuery(nc.ev_done) == hipSuccess)) {
+        HCK(hipStreamWaitEvent(h->stream, nc.ev_done, 0)); nc.waited = true; ready = true;
+    }
+    (void)hipGetLastError();                      // (hipErrorNotReady of the query is not an error)
+    if (!ready) return SSF_OK;
+    const FrameMaps nm = batch_slot(nc.maps, nslot);
+    IcpLoop first;
+    icp_start_from(first, h->pose);
+    next = NextIcp{h->cam, nm.pix2, nm.fpack, icp_transform(first), h->d_icp_replicas, h->d_tickets + 8, h->d_icp, h->mb_dev, ++h->icp_seq};
+    if (h->p2p.on) next_pv = p2p_view(h, ++h->p2p.seq_icp);
+    h->ahead.valid = true; h->ahead.seq = next.seq; h->ahead.ctx = &nc; h->ahead.slot = nslot;
+    h->ahead.stamp = h->stamp + 1; h->ahead.pose = h->pose;
+    have_next = true;
+    return SSF_OK;
+}
+// The frame's last launches: arrivals from other shards, the row moves (or the first frame's copy), and -- a sharded map -- the
+// exchange of the shard sizes; counter record `seq` is published on the way.
+static int fuse_launch_moves(ssf_handle* h, const int32_t* d_table, unsigned long long seq) {
     SurfelSoA& M = h->model[h->mcur];
-    const unsigned long long seq = ++h->cnt_seq;
-    h->fusing = false;                           // (also on every error path below: the frame is over either way)
-    if (!h->fuse_first) {
-        const PartitionWs& ws = h->fuse_ws;
-        if (h->fuse_migrate && d_table)
-            launch_migrate_in(h->stream, M, d_table, h->S, h->cfg.nb_supersurfels_max, h->d_cnt, h->shard, h->classify, h->pose, h->stamp,
-                              h->d_state, ws);
-        // The rows the move kernel writes to the new visible array are the rows the next frame's first ICP iteration
-        // reads, under a transform that is known now (the pose just estimated, when the caller supplies no prior):
-        // if that frame's extract has finished, the move kernel accumulates the record on the way (k_move_rows<true>).
-        NextIcp next{};
-        P2PView next_pv{};
-        bool have_next = false;
-        if (h->icp_ahead && (h->p2p.on || h->ahead_tuner.current() == 1) && icp_is_one_launch(h) && h->cfg.icp_iter > 0 && !h->pending.empty()) {
-            ExtractCtx& nc = h->ctx[h->pending.front().first];
-            const int nslot = h->pending.front().second;
-            const bool multi = h->ctx.size() > 1;         // one context: extract ran on the track stream itself
-            // Only when that frame's extract HAS finished (round 5).  Frames of the batch being consumed are ready by construction;
-            // at a batch boundary the next context's event is asked.  Until round 4 the track stream was made to wait for it here --
-            // in a sequence's fill phase that parked the row moves behind a batch that was still 100-200 us from done, and the
-            // driver's 20-frame form ran 4 % slower with the fusion than without (7680-7730 against 8030-8060 frames/s, same box,
-            // alternated twice: profiles/track_chain_r05.txt); in the steady state the next batch is ready and nothing changes.
-            bool ready = nc.launched && (!multi || nc.waited);
-            // (peer-to-peer shards: every rank must take the SAME form for a frame -- a rank that fused would spin in the exchange until
-            //  its peer's later launch publishes -- so there the decision stays host-deterministic: wait for the event, as until round 4)
-            if (nc.launched && !ready && (h->icp_ahead_mode == 2 || h->p2p.on || hipEventQuery(nc.ev_done) == hipSuccess)) {
-                HCK(hipStreamWaitEvent(h->stream, nc.ev_done, 0)); nc.waited = true; ready = true;
-            }
-            (void)hipGetLastError();                      // (hipErrorNotReady of the query is not an error)
-            if (ready) {
-                const FrameMaps nm = batch_slot(nc.maps, nslot);
-                IcpLoop first;
-                icp_start_from(first, h->pose);
-                next = NextIcp{h->cam, nm.pix2, nm.fpack, icp_transform(first), h->d_icp_replicas, h->d_tickets + 8, h->d_icp, h->mb_dev, ++h->icp_seq};
-                if (h->p2p.on) next_pv = p2p_view(h, ++h->p2p.seq_icp);
-                h->ahead.valid = true; h->ahead.seq = next.seq; h->ahead.ctx = &nc; h->ahead.slot = nslot;
-                h->ahead.stamp = h->stamp + 1; h->ahead.pose = h->pose;
-                have_next = true;
-            }
-        }
-        // move: the host continues once the counters arrive (published by the fuse launch), the row moves of this
-        // frame overlap the host-side launch work of the next one (stream order keeps every later reader of the
-        // model behind them)
-        // (a sharded map: the shard sizes of all ranks are exchanged now -- the counters are final -- so that the next
-        // frame does not have to wait for the row moves to learn them)
-        if (exchanges_natively(h)) { int rg = comm_gather_counts(h); if (rg) return rg; }
-        launch_move_rows(h->stream, M, h->model[h->mcur ^ 1], h->oov[h->ocur], h->n_visible + (h->fuse_migrate ? 2 : 1) * h->S, h->oov_tail - h->oov_head,
-                         h->d_state, h->d_state_oov, h->d_bc_oov, ws, h->d_cnt, h->mb_dev, seq, have_next ? &next : nullptr,
-                         have_next && h->p2p.on ? &next_pv : nullptr, h->fuse_totals.from_tot ? &h->fuse_totals : nullptr);
-        h->mcur ^= 1;
-    } else {
+    if (h->fuse_first) {
         launch_first_frame(h->stream, M, h->cc->frame, h->pose, h->S, h->cfg.nb_supersurfels_max, h->shard, h->d_cnt);
         launch_publish_counts(h->stream, h->d_cnt, 0, h->mb_dev, seq);
         if (exchanges_natively(h)) { int rg = comm_gather_counts(h); if (rg) return rg; }
+        return SSF_OK;
     }
-    HCK(hipGetLastError());
-    { int rr = retire_active(h); if (rr) return rr; }     // last reader of this frame's buffers is enqueued
-    h->stamp_bias = 1;                                     // the frame being fused still holds h->stamp
-    while (h->seq_next < h->seq_n && !h->ctx[h->open_ctx].launched) {      // see seq_rgb
-        int rs = seq_submit(h);
-        if (rs) { h->stamp_bias = 0; return rs; }
-    }
-    h->stamp_bias = 0;
+    const PartitionWs& ws = h->fuse_ws;
+    if (h->fuse_migrate && d_table)
+        launch_migrate_in(h->stream, M, d_table, h->S, h->cfg.nb_supersurfels_max, h->d_cnt, h->shard, h->classify, h->pose, h->stamp,
+                          h->d_state, ws);
+    NextIcp next{};
+    P2PView next_pv{};
+    bool have_next;
+    { int rn = fuse_next_icp(h, next, next_pv, have_next); if (rn) return rn; }
+    // move: the host continues once the counters arrive (published by the fuse launch), the row moves of this
+    // frame overlap the host-side launch work of the next one (stream order keeps every later reader of the
+    // model behind them)
+    // (a sharded map: the shard sizes of all ranks are exchanged now -- the counters are final -- so that the next
+    // frame does not have to wait for the row moves to learn them)
+    if (exchanges_natively(h)) { int rg = comm_gather_counts(h); if (rg) return rg; }
+    launch_move_rows(h->stream, M, h->model[h->mcur ^ 1], h->oov[h->ocur], h->n_visible + (h->fuse_migrate ? 2 : 1) * h->S, h->oov_tail - h->oov_head,
+                     h->d_state, h->d_state_oov, h->d_bc_oov, ws, h->d_cnt, h->mb_dev, seq, have_next ? &next : nullptr,
+                     have_next && h->p2p.on ? &next_pv : nullptr, h->fuse_totals.from_tot ? &h->fuse_totals : nullptr);
+    h->mcur ^= 1;
+    return SSF_OK;
+}
+// wait for counter record `seq`, read it into c and take the handle's mirrors of the model's sizes from it
+static int fuse_read_counters(ssf_handle* h, unsigned long long seq, Counters& c) {
     int rc = wait_seq(h, &h->mb_host->cnt_seq, seq);
     if (rc) return rc;
-    Counters c;
-    for (int attempt = 0;; attempt++) {
-        unsigned long long check = seq;
-        const int* srcw = reinterpret_cast<const int*>(&h->mb_host->cnt);
-        int* dstw = reinterpret_cast<int*>(&c);
-        for (int i = 0; i < (int)(sizeof(Counters) / sizeof(int)); i++) {
-            dstw[i] = __atomic_load_n(&srcw[i], __ATOMIC_RELAXED);
-            check += (unsigned long long)(unsigned int)dstw[i];
-        }
-        if (check == __atomic_load_n(&h->mb_host->cnt_check, __ATOMIC_ACQUIRE)) break;
+    for (int attempt = 0; !int_record_read(reinterpret_cast<const int*>(&h->mb_host->cnt), MAILBOX_COUNTER_WORDS, &h->mb_host->cnt_check, seq,
+                                           reinterpret_cast<int*>(&c)); attempt++)
         if (attempt > 100000) { h->err = "counter mailbox record failed its checksum"; return SSF_ERR_DEVICE; }
-    }
     h->n_model = c.n_model; h->n_visible = c.n_visible;
     h->oov_head = c.oov_head; h->oov_tail = c.oov_tail; h->oov_live = c.oov_live;
+    return SSF_OK;
+}
+// the two flags a kernel without a record of its own to withhold leaves in the mailbox: each is reported once
+static int fuse_device_flags(ssf_handle* h) {
     if (__atomic_load_n(&h->mb_host->extract_abort, __ATOMIC_ACQUIRE) != 0u) {
         __atomic_store_n(&h->mb_host->extract_abort, 0u, __ATOMIC_RELEASE);
         h->err = "a team launch of the relabelling passes could not get all its workgroups onto the GPU and gave up (the GPU is oversubscribed: "
@@ -1023,17 +1007,36 @@ static int fuse_end(ssf_handle* h, const int32_t* d_table, ssf_frame_result* out
         __atomic_store_n(&h->mb_host->p2p_timeout, 0u, __ATOMIC_RELEASE);       // reported once; a later frame starts clean
         h->err = "a peer's association / migrant tables never arrived (peer-to-peer exchange)"; return SSF_ERR_DEVICE;
     }
-    if (out) {
-        std::memset(out, 0, sizeof(*out));
-        pose_to12(h->pose, out->pose);
-        out->icp_valid = h->last_icp_valid; out->icp_iters = h->last_icp_iters;
-        out->n_model = h->n_model; out->n_visible = h->n_visible; out->n_removed = c.n_removed;
-        out->n_inserted = c.n_inserted; out->n_updated = c.n_updated; out->stamp = h->stamp;
-        ExtractCtx* ec = h->active.ctx;            // extract time of the batch this frame came in, per frame
-        float ms;
-        if (h->cfg.profile != 0 && ec && ec->timed && hipEventElapsedTime(&ms, ec->ev_t0, ec->ev_t1) == hipSuccess)
-            out->stage_ms[0] = ms / (float)ec->nb_launched;
-    }
+    return SSF_OK;
+}
+static void fuse_result(ssf_handle* h, const Counters& c, ssf_frame_result* out) {
+    std::memset(out, 0, sizeof(*out));
+    pose_to12(h->pose, out->pose);
+    out->icp_valid = h->last_icp_valid; out->icp_iters = h->last_icp_iters;
+    out->n_model = h->n_model; out->n_visible = h->n_visible; out->n_removed = c.n_removed;
+    out->n_inserted = c.n_inserted; out->n_updated = c.n_updated; out->stamp = h->stamp;
+    ExtractCtx* ec = h->active.ctx;            // extract time of the batch this frame came in, per frame
+    float ms;
+    if (h->cfg.profile != 0 && ec && ec->timed && hipEventElapsedTime(&ms, ec->ev_t0, ec->ev_t1) == hipSuccess)
+        out->stage_ms[0] = ms / (float)ec->nb_launched;
+}
+static int fuse_end(ssf_handle* h, const int32_t* d_table, ssf_frame_result* out) {
+    const unsigned long long seq = ++h->cnt_seq;
+    h->fusing = false;                           // (also on every error path below: the frame is over either way)
+    int rc = fuse_launch_moves(h, d_table, seq);
+    if (rc) return rc;
+    HCK(hipGetLastError());
+    rc = retire_active(h);                       // last reader of this frame's buffers is enqueued
+    if (rc) return rc;
+    h->stamp_bias = 1;                           // the frame being fused still holds h->stamp
+    while (!rc && h->seq_next < h->seq_n && !h->ctx[h->open_ctx].launched) rc = seq_submit(h);      // see seq_rgb
+    h->stamp_bias = 0;
+    if (rc) return rc;
+    Counters c;
+    rc = fuse_read_counters(h, seq, c);
+    if (!rc) rc = fuse_device_flags(h);
+    if (rc) return rc;
+    if (out) fuse_result(h, c, out);
     h->stamp++;
     h->global_n_model = -1; h->global_n_visible = -1;
     if (h->cfg.profile == 1) { HCK(hipStreamSynchronize(h->stream)); timer_collect(&h->timer); }

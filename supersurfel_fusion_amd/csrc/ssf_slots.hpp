@@ -1,12 +1,13 @@
 // ssf_slots.hpp -- device helpers of the kernels that walk the model one thread per SLOT (ModelView, ssf_device.hpp) and of the
 // store upkeep (out-of-view compaction, re-homing): the slot -> row map, live counts and ranks inside a 256-thread block, the
 // integer wave reductions, and the one-workgroup exclusive scan that turns per-block counts into offsets.  Included by
-// ssf_render.hip, ssf_query.hip, ssf_navgrid.hip, ssf_raycast.hip, ssf_graph.hip, ssf_keyframes.hip and ssf_track_fuse.hip.
+// ssf_render.hip, ssf_query.hip, ssf_navgrid.hip, ssf_raycast.hip, ssf_graph.hip, ssf_keyframes.hip and, through ssf_rows.hpp,
+// ssf_track_fuse.hip, ssf_upkeep.hip and ssf_p2p.hip.
 // The kernels shared by several of these files live in ssf_slots.hip (the library is built without relocatable device
 // code), reached through the host launchers declared at the end: k_slots_scan -- the scan of render's and the navigation grid's
 // tile counts, the ray cast's bucket counts and of every out-of-view live count; k_slots_scan32, the same body with 32-bit sums
 // for the graph's sort histograms -- and k_slots_oov_count.  What does NOT go through them: k_query_scan (two counters plus the record), k_oov_scan and k_rehome_scan
-// (a device-side n, store upkeep), k_bin_scan, everything of the per-frame kernels (ICP, association, fuse, partition, row move,
+// (ssf_upkeep.hip: a device-side n, store upkeep), k_bin_scan, everything of the per-frame kernels (ICP, association, fuse, partition, row move,
 // k_bin_*: their own ballots and scans, tuned to the instruction) and of ssf_extract.hip, and the fill kernels (render's plain
 // one, the LDS-histogram ones of the navigation grid and the ray cast with their different bin functions: measured choices).
 #pragma once

@@ -1,10 +1,11 @@
-// ssf_track_fuse.hip -- ICP normal-equation accumulation and the model fuse kernels for gfx950.
+// ssf_track_fuse.hip -- the per-frame chain for gfx950: ICP normal-equation accumulation, association and the model fuse
+// kernels, and nothing else (what runs between frames: ssf_upkeep.hip; between ranks: ssf_p2p.hip; shared row helpers:
+// ssf_rows.hpp; the mailbox records: ssf_mailbox.hpp).
 //
 // What is computed follows the reference: computeSymmetricICPSystem
 // (core/include/supersurfel_fusion/dense_registration_kernels.cuh:175-291), findBestMatches /
 // updateSupersurfels / insertSupersurfels / filterModel (core/src/supersurfel_fusion_kernels.cu:
-// 348-467,522-682), thrust::sort_by_key over the model (core/src/supersurfel_fusion.cu:469-472) and
-// applyDeformation (core/src/deformation_graph_kernels.cu:27-73).  How:
+// 348-467,522-682) and thrust::sort_by_key over the model (core/src/supersurfel_fusion.cu:469-472).  How:
 //   * ICP streams 36 B per visible supersurfel (pos, cached Lab, normal row) from separate SoA
 //     streams; an inlier adds its 29 fixed-point terms with LDS integer atomics, every workgroup
 //     issues 29 global integer atomics, the last workgroup (two-level arrival counter) publishes
@@ -17,27 +18,11 @@
 //     per-block class histograms, a one-workgroup scan turns them into offsets (and publishes the
 //     frame's counters), one pass moves only the rows whose place changes (visible rows are a dense
 //     array, out-of-view rows a deque-like store with live flags: OovStore, ssf_device.hpp).
-//   * the loop-closure registration (DenseRegistration::align) is one single-workgroup launch per
-//     iteration with exact sums; fern codes are a gather.
 #include <stdlib.h>
 #include <algorithm>
-#include "ssf_slots.hpp"
+#include "ssf_rows.hpp"
 
 namespace ssf {
-
-__device__ __forceinline__ long long wsum64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ V3 ld3(const float* __restrict__ p, size_t i) { return v3(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
-__device__ __forceinline__ void st3(float* __restrict__ p, size_t i, V3 v) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; }
-__device__ __forceinline__ Sym3 ld6(const float* __restrict__ p, size_t i) {
-    return sym3(p[6 * i], p[6 * i + 1], p[6 * i + 2], p[6 * i + 3], p[6 * i + 4], p[6 * i + 5]);
-}
-__device__ __forceinline__ void st6(float* __restrict__ p, size_t i, Sym3 c) {
-    p[6 * i] = c.xx; p[6 * i + 1] = c.xy; p[6 * i + 2] = c.xz; p[6 * i + 3] = c.yy; p[6 * i + 4] = c.yz; p[6 * i + 5] = c.zz;
-}
 
 // ---- ICP ---------------------------------------------------------------------------------------
 // One supersurfel per lane.  An inlier adds its 29 fixed-point terms with LDS integer atomics into a
@@ -49,9 +34,6 @@ __device__ __forceinline__ void st6(float* __restrict__ p, size_t i, Sym3 c) {
 #ifndef ICP_SLOTS
 #define ICP_SLOTS 16      // lane & 15 spreads the same-address traffic (64 columns measured no faster)
 #endif
-// the 29 terms of one visible supersurfel (position, cached Lab, normal row) under transform (R, t), each handed to
-// emit(k, value) as soon as it is computed (k is a compile-time constant after unrolling): JtJ k = 0..20 (fixed point 2^20),
-// Jtr 21..26 (2^24), squared residual 27 (2^44), inlier count 28
 // The 29 terms of one visible supersurfel (position, cached Lab, normal row) under transform (R, t), each handed to
 // emit(k, value) as soon as it is computed (k is a compile-time constant after unrolling): JtJ k = 0..20 (fixed point 2^20),
 // Jtr 21..26 (2^24), squared residual 27 (2^44), inlier count 28.  Gates: dense_registration_kernels.cuh:217-249.
@@ -120,9 +102,8 @@ __device__ __forceinline__ void icp_row(const Cam& cam, const uint2* __restrict_
                                         unsigned long long* red, int slot, int dbg) {
     icp_row_terms(cam, pix2, fpack, R, t, mpos, mlab, mnrm, dbg, [&](int k, long long v) { atomicAdd(&red[k * ICP_SLOTS + slot], (unsigned long long)v); });
 }
-template <typename T> __device__ __forceinline__ void atomic_add_done(T* p, T v);
 // end of an accumulating kernel, in three steps called by every thread of a workgroup after a barrier:
-// fold the workgroup's table into a replica record ...
+// fold the workgroup's table into a replica record, count the arrival (grid_arrive, ssf_rows.hpp) ...
 __device__ __forceinline__ void icp_fold(unsigned long long* red, long long* __restrict__ replicas) {
     if (threadIdx.x < 29) {
         unsigned long long tot = 0;
@@ -137,113 +118,6 @@ __device__ __forceinline__ void icp_fold(unsigned long long* red, long long* __r
     // invalidate fence is needed.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-}
-// What a workgroup hands to the LAST workgroup of its launch (the one that sums up and publishes) must have been PERFORMED at
-// the coherence point before the workgroup counts its arrival.  For an atomic without return value the wait counter
-// (s_waitcnt vmcnt(0)) only says that the request has been accepted: with several handles hammering the fabric side by
-// side (tools/p2p_first_frame_stress.py: four ranks of a sharded map on one GPU) the last workgroup was seen reading a
-// replica record / a partition total BEFORE another workgroup's add had landed -- one frame in a few hundred came out a
-// workgroup's worth short.  The value a RETURNING atomic brings back is the proof that it has been performed; these
-// helpers are used for everything the last workgroup of the same launch reads.  (What the NEXT launch reads needs
-// nothing: a kernel boundary completes everything.)
-template <typename T> __device__ __forceinline__ void atomic_add_done(T* p, T v) {
-    const T before = atomicAdd(p, v);
-    asm volatile("" :: "v"(before));
-}
-__device__ __forceinline__ void atomic_store_done(int* p, int v) {
-    const int before = __hip_atomic_exchange(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("" :: "v"(before));
-}
-// ... count the arrival (is this the last workgroup?) ...
-// two-level arrival count over all workgroups of the grid (a single counter serialises thousands of same-address
-// atomics at L2): 64 group counters, the last workgroup of a group reports to the global counter.  Thread 0 only.
-#ifndef ARRIVE_GROUPS
-#define ARRIVE_GROUPS 64u
-#endif
-// SSF_ARRIVE_FENCED (an experiment build, tools/build_variant.sh fenced -DSSF_ARRIVE_FENCED): real
-// agent-scope release / acquire ordering around the arrival ticket -- one fence per workgroup, not per atomic -- to tell
-// whether the first-frame divergence seen with UNCACHED exchange regions (round 2) was the relaxed arrival protocol's.
-#if defined(SSF_EXPERIMENTS) && defined(SSF_ARRIVE_FENCED)
-#define SSF_ARRIVE_RELEASE() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); } while (0)
-#define SSF_ARRIVE_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")
-#else
-#define SSF_ARRIVE_RELEASE() do { } while (0)
-#define SSF_ARRIVE_ACQUIRE() do { } while (0)
-#endif
-__device__ __forceinline__ int grid_arrive(unsigned int* ticket) {
-    SSF_ARRIVE_RELEASE();
-    const unsigned int g = blockIdx.x & (ARRIVE_GROUPS - 1u);
-    const unsigned int in_group = (gridDim.x - g + ARRIVE_GROUPS - 1u) / ARRIVE_GROUPS, groups = min(gridDim.x, ARRIVE_GROUPS);
-    int last = 0;
-    const unsigned int tk = __hip_atomic_fetch_add(&ticket[1 + g], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tk == in_group - 1) {
-        __hip_atomic_store(&ticket[1 + g], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned int tg = __hip_atomic_fetch_add(&ticket[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (tg == groups - 1) { last = 1; __hip_atomic_store(&ticket[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    }
-    if (last) SSF_ARRIVE_ACQUIRE();
-    return last;
-}
-// ---- peer-to-peer exchange helpers (ssf_device.hpp: P2PView) ----------------------------------------------------------
-__device__ __forceinline__ unsigned char* p2p_peer(const P2PView& pv, int r) {       // uniform select chain (no dynamic kernarg indexing)
-    unsigned char* v = pv.peer[0];
-#pragma unroll
-    for (int i = 1; i < SSF_P2P_MAX_RANKS; i++) v = (r == i) ? pv.peer[i] : v;
-    return v;
-}
-__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int src) {
-    const unsigned int lo = (unsigned int)__shfl((int)(unsigned int)v, src), hi = (unsigned int)__shfl((int)(unsigned int)(v >> 32), src);
-    return ((unsigned long long)hi << 32) | lo;
-}
-// A peer that never arrives must not hang the device: every wait for a peer is bounded by WALL-CLOCK time (the constant-rate
-// counter behind wall_clock64(), P2PView::timeout_ticks = ssf_p2p_configure's timeout), not by a spin count -- ranks in
-// separate processes reach their first exchange seconds apart (set_model of a large map, graph captures, a cold box).
-struct P2PDeadline {
-    unsigned long long t0, ticks; unsigned int spins;
-    __device__ __forceinline__ explicit P2PDeadline(const P2PView& pv) : t0(wall_clock64()), ticks(pv.timeout_ticks), spins(0u) {}
-    // call once per unsuccessful poll; true = give up
-    __device__ __forceinline__ bool expired() {
-        __builtin_amdgcn_s_sleep(1);
-        if ((++spins & 1023u) != 0u) return false;
-        return wall_clock64() - t0 > ticks;
-    }
-};
-// Wave 0 of the last workgroup: this rank's record (tot in lanes 0..28) goes into slot [parity][me] of every peer's region
-// as five self-validating lines (the format of Mailbox::icp_rec); the records of the others are awaited in this rank's
-// own region and added in rank order.  Returns false when a peer's record never arrived.
-__device__ __forceinline__ bool p2p_icp_exchange(const P2PView& pv, unsigned long long seq, long long& tot, unsigned long long* pay /* LDS, 30 */) {
-    const int l = lane();
-    const int par = (int)(seq & 1ull);
-    if (l < 29) pay[l] = (unsigned long long)tot;
-    const unsigned long long check = (unsigned long long)wsum64(l < 29 ? tot : 0ll) + seq;
-    if (l == 0) pay[29] = check;
-    __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0): one wave, its LDS writes have landed
-    const unsigned long long word = l < 40 ? SSF_ICP_REC_WORD(l, pay, seq) : 0ull;
-#pragma unroll
-    for (int r = 0; r < SSF_P2P_MAX_RANKS; r++) {
-        if (r >= pv.nranks || r == pv.me) continue;
-        unsigned long long* dst = reinterpret_cast<unsigned long long*>(pv.peer[r] + p2p_off_icp(par, pv.me));
-        if (l < 40) __hip_atomic_store(&dst[l], word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    unsigned char* mine = p2p_peer(pv, pv.me);
-    const bool is_seq_word = l < 40 && (l & 7) == 7, is_payload = l < 40 && (l & 7) != 7 && (7 * (l >> 3) + (l & 7)) < 29;
-    P2PDeadline deadline(pv);
-    for (int r = 0; r < pv.nranks; r++) {
-        if (r == pv.me) continue;
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(mine + p2p_off_icp(par, r));
-        for (;;) {
-            const unsigned long long w = l < 40 ? __hip_atomic_load(&src[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0ull;
-            const bool lines_ok = __ballot(is_seq_word && w != seq) == 0ull;
-            const unsigned long long sum = (unsigned long long)wsum64(is_payload ? (long long)w : 0ll) + seq;
-            if (lines_ok && sum == shfl_u64(w, 33)) {                   // payload word 29 (the checksum) sits in lane 8 * 4 + 1
-                const unsigned long long v = shfl_u64(w, l < 29 ? 8 * (l / 7) + l % 7 : 0);       // payload word l of the peer
-                if (l < 29) tot += (long long)v;
-                break;
-            }
-            if (deadline.expired()) return false;
-        }
-    }
-    return true;
 }
 // ... and, in the last workgroup, sum the replicas and publish the record (P2P: the SUM of the records of all ranks)
 // (the number of the peer exchange travels beside the view, not in it: a kernel that writes into its P2PView argument gets a
@@ -275,17 +149,8 @@ __device__ __forceinline__ void icp_publish(long long* __restrict__ replicas, lo
             if (threadIdx.x < 29) sums[32 + threadIdx.x] = tot;        // (this shard's own record, for tools/p2p_first_frame_stress.py)
             if (!p2p_icp_exchange(pv, p2p_seq, tot, pay)) return;
         }      // (no record: the host reports the missing peer)
-        if (threadIdx.x < 29) {
-            sums[threadIdx.x] = tot;
-            pay[threadIdx.x] = (unsigned long long)tot;
-        }
-        const unsigned long long check = (unsigned long long)wsum64(tot) + seq;
-        if (threadIdx.x == 0) pay[29] = check;
-        // one wave: LDS operations of a wave execute in order, so the reads below see the writes above; 40 lanes
-        // store the five self-validating lines in one instruction
-        __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0): the LDS writes have landed
-        if (threadIdx.x < 40)
-            __hip_atomic_store(&mb->icp_rec[threadIdx.x], SSF_ICP_REC_WORD(threadIdx.x, pay, seq), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (threadIdx.x < 29) sums[threadIdx.x] = tot;
+        icp_record_store(mb->icp_rec, tot, seq, pay, threadIdx.x);
     }
 }
 // ---- the counted record: the end of an accumulating launch in ONE trip instead of three ------------------------------------
@@ -375,15 +240,8 @@ __device__ __forceinline__ bool icp_collect_counted(unsigned long long* __restri
         const long long hi27 = (long long)shfl_u64((unsigned long long)tot, 29);
         if (tid == 27) tot = (long long)(((unsigned long long)hi27 << 40) + (unsigned long long)tot);
         if (tid >= 29) tot = 0;
-        if (tid < 29) {
-            sums[tid] = tot;
-            pay[tid] = (unsigned long long)tot;
-        }
-        const unsigned long long check = (unsigned long long)wsum64(tot) + seq;
-        if (tid == 0) pay[29] = check;
-        __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0): the LDS writes have landed
-        if (tid < 40)
-            __hip_atomic_store(&mb->icp_rec[tid], SSF_ICP_REC_WORD(tid, pay, seq), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (tid < 29) sums[tid] = tot;
+        icp_record_store(mb->icp_rec, tot, seq, pay, tid);
     }
     return true;
 }
@@ -723,132 +581,6 @@ __global__ __launch_bounds__(256, 7) __attribute__((amdgpu_num_sgpr(SSF_ICP_NUM_
     }
 }
 
-// ---- loop-closure registration (DenseRegistration::align) -----------------------------------------------------
-// makeCorrespondences, dense_registration_kernels.cu:27-100, for one source supersurfel
-__device__ __forceinline__ bool align_pair(const Cam& cam, const float* __restrict__ spos, const float* __restrict__ slab,
-                                           const float* __restrict__ snrm, const float* __restrict__ sconf, int id,
-                                           const SurfelSoA& frame, const int32_t* __restrict__ label,
-                                           const float* __restrict__ plane_depth, const M3& R, const V3& t,
-                                           V3& pv, V3& sn, V3& tp, V3& tn) {
-    if (sconf && !(sconf[id] > 0.0f)) return false;
-    pv = add(m3_mulv(R, ld3(spos, id)), t);
-    const int u = pixel_round(pv.x * cam.fx / pv.z + cam.cx), v = pixel_round(pv.y * cam.fy / pv.z + cam.cy);
-    if (!(u >= 0 && u < cam.W && v >= 0 && v < cam.H)) return false;
-    const size_t q = (size_t)v * cam.W + u;
-    const int tid = label[q];
-    if (!(frame.conf[tid] > 0.0f)) return false;
-    const float dist_color = len3(sub(ld3(slab, id), ld3(frame.lab, tid)));
-    const float td = plane_depth[q];
-    if (!isfinite(td)) return false;
-    sn = unit3(ld3(snrm, id));
-    sn = unit3(m3_mulv(R, sn));
-    tn = unit3(ld3(frame.r2, tid));
-    tp = v3(td * ((float)u - cam.cx) / cam.fx, td * ((float)v - cam.cy) / cam.fy, td);
-    return dist_color < 20.0f && len3(sub(pv, tp)) < 0.1f && fabsf(dot3(sn, tn)) > 0.8f;
-}
-// One iteration of align in ONE single-workgroup launch: pair count + centroids, scale, normalised symmetric
-// point-to-plane system (buildSymmetricPoint2PlaneSystem, dense_registration_kernels.cuh:87-173).  The reference
-// compacts the valid pairs (thrust::remove_if) to feed three reductions; all sums here are exact integers, so the
-// pairs are simply re-derived in each phase (a keyframe has ~S sources: the whole problem is LDS-sized).
-// out: [0..28] record as k_icp, [29] pairs, [30..32] source centroid bits, [33..35] target centroid bits, [36] scale bits
-__global__ __launch_bounds__(1024) void k_align(Cam cam, const float* __restrict__ spos, const float* __restrict__ slab,
-                                                const float* __restrict__ snrm, const float* __restrict__ sconf, int n,
-                                                SurfelSoA frame, const int32_t* __restrict__ label,
-                                                const float* __restrict__ plane_depth, Rt T, long long* __restrict__ out) {
-    __shared__ unsigned long long acc[8];
-    __shared__ unsigned long long red[29 * 16];
-    __shared__ float s_c[7];
-    __shared__ int s_pairs;
-    for (int i = threadIdx.x; i < 29 * 16; i += blockDim.x) red[i] = 0ull;
-    if (threadIdx.x < 8) acc[threadIdx.x] = 0ull;
-    __syncthreads();
-    const M3 R = T.R; const V3 t = T.t;
-    V3 pv, sn, tp, tn;
-    for (int id = threadIdx.x; id < n; id += blockDim.x) {
-        if (!align_pair(cam, spos, slab, snrm, sconf, id, frame, label, plane_depth, R, t, pv, sn, tp, tn)) continue;
-        atomicAdd(&acc[0], (unsigned long long)fx64((double)pv.x, SSF_ALIGN_SCALE_POS, SSF_ALIGN_LIM));
-        atomicAdd(&acc[1], (unsigned long long)fx64((double)pv.y, SSF_ALIGN_SCALE_POS, SSF_ALIGN_LIM));
-        atomicAdd(&acc[2], (unsigned long long)fx64((double)pv.z, SSF_ALIGN_SCALE_POS, SSF_ALIGN_LIM));
-        atomicAdd(&acc[3], (unsigned long long)fx64((double)tp.x, SSF_ALIGN_SCALE_POS, SSF_ALIGN_LIM));
-        atomicAdd(&acc[4], (unsigned long long)fx64((double)tp.y, SSF_ALIGN_SCALE_POS, SSF_ALIGN_LIM));
-        atomicAdd(&acc[5], (unsigned long long)fx64((double)tp.z, SSF_ALIGN_SCALE_POS, SSF_ALIGN_LIM));
-        atomicAdd(&acc[6], 1ull);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int pairs = (int)acc[6];
-        s_pairs = pairs;
-        for (int i = 0; i < 6; i++) s_c[i] = (float)((double)(long long)acc[i] / SSF_ALIGN_SCALE_POS) / (float)pairs;
-        out[29] = pairs;
-    }
-    __syncthreads();
-    const int pairs = s_pairs;
-    if (pairs < 100) {                                       // the host stops here (dense_registration.cu:133-138)
-        if (threadIdx.x < 29) out[threadIdx.x] = 0;
-        if (threadIdx.x >= 30 && threadIdx.x < 37) out[threadIdx.x] = 0;
-        return;
-    }
-    const V3 cs = v3(s_c[0], s_c[1], s_c[2]), ct = v3(s_c[3], s_c[4], s_c[5]);
-    for (int id = threadIdx.x; id < n; id += blockDim.x) {
-        if (!align_pair(cam, spos, slab, snrm, sconf, id, frame, label, plane_depth, R, t, pv, sn, tp, tn)) continue;
-        const V3 a = v3(tp.x - ct.x, tp.y - ct.y, tp.z - ct.z), b = v3(pv.x - cs.x, pv.y - cs.y, pv.z - cs.z);
-        atomicAdd(&acc[7], (unsigned long long)fx64((double)((a.x * a.x + a.y * a.y) + a.z * a.z), SSF_ALIGN_SCALE_D2, SSF_ALIGN_LIM));
-        atomicAdd(&acc[7], (unsigned long long)fx64((double)((b.x * b.x + b.y * b.y) + b.z * b.z), SSF_ALIGN_SCALE_D2, SSF_ALIGN_LIM));
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float sv = (float)((double)(long long)acc[7] / SSF_ALIGN_SCALE_D2);
-        sv = sqrtf(sv / (2.0f * (float)pairs));
-        s_c[6] = 1.0f / sv;
-    }
-    __syncthreads();
-    const float sc = s_c[6];
-    const int slot = lane() & 15;
-    for (int id = threadIdx.x; id < n; id += blockDim.x) {
-        if (!align_pair(cam, spos, slab, snrm, sconf, id, frame, label, plane_depth, R, t, pv, sn, tp, tn)) continue;
-        const V3 ps = scale(sc, sub(pv, cs)), pt = scale(sc, sub(tp, ct));
-        const V3 ns = unit3(sn), nt = unit3(tn);
-        const V3 d = sub(pt, ps), c1 = cross3(pt, ns), c2 = cross3(ps, nt);
-        const float dn1 = dot3(d, ns), dn2 = dot3(d, nt);
-        const float x1[6] = {c1.x, c1.y, c1.z, ns.x, ns.y, ns.z};
-        const float x2[6] = {c2.x, c2.y, c2.z, nt.x, nt.y, nt.z};
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int j = i; j < 6; j++, k++)
-                atomicAdd(&red[k * 16 + slot], (unsigned long long)(long long)fx32(x1[i] * x1[j] + x2[i] * x2[j], 1048576.0f));
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-            atomicAdd(&red[(21 + i) * 16 + slot], (unsigned long long)(long long)fx32(dn1 * x1[i] + dn2 * x2[i], 16777216.0f));
-        atomicAdd(&red[27 * 16 + slot], (unsigned long long)fx64((double)(dn2 * dn2), 17592186044416.0, 4611686018427387904.0));
-        atomicAdd(&red[28 * 16 + slot], 1ull);
-    }
-    __syncthreads();
-    if (threadIdx.x < 29) {
-        unsigned long long tot = 0;
-        for (int sidx = 0; sidx < 16; sidx++) tot += red[threadIdx.x * 16 + sidx];
-        out[threadIdx.x] = (long long)tot;
-    }
-    if (threadIdx.x < 7) out[30 + threadIdx.x] = (long long)__float_as_uint(s_c[threadIdx.x]);
-}
-
-// computeCodes_kernel, ferns_kernels.cu:48-70 (point sampling, clamp: texture_impl.hpp:43-46)
-__global__ void k_fern_codes(const uint8_t* __restrict__ rgb, const float* __restrict__ depth, int W, int H,
-                             const uint32_t* __restrict__ fpos, const uint8_t* __restrict__ frgb,
-                             const float* __restrict__ fdepth, int n, uint8_t* __restrict__ codes) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const int x = (int)min(fpos[2 * k], (uint32_t)W - 1u), y = (int)min(fpos[2 * k + 1], (uint32_t)H - 1u);
-    const size_t q = (size_t)y * W + x;
-    uint8_t r = 0;
-    r |= rgb[3 * q] > frgb[3 * k] ? 1 : 0;
-    r |= rgb[3 * q + 1] > frgb[3 * k + 1] ? 2 : 0;
-    r |= rgb[3 * q + 2] > frgb[3 * k + 2] ? 4 : 0;
-    r |= depth[q] > fdepth[k] ? 8 : 0;
-    codes[k] = r;
-}
-
 // ---- association ---------------------------------------------------------------------------------
 // one frame supersurfel (or none) per visible model row; cand[id] = the frame supersurfel this row has bid for
 // (-1: none) -- the fuse launch uses it to tell which rows the update is about to rewrite
@@ -1066,7 +798,6 @@ __device__ __forceinline__ void classify_oov_block(const Cam& cam, const OovStor
 //               exchanged with shuffles inside the group; the first lane stores colour and Lab
 // (the two kinds of work sit in different waves, so neither waits for the other's instruction stream)
 #define UPD_PER_WG 32
-__device__ __forceinline__ int tile_owner(const V3& pw, int nranks, float tile);
 __device__ __forceinline__ float pick3(const V3& v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
 __device__ __forceinline__ void update_group(SurfelSoA M, SurfelSoA F, Rt pose, int stamp, long long id_offset, int n_visible,
                                              const unsigned long long* __restrict__ best, const uint8_t* __restrict__ matched,
@@ -1159,12 +890,7 @@ __device__ __forceinline__ void update_group(SurfelSoA M, SurfelSoA F, Rt pose, 
     }
 }
 
-// spatial-tile owner of a world position / of a frame supersurfel (multi-GPU sharding)
-__device__ __forceinline__ int tile_owner(const V3& pw, int nranks, float tile) {
-    const int ix = (int)floorf(pw.x / tile), iy = (int)floorf(pw.y / tile), iz = (int)floorf(pw.z / tile);
-    const uint32_t h = ((uint32_t)ix * 73856093u) ^ ((uint32_t)iy * 19349663u) ^ ((uint32_t)iz * 83492791u);
-    return (int)(h % (uint32_t)nranks);
-}
+// spatial-tile owner of a frame supersurfel (multi-GPU sharding; tile_owner: ssf_rows.hpp)
 __device__ __forceinline__ int shard_owner(const SurfelSoA& F, int f, const Rt& pose, int nranks, float tile) {
     if (nranks <= 1) return 0;
     if (!(F.conf[f] > 0.0f)) return f % nranks;
@@ -1409,29 +1135,7 @@ __global__ __launch_bounds__(1024) void k_first_frame(SurfelSoA M, SurfelSoA F, 
     }
 }
 
-// ---- stable partition over the model store (see OovStore in ssf_device.hpp) ----------------------------------------
-// one model row in registers: all loads are issued before the first store (source and destination arrays may alias as
-// far as the compiler knows, so a field-by-field copy is a chain of dependent round trips)
-struct RowRegs { V3 pos, col, lab, r0, r1, r2; Sym3 shape; int s0, s1; float d0, d1, conf; };
-__device__ __forceinline__ RowRegs load_row(const SurfelSoA& A, size_t i) {
-    RowRegs r;
-    r.pos = ld3(A.pos, i); r.col = ld3(A.col, i); r.lab = ld3(A.lab, i);
-    r.s0 = A.stamps[2 * i]; r.s1 = A.stamps[2 * i + 1];
-    r.r0 = ld3(A.r0, i); r.r1 = ld3(A.r1, i); r.r2 = ld3(A.r2, i);
-    r.shape = ld6(A.shape, i);
-    r.d0 = A.dims[2 * i]; r.d1 = A.dims[2 * i + 1];
-    r.conf = A.conf[i];
-    return r;
-}
-__device__ __forceinline__ void store_row(const SurfelSoA& B, size_t j, const RowRegs& r) {
-    st3(B.pos, j, r.pos); st3(B.col, j, r.col); st3(B.lab, j, r.lab);
-    B.stamps[2 * j] = r.s0; B.stamps[2 * j + 1] = r.s1;
-    st3(B.r0, j, r.r0); st3(B.r1, j, r.r1); st3(B.r2, j, r.r2);
-    st6(B.shape, j, r.shape);
-    B.dims[2 * j] = r.d0; B.dims[2 * j + 1] = r.d1;
-    B.conf[j] = r.conf;
-}
-__device__ __forceinline__ void copy_row(const SurfelSoA& A, size_t i, const SurfelSoA& B, size_t j) { store_row(B, j, load_row(A, i)); }
+// ---- stable partition over the model store (see OovStore in ssf_device.hpp; a row in registers: RowRegs, ssf_rows.hpp) ----
 // copy of a row that enters the new visible array; hands back the three fields the ICP terms read
 __device__ __forceinline__ void copy_row_keep(const SurfelSoA& A, size_t i, const SurfelSoA& B, size_t j, V3& pos, V3& lab, V3& nrm) {
     const RowRegs r = load_row(A, i);
@@ -1680,11 +1384,7 @@ __global__ __launch_bounds__(256) void k_pack_emigrants(SurfelSoA M, const unsig
             if (state_vis[m] == 2 && conf > 0.0f) {
                 const RowRegs r = load_row(M, m);
                 w[0] = tile_owner(r.pos, nranks, tile) + 1;
-                const float v[26] = {r.pos.x, r.pos.y, r.pos.z, r.col.x, r.col.y, r.col.z, __int_as_float(r.s0), __int_as_float(r.s1),
-                                     r.r0.x, r.r0.y, r.r0.z, r.r1.x, r.r1.y, r.r1.z, r.r2.x, r.r2.y, r.r2.z,
-                                     r.shape.xx, r.shape.xy, r.shape.xz, r.shape.yy, r.shape.yz, r.shape.zz, r.d0, r.d1, r.conf};
-#pragma unroll
-                for (int i = 0; i < 26; i++) w[2 + i] = __float_as_int(v[i]);
+                migrant_pack(r, w);
             }
         }
     }
@@ -1712,6 +1412,7 @@ __global__ __launch_bounds__(1024) void k_migrate_in(SurfelSoA M, const int32_t*
         int total;
         const int r = block_rank_1024(flag, wave_tot, total);
         if (flag && total_before + running + r < capacity) {
+            // (migrant_unpack, written out: through the helper this kernel's registers come out differently)
             const int32_t* w = table + (size_t)SSF_MIGRANT_WORDS * f;
             float v[26];
 #pragma unroll
@@ -1750,101 +1451,6 @@ __global__ __launch_bounds__(1024) void k_migrate_in(SurfelSoA M, const int32_t*
     }
 }
 
-// ---- re-homing of a sharded map after positions changed outside a frame (ssf_rehome_begin / _end in ssf.h) ---------------
-// over the dense logical view [visible | out of view]: a row leaves when it is valid and its position belongs to another
-// rank's tile.  Three launches: per-block counts (staying rows, leaving rows, staying rows of the visible block), their
-// exclusive scan by one workgroup (totals -> tot3), and the ordered scatter: staying rows close ranks in `stay`, leaving
-// rows become migrant-table records (word 1 = 1: the row sat in the visible block) in logical order.
-__device__ __forceinline__ int rehome_class(const SurfelSoA& D, int i, int n, int rank, int nranks, float tile) {
-    if (i >= n) return 2;                                          // 0 stays, 1 leaves
-    return (D.conf[i] > 0.0f && tile_owner(ld3(D.pos, i), nranks, tile) != rank) ? 1 : 0;
-}
-__global__ __launch_bounds__(256) void k_rehome_count(SurfelSoA D, int n, int n_visible, int rank, int nranks, float tile, uint32_t* __restrict__ bc) {
-    __shared__ int part[4][3];
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int c = rehome_class(D, i, n, rank, nranks, tile);
-    const int k0 = __popcll(__ballot(c == 0)), k1 = __popcll(__ballot(c == 1)), k2 = __popcll(__ballot(c == 0 && i < n_visible));
-    if (lane() == 0) { part[threadIdx.x >> 6][0] = k0; part[threadIdx.x >> 6][1] = k1; part[threadIdx.x >> 6][2] = k2; }
-    __syncthreads();
-    if (threadIdx.x < 3) bc[3 * blockIdx.x + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-}
-__global__ __launch_bounds__(1024) void k_rehome_scan(uint32_t* __restrict__ bc, int nblocks, int* __restrict__ tot3) {
-    __shared__ uint32_t tot[3];
-    workgroup_scan<3, uint32_t>(bc, nblocks, nullptr, tot);
-    if (threadIdx.x < 3) tot3[threadIdx.x] = (int)tot[threadIdx.x];
-}
-__global__ __launch_bounds__(256) void k_rehome_scatter(SurfelSoA D, int n, int n_visible, int rank, int nranks, float tile,
-                                                        const uint32_t* __restrict__ bc, SurfelSoA stay, int32_t* __restrict__ table, int table_rows) {
-    __shared__ int part[2][4];
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int c = rehome_class(D, i, n, rank, nranks, tile);
-    const int r0 = block_rank256(c == 0, part[0]), r1 = block_rank256(c == 1, part[1]);      // (before any thread leaves)
-    if (c > 1) return;
-    const size_t j = (size_t)bc[3 * blockIdx.x + c] + (c == 0 ? r0 : r1);
-    if (c == 0) { copy_row(D, (size_t)i, stay, j); return; }
-    if (j >= (size_t)table_rows) return;                               // (the host sees the total and reports SSF_ERR_CAPACITY)
-    const RowRegs r = load_row(D, (size_t)i);
-    int32_t* o = table + (size_t)SSF_MIGRANT_WORDS * j;
-    o[0] = tile_owner(r.pos, nranks, tile) + 1; o[1] = i < n_visible ? 1 : 0;
-    const float v[26] = {r.pos.x, r.pos.y, r.pos.z, r.col.x, r.col.y, r.col.z, __int_as_float(r.s0), __int_as_float(r.s1),
-                         r.r0.x, r.r0.y, r.r0.z, r.r1.x, r.r1.y, r.r1.z, r.r2.x, r.r2.y, r.r2.z,
-                         r.shape.xx, r.shape.xy, r.shape.xz, r.shape.yy, r.shape.yz, r.shape.zz, r.d0, r.d1, r.conf};
-#pragma unroll
-    for (int q = 0; q < 26; q++) o[2 + q] = __float_as_int(v[q]);
-}
-// records [0, n) of a packed table -> rows [base, base + n) of D (the Lab cache is rebuilt from the colour)
-__global__ __launch_bounds__(256) void k_rehome_unpack(const int32_t* __restrict__ table, int n, SurfelSoA D, int base) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const int32_t* w = table + (size_t)SSF_MIGRANT_WORDS * j;
-    float v[26];
-#pragma unroll
-    for (int q = 0; q < 26; q++) v[q] = __int_as_float(w[2 + q]);
-    RowRegs row;
-    row.pos = v3(v[0], v[1], v[2]); row.col = v3(v[3], v[4], v[5]); row.lab = rgb_to_lab(row.col);
-    row.s0 = __float_as_int(v[6]); row.s1 = __float_as_int(v[7]);
-    row.r0 = v3(v[8], v[9], v[10]); row.r1 = v3(v[11], v[12], v[13]); row.r2 = v3(v[14], v[15], v[16]);
-    row.shape = sym3(v[17], v[18], v[19], v[20], v[21], v[22]); row.d0 = v[23]; row.d1 = v[24]; row.conf = v[25];
-    store_row(D, (size_t)base + j, row);
-}
-void launch_rehome_split(hipStream_t st, SurfelSoA dense, int n, int n_visible, int rank, int nranks, float tile, uint32_t* bc, int* tot3,
-                         SurfelSoA stay, int32_t* table, int table_rows) {
-    const int nb = (n + 255) / 256;
-    if (nb <= 0) return;
-    hipLaunchKernelGGL(k_rehome_count, dim3(nb), dim3(256), 0, st, dense, n, n_visible, rank, nranks, tile, bc);
-    hipLaunchKernelGGL(k_rehome_scan, dim3(1), dim3(1024), 0, st, bc, nb, tot3);
-    hipLaunchKernelGGL(k_rehome_scatter, dim3(nb), dim3(256), 0, st, dense, n, n_visible, rank, nranks, tile, bc, stay, table, table_rows);
-}
-void launch_rehome_unpack(hipStream_t st, const int32_t* table, int n, SurfelSoA dst, int base) {
-    if (n > 0) hipLaunchKernelGGL(k_rehome_unpack, dim3((n + 255) / 256), dim3(256), 0, st, table, n, dst, base);
-}
-
-// ---- out-of-view store maintenance: stable compaction of the live rows into the other store -------------------
-// (head and tail come from the device counters: the launches are enqueued before the host knows them)
-__global__ __launch_bounds__(256) void k_oov_count(OovStore O, uint32_t* __restrict__ bc, const Counters* __restrict__ cnt) {
-    __shared__ int part[4];
-    size_t phys;
-    const int k = block_count256(span_live(O.live, cnt->oov_head, cnt->oov_tail, blockIdx.x * 256u + threadIdx.x, phys), part);
-    if (threadIdx.x == 0) bc[blockIdx.x] = k;
-}
-__global__ __launch_bounds__(1024) void k_oov_scan(uint32_t* __restrict__ bc, int nb_upper, const Counters* __restrict__ cnt) {
-    __shared__ uint32_t tot[1];
-    workgroup_scan<1, uint32_t>(bc, min(nb_upper, (cnt->oov_tail - cnt->oov_head + 255) / 256), nullptr, tot);
-}
-__global__ __launch_bounds__(256) void k_oov_compact(OovStore A, OovStore B, const uint32_t* __restrict__ bc, int new_head,
-                                                     const Counters* __restrict__ cnt) {
-    __shared__ int part[4];
-    size_t phys;
-    const bool lv = span_live(A.live, cnt->oov_head, cnt->oov_tail, blockIdx.x * 256u + threadIdx.x, phys);
-    const int before = block_rank256(lv, part);
-    if (lv) {
-        const size_t j = (size_t)new_head + bc[blockIdx.x] + before;
-        copy_row(A.rows, phys, B.rows, j);
-        B.live[j] = 1;
-    }
-}
-__global__ void k_oov_set_span(Counters* cnt, int new_head) { cnt->oov_head = new_head; cnt->oov_tail = new_head + cnt->oov_live; }
-
 // end of the fuse stage: nbSupersurfels -= nbRemoved (supersurfel_fusion.cu:474), publish the
 // counters to the host-mapped mailbox, reset the per-frame ones for the next frame
 // finalise_counters: the frame's counters become final in device memory (cnt[0] = the values the next frame starts
@@ -1859,304 +1465,14 @@ __device__ __forceinline__ Counters finalise_counters(Counters* cnt, Counters c,
     return c;
 }
 __device__ __forceinline__ void mailbox_counters(const Counters& c, Mailbox* mb, unsigned long long seq) {
-    int* dst = reinterpret_cast<int*>(&mb->cnt);
-    const int* src = reinterpret_cast<const int*>(&c);
-    unsigned long long check = seq;
-    for (int i = 0; i < (int)(sizeof(Counters) / sizeof(int)); i++) {
-        __hip_atomic_store(&dst[i], src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        check += (unsigned long long)(unsigned int)src[i];
-    }
-    __hip_atomic_store(&mb->cnt_check, check, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // payload write-through stores acknowledged
-    __hip_atomic_store(&mb->cnt_seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    int_record_store(reinterpret_cast<int*>(&mb->cnt), reinterpret_cast<const int*>(&c), MAILBOX_COUNTER_WORDS, &mb->cnt_check, &mb->cnt_seq, seq);
 }
 __device__ __forceinline__ void publish_counters_value(Counters* cnt, Counters c, int shrink_by_removed, Mailbox* mb, unsigned long long seq) {
     mailbox_counters(finalise_counters(cnt, c, shrink_by_removed), mb, seq);
 }
-// a 29-value device record (e.g. the rank-reduced ICP system) -> mailbox, as the ICP kernel's tail does
-__global__ void k_publish_icp(const long long* __restrict__ rec, Mailbox* mb, unsigned long long seq) {
-    __shared__ unsigned long long pay[30];
-    long long v = 0;
-    if (threadIdx.x < 29) { v = rec[threadIdx.x]; pay[threadIdx.x] = (unsigned long long)v; }
-    const unsigned long long check = (unsigned long long)wsum64(v) + seq;
-    if (threadIdx.x == 0) pay[29] = check;
-    __syncthreads();
-    if (threadIdx.x < 40)
-        __hip_atomic_store(&mb->icp_rec[threadIdx.x], SSF_ICP_REC_WORD(threadIdx.x, pay, seq), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__global__ void k_publish_all_counts(const int* __restrict__ all5, int n, Mailbox* mb, unsigned long long seq) {
-    unsigned long long part = 0;
-    for (int i = threadIdx.x; i < n; i += 64) {
-        const int v = all5[i];
-        __hip_atomic_store(&mb->all_cnt[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        part += (unsigned long long)(unsigned int)v;
-    }
-    const unsigned long long check = (unsigned long long)wsum64((long long)part) + seq;
-    if (threadIdx.x == 0) __hip_atomic_store(&mb->all_check, check, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (threadIdx.x == 0) __hip_atomic_store(&mb->all_seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 __global__ void k_publish_counts(Counters* cnt, int shrink_by_removed, Mailbox* mb, unsigned long long seq) {
     publish_counters_value(cnt, *cnt, shrink_by_removed, mb, seq);
 }
-
-// the three row streams of the orientations -> packed row-major Mat33 (the reference's layout, supersurfels.hpp:37)
-__global__ void k_pack_orient(SurfelSoA s, int n, float* __restrict__ out9) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const V3 a = ld3(s.r0, i), b = ld3(s.r1, i), c = ld3(s.r2, i);
-    float* o = out9 + 9 * (size_t)i;
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = b.x; o[4] = b.y; o[5] = b.z; o[6] = c.x; o[7] = c.y; o[8] = c.z;
-}
-void launch_pack_orient(hipStream_t st, SurfelSoA s, int n, float* out9) {
-    if (n > 0) hipLaunchKernelGGL(k_pack_orient, dim3((n + 255) / 256), dim3(256), 0, st, s, n, out9);
-}
-__global__ void k_lab_refresh(SurfelSoA s, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) st3(s.lab, i, rgb_to_lab(ld3(s.col, i)));
-}
-
-// ---- deformation apply ("next" row) -----------------------------------------------------------------
-// rotMatToQuat matrix_math.cuh:529-618; quatToRotMat :512-527 (its wy = q.w*q.z is reproduced)
-// The nodes of the deformation graph as ONE 64-BYTE RECORD each (round 6): (g.xyz, R00) (t.xyz, R01) (R02, R10, R11, R12) (R20, R21,
-// R22, 0) -- a supersurfel's four nodes are 4 x 4 whole 16-byte loads, each record one aligned 64-byte piece of a line, the table
-// 1.28 MB at 20 k nodes.  The node's quaternion (rotMatToQuat: four branches, an IEEE sqrt and a divide) is worked out per row and
-// node, as the reference does (deformation_graph_kernels.cu:44-52) -- the same operations on the same operands, so the same bits.
-// Measured (tools/deform_probe.py, profiles/deformation_r06.txt, 1 M rows, N / 50 nodes): rounds 2-5 kept a 96-byte record with the
-// quaternion precomputed (five gathers per node): 75 us with uniformly random node indices, of which 35 us were the gathers (nodes
-// 0 / 1 only: 40 us) -- this form: 60 us; records padded to 128 bytes: 85 (the table's footprint in L2 matters, not lines per
-// record); non-temporal row accesses: no change; one or two nodes per round at 8 / 5 waves per SIMD: 68-88.  With node indices that
-// follow the row order (what a time-ordered graph gives rows in arrival order) every form runs at 40-42 us = 0.52-0.55 of HBM peak.
-__global__ __launch_bounds__(256) void k_pack_nodes(int m, const float* __restrict__ npos, const float* __restrict__ nrot,
-                                                    const float* __restrict__ ntrans, float4* __restrict__ nodes) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= m) return;
-    const V3 g = ld3(npos, k), t = ld3(ntrans, k);
-    float4* o = nodes + 4 * (size_t)k;
-    o[0] = make_float4(g.x, g.y, g.z, nrot[9 * k]); o[1] = make_float4(t.x, t.y, t.z, nrot[9 * k + 1]);
-    o[2] = make_float4(nrot[9 * k + 2], nrot[9 * k + 3], nrot[9 * k + 4], nrot[9 * k + 5]);
-    o[3] = make_float4(nrot[9 * k + 6], nrot[9 * k + 7], nrot[9 * k + 8], 0.f);
-}
-__global__ __launch_bounds__(256) void k_deformation(SurfelSoA M, int n, const float4* __restrict__ nodes,
-                                                     const float* __restrict__ w4, const int32_t* __restrict__ idx4) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const V3 pi = ld3(M.pos, i);
-    const int4 id = reinterpret_cast<const int4*>(idx4)[i];
-    const float4 w = reinterpret_cast<const float4*>(w4)[i];
-    const int node[4] = {id.x, id.y, id.z, id.w};
-    const float wv[4] = {w.x, w.y, w.z, w.w};
-    float4 rec[4][4];
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) rec[k][j] = nodes[4 * (size_t)node[k] + j];       // all sixteen gathers in one round
-    V3 po = v3(0, 0, 0);
-    float bq[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float wk = wv[k];
-        const V3 gk = v3(rec[k][0].x, rec[k][0].y, rec[k][0].z), tk = v3(rec[k][1].x, rec[k][1].y, rec[k][1].z);
-        const M3 Rk = m3(v3(rec[k][0].w, rec[k][1].w, rec[k][2].x), v3(rec[k][2].y, rec[k][2].z, rec[k][2].w),
-                         v3(rec[k][3].x, rec[k][3].y, rec[k][3].z));
-        // rot_to_quat (ssf_math.hpp) with its result in named scalars: through the array the compiler kept it in scratch
-        float s_, qx, qy, qz, qw; const float tr = (Rk.r0.x + Rk.r1.y) + Rk.r2.z;
-        if (tr > 0) { s_ = sqrtf(tr + 1); qw = 0.5f * s_; s_ = 0.5f / s_; qx = (Rk.r2.y - Rk.r1.z) * s_; qy = (Rk.r0.z - Rk.r2.x) * s_; qz = (Rk.r1.x - Rk.r0.y) * s_; }
-        else {
-            int ii = 0;
-            if (Rk.r1.y > Rk.r0.x) ii = 1;
-            if (Rk.r2.z > Rk.r0.x || Rk.r2.z > Rk.r1.y) ii = 2;
-            if (ii == 0) { s_ = sqrtf(((1.0f + Rk.r0.x) - Rk.r1.y) - Rk.r2.z); qx = 0.5f * s_; s_ = 0.5f / s_; qw = (Rk.r2.y - Rk.r1.z) * s_; qy = (Rk.r0.y + Rk.r1.x) * s_; qz = (Rk.r0.z + Rk.r2.x) * s_; }
-            else if (ii == 1) { s_ = sqrtf(((1.0f + Rk.r1.y) - Rk.r0.x) - Rk.r2.z); qy = 0.5f * s_; s_ = 0.5f / s_; qw = (Rk.r0.z - Rk.r2.x) * s_; qx = (Rk.r0.y + Rk.r1.x) * s_; qz = (Rk.r1.z + Rk.r2.y) * s_; }
-            else { s_ = sqrtf(((1.0f + Rk.r2.z) - Rk.r0.x) - Rk.r1.y); qz = 0.5f * s_; s_ = 0.5f / s_; qw = (Rk.r1.x - Rk.r0.y) * s_; qx = (Rk.r0.z + Rk.r2.x) * s_; qy = (Rk.r1.z + Rk.r2.y) * s_; }
-        }
-        po = add(po, scale(wk, add(add(m3_mulv(Rk, sub(pi, gk)), gk), tk)));
-        bq[0] += wk * qx; bq[1] += wk * qy; bq[2] += wk * qz; bq[3] += wk * qw;
-    }
-    const float len = sqrtf(((bq[0] * bq[0] + bq[1] * bq[1]) + bq[2] * bq[2]) + bq[3] * bq[3]);
-    const float inv = 1.0f / len;
-#pragma unroll
-    for (int a = 0; a < 4; a++) bq[a] *= inv;
-    const M3 av = quat_to_rot_quirk(bq);
-    const M3 avT = m3_transpose(av);
-    st3(M.r0, i, row_mul(ld3(M.r0, i), avT));
-    st3(M.r1, i, row_mul(ld3(M.r1, i), avT));
-    st3(M.r2, i, row_mul(ld3(M.r2, i), avT));
-    st6(M.shape, i, rot_sym(av, ld6(M.shape, i)));
-    st3(M.pos, i, po);
-}
-
-// ---- peer-to-peer exchanges of the fuse stage (ssf_device.hpp: P2PView) ----------------------------------------------------
-// shard sizes: one self-validating line per rank (Counters::last, checksum, sequence number) -> every peer; the lines of
-// all ranks -> the host mailbox (as k_publish_all_counts).  One wave.
-__global__ void k_p2p_counts(P2PView pv, const Counters* __restrict__ cnt, Mailbox* mb, unsigned long long all_seq) {
-    const int l = lane();
-    const unsigned long long seq = pv.seq;
-    const int par = (int)(seq & 1ull);
-    const unsigned int a = (unsigned int)cnt->last[0], b = (unsigned int)cnt->last[1], c = (unsigned int)cnt->last[2],
-                       d = (unsigned int)cnt->last[3], e = (unsigned int)cnt->last[4];
-    const unsigned long long w0 = a | ((unsigned long long)b << 32), w1 = c | ((unsigned long long)d << 32), w2 = e;
-    const unsigned long long mine_word = l == 0 ? w0 : l == 1 ? w1 : l == 2 ? w2 : l == 6 ? w0 + w1 + w2 + seq : l == 7 ? seq : 0ull;
-#pragma unroll
-    for (int r = 0; r < SSF_P2P_MAX_RANKS; r++) {
-        if (r >= pv.nranks || r == pv.me) continue;
-        unsigned long long* dst = reinterpret_cast<unsigned long long*>(pv.peer[r] + p2p_off_cnt(par, pv.me));
-        if (l < 8) __hip_atomic_store(&dst[l], mine_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    unsigned char* mine = p2p_peer(pv, pv.me);
-    unsigned long long part = 0;
-    P2PDeadline deadline(pv);
-    for (int r = 0; r < pv.nranks; r++) {
-        unsigned long long w = mine_word;
-        if (r != pv.me) {
-            const unsigned long long* src = reinterpret_cast<const unsigned long long*>(mine + p2p_off_cnt(par, r));
-            for (;;) {
-                w = l < 8 ? __hip_atomic_load(&src[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0ull;
-                const unsigned long long sum = (unsigned long long)wsum64(l < 3 ? (long long)w : 0ll) + seq;
-                if (shfl_u64(w, 7) == seq && shfl_u64(w, 6) == sum) break;
-                if (deadline.expired()) return;
-            }
-        }
-        if (l < 3) {
-            const int lo = (int)(unsigned int)w, hi = (int)(unsigned int)(w >> 32);
-            __hip_atomic_store(&mb->all_cnt[5 * r + 2 * l], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            part += (unsigned long long)(unsigned int)lo;
-            if (l < 2) { __hip_atomic_store(&mb->all_cnt[5 * r + 2 * l + 1], hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); part += (unsigned long long)(unsigned int)hi; }
-        }
-    }
-    const unsigned long long check = (unsigned long long)wsum64((long long)part) + all_seq;
-    if (l == 0) __hip_atomic_store(&mb->all_check, check, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (l == 0) __hip_atomic_store(&mb->all_seq, all_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-// thread 0: every peer's flag line of `kind` carries pv.seq (its data stores were acknowledged before the flag left)
-__device__ __forceinline__ bool p2p_wait_flags(const P2PView& pv, int kind) {
-    unsigned char* mine = p2p_peer(pv, pv.me);
-    const int par = (int)(pv.seq & 1ull);
-    P2PDeadline deadline(pv);
-    for (int r = 0; r < pv.nranks; r++) {
-        if (r == pv.me) continue;
-        const unsigned long long* f = reinterpret_cast<const unsigned long long*>(mine + p2p_off_flag(kind, par, r));
-        while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) != pv.seq)
-            if (deadline.expired()) return false;
-    }
-    return true;
-}
-__device__ __forceinline__ void p2p_raise_flags(const P2PView& pv, int kind) {       // threads 0..nranks-1, after a barrier
-    const int par = (int)(pv.seq & 1ull);
-    const int r = threadIdx.x;
-    if (r < pv.nranks && r != pv.me)
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(p2p_peer(pv, r) + p2p_off_flag(kind, par, pv.me)), pv.seq,
-                           __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-// association tables: this rank's best[] / matched[] -> every peer, then best := MIN, matched := OR over the ranks.
-// One workgroup (S entries of 9 bytes).
-__device__ __forceinline__ void p2p_assoc_exchange(const P2PView& pv, unsigned long long* __restrict__ best, uint8_t* __restrict__ matched, int* s_ok, Mailbox* mb) {
-    const int par = (int)(pv.seq & 1ull), S = pv.S;
-    // (own tables: device-scope atomic loads -- inside k_match they were written by other workgroups of this launch)
-#pragma unroll
-    for (int r = 0; r < SSF_P2P_MAX_RANKS; r++) {
-        if (r >= pv.nranks || r == pv.me) continue;
-        unsigned long long* db = reinterpret_cast<unsigned long long*>(pv.peer[r] + p2p_off_best(S, par, pv.me));
-        uint8_t* dm = pv.peer[r] + p2p_off_matched(S, par, pv.me);
-        // (returning exchanges, not stores: what comes back is the proof that the word has landed in the peer's memory
-        // before this rank raises its flag -- see atomic_add_done)
-        unsigned int* dm32 = reinterpret_cast<unsigned int*>(dm);
-        const unsigned int* m32 = reinterpret_cast<const unsigned int*>(matched);
-        unsigned long long sink = 0;
-        for (int i = threadIdx.x; i < S; i += blockDim.x)
-            sink ^= __hip_atomic_exchange(&db[i], __hip_atomic_load(&best[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        for (int i = threadIdx.x; i < (S + 3) / 4; i += blockDim.x)
-            sink ^= __hip_atomic_exchange(&dm32[i], __hip_atomic_load(&m32[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        asm volatile("" :: "v"(sink));
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    p2p_raise_flags(pv, P2P_FLAG_ASSOC);
-    if (threadIdx.x == 0) {
-        *s_ok = p2p_wait_flags(pv, P2P_FLAG_ASSOC) ? 1 : 0;
-        if (!*s_ok) __hip_atomic_store(&mb->p2p_timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    __syncthreads();
-    if (!*s_ok) return;
-    unsigned char* mine = p2p_peer(pv, pv.me);
-    for (int i = threadIdx.x; i < S; i += blockDim.x) {
-        unsigned long long b = __hip_atomic_load(&best[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint8_t m = __hip_atomic_load(&matched[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (int r = 0; r < pv.nranks; r++) {
-            if (r == pv.me) continue;
-            const unsigned long long* sb = reinterpret_cast<const unsigned long long*>(mine + p2p_off_best(S, par, r));
-            const uint8_t* sm = mine + p2p_off_matched(S, par, r);
-            const unsigned long long ob = __hip_atomic_load(&sb[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            const uint8_t om = __hip_atomic_load(&sm[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            b = ob < b ? ob : b; m = om > m ? om : m;
-        }
-        best[i] = b; matched[i] = m;
-    }
-}
-__global__ __launch_bounds__(1024) void k_p2p_assoc(P2PView pv, unsigned long long* __restrict__ best, uint8_t* __restrict__ matched, Mailbox* mb) {
-    __shared__ int s_ok;
-    p2p_assoc_exchange(pv, best, matched, &s_ok, mb);
-}
-// migrant table: slot f of this rank's table -> slot f of [parity][me] in every peer (an empty slot sends its first two
-// words only); the last workgroup to finish raises the flags.  One thread per slot.
-__global__ __launch_bounds__(256) void k_p2p_migr_share(P2PView pv, const int32_t* __restrict__ table, unsigned int* ticket) {
-    const int par = (int)(pv.seq & 1ull), S = pv.S;
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f < S) {
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(table + (size_t)SSF_MIGRANT_WORDS * f);
-        unsigned long long w[SSF_MIGRANT_WORDS / 2];
-        w[0] = src[0];
-        const bool full = (unsigned int)w[0] != 0u;
-#pragma unroll
-        for (int k = 1; k < SSF_MIGRANT_WORDS / 2; k++) w[k] = full ? src[k] : 0ull;
-#pragma unroll
-        for (int r = 0; r < SSF_P2P_MAX_RANKS; r++) {
-            if (r >= pv.nranks || r == pv.me) continue;
-            unsigned long long* dst = reinterpret_cast<unsigned long long*>(pv.peer[r] + p2p_off_migr(S, par, pv.me)) + (size_t)(SSF_MIGRANT_WORDS / 2) * f;
-            unsigned long long sink = __hip_atomic_exchange(&dst[0], w[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);     // (returning: see p2p_assoc_exchange)
-            if (full) {
-#pragma unroll
-                for (int k = 1; k < SSF_MIGRANT_WORDS / 2; k++) sink ^= __hip_atomic_exchange(&dst[k], w[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            asm volatile("" :: "v"(sink));
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    __shared__ int s_last;
-    if (threadIdx.x == 0) s_last = grid_arrive(ticket);
-    __syncthreads();
-    if (s_last) p2p_raise_flags(pv, P2P_FLAG_MIGR);
-}
-// ... and the peers' slots are added into this rank's table (at most one rank fills a slot: the sum is the union)
-__global__ __launch_bounds__(256) void k_p2p_migr_gather(P2PView pv, int32_t* __restrict__ table, Mailbox* mb) {
-    const int par = (int)(pv.seq & 1ull), S = pv.S;
-    __shared__ int s_ok;
-    if (threadIdx.x == 0) {
-        s_ok = p2p_wait_flags(pv, P2P_FLAG_MIGR) ? 1 : 0;
-        if (!s_ok) __hip_atomic_store(&mb->p2p_timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    __syncthreads();
-    if (!s_ok) return;
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= S) return;
-    unsigned char* mine = p2p_peer(pv, pv.me);
-    int32_t* own = table + (size_t)SSF_MIGRANT_WORDS * f;
-    for (int r = 0; r < pv.nranks; r++) {
-        if (r == pv.me) continue;
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(mine + p2p_off_migr(S, par, r)) + (size_t)(SSF_MIGRANT_WORDS / 2) * f;
-        const unsigned long long w0 = __hip_atomic_load(&src[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if ((unsigned int)w0 == 0u) continue;
-        own[0] += (int32_t)(unsigned int)w0; own[1] += (int32_t)(unsigned int)(w0 >> 32);
-#pragma unroll
-        for (int k = 1; k < SSF_MIGRANT_WORDS / 2; k++) {
-            const unsigned long long w = __hip_atomic_load(&src[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            own[2 * k] += (int32_t)(unsigned int)w; own[2 * k + 1] += (int32_t)(unsigned int)(w >> 32);
-        }
-    }
-}
-
 // ---- launchers -----------------------------------------------------------------------------------
 // measurement arms of k_icp (lab build, environment read once): 0 = the product's form; only that one can be told to do the
 // association (SSF_ICP_GO_MATCH) -- the host asks before it sends that word
@@ -2255,60 +1571,8 @@ void launch_move_rows(hipStream_t st, SurfelSoA vis_src, SurfelSoA vis_dst, OovS
     hipLaunchKernelGGL(kernel, dim3(nb_vis + nb_oov), dim3(256), 0, st, vis_src, vis_dst, oov, state_vis, state_oov, bc_oov, ws, cnt, nb_vis,
                        next ? *next : NextIcp{}, mb, cnt_seq, next_pv ? *next_pv : P2PView{}, mt);
 }
-void launch_oov_compact(hipStream_t st, OovStore src, OovStore dst, int span_upper, int new_head, uint32_t* bc_oov, Counters* cnt,
-                        int set_span) {
-    const int nb = (span_upper + 255) / 256;
-    ScopedKernel sk("oov_compact", st);
-    if (nb > 0) {
-        hipLaunchKernelGGL(k_oov_count, dim3(nb), dim3(256), 0, st, src, bc_oov, cnt);
-        hipLaunchKernelGGL(k_oov_scan, dim3(1), dim3(1024), 0, st, bc_oov, nb, cnt);
-        hipLaunchKernelGGL(k_oov_compact, dim3(nb), dim3(256), 0, st, src, dst, bc_oov, new_head, cnt);
-    }
-    if (set_span) hipLaunchKernelGGL(k_oov_set_span, dim3(1), dim3(1), 0, st, cnt, new_head);
-}
-void launch_align(hipStream_t st, const Cam& cam, const float* spos, const float* slab, const float* snrm, const float* sconf,
-                  int n, SurfelSoA frame, const int32_t* label, const float* plane_depth, Rt T, long long* out40) {
-    ScopedKernel sk("align_iteration", st);
-    hipLaunchKernelGGL(k_align, dim3(1), dim3(1024), 0, st, cam, spos, slab, snrm, sconf, n, frame, label, plane_depth, T, out40);
-}
-void launch_fern_codes(hipStream_t st, const uint8_t* rgb, const float* depth, int W, int H, const uint32_t* fpos,
-                       const uint8_t* frgb, const float* fdepth, int n, uint8_t* codes) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_fern_codes, dim3((n + 63) / 64), dim3(64), 0, st, rgb, depth, W, H, fpos, frgb, fdepth, n, codes);
-}
-void launch_p2p_counts(hipStream_t st, const P2PView& pv, const Counters* cnt, Mailbox* mb, unsigned long long all_seq) {
-    ScopedKernel sk("p2p_counts", st);
-    hipLaunchKernelGGL(k_p2p_counts, dim3(1), dim3(64), 0, st, pv, cnt, mb, all_seq);
-}
-void launch_p2p_assoc(hipStream_t st, const P2PView& pv, unsigned long long* best, uint8_t* matched, Mailbox* mb) {
-    ScopedKernel sk("p2p_assoc", st);
-    hipLaunchKernelGGL(k_p2p_assoc, dim3(1), dim3(1024), 0, st, pv, best, matched, mb);
-}
-void launch_p2p_migrants(hipStream_t st, const P2PView& pv, int32_t* table, unsigned int* ticket, Mailbox* mb) {
-    ScopedKernel sk("p2p_migrants", st);
-    const int grid = (pv.S + 255) / 256;
-    hipLaunchKernelGGL(k_p2p_migr_share, dim3(grid), dim3(256), 0, st, pv, table, ticket);
-    hipLaunchKernelGGL(k_p2p_migr_gather, dim3(grid), dim3(256), 0, st, pv, table, mb);
-}
-void launch_publish_icp(hipStream_t st, const long long* rec, Mailbox* mb, unsigned long long seq) {
-    hipLaunchKernelGGL(k_publish_icp, dim3(1), dim3(64), 0, st, rec, mb, seq);
-}
-void launch_publish_all_counts(hipStream_t st, const int* all5, int nranks, Mailbox* mb, unsigned long long seq) {
-    hipLaunchKernelGGL(k_publish_all_counts, dim3(1), dim3(64), 0, st, all5, 5 * nranks, mb, seq);
-}
 void launch_publish_counts(hipStream_t st, Counters* cnt, int shrink_by_removed, Mailbox* mb, unsigned long long seq) {
     hipLaunchKernelGGL(k_publish_counts, dim3(1), dim3(1), 0, st, cnt, shrink_by_removed, mb, seq);
-}
-void launch_lab_refresh(hipStream_t st, SurfelSoA s, int n) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_lab_refresh, dim3((n + 255) / 256), dim3(256), 0, st, s, n);
-}
-void launch_deformation(hipStream_t st, SurfelSoA model, int n, int m, const float* npos, const float* nrot,
-                        const float* ntrans, float* nodes16, const float* w4, const int32_t* idx4) {
-    if (n <= 0) return;
-    ScopedKernel sk("apply_deformation", st);
-    hipLaunchKernelGGL(k_pack_nodes, dim3((m + 255) / 256), dim3(256), 0, st, m, npos, nrot, ntrans, reinterpret_cast<float4*>(nodes16));
-    hipLaunchKernelGGL(k_deformation, dim3((n + 255) / 256), dim3(256), 0, st, model, n, reinterpret_cast<const float4*>(nodes16), w4, idx4);
 }
 
 }  // namespace ssf

@@ -80,7 +80,8 @@ def test_the_product_library_reads_no_environment_variable(product_lib):
     import subprocess
     out = subprocess.run(["strings", product_lib.path], stdout=subprocess.PIPE, text=True).stdout.splitlines()
     assert [l for l in out if l.startswith("SSF_")] == []
-    for src in ("ssf_extract.hip", "ssf_pass_tile.hpp", "ssf_track_fuse.hip", "ssf_tile_rows.inc", "ssf_host.hip", "ssf_device.hpp", "ssf_math.hpp",
+    for src in ("ssf_extract.hip", "ssf_pass_tile.hpp", "ssf_track_fuse.hip", "ssf_upkeep.hip", "ssf_p2p.hip", "ssf_rows.hpp", "ssf_mailbox.hpp", "ssf_tile_rows.inc",
+                "ssf_host.hip", "ssf_device.hpp", "ssf_math.hpp",
                 "ssf_handle.hpp", "ssf_render.hip", "ssf_graph.hip", "ssf_graph_solve.hip", "ssf_keyframes.hip", "ssf_slots.hpp",
                 "ssf_exchange.hip", "ssf_exchange.hpp", "ssf_testing.hip", "ssf_solvers.hpp"):
         txt = open(os.path.join(ROOT, "supersurfel_fusion_amd", "csrc", src)).read()
@@ -101,7 +102,7 @@ def test_the_product_exports_no_probe_entry_points(product_lib):
     assert exported == hooks, sorted(set(exported) ^ set(hooks))
     dev = open(os.path.join(ROOT, "supersurfel_fusion_amd", "csrc", "ssf_device.hpp")).read()
     assert "#define SSF_PROBE(dbg, bits) (false)" in dev
-    for src in ("ssf_extract.hip", "ssf_track_fuse.hip"):
+    for src in ("ssf_extract.hip", "ssf_track_fuse.hip", "ssf_upkeep.hip", "ssf_p2p.hip"):
         body = open(os.path.join(ROOT, "supersurfel_fusion_amd", "csrc", src)).read()
         assert not re.search(r"\bdbg\s*&\s*\d", body), src          # a probe bit tested outside SSF_PROBE
 

@@ -25,7 +25,7 @@ def main():
     extra = sys.argv[1:]
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        for src in ("ssf_extract.hip", "ssf_track_fuse.hip", "ssf_slots.hip", "ssf_render.hip", "ssf_query.hip", "ssf_navgrid.hip",
+        for src in ("ssf_extract.hip", "ssf_track_fuse.hip", "ssf_upkeep.hip", "ssf_p2p.hip", "ssf_slots.hip", "ssf_render.hip", "ssf_query.hip", "ssf_navgrid.hip",
                     "ssf_raycast.hip", "ssf_graph.hip", "ssf_graph_solve.hip", "ssf_keyframes.hip"):
             r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + extra + ["-c", src, "-o", os.path.join(tmp, src + ".o")],
                                cwd=CSRC, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
