@@ -22,6 +22,7 @@
 #include <cstddef>
 #include "ssf_math.hpp"
 #include "ssf_mailbox.hpp"
+#include "ssf_tile_geometry.hpp"
 #include "../../include/ssf.h"
 #include "../../include/ssf_input.h"
 #include "../../include/ssf_dynamic.h"
@@ -104,13 +105,9 @@ struct SegParams {
     // per tile of the relabelling passes' grid, [OX = 0 | OX = 1]: the window of grid cells around the tile and whether the tile
     // lies inside the image (pass_geometry_table: built once per handle on the host; k_update_pass fetches one 8-byte entry
     // instead of working the same ~60 scalar instructions out in every wave of every pass)
-    const uint2* pass_geom; int pass_ntile;
+    const PassGeomEntry* pass_geom; int pass_ntile;
     int win_cells_max;    // the largest cell window of a tile of the plain 32 x 32 grid (tile_window_cells_max): <= 36 selects the small-LDS instantiations of the tile kernels
 };
-int tile_window_cells_max(const SegParams& p);
-// entry: x = (wcx0 & 0xFFFF) | (wcy0 << 16) (first window cell, may be negative), y = nwx | nwy << 8 | interior << 16 (nwx = nwy = 0: no window)
-int pass_geometry_entries(int W, int H);                                  // 2 x tiles of the shifted 32-wide grid
-void pass_geometry_table(const SegParams& p, uint2* host_out);
 
 // One relabelled pixel of a pass, replayed by the next pass into the lagging sums buffer.
 // flags: 1 = label moved (from -> to), 2 = add the disparity terms to `to`, 4 = remove them from `from`
@@ -205,9 +202,6 @@ struct Mailbox {
     // peer-to-peer exchanges: set (never cleared) when a bounded wait for a peer ran out inside a kernel that has no record
     // of its own to withhold (association, migrant table); the host turns it into SSF_ERR_DEVICE at the end of the frame
     unsigned int p2p_timeout;
-    // the team form of the relabelling passes (lab build): set (never cleared by the device) when a launch's workgroups could not
-    // all become resident within its bound and gave up (the frames of that batch are invalid; the host reports SSF_ERR_DEVICE)
-    unsigned int extract_abort;
 };
 #ifndef SSF_ICP_REPLICAS
 #define SSF_ICP_REPLICAS 8
@@ -218,16 +212,7 @@ struct Mailbox {
 // frame k of the batch is frame number epoch0 + k of this handle (keys its RANSAC draws)
 void launch_ingest(hipStream_t st, const SegParams& p, const BatchIn& in, FrameMaps& m, int nb, uint32_t epoch0);
 // pass number k (0-based over the whole frame) selects label/sums/log buffers: see FrameMaps
-int pass_tile_npx(int nb);     // pass pixels per thread: 1 (32-wide relabelling tiles; the 64-wide form was measured and removed)
 void launch_update_pass(hipStream_t st, const SegParams& p, FrameMaps& m, int nb, int k, int ox, int oy, bool rgbd, int dbg = 0);
-// The passes k0 .. k1 - 1 of a batch in ONE launch whose workgroups stay, a frame per XCD, meeting inside their XCD between passes
-// (k_passes_team in ssf_extract.hip).  d_pas: the context's table of per-pass arguments (pass_args_table, pass_args_bytes(kmax) bytes
-// uploaded once); d_ws: pass_team_ws_bytes() of device memory ZEROED in stream order in front of every launch.
-size_t pass_team_ws_bytes();
-size_t pass_args_bytes(int kmax);
-void pass_args_table(const SegParams& p, const FrameMaps& m, int kmax, void* host_out);
-void launch_update_passes_team(hipStream_t st, const SegParams& p, FrameMaps& m, int nb, int k0, int k1, bool rgbd, const void* d_pas, void* d_ws,
-                               unsigned int* abort_flag);
 void launch_init_samples(hipStream_t st, const SegParams& p, FrameMaps& m, int nb, int true_buf);
 void launch_eval_samples(hipStream_t st, const SegParams& p, FrameMaps& m, int nb);
 void launch_init_disp(hipStream_t st, const SegParams& p, FrameMaps& m, int nb, bool ransac);

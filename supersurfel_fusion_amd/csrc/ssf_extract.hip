@@ -119,38 +119,22 @@ __device__ __forceinline__ SpRow ld_global_row(const SpRow* p) {
     r.size = c.x; r.pad0 = c.y; r.pad1 = c.z; r.pad2 = c.w;
     return r;
 }
-// A load that must see what ANOTHER compute unit of this XCD stored earlier in the same launch (k_passes_team: a pass reads what
-// the pass before wrote): past the compute unit's vector L1, served by the XCD's L2 (the sc1 bit; an L1 invalidate at workgroup
-// scope -- buffer_inv sc0 -- does nothing on this part and one at agent scope costs 8-15 us: tools/probe/xcd_team_barrier.hip).
-// COH = false: an ordinary load.  16-byte values travel as two 8-byte loads (4-byte alignment suffices for the hardware).
-template <bool COH, typename T> __device__ __forceinline__ T ld_coh(const T* p) {
-    if (!COH) return *p;
-    T out;
-    if (sizeof(T) == 1) { const unsigned char v = __hip_atomic_load(reinterpret_cast<const unsigned char*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __builtin_memcpy(&out, &v, 1); }
-    else if (sizeof(T) == 4) { const unsigned int v = __hip_atomic_load(reinterpret_cast<const unsigned int*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __builtin_memcpy(&out, &v, 4); }
-    else if (sizeof(T) == 8) { const unsigned long long v = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __builtin_memcpy(&out, &v, 8); }
-    else {
-        static_assert(sizeof(T) == 1 || sizeof(T) == 4 || sizeof(T) == 8 || sizeof(T) == 16, "ld_coh: 1, 4, 8 or 16 bytes");
-        const unsigned long long* q = reinterpret_cast<const unsigned long long*>(p);
-        const unsigned long long v[2] = {__hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)};
-        __builtin_memcpy(&out, v, 16);
-    }
-    return out;
-}
-template <bool COH = false>
+// (a piece of a sums record, as the VALUE of a call: read in place -- `*rec` -- the same loads leave the plane-filter kernels with
+// the operands of one multiply swapped and the RGB-D pass with another schedule, profiles/pass_body_refactor.txt)
+template <typename T> __device__ __forceinline__ T ld_piece(const T* p) { return *p; }
 __device__ __forceinline__ SpRow row_from_sums(const SpSums& s, int k, bool with_planes, SpRow prev) {
     SpRow row = prev;
     // the record is read as whole 16-byte pieces (two cache lines per superpixel)
     const int4* __restrict__ rec = reinterpret_cast<const int4*>(&s.r[k]);
-    const int4 i0 = ld_coh<COH>(rec), i1 = ld_coh<COH>(rec + 1);             // sx sy sr sg | sb n dx dy
+    const int4 i0 = ld_piece(rec), i1 = ld_piece(rec + 1);             // sx sy sr sg | sb n dx dy
     const float n = (float)i1.y;
     row.cx = (float)i0.x / n; row.cy = (float)i0.y / n;
     row.r = (float)i0.z / n; row.g = (float)i0.w / n; row.b = (float)i1.x / n;
     row.size = n;
     if (with_planes) {
-        int dn_i = ld_coh<COH>(&s.r[k].dn);
+        int dn_i = ld_piece(&s.r[k].dn);
         const longlong2* __restrict__ q = reinterpret_cast<const longlong2*>(&s.r[k].dxx);
-        longlong2 q0 = ld_coh<COH>(q), q1 = ld_coh<COH>(q + 1), q2 = ld_coh<COH>(q + 2);         // dxx dyy | dxy dxd | dyd dd
+        longlong2 q0 = ld_piece(q), q1 = ld_piece(q + 1), q2 = ld_piece(q + 2);         // dxx dyy | dxy dxd | dyd dd
         // the whole record in ONE round trip: left alone, the compiler fetches dxd / dyd / dd only behind the first
         // test of the plane solve, a second dependent trip to memory in every RGB-D pass
         asm volatile("" : "+v"(dn_i), "+v"(q0.x), "+v"(q0.y), "+v"(q1.x), "+v"(q1.y), "+v"(q2.x), "+v"(q2.y));
@@ -169,22 +153,20 @@ __device__ __forceinline__ SpRow row_from_sums(const SpSums& s, int k, bool with
 }
 // the same in two independent halves, so that two waves of a workgroup can build a window row side by side (the plane
 // solve is a chain of three dependent IEEE divisions; the means are five independent ones): identical arithmetic
-template <bool COH = false>
 __device__ __forceinline__ void row_means_from_sums(const SpSums& s, int k, SpRow& row) {
     const int4* __restrict__ rec = reinterpret_cast<const int4*>(&s.r[k]);
-    const int4 i0 = ld_coh<COH>(rec), i1 = ld_coh<COH>(rec + 1);             // sx sy sr sg | sb n dx dy
+    const int4 i0 = ld_piece(rec), i1 = ld_piece(rec + 1);             // sx sy sr sg | sb n dx dy
     const float n = (float)i1.y;
     row.cx = (float)i0.x / n; row.cy = (float)i0.y / n;
     row.r = (float)i0.z / n; row.g = (float)i0.w / n; row.b = (float)i1.x / n;
     row.size = n;
 }
-template <bool COH = false>
 __device__ __forceinline__ void row_plane_from_sums(const SpSums& s, int k, float& ta, float& tb, float& tc) {
     const int4* __restrict__ rec = reinterpret_cast<const int4*>(&s.r[k]);
-    int4 i1 = ld_coh<COH>(rec + 1);
-    int dn_i = ld_coh<COH>(&s.r[k].dn);
+    int4 i1 = ld_piece(rec + 1);
+    int dn_i = ld_piece(&s.r[k].dn);
     const longlong2* __restrict__ q = reinterpret_cast<const longlong2*>(&s.r[k].dxx);
-    longlong2 q0 = ld_coh<COH>(q), q1 = ld_coh<COH>(q + 1), q2 = ld_coh<COH>(q + 2);         // dxx dyy | dxy dxd | dyd dd
+    longlong2 q0 = ld_piece(q), q1 = ld_piece(q + 1), q2 = ld_piece(q + 2);         // dxx dyy | dxy dxd | dyd dd
     asm volatile("" : "+v"(i1.z), "+v"(i1.w), "+v"(dn_i), "+v"(q0.x), "+v"(q0.y), "+v"(q1.x), "+v"(q1.y), "+v"(q2.x), "+v"(q2.y));
     const double inv = 1.0 / SSF_DISP_SCALE;
     const float dx = (float)i1.z, dy = (float)i1.w, dn = (float)dn_i;
@@ -195,10 +177,8 @@ __device__ __forceinline__ void row_plane_from_sums(const SpSums& s, int k, floa
         ta = 0.f; tb = 0.f; tc = __uint_as_float(0xFFE00000u);
     }
 }
-// ---- relabelling pass --------------------------------------------------------------------------
-#define TILE 32
+// ---- label tiles (TILE x TILE pixels, WIN_MAX: ssf_tile_geometry.hpp) ---------------------------------
 #define TW (TILE + 2)
-#define WIN_MAX 64
 #ifndef WIN_SMALL
 #define WIN_SMALL 36          // the window of a 32 x 32 tile at cell size 16 with its margin of two cells: (2 + 4)^2
 #endif
@@ -248,19 +228,13 @@ __device__ __forceinline__ int tile_boundary(const int* tile, int lx, int ly) { 
 
 // Window of grid cells around a 32x32 tile.  Superpixels stay close to their seed cell, so per-tile
 // LDS tables indexed by window cell serve (almost) every label of the tile; a label that drifted out
-// of the window takes an exact global-memory slow path.
-// x / p.cell for a pixel coordinate (0 <= x < 65536) without the 20-instruction integer division
-__device__ __forceinline__ int div_cell(const SegParams& p, int x) { return p.cell_magic ? (int)__umulhi((unsigned int)x, p.cell_magic) : x; }
+// of the window takes an exact global-memory slow path.  The window itself: tile_window (ssf_tile_geometry.hpp).
 struct CellWindow {
     int cx0, cy0, nwx, nwy, gx; float inv_gx; bool ok;
     __device__ __forceinline__ void init(const SegParams& p, int X0, int Y0, int max_entries) {
-        int margin = 2;
-        const int tcx0 = div_cell(p, X0), tcy0 = div_cell(p, Y0);
-        const int tcx1 = div_cell(p, min(X0 + TILE - 1, p.W - 1)), tcy1 = div_cell(p, min(Y0 + TILE - 1, p.H - 1));
-        while (margin > 0 && (tcx1 - tcx0 + 1 + 2 * margin) * (tcy1 - tcy0 + 1 + 2 * margin) > max_entries) margin--;
-        cx0 = tcx0 - margin; cy0 = tcy0 - margin;
-        nwx = tcx1 - tcx0 + 1 + 2 * margin; nwy = tcy1 - tcy0 + 1 + 2 * margin;
-        ok = nwx * nwy <= max_entries; gx = p.gx; inv_gx = 1.0f / (float)p.gx;
+        const TileWindow w = tile_window(p.cell_magic, X0, min(X0 + TILE - 1, p.W - 1), Y0, min(Y0 + TILE - 1, p.H - 1), max_entries);
+        cx0 = w.cx0; cy0 = w.cy0; nwx = w.nwx; nwy = w.nwy; ok = w.ok;
+        gx = p.gx; inv_gx = 1.0f / (float)p.gx;
     }
     __device__ __forceinline__ int size() const { return ok ? nwx * nwy : 0; }
     // window slot of a label, -1 when outside
@@ -287,84 +261,6 @@ __device__ __forceinline__ void disp_sums_add(const SpSums& s, int k, int x, int
     atomic_add_i64(&s.r[k].dyd, sign * fx64((double)((float)y * d), SSF_DISP_SCALE, SSF_DISP_LIM));
     atomic_add_i64(&s.r[k].dd, sign * fx64((double)d, SSF_DISP_SCALE, SSF_DISP_LIM));
 }
-// Field order of the per-window-superpixel LDS accumulators of a pass (15 exact integer sums).
-enum { F_SX, F_SY, F_SR, F_SG, F_SB, F_N, F_DX, F_DY, F_DN, F_DXX, F_DYY, F_DXY, F_DXD, F_DYD, F_DD, F_COUNT };
-__device__ __forceinline__ void lds_rgb(unsigned long long* a, int sign, int x, int y, uint32_t rgbf) {
-    lds_add_i64(&a[F_SX], sign * x); lds_add_i64(&a[F_SY], sign * y);
-    lds_add_i64(&a[F_SR], sign * (int)(rgbf & 255u)); lds_add_i64(&a[F_SG], sign * (int)((rgbf >> 8) & 255u));
-    lds_add_i64(&a[F_SB], sign * (int)((rgbf >> 16) & 255u)); lds_add_i64(&a[F_N], sign);
-}
-__device__ __forceinline__ void lds_disp(unsigned long long* a, int sign, int x, int y, float d) {
-    lds_add_i64(&a[F_DX], sign * x); lds_add_i64(&a[F_DY], sign * y); lds_add_i64(&a[F_DN], sign);
-    lds_add_i64(&a[F_DXX], (long long)sign * x * x); lds_add_i64(&a[F_DYY], (long long)sign * y * y);
-    lds_add_i64(&a[F_DXY], (long long)sign * x * y);
-    lds_add_i64(&a[F_DXD], sign * fx64((double)((float)x * d), SSF_DISP_SCALE, SSF_DISP_LIM));
-    lds_add_i64(&a[F_DYD], sign * fx64((double)((float)y * d), SSF_DISP_SCALE, SSF_DISP_LIM));
-    lds_add_i64(&a[F_DD], sign * fx64((double)d, SSF_DISP_SCALE, SSF_DISP_LIM));
-}
-__device__ __forceinline__ void flush_field(const SpSums& s, int l, int field, long long v) {
-    switch (field) {
-        case F_SX: atomicAdd(&s.r[l].sx, (int)v); break;
-        case F_SY: atomicAdd(&s.r[l].sy, (int)v); break;
-        case F_SR: atomicAdd(&s.r[l].sr, (int)v); break;
-        case F_SG: atomicAdd(&s.r[l].sg, (int)v); break;
-        case F_SB: atomicAdd(&s.r[l].sb, (int)v); break;
-        case F_N: atomicAdd(&s.r[l].n, (int)v); break;
-        case F_DX: atomicAdd(&s.r[l].dx, (int)v); break;
-        case F_DY: atomicAdd(&s.r[l].dy, (int)v); break;
-        case F_DN: atomicAdd(&s.r[l].dn, (int)v); break;
-        case F_DXX: atomic_add_i64(&s.r[l].dxx, v); break;
-        case F_DYY: atomic_add_i64(&s.r[l].dyy, v); break;
-        case F_DXY: atomic_add_i64(&s.r[l].dxy, v); break;
-        case F_DXD: atomic_add_i64(&s.r[l].dxd, v); break;
-        case F_DYD: atomic_add_i64(&s.r[l].dyd, v); break;
-        default: atomic_add_i64(&s.r[l].dd, v); break;
-    }
-}
-
-// One pass (OX,OY) of the boundary relabelling: updateTPSRGB_kernel / updateTPSRGBD_kernel,
-// TPS_RGBD_kernels.cuh:235-651.  256 threads own the 256 pass pixels of a 32x32 tile.
-//
-// Labels are updated IN PLACE.  A pass touches rows y = OY (mod 2) and columns x = 0,3 (mod 4) for
-// OX = 0 or x = 1,2 (mod 4) for OX = 1, i.e. horizontally adjacent PAIRS of pixels; everything else a
-// pass pixel looks at (rows y-1, y+1, the outer neighbours of its pair) is not modified in this pass.
-// The tile grid is shifted so that a pair never straddles two tiles (X0 = 2 mod 4 for OX = 0): a
-// workgroup snapshots its tile + halo into LDS, decides from the snapshot, and is the only writer of
-// the pass pixels it read -- exactly the "all reads before any write" schedule of the oracle (A1)
-// without a second label map or a copy of the untouched pixels.
-//
-// No merge launch between passes.  The exact sums are double buffered: pass k builds the superpixel
-// rows (means, plane) it needs straight from sums[k&1], which nothing writes during the pass, and
-// applies its relabelling deltas to sums[(k+1)&1] together with the replayed log of pass k-1 (the
-// deltas that buffer is still missing).  Integer adds commute, so the lagging buffer catches up
-// exactly.  The rows of the superpixels around the tile (a window of grid cells) are computed by
-// the first threads of the workgroup into LDS while the label tile is being staged; the energy
-// then reads rows from LDS.  Labels that have drifted out of the window take an exact slow path.
-// NPX = pass pixels per thread: the tile is 32 * NPX pixels wide (32 rows).  NPX = 2 halves the number of workgroups of a
-// launch: with 8 frames per launch the 32-wide grid is 2520 workgroups = 10080 waves, more than the 8192 the part
-// holds at once (a second, mostly empty round of workgroups); the 64-wide grid fits in one round and amortises the
-// window's row computation and the flush over twice the pixels.  NPX = 1 stays for single-frame launches (latency).
-// Instruction diet (round 3).  Counters + an experiment (150 extra vector instructions per wave: +2.3 us on a 20 us launch) show the
-// pass is bound by instruction ISSUE as much as by latency: 6.3 M wave-level VALU instructions per 8-frame RGB-D launch are
-// 10 us of the part's vector issue capacity.  Hence: the candidate labels of a pixel de-duplicated and compacted (the wave walks
-// 1-2 candidates instead of 4 directions), interior tiles staged without bounds tests and through one scalar base, the
-// connectivity guard as a bit mask + popcount, window slots by unsigned compares, the nine 32-bit sums in 32-bit LDS
-// accumulators, the disparity terms of a pixel converted once for both signs, the flush addressed by field offset
-// instead of a 15-way switch, the previous pass' log entry fetched without a branch (behind one, the compiler waited for
-// it -- a second dependent trip to memory -- before it requested the window's sums).
-// Global accesses of the pass as (uniform 64-bit base) + (32-bit BYTE offset in a vector register): the form the hardware
-// takes directly (`global_load_dword v, v_off, s[base]`).  Indexing a typed pointer with an integer makes the compiler
-// widen, shift and add in 64 bits per access (v_mad_i64_i32 / v_lshl_add_u64 and a zeroed high half): two or three
-// vector instructions and a register pair each, a dozen times per thread.  Every map of a frame is far below 4 GB.
-template <typename T> __device__ __forceinline__ T ld_off(const void* __restrict__ base, unsigned int byte_off) {
-    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-template <bool COH, typename T> __device__ __forceinline__ T ld_off_c(const void* __restrict__ base, unsigned int byte_off) {      // (see ld_coh)
-    return ld_coh<COH>(reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off));
-}
-template <typename T> __device__ __forceinline__ void st_off(void* __restrict__ base, unsigned int byte_off, const T& v) {
-    *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off) = v;
-}
 // XCD-aware tile order.  A launch's workgroups are dealt to the eight XCDs round-robin (workgroup b of the x-fastest linear
 // order runs on XCD b % 8: observed placement, only speed depends on it), so with tiles taken in grid order the neighbours
 // of a tile run on seven OTHER XCDs -- and every 128-byte line that two tiles share (the halo columns, the shifted tiles'
@@ -390,109 +286,29 @@ static inline TileOrder tile_order(dim3 grid) {
 }
 // the same order for the other tile kernels of the extract stage (round 6: k_eval_samples, k_init_disp, k_render_moments fetch a
 // label tile WITH its halo -- three 128-byte lines per tile row instead of one -- and share the inlier lines four tiles to a line;
-// in grid order the neighbours of a tile run on seven other XCDs and every one of those lines is pulled into several L2s)
+// in grid order the neighbours of a tile run on seven other XCDs and every one of those lines is pulled into several L2s).
+// They test the switch at run time; the pass (ssf_pass_tile.hpp) passes a constant in the product.
 #ifndef SSF_TILE_XCD
 #define SSF_TILE_XCD 1
 #endif
 struct TileIdx { unsigned int bx, by, bz; };
-__device__ __forceinline__ TileIdx tile_index(const TileOrder& ord) {
-    TileIdx t; t.bx = blockIdx.x; t.by = blockIdx.y; t.bz = blockIdx.z;
-    if (SSF_TILE_XCD && ord.xcd) {
+__device__ __forceinline__ void tile_index(const TileOrder& ord, bool xcd_order, unsigned int& bx, unsigned int& by, unsigned int& bz) {
+    bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
+    if (xcd_order) {
         const unsigned int lin = blockIdx.x + ord.ntx * blockIdx.y + ord.ntile * blockIdx.z;
         const unsigned int u = xcd_share(lin, ord.total);
-        t.bz = __umulhi(u, ord.magic_ntile);
-        const unsigned int r = u - t.bz * ord.ntile;
-        t.by = __umulhi(r, ord.magic_ntx); t.bx = r - t.by * ord.ntx;
-    }
-    return t;
-}
-#ifndef SSF_PASS_NPREV_RGBD
-#define SSF_PASS_NPREV_RGBD 1
-#endif
-#ifndef SSF_PASS_NPREV_RGB
-#define SSF_PASS_NPREV_RGB 1
-#endif
-#define PASS_F32 9                  // F_SX .. F_DN: 32-bit accumulators; F_DXX .. F_DD: 64-bit
-#define PASS_F64 (F_COUNT - PASS_F32)
-// accumulators of one window slot: 24 dwords = six 16-byte chunks -- the nine 32-bit sums (chunks 0-2, three dwords of padding),
-// then the six 64-bit sums (chunks 3-5; RGB passes never touch them).  Zeroed and scanned a chunk at a time.
-#define PASS_ACC_DW 24
-#define PASS_ACC_WIDE_DW 12
-// What a pass touches of a frame's working set, chosen on the HOST (round 5): the read / write sums buffer by the pass' parity, the
-// previous / current log by pass mod 3.  Selected in the kernel -- from FrameMaps, after shifting all of its ~30 pointers to the
-// batch slot -- it was ~50 scalar instructions of every wave's prologue (s_cselect chains + 64-bit adds); the counters put the
-// prologue at 205 of the RGB-D wave's 321 scalar instructions, and 150 extra scalar instructions per wave cost the 8-frame
-// launch 1.8 us (profiles/pass_issue_r05.txt): ONE scalar unit serves the four SIMDs of a compute unit, and this kernel is as
-// close to its issue limit as to the vector pipes'.
-struct PassArgs {
-    const SumRec* sr; SumRec* sw;                                      // sums[k & 1] (read), sums[(k + 1) & 1] (written)
-    const int4* pent; const float* pdis; const unsigned int* pcnt;     // log of pass k - 1
-    int4* cent; float* cdis; unsigned int* ccnt;                       // log of pass k
-    const uint2* geom;                                                 // window geometry per tile of this pass' grid (PassGeomEntry), or null
-};
-// lab: when g_pass_trace is set every workgroup of a pass launch leaves five ticks of the 100 MHz wall clock -- entry | everything it
-// requested up front has arrived | staged (first barrier) | decisions taken (second barrier) | end -- at 5 x its linear block index
-// (ssf_dbg_trace_pass, tools/pass_trace.py: where does a tile's 5-6 us go?).  Nothing of it in the product.
-#ifdef SSF_EXPERIMENTS
-__device__ unsigned long long* g_pass_trace = nullptr;
-void set_pass_trace(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pass_trace), &p, sizeof(p)); }
-#define SSF_PASS_TICK_BEGIN() unsigned long long* const pass_trace = g_pass_trace; \
-    const size_t pass_wg = blockIdx.x + (size_t)gridDim.x * (blockIdx.y + (size_t)gridDim.y * blockIdx.z); \
-    if (pass_trace && threadIdx.x == 0) pass_trace[5 * pass_wg] = wall_clock64()
-#define SSF_PASS_TICK(i) do { if (pass_trace && threadIdx.x == 0) pass_trace[5 * pass_wg + (i)] = wall_clock64(); } while (0)
-#define SSF_PASS_TICK_LOADS() do { if (pass_trace) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); __syncthreads(); SSF_PASS_TICK(1); } } while (0)
-// lab: statistics of a frame's relabelling passes in FrameMaps::epoch[8 ..] (ssf_dbg_pass_stats; bench.py's real-frame leg, round 6):
-// [8] log entries written (sum over tiles and passes), [9] the largest log of a tile in a pass, [10] tiles x passes, [11] superpixel-row
-// lookups that found their label OUTSIDE the tile's LDS window (the exact global path), [12] all row lookups
-// (only while g_pass_stats is set -- ssf_dbg_pass_stats_enable: a global atomic per lookup is not something an A/B of the lab build should pay)
-__device__ int g_pass_stats = 0;
-void set_pass_stats(int on) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pass_stats), &on, sizeof(on)); }
-#define SSF_PASS_STAT_LOOKUP(far) do { if (g_pass_stats) { atomicAdd(&m.epoch[12], 1u); if (far) atomicAdd(&m.epoch[11], 1u); } } while (0)
-#define SSF_PASS_STAT_END(nlog) do { if (g_pass_stats && threadIdx.x == 0) { atomicAdd(&m.epoch[8], (nlog)); atomicMax(&m.epoch[9], (nlog)); atomicAdd(&m.epoch[10], 1u); } } while (0)
-#else
-#define SSF_PASS_TICK_BEGIN() ((void)0)
-#define SSF_PASS_TICK(i) ((void)0)
-#define SSF_PASS_TICK_LOADS() ((void)0)
-#define SSF_PASS_STAT_LOOKUP(far) ((void)0)
-#define SSF_PASS_STAT_END(nlog) ((void)0)
-#endif
-template <bool RGBD, int NPX, int WAVES>
-__global__ __launch_bounds__(256, WAVES) void k_update_pass(SegParams p, FrameMaps m, PassArgs pa, int pass, int OX, int OY, int dbg, TileOrder ord) {
-    constexpr bool COH = false;
-    // this workgroup's (frame, tile row, tile column): see TileOrder
-    unsigned int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-#ifdef SSF_EXPERIMENTS
-    if (ord.xcd) {              // (lab: SSF_PASS_XCD=0 = tiles in grid order)
-#else
-    {
-#endif
-        const unsigned int lin = blockIdx.x + ord.ntx * blockIdx.y + ord.ntile * blockIdx.z;
-        const unsigned int t = xcd_share(lin, ord.total);
-        bz = __umulhi(t, ord.magic_ntile);
-        const unsigned int r = t - bz * ord.ntile;
+        bz = __umulhi(u, ord.magic_ntile);
+        const unsigned int r = u - bz * ord.ntile;
         by = __umulhi(r, ord.magic_ntx); bx = r - by * ord.ntx;
     }
-#include "ssf_pass_tile.hpp"
 }
-#ifdef SSF_EXPERIMENTS
-// the same body as a function of (tile column, row, frame slot): lab/passes_team.inc
-template <bool RGBD, int NPX, bool COH>
-__device__ __forceinline__ void update_pass_tile(const SegParams& p, FrameMaps m, const PassArgs& pa, int pass, int OX, int OY, int dbg,
-                                                 const TileOrder& ord, unsigned int bx, unsigned int by, unsigned int bz) {
-#include "ssf_pass_tile.hpp"
+__device__ __forceinline__ TileIdx tile_index(const TileOrder& ord) {
+    unsigned int bx, by, bz;
+    tile_index(ord, SSF_TILE_XCD && ord.xcd, bx, by, bz);
+    TileIdx t; t.bx = bx; t.by = by; t.bz = bz;
+    return t;
 }
-#endif
-
-// ---- the passes of a phase in ONE launch, a frame per XCD (round 5): a measurement arm that lost its A/B (DESIGN.md section 7,
-// profiles/pass_team_r05.txt) -- lab/passes_team.inc, compiled only into the lab variant of the library
-#ifdef SSF_EXPERIMENTS
-#include "lab/passes_team.inc"
-#else
-size_t pass_team_ws_bytes() { return 0; }
-size_t pass_args_bytes(int) { return 0; }
-void pass_args_table(const SegParams&, const FrameMaps&, int, void*) {}
-void launch_update_passes_team(hipStream_t, const SegParams&, FrameMaps&, int, int, int, bool, const void*, void*, unsigned int*) {}
-#endif
+#include "ssf_pass_tile.hpp"          // ---- the relabelling pass: k_update_pass
 
 // ---- RANSAC plane initialisation ---------------------------------------------------------------
 __device__ __forceinline__ size_t tex_index(float x, float y, int W, int H) {   // point sampling, clamp
@@ -578,9 +394,6 @@ __global__ __launch_bounds__(256) void k_init_samples(SegParams p, FrameMaps m, 
 #define ACC_REP 8
 #define EVAL_NS 16
 #define EVAL_REP 8
-#ifndef SSF_PASS_RGBD_WAVES
-#define SSF_PASS_RGBD_WAVES 6          // waves per SIMD the RGB-D pass is compiled for (launch bounds)
-#endif
 // unused dynamic LDS of the two accumulator-heavy tile kernels: caps their workgroups per compute unit (an occupancy knob for A/Bs)
 #ifndef SSF_INITDISP_DYN_LDS
 #define SSF_INITDISP_DYN_LDS 0
@@ -1693,50 +1506,6 @@ void launch_ingest(hipStream_t st, const SegParams& p, const BatchIn& in, FrameM
     default: launch_ingest_cf<SSF_COLOR_RGB8>(st, p, in, m, nb, epoch0); break;
     }
 }
-// pass pixels per thread (tile width / 32) for a launch over nb frames; SSF_PASS_NPX = 1 / 2 forces it (measurement)
-int pass_tile_npx(int nb) {
-    (void)nb;
-    return 1;       // measured (profiles/bench_r02_npx*.json): the 64-wide tiles cut the pass's HBM traffic from 1.25x to 1.01x of
-                    // the algorithmic bytes but not its time -- the kernel is bound by instruction issue, not by memory or by
-                    // how many workgroups are resident -- and cost a single-frame launch 50 % more (8 -> 12 us)
-}
-// the largest cell window CellWindow::init gives a tile of the plain 32 x 32 grid (same formulas, host integers): SegParams::win_cells_max
-int tile_window_cells_max(const SegParams& p) {
-    auto cell_of = [&](int x) { return p.cell_magic ? (int)(((uint64_t)(uint32_t)x * p.cell_magic) >> 32) : x; };
-    int best = 0;
-    for (int Y0 = 0; Y0 < p.H; Y0 += TILE)
-        for (int X0 = 0; X0 < p.W; X0 += TILE) {
-            int margin = 2;
-            const int tcx0 = cell_of(X0), tcy0 = cell_of(Y0), tcx1 = cell_of(std::min(X0 + TILE - 1, p.W - 1)), tcy1 = cell_of(std::min(Y0 + TILE - 1, p.H - 1));
-            while (margin > 0 && (tcx1 - tcx0 + 1 + 2 * margin) * (tcy1 - tcy0 + 1 + 2 * margin) > WIN_MAX) margin--;
-            const int n = (tcx1 - tcx0 + 1 + 2 * margin) * (tcy1 - tcy0 + 1 + 2 * margin);
-            best = std::max(best, n <= WIN_MAX ? n : WIN_MAX + 1);          // (no window at all: the large instantiation, which then takes the exact path)
-        }
-    return best;
-}
-// the table behind SegParams::pass_geom: exactly what k_update_pass<., 1, .> works out for a tile (same formulas, host integers)
-int pass_geometry_entries(int W, int H) { return 2 * ((W + (TILE - 2) + TILE - 1) / TILE) * ((H + TILE - 1) / TILE); }
-void pass_geometry_table(const SegParams& p, uint2* out) {
-    const int ntx = (p.W + (TILE - 2) + TILE - 1) / TILE, nty = (p.H + TILE - 1) / TILE;
-    auto cell_of = [&](int x) { return p.cell_magic ? (int)(((uint64_t)(uint32_t)x * p.cell_magic) >> 32) : x; };
-    for (int ox = 0; ox < 2; ox++)
-        for (int by = 0; by < nty; by++)
-            for (int bx = 0; bx < ntx; bx++) {
-                const int X0 = bx * TILE - (ox ? 0 : TILE - 2), Y0 = by * TILE;
-                const int TWP1 = TILE + 4;
-                const bool interior = X0 >= 1 && X0 - 1 + TWP1 <= p.W && Y0 >= 1 && Y0 + TILE < p.H;
-                int margin = 2;
-                const int tcx0 = cell_of(std::max(X0, 0)), tcy0 = cell_of(Y0);
-                const int tcx1 = cell_of(std::min(X0 + TILE - 1, p.W - 1)), tcy1 = cell_of(std::min(Y0 + TILE - 1, p.H - 1));
-                while (margin > 0 && (tcx1 - tcx0 + 1 + 2 * margin) * (tcy1 - tcy0 + 1 + 2 * margin) > WIN_MAX) margin--;
-                const int nwx = tcx1 - tcx0 + 1 + 2 * margin, nwy = tcy1 - tcy0 + 1 + 2 * margin;
-                const bool ok = nwx * nwy <= WIN_MAX && nwx < 256 && nwy < 256;
-                uint2 e;
-                e.x = ((uint32_t)(tcx0 - margin) & 0xFFFFu) | ((uint32_t)(tcy0 - margin) << 16);
-                e.y = (ok ? (uint32_t)nwx | ((uint32_t)nwy << 8) : 0u) | (interior ? 1u << 16 : 0u);
-                out[(size_t)ox * ntx * nty + (size_t)by * ntx + bx] = e;
-            }
-}
 void launch_update_pass(hipStream_t st, const SegParams& p, FrameMaps& m, int nb, int k, int ox, int oy, bool rgbd, int dbg) {
 #ifdef SSF_EXPERIMENTS
     static const char* per_pass_names[64] = {nullptr};
@@ -1750,14 +1519,9 @@ void launch_update_pass(hipStream_t st, const SegParams& p, FrameMaps& m, int nb
 #else
     ScopedKernel sk(rgbd ? "update_pass_rgbd" : "update_pass_rgb", st);
 #endif
-    // OX = 0: tiles shifted left by (tile width - 2): [-30,1], [2,33], ...  The same (larger) grid is used for OX = 1 so
-    // that tile ids -- and with them the per-tile log regions replayed by the next pass -- coincide.  All passes of a
-    // frame use the same tile width (the log layout depends on it): 64 when the launch covers several frames.
-    const int npx = pass_tile_npx(nb);
-    const int twx = TILE * npx;
-    dim3 grid = tile_grid(p);
-    grid.x = (p.W + (twx - 2) + twx - 1) / twx;
-    grid.z = nb;
+    // OX = 0: tiles shifted left by TILE - 2: [-30,1], [2,33], ...  The same (larger) grid is used for OX = 1 so that tile ids -- and
+    // with them the per-tile log regions replayed by the next pass and the entries of the geometry table -- coincide.
+    const dim3 grid(pass_grid_columns(p.W), pass_grid_rows(p.H), nb);
     const TileOrder ord = tile_order(grid);
     PassArgs pa;
     {
@@ -1765,15 +1529,15 @@ void launch_update_pass(hipStream_t st, const SegParams& p, FrameMaps& m, int nb
         pa.sr = m.sums[odd].r; pa.sw = m.sums[odd ^ 1].r;
         pa.pent = m.log.ent[lp]; pa.pdis = m.log.disp[lp]; pa.pcnt = m.log.count[lp];
         pa.cent = m.log.ent[lc]; pa.cdis = m.log.disp[lc]; pa.ccnt = m.log.count[lc];
-        pa.geom = npx == 1 ? p.pass_geom + (size_t)(ox ? p.pass_ntile : 0) : nullptr;        // (pass_geometry_table: this grid, by construction)
+        pa.geom = p.pass_geom + (size_t)(ox ? p.pass_ntile : 0);        // (pass_geometry_table: this grid, by construction)
     }
     // (Measured against this kernel and removed from the source, all bit-exact, all slower -- docs/HISTORY.md section 4.1.1 / 4.1.3:
     // 64-wide tiles with two pass pixels per thread, the RGB-D variant forced to 7 / 8 waves per SIMD, one wave per tile with the
     // changeable pixels compacted, four waves that release the ones the compacted list does not need, clean-tile skipping, all
     // passes of a phase in one resident launch with the label regions in LDS.  Round 6: a 64-register body (the replay ahead of the
     // decisions) and direct-to-LDS tile loads -- no gain, profiles/pass_ldsdma_r06.txt.)
-    if (rgbd) hipLaunchKernelGGL((k_update_pass<true, 1, SSF_PASS_RGBD_WAVES>), grid, dim3(256), 0, st, p, m, pa, k, ox, oy, dbg, ord);
-    else hipLaunchKernelGGL((k_update_pass<false, 1, 8>), grid, dim3(256), 0, st, p, m, pa, k, ox, oy, dbg, ord);
+    if (rgbd) hipLaunchKernelGGL((k_update_pass<true, SSF_PASS_RGBD_WAVES>), grid, dim3(256), 0, st, p, m, pa, k, ox, oy, dbg, ord);
+    else hipLaunchKernelGGL((k_update_pass<false, 8>), grid, dim3(256), 0, st, p, m, pa, k, ox, oy, dbg, ord);
 }
 void launch_init_samples(hipStream_t st, const SegParams& p, FrameMaps& m, int nb, int true_buf) {
     ScopedKernel sk("init_samples", st);

@@ -93,7 +93,6 @@ struct ExtractCtx {
     unsigned long long* d_best = nullptr; uint8_t* d_matched = nullptr;
     uint8_t* d_rgb_in = nullptr; float* d_depth_in = nullptr; float* d_depth_filt = nullptr; uint8_t* d_mask = nullptr;
     float* d_wire = nullptr;                      // 26 S words: the frame supersurfels of a frame extracted elsewhere (ssf_submit_frame_tables)
-    char* d_pas = nullptr; char* d_team_ws = nullptr;      // relabelling passes in one launch per phase (k_passes_team): per-pass arguments, team workspace
     ncclComm_t deal_comm = nullptr;               // dealt extract stage: this context's own communicator (a collective per batch on ITS stream)
     bool mine = true; long long deal_batch = 0;   // ... whether the open batch is this rank's to extract, and its number in the frame stream
     hipStream_t stream = nullptr; bool own_stream = false; int stream_prio = 0;
@@ -433,10 +432,6 @@ struct ssf_handle {
     TileCopy bins;                                // tile-sorted copy of the visible rows' ICP / association fields, for large visible sets
     // what the fuse launches take as groups: built by ssf_create; plane_depth and migrate are the frame's (fuse_begin)
     ClassifyArgs classify{}; ShardArgs shard{};
-    // pass_team: the relabelling passes of a phase as ONE launch with a frame per XCD (k_passes_team) instead of a launch per pass.
-    // Its workgroups must all be on the chip at once, so whole batches take turns across the contexts (launch_batch: a batch's
-    // chain waits for the previous batch's ev_done).
-    bool pass_team = false; ExtractCtx* team_prev = nullptr;
     long long h_icp_local[SSF_ICP_RECORD];
     long long* h_icp = nullptr; Counters* h_cnt = nullptr;
     int n_model = 0, n_visible = 0, stamp = 0, max_passes = 0;

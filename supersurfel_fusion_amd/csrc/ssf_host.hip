@@ -332,13 +332,7 @@ static void enqueue_segmentation(ssf_handle* h, ExtractCtx& c, hipStream_t st, b
     const int limit = h->max_passes > 0 ? h->max_passes : (1 << 30);
     const int ox[4] = {0, 1, 0, 1}, oy[4] = {0, 1, 1, 0};                 // pass order, TPS_RGBD.cu:190-268
     const int k1 = std::min(4 * (h->cfg.seg_iter / 2), limit), k2 = std::min(4 * h->cfg.seg_iter, std::max(limit, k1));
-    unsigned int* abort_flag = &h->mb_dev->extract_abort;
-    const bool team = h->pass_team && c.d_pas && c.d_team_ws && h->max_passes == 0;        // (lab: lab/passes_team.inc)
-    if (team) {
-        (void)hipMemsetAsync(c.d_team_ws, 0, pass_team_ws_bytes(), st);
-        launch_update_passes_team(st, p, c.maps, nb, 0, k1, false, c.d_pas, c.d_team_ws, abort_flag);
-    } else
-        for (int k = 0; k < k1; k++) launch_update_pass(st, p, c.maps, nb, k, ox[k & 3], oy[k & 3], false, 0);
+    for (int k = 0; k < k1; k++) launch_update_pass(st, p, c.maps, nb, k, ox[k & 3], oy[k & 3], false, 0);
     // sums[k1&1] holds the exact sums after k1 passes; RANSAC and the inlier initialisation read them directly
     if (h->cfg.seg_use_ransac) {
         launch_init_samples(st, p, c.maps, nb, k1 & 1);
@@ -346,12 +340,7 @@ static void enqueue_segmentation(ssf_handle* h, ExtractCtx& c, hipStream_t st, b
         launch_init_disp(st, p, c.maps, nb, true);
     } else launch_init_disp(st, p, c.maps, nb, false);
     int k = k1;
-    if (team) {
-        (void)hipMemsetAsync(c.d_team_ws, 0, pass_team_ws_bytes(), st);
-        launch_update_passes_team(st, p, c.maps, nb, k1, k2, true, c.d_pas, c.d_team_ws, abort_flag);
-        k = std::max(k1, k2);
-    } else
-        for (; k < k2; k++) launch_update_pass(st, p, c.maps, nb, k, ox[k & 3], oy[k & 3], true, 0);
+    for (; k < k2; k++) launch_update_pass(st, p, c.maps, nb, k, ox[k & 3], oy[k & 3], true, 0);
     launch_plane_filter(st, p, c.maps, nb, k & 1);             // final merge (table + planes) + smoothing sweeps
     if (pixmask) launch_render_moments_pixmask(st, p, h->cam, c.maps, nb, c.d_pixmask, c.d_pixcnt);
     else launch_render_moments(st, p, h->cam, c.maps, nb);
@@ -398,7 +387,6 @@ static int launch_batch(ssf_handle* h, ExtractCtx& c) {
     const int nb = c.count;
     // the track/fuse chain must be done with the frames this context held before they are overwritten
     if (multi && c.consumed_valid) HCK(hipStreamWaitEvent(st, c.ev_consumed, 0));
-    if (multi && h->pass_team && h->team_prev && h->team_prev != &c) HCK(hipStreamWaitEvent(st, h->team_prev->ev_done, 0));      // (see pass_team)
     c.timed = h->cfg.profile != 0;
     if (c.timed) HCK(hipEventRecord(c.ev_t0, st));
     // The extract stage DEALT over the ranks of a sharded map (ssf_comm_deal_extract): batch j of the frame
@@ -451,7 +439,6 @@ static int launch_batch(ssf_handle* h, ExtractCtx& c) {
     HCK(hipGetLastError());
     if (c.timed) HCK(hipEventRecord(c.ev_t1, st));
     if (multi) HCK(hipEventRecord(c.ev_done, st));
-    if (multi && h->pass_team) h->team_prev = &c;
     c.launched = true; c.waited = false; c.inflight = nb; c.nb_launched = nb;
     h->open_ctx = (int)((&c - h->ctx.data() + 1) % (ptrdiff_t)h->ctx.size());
     if (h->seq_n > 0) {
@@ -995,14 +982,8 @@ static int fuse_read_counters(ssf_handle* h, unsigned long long seq, Counters& c
     h->oov_head = c.oov_head; h->oov_tail = c.oov_tail; h->oov_live = c.oov_live;
     return SSF_OK;
 }
-// the two flags a kernel without a record of its own to withhold leaves in the mailbox: each is reported once
+// the flag a kernel without a record of its own to withhold leaves in the mailbox: reported once
 static int fuse_device_flags(ssf_handle* h) {
-    if (__atomic_load_n(&h->mb_host->extract_abort, __ATOMIC_ACQUIRE) != 0u) {
-        __atomic_store_n(&h->mb_host->extract_abort, 0u, __ATOMIC_RELEASE);
-        h->err = "a team launch of the relabelling passes could not get all its workgroups onto the GPU and gave up (the GPU is oversubscribed: "
-                 "several processes?); the frames of that batch are invalid";
-        return SSF_ERR_DEVICE;
-    }
     if (h->p2p.on && __atomic_load_n(&h->mb_host->p2p_timeout, __ATOMIC_ACQUIRE) != 0u) {
         __atomic_store_n(&h->mb_host->p2p_timeout, 0u, __ATOMIC_RELEASE);       // reported once; a later frame starts clean
         h->err = "a peer's association / migrant tables never arrived (peer-to-peer exchange)"; return SSF_ERR_DEVICE;
@@ -1556,27 +1537,27 @@ int ssf_create(const ssf_config* cfg, ssf_handle** out) {
     p.filter_iter = cfg->filter_iter; p.seed = cfg->rng_seed;
     p.inv_gx = 1.0f / (float)h->gx;
     p.cell_magic = c > 1 ? (uint32_t)((0x100000000ull + (uint64_t)c - 1) / (uint64_t)c) : 0u;
-    p.win_cells_max = tile_window_cells_max(p);          // (selects the LDS footprint of the tile kernels: ssf_extract.hip, WCAP)
+    p.win_cells_max = tile_window_cells_max(W, H, p.cell_magic);          // (selects the LDS footprint of the tile kernels: ssf_extract.hip, WCAP)
     h->cam.fx = cfg->fx; h->cam.fy = cfg->fy; h->cam.cx = cfg->cx; h->cam.cy = cfg->cy; h->cam.W = W; h->cam.H = H;
     h->classify = ClassifyArgs{h->cam, nullptr, cfg->delta_t, cfg->conf_thresh, cfg->range_min, cfg->range_max};
     h->shard = ShardArgs{cfg->rank, cfg->nranks, 0, cfg->shard_tile};
     const size_t P = (size_t)W * H, S = h->S, N = cfg->nb_supersurfels_max, NS = S * cfg->nb_samples;
-    // relabelling tiles (the shifted grid has one more column): 32-wide tiles with 256 log entries each, or 64-wide
-    // ones with 512 (ssf_extract.hip, k_update_pass<., NPX>); the log regions are sized for whichever needs more
+    // relabelling tiles (the shifted grid has one more column), a log region of 256 entries each.  NT32 is the grid k_update_pass
+    // runs (pass_geometry_entries / 2); the larger 2 * NT64 is what the 64-wide tiles deleted in round 6 needed.  It stays until the
+    // smaller slab has been measured: every pointer carved behind the logs moves with it (profiles/pass_body_refactor.txt).
     const size_t NT32 = (size_t)((W + 30 + 31) / 32) * ((H + 31) / 32), NT64 = (size_t)((W + 62 + 63) / 64) * ((H + 31) / 32);
     const size_t NT = std::max(NT32, 2 * NT64);
     const int nctx = std::max(0, std::min(cfg->pipeline_depth, SSF_MAX_PIPELINE_DEPTH)) + 1;
     h->batch = std::max(1, std::min(cfg->extract_batch, SSF_MAX_BATCH));
     h->ctx.resize(nctx);
-    h->pass_team = SSF_ENV_INT("PASS_TEAM", 0) != 0;              // (lab arm, lab/passes_team.inc: the product never takes it)
     bool ok = dalloc(h, &h->d_srgb_lut, 256) && dalloc(h, &h->d_tickets, 512);
     {   // window geometry of the relabelling tiles (SegParams::pass_geom)
         const int ne = pass_geometry_entries(W, H);
-        std::vector<uint2> tab((size_t)ne);
+        std::vector<PassGeomEntry> tab((size_t)ne);
         p.pass_geom = nullptr; p.pass_ntile = ne / 2;
-        pass_geometry_table(p, tab.data());
-        uint2* d_geom = nullptr;
-        ok = ok && dalloc(h, &d_geom, (size_t)ne) && hipMemcpy(d_geom, tab.data(), (size_t)ne * sizeof(uint2), hipMemcpyHostToDevice) == hipSuccess;
+        pass_geometry_table(W, H, p.cell_magic, tab.data());
+        PassGeomEntry* d_geom = nullptr;
+        ok = ok && dalloc(h, &d_geom, (size_t)ne) && hipMemcpy(d_geom, tab.data(), (size_t)ne * sizeof(PassGeomEntry), hipMemcpyHostToDevice) == hipSuccess;
         if (ok) p.pass_geom = d_geom;
     }
     // working set of one frame, carved out of a slab (256 B aligned pieces); a context owns `batch` slabs
@@ -1626,13 +1607,6 @@ int ssf_create(const ssf_config* cfg, ssf_handle** out) {
             static const bool ctx0_up = SSF_ENV_INT("CTX0_PRIORITY", 1) != 0;
             const int prio = (ci == 0 && ctx0_up && least - greatest >= 2) ? least - 1 : least;
             c.stream = stream_pool().take(h->cfg.device_id, prio); ok = c.stream != nullptr; c.own_stream = ok; c.stream_prio = prio;
-        }
-        if (ok && h->pass_team) {
-            const int kmax = 4 * std::max(cfg->seg_iter, 0);
-            std::vector<char> tab(pass_args_bytes(std::max(kmax, 1)));
-            pass_args_table(p, c.maps, kmax, tab.data());
-            ok = dalloc(h, &c.d_pas, tab.size()) && dalloc(h, &c.d_team_ws, pass_team_ws_bytes()) &&
-                 hipMemcpy(c.d_pas, tab.data(), tab.size(), hipMemcpyHostToDevice) == hipSuccess;
         }
         ok = ok && hipEventCreateWithFlags(&c.ev_done, hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&c.ev_consumed, hipEventDisableTiming) == hipSuccess &&

@@ -1,13 +1,122 @@
-// ssf_pass_tile.hpp -- ONE TILE OF ONE RELABELLING PASS: the body of k_update_pass (ssf_extract.hip), as text.
-// Included inside a function whose scope provides: constexpr bool RGBD, COH; constexpr int NPX; SegParams p; FrameMaps m (a copy: it
-// is shifted to the frame's slot here); PassArgs pa; int pass, OX, OY, dbg; TileOrder ord; unsigned int bx, by, bz (the
-// tile's column, row and frame slot).  The product includes it once, in the kernel (COH = false); the lab build a second time, in
-// update_pass_tile -- the body its resident arm walks tile by tile (lab/passes_team.inc; COH = true: what another workgroup wrote in
-// an earlier pass of the same launch is read past the L1, ld_coh).  As a function called from the kernel the same text ran 1-1.5 %
-// slower in place (gpurun r13b, alternated three times), hence the include.
-    constexpr int TWX = TILE * NPX, LOGN = 256 * NPX;
+// ssf_pass_tile.hpp -- THE RELABELLING PASS: k_update_pass, the dominant kernel of the extract stage, with what only it uses -- its
+// arguments, the layout of its LDS accumulators, the lab build's ticks and statistics.  Included once by ssf_extract.hip, at file
+// scope inside namespace ssf, behind the helpers the pass shares with the other tile kernels (TileOrder / tile_index, the row
+// builders, lds_add_i64, disp_sums_add).  One body, one tile width (32), one tile order (tile_index) and one source of the window
+// geometry (the host's table, ssf_tile_geometry.hpp): the arms that were measured against it and dropped are in docs/HISTORY.md
+// section 4.1.1, not here.
+#pragma once
+
+// One pass (OX,OY) of the boundary relabelling: updateTPSRGB_kernel / updateTPSRGBD_kernel,
+// TPS_RGBD_kernels.cuh:235-651.  256 threads own the 256 pass pixels of a 32x32 tile.
+//
+// Labels are updated IN PLACE.  A pass touches rows y = OY (mod 2) and columns x = 0,3 (mod 4) for
+// OX = 0 or x = 1,2 (mod 4) for OX = 1, i.e. horizontally adjacent PAIRS of pixels; everything else a
+// pass pixel looks at (rows y-1, y+1, the outer neighbours of its pair) is not modified in this pass.
+// The tile grid is shifted so that a pair never straddles two tiles (X0 = 2 mod 4 for OX = 0): a
+// workgroup snapshots its tile + halo into LDS, decides from the snapshot, and is the only writer of
+// the pass pixels it read -- exactly the "all reads before any write" schedule of the oracle (A1)
+// without a second label map or a copy of the untouched pixels.
+//
+// No merge launch between passes.  The exact sums are double buffered: pass k builds the superpixel
+// rows (means, plane) it needs straight from sums[k&1], which nothing writes during the pass, and
+// applies its relabelling deltas to sums[(k+1)&1] together with the replayed log of pass k-1 (the
+// deltas that buffer is still missing).  Integer adds commute, so the lagging buffer catches up
+// exactly.  The rows of the superpixels around the tile (a window of grid cells) are computed by
+// the first threads of the workgroup into LDS while the label tile is being staged; the energy
+// then reads rows from LDS.  Labels that have drifted out of the window take an exact slow path.
+// (64-wide tiles with two pass pixels per thread cut the pass's HBM traffic from 1.25x to 1.01x of the algorithmic bytes but not its
+// time, and cost a single-frame launch 50 % more: measured and removed, docs/HISTORY.md section 4.1.1.)
+// Instruction diet (round 3).  Counters + an experiment (150 extra vector instructions per wave: +2.3 us on a 20 us launch) show the
+// pass is bound by instruction ISSUE as much as by latency: 6.3 M wave-level VALU instructions per 8-frame RGB-D launch are
+// 10 us of the part's vector issue capacity.  Hence: the candidate labels of a pixel de-duplicated and compacted (the wave walks
+// 1-2 candidates instead of 4 directions), interior tiles staged without bounds tests and through one scalar base, the
+// connectivity guard as a bit mask + popcount, window slots by unsigned compares, the nine 32-bit sums in 32-bit LDS
+// accumulators, the disparity terms of a pixel converted once for both signs, the flush addressed by field offset
+// instead of a 15-way switch, the previous pass' log entry fetched without a branch (behind one, the compiler waited for
+// it -- a second dependent trip to memory -- before it requested the window's sums).
+// Global accesses of the pass as (uniform 64-bit base) + (32-bit BYTE offset in a vector register): the form the hardware
+// takes directly (`global_load_dword v, v_off, s[base]`).  Indexing a typed pointer with an integer makes the compiler
+// widen, shift and add in 64 bits per access (v_mad_i64_i32 / v_lshl_add_u64 and a zeroed high half): two or three
+// vector instructions and a register pair each, a dozen times per thread.  Every map of a frame is far below 4 GB.
+template <typename T> __device__ __forceinline__ T ld_off(const void* __restrict__ base, unsigned int byte_off) {
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+template <typename T> __device__ __forceinline__ void st_off(void* __restrict__ base, unsigned int byte_off, const T& v) {
+    *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off) = v;
+}
+#ifndef SSF_PASS_RGBD_WAVES
+#define SSF_PASS_RGBD_WAVES 6          // waves per SIMD the RGB-D pass is compiled for (launch bounds)
+#endif
+#ifndef SSF_PASS_NPREV_RGBD
+#define SSF_PASS_NPREV_RGBD 1
+#endif
+#ifndef SSF_PASS_NPREV_RGB
+#define SSF_PASS_NPREV_RGB 1
+#endif
+// What a pass touches of a frame's working set, chosen on the HOST (round 5): the read / write sums buffer by the pass' parity, the
+// previous / current log by pass mod 3.  Selected in the kernel -- from FrameMaps, after shifting all of its ~30 pointers to the
+// batch slot -- it was ~50 scalar instructions of every wave's prologue (s_cselect chains + 64-bit adds); the counters put the
+// prologue at 205 of the RGB-D wave's 321 scalar instructions, and 150 extra scalar instructions per wave cost the 8-frame
+// launch 1.8 us (profiles/pass_issue_r05.txt): ONE scalar unit serves the four SIMDs of a compute unit, and this kernel is as
+// close to its issue limit as to the vector pipes'.
+struct PassArgs {
+    const SumRec* sr; SumRec* sw;                                      // sums[k & 1] (read), sums[(k + 1) & 1] (written)
+    const int4* pent; const float* pdis; const unsigned int* pcnt;     // log of pass k - 1
+    int4* cent; float* cdis; unsigned int* ccnt;                       // log of pass k
+    const PassGeomEntry* geom;                                         // window geometry per tile of this pass' grid (pass_geometry_table)
+};
+// Field order of the per-window-superpixel LDS accumulators of a pass (15 exact integer sums): F_SX .. F_DN are 32-bit (PASS_F32 of
+// them), F_DXX .. F_DD 64-bit.  A window slot: 24 dwords = six 16-byte chunks -- the nine 32-bit sums (chunks 0-2, three dwords of
+// padding), then the six 64-bit sums (chunks 3-5; RGB passes never touch them).  Zeroed and scanned a chunk at a time.
+enum { F_SX, F_SY, F_SR, F_SG, F_SB, F_N, F_DX, F_DY, F_DN, F_DXX, F_DYY, F_DXY, F_DXD, F_DYD, F_DD, F_COUNT };
+#define PASS_F32 9
+#define PASS_ACC_DW 24
+#define PASS_ACC_WIDE_DW 12
+// lab: when g_pass_trace is set every workgroup of a pass launch leaves five ticks of the 100 MHz wall clock -- entry | everything it
+// requested up front has arrived | staged (first barrier) | decisions taken (second barrier) | end -- at 5 x its linear block index
+// (ssf_dbg_trace_pass, tools/pass_trace.py: where does a tile's 5-6 us go?).  Nothing of it in the product.
+#ifdef SSF_EXPERIMENTS
+__device__ unsigned long long* g_pass_trace = nullptr;
+void set_pass_trace(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pass_trace), &p, sizeof(p)); }
+#define SSF_PASS_TICK_BEGIN() unsigned long long* const pass_trace = g_pass_trace; \
+    const size_t pass_wg = blockIdx.x + (size_t)gridDim.x * (blockIdx.y + (size_t)gridDim.y * blockIdx.z); \
+    if (pass_trace && threadIdx.x == 0) pass_trace[5 * pass_wg] = wall_clock64()
+#define SSF_PASS_TICK(i) do { if (pass_trace && threadIdx.x == 0) pass_trace[5 * pass_wg + (i)] = wall_clock64(); } while (0)
+#define SSF_PASS_TICK_LOADS() do { if (pass_trace) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); __syncthreads(); SSF_PASS_TICK(1); } } while (0)
+// lab: statistics of a frame's relabelling passes in FrameMaps::epoch[8 ..] (ssf_dbg_pass_stats; bench.py's real-frame leg, round 6):
+// [8] log entries written (sum over tiles and passes), [9] the largest log of a tile in a pass, [10] tiles x passes, [11] superpixel-row
+// lookups that found their label OUTSIDE the tile's LDS window (the exact global path), [12] all row lookups
+// (only while g_pass_stats is set -- ssf_dbg_pass_stats_enable: a global atomic per lookup is not something an A/B of the lab build should pay)
+__device__ int g_pass_stats = 0;
+void set_pass_stats(int on) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pass_stats), &on, sizeof(on)); }
+#define SSF_PASS_STAT_LOOKUP(far) do { if (g_pass_stats) { atomicAdd(&m.epoch[12], 1u); if (far) atomicAdd(&m.epoch[11], 1u); } } while (0)
+#define SSF_PASS_STAT_END(nlog) do { if (g_pass_stats && threadIdx.x == 0) { atomicAdd(&m.epoch[8], (nlog)); atomicMax(&m.epoch[9], (nlog)); atomicAdd(&m.epoch[10], 1u); } } while (0)
+#else
+#define SSF_PASS_TICK_BEGIN() ((void)0)
+#define SSF_PASS_TICK(i) ((void)0)
+#define SSF_PASS_TICK_LOADS() ((void)0)
+#define SSF_PASS_STAT_LOOKUP(far) ((void)0)
+#define SSF_PASS_STAT_END(nlog) ((void)0)
+#endif
+
+// m: a copy, shifted to the frame's slot here.  pass: its number over the whole frame (0-based).  dbg: lab probes (SSF_PROBE).
+template <bool RGBD, int WAVES>
+__global__ __launch_bounds__(256, WAVES) void k_update_pass(SegParams p, FrameMaps m, PassArgs pa, int pass, int OX, int OY, int dbg, TileOrder ord) {
+    // A thread owns ONE pass pixel.  What is per pixel is still written as arrays of NPX = 1 elements and loops of one trip: as
+    // plain scalars the same statements compile to another schedule and register allocation (every one of the four loops below
+    // on its own, profiles/pass_body_refactor.txt), and this kernel's code is what every measurement of section 4.1 stands on.
+    constexpr int NPX = 1;
+    // this workgroup's (tile column, tile row, frame slot) in the XCD-aware order: always in the product (lab: SSF_PASS_XCD=0 =
+    // tiles in grid order)
+    unsigned int bx, by, bz;
+#ifdef SSF_EXPERIMENTS
+    tile_index(ord, ord.xcd != 0, bx, by, bz);
+#else
+    tile_index(ord, true, bx, by, bz);
+#endif
+    constexpr int LOGN = 256;                     // log entries of a tile: a pass relabels at most its 256 pass pixels
     SSF_PASS_TICK_BEGIN();                        // (lab: five ticks of the wall clock per workgroup -- tools/pass_trace.py)
-    __shared__ __attribute__((aligned(16))) int tile[(TWX + 4) * TW];      // rows of TWX + 4 labels: see the tile loads below
+    __shared__ __attribute__((aligned(16))) int tile[(TILE + 4) * TW];      // rows of TILE + 4 labels: see the tile loads below
     __shared__ SpRow w_row[WIN_MAX];
     __shared__ int w_label[WIN_MAX];                          // label of a window slot (-1: outside the grid)
     __shared__ __attribute__((aligned(16))) unsigned int w_acc[WIN_MAX * PASS_ACC_DW];      // this tile's sum deltas (own + replayed), flushed once
@@ -17,7 +126,7 @@
     m.inlier = slab_shift(m.inlier, slot_off); m.epoch = slab_shift(m.epoch, slot_off);
     SpSums sr, sw;
     sr.r = const_cast<SumRec*>(slab_shift(pa.sr, slot_off)); sw.r = slab_shift(pa.sw, slot_off);
-    const int X0 = __builtin_amdgcn_readfirstlane((int)bx * TWX - (OX ? 0 : TWX - 2)), Y0 = __builtin_amdgcn_readfirstlane((int)by * TILE);  // OX = 0: tiles start at 2 (mod 4)
+    const int X0 = __builtin_amdgcn_readfirstlane((int)bx * TILE - (OX ? 0 : TILE - 2)), Y0 = __builtin_amdgcn_readfirstlane((int)by * TILE);  // OX = 0: tiles start at 2 (mod 4)
     int32_t* __restrict__ lab = m.label;
     // this thread's pass pixels: local columns 4j+1, 4j+2 of pass rows; pixel s of the thread is element threadIdx.x + 256 s
     int x[NPX], y[NPX], lxh[NPX], lyh[NPX]; bool in_image[NPX]; unsigned int q[NPX];
@@ -40,8 +149,7 @@
     // pays is measured per variant (SSF_PASS_NPREV_RGBD / SSF_PASS_NPREV_RGB).
     constexpr int NPREV_FORM = RGBD ? SSF_PASS_NPREV_RGBD : SSF_PASS_NPREV_RGB;
     unsigned int n_prev_word = 0u;
-    if (COH) n_prev_word = ld_coh<true>(&pcnt[tile_id]);      // (never through the scalar cache: the count was stored by a vector store of this launch)
-    else if (NPREV_FORM == 0) { if (pass > 0) n_prev_word = pcnt[tile_id]; }
+    if (NPREV_FORM == 0) { if (pass > 0) n_prev_word = pcnt[tile_id]; }
     else if (NPREV_FORM == 1) n_prev_word = pcnt[tile_id];
     else { int lane_zero = 0; asm volatile("" : "+v"(lane_zero)); n_prev_word = pcnt[tile_id + lane_zero]; }
     // operands that do not depend on the label tile: in flight while the tile is staged
@@ -50,11 +158,11 @@
     for (int s = 0; s < NPX; s++) {
         px[s] = ld_off<uint32_t>(m.rgba, 4u * q[s]);
         disp[s] = 0.f; prev_inlier[s] = 0;
-        if (RGBD) { disp[s] = ld_off<float>(m.disp, 4u * q[s]); prev_inlier[s] = ld_off_c<COH, unsigned char>(m.inlier, q[s]); }
+        if (RGBD) { disp[s] = ld_off<float>(m.disp, 4u * q[s]); prev_inlier[s] = ld_off<unsigned char>(m.inlier, q[s]); }
     }
     // the label tile + halo: requested into registers NOW (independent loads), stored to LDS after the superpixel rows
     // have been computed -- one memory round trip for tile, pixel operands, sums and log.
-    // The tile travels in QUADS: a row of the LDS tile is TWP = TWX + 4 labels (the 2 + TWX halo columns and two columns of
+    // The tile travels in QUADS: a row of the LDS tile is TWP = TILE + 4 labels (the 2 + TILE halo columns and two columns of
     // padding that nothing reads), i.e. TWP / 4 16-byte quads, and quad e of the tile lies at LDS dword 4 e.  When the
     // halo (and the padding) lies inside the image -- a uniform test -- a lane fetches a quad with ONE 16-byte load (the
     // address is only 4-byte aligned: X0 - 1 is odd; global loads take that) and stores it with one ds_write_b128: two
@@ -62,17 +170,15 @@
     // four labels of a quad one by one from offsets clamped into the image; `outside` = the labels that are not in it.
     // Either way the loads are unconditional (loads behind a branch made the compiler wait for the pixel operands before it
     // issued them: a second dependent trip to memory); the idle lanes of the last round re-read the tile's last quad.
-    constexpr int TWP = TWX + 4, QPR = TWP / 4, NQ = QPR * TW, TILE_LOADS = (NQ + 255) / 256;
+    constexpr int TWP = TILE + 4, QPR = TWP / 4, NQ = QPR * TW, TILE_LOADS = (NQ + 255) / 256;
     constexpr unsigned int QPR_MAGIC = 65536u / QPR + 1u;          // e / QPR == (e * QPR_MAGIC) >> 16 for e < 1024
     static_assert(NQ <= 1024 && TILE_LOADS * 4 <= 32, "quad index / outside mask");
     uint4 tile_reg[TILE_LOADS]; unsigned int outside = 0u;
     const bool no_tile = SSF_PROBE(dbg, 32);                     // (probe: every element reads as outside the image)
-    // (window geometry and the interior test: one 8-byte table entry per tile for the product's 32-wide tiles, fetched by a scalar
-    // load that travels with the kernel arguments; worked out here for the lab's 64-wide tiles)
-    uint2 geom = make_uint2(0u, 0u);
-    constexpr bool have_geom = NPX == 1;                      // (launch_update_pass always supplies the table for 32-wide tiles)
-    if (have_geom) geom = pa.geom[by * ord.ntx + bx];
-    const bool interior = have_geom ? ((geom.y >> 16) & 1u) != 0u : (X0 >= 1 && X0 - 1 + TWP <= p.W && Y0 >= 1 && Y0 + TILE < p.H);
+    // window geometry and the interior test: one 8-byte table entry per tile (pass_geometry_table), fetched by a scalar load that
+    // travels with the kernel arguments
+    const PassGeomEntry geom = pa.geom[by * ord.ntx + bx];
+    const bool interior = ((geom.y >> 16) & 1u) != 0u;
     if (interior) {
         typedef uint32_t Quad __attribute__((ext_vector_type(4), aligned(4)));     // ONE load of four labels, 4-byte aligned
         const unsigned int base_off = (unsigned int)((Y0 - 1) * p.W + (X0 - 1));
@@ -85,7 +191,7 @@
         }
 #pragma unroll
         for (int k = 0; k < TILE_LOADS; k++) {
-            const Quad v = ld_off_c<COH, Quad>(lab, tile_off[k]);
+            const Quad v = ld_off<Quad>(lab, tile_off[k]);
             tile_reg[k] = make_uint4(v.x, v.y, v.z, v.w);
         }
     } else {
@@ -105,29 +211,12 @@
         }
 #pragma unroll
         for (int k = 0; k < TILE_LOADS; k++)
-            tile_reg[k] = make_uint4(ld_off_c<COH, uint32_t>(lab, tile_off[k][0]), ld_off_c<COH, uint32_t>(lab, tile_off[k][1]), ld_off_c<COH, uint32_t>(lab, tile_off[k][2]), ld_off_c<COH, uint32_t>(lab, tile_off[k][3]));
+            tile_reg[k] = make_uint4(ld_off<uint32_t>(lab, tile_off[k][0]), ld_off<uint32_t>(lab, tile_off[k][1]), ld_off<uint32_t>(lab, tile_off[k][2]), ld_off<uint32_t>(lab, tile_off[k][3]));
     }
     if (no_tile) outside = 0xFFFFFFFFu;
-    // window of grid cells around the tile whose superpixel rows are cached in LDS
-    int wcx0, wcy0, nwx, nwy;
-    bool window_ok;
-    if (have_geom) {
-        wcx0 = __builtin_amdgcn_readfirstlane((int)(short)(geom.x & 0xFFFFu)); wcy0 = __builtin_amdgcn_readfirstlane((int)(short)(geom.x >> 16));
-        nwx = __builtin_amdgcn_readfirstlane((int)(geom.y & 255u)); nwy = __builtin_amdgcn_readfirstlane((int)((geom.y >> 8) & 255u));
-        window_ok = nwx != 0;
-    } else {
-        int margin = 2;
-        const int tcx0 = div_cell(p, max(X0, 0)), tcy0 = div_cell(p, Y0);
-        const int tcx1 = div_cell(p, min(X0 + TWX - 1, p.W - 1)), tcy1 = div_cell(p, min(Y0 + TILE - 1, p.H - 1));
-        while (margin > 0 && (tcx1 - tcx0 + 1 + 2 * margin) * (tcy1 - tcy0 + 1 + 2 * margin) > WIN_MAX) margin--;
-        // (uniform values, said so: without the readfirstlane the RGB-D variant computed the whole window geometry -- two
-        // mul_hi, four quarter-rate mul_lo, the margin loop -- in vector registers, ~45 issue slots per wave)
-        margin = __builtin_amdgcn_readfirstlane(margin);
-        wcx0 = __builtin_amdgcn_readfirstlane(tcx0 - margin); wcy0 = __builtin_amdgcn_readfirstlane(tcy0 - margin);
-        const int nwx_ = tcx1 - tcx0 + 1 + 2 * margin, nwy_ = tcy1 - tcy0 + 1 + 2 * margin;
-        window_ok = nwx_ * nwy_ <= WIN_MAX;
-        nwx = __builtin_amdgcn_readfirstlane(window_ok ? nwx_ : 0); nwy = __builtin_amdgcn_readfirstlane(window_ok ? nwy_ : 0);   // no window: every label takes the exact path
-    }
+    // window of grid cells around the tile whose superpixel rows are cached in LDS (nwx = nwy = 0: no window, every label takes the exact path)
+    const int wcx0 = __builtin_amdgcn_readfirstlane((int)(short)(geom.x & 0xFFFFu)), wcy0 = __builtin_amdgcn_readfirstlane((int)(short)(geom.x >> 16));
+    const int nwx = __builtin_amdgcn_readfirstlane((int)(geom.y & 255u)), nwy = __builtin_amdgcn_readfirstlane((int)((geom.y >> 8) & 255u));
     const int nslots = nwx * nwy;
     const SpRow zero_row = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // (window <= 64 cells: wave 0 builds the means of cell `lane`, wave 1 -- RGB-D passes -- its plane, side by side)
@@ -143,13 +232,13 @@
             if (inside && !SSF_PROBE(dbg, 1)) {
                 if (threadIdx.x < 64) {
                     SpRow row = zero_row;
-                    row_means_from_sums<COH>(sr, k, row);
+                    row_means_from_sums(sr, k, row);
                     w_row[i].cx = row.cx; w_row[i].cy = row.cy; w_row[i].r = row.r; w_row[i].g = row.g; w_row[i].b = row.b; w_row[i].size = row.size;
                     w_row[i].pad0 = row.size / (row.size - 1.f);      // the pixel's own-energy scale n / (n - 1): one division per window cell instead of one per pass pixel
                     if (!RGBD) { w_row[i].ta = 0.f; w_row[i].tb = 0.f; w_row[i].tc = 0.f; }
                 } else {
                     float ta, tb, tc;
-                    row_plane_from_sums<COH>(sr, k, ta, tb, tc);
+                    row_plane_from_sums(sr, k, ta, tb, tc);
                     w_row[i].ta = ta; w_row[i].tb = tb; w_row[i].tc = tc;
                 }
             }
@@ -166,9 +255,9 @@
     for (int s = 0; s < NPX; s++) {
         const unsigned int e = threadIdx.x + 256u * s;
         const unsigned int le = (unsigned int)tile_id * LOGN + (e < n_prev ? e : 0u);
-        prev_ent[s] = ld_off_c<COH, int4>(pent, 16u * le);
+        prev_ent[s] = ld_off<int4>(pent, 16u * le);
         prev_disp[s] = 0.f;
-        if (RGBD) prev_disp[s] = ld_off_c<COH, float>(pdis, 4u * le);
+        if (RGBD) prev_disp[s] = ld_off<float>(pdis, 4u * le);
     }
     if (threadIdx.x == 0) s_nlog = 0;
     constexpr int ACC_CHUNKS = RGBD ? 6 : 2;                  // 16-byte chunks of a slot that a pass of this kind can touch (RGB: sx .. n)
@@ -203,7 +292,7 @@
         const int ws = slot_of(l);
         SSF_PASS_STAT_LOOKUP(ws < 0);
         if (ws >= 0) return *reinterpret_cast<const SpRow*>(reinterpret_cast<const char*>(w_row) + __umul24((unsigned int)ws, (unsigned int)sizeof(SpRow)));
-        SpRow far = row_from_sums<COH>(sr, l, RGBD, zero_row);     // drifted out of the window: exact slow path
+        SpRow far = row_from_sums(sr, l, RGBD, zero_row);     // drifted out of the window: exact slow path
         far.pad0 = far.size / (far.size - 1.f);
         return far;
     };
@@ -396,3 +485,5 @@
     }
     SSF_PASS_STAT_END(s_nlog);
     SSF_PASS_TICK(4);
+
+}

@@ -80,7 +80,7 @@ def test_the_product_library_reads_no_environment_variable(product_lib):
     import subprocess
     out = subprocess.run(["strings", product_lib.path], stdout=subprocess.PIPE, text=True).stdout.splitlines()
     assert [l for l in out if l.startswith("SSF_")] == []
-    for src in ("ssf_extract.hip", "ssf_pass_tile.hpp", "ssf_track_fuse.hip", "ssf_upkeep.hip", "ssf_p2p.hip", "ssf_rows.hpp", "ssf_mailbox.hpp", "ssf_tile_rows.inc",
+    for src in ("ssf_extract.hip", "ssf_pass_tile.hpp", "ssf_tile_geometry.hpp", "ssf_track_fuse.hip", "ssf_upkeep.hip", "ssf_p2p.hip", "ssf_rows.hpp", "ssf_mailbox.hpp", "ssf_tile_rows.inc",
                 "ssf_host.hip", "ssf_device.hpp", "ssf_math.hpp",
                 "ssf_handle.hpp", "ssf_render.hip", "ssf_graph.hip", "ssf_graph_solve.hip", "ssf_keyframes.hip", "ssf_slots.hpp",
                 "ssf_exchange.hip", "ssf_exchange.hpp", "ssf_testing.hip", "ssf_solvers.hpp"):
