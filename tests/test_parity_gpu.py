@@ -314,16 +314,24 @@ def test_segmentation_parameter_space(kw, oracle_lib, product_lib):
 
 
 @pytest.mark.parametrize("size,cell,filter_iter", [((640, 480), 12, 3), ((640, 480), 12, 7), ((1280, 960), 16, 3), ((1280, 960), 16, 0), ((640, 480), 8, 3), ((960, 720), 8, 4),
-                                                   ((320, 240), 16, 1), ((330, 250), 16, 5), ((640, 480), 16, 12), ((640, 480), 12, 12), ((1280, 960), 16, 12), ((960, 720), 8, 12)],
+                                                   ((320, 240), 16, 1), ((330, 250), 16, 5), ((640, 480), 16, 12), ((640, 480), 12, 12), ((1280, 960), 16, 12), ((960, 720), 8, 12),
+                                                   ((160, 128), 16, 4), ((640, 480), 16, 9), ((640, 480), 16, 10), ((1024, 512), 16, 12),
+                                                   ((640, 480), 16, 7), ((640, 480), 16, 8), ((960, 720), 16, 9), ((960, 720), 16, 10)],
                          ids=lambda v: "x".join(str(t) for t in v) if isinstance(v, tuple) else str(v))
 def test_plane_filter_at_every_grid_size(size, cell, filter_iter, oracle_lib, product_lib):
-    """TPS_RGBD::filter by the size of the superpixel grid and the number of sweeps.  Up to filter_iter 9 every grid larger than one
-    16 x 12 tile takes the round-5 form (k_plane_filter_tiled): many workgroups per frame, each computing its core tile and
-    everything within filter_iter of it -- including, for windows that touch the last column, the first columns one row down
-    (the reference's `x<gridSizeX` typo makes those neighbours).  More sweeps than a 1024-thread window holds fall back to one
-    workgroup per frame: all eleven floats per node in LDS up to 1396 nodes (k_plane_filter<true>), states + centroids in up to
-    160 KB of LDS with the data term in registers up to 5120 nodes (k_plane_filter_regs<3> / <5>: 2160 and 4800 nodes here), the
-    global scratch beyond (10 800 nodes).  Planes and everything rendered from them must be the oracle's, bit for bit."""
+    """TPS_RGBD::filter by the size of the superpixel grid and the number of sweeps: every form of pf_plan (csrc/ssf_tile_geometry.hpp;
+    tests/cpp/tile_geometry_smoke.cpp pins which grid takes which).
+    k_plane_filter_lds<1>: while the largest window of a 16 x 12 core tile holds at most 1024 nodes, a workgroup per tile computes
+    its core and everything within filter_iter of it -- including, for windows that touch the last column, the first columns one
+    row down (the reference's `x<gridSizeX` typo makes those neighbours).  A grid of one tile is such a window too (160x128).
+    640x480 at cell 16 (40 x 30) crosses the 1024 nodes between 7 sweeps (750) and 8 (1032: the middle tile's window reaches the
+    last column and takes the second rectangle), 960x720 at cell 16 (60 x 45), which has interior tiles, between 9 (1020) and 10
+    (1152).
+    k_plane_filter_lds<2> / <3> / <5>: beyond that one workgroup per frame holds the whole grid, up to 5120 nodes: 1200 nodes
+    (640x480 / 16), 2048 = 64 KB of LDS exactly, the most a launch gets without asking (1024x512 / 16: a refused launch would show
+    as SSF_ERR_DEVICE), 2160 (640x480 / 12) and 4800 (1280x960 / 16) in up to 160 KB.
+    k_plane_filter_global: the scratch in global memory beyond (10 800 nodes, 960x720 / 8).
+    Planes and everything rendered from them must be the oracle's, bit for bit."""
     W, H = size
     fo, fh = pair(oracle_lib, product_lib, W, H, nb_supersurfels_max=40000, cell_size=cell, filter_iter=filter_iter)
     rgb, depth = util.frame(1, W, H, noise=True, holes=0.03)
