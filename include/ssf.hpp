@@ -13,6 +13,7 @@
 #ifndef SSF_HPP
 #define SSF_HPP
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <limits>
 #include <stdexcept>
@@ -24,6 +25,7 @@
 #include "ssf_render.h"
 #include "ssf_query.h"
 #include "ssf_navgrid.h"
+#include "ssf_navcarve.h"
 #include "ssf_raycast.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
@@ -255,6 +257,22 @@ struct NavGrid {
     std::vector<int8_t> state;                     /* nav_msgs/OccupancyGrid's values: 100 occupied, 0 free, -1 unknown */
     std::vector<int32_t> dist2;                    /* squared distance in cells to the nearest obstacle cell, capped at max_dist_cells^2 */
     ssf_navgrid_stats stats;
+};
+/* buildNavGrid with views (ssf_navcarve.h; exported by libssf_hip_navcarve.so, linked INSTEAD of libssf_hip.so -- a program that
+ * does not call it links against libssf_hip.so as before: the inline member leaves no reference behind): the grid with free space carved along camera rays.  The
+ * members start at ssf_navcarve_default_params' values: width 0 = the configured camera and its intrinsics, t_min = t_max = 0 =
+ * the configured depth range, ray_splat_scale 0 = the ray cast's 3.  A miss carves nothing unless carve_misses says so. */
+struct CarveParams {
+    float fx = 0.f, fy = 0.f, cx = 0.f, cy = 0.f; int width = 0, height = 0;
+    int stride = 8;
+    float t_min = 0.f, t_max = 0.f, ray_min_conf = 0.f, ray_splat_scale = 0.f, hit_margin_cells = 1.f;
+    bool carve_misses = false; int min_seen = 1;
+    bool want_seen = true;
+};
+/* a NavGrid whose state and dist2 are carved, with the ray entries per cell; stats (the base's) = carve.grid */
+struct CarvedNavGrid : NavGrid {
+    std::vector<uint32_t> seen;
+    ssf_navcarve_stats carve;
 };
 
 /* castRays (ssf_raycast.h; exported by libssf_hip.so only): the first disc of the map that each ray hits.  The members start at
@@ -633,6 +651,33 @@ public:
      * rasteriser and the host distance transform a node would otherwise need.  INTEGRATION.md section 2 has the publishing side. */
     void buildNavGrid(const NavGridParams& g, NavGrid& out) {
         ssf_navgrid_params p; float v[12];
+        const ssf_navgrid_out o = navGridCall(g, p, v, out);
+        check(ssf_navgrid_build(need(), &p, &o, &out.stats));
+    }
+    /* The same grid with free space carved along the rays of `views` (ssf_navcarve.h): n camera-to-map poses of 12 floats each
+     * (R row-major, then t: transform3_to_rt), e.g. the node's trajectory so far.  out.seen counts, per cell, the rays that crossed
+     * the band of the robot's body before their hit; out.state and out.dist2 are carved, and fillOccupancyGrid takes out as it is. */
+    void buildNavGrid(const NavGridParams& g, const CarveParams& c, const float* views12, int n_views, CarvedNavGrid& out) {
+        ssf_navgrid_params p; float v[12];
+        ssf_navcarve_out o;
+        o.grid = navGridCall(g, p, v, out);
+        ssf_navcarve_params q;
+        check(ssf_navcarve_default_params(need(), &q));
+        q.views = views12; q.n_views = n_views;
+        q.fx = c.fx; q.fy = c.fy; q.cx = c.cx; q.cy = c.cy; q.cam_width = c.width; q.cam_height = c.height; q.stride = c.stride;
+        q.t_min = c.t_min; q.t_max = c.t_max; q.ray_min_conf = c.ray_min_conf; q.ray_splat_scale = c.ray_splat_scale;
+        q.hit_margin_cells = c.hit_margin_cells; q.carve_misses = c.carve_misses ? 1 : 0; q.min_seen = c.min_seen;
+        out.seen.resize(c.want_seen ? (size_t)(out.width >= 1 && out.height >= 1 ? (size_t)out.width * (size_t)out.height : 1) : 0);
+        o.seen = c.want_seen ? out.seen.data() : nullptr;
+        check(ssf_navgrid_carve(need(), &p, &q, &o, &out.carve));
+        out.stats = out.carve.grid;
+    }
+    void buildNavGrid(const NavGridParams& g, const CarveParams& c, const std::vector<std::array<float, 12> >& views, CarvedNavGrid& out) {
+        buildNavGrid(g, c, views.empty() ? nullptr : views[0].data(), (int)views.size(), out);
+    }
+private:
+    /* the C parameters of a grid call (v: room for the pose), out's vectors sized, and the output pointers into them */
+    ssf_navgrid_out navGridCall(const NavGridParams& g, ssf_navgrid_params& p, float* v, NavGrid& out) {
         check(ssf_navgrid_default_params(need(), &p));
         if (g.pose) { transform3_to_rt(*g.pose, v); p.pose = v; }
         p.width = g.width; p.height = g.height; p.res = g.res;
@@ -647,8 +692,9 @@ public:
         const ssf_navgrid_out o = {g.want_heights ? out.zmin.data() : nullptr, g.want_heights ? out.zmax.data() : nullptr,
                                    g.want_hits ? out.hits.data() : nullptr, g.want_state ? out.state.data() : nullptr,
                                    g.want_dist2 ? out.dist2.data() : nullptr};
-        check(ssf_navgrid_build(need(), &p, &o, &out.stats));
+        return o;
     }
+public:
     /* The fields of a nav_msgs::OccupancyGrid that the grid determines: data, info.resolution, info.width, info.height and
      * info.origin (the map-frame pose of cell (0, 0)'s corner: the grid frame's t, and its rotation as a quaternion).  header and
      * info.map_load_time are the node's.  Any message type with these members works (tests use a double). */

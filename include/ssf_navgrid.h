@@ -5,7 +5,8 @@
  * Without this call it copies the whole model out (ssf_get_model: 104 B per row), rasterises discs and runs a distance
  * transform on the host.  A top view of ssf_render_model does not replace it: the render keeps the NEAREST disc per pixel of a
  * pinhole camera, the grid is an orthographic aggregate over ALL discs above a cell, split by height band.  "Free" means floor
- * was observed in the cell, not that space was seen through: nothing is carved along the camera's rays.
+ * was observed in the cell, not that space was seen through: this call carves nothing along the camera's rays (ssf_navgrid_carve,
+ * ssf_navcarve.h, builds the same grid and does).
  *
  * What is aggregated: the model as it stands after the last completed frame (or ssf_set_model / ssf_apply_deformation).  Every
  * step below is one IEEE f32 operation, in the order written (the library builds with -ffp-contract=off and correctly rounded

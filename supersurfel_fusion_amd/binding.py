@@ -14,6 +14,9 @@ ICP_RECORD = 29
 MIGRANT_WORDS = 28
 _HERE = os.path.dirname(os.path.abspath(__file__))
 PRODUCT_LIB = os.path.join(_HERE, "csrc", "libssf_hip.so")
+# the product's objects plus the carve of the navigation grid (include/ssf_navcarve.h; csrc/Makefile): everything the product exports,
+# and the carve's entry points, which the product library does not export
+NAVCARVE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_navcarve.so")
 
 
 class SsfConfig(C.Structure):
@@ -104,6 +107,11 @@ NAVGRID_SYMBOLS = ["ssf_navgrid_default_params", "ssf_navgrid_default_pose", "ss
 NAVGRID_OUTPUTS = (("zmin", np.float32, ()), ("zmax", np.float32, ()), ("hits", np.uint32, (2,)), ("state", np.int8, ()),
                    ("dist2", np.int32, ()))
 NAVGRID_OUTPUT_NAMES = tuple(nm for nm, _, _ in NAVGRID_OUTPUTS)
+# the navigation grid with free space carved along camera rays (include/ssf_navcarve.h): exported by libssf_hip_navcarve.so only
+# (load_navcarve), not part of ssf.h
+NAVCARVE_SYMBOLS = ["ssf_navcarve_default_params", "ssf_navgrid_carve", "ssf_debug_navcarve_set_chunk_rays", "ssf_debug_navcarve_last"]
+NAVCARVE_OUTPUTS = NAVGRID_OUTPUTS + (("seen", np.uint32, ()),)
+NAVCARVE_OUTPUT_NAMES = tuple(nm for nm, _, _ in NAVCARVE_OUTPUTS)
 # rays cast through the model (include/ssf_raycast.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 RAYCAST_SYMBOLS = ["ssf_raycast_default_params", "ssf_raycast"]
 # the output arrays of ssf_raycast, in its argument order: name, dtype, per-ray shape
@@ -226,6 +234,30 @@ class SsfNavGridStats(C.Structure):
     def as_dict(self):
         d = {nm: int(getattr(self, nm)) for nm, _ in self._fields_ if nm != "pose"}
         d["pose"] = np.array(self.pose[:], np.float32)
+        return d
+
+
+class SsfNavCarveParams(C.Structure):
+    """ssf_navcarve_params (include/ssf_navcarve.h)"""
+    _fields_ = [("views", C.c_void_p), ("n_views", C.c_int)] + [(nm, C.c_float) for nm in ("fx", "fy", "cx", "cy")] + \
+               [(nm, C.c_int) for nm in ("cam_width", "cam_height", "stride")] + \
+               [(nm, C.c_float) for nm in ("t_min", "t_max", "ray_min_conf", "ray_splat_scale", "hit_margin_cells")] + \
+               [("carve_misses", C.c_int), ("min_seen", C.c_int)]
+
+
+class SsfNavCarveOut(C.Structure):
+    """ssf_navcarve_out (include/ssf_navcarve.h)"""
+    _fields_ = [("grid", SsfNavGridOut), ("seen", C.c_void_p)]
+
+
+class SsfNavCarveStats(C.Structure):
+    """ssf_navcarve_stats (include/ssf_navcarve.h)"""
+    _fields_ = [("grid", SsfNavGridStats)] + [(nm, C.c_int64) for nm in ("rays", "rays_hit", "rays_invalid", "rays_carving", "ray_samples",
+                                                                         "ray_entries", "cells_seen", "cells_carved")]
+
+    def as_dict(self):
+        d = self.grid.as_dict()
+        d.update({nm: int(getattr(self, nm)) for nm, _ in self._fields_ if nm != "grid"})
         return d
 
 
@@ -393,6 +425,13 @@ class Library:
         if self.has_raycast:
             L.ssf_raycast_default_params.argtypes = [vp, C.POINTER(SsfRaycastParams)]
             L.ssf_raycast.argtypes = [vp, C.POINTER(SsfRaycastParams), vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(SsfRaycastStats)]
+        self.has_navcarve = all(hasattr(L, nm) for nm in NAVCARVE_SYMBOLS)
+        if self.has_navcarve:
+            L.ssf_navcarve_default_params.argtypes = [vp, C.POINTER(SsfNavCarveParams)]
+            L.ssf_navgrid_carve.argtypes = [vp, C.POINTER(SsfNavGridParams), C.POINTER(SsfNavCarveParams), C.POINTER(SsfNavCarveOut),
+                                            C.POINTER(SsfNavCarveStats)]
+            L.ssf_debug_navcarve_set_chunk_rays.argtypes = [vp, C.c_int]
+            L.ssf_debug_navcarve_last.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
         if self.has_navgrid:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
@@ -483,6 +522,14 @@ def load_product():
     # csrc/Makefile; the product itself reads no environment variable); others by tools/build_variant.sh
     tag = os.environ.get("SSF_PRODUCT_VARIANT")
     return Library(os.path.join(_HERE, "csrc", "variants", tag, "libssf_hip.so") if tag else PRODUCT_LIB)
+
+
+def load_navcarve():
+    """Load libssf_hip_navcarve.so: the product's objects with the carve of the navigation grid linked in (include/ssf_navcarve.h).
+    A handle belongs to the library that created it: create the Fusion from THIS library to call nav_grid_carve on it.  Fails
+    loudly when it has not been built."""
+    import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
+    return Library(NAVCARVE_LIB)
 
 
 def load_lab():
@@ -1127,6 +1174,87 @@ class Fusion:
         pose = np.zeros(12, np.float32)
         self._ck(self.L.lib.ssf_navgrid_default_pose(self.h, C.byref(p), _ptr(pose)), "ssf_navgrid_default_pose")
         return pose
+
+    # ---- the navigation grid with free space carved along camera rays (include/ssf_navcarve.h) ------
+    def _need_navcarve(self, symbol):
+        if not self.L.has_navcarve:
+            raise SsfError("%s does not export %s: it carves no navigation grid (include/ssf_navcarve.h: libssf_hip_navcarve.so, binding.load_navcarve)"
+                           % (self.L.path, symbol))
+
+    def _navcarve_params(self, views, carve):
+        """(SsfNavCarveParams, the views array it points into).  views: n x 12 floats or n x 3 x 4 [R | t], camera-to-map, host memory
+        (None or empty: no views); carve: the other fields of ssf_navcarve_params by name, each at ssf_navcarve_default_params'
+        value when missing."""
+        c = SsfNavCarveParams()
+        self._ck(self.L.lib.ssf_navcarve_default_params(self.h, C.byref(c)), "ssf_navcarve_default_params")
+        keep = None
+        if views is not None and np.size(views):
+            v = np.asarray(views, np.float32)
+            if v.ndim == 3 and v.shape[1:] == (3, 4):
+                v = np.concatenate([v[:, :, :3].reshape(len(v), 9), v[:, :, 3]], axis=1)
+            if v.ndim != 2 or v.shape[1] != 12:
+                raise SsfError("views are n x 12 floats (R row-major, then t) or n x 3 x 4 [R | t], got shape %s" % (v.shape,))
+            keep = np.ascontiguousarray(v, np.float32)
+            c.views, c.n_views = keep.ctypes.data, len(keep)
+        kinds = dict(c._fields_)
+        for nm, val in (carve or {}).items():
+            if nm not in kinds or nm in ("views", "n_views"):
+                raise SsfError("unknown carve parameter %r" % nm)
+            setattr(c, nm, float(val) if kinds[nm] is C.c_float else int(val))
+        return c, keep
+
+    def _navgrid_carve(self, p, c, ptrs):
+        st = SsfNavCarveStats()
+        out = SsfNavCarveOut(SsfNavGridOut(*[ptrs.get(nm) for nm in NAVGRID_OUTPUT_NAMES]), ptrs.get("seen"))
+        self._ck(self.L.lib.ssf_navgrid_carve(self.h, C.byref(p), C.byref(c), C.byref(out), C.byref(st)), "ssf_navgrid_carve")
+        return st.as_dict()
+
+    def nav_grid_carve(self, views, outputs=NAVCARVE_OUTPUT_NAMES, carve=None, **kw):
+        """The navigation grid with free space carved along the rays of `views` (ssf_navgrid_carve): nav_grid's dict (the state and
+        dist2 carved) plus seen (H x W u32: ray entries per cell) and the carve's counts in 'stats'.  views, carve:
+        _navcarve_params; the other keywords: _navgrid_params."""
+        self._need_navcarve("ssf_navgrid_carve")
+        bad = [nm for nm in outputs if nm not in NAVCARVE_OUTPUT_NAMES]
+        if bad:
+            raise SsfError("unknown carved grid outputs %s (known: %s)" % (bad, ", ".join(NAVCARVE_OUTPUT_NAMES)))
+        p, keep = self._navgrid_params(False, **kw)
+        c, keep_views = self._navcarve_params(views, carve)
+        W, H = p.width, p.height
+        if not (1 <= W <= 4096 and 1 <= H <= 4096):
+            W = H = 1                        # (the library refuses the size and writes nothing)
+        out = {nm: np.empty((H, W) + tail, dt) for nm, dt, tail in NAVCARVE_OUTPUTS if nm in outputs}
+        stats = self._navgrid_carve(p, c, {nm: _ptr(a) for nm, a in out.items()})
+        out["stats"] = stats
+        return out
+
+    def nav_grid_carve_device(self, views, zmin=None, zmax=None, hits=None, state=None, dist2=None, seen=None, carve=None, **kw):
+        """ssf_navgrid_carve into device memory: each output is None, a contiguous torch tensor on the device or the device address
+        (int) of a buffer of the shape and dtype nav_grid_carve returns; the views stay host memory.  Returns the stats dict."""
+        self._need_navcarve("ssf_navgrid_carve")
+        p, keep = self._navgrid_params(True, **kw)
+        c, keep_views = self._navcarve_params(views, carve)
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        return self._navgrid_carve(p, c, dict(zmin=addr(zmin), zmax=addr(zmax), hits=addr(hits), state=addr(state), dist2=addr(dist2),
+                                              seen=addr(seen)))
+
+    def nav_grid_carve_default_params(self):
+        """ssf_navcarve_default_params as a dict"""
+        self._need_navcarve("ssf_navcarve_default_params")
+        c = SsfNavCarveParams()
+        self._ck(self.L.lib.ssf_navcarve_default_params(self.h, C.byref(c)), "ssf_navcarve_default_params")
+        return {nm: getattr(c, nm) for nm, _ in c._fields_ if nm != "views"}
+
+    def debug_navcarve_set_chunk_rays(self, max_rays):
+        """test hook: the rays per chunk of nav_grid_carve (0 = the default); results do not depend on it"""
+        self._need_navcarve("ssf_debug_navcarve_set_chunk_rays")
+        self._ck(self.L.lib.ssf_debug_navcarve_set_chunk_rays(self.h, int(max_rays)), "ssf_debug_navcarve_set_chunk_rays")
+
+    def debug_navcarve_last(self):
+        """dict(chunks, atomics) of the last nav_grid_carve of this handle"""
+        self._need_navcarve("ssf_debug_navcarve_last")
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.lib.ssf_debug_navcarve_last(self.h, C.byref(a), C.byref(b)), "ssf_debug_navcarve_last")
+        return dict(chunks=int(a.value), atomics=int(b.value))
 
     # ---- rays cast through the model: the first disc each ray hits (include/ssf_raycast.h) ------------
     def _need_raycast(self, symbol):

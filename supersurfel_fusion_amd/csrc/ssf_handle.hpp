@@ -329,6 +329,16 @@ struct NavGridWs {
     unsigned long long* stats = nullptr;
     unsigned char* img = nullptr; size_t img_bytes = 0;
 };
+// ssf_navgrid_carve (ssf_navcarve.h, ssf_navcarve.hip: linked into libssf_hip_navcarve.so only), next to NavGridWs, which it shares with ssf_navgrid_build: the views (4096 x 12 floats), a
+// chunk of rays with their hits (t, index), per cell the ray entries, the sums.  Allocated on first use; each group is grown as a
+// whole or not at all (DevBufs::grow).  chunk_rays: the test hook (0 = 2^20 rays per chunk); last_*: what the last call did.
+struct NavCarveWs {
+    DevBufs bufs;
+    float* views = nullptr; unsigned long long* stats = nullptr;
+    float* rays = nullptr; float* t = nullptr; int32_t* index = nullptr; size_t ray_cap = 0;
+    uint32_t* seen = nullptr; size_t cells = 0;
+    int chunk_rays = 0; long long last_chunks = 0, last_atomics = 0;
+};
 // ssf_raycast (ssf_raycast.h): the resident index -- per slot the 64-byte record and the box of cells with the row's class, the
 // out-of-view blocks' live offsets, the oversize list; per bucket (+ 1) the list offsets and the fill's cursors; the (bucket -> slot)
 // lists; the sums and the box of indexed cells -- and the staging buffer of a call's host rays and outputs.  The index is valid
@@ -454,6 +464,7 @@ struct ssf_handle {
     MotionWs motion;                              // ssf_motion_* (ssf_motion.h)
     OdoWs odo;                                    // ssf_odometry_* (ssf_odometry.h)
     NavGridWs navgrid;                            // ssf_navgrid_build (ssf_navgrid.h)
+    NavCarveWs navcarve;                          // ssf_navgrid_carve (ssf_navcarve.h)
     RaycastWs raycast;                            // ssf_raycast (ssf_raycast.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense); the out-of-view
                                                   // compaction keeps rows and order but moves slots: who keeps slot numbers also watches n_recentres (RaycastWs)

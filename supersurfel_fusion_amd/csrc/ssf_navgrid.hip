@@ -27,27 +27,12 @@
 //              over |dx| <= R of g^2 + dx^2, capped at R^2.  Integers throughout.
 // Sums are reduced per workgroup and added with one 64-bit atomic each.  Nothing here writes to the handle's stores, counters or
 // scratch: the working set is NavGridWs (ssf_handle.hpp).
-#include "ssf_slots.hpp"
-#include "ssf_handle.hpp"
+//
+// The call is made of four parts -- begin, reserve, accumulate, finish (ssf_navgrid.hpp) -- which ssf_navgrid_carve
+// (ssf_navcarve.hip, include/ssf_navcarve.h) runs as well, with its rays between accumulate and finish.
+#include "ssf_navgrid.hpp"
 
 namespace ssf {
-
-enum { NAV_TILE = 32, NAV_TILE_SHIFT = 5, NAV_CELLS = NAV_TILE * NAV_TILE, NAV_CHUNK = 256, NAV_HIST = 2048, NAV_MAX_SPLIT = 32 };
-// the grid's accumulators: four planes of P words.  Empty: ~0 in the minimum's plane, 0 in the others (no float's image is either)
-struct NavAcc { uint32_t* zmin; uint32_t* zmax; uint32_t* nfloor; uint32_t* nobst; };
-// the sums the host reads: rows used, samples that exist, samples accepted, cells free / occupied / unknown, list entries
-enum { NAV_ROWS = 0, NAV_SAMPLES = 1, NAV_ACCEPTED = 2, NAV_FREE = 3, NAV_OCC = 4, NAV_UNKNOWN = 5, NAV_LIST = 6, NAV_STATS = 8 };
-
-// R = 9 floats row-major and t (grid-to-map, ssf_get_pose's layout); ntx x nty tiles of 32 x 32 cells; fW = (float)W
-struct NavGrid {
-    float R[9], t[3];
-    int W, H, ntx, nty;
-    float res, step, fW, fH, zmin, zmax, floor_max, floor_cos, min_conf, s;
-    int32_t ti0, ti1, tl0, tl1;
-    int max_steps, min_hits;
-};
-struct NavView { NavGrid grid; ModelView model; };               // one kernel argument: the grid and the rows put into it
-struct NavOut { float* zmin; float* zmax; uint32_t* hits; int8_t* state; };       // nullptr = not produced
 
 // steps per half-axis (include/ssf_navgrid.h step 3): q = ceilf(h / step)
 __device__ __forceinline__ int nav_steps(float h, float step, int max_steps) {
@@ -248,27 +233,9 @@ __global__ __launch_bounds__(1024) void k_navgrid_tile(NavGrid G, int split, con
     }
 }
 
-// ---- cells: one thread per cell -------------------------------------------------------------------------------------------
+// ---- cells: one thread per cell (the body: ssf_navgrid.hpp) --------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_navgrid_cells(NavAcc acc, size_t P, int min_hits, NavOut out, unsigned long long* __restrict__ stats) {
-    __shared__ unsigned long long red[3][4];
-    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
-    unsigned long long nfree = 0, nocc = 0, nunk = 0;
-    if (p < P) {
-        const uint32_t zlo = acc.zmin[p], zhi = acc.zmax[p], nfloor = acc.nfloor[p], nobst = acc.nobst[p];
-        const int8_t st = nobst >= (uint32_t)min_hits ? (int8_t)100 : (nfloor >= (uint32_t)min_hits ? (int8_t)0 : (int8_t)-1);
-        nocc = st == 100; nfree = st == 0; nunk = st < 0;
-        if (out.zmin) out.zmin[p] = __uint_as_float(zlo == ~0u ? 0x7F800000u : float_order_bits_inv(zlo));       // empty: +inf
-        if (out.zmax) out.zmax[p] = __uint_as_float(zhi == 0u ? 0xFF800000u : float_order_bits_inv(zhi));        // empty: -inf
-        if (out.hits) { out.hits[2 * p] = nfloor; out.hits[2 * p + 1] = nobst; }
-        if (out.state) out.state[p] = st;
-    }
-    nfree = wave_sum(nfree); nocc = wave_sum(nocc); nunk = wave_sum(nunk);
-    if (lane() == 0) { red[0][threadIdx.x >> 6] = nfree; red[1][threadIdx.x >> 6] = nocc; red[2][threadIdx.x >> 6] = nunk; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const unsigned long long sum = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
-        if (sum) atomicAdd(&stats[NAV_FREE + threadIdx.x], sum);
-    }
+    navgrid_cells_body<false>(acc, P, min_hits, out, stats, NavSeen{nullptr, 1, nullptr, nullptr});
 }
 
 // ---- clearance: columns, then rows ------------------------------------------------------------------------------------------
@@ -319,14 +286,17 @@ static void launch_navgrid_fill(hipStream_t st, const NavView& nv, const uint2* 
     if (nv.model.nslots > 0)
         hipLaunchKernelGGL(k_navgrid_fill, dim3(nv.model.nslots / 256), dim3(256), 0, st, nv.model.nslots, nv.grid.ntx, nv.grid.ntx * nv.grid.nty, rbox, cursor, list);
 }
-// acc (its minimum plane set to ~0, the others to 0 by the caller) += the samples; then the cells' outputs and counts
+// acc (its minimum plane set to ~0, the others to 0 by the caller) += the samples
 static void launch_navgrid_tile(hipStream_t st, const NavGrid& G, int split, const float4* rec, const uint32_t* list, const uint32_t* toff,
-                                const NavAcc& acc, const NavOut& out, unsigned long long* stats) {
-    { ScopedKernel sk("navgrid_tile", st);
-      hipLaunchKernelGGL(k_navgrid_tile, dim3(G.ntx * G.nty * split), dim3(1024), 0, st, G, split, rec, list, toff, acc, stats); }
-    { ScopedKernel sk("navgrid_cells", st);
-      const size_t P = (size_t)G.W * G.H;
-      hipLaunchKernelGGL(k_navgrid_cells, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, acc, P, G.min_hits, out, stats); }
+                                const NavAcc& acc, unsigned long long* stats) {
+    ScopedKernel sk("navgrid_tile", st);
+    hipLaunchKernelGGL(k_navgrid_tile, dim3(G.ntx * G.nty * split), dim3(1024), 0, st, G, split, rec, list, toff, acc, stats);
+}
+// the cells' outputs and counts (a NavCellsLaunch: the carve has its own)
+static void launch_navgrid_cells(hipStream_t st, const NavGrid& G, const NavAcc& acc, const NavOut& out, unsigned long long* stats, const NavSeen*) {
+    ScopedKernel sk("navgrid_cells", st);
+    const size_t P = (size_t)G.W * G.H;
+    hipLaunchKernelGGL(k_navgrid_cells, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, acc, P, G.min_hits, out, stats);
 }
 static void launch_navgrid_clearance(hipStream_t st, const int8_t* state, int W, int H, int R, int unknown_too, uint16_t* g, int32_t* dist2) {
     { ScopedKernel sk("navgrid_columns", st);
@@ -346,10 +316,116 @@ static void navgrid_default_pose(const ssf_handle* h, float res, int W, int H, f
     pose[10] = 0.0f;
     pose[11] = (floorf(h->pose.t.z / res) - (float)(H / 2)) * res;
 }
-static const char* navgrid_size_res(const ssf_navgrid_params* p) {
+const char* navgrid_size_res(const ssf_navgrid_params* p) {
     if (p->width < 1 || p->width > 4096 || p->height < 1 || p->height > 4096) return "the grid's size must be 1..4096 x 1..4096";
     if (!std::isfinite(p->res) || !(p->res > 0.0f)) return "res must be finite and > 0";
     return nullptr;
+}
+
+int navgrid_begin(ssf_handle* h, const ssf_navgrid_params* p, NavCall& c) {
+    auto refuse = [&](const char* what) { h->err = std::string(c.who) + ": " + what; return SSF_ERR_INVALID_ARG; };
+    if (const char* what = navgrid_size_res(p)) return refuse(what);
+    NavGrid& G = c.G;
+    G.s = p->splat_scale == 0.0f ? 2.0f : p->splat_scale;
+    if (!(G.s >= 0.0f) || !std::isfinite(G.s)) return refuse("splat_scale must be finite and >= 0");
+    if (p->max_steps < 1 || p->max_steps > 16) return refuse("max_steps must be 1..16");
+    if (p->max_dist_cells < 1 || p->max_dist_cells > 1024) return refuse("max_dist_cells must be 1..1024");
+    if (p->min_hits < 1) return refuse("min_hits must be >= 1");
+    if (!(p->z_max >= p->z_min)) return refuse("the height range needs z_min <= z_max");
+    if (p->t_init_min > p->t_init_max || p->t_last_min > p->t_last_max) return refuse("a stamp range has min > max");
+    if (!(p->floor_cos >= 0.0f) || !(p->floor_cos <= 1.0f)) return refuse("floor_cos must be in [0, 1]");
+    { int rc = model_at_rest(h, c.who, "has no navigation grid"); if (rc) return rc; }
+    float* pose = c.pose;
+    if (p->pose) std::memcpy(pose, p->pose, sizeof(c.pose));
+    else navgrid_default_pose(h, p->res, p->width, p->height, pose);
+    std::memcpy(G.R, pose, 9 * sizeof(float)); G.t[0] = pose[9]; G.t[1] = pose[10]; G.t[2] = pose[11];
+    G.W = p->width; G.H = p->height; G.ntx = (G.W + NAV_TILE - 1) / NAV_TILE; G.nty = (G.H + NAV_TILE - 1) / NAV_TILE;
+    G.res = p->res; G.step = p->res * 0.5f; G.fW = (float)G.W; G.fH = (float)G.H;
+    G.zmin = p->z_min; G.zmax = p->z_max; G.floor_max = p->floor_max; G.floor_cos = p->floor_cos; G.min_conf = p->min_conf;
+    G.ti0 = p->t_init_min; G.ti1 = p->t_init_max; G.tl0 = p->t_last_min; G.tl1 = p->t_last_max;
+    G.max_steps = p->max_steps; G.min_hits = p->min_hits;
+    c.P = (size_t)G.W * G.H; c.total = 0;
+    return SSF_OK;
+}
+
+int navgrid_reserve(ssf_handle* h, const ssf_navgrid_params* p, const NavCall& c, StagedIo& io) {
+    NavGridWs& w = h->navgrid;
+    const size_t P = c.P;
+    const size_t slots = std::max<size_t>(model_view(h, p->visible_only != 0).nslots, 256);
+    bool ok = true;
+    if (slots > w.slots) {
+        ok = w.bufs.grow({{(void**)&w.rec, 64 * slots}, {(void**)&w.rbox, 8 * slots}});
+        if (ok) w.slots = slots;
+    }
+    if (ok) ok = w.tl.reserve_bins(w.bufs, (size_t)c.G.ntx * c.G.nty);
+    if (ok && P > w.cells) {
+        ok = w.bufs.grow({{(void**)&w.acc, 16 * P}, {(void**)&w.colg, 2 * P}, {(void**)&w.state, P}});
+        if (ok) w.cells = P;
+    }
+    if (ok && !w.stats) ok = w.bufs.grow({{(void**)&w.stats, NAV_STATS * sizeof(unsigned long long)}});
+    if (ok) ok = io.reserve(w.bufs, &w.img, &w.img_bytes, io.need());
+    if (!ok) { h->err = std::string(c.who) + ": allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
+    return SSF_OK;
+}
+
+// (under the caller's TimerScope) the accumulators of the grid from the model's rows; c.total = the list entries
+int navgrid_accumulate(ssf_handle* h, const ssf_navgrid_params* p, NavCall& c) {
+    NavGridWs& w = h->navgrid;
+    const NavGrid& G = c.G;
+    const size_t P = c.P;
+    const int ntiles = G.ntx * G.nty;
+    const NavView nv{G, model_view(h, p->visible_only != 0)};
+    hipStream_t st = h->stream;
+    HCK(hipMemsetAsync(w.tl.off, 0, 4 * ((size_t)ntiles + 1), st));
+    HCK(hipMemsetAsync(w.stats, 0, NAV_STATS * sizeof(unsigned long long), st));
+    launch_navgrid_prep(st, nv, w.rec, w.rbox, w.tl.off, w.tl.cursor, w.stats);
+    HCK(hipGetLastError());
+    unsigned long long total = 0;
+    HCK(hipMemcpyAsync(&total, w.stats + NAV_LIST, sizeof(total), hipMemcpyDeviceToHost, st));
+    HCK(hipStreamSynchronize(st));
+    const std::string who(c.who);
+    { int rc = w.tl.reserve_list(w.bufs, total, h->err, (who + ": more than 2^32 - 1 (tile, row) list entries").c_str(),
+                                 (who + ": allocation of ").c_str(), " bytes for the tile lists failed"); if (rc) return rc; }
+    if (total > 0) { launch_navgrid_fill(st, nv, w.rbox, w.tl.cursor, w.tl.list); HCK(hipGetLastError()); }
+    const NavAcc acc{w.acc, w.acc + P, w.acc + 2 * P, w.acc + 3 * P};
+    HCK(hipMemsetAsync(acc.zmin, 0xFF, 4 * P, st));
+    HCK(hipMemsetAsync(acc.zmax, 0, 12 * P, st));
+    // parts per tile: enough workgroups for the chip when the lists are long, one when they are short
+    const int split = (int)std::min<unsigned long long>(NAV_MAX_SPLIT, std::max<unsigned long long>(1, total / (16 * NAV_CHUNK)));
+    launch_navgrid_tile(st, G, split, w.rec, w.tl.list, w.tl.off, acc, w.stats);
+    HCK(hipGetLastError());
+    c.total = total;
+    return SSF_OK;
+}
+
+// (under the caller's TimerScope) sn: nullptr, or the carve's ray entries, whose NC_STATS sums come back in carve_sums
+int navgrid_finish(ssf_handle* h, const ssf_navgrid_params* p, const NavCall& c, NavOut o, int32_t* d2, const StagedIo& io, NavCellsLaunch cells,
+                   const NavSeen* sn, ssf_navgrid_stats* stats, unsigned long long* carve_sums) {
+    NavGridWs& w = h->navgrid;
+    const NavGrid& G = c.G;
+    const size_t P = c.P;
+    hipStream_t st = h->stream;
+    const NavAcc acc{w.acc, w.acc + P, w.acc + 2 * P, w.acc + 3 * P};
+    const bool want_dist = d2 != nullptr;
+    if (want_dist && !o.state) o.state = w.state;                    // dist2 alone: the state is still computed, internally
+    cells(st, G, acc, o, w.stats, sn);
+    HCK(hipGetLastError());
+    if (want_dist) {
+        launch_navgrid_clearance(st, o.state, G.W, G.H, p->max_dist_cells, p->unknown_is_obstacle != 0, w.colg, d2);
+        HCK(hipGetLastError());
+    }
+    unsigned long long s7[NAV_LIST] = {0, 0, 0, 0, 0, 0};
+    HCK(hipMemcpyAsync(s7, w.stats, sizeof(s7), hipMemcpyDeviceToHost, st));
+    if (sn && carve_sums) HCK(hipMemcpyAsync(carve_sums, sn->stats, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HCK(io.copy_out(st));
+    { int rc = sync_collect(h); if (rc) return rc; }
+    if (stats) {
+        stats->rows_used = (int64_t)s7[NAV_ROWS]; stats->samples = (int64_t)s7[NAV_SAMPLES]; stats->samples_in_grid = (int64_t)s7[NAV_ACCEPTED];
+        stats->cells_free = (int64_t)s7[NAV_FREE]; stats->cells_occupied = (int64_t)s7[NAV_OCC]; stats->cells_unknown = (int64_t)s7[NAV_UNKNOWN];
+        stats->list_entries = (int64_t)c.total;
+        std::memcpy(stats->pose, c.pose, sizeof(c.pose));
+    }
+    return SSF_OK;
 }
 
 extern "C" {
@@ -374,32 +450,10 @@ int ssf_navgrid_build(ssf_handle* h, const ssf_navgrid_params* p, const ssf_navg
     if (!h || !p) return SSF_ERR_INVALID_ARG;
     auto refuse = [&](const char* what) { h->err = std::string("ssf_navgrid_build: ") + what; return SSF_ERR_INVALID_ARG; };
     if (!out || (!out->zmin && !out->zmax && !out->hits && !out->state && !out->dist2)) return refuse("every output is NULL");
-    if (const char* what = navgrid_size_res(p)) return refuse(what);
-    NavGrid G;
-    G.s = p->splat_scale == 0.0f ? 2.0f : p->splat_scale;
-    if (!(G.s >= 0.0f) || !std::isfinite(G.s)) return refuse("splat_scale must be finite and >= 0");
-    if (p->max_steps < 1 || p->max_steps > 16) return refuse("max_steps must be 1..16");
-    if (p->max_dist_cells < 1 || p->max_dist_cells > 1024) return refuse("max_dist_cells must be 1..1024");
-    if (p->min_hits < 1) return refuse("min_hits must be >= 1");
-    if (!(p->z_max >= p->z_min)) return refuse("the height range needs z_min <= z_max");
-    if (p->t_init_min > p->t_init_max || p->t_last_min > p->t_last_max) return refuse("a stamp range has min > max");
-    if (!(p->floor_cos >= 0.0f) || !(p->floor_cos <= 1.0f)) return refuse("floor_cos must be in [0, 1]");
-    { int rc = model_at_rest(h, "ssf_navgrid_build", "has no navigation grid"); if (rc) return rc; }
-    float pose[12];
-    if (p->pose) std::memcpy(pose, p->pose, sizeof(pose));
-    else navgrid_default_pose(h, p->res, p->width, p->height, pose);
-    std::memcpy(G.R, pose, 9 * sizeof(float)); G.t[0] = pose[9]; G.t[1] = pose[10]; G.t[2] = pose[11];
-    G.W = p->width; G.H = p->height; G.ntx = (G.W + NAV_TILE - 1) / NAV_TILE; G.nty = (G.H + NAV_TILE - 1) / NAV_TILE;
-    G.res = p->res; G.step = p->res * 0.5f; G.fW = (float)G.W; G.fH = (float)G.H;
-    G.zmin = p->z_min; G.zmax = p->z_max; G.floor_max = p->floor_max; G.floor_cos = p->floor_cos; G.min_conf = p->min_conf;
-    G.ti0 = p->t_init_min; G.ti1 = p->t_init_max; G.tl0 = p->t_last_min; G.tl1 = p->t_last_max;
-    G.max_steps = p->max_steps; G.min_hits = p->min_hits;
-    const int ntiles = G.ntx * G.nty;
-    const NavView nv{G, model_view(h, p->visible_only != 0)};
-
-    NavGridWs& w = h->navgrid;
-    const size_t P = (size_t)G.W * G.H;
-    const bool want_dist = out->dist2 != nullptr;
+    NavCall c;
+    c.who = "ssf_navgrid_build";
+    { int rc = navgrid_begin(h, p, c); if (rc) return rc; }
+    const size_t P = c.P;
     NavOut o{out->zmin, out->zmax, out->hits, out->state};
     int32_t* d2 = out->dist2;
     StagedIo io;                                                     // host outputs are staged on the device
@@ -407,55 +461,10 @@ int ssf_navgrid_build(ssf_handle* h, const ssf_navgrid_params* p, const ssf_navg
         io.out(out->zmin, 4 * P, &o.zmin); io.out(out->zmax, 4 * P, &o.zmax); io.out(out->hits, 8 * P, &o.hits);
         io.out(out->state, P, &o.state); io.out(out->dist2, 4 * P, &d2);
     }
-    const size_t slots = std::max<size_t>(nv.model.nslots, 256);
-    bool ok = true;
-    if (slots > w.slots) {
-        ok = w.bufs.grow({{(void**)&w.rec, 64 * slots}, {(void**)&w.rbox, 8 * slots}});
-        if (ok) w.slots = slots;
-    }
-    if (ok) ok = w.tl.reserve_bins(w.bufs, (size_t)ntiles);
-    if (ok && P > w.cells) {
-        ok = w.bufs.grow({{(void**)&w.acc, 16 * P}, {(void**)&w.colg, 2 * P}, {(void**)&w.state, P}});
-        if (ok) w.cells = P;
-    }
-    if (ok && !w.stats) ok = w.bufs.grow({{(void**)&w.stats, NAV_STATS * sizeof(unsigned long long)}});
-    if (ok) ok = io.reserve(w.bufs, &w.img, &w.img_bytes, io.need());
-    if (!ok) { h->err = "ssf_navgrid_build: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
-
+    { int rc = navgrid_reserve(h, p, c, io); if (rc) return rc; }
     TimerScope ts(h);
-    hipStream_t st = h->stream;
-    HCK(hipMemsetAsync(w.tl.off, 0, 4 * ((size_t)ntiles + 1), st));
-    HCK(hipMemsetAsync(w.stats, 0, NAV_STATS * sizeof(unsigned long long), st));
-    launch_navgrid_prep(st, nv, w.rec, w.rbox, w.tl.off, w.tl.cursor, w.stats);
-    HCK(hipGetLastError());
-    unsigned long long total = 0;
-    HCK(hipMemcpyAsync(&total, w.stats + NAV_LIST, sizeof(total), hipMemcpyDeviceToHost, st));
-    HCK(hipStreamSynchronize(st));
-    { int rc = w.tl.reserve_list(w.bufs, total, h->err, "ssf_navgrid_build: more than 2^32 - 1 (tile, row) list entries",
-                                 "ssf_navgrid_build: allocation of ", " bytes for the tile lists failed"); if (rc) return rc; }
-    if (total > 0) { launch_navgrid_fill(st, nv, w.rbox, w.tl.cursor, w.tl.list); HCK(hipGetLastError()); }
-    const NavAcc acc{w.acc, w.acc + P, w.acc + 2 * P, w.acc + 3 * P};
-    HCK(hipMemsetAsync(acc.zmin, 0xFF, 4 * P, st));
-    HCK(hipMemsetAsync(acc.zmax, 0, 12 * P, st));
-    // parts per tile: enough workgroups for the chip when the lists are long, one when they are short
-    const int split = (int)std::min<unsigned long long>(NAV_MAX_SPLIT, std::max<unsigned long long>(1, total / (16 * NAV_CHUNK)));
-    if (want_dist && !o.state) o.state = w.state;                    // dist2 alone: the state is still computed, internally
-    launch_navgrid_tile(st, G, split, w.rec, w.tl.list, w.tl.off, acc, o, w.stats);
-    HCK(hipGetLastError());
-    if (want_dist) {
-        launch_navgrid_clearance(st, o.state, G.W, G.H, p->max_dist_cells, p->unknown_is_obstacle != 0, w.colg, d2);
-        HCK(hipGetLastError());
-    }
-    unsigned long long s7[NAV_LIST] = {0, 0, 0, 0, 0, 0};
-    HCK(hipMemcpyAsync(s7, w.stats, sizeof(s7), hipMemcpyDeviceToHost, st));
-    HCK(io.copy_out(st));
-    { int rc = sync_collect(h); if (rc) return rc; }
-    if (stats) {
-        stats->rows_used = (int64_t)s7[NAV_ROWS]; stats->samples = (int64_t)s7[NAV_SAMPLES]; stats->samples_in_grid = (int64_t)s7[NAV_ACCEPTED];
-        stats->cells_free = (int64_t)s7[NAV_FREE]; stats->cells_occupied = (int64_t)s7[NAV_OCC]; stats->cells_unknown = (int64_t)s7[NAV_UNKNOWN];
-        stats->list_entries = (int64_t)total;
-        std::memcpy(stats->pose, pose, sizeof(pose));
-    }
-    return SSF_OK;
+    { int rc = navgrid_accumulate(h, p, c); if (rc) return rc; }
+    return navgrid_finish(h, p, c, o, d2, io, launch_navgrid_cells, nullptr, stats);
 }
+
 }  // extern "C"

@@ -1,0 +1,91 @@
+// ssf_navgrid.hpp -- what ssf_navgrid.hip (ssf_navgrid_build, in the product library) shares with ssf_navcarve.hip
+// (ssf_navgrid_carve, include/ssf_navcarve.h): the kernels' view of a grid, the cells kernel's body, and the four parts of a
+// grid call.  Private to the library's own files: nothing here is exported.
+#pragma once
+#include "ssf_slots.hpp"
+#include "ssf_handle.hpp"
+
+namespace ssf {
+
+enum { NAV_TILE = 32, NAV_TILE_SHIFT = 5, NAV_CELLS = NAV_TILE * NAV_TILE, NAV_CHUNK = 256, NAV_HIST = 2048, NAV_MAX_SPLIT = 32 };
+// the grid's accumulators: four planes of P words.  Empty: ~0 in the minimum's plane, 0 in the others (no float's image is either)
+struct NavAcc { uint32_t* zmin; uint32_t* zmax; uint32_t* nfloor; uint32_t* nobst; };
+// the sums the host reads: rows used, samples that exist, samples accepted, cells free / occupied / unknown, list entries
+enum { NAV_ROWS = 0, NAV_SAMPLES = 1, NAV_ACCEPTED = 2, NAV_FREE = 3, NAV_OCC = 4, NAV_UNKNOWN = 5, NAV_LIST = 6, NAV_STATS = 8 };
+// ... of a carve (include/ssf_navcarve.h): carving rays, their samples, entries, cells seen, cells carved | atomics issued on `seen`
+enum { NC_CARVING = 0, NC_SAMPLES = 1, NC_ENTRIES = 2, NC_SEEN = 3, NC_CARVED = 4, NC_ATOMICS = 5, NC_STATS = 8 };
+
+// R = 9 floats row-major and t (grid-to-map, ssf_get_pose's layout); ntx x nty tiles of 32 x 32 cells; fW = (float)W
+struct NavGrid {
+    float R[9], t[3];
+    int W, H, ntx, nty;
+    float res, step, fW, fH, zmin, zmax, floor_max, floor_cos, min_conf, s;
+    int32_t ti0, ti1, tl0, tl1;
+    int max_steps, min_hits;
+};
+struct NavView { NavGrid grid; ModelView model; };               // one kernel argument: the grid and the rows put into it
+struct NavOut { float* zmin; float* zmax; uint32_t* hits; int8_t* state; };       // nullptr = not produced
+
+// ---- cells: one thread per cell -------------------------------------------------------------------------------------------
+// CARVE (include/ssf_navcarve.h step 7): a cell with seen >= min_seen ray entries is free unless it is occupied; the cells seen
+// and the cells that this turned from unknown to free are counted, and `seen` goes out with the other arrays
+struct NavSeen { const uint32_t* seen; int min_seen; uint32_t* out; unsigned long long* stats; };
+// the body of k_navgrid_cells (ssf_navgrid.hip) and of its carving sibling k_navcarve_cells (ssf_navcarve.hip): workgroups of 256
+template <bool CARVE>
+__device__ __forceinline__ void navgrid_cells_body(const NavAcc& acc, size_t P, int min_hits, const NavOut& out, unsigned long long* __restrict__ stats,
+                                                   const NavSeen& sn) {
+    __shared__ unsigned long long red[CARVE ? 5 : 3][4];
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long nfree = 0, nocc = 0, nunk = 0, nseen = 0, ncarved = 0;
+    if (p < P) {
+        const uint32_t zlo = acc.zmin[p], zhi = acc.zmax[p], nfloor = acc.nfloor[p], nobst = acc.nobst[p];
+        int8_t st = nobst >= (uint32_t)min_hits ? (int8_t)100 : (nfloor >= (uint32_t)min_hits ? (int8_t)0 : (int8_t)-1);
+        if (CARVE) {
+            const uint32_t s = sn.seen[p];
+            const bool through = s >= (uint32_t)sn.min_seen;
+            nseen = through; ncarved = through && st < 0;
+            if (ncarved) st = (int8_t)0;
+            if (sn.out) sn.out[p] = s;
+        }
+        nocc = st == 100; nfree = st == 0; nunk = st < 0;
+        if (out.zmin) out.zmin[p] = __uint_as_float(zlo == ~0u ? 0x7F800000u : float_order_bits_inv(zlo));       // empty: +inf
+        if (out.zmax) out.zmax[p] = __uint_as_float(zhi == 0u ? 0xFF800000u : float_order_bits_inv(zhi));        // empty: -inf
+        if (out.hits) { out.hits[2 * p] = nfloor; out.hits[2 * p + 1] = nobst; }
+        if (out.state) out.state[p] = st;
+    }
+    nfree = wave_sum(nfree); nocc = wave_sum(nocc); nunk = wave_sum(nunk);
+    if (lane() == 0) { red[0][threadIdx.x >> 6] = nfree; red[1][threadIdx.x >> 6] = nocc; red[2][threadIdx.x >> 6] = nunk; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const unsigned long long sum = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+        if (sum) atomicAdd(&stats[NAV_FREE + threadIdx.x], sum);
+    }
+    if (CARVE) {
+        nseen = wave_sum(nseen); ncarved = wave_sum(ncarved);
+        if (lane() == 0) { red[3][threadIdx.x >> 6] = nseen; red[4][threadIdx.x >> 6] = ncarved; }
+        __syncthreads();
+        if (threadIdx.x >= 3 && threadIdx.x < 5) {
+            const unsigned long long sum = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+            if (sum) atomicAdd(&sn.stats[NC_SEEN + (threadIdx.x - 3)], sum);
+        }
+    }
+}
+
+}  // namespace ssf
+
+#pragma GCC visibility push(hidden)
+// One grid call in four parts, shared by ssf_navgrid_build and ssf_navgrid_carve (`who` words the errors): begin = the refusals, the
+// frame and the kernels' view of the grid; reserve = the working buffers and the staged outputs; accumulate = prep, fill and tile
+// into the accumulators; finish = the cells (carved by `sn` when given), the clearance, the outputs and the stats.
+struct NavCall { const char* who; NavGrid G; float pose[12]; size_t P; unsigned long long total; };
+
+// how finish launches the cells kernel: ssf_navgrid.hip's own, or the carve's with `seen`
+typedef void (*NavCellsLaunch)(hipStream_t st, const ssf::NavGrid& G, const ssf::NavAcc& acc, const ssf::NavOut& out, unsigned long long* stats,
+                               const ssf::NavSeen* sn);
+const char* navgrid_size_res(const ssf_navgrid_params* p);
+int navgrid_begin(ssf_handle* h, const ssf_navgrid_params* p, NavCall& c);
+int navgrid_reserve(ssf_handle* h, const ssf_navgrid_params* p, const NavCall& c, StagedIo& io);
+int navgrid_accumulate(ssf_handle* h, const ssf_navgrid_params* p, NavCall& c);            // (under the caller's TimerScope)
+int navgrid_finish(ssf_handle* h, const ssf_navgrid_params* p, const NavCall& c, ssf::NavOut o, int32_t* d2, const StagedIo& io,
+                   NavCellsLaunch cells, const ssf::NavSeen* sn, ssf_navgrid_stats* stats, unsigned long long* carve_sums = nullptr);
+#pragma GCC visibility pop

@@ -26,8 +26,7 @@
 //            clipped to the indexed cells by a guess that is then VERIFIED with the same monotone functions (else not clipped).
 // Nothing here writes to the handle's stores, counters or scratch: the working set is RaycastWs (ssf_handle.hpp).
 #include "ssf_slots.hpp"
-#include "ssf_handle.hpp"
-#include "../../include/ssf_raycast.h"
+#include "ssf_raycast.hpp"
 
 namespace ssf {
 
@@ -449,6 +448,20 @@ static int raycast_build(ssf_handle* h, float cell, float s, int hash_bits) {
     return SSF_OK;
 }
 
+const char* raycast_params_refusal(const ssf_handle* h, const ssf_raycast_params* p, RaycastResolved& r) {
+    r.tmin = p->t_min; r.tmax = p->t_max;
+    if (r.tmin == 0.0f && r.tmax == 0.0f) { r.tmin = h->cfg.range_min; r.tmax = h->cfg.range_max; }
+    if (!std::isfinite(r.tmin) || !std::isfinite(r.tmax) || !(r.tmin > 0.0f) || !(r.tmax > r.tmin)) return "the range needs 0 < t_min < t_max, both finite";
+    if (std::isnan(p->min_conf)) return "min_conf is a NaN";
+    const float lo = 0.0009765625f, hi = 1024.0f;
+    r.s = p->splat_scale == 0.0f ? 3.0f : p->splat_scale;
+    if (!(r.s >= lo && r.s <= hi)) return "splat_scale must be 0 or in [2^-10, 2^10]";
+    r.cell = p->cell == 0.0f ? 0.125f : p->cell;
+    if (!(r.cell >= lo && r.cell <= hi)) return "cell must be 0 or in [2^-10, 2^10]";
+    if (p->hash_bits != 0 && (p->hash_bits < 4 || p->hash_bits > 24)) return "hash_bits must be 0 or 4..24";
+    return nullptr;
+}
+
 extern "C" {
 int ssf_raycast_default_params(const ssf_handle* h, ssf_raycast_params* p) {
     if (!h || !p) return SSF_ERR_INVALID_ARG;
@@ -463,17 +476,11 @@ int ssf_raycast(ssf_handle* h, const ssf_raycast_params* p, const float* rays, i
     if (n < 0) return refuse("n < 0");
     if (!rays && n > 0) return refuse("rays is NULL");
     if (!t && !index && !point && !normal && !color) return refuse("every output is NULL");
+    RaycastResolved rr;
+    if (const char* what = raycast_params_refusal(h, p, rr)) return refuse(what);
     RayCast q;
-    q.tmin = p->t_min; q.tmax = p->t_max;
-    if (q.tmin == 0.0f && q.tmax == 0.0f) { q.tmin = h->cfg.range_min; q.tmax = h->cfg.range_max; }
-    if (!std::isfinite(q.tmin) || !std::isfinite(q.tmax) || !(q.tmin > 0.0f) || !(q.tmax > q.tmin)) return refuse("the range needs 0 < t_min < t_max, both finite");
-    if (std::isnan(p->min_conf)) return refuse("min_conf is a NaN");
-    const float lo = 0.0009765625f, hi = 1024.0f;
-    const float s = p->splat_scale == 0.0f ? 3.0f : p->splat_scale;
-    if (!(s >= lo && s <= hi)) return refuse("splat_scale must be 0 or in [2^-10, 2^10]");
-    const float cell = p->cell == 0.0f ? 0.125f : p->cell;
-    if (!(cell >= lo && cell <= hi)) return refuse("cell must be 0 or in [2^-10, 2^10]");
-    if (p->hash_bits != 0 && (p->hash_bits < 4 || p->hash_bits > 24)) return refuse("hash_bits must be 0 or 4..24");
+    q.tmin = rr.tmin; q.tmax = rr.tmax;
+    const float s = rr.s, cell = rr.cell;
     { int rc = model_at_rest(h, "ssf_raycast", "casts no rays"); if (rc) return rc; }
     float pose[12];
     if (p->pose) std::memcpy(pose, p->pose, sizeof(pose)); else pose_to12(h->pose, pose);

@@ -199,13 +199,25 @@ def write_local_cloud(fusion, cloud_dir, k, radius):
     return out["stats"]
 
 
-def write_nav_grid(fusion, grid_dir, k, res):
+def thin_views(poses, most=256):
+    """at most `most` of the poses (12 floats each), evenly thinned, the first and the last kept: n x 12 f32"""
+    v = np.asarray(poses, np.float32).reshape(-1, 12)
+    if len(v) > most:
+        v = v[np.round(np.linspace(0, len(v) - 1, most)).astype(np.int64)]
+    return np.ascontiguousarray(v)
+
+
+def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8):
     """the navigation grid of the map, built on the device (include/ssf_navgrid.h) at the default size and frame (floor-aligned
     about the tracked camera) with cells of `res` metres: grid_dir/<k as %06d>.pgm -- the state in map_server's convention (205
     unknown, 254 free, 0 occupied; the image's top row is the grid's last) --, <k>.yaml beside it (map_server's keys; origin = the
     grid's corner along its own x and y axes; grid_to_map = the grid frame's 12 floats) and <k>_dist2.npy (squared clearance in
-    cells)"""
-    out = fusion.nav_grid(outputs=("state", "dist2"), res=res)
+    cells).  carve_views (n x 12 camera poses): the grid is carved along their rays on a pixel lattice of carve_stride
+    (include/ssf_navcarve.h), the files show the carved state, and <k>_seen.npy holds the ray entries per cell"""
+    if carve_views is None:
+        out = fusion.nav_grid(outputs=("state", "dist2"), res=res)
+    else:
+        out = fusion.nav_grid_carve(thin_views(carve_views), outputs=("state", "dist2", "seen"), carve=dict(stride=carve_stride), res=res)
     state, pose = out["state"], out["stats"]["pose"]
     os.makedirs(grid_dir, exist_ok=True)
     name = "%06d" % k
@@ -219,6 +231,8 @@ def write_nav_grid(fusion, grid_dir, k, res):
                 % (name, res, float(R[:, 0] @ t), float(R[:, 1] @ t)))
         f.write("grid_to_map: [%s]\n" % ", ".join("%.9g" % v for v in pose))
     np.save(os.path.join(grid_dir, name + "_dist2.npy"), out["dist2"])
+    if carve_views is not None:
+        np.save(os.path.join(grid_dir, name + "_seen.npy"), out["seen"])
     return out["stats"]
 
 
@@ -255,7 +269,7 @@ def write_laser_scan(fusion, scan_dir, k, beams):
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
            keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30, detect_motion=False,
            motion_mask_dir=None, odometry_prior=False, nav_grid_dir=None, nav_grid_every=30, nav_grid_res=0.05,
-           laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
+           nav_grid_carve=False, nav_grid_carve_stride=8, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
@@ -266,7 +280,9 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     local_cloud_dir: after frames 0, local_cloud_every, 2 local_cloud_every, ... the rows within local_cloud_radius of the tracked
     pose are written (write_local_cloud, numbered by frame); pipelined, submission pauses as for a render.
     nav_grid_dir: after frames 0, nav_grid_every, 2 nav_grid_every, ... the navigation grid of the map with cells of nav_grid_res
-    metres is written (write_nav_grid, numbered by frame); pipelined, submission pauses as for a render.
+    metres is written (write_nav_grid, numbered by frame); pipelined, submission pauses as for a render.  nav_grid_carve: the grid
+    is carved along the rays of the poses estimated so far (thin_views: at most 256 of them) on a pixel lattice of
+    nav_grid_carve_stride, and <k>_seen.npy is written as well.
     laser_scan_dir: after frames 0, laser_scan_every, 2 laser_scan_every, ... a planar scan of laser_scan_beams beams from the tracked
     pose is written (write_laser_scan, numbered by frame); pipelined, submission pauses as for a render.
     keyframes: a dict of ssf_keyframes_params fields ({} = the defaults): the keyframe database is configured and
@@ -279,6 +295,9 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     against the frame before (include/ssf_odometry.h); sequential only, not together with mask_dir; with detect_motion the mask
     is rendered at that prior."""
     lines, results = [], []
+    if nav_grid_carve and not nav_grid_dir:
+        raise ValueError("nav_grid_carve needs nav_grid_dir")
+    carve_views = (lambda: [r["pose"] for r in results]) if nav_grid_carve else (lambda: None)
     if odometry_prior:
         if pipelined:
             raise ValueError("the odometry prior needs sequential processing (the prior of frame k is composed with the pose of frame "
@@ -328,7 +347,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             if local_cloud_dir and (len(lines) - 1) % local_cloud_every == 0:
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
-                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res)
+                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride)
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     else:
@@ -360,7 +379,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             if local_cloud_dir and (len(lines) - 1) % local_cloud_every == 0:
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
-                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res)
+                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride)
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     if out_path:
@@ -493,6 +512,10 @@ def parse_args(argv=None):
                          "(map_server's convention), .yaml and _dist2.npy (squared clearance in cells)")
     ap.add_argument("--nav-grid-every", type=int, default=30, metavar="K")
     ap.add_argument("--nav-grid-res", type=float, default=0.05, metavar="R", help="metres per cell (default 0.05)")
+    ap.add_argument("--nav-grid-carve", action="store_true",
+                    help="with --nav-grid-dir: carve free space along the rays of the poses estimated so far (at most 256, evenly thinned); "
+                         "the files show the carved state, and _seen.npy (ray entries per cell) is written as well")
+    ap.add_argument("--nav-grid-carve-stride", type=int, default=8, metavar="S", help="pixel lattice of the carving rays (default 8)")
     ap.add_argument("--laser-scan-dir", default=None, metavar="DIR",
                     help="every --laser-scan-every frames, a planar laser scan simulated from the map on the device, from the tracked pose: "
                          "DIR/<frame number as %%06d>.npy (ranges in metres, +inf where nothing is hit)")
@@ -515,13 +538,15 @@ def parse_args(argv=None):
         ap.error("--odometry-prior combines with --detect-motion, not with --dynamic-masks")
     if a.motion_mask_dir and not a.detect_motion:
         ap.error("--motion-mask-dir needs --detect-motion")
+    if a.nav_grid_carve and not a.nav_grid_dir:
+        ap.error("--nav-grid-carve needs --nav-grid-dir")
     return a
 
 
 def main():
     a = parse_args()
     from . import binding
-    lib = binding.load_product()
+    lib = binding.load_navcarve() if a.nav_grid_carve else binding.load_product()     # (the carve's entry points: a library of their own)
     cfg = lib.default_config(pipeline_depth=2 if a.pipelined else 0, extract_batch=4 if a.pipelined else 1, **BENCHMARK_LAUNCH)
     f = binding.Fusion(lib, cfg)
     if a.raw_frames:
@@ -533,7 +558,8 @@ def main():
                         local_cloud_radius=a.local_cloud_radius, local_cloud_every=a.local_cloud_every, keyframes={} if a.keyframes else None,
                         keyframe_log=a.keyframe_log, detect_motion=a.detect_motion, motion_mask_dir=a.motion_mask_dir,
                         odometry_prior=a.odometry_prior, nav_grid_dir=a.nav_grid_dir, nav_grid_every=a.nav_grid_every,
-                        nav_grid_res=a.nav_grid_res, laser_scan_dir=a.laser_scan_dir, laser_scan_every=a.laser_scan_every,
+                        nav_grid_res=a.nav_grid_res, nav_grid_carve=a.nav_grid_carve, nav_grid_carve_stride=a.nav_grid_carve_stride,
+                        laser_scan_dir=a.laser_scan_dir, laser_scan_every=a.laser_scan_every,
                         laser_scan_beams=a.laser_scan_beams)
     if a.keyframes and not a.keyframe_log:
         print("\n".join(f.keyframe_lines))
