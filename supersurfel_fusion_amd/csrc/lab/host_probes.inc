@@ -120,6 +120,37 @@ int ssf_dbg_trace_fuse(ssf_handle* h, unsigned long long* out, int cap_wgs, int*
     std::memcpy(out, all.data(), (size_t)m * 24);
     return m;
 }
+// the ticks of the move launches (g_move_trace in ssf_track_fuse.hip; tools/move_probe.py).  on: from now on every workgroup of every
+// k_move_rows launch leaves eight words -- entry | row and state arrived | prefix known | stores issued | terms in the table | fold
+// done | end (100 MHz wall clock; 0: not reached), kind (1 visible, 2 out of view with returning rows, 3 out of view without,
+// 4 nothing moves; + 16 a visible block past the last row; + 256 the fused form) -- and a later launch overwrites an earlier one's.
+// read: the words of the handle's last move launch, returns the workgroups copied.
+static unsigned long long* g_move_trace_words = nullptr;
+int ssf_dbg_move_trace(int on) {
+    const size_t bytes = (size_t)8 * 65536 * sizeof(unsigned long long);
+    if (on && !g_move_trace_words) {
+        if (hipMalloc((void**)&g_move_trace_words, bytes) != hipSuccess) return SSF_ERR_INVALID_ARG;
+        (void)hipMemset(g_move_trace_words, 0, bytes);
+        set_move_trace(g_move_trace_words);
+    } else if (!on && g_move_trace_words) {
+        (void)hipDeviceSynchronize();
+        set_move_trace(nullptr);
+        (void)hipFree(g_move_trace_words);
+        g_move_trace_words = nullptr;
+    }
+    return SSF_OK;
+}
+int ssf_dbg_move_trace_read(ssf_handle* h, unsigned long long* out, int cap_wgs) {
+    if (!h || !out || !g_move_trace_words) return -1;
+    (void)hipStreamSynchronize(h->stream);
+    std::vector<unsigned long long> all((size_t)8 * 65536);
+    (void)hipMemcpy(all.data(), g_move_trace_words, all.size() * 8, hipMemcpyDeviceToHost);
+    int n = 0;
+    for (int i = 0; i < 65536; i++) if (all[8 * (size_t)i]) n = i + 1;
+    const int m = n < cap_wgs ? n : cap_wgs;
+    std::memcpy(out, all.data(), (size_t)m * 64);
+    return m;
+}
 // the relabelling statistics of the frame just processed (FrameMaps::epoch, SSF_PASS_STAT_* in ssf_extract.hip): out64[8 .. 12];
 // collected only after ssf_dbg_pass_stats_enable(1)
 int ssf_dbg_pass_stats_enable(int on) { set_pass_stats(on ? 1 : 0); return SSF_OK; }

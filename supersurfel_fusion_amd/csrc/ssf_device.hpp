@@ -331,6 +331,7 @@ void launch_fuse(hipStream_t st, SurfelSoA model /* visible array */, SurfelSoA 
 void set_pass_stats(int on);         // (lab: the relabelling statistics of ssf_dbg_pass_stats are collected only while set)
 void set_pass_trace(unsigned long long* device_words /* 5 per workgroup of a relabelling pass launch; nullptr: off */);     // (lab: tools/pass_trace.py)
 void set_fuse_trace(unsigned long long* device_words /* 3 per workgroup of the fuse launch; nullptr: off */);      // (lab: tools/fuse_probe.py)
+void set_move_trace(unsigned long long* device_words /* 8 per workgroup of a move launch, 65536 workgroups; nullptr: off */);      // (lab: tools/move_probe.py)
 #endif
 struct MoveTotals { int from_tot, nv /* visible rows before the frame */, head_old, tail_old /* out-of-view span before the frame */; };
 // Multi-GPU migration (ssf_stage_fuse_begin / _end in ssf.h).  launch_fuse(migrate = 1) marks an updated row whose new

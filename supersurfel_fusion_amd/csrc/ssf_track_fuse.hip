@@ -43,25 +43,25 @@ namespace ssf {
 // UNIFORM = false: a row that is no inlier emits nothing (its lane leaves).  UNIFORM = true (the wave-reduction arm): EVERY lane
 // emits all 29 terms, a row that is no inlier as zeros -- emit is then called in uniform control flow, as cross-lane
 // operations need.
+// The terms come in three steps, so that a kernel with other loads to send (k_move_rows) can put them between the two dependent
+// gathers: icp_look -- where the row lands in the frame --, the gathers (pix2[q], then fpack[4 * label] and the word behind it),
+// icp_terms_gathered -- gates and terms from what the gathers brought.  icp_row_terms_ is the three in a row.
+struct IcpLook { V3 ps; int u, v; bool ok; size_t q; };          // ps: the row's position under (R, t); ok: it projects into the image, at pixel q
+__device__ __forceinline__ IcpLook icp_look(const Cam& cam, const V3& ps, bool live) {
+    IcpLook l;
+    l.ps = ps;
+    l.u = pixel_round(ps.x * cam.fx / ps.z + cam.cx);
+    l.v = pixel_round(ps.y * cam.fy / ps.z + cam.cy);
+    l.ok = live && l.u >= 0 && l.u < cam.W && l.v >= 0 && l.v < cam.H;
+    l.q = l.ok ? (size_t)l.v * cam.W + l.u : 0;
+    return l;
+}
 template <bool UNIFORM, typename Emit>
-__device__ __forceinline__ void icp_row_terms_(const Cam& cam, const uint2* __restrict__ pix2, const float4* __restrict__ fpack,
-                                               const M3& R, const V3& t, const V3& mpos, const V3& mlab, const V3& mnrm, int dbg, Emit emit,
-                                               bool live = true) {
-    const V3 ps = add(m3_mulv(R, mpos), t);
-    if (SSF_PROBE(dbg, 1)) { if (ps.z > 1e30f) emit(28, 1ll); return; }
-    const int u = pixel_round(ps.x * cam.fx / ps.z + cam.cx);
-    const int v = pixel_round(ps.y * cam.fy / ps.z + cam.cy);
-    bool ok = live && u >= 0 && u < cam.W && v >= 0 && v < cam.H;
-    if (!UNIFORM && !ok) return;
-    size_t q = ok ? (size_t)v * cam.W + u : 0;
-    if (SSF_PROBE(dbg, 16)) q = (blockIdx.x * blockDim.x + threadIdx.x) & 0x7ffffu;          // probe: the lanes of a wave gather ADJACENT pixels (the first 2^19 of the table)
-    const uint2 pl = pix2[q];                                    // (label, plane depth) of the pixel: one 8-byte gather
-    const int tid = SSF_PROBE(dbg, 8) ? (int)(q & 1023) : (int)pl.x;     // probe (8): the frame supersurfel does not depend on the pixel's word -- two trips instead of three
-    const float zt = __uint_as_float(pl.y);
-    float4 f0 = fpack[4 * tid], f1 = fpack[4 * tid + 1];         // (conf, lab) (normal) of the frame supersurfel: one 32-byte gather
-    // (keeps the gather whole: left alone, the compiler fetches the confidence first, tests it, and only then the
-    // rest -- a second dependent round trip)
-    asm volatile("" : "+v"(f0.y), "+v"(f1.x));
+__device__ __forceinline__ void icp_terms_gathered(const Cam& cam, const M3& R, const IcpLook& l, float zt, const float4& f0, const float4& f1,
+                                                   const V3& mlab, const V3& mnrm, int dbg, Emit emit) {
+    const V3& ps = l.ps;
+    const int u = l.u, v = l.v;
+    bool ok = l.ok;
     ok = ok && (f0.x > 0.0f && zt >= 0.2f && zt <= 5.0f);
     if (!UNIFORM && !ok) return;
     const float dist_color = len3(sub(mlab, v3(f0.y, f0.z, f0.w)));
@@ -90,6 +90,25 @@ __device__ __forceinline__ void icp_row_terms_(const Cam& cam, const uint2* __re
     for (int i = 0; i < 6; i++) emit(21 + i, (long long)fx32r(D1 * X1[i] + D2 * X2[i]));
     emit(27, fx64((double)(UNIFORM && !ok ? 0.0f : dn2 * dn2), 17592186044416.0, 4611686018427387904.0));
     emit(28, (UNIFORM && !ok) ? 0ll : 1ll);
+}
+template <bool UNIFORM, typename Emit>
+__device__ __forceinline__ void icp_row_terms_(const Cam& cam, const uint2* __restrict__ pix2, const float4* __restrict__ fpack,
+                                               const M3& R, const V3& t, const V3& mpos, const V3& mlab, const V3& mnrm, int dbg, Emit emit,
+                                               bool live = true) {
+    const V3 ps = add(m3_mulv(R, mpos), t);
+    if (SSF_PROBE(dbg, 1)) { if (ps.z > 1e30f) emit(28, 1ll); return; }
+    const IcpLook l = icp_look(cam, ps, live);
+    if (!UNIFORM && !l.ok) return;
+    size_t q = l.q;
+    if (SSF_PROBE(dbg, 16)) q = (blockIdx.x * blockDim.x + threadIdx.x) & 0x7ffffu;          // probe: the lanes of a wave gather ADJACENT pixels (the first 2^19 of the table)
+    const uint2 pl = pix2[q];                                    // (label, plane depth) of the pixel: one 8-byte gather
+    const int tid = SSF_PROBE(dbg, 8) ? (int)(q & 1023) : (int)pl.x;     // probe (8): the frame supersurfel does not depend on the pixel's word -- two trips instead of three
+    const float zt = __uint_as_float(pl.y);
+    float4 f0 = fpack[4 * tid], f1 = fpack[4 * tid + 1];         // (conf, lab) (normal) of the frame supersurfel: one 32-byte gather
+    // (keeps the gather whole: left alone, the compiler fetches the confidence first, tests it, and only then the
+    // rest -- a second dependent round trip)
+    asm volatile("" : "+v"(f0.y), "+v"(f1.x));
+    icp_terms_gathered<UNIFORM>(cam, R, l, zt, f0, f1, mlab, mnrm, dbg, emit);
 }
 template <typename Emit>
 __device__ __forceinline__ void icp_row_terms(const Cam& cam, const uint2* __restrict__ pix2, const float4* __restrict__ fpack,
@@ -333,6 +352,17 @@ __device__ __forceinline__ unsigned long long assoc_best(const unsigned long lon
 // understood" -- this is the reason.  Capped at 80 (78 used, 61 vector registers, no scratch): same-box A/B in profiles/track_chain_r05.txt.
 #ifndef SSF_ICP_NUM_SGPR
 #define SSF_ICP_NUM_SGPR 80
+#endif
+// The fuse launch (k_update_insert) and the row move (k_move_rows) took 104-106 left alone: six per compute unit.  The move is capped
+// at 80 (78 used: eight), the fuse launch at 96 (94 used: seven) -- no scratch, the vector registers unchanged (69 and 74); 0 = no
+// cap.  Same-box A/B of each cap at 96 and at 80, alone and together, in profiles/move_icp_fused.txt: the two together pay on the
+// move that sends its gathers beside the prefix (not on the one before it, not one alone); the fuse launch at 80 gains more at the
+// metric's workload and loses at BASELINE config 3.
+#ifndef SSF_FUSE_NUM_SGPR
+#define SSF_FUSE_NUM_SGPR 96
+#endif
+#ifndef SSF_MOVE_NUM_SGPR
+#define SSF_MOVE_NUM_SGPR 80
 #endif
 // Wave 0 of a workgroup (all 64 lanes) waits for the host's word `want` in the line `go`: 0 = leave (told to, or gave up), 1 = iterate,
 // 2 = associate (SSF_ICP_GO_MATCH).  w: this lane's dword of the line as it was when the word was accepted (lanes 0-11 the transform,
@@ -1014,7 +1044,7 @@ __device__ __forceinline__ Counters frame_counters(const Counters& c_in, const u
 __device__ unsigned long long* g_fuse_trace = nullptr;
 void set_fuse_trace(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fuse_trace), &p, sizeof(p)); }
 #endif
-__global__ __launch_bounds__(256) void k_update_insert(SurfelSoA M, SurfelSoA F, Rt pose, int stamp, long long id_offset,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(SSF_FUSE_NUM_SGPR))) void k_update_insert(SurfelSoA M, SurfelSoA F, Rt pose, int stamp, long long id_offset,
                                                        int n_visible, const unsigned long long* __restrict__ best,
                                                        const uint8_t* __restrict__ matched, const int32_t* __restrict__ cand, int S,
                                                        int do_update, int capacity, int rank, int nranks, float tile, Counters* cnt,
@@ -1136,12 +1166,6 @@ __global__ __launch_bounds__(1024) void k_first_frame(SurfelSoA M, SurfelSoA F, 
 }
 
 // ---- stable partition over the model store (see OovStore in ssf_device.hpp; a row in registers: RowRegs, ssf_rows.hpp) ----
-// copy of a row that enters the new visible array; hands back the three fields the ICP terms read
-__device__ __forceinline__ void copy_row_keep(const SurfelSoA& A, size_t i, const SurfelSoA& B, size_t j, V3& pos, V3& lab, V3& nrm) {
-    const RowRegs r = load_row(A, i);
-    pos = r.pos; lab = r.lab; nrm = r.r2;
-    store_row(B, j, r);
-}
 // move the rows whose place changes (stable within each class): A0, C0 -> new visible array, A1 -> in front of the
 // out-of-view span, C1 -> behind it, B0 -> new visible array (slot freed), B2 -> slot freed.  B1 stays where it is.
 // ICP = true: the rows written to the new visible array (A0, B0, C0) are exactly the rows the next frame's first ICP
@@ -1151,13 +1175,26 @@ __device__ __forceinline__ void copy_row_keep(const SurfelSoA& A, size_t i, cons
 // P2P (with ICP): the record is this shard's; the publishing workgroup trades it with the peers as k_icp<true> does.
 // (Measured and removed, round 2: one more workgroup of this launch trading the shard sizes with the peers instead of a launch of
 // its own in front of it -- 7030-7180 against 7260-7320 frames/s with every exchange on one rank, nothing at 2 / 4 ranks.)
+#ifdef SSF_EXPERIMENTS
+__device__ unsigned long long* g_move_trace = nullptr;
+void set_move_trace(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_move_trace), &p, sizeof(p)); }
+#define MOVE_TICK(k) do { if (trace && threadIdx.x == 0) trace[k] = wall_clock64(); } while (0)
+#define MOVE_KIND(k) do { if (trace && threadIdx.x == 0) trace[7] = (unsigned long long)(k) | (ICP ? 0x100ull : 0ull); } while (0)
+#else
+#define MOVE_TICK(k) do { } while (0)
+#define MOVE_KIND(k) do { } while (0)
+#endif
 template <bool ICP, bool P2P>
-__global__ __launch_bounds__(256) void k_move_rows(SurfelSoA V, SurfelSoA Vn, OovStore O, const uint8_t* __restrict__ state_vis,
+__global__ __launch_bounds__(256, 6) __attribute__((amdgpu_num_sgpr(SSF_MOVE_NUM_SGPR))) void k_move_rows(SurfelSoA V, SurfelSoA Vn, OovStore O, const uint8_t* __restrict__ state_vis,
                                                    const uint8_t* __restrict__ state_oov,
                                                    const uint32_t* __restrict__ bc_oov, PartitionWs ws,
                                                    Counters* cnt, int nb_vis, NextIcp nx, Mailbox* mb,
                                                    unsigned long long cnt_seq, P2PView pv, MoveTotals mt) {
     __builtin_amdgcn_s_setprio(3);            // the track chain is the critical path: its waves issue ahead of the extract waves sharing a SIMD
+#ifdef SSF_EXPERIMENTS
+    unsigned long long* const trace = (g_move_trace && blockIdx.x < 65536u) ? g_move_trace + 8 * (size_t)blockIdx.x : nullptr;
+    if (trace && threadIdx.x < 8) trace[threadIdx.x] = threadIdx.x == 0 ? wall_clock64() : 0ull;
+#endif
     // the frame's counters go to the host while the rows move: finalised by the fuse launch (cnt[1]), or -- mt.from_tot, a
     // single shard: the fuse launch ended without its tail -- worked out HERE by block 0 from the class totals (the kernel
     // boundary has completed every atomic of the fuse launch), which also clears the other set of partition sums for the next
@@ -1190,8 +1227,28 @@ __global__ __launch_bounds__(256) void k_move_rows(SurfelSoA V, SurfelSoA Vn, Oo
     if (mt.from_tot && blockIdx.x == 0 && threadIdx.x >= 64 && threadIdx.x < 255)
         for (int i = threadIdx.x - 64; i < ws.words; i += 191) ws.other[i] = 0u;      // the other set: next frame's sums
     // out-of-view blocks: nothing moves in most of them (bc_oov: see classify_oov_block) -- leave at once
-    if ((int)blockIdx.x >= nb_vis && bc_oov[blockIdx.x - nb_vis] == 0u) return;
+    const bool vis = (int)blockIdx.x < nb_vis;
+    const uint32_t bc = vis ? 0u : bc_oov[blockIdx.x - nb_vis];
+    if (!vis && bc == 0u) { MOVE_KIND(4); MOVE_TICK(6); return; }
     // the frozen inputs of the move (Counters::mv_*): from the fuse launch's last block, or from the arguments + the replicas
+    const int mv_nv = mt.from_tot ? mt.nv : cnt->mv_nv, mv_nc = mt.from_tot ? cnt->n_inserted : cnt->mv_nc;
+    const int mv_head_old = mt.from_tot ? mt.head_old : cnt->mv_head_old, mv_tail_old = mt.from_tot ? mt.tail_old : cnt->mv_tail_old;
+    const int nbr = (mv_nv + mv_nc + 255) / 256;                   // the blocks of the visible array that hold rows at all
+    // A workgroup that moves no row into the new visible array has no part in the prefix, the ICP table or the row count, and
+    // leaves before it touches any of them: a visible block past the last row (the grid is sized by the host's upper bound) --
+    // block 0 of a shard stays: it owes the peers the record of an empty shard --, and an out-of-view block whose rows are only
+    // removed (bc: none comes back into view), which frees their slots on its way out.
+    if (vis && (int)blockIdx.x >= nbr && !(P2P && blockIdx.x == 0)) { MOVE_KIND(1 + 16); MOVE_TICK(6); return; }
+    if (!vis && (bc & 0xFFFFu) == 0u) {
+        const long long phys = (long long)mv_head_old + (long long)(blockIdx.x - nb_vis) * blockDim.x + threadIdx.x;
+        if (phys < mv_tail_old) {                  // (both bytes in one round trip)
+            int lv = (int)O.live[phys], st = (int)state_oov[phys];
+            asm volatile("" : "+v"(lv), "+v"(st));
+            if (lv && st == 2) O.live[phys] = 0;
+        }
+        MOVE_KIND(3); MOVE_TICK(6);
+        return;
+    }
     __shared__ uint32_t s_tot[8];
     if (mt.from_tot && threadIdx.x < 8) {
         uint32_t v = 0;
@@ -1199,12 +1256,13 @@ __global__ __launch_bounds__(256) void k_move_rows(SurfelSoA V, SurfelSoA Vn, Oo
         for (int r = 0; r < PART_REPLICAS; r++) v += ws.tot[r * 8 + threadIdx.x];
         s_tot[threadIdx.x] = v;
     }
-    const int mv_nv = mt.from_tot ? mt.nv : cnt->mv_nv, mv_nc = mt.from_tot ? cnt->n_inserted : cnt->mv_nc;
-    const int mv_head_old = mt.from_tot ? mt.head_old : cnt->mv_head_old, mv_tail_old = mt.from_tot ? mt.tail_old : cnt->mv_tail_old;
-    auto mv_a0 = [&]() -> int { return mt.from_tot ? (int)s_tot[0] : cnt->mv_a0; };          // (s_tot: valid behind the next barrier)
-    auto mv_b0 = [&]() -> int { return mt.from_tot ? (int)s_tot[6] : cnt->mv_b0; };
-    auto mv_head_new = [&]() -> int { return mt.from_tot ? mt.head_old - (int)s_tot[1] : cnt->mv_head_new; };
-    auto new_n_visible = [&]() -> int { return mt.from_tot ? (int)(s_tot[0] + s_tot[6] + s_tot[3]) : cnt->n_visible; };
+    // (the fuse launch's own counts are read HERE, whichever form is taken: chosen between at their use, `s_tot[k]` or `cnt->...`
+    // is one load through a generic pointer, which waits for every load in flight -- the ICP gathers among them)
+    const int c_a0 = cnt->mv_a0, c_b0 = cnt->mv_b0, c_head_new = cnt->mv_head_new, c_n_visible = cnt->n_visible;
+    auto mv_a0 = [&]() -> int { const int t = (int)s_tot[0]; return mt.from_tot ? t : c_a0; };          // (s_tot: valid behind the next barrier)
+    auto mv_b0 = [&]() -> int { const int t = (int)s_tot[6]; return mt.from_tot ? t : c_b0; };
+    auto mv_head_new = [&]() -> int { const int t = mt.head_old - (int)s_tot[1]; return mt.from_tot ? t : c_head_new; };
+    auto new_n_visible = [&]() -> int { const int t = (int)(s_tot[0] + s_tot[6] + s_tot[3]); return mt.from_tot ? t : c_n_visible; };
     __shared__ int hist[4][6];
     __shared__ uint32_t base[6];                  // rows of each class in the blocks before this one
     __shared__ unsigned long long red[ICP ? 29 * ICP_SLOTS : 1];
@@ -1212,9 +1270,34 @@ __global__ __launch_bounds__(256) void k_move_rows(SurfelSoA V, SurfelSoA Vn, Oo
     if (threadIdx.x < 6) base[threadIdx.x] = 0u;
     const int wv = threadIdx.x >> 6;
     int cls = 7, in_wave = 0;
-    bool keep = false;
-    V3 pos, lab, nrm;
-    if ((int)blockIdx.x < nb_vis) {
+    bool keep = false;                            // the row goes to the new visible array (and into the next frame's record)
+    // ICP: the two dependent gathers of a row's terms (icp_look / icp_terms_gathered) travel BESIDE the prefix -- the first is sent
+    // as soon as the row's position and class are in registers, together with the prefix loads, the second when the first is back
+    // and before the prefix is summed -- instead of behind the stores: two trips to memory off the workgroup's path.
+    IcpLook lk{};
+    uint2 pl = make_uint2(0u, 0u);
+    float4 f0 = make_float4(0.f, 0.f, 0.f, 0.f), f1 = f0;
+    V3 lab = v3(0.f, 0.f, 0.f), nrm = lab;
+    // (None of the loads sent ahead sits under a condition: the compiler waits for such a load on the spot.  A lane with nothing
+    // to fetch reads word 0 of the table and drops it.)
+    auto icp_look_row = [&](const RowRegs& r) { lab = r.lab; nrm = r.r2; lk = icp_look(nx.cam, add(m3_mulv(nx.T.R, r.pos), nx.T.t), true); };
+    auto icp_first_gather = [&]() { pl = nx.pix2[lk.q]; };
+    auto icp_second_gather = [&]() {
+        asm volatile("" : "+v"(pl.x), "+v"(pl.y));
+        const int tid = lk.ok ? (int)pl.x : 0;
+        f0 = nx.fpack[4 * tid]; f1 = nx.fpack[4 * tid + 1];
+    };
+    // (behind the barriers that order the zeroing of `red`, in front of the stores: behind them, the wait for the second gather
+    // would be a wait for the stores' acknowledgements too -- the counter is one, and the stores sit on diverging paths)
+    auto icp_terms = [&]() {
+        asm volatile("" : "+v"(f0.x), "+v"(f0.y), "+v"(f1.x));
+        if (lk.ok) {
+            const int slot = lane() & (ICP_SLOTS - 1);
+            icp_terms_gathered<false>(nx.cam, nx.T.R, lk, __uint_as_float(pl.y), f0, f1, lab, nrm, 0,
+                                      [&](int k, long long v) { atomicAdd(&red[k * ICP_SLOTS + slot], (unsigned long long)v); });
+        }
+    };
+    if (vis) {
         const int nv = mv_nv, n_rows = nv + mv_nc;                        // mv_nc = rows appended in this frame (insertions + arrivals)
         const int i = blockIdx.x * blockDim.x + threadIdx.x;
         // the row itself is requested now, together with its state byte (not behind it: a row that turns out to be removed is
@@ -1224,46 +1307,51 @@ __global__ __launch_bounds__(256) void k_move_rows(SurfelSoA V, SurfelSoA Vn, Oo
         if (i < n_rows) {
             int st = (int)state_vis[i];
             row = load_row(V, i);
-            asm volatile("" : "+v"(st), "+v"(row.pos.x));
+            asm volatile("" : "+v"(st), "+v"(row.pos.x), "+v"(row.pos.y), "+v"(row.pos.z));
             cls = (i < nv ? 0 : 3) + st;
         }
+        MOVE_KIND(1); MOVE_TICK(1);
+        keep = cls == 0 || cls == 3;
+        if (ICP && keep) icp_look_row(row);
+        if (ICP) icp_first_gather();
         // prefix: the sums of the groups before this block's group (6 counters wide: word w belongs to class w % 6),
-        // then the states of the rows of the earlier blocks of its own group, 16 per load
+        // then the states of the rows of the earlier blocks of its own group, 16 per load.  Each thread's first word of either
+        // is requested here, in front of the barrier, and summed behind it.
         const int g0 = (int)(blockIdx.x / PART_GROUP), ng = 6 * g0;
         const int row0 = g0 * PART_GROUP * 256, n16 = 16 * ((int)blockIdx.x - g0 * PART_GROUP);
+        static_assert(16 * (PART_GROUP - 1) <= 256, "one 16-byte state load per thread covers the earlier blocks of a group");
+        const int r0 = row0 + 16 * (int)threadIdx.x;
+        const bool have_sup = (int)threadIdx.x < ng, have_sv = (int)threadIdx.x < n16 && r0 < n_rows;
+        uint32_t sup = ws.sup_vis[have_sup ? threadIdx.x : 0];
+        uint4 sv = *reinterpret_cast<const uint4*>(state_vis + (have_sv ? r0 : 0));
+        if (ICP) icp_second_gather();
+        asm volatile("" : "+v"(sup), "+v"(sv.x), "+v"(sv.y), "+v"(sv.z), "+v"(sv.w));
+        // the classes that move, counted in two packed words (a0 | a1 << 16, c0 | c1 << 16: a wave's sum stays below 2^16)
+        uint32_t pa = 0u, pc = 0u;
+        if (have_sv) {
+            const uint32_t wd[4] = {sv.x, sv.y, sv.z, sv.w};
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const int rr = r0 + j;
+                const uint32_t stt = (wd[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+                const uint32_t one = stt == 0u ? 1u : (stt == 1u ? 0x10000u : 0u);
+                if (rr < nv) pa += one; else if (rr < n_rows) pc += one;
+            }
+        }
         __syncthreads();
-        for (int w = threadIdx.x; w < ng; w += blockDim.x) {
+        if (have_sup && sup) atomicAdd(&base[threadIdx.x % 6], sup);
+        for (int w = threadIdx.x + blockDim.x; w < ng; w += blockDim.x) {
             const uint32_t v = ws.sup_vis[w];
             if (v) atomicAdd(&base[w % 6], v);
         }
-        uint32_t pa0 = 0, pa1 = 0, pc0 = 0, pc1 = 0;
-        for (int q = threadIdx.x; q < n16; q += blockDim.x) {
-            const int r0 = row0 + 16 * q;
-            if (r0 < n_rows) {
-                const uint4 sv = *reinterpret_cast<const uint4*>(state_vis + r0);
-                const uint32_t wd[4] = {sv.x, sv.y, sv.z, sv.w};
-                uint32_t a0 = 0, a1 = 0, c0 = 0, c1 = 0;         // the classes that move
-#pragma unroll
-                for (int j = 0; j < 16; j++) {
-                    const int rr = r0 + j;
-                    const uint32_t stt = (wd[j >> 2] >> (8 * (j & 3))) & 0xFFu;
-                    const bool in = rr < n_rows, old = rr < nv;
-                    a0 += (in && old && stt == 0u) ? 1u : 0u; a1 += (in && old && stt == 1u) ? 1u : 0u;
-                    c0 += (in && !old && stt == 0u) ? 1u : 0u; c1 += (in && !old && stt == 1u) ? 1u : 0u;
-                }
-                pa0 += a0; pa1 += a1; pc0 += c0; pc1 += c1;
-            }
-        }
         // (one LDS atomic per wave and class: 256 lanes on four addresses would serialise)
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            pa0 += __shfl_xor(pa0, o, 64); pa1 += __shfl_xor(pa1, o, 64); pc0 += __shfl_xor(pc0, o, 64); pc1 += __shfl_xor(pc1, o, 64);
-        }
+        for (int o = 32; o > 0; o >>= 1) { pa += __shfl_xor(pa, o, 64); pc += __shfl_xor(pc, o, 64); }
         if (lane() == 0) {
-            if (pa0) atomicAdd(&base[0], pa0);
-            if (pa1) atomicAdd(&base[1], pa1);
-            if (pc0) atomicAdd(&base[3], pc0);
-            if (pc1) atomicAdd(&base[4], pc1);
+            if (pa & 0xFFFFu) atomicAdd(&base[0], pa & 0xFFFFu);
+            if (pa >> 16) atomicAdd(&base[1], pa >> 16);
+            if (pc & 0xFFFFu) atomicAdd(&base[3], pc & 0xFFFFu);
+            if (pc >> 16) atomicAdd(&base[4], pc >> 16);
         }
 #pragma unroll
         for (int c = 0; c < 6; c++) {
@@ -1272,21 +1360,24 @@ __global__ __launch_bounds__(256) void k_move_rows(SurfelSoA V, SurfelSoA Vn, Oo
             if (lane() == 0) hist[wv][c] = __popcll(mask);
         }
         __syncthreads();
+        MOVE_TICK(2);
+        if (ICP) icp_terms();
         if (cls == 0 || cls == 1 || cls == 3 || cls == 4) {
             int before = 0;
             for (int w = 0; w < wv; w++) before += hist[w][cls];
             const size_t r = (size_t)base[cls] + before + in_wave;
-            if (cls == 0 || cls == 3) {
+            if (keep) {
                 const size_t j = cls == 0 ? r : (size_t)mv_a0() + mv_b0() + r;
                 store_row(Vn, j, row);
-                if (ICP) { pos = row.pos; lab = row.lab; nrm = row.r2; keep = true; }
             } else {
                 const size_t j = (cls == 1 ? (size_t)mv_head_new() : (size_t)mv_tail_old) + r;
                 store_row(O.rows, j, row);
                 O.live[j] = 1;
             }
         }
+        MOVE_TICK(3);
     } else {
+        // an out-of-view block with rows that come back into view (few blocks have any)
         const int ob = blockIdx.x - nb_vis;
         const long long phys = (long long)mv_head_old + (long long)ob * blockDim.x + threadIdx.x;
         if (phys < mv_tail_old) {                  // (both bytes in one round trip)
@@ -1294,29 +1385,46 @@ __global__ __launch_bounds__(256) void k_move_rows(SurfelSoA V, SurfelSoA Vn, Oo
             asm volatile("" : "+v"(lv), "+v"(st));
             if (lv) cls = st;
         }
-        const unsigned long long mask = __ballot(cls == 0);
-        if (cls == 0) in_wave = __popcll(mask & ((1ull << lane()) - 1ull));
-        if (lane() == 0) hist[wv][0] = __popcll(mask);
-        if (__syncthreads_count(cls == 0)) {      // (few blocks have rows that come back into view)
-            const int g0 = ob / PART_GROUP, nw = g0 + (ob - g0 * PART_GROUP);
-            for (int w = threadIdx.x; w < nw; w += blockDim.x) {
-                const uint32_t v = w < g0 ? ws.sup_oov[w] : (bc_oov[g0 * PART_GROUP + (w - g0)] & 0xFFFFu);
-                if (v) atomicAdd(&base[0], v);
+        MOVE_KIND(2); MOVE_TICK(1);
+        // the returning row is requested right behind its state, beside the prefix
+        keep = cls == 0;
+        RowRegs row;
+        if (keep) {
+            row = load_row(O.rows, (size_t)phys);
+            if (ICP) {
+                asm volatile("" : "+v"(row.pos.x), "+v"(row.pos.y), "+v"(row.pos.z));
+                icp_look_row(row);
             }
-            __syncthreads();
         }
-        if (cls == 0) {
+        if (ICP) icp_first_gather();
+        const unsigned long long mask = __ballot(keep);
+        if (keep) in_wave = __popcll(mask & ((1ull << lane()) - 1ull));
+        if (lane() == 0) hist[wv][0] = __popcll(mask);
+        // prefix: returning rows of the groups before this block's group, then of the earlier blocks of its own group
+        const int g0 = ob / PART_GROUP, nw = g0 + (ob - g0 * PART_GROUP);
+        auto returning_before = [&](int w) -> uint32_t { return *(w < g0 ? &ws.sup_oov[w] : &bc_oov[g0 * PART_GROUP + (w - g0)]) & 0xFFFFu; };     // (a group holds 4096 slots: its sum has no high half)
+        const bool have_sup = (int)threadIdx.x < nw;
+        uint32_t sup = returning_before(have_sup ? (int)threadIdx.x : 0);
+        if (ICP) icp_second_gather();
+        asm volatile("" : "+v"(sup));
+        __syncthreads();
+        if (have_sup && sup) atomicAdd(&base[0], sup);
+        for (int w = threadIdx.x + blockDim.x; w < nw; w += blockDim.x) {
+            const uint32_t v = returning_before(w);
+            if (v) atomicAdd(&base[0], v);
+        }
+        __syncthreads();
+        MOVE_TICK(2);
+        if (ICP) icp_terms();
+        if (keep) {
             int before = 0;
             for (int w = 0; w < wv; w++) before += hist[w][0];
-            const size_t j = (size_t)mv_a0() + base[0] + before + in_wave;
-            if (ICP) { copy_row_keep(O.rows, (size_t)phys, Vn, j, pos, lab, nrm); keep = true; }
-            else copy_row(O.rows, (size_t)phys, Vn, j);
+            store_row(Vn, (size_t)mv_a0() + base[0] + before + in_wave, row);
         }
         if (cls == 0 || cls == 2) O.live[phys] = 0;
+        MOVE_TICK(3);
     }
     if (ICP) {
-        // (the barrier after the class histogram also ordered the zeroing of `red`)
-        if (keep) icp_row(nx.cam, nx.pix2, nx.fpack, nx.T.R, nx.T.t, pos, lab, nrm, red, lane() & (ICP_SLOTS - 1), 0);
         // Arrivals are counted in ROWS: the workgroup that completes cnt->n_visible (written by the fuse launch) is
         // the last.  Two levels, as in k_icp (thousands of returning atomics on one word serialise at L2): the
         // blocks of the visible array that hold rows at all (index < nbr) arrive at one of 64 group words packed
@@ -1324,15 +1432,15 @@ __global__ __launch_bounds__(256) void k_move_rows(SurfelSoA V, SurfelSoA Vn, Oo
         // global row counter.  The few out-of-view blocks with rows that come back into view go there directly.
         // No rows at all: no record is published, and the host does not ask for one (ICP needs visible rows).
         const int nkeep = __syncthreads_count(keep);
+        MOVE_TICK(4);
         if (P2P && new_n_visible() == 0) {         // an empty shard still owes its peers a (zero) record
             if (blockIdx.x == 0) icp_publish<true>(nx.replicas, nx.sums, nx.mb, nx.seq, pv, pv.seq);
             return;
         }
-        const bool vis = (int)blockIdx.x < nb_vis;
-        const int nbr = (mv_nv + mv_nc + 255) / 256;
-        if (vis ? (int)blockIdx.x >= nbr : nkeep == 0) return;
+        if (vis ? (int)blockIdx.x >= nbr : nkeep == 0) { MOVE_TICK(6); return; }
         __shared__ int s_last;
         icp_fold(red, nx.replicas);
+        MOVE_TICK(5);
         if (threadIdx.x == 0) {
             SSF_ARRIVE_RELEASE();
             unsigned int rows = (unsigned int)nkeep;
@@ -1361,6 +1469,7 @@ __global__ __launch_bounds__(256) void k_move_rows(SurfelSoA V, SurfelSoA Vn, Oo
         __syncthreads();
         if (s_last) icp_publish<P2P>(nx.replicas, nx.sums, nx.mb, nx.seq, pv, pv.seq);
     }
+    MOVE_TICK(6);
 }
 
 // ---- multi-GPU migration: rows that crossed a tile edge move to the rank that owns their new tile -----------------
