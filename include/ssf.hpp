@@ -26,6 +26,7 @@
 #include "ssf_query.h"
 #include "ssf_navgrid.h"
 #include "ssf_navcarve.h"
+#include "ssf_navplan.h"
 #include "ssf_raycast.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
@@ -273,6 +274,29 @@ struct CarveParams {
 struct CarvedNavGrid : NavGrid {
     std::vector<uint32_t> seen;
     ssf_navcarve_stats carve;
+};
+
+/* planOnGrid (ssf_navplan.h; exported by libssf_hip_nav.so, linked INSTEAD of libssf_hip.so or libssf_hip_navcarve.so -- a program
+ * that does not call it links as before: the inline member leaves no reference behind): the cost-to-goal field of a grid and the
+ * cell paths down it.  The members start at ssf_navplan_default_params' values. */
+struct PlanParams {
+    int min_dist2 = 0;                             /* the robot's squared radius in cells */
+    int soft_dist2 = 0, near_penalty = 0;          /* extra cost below a squared clearance; 0 = none */
+    bool allow_unknown = false, goals_from_frontier = false;
+    int max_path = 0;                              /* cells per path; 0 = no paths */
+    bool want_cost = true, want_frontier = true;   /* false: not produced (its vector stays empty) */
+};
+typedef std::array<int32_t, 2> GridCell;           /* (ix, iy) */
+/* what planOnGrid makes: the field and the frontier, row-major height x width; per start its cost, status (ssf_navplan.h step 7)
+ * and the cells of its path */
+struct NavPlan {
+    int width = 0, height = 0;
+    std::vector<uint32_t> cost;                    /* 0xFFFFFFFF = not reached */
+    std::vector<uint8_t> frontier;
+    std::vector<uint32_t> start_cost;
+    std::vector<int32_t> start_status;
+    std::vector<std::vector<GridCell> > paths;
+    ssf_navplan_stats stats;
 };
 
 /* castRays (ssf_raycast.h; exported by libssf_hip.so only): the first disc of the map that each ray hits.  The members start at
@@ -713,6 +737,50 @@ public:
         else if (m11 > m22) { const double s = 2.0 * std::sqrt(1.0 + m11 - m00 - m22); qw = (m02 - m20) / s; qx = (m01 + m10) / s; qy = 0.25 * s; qz = (m12 + m21) / s; }
         else { const double s = 2.0 * std::sqrt(1.0 + m22 - m00 - m11); qw = (m10 - m01) / s; qx = (m02 + m20) / s; qy = (m12 + m21) / s; qz = 0.25 * s; }
         msg.info.origin.orientation.x = qx; msg.info.origin.orientation.y = qy; msg.info.origin.orientation.z = qz; msg.info.origin.orientation.w = qw;
+    }
+    /* Plan on a grid that buildNavGrid made (ssf_navplan.h), plain or carved: the cost-to-goal field over the cells a robot of
+     * squared radius q.min_dist2 can be in, for `goals` (and, with goals_from_frontier, the grid's frontier), and for every start
+     * its cost, status and path.  The grid needs its state and dist2 (want_state, want_dist2). */
+    void planOnGrid(const NavGrid& g, const PlanParams& q, const std::vector<GridCell>& goals, const std::vector<GridCell>& starts, NavPlan& out) {
+        const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
+        if (n == 0 || g.state.size() != n || g.dist2.size() != n) throw std::logic_error("planOnGrid: the grid has no state or no dist2 (want_state, want_dist2)");
+        ssf_navplan_params p;
+        check(ssf_navplan_default_params(need(), &p));
+        p.width = g.width; p.height = g.height; p.min_dist2 = q.min_dist2; p.soft_dist2 = q.soft_dist2; p.near_penalty = q.near_penalty;
+        p.allow_unknown = q.allow_unknown ? 1 : 0; p.goals_from_frontier = q.goals_from_frontier ? 1 : 0; p.max_path = q.max_path; p.on_device = 0;
+        p.goals = goals.empty() ? nullptr : goals[0].data(); p.n_goals = (int)goals.size();
+        p.starts = starts.empty() ? nullptr : starts[0].data(); p.n_starts = (int)starts.size();
+        const size_t ns = starts.size(), mp = q.max_path > 0 ? (size_t)q.max_path : 0;
+        out.width = g.width; out.height = g.height;
+        out.cost.resize(q.want_cost ? n : 0); out.frontier.resize(q.want_frontier ? n : 0);
+        out.start_cost.assign(ns, SSF_NAVPLAN_UNREACHED); out.start_status.assign(ns, 0);
+        std::vector<int32_t> len(ns, 0), cells(ns * mp * 2);
+        ssf_navplan_out o;
+        o.cost = q.want_cost ? out.cost.data() : nullptr; o.frontier = q.want_frontier ? out.frontier.data() : nullptr;
+        o.start_cost = ns ? out.start_cost.data() : nullptr; o.start_status = ns ? out.start_status.data() : nullptr;
+        o.path_len = ns ? len.data() : nullptr; o.path = cells.empty() ? nullptr : cells.data();
+        check(ssf_navplan_field(need(), &p, g.state.data(), g.dist2.data(), &o, &out.stats));
+        out.paths.assign(ns, std::vector<GridCell>());
+        for (size_t i = 0; i < ns && mp; i++) {
+            out.paths[i].resize((size_t)len[i]);
+            for (size_t k = 0; k < (size_t)len[i]; k++) { out.paths[i][k][0] = cells[(i * mp + k) * 2]; out.paths[i][k][1] = cells[(i * mp + k) * 2 + 1]; }
+        }
+    }
+    /* The poses of a nav_msgs::Path from the path of start `start`: the centre of every cell, ((ix + 0.5) res, (iy + 0.5) res, 0) in
+     * the grid frame, taken to the map frame by pose12 (grid-to-map, R row-major then t: NavGrid::stats.pose); the orientation is
+     * the identity.  header and the poses' headers are the node's.  Any message type with poses[i].pose works (tests use a double). */
+    template <typename PathT> static void fillPath(const NavPlan& plan, size_t start, const float pose12[12], float res, PathT& msg) {
+        if (start >= plan.paths.size()) throw std::logic_error("fillPath: no such start");
+        const std::vector<GridCell>& cells = plan.paths[start];
+        msg.poses.resize(cells.size());
+        for (size_t i = 0; i < cells.size(); i++) {
+            const double x = ((double)cells[i][0] + 0.5) * (double)res, y = ((double)cells[i][1] + 0.5) * (double)res;
+            msg.poses[i].pose.position.x = (double)pose12[0] * x + (double)pose12[1] * y + (double)pose12[9];
+            msg.poses[i].pose.position.y = (double)pose12[3] * x + (double)pose12[4] * y + (double)pose12[10];
+            msg.poses[i].pose.position.z = (double)pose12[6] * x + (double)pose12[7] * y + (double)pose12[11];
+            msg.poses[i].pose.orientation.x = 0.0; msg.poses[i].pose.orientation.y = 0.0; msg.poses[i].pose.orientation.z = 0.0;
+            msg.poses[i].pose.orientation.w = 1.0;
+        }
     }
     /* Rays cast through the map on the device (ssf_raycast.h): rays6 holds n rays of six floats (origin, direction) in the frame of
      * r.pose.  The library keeps a spatial index of the map between calls and rebuilds it when the map has changed.  INTEGRATION.md

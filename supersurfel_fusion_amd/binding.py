@@ -17,6 +17,9 @@ PRODUCT_LIB = os.path.join(_HERE, "csrc", "libssf_hip.so")
 # the product's objects plus the carve of the navigation grid (include/ssf_navcarve.h; csrc/Makefile): everything the product exports,
 # and the carve's entry points, which the product library does not export
 NAVCARVE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_navcarve.so")
+# the product's objects, the carve and the plan on the navigation grid (include/ssf_navplan.h): the one library of a robot that
+# builds, carves and plans.  Neither of the two libraries above exports the plan's entry points
+NAV_LIB = os.path.join(_HERE, "csrc", "libssf_hip_nav.so")
 
 
 class SsfConfig(C.Structure):
@@ -112,6 +115,10 @@ NAVGRID_OUTPUT_NAMES = tuple(nm for nm, _, _ in NAVGRID_OUTPUTS)
 NAVCARVE_SYMBOLS = ["ssf_navcarve_default_params", "ssf_navgrid_carve", "ssf_debug_navcarve_set_chunk_rays", "ssf_debug_navcarve_last"]
 NAVCARVE_OUTPUTS = NAVGRID_OUTPUTS + (("seen", np.uint32, ()),)
 NAVCARVE_OUTPUT_NAMES = tuple(nm for nm, _, _ in NAVCARVE_OUTPUTS)
+# the plan on the navigation grid (include/ssf_navplan.h): exported by libssf_hip_nav.so only (load_nav), not part of ssf.h
+NAVPLAN_SYMBOLS = ["ssf_navplan_default_params", "ssf_navplan_field", "ssf_debug_navplan_set_round_batch", "ssf_debug_navplan_last"]
+NAVPLAN_OUTPUT_NAMES = ("cost", "frontier", "start_cost", "start_status", "path_len", "path")
+NAVPLAN_UNREACHED = 0xFFFFFFFF
 # rays cast through the model (include/ssf_raycast.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 RAYCAST_SYMBOLS = ["ssf_raycast_default_params", "ssf_raycast"]
 # the output arrays of ssf_raycast, in its argument order: name, dtype, per-ray shape
@@ -259,6 +266,27 @@ class SsfNavCarveStats(C.Structure):
         d = self.grid.as_dict()
         d.update({nm: int(getattr(self, nm)) for nm, _ in self._fields_ if nm != "grid"})
         return d
+
+
+class SsfNavPlanParams(C.Structure):
+    """ssf_navplan_params (include/ssf_navplan.h)"""
+    _fields_ = [(nm, C.c_int) for nm in ("width", "height", "min_dist2", "soft_dist2", "near_penalty", "allow_unknown")] + \
+               [("goals", C.c_void_p), ("n_goals", C.c_int), ("goals_from_frontier", C.c_int), ("starts", C.c_void_p), ("n_starts", C.c_int),
+                ("max_path", C.c_int), ("on_device", C.c_int)]
+
+
+class SsfNavPlanOut(C.Structure):
+    """ssf_navplan_out (include/ssf_navplan.h)"""
+    _fields_ = [(nm, C.c_void_p) for nm in NAVPLAN_OUTPUT_NAMES]
+
+
+class SsfNavPlanStats(C.Structure):
+    """ssf_navplan_stats (include/ssf_navplan.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("cells_traversable", "cells_reached", "frontier_cells", "frontier_goals", "goals_used", "goals_blocked",
+                                           "goals_outside", "max_cost", "rounds", "tile_visits")]
+
+    def as_dict(self):
+        return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
 
 
 class SsfRaycastParams(C.Structure):
@@ -432,6 +460,12 @@ class Library:
                                             C.POINTER(SsfNavCarveStats)]
             L.ssf_debug_navcarve_set_chunk_rays.argtypes = [vp, C.c_int]
             L.ssf_debug_navcarve_last.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        self.has_navplan = all(hasattr(L, nm) for nm in NAVPLAN_SYMBOLS)
+        if self.has_navplan:
+            L.ssf_navplan_default_params.argtypes = [vp, C.POINTER(SsfNavPlanParams)]
+            L.ssf_navplan_field.argtypes = [vp, C.POINTER(SsfNavPlanParams), vp, vp, C.POINTER(SsfNavPlanOut), C.POINTER(SsfNavPlanStats)]
+            L.ssf_debug_navplan_set_round_batch.argtypes = [vp, C.c_int]
+            L.ssf_debug_navplan_last.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
         if self.has_navgrid:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
@@ -530,6 +564,14 @@ def load_navcarve():
     loudly when it has not been built."""
     import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
     return Library(NAVCARVE_LIB)
+
+
+def load_nav():
+    """Load libssf_hip_nav.so: the product's objects with the carve and the plan on the navigation grid linked in
+    (include/ssf_navcarve.h, include/ssf_navplan.h).  A handle belongs to the library that created it: create the Fusion from THIS
+    library to call nav_plan on it.  Fails loudly when it has not been built."""
+    import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
+    return Library(NAV_LIB)
 
 
 def load_lab():
@@ -1255,6 +1297,137 @@ class Fusion:
         a, b = C.c_int64(0), C.c_int64(0)
         self._ck(self.L.lib.ssf_debug_navcarve_last(self.h, C.byref(a), C.byref(b)), "ssf_debug_navcarve_last")
         return dict(chunks=int(a.value), atomics=int(b.value))
+
+    # ---- plan on the navigation grid: cost-to-goal field and paths (include/ssf_navplan.h) ------------
+    def _need_navplan(self, symbol):
+        if not self.L.has_navplan:
+            raise SsfError("%s does not export %s: it plans on no navigation grid (include/ssf_navplan.h: libssf_hip_nav.so, binding.load_nav)"
+                           % (self.L.path, symbol))
+
+    @staticmethod
+    def _cell_list(cells, what):
+        """n x 2 int32 (ix, iy), contiguous; None or empty: no cells"""
+        if cells is None or np.size(cells) == 0:
+            return np.zeros((0, 2), np.int32)
+        a = np.asarray(cells)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise SsfError("%s are n x 2 cells (ix, iy), got shape %s" % (what, a.shape))
+        return np.ascontiguousarray(a, np.int32)
+
+    def _navplan_params(self, on_device, width, height, goals, starts, params):
+        """(SsfNavPlanParams, the goal and start arrays it points into).  goals, starts: n x 2 cells (ix, iy), host memory; params:
+        the other fields of ssf_navplan_params by name, each at ssf_navplan_default_params' value when missing."""
+        p = SsfNavPlanParams()
+        self._ck(self.L.lib.ssf_navplan_default_params(self.h, C.byref(p)), "ssf_navplan_default_params")
+        g, s = self._cell_list(goals, "goals"), self._cell_list(starts, "starts")
+        kinds = dict(p._fields_)
+        for nm, val in params.items():
+            if nm not in kinds or nm in ("width", "height", "goals", "n_goals", "starts", "n_starts", "on_device"):
+                raise SsfError("unknown plan parameter %r" % nm)
+            setattr(p, nm, int(val))
+        p.width, p.height, p.on_device = int(width), int(height), int(bool(on_device))
+        p.goals, p.n_goals = (g.ctypes.data if len(g) else None), len(g)
+        p.starts, p.n_starts = (s.ctypes.data if len(s) else None), len(s)
+        return p, (g, s)
+
+    def _navplan_field(self, p, state, dist2, ptrs):
+        st = SsfNavPlanStats()
+        out = SsfNavPlanOut(*[ptrs.get(nm) for nm in NAVPLAN_OUTPUT_NAMES])
+        self._ck(self.L.lib.ssf_navplan_field(self.h, C.byref(p), state, dist2, C.byref(out), C.byref(st)), "ssf_navplan_field")
+        return st.as_dict()
+
+    def nav_plan(self, state, dist2, goals=None, starts=None, outputs=NAVPLAN_OUTPUT_NAMES, **params):
+        """The cost-to-goal field of a navigation grid and the paths down it (ssf_navplan_field).  state H x W int8 and dist2
+        H x W int32 as nav_grid / nav_grid_carve return them; goals, starts: n x 2 cells (ix, iy).  Returns a dict of the requested
+        outputs -- cost H x W u32 (0xFFFFFFFF: not reached), frontier H x W u8, start_cost (n u32), start_status (n i32), path_len
+        (n i32), path: a list with one (len, 2) int32 array per start -- and 'stats'.  params: min_dist2, soft_dist2, near_penalty,
+        allow_unknown, goals_from_frontier, max_path."""
+        self._need_navplan("ssf_navplan_field")
+        bad = [nm for nm in outputs if nm not in NAVPLAN_OUTPUT_NAMES]
+        if bad:
+            raise SsfError("unknown plan outputs %s (known: %s)" % (bad, ", ".join(NAVPLAN_OUTPUT_NAMES)))
+        state, dist2 = np.ascontiguousarray(state, np.int8), np.ascontiguousarray(dist2, np.int32)
+        if state.ndim != 2 or dist2.shape != state.shape:
+            raise SsfError("state and dist2 are H x W arrays of one shape, got %s and %s" % (state.shape, dist2.shape))
+        H, W = state.shape
+        p, keep = self._navplan_params(False, W, H, goals, starts, params)
+        n, mp = p.n_starts, max(p.max_path, 0)
+        shapes = dict(cost=((H, W), np.uint32), frontier=((H, W), np.uint8), start_cost=((n,), np.uint32), start_status=((n,), np.int32),
+                      path_len=((n,), np.int32), path=((n, min(mp, 1 << 20), 2), np.int32))
+        want = set(outputs)
+        if "path" in want:
+            want.add("path_len")                     # (the lengths cut the paths)
+        out = {nm: np.zeros(*shapes[nm]) for nm in NAVPLAN_OUTPUT_NAMES if nm in want}
+        stats = self._navplan_field(p, _ptr(state), _ptr(dist2), {nm: _ptr(a) for nm, a in out.items()})
+        if "path" in out:
+            out["path"] = [out["path"][i, :out["path_len"][i]].copy() for i in range(n)]
+        if "path_len" not in outputs:
+            out.pop("path_len", None)
+        out["stats"] = stats
+        return out
+
+    def nav_plan_device(self, state, dist2, width, height, goals=None, starts=None, cost=None, frontier=None, start_cost=None, start_status=None,
+                        path_len=None, path=None, **params):
+        """ssf_navplan_field on device memory: state, dist2 and each output are a contiguous torch tensor on the device or the device
+        address (int) of a buffer of the shape and dtype nav_plan works on (path: n_starts x max_path x 2 int32; outputs may be
+        None); goals and starts stay host memory.  Returns the stats dict."""
+        self._need_navplan("ssf_navplan_field")
+        p, keep = self._navplan_params(True, width, height, goals, starts, params)
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        return self._navplan_field(p, addr(state), addr(dist2), dict(cost=addr(cost), frontier=addr(frontier), start_cost=addr(start_cost),
+                                                                     start_status=addr(start_status), path_len=addr(path_len), path=addr(path)))
+
+    def nav_plan_default_params(self):
+        """ssf_navplan_default_params as a dict"""
+        self._need_navplan("ssf_navplan_default_params")
+        p = SsfNavPlanParams()
+        self._ck(self.L.lib.ssf_navplan_default_params(self.h, C.byref(p)), "ssf_navplan_default_params")
+        return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm not in ("goals", "starts")}
+
+    def nav_plan_from_map(self, views, goals=None, starts=None, grid=None, carve=None, plan=None, outputs=NAVPLAN_OUTPUT_NAMES):
+        """Carve the navigation grid of the map along `views` (nav_grid_carve_device) into device tensors and plan on them
+        (nav_plan_device) without the grid leaving the device.  grid: nav_grid's keywords; carve: the carve's parameters; plan: the
+        plan's.  Returns nav_plan's dict, with 'grid_stats' (the carve's) beside 'stats'."""
+        import torch
+        self._need_navplan("ssf_navplan_field")
+        self._need_navcarve("ssf_navgrid_carve")
+        grid, plan = dict(grid or {}), dict(plan or {})
+        gp, _ = self._navgrid_params(True, **grid)
+        W, H = gp.width, gp.height
+        if not (1 <= W <= 4096 and 1 <= H <= 4096):
+            raise SsfError("the grid's size must be 1..4096 x 1..4096")
+        dev = torch.device("cuda")
+        state, dist2 = torch.empty((H, W), dtype=torch.int8, device=dev), torch.empty((H, W), dtype=torch.int32, device=dev)
+        grid_stats = self.nav_grid_carve_device(views, state=state, dist2=dist2, carve=carve, **grid)
+        g, s = self._cell_list(goals, "goals"), self._cell_list(starts, "starts")
+        n, mp = len(s), int(plan.get("max_path", 0))
+        kinds = dict(cost=((H, W), torch.int32), frontier=((H, W), torch.uint8), start_cost=((n,), torch.int32), start_status=((n,), torch.int32),
+                     path_len=((n,), torch.int32), path=((n, max(min(mp, 1 << 20), 0), 2), torch.int32))
+        want = set(outputs) | ({"path_len"} if "path" in outputs else set())
+        t = {nm: torch.zeros(kinds[nm][0], dtype=kinds[nm][1], device=dev) for nm in NAVPLAN_OUTPUT_NAMES if nm in want}
+        stats = self.nav_plan_device(state, dist2, W, H, g, s, **dict(t, **plan))
+        out = {nm: a.cpu().numpy() for nm, a in t.items()}
+        for nm in ("cost", "start_cost"):
+            if nm in out:
+                out[nm] = out[nm].view(np.uint32)
+        if "path" in out:
+            out["path"] = [out["path"][i, :out["path_len"][i]].copy() for i in range(n)]
+        if "path_len" not in outputs:
+            out.pop("path_len", None)
+        out["stats"], out["grid_stats"] = stats, grid_stats
+        return out
+
+    def debug_navplan_set_round_batch(self, rounds):
+        """test hook: the relaxation rounds per look at the flagged-tile count (0 = the default); results never depend on it"""
+        self._need_navplan("ssf_debug_navplan_set_round_batch")
+        self._ck(self.L.lib.ssf_debug_navplan_set_round_batch(self.h, int(rounds)), "ssf_debug_navplan_set_round_batch")
+
+    def debug_navplan_last(self):
+        """dict(rounds, tile_visits) of the last nav_plan of this handle"""
+        self._need_navplan("ssf_debug_navplan_last")
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.lib.ssf_debug_navplan_last(self.h, C.byref(a), C.byref(b)), "ssf_debug_navplan_last")
+        return dict(rounds=int(a.value), tile_visits=int(b.value))
 
     # ---- rays cast through the model: the first disc each ray hits (include/ssf_raycast.h) ------------
     def _need_raycast(self, symbol):

@@ -339,6 +339,20 @@ struct NavCarveWs {
     uint32_t* seen = nullptr; size_t cells = 0;
     int chunk_rays = 0; long long last_chunks = 0, last_atomics = 0;
 };
+// ssf_navplan_field (ssf_navplan.h, ssf_navplan.hip: linked into libssf_hip_nav.so only): per cell the grid as the call got it (state,
+// dist2: the copy of host arrays), the packed (traversable, penalty) word, the cost and the frontier; per 32 x 32-cell tile the two
+// ping-pong flag words; the goals (65536 pairs) and starts (4096 pairs) with the starts' results; the paths of a call with host
+// outputs; the sums.  Allocated on first use; each group is grown as a whole or not at all (DevBufs::grow).  round_batch: the test
+// hook (0 = the default); last_*: what the last call did.  Nothing here is read or written by the frame path.
+struct NavPlanWs {
+    DevBufs bufs;
+    int8_t* state = nullptr; int32_t* dist2 = nullptr; uint32_t* pk = nullptr; uint32_t* cost = nullptr; uint8_t* frontier = nullptr; size_t cells = 0;
+    uint32_t* flags = nullptr; size_t tiles = 0;
+    int32_t* goals = nullptr; int32_t* starts = nullptr; uint32_t* start_cost = nullptr; int32_t* start_status = nullptr; int32_t* path_len = nullptr;
+    unsigned long long* stats = nullptr;
+    int32_t* path = nullptr; size_t path_words = 0;
+    int round_batch = 0; long long last_rounds = 0, last_visits = 0;
+};
 // ssf_raycast (ssf_raycast.h): the resident index -- per slot the 64-byte record and the box of cells with the row's class, the
 // out-of-view blocks' live offsets, the oversize list; per bucket (+ 1) the list offsets and the fill's cursors; the (bucket -> slot)
 // lists; the sums and the box of indexed cells -- and the staging buffer of a call's host rays and outputs.  The index is valid
@@ -465,6 +479,7 @@ struct ssf_handle {
     OdoWs odo;                                    // ssf_odometry_* (ssf_odometry.h)
     NavGridWs navgrid;                            // ssf_navgrid_build (ssf_navgrid.h)
     NavCarveWs navcarve;                          // ssf_navgrid_carve (ssf_navcarve.h)
+    NavPlanWs navplan;                            // ssf_navplan_field (ssf_navplan.h)
     RaycastWs raycast;                            // ssf_raycast (ssf_raycast.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense); the out-of-view
                                                   // compaction keeps rows and order but moves slots: who keeps slot numbers also watches n_recentres (RaycastWs)

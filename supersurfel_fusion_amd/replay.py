@@ -207,13 +207,26 @@ def thin_views(poses, most=256):
     return np.ascontiguousarray(v)
 
 
-def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8):
+def plan_cells(pose, res, cam_t, goals_m):
+    """the camera's cell (the plan's start) and the goals' cells: cam_t is the camera position in the map frame, goals_m are
+    (X, Y) in metres in the grid frame whose 12 floats are `pose`; cell = floor(metres / res)"""
+    R, t = np.asarray(pose[:9], np.float64).reshape(3, 3), np.asarray(pose[9:], np.float64)
+    c = R.T @ (np.asarray(cam_t, np.float64) - t)
+    start = np.floor(c[:2] / res).astype(np.int32).reshape(1, 2)
+    goals = np.floor(np.asarray(goals_m, np.float64).reshape(-1, 2) / res).astype(np.int32)
+    return start, goals
+
+
+def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, plan=None):
     """the navigation grid of the map, built on the device (include/ssf_navgrid.h) at the default size and frame (floor-aligned
     about the tracked camera) with cells of `res` metres: grid_dir/<k as %06d>.pgm -- the state in map_server's convention (205
     unknown, 254 free, 0 occupied; the image's top row is the grid's last) --, <k>.yaml beside it (map_server's keys; origin = the
     grid's corner along its own x and y axes; grid_to_map = the grid frame's 12 floats) and <k>_dist2.npy (squared clearance in
     cells).  carve_views (n x 12 camera poses): the grid is carved along their rays on a pixel lattice of carve_stride
-    (include/ssf_navcarve.h), the files show the carved state, and <k>_seen.npy holds the ray entries per cell"""
+    (include/ssf_navcarve.h), the files show the carved state, and <k>_seen.npy holds the ray entries per cell.
+    plan (dict(goals=(X, Y) pairs in metres in the grid frame, frontier=bool, radius=metres)): the cost-to-goal field of that grid
+    for a robot of that radius, from the camera's cell (include/ssf_navplan.h): <k>_cost.npy (u32, 0xFFFFFFFF = not reached),
+    <k>_path.npy (the cells (ix, iy) from the camera's cell to the goal) and <k>_plan.json (the stats, the start and its status)"""
     if carve_views is None:
         out = fusion.nav_grid(outputs=("state", "dist2"), res=res)
     else:
@@ -233,6 +246,17 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8):
     np.save(os.path.join(grid_dir, name + "_dist2.npy"), out["dist2"])
     if carve_views is not None:
         np.save(os.path.join(grid_dir, name + "_seen.npy"), out["seen"])
+    if plan is not None:
+        import json
+        start, goals = plan_cells(pose, res, fusion.get_pose()[9:12], plan.get("goals") or [])
+        cells = int(np.ceil(float(plan.get("radius") or 0.0) / res))
+        got = fusion.nav_plan(state, out["dist2"], goals, start, outputs=("cost", "start_cost", "start_status", "path"),
+                              goals_from_frontier=bool(plan.get("frontier")), min_dist2=cells * cells, max_path=4 * sum(state.shape))
+        np.save(os.path.join(grid_dir, name + "_cost.npy"), got["cost"])
+        np.save(os.path.join(grid_dir, name + "_path.npy"), got["path"][0])
+        with open(os.path.join(grid_dir, name + "_plan.json"), "w") as f:
+            json.dump(dict(got["stats"], start=[int(v) for v in start[0]], start_status=int(got["start_status"][0]),
+                           start_cost=int(got["start_cost"][0]), min_dist2=cells * cells), f, sort_keys=True)
     return out["stats"]
 
 
@@ -269,7 +293,7 @@ def write_laser_scan(fusion, scan_dir, k, beams):
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
            keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30, detect_motion=False,
            motion_mask_dir=None, odometry_prior=False, nav_grid_dir=None, nav_grid_every=30, nav_grid_res=0.05,
-           nav_grid_carve=False, nav_grid_carve_stride=8, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
+           nav_grid_carve=False, nav_grid_carve_stride=8, nav_plan=None, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
@@ -282,7 +306,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     nav_grid_dir: after frames 0, nav_grid_every, 2 nav_grid_every, ... the navigation grid of the map with cells of nav_grid_res
     metres is written (write_nav_grid, numbered by frame); pipelined, submission pauses as for a render.  nav_grid_carve: the grid
     is carved along the rays of the poses estimated so far (thin_views: at most 256 of them) on a pixel lattice of
-    nav_grid_carve_stride, and <k>_seen.npy is written as well.
+    nav_grid_carve_stride, and <k>_seen.npy is written as well.  nav_plan (write_nav_grid's plan): the field, path and stats of a
+    plan from the camera's cell are written next to each grid.
     laser_scan_dir: after frames 0, laser_scan_every, 2 laser_scan_every, ... a planar scan of laser_scan_beams beams from the tracked
     pose is written (write_laser_scan, numbered by frame); pipelined, submission pauses as for a render.
     keyframes: a dict of ssf_keyframes_params fields ({} = the defaults): the keyframe database is configured and
@@ -297,6 +322,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     lines, results = [], []
     if nav_grid_carve and not nav_grid_dir:
         raise ValueError("nav_grid_carve needs nav_grid_dir")
+    if nav_plan is not None and not nav_grid_dir:
+        raise ValueError("nav_plan needs nav_grid_dir")
     carve_views = (lambda: [r["pose"] for r in results]) if nav_grid_carve else (lambda: None)
     if odometry_prior:
         if pipelined:
@@ -347,7 +374,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             if local_cloud_dir and (len(lines) - 1) % local_cloud_every == 0:
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
-                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride)
+                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan)
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     else:
@@ -379,7 +406,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             if local_cloud_dir and (len(lines) - 1) % local_cloud_every == 0:
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
-                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride)
+                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan)
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     if out_path:
@@ -516,6 +543,12 @@ def parse_args(argv=None):
                     help="with --nav-grid-dir: carve free space along the rays of the poses estimated so far (at most 256, evenly thinned); "
                          "the files show the carved state, and _seen.npy (ray entries per cell) is written as well")
     ap.add_argument("--nav-grid-carve-stride", type=int, default=8, metavar="S", help="pixel lattice of the carving rays (default 8)")
+    ap.add_argument("--nav-plan-goal", nargs=2, type=float, action="append", default=None, metavar=("X", "Y"),
+                    help="with --nav-grid-dir: plan on every grid from the camera's cell to this goal (metres in the grid frame; repeatable); "
+                         "_cost.npy, _path.npy and _plan.json are written next to the grid")
+    ap.add_argument("--nav-plan-frontier", action="store_true", help="with --nav-grid-dir: every frontier cell of the grid is a goal")
+    ap.add_argument("--nav-plan-radius", type=float, default=0.0, metavar="R",
+                    help="the robot's radius in metres: cells with less clearance are not traversable (min_dist2 = ceil(R / res)^2)")
     ap.add_argument("--laser-scan-dir", default=None, metavar="DIR",
                     help="every --laser-scan-every frames, a planar laser scan simulated from the map on the device, from the tracked pose: "
                          "DIR/<frame number as %%06d>.npy (ranges in metres, +inf where nothing is hit)")
@@ -540,13 +573,26 @@ def parse_args(argv=None):
         ap.error("--motion-mask-dir needs --detect-motion")
     if a.nav_grid_carve and not a.nav_grid_dir:
         ap.error("--nav-grid-carve needs --nav-grid-dir")
+    if (a.nav_plan_goal or a.nav_plan_frontier) and not a.nav_grid_dir:
+        ap.error("--nav-plan-goal and --nav-plan-frontier need --nav-grid-dir")
+    if a.nav_plan_radius < 0.0 or (a.nav_plan_radius > 0.0 and not (a.nav_plan_goal or a.nav_plan_frontier)):
+        ap.error("--nav-plan-radius is >= 0 and goes with --nav-plan-goal or --nav-plan-frontier")
     return a
+
+
+def nav_plan_of(a):
+    """replay()'s nav_plan from the parsed options, or None"""
+    if not (a.nav_plan_goal or a.nav_plan_frontier):
+        return None
+    return dict(goals=[tuple(g) for g in (a.nav_plan_goal or [])], frontier=bool(a.nav_plan_frontier), radius=float(a.nav_plan_radius))
 
 
 def main():
     a = parse_args()
     from . import binding
-    lib = binding.load_navcarve() if a.nav_grid_carve else binding.load_product()     # (the carve's entry points: a library of their own)
+    plan = nav_plan_of(a)
+    # (the carve's and the plan's entry points: libraries of their own)
+    lib = binding.load_nav() if plan else (binding.load_navcarve() if a.nav_grid_carve else binding.load_product())
     cfg = lib.default_config(pipeline_depth=2 if a.pipelined else 0, extract_batch=4 if a.pipelined else 1, **BENCHMARK_LAUNCH)
     f = binding.Fusion(lib, cfg)
     if a.raw_frames:
@@ -558,7 +604,7 @@ def main():
                         local_cloud_radius=a.local_cloud_radius, local_cloud_every=a.local_cloud_every, keyframes={} if a.keyframes else None,
                         keyframe_log=a.keyframe_log, detect_motion=a.detect_motion, motion_mask_dir=a.motion_mask_dir,
                         odometry_prior=a.odometry_prior, nav_grid_dir=a.nav_grid_dir, nav_grid_every=a.nav_grid_every,
-                        nav_grid_res=a.nav_grid_res, nav_grid_carve=a.nav_grid_carve, nav_grid_carve_stride=a.nav_grid_carve_stride,
+                        nav_grid_res=a.nav_grid_res, nav_grid_carve=a.nav_grid_carve, nav_grid_carve_stride=a.nav_grid_carve_stride, nav_plan=plan,
                         laser_scan_dir=a.laser_scan_dir, laser_scan_every=a.laser_scan_every,
                         laser_scan_beams=a.laser_scan_beams)
     if a.keyframes and not a.keyframe_log:
