@@ -27,6 +27,7 @@
 #include "ssf_navgrid.h"
 #include "ssf_navcarve.h"
 #include "ssf_navplan.h"
+#include "ssf_navfrontier.h"
 #include "ssf_raycast.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
@@ -297,6 +298,36 @@ struct NavPlan {
     std::vector<int32_t> start_status;
     std::vector<std::vector<GridCell> > paths;
     ssf_navplan_stats stats;
+};
+
+/* frontierRegions and exploreGoal (ssf_navfrontier.h; exported by libssf_hip_explore.so, linked INSTEAD of the other libraries -- a
+ * program that calls neither links as before: the inline members leave no reference behind): the grid's frontier as regions, and
+ * the region to drive to next.  The members start at ssf_navfrontier_default_params' values. */
+struct FrontierParams {
+    int connectivity = 8;                          /* 8 or 4 */
+    bool traversable_only = false; int min_dist2 = 0;       /* members with dist2 >= min_dist2 only (the grid needs dist2) */
+    int min_cells = 1;                             /* smaller regions are dropped */
+    bool reachable_only = false;                   /* regions without a reached member are dropped (needs a cost field) */
+    int max_regions = 4096, gain_radius = 0;
+    int cost_weight = 1, gain_weight = 0, size_weight = 0;
+    bool want_region = true;                       /* false: the map is not produced (its vector stays empty) */
+};
+/* what frontierRegions makes: the map (row-major height x width: table index, -1 no member, -2 not in the table), the table in
+ * label order and the table indices best first */
+struct FrontierRegions {
+    int width = 0, height = 0;
+    std::vector<int32_t> region;
+    std::vector<ssf_navfrontier_region> regions;
+    std::vector<int32_t> order;
+    ssf_navfrontier_stats stats;
+};
+/* what exploreGoal makes: the regions ranked by the cost of reaching them from the robot, the chosen one (order[0]; -1 = none was
+ * reached), its representative cell and the robot's path to it (drive.paths[0]) */
+struct ExploreGoal {
+    FrontierRegions frontier;
+    int chosen = -1;
+    GridCell goal;
+    NavPlan drive;
 };
 
 /* castRays (ssf_raycast.h; exported by libssf_hip.so only): the first disc of the map that each ray hits.  The members start at
@@ -781,6 +812,59 @@ public:
             msg.poses[i].pose.orientation.x = 0.0; msg.poses[i].pose.orientation.y = 0.0; msg.poses[i].pose.orientation.z = 0.0;
             msg.poses[i].pose.orientation.w = 1.0;
         }
+    }
+    /* The frontier of a grid that buildNavGrid made, plain or carved, as regions (ssf_navfrontier.h).  cost: the field of a
+     * planOnGrid on the same grid (NavPlan::cost), or nullptr: then no region has a representative cost.  The grid needs its state,
+     * and its dist2 with traversable_only. */
+    void frontierRegions(const NavGrid& g, const FrontierParams& q, const std::vector<uint32_t>* cost, FrontierRegions& out) {
+        const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
+        if (n == 0 || g.state.size() != n) throw std::logic_error("frontierRegions: the grid has no state (want_state)");
+        if (q.traversable_only && g.dist2.size() != n) throw std::logic_error("frontierRegions: traversable_only needs the grid's dist2 (want_dist2)");
+        if (cost && cost->size() != n) throw std::logic_error("frontierRegions: the cost field is not the grid's size");
+        ssf_navfrontier_params p;
+        check(ssf_navfrontier_default_params(need(), &p));
+        p.width = g.width; p.height = g.height; p.connectivity = q.connectivity; p.traversable_only = q.traversable_only ? 1 : 0;
+        p.min_dist2 = q.min_dist2; p.min_cells = q.min_cells; p.reachable_only = q.reachable_only ? 1 : 0; p.max_regions = q.max_regions;
+        p.gain_radius = q.gain_radius; p.cost_weight = q.cost_weight; p.gain_weight = q.gain_weight; p.size_weight = q.size_weight; p.on_device = 0;
+        const size_t cap = q.max_regions >= 1 && q.max_regions <= 65536 ? (size_t)q.max_regions : 1;     /* (outside: the library refuses) */
+        out.width = g.width; out.height = g.height;
+        out.region.resize(q.want_region ? n : 0); out.regions.resize(cap); out.order.resize(cap);
+        ssf_navfrontier_out o;
+        o.region = q.want_region ? out.region.data() : nullptr; o.regions = out.regions.data(); o.order = out.order.data();
+        check(ssf_navfrontier_regions(need(), &p, g.state.data(), g.dist2.size() == n ? g.dist2.data() : nullptr, cost ? cost->data() : nullptr, &o,
+                                      &out.stats));
+        out.regions.resize((size_t)out.stats.regions_written); out.order.resize((size_t)out.stats.regions_written);
+    }
+    /* Where to go next, in three calls: (1) planOnGrid with the robot's cell as the only goal: the field; (2) frontierRegions with
+     * that field as the cost (reachable_only is switched on); (3) planOnGrid from the robot to the representative of order[0], with
+     * plan.max_path cells at most (0: width * height, capped at 1 << 20).  The field's cost is "from the cell to the robot": with a
+     * clearance penalty it differs from the drive out by pen[cell] - pen[robot]; the regions are ranked by the field as it is, and
+     * drive.start_cost[0] is the drive out.  Without a reached region chosen is -1 and drive is empty. */
+    void exploreGoal(const NavGrid& g, const GridCell& robot, PlanParams plan, FrontierParams frontier, ExploreGoal& out) {
+        const std::vector<GridCell> at(1, robot), none;
+        const int max_path = plan.max_path > 0 ? plan.max_path : (int)std::min<size_t>((size_t)g.width * (size_t)g.height, (size_t)1 << 20);
+        plan.goals_from_frontier = false; plan.max_path = 0; plan.want_cost = true; plan.want_frontier = false;
+        NavPlan field;
+        planOnGrid(g, plan, at, none, field);
+        frontier.reachable_only = true;
+        frontierRegions(g, frontier, &field.cost, out.frontier);
+        out.chosen = -1; out.goal[0] = -1; out.goal[1] = -1; out.drive = NavPlan();
+        if (out.frontier.order.empty()) return;
+        const ssf_navfrontier_region& r = out.frontier.regions[(size_t)out.frontier.order[0]];
+        out.chosen = out.frontier.order[0]; out.goal[0] = r.rep_x; out.goal[1] = r.rep_y;
+        plan.max_path = max_path; plan.want_cost = false;
+        planOnGrid(g, plan, std::vector<GridCell>(1, out.goal), at, out.drive);
+    }
+    /* The pose of a geometry_msgs::PoseStamped from the chosen cell: its centre, ((ix + 0.5) res, (iy + 0.5) res, 0) in the grid
+     * frame, taken to the map frame by pose12 (grid-to-map: NavGrid::stats.pose); the orientation is the identity.  header is the
+     * node's.  Any message type with pose.position and pose.orientation works (tests use a double). */
+    template <typename PoseStampedT> static void fillExploreGoal(const ExploreGoal& e, const float pose12[12], float res, PoseStampedT& msg) {
+        if (e.chosen < 0) throw std::logic_error("fillExploreGoal: no region was chosen");
+        const double x = ((double)e.goal[0] + 0.5) * (double)res, y = ((double)e.goal[1] + 0.5) * (double)res;
+        msg.pose.position.x = (double)pose12[0] * x + (double)pose12[1] * y + (double)pose12[9];
+        msg.pose.position.y = (double)pose12[3] * x + (double)pose12[4] * y + (double)pose12[10];
+        msg.pose.position.z = (double)pose12[6] * x + (double)pose12[7] * y + (double)pose12[11];
+        msg.pose.orientation.x = 0.0; msg.pose.orientation.y = 0.0; msg.pose.orientation.z = 0.0; msg.pose.orientation.w = 1.0;
     }
     /* Rays cast through the map on the device (ssf_raycast.h): rays6 holds n rays of six floats (origin, direction) in the frame of
      * r.pose.  The library keeps a spatial index of the map between calls and rebuilds it when the map has changed.  INTEGRATION.md

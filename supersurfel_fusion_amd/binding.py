@@ -20,6 +20,9 @@ NAVCARVE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_navcarve.so")
 # the product's objects, the carve and the plan on the navigation grid (include/ssf_navplan.h): the one library of a robot that
 # builds, carves and plans.  Neither of the two libraries above exports the plan's entry points
 NAV_LIB = os.path.join(_HERE, "csrc", "libssf_hip_nav.so")
+# nav's objects and the frontier regions (include/ssf_navfrontier.h): the one library of a robot that builds, carves, plans and
+# explores.  None of the three libraries above exports the regions' entry points
+EXPLORE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_explore.so")
 
 
 class SsfConfig(C.Structure):
@@ -119,6 +122,13 @@ NAVCARVE_OUTPUT_NAMES = tuple(nm for nm, _, _ in NAVCARVE_OUTPUTS)
 NAVPLAN_SYMBOLS = ["ssf_navplan_default_params", "ssf_navplan_field", "ssf_debug_navplan_set_round_batch", "ssf_debug_navplan_last"]
 NAVPLAN_OUTPUT_NAMES = ("cost", "frontier", "start_cost", "start_status", "path_len", "path")
 NAVPLAN_UNREACHED = 0xFFFFFFFF
+# the frontier regions of the navigation grid (include/ssf_navfrontier.h): exported by libssf_hip_explore.so only (load_explore)
+NAVFRONTIER_SYMBOLS = ["ssf_navfrontier_default_params", "ssf_navfrontier_regions"]
+NAVFRONTIER_MAX_REGIONS = 65536
+# ssf_navfrontier_region as a numpy record (56 bytes)
+NAVFRONTIER_REGION_DTYPE = np.dtype([("sum_x", np.int64), ("sum_y", np.int64), ("label", np.int32), ("cells", np.int32), ("x0", np.int32),
+                                     ("y0", np.int32), ("x1", np.int32), ("y1", np.int32), ("rep_x", np.int32), ("rep_y", np.int32),
+                                     ("rep_cost", np.uint32), ("gain", np.int32)])
 # rays cast through the model (include/ssf_raycast.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 RAYCAST_SYMBOLS = ["ssf_raycast_default_params", "ssf_raycast"]
 # the output arrays of ssf_raycast, in its argument order: name, dtype, per-ray shape
@@ -284,6 +294,32 @@ class SsfNavPlanStats(C.Structure):
     """ssf_navplan_stats (include/ssf_navplan.h)"""
     _fields_ = [(nm, C.c_int64) for nm in ("cells_traversable", "cells_reached", "frontier_cells", "frontier_goals", "goals_used", "goals_blocked",
                                            "goals_outside", "max_cost", "rounds", "tile_visits")]
+
+    def as_dict(self):
+        return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
+
+
+class SsfNavFrontierParams(C.Structure):
+    """ssf_navfrontier_params (include/ssf_navfrontier.h)"""
+    _fields_ = [(nm, C.c_int) for nm in ("width", "height", "connectivity", "traversable_only", "min_dist2", "min_cells", "reachable_only",
+                                         "max_regions", "gain_radius", "cost_weight", "gain_weight", "size_weight", "on_device")]
+
+
+class SsfNavFrontierRegion(C.Structure):
+    """ssf_navfrontier_region (include/ssf_navfrontier.h); NAVFRONTIER_REGION_DTYPE is the same record for numpy"""
+    _fields_ = [("sum_x", C.c_int64), ("sum_y", C.c_int64)] + \
+               [(nm, C.c_int32) for nm in ("label", "cells", "x0", "y0", "x1", "y1", "rep_x", "rep_y")] + [("rep_cost", C.c_uint32), ("gain", C.c_int32)]
+
+
+class SsfNavFrontierOut(C.Structure):
+    """ssf_navfrontier_out (include/ssf_navfrontier.h)"""
+    _fields_ = [("region", C.c_void_p), ("regions", C.c_void_p), ("order", C.c_void_p)]
+
+
+class SsfNavFrontierStats(C.Structure):
+    """ssf_navfrontier_stats (include/ssf_navfrontier.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("frontier_cells", "regions_found", "regions_small", "regions_unreached", "regions_kept",
+                                           "regions_written", "largest_cells", "gain_rays", "merge_pairs")]
 
     def as_dict(self):
         return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
@@ -466,6 +502,11 @@ class Library:
             L.ssf_navplan_field.argtypes = [vp, C.POINTER(SsfNavPlanParams), vp, vp, C.POINTER(SsfNavPlanOut), C.POINTER(SsfNavPlanStats)]
             L.ssf_debug_navplan_set_round_batch.argtypes = [vp, C.c_int]
             L.ssf_debug_navplan_last.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        self.has_navfrontier = all(hasattr(L, nm) for nm in NAVFRONTIER_SYMBOLS)
+        if self.has_navfrontier:
+            L.ssf_navfrontier_default_params.argtypes = [vp, C.POINTER(SsfNavFrontierParams)]
+            L.ssf_navfrontier_regions.argtypes = [vp, C.POINTER(SsfNavFrontierParams), vp, vp, vp, C.POINTER(SsfNavFrontierOut),
+                                                  C.POINTER(SsfNavFrontierStats)]
         self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
         if self.has_navgrid:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
@@ -572,6 +613,14 @@ def load_nav():
     library to call nav_plan on it.  Fails loudly when it has not been built."""
     import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
     return Library(NAV_LIB)
+
+
+def load_explore():
+    """Load libssf_hip_explore.so: nav's objects (the product, the carve, the plan) with the frontier regions linked in
+    (include/ssf_navfrontier.h).  A handle belongs to the library that created it: create the Fusion from THIS library to call
+    nav_frontiers or nav_explore on it.  Fails loudly when it has not been built."""
+    import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
+    return Library(EXPLORE_LIB)
 
 
 def load_lab():
@@ -1428,6 +1477,113 @@ class Fusion:
         a, b = C.c_int64(0), C.c_int64(0)
         self._ck(self.L.lib.ssf_debug_navplan_last(self.h, C.byref(a), C.byref(b)), "ssf_debug_navplan_last")
         return dict(rounds=int(a.value), tile_visits=int(b.value))
+
+    # ---- the frontier of the navigation grid as regions (include/ssf_navfrontier.h) --------------------
+    def _need_navfrontier(self, symbol):
+        if not self.L.has_navfrontier:
+            raise SsfError("%s does not export %s: it groups no frontier (include/ssf_navfrontier.h: libssf_hip_explore.so, binding.load_explore)"
+                           % (self.L.path, symbol))
+
+    def _navfrontier_params(self, on_device, width, height, params):
+        """SsfNavFrontierParams: the fields of ssf_navfrontier_params by name, each at ssf_navfrontier_default_params' value when
+        missing"""
+        p = SsfNavFrontierParams()
+        self._ck(self.L.lib.ssf_navfrontier_default_params(self.h, C.byref(p)), "ssf_navfrontier_default_params")
+        kinds = dict(p._fields_)
+        for nm, val in params.items():
+            if nm not in kinds or nm in ("width", "height", "on_device"):
+                raise SsfError("unknown frontier parameter %r" % nm)
+            setattr(p, nm, int(val))
+        p.width, p.height, p.on_device = int(width), int(height), int(bool(on_device))
+        return p
+
+    def _navfrontier_regions(self, p, state, dist2, cost, region):
+        """the call with a host table and order of max_regions records: (regions, order, stats), cut to regions_written"""
+        n = min(max(p.max_regions, 0), NAVFRONTIER_MAX_REGIONS)
+        regions, order = np.zeros(n, NAVFRONTIER_REGION_DTYPE), np.zeros(n, np.int32)
+        st, out = SsfNavFrontierStats(), SsfNavFrontierOut(region, _ptr(regions), _ptr(order))
+        self._ck(self.L.lib.ssf_navfrontier_regions(self.h, C.byref(p), state, dist2, cost, C.byref(out), C.byref(st)), "ssf_navfrontier_regions")
+        stats = st.as_dict()
+        k = stats["regions_written"]
+        return regions[:k].copy(), order[:k].copy(), stats
+
+    def nav_frontiers(self, state, dist2=None, cost=None, **params):
+        """The frontier of a navigation grid grouped into regions (ssf_navfrontier_regions).  state H x W int8 and dist2 H x W int32
+        as nav_grid / nav_grid_carve return them, cost H x W uint32 as nav_plan returns it (both may be None).  Returns a dict:
+        'region' H x W int32 (table index, -1 no member, -2 not in the table), 'regions' (NAVFRONTIER_REGION_DTYPE records, in label
+        order), 'order' (table indices, best first) and 'stats'.  params: connectivity, traversable_only, min_dist2, min_cells,
+        reachable_only, max_regions, gain_radius, cost_weight, gain_weight, size_weight."""
+        self._need_navfrontier("ssf_navfrontier_regions")
+        state = np.ascontiguousarray(state, np.int8)
+        if state.ndim != 2:
+            raise SsfError("state is an H x W array, got shape %s" % (state.shape,))
+        if dist2 is not None:
+            dist2 = np.ascontiguousarray(dist2, np.int32)
+        if cost is not None:
+            cost = np.ascontiguousarray(cost, np.uint32)
+        for nm, a in (("dist2", dist2), ("cost", cost)):
+            if a is not None and a.shape != state.shape:
+                raise SsfError("state and %s are H x W arrays of one shape, got %s and %s" % (nm, state.shape, a.shape))
+        H, W = state.shape
+        p = self._navfrontier_params(False, W, H, params)
+        region = np.zeros((H, W), np.int32)
+        regions, order, stats = self._navfrontier_regions(p, _ptr(state), _ptr(dist2), _ptr(cost), _ptr(region))
+        return dict(region=region, regions=regions, order=order, stats=stats)
+
+    def nav_frontiers_device(self, state, width, height, dist2=None, cost=None, region=None, **params):
+        """ssf_navfrontier_regions on device memory: state, dist2, cost and region are contiguous torch tensors on the device or
+        device addresses (int) of buffers of the shapes and dtypes nav_frontiers works on (dist2, cost and region may be None); the
+        table and the order stay host memory.  Returns a dict of 'regions', 'order' and 'stats'."""
+        self._need_navfrontier("ssf_navfrontier_regions")
+        p = self._navfrontier_params(True, width, height, params)
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        regions, order, stats = self._navfrontier_regions(p, addr(state), addr(dist2), addr(cost), addr(region))
+        return dict(regions=regions, order=order, stats=stats)
+
+    def nav_frontiers_default_params(self):
+        """ssf_navfrontier_default_params as a dict"""
+        self._need_navfrontier("ssf_navfrontier_default_params")
+        p = SsfNavFrontierParams()
+        self._ck(self.L.lib.ssf_navfrontier_default_params(self.h, C.byref(p)), "ssf_navfrontier_default_params")
+        return {nm: getattr(p, nm) for nm, _ in p._fields_}
+
+    def nav_explore(self, state, dist2, robot_cell, plan=None, frontier=None):
+        """Where to go next on a navigation grid, in three calls: (1) nav_plan with the robot's cell as the only goal: the field;
+        (2) nav_frontiers with that field as `cost`; (3) nav_plan with the chosen region's representative as the only goal and the
+        robot as the start: the path.  The chosen region is order[0], if it was reached.  plan: the plan's parameters (min_dist2,
+        soft_dist2, near_penalty, allow_unknown, max_path; max_path defaults to width * height capped at 1 << 20); frontier:
+        nav_frontiers' parameters (reachable_only defaults to 1).
+
+        The field's cost is "from the cell to the robot": the cost of driving from the cell to the robot's cell.  With a clearance
+        penalty it differs from the drive out, robot to cell, by pen[cell] - pen[robot], because a move pays the penalty of the cell
+        it enters; rep_cost and the ranking use the field as it is, and 'cost' below is the drive out as step (3) computes it.
+
+        Returns a dict: 'region', 'regions', 'order', 'stats' as nav_frontiers; 'chosen' (the table index, or -1 when no region was
+        reached); 'goal' ((ix, iy) or None); 'cost' (u32), 'status' and 'path' ((len, 2) int32) of the drive to it, None / empty
+        without a goal; 'field_stats' and 'path_stats' (the two plans' stats)."""
+        self._need_navplan("ssf_navplan_field")
+        self._need_navfrontier("ssf_navfrontier_regions")
+        plan, frontier = dict(plan or {}), dict(frontier or {})
+        for nm in ("goals_from_frontier",):
+            if nm in plan:
+                raise SsfError("nav_explore sets %s itself" % nm)
+        state = np.ascontiguousarray(state, np.int8)
+        if state.ndim != 2:
+            raise SsfError("state is an H x W array, got shape %s" % (state.shape,))
+        H, W = state.shape
+        robot = self._cell_list([tuple(robot_cell)], "robot_cell")
+        max_path = int(plan.pop("max_path", min(W * H, 1 << 20)))
+        field = self.nav_plan(state, dist2, goals=robot, outputs=("cost",), **plan)
+        frontier.setdefault("reachable_only", 1)
+        out = self.nav_frontiers(state, dist2, field["cost"], **frontier)
+        out.update(field_stats=field["stats"], chosen=-1, goal=None, cost=None, status=None, path=np.zeros((0, 2), np.int32), path_stats=None)
+        if len(out["order"]) and out["regions"]["rep_cost"][out["order"][0]] != NAVPLAN_UNREACHED:
+            c = int(out["order"][0])
+            goal = (int(out["regions"]["rep_x"][c]), int(out["regions"]["rep_y"][c]))
+            drive = self.nav_plan(state, dist2, goals=[goal], starts=robot, outputs=("start_cost", "start_status", "path"), max_path=max_path, **plan)
+            out.update(chosen=c, goal=goal, cost=int(drive["start_cost"][0]), status=int(drive["start_status"][0]), path=drive["path"][0],
+                       path_stats=drive["stats"])
+        return out
 
     # ---- rays cast through the model: the first disc each ray hits (include/ssf_raycast.h) ------------
     def _need_raycast(self, symbol):

@@ -353,6 +353,18 @@ struct NavPlanWs {
     int32_t* path = nullptr; size_t path_words = 0;
     int round_batch = 0; long long last_rounds = 0, last_visits = 0;
 };
+// ssf_navfrontier_regions (ssf_navfrontier.h, ssf_navfrontier.hip: linked into libssf_hip_explore.so only): per cell the grid and the
+// cost field as the call got them (the copies of host arrays), the union-find's parent word and the label; per 256 cells and per 256
+// regions (+ 1) the counts that are scanned into offsets; per region found the accumulators (acc: NavFrontierAcc, ssf_navfrontier.hip);
+// the table (65536 records) and the sums.  Allocated on first use; each group is grown as a whole or not at all (DevBufs::grow).
+// Nothing here is read or written by the frame path.
+struct NavFrontierWs {
+    DevBufs bufs;
+    int8_t* state = nullptr; int32_t* dist2 = nullptr; uint32_t* cost = nullptr; int32_t* parent = nullptr; int32_t* label = nullptr;
+    uint32_t* cell_blocks = nullptr; size_t cells = 0;
+    void* acc = nullptr; uint32_t* region_blocks = nullptr; size_t regions = 0;
+    void* table = nullptr; unsigned long long* stats = nullptr;
+};
 // ssf_raycast (ssf_raycast.h): the resident index -- per slot the 64-byte record and the box of cells with the row's class, the
 // out-of-view blocks' live offsets, the oversize list; per bucket (+ 1) the list offsets and the fill's cursors; the (bucket -> slot)
 // lists; the sums and the box of indexed cells -- and the staging buffer of a call's host rays and outputs.  The index is valid
@@ -480,6 +492,7 @@ struct ssf_handle {
     NavGridWs navgrid;                            // ssf_navgrid_build (ssf_navgrid.h)
     NavCarveWs navcarve;                          // ssf_navgrid_carve (ssf_navcarve.h)
     NavPlanWs navplan;                            // ssf_navplan_field (ssf_navplan.h)
+    NavFrontierWs navfrontier;                    // ssf_navfrontier_regions (ssf_navfrontier.h)
     RaycastWs raycast;                            // ssf_raycast (ssf_raycast.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense); the out-of-view
                                                   // compaction keeps rows and order but moves slots: who keeps slot numbers also watches n_recentres (RaycastWs)

@@ -217,7 +217,7 @@ def plan_cells(pose, res, cam_t, goals_m):
     return start, goals
 
 
-def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, plan=None):
+def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, plan=None, frontiers=None):
     """the navigation grid of the map, built on the device (include/ssf_navgrid.h) at the default size and frame (floor-aligned
     about the tracked camera) with cells of `res` metres: grid_dir/<k as %06d>.pgm -- the state in map_server's convention (205
     unknown, 254 free, 0 occupied; the image's top row is the grid's last) --, <k>.yaml beside it (map_server's keys; origin = the
@@ -226,7 +226,10 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
     (include/ssf_navcarve.h), the files show the carved state, and <k>_seen.npy holds the ray entries per cell.
     plan (dict(goals=(X, Y) pairs in metres in the grid frame, frontier=bool, radius=metres)): the cost-to-goal field of that grid
     for a robot of that radius, from the camera's cell (include/ssf_navplan.h): <k>_cost.npy (u32, 0xFFFFFFFF = not reached),
-    <k>_path.npy (the cells (ix, iy) from the camera's cell to the goal) and <k>_plan.json (the stats, the start and its status)"""
+    <k>_path.npy (the cells (ix, iy) from the camera's cell to the goal) and <k>_plan.json (the stats, the start and its status).
+    frontiers (dict(min_cells, gain_radius)): the grid's frontier as regions (include/ssf_navfrontier.h), ranked by the cost of
+    driving to them from the camera's cell for a robot of the plan's radius (0 without a plan): <k>_frontiers.json (regions = the
+    table's records, order, stats, start) and <k>_frontier_regions.npy (the map: table index, -1 no member, -2 not in the table)"""
     if carve_views is None:
         out = fusion.nav_grid(outputs=("state", "dist2"), res=res)
     else:
@@ -257,6 +260,17 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
         with open(os.path.join(grid_dir, name + "_plan.json"), "w") as f:
             json.dump(dict(got["stats"], start=[int(v) for v in start[0]], start_status=int(got["start_status"][0]),
                            start_cost=int(got["start_cost"][0]), min_dist2=cells * cells), f, sort_keys=True)
+    if frontiers is not None:
+        import json
+        start, _ = plan_cells(pose, res, fusion.get_pose()[9:12], [])
+        cells = int(np.ceil(float((plan or {}).get("radius") or 0.0) / res))
+        field = fusion.nav_plan(state, out["dist2"], start, outputs=("cost",), min_dist2=cells * cells)
+        got = fusion.nav_frontiers(state, out["dist2"], field["cost"], min_cells=int(frontiers.get("min_cells", 1)),
+                                   gain_radius=int(frontiers.get("gain_radius", 0)))
+        np.save(os.path.join(grid_dir, name + "_frontier_regions.npy"), got["region"])
+        with open(os.path.join(grid_dir, name + "_frontiers.json"), "w") as f:
+            json.dump(dict(regions=[{nm: int(r[nm]) for nm in got["regions"].dtype.names} for r in got["regions"]],
+                           order=[int(i) for i in got["order"]], stats=got["stats"], start=[int(v) for v in start[0]]), f, sort_keys=True)
     return out["stats"]
 
 
@@ -293,7 +307,7 @@ def write_laser_scan(fusion, scan_dir, k, beams):
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
            keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30, detect_motion=False,
            motion_mask_dir=None, odometry_prior=False, nav_grid_dir=None, nav_grid_every=30, nav_grid_res=0.05,
-           nav_grid_carve=False, nav_grid_carve_stride=8, nav_plan=None, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
+           nav_grid_carve=False, nav_grid_carve_stride=8, nav_plan=None, nav_frontiers=None, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
@@ -307,7 +321,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     metres is written (write_nav_grid, numbered by frame); pipelined, submission pauses as for a render.  nav_grid_carve: the grid
     is carved along the rays of the poses estimated so far (thin_views: at most 256 of them) on a pixel lattice of
     nav_grid_carve_stride, and <k>_seen.npy is written as well.  nav_plan (write_nav_grid's plan): the field, path and stats of a
-    plan from the camera's cell are written next to each grid.
+    plan from the camera's cell are written next to each grid.  nav_frontiers (write_nav_grid's frontiers): the frontier regions
+    of each grid, ranked from the camera's cell, are written next to it.
     laser_scan_dir: after frames 0, laser_scan_every, 2 laser_scan_every, ... a planar scan of laser_scan_beams beams from the tracked
     pose is written (write_laser_scan, numbered by frame); pipelined, submission pauses as for a render.
     keyframes: a dict of ssf_keyframes_params fields ({} = the defaults): the keyframe database is configured and
@@ -324,6 +339,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
         raise ValueError("nav_grid_carve needs nav_grid_dir")
     if nav_plan is not None and not nav_grid_dir:
         raise ValueError("nav_plan needs nav_grid_dir")
+    if nav_frontiers is not None and not nav_grid_dir:
+        raise ValueError("nav_frontiers needs nav_grid_dir")
     carve_views = (lambda: [r["pose"] for r in results]) if nav_grid_carve else (lambda: None)
     if odometry_prior:
         if pipelined:
@@ -374,7 +391,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             if local_cloud_dir and (len(lines) - 1) % local_cloud_every == 0:
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
-                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan)
+                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan, nav_frontiers)
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     else:
@@ -406,7 +423,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             if local_cloud_dir and (len(lines) - 1) % local_cloud_every == 0:
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
-                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan)
+                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan, nav_frontiers)
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     if out_path:
@@ -549,6 +566,12 @@ def parse_args(argv=None):
     ap.add_argument("--nav-plan-frontier", action="store_true", help="with --nav-grid-dir: every frontier cell of the grid is a goal")
     ap.add_argument("--nav-plan-radius", type=float, default=0.0, metavar="R",
                     help="the robot's radius in metres: cells with less clearance are not traversable (min_dist2 = ceil(R / res)^2)")
+    ap.add_argument("--nav-frontiers", action="store_true",
+                    help="with --nav-grid-dir: the frontier of every grid as regions, ranked by the cost of driving to them from the camera's "
+                         "cell; _frontiers.json (table, order, stats) and _frontier_regions.npy (the map) are written next to the grid")
+    ap.add_argument("--nav-frontier-min-cells", type=int, default=None, metavar="N", help="regions of fewer cells are dropped (default 1)")
+    ap.add_argument("--nav-frontier-gain-radius", type=int, default=None, metavar="R",
+                    help="cells, 0..128: count the unknown cells seen along rays of this length from each region (default 0: no gain)")
     ap.add_argument("--laser-scan-dir", default=None, metavar="DIR",
                     help="every --laser-scan-every frames, a planar laser scan simulated from the map on the device, from the tracked pose: "
                          "DIR/<frame number as %%06d>.npy (ranges in metres, +inf where nothing is hit)")
@@ -577,6 +600,14 @@ def parse_args(argv=None):
         ap.error("--nav-plan-goal and --nav-plan-frontier need --nav-grid-dir")
     if a.nav_plan_radius < 0.0 or (a.nav_plan_radius > 0.0 and not (a.nav_plan_goal or a.nav_plan_frontier)):
         ap.error("--nav-plan-radius is >= 0 and goes with --nav-plan-goal or --nav-plan-frontier")
+    if a.nav_frontiers and not a.nav_grid_dir:
+        ap.error("--nav-frontiers needs --nav-grid-dir")
+    if (a.nav_frontier_min_cells is not None or a.nav_frontier_gain_radius is not None) and not a.nav_frontiers:
+        ap.error("--nav-frontier-min-cells and --nav-frontier-gain-radius go with --nav-frontiers")
+    if a.nav_frontier_min_cells is not None and a.nav_frontier_min_cells < 1:
+        ap.error("--nav-frontier-min-cells is >= 1")
+    if a.nav_frontier_gain_radius is not None and not 0 <= a.nav_frontier_gain_radius <= 128:
+        ap.error("--nav-frontier-gain-radius is 0..128")
     return a
 
 
@@ -587,12 +618,20 @@ def nav_plan_of(a):
     return dict(goals=[tuple(g) for g in (a.nav_plan_goal or [])], frontier=bool(a.nav_plan_frontier), radius=float(a.nav_plan_radius))
 
 
+def nav_frontiers_of(a):
+    """replay()'s nav_frontiers from the parsed options, or None"""
+    if not a.nav_frontiers:
+        return None
+    return dict(min_cells=1 if a.nav_frontier_min_cells is None else int(a.nav_frontier_min_cells),
+                gain_radius=0 if a.nav_frontier_gain_radius is None else int(a.nav_frontier_gain_radius))
+
+
 def main():
     a = parse_args()
     from . import binding
-    plan = nav_plan_of(a)
-    # (the carve's and the plan's entry points: libraries of their own)
-    lib = binding.load_nav() if plan else (binding.load_navcarve() if a.nav_grid_carve else binding.load_product())
+    plan, frontiers = nav_plan_of(a), nav_frontiers_of(a)
+    # (the carve's, the plan's and the regions' entry points: libraries of their own)
+    lib = binding.load_explore() if frontiers else (binding.load_nav() if plan else (binding.load_navcarve() if a.nav_grid_carve else binding.load_product()))
     cfg = lib.default_config(pipeline_depth=2 if a.pipelined else 0, extract_batch=4 if a.pipelined else 1, **BENCHMARK_LAUNCH)
     f = binding.Fusion(lib, cfg)
     if a.raw_frames:
@@ -605,6 +644,7 @@ def main():
                         keyframe_log=a.keyframe_log, detect_motion=a.detect_motion, motion_mask_dir=a.motion_mask_dir,
                         odometry_prior=a.odometry_prior, nav_grid_dir=a.nav_grid_dir, nav_grid_every=a.nav_grid_every,
                         nav_grid_res=a.nav_grid_res, nav_grid_carve=a.nav_grid_carve, nav_grid_carve_stride=a.nav_grid_carve_stride, nav_plan=plan,
+                        nav_frontiers=frontiers,
                         laser_scan_dir=a.laser_scan_dir, laser_scan_every=a.laser_scan_every,
                         laser_scan_beams=a.laser_scan_beams)
     if a.keyframes and not a.keyframe_log:
