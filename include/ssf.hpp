@@ -28,6 +28,7 @@
 #include "ssf_navcarve.h"
 #include "ssf_navplan.h"
 #include "ssf_navfrontier.h"
+#include "ssf_navpath.h"
 #include "ssf_raycast.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
@@ -328,6 +329,24 @@ struct ExploreGoal {
     int chosen = -1;
     GridCell goal;
     NavPlan drive;
+};
+
+/* refinePaths (ssf_navpath.h; exported by libssf_hip_drive.so, linked INSTEAD of the other libraries -- a program that does not call
+ * it links as before: the inline member leaves no reference behind): the cell paths of a plan reduced to any-angle waypoints.  The
+ * members start at ssf_navpath_default_params' values. */
+struct WaypointParams {
+    int min_dist2 = 0; bool allow_unknown = false;      /* the plan's: what the robot may stand on */
+    int los_dist2 = 0;                                  /* every cell of a segment has at least this squared clearance */
+    bool keep_clearance = false; int clearance_cap = 0; /* a segment keeps the clearance of the piece of path it replaces, up to the cap */
+    int lookahead = 256;                                /* candidates per anchor, 1..4096 */
+    int max_waypoints = 0;                              /* per path; 0 = as many as the longest path has cells */
+};
+struct Waypoint { int32_t ix, iy, index, seg_min; };    /* index: into the path, bit 30 (SSF_NAVPATH_FORCED) on a forced step */
+/* what refinePaths makes: per path its waypoints, status (ssf_navpath.h step 6) and smallest seg_min (-1: no waypoint) */
+struct NavWaypoints {
+    std::vector<std::vector<Waypoint> > waypoints;
+    std::vector<int32_t> status, path_min;
+    ssf_navpath_stats stats;
 };
 
 /* castRays (ssf_raycast.h; exported by libssf_hip.so only): the first disc of the map that each ray hits.  The members start at
@@ -865,6 +884,69 @@ public:
         msg.pose.position.y = (double)pose12[3] * x + (double)pose12[4] * y + (double)pose12[10];
         msg.pose.position.z = (double)pose12[6] * x + (double)pose12[7] * y + (double)pose12[11];
         msg.pose.orientation.x = 0.0; msg.pose.orientation.y = 0.0; msg.pose.orientation.z = 0.0; msg.pose.orientation.w = 1.0;
+    }
+    /* The paths of a planOnGrid on the same grid reduced to waypoints (ssf_navpath.h): consecutive waypoints are joined by a straight
+     * segment whose every cell is traversable with the asked clearance.  The grid needs its state and dist2. */
+    void refinePaths(const NavGrid& g, const std::vector<std::vector<GridCell> >& paths, const WaypointParams& q, NavWaypoints& out) {
+        const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
+        if (n == 0 || g.state.size() != n || g.dist2.size() != n) throw std::logic_error("refinePaths: the grid has no state or no dist2 (want_state, want_dist2)");
+        if (paths.empty()) throw std::logic_error("refinePaths: no path");
+        size_t mp = 1;
+        for (size_t i = 0; i < paths.size(); i++) mp = std::max(mp, paths[i].size());
+        const size_t np = paths.size(), mw = q.max_waypoints > 0 ? (size_t)q.max_waypoints : mp;
+        ssf_navpath_params p;
+        check(ssf_navpath_default_params(need(), &p));
+        p.width = g.width; p.height = g.height; p.min_dist2 = q.min_dist2; p.allow_unknown = q.allow_unknown ? 1 : 0; p.los_dist2 = q.los_dist2;
+        p.keep_clearance = q.keep_clearance ? 1 : 0; p.clearance_cap = q.clearance_cap; p.lookahead = q.lookahead;
+        p.n_paths = (int)std::min<size_t>(np, 1u << 30); p.max_path = (int)std::min<size_t>(mp, 1u << 30);        /* (too many: the library refuses) */
+        p.max_waypoints = (int)std::min<size_t>(mw, 1u << 30); p.on_device = 0;
+        const bool fits = np <= 4096 && mp <= ((size_t)1 << 20) && mw <= ((size_t)1 << 20);
+        std::vector<int32_t> cells(fits ? np * mp * 2 : 2), len(np), count(np, 0), wp(fits ? np * mw * 4 : 4);
+        for (size_t i = 0; i < np; i++) {
+            len[i] = (int32_t)paths[i].size();
+            for (size_t k = 0; fits && k < paths[i].size(); k++) { cells[(i * mp + k) * 2] = paths[i][k][0]; cells[(i * mp + k) * 2 + 1] = paths[i][k][1]; }
+        }
+        out.status.assign(np, 0); out.path_min.assign(np, -1);
+        ssf_navpath_out o;
+        o.n_waypoints = count.data(); o.status = out.status.data(); o.waypoints = wp.data(); o.path_min = out.path_min.data();
+        check(ssf_navpath_waypoints(need(), &p, g.state.data(), g.dist2.data(), cells.data(), len.data(), &o, &out.stats));
+        out.waypoints.assign(np, std::vector<Waypoint>());
+        for (size_t i = 0; i < np; i++) {
+            out.waypoints[i].resize((size_t)count[i]);
+            for (size_t k = 0; k < (size_t)count[i]; k++) {
+                const int32_t* w = &wp[(i * mw + k) * 4];
+                Waypoint& d = out.waypoints[i][k];
+                d.ix = w[0]; d.iy = w[1]; d.index = w[2]; d.seg_min = w[3];
+            }
+        }
+    }
+    /* The poses of a nav_msgs::Path from the waypoints of path i, one pose per waypoint: the position as fillPath makes it (the
+     * cell's centre in the grid frame, taken to the map frame by pose12 = NavGrid::stats.pose); the orientation is the grid frame's
+     * rotation times the yaw about the grid's z towards the next waypoint, and the last pose repeats the one before it (a path of
+     * one waypoint has yaw 0).  header and the poses' headers are the node's. */
+    template <typename PathT> static void fillWaypointPath(const NavWaypoints& wp, size_t i, const float pose12[12], float res, PathT& msg) {
+        if (i >= wp.waypoints.size()) throw std::logic_error("fillWaypointPath: no such path");
+        const std::vector<Waypoint>& w = wp.waypoints[i];
+        const double m00 = pose12[0], m01 = pose12[1], m02 = pose12[2], m10 = pose12[3], m11 = pose12[4], m12 = pose12[5], m20 = pose12[6], m21 = pose12[7],
+                     m22 = pose12[8];
+        const double tr = m00 + m11 + m22;
+        double qw, qx, qy, qz;
+        if (tr > 0.0) { const double s = 2.0 * std::sqrt(1.0 + tr); qw = 0.25 * s; qx = (m21 - m12) / s; qy = (m02 - m20) / s; qz = (m10 - m01) / s; }
+        else if (m00 > m11 && m00 > m22) { const double s = 2.0 * std::sqrt(1.0 + m00 - m11 - m22); qw = (m21 - m12) / s; qx = 0.25 * s; qy = (m01 + m10) / s; qz = (m02 + m20) / s; }
+        else if (m11 > m22) { const double s = 2.0 * std::sqrt(1.0 + m11 - m00 - m22); qw = (m02 - m20) / s; qx = (m01 + m10) / s; qy = 0.25 * s; qz = (m12 + m21) / s; }
+        else { const double s = 2.0 * std::sqrt(1.0 + m22 - m00 - m11); qw = (m10 - m01) / s; qx = (m02 + m20) / s; qy = (m12 + m21) / s; qz = 0.25 * s; }
+        msg.poses.resize(w.size());
+        double yaw = 0.0;
+        for (size_t k = 0; k < w.size(); k++) {
+            const double x = ((double)w[k].ix + 0.5) * (double)res, y = ((double)w[k].iy + 0.5) * (double)res;
+            msg.poses[k].pose.position.x = m00 * x + m01 * y + (double)pose12[9];
+            msg.poses[k].pose.position.y = m10 * x + m11 * y + (double)pose12[10];
+            msg.poses[k].pose.position.z = m20 * x + m21 * y + (double)pose12[11];
+            if (k + 1 < w.size()) yaw = std::atan2((double)(w[k + 1].iy - w[k].iy), (double)(w[k + 1].ix - w[k].ix));
+            const double sz = std::sin(0.5 * yaw), cz = std::cos(0.5 * yaw);       /* q(R) * (0, 0, sz, cz) */
+            msg.poses[k].pose.orientation.w = qw * cz - qz * sz; msg.poses[k].pose.orientation.x = qx * cz + qy * sz;
+            msg.poses[k].pose.orientation.y = qy * cz - qx * sz; msg.poses[k].pose.orientation.z = qz * cz + qw * sz;
+        }
     }
     /* Rays cast through the map on the device (ssf_raycast.h): rays6 holds n rays of six floats (origin, direction) in the frame of
      * r.pose.  The library keeps a spatial index of the map between calls and rebuilds it when the map has changed.  INTEGRATION.md

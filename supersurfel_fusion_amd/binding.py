@@ -23,6 +23,9 @@ NAV_LIB = os.path.join(_HERE, "csrc", "libssf_hip_nav.so")
 # nav's objects and the frontier regions (include/ssf_navfrontier.h): the one library of a robot that builds, carves, plans and
 # explores.  None of the three libraries above exports the regions' entry points
 EXPLORE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_explore.so")
+# explore's objects and the waypoints of the plan's paths (include/ssf_navpath.h): the one library of a robot that builds, carves, plans,
+# explores and drives.  None of the four libraries above exports the waypoints' entry points
+DRIVE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_drive.so")
 
 
 class SsfConfig(C.Structure):
@@ -129,6 +132,10 @@ NAVFRONTIER_MAX_REGIONS = 65536
 NAVFRONTIER_REGION_DTYPE = np.dtype([("sum_x", np.int64), ("sum_y", np.int64), ("label", np.int32), ("cells", np.int32), ("x0", np.int32),
                                      ("y0", np.int32), ("x1", np.int32), ("y1", np.int32), ("rep_x", np.int32), ("rep_y", np.int32),
                                      ("rep_cost", np.uint32), ("gain", np.int32)])
+# the waypoints of the plan's paths (include/ssf_navpath.h): exported by libssf_hip_drive.so only (load_drive)
+NAVPATH_SYMBOLS = ["ssf_navpath_default_params", "ssf_navpath_waypoints"]
+NAVPATH_OUTPUT_NAMES = ("n_waypoints", "status", "waypoints", "path_min")
+NAVPATH_FORCED = 1 << 30             # bit 30 of a waypoint's index word: the segment that leads to it was not visible
 # rays cast through the model (include/ssf_raycast.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 RAYCAST_SYMBOLS = ["ssf_raycast_default_params", "ssf_raycast"]
 # the output arrays of ssf_raycast, in its argument order: name, dtype, per-ray shape
@@ -325,6 +332,25 @@ class SsfNavFrontierStats(C.Structure):
         return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
 
 
+class SsfNavPathParams(C.Structure):
+    """ssf_navpath_params (include/ssf_navpath.h)"""
+    _fields_ = [(nm, C.c_int) for nm in ("width", "height", "min_dist2", "allow_unknown", "los_dist2", "keep_clearance", "clearance_cap", "lookahead",
+                                         "n_paths", "max_path", "max_waypoints", "on_device")]
+
+
+class SsfNavPathOut(C.Structure):
+    """ssf_navpath_out (include/ssf_navpath.h)"""
+    _fields_ = [(nm, C.c_void_p) for nm in NAVPATH_OUTPUT_NAMES]
+
+
+class SsfNavPathStats(C.Structure):
+    """ssf_navpath_stats (include/ssf_navpath.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("paths_ok", "paths_bad", "paths_truncated", "waypoints", "forced_steps", "cells_in", "segments_tested")]
+
+    def as_dict(self):
+        return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
+
+
 class SsfRaycastParams(C.Structure):
     """ssf_raycast_params (include/ssf_raycast.h)"""
     _fields_ = [("pose", C.c_void_p), ("t_min", C.c_float), ("t_max", C.c_float), ("min_conf", C.c_float), ("splat_scale", C.c_float),
@@ -507,6 +533,10 @@ class Library:
             L.ssf_navfrontier_default_params.argtypes = [vp, C.POINTER(SsfNavFrontierParams)]
             L.ssf_navfrontier_regions.argtypes = [vp, C.POINTER(SsfNavFrontierParams), vp, vp, vp, C.POINTER(SsfNavFrontierOut),
                                                   C.POINTER(SsfNavFrontierStats)]
+        self.has_navpath = all(hasattr(L, nm) for nm in NAVPATH_SYMBOLS)
+        if self.has_navpath:
+            L.ssf_navpath_default_params.argtypes = [vp, C.POINTER(SsfNavPathParams)]
+            L.ssf_navpath_waypoints.argtypes = [vp, C.POINTER(SsfNavPathParams), vp, vp, vp, vp, C.POINTER(SsfNavPathOut), C.POINTER(SsfNavPathStats)]
         self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
         if self.has_navgrid:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
@@ -621,6 +651,14 @@ def load_explore():
     nav_frontiers or nav_explore on it.  Fails loudly when it has not been built."""
     import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
     return Library(EXPLORE_LIB)
+
+
+def load_drive():
+    """Load libssf_hip_drive.so: explore's objects (the product, the carve, the plan, the frontier regions) with the waypoints linked
+    in (include/ssf_navpath.h).  A handle belongs to the library that created it: create the Fusion from THIS library to call
+    nav_waypoints or nav_plan_waypoints on it.  Fails loudly when it has not been built."""
+    import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
+    return Library(DRIVE_LIB)
 
 
 def load_lab():
@@ -1584,6 +1622,129 @@ class Fusion:
             out.update(chosen=c, goal=goal, cost=int(drive["start_cost"][0]), status=int(drive["start_status"][0]), path=drive["path"][0],
                        path_stats=drive["stats"])
         return out
+
+    # ---- any-angle waypoints from the plan's cell paths (include/ssf_navpath.h) -----------------------
+    def _need_navpath(self, symbol):
+        if not self.L.has_navpath:
+            raise SsfError("%s does not export %s: it refines no path (include/ssf_navpath.h: libssf_hip_drive.so, binding.load_drive)"
+                           % (self.L.path, symbol))
+
+    def _navpath_params(self, on_device, width, height, n_paths, max_path, params):
+        """SsfNavPathParams: the fields of ssf_navpath_params by name, each at ssf_navpath_default_params' value when missing;
+        max_waypoints defaults to max_path (no path has more waypoints than cells)"""
+        p = SsfNavPathParams()
+        self._ck(self.L.lib.ssf_navpath_default_params(self.h, C.byref(p)), "ssf_navpath_default_params")
+        kinds = dict(p._fields_)
+        for nm, val in params.items():
+            if nm not in kinds or nm in ("width", "height", "n_paths", "max_path", "on_device"):
+                raise SsfError("unknown waypoint parameter %r" % nm)
+            setattr(p, nm, int(val))
+        p.width, p.height, p.n_paths, p.max_path, p.on_device = int(width), int(height), int(n_paths), int(max_path), int(bool(on_device))
+        if "max_waypoints" not in params:
+            p.max_waypoints = p.max_path
+        return p
+
+    def _navpath_waypoints(self, p, state, dist2, path, path_len, ptrs):
+        st = SsfNavPathStats()
+        out = SsfNavPathOut(*[ptrs.get(nm) for nm in NAVPATH_OUTPUT_NAMES])
+        self._ck(self.L.lib.ssf_navpath_waypoints(self.h, C.byref(p), state, dist2, path, path_len, C.byref(out), C.byref(st)), "ssf_navpath_waypoints")
+        return st.as_dict()
+
+    def nav_waypoints(self, state, dist2, path, path_len=None, outputs=NAVPATH_OUTPUT_NAMES, **params):
+        """The cell paths of a plan reduced to any-angle waypoints (ssf_navpath_waypoints).  state H x W int8 and dist2 H x W int32
+        as nav_grid / nav_grid_carve return them; path: n x max_path x 2 int32 with path_len (n), or a list of (len, 2) arrays as
+        nav_plan returns it (path_len None).  Returns a dict of the requested outputs -- n_waypoints (n i32), status (n i32),
+        waypoints: a list with one (n_waypoints, 4) int32 array per path, (ix, iy, index | NAVPATH_FORCED, seg_min), path_min
+        (n i32) -- and 'stats'.  params: min_dist2, allow_unknown, los_dist2, keep_clearance, clearance_cap, lookahead,
+        max_waypoints (default: max_path)."""
+        self._need_navpath("ssf_navpath_waypoints")
+        bad = [nm for nm in outputs if nm not in NAVPATH_OUTPUT_NAMES]
+        if bad:
+            raise SsfError("unknown waypoint outputs %s (known: %s)" % (bad, ", ".join(NAVPATH_OUTPUT_NAMES)))
+        state, dist2 = np.ascontiguousarray(state, np.int8), np.ascontiguousarray(dist2, np.int32)
+        if state.ndim != 2 or dist2.shape != state.shape:
+            raise SsfError("state and dist2 are H x W arrays of one shape, got %s and %s" % (state.shape, dist2.shape))
+        if path_len is None:
+            cells = [self._cell_list(c, "a path's cells") for c in path]
+            path_len = np.array([len(c) for c in cells], np.int32)
+            path = np.zeros((len(cells), max(1, int(path_len.max()) if len(cells) else 1), 2), np.int32)
+            for i, c in enumerate(cells):
+                path[i, :len(c)] = c
+        path, path_len = np.ascontiguousarray(path, np.int32), np.ascontiguousarray(path_len, np.int32)
+        if path.ndim != 3 or path.shape[2] != 2 or path_len.shape != (path.shape[0],):
+            raise SsfError("path is n x max_path x 2 and path_len n, got %s and %s" % (path.shape, path_len.shape))
+        H, W = state.shape
+        n, mp = path.shape[0], path.shape[1]
+        p = self._navpath_params(False, W, H, n, mp, params)
+        mw = min(max(p.max_waypoints, 0), 1 << 20)
+        shapes = dict(n_waypoints=((n,), np.int32), status=((n,), np.int32), waypoints=((n, mw, 4), np.int32), path_min=((n,), np.int32))
+        want = set(outputs)
+        if "waypoints" in want:
+            want.add("n_waypoints")                  # (the counts cut the lists)
+        out = {nm: np.zeros(*shapes[nm]) for nm in NAVPATH_OUTPUT_NAMES if nm in want}
+        stats = self._navpath_waypoints(p, _ptr(state), _ptr(dist2), _ptr(path), _ptr(path_len), {nm: _ptr(a) for nm, a in out.items()})
+        if "waypoints" in out:
+            out["waypoints"] = [out["waypoints"][i, :out["n_waypoints"][i]].copy() for i in range(n)]
+        if "n_waypoints" not in outputs:
+            out.pop("n_waypoints", None)
+        out["stats"] = stats
+        return out
+
+    def nav_waypoints_device(self, state, dist2, width, height, path, path_len, n_paths, max_path, n_waypoints=None, status=None, waypoints=None,
+                             path_min=None, **params):
+        """ssf_navpath_waypoints on device memory: state, dist2, path, path_len and each output are a contiguous torch tensor on the
+        device or the device address (int) of a buffer of the shape and dtype nav_waypoints works on (waypoints: n_paths x
+        max_waypoints x 4 int32; outputs may be None).  Returns the stats dict."""
+        self._need_navpath("ssf_navpath_waypoints")
+        p = self._navpath_params(True, width, height, n_paths, max_path, params)
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        return self._navpath_waypoints(p, addr(state), addr(dist2), addr(path), addr(path_len),
+                                       dict(n_waypoints=addr(n_waypoints), status=addr(status), waypoints=addr(waypoints), path_min=addr(path_min)))
+
+    def nav_waypoints_default_params(self):
+        """ssf_navpath_default_params as a dict"""
+        self._need_navpath("ssf_navpath_default_params")
+        p = SsfNavPathParams()
+        self._ck(self.L.lib.ssf_navpath_default_params(self.h, C.byref(p)), "ssf_navpath_default_params")
+        return {nm: getattr(p, nm) for nm, _ in p._fields_}
+
+    def nav_plan_waypoints(self, state, dist2, goals=None, starts=None, plan=None, waypoints=None):
+        """Plan and refine without the paths leaving the device: state and dist2 (host arrays) are uploaded once, nav_plan_device
+        writes the field's paths into device tensors and nav_waypoints_device reads them there.  plan: the plan's parameters
+        (max_path defaults to width * height capped at 1 << 20); waypoints: the waypoints' parameters (min_dist2 and allow_unknown
+        default to the plan's; max_waypoints to 4096 or max_path, whichever is less).  Returns a dict: 'plan' (start_cost,
+        start_status, path_len, path, stats, as nav_plan) and 'waypoints' (nav_waypoints' dict)."""
+        import torch
+        self._need_navplan("ssf_navplan_field")
+        self._need_navpath("ssf_navpath_waypoints")
+        plan, wq = dict(plan or {}), dict(waypoints or {})
+        state, dist2 = np.ascontiguousarray(state, np.int8), np.ascontiguousarray(dist2, np.int32)
+        if state.ndim != 2 or dist2.shape != state.shape:
+            raise SsfError("state and dist2 are H x W arrays of one shape, got %s and %s" % (state.shape, dist2.shape))
+        H, W = state.shape
+        s = self._cell_list(starts, "starts")
+        n = len(s)
+        if n < 1:
+            raise SsfError("nav_plan_waypoints needs a start")
+        mp = int(plan.setdefault("max_path", min(W * H, 1 << 20)))
+        for nm in ("min_dist2", "allow_unknown"):
+            wq.setdefault(nm, plan.get(nm, 0))
+        mw = int(wq.setdefault("max_waypoints", max(1, min(4096, mp))))
+        dev = torch.device("cuda")
+        d_state, d_dist2 = torch.from_numpy(state).to(dev), torch.from_numpy(dist2).to(dev)
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        t = dict(start_cost=i32(n), start_status=i32(n), path_len=i32(n), path=i32(n, max(mp, 1), 2))
+        plan_stats = self.nav_plan_device(d_state, d_dist2, W, H, goals, s, **dict(t, **plan))
+        o = dict(n_waypoints=i32(n), status=i32(n), waypoints=i32(n, max(mw, 1), 4), path_min=i32(n))
+        wp_stats = self.nav_waypoints_device(d_state, d_dist2, W, H, t["path"], t["path_len"], n, mp, **dict(o, **wq))
+        got = {nm: a.cpu().numpy() for nm, a in t.items()}
+        got["start_cost"] = got["start_cost"].view(np.uint32)
+        got["path"] = [got["path"][i, :got["path_len"][i]].copy() for i in range(n)]
+        got["stats"] = plan_stats
+        ref = {nm: a.cpu().numpy() for nm, a in o.items()}
+        ref["waypoints"] = [ref["waypoints"][i, :ref["n_waypoints"][i]].copy() for i in range(n)]
+        ref["stats"] = wp_stats
+        return dict(plan=got, waypoints=ref)
 
     # ---- rays cast through the model: the first disc each ray hits (include/ssf_raycast.h) ------------
     def _need_raycast(self, symbol):

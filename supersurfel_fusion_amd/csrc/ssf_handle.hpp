@@ -365,6 +365,17 @@ struct NavFrontierWs {
     void* acc = nullptr; uint32_t* region_blocks = nullptr; size_t regions = 0;
     void* table = nullptr; unsigned long long* stats = nullptr;
 };
+// ssf_navpath_waypoints (ssf_navpath.h, ssf_navpath.hip: linked into libssf_hip_drive.so only): per cell the grid as the call got it
+// (the copies of host arrays) and the packed (traversable, d) word; per path (4096) the length, status, waypoint count and minimum;
+// the paths and the waypoints of a call with host arrays; the sums.  Allocated on first use; each group is grown as a whole or not
+// at all (DevBufs::grow).  Nothing here is read or written by the frame path.
+struct NavPathWs {
+    DevBufs bufs;
+    int8_t* state = nullptr; int32_t* dist2 = nullptr; uint32_t* pk = nullptr; size_t cells = 0;
+    int32_t* path_len = nullptr; int32_t* status = nullptr; int32_t* n_wp = nullptr; int32_t* path_min = nullptr; unsigned long long* stats = nullptr;
+    int32_t* path = nullptr; size_t path_words = 0;
+    int32_t* wp = nullptr; size_t wp_words = 0;
+};
 // ssf_raycast (ssf_raycast.h): the resident index -- per slot the 64-byte record and the box of cells with the row's class, the
 // out-of-view blocks' live offsets, the oversize list; per bucket (+ 1) the list offsets and the fill's cursors; the (bucket -> slot)
 // lists; the sums and the box of indexed cells -- and the staging buffer of a call's host rays and outputs.  The index is valid
@@ -493,6 +504,7 @@ struct ssf_handle {
     NavCarveWs navcarve;                          // ssf_navgrid_carve (ssf_navcarve.h)
     NavPlanWs navplan;                            // ssf_navplan_field (ssf_navplan.h)
     NavFrontierWs navfrontier;                    // ssf_navfrontier_regions (ssf_navfrontier.h)
+    NavPathWs navpath;                            // ssf_navpath_waypoints (ssf_navpath.h)
     RaycastWs raycast;                            // ssf_raycast (ssf_raycast.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense); the out-of-view
                                                   // compaction keeps rows and order but moves slots: who keeps slot numbers also watches n_recentres (RaycastWs)

@@ -217,7 +217,7 @@ def plan_cells(pose, res, cam_t, goals_m):
     return start, goals
 
 
-def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, plan=None, frontiers=None):
+def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, plan=None, frontiers=None, waypoints=None):
     """the navigation grid of the map, built on the device (include/ssf_navgrid.h) at the default size and frame (floor-aligned
     about the tracked camera) with cells of `res` metres: grid_dir/<k as %06d>.pgm -- the state in map_server's convention (205
     unknown, 254 free, 0 occupied; the image's top row is the grid's last) --, <k>.yaml beside it (map_server's keys; origin = the
@@ -229,7 +229,10 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
     <k>_path.npy (the cells (ix, iy) from the camera's cell to the goal) and <k>_plan.json (the stats, the start and its status).
     frontiers (dict(min_cells, gain_radius)): the grid's frontier as regions (include/ssf_navfrontier.h), ranked by the cost of
     driving to them from the camera's cell for a robot of the plan's radius (0 without a plan): <k>_frontiers.json (regions = the
-    table's records, order, stats, start) and <k>_frontier_regions.npy (the map: table index, -1 no member, -2 not in the table)"""
+    table's records, order, stats, start) and <k>_frontier_regions.npy (the map: table index, -1 no member, -2 not in the table).
+    waypoints (dict(lookahead=cells, los_radius=metres), with a plan only): the plan's path reduced to any-angle waypoints
+    (include/ssf_navpath.h) that keep the path's clearance up to the squared los_radius and at least that: <k>_waypoints.npy ((n, 4)
+    int32: ix, iy, index into the path with bit 30 on a forced step, seg_min) and <k>_waypoints.json (stats, status, path_min)"""
     if carve_views is None:
         out = fusion.nav_grid(outputs=("state", "dist2"), res=res)
     else:
@@ -260,6 +263,14 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
         with open(os.path.join(grid_dir, name + "_plan.json"), "w") as f:
             json.dump(dict(got["stats"], start=[int(v) for v in start[0]], start_status=int(got["start_status"][0]),
                            start_cost=int(got["start_cost"][0]), min_dist2=cells * cells), f, sort_keys=True)
+        if waypoints is not None:
+            los = int(np.ceil(float(waypoints.get("los_radius") or 0.0) / res))
+            kw = dict(min_dist2=cells * cells, los_dist2=los * los, keep_clearance=1, clearance_cap=min(los * los, 1024 * 1024),
+                      lookahead=int(waypoints.get("lookahead", 256)))
+            wp = fusion.nav_waypoints(state, out["dist2"], [got["path"][0]], **kw)
+            np.save(os.path.join(grid_dir, name + "_waypoints.npy"), wp["waypoints"][0])
+            with open(os.path.join(grid_dir, name + "_waypoints.json"), "w") as f:
+                json.dump(dict(wp["stats"], status=int(wp["status"][0]), path_min=int(wp["path_min"][0]), **kw), f, sort_keys=True)
     if frontiers is not None:
         import json
         start, _ = plan_cells(pose, res, fusion.get_pose()[9:12], [])
@@ -307,7 +318,7 @@ def write_laser_scan(fusion, scan_dir, k, beams):
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
            keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30, detect_motion=False,
            motion_mask_dir=None, odometry_prior=False, nav_grid_dir=None, nav_grid_every=30, nav_grid_res=0.05,
-           nav_grid_carve=False, nav_grid_carve_stride=8, nav_plan=None, nav_frontiers=None, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
+           nav_grid_carve=False, nav_grid_carve_stride=8, nav_plan=None, nav_frontiers=None, nav_waypoints=None, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
@@ -322,7 +333,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     is carved along the rays of the poses estimated so far (thin_views: at most 256 of them) on a pixel lattice of
     nav_grid_carve_stride, and <k>_seen.npy is written as well.  nav_plan (write_nav_grid's plan): the field, path and stats of a
     plan from the camera's cell are written next to each grid.  nav_frontiers (write_nav_grid's frontiers): the frontier regions
-    of each grid, ranked from the camera's cell, are written next to it.
+    of each grid, ranked from the camera's cell, are written next to it.  nav_waypoints (write_nav_grid's waypoints; needs nav_plan):
+    the plan's path reduced to waypoints is written next to it.
     laser_scan_dir: after frames 0, laser_scan_every, 2 laser_scan_every, ... a planar scan of laser_scan_beams beams from the tracked
     pose is written (write_laser_scan, numbered by frame); pipelined, submission pauses as for a render.
     keyframes: a dict of ssf_keyframes_params fields ({} = the defaults): the keyframe database is configured and
@@ -339,6 +351,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
         raise ValueError("nav_grid_carve needs nav_grid_dir")
     if nav_plan is not None and not nav_grid_dir:
         raise ValueError("nav_plan needs nav_grid_dir")
+    if nav_waypoints is not None and nav_plan is None:
+        raise ValueError("nav_waypoints needs nav_plan")
     if nav_frontiers is not None and not nav_grid_dir:
         raise ValueError("nav_frontiers needs nav_grid_dir")
     carve_views = (lambda: [r["pose"] for r in results]) if nav_grid_carve else (lambda: None)
@@ -391,7 +405,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             if local_cloud_dir and (len(lines) - 1) % local_cloud_every == 0:
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
-                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan, nav_frontiers)
+                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan, nav_frontiers,
+                               nav_waypoints)
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     else:
@@ -423,7 +438,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             if local_cloud_dir and (len(lines) - 1) % local_cloud_every == 0:
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
-                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan, nav_frontiers)
+                write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan, nav_frontiers,
+                               nav_waypoints)
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     if out_path:
@@ -566,6 +582,12 @@ def parse_args(argv=None):
     ap.add_argument("--nav-plan-frontier", action="store_true", help="with --nav-grid-dir: every frontier cell of the grid is a goal")
     ap.add_argument("--nav-plan-radius", type=float, default=0.0, metavar="R",
                     help="the robot's radius in metres: cells with less clearance are not traversable (min_dist2 = ceil(R / res)^2)")
+    ap.add_argument("--nav-plan-waypoints", action="store_true",
+                    help="with --nav-plan-goal or --nav-plan-frontier: the plan's path reduced to any-angle waypoints on the device; "
+                         "_waypoints.npy and _waypoints.json are written next to the plan's files")
+    ap.add_argument("--nav-plan-lookahead", type=int, default=None, metavar="N", help="cells of the path looked ahead per waypoint, 1..4096 (default 256)")
+    ap.add_argument("--nav-plan-los-radius", type=float, default=None, metavar="R",
+                    help="metres: every cell of a straight leg keeps this clearance where the path has it (default 0)")
     ap.add_argument("--nav-frontiers", action="store_true",
                     help="with --nav-grid-dir: the frontier of every grid as regions, ranked by the cost of driving to them from the camera's "
                          "cell; _frontiers.json (table, order, stats) and _frontier_regions.npy (the map) are written next to the grid")
@@ -600,6 +622,14 @@ def parse_args(argv=None):
         ap.error("--nav-plan-goal and --nav-plan-frontier need --nav-grid-dir")
     if a.nav_plan_radius < 0.0 or (a.nav_plan_radius > 0.0 and not (a.nav_plan_goal or a.nav_plan_frontier)):
         ap.error("--nav-plan-radius is >= 0 and goes with --nav-plan-goal or --nav-plan-frontier")
+    if a.nav_plan_waypoints and not (a.nav_plan_goal or a.nav_plan_frontier):
+        ap.error("--nav-plan-waypoints goes with --nav-plan-goal or --nav-plan-frontier")
+    if (a.nav_plan_lookahead is not None or a.nav_plan_los_radius is not None) and not a.nav_plan_waypoints:
+        ap.error("--nav-plan-lookahead and --nav-plan-los-radius go with --nav-plan-waypoints")
+    if a.nav_plan_lookahead is not None and not 1 <= a.nav_plan_lookahead <= 4096:
+        ap.error("--nav-plan-lookahead is 1..4096")
+    if a.nav_plan_los_radius is not None and a.nav_plan_los_radius < 0.0:
+        ap.error("--nav-plan-los-radius is >= 0")
     if a.nav_frontiers and not a.nav_grid_dir:
         ap.error("--nav-frontiers needs --nav-grid-dir")
     if (a.nav_frontier_min_cells is not None or a.nav_frontier_gain_radius is not None) and not a.nav_frontiers:
@@ -618,6 +648,14 @@ def nav_plan_of(a):
     return dict(goals=[tuple(g) for g in (a.nav_plan_goal or [])], frontier=bool(a.nav_plan_frontier), radius=float(a.nav_plan_radius))
 
 
+def nav_waypoints_of(a):
+    """replay()'s nav_waypoints from the parsed options, or None"""
+    if not a.nav_plan_waypoints:
+        return None
+    return dict(lookahead=256 if a.nav_plan_lookahead is None else int(a.nav_plan_lookahead),
+                los_radius=0.0 if a.nav_plan_los_radius is None else float(a.nav_plan_los_radius))
+
+
 def nav_frontiers_of(a):
     """replay()'s nav_frontiers from the parsed options, or None"""
     if not a.nav_frontiers:
@@ -629,9 +667,9 @@ def nav_frontiers_of(a):
 def main():
     a = parse_args()
     from . import binding
-    plan, frontiers = nav_plan_of(a), nav_frontiers_of(a)
-    # (the carve's, the plan's and the regions' entry points: libraries of their own)
-    lib = binding.load_explore() if frontiers else (binding.load_nav() if plan else (binding.load_navcarve() if a.nav_grid_carve else binding.load_product()))
+    plan, frontiers, waypoints = nav_plan_of(a), nav_frontiers_of(a), nav_waypoints_of(a)
+    # (the carve's, the plan's, the regions' and the waypoints' entry points: libraries of their own)
+    lib = binding.load_drive() if waypoints else binding.load_explore() if frontiers else (binding.load_nav() if plan else (binding.load_navcarve() if a.nav_grid_carve else binding.load_product()))
     cfg = lib.default_config(pipeline_depth=2 if a.pipelined else 0, extract_batch=4 if a.pipelined else 1, **BENCHMARK_LAUNCH)
     f = binding.Fusion(lib, cfg)
     if a.raw_frames:
@@ -644,7 +682,7 @@ def main():
                         keyframe_log=a.keyframe_log, detect_motion=a.detect_motion, motion_mask_dir=a.motion_mask_dir,
                         odometry_prior=a.odometry_prior, nav_grid_dir=a.nav_grid_dir, nav_grid_every=a.nav_grid_every,
                         nav_grid_res=a.nav_grid_res, nav_grid_carve=a.nav_grid_carve, nav_grid_carve_stride=a.nav_grid_carve_stride, nav_plan=plan,
-                        nav_frontiers=frontiers,
+                        nav_frontiers=frontiers, nav_waypoints=waypoints,
                         laser_scan_dir=a.laser_scan_dir, laser_scan_every=a.laser_scan_every,
                         laser_scan_beams=a.laser_scan_beams)
     if a.keyframes and not a.keyframe_log:
