@@ -29,6 +29,7 @@
 #include "ssf_navplan.h"
 #include "ssf_navfrontier.h"
 #include "ssf_navpath.h"
+#include "ssf_navlive.h"
 #include "ssf_raycast.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
@@ -347,6 +348,27 @@ struct NavWaypoints {
     std::vector<std::vector<Waypoint> > waypoints;
     std::vector<int32_t> status, path_min;
     ssf_navpath_stats stats;
+};
+
+/* overlayDepthFrame (ssf_navlive.h; exported by libssf_hip_live.so, linked INSTEAD of the other libraries -- a program that does not
+ * call it links as before: the inline member leaves no reference behind): the depth frame of the instant stamped onto a grid.  The
+ * members start at ssf_navlive_default_params' values: cam_pose nullptr = the tracked pose, width 0 = the configured camera and its
+ * intrinsics, t_min = t_max = 0 = the configured depth range.  The grid's size, res and frame are the input grid's. */
+struct LiveParams {
+    const Transform3* cam_pose = nullptr;          /* camera-to-map of the depth frame */
+    float fx = 0.f, fy = 0.f, cx = 0.f, cy = 0.f; int width = 0, height = 0;
+    float t_min = 0.f, t_max = 0.f;
+    float floor_max = -0.8f, z_max = 0.5f;         /* the band of the robot's body, as the grid was built with */
+    int max_dist_cells = 40; bool unknown_is_obstacle = false;
+    int mask_mode = 0;                             /* 0 no mask; 1 only pixels with mask != 0 stamp; 2 only pixels with mask == 0 */
+    int min_hits = 4, stride = 4; float hit_margin_cells = 1.f; int min_seen = 1; bool open_unknown = true;
+    bool want_hits = true, want_seen = true, want_dist2 = true;      /* false: not produced (its vector stays empty) */
+};
+/* a NavGrid whose state and dist2 hold the live layer, with the frame's points and ray entries per cell; stats.pose and the cell
+ * counts of stats are the live grid's, zmin / zmax / hits stay empty */
+struct LiveNavGrid : NavGrid {
+    std::vector<uint32_t> live_hits, live_seen;
+    ssf_navlive_stats live;
 };
 
 /* castRays (ssf_raycast.h; exported by libssf_hip.so only): the first disc of the map that each ray hits.  The members start at
@@ -788,6 +810,75 @@ public:
         else { const double s = 2.0 * std::sqrt(1.0 + m22 - m00 - m11); qw = (m10 - m01) / s; qx = (m02 + m20) / s; qy = (m12 + m21) / s; qz = 0.25 * s; }
         msg.info.origin.orientation.x = qx; msg.info.origin.orientation.y = qy; msg.info.origin.orientation.z = qz; msg.info.origin.orientation.w = qw;
     }
+    /* The depth frame of the instant stamped onto a grid that buildNavGrid made, plain or carved, or onto an earlier live grid
+     * (ssf_navlive.h): cells in which the frame's points lie in the band of the robot's body become occupied, unknown cells the
+     * sensor looked through become free, and dist2 is recomputed.  g needs its state and stats.pose (its frame); depth is width x
+     * height of the camera in the input format (float metres, or after setInputFormat uint16 counts); mask: empty, or one byte per
+     * pixel for q.mask_mode (detectMotion's mask plugs in).  fillOccupancyGrid and planOnGrid take out as it is. */
+    void overlayDepthFrame(const NavGrid& g, const LiveParams& q, const std::vector<float>& depth_m, const std::vector<uint8_t>& mask, LiveNavGrid& out) {
+        if (depth_u16_) throw std::logic_error("overlayDepthFrame: the input format is uint16 depth; pass the counts as std::vector<uint16_t>");
+        overlay_depth(g, q, depth_m.data(), depth_m.size(), mask, out);
+    }
+    void overlayDepthFrame(const NavGrid& g, const LiveParams& q, const std::vector<uint16_t>& depth_counts, const std::vector<uint8_t>& mask,
+                           LiveNavGrid& out) {
+        if (!depth_u16_) throw std::logic_error("overlayDepthFrame(uint16_t depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+        overlay_depth(g, q, depth_counts.data(), depth_counts.size(), mask, out);
+    }
+#if defined(CV_VERSION) && defined(CV_32FC1) && defined(CV_8UC1)
+    /* ... with the depth as CV_32FC1 (or, after setInputFormat, CV_16UC1) and the mask as CV_8UC1 (an empty Mat = no mask) */
+    void overlayDepthFrame(const NavGrid& g, const LiveParams& q, const cv::Mat& depth_h, const cv::Mat& mask_h, LiveNavGrid& out) {
+        const cv::Mat d = depth_h.isContinuous() ? depth_h : depth_h.clone(), m = mask_h.isContinuous() ? mask_h : mask_h.clone();
+        const size_t n = (size_t)d.rows * (size_t)d.cols;
+        const bool masked = m.rows != 0 || m.cols != 0;
+        if (masked && (m.type() != CV_8UC1 || m.rows != d.rows || m.cols != d.cols)) throw std::invalid_argument("overlayDepthFrame: the mask must be CV_8UC1 of the depth image's size");
+        std::vector<uint8_t> mk;
+        if (masked) mk.assign(m.ptr<uint8_t>(), m.ptr<uint8_t>() + n);
+#ifdef CV_16UC1
+        if (d.type() == CV_16UC1) {
+            if (!depth_u16_) throw std::logic_error("overlayDepthFrame(CV_16UC1 depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+            overlay_depth(g, q, d.ptr<uint16_t>(), n, mk, out);
+            return;
+        }
+#endif
+        if (d.type() != CV_32FC1) throw std::invalid_argument("overlayDepthFrame: the depth image must be CV_32FC1 or CV_16UC1");
+        if (depth_u16_) throw std::logic_error("overlayDepthFrame: the input format is uint16 depth; pass a CV_16UC1 image");
+        overlay_depth(g, q, d.ptr<float>(), n, mk, out);
+    }
+#endif
+private:
+    void overlay_depth(const NavGrid& g, const LiveParams& q, const void* depth, size_t n_depth, const std::vector<uint8_t>& mask, LiveNavGrid& out) {
+        const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
+        if (n == 0 || g.state.size() != n) throw std::logic_error("overlayDepthFrame: the grid has no state (want_state)");
+        const size_t npix = q.width > 0 ? (size_t)q.width * (size_t)(q.height > 0 ? q.height : 0) : (size_t)width_ * (size_t)height_;
+        if (n_depth != npix) throw std::invalid_argument("overlayDepthFrame: the depth image must be width x height of the camera");
+        if (!mask.empty() && mask.size() != npix) throw std::invalid_argument("overlayDepthFrame: the mask must be width x height of the camera");
+        ssf_navlive_params p;
+        check(ssf_navlive_default_params(need(), &p));
+        float cam[12];
+        if (q.cam_pose) { transform3_to_rt(*q.cam_pose, cam); p.cam_pose = cam; }
+        p.grid_pose = g.stats.pose; p.width = g.width; p.height = g.height; p.res = g.res;
+        p.floor_max = q.floor_max; p.z_max = q.z_max; p.max_dist_cells = q.max_dist_cells; p.unknown_is_obstacle = q.unknown_is_obstacle ? 1 : 0;
+        p.fx = q.fx; p.fy = q.fy; p.cx = q.cx; p.cy = q.cy; p.cam_width = q.width; p.cam_height = q.height; p.t_min = q.t_min; p.t_max = q.t_max;
+        p.mask_mode = q.mask_mode; p.min_hits = q.min_hits; p.stride = q.stride; p.hit_margin_cells = q.hit_margin_cells; p.min_seen = q.min_seen;
+        p.open_unknown = q.open_unknown ? 1 : 0; p.on_device = 0; p.frame_on_device = 0;
+        std::vector<int8_t> state(n);                             /* (g may be out itself) */
+        std::vector<uint32_t> hits(q.want_hits ? n : 0), seen(q.want_seen ? n : 0);
+        std::vector<int32_t> dist2(q.want_dist2 ? n : 0);
+        ssf_navlive_out o;
+        o.live_hits = q.want_hits ? hits.data() : nullptr; o.live_seen = q.want_seen ? seen.data() : nullptr;
+        o.state = state.data(); o.dist2 = q.want_dist2 ? dist2.data() : nullptr;
+        ssf_navlive_stats st;
+        check(ssf_navlive_overlay(need(), &p, depth, mask.empty() ? nullptr : mask.data(), g.state.data(), &o, &st));
+        out.width = g.width; out.height = g.height; out.res = g.res;
+        out.zmin.clear(); out.zmax.clear(); out.hits.clear();
+        out.state.swap(state); out.dist2.swap(dist2); out.live_hits.swap(hits); out.live_seen.swap(seen);
+        out.live = st;
+        ssf_navgrid_stats gs = ssf_navgrid_stats();
+        gs.cells_free = st.cells_free; gs.cells_occupied = st.cells_occupied; gs.cells_unknown = st.cells_unknown;
+        std::copy(st.pose, st.pose + 12, gs.pose);
+        out.stats = gs;
+    }
+public:
     /* Plan on a grid that buildNavGrid made (ssf_navplan.h), plain or carved: the cost-to-goal field over the cells a robot of
      * squared radius q.min_dist2 can be in, for `goals` (and, with goals_from_frontier, the grid's frontier), and for every start
      * its cost, status and path.  The grid needs its state and dist2 (want_state, want_dist2). */

@@ -26,6 +26,9 @@ EXPLORE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_explore.so")
 # explore's objects and the waypoints of the plan's paths (include/ssf_navpath.h): the one library of a robot that builds, carves, plans,
 # explores and drives.  None of the four libraries above exports the waypoints' entry points
 DRIVE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_drive.so")
+# drive's objects and the live obstacle layer (include/ssf_navlive.h): the one library of a robot that also stamps the depth frame of
+# the instant onto its grid.  None of the five libraries above exports the overlay's entry points
+LIVE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_live.so")
 
 
 class SsfConfig(C.Structure):
@@ -136,6 +139,10 @@ NAVFRONTIER_REGION_DTYPE = np.dtype([("sum_x", np.int64), ("sum_y", np.int64), (
 NAVPATH_SYMBOLS = ["ssf_navpath_default_params", "ssf_navpath_waypoints"]
 NAVPATH_OUTPUT_NAMES = ("n_waypoints", "status", "waypoints", "path_min")
 NAVPATH_FORCED = 1 << 30             # bit 30 of a waypoint's index word: the segment that leads to it was not visible
+# the live obstacle layer (include/ssf_navlive.h): exported by libssf_hip_live.so only (load_live)
+NAVLIVE_SYMBOLS = ["ssf_navlive_default_params", "ssf_navlive_overlay"]
+NAVLIVE_OUTPUTS = (("live_hits", np.uint32), ("live_seen", np.uint32), ("state", np.int8), ("dist2", np.int32))
+NAVLIVE_OUTPUT_NAMES = tuple(nm for nm, _ in NAVLIVE_OUTPUTS)
 # rays cast through the model (include/ssf_raycast.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 RAYCAST_SYMBOLS = ["ssf_raycast_default_params", "ssf_raycast"]
 # the output arrays of ssf_raycast, in its argument order: name, dtype, per-ray shape
@@ -351,6 +358,33 @@ class SsfNavPathStats(C.Structure):
         return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
 
 
+class SsfNavLiveParams(C.Structure):
+    """ssf_navlive_params (include/ssf_navlive.h)"""
+    _fields_ = [("grid_pose", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("res", C.c_float), ("floor_max", C.c_float),
+                ("z_max", C.c_float), ("max_dist_cells", C.c_int), ("unknown_is_obstacle", C.c_int), ("cam_pose", C.c_void_p),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("cam_width", C.c_int), ("cam_height", C.c_int),
+                ("t_min", C.c_float), ("t_max", C.c_float), ("mask_mode", C.c_int), ("min_hits", C.c_int), ("stride", C.c_int),
+                ("hit_margin_cells", C.c_float), ("min_seen", C.c_int), ("open_unknown", C.c_int), ("on_device", C.c_int),
+                ("frame_on_device", C.c_int)]
+
+
+class SsfNavLiveOut(C.Structure):
+    """ssf_navlive_out (include/ssf_navlive.h)"""
+    _fields_ = [(nm, C.c_void_p) for nm in NAVLIVE_OUTPUT_NAMES]
+
+
+class SsfNavLiveStats(C.Structure):
+    """ssf_navlive_stats (include/ssf_navlive.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("pixels_valid", "pixels_stamping", "points_in_band", "rays", "rays_carving", "ray_samples",
+                                           "ray_entries", "cells_stamped", "cells_opened", "cells_free", "cells_occupied", "cells_unknown",
+                                           "atomics")] + [("pose", C.c_float * 12)]
+
+    def as_dict(self):
+        d = {nm: int(getattr(self, nm)) for nm, _ in self._fields_ if nm != "pose"}
+        d["pose"] = np.array(self.pose, np.float32)
+        return d
+
+
 class SsfRaycastParams(C.Structure):
     """ssf_raycast_params (include/ssf_raycast.h)"""
     _fields_ = [("pose", C.c_void_p), ("t_min", C.c_float), ("t_max", C.c_float), ("min_conf", C.c_float), ("splat_scale", C.c_float),
@@ -537,6 +571,10 @@ class Library:
         if self.has_navpath:
             L.ssf_navpath_default_params.argtypes = [vp, C.POINTER(SsfNavPathParams)]
             L.ssf_navpath_waypoints.argtypes = [vp, C.POINTER(SsfNavPathParams), vp, vp, vp, vp, C.POINTER(SsfNavPathOut), C.POINTER(SsfNavPathStats)]
+        self.has_navlive = all(hasattr(L, nm) for nm in NAVLIVE_SYMBOLS)
+        if self.has_navlive:
+            L.ssf_navlive_default_params.argtypes = [vp, C.POINTER(SsfNavLiveParams)]
+            L.ssf_navlive_overlay.argtypes = [vp, C.POINTER(SsfNavLiveParams), vp, vp, vp, C.POINTER(SsfNavLiveOut), C.POINTER(SsfNavLiveStats)]
         self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
         if self.has_navgrid:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
@@ -659,6 +697,14 @@ def load_drive():
     nav_waypoints or nav_plan_waypoints on it.  Fails loudly when it has not been built."""
     import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
     return Library(DRIVE_LIB)
+
+
+def load_live():
+    """Load libssf_hip_live.so: drive's objects (the product, the carve, the plan, the frontier regions, the waypoints) with the live
+    obstacle layer linked in (include/ssf_navlive.h).  A handle belongs to the library that created it: create the Fusion from THIS
+    library to call nav_live or nav_live_plan on it.  Fails loudly when it has not been built."""
+    import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
+    return Library(LIVE_LIB)
 
 
 def load_lab():
@@ -1745,6 +1791,144 @@ class Fusion:
         ref["waypoints"] = [ref["waypoints"][i, :ref["n_waypoints"][i]].copy() for i in range(n)]
         ref["stats"] = wp_stats
         return dict(plan=got, waypoints=ref)
+
+    # ---- the live obstacle layer: the depth frame stamped onto a navigation grid (include/ssf_navlive.h) ----
+    def _need_navlive(self, symbol):
+        if not self.L.has_navlive:
+            raise SsfError("%s does not export %s: it overlays no depth frame (include/ssf_navlive.h: libssf_hip_live.so, binding.load_live)"
+                           % (self.L.path, symbol))
+
+    def _navlive_params(self, on_device, frame_on_device, grid_pose=None, cam_pose=None, **kw):
+        """(SsfNavLiveParams, the pose arrays it points into).  grid_pose: grid-to-map, what the grid's stats returned as 'pose' (None =
+        nav_grid_default_pose now); cam_pose: camera-to-map (None = the handle's pose); the other keywords are fields of
+        ssf_navlive_params by name, each at ssf_navlive_default_params' value when missing."""
+        p = SsfNavLiveParams()
+        self._ck(self.L.lib.ssf_navlive_default_params(self.h, C.byref(p)), "ssf_navlive_default_params")
+        keep = []
+        for nm, pose in (("grid_pose", grid_pose), ("cam_pose", cam_pose)):
+            if pose is not None:
+                keep.append(self._pose12(pose, nm))
+                setattr(p, nm, keep[-1].ctypes.data)
+        kinds = dict(p._fields_)
+        for nm, val in kw.items():
+            if nm not in kinds or nm in ("grid_pose", "cam_pose", "on_device", "frame_on_device"):
+                raise SsfError("unknown overlay parameter %r" % nm)
+            setattr(p, nm, float(val) if kinds[nm] is C.c_float else int(val))
+        p.on_device, p.frame_on_device = int(bool(on_device)), int(bool(frame_on_device))
+        return p, keep
+
+    def _navlive_overlay(self, p, depth, mask, state_in, ptrs):
+        st = SsfNavLiveStats()
+        out = SsfNavLiveOut(*[ptrs.get(nm) for nm in NAVLIVE_OUTPUT_NAMES])
+        self._ck(self.L.lib.ssf_navlive_overlay(self.h, C.byref(p), depth, mask, state_in, C.byref(out), C.byref(st)), "ssf_navlive_overlay")
+        return st.as_dict()
+
+    def nav_live(self, depth, state, mask=None, outputs=NAVLIVE_OUTPUT_NAMES, **kw):
+        """The depth frame of the instant stamped onto a navigation grid (ssf_navlive_overlay), host arrays.  depth: H x W in the
+        handle's input format (set_input_format); state: height x width int8 as nav_grid / nav_grid_carve or an earlier nav_live
+        returned it (it fixes width and height); mask: H x W uint8 or None (with mask_mode 1 or 2: nav_motion_mask's output plugs in
+        here).  Returns a dict of the requested outputs -- live_hits, live_seen (u32), state (i8), dist2 (i32), each height x
+        width -- and 'stats'.  Keywords: _navlive_params."""
+        self._need_navlive("ssf_navlive_overlay")
+        bad = [nm for nm in outputs if nm not in NAVLIVE_OUTPUT_NAMES]
+        if bad:
+            raise SsfError("unknown overlay outputs %s (known: %s)" % (bad, ", ".join(NAVLIVE_OUTPUT_NAMES)))
+        state = np.ascontiguousarray(state, np.int8)
+        if state.ndim != 2:
+            raise SsfError("state is a height x width array, got shape %s" % (state.shape,))
+        for nm in ("width", "height"):
+            if nm in kw:
+                raise SsfError("nav_live takes %s from state" % nm)
+        H, W = state.shape
+        p, keep = self._navlive_params(False, False, width=W, height=H, **kw)
+        cw, ch = (p.cam_width, p.cam_height) if p.cam_width else (self.W, self.H)
+        depth = np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32)
+        if depth.shape != (ch, cw):
+            raise SsfError("depth is %d x %d in the handle's input format, got shape %s" % (ch, cw, depth.shape))
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            if mask.shape != depth.shape:
+                raise SsfError("mask and depth are images of one shape, got %s and %s" % (mask.shape, depth.shape))
+        out = {nm: np.zeros((H, W), dt) for nm, dt in NAVLIVE_OUTPUTS if nm in outputs}
+        stats = self._navlive_overlay(p, _ptr(depth), _ptr(mask), _ptr(state), {nm: _ptr(a) for nm, a in out.items()})
+        out["stats"] = stats
+        return out
+
+    def nav_live_device(self, depth, state, width, height, mask=None, live_hits=None, live_seen=None, state_out=None, dist2=None,
+                        frame_on_device=True, **kw):
+        """ssf_navlive_overlay on device memory: state and each output are a contiguous torch tensor on the device or the device
+        address (int) of a buffer of the shape and dtype nav_live works on (outputs may be None, not all; state_out may be `state`
+        itself: the update in place); depth and mask likewise, or host arrays with frame_on_device=False.  Returns the stats dict."""
+        self._need_navlive("ssf_navlive_overlay")
+        p, keep = self._navlive_params(True, frame_on_device, width=width, height=height, **kw)
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        if frame_on_device:
+            d, m = addr(depth), addr(mask)
+        else:
+            depth = np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32)
+            mask = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+            d, m = _ptr(depth), _ptr(mask)
+        return self._navlive_overlay(p, d, m, addr(state), dict(live_hits=addr(live_hits), live_seen=addr(live_seen), state=addr(state_out),
+                                                                dist2=addr(dist2)))
+
+    def nav_live_default_params(self):
+        """ssf_navlive_default_params as a dict"""
+        self._need_navlive("ssf_navlive_default_params")
+        p = SsfNavLiveParams()
+        self._ck(self.L.lib.ssf_navlive_default_params(self.h, C.byref(p)), "ssf_navlive_default_params")
+        return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm not in ("grid_pose", "cam_pose")}
+
+    def nav_live_plan(self, depth, state, goals, starts, waypoints=False, mask=None, live=None, plan=None, waypoint_params=None):
+        """Overlay, plan and (waypoints=True) refine without the grid leaving the device: state (host, height x width int8) and the
+        depth frame (host array in the input format, or a device tensor) are uploaded once, nav_live_device writes the live state and
+        dist2 into device tensors, nav_plan_device plans on them and nav_waypoints_device reads its paths there.  live: the overlay's
+        keywords (_navlive_params); plan: the plan's parameters (max_path defaults to width * height capped at 1 << 20);
+        waypoint_params: the waypoints' (defaults as nav_plan_waypoints).  Returns a dict: 'live' (state, dist2, stats), 'plan'
+        (start_cost, start_status, path_len, path, stats, as nav_plan) and, with waypoints, 'waypoints' (nav_waypoints' dict)."""
+        import torch
+        self._need_navlive("ssf_navlive_overlay")
+        self._need_navplan("ssf_navplan_field")
+        if waypoints:
+            self._need_navpath("ssf_navpath_waypoints")
+        live, plan, wq = dict(live or {}), dict(plan or {}), dict(waypoint_params or {})
+        state = np.ascontiguousarray(state, np.int8)
+        if state.ndim != 2:
+            raise SsfError("state is a height x width array, got shape %s" % (state.shape,))
+        H, W = state.shape
+        s = self._cell_list(starts, "starts")
+        n = len(s)
+        if n < 1:
+            raise SsfError("nav_live_plan needs a start")
+        dev = torch.device("cuda")
+        on_dev = isinstance(depth, torch.Tensor)
+        if not on_dev:
+            depth = torch.from_numpy(np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32).view(
+                np.int16 if self.depth_format == "u16" else np.float32)).to(dev)
+        if mask is not None and not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).to(dev)
+        d_state = torch.from_numpy(state).to(dev)
+        d_dist2 = torch.empty((H, W), dtype=torch.int32, device=dev)
+        live_stats = self.nav_live_device(depth, d_state, W, H, mask=mask, state_out=d_state, dist2=d_dist2, **live)
+        mp = int(plan.setdefault("max_path", min(W * H, 1 << 20)))
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        t = dict(start_cost=i32(n), start_status=i32(n), path_len=i32(n), path=i32(n, max(mp, 1), 2))
+        plan_stats = self.nav_plan_device(d_state, d_dist2, W, H, goals, s, **dict(t, **plan))
+        got = {nm: a.cpu().numpy() for nm, a in t.items()}
+        got["start_cost"] = got["start_cost"].view(np.uint32)
+        got["path"] = [got["path"][i, :got["path_len"][i]].copy() for i in range(n)]
+        got["stats"] = plan_stats
+        res = dict(live=dict(state=d_state.cpu().numpy(), dist2=d_dist2.cpu().numpy(), stats=live_stats), plan=got)
+        if waypoints:
+            for nm in ("min_dist2", "allow_unknown"):
+                wq.setdefault(nm, plan.get(nm, 0))
+            mw = int(wq.setdefault("max_waypoints", max(1, min(4096, mp))))
+            o = dict(n_waypoints=i32(n), status=i32(n), waypoints=i32(n, max(mw, 1), 4), path_min=i32(n))
+            wp_stats = self.nav_waypoints_device(d_state, d_dist2, W, H, t["path"], t["path_len"], n, mp, **dict(o, **wq))
+            ref = {nm: a.cpu().numpy() for nm, a in o.items()}
+            ref["waypoints"] = [ref["waypoints"][i, :ref["n_waypoints"][i]].copy() for i in range(n)]
+            ref["stats"] = wp_stats
+            res["waypoints"] = ref
+        return res
 
     # ---- rays cast through the model: the first disc each ray hits (include/ssf_raycast.h) ------------
     def _need_raycast(self, symbol):

@@ -376,6 +376,16 @@ struct NavPathWs {
     int32_t* path = nullptr; size_t path_words = 0;
     int32_t* wp = nullptr; size_t wp_words = 0;
 };
+// ssf_navlive_overlay (ssf_navlive.h, ssf_navlive.hip: linked into libssf_hip_live.so only): per cell the points and the ray entries of
+// the frame, the column distances of the clearance and the state when the caller did not ask for it (11 bytes); the sums; the staging
+// buffer of host arrays (depth, mask, state_in and the outputs).  Allocated on first use; each group is grown as a whole or not at
+// all (DevBufs::grow).  Nothing here is read or written by the frame path.
+struct NavLiveWs {
+    DevBufs bufs;
+    uint32_t* hits = nullptr; uint32_t* seen = nullptr; uint16_t* colg = nullptr; int8_t* state = nullptr; size_t cells = 0;
+    unsigned long long* stats = nullptr;
+    unsigned char* img = nullptr; size_t img_bytes = 0;
+};
 // ssf_raycast (ssf_raycast.h): the resident index -- per slot the 64-byte record and the box of cells with the row's class, the
 // out-of-view blocks' live offsets, the oversize list; per bucket (+ 1) the list offsets and the fill's cursors; the (bucket -> slot)
 // lists; the sums and the box of indexed cells -- and the staging buffer of a call's host rays and outputs.  The index is valid
@@ -505,6 +515,7 @@ struct ssf_handle {
     NavPlanWs navplan;                            // ssf_navplan_field (ssf_navplan.h)
     NavFrontierWs navfrontier;                    // ssf_navfrontier_regions (ssf_navfrontier.h)
     NavPathWs navpath;                            // ssf_navpath_waypoints (ssf_navpath.h)
+    NavLiveWs navlive;                            // ssf_navlive_overlay (ssf_navlive.h)
     RaycastWs raycast;                            // ssf_raycast (ssf_raycast.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense); the out-of-view
                                                   // compaction keeps rows and order but moves slots: who keeps slot numbers also watches n_recentres (RaycastWs)

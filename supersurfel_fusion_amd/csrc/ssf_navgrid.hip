@@ -298,7 +298,7 @@ static void launch_navgrid_cells(hipStream_t st, const NavGrid& G, const NavAcc&
     const size_t P = (size_t)G.W * G.H;
     hipLaunchKernelGGL(k_navgrid_cells, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, acc, P, G.min_hits, out, stats);
 }
-static void launch_navgrid_clearance(hipStream_t st, const int8_t* state, int W, int H, int R, int unknown_too, uint16_t* g, int32_t* dist2) {
+void launch_navgrid_clearance(hipStream_t st, const int8_t* state, int W, int H, int R, int unknown_too, uint16_t* g, int32_t* dist2) {
     { ScopedKernel sk("navgrid_columns", st);
       hipLaunchKernelGGL(k_navgrid_columns, dim3((W + 63) / 64), dim3(64), 0, st, state, W, H, R, unknown_too, g); }
     { ScopedKernel sk("navgrid_rows", st);

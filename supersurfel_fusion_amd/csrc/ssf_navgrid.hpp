@@ -88,4 +88,9 @@ int navgrid_reserve(ssf_handle* h, const ssf_navgrid_params* p, const NavCall& c
 int navgrid_accumulate(ssf_handle* h, const ssf_navgrid_params* p, NavCall& c);            // (under the caller's TimerScope)
 int navgrid_finish(ssf_handle* h, const ssf_navgrid_params* p, const NavCall& c, ssf::NavOut o, int32_t* d2, const StagedIo& io,
                    NavCellsLaunch cells, const ssf::NavSeen* sn, ssf_navgrid_stats* stats, unsigned long long* carve_sums = nullptr);
+// the clearance of ssf_navgrid.h step 8 on a state that is on the device (navgrid_columns, navgrid_rows): what finish runs, and what
+// ssf_navlive_overlay (ssf_navlive.hip) runs on its own state.  g: W * H words of working space
+namespace ssf {
+void launch_navgrid_clearance(hipStream_t st, const int8_t* state, int W, int H, int R, int unknown_too, uint16_t* g, int32_t* dist2);
+}
 #pragma GCC visibility pop

@@ -217,7 +217,7 @@ def plan_cells(pose, res, cam_t, goals_m):
     return start, goals
 
 
-def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, plan=None, frontiers=None, waypoints=None):
+def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, plan=None, frontiers=None, waypoints=None, live=None):
     """the navigation grid of the map, built on the device (include/ssf_navgrid.h) at the default size and frame (floor-aligned
     about the tracked camera) with cells of `res` metres: grid_dir/<k as %06d>.pgm -- the state in map_server's convention (205
     unknown, 254 free, 0 occupied; the image's top row is the grid's last) --, <k>.yaml beside it (map_server's keys; origin = the
@@ -232,7 +232,10 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
     table's records, order, stats, start) and <k>_frontier_regions.npy (the map: table index, -1 no member, -2 not in the table).
     waypoints (dict(lookahead=cells, los_radius=metres), with a plan only): the plan's path reduced to any-angle waypoints
     (include/ssf_navpath.h) that keep the path's clearance up to the squared los_radius and at least that: <k>_waypoints.npy ((n, 4)
-    int32: ix, iy, index into the path with bit 30 on a forced step, seg_min) and <k>_waypoints.json (stats, status, path_min)"""
+    int32: ix, iy, index into the path with bit 30 on a forced step, seg_min) and <k>_waypoints.json (stats, status, path_min).
+    live (dict(depth=the depth image of the frame just processed, min_hits, stride)): that frame stamped onto the grid
+    (include/ssf_navlive.h) from the tracked pose: <k>_live_state.npy and <k>_live_dist2.npy, and one log line with the stats; the
+    map's own grid, plan and regions above are written as without it"""
     if carve_views is None:
         out = fusion.nav_grid(outputs=("state", "dist2"), res=res)
     else:
@@ -252,6 +255,12 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
     np.save(os.path.join(grid_dir, name + "_dist2.npy"), out["dist2"])
     if carve_views is not None:
         np.save(os.path.join(grid_dir, name + "_seen.npy"), out["seen"])
+    if live is not None:
+        lv = fusion.nav_live(live["depth"], state, outputs=("state", "dist2"), grid_pose=pose, res=res, min_hits=int(live.get("min_hits", 4)),
+                             stride=int(live.get("stride", 4)))
+        np.save(os.path.join(grid_dir, name + "_live_state.npy"), lv["state"])
+        np.save(os.path.join(grid_dir, name + "_live_dist2.npy"), lv["dist2"])
+        print("nav-live %s: %s" % (name, " ".join("%s=%d" % (nm, v) for nm, v in lv["stats"].items() if nm != "pose")))
     if plan is not None:
         import json
         start, goals = plan_cells(pose, res, fusion.get_pose()[9:12], plan.get("goals") or [])
@@ -318,7 +327,7 @@ def write_laser_scan(fusion, scan_dir, k, beams):
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
            keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30, detect_motion=False,
            motion_mask_dir=None, odometry_prior=False, nav_grid_dir=None, nav_grid_every=30, nav_grid_res=0.05,
-           nav_grid_carve=False, nav_grid_carve_stride=8, nav_plan=None, nav_frontiers=None, nav_waypoints=None, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
+           nav_grid_carve=False, nav_grid_carve_stride=8, nav_plan=None, nav_frontiers=None, nav_waypoints=None, nav_live=None, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
@@ -333,7 +342,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     is carved along the rays of the poses estimated so far (thin_views: at most 256 of them) on a pixel lattice of
     nav_grid_carve_stride, and <k>_seen.npy is written as well.  nav_plan (write_nav_grid's plan): the field, path and stats of a
     plan from the camera's cell are written next to each grid.  nav_frontiers (write_nav_grid's frontiers): the frontier regions
-    of each grid, ranked from the camera's cell, are written next to it.  nav_waypoints (write_nav_grid's waypoints; needs nav_plan):
+    of each grid, ranked from the camera's cell, are written next to it.  nav_live (dict(min_hits, stride)): the depth image of the
+    frame just processed is stamped onto each grid (write_nav_grid's live).  nav_waypoints (write_nav_grid's waypoints; needs nav_plan):
     the plan's path reduced to waypoints is written next to it.
     laser_scan_dir: after frames 0, laser_scan_every, 2 laser_scan_every, ... a planar scan of laser_scan_beams beams from the tracked
     pose is written (write_laser_scan, numbered by frame); pipelined, submission pauses as for a render.
@@ -355,6 +365,9 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
         raise ValueError("nav_waypoints needs nav_plan")
     if nav_frontiers is not None and not nav_grid_dir:
         raise ValueError("nav_frontiers needs nav_grid_dir")
+    if nav_live is not None and not nav_grid_dir:
+        raise ValueError("nav_live needs nav_grid_dir")
+    live_of = (lambda depth: dict(nav_live, depth=depth)) if nav_live is not None else (lambda depth: None)
     carve_views = (lambda: [r["pose"] for r in results]) if nav_grid_carve else (lambda: None)
     if odometry_prior:
         if pipelined:
@@ -406,7 +419,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
                 write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan, nav_frontiers,
-                               nav_waypoints)
+                               nav_waypoints, live_of(depth))
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     else:
@@ -430,7 +443,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
             if fusion.pending_frames() == 0:
                 break
             r = fusion.process_submitted().as_dict()
-            held.pop(0)
+            last_depth = held.pop(0)[1]
             results.append(r)
             lines.append(tum_line(stamps[len(lines)], r["pose"]))
             if render_dir and (len(lines) - 1) % render_every == 0:
@@ -439,7 +452,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
                 write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan, nav_frontiers,
-                               nav_waypoints)
+                               nav_waypoints, live_of(last_depth))
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     if out_path:
@@ -594,6 +607,11 @@ def parse_args(argv=None):
     ap.add_argument("--nav-frontier-min-cells", type=int, default=None, metavar="N", help="regions of fewer cells are dropped (default 1)")
     ap.add_argument("--nav-frontier-gain-radius", type=int, default=None, metavar="R",
                     help="cells, 0..128: count the unknown cells seen along rays of this length from each region (default 0: no gain)")
+    ap.add_argument("--nav-live", action="store_true",
+                    help="with --nav-grid-dir: the depth image of the frame just processed stamped onto every grid on the device (the live "
+                         "obstacle layer); _live_state.npy and _live_dist2.npy are written next to the grid, and one log line with the stats")
+    ap.add_argument("--nav-live-min-hits", type=int, default=None, metavar="N", help="points of the frame that make a cell occupied (default 4)")
+    ap.add_argument("--nav-live-stride", type=int, default=None, metavar="S", help="pixel lattice of the see-through rays, 1..64 (default 4)")
     ap.add_argument("--laser-scan-dir", default=None, metavar="DIR",
                     help="every --laser-scan-every frames, a planar laser scan simulated from the map on the device, from the tracked pose: "
                          "DIR/<frame number as %%06d>.npy (ranges in metres, +inf where nothing is hit)")
@@ -632,6 +650,14 @@ def parse_args(argv=None):
         ap.error("--nav-plan-los-radius is >= 0")
     if a.nav_frontiers and not a.nav_grid_dir:
         ap.error("--nav-frontiers needs --nav-grid-dir")
+    if a.nav_live and not a.nav_grid_dir:
+        ap.error("--nav-live needs --nav-grid-dir")
+    if (a.nav_live_min_hits is not None or a.nav_live_stride is not None) and not a.nav_live:
+        ap.error("--nav-live-min-hits and --nav-live-stride go with --nav-live")
+    if a.nav_live_min_hits is not None and a.nav_live_min_hits < 1:
+        ap.error("--nav-live-min-hits is >= 1")
+    if a.nav_live_stride is not None and not 1 <= a.nav_live_stride <= 64:
+        ap.error("--nav-live-stride is 1..64")
     if (a.nav_frontier_min_cells is not None or a.nav_frontier_gain_radius is not None) and not a.nav_frontiers:
         ap.error("--nav-frontier-min-cells and --nav-frontier-gain-radius go with --nav-frontiers")
     if a.nav_frontier_min_cells is not None and a.nav_frontier_min_cells < 1:
@@ -656,6 +682,13 @@ def nav_waypoints_of(a):
                 los_radius=0.0 if a.nav_plan_los_radius is None else float(a.nav_plan_los_radius))
 
 
+def nav_live_of(a):
+    """replay()'s nav_live from the parsed options, or None"""
+    if not a.nav_live:
+        return None
+    return dict(min_hits=4 if a.nav_live_min_hits is None else int(a.nav_live_min_hits), stride=4 if a.nav_live_stride is None else int(a.nav_live_stride))
+
+
 def nav_frontiers_of(a):
     """replay()'s nav_frontiers from the parsed options, or None"""
     if not a.nav_frontiers:
@@ -667,9 +700,9 @@ def nav_frontiers_of(a):
 def main():
     a = parse_args()
     from . import binding
-    plan, frontiers, waypoints = nav_plan_of(a), nav_frontiers_of(a), nav_waypoints_of(a)
-    # (the carve's, the plan's, the regions' and the waypoints' entry points: libraries of their own)
-    lib = binding.load_drive() if waypoints else binding.load_explore() if frontiers else (binding.load_nav() if plan else (binding.load_navcarve() if a.nav_grid_carve else binding.load_product()))
+    plan, frontiers, waypoints, live = nav_plan_of(a), nav_frontiers_of(a), nav_waypoints_of(a), nav_live_of(a)
+    # (the carve's, the plan's, the regions', the waypoints' and the live layer's entry points: libraries of their own)
+    lib = binding.load_live() if live else binding.load_drive() if waypoints else binding.load_explore() if frontiers else (binding.load_nav() if plan else (binding.load_navcarve() if a.nav_grid_carve else binding.load_product()))
     cfg = lib.default_config(pipeline_depth=2 if a.pipelined else 0, extract_batch=4 if a.pipelined else 1, **BENCHMARK_LAUNCH)
     f = binding.Fusion(lib, cfg)
     if a.raw_frames:
@@ -682,7 +715,7 @@ def main():
                         keyframe_log=a.keyframe_log, detect_motion=a.detect_motion, motion_mask_dir=a.motion_mask_dir,
                         odometry_prior=a.odometry_prior, nav_grid_dir=a.nav_grid_dir, nav_grid_every=a.nav_grid_every,
                         nav_grid_res=a.nav_grid_res, nav_grid_carve=a.nav_grid_carve, nav_grid_carve_stride=a.nav_grid_carve_stride, nav_plan=plan,
-                        nav_frontiers=frontiers, nav_waypoints=waypoints,
+                        nav_frontiers=frontiers, nav_waypoints=waypoints, nav_live=live,
                         laser_scan_dir=a.laser_scan_dir, laser_scan_every=a.laser_scan_every,
                         laser_scan_beams=a.laser_scan_beams)
     if a.keyframes and not a.keyframe_log:
