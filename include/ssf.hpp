@@ -30,6 +30,7 @@
 #include "ssf_navfrontier.h"
 #include "ssf_navpath.h"
 #include "ssf_navlive.h"
+#include "ssf_navsteer.h"
 #include "ssf_raycast.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
@@ -369,6 +370,40 @@ struct LiveParams {
 struct LiveNavGrid : NavGrid {
     std::vector<uint32_t> live_hits, live_seen;
     ssf_navlive_stats live;
+};
+
+/* steerOnGrid (ssf_navsteer.h; exported by libssf_hip_steer.so, linked INSTEAD of the other libraries -- a program that does not call
+ * it links as before: the inline member leaves no reference behind): a lattice of (v, w) candidates rolled out over a grid from
+ * every pose, and the best admissible one.  The members start at ssf_navsteer_default_params' values; units as in ssf_navsteer.h:
+ * 1024 sub-units per cell, 65536 heading units per turn, per step. */
+struct SteerParams {
+    int min_dist2 = 0; bool allow_unknown = false;      /* the plan's: what the robot may stand on */
+    int clearance_cap = 64;
+    int n_v = 9, n_w = 33, v_min = 0, v_step = 64, w_min = -2048, w_step = 128;       /* the lattice (steerWindow makes one) */
+    int n_steps = 32, min_free_steps = 2, brake_div = 128;
+    int cost_weight = 1, target_weight = 0, clear_weight = 1, speed_weight = 1, turn_weight = 0;
+    bool want_traj = true, want_candidates = false;     /* false: not produced (its vectors stay empty) */
+};
+struct SteerPose { int32_t x, y, heading; };            /* units */
+struct SteerTarget { int32_t x, y; };
+/* a metric grid-frame pose (x m, y m, yaw rad) in units */
+inline SteerPose steerUnits(double x_m, double y_m, double yaw, float res) {
+    SteerPose p;
+    p.x = (int32_t)std::floor(x_m / (double)res * 1024.0); p.y = (int32_t)std::floor(y_m / (double)res * 1024.0);
+    p.heading = (int32_t)((long long)std::floor(yaw / 6.283185307179586476925286766559 * 65536.0 + 0.5) & 0xFFFF);
+    return p;
+}
+/* what steerOnGrid makes: per pose the winning candidate (-1: none), its command, score, the admissible count, the status
+ * (ssf_navsteer.h step 8) and the winner's arc; with want_candidates the per-candidate arrays, n_poses x K */
+struct NavSteer {
+    int n_steps = 0, candidates = 0;                   /* K */
+    std::vector<int32_t> best, v, w, n_admissible, status;
+    std::vector<int64_t> score;
+    std::vector<std::vector<SteerPose> > traj;
+    std::vector<int32_t> cand_free, cand_min_d, cand_end;      /* cand_end x 3 */
+    std::vector<uint32_t> cand_end_cost;
+    std::vector<int64_t> cand_score;
+    ssf_navsteer_stats stats;
 };
 
 /* castRays (ssf_raycast.h; exported by libssf_hip.so only): the first disc of the map that each ray hits.  The members start at
@@ -1039,6 +1074,107 @@ public:
             msg.poses[k].pose.orientation.y = qy * cz - qx * sz; msg.poses[k].pose.orientation.z = qz * cz + qw * sz;
         }
     }
+    /* Velocity commands on a grid (ssf_navsteer.h): from every pose the lattice of q is rolled out over g, and the best admissible
+     * candidate comes back with its arc.  g: a grid that buildNavGrid or overlayDepthFrame made (state and dist2); plan: a planOnGrid
+     * on the same grid whose cost field is the cost-to-goal term (nullptr with q.cost_weight 0); targets: one per pose, or empty with
+     * q.target_weight 0. */
+    void steerOnGrid(const NavGrid& g, const NavPlan* plan, const std::vector<SteerPose>& poses, const std::vector<SteerTarget>& targets,
+                     const SteerParams& q, NavSteer& out) {
+        const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
+        if (n == 0 || g.state.size() != n || g.dist2.size() != n) throw std::logic_error("steerOnGrid: the grid has no state or no dist2 (want_state, want_dist2)");
+        if (plan && plan->cost.size() != n) throw std::logic_error("steerOnGrid: the plan's cost field is not the grid's size (want_cost)");
+        if (poses.empty()) throw std::logic_error("steerOnGrid: no pose");
+        if (!targets.empty() && targets.size() != poses.size()) throw std::logic_error("steerOnGrid: one target per pose, or none");
+        ssf_navsteer_params p;
+        check(ssf_navsteer_default_params(need(), &p));
+        p.width = g.width; p.height = g.height; p.min_dist2 = q.min_dist2; p.allow_unknown = q.allow_unknown ? 1 : 0; p.clearance_cap = q.clearance_cap;
+        p.n_poses = (int)std::min<size_t>(poses.size(), 1u << 30);          /* (too many: the library refuses) */
+        p.n_v = q.n_v; p.n_w = q.n_w; p.v_min = q.v_min; p.v_step = q.v_step; p.w_min = q.w_min; p.w_step = q.w_step; p.n_steps = q.n_steps;
+        p.min_free_steps = q.min_free_steps; p.brake_div = q.brake_div; p.cost_weight = q.cost_weight; p.target_weight = q.target_weight;
+        p.clear_weight = q.clear_weight; p.speed_weight = q.speed_weight; p.turn_weight = q.turn_weight; p.on_device = 0;
+        const size_t np = poses.size();
+        const bool fits = q.n_v >= 1 && q.n_v <= 256 && q.n_w >= 1 && q.n_w <= 1024 && q.n_v * q.n_w <= 65536 && q.n_steps >= 1 && q.n_steps <= 256 &&
+                          np <= 4096 && np * (size_t)(q.n_v * q.n_w) <= ((size_t)1 << 24);
+        const size_t K = fits ? (size_t)(q.n_v * q.n_w) : 1, T1 = fits ? (size_t)q.n_steps + 1 : 1;
+        std::vector<int32_t> cmd(np * 2, 0), len(np, 0), traj(q.want_traj ? np * T1 * 3 : 0);
+        out.n_steps = q.n_steps; out.candidates = (int)K;
+        out.best.assign(np, -1); out.n_admissible.assign(np, 0); out.status.assign(np, 0); out.score.assign(np, -1);
+        const size_t nk = q.want_candidates ? np * K : 0;
+        out.cand_free.assign(nk, 0); out.cand_min_d.assign(nk, -1); out.cand_end.assign(nk * 3, 0); out.cand_end_cost.assign(nk, SSF_NAVSTEER_NO_COST);
+        out.cand_score.assign(nk, -1);
+        ssf_navsteer_out o;
+        o.best = out.best.data(); o.best_cmd = cmd.data(); o.best_score = out.score.data(); o.n_admissible = out.n_admissible.data();
+        o.pose_status = out.status.data(); o.best_len = len.data(); o.best_traj = q.want_traj ? traj.data() : nullptr;
+        o.cand_free = nk ? out.cand_free.data() : nullptr; o.cand_min_d = nk ? out.cand_min_d.data() : nullptr; o.cand_end = nk ? out.cand_end.data() : nullptr;
+        o.cand_end_cost = nk ? out.cand_end_cost.data() : nullptr; o.cand_score = nk ? out.cand_score.data() : nullptr;
+        check(ssf_navsteer_rollouts(need(), &p, g.state.data(), g.dist2.data(), plan ? plan->cost.data() : nullptr, &poses[0].x,
+                                    targets.empty() ? nullptr : &targets[0].x, &o, &out.stats));
+        out.v.resize(np); out.w.resize(np); out.traj.assign(np, std::vector<SteerPose>());
+        for (size_t i = 0; i < np; i++) {
+            out.v[i] = cmd[2 * i]; out.w[i] = cmd[2 * i + 1];
+            if (!q.want_traj) continue;
+            out.traj[i].resize((size_t)len[i]);
+            for (size_t k = 0; k < (size_t)len[i]; k++) {
+                const int32_t* e = &traj[(i * T1 + k) * 3];
+                out.traj[i][k].x = e[0]; out.traj[i][k].y = e[1]; out.traj[i][k].heading = e[2];
+            }
+        }
+    }
+    /* The integer lattice of a dynamic window (pure host arithmetic, no handle): the speeds (m/s) and turn rates (rad/s) reachable
+     * from (v_now, w_now) within one step of dt seconds under (accel_v m/s^2, accel_w rad/s^2), cut to [v_lo, v_hi] and [w_lo, w_hi]
+     * and to the call's own |v| <= 1024, |w| <= 16384, in units per step: v = speed * dt * 1024 / res, w = rate * dt * 65536 / 2 pi.
+     * The lattice starts at the window's lower end rounded up and its step is rounded down, so that no candidate lies outside the
+     * window; an axis whose window is narrower than its count keeps fewer candidates.  q's six lattice members are set. */
+    static void steerWindow(double v_now, double w_now, double v_lo, double v_hi, double w_lo, double w_hi, double accel_v, double accel_w, double dt,
+                            float res, int n_v, int n_w, SteerParams& q) {
+        if (!(dt > 0.0) || !(res > 0.f) || n_v < 1 || n_w < 1) throw std::invalid_argument("steerWindow needs dt > 0, res > 0, n_v >= 1 and n_w >= 1");
+        steer_axis(v_now, v_lo, v_hi, accel_v * dt, dt * 1024.0 / (double)res, 1024, n_v, q.n_v, q.v_min, q.v_step);
+        steer_axis(w_now, w_lo, w_hi, accel_w * dt, dt * 65536.0 / 6.283185307179586476925286766559, 16384, n_w, q.n_w, q.w_min, q.w_step);
+    }
+    /* A geometry_msgs::Twist from the command of pose `pose`: linear.x = v * res / (1024 dt), angular.z = w * 2 pi / (65536 dt), the
+     * other four components 0.  A pose without a winner gives the zero twist: stop.  Any message type with linear and angular works
+     * (tests use a double). */
+    template <typename TwistT> static void fillTwist(const NavSteer& s, size_t pose, float res, float dt, TwistT& msg) {
+        if (pose >= s.best.size()) throw std::logic_error("fillTwist: no such pose");
+        if (!(dt > 0.f)) throw std::invalid_argument("fillTwist: dt must be > 0");
+        msg.linear.x = (double)s.v[pose] * (double)res / (1024.0 * (double)dt); msg.linear.y = 0.0; msg.linear.z = 0.0;
+        msg.angular.x = 0.0; msg.angular.y = 0.0; msg.angular.z = (double)s.w[pose] * 6.283185307179586476925286766559 / (65536.0 * (double)dt);
+    }
+    /* The poses of a nav_msgs::Path from the winner's arc of pose `pose`, one per entry: the position (x / 1024 res, y / 1024 res, 0)
+     * in the grid frame, taken to the map frame by pose12 (grid-to-map: NavGrid::stats.pose) as fillWaypointPath does; the
+     * orientation is the grid frame's rotation times the yaw heading * 2 pi / 65536 about the grid's z. */
+    template <typename PathT> static void fillLocalPlan(const NavSteer& s, size_t pose, const float pose12[12], float res, PathT& msg) {
+        if (pose >= s.traj.size()) throw std::logic_error("fillLocalPlan: no such pose (want_traj)");
+        const std::vector<SteerPose>& t = s.traj[pose];
+        const double m00 = pose12[0], m01 = pose12[1], m02 = pose12[2], m10 = pose12[3], m11 = pose12[4], m12 = pose12[5], m20 = pose12[6], m21 = pose12[7],
+                     m22 = pose12[8];
+        const double tr = m00 + m11 + m22;
+        double qw, qx, qy, qz;
+        if (tr > 0.0) { const double k = 2.0 * std::sqrt(1.0 + tr); qw = 0.25 * k; qx = (m21 - m12) / k; qy = (m02 - m20) / k; qz = (m10 - m01) / k; }
+        else if (m00 > m11 && m00 > m22) { const double k = 2.0 * std::sqrt(1.0 + m00 - m11 - m22); qw = (m21 - m12) / k; qx = 0.25 * k; qy = (m01 + m10) / k; qz = (m02 + m20) / k; }
+        else if (m11 > m22) { const double k = 2.0 * std::sqrt(1.0 + m11 - m00 - m22); qw = (m02 - m20) / k; qx = (m01 + m10) / k; qy = 0.25 * k; qz = (m12 + m21) / k; }
+        else { const double k = 2.0 * std::sqrt(1.0 + m22 - m00 - m11); qw = (m10 - m01) / k; qx = (m02 + m20) / k; qy = (m12 + m21) / k; qz = 0.25 * k; }
+        msg.poses.resize(t.size());
+        for (size_t k = 0; k < t.size(); k++) {
+            const double x = (double)t[k].x / 1024.0 * (double)res, y = (double)t[k].y / 1024.0 * (double)res;
+            msg.poses[k].pose.position.x = m00 * x + m01 * y + (double)pose12[9];
+            msg.poses[k].pose.position.y = m10 * x + m11 * y + (double)pose12[10];
+            msg.poses[k].pose.position.z = m20 * x + m21 * y + (double)pose12[11];
+            const double yaw = (double)t[k].heading * 6.283185307179586476925286766559 / 65536.0;
+            const double sz = std::sin(0.5 * yaw), cz = std::cos(0.5 * yaw);       /* q(R) * (0, 0, sz, cz) */
+            msg.poses[k].pose.orientation.w = qw * cz - qz * sz; msg.poses[k].pose.orientation.x = qx * cz + qy * sz;
+            msg.poses[k].pose.orientation.y = qy * cz - qx * sz; msg.poses[k].pose.orientation.z = qz * cz + qw * sz;
+        }
+    }
+private:
+    static void steer_axis(double now, double lo_limit, double hi_limit, double reach, double scale, int cap, int n, int& n_out, int& first, int& step) {
+        double lo = std::max(lo_limit, now - reach), hi = std::min(hi_limit, now + reach);
+        if (lo > hi) lo = hi = std::min(std::max(now, lo_limit), hi_limit);      /* (the current value lies outside the limits: the nearest limit) */
+        int a0 = std::max((int)std::ceil(lo * scale), -cap), a1 = std::min((int)std::floor(hi * scale), cap);
+        if (a0 > a1) a0 = a1 = std::min(std::max((int)std::floor(0.5 * (lo + hi) * scale + 0.5), -cap), cap);     /* (narrower than one unit) */
+        n_out = std::min(n, a1 - a0 + 1); first = a0; step = n_out > 1 ? (a1 - a0) / (n_out - 1) : 0;
+    }
+public:
     /* Rays cast through the map on the device (ssf_raycast.h): rays6 holds n rays of six floats (origin, direction) in the frame of
      * r.pose.  The library keeps a spatial index of the map between calls and rebuilds it when the map has changed.  INTEGRATION.md
      * section 2 has the uses (a simulated lidar scan, line of sight, picking). */

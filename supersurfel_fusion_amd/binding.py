@@ -29,6 +29,9 @@ DRIVE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_drive.so")
 # drive's objects and the live obstacle layer (include/ssf_navlive.h): the one library of a robot that also stamps the depth frame of
 # the instant onto its grid.  None of the five libraries above exports the overlay's entry points
 LIVE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_live.so")
+# live's objects and the velocity commands (include/ssf_navsteer.h): the one library of a robot that also steers on its grid.  None of
+# the six libraries above exports the rollouts' entry points
+STEER_LIB = os.path.join(_HERE, "csrc", "libssf_hip_steer.so")
 
 
 class SsfConfig(C.Structure):
@@ -143,6 +146,16 @@ NAVPATH_FORCED = 1 << 30             # bit 30 of a waypoint's index word: the se
 NAVLIVE_SYMBOLS = ["ssf_navlive_default_params", "ssf_navlive_overlay"]
 NAVLIVE_OUTPUTS = (("live_hits", np.uint32), ("live_seen", np.uint32), ("state", np.int8), ("dist2", np.int32))
 NAVLIVE_OUTPUT_NAMES = tuple(nm for nm, _ in NAVLIVE_OUTPUTS)
+# the velocity commands (include/ssf_navsteer.h): exported by libssf_hip_steer.so only (load_steer)
+NAVSTEER_SYMBOLS = ["ssf_navsteer_rollouts", "ssf_navsteer_default_params", "ssf_navsteer_direction_table"]
+# (name, dtype, per pose or per candidate, trailing shape; 'T1' = n_steps + 1)
+NAVSTEER_OUTPUTS = (("best", np.int32, "pose", ()), ("best_cmd", np.int32, "pose", (2,)), ("best_score", np.int64, "pose", ()),
+                    ("n_admissible", np.int32, "pose", ()), ("pose_status", np.int32, "pose", ()), ("best_len", np.int32, "pose", ()),
+                    ("best_traj", np.int32, "pose", ("T1", 3)), ("cand_free", np.int32, "cand", ()), ("cand_min_d", np.int32, "cand", ()),
+                    ("cand_end", np.int32, "cand", (3,)), ("cand_end_cost", np.uint32, "cand", ()), ("cand_score", np.int64, "cand", ()))
+NAVSTEER_OUTPUT_NAMES = tuple(o[0] for o in NAVSTEER_OUTPUTS)
+NAVSTEER_POSE_OUTPUTS = tuple(o[0] for o in NAVSTEER_OUTPUTS if o[2] == "pose")
+NAVSTEER_SUBUNITS, NAVSTEER_TURN, NAVSTEER_NO_COST = 1024, 65536, 0xFFFFFFFF
 # rays cast through the model (include/ssf_raycast.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 RAYCAST_SYMBOLS = ["ssf_raycast_default_params", "ssf_raycast"]
 # the output arrays of ssf_raycast, in its argument order: name, dtype, per-ray shape
@@ -385,6 +398,27 @@ class SsfNavLiveStats(C.Structure):
         return d
 
 
+class SsfNavSteerParams(C.Structure):
+    """ssf_navsteer_params (include/ssf_navsteer.h)"""
+    _fields_ = [(nm, C.c_int) for nm in ("width", "height", "min_dist2", "allow_unknown", "clearance_cap", "n_poses", "n_v", "n_w", "v_min", "v_step",
+                                         "w_min", "w_step", "n_steps", "min_free_steps", "brake_div", "cost_weight", "target_weight", "clear_weight",
+                                         "speed_weight", "turn_weight", "walk", "on_device")]
+
+
+class SsfNavSteerOut(C.Structure):
+    """ssf_navsteer_out (include/ssf_navsteer.h)"""
+    _fields_ = [(nm, C.c_void_p) for nm in NAVSTEER_OUTPUT_NAMES]
+
+
+class SsfNavSteerStats(C.Structure):
+    """ssf_navsteer_stats (include/ssf_navsteer.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("poses_ok", "poses_blocked", "poses_stuck", "candidates", "admissible", "collided", "steps_taken",
+                                           "windows_staged", "windows_global")]
+
+    def as_dict(self):
+        return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
+
+
 class SsfRaycastParams(C.Structure):
     """ssf_raycast_params (include/ssf_raycast.h)"""
     _fields_ = [("pose", C.c_void_p), ("t_min", C.c_float), ("t_max", C.c_float), ("min_conf", C.c_float), ("splat_scale", C.c_float),
@@ -575,6 +609,12 @@ class Library:
         if self.has_navlive:
             L.ssf_navlive_default_params.argtypes = [vp, C.POINTER(SsfNavLiveParams)]
             L.ssf_navlive_overlay.argtypes = [vp, C.POINTER(SsfNavLiveParams), vp, vp, vp, C.POINTER(SsfNavLiveOut), C.POINTER(SsfNavLiveStats)]
+        self.has_navsteer = all(hasattr(L, nm) for nm in NAVSTEER_SYMBOLS)
+        if self.has_navsteer:
+            L.ssf_navsteer_default_params.argtypes = [vp, C.POINTER(SsfNavSteerParams)]
+            L.ssf_navsteer_direction_table.argtypes = [vp, vp]
+            L.ssf_navsteer_rollouts.argtypes = [vp, C.POINTER(SsfNavSteerParams), vp, vp, vp, vp, vp, C.POINTER(SsfNavSteerOut),
+                                                C.POINTER(SsfNavSteerStats)]
         self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
         if self.has_navgrid:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
@@ -705,6 +745,28 @@ def load_live():
     library to call nav_live or nav_live_plan on it.  Fails loudly when it has not been built."""
     import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
     return Library(LIVE_LIB)
+
+
+def load_steer():
+    """Load libssf_hip_steer.so: live's objects (the product, the carve, the plan, the frontier regions, the waypoints, the live
+    obstacle layer) with the velocity commands linked in (include/ssf_navsteer.h).  A handle belongs to the library that created it:
+    create the Fusion from THIS library to call nav_steer or nav_live_steer on it.  Fails loudly when it has not been built."""
+    import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
+    return Library(STEER_LIB)
+
+
+def navsteer_direction_table(library=None):
+    """(C, S): the 1024-entry direction table of include/ssf_navsteer.h step 1, int32 each, as ssf_navsteer_direction_table returns it.
+    It takes no handle and touches no device.  library: a Library that exports it (default: load_steer())."""
+    lib = library or load_steer()
+    if not lib.has_navsteer:
+        raise SsfError("%s does not export ssf_navsteer_direction_table: it steers nothing (include/ssf_navsteer.h: libssf_hip_steer.so, "
+                       "binding.load_steer)" % lib.path)
+    c, s = np.zeros(1024, np.int32), np.zeros(1024, np.int32)
+    rc = lib.lib.ssf_navsteer_direction_table(_ptr(c), _ptr(s))
+    if rc != 0:
+        raise SsfError("ssf_navsteer_direction_table failed (%d)" % rc)
+    return c, s
 
 
 def load_lab():
@@ -1929,6 +1991,181 @@ class Fusion:
             ref["stats"] = wp_stats
             res["waypoints"] = ref
         return res
+
+    # ---- velocity commands on the navigation grid: rollouts scored on the device (include/ssf_navsteer.h) ----
+    def _need_navsteer(self, symbol):
+        if not self.L.has_navsteer:
+            raise SsfError("%s does not export %s: it steers nothing (include/ssf_navsteer.h: libssf_hip_steer.so, binding.load_steer)"
+                           % (self.L.path, symbol))
+
+    def _navsteer_params(self, on_device, width, height, n_poses, params):
+        """SsfNavSteerParams: the fields of ssf_navsteer_params by name, each at ssf_navsteer_default_params' value when missing"""
+        p = SsfNavSteerParams()
+        self._ck(self.L.lib.ssf_navsteer_default_params(self.h, C.byref(p)), "ssf_navsteer_default_params")
+        kinds = dict(p._fields_)
+        for nm, val in params.items():
+            if nm not in kinds or nm in ("width", "height", "n_poses", "on_device"):
+                raise SsfError("unknown steering parameter %r" % nm)
+            setattr(p, nm, int(val))
+        p.width, p.height, p.n_poses, p.on_device = int(width), int(height), int(n_poses), int(bool(on_device))
+        return p
+
+    def _navsteer_rollouts(self, p, state, dist2, cost, poses, targets, ptrs):
+        st = SsfNavSteerStats()
+        out = SsfNavSteerOut(*[ptrs.get(nm) for nm in NAVSTEER_OUTPUT_NAMES])
+        self._ck(self.L.lib.ssf_navsteer_rollouts(self.h, C.byref(p), state, dist2, cost, poses, targets, C.byref(out), C.byref(st)),
+                 "ssf_navsteer_rollouts")
+        return st.as_dict()
+
+    @staticmethod
+    def _navsteer_shape(kind, tail, n, K, T):
+        return (n,) + ((K,) if kind == "cand" else ()) + tuple(T + 1 if d == "T1" else d for d in tail)
+
+    def nav_steer(self, state, dist2, poses, cost=None, targets=None, outputs=NAVSTEER_POSE_OUTPUTS, **params):
+        """A lattice of (v, w) candidates rolled out from every pose over the grid, tested and scored (ssf_navsteer_rollouts), host
+        arrays.  state H x W int8 and dist2 H x W int32 as the grid calls or nav_live return them; cost H x W uint32 as nav_plan
+        returns it (None with cost_weight=0); poses n x 3 int32 (x, y, heading) in units (nav_steer_units); targets n x 2 int32 (None
+        with target_weight 0).  Returns a dict of the requested outputs (NAVSTEER_OUTPUTS; best_traj: a list with one (best_len, 3)
+        array per pose) and 'stats'.  params: the other fields of ssf_navsteer_params by name."""
+        self._need_navsteer("ssf_navsteer_rollouts")
+        bad = [nm for nm in outputs if nm not in NAVSTEER_OUTPUT_NAMES]
+        if bad:
+            raise SsfError("unknown steering outputs %s (known: %s)" % (bad, ", ".join(NAVSTEER_OUTPUT_NAMES)))
+        state, dist2 = np.ascontiguousarray(state, np.int8), np.ascontiguousarray(dist2, np.int32)
+        if state.ndim != 2 or dist2.shape != state.shape:
+            raise SsfError("state and dist2 are H x W arrays of one shape, got %s and %s" % (state.shape, dist2.shape))
+        H, W = state.shape
+        poses = np.ascontiguousarray(poses, np.int32)
+        if poses.ndim != 2 or poses.shape[1] != 3:
+            raise SsfError("poses are n x 3 (x, y, heading) in units, got shape %s" % (poses.shape,))
+        n = poses.shape[0]
+        if cost is not None:
+            cost = np.ascontiguousarray(cost, np.uint32)
+            if cost.shape != state.shape:
+                raise SsfError("cost is an H x W array like state, got %s" % (cost.shape,))
+        if targets is not None:
+            targets = np.ascontiguousarray(targets, np.int32)
+            if targets.shape != (n, 2):
+                raise SsfError("targets are n x 2 (x, y) in units, one per pose, got shape %s" % (targets.shape,))
+        p = self._navsteer_params(False, W, H, n, params)
+        K, T = max(p.n_v, 0) * max(p.n_w, 0), max(p.n_steps, 0)
+        if not (0 < K <= 65536 and T <= 256 and n * K <= 1 << 24):
+            K = T = 1                                # (the call refuses it: the arrays only have to exist)
+        want = set(outputs)
+        if "best_traj" in want:
+            want.add("best_len")                     # (the counts cut the lists)
+        out = {nm: np.zeros(self._navsteer_shape(kind, tail, n, K, T), dt) for nm, dt, kind, tail in NAVSTEER_OUTPUTS if nm in want}
+        stats = self._navsteer_rollouts(p, _ptr(state), _ptr(dist2), _ptr(cost), _ptr(poses), _ptr(targets), {nm: _ptr(a) for nm, a in out.items()})
+        if "best_traj" in out:
+            out["best_traj"] = [out["best_traj"][i, :out["best_len"][i]].copy() for i in range(n)]
+        if "best_len" not in outputs:
+            out.pop("best_len", None)
+        out["stats"] = stats
+        return out
+
+    def nav_steer_device(self, state, dist2, width, height, poses, n_poses, cost=None, targets=None, best=None, best_cmd=None, best_score=None,
+                         n_admissible=None, pose_status=None, best_len=None, best_traj=None, cand_free=None, cand_min_d=None, cand_end=None,
+                         cand_end_cost=None, cand_score=None, **params):
+        """ssf_navsteer_rollouts on device memory: state, dist2, cost, poses, targets and each output are a contiguous torch tensor on
+        the device or the device address (int) of a buffer of the shape and dtype nav_steer works on (outputs may be None, not all):
+        nav_live_device's state and dist2 and nav_plan_device's cost are read where they lie.  Returns the stats dict."""
+        self._need_navsteer("ssf_navsteer_rollouts")
+        p = self._navsteer_params(True, width, height, n_poses, params)
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        return self._navsteer_rollouts(p, addr(state), addr(dist2), addr(cost), addr(poses), addr(targets),
+                                       dict(best=addr(best), best_cmd=addr(best_cmd), best_score=addr(best_score), n_admissible=addr(n_admissible),
+                                            pose_status=addr(pose_status), best_len=addr(best_len), best_traj=addr(best_traj), cand_free=addr(cand_free),
+                                            cand_min_d=addr(cand_min_d), cand_end=addr(cand_end), cand_end_cost=addr(cand_end_cost),
+                                            cand_score=addr(cand_score)))
+
+    def nav_steer_default_params(self):
+        """ssf_navsteer_default_params as a dict"""
+        self._need_navsteer("ssf_navsteer_default_params")
+        p = SsfNavSteerParams()
+        self._ck(self.L.lib.ssf_navsteer_default_params(self.h, C.byref(p)), "ssf_navsteer_default_params")
+        return {nm: getattr(p, nm) for nm, _ in p._fields_}
+
+    @staticmethod
+    def nav_steer_window(v_now, w_now, v_limits, w_limits, accel, dt, res, n_v, n_w):
+        """The integer lattice of a dynamic window (pure host arithmetic): the speeds (m/s) and turn rates (rad/s) reachable from
+        (v_now, w_now) within one step of dt seconds under accel = (a_v m/s^2, a_w rad/s^2), cut to v_limits = (lo, hi) and
+        w_limits = (lo, hi) and to the call's own |v| <= 1024, |w| <= 16384, in units per step: v = speed * dt * 1024 / res,
+        w = rate * dt * 65536 / 2 pi.  The lattice starts at the window's lower end rounded up and its step is rounded down, so that
+        no candidate lies outside the window; an axis whose window is narrower than its count keeps fewer candidates (a step of 0 and
+        a count of 1 when it is narrower than one unit).  Returns dict(n_v, n_w, v_min, v_step, w_min, w_step): nav_steer's keywords."""
+        if not (dt > 0 and res > 0 and n_v >= 1 and n_w >= 1):
+            raise SsfError("nav_steer_window needs dt > 0, res > 0, n_v >= 1 and n_w >= 1")
+
+        def axis(now, limits, a, scale, cap, n):
+            lo, hi = max(float(limits[0]), now - a * dt), min(float(limits[1]), now + a * dt)
+            if lo > hi:                              # (the current value lies outside the limits: the nearest limit)
+                lo = hi = min(max(now, float(limits[0])), float(limits[1]))
+            a0, a1 = max(int(np.ceil(lo * scale)), -cap), min(int(np.floor(hi * scale)), cap)
+            if a0 > a1:                              # (narrower than one unit: the unit nearest to its middle)
+                a0 = a1 = min(max(int(np.rint(0.5 * (lo + hi) * scale)), -cap), cap)
+            n = min(int(n), a1 - a0 + 1)
+            return n, a0, ((a1 - a0) // (n - 1) if n > 1 else 0)
+
+        nv, v0, dv = axis(float(v_now), v_limits, float(accel[0]), dt * NAVSTEER_SUBUNITS / res, 1024, n_v)
+        nw, w0, dw = axis(float(w_now), w_limits, float(accel[1]), dt * NAVSTEER_TURN / (2.0 * np.pi), 16384, n_w)
+        return dict(n_v=nv, n_w=nw, v_min=v0, v_step=dv, w_min=w0, w_step=dw)
+
+    @staticmethod
+    def nav_steer_units(pose_xy_yaw, res):
+        """Metric grid-frame poses (x m, y m, yaw rad; one or n x 3) in the call's units (pure host arithmetic): n x 3 int32
+        (floor(x / res * 1024), floor(y / res * 1024), round(yaw / 2 pi * 65536) & 0xFFFF)"""
+        a = np.atleast_2d(np.asarray(pose_xy_yaw, np.float64))
+        if a.shape[1] != 3 or not res > 0:
+            raise SsfError("nav_steer_units takes (x, y, yaw) rows and res > 0, got shape %s" % (a.shape,))
+        out = np.zeros(a.shape, np.int64)
+        out[:, :2] = np.floor(a[:, :2] / res * NAVSTEER_SUBUNITS)
+        out[:, 2] = np.rint(a[:, 2] / (2.0 * np.pi) * NAVSTEER_TURN).astype(np.int64) & 0xFFFF
+        return out.astype(np.int32)
+
+    def nav_live_steer(self, depth, state, goals, poses, targets=None, mask=None, live=None, plan=None, steer=None):
+        """Overlay, plan and steer with nothing but the command leaving the device: state (host, height x width int8) and the depth
+        frame (host array in the input format, or a device tensor) are uploaded once, nav_live_device writes the live state and dist2
+        into device tensors, nav_plan_device writes the cost-to-goal field of `goals` beside them and nav_steer_device reads all
+        three there.  poses: n x 3 int32 in units; live, plan, steer: the three calls' keywords (steer's min_dist2 and allow_unknown
+        default to the plan's).  Returns a dict: 'live' (stats), 'plan' (stats) and 'steer' (the per-pose outputs as nav_steer
+        returns them, and stats)."""
+        import torch
+        self._need_navlive("ssf_navlive_overlay")
+        self._need_navplan("ssf_navplan_field")
+        self._need_navsteer("ssf_navsteer_rollouts")
+        live, plan, sq = dict(live or {}), dict(plan or {}), dict(steer or {})
+        state = np.ascontiguousarray(state, np.int8)
+        if state.ndim != 2:
+            raise SsfError("state is a height x width array, got shape %s" % (state.shape,))
+        H, W = state.shape
+        poses = np.ascontiguousarray(poses, np.int32)
+        if poses.ndim != 2 or poses.shape[1] != 3 or poses.shape[0] < 1:
+            raise SsfError("poses are n x 3 (x, y, heading) in units, n >= 1, got shape %s" % (poses.shape,))
+        n = poses.shape[0]
+        dev = torch.device("cuda")
+        if not isinstance(depth, torch.Tensor):
+            depth = torch.from_numpy(np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32).view(
+                np.int16 if self.depth_format == "u16" else np.float32)).to(dev)
+        if mask is not None and not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).to(dev)
+        d_state = torch.from_numpy(state).to(dev)
+        d_dist2 = torch.empty((H, W), dtype=torch.int32, device=dev)
+        d_cost = torch.empty((H, W), dtype=torch.int32, device=dev)       # (uint32 words)
+        live_stats = self.nav_live_device(depth, d_state, W, H, mask=mask, state_out=d_state, dist2=d_dist2, **live)
+        plan_stats = self.nav_plan_device(d_state, d_dist2, W, H, goals, None, cost=d_cost, **plan)
+        for nm in ("min_dist2", "allow_unknown"):
+            sq.setdefault(nm, plan.get(nm, 0))
+        p = self._navsteer_params(True, W, H, n, sq)
+        T = min(max(p.n_steps, 0), 256)
+        d_poses = torch.from_numpy(poses).to(dev)
+        d_targets = None if targets is None else torch.from_numpy(np.ascontiguousarray(targets, np.int32)).to(dev)
+        o = {nm: torch.zeros(self._navsteer_shape(kind, tail, n, 1, T), dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
+             for nm, dt, kind, tail in NAVSTEER_OUTPUTS if kind == "pose"}
+        steer_stats = self.nav_steer_device(d_state, d_dist2, W, H, d_poses, n, cost=d_cost, targets=d_targets, **dict(o, **sq))
+        got = {nm: a.cpu().numpy() for nm, a in o.items()}
+        got["best_traj"] = [got["best_traj"][i, :got["best_len"][i]].copy() for i in range(n)]
+        got["stats"] = steer_stats
+        return dict(live=dict(stats=live_stats), plan=dict(stats=plan_stats), steer=got)
 
     # ---- rays cast through the model: the first disc each ray hits (include/ssf_raycast.h) ------------
     def _need_raycast(self, symbol):

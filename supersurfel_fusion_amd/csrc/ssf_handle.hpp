@@ -386,6 +386,17 @@ struct NavLiveWs {
     unsigned long long* stats = nullptr;
     unsigned char* img = nullptr; size_t img_bytes = 0;
 };
+// ssf_navsteer_rollouts (ssf_navsteer.h, ssf_navsteer.hip: linked into libssf_hip_steer.so only): per cell the packed (traversable, d)
+// word; per pose (4096) the smallest (score, candidate) key and the admissible count; the packed direction table (uploaded once);
+// the sums; the staging buffer of a call with host arrays.  Allocated on first use; each group is grown as a whole or not at all
+// (DevBufs::grow).  Nothing here is read or written by the frame path.
+struct NavSteerWs {
+    DevBufs bufs;
+    uint32_t* pk = nullptr; size_t cells = 0;
+    unsigned long long* keys = nullptr; int32_t* n_adm = nullptr; uint32_t* dirs = nullptr; unsigned long long* stats = nullptr;
+    bool dirs_sent = false;                       // the table's upload has been enqueued (a call may fail between allocation and upload)
+    unsigned char* io = nullptr; size_t io_bytes = 0;
+};
 // ssf_raycast (ssf_raycast.h): the resident index -- per slot the 64-byte record and the box of cells with the row's class, the
 // out-of-view blocks' live offsets, the oversize list; per bucket (+ 1) the list offsets and the fill's cursors; the (bucket -> slot)
 // lists; the sums and the box of indexed cells -- and the staging buffer of a call's host rays and outputs.  The index is valid
@@ -516,6 +527,7 @@ struct ssf_handle {
     NavFrontierWs navfrontier;                    // ssf_navfrontier_regions (ssf_navfrontier.h)
     NavPathWs navpath;                            // ssf_navpath_waypoints (ssf_navpath.h)
     NavLiveWs navlive;                            // ssf_navlive_overlay (ssf_navlive.h)
+    NavSteerWs navsteer;                          // ssf_navsteer_rollouts (ssf_navsteer.h)
     RaycastWs raycast;                            // ssf_raycast (ssf_raycast.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense); the out-of-view
                                                   // compaction keeps rows and order but moves slots: who keeps slot numbers also watches n_recentres (RaycastWs)

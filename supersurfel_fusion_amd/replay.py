@@ -217,7 +217,27 @@ def plan_cells(pose, res, cam_t, goals_m):
     return start, goals
 
 
-def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, plan=None, frontiers=None, waypoints=None, live=None):
+NAV_STEER_DT = 0.1                     # seconds per rollout step of --nav-steer
+
+
+def steer_pose(pose, res, cam_pose):
+    """the tracked camera projected into the grid whose 12 floats are `pose`, in the units of include/ssf_navsteer.h: its position
+    (1024 sub-units per cell) and the heading of its optical axis in the grid's plane (65536 per turn): 1 x 3 int32"""
+    R, t = np.asarray(pose[:9], np.float64).reshape(3, 3), np.asarray(pose[9:], np.float64)
+    cam = np.asarray(cam_pose, np.float64)
+    c = R.T @ (cam[9:12] - t)
+    z = R.T @ cam[[2, 5, 8]]                                               # the camera's viewing direction in the grid frame
+    yaw = float(np.arctan2(z[1], z[0]))
+    return np.array([[np.floor(c[0] / res * 1024.0), np.floor(c[1] / res * 1024.0), int(np.rint(yaw / (2.0 * np.pi) * 65536.0)) & 0xFFFF]]).astype(np.int32)
+
+
+def steer_lattice(speed, res):
+    """the lattice of --nav-steer: 9 speeds from 0 to `speed` m/s (capped at one cell per step of NAV_STEER_DT), the default 33 turn rates"""
+    top = min(1024, int(np.floor(speed * NAV_STEER_DT * 1024.0 / res)))
+    return dict(n_v=9, v_min=0, v_step=top // 8) if top >= 8 else dict(n_v=1, v_min=top, v_step=0)
+
+
+def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, plan=None, frontiers=None, waypoints=None, live=None, steer=None):
     """the navigation grid of the map, built on the device (include/ssf_navgrid.h) at the default size and frame (floor-aligned
     about the tracked camera) with cells of `res` metres: grid_dir/<k as %06d>.pgm -- the state in map_server's convention (205
     unknown, 254 free, 0 occupied; the image's top row is the grid's last) --, <k>.yaml beside it (map_server's keys; origin = the
@@ -235,7 +255,11 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
     int32: ix, iy, index into the path with bit 30 on a forced step, seg_min) and <k>_waypoints.json (stats, status, path_min).
     live (dict(depth=the depth image of the frame just processed, min_hits, stride)): that frame stamped onto the grid
     (include/ssf_navlive.h) from the tracked pose: <k>_live_state.npy and <k>_live_dist2.npy, and one log line with the stats; the
-    map's own grid, plan and regions above are written as without it"""
+    map's own grid, plan and regions above are written as without it.
+    steer (dict(horizon=steps, speed=metres per second), with a plan only): the velocity command of include/ssf_navsteer.h from the
+    tracked camera projected into the grid (steer_pose), over steer_lattice's candidates with steps of NAV_STEER_DT seconds, on the
+    live layer's state and dist2 when there is one and the grid's otherwise, with the plan's field as the cost and the plan's
+    radius: <k>_steer_traj.npy ((best_len, 3) int32: x, y, heading of the winner's arc) and one log line with the command and the stats"""
     if carve_views is None:
         out = fusion.nav_grid(outputs=("state", "dist2"), res=res)
     else:
@@ -255,6 +279,7 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
     np.save(os.path.join(grid_dir, name + "_dist2.npy"), out["dist2"])
     if carve_views is not None:
         np.save(os.path.join(grid_dir, name + "_seen.npy"), out["seen"])
+    lv = None
     if live is not None:
         lv = fusion.nav_live(live["depth"], state, outputs=("state", "dist2"), grid_pose=pose, res=res, min_hits=int(live.get("min_hits", 4)),
                              stride=int(live.get("stride", 4)))
@@ -280,6 +305,16 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
             np.save(os.path.join(grid_dir, name + "_waypoints.npy"), wp["waypoints"][0])
             with open(os.path.join(grid_dir, name + "_waypoints.json"), "w") as f:
                 json.dump(dict(wp["stats"], status=int(wp["status"][0]), path_min=int(wp["path_min"][0]), **kw), f, sort_keys=True)
+        if steer is not None:
+            on = lv if lv is not None else dict(state=state, dist2=out["dist2"])
+            st = fusion.nav_steer(on["state"], on["dist2"], steer_pose(pose, res, fusion.get_pose()), cost=got["cost"], min_dist2=cells * cells,
+                                  n_steps=int(steer.get("horizon", 32)), **steer_lattice(float(steer.get("speed", 0.5)), res))
+            np.save(os.path.join(grid_dir, name + "_steer_traj.npy"), st["best_traj"][0])
+            v, w = int(st["best_cmd"][0, 0]), int(st["best_cmd"][0, 1])
+            print("nav-steer %s: status=%d best=%d v=%d w=%d linear_x=%.4f angular_z=%.4f score=%d n_admissible=%d best_len=%d %s"
+                  % (name, int(st["pose_status"][0]), int(st["best"][0]), v, w, v * res / (1024.0 * NAV_STEER_DT), w * 2.0 * np.pi / (65536.0 * NAV_STEER_DT),
+                     int(st["best_score"][0]), int(st["n_admissible"][0]), int(st["best_len"][0]),
+                     " ".join("%s=%d" % (nm, n) for nm, n in st["stats"].items())))
     if frontiers is not None:
         import json
         start, _ = plan_cells(pose, res, fusion.get_pose()[9:12], [])
@@ -327,7 +362,7 @@ def write_laser_scan(fusion, scan_dir, k, beams):
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
            keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30, detect_motion=False,
            motion_mask_dir=None, odometry_prior=False, nav_grid_dir=None, nav_grid_every=30, nav_grid_res=0.05,
-           nav_grid_carve=False, nav_grid_carve_stride=8, nav_plan=None, nav_frontiers=None, nav_waypoints=None, nav_live=None, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
+           nav_grid_carve=False, nav_grid_carve_stride=8, nav_plan=None, nav_frontiers=None, nav_waypoints=None, nav_live=None, nav_steer=None, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
@@ -344,7 +379,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     plan from the camera's cell are written next to each grid.  nav_frontiers (write_nav_grid's frontiers): the frontier regions
     of each grid, ranked from the camera's cell, are written next to it.  nav_live (dict(min_hits, stride)): the depth image of the
     frame just processed is stamped onto each grid (write_nav_grid's live).  nav_waypoints (write_nav_grid's waypoints; needs nav_plan):
-    the plan's path reduced to waypoints is written next to it.
+    the plan's path reduced to waypoints is written next to it.  nav_steer (write_nav_grid's steer; needs nav_plan): the velocity command
+    from the tracked camera's pose on each grid is logged and its arc written next to it.
     laser_scan_dir: after frames 0, laser_scan_every, 2 laser_scan_every, ... a planar scan of laser_scan_beams beams from the tracked
     pose is written (write_laser_scan, numbered by frame); pipelined, submission pauses as for a render.
     keyframes: a dict of ssf_keyframes_params fields ({} = the defaults): the keyframe database is configured and
@@ -367,6 +403,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
         raise ValueError("nav_frontiers needs nav_grid_dir")
     if nav_live is not None and not nav_grid_dir:
         raise ValueError("nav_live needs nav_grid_dir")
+    if nav_steer is not None and nav_plan is None:
+        raise ValueError("nav_steer needs nav_plan")
     live_of = (lambda depth: dict(nav_live, depth=depth)) if nav_live is not None else (lambda depth: None)
     carve_views = (lambda: [r["pose"] for r in results]) if nav_grid_carve else (lambda: None)
     if odometry_prior:
@@ -419,7 +457,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
                 write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan, nav_frontiers,
-                               nav_waypoints, live_of(depth))
+                               nav_waypoints, live_of(depth), nav_steer)
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     else:
@@ -452,7 +490,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
                 write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan, nav_frontiers,
-                               nav_waypoints, live_of(last_depth))
+                               nav_waypoints, live_of(last_depth), nav_steer)
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     if out_path:
@@ -612,6 +650,11 @@ def parse_args(argv=None):
                          "obstacle layer); _live_state.npy and _live_dist2.npy are written next to the grid, and one log line with the stats")
     ap.add_argument("--nav-live-min-hits", type=int, default=None, metavar="N", help="points of the frame that make a cell occupied (default 4)")
     ap.add_argument("--nav-live-stride", type=int, default=None, metavar="S", help="pixel lattice of the see-through rays, 1..64 (default 4)")
+    ap.add_argument("--nav-steer", action="store_true",
+                    help="with --nav-plan-goal or --nav-plan-frontier: the velocity command from the tracked camera's pose on each grid, rolled out "
+                         "and scored on the device (include/ssf_navsteer.h): one nav-steer log line and <k>_steer_traj.npy per grid")
+    ap.add_argument("--nav-steer-horizon", type=int, default=None, metavar="T", help="steps of 0.1 s per rollout, 1..256 (default 32)")
+    ap.add_argument("--nav-steer-speed", type=float, default=None, metavar="V", help="the largest speed of the candidates in m/s, > 0 (default 0.5)")
     ap.add_argument("--laser-scan-dir", default=None, metavar="DIR",
                     help="every --laser-scan-every frames, a planar laser scan simulated from the map on the device, from the tracked pose: "
                          "DIR/<frame number as %%06d>.npy (ranges in metres, +inf where nothing is hit)")
@@ -658,6 +701,14 @@ def parse_args(argv=None):
         ap.error("--nav-live-min-hits is >= 1")
     if a.nav_live_stride is not None and not 1 <= a.nav_live_stride <= 64:
         ap.error("--nav-live-stride is 1..64")
+    if a.nav_steer and not (a.nav_plan_goal or a.nav_plan_frontier):
+        ap.error("--nav-steer goes with --nav-plan-goal or --nav-plan-frontier")
+    if (a.nav_steer_horizon is not None or a.nav_steer_speed is not None) and not a.nav_steer:
+        ap.error("--nav-steer-horizon and --nav-steer-speed go with --nav-steer")
+    if a.nav_steer_horizon is not None and not 1 <= a.nav_steer_horizon <= 256:
+        ap.error("--nav-steer-horizon is 1..256")
+    if a.nav_steer_speed is not None and not a.nav_steer_speed > 0.0:
+        ap.error("--nav-steer-speed is > 0")
     if (a.nav_frontier_min_cells is not None or a.nav_frontier_gain_radius is not None) and not a.nav_frontiers:
         ap.error("--nav-frontier-min-cells and --nav-frontier-gain-radius go with --nav-frontiers")
     if a.nav_frontier_min_cells is not None and a.nav_frontier_min_cells < 1:
@@ -689,6 +740,13 @@ def nav_live_of(a):
     return dict(min_hits=4 if a.nav_live_min_hits is None else int(a.nav_live_min_hits), stride=4 if a.nav_live_stride is None else int(a.nav_live_stride))
 
 
+def nav_steer_of(a):
+    """replay()'s nav_steer from the parsed options, or None"""
+    if not a.nav_steer:
+        return None
+    return dict(horizon=32 if a.nav_steer_horizon is None else int(a.nav_steer_horizon), speed=0.5 if a.nav_steer_speed is None else float(a.nav_steer_speed))
+
+
 def nav_frontiers_of(a):
     """replay()'s nav_frontiers from the parsed options, or None"""
     if not a.nav_frontiers:
@@ -700,9 +758,9 @@ def nav_frontiers_of(a):
 def main():
     a = parse_args()
     from . import binding
-    plan, frontiers, waypoints, live = nav_plan_of(a), nav_frontiers_of(a), nav_waypoints_of(a), nav_live_of(a)
-    # (the carve's, the plan's, the regions', the waypoints' and the live layer's entry points: libraries of their own)
-    lib = binding.load_live() if live else binding.load_drive() if waypoints else binding.load_explore() if frontiers else (binding.load_nav() if plan else (binding.load_navcarve() if a.nav_grid_carve else binding.load_product()))
+    plan, frontiers, waypoints, live, steer = nav_plan_of(a), nav_frontiers_of(a), nav_waypoints_of(a), nav_live_of(a), nav_steer_of(a)
+    # (the carve's, the plan's, the regions', the waypoints', the live layer's and the commands' entry points: libraries of their own)
+    lib = binding.load_steer() if steer else binding.load_live() if live else binding.load_drive() if waypoints else binding.load_explore() if frontiers else (binding.load_nav() if plan else (binding.load_navcarve() if a.nav_grid_carve else binding.load_product()))
     cfg = lib.default_config(pipeline_depth=2 if a.pipelined else 0, extract_batch=4 if a.pipelined else 1, **BENCHMARK_LAUNCH)
     f = binding.Fusion(lib, cfg)
     if a.raw_frames:
@@ -715,7 +773,7 @@ def main():
                         keyframe_log=a.keyframe_log, detect_motion=a.detect_motion, motion_mask_dir=a.motion_mask_dir,
                         odometry_prior=a.odometry_prior, nav_grid_dir=a.nav_grid_dir, nav_grid_every=a.nav_grid_every,
                         nav_grid_res=a.nav_grid_res, nav_grid_carve=a.nav_grid_carve, nav_grid_carve_stride=a.nav_grid_carve_stride, nav_plan=plan,
-                        nav_frontiers=frontiers, nav_waypoints=waypoints, nav_live=live,
+                        nav_frontiers=frontiers, nav_waypoints=waypoints, nav_live=live, nav_steer=steer,
                         laser_scan_dir=a.laser_scan_dir, laser_scan_every=a.laser_scan_every,
                         laser_scan_beams=a.laser_scan_beams)
     if a.keyframes and not a.keyframe_log:
