@@ -17,7 +17,8 @@
  *      0xFFFFFFFF = not reached.  p = iy * width + ix.  dist2 and cost may be NULL (steps 1, 3, 4).
  *   1. Member.  member[p] = state[p] == 0 && some 4-neighbour inside the grid has state -1: step 4 of ssf_navplan.h, word for
  *      word.  With traversable_only, dist2[p] >= min_dist2 is required as well.  dist2 == NULL is allowed only with
- *      traversable_only == 0.
+ *      traversable_only == 0.  A state other than 0, -1 and 100 (1..99, 101..127, -2..-128) is no member, makes no member of its
+ *      neighbour, does not stop a ray of step 6 and is not counted by one; a negative dist2 is below every min_dist2.
  *   2. Regions.  The connected components of the members under `connectivity`: 8 (the default: the eight neighbours) or 4 (the
  *      four axial ones).  A region's label is the smallest p among its cells, so the labelling has one answer whatever order the
  *      hardware works in.

@@ -13,7 +13,8 @@
  *      ssf_navgrid_build / ssf_navgrid_carve write.  p = iy * width + ix.  path (n_paths x max_path x 2 int32, (ix, iy)) and path_len
  *      (n_paths int32): exactly what ssf_navplan_field writes; entries past path_len are not read.
  *   1. Traversable.  As step 1 of ssf_navplan.h: trav[p] = (state[p] == 0 || (allow_unknown && state[p] == -1)) &&
- *      dist2[p] >= min_dist2.  d(p) = max(dist2[p], 0).  Cells outside the grid are not traversable.
+ *      dist2[p] >= min_dist2.  d(p) = max(dist2[p], 0).  Cells outside the grid are not traversable, nor is a cell of any other
+ *      state (1..99, 101..127, -2..-128) or of negative dist2, whatever allow_unknown.
  *   2. Path check.  L = path_len[i].  Status 1: L < 0 or L > max_path.  Status 2: some cell of the path is outside the grid or not
  *      traversable.  Status 3: two consecutive cells are not distinct 8-neighbours (their Chebyshev distance is not 1).  The
  *      smallest applicable status wins.  Such a path gets 0 waypoints and path_min -1; the other paths of the call are unaffected.

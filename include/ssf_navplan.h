@@ -15,7 +15,9 @@
  *      Note that dist2 is capped at the grid's max_dist_cells^2: min_dist2 or soft_dist2 above that cap ask for more clearance
  *      than the grid ever reports.
  *   1. Traversable.  trav[p] = (state[p] == 0 || (allow_unknown && state[p] == -1)) && dist2[p] >= min_dist2.  min_dist2 >= 0 is
- *      the robot's squared radius in cells.  Cells outside the grid are not traversable.
+ *      the robot's squared radius in cells.  Cells outside the grid are not traversable.  A cell of any other state (1..99 of a
+ *      nav_msgs/OccupancyGrid, 101..127, -2..-128) is neither free nor unknown: not traversable whatever allow_unknown, and no
+ *      frontier's neighbour (step 4); a negative dist2 is below every min_dist2.
  *   2. Penalty.  pen[p] = soft_dist2 > 0 ? near_penalty * (soft_dist2 - min(dist2[p], soft_dist2)) / soft_dist2 : 0 (integer
  *      division; a negative dist2, which no grid call writes, counts as 0).  0 <= near_penalty <= 1000 and
  *      0 <= soft_dist2 <= 1024 * 1024, so the product fits an int32.

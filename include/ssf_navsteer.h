@@ -25,7 +25,8 @@
  *   2. Candidates.  K = n_v * n_w, candidate c = i * n_w + j has v = v_min + i * v_step, w = w_min + j * w_step.  v_abs_max is the
  *      largest |v| of the lattice.
  *   3. Traversable.  As step 1 of ssf_navplan.h: trav[p] = (state[p] == 0 || (allow_unknown && state[p] == -1)) &&
- *      dist2[p] >= min_dist2.  Cells outside the grid are not traversable.  d(p) = min(max(dist2[p], 0), clearance_cap).
+ *      dist2[p] >= min_dist2.  Cells outside the grid are not traversable.  d(p) = min(max(dist2[p], 0), clearance_cap).  A cell of
+ *      any other state (1..99, 101..127, -2..-128) or of negative dist2 is not traversable, whatever allow_unknown.
  *   4. Rollout of one candidate from one pose (x, y, h).  If the start cell is outside the grid or not traversable: free_steps = 0,
  *      min_d = -1, the end is the start, and the candidate is inadmissible.  Otherwise min_d = d(start cell) and, for each of the
  *      n_steps steps:

@@ -274,3 +274,49 @@ def fnv1a(data, h=1469598103934665603):
     for b in bytes(data):
         h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
     return h
+
+
+# ---- grids as a caller may hand them over: states outside {0, -1, 100}, dist2 outside 0 .. the cap ---------------------------------------
+ODD_STATES = (1, 50, 99, 101, 127, -2, -128)                            # nav_msgs/OccupancyGrid allows 1..99; the rest is what an int8 can hold
+ODD_DIST2 = (-1, -7, -(1 << 31), 0, 41, 1 << 20, (1 << 20) + 1, (1 << 31) - 1)
+FOREIGN_SIZES = ((45, 70), (64, 65))                                     # (h, w); 65 cells wide: three tile columns, two tile rows
+
+
+def foreign_grid(h, w, seed):
+    """(state, dist2): about two thirds plain free cells, a tenth unknown, a twelfth occupied and a seventh drawn from ODD_STATES; dist2
+    in 1..40 but for a sixth of the cells, which draw from ODD_DIST2.  Every call states what it does with such values (the headers'
+    step 1): only 0 is free, only -1 is unknown, only 100 stops a gain ray, and a negative dist2 is below every min_dist2."""
+    rng = np.random.default_rng(seed)
+    u = rng.random((h, w))
+    odd = np.array(ODD_STATES, np.int64)[rng.integers(0, len(ODD_STATES), (h, w))]
+    state = np.where(u < 0.68, 0, np.where(u < 0.78, -1, np.where(u < 0.86, 100, odd))).astype(np.int8)
+    dist2 = rng.integers(1, 41, (h, w)).astype(np.int64)
+    pick = np.array(ODD_DIST2, np.int64)[rng.integers(0, len(ODD_DIST2), (h, w))]
+    return state, np.where(rng.random((h, w)) < 0.16, pick, dist2).astype(np.int32)
+
+
+def plain_grid(state, dist2):
+    """foreign_grid's arrays with every odd value replaced by the plain one a careless reader would take it for: an odd state is free,
+    a dist2 outside 0..40 is 40.  The CPU guards plan on both: where the answers differ, an odd value decided an outcome."""
+    return (np.where(np.isin(state, (0, -1, 100)), state, 0).astype(np.int8),
+            np.where((dist2 < 0) | (dist2 > 40), 40, dist2).astype(np.int32))
+
+
+_FOREIGN = {}
+
+
+def foreign_case(h, w, allow_unknown):
+    """the inputs of the foreign-grid cases of the four GPU files and the plan's restatement on them, computed once and shared (the
+    callers leave it unchanged): dict(state, dist2, goals, starts, kw, plan, frontier_plan)"""
+    key = (h, w, allow_unknown)
+    if key not in _FOREIGN:
+        state, dist2 = foreign_grid(h, w, 7000 + 10 * h + w)
+        rng = np.random.default_rng(h * w + allow_unknown)
+        goals = [(w // 2, h // 2), (3, h - 4), (w - 3, 2)]
+        for gx, gy in goals:                                             # the goals stand on plain free cells: every case plans something
+            state[gy, gx], dist2[gy, gx] = 0, 9
+        starts = np.stack([rng.integers(0, w, 10), rng.integers(0, h, 10)], axis=1).astype(np.int32)
+        kw = dict(allow_unknown=allow_unknown, soft_dist2=30, near_penalty=40, max_path=h * w)
+        _FOREIGN[key] = dict(state=state, dist2=dist2, goals=goals, starts=starts, kw=kw, plan=plan(state, dist2, goals, starts, **kw),
+                             frontier_plan=plan(state, dist2, None, starts, goals_from_frontier=1, min_dist2=2, **kw))
+    return _FOREIGN[key]

@@ -308,3 +308,100 @@ def big_scene():
     state[40:80, 60] = 100
     poses = np.array([centre(30, 60, 0), centre(1, 1, 8192), centre(90, 30, 30000)], np.int32)
     return dict(state=state, dist2=clearance(state), cost=None, poses=poses, targets=None, c=c)
+
+
+I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
+MIXED_EDGE_STAGED, MIXED_EDGE_WALKED, MIXED_CORNER, MIXED_CENTRAL = 0, 1, 2, 3            # mixed_scene's hand-placed poses
+MIXED_LIVE = 400
+
+
+def mixed_scene(n_poses=1281):
+    """78 x 120 inside a wall with one bar across it, T = 38 at |v| = 1024: R = 39, the clipped bound is 78 x 79 = 6162 cells and a
+    workgroup's LDS 28904 B, more than leaves a CU its eight workgroups, so from 1281 workgroups on (K = 16: one per pose) the launch
+    stages only the windows of up to 4056 cells and walks the others.  centre(38, 12) has a 78 x 52 = 4056-cell window, centre(38, 13)
+    one of 78 x 53 = 4134; then a corner, the middle (the whole width, 79 rows), MIXED_LIVE poses at random in the grid, and the rest
+    outside the grid or in the wall: they end at once but count as workgroups.  n_poses = 1280 drops one of those."""
+    W, H = 78, 120
+    c = params(width=W, height=H, n_poses=n_poses, n_v=2, n_w=8, v_min=-1024, v_step=2048, w_min=-1792, w_step=512, n_steps=38, cost_weight=0,
+               turn_weight=1)
+    state = np.zeros((H, W), np.int8)
+    state[0, :] = state[-1, :] = 100
+    state[:, 0] = state[:, -1] = 100
+    state[70, 15:60] = 100
+    rng = np.random.default_rng(78120)
+    poses = [centre(38, 12, 16384), centre(38, 13, 16384), centre(1, 1, 8192), centre(38, 60, 49152)]
+    poses += [(int(rng.integers(SUB, (W - 1) * SUB)), int(rng.integers(SUB, (H - 1) * SUB)), int(rng.integers(0, TURN))) for _ in range(MIXED_LIVE)]
+    k = 0
+    while len(poses) < 1281:
+        poses.append(((-3 - k) * SUB, 5 * SUB, k) if k % 2 else centre(k % W, 0, k))           # outside / in the top wall
+        k += 1
+    return dict(state=state, dist2=clearance(state), cost=None, poses=np.array(poses[:n_poses], np.int32), targets=None, c=c)
+
+
+def lattice_scene(tie):
+    """K = 65536 on the 33 x 31 room, two steps, two poses: open floor, and a wall one cell behind the robot.
+    tie False: the score is (v_abs_max - |v|) + |w| with the fastest row and the straightest column last: c = 65535 alone has score 0
+    on the open floor; the other pose faces the wall, where the fast rows collide.
+    tie True: the score is v_abs_max - |v| with v = -1020 .. 1020: rows 0 and 255 tie wherever both are admissible, so on the open
+    floor c = 0 wins a tie of 512 that spans the first and the last chunk; with the wall behind, row 0 collides, and c = 65280 wins
+    the tie of the last row, c = 65535 among it."""
+    W, H = 33, 31
+    kw = dict(n_v=256, n_w=256, v_min=-1020, v_step=8, w_min=-512, w_step=4, turn_weight=0) if tie else \
+         dict(n_v=256, n_w=256, v_min=0, v_step=4, w_min=-16320, w_step=64, turn_weight=1)
+    c = params(width=W, height=H, n_poses=2, n_steps=2, cost_weight=0, clear_weight=0, speed_weight=1, **kw)
+    state = room(W, H, 21)
+    poses = np.array([centre(24, 15, 0), centre(1, 15, 0 if tie else 32768)], np.int32)                 # (without the tie it faces the wall)
+    return dict(state=state, dist2=clearance(state), cost=None, poses=poses, targets=None, c=c)
+
+
+EXTREME_POSES = ((I32_MIN, 0, 0), (I32_MAX, I32_MAX, -1), (0, I32_MIN, 65536))
+
+
+def wide_scene(extremes=True):
+    """the widest scores the call allows, on the 33 x 31 room: every weight 1000, clearance_cap 1024 * 1024, a cost field set by hand
+    (0xFFFF0000 .. 0xFFFFFFFE, a sixth of the cells unreached), targets at the corners of the int32 square, dist2 0 on a tenth of the
+    cells; with extremes, EXTREME_POSES stand among the live poses (at 2, 5 and the end)."""
+    W, H = 33, 31
+    rng = np.random.default_rng(44)
+    state = room(W, H, 22)
+    dist2 = clearance(state)
+    dist2[rng.random((H, W)) < 0.1] = 0
+    cost = rng.integers(0xFFFF0000, 0xFFFFFFFF, (H, W)).astype(np.uint32)
+    cost[rng.random((H, W)) < 0.05] = 0xFFFFFFFE
+    cost[rng.random((H, W)) < 0.16] = NO_COST
+    live = [centre(16, 17, 65535), centre(1, 1, 8192), centre(24, 15, 32768), centre(8, 25, 50000), centre(28, 5, 20000), centre(16, 6, 0),
+            centre(3, 3, 0)]
+    live += [(int(rng.integers(SUB, (W - 1) * SUB)), int(rng.integers(SUB, (H - 1) * SUB)), int(rng.integers(-TURN, 2 * TURN))) for _ in range(5)]
+    poses = live[:2] + [EXTREME_POSES[0]] + live[2:4] + [EXTREME_POSES[1]] + live[4:] + [EXTREME_POSES[2]] if extremes else live
+    corners = [(I32_MIN, I32_MAX), (I32_MAX, I32_MIN), (I32_MIN + 1, I32_MAX - 1), (I32_MAX - 3, I32_MIN + 2), (I32_MIN, I32_MIN), (I32_MAX, I32_MAX)]
+    targets = np.array([corners[q % len(corners)] for q in range(len(poses))], np.int32)
+    c = params(width=W, height=H, n_poses=len(poses), n_v=4, n_w=16, v_min=-256, v_step=256, w_min=-16384, w_step=2048, n_steps=12,
+               clearance_cap=1024 * 1024, cost_weight=1000, target_weight=1000, clear_weight=1000, speed_weight=1000, turn_weight=1000)
+    return dict(state=state, dist2=dist2, cost=cost, poses=np.array(poses, np.int32), targets=targets, c=c)
+
+
+def foreign_scene(h, w, allow_unknown):
+    """rollouts down the cost field planned on navplan_ref.foreign_grid (states outside {0, -1, 100}, dist2 negative and above the
+    cap): the plan's own restatement supplies the field"""
+    import navplan_ref as pr
+    f = pr.foreign_case(h, w, allow_unknown)
+    state, dist2 = f["state"], f["dist2"]
+    rng = np.random.default_rng(h + w + allow_unknown)
+    trav, _ = traversable(state, dist2, dict(allow_unknown=allow_unknown, min_dist2=0, clearance_cap=20))
+    iy, ix = np.nonzero(trav)
+    at = rng.choice(len(ix), 10, replace=False)
+    poses = [(int(ix[k]) * SUB + int(rng.integers(0, SUB)), int(iy[k]) * SUB + int(rng.integers(0, SUB)), int(rng.integers(0, TURN))) for k in at]
+    odd = np.argwhere(~np.isin(state, (0, -1, 100)))
+    poses += [centre(int(odd[0][1]), int(odd[0][0])), (w * SUB, 0, 0)]         # on a cell of an odd state: status 2; outside: status 1
+    c = params(width=w, height=h, n_poses=len(poses), allow_unknown=allow_unknown, clearance_cap=20, n_steps=16, v_step=96, brake_div=256)
+    return dict(state=state, dist2=dist2, cost=f["plan"]["cost"], poses=np.array(poses, np.int32), targets=None, c=c)
+
+
+def scene_reference(key, make):
+    """rollouts() of make(), computed once under `key` and shared (the callers leave it unchanged): (inputs, outputs)"""
+    if key not in _WANT:
+        i = make()
+        c = i["c"]
+        _WANT[key] = (i, rollouts(i["state"], i["dist2"], i["cost"] if c["cost_weight"] else None, i["poses"],
+                                  i["targets"] if c["target_weight"] else None, c))
+    return _WANT[key]

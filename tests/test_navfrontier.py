@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import navfrontier_ref as fr
+import navplan_ref as pr
 from conftest import ROOT
 from supersurfel_fusion_amd import binding, replay
 
@@ -275,3 +276,44 @@ def test_distinct_cells_against_one_list_per_ray(seed):
             assert distinct == fr.gain(state, int(ox), int(oy), R) <= visits
             shared += visits > distinct
     assert shared > 10                                                   # many rays share their first cells
+
+
+# ---- grids with values outside {0, -1, 100} (tests/navplan_ref.py's foreign grid, the GPU file's foreign cases) -------------------------
+def test_what_the_regions_do_with_an_odd_state_by_hand():
+    """a member is a cell of state 0 beside a cell of state -1: no other negative state makes one, and no other state is one; a gain ray
+    stops at 100 alone and counts -1 alone"""
+    for odd in pr.ODD_STATES:
+        state = np.array([[0, odd, 0, -1, odd]], np.int8)
+        got = fr.frontiers(state)
+        assert got["region"].tolist() == [[-1, -1, 0, -1, -1]] and got["stats"]["frontier_cells"] == 1, odd
+        # from (2, 0) with R = 2: the ray to the right passes -1 and the odd cell; the ray to the left passes the odd cell and a free one
+        assert fr.ray_cells(state, 2, 0, 2, 0, 2) == [(3, 0), (4, 0)] and fr.ray_cells(state, 2, 0, -2, 0, 2) == [(1, 0), (0, 0)] and fr.gain(state, 2, 0, 2) == 1
+    state = np.array([[0, 100, -1, 0, -1, 100, -1]], np.int8)
+    assert fr.gain(state, 3, 0, 3) == 2 and fr.ray_cells(state, 3, 0, 3, 0, 3) == [(4, 0)]
+    state, dist2 = np.array([[0, -1, 0]], np.int8), np.array([[-5, 3, (1 << 31) - 1]], np.int32)       # a negative dist2 is below min_dist2 = 0
+    assert fr.frontiers(state, dist2, traversable_only=1)["region"].tolist() == [[-1, -1, 0]]
+    assert fr.frontiers(state, dist2)["stats"]["frontier_cells"] == 2
+
+
+@pytest.mark.parametrize("h,w", pr.FOREIGN_SIZES)
+def test_the_foreign_grids_odd_values_decide_the_regions(h, w):
+    f = pr.foreign_case(h, w, 0)
+    state, dist2, cost = f["state"], f["dist2"], f["plan"]["cost"]
+    kw = dict(min_cells=2, reachable_only=1, gain_radius=4, gain_weight=5, size_weight=2, traversable_only=1)
+    got = fr.frontiers(state, dist2, cost, **kw)
+    s = got["stats"]
+    assert s["regions_kept"] >= 5 and s["regions_small"] >= 1 and s["regions_unreached"] >= 1 and max(r["gain"] for r in got["regions"]) > 3
+    # a free cell whose only negative 4-neighbours are -2 or -128 is no member
+    def beside(mask):
+        m = np.pad(mask, 1, constant_values=False)
+        return m[1:-1, 2:] | m[1:-1, :-2] | m[2:, 1:-1] | m[:-2, 1:-1]
+    lone = (state == 0) & beside((state == -2) | (state == -128)) & ~beside(state == -1)
+    assert lone.sum() > 10 and (got["region"][lone] == -1).all()
+    assert ((state == 0) & (dist2 < 0) & beside(state == -1)).any() and (got["region"][(state == 0) & (dist2 < 0)] == -1).all()
+    # the rays pass cells of odd states: with those cells occupied the gains are smaller
+    walls = np.where(np.isin(state, (0, -1)), state, 100).astype(np.int8)
+    reps = [(r["rep_x"], r["rep_y"]) for r in got["regions"]]
+    assert sum(fr.gain(walls, x, y, 4) for x, y in reps) < sum(fr.gain(state, x, y, 4) for x, y in reps)
+    # ... and cells of state -2 and -128, which are not counted
+    minus = np.where(state < -1, -1, state).astype(np.int8)
+    assert sum(fr.gain(minus, x, y, 4) for x, y in reps) > sum(r["gain"] for r in got["regions"])

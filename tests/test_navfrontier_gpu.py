@@ -88,6 +88,22 @@ def test_random_grids(h, w, fusion):
     assert (no_cost["regions"]["rep_cost"] == INF).all() and no_cost["stats"]["frontier_cells"] == plain["stats"]["frontier_cells"]
 
 
+@pytest.mark.parametrize("h,w", pr.FOREIGN_SIZES)
+@pytest.mark.parametrize("allow", [0, 1])
+def test_grids_with_states_outside_0_minus_1_100(h, w, allow, fusion):
+    """tests/navplan_ref.py's foreign grid with the field planned on it: a member is a cell of state 0 beside one of state -1 (-2 and
+    -128 make none), a negative dist2 is below min_dist2 = 0, a gain ray stops at 100 alone and counts -1 alone"""
+    f = pr.foreign_case(h, w, allow)
+    state, dist2, cost = f["state"], f["dist2"], f["plan"]["cost"]
+    for conn in (8, 4):
+        what = "foreign %d x %d unknown %d connectivity %d" % (h, w, allow, conn)
+        check(fusion, what, state, dist2, cost, connectivity=conn, gain_radius=2)
+        got, want = check(fusion, what + " filtered", state, dist2, cost, connectivity=conn, min_cells=2, reachable_only=1, gain_radius=4, gain_weight=5,
+                          size_weight=2, traversable_only=1)
+        assert want["stats"]["regions_kept"] >= 5 and want["stats"]["regions_small"] + want["stats"]["regions_unreached"] >= 2
+        assert int(got["regions"]["gain"].max()) > 3
+
+
 def two_members(a, b, size=64):
     """walls everywhere but two free cells a and b, each with an unknown cell on its far side: the only members"""
     state = np.full((size, size), 100, np.int8)

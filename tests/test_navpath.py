@@ -328,3 +328,41 @@ def test_the_waypoints_are_an_increasing_subsequence_whose_unforced_segments_are
                 assert seg_min >= min(q["clearance_cap"], run)           # the shortcut keeps the clearance of the piece it replaces
     assert forced == got["stats"]["forced_steps"] and (forced > 0) == (q["los_dist2"] > 0)
     assert got["stats"]["waypoints"] == sum(len(w) for w in got["waypoints"]) < got["stats"]["cells_in"] == sum(len(p) for p in paths)
+
+
+# ---- grids with values outside {0, -1, 100} and dist2 outside 0 .. the cap (the GPU file's foreign cases) ------------------------------
+def test_what_the_waypoints_do_with_an_odd_state_or_dist2_by_hand():
+    """a path over a cell of an odd state, or of negative dist2, is status 2 whether unknown cells are allowed or not; such a cell beside
+    the path hides what lies behind it; d is max(dist2, 0), uncapped: INT32_MAX stays INT32_MAX"""
+    row = np.array([(x, 0) for x in range(5)], np.int32)
+    for allow in (0, 1):
+        for odd in pr.ODD_STATES:
+            state, dist2 = wr.open_grid(2, 5, 7)
+            state[0, 2] = odd
+            got = wr.waypoints(state, dist2, [row, row[:2]], allow_unknown=allow)
+            assert got["status"].tolist() == [2, 0] and got["n_waypoints"].tolist() == [0, 2] and got["path_min"].tolist() == [-1, 7], (odd, allow)
+            round_it = np.array([(0, 0), (1, 1), (2, 1), (3, 1), (4, 0)], np.int32)      # the straight line back crosses the odd cell
+            got = wr.waypoints(state, dist2, [round_it], allow_unknown=allow)
+            assert got["status"].tolist() == [0] and got["n_waypoints"][0] > 2 and got["stats"]["forced_steps"] == 0
+        state, dist2 = wr.open_grid(2, 5, 7)
+        dist2[0, 2] = -3
+        assert wr.waypoints(state, dist2, [row], allow_unknown=allow)["status"].tolist() == [2]
+    state, dist2 = wr.open_grid(1, 5, (1 << 31) - 1)
+    got = wr.waypoints(state, dist2, [row], keep_clearance=1, clearance_cap=1 << 20)
+    assert got["waypoints"][0].tolist() == [[0, 0, 0, (1 << 31) - 1], [4, 0, 4, (1 << 31) - 1]] and got["path_min"].tolist() == [(1 << 31) - 1]
+
+
+@pytest.mark.parametrize("h,w", pr.FOREIGN_SIZES)
+@pytest.mark.parametrize("allow", [0, 1])
+def test_the_foreign_grids_odd_values_decide_the_waypoints(h, w, allow):
+    f = pr.foreign_case(h, w, allow)
+    state, dist2, paths = f["state"], f["dist2"], f["plan"]["path"]
+    assert sum(len(p) > 10 for p in paths) >= 2
+    kw = dict(allow_unknown=allow, keep_clearance=1, clearance_cap=12, los_dist2=2)
+    got = wr.waypoints(state, dist2, paths, **kw)
+    assert (got["status"] == 0).all() and got["stats"]["waypoints"] > 2 * len(paths)
+    plain_state, plain_dist2 = pr.plain_grid(state, dist2)
+    fewer = wr.waypoints(plain_state, dist2, paths, **kw)                 # with the odd cells free, more is seen: fewer waypoints
+    assert fewer["stats"]["waypoints"] < got["stats"]["waypoints"]
+    other = wr.waypoints(state, np.where(dist2 < 0, 40, dist2), paths, **kw)        # likewise the cells of negative dist2
+    assert other["stats"]["waypoints"] < got["stats"]["waypoints"]

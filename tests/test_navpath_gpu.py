@@ -98,6 +98,28 @@ def test_planned_paths_under_every_rule(h, w, fusion):
               lookahead=9)
 
 
+@pytest.mark.parametrize("h,w", pr.FOREIGN_SIZES)
+@pytest.mark.parametrize("allow", [0, 1])
+def test_paths_planned_on_grids_with_states_outside_0_minus_1_100_and_dist2_outside_the_cap(h, w, allow, fusion):
+    """tests/navplan_ref.py's foreign grid and the paths planned on it: a cell of any state but 0 (and -1 when allowed) or of negative
+    dist2 hides what lies behind it; d is max(dist2, 0), whatever its size"""
+    f = pr.foreign_case(h, w, allow)
+    state, dist2 = f["state"], f["dist2"]
+    plan = fusion.nav_plan(state, dist2, f["goals"], f["starts"], outputs=("path", "path_len"), **f["kw"])
+    paths = plan["path"]
+    assert len(paths) == len(f["plan"]["path"]) and all((a == b).all() for a, b in zip(paths, f["plan"]["path"])) and sum(len(p) > 10 for p in paths) >= 2
+    what = "foreign %d x %d unknown %d" % (h, w, allow)
+    got, _ = check(fusion, what + " defaults", state, dist2, paths, allow_unknown=allow)
+    assert (got["status"] == 0).all() and got["stats"]["forced_steps"] == 0
+    check(fusion, what + " keep_clearance, los", state, dist2, paths, allow_unknown=allow, keep_clearance=1, clearance_cap=12, los_dist2=2)
+    check(fusion, what + " the largest cap, a window of 9", state, dist2, paths, allow_unknown=allow, keep_clearance=1, clearance_cap=1024 * 1024, lookahead=9)
+    got, _ = check(fusion, what + " los above the paths' clearance", state, dist2, paths, allow_unknown=allow, los_dist2=41)
+    assert got["stats"]["forced_steps"] > 0
+    if allow:                                                            # the same paths where unknown cells are not allowed
+        strict, _ = check(fusion, what + " unknown refused", state, dist2, paths)
+        assert (strict["status"] == 2).any()
+
+
 # ---- the edges of the window and of the chunks ---------------------------------------------------------------------------------
 LENGTHS = (1, 2, 63, 64, 65, 255, 256, 257, 258, 513, 4097)
 LOOKAHEADS = (1, 2, 255, 256, 257, 4096)

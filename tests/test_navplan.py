@@ -259,3 +259,52 @@ def test_a_goal_on_a_tile_edge_wakes_the_neighbour_tile():
         goal, _ = pr.goal_cells(trav, frontier, [cell], q)
         got, rounds, _ = pr.field_by_tile_rounds(trav, pen, goal, stale=True)
         assert np.array_equal(got, pr.field(trav, pen, goal)), cell
+
+
+# ---- grids with values outside {0, -1, 100} and dist2 outside 0 .. the cap (the GPU files' foreign cases) -------------------------------
+def test_what_the_plan_does_with_an_odd_state_or_a_negative_dist2_by_hand():
+    """only 0 is free and only -1 is unknown, whatever allow_unknown; a negative dist2 is below min_dist2 = 0 and pays the full penalty"""
+    for allow in (0, 1):
+        for odd in pr.ODD_STATES:
+            state, dist2 = pr.open_grid(1, 5)
+            state[0, 2] = odd                                            # a corridor of one row with the odd cell in the way
+            got = pr.plan(state, dist2, [(4, 0)], [(0, 0), (2, 0), (3, 0)], allow_unknown=allow, max_path=9)
+            assert got["start_status"].tolist() == [3, 2, 0] and got["stats"]["cells_reached"] == 2 and got["stats"]["frontier_cells"] == 0, (odd, allow)
+        state, dist2 = pr.open_grid(1, 5)
+        dist2[0, 2] = -1
+        assert pr.plan(state, dist2, [(4, 0)], [(0, 0)], allow_unknown=allow)["start_status"].tolist() == [3]
+    state, dist2 = pr.open_grid(1, 3)
+    dist2[0, 1] = (1 << 31) - 1                                          # far above soft_dist2: no penalty
+    assert pr.plan(state, dist2, [(2, 0)], [(0, 0)], soft_dist2=30, near_penalty=40)["start_cost"].tolist() == [20]
+    state[0, 1], dist2[0, 1] = -1, -(1 << 31)                            # unknown and allowed, but its dist2 is negative
+    assert pr.plan(state, dist2, [(2, 0)], [(0, 0)], allow_unknown=1)["start_status"].tolist() == [3]
+    assert pr.prep(state, dist2, pr.params(soft_dist2=30, near_penalty=40))[1][0, 1] == 40
+
+
+@pytest.mark.parametrize("h,w", pr.FOREIGN_SIZES)
+@pytest.mark.parametrize("allow", [0, 1])
+def test_the_foreign_grids_odd_values_decide_the_plan(h, w, allow):
+    f = pr.foreign_case(h, w, allow)
+    state, dist2, got = f["state"], f["dist2"], f["plan"]
+    assert set(np.unique(state).tolist()) == set(pr.ODD_STATES) | {0, -1, 100} and set(pr.ODD_DIST2) <= set(np.unique(dist2).tolist())
+    assert (w + 31) // 32 == 3 and (h + 31) // 32 == 2
+    s = got["stats"]
+    assert s["cells_reached"] > h * w // 3 and (got["start_status"] == 0).sum() >= 2 and max(got["path_len"]) > 10 and s["frontier_cells"] > 100
+    assert f["frontier_plan"]["stats"]["frontier_goals"] > 100 and (f["frontier_plan"]["start_status"] == 0).any()
+    reached = np.pad(got["cost"] != pr.INF, 1, constant_values=False)
+    beside = reached[1:-1, 2:] | reached[1:-1, :-2] | reached[2:, 1:-1] | reached[:-2, 1:-1]          # a reached 4-neighbour
+    for odd in pr.ODD_STATES:                                            # every odd state stands in the field's way somewhere
+        assert ((state == odd) & beside & (got["cost"] == pr.INF)).any(), odd
+    assert ((state == 0) & (dist2 < 0) & beside & ~got["trav"]).any()    # a free cell of negative dist2 does
+    # taken for plain values, the same grid plans otherwise: a shorter path where a cell of state 50 stood
+    plain_state, plain_dist2 = pr.plain_grid(state, dist2)
+    fifty = np.where(state == 50, 0, state).astype(np.int8)
+    other = pr.plan(fifty, dist2, f["goals"], f["starts"], **f["kw"])
+    ok = (got["start_status"] == 0) & (other["start_status"] == 0)
+    assert (other["start_cost"][ok] < got["start_cost"][ok]).any() or (other["start_status"] == 0).sum() > (got["start_status"] == 0).sum()
+    assert (pr.plan(plain_state, dist2, f["goals"], **f["kw"])["cost"] != got["cost"]).any()
+    assert (pr.plan(state, plain_dist2, f["goals"], **f["kw"])["cost"] != got["cost"]).any()
+    # a cell of state -2 or -128 beside a free cell makes no frontier; taken for unknown it would
+    minus = np.where((state == -2) | (state == -128), -1, state).astype(np.int8)
+    more = pr.prep(minus, dist2, pr.params(**f["kw"]))[2]
+    assert (more >= got["frontier"]).all() and int(more.sum()) > int(got["frontier"].sum())

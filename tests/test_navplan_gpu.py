@@ -1,6 +1,6 @@
 """ssf_navplan_field (include/ssf_navplan.h) on the MI355X against the restatement (tests/navplan_ref.py): every cell of every
 output and every exact stat with == -- grids at the tile edges, doors on tile edges and corners, serpentines inside one tile and
-across many rounds (whatever the round batch), a grid 128 tiles wide, unknown cells, clearance, frontier goals, goal and start
+across many rounds (whatever the round batch), a grid 128 tiles wide, unknown cells, states outside {0, -1, 100}, clearance, frontier goals, goal and start
 bookkeeping, truncation and the tie-break; plus device arrays, the plan of a carved map without the grid leaving the device, no side
 effects on the frame path, the refusals, profiling, replay's files and the C++ surface."""
 import os
@@ -83,6 +83,22 @@ def test_random_grids_with_penalties(h, w, fusion):
         got, want = check(fusion, "%d x %d goals %s" % (h, w, goals), state, dist2, goals, starts, max_path=h * w, **kw)
         assert got["stats"]["goals_used"] == len(goals) and got["stats"]["cells_reached"] >= 1
         assert got["stats"]["rounds"] >= 1 and (h * w < 2000 or got["stats"]["cells_reached"] > h * w // 3)
+
+
+@pytest.mark.parametrize("h,w", pr.FOREIGN_SIZES)
+@pytest.mark.parametrize("allow", [0, 1])
+def test_grids_with_states_outside_0_minus_1_100_and_dist2_outside_the_cap(h, w, allow, fusion):
+    """tests/navplan_ref.py's foreign grid (states 1, 50, 99, 101, 127, -2, -128; dist2 negative, INT32_MIN, above the cap, INT32_MAX):
+    only 0 is free, only -1 is unknown and a frontier's neighbour, a negative dist2 is below min_dist2 = 0 and counts as 0 in the penalty"""
+    f = pr.foreign_case(h, w, allow)
+    want = f["plan"]
+    got = fusion.nav_plan(f["state"], f["dist2"], f["goals"], f["starts"], **f["kw"])
+    same(got, want, "foreign %d x %d unknown %d, goals" % (h, w, allow))
+    assert got["stats"]["cells_reached"] > h * w // 3 and max(got["path_len"]) > 10
+    got = fusion.nav_plan(f["state"], f["dist2"], None, f["starts"], goals_from_frontier=1, min_dist2=2, **f["kw"])
+    same(got, f["frontier_plan"], "foreign %d x %d unknown %d, frontier" % (h, w, allow))
+    assert got["stats"]["frontier_goals"] > 100
+    check(fusion, "foreign, no penalty, both", f["state"], f["dist2"], f["goals"], f["starts"], allow_unknown=allow, goals_from_frontier=1, max_path=50)
 
 
 DOORS = [dict(wall_x=32, door=31), dict(wall_x=32, door=32), dict(wall_x=31, door=31), dict(wall_x=31, door=0), dict(wall_y=32, door=31),

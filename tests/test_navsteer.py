@@ -1,7 +1,7 @@
 """Velocity commands on the navigation grid (include/ssf_navsteer.h) without a GPU: who exports the entry points, the header on its
 own, the struct layouts of the binding, the direction table, the host helpers, the C++ surface, replay.py's options, and the
-restatement the GPU tests compare against (tests/navsteer_ref.py): hand cases with written-out answers, and a guard that no
-parametrised scene of the GPU file is vacuous."""
+restatement the GPU tests compare against (tests/navsteer_ref.py): hand cases with written-out answers, and guards that no
+scene of the GPU file is vacuous."""
 import ctypes as C
 import os
 import subprocess
@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import navplan_ref as pr
 import navsteer_ref as sr
 from conftest import ROOT
 from supersurfel_fusion_amd import binding, replay
@@ -426,3 +427,103 @@ def test_ssf_hpp_steering_members_compile_and_link_against_the_steer_library(ste
     assert "window " + " ".join("%s=%d" % (k, win[k]) for k in ("n_v", "n_w", "v_min", "v_step", "w_min", "w_step")) in out, out
     x, y, h = binding.Fusion.nav_steer_units((1.0, 2.0, -0.1), float(np.float32(0.05)))[0]
     assert "units x=%d y=%d heading=%d" % (x, y, h) in out, out
+
+
+# ---- the guards of the scenes beyond the room: the mixed launch, the largest lattice, the widest scores, foreign grids -------------
+def window_cells(i, q):
+    c, R = i["c"], sr.reach(i["c"])
+    cx, cy = int(i["poses"][q, 0]) >> 10, int(i["poses"][q, 1]) >> 10
+    return (min(cx + R, c["width"] - 1) - max(cx - R, 0) + 1) * (min(cy + R, c["height"] - 1) - max(cy - R, 0) + 1)
+
+
+def test_the_mixed_scene_stages_some_windows_and_walks_others():
+    i, got = sr.scene_reference("mixed", sr.mixed_scene)
+    c, s = i["c"], got["stats"]
+    assert len(i["poses"]) == 1281 and c["n_v"] * c["n_w"] == 16 and sr.reach(c) == 39
+    assert sr.stage_cells(c) == 4056 and sr.stage_cells(dict(c, n_poses=1280)) == sr.LDS_CELLS == 14336
+    assert (window_cells(i, sr.MIXED_EDGE_STAGED), window_cells(i, sr.MIXED_EDGE_WALKED)) == (78 * 52, 78 * 53) == (4056, 4134)
+    assert window_cells(i, sr.MIXED_CORNER) == 41 * 41 and window_cells(i, sr.MIXED_CENTRAL) == 78 * 79
+    assert (got["pose_status"][:4 + sr.MIXED_LIVE] == 0).sum() >= 200 and (got["pose_status"][:4] == 0).all()
+    assert s["windows_staged"] >= 100 and s["windows_global"] >= 100 and s["windows_staged"] + s["windows_global"] == s["poses_ok"] + s["poses_stuck"]
+    assert s["collided"] > 0 and 0 < s["admissible"] < s["candidates"] and (got["best"] > 0).any()
+    assert int(got["cand_free"][sr.MIXED_CENTRAL].max()) == 38 and int(got["cand_free"][sr.MIXED_EDGE_WALKED].max()) == 38      # arcs that cross the window
+    assert (got["pose_status"][4 + sr.MIXED_LIVE:] == 1).any() and (got["pose_status"][4 + sr.MIXED_LIVE:] == 2).any()
+    # one pose fewer: the same poses, every window staged
+    j = sr.mixed_scene(1280)
+    assert (j["poses"] == i["poses"][:1280]).all() and got["pose_status"][1280] in (1, 2)         # (the pose dropped was not live)
+
+
+def test_the_largest_lattice_has_its_last_candidate_among_the_minima():
+    i, got = sr.scene_reference(("lattice", False), lambda: sr.lattice_scene(False))
+    assert i["c"]["n_v"] * i["c"]["n_w"] == 65536 and got["cand_score"].shape == (2, 65536)
+    assert i["state"][15, 0] == 100 and not i["state"][15, 1:4].any() and not i["state"][15, 22:27].any()      # the wall behind, the floor ahead
+    assert got["best"][0] == 65535 and got["best_score"][0] == 0 and 256 < got["best"][1] < 65535 and got["best_score"][1] > 0 and not sr.tied_poses(got)
+    assert (got["cand_score"][0, :65535] > 0).all() and got["stats"]["collided"] > 0 and got["cand_score"][1, 65535] == -1
+    i, got = sr.scene_reference(("lattice", True), lambda: sr.lattice_scene(True))
+    assert got["best"].tolist() == [0, 65280] and sr.tied_poses(got) == [0, 1] and (got["cand_score"][:, 65535] == got["best_score"]).all()
+    assert int((got["cand_score"][0] == 0).sum()) == 512 and int((got["cand_score"][1] == 0).sum()) == 256 and (got["cand_score"][1, :256] == -1).all()
+    assert 0 < got["n_admissible"][1] < 65536 == got["n_admissible"][0]
+
+
+def test_the_widest_scores_pass_2_to_the_41_and_stay_below_2_to_the_44():
+    i, got = sr.scene_reference("wide", sr.wide_scene)
+    c = i["c"]
+    assert all(c[k] == 1000 for k in ("cost_weight", "target_weight", "clear_weight", "speed_weight", "turn_weight")) and c["clearance_cap"] == 1 << 20
+    top = int(got["cand_score"].max())
+    assert 1 << 41 < top < 1 << 44 and top == int(got["cand_score"].astype(object).max())
+    assert (got["pose_status"] == 0).sum() >= 5 and int(got["best_score"].max()) > 1 << 41
+    reached = got["cand_end_cost"][got["cand_score"] >= 0]
+    assert int(reached.max()) == 0xFFFFFFFE and (got["cand_end_cost"][got["pose_status"] == 0] == sr.NO_COST).any()
+    assert (i["cost"] == sr.NO_COST).any() and int(i["cost"].min()) >= 0xFFFF0000
+    assert ((got["cand_min_d"] == 0) & (got["cand_score"] >= 0)).any()                       # dist2 0 along an admissible arc: the whole cap counts
+    t = i["targets"].astype(np.int64)
+    assert {(sr.I32_MIN, sr.I32_MAX), (sr.I32_MAX, sr.I32_MIN)} <= {tuple(r) for r in t.tolist()}
+    # the target term alone passes 32 bits: 1000 * ((10 * 2^31 + 4 * 2^31) >> 10) is about 2^34.8
+    far = np.abs(got["cand_end"][0, 0, :2].astype(np.int64) - t[0])
+    assert 1000 * ((10 * int(far.max()) + 4 * int(far.min())) >> 10) > 1 << 34
+    # the extreme poses: outside, their ends are the poses with the heading masked, and the live poses are as without them
+    at = [q for q in range(len(i["poses"])) if tuple(i["poses"][q]) in sr.EXTREME_POSES]
+    assert at == [2, 5, len(i["poses"]) - 1] and (got["pose_status"][at] == 1).all()
+    assert got["cand_end"][at, 0].tolist() == [[sr.I32_MIN, 0, 0], [sr.I32_MAX, sr.I32_MAX, 65535], [0, sr.I32_MIN, 0]]
+    _, alone = sr.scene_reference("wide, live only", lambda: sr.wide_scene(False))
+    live = [q for q in range(len(i["poses"])) if q not in at]
+    # (the targets go round by pose index, so only what does not read them is compared here; the GPU test gives each pose its target)
+    for nm in ("pose_status", "n_admissible", "cand_free", "cand_min_d", "cand_end", "cand_end_cost"):
+        assert (got[nm][live] == alone[nm]).all(), nm
+
+
+@pytest.mark.parametrize("h,w", pr.FOREIGN_SIZES)
+@pytest.mark.parametrize("allow", [0, 1])
+def test_the_rollouts_on_a_foreign_grid_meet_its_odd_values(h, w, allow):
+    """cells of a state outside {0, -1, 100} and of negative dist2 stop arcs; dist2 above the cap counts as the cap"""
+    i, got = sr.scene_reference(("foreign", h, w, allow), lambda: sr.foreign_scene(h, w, allow))
+    c, s = i["c"], got["stats"]
+    assert s["poses_ok"] >= 8 and s["collided"] > 0 and 0 < s["admissible"] < s["candidates"] and got["pose_status"][-2:].tolist() == [2, 1]
+    assert (got["cand_min_d"] == c["clearance_cap"]).any() and int(i["dist2"].max()) == sr.I32_MAX and int(i["dist2"].min()) == sr.I32_MIN
+    cost = i["cost"]
+    run = lambda state, dist2: sr.rollouts(state, dist2, cost, i["poses"], None, dict(c, cost_weight=0))["cand_free"]
+    free = got["cand_free"]
+    plain_state, plain_dist2 = pr.plain_grid(i["state"], i["dist2"])
+    assert (run(plain_state, i["dist2"]) > free).any()                    # an odd state ended an arc
+    assert (run(i["state"], np.where(i["dist2"] < 0, 1, i["dist2"])) > free).any()          # a negative dist2 did
+    # hand cases: state 50 and -2 are walls whether unknown cells are allowed or not; a negative dist2 is below min_dist2 = 0
+    for odd in (1, 50, 99, 101, 127, -2, -128):
+        s3, d3 = np.zeros((3, 6), np.int8), np.full((3, 6), 5, np.int32)
+        s3[:, 3] = odd
+        r = run_hand(s3, d3, allow)
+        assert r["cand_free"].tolist() == [[1]] and r["cand_end"][0, 0, 0] >> 10 == 2, odd
+    s3, d3 = np.zeros((3, 6), np.int8), np.full((3, 6), 5, np.int32)
+    d3[:, 3] = -1
+    assert run_hand(s3, d3, allow)["cand_free"].tolist() == [[1]]
+    d3[:, 3] = sr.I32_MAX                                                # above the cap: the cap
+    r = run_hand(s3, d3, allow)
+    assert r["cand_free"].tolist() == [[4]] and r["cand_min_d"].tolist() == [[5]]
+    d3[:] = sr.I32_MAX
+    assert run_hand(s3, d3, allow)["cand_min_d"].tolist() == [[20]]
+
+
+def run_hand(state, dist2, allow):
+    """one candidate straight along row 1 from cell 1 of a 3 x 6 grid, four steps of one cell"""
+    c = sr.params(width=6, height=3, n_poses=1, n_v=1, n_w=1, v_min=1024, v_step=0, w_min=0, w_step=0, n_steps=4, min_free_steps=0, brake_div=0,
+                  cost_weight=0, allow_unknown=allow, clearance_cap=20)
+    return sr.rollouts(state, dist2, None, np.array([sr.centre(1, 1)], np.int32), None, c)

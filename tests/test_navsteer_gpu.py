@@ -1,7 +1,8 @@
 """Velocity commands on the navigation grid (include/ssf_navsteer.h) on the GPU: every array and every exact stat of
 ssf_navsteer_rollouts equals the numpy restatement (tests/navsteer_ref.py) with ==, on the scenes that tests/test_navsteer.py guards
 against being vacuous, at the smallest grids, lattices and horizons at which the kernels take another path, with the window staged on
-chip and not, through device pointers fed by the overlay and the plan, through nav_live_steer, replay.py and the C++ wrapper."""
+chip and not and both in one launch, at the largest lattice, the widest scores and poses at the ends of int32, on grids of
+states outside {0, -1, 100}, through device pointers fed by the overlay and the plan, through nav_live_steer, replay.py and the C++ wrapper."""
 import os
 import re
 import subprocess
@@ -105,6 +106,85 @@ def test_a_window_too_large_to_stage_is_walked_in_the_grid(fusion):
     j = dict(i, state=i["state"][1:], dist2=sr.clearance(i["state"][1:]), c=dict(i["c"], height=119))
     got, _ = check(fusion, "just small enough", j)
     assert got["stats"]["windows_staged"] == 3 and got["stats"]["windows_global"] == 0
+
+
+def same_bytes(a, b, what):
+    for nm in sr.OUTPUTS:
+        if nm == "best_traj":
+            assert all(x.tobytes() == y.tobytes() for x, y in zip(a[nm], b[nm])), (what, nm)
+        else:
+            assert a[nm].tobytes() == b[nm].tobytes(), (what, nm)
+    assert {k: a["stats"][k] for k in sr.STATS} == {k: b["stats"][k] for k in sr.STATS}, what
+
+
+def test_a_launch_that_stages_some_windows_and_walks_the_others(fusion):
+    """1281 workgroups whose largest window would take 28904 B of LDS: the launch stages the windows of up to 4056 cells and walks
+    the others in the grid, in one launch with the dynamic LDS sized for the smaller bound; with 1280 it stages them all"""
+    i, want = sr.scene_reference("mixed", sr.mixed_scene)
+    assert sr.stage_cells(i["c"]) == 4056 and len(i["poses"]) == 1281
+    got, _ = check(fusion, "mixed", i, want=want)
+    s = got["stats"]
+    print("mixed launch: windows_staged=%d windows_global=%d" % (s["windows_staged"], s["windows_global"]))
+    assert s["windows_staged"] == want["stats"]["windows_staged"] > 0 and s["windows_global"] == want["stats"]["windows_global"] > 0
+    walked, _ = check(fusion, "mixed walk=1", i, want=want, walk=1)
+    assert walked["stats"]["windows_staged"] == 0 and walked["stats"]["windows_global"] == s["windows_staged"] + s["windows_global"]
+    same_bytes(got, walked, "mixed against walk=1")
+    for q in (sr.MIXED_EDGE_STAGED, sr.MIXED_EDGE_WALKED, sr.MIXED_CORNER, sr.MIXED_CENTRAL):       # the poses on either side of the rule
+        assert got["pose_status"][q] == 0 and (got["cand_free"][q] == walked["cand_free"][q]).all() and (got["cand_free"][q] == want["cand_free"][q]).all(), q
+    # one pose fewer: the launch is resident at once and every window is staged; the poses it shares give the same results
+    j = sr.mixed_scene(1280)
+    fewer = fusion.nav_steer(j["state"], j["dist2"], j["poses"], outputs=sr.OUTPUTS, **call_kw(j["c"]))
+    assert fewer["stats"]["windows_global"] == 0 and fewer["stats"]["windows_staged"] == s["windows_staged"] + s["windows_global"]
+    for nm in sr.OUTPUTS:
+        if nm == "best_traj":
+            assert all(x.tobytes() == y.tobytes() for x, y in zip(fewer[nm], got[nm][:1280])), nm
+        else:
+            assert (fewer[nm] == want[nm][:1280]).all(), nm
+
+
+@pytest.mark.parametrize("tie", [False, True], ids=["last candidate alone", "ties with the last candidate"])
+def test_the_largest_lattice(tie, fusion):
+    """K = 65536: c = 65535 fills the low 16 bits of the key; it wins alone, or ties and loses to the smallest index"""
+    i, want = sr.scene_reference(("lattice", tie), lambda: sr.lattice_scene(tie))
+    got, _ = check(fusion, "K = 65536, tie %d" % tie, i, want=want)
+    K = got["cand_score"].shape[1]
+    print("largest lattice: K == %d best=%s" % (K, got["best"].tolist()))
+    assert K == 65536 and got["stats"]["candidates"] == 2 * 65536
+    if tie:
+        assert got["best"].tolist() == [0, 65280] and (got["cand_score"][:, 65535] == got["best_score"]).all() and sr.tied_poses(got) == [0, 1]
+    else:
+        assert got["best"][0] == 65535 and got["best_score"][0] == 0 and 0 < got["n_admissible"][1] < 65536
+
+
+def test_the_widest_scores_and_poses_at_the_ends_of_int32(fusion):
+    """every weight 1000, costs up to 0xFFFFFFFE, targets at the corners of the int32 square: scores above 2^41; poses at INT32_MIN /
+    INT32_MAX are outside the grid, read nothing and leave the live poses' results as they are without them"""
+    i, want = sr.scene_reference("wide", sr.wide_scene)
+    got, _ = check(fusion, "wide", i, want=want)
+    assert 1 << 41 < int(got["cand_score"].max()) < 1 << 44 and int(got["best_score"].max()) > 1 << 41
+    at = [q for q in range(len(i["poses"])) if tuple(i["poses"][q]) in sr.EXTREME_POSES]
+    live = [q for q in range(len(i["poses"])) if q not in at]
+    assert len(at) == 3 and (got["pose_status"][at] == 1).all() and (got["cand_score"][at] == -1).all() and (got["best"][at] == -1).all()
+    assert got["cand_end"][at, 0].tolist() == [[sr.I32_MIN, 0, 0], [sr.I32_MAX, sr.I32_MAX, 65535], [0, sr.I32_MIN, 0]]
+    alone = fusion.nav_steer(i["state"], i["dist2"], i["poses"][live], cost=i["cost"], targets=i["targets"][live], outputs=sr.OUTPUTS, **call_kw(i["c"]))
+    for nm in sr.OUTPUTS:
+        if nm == "best_traj":
+            assert all(alone[nm][k].tobytes() == got[nm][q].tobytes() for k, q in enumerate(live)), nm
+        else:
+            assert alone[nm].tobytes() == np.ascontiguousarray(got[nm][live]).tobytes(), nm
+
+
+@pytest.mark.parametrize("h,w", pr.FOREIGN_SIZES)
+@pytest.mark.parametrize("allow", [0, 1])
+def test_a_grid_with_states_outside_0_minus_1_100_and_dist2_outside_the_cap(h, w, allow, fusion):
+    """tests/navplan_ref.py's foreign grid, steered down the field planned on it: only 0 (and -1 when allowed) is traversable, a negative
+    dist2 is below min_dist2 = 0, dist2 above the cap counts as the cap"""
+    i, want = sr.scene_reference(("foreign", h, w, allow), lambda: sr.foreign_scene(h, w, allow))
+    got, _ = check(fusion, "foreign %d x %d unknown %d" % (h, w, allow), i, want=want)
+    assert got["stats"]["windows_global"] == 0 and got["stats"]["collided"] > 0 and (got["cand_min_d"] == i["c"]["clearance_cap"]).any()
+    check(fusion, "foreign, walk=1", i, want=want, walk=1)
+    field = fusion.nav_plan(i["state"], i["dist2"], pr.foreign_case(h, w, allow)["goals"], outputs=("cost",), **pr.foreign_case(h, w, allow)["kw"])
+    assert (field["cost"] == i["cost"]).all()                             # the field steered on is the one the device plans
 
 
 def test_poses_on_cell_boundaries_in_corners_and_on_edges(fusion):
