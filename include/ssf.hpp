@@ -31,6 +31,7 @@
 #include "ssf_navpath.h"
 #include "ssf_navlive.h"
 #include "ssf_navsteer.h"
+#include "ssf_navfoot.h"
 #include "ssf_raycast.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
@@ -404,6 +405,31 @@ struct NavSteer {
     std::vector<uint32_t> cand_end_cost;
     std::vector<int64_t> cand_score;
     ssf_navsteer_stats stats;
+};
+
+/* footprintLayers and steerWithFootprint (ssf_navfoot.h; exported by libssf_hip_foot.so, linked INSTEAD of the other libraries -- a
+ * program that calls neither links as before): a rectangular body from the robot's centre, in sub-units (1024 per cell; x forward,
+ * +y left), and the heading bins its layers are made for.  pad < 0: footprintPad's value, which makes the layers conservative
+ * for any position in a cell and any heading in a bin. */
+struct FootprintParams {
+    int front = 0, back = 0, left = 0, right = 0, pad = -1;
+    int n_headings = 16;                                /* 1, 2, 4, 8, 16 or 32 */
+    bool allow_unknown = false;                         /* the plan's */
+    bool want_n_free = false;
+};
+/* a body in metres, each side rounded up to sub-units */
+inline FootprintParams footprintUnits(double front_m, double back_m, double left_m, double right_m, float res) {
+    FootprintParams f;
+    f.front = (int)std::ceil(front_m / (double)res * 1024.0); f.back = (int)std::ceil(back_m / (double)res * 1024.0);
+    f.left = (int)std::ceil(left_m / (double)res * 1024.0); f.right = (int)std::ceil(right_m / (double)res * 1024.0);
+    return f;
+}
+/* what footprintLayers makes: per cell the bit mask of the heading bins at which the body centred there stands on clear cells only */
+struct FootprintLayers {
+    int width = 0, height = 0, n_headings = 0;
+    std::vector<uint32_t> free_mask;
+    std::vector<uint8_t> n_free;                        /* with want_n_free */
+    ssf_navfoot_stats stats;
 };
 
 /* castRays (ssf_raycast.h; exported by libssf_hip.so only): the first disc of the map that each ray hits.  The members start at
@@ -1082,43 +1108,42 @@ public:
                      const SteerParams& q, NavSteer& out) {
         const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
         if (n == 0 || g.state.size() != n || g.dist2.size() != n) throw std::logic_error("steerOnGrid: the grid has no state or no dist2 (want_state, want_dist2)");
-        if (plan && plan->cost.size() != n) throw std::logic_error("steerOnGrid: the plan's cost field is not the grid's size (want_cost)");
-        if (poses.empty()) throw std::logic_error("steerOnGrid: no pose");
-        if (!targets.empty() && targets.size() != poses.size()) throw std::logic_error("steerOnGrid: one target per pose, or none");
-        ssf_navsteer_params p;
-        check(ssf_navsteer_default_params(need(), &p));
-        p.width = g.width; p.height = g.height; p.min_dist2 = q.min_dist2; p.allow_unknown = q.allow_unknown ? 1 : 0; p.clearance_cap = q.clearance_cap;
-        p.n_poses = (int)std::min<size_t>(poses.size(), 1u << 30);          /* (too many: the library refuses) */
-        p.n_v = q.n_v; p.n_w = q.n_w; p.v_min = q.v_min; p.v_step = q.v_step; p.w_min = q.w_min; p.w_step = q.w_step; p.n_steps = q.n_steps;
-        p.min_free_steps = q.min_free_steps; p.brake_div = q.brake_div; p.cost_weight = q.cost_weight; p.target_weight = q.target_weight;
-        p.clear_weight = q.clear_weight; p.speed_weight = q.speed_weight; p.turn_weight = q.turn_weight; p.on_device = 0;
-        const size_t np = poses.size();
-        const bool fits = q.n_v >= 1 && q.n_v <= 256 && q.n_w >= 1 && q.n_w <= 1024 && q.n_v * q.n_w <= 65536 && q.n_steps >= 1 && q.n_steps <= 256 &&
-                          np <= 4096 && np * (size_t)(q.n_v * q.n_w) <= ((size_t)1 << 24);
-        const size_t K = fits ? (size_t)(q.n_v * q.n_w) : 1, T1 = fits ? (size_t)q.n_steps + 1 : 1;
-        std::vector<int32_t> cmd(np * 2, 0), len(np, 0), traj(q.want_traj ? np * T1 * 3 : 0);
-        out.n_steps = q.n_steps; out.candidates = (int)K;
-        out.best.assign(np, -1); out.n_admissible.assign(np, 0); out.status.assign(np, 0); out.score.assign(np, -1);
-        const size_t nk = q.want_candidates ? np * K : 0;
-        out.cand_free.assign(nk, 0); out.cand_min_d.assign(nk, -1); out.cand_end.assign(nk * 3, 0); out.cand_end_cost.assign(nk, SSF_NAVSTEER_NO_COST);
-        out.cand_score.assign(nk, -1);
-        ssf_navsteer_out o;
-        o.best = out.best.data(); o.best_cmd = cmd.data(); o.best_score = out.score.data(); o.n_admissible = out.n_admissible.data();
-        o.pose_status = out.status.data(); o.best_len = len.data(); o.best_traj = q.want_traj ? traj.data() : nullptr;
-        o.cand_free = nk ? out.cand_free.data() : nullptr; o.cand_min_d = nk ? out.cand_min_d.data() : nullptr; o.cand_end = nk ? out.cand_end.data() : nullptr;
-        o.cand_end_cost = nk ? out.cand_end_cost.data() : nullptr; o.cand_score = nk ? out.cand_score.data() : nullptr;
-        check(ssf_navsteer_rollouts(need(), &p, g.state.data(), g.dist2.data(), plan ? plan->cost.data() : nullptr, &poses[0].x,
-                                    targets.empty() ? nullptr : &targets[0].x, &o, &out.stats));
-        out.v.resize(np); out.w.resize(np); out.traj.assign(np, std::vector<SteerPose>());
-        for (size_t i = 0; i < np; i++) {
-            out.v[i] = cmd[2 * i]; out.w[i] = cmd[2 * i + 1];
-            if (!q.want_traj) continue;
-            out.traj[i].resize((size_t)len[i]);
-            for (size_t k = 0; k < (size_t)len[i]; k++) {
-                const int32_t* e = &traj[(i * T1 + k) * 3];
-                out.traj[i][k].x = e[0]; out.traj[i][k].y = e[1]; out.traj[i][k].heading = e[2];
-            }
-        }
+        steer_run("steerOnGrid", g, plan, poses, targets, q, out, DiscRollouts(g.state.data()));
+    }
+    /* The pad (sub-units, pure host arithmetic) that makes the layers conservative for any position in the cell a pose lies in and any
+     * heading in the bin its heading lies in: ceil(2 * 724.1 + rho * pi / n_headings), rho the distance of the farthest corner
+     * (ssf_navfoot.h step 1).  The library refuses a pad above 4096: a long body needs more headings. */
+    static int footprintPad(int front, int back, int left, int right, int n_headings) {
+        if (front < 0 || back < 0 || left < 0 || right < 0 || n_headings < 1) throw std::invalid_argument("footprintPad needs sides >= 0 and n_headings >= 1");
+        const double a = (double)std::max(front, back), b = (double)std::max(left, right);
+        return (int)std::ceil(2.0 * 724.1 + std::sqrt(a * a + b * b) * 3.14159265358979323846 / (double)n_headings);
+    }
+    /* The heading layers of a body on a grid (ssf_navfoot.h step 2): g: a grid that buildNavGrid or overlayDepthFrame made (state). */
+    void footprintLayers(const NavGrid& g, const FootprintParams& f, FootprintLayers& out) {
+        const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
+        if (n == 0 || g.state.size() != n) throw std::logic_error("footprintLayers: the grid has no state (want_state)");
+        ssf_navfoot_params p;
+        check(ssf_navfoot_default_params(need(), &p));
+        p.width = g.width; p.height = g.height; p.allow_unknown = f.allow_unknown ? 1 : 0; p.n_headings = f.n_headings;
+        p.front = f.front; p.back = f.back; p.left = f.left; p.right = f.right;
+        p.pad = f.pad >= 0 ? f.pad : footprintPad(f.front, f.back, f.left, f.right, f.n_headings);
+        p.on_device = 0;
+        out.width = g.width; out.height = g.height; out.n_headings = f.n_headings;
+        out.free_mask.assign(n, 0u); out.n_free.assign(f.want_n_free ? n : 0, 0);
+        ssf_navfoot_out o;
+        o.free_mask = out.free_mask.data(); o.n_free = f.want_n_free ? out.n_free.data() : nullptr;
+        check(ssf_navfoot_layers(need(), &p, g.state.data(), &o, &out.stats));
+    }
+    /* steerOnGrid with the oriented body in the place of the disc (ssf_navfoot.h step 3): a cell is traversable for a step iff its
+     * mask holds every bin the heading sweeps in that step and dist2 >= q.min_dist2.  layers: footprintLayers of the same grid.  The
+     * result feeds fillTwist and fillLocalPlan as steerOnGrid's does. */
+    void steerWithFootprint(const NavGrid& g, const FootprintLayers& layers, const NavPlan* plan, const std::vector<SteerPose>& poses,
+                            const std::vector<SteerTarget>& targets, const SteerParams& q, NavSteer& out) {
+        const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
+        if (n == 0 || g.dist2.size() != n) throw std::logic_error("steerWithFootprint: the grid has no dist2 (want_dist2)");
+        if (layers.width != g.width || layers.height != g.height || layers.free_mask.size() != n)
+            throw std::logic_error("steerWithFootprint: the layers are not the grid's size (footprintLayers of the same grid)");
+        steer_run("steerWithFootprint", g, plan, poses, targets, q, out, FootRollouts(layers.free_mask.data(), layers.n_headings));
     }
     /* The integer lattice of a dynamic window (pure host arithmetic, no handle): the speeds (m/s) and turn rates (rad/s) reachable
      * from (v_now, w_now) within one step of dt seconds under (accel_v m/s^2, accel_w rad/s^2), cut to [v_lo, v_hi] and [w_lo, w_hi]
@@ -1167,6 +1192,66 @@ public:
         }
     }
 private:
+    /* the rollouts' two entry points behind one signature: a program that calls only one of the public members references only that one */
+    struct DiscRollouts {
+        const int8_t* state;
+        explicit DiscRollouts(const int8_t* s) : state(s) {}
+        int operator()(ssf_handle* h, const ssf_navsteer_params* p, const int32_t* dist2, const uint32_t* cost, const int32_t* poses, const int32_t* targets,
+                       const ssf_navsteer_out* o, ssf_navsteer_stats* st) const {
+            return ssf_navsteer_rollouts(h, p, state, dist2, cost, poses, targets, o, st);
+        }
+    };
+    struct FootRollouts {
+        const uint32_t* mask; int n_headings;
+        FootRollouts(const uint32_t* m, int b) : mask(m), n_headings(b) {}
+        int operator()(ssf_handle* h, const ssf_navsteer_params* p, const int32_t* dist2, const uint32_t* cost, const int32_t* poses, const int32_t* targets,
+                       const ssf_navsteer_out* o, ssf_navsteer_stats* st) const {
+            return ssf_navfoot_rollouts(h, p, n_headings, mask, dist2, cost, poses, targets, o, st);
+        }
+    };
+    /* steerOnGrid's and steerWithFootprint's body: the params, the outputs' vectors, the call, the arcs */
+    template <typename Call>
+    void steer_run(const char* who, const NavGrid& g, const NavPlan* plan, const std::vector<SteerPose>& poses, const std::vector<SteerTarget>& targets,
+                   const SteerParams& q, NavSteer& out, const Call& call) {
+        const size_t n = (size_t)g.width * (size_t)g.height;
+        if (plan && plan->cost.size() != n) throw std::logic_error(std::string(who) + ": the plan's cost field is not the grid's size (want_cost)");
+        if (poses.empty()) throw std::logic_error(std::string(who) + ": no pose");
+        if (!targets.empty() && targets.size() != poses.size()) throw std::logic_error(std::string(who) + ": one target per pose, or none");
+        ssf_navsteer_params p;
+        check(ssf_navsteer_default_params(need(), &p));
+        p.width = g.width; p.height = g.height; p.min_dist2 = q.min_dist2; p.allow_unknown = q.allow_unknown ? 1 : 0; p.clearance_cap = q.clearance_cap;
+        p.n_poses = (int)std::min<size_t>(poses.size(), 1u << 30);          /* (too many: the library refuses) */
+        p.n_v = q.n_v; p.n_w = q.n_w; p.v_min = q.v_min; p.v_step = q.v_step; p.w_min = q.w_min; p.w_step = q.w_step; p.n_steps = q.n_steps;
+        p.min_free_steps = q.min_free_steps; p.brake_div = q.brake_div; p.cost_weight = q.cost_weight; p.target_weight = q.target_weight;
+        p.clear_weight = q.clear_weight; p.speed_weight = q.speed_weight; p.turn_weight = q.turn_weight; p.on_device = 0;
+        const size_t np = poses.size();
+        const bool fits = q.n_v >= 1 && q.n_v <= 256 && q.n_w >= 1 && q.n_w <= 1024 && q.n_v * q.n_w <= 65536 && q.n_steps >= 1 && q.n_steps <= 256 &&
+                          np <= 4096 && np * (size_t)(q.n_v * q.n_w) <= ((size_t)1 << 24);
+        const size_t K = fits ? (size_t)(q.n_v * q.n_w) : 1, T1 = fits ? (size_t)q.n_steps + 1 : 1;
+        std::vector<int32_t> cmd(np * 2, 0), len(np, 0), traj(q.want_traj ? np * T1 * 3 : 0);
+        out.n_steps = q.n_steps; out.candidates = (int)K;
+        out.best.assign(np, -1); out.n_admissible.assign(np, 0); out.status.assign(np, 0); out.score.assign(np, -1);
+        const size_t nk = q.want_candidates ? np * K : 0;
+        out.cand_free.assign(nk, 0); out.cand_min_d.assign(nk, -1); out.cand_end.assign(nk * 3, 0); out.cand_end_cost.assign(nk, SSF_NAVSTEER_NO_COST);
+        out.cand_score.assign(nk, -1);
+        ssf_navsteer_out o;
+        o.best = out.best.data(); o.best_cmd = cmd.data(); o.best_score = out.score.data(); o.n_admissible = out.n_admissible.data();
+        o.pose_status = out.status.data(); o.best_len = len.data(); o.best_traj = q.want_traj ? traj.data() : nullptr;
+        o.cand_free = nk ? out.cand_free.data() : nullptr; o.cand_min_d = nk ? out.cand_min_d.data() : nullptr; o.cand_end = nk ? out.cand_end.data() : nullptr;
+        o.cand_end_cost = nk ? out.cand_end_cost.data() : nullptr; o.cand_score = nk ? out.cand_score.data() : nullptr;
+        check(call(need(), &p, g.dist2.data(), plan ? plan->cost.data() : nullptr, &poses[0].x, targets.empty() ? nullptr : &targets[0].x, &o,
+                   &out.stats));
+        out.v.resize(np); out.w.resize(np); out.traj.assign(np, std::vector<SteerPose>());
+        for (size_t i = 0; i < np; i++) {
+            out.v[i] = cmd[2 * i]; out.w[i] = cmd[2 * i + 1];
+            if (!q.want_traj) continue;
+            out.traj[i].resize((size_t)len[i]);
+            for (size_t k = 0; k < (size_t)len[i]; k++) {
+                const int32_t* e = &traj[(i * T1 + k) * 3];
+                out.traj[i][k].x = e[0]; out.traj[i][k].y = e[1]; out.traj[i][k].heading = e[2];
+            }
+        }
+    }
     static void steer_axis(double now, double lo_limit, double hi_limit, double reach, double scale, int cap, int n, int& n_out, int& first, int& step) {
         double lo = std::max(lo_limit, now - reach), hi = std::min(hi_limit, now + reach);
         if (lo > hi) lo = hi = std::min(std::max(now, lo_limit), hi_limit);      /* (the current value lies outside the limits: the nearest limit) */

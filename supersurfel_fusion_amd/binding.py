@@ -32,6 +32,9 @@ LIVE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_live.so")
 # live's objects and the velocity commands (include/ssf_navsteer.h): the one library of a robot that also steers on its grid.  None of
 # the six libraries above exports the rollouts' entry points
 STEER_LIB = os.path.join(_HERE, "csrc", "libssf_hip_steer.so")
+# steer's objects and the oriented footprint (include/ssf_navfoot.h): the one library of a robot whose base is not round.  None of the
+# seven libraries above exports the footprint's entry points
+FOOT_LIB = os.path.join(_HERE, "csrc", "libssf_hip_foot.so")
 
 
 class SsfConfig(C.Structure):
@@ -156,6 +159,10 @@ NAVSTEER_OUTPUTS = (("best", np.int32, "pose", ()), ("best_cmd", np.int32, "pose
 NAVSTEER_OUTPUT_NAMES = tuple(o[0] for o in NAVSTEER_OUTPUTS)
 NAVSTEER_POSE_OUTPUTS = tuple(o[0] for o in NAVSTEER_OUTPUTS if o[2] == "pose")
 NAVSTEER_SUBUNITS, NAVSTEER_TURN, NAVSTEER_NO_COST = 1024, 65536, 0xFFFFFFFF
+# the oriented footprint (include/ssf_navfoot.h): exported by libssf_hip_foot.so only (load_foot)
+NAVFOOT_SYMBOLS = ["ssf_navfoot_spans", "ssf_navfoot_default_params", "ssf_navfoot_layers", "ssf_navfoot_rollouts"]
+NAVFOOT_MAX_REACH, NAVFOOT_ROWS, NAVFOOT_MAX_SIDE, NAVFOOT_MAX_PAD = 40, 81, 24576, 4096
+NAVFOOT_HEADINGS = (1, 2, 4, 8, 16, 32)
 # rays cast through the model (include/ssf_raycast.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 RAYCAST_SYMBOLS = ["ssf_raycast_default_params", "ssf_raycast"]
 # the output arrays of ssf_raycast, in its argument order: name, dtype, per-ray shape
@@ -419,6 +426,24 @@ class SsfNavSteerStats(C.Structure):
         return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
 
 
+class SsfNavFootParams(C.Structure):
+    """ssf_navfoot_params (include/ssf_navfoot.h)"""
+    _fields_ = [(nm, C.c_int) for nm in ("width", "height", "allow_unknown", "n_headings", "front", "back", "left", "right", "pad", "on_device")]
+
+
+class SsfNavFootOut(C.Structure):
+    """ssf_navfoot_out (include/ssf_navfoot.h)"""
+    _fields_ = [("free_mask", C.c_void_p), ("n_free", C.c_void_p)]
+
+
+class SsfNavFootStats(C.Structure):
+    """ssf_navfoot_stats (include/ssf_navfoot.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("cells_clear", "cells_all", "cells_some", "cells_none", "reach", "kernel_cells")]
+
+    def as_dict(self):
+        return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
+
+
 class SsfRaycastParams(C.Structure):
     """ssf_raycast_params (include/ssf_raycast.h)"""
     _fields_ = [("pose", C.c_void_p), ("t_min", C.c_float), ("t_max", C.c_float), ("min_conf", C.c_float), ("splat_scale", C.c_float),
@@ -615,6 +640,13 @@ class Library:
             L.ssf_navsteer_direction_table.argtypes = [vp, vp]
             L.ssf_navsteer_rollouts.argtypes = [vp, C.POINTER(SsfNavSteerParams), vp, vp, vp, vp, vp, C.POINTER(SsfNavSteerOut),
                                                 C.POINTER(SsfNavSteerStats)]
+        self.has_navfoot = all(hasattr(L, nm) for nm in NAVFOOT_SYMBOLS)
+        if self.has_navfoot:
+            L.ssf_navfoot_spans.argtypes = [C.c_int] * 6 + [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+            L.ssf_navfoot_default_params.argtypes = [vp, C.POINTER(SsfNavFootParams)]
+            L.ssf_navfoot_layers.argtypes = [vp, C.POINTER(SsfNavFootParams), vp, C.POINTER(SsfNavFootOut), C.POINTER(SsfNavFootStats)]
+            L.ssf_navfoot_rollouts.argtypes = [vp, C.POINTER(SsfNavSteerParams), C.c_int, vp, vp, vp, vp, vp, C.POINTER(SsfNavSteerOut),
+                                               C.POINTER(SsfNavSteerStats)]
         self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
         if self.has_navgrid:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
@@ -767,6 +799,33 @@ def navsteer_direction_table(library=None):
     if rc != 0:
         raise SsfError("ssf_navsteer_direction_table failed (%d)" % rc)
     return c, s
+
+
+def load_foot():
+    """Load libssf_hip_foot.so: steer's objects (the product and every navigation call up to the velocity commands) with the oriented
+    footprint linked in (include/ssf_navfoot.h).  A handle belongs to the library that created it: create the Fusion from THIS
+    library to call nav_foot, nav_foot_steer or nav_live_foot_steer on it.  Fails loudly when it has not been built."""
+    import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
+    return Library(FOOT_LIB)
+
+
+def navfoot_spans(front, back, left, right, pad, n_headings, library=None):
+    """(spans, reach, kernel_cells): the cells a rectangular footprint covers at every heading bin (include/ssf_navfoot.h step 1), as
+    ssf_navfoot_spans returns them: spans n_headings x 81 x 2 int16, (lo, hi) of the covered dx for dy = -40..40, (1, 0) where empty.
+    front, back, left, right and pad in sub-units.  It takes no handle and touches no device.  library: a Library that exports it
+    (default: load_foot())."""
+    lib = library or load_foot()
+    if not lib.has_navfoot:
+        raise SsfError("%s does not export ssf_navfoot_spans: it holds no footprint (include/ssf_navfoot.h: libssf_hip_foot.so, "
+                       "binding.load_foot)" % lib.path)
+    B = int(n_headings)
+    spans = np.zeros((B if B in NAVFOOT_HEADINGS else 1, NAVFOOT_ROWS, 2), np.int16)
+    reach, cells = C.c_int32(0), C.c_int64(0)
+    rc = lib.lib.ssf_navfoot_spans(int(front), int(back), int(left), int(right), int(pad), B, _ptr(spans), C.byref(reach), C.byref(cells))
+    if rc != 0:
+        raise SsfError("ssf_navfoot_spans refused the footprint (%d): sides 0..%d, pad 0..%d, n_headings one of %s, reach <= %d cells"
+                       % (rc, NAVFOOT_MAX_SIDE, NAVFOOT_MAX_PAD, NAVFOOT_HEADINGS, NAVFOOT_MAX_REACH))
+    return spans, int(reach.value), int(cells.value)
 
 
 def load_lab():
@@ -2010,11 +2069,16 @@ class Fusion:
         p.width, p.height, p.n_poses, p.on_device = int(width), int(height), int(n_poses), int(bool(on_device))
         return p
 
-    def _navsteer_rollouts(self, p, state, dist2, cost, poses, targets, ptrs):
+    def _navsteer_rollouts(self, p, state, dist2, cost, poses, targets, ptrs, n_headings=None):
+        """the disc's rollouts over `state`, or with n_headings the footprint's over the mask given in its place"""
         st = SsfNavSteerStats()
         out = SsfNavSteerOut(*[ptrs.get(nm) for nm in NAVSTEER_OUTPUT_NAMES])
-        self._ck(self.L.lib.ssf_navsteer_rollouts(self.h, C.byref(p), state, dist2, cost, poses, targets, C.byref(out), C.byref(st)),
-                 "ssf_navsteer_rollouts")
+        if n_headings is None:
+            self._ck(self.L.lib.ssf_navsteer_rollouts(self.h, C.byref(p), state, dist2, cost, poses, targets, C.byref(out), C.byref(st)),
+                     "ssf_navsteer_rollouts")
+        else:
+            self._ck(self.L.lib.ssf_navfoot_rollouts(self.h, C.byref(p), int(n_headings), state, dist2, cost, poses, targets, C.byref(out),
+                                                     C.byref(st)), "ssf_navfoot_rollouts")
         return st.as_dict()
 
     @staticmethod
@@ -2028,12 +2092,16 @@ class Fusion:
         with target_weight 0).  Returns a dict of the requested outputs (NAVSTEER_OUTPUTS; best_traj: a list with one (best_len, 3)
         array per pose) and 'stats'.  params: the other fields of ssf_navsteer_params by name."""
         self._need_navsteer("ssf_navsteer_rollouts")
+        return self._nav_steer_host(state, np.int8, "state", None, dist2, poses, cost, targets, outputs, params)
+
+    def _nav_steer_host(self, state, grid_dtype, grid_name, n_headings, dist2, poses, cost, targets, outputs, params):
+        """nav_steer's body, and nav_foot_steer's with the mask in the place of state"""
         bad = [nm for nm in outputs if nm not in NAVSTEER_OUTPUT_NAMES]
         if bad:
             raise SsfError("unknown steering outputs %s (known: %s)" % (bad, ", ".join(NAVSTEER_OUTPUT_NAMES)))
-        state, dist2 = np.ascontiguousarray(state, np.int8), np.ascontiguousarray(dist2, np.int32)
+        state, dist2 = np.ascontiguousarray(state, grid_dtype), np.ascontiguousarray(dist2, np.int32)
         if state.ndim != 2 or dist2.shape != state.shape:
-            raise SsfError("state and dist2 are H x W arrays of one shape, got %s and %s" % (state.shape, dist2.shape))
+            raise SsfError("%s and dist2 are H x W arrays of one shape, got %s and %s" % (grid_name, state.shape, dist2.shape))
         H, W = state.shape
         poses = np.ascontiguousarray(poses, np.int32)
         if poses.ndim != 2 or poses.shape[1] != 3:
@@ -2055,7 +2123,8 @@ class Fusion:
         if "best_traj" in want:
             want.add("best_len")                     # (the counts cut the lists)
         out = {nm: np.zeros(self._navsteer_shape(kind, tail, n, K, T), dt) for nm, dt, kind, tail in NAVSTEER_OUTPUTS if nm in want}
-        stats = self._navsteer_rollouts(p, _ptr(state), _ptr(dist2), _ptr(cost), _ptr(poses), _ptr(targets), {nm: _ptr(a) for nm, a in out.items()})
+        stats = self._navsteer_rollouts(p, _ptr(state), _ptr(dist2), _ptr(cost), _ptr(poses), _ptr(targets), {nm: _ptr(a) for nm, a in out.items()},
+                                        n_headings)
         if "best_traj" in out:
             out["best_traj"] = [out["best_traj"][i, :out["best_len"][i]].copy() for i in range(n)]
         if "best_len" not in outputs:
@@ -2166,6 +2235,158 @@ class Fusion:
         got["best_traj"] = [got["best_traj"][i, :got["best_len"][i]].copy() for i in range(n)]
         got["stats"] = steer_stats
         return dict(live=dict(stats=live_stats), plan=dict(stats=plan_stats), steer=got)
+
+    # ---- an oriented footprint on the navigation grid: heading layers and rollouts over them (include/ssf_navfoot.h) ----
+    def _need_navfoot(self, symbol):
+        if not self.L.has_navfoot:
+            raise SsfError("%s does not export %s: it holds no footprint (include/ssf_navfoot.h: libssf_hip_foot.so, binding.load_foot)"
+                           % (self.L.path, symbol))
+
+    def _navfoot_params(self, on_device, width, height, params):
+        p = SsfNavFootParams()
+        self._ck(self.L.lib.ssf_navfoot_default_params(self.h, C.byref(p)), "ssf_navfoot_default_params")
+        kinds = dict(p._fields_)
+        for nm, val in params.items():
+            if nm not in kinds or nm in ("width", "height", "on_device"):
+                raise SsfError("unknown footprint parameter %r" % nm)
+            setattr(p, nm, int(val))
+        p.width, p.height, p.on_device = int(width), int(height), int(bool(on_device))
+        return p
+
+    def _navfoot_layers(self, p, state, free_mask, n_free):
+        st = SsfNavFootStats()
+        out = SsfNavFootOut(free_mask, n_free)
+        self._ck(self.L.lib.ssf_navfoot_layers(self.h, C.byref(p), state, C.byref(out), C.byref(st)), "ssf_navfoot_layers")
+        return st.as_dict()
+
+    def nav_foot(self, state, outputs=("free_mask",), **params):
+        """The heading layers of a rectangular footprint (ssf_navfoot_layers), host arrays.  state H x W int8 as the grid calls or
+        nav_live return it.  params: the fields of ssf_navfoot_params by name (front, back, left, right, pad in sub-units:
+        nav_foot_units, nav_foot_pad; n_headings; allow_unknown).  Returns a dict of the requested outputs ('free_mask' H x W uint32:
+        bit b set iff the footprint at heading bin b centred on the cell stands on clear cells only; 'n_free' H x W uint8) and 'stats'."""
+        self._need_navfoot("ssf_navfoot_layers")
+        bad = [nm for nm in outputs if nm not in ("free_mask", "n_free")]
+        if bad:
+            raise SsfError("unknown footprint outputs %s (known: free_mask, n_free)" % (bad,))
+        state = np.ascontiguousarray(state, np.int8)
+        if state.ndim != 2:
+            raise SsfError("state is an H x W array, got shape %s" % (state.shape,))
+        H, W = state.shape
+        p = self._navfoot_params(False, W, H, params)
+        out = {}
+        if "free_mask" in outputs:
+            out["free_mask"] = np.zeros((H, W), np.uint32)
+        if "n_free" in outputs:
+            out["n_free"] = np.zeros((H, W), np.uint8)
+        out["stats"] = self._navfoot_layers(p, _ptr(state), _ptr(out.get("free_mask")), _ptr(out.get("n_free")))
+        return out
+
+    def nav_foot_device(self, state, width, height, free_mask=None, n_free=None, **params):
+        """ssf_navfoot_layers on device memory: state and each output are a contiguous torch tensor on the device or the device address
+        (int) of a buffer of the shape and dtype nav_foot works on (free_mask: 4-byte words; outputs may be None, not both):
+        nav_live_device's state is read where it lies.  Returns the stats dict."""
+        self._need_navfoot("ssf_navfoot_layers")
+        p = self._navfoot_params(True, width, height, params)
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        return self._navfoot_layers(p, addr(state), addr(free_mask), addr(n_free))
+
+    def nav_foot_default_params(self):
+        """ssf_navfoot_default_params as a dict"""
+        self._need_navfoot("ssf_navfoot_default_params")
+        p = SsfNavFootParams()
+        self._ck(self.L.lib.ssf_navfoot_default_params(self.h, C.byref(p)), "ssf_navfoot_default_params")
+        return {nm: getattr(p, nm) for nm, _ in p._fields_}
+
+    @staticmethod
+    def nav_foot_pad(front, back, left, right, n_headings):
+        """The pad (sub-units, pure host arithmetic) that makes the layers conservative for any position in the cell a pose lies in and
+        any heading in the bin its heading lies in: ceil(2 * 724.1 + rho * pi / n_headings), rho the distance of the farthest corner
+        (include/ssf_navfoot.h step 1).  The call refuses a pad above 4096: a long body needs more headings."""
+        if int(n_headings) not in NAVFOOT_HEADINGS or min(front, back, left, right) < 0:
+            raise SsfError("nav_foot_pad takes sides >= 0 in sub-units and n_headings one of %s" % (NAVFOOT_HEADINGS,))
+        rho = float(np.hypot(max(front, back), max(left, right)))
+        return int(np.ceil(2 * 724.1 + rho * np.pi / int(n_headings)))
+
+    @staticmethod
+    def nav_foot_units(front_m, back_m, left_m, right_m, res):
+        """A footprint in metres from the robot's centre in the call's sub-units (pure host arithmetic), each side rounded up:
+        dict(front, back, left, right), nav_foot's keywords"""
+        if not res > 0 or min(front_m, back_m, left_m, right_m) < 0:
+            raise SsfError("nav_foot_units takes four sides >= 0 in metres and res > 0")
+        return {nm: int(np.ceil(v / res * NAVSTEER_SUBUNITS)) for nm, v in (("front", front_m), ("back", back_m), ("left", left_m), ("right", right_m))}
+
+    def nav_foot_steer(self, free_mask, dist2, poses, n_headings, cost=None, targets=None, outputs=NAVSTEER_POSE_OUTPUTS, **params):
+        """nav_steer with the oriented footprint in the place of the disc (ssf_navfoot_rollouts), host arrays: free_mask H x W uint32 as
+        nav_foot returns it for n_headings bins.  A cell is traversable for a step iff its mask holds every bin the heading sweeps in
+        that step and dist2 >= min_dist2.  Everything else, the outputs included, is nav_steer's."""
+        self._need_navfoot("ssf_navfoot_rollouts")
+        return self._nav_steer_host(free_mask, np.uint32, "free_mask", n_headings, dist2, poses, cost, targets, outputs, params)
+
+    def nav_foot_steer_device(self, free_mask, dist2, width, height, poses, n_poses, n_headings, cost=None, targets=None, best=None, best_cmd=None,
+                              best_score=None, n_admissible=None, pose_status=None, best_len=None, best_traj=None, cand_free=None, cand_min_d=None,
+                              cand_end=None, cand_end_cost=None, cand_score=None, **params):
+        """ssf_navfoot_rollouts on device memory, as nav_steer_device: nav_foot_device's free_mask is read where it lies.  Returns the
+        stats dict."""
+        self._need_navfoot("ssf_navfoot_rollouts")
+        p = self._navsteer_params(True, width, height, n_poses, params)
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        return self._navsteer_rollouts(p, addr(free_mask), addr(dist2), addr(cost), addr(poses), addr(targets),
+                                       dict(best=addr(best), best_cmd=addr(best_cmd), best_score=addr(best_score), n_admissible=addr(n_admissible),
+                                            pose_status=addr(pose_status), best_len=addr(best_len), best_traj=addr(best_traj), cand_free=addr(cand_free),
+                                            cand_min_d=addr(cand_min_d), cand_end=addr(cand_end), cand_end_cost=addr(cand_end_cost),
+                                            cand_score=addr(cand_score)), n_headings)
+
+    def nav_live_foot_steer(self, depth, state, goals, poses, foot, targets=None, mask=None, live=None, plan=None, steer=None, keep_mask=False):
+        """Overlay, plan, heading layers and rollouts with nothing but the command leaving the device: nav_live_steer with
+        nav_foot_device between the plan and the rollouts.  foot: nav_foot's keywords (front, back, left, right, n_headings; pad
+        defaults to nav_foot_pad's, allow_unknown to the plan's).  The plan is the disc's by its own min_dist2 (the inscribed radius).
+        Returns a dict: 'live', 'plan' and 'foot' (stats; with keep_mask also 'free_mask', copied out) and 'steer' (the per-pose
+        outputs as nav_steer returns them, and stats)."""
+        import torch
+        self._need_navlive("ssf_navlive_overlay")
+        self._need_navplan("ssf_navplan_field")
+        self._need_navfoot("ssf_navfoot_rollouts")
+        live, plan, fq, sq = dict(live or {}), dict(plan or {}), dict(foot or {}), dict(steer or {})
+        state = np.ascontiguousarray(state, np.int8)
+        if state.ndim != 2:
+            raise SsfError("state is a height x width array, got shape %s" % (state.shape,))
+        H, W = state.shape
+        poses = np.ascontiguousarray(poses, np.int32)
+        if poses.ndim != 2 or poses.shape[1] != 3 or poses.shape[0] < 1:
+            raise SsfError("poses are n x 3 (x, y, heading) in units, n >= 1, got shape %s" % (poses.shape,))
+        n = poses.shape[0]
+        fq.setdefault("n_headings", self.nav_foot_default_params()["n_headings"])
+        fq.setdefault("allow_unknown", plan.get("allow_unknown", 0))
+        fq.setdefault("pad", self.nav_foot_pad(fq.get("front", 0), fq.get("back", 0), fq.get("left", 0), fq.get("right", 0), fq["n_headings"]))
+        dev = torch.device("cuda")
+        if not isinstance(depth, torch.Tensor):
+            depth = torch.from_numpy(np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32).view(
+                np.int16 if self.depth_format == "u16" else np.float32)).to(dev)
+        if mask is not None and not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).to(dev)
+        d_state = torch.from_numpy(state).to(dev)
+        d_dist2 = torch.empty((H, W), dtype=torch.int32, device=dev)
+        d_cost = torch.empty((H, W), dtype=torch.int32, device=dev)       # (uint32 words)
+        d_mask = torch.empty((H, W), dtype=torch.int32, device=dev)       # (uint32 words)
+        live_stats = self.nav_live_device(depth, d_state, W, H, mask=mask, state_out=d_state, dist2=d_dist2, **live)
+        plan_stats = self.nav_plan_device(d_state, d_dist2, W, H, goals, None, cost=d_cost, **plan)
+        foot_stats = self.nav_foot_device(d_state, W, H, free_mask=d_mask, **fq)
+        for nm in ("min_dist2", "allow_unknown"):
+            sq.setdefault(nm, plan.get(nm, 0))
+        p = self._navsteer_params(True, W, H, n, sq)
+        T = min(max(p.n_steps, 0), 256)
+        d_poses = torch.from_numpy(poses).to(dev)
+        d_targets = None if targets is None else torch.from_numpy(np.ascontiguousarray(targets, np.int32)).to(dev)
+        o = {nm: torch.zeros(self._navsteer_shape(kind, tail, n, 1, T), dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
+             for nm, dt, kind, tail in NAVSTEER_OUTPUTS if kind == "pose"}
+        steer_stats = self.nav_foot_steer_device(d_mask, d_dist2, W, H, d_poses, n, fq["n_headings"], cost=d_cost, targets=d_targets, **dict(o, **sq))
+        got = {nm: a.cpu().numpy() for nm, a in o.items()}
+        got["best_traj"] = [got["best_traj"][i, :got["best_len"][i]].copy() for i in range(n)]
+        got["stats"] = steer_stats
+        res = dict(live=dict(stats=live_stats), plan=dict(stats=plan_stats), foot=dict(stats=foot_stats), steer=got)
+        if keep_mask:
+            res["foot"]["free_mask"] = d_mask.cpu().numpy().view(np.uint32)
+        return res
 
     # ---- rays cast through the model: the first disc each ray hits (include/ssf_raycast.h) ------------
     def _need_raycast(self, symbol):

@@ -7,6 +7,7 @@
 #include <cassert>
 #include <climits>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <initializer_list>
@@ -397,6 +398,21 @@ struct NavSteerWs {
     bool dirs_sent = false;                       // the table's upload has been enqueued (a call may fail between allocation and upload)
     unsigned char* io = nullptr; size_t io_bytes = 0;
 };
+// ssf_navfoot_layers and ssf_navfoot_rollouts (ssf_navfoot.h, ssf_navfoot.hip: linked into libssf_hip_foot.so only): the footprint's
+// table of spans as the layers kernel reads it (kept from call to call while the footprint is the same), the layers' sums and the staging buffer of a layers call with host arrays; per cell
+// the rollouts' packed (heading mask, d) word of 8 bytes.  The rollouts' keys, counts, direction table, sums and staging are
+// NavSteerWs's.  Allocated on first use; each group is grown as a whole or not at all (DevBufs::grow).  Nothing here is read or
+// written by the frame path.
+struct NavFootWs {
+    DevBufs bufs;
+    unsigned long long* table = nullptr; unsigned long long* stats = nullptr;
+    int key[6] = {0, 0, 0, 0, 0, 0}; int reach = 0; long long cells = 0; bool table_valid = false;      // the footprint the table on the device is of
+    // the table as it is uploaded (malloc, freed with the handle): it outlives the call, whose copies may still read it after an early return
+    unsigned long long* host_table = nullptr;
+    NavFootWs() = default; NavFootWs(const NavFootWs&) = delete; ~NavFootWs() { std::free(host_table); }
+    unsigned char* io = nullptr; size_t io_bytes = 0;
+    unsigned long long* pk = nullptr; size_t pk_cells = 0;
+};
 // ssf_raycast (ssf_raycast.h): the resident index -- per slot the 64-byte record and the box of cells with the row's class, the
 // out-of-view blocks' live offsets, the oversize list; per bucket (+ 1) the list offsets and the fill's cursors; the (bucket -> slot)
 // lists; the sums and the box of indexed cells -- and the staging buffer of a call's host rays and outputs.  The index is valid
@@ -528,6 +544,7 @@ struct ssf_handle {
     NavPathWs navpath;                            // ssf_navpath_waypoints (ssf_navpath.h)
     NavLiveWs navlive;                            // ssf_navlive_overlay (ssf_navlive.h)
     NavSteerWs navsteer;                          // ssf_navsteer_rollouts (ssf_navsteer.h)
+    NavFootWs navfoot;                            // ssf_navfoot_layers, ssf_navfoot_rollouts (ssf_navfoot.h)
     RaycastWs raycast;                            // ssf_raycast (ssf_raycast.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense); the out-of-view
                                                   // compaction keeps rows and order but moves slots: who keeps slot numbers also watches n_recentres (RaycastWs)

@@ -259,7 +259,11 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
     steer (dict(horizon=steps, speed=metres per second), with a plan only): the velocity command of include/ssf_navsteer.h from the
     tracked camera projected into the grid (steer_pose), over steer_lattice's candidates with steps of NAV_STEER_DT seconds, on the
     live layer's state and dist2 when there is one and the grid's otherwise, with the plan's field as the cost and the plan's
-    radius: <k>_steer_traj.npy ((best_len, 3) int32: x, y, heading of the winner's arc) and one log line with the command and the stats"""
+    radius: <k>_steer_traj.npy ((best_len, 3) int32: x, y, heading of the winner's arc) and one log line with the command and the stats.
+    With steer['footprint'] = (front, back, left, right) in metres from the robot's centre (and steer['headings'], default 16) the
+    rollouts test that oriented rectangle instead of the disc alone (include/ssf_navfoot.h): its heading layers are made on the same
+    state with nav_foot_pad's pad and written to <k>_foot_mask.npy (uint32 per cell: bit b = the body fits at heading bin b), with
+    one nav-foot log line; the command is logged as without it"""
     if carve_views is None:
         out = fusion.nav_grid(outputs=("state", "dist2"), res=res)
     else:
@@ -307,8 +311,15 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
                 json.dump(dict(wp["stats"], status=int(wp["status"][0]), path_min=int(wp["path_min"][0]), **kw), f, sort_keys=True)
         if steer is not None:
             on = lv if lv is not None else dict(state=state, dist2=out["dist2"])
-            st = fusion.nav_steer(on["state"], on["dist2"], steer_pose(pose, res, fusion.get_pose()), cost=got["cost"], min_dist2=cells * cells,
-                                  n_steps=int(steer.get("horizon", 32)), **steer_lattice(float(steer.get("speed", 0.5)), res))
+            kw = dict(cost=got["cost"], min_dist2=cells * cells, n_steps=int(steer.get("horizon", 32)), **steer_lattice(float(steer.get("speed", 0.5)), res))
+            if steer.get("footprint") is not None:
+                body, bins = fusion.nav_foot_units(*[float(v) for v in steer["footprint"]], res), int(steer.get("headings", 16))
+                lay = fusion.nav_foot(on["state"], n_headings=bins, pad=fusion.nav_foot_pad(n_headings=bins, **body), **body)
+                np.save(os.path.join(grid_dir, name + "_foot_mask.npy"), lay["free_mask"])
+                print("nav-foot %s: headings=%d %s" % (name, bins, " ".join("%s=%d" % (nm, n) for nm, n in lay["stats"].items())))
+                st = fusion.nav_foot_steer(lay["free_mask"], on["dist2"], steer_pose(pose, res, fusion.get_pose()), bins, **kw)
+            else:
+                st = fusion.nav_steer(on["state"], on["dist2"], steer_pose(pose, res, fusion.get_pose()), **kw)
             np.save(os.path.join(grid_dir, name + "_steer_traj.npy"), st["best_traj"][0])
             v, w = int(st["best_cmd"][0, 0]), int(st["best_cmd"][0, 1])
             print("nav-steer %s: status=%d best=%d v=%d w=%d linear_x=%.4f angular_z=%.4f score=%d n_admissible=%d best_len=%d %s"
@@ -655,6 +666,10 @@ def parse_args(argv=None):
                          "and scored on the device (include/ssf_navsteer.h): one nav-steer log line and <k>_steer_traj.npy per grid")
     ap.add_argument("--nav-steer-horizon", type=int, default=None, metavar="T", help="steps of 0.1 s per rollout, 1..256 (default 32)")
     ap.add_argument("--nav-steer-speed", type=float, default=None, metavar="V", help="the largest speed of the candidates in m/s, > 0 (default 0.5)")
+    ap.add_argument("--nav-steer-footprint", type=float, nargs=4, default=None, metavar=("FRONT", "BACK", "LEFT", "RIGHT"),
+                    help="with --nav-steer: the robot's body as a rectangle, metres from its centre; the rollouts test it at the headings they "
+                         "sweep (include/ssf_navfoot.h) and <k>_foot_mask.npy holds its heading layers")
+    ap.add_argument("--nav-steer-headings", type=int, default=None, metavar="B", help="heading bins of --nav-steer-footprint: 1, 2, 4, 8, 16 or 32 (default 16)")
     ap.add_argument("--laser-scan-dir", default=None, metavar="DIR",
                     help="every --laser-scan-every frames, a planar laser scan simulated from the map on the device, from the tracked pose: "
                          "DIR/<frame number as %%06d>.npy (ranges in metres, +inf where nothing is hit)")
@@ -709,6 +724,14 @@ def parse_args(argv=None):
         ap.error("--nav-steer-horizon is 1..256")
     if a.nav_steer_speed is not None and not a.nav_steer_speed > 0.0:
         ap.error("--nav-steer-speed is > 0")
+    if a.nav_steer_footprint is not None and not a.nav_steer:
+        ap.error("--nav-steer-footprint goes with --nav-steer")
+    if a.nav_steer_footprint is not None and min(a.nav_steer_footprint) < 0.0:
+        ap.error("--nav-steer-footprint takes four lengths >= 0")
+    if a.nav_steer_headings is not None and a.nav_steer_footprint is None:
+        ap.error("--nav-steer-headings goes with --nav-steer-footprint")
+    if a.nav_steer_headings is not None and a.nav_steer_headings not in (1, 2, 4, 8, 16, 32):
+        ap.error("--nav-steer-headings is 1, 2, 4, 8, 16 or 32")
     if (a.nav_frontier_min_cells is not None or a.nav_frontier_gain_radius is not None) and not a.nav_frontiers:
         ap.error("--nav-frontier-min-cells and --nav-frontier-gain-radius go with --nav-frontiers")
     if a.nav_frontier_min_cells is not None and a.nav_frontier_min_cells < 1:
@@ -744,7 +767,10 @@ def nav_steer_of(a):
     """replay()'s nav_steer from the parsed options, or None"""
     if not a.nav_steer:
         return None
-    return dict(horizon=32 if a.nav_steer_horizon is None else int(a.nav_steer_horizon), speed=0.5 if a.nav_steer_speed is None else float(a.nav_steer_speed))
+    steer = dict(horizon=32 if a.nav_steer_horizon is None else int(a.nav_steer_horizon), speed=0.5 if a.nav_steer_speed is None else float(a.nav_steer_speed))
+    if a.nav_steer_footprint is not None:
+        steer.update(footprint=tuple(float(v) for v in a.nav_steer_footprint), headings=16 if a.nav_steer_headings is None else int(a.nav_steer_headings))
+    return steer
 
 
 def nav_frontiers_of(a):
@@ -755,12 +781,29 @@ def nav_frontiers_of(a):
                 gain_radius=0 if a.nav_frontier_gain_radius is None else int(a.nav_frontier_gain_radius))
 
 
-def main():
-    a = parse_args()
+def library_of(a):
+    """the name of binding's loader of the library that exports every entry point the parsed options ask for (the carve's, the plan's,
+    the regions', the waypoints', the live layer's, the commands' and the footprint's entry points: libraries of their own, each
+    holding the one before it)"""
+    steer = nav_steer_of(a)
+    if steer:
+        return "load_foot" if steer.get("footprint") is not None else "load_steer"
+    if nav_live_of(a):
+        return "load_live"
+    if nav_waypoints_of(a):
+        return "load_drive"
+    if nav_frontiers_of(a):
+        return "load_explore"
+    if nav_plan_of(a):
+        return "load_nav"
+    return "load_navcarve" if a.nav_grid_carve else "load_product"
+
+
+def main(argv=None):
+    a = parse_args(argv)
     from . import binding
     plan, frontiers, waypoints, live, steer = nav_plan_of(a), nav_frontiers_of(a), nav_waypoints_of(a), nav_live_of(a), nav_steer_of(a)
-    # (the carve's, the plan's, the regions', the waypoints', the live layer's and the commands' entry points: libraries of their own)
-    lib = binding.load_steer() if steer else binding.load_live() if live else binding.load_drive() if waypoints else binding.load_explore() if frontiers else (binding.load_nav() if plan else (binding.load_navcarve() if a.nav_grid_carve else binding.load_product()))
+    lib = getattr(binding, library_of(a))()
     cfg = lib.default_config(pipeline_depth=2 if a.pipelined else 0, extract_batch=4 if a.pipelined else 1, **BENCHMARK_LAUNCH)
     f = binding.Fusion(lib, cfg)
     if a.raw_frames:
