@@ -32,6 +32,7 @@
 #include "ssf_navlive.h"
 #include "ssf_navsteer.h"
 #include "ssf_navfoot.h"
+#include "ssf_navpose.h"
 #include "ssf_raycast.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
@@ -430,6 +431,34 @@ struct FootprintLayers {
     std::vector<uint32_t> free_mask;
     std::vector<uint8_t> n_free;                        /* with want_n_free */
     ssf_navfoot_stats stats;
+};
+
+/* planPoses (ssf_navpose.h; exported by libssf_hip_pose.so, linked INSTEAD of the other libraries -- a program that does not call it
+ * links as before): the cost-to-goal field over (cell, heading bin) of the body whose layers footprintLayers made, and the state
+ * paths down it.  The members start at ssf_navpose_default_params' values; the heading bins are the layers'. */
+struct PosePlanParams {
+    int min_dist2 = 0;
+    int soft_dist2 = 0, near_penalty = 0;              /* extra cost below a squared clearance; 0 = none */
+    int move_tol = 64;                                  /* direction units between heading and move, 0..256 */
+    bool allow_reverse = true;
+    int reverse_cost = 10, turn_cost = 5;
+    int max_path = 0;                                   /* states per path; 0 = no paths */
+    bool want_cost = false, want_cells = true;          /* the field over the states; its projection onto the cells */
+};
+typedef std::array<int32_t, 3> PoseState;              /* (ix, iy, bin); as a goal, bin -1 = every bin the body fits at */
+/* what planPoses makes: the field, layer-major n_headings x height x width; cell_cost (steerWithFootprint's cost term: costAsPlan)
+ * and cell_bin, height x width; per start its cost, status (ssf_navpose.h step 9) and the states of its path */
+struct PosePlan {
+    int width = 0, height = 0, n_headings = 0;
+    std::vector<uint32_t> cost;                         /* with want_cost; 0xFFFFFFFF = not reached */
+    std::vector<uint32_t> cell_cost;
+    std::vector<uint8_t> cell_bin;                      /* 255 = no bin reached */
+    std::vector<uint32_t> start_cost;
+    std::vector<int32_t> start_status;
+    std::vector<std::vector<PoseState> > paths;
+    ssf_navpose_stats stats;
+    /* cell_cost as the plan steerWithFootprint scores against */
+    NavPlan costAsPlan() const { NavPlan p; p.width = width; p.height = height; p.cost = cell_cost; p.stats = ssf_navplan_stats(); return p; }
 };
 
 /* castRays (ssf_raycast.h; exported by libssf_hip.so only): the first disc of the map that each ray hits.  The members start at
@@ -1145,6 +1174,27 @@ public:
             throw std::logic_error("steerWithFootprint: the layers are not the grid's size (footprintLayers of the same grid)");
         steer_run("steerWithFootprint", g, plan, poses, targets, q, out, FootRollouts(layers.free_mask.data(), layers.n_headings));
     }
+    /* Plan over (x, y, heading) for the body of `layers` (ssf_navpose.h): g: the grid the layers were made of (dist2); goals: states,
+     * bin -1 = any; starts: poses in units, as steerWithFootprint takes them. */
+    void planPoses(const NavGrid& g, const FootprintLayers& layers, const PosePlanParams& q, const std::vector<PoseState>& goals,
+                   const std::vector<SteerPose>& starts, PosePlan& out) {
+        pose_run(g, layers, q, goals, starts, out, PoseField());
+    }
+    /* The poses of a nav_msgs::Path from the path of start `start`, one per state: the cell's centre in the grid frame, taken to the
+     * map frame by pose12 (grid-to-map: NavGrid::stats.pose); the orientation is the grid frame's rotation times the yaw of the
+     * state's bin, bin * 2 pi / n_headings, about the grid's z (fillLocalPlan's arithmetic). */
+    template <typename PathT> static void fillPosePath(const PosePlan& plan, size_t start, const float pose12[12], float res, PathT& msg) {
+        if (start >= plan.paths.size()) throw std::logic_error("fillPosePath: no such start");
+        if (plan.n_headings < 1) throw std::logic_error("fillPosePath: the plan has no heading bins");
+        NavSteer arc;
+        arc.traj.resize(1);
+        const std::vector<PoseState>& st = plan.paths[start];
+        arc.traj[0].resize(st.size());
+        for (size_t k = 0; k < st.size(); k++) {
+            arc.traj[0][k].x = st[k][0] * 1024 + 512; arc.traj[0][k].y = st[k][1] * 1024 + 512; arc.traj[0][k].heading = st[k][2] * (65536 / plan.n_headings);
+        }
+        fillLocalPlan(arc, 0, pose12, res, msg);
+    }
     /* The integer lattice of a dynamic window (pure host arithmetic, no handle): the speeds (m/s) and turn rates (rad/s) reachable
      * from (v_now, w_now) within one step of dt seconds under (accel_v m/s^2, accel_w rad/s^2), cut to [v_lo, v_hi] and [w_lo, w_hi]
      * and to the call's own |v| <= 1024, |w| <= 16384, in units per step: v = speed * dt * 1024 / res, w = rate * dt * 65536 / 2 pi.
@@ -1209,6 +1259,50 @@ private:
             return ssf_navfoot_rollouts(h, p, n_headings, mask, dist2, cost, poses, targets, o, st);
         }
     };
+    /* the pose plan's entry point behind a functor of its own: only a program that calls planPoses references it */
+    struct PoseField {
+        int operator()(ssf_handle* h, const ssf_navpose_params* p, const uint32_t* mask, const int32_t* dist2, const ssf_navpose_out* o,
+                       ssf_navpose_stats* st) const {
+            return ssf_navpose_field(h, p, mask, dist2, o, st);
+        }
+        int defaults(const ssf_handle* h, ssf_navpose_params* p) const { return ssf_navpose_default_params(h, p); }
+    };
+    template <typename Call>
+    void pose_run(const NavGrid& g, const FootprintLayers& layers, const PosePlanParams& q, const std::vector<PoseState>& goals,
+                  const std::vector<SteerPose>& starts, PosePlan& out, const Call& call) {
+        const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
+        if (n == 0 || g.dist2.size() != n) throw std::logic_error("planPoses: the grid has no dist2 (want_dist2)");
+        if (layers.width != g.width || layers.height != g.height || layers.free_mask.size() != n)
+            throw std::logic_error("planPoses: the layers are not the grid's size (footprintLayers of the same grid)");
+        if (!q.want_cost && !q.want_cells && starts.empty()) throw std::logic_error("planPoses: nothing asked for");
+        ssf_navpose_params p;
+        check(call.defaults(need(), &p));
+        p.width = g.width; p.height = g.height; p.n_headings = layers.n_headings; p.min_dist2 = q.min_dist2; p.soft_dist2 = q.soft_dist2;
+        p.near_penalty = q.near_penalty; p.move_tol = q.move_tol; p.allow_reverse = q.allow_reverse ? 1 : 0; p.reverse_cost = q.reverse_cost;
+        p.turn_cost = q.turn_cost; p.max_path = q.max_path; p.on_device = 0;
+        p.goals = goals.empty() ? nullptr : goals[0].data(); p.n_goals = (int)std::min<size_t>(goals.size(), 1u << 30);
+        static_assert(sizeof(SteerPose) == 3 * sizeof(int32_t), "a pose is three int32");
+        p.starts = starts.empty() ? nullptr : &starts[0].x; p.n_starts = (int)std::min<size_t>(starts.size(), 1u << 30);
+        const bool bins = layers.n_headings >= 1 && layers.n_headings <= SSF_NAVFOOT_MAX_HEADINGS && n * (size_t)layers.n_headings <= (size_t)SSF_NAVPOSE_MAX_STATES;
+        const size_t ns = starts.size() <= 4096 ? starts.size() : 0, mp = q.max_path > 0 && q.max_path <= (1 << 20) ? (size_t)q.max_path : 0;
+        out.width = g.width; out.height = g.height; out.n_headings = layers.n_headings;
+        out.cost.resize(q.want_cost && bins ? n * (size_t)layers.n_headings : 0);        /* (a size the library refuses: nothing is written) */
+        out.cell_cost.resize(q.want_cells ? n : 0); out.cell_bin.resize(q.want_cells ? n : 0);
+        out.start_cost.assign(ns, SSF_NAVPOSE_UNREACHED); out.start_status.assign(ns, 0);
+        std::vector<int32_t> len(ns, 0), states(ns * mp * 3);
+        ssf_navpose_out o;
+        o.cost = out.cost.empty() ? nullptr : out.cost.data();
+        o.cell_cost = q.want_cells ? out.cell_cost.data() : nullptr; o.cell_bin = q.want_cells ? out.cell_bin.data() : nullptr;
+        o.start_cost = ns ? out.start_cost.data() : nullptr; o.start_status = ns ? out.start_status.data() : nullptr;
+        o.path_len = ns ? len.data() : nullptr; o.path = states.empty() ? nullptr : states.data();
+        check(call(need(), &p, layers.free_mask.data(), g.dist2.data(), &o, &out.stats));
+        out.paths.assign(ns, std::vector<PoseState>());
+        for (size_t i = 0; i < ns && mp; i++) {
+            out.paths[i].resize((size_t)len[i]);
+            for (size_t k = 0; k < (size_t)len[i]; k++)
+                for (int c = 0; c < 3; c++) out.paths[i][k][(size_t)c] = states[(i * mp + k) * 3 + (size_t)c];
+        }
+    }
     /* steerOnGrid's and steerWithFootprint's body: the params, the outputs' vectors, the call, the arcs */
     template <typename Call>
     void steer_run(const char* who, const NavGrid& g, const NavPlan* plan, const std::vector<SteerPose>& poses, const std::vector<SteerTarget>& targets,

@@ -7,6 +7,8 @@
  * a 0.5 m corridor cannot enter by its circumscribed radius, and by its inscribed radius turns on the spot into the wall.  The
  * standard answer is a global plan by the inscribed radius (ssf_navplan_field as it is) and a local planner that tests the oriented
  * footprint: the two calls here.  Without them a caller copies state out and dilates it per heading on the host at control rate.
+ * Where that global plan is wrong for a long body (a bend it cannot turn, a corridor it drives through lengthwise), ssf_navpose.h plans
+ * over (x, y, heading) on the layers made here, and its cell_cost is the rollouts' `cost`.
  *
  * All arithmetic is integer and the rule has exactly one answer, so the result does not depend on the order the hardware works in,
  * and a small restatement (tests/navfoot_ref.py) reproduces every output bit for bit.

@@ -35,6 +35,9 @@ STEER_LIB = os.path.join(_HERE, "csrc", "libssf_hip_steer.so")
 # steer's objects and the oriented footprint (include/ssf_navfoot.h): the one library of a robot whose base is not round.  None of the
 # seven libraries above exports the footprint's entry points
 FOOT_LIB = os.path.join(_HERE, "csrc", "libssf_hip_foot.so")
+# foot's objects and the plan over (x, y, heading) (include/ssf_navpose.h): the one library of a robot whose global plan knows its
+# body as well.  None of the eight libraries above exports the pose plan's entry points
+POSE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_pose.so")
 
 
 class SsfConfig(C.Structure):
@@ -163,6 +166,10 @@ NAVSTEER_SUBUNITS, NAVSTEER_TURN, NAVSTEER_NO_COST = 1024, 65536, 0xFFFFFFFF
 NAVFOOT_SYMBOLS = ["ssf_navfoot_spans", "ssf_navfoot_default_params", "ssf_navfoot_layers", "ssf_navfoot_rollouts"]
 NAVFOOT_MAX_REACH, NAVFOOT_ROWS, NAVFOOT_MAX_SIDE, NAVFOOT_MAX_PAD = 40, 81, 24576, 4096
 NAVFOOT_HEADINGS = (1, 2, 4, 8, 16, 32)
+# the plan over (x, y, heading) (include/ssf_navpose.h): exported by libssf_hip_pose.so only (load_pose)
+NAVPOSE_SYMBOLS = ["ssf_navpose_moves", "ssf_navpose_default_params", "ssf_navpose_field"]
+NAVPOSE_OUTPUT_NAMES = ("cost", "cell_cost", "cell_bin", "start_cost", "start_status", "path_len", "path")
+NAVPOSE_UNREACHED, NAVPOSE_NO_BIN, NAVPOSE_TILE, NAVPOSE_ROUND_BATCH, NAVPOSE_MAX_STATES = 0xFFFFFFFF, 255, 16, 16, 1 << 26
 # rays cast through the model (include/ssf_raycast.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 RAYCAST_SYMBOLS = ["ssf_raycast_default_params", "ssf_raycast"]
 # the output arrays of ssf_raycast, in its argument order: name, dtype, per-ray shape
@@ -426,6 +433,27 @@ class SsfNavSteerStats(C.Structure):
         return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
 
 
+class SsfNavPoseParams(C.Structure):
+    """ssf_navpose_params (include/ssf_navpose.h)"""
+    _fields_ = [(nm, C.c_int) for nm in ("width", "height", "n_headings", "min_dist2", "soft_dist2", "near_penalty", "move_tol", "allow_reverse",
+                                         "reverse_cost", "turn_cost")] + \
+               [("goals", C.c_void_p), ("n_goals", C.c_int), ("starts", C.c_void_p), ("n_starts", C.c_int), ("max_path", C.c_int), ("on_device", C.c_int)]
+
+
+class SsfNavPoseOut(C.Structure):
+    """ssf_navpose_out (include/ssf_navpose.h)"""
+    _fields_ = [(nm, C.c_void_p) for nm in NAVPOSE_OUTPUT_NAMES]
+
+
+class SsfNavPoseStats(C.Structure):
+    """ssf_navpose_stats (include/ssf_navpose.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("states_traversable", "states_reached", "cells_reached", "goals_used", "goals_blocked", "goals_outside",
+                                           "max_cost", "rounds", "tile_visits")]
+
+    def as_dict(self):
+        return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
+
+
 class SsfNavFootParams(C.Structure):
     """ssf_navfoot_params (include/ssf_navfoot.h)"""
     _fields_ = [(nm, C.c_int) for nm in ("width", "height", "allow_unknown", "n_headings", "front", "back", "left", "right", "pad", "on_device")]
@@ -647,6 +675,11 @@ class Library:
             L.ssf_navfoot_layers.argtypes = [vp, C.POINTER(SsfNavFootParams), vp, C.POINTER(SsfNavFootOut), C.POINTER(SsfNavFootStats)]
             L.ssf_navfoot_rollouts.argtypes = [vp, C.POINTER(SsfNavSteerParams), C.c_int, vp, vp, vp, vp, vp, C.POINTER(SsfNavSteerOut),
                                                C.POINTER(SsfNavSteerStats)]
+        self.has_navpose = all(hasattr(L, nm) for nm in NAVPOSE_SYMBOLS)
+        if self.has_navpose:
+            L.ssf_navpose_moves.argtypes = [C.c_int, C.c_int, C.c_int, vp]
+            L.ssf_navpose_default_params.argtypes = [vp, C.POINTER(SsfNavPoseParams)]
+            L.ssf_navpose_field.argtypes = [vp, C.POINTER(SsfNavPoseParams), vp, vp, C.POINTER(SsfNavPoseOut), C.POINTER(SsfNavPoseStats)]
         self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
         if self.has_navgrid:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
@@ -826,6 +859,30 @@ def navfoot_spans(front, back, left, right, pad, n_headings, library=None):
         raise SsfError("ssf_navfoot_spans refused the footprint (%d): sides 0..%d, pad 0..%d, n_headings one of %s, reach <= %d cells"
                        % (rc, NAVFOOT_MAX_SIDE, NAVFOOT_MAX_PAD, NAVFOOT_HEADINGS, NAVFOOT_MAX_REACH))
     return spans, int(reach.value), int(cells.value)
+
+
+def load_pose():
+    """Load libssf_hip_pose.so: foot's objects (the product and every navigation call up to the oriented footprint) with the plan over
+    (x, y, heading) linked in (include/ssf_navpose.h).  A handle belongs to the library that created it: create the Fusion from THIS
+    library to call nav_pose_plan or nav_live_pose_steer on it.  Fails loudly when it has not been built."""
+    import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
+    return Library(POSE_LIB)
+
+
+def navpose_moves(n_headings, move_tol, allow_reverse, library=None):
+    """The move table of include/ssf_navpose.h step 5 as ssf_navpose_moves returns it: n_headings x 8 int8, 0 = not a move of the bin,
+    1 = forward, 2 = reverse.  It takes no handle and touches no device.  library: a Library that exports it (default: load_pose())."""
+    lib = library or load_pose()
+    if not lib.has_navpose:
+        raise SsfError("%s does not export ssf_navpose_moves: it plans over no headings (include/ssf_navpose.h: libssf_hip_pose.so, "
+                       "binding.load_pose)" % lib.path)
+    B = int(n_headings)
+    out = np.zeros((B if B in NAVFOOT_HEADINGS else 1, 8), np.int8)
+    rc = lib.lib.ssf_navpose_moves(B, int(move_tol), int(allow_reverse), _ptr(out))
+    if rc != 0:
+        raise SsfError("ssf_navpose_moves refused its arguments (%d): n_headings one of %s, move_tol 0..256, allow_reverse 0 or 1"
+                       % (rc, NAVFOOT_HEADINGS))
+    return out
 
 
 def load_lab():
@@ -2386,6 +2443,154 @@ class Fusion:
         res = dict(live=dict(stats=live_stats), plan=dict(stats=plan_stats), foot=dict(stats=foot_stats), steer=got)
         if keep_mask:
             res["foot"]["free_mask"] = d_mask.cpu().numpy().view(np.uint32)
+        return res
+
+    # ---- plan over (x, y, heading): the cost-to-goal field over (cell, heading bin) and the state paths (include/ssf_navpose.h) ----
+    def _need_navpose(self, symbol):
+        if not self.L.has_navpose:
+            raise SsfError("%s does not export %s: it plans over no headings (include/ssf_navpose.h: libssf_hip_pose.so, binding.load_pose)"
+                           % (self.L.path, symbol))
+
+    @staticmethod
+    def _triple_list(a, what):
+        if a is None or len(a) == 0:
+            return np.zeros((0, 3), np.int32)
+        a = np.asarray(a)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise SsfError("%s are n x 3, got shape %s" % (what, a.shape))
+        return np.ascontiguousarray(a, np.int32)
+
+    def _navpose_params(self, on_device, width, height, goals, starts, params):
+        """(SsfNavPoseParams, the goal and start arrays it points into).  goals: n x 3 (ix, iy, bin; bin -1 = any); starts: n x 3 poses
+        (x, y, heading) in units; host memory both; params: the other fields of ssf_navpose_params by name, each at
+        ssf_navpose_default_params' value when missing."""
+        p = SsfNavPoseParams()
+        self._ck(self.L.lib.ssf_navpose_default_params(self.h, C.byref(p)), "ssf_navpose_default_params")
+        g, s = self._triple_list(goals, "goals"), self._triple_list(starts, "starts")
+        kinds = dict(p._fields_)
+        for nm, val in params.items():
+            if nm not in kinds or nm in ("width", "height", "goals", "n_goals", "starts", "n_starts", "on_device"):
+                raise SsfError("unknown pose plan parameter %r" % nm)
+            setattr(p, nm, int(val))
+        p.width, p.height, p.on_device = int(width), int(height), int(bool(on_device))
+        p.goals, p.n_goals = (g.ctypes.data if len(g) else None), len(g)
+        p.starts, p.n_starts = (s.ctypes.data if len(s) else None), len(s)
+        return p, (g, s)
+
+    def _navpose_field(self, p, free_mask, dist2, ptrs):
+        st = SsfNavPoseStats()
+        out = SsfNavPoseOut(*[ptrs.get(nm) for nm in NAVPOSE_OUTPUT_NAMES])
+        self._ck(self.L.lib.ssf_navpose_field(self.h, C.byref(p), free_mask, dist2, C.byref(out), C.byref(st)), "ssf_navpose_field")
+        return st.as_dict()
+
+    def nav_pose_plan(self, free_mask, dist2, goals, starts=None, outputs=NAVPOSE_OUTPUT_NAMES, **params):
+        """The cost-to-goal field over (cell, heading bin) of an oriented footprint and the state paths down it (ssf_navpose_field),
+        host arrays.  free_mask H x W uint32 as nav_foot returns it for n_headings bins, dist2 H x W int32; goals: n x 3 (ix, iy, bin),
+        bin -1 = every bin the body fits at; starts: n x 3 poses (x, y, heading) in nav_steer's units.  Returns a dict of the requested
+        outputs -- cost B x H x W u32 (0xFFFFFFFF: not reached), cell_cost H x W u32 (the minimum over the bins: nav_foot_steer's
+        `cost`), cell_bin H x W u8 (255: none), start_cost, start_status, path_len, path: a list with one (len, 3) int32 array
+        (ix, iy, bin) per start -- and 'stats'.  params: n_headings, min_dist2, soft_dist2, near_penalty, move_tol, allow_reverse,
+        reverse_cost, turn_cost, max_path."""
+        self._need_navpose("ssf_navpose_field")
+        bad = [nm for nm in outputs if nm not in NAVPOSE_OUTPUT_NAMES]
+        if bad:
+            raise SsfError("unknown pose plan outputs %s (known: %s)" % (bad, ", ".join(NAVPOSE_OUTPUT_NAMES)))
+        free_mask, dist2 = np.ascontiguousarray(free_mask, np.uint32), np.ascontiguousarray(dist2, np.int32)
+        if free_mask.ndim != 2 or dist2.shape != free_mask.shape:
+            raise SsfError("free_mask and dist2 are H x W arrays of one shape, got %s and %s" % (free_mask.shape, dist2.shape))
+        H, W = free_mask.shape
+        p, keep = self._navpose_params(False, W, H, goals, starts, params)
+        n, mp = p.n_starts, max(p.max_path, 0)
+        B = p.n_headings if p.n_headings in NAVFOOT_HEADINGS and H * W * p.n_headings <= NAVPOSE_MAX_STATES else 1     # (else the call refuses)
+        shapes = dict(cost=((B, H, W), np.uint32), cell_cost=((H, W), np.uint32), cell_bin=((H, W), np.uint8), start_cost=((n,), np.uint32),
+                      start_status=((n,), np.int32), path_len=((n,), np.int32), path=((n, min(mp, 1 << 20), 3), np.int32))
+        want = set(outputs)
+        if "path" in want:
+            want.add("path_len")                     # (the lengths cut the paths)
+        out = {nm: np.zeros(*shapes[nm]) for nm in NAVPOSE_OUTPUT_NAMES if nm in want}
+        stats = self._navpose_field(p, _ptr(free_mask), _ptr(dist2), {nm: _ptr(a) for nm, a in out.items()})
+        if "path" in out:
+            out["path"] = [out["path"][i, :out["path_len"][i]].copy() for i in range(n)]
+        if "path_len" not in outputs:
+            out.pop("path_len", None)
+        out["stats"] = stats
+        return out
+
+    def nav_pose_plan_device(self, free_mask, dist2, width, height, goals, starts=None, cost=None, cell_cost=None, cell_bin=None, start_cost=None,
+                             start_status=None, path_len=None, path=None, **params):
+        """ssf_navpose_field on device memory: free_mask, dist2 and each output are a contiguous torch tensor on the device or the
+        device address (int) of a buffer of the shape and dtype nav_pose_plan works on (path: n_starts x max_path x 3 int32; outputs
+        may be None, not all): nav_foot_device's free_mask is read where it lies, and cell_cost is nav_foot_steer_device's `cost`.
+        goals and starts stay host memory.  Returns the stats dict."""
+        self._need_navpose("ssf_navpose_field")
+        p, keep = self._navpose_params(True, width, height, goals, starts, params)
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        return self._navpose_field(p, addr(free_mask), addr(dist2), dict(cost=addr(cost), cell_cost=addr(cell_cost), cell_bin=addr(cell_bin),
+                                                                         start_cost=addr(start_cost), start_status=addr(start_status),
+                                                                         path_len=addr(path_len), path=addr(path)))
+
+    def nav_pose_default_params(self):
+        """ssf_navpose_default_params as a dict"""
+        self._need_navpose("ssf_navpose_default_params")
+        p = SsfNavPoseParams()
+        self._ck(self.L.lib.ssf_navpose_default_params(self.h, C.byref(p)), "ssf_navpose_default_params")
+        return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm not in ("goals", "starts")}
+
+    def nav_live_pose_steer(self, depth, state, goals, poses, foot, targets=None, mask=None, live=None, pose=None, steer=None, keep_mask=False,
+                            keep_cost=False):
+        """Overlay, disc clearance, heading layers, the plan over (x, y, heading) and the rollouts on its cell_cost, with nothing but
+        the command leaving the device: nav_live_foot_steer with nav_pose_plan_device in the place of the disc's plan.  goals: n x 3
+        (ix, iy, bin), bin -1 = any; foot: nav_foot's keywords (pad defaults to nav_foot_pad's); pose: nav_pose_plan's parameters
+        (n_headings is the footprint's).  Returns a dict: 'live', 'foot' and 'pose' (stats; with keep_mask 'free_mask' under 'foot',
+        with keep_cost 'cell_cost' under 'pose', copied out) and 'steer' (the per-pose outputs as nav_steer returns them, and stats)."""
+        import torch
+        self._need_navlive("ssf_navlive_overlay")
+        self._need_navfoot("ssf_navfoot_rollouts")
+        self._need_navpose("ssf_navpose_field")
+        live, pq, fq, sq = dict(live or {}), dict(pose or {}), dict(foot or {}), dict(steer or {})
+        state = np.ascontiguousarray(state, np.int8)
+        if state.ndim != 2:
+            raise SsfError("state is a height x width array, got shape %s" % (state.shape,))
+        H, W = state.shape
+        poses = np.ascontiguousarray(poses, np.int32)
+        if poses.ndim != 2 or poses.shape[1] != 3 or poses.shape[0] < 1:
+            raise SsfError("poses are n x 3 (x, y, heading) in units, n >= 1, got shape %s" % (poses.shape,))
+        n = poses.shape[0]
+        fq.setdefault("n_headings", self.nav_foot_default_params()["n_headings"])
+        if pq.setdefault("n_headings", fq["n_headings"]) != fq["n_headings"]:
+            raise SsfError("the pose plan's n_headings is the footprint's (%d), got %d" % (fq["n_headings"], pq["n_headings"]))
+        fq.setdefault("allow_unknown", sq.get("allow_unknown", 0))
+        fq.setdefault("pad", self.nav_foot_pad(fq.get("front", 0), fq.get("back", 0), fq.get("left", 0), fq.get("right", 0), fq["n_headings"]))
+        dev = torch.device("cuda")
+        if not isinstance(depth, torch.Tensor):
+            depth = torch.from_numpy(np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32).view(
+                np.int16 if self.depth_format == "u16" else np.float32)).to(dev)
+        if mask is not None and not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).to(dev)
+        d_state = torch.from_numpy(state).to(dev)
+        d_dist2 = torch.empty((H, W), dtype=torch.int32, device=dev)
+        d_cost = torch.empty((H, W), dtype=torch.int32, device=dev)       # (uint32 words)
+        d_mask = torch.empty((H, W), dtype=torch.int32, device=dev)       # (uint32 words)
+        live_stats = self.nav_live_device(depth, d_state, W, H, mask=mask, state_out=d_state, dist2=d_dist2, **live)
+        foot_stats = self.nav_foot_device(d_state, W, H, free_mask=d_mask, **fq)
+        pose_stats = self.nav_pose_plan_device(d_mask, d_dist2, W, H, goals, None, cell_cost=d_cost, **pq)
+        sq.setdefault("min_dist2", pq.get("min_dist2", 0))
+        sq.setdefault("allow_unknown", fq["allow_unknown"])
+        p = self._navsteer_params(True, W, H, n, sq)
+        T = min(max(p.n_steps, 0), 256)
+        d_poses = torch.from_numpy(poses).to(dev)
+        d_targets = None if targets is None else torch.from_numpy(np.ascontiguousarray(targets, np.int32)).to(dev)
+        o = {nm: torch.zeros(self._navsteer_shape(kind, tail, n, 1, T), dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
+             for nm, dt, kind, tail in NAVSTEER_OUTPUTS if kind == "pose"}
+        steer_stats = self.nav_foot_steer_device(d_mask, d_dist2, W, H, d_poses, n, fq["n_headings"], cost=d_cost, targets=d_targets, **dict(o, **sq))
+        got = {nm: a.cpu().numpy() for nm, a in o.items()}
+        got["best_traj"] = [got["best_traj"][i, :got["best_len"][i]].copy() for i in range(n)]
+        got["stats"] = steer_stats
+        res = dict(live=dict(stats=live_stats), foot=dict(stats=foot_stats), pose=dict(stats=pose_stats), steer=got)
+        if keep_mask:
+            res["foot"]["free_mask"] = d_mask.cpu().numpy().view(np.uint32)
+        if keep_cost:
+            res["pose"]["cell_cost"] = d_cost.cpu().numpy().view(np.uint32)
         return res
 
     # ---- rays cast through the model: the first disc each ray hits (include/ssf_raycast.h) ------------

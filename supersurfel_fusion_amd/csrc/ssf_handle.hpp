@@ -413,6 +413,21 @@ struct NavFootWs {
     unsigned char* io = nullptr; size_t io_bytes = 0;
     unsigned long long* pk = nullptr; size_t pk_cells = 0;
 };
+// ssf_navpose_field (ssf_navpose.h, ssf_navpose.hip: linked into libssf_hip_pose.so only): per cell the mask and dist2 as the call got
+// them (the copies of host arrays), the packed (traversable bins, penalty) word of 8 bytes, the projection (cell_cost, cell_bin); per
+// state the cost; per 16 x 16-cell tile the two ping-pong flag words; the goals (65536 triples) and starts (4096 triples) with the
+// starts' results; the paths of a call with host outputs; the sums.  Allocated on first use; each group is grown as a whole or not at
+// all (DevBufs::grow).  Nothing here is read or written by the frame path.
+struct NavPoseWs {
+    DevBufs bufs;
+    uint32_t* mask = nullptr; int32_t* dist2 = nullptr; unsigned long long* pk = nullptr; uint32_t* cell_cost = nullptr; uint8_t* cell_bin = nullptr;
+    size_t cells = 0;
+    uint32_t* cost = nullptr; size_t states = 0;
+    uint32_t* flags = nullptr; size_t tiles = 0;
+    int32_t* goals = nullptr; int32_t* starts = nullptr; uint32_t* start_cost = nullptr; int32_t* start_status = nullptr; int32_t* path_len = nullptr;
+    unsigned long long* stats = nullptr;
+    int32_t* path = nullptr; size_t path_words = 0;
+};
 // ssf_raycast (ssf_raycast.h): the resident index -- per slot the 64-byte record and the box of cells with the row's class, the
 // out-of-view blocks' live offsets, the oversize list; per bucket (+ 1) the list offsets and the fill's cursors; the (bucket -> slot)
 // lists; the sums and the box of indexed cells -- and the staging buffer of a call's host rays and outputs.  The index is valid
@@ -545,6 +560,7 @@ struct ssf_handle {
     NavLiveWs navlive;                            // ssf_navlive_overlay (ssf_navlive.h)
     NavSteerWs navsteer;                          // ssf_navsteer_rollouts (ssf_navsteer.h)
     NavFootWs navfoot;                            // ssf_navfoot_layers, ssf_navfoot_rollouts (ssf_navfoot.h)
+    NavPoseWs navpose;                            // ssf_navpose_field (ssf_navpose.h)
     RaycastWs raycast;                            // ssf_raycast (ssf_raycast.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense); the out-of-view
                                                   // compaction keeps rows and order but moves slots: who keeps slot numbers also watches n_recentres (RaycastWs)

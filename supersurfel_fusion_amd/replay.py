@@ -263,7 +263,10 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
     With steer['footprint'] = (front, back, left, right) in metres from the robot's centre (and steer['headings'], default 16) the
     rollouts test that oriented rectangle instead of the disc alone (include/ssf_navfoot.h): its heading layers are made on the same
     state with nav_foot_pad's pad and written to <k>_foot_mask.npy (uint32 per cell: bit b = the body fits at heading bin b), with
-    one nav-foot log line; the command is logged as without it"""
+    one nav-foot log line; the command is logged as without it.  With steer['poses'] = dict(turn_cost) as well, the rollouts' cost term
+    is no longer the disc's field but the projection of the plan over (x, y, heading) for that body (include/ssf_navpose.h), from the
+    plan's goal cells at any heading and the steer pose: <k>_pose_cost.npy (cell_cost), <k>_pose_bin.npy, <k>_pose_path.npy ((len, 3)
+    int32: ix, iy, bin) and one nav-pose log line with the start's status and cost and the stats"""
     if carve_views is None:
         out = fusion.nav_grid(outputs=("state", "dist2"), res=res)
     else:
@@ -317,7 +320,18 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
                 lay = fusion.nav_foot(on["state"], n_headings=bins, pad=fusion.nav_foot_pad(n_headings=bins, **body), **body)
                 np.save(os.path.join(grid_dir, name + "_foot_mask.npy"), lay["free_mask"])
                 print("nav-foot %s: headings=%d %s" % (name, bins, " ".join("%s=%d" % (nm, n) for nm, n in lay["stats"].items())))
-                st = fusion.nav_foot_steer(lay["free_mask"], on["dist2"], steer_pose(pose, res, fusion.get_pose()), bins, **kw)
+                at = steer_pose(pose, res, fusion.get_pose())
+                if steer.get("poses") is not None:
+                    pp = fusion.nav_pose_plan(lay["free_mask"], on["dist2"], [(int(g[0]), int(g[1]), -1) for g in goals], at,
+                                              outputs=("cell_cost", "cell_bin", "start_cost", "start_status", "path"), n_headings=bins,
+                                              min_dist2=cells * cells, turn_cost=int(steer["poses"].get("turn_cost", 5)), max_path=16 * sum(state.shape))
+                    for nm in ("cell_cost", "cell_bin"):
+                        np.save(os.path.join(grid_dir, name + "_pose_" + nm[5:] + ".npy"), pp[nm])
+                    np.save(os.path.join(grid_dir, name + "_pose_path.npy"), pp["path"][0])
+                    print("nav-pose %s: headings=%d status=%d cost=%d path=%d %s" % (name, bins, int(pp["start_status"][0]), int(pp["start_cost"][0]),
+                                                                                    len(pp["path"][0]), " ".join("%s=%d" % (nm, n) for nm, n in pp["stats"].items())))
+                    kw["cost"] = pp["cell_cost"]
+                st = fusion.nav_foot_steer(lay["free_mask"], on["dist2"], at, bins, **kw)
             else:
                 st = fusion.nav_steer(on["state"], on["dist2"], steer_pose(pose, res, fusion.get_pose()), **kw)
             np.save(os.path.join(grid_dir, name + "_steer_traj.npy"), st["best_traj"][0])
@@ -670,6 +684,10 @@ def parse_args(argv=None):
                     help="with --nav-steer: the robot's body as a rectangle, metres from its centre; the rollouts test it at the headings they "
                          "sweep (include/ssf_navfoot.h) and <k>_foot_mask.npy holds its heading layers")
     ap.add_argument("--nav-steer-headings", type=int, default=None, metavar="B", help="heading bins of --nav-steer-footprint: 1, 2, 4, 8, 16 or 32 (default 16)")
+    ap.add_argument("--nav-plan-poses", action="store_true",
+                    help="with --nav-steer-footprint and --nav-plan-goal: plan over (x, y, heading) for that body (include/ssf_navpose.h) and score the "
+                         "rollouts on its field instead of the disc's: one nav-pose log line, <k>_pose_cost.npy, <k>_pose_bin.npy and <k>_pose_path.npy")
+    ap.add_argument("--nav-plan-turn-cost", type=int, default=None, metavar="C", help="with --nav-plan-poses: the cost of turning by one heading bin, 1..1000 (default 5)")
     ap.add_argument("--laser-scan-dir", default=None, metavar="DIR",
                     help="every --laser-scan-every frames, a planar laser scan simulated from the map on the device, from the tracked pose: "
                          "DIR/<frame number as %%06d>.npy (ranges in metres, +inf where nothing is hit)")
@@ -732,6 +750,12 @@ def parse_args(argv=None):
         ap.error("--nav-steer-headings goes with --nav-steer-footprint")
     if a.nav_steer_headings is not None and a.nav_steer_headings not in (1, 2, 4, 8, 16, 32):
         ap.error("--nav-steer-headings is 1, 2, 4, 8, 16 or 32")
+    if a.nav_plan_poses and (a.nav_steer_footprint is None or not a.nav_plan_goal):
+        ap.error("--nav-plan-poses goes with --nav-steer-footprint and --nav-plan-goal (its goals are cells, not the frontier)")
+    if a.nav_plan_turn_cost is not None and not a.nav_plan_poses:
+        ap.error("--nav-plan-turn-cost goes with --nav-plan-poses")
+    if a.nav_plan_turn_cost is not None and not 1 <= a.nav_plan_turn_cost <= 1000:
+        ap.error("--nav-plan-turn-cost is 1..1000")
     if (a.nav_frontier_min_cells is not None or a.nav_frontier_gain_radius is not None) and not a.nav_frontiers:
         ap.error("--nav-frontier-min-cells and --nav-frontier-gain-radius go with --nav-frontiers")
     if a.nav_frontier_min_cells is not None and a.nav_frontier_min_cells < 1:
@@ -770,6 +794,8 @@ def nav_steer_of(a):
     steer = dict(horizon=32 if a.nav_steer_horizon is None else int(a.nav_steer_horizon), speed=0.5 if a.nav_steer_speed is None else float(a.nav_steer_speed))
     if a.nav_steer_footprint is not None:
         steer.update(footprint=tuple(float(v) for v in a.nav_steer_footprint), headings=16 if a.nav_steer_headings is None else int(a.nav_steer_headings))
+    if a.nav_plan_poses:
+        steer.update(poses=dict(turn_cost=5 if a.nav_plan_turn_cost is None else int(a.nav_plan_turn_cost)))
     return steer
 
 
@@ -783,10 +809,12 @@ def nav_frontiers_of(a):
 
 def library_of(a):
     """the name of binding's loader of the library that exports every entry point the parsed options ask for (the carve's, the plan's,
-    the regions', the waypoints', the live layer's, the commands' and the footprint's entry points: libraries of their own, each
-    holding the one before it)"""
+    the regions', the waypoints', the live layer's, the commands', the footprint's and the pose plan's entry points: libraries of their
+    own, each holding the one before it)"""
     steer = nav_steer_of(a)
     if steer:
+        if steer.get("poses") is not None:
+            return "load_pose"
         return "load_foot" if steer.get("footprint") is not None else "load_steer"
     if nav_live_of(a):
         return "load_live"
