@@ -33,6 +33,7 @@
 #include "ssf_navsteer.h"
 #include "ssf_navfoot.h"
 #include "ssf_navpose.h"
+#include "ssf_navdyn.h"
 #include "ssf_raycast.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
@@ -459,6 +460,69 @@ struct PosePlan {
     ssf_navpose_stats stats;
     /* cell_cost as the plan steerWithFootprint scores against */
     NavPlan costAsPlan() const { NavPlan p; p.width = width; p.height = height; p.cost = cell_cost; p.stats = ssf_navplan_stats(); return p; }
+};
+
+/* steerAmongMovers, steerFootprintAmongMovers and moverBlobs (ssf_navdyn.h; exported by libssf_hip_dyn.so, linked INSTEAD of the other
+ * libraries -- a program that calls none of them links as before): the rollouts refused where they meet a predicted mover and scored
+ * by the gap they keep, and the moving pixels of a depth frame as blobs in the grid frame.  Units as in ssf_navdyn.h: sub-units
+ * (1024 per cell) and sub-units per step. */
+struct Mover { int32_t x, y, vx, vy, r, grow; };
+struct MoverBlob { int32_t label, n, cx, cy, r, ex, ey, pad; };
+struct MoverParams {
+    int mover_cap = 4096, mover_weight = 1;             /* ssf_navdyn_default_params' values */
+    bool want_candidates = false;                       /* cand_hit and cand_min_gap, n_poses x K */
+};
+/* what the two steering members make: a NavSteer (fillTwist and fillLocalPlan take it as it is) with the winner's smallest gap per pose
+ * (-1: no winner) and, with want_candidates, the mover that ended each rollout (-1: none) and each rollout's smallest gap */
+struct NavSteerAmongMovers : NavSteer {
+    std::vector<int32_t> min_gap, cand_hit, cand_min_gap;
+    ssf_navdyn_stats dyn;
+};
+struct MoverBlobParams {
+    int min_points = 16, max_blobs = SSF_NAVDYN_MAX_BLOBS;
+};
+struct MoverBlobs {
+    std::vector<MoverBlob> blobs;                       /* ordered by (-n, label) */
+    ssf_navdyn_blob_stats stats;
+};
+/* From two successive blob tables to movers: host only, integer only (ssf_navdyn.h part C; binding.MoverTracker states the same rule).
+ * gate: the largest centre distance of a match; inflate: added to every radius (the robot's own radius goes here); grow: the growth
+ * of a matched mover per step; grow_unmatched: that of a blob without a predecessor, whose velocity is taken as 0. */
+class MoverTracker {
+public:
+    explicit MoverTracker(int gate = 2048, int inflate = 0, int grow = 16, int grow_unmatched = 128)
+        : gate_(gate), inflate_(inflate), grow_(grow), grow_unmatched_(grow_unmatched) {}
+    void reset() { prev_.clear(); }
+    /* steps_since >= 1: the rollout steps between the previous table and this one.  Every field is clamped to the call's bounds. */
+    std::vector<Mover> update(const std::vector<MoverBlob>& blobs, int steps_since = 1) {
+        if (steps_since < 1 || blobs.size() > (size_t)SSF_NAVDYN_MAX_BLOBS) throw std::invalid_argument("MoverTracker::update takes at most 64 blobs and steps_since >= 1");
+        std::vector<bool> used(prev_.size(), false);
+        std::vector<Mover> out(blobs.size());
+        for (size_t i = 0; i < blobs.size(); i++) {
+            const long long cx = blobs[i].cx, cy = blobs[i].cy;
+            long long best_d2 = -1; size_t best = 0;
+            for (size_t j = 0; j < prev_.size(); j++) {
+                if (used[j]) continue;
+                const long long dx = cx - prev_[j].cx, dy = cy - prev_[j].cy, d2 = dx * dx + dy * dy;
+                if (d2 <= (long long)gate_ * gate_ && (best_d2 < 0 || d2 < best_d2)) { best_d2 = d2; best = j; }      /* (j grows: the smaller index wins a tie) */
+            }
+            long long vx = 0, vy = 0, grow = grow_unmatched_;
+            if (best_d2 >= 0) {
+                used[best] = true;
+                vx = floor_div(cx - prev_[best].cx, steps_since); vy = floor_div(cy - prev_[best].cy, steps_since); grow = grow_;
+            }
+            Mover& m = out[i];
+            m.x = clamp(cx, -(1 << 24), 1 << 24); m.y = clamp(cy, -(1 << 24), 1 << 24); m.vx = clamp(vx, -4096, 4096); m.vy = clamp(vy, -4096, 4096);
+            m.r = clamp((long long)blobs[i].r + inflate_, 0, 1 << 20); m.grow = clamp(grow, 0, 4096);
+        }
+        prev_ = blobs;
+        return out;
+    }
+private:
+    static long long floor_div(long long a, long long b) { const long long q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }
+    static int32_t clamp(long long v, long long lo, long long hi) { return (int32_t)(v < lo ? lo : (v > hi ? hi : v)); }
+    int gate_, inflate_, grow_, grow_unmatched_;
+    std::vector<MoverBlob> prev_;
 };
 
 /* castRays (ssf_raycast.h; exported by libssf_hip.so only): the first disc of the map that each ray hits.  The members start at
@@ -1174,6 +1238,47 @@ public:
             throw std::logic_error("steerWithFootprint: the layers are not the grid's size (footprintLayers of the same grid)");
         steer_run("steerWithFootprint", g, plan, poses, targets, q, out, FootRollouts(layers.free_mask.data(), layers.n_headings));
     }
+    /* steerOnGrid among predicted movers (ssf_navdyn.h part A): a step is refused where it lies inside a mover's disc of that step, and
+     * the score gains m.mover_weight * the lack of gap below m.mover_cap.  movers: at most 64 (MoverTracker::update makes them), one
+     * list for all poses; a mover's r carries the robot's own radius. */
+    void steerAmongMovers(const NavGrid& g, const NavPlan* plan, const std::vector<SteerPose>& poses, const std::vector<SteerTarget>& targets,
+                          const std::vector<Mover>& movers, const SteerParams& q, const MoverParams& m, NavSteerAmongMovers& out) {
+        const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
+        if (n == 0 || g.state.size() != n || g.dist2.size() != n) throw std::logic_error("steerAmongMovers: the grid has no state or no dist2 (want_state, want_dist2)");
+        MoverCall mc(movers, m, q, poses.size(), out);
+        steer_run("steerAmongMovers", g, plan, poses, targets, q, out, DynDiscRollouts(g.state.data(), mc));
+    }
+    /* steerWithFootprint among predicted movers: a mover's r carries the body's circumscribed radius. */
+    void steerFootprintAmongMovers(const NavGrid& g, const FootprintLayers& layers, const NavPlan* plan, const std::vector<SteerPose>& poses,
+                                   const std::vector<SteerTarget>& targets, const std::vector<Mover>& movers, const SteerParams& q, const MoverParams& m,
+                                   NavSteerAmongMovers& out) {
+        const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
+        if (n == 0 || g.dist2.size() != n) throw std::logic_error("steerFootprintAmongMovers: the grid has no dist2 (want_dist2)");
+        if (layers.width != g.width || layers.height != g.height || layers.free_mask.size() != n)
+            throw std::logic_error("steerFootprintAmongMovers: the layers are not the grid's size (footprintLayers of the same grid)");
+        MoverCall mc(movers, m, q, poses.size(), out);
+        steer_run("steerFootprintAmongMovers", g, plan, poses, targets, q, out, DynFootRollouts(layers.free_mask.data(), layers.n_headings, mc));
+    }
+    /* The moving pixels of a depth frame as blobs in g's frame (ssf_navdyn.h part B).  depth in the handle's input format (float metres
+     * or uint16 counts), mask and label as ssf_motion_mask writes them, all of the camera's size; q: the camera, the depth range and the
+     * band, as overlayDepthFrame takes them (its other members are not read). */
+    void moverBlobs(const NavGrid& g, const LiveParams& q, const void* depth, const std::vector<uint8_t>& mask, const std::vector<int32_t>& label,
+                    const MoverBlobParams& b, MoverBlobs& out) {
+        const size_t npix = q.width > 0 ? (size_t)q.width * (size_t)(q.height > 0 ? q.height : 0) : (size_t)width_ * (size_t)height_;
+        if (!depth || mask.size() != npix || label.size() != npix) throw std::invalid_argument("moverBlobs: depth, mask and label must be width x height of the camera");
+        ssf_navdyn_blob_params p;
+        check(ssf_navdyn_default_blob_params(need(), &p));
+        float cam[12];
+        if (q.cam_pose) { transform3_to_rt(*q.cam_pose, cam); p.cam_pose = cam; }
+        p.grid_pose = g.stats.pose; p.width = g.width; p.height = g.height; p.res = g.res; p.floor_max = q.floor_max; p.z_max = q.z_max;
+        p.fx = q.fx; p.fy = q.fy; p.cx = q.cx; p.cy = q.cy; p.cam_width = q.width; p.cam_height = q.height; p.t_min = q.t_min; p.t_max = q.t_max;
+        p.min_points = b.min_points; p.max_blobs = b.max_blobs; p.on_device = 0; p.frame_on_device = 0;
+        static_assert(sizeof(MoverBlob) == SSF_NAVDYN_BLOB_WORDS * sizeof(int32_t), "a blob is eight int32");
+        std::vector<MoverBlob> rows((size_t)SSF_NAVDYN_MAX_BLOBS);
+        check(ssf_navdyn_blobs(need(), &p, depth, mask.data(), label.data(), &rows[0].label, &out.stats));
+        rows.resize((size_t)out.stats.blobs_written);
+        out.blobs.swap(rows);
+    }
     /* Plan over (x, y, heading) for the body of `layers` (ssf_navpose.h): g: the grid the layers were made of (dist2); goals: states,
      * bin -1 = any; starts: poses in units, as steerWithFootprint takes them. */
     void planPoses(const NavGrid& g, const FootprintLayers& layers, const PosePlanParams& q, const std::vector<PoseState>& goals,
@@ -1259,6 +1364,45 @@ private:
             return ssf_navfoot_rollouts(h, p, n_headings, mask, dist2, cost, poses, targets, o, st);
         }
     };
+    /* what the movers add to a rollouts call: the params, the list, the outputs' vectors (sized as steer_run sizes its own) */
+    struct MoverCall {
+        ssf_navdyn_params dp; const int32_t* movers; ssf_navdyn_out o; ssf_navdyn_stats* stats;
+        MoverCall(const std::vector<Mover>& mv, const MoverParams& m, const SteerParams& q, size_t np, NavSteerAmongMovers& out) {
+            static_assert(sizeof(Mover) == SSF_NAVDYN_MOVER_WORDS * sizeof(int32_t), "a mover is six int32");
+            dp.n_movers = (int)std::min<size_t>(mv.size(), 1u << 30); dp.mover_cap = m.mover_cap; dp.mover_weight = m.mover_weight;
+            movers = mv.empty() ? nullptr : &mv[0].x;
+            size_t K, T1;
+            steer_sizes(q, np, K, T1);
+            const size_t nk = m.want_candidates ? np * K : 0;
+            out.min_gap.assign(np, -1); out.cand_hit.assign(nk, -1); out.cand_min_gap.assign(nk, -1);
+            o.cand_hit = nk ? out.cand_hit.data() : nullptr; o.cand_min_gap = nk ? out.cand_min_gap.data() : nullptr;
+            o.best_min_gap = np ? out.min_gap.data() : nullptr;
+            out.dyn = ssf_navdyn_stats();
+            stats = &out.dyn;
+        }
+    };
+    struct DynDiscRollouts {
+        const int8_t* state; const MoverCall& mc;
+        DynDiscRollouts(const int8_t* s, const MoverCall& m) : state(s), mc(m) {}
+        int operator()(ssf_handle* h, const ssf_navsteer_params* p, const int32_t* dist2, const uint32_t* cost, const int32_t* poses, const int32_t* targets,
+                       const ssf_navsteer_out* o, ssf_navsteer_stats* st) const {
+            return ssf_navdyn_rollouts(h, p, &mc.dp, state, dist2, cost, poses, targets, mc.movers, o, &mc.o, st, mc.stats);
+        }
+    };
+    struct DynFootRollouts {
+        const uint32_t* mask; int n_headings; const MoverCall& mc;
+        DynFootRollouts(const uint32_t* m, int b, const MoverCall& c) : mask(m), n_headings(b), mc(c) {}
+        int operator()(ssf_handle* h, const ssf_navsteer_params* p, const int32_t* dist2, const uint32_t* cost, const int32_t* poses, const int32_t* targets,
+                       const ssf_navsteer_out* o, ssf_navsteer_stats* st) const {
+            return ssf_navdyn_foot_rollouts(h, p, &mc.dp, n_headings, mask, dist2, cost, poses, targets, mc.movers, o, &mc.o, st, mc.stats);
+        }
+    };
+    /* K and n_steps + 1 of a call, 1 each where the library refuses the lattice (its arrays only have to exist) */
+    static void steer_sizes(const SteerParams& q, size_t np, size_t& K, size_t& T1) {
+        const bool fits = q.n_v >= 1 && q.n_v <= 256 && q.n_w >= 1 && q.n_w <= 1024 && q.n_v * q.n_w <= 65536 && q.n_steps >= 1 && q.n_steps <= 256 &&
+                          np <= 4096 && np * (size_t)(q.n_v * q.n_w) <= ((size_t)1 << 24);
+        K = fits ? (size_t)(q.n_v * q.n_w) : 1; T1 = fits ? (size_t)q.n_steps + 1 : 1;
+    }
     /* the pose plan's entry point behind a functor of its own: only a program that calls planPoses references it */
     struct PoseField {
         int operator()(ssf_handle* h, const ssf_navpose_params* p, const uint32_t* mask, const int32_t* dist2, const ssf_navpose_out* o,
@@ -1319,9 +1463,8 @@ private:
         p.min_free_steps = q.min_free_steps; p.brake_div = q.brake_div; p.cost_weight = q.cost_weight; p.target_weight = q.target_weight;
         p.clear_weight = q.clear_weight; p.speed_weight = q.speed_weight; p.turn_weight = q.turn_weight; p.on_device = 0;
         const size_t np = poses.size();
-        const bool fits = q.n_v >= 1 && q.n_v <= 256 && q.n_w >= 1 && q.n_w <= 1024 && q.n_v * q.n_w <= 65536 && q.n_steps >= 1 && q.n_steps <= 256 &&
-                          np <= 4096 && np * (size_t)(q.n_v * q.n_w) <= ((size_t)1 << 24);
-        const size_t K = fits ? (size_t)(q.n_v * q.n_w) : 1, T1 = fits ? (size_t)q.n_steps + 1 : 1;
+        size_t K, T1;
+        steer_sizes(q, np, K, T1);
         std::vector<int32_t> cmd(np * 2, 0), len(np, 0), traj(q.want_traj ? np * T1 * 3 : 0);
         out.n_steps = q.n_steps; out.candidates = (int)K;
         out.best.assign(np, -1); out.n_admissible.assign(np, 0); out.status.assign(np, 0); out.score.assign(np, -1);

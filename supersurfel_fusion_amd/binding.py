@@ -38,6 +38,9 @@ FOOT_LIB = os.path.join(_HERE, "csrc", "libssf_hip_foot.so")
 # foot's objects and the plan over (x, y, heading) (include/ssf_navpose.h): the one library of a robot whose global plan knows its
 # body as well.  None of the eight libraries above exports the pose plan's entry points
 POSE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_pose.so")
+# pose's objects and steering among movers (include/ssf_navdyn.h): the one library of a robot that also drives among people.  None
+# of the nine libraries above exports the movers' entry points
+DYN_LIB = os.path.join(_HERE, "csrc", "libssf_hip_dyn.so")
 
 
 class SsfConfig(C.Structure):
@@ -170,6 +173,15 @@ NAVFOOT_HEADINGS = (1, 2, 4, 8, 16, 32)
 NAVPOSE_SYMBOLS = ["ssf_navpose_moves", "ssf_navpose_default_params", "ssf_navpose_field"]
 NAVPOSE_OUTPUT_NAMES = ("cost", "cell_cost", "cell_bin", "start_cost", "start_status", "path_len", "path")
 NAVPOSE_UNREACHED, NAVPOSE_NO_BIN, NAVPOSE_TILE, NAVPOSE_ROUND_BATCH, NAVPOSE_MAX_STATES = 0xFFFFFFFF, 255, 16, 16, 1 << 26
+# steering among movers (include/ssf_navdyn.h): exported by libssf_hip_dyn.so only (load_dyn)
+NAVDYN_SYMBOLS = ["ssf_navdyn_default_params", "ssf_navdyn_rollouts", "ssf_navdyn_foot_rollouts", "ssf_navdyn_default_blob_params",
+                  "ssf_navdyn_blobs"]
+# the arrays of ssf_navdyn_out, as NAVSTEER_OUTPUTS
+NAVDYN_OUTPUTS = (("cand_hit", np.int32, "cand", ()), ("cand_min_gap", np.int32, "cand", ()), ("best_min_gap", np.int32, "pose", ()))
+NAVDYN_OUTPUT_NAMES = tuple(o[0] for o in NAVDYN_OUTPUTS)
+NAVDYN_MAX_MOVERS, NAVDYN_MOVER_WORDS, NAVDYN_MAX_BLOBS, NAVDYN_BLOB_WORDS = 64, 6, 64, 8
+# the bounds of a mover (x, y, vx, vy, r, grow): |x|, |y|; |vx|, |vy|; r; grow
+NAVDYN_MAX_XY, NAVDYN_MAX_V, NAVDYN_MAX_R, NAVDYN_MAX_GROW = 1 << 24, 4096, 1 << 20, 4096
 # rays cast through the model (include/ssf_raycast.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 RAYCAST_SYMBOLS = ["ssf_raycast_default_params", "ssf_raycast"]
 # the output arrays of ssf_raycast, in its argument order: name, dtype, per-ray shape
@@ -433,6 +445,40 @@ class SsfNavSteerStats(C.Structure):
         return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
 
 
+class SsfNavDynParams(C.Structure):
+    """ssf_navdyn_params (include/ssf_navdyn.h)"""
+    _fields_ = [(nm, C.c_int) for nm in ("n_movers", "mover_cap", "mover_weight")]
+
+
+class SsfNavDynOut(C.Structure):
+    """ssf_navdyn_out (include/ssf_navdyn.h)"""
+    _fields_ = [(nm, C.c_void_p) for nm in NAVDYN_OUTPUT_NAMES]
+
+
+class SsfNavDynStats(C.Structure):
+    """ssf_navdyn_stats (include/ssf_navdyn.h)"""
+    _fields_ = [("hit_movers", C.c_int64)]
+
+    def as_dict(self):
+        return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
+
+
+class SsfNavDynBlobParams(C.Structure):
+    """ssf_navdyn_blob_params (include/ssf_navdyn.h)"""
+    _fields_ = [("grid_pose", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("res", C.c_float), ("floor_max", C.c_float),
+                ("z_max", C.c_float), ("cam_pose", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("cam_width", C.c_int), ("cam_height", C.c_int), ("t_min", C.c_float), ("t_max", C.c_float), ("min_points", C.c_int),
+                ("max_blobs", C.c_int), ("direct", C.c_int), ("on_device", C.c_int), ("frame_on_device", C.c_int)]
+
+
+class SsfNavDynBlobStats(C.Structure):
+    """ssf_navdyn_blob_stats (include/ssf_navdyn.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("pixels_member", "pixels_valid", "points_in_band", "labels_seen", "blobs_kept", "blobs_written")]
+
+    def as_dict(self):
+        return {nm: int(getattr(self, nm)) for nm, _ in self._fields_}
+
+
 class SsfNavPoseParams(C.Structure):
     """ssf_navpose_params (include/ssf_navpose.h)"""
     _fields_ = [(nm, C.c_int) for nm in ("width", "height", "n_headings", "min_dist2", "soft_dist2", "near_penalty", "move_tol", "allow_reverse",
@@ -680,6 +726,15 @@ class Library:
             L.ssf_navpose_moves.argtypes = [C.c_int, C.c_int, C.c_int, vp]
             L.ssf_navpose_default_params.argtypes = [vp, C.POINTER(SsfNavPoseParams)]
             L.ssf_navpose_field.argtypes = [vp, C.POINTER(SsfNavPoseParams), vp, vp, C.POINTER(SsfNavPoseOut), C.POINTER(SsfNavPoseStats)]
+        self.has_navdyn = all(hasattr(L, nm) for nm in NAVDYN_SYMBOLS)
+        if self.has_navdyn:
+            sp, dp = C.POINTER(SsfNavSteerParams), C.POINTER(SsfNavDynParams)
+            tail = [C.POINTER(SsfNavSteerOut), C.POINTER(SsfNavDynOut), C.POINTER(SsfNavSteerStats), C.POINTER(SsfNavDynStats)]
+            L.ssf_navdyn_default_params.argtypes = [vp, dp]
+            L.ssf_navdyn_rollouts.argtypes = [vp, sp, dp, vp, vp, vp, vp, vp, vp] + tail
+            L.ssf_navdyn_foot_rollouts.argtypes = [vp, sp, dp, C.c_int, vp, vp, vp, vp, vp, vp] + tail
+            L.ssf_navdyn_default_blob_params.argtypes = [vp, C.POINTER(SsfNavDynBlobParams)]
+            L.ssf_navdyn_blobs.argtypes = [vp, C.POINTER(SsfNavDynBlobParams), vp, vp, vp, vp, C.POINTER(SsfNavDynBlobStats)]
         self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
         if self.has_navgrid:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
@@ -883,6 +938,59 @@ def navpose_moves(n_headings, move_tol, allow_reverse, library=None):
         raise SsfError("ssf_navpose_moves refused its arguments (%d): n_headings one of %s, move_tol 0..256, allow_reverse 0 or 1"
                        % (rc, NAVFOOT_HEADINGS))
     return out
+
+
+def load_dyn():
+    """Load libssf_hip_dyn.so: pose's objects (the product and every navigation call up to the plan over headings) with steering among
+    movers linked in (include/ssf_navdyn.h).  A handle belongs to the library that created it: create the Fusion from THIS library to
+    call nav_dyn_steer, nav_dyn_blobs or nav_live_dyn_steer on it.  Fails loudly when it has not been built."""
+    import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
+    return Library(DYN_LIB)
+
+
+class MoverTracker:
+    """From two successive blob tables (nav_dyn_blobs) to the movers of nav_dyn_steer: host only, integer only, the rule of
+    include/ssf_navdyn.h part C (ssf.hpp's supersurfel_fusion::MoverTracker states the same).  gate: the largest centre distance of a match,
+    sub-units; inflate: added to every radius (the robot's own radius goes here); grow: the growth of a matched mover, sub-units per
+    step; grow_unmatched: that of a blob with no predecessor, whose velocity is unknown and taken as 0."""
+
+    def __init__(self, gate=2048, inflate=0, grow=16, grow_unmatched=128):
+        self.gate, self.inflate, self.grow, self.grow_unmatched = int(gate), int(inflate), int(grow), int(grow_unmatched)
+        self.prev = np.zeros((0, NAVDYN_BLOB_WORDS), np.int32)
+
+    def reset(self):
+        self.prev = np.zeros((0, NAVDYN_BLOB_WORDS), np.int32)
+
+    def update(self, blobs, steps_since=1):
+        """blobs: n x 8 int32 rows (label, n, cx, cy, r, ex, ey, 0), n <= 64; steps_since >= 1: the rollout steps between the previous
+        table and this one.  Returns n x 6 int32 (x, y, vx, vy, r, grow), every field clamped to the call's bounds."""
+        blobs = np.ascontiguousarray(blobs, np.int32).reshape(-1, NAVDYN_BLOB_WORDS)
+        steps = int(steps_since)
+        if steps < 1 or blobs.shape[0] > NAVDYN_MAX_BLOBS:
+            raise SsfError("MoverTracker.update takes at most %d blobs and steps_since >= 1" % NAVDYN_MAX_BLOBS)
+        clamp = lambda v, lo, hi: lo if v < lo else (hi if v > hi else v)
+        used = [False] * self.prev.shape[0]
+        out = np.zeros((blobs.shape[0], NAVDYN_MOVER_WORDS), np.int32)
+        for i in range(blobs.shape[0]):
+            cx, cy, r = int(blobs[i, 2]), int(blobs[i, 3]), int(blobs[i, 4])
+            best = None
+            for j in range(self.prev.shape[0]):
+                if used[j]:
+                    continue
+                d2 = (cx - int(self.prev[j, 2])) ** 2 + (cy - int(self.prev[j, 3])) ** 2
+                if d2 <= self.gate * self.gate and (best is None or d2 < best[0]):      # (j grows: the smaller index wins a tie)
+                    best = (d2, j)
+            vx = vy = 0
+            grow = self.grow_unmatched
+            if best is not None:
+                j = best[1]
+                used[j] = True
+                vx, vy = (cx - int(self.prev[j, 2])) // steps, (cy - int(self.prev[j, 3])) // steps       # (floor)
+                grow = self.grow
+            out[i] = (clamp(cx, -NAVDYN_MAX_XY, NAVDYN_MAX_XY), clamp(cy, -NAVDYN_MAX_XY, NAVDYN_MAX_XY), clamp(vx, -NAVDYN_MAX_V, NAVDYN_MAX_V),
+                      clamp(vy, -NAVDYN_MAX_V, NAVDYN_MAX_V), clamp(r + self.inflate, 0, NAVDYN_MAX_R), clamp(grow, 0, NAVDYN_MAX_GROW))
+        self.prev = blobs.copy()
+        return out
 
 
 def load_lab():
@@ -2592,6 +2700,226 @@ class Fusion:
         if keep_cost:
             res["pose"]["cell_cost"] = d_cost.cpu().numpy().view(np.uint32)
         return res
+
+    # ---- steering among movers: rollouts tested against predicted movers, blobs of the moving pixels (include/ssf_navdyn.h) ----
+    def _need_navdyn(self, symbol):
+        if not self.L.has_navdyn:
+            raise SsfError("%s does not export %s: it sees no movers (include/ssf_navdyn.h: libssf_hip_dyn.so, binding.load_dyn)"
+                           % (self.L.path, symbol))
+
+    def _navdyn_params(self, n_movers, params):
+        """(SsfNavDynParams, the rest of `params`): mover_cap and mover_weight taken out of a steering call's keywords, each at
+        ssf_navdyn_default_params' value when missing"""
+        dp = SsfNavDynParams()
+        self._ck(self.L.lib.ssf_navdyn_default_params(self.h, C.byref(dp)), "ssf_navdyn_default_params")
+        rest = dict(params)
+        for nm in ("mover_cap", "mover_weight"):
+            if nm in rest:
+                setattr(dp, nm, int(rest.pop(nm)))
+        dp.n_movers = int(n_movers)
+        return dp, rest
+
+    def _navdyn_rollouts(self, p, dp, grid, dist2, cost, poses, targets, movers, ptrs, n_headings=None):
+        """the disc's rollouts among movers over `grid` = state, or with n_headings the footprint's over the mask given in its place"""
+        st, dst = SsfNavSteerStats(), SsfNavDynStats()
+        out = SsfNavSteerOut(*[ptrs.get(nm) for nm in NAVSTEER_OUTPUT_NAMES])
+        dout = SsfNavDynOut(*[ptrs.get(nm) for nm in NAVDYN_OUTPUT_NAMES])
+        if n_headings is None:
+            self._ck(self.L.lib.ssf_navdyn_rollouts(self.h, C.byref(p), C.byref(dp), grid, dist2, cost, poses, targets, movers, C.byref(out),
+                                                    C.byref(dout), C.byref(st), C.byref(dst)), "ssf_navdyn_rollouts")
+        else:
+            self._ck(self.L.lib.ssf_navdyn_foot_rollouts(self.h, C.byref(p), C.byref(dp), int(n_headings), grid, dist2, cost, poses, targets, movers,
+                                                         C.byref(out), C.byref(dout), C.byref(st), C.byref(dst)), "ssf_navdyn_foot_rollouts")
+        return dict(st.as_dict(), **dst.as_dict())
+
+    def _nav_dyn_steer_host(self, grid, grid_dtype, grid_name, n_headings, dist2, poses, movers, cost, targets, outputs, params):
+        known = NAVSTEER_OUTPUTS + NAVDYN_OUTPUTS
+        bad = [nm for nm in outputs if nm not in [o[0] for o in known]]
+        if bad:
+            raise SsfError("unknown steering outputs %s (known: %s)" % (bad, ", ".join(o[0] for o in known)))
+        grid, dist2 = np.ascontiguousarray(grid, grid_dtype), np.ascontiguousarray(dist2, np.int32)
+        if grid.ndim != 2 or dist2.shape != grid.shape:
+            raise SsfError("%s and dist2 are H x W arrays of one shape, got %s and %s" % (grid_name, grid.shape, dist2.shape))
+        H, W = grid.shape
+        poses = np.ascontiguousarray(poses, np.int32)
+        if poses.ndim != 2 or poses.shape[1] != 3:
+            raise SsfError("poses are n x 3 (x, y, heading) in units, got shape %s" % (poses.shape,))
+        n = poses.shape[0]
+        if cost is not None:
+            cost = np.ascontiguousarray(cost, np.uint32)
+            if cost.shape != grid.shape:
+                raise SsfError("cost is an H x W array like %s, got %s" % (grid_name, cost.shape))
+        if targets is not None:
+            targets = np.ascontiguousarray(targets, np.int32)
+            if targets.shape != (n, 2):
+                raise SsfError("targets are n x 2 (x, y) in units, one per pose, got shape %s" % (targets.shape,))
+        movers = np.zeros((0, NAVDYN_MOVER_WORDS), np.int32) if movers is None else np.ascontiguousarray(movers, np.int32)
+        if movers.ndim != 2 or movers.shape[1] != NAVDYN_MOVER_WORDS:
+            raise SsfError("movers are m x 6 (x, y, vx, vy, r, grow) in units, got shape %s" % (movers.shape,))
+        dp, rest = self._navdyn_params(movers.shape[0], params)
+        p = self._navsteer_params(False, W, H, n, rest)
+        K, T = max(p.n_v, 0) * max(p.n_w, 0), max(p.n_steps, 0)
+        if not (0 < K <= 65536 and T <= 256 and n * K <= 1 << 24):
+            K = T = 1                                # (the call refuses it: the arrays only have to exist)
+        want = set(outputs)
+        if "best_traj" in want:
+            want.add("best_len")                     # (the counts cut the lists)
+        out = {nm: np.zeros(self._navsteer_shape(kind, tail, n, K, T), dt) for nm, dt, kind, tail in known if nm in want}
+        stats = self._navdyn_rollouts(p, dp, _ptr(grid), _ptr(dist2), _ptr(cost), _ptr(poses), _ptr(targets),
+                                      _ptr(movers) if movers.shape[0] else None, {nm: _ptr(a) for nm, a in out.items()}, n_headings)
+        if "best_traj" in out:
+            out["best_traj"] = [out["best_traj"][i, :out["best_len"][i]].copy() for i in range(n)]
+        if "best_len" not in outputs:
+            out.pop("best_len", None)
+        out["stats"] = stats
+        return out
+
+    def nav_dyn_steer(self, state, dist2, poses, movers=None, cost=None, targets=None, outputs=NAVSTEER_POSE_OUTPUTS + ("best_min_gap",), **params):
+        """nav_steer among predicted movers (ssf_navdyn_rollouts), host arrays: movers m x 6 int32 (x, y, vx, vy, r, grow) in sub-units
+        and sub-units per step (MoverTracker.update makes them; None or empty: none), one list for all poses.  A step is refused where
+        it lies inside a mover's disc of that step, and the score gains mover_weight * the lack of gap below mover_cap.  Outputs:
+        nav_steer's and cand_hit, cand_min_gap, best_min_gap; 'stats' gains hit_movers.  params: the fields of ssf_navsteer_params
+        and mover_cap, mover_weight by name."""
+        self._need_navdyn("ssf_navdyn_rollouts")
+        return self._nav_dyn_steer_host(state, np.int8, "state", None, dist2, poses, movers, cost, targets, outputs, params)
+
+    def nav_dyn_foot_steer(self, free_mask, dist2, poses, n_headings, movers=None, cost=None, targets=None,
+                           outputs=NAVSTEER_POSE_OUTPUTS + ("best_min_gap",), **params):
+        """nav_foot_steer among predicted movers (ssf_navdyn_foot_rollouts), host arrays: nav_dyn_steer with the oriented footprint's
+        mask in the place of state.  A mover's r carries the footprint's circumscribed radius."""
+        self._need_navdyn("ssf_navdyn_foot_rollouts")
+        return self._nav_dyn_steer_host(free_mask, np.uint32, "free_mask", n_headings, dist2, poses, movers, cost, targets, outputs, params)
+
+    def nav_dyn_steer_device(self, state, dist2, width, height, poses, n_poses, movers=None, n_movers=0, n_headings=None, cost=None, targets=None,
+                             best=None, best_cmd=None, best_score=None, n_admissible=None, pose_status=None, best_len=None, best_traj=None,
+                             cand_free=None, cand_min_d=None, cand_end=None, cand_end_cost=None, cand_score=None, cand_hit=None, cand_min_gap=None,
+                             best_min_gap=None, **params):
+        """ssf_navdyn_rollouts (with n_headings: ssf_navdyn_foot_rollouts, `state` then the footprint's mask) on device memory, as
+        nav_steer_device: movers is a device tensor or address of n_movers x 6 int32, whose values the library does not check.
+        Returns the stats dict."""
+        self._need_navdyn("ssf_navdyn_rollouts")
+        dp, rest = self._navdyn_params(n_movers, params)
+        p = self._navsteer_params(True, width, height, n_poses, rest)
+        addr = self._dev_addr
+        return self._navdyn_rollouts(p, dp, addr(state), addr(dist2), addr(cost), addr(poses), addr(targets), addr(movers),
+                                     dict(best=addr(best), best_cmd=addr(best_cmd), best_score=addr(best_score), n_admissible=addr(n_admissible),
+                                          pose_status=addr(pose_status), best_len=addr(best_len), best_traj=addr(best_traj), cand_free=addr(cand_free),
+                                          cand_min_d=addr(cand_min_d), cand_end=addr(cand_end), cand_end_cost=addr(cand_end_cost),
+                                          cand_score=addr(cand_score), cand_hit=addr(cand_hit), cand_min_gap=addr(cand_min_gap),
+                                          best_min_gap=addr(best_min_gap)), n_headings)
+
+    def nav_dyn_default_params(self):
+        """ssf_navdyn_default_params and ssf_navdyn_default_blob_params as one dict: 'steer' and 'blobs'"""
+        self._need_navdyn("ssf_navdyn_default_params")
+        dp, bp = SsfNavDynParams(), SsfNavDynBlobParams()
+        self._ck(self.L.lib.ssf_navdyn_default_params(self.h, C.byref(dp)), "ssf_navdyn_default_params")
+        self._ck(self.L.lib.ssf_navdyn_default_blob_params(self.h, C.byref(bp)), "ssf_navdyn_default_blob_params")
+        return dict(steer={nm: getattr(dp, nm) for nm, _ in dp._fields_},
+                    blobs={nm: getattr(bp, nm) for nm, _ in bp._fields_ if nm not in ("grid_pose", "cam_pose")})
+
+    def _navdyn_blob_params(self, on_device, frame_on_device, grid_pose=None, cam_pose=None, **kw):
+        """(SsfNavDynBlobParams, the pose arrays it points into), as _navlive_params"""
+        p = SsfNavDynBlobParams()
+        self._ck(self.L.lib.ssf_navdyn_default_blob_params(self.h, C.byref(p)), "ssf_navdyn_default_blob_params")
+        keep = []
+        for nm, pose in (("grid_pose", grid_pose), ("cam_pose", cam_pose)):
+            if pose is not None:
+                keep.append(self._pose12(pose, nm))
+                setattr(p, nm, keep[-1].ctypes.data)
+        kinds = dict(p._fields_)
+        for nm, val in kw.items():
+            if nm not in kinds or nm in ("grid_pose", "cam_pose", "on_device", "frame_on_device"):
+                raise SsfError("unknown blob parameter %r" % nm)
+            setattr(p, nm, float(val) if kinds[nm] is C.c_float else int(val))
+        p.on_device, p.frame_on_device = int(bool(on_device)), int(bool(frame_on_device))
+        return p, keep
+
+    def nav_dyn_blobs(self, depth, mask, label, **kw):
+        """The moving pixels of a depth frame as blobs in the grid frame (ssf_navdyn_blobs), host arrays: depth in the handle's input
+        format, mask uint8 and label int32 as motion_mask returns them, all of the camera's size.  Returns dict(blobs: k x 8 int32 rows
+        (label, n, cx, cy, r, ex, ey, 0) in sub-units, ordered by (-n, label), k = stats['blobs_written']; stats).  Keywords: the
+        fields of ssf_navdyn_blob_params by name, grid_pose and cam_pose as nav_live."""
+        self._need_navdyn("ssf_navdyn_blobs")
+        p, keep = self._navdyn_blob_params(False, False, **kw)
+        cw, ch = (p.cam_width, p.cam_height) if p.cam_width else (self.W, self.H)
+        depth = np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32)
+        mask, label = np.ascontiguousarray(mask, np.uint8), np.ascontiguousarray(label, np.int32)
+        for nm, a in (("depth", depth), ("mask", mask), ("label", label)):
+            if a.shape != (ch, cw):
+                raise SsfError("%s is a %d x %d image, got shape %s" % (nm, ch, cw, a.shape))
+        blobs = np.zeros((NAVDYN_MAX_BLOBS, NAVDYN_BLOB_WORDS), np.int32)
+        st = SsfNavDynBlobStats()
+        self._ck(self.L.lib.ssf_navdyn_blobs(self.h, C.byref(p), _ptr(depth), _ptr(mask), _ptr(label), _ptr(blobs), C.byref(st)), "ssf_navdyn_blobs")
+        stats = st.as_dict()
+        return dict(blobs=blobs[:stats["blobs_written"]].copy(), stats=stats)
+
+    def nav_dyn_blobs_device(self, depth, mask, label, blobs=None, **kw):
+        """ssf_navdyn_blobs on device images: depth, mask and label are device tensors or addresses (motion_mask_device's outputs are
+        read where they lie).  blobs: None (the table comes back as nav_dyn_blobs returns it) or a device tensor or address of
+        64 x 8 int32, written on the device.  Returns dict(blobs (None when written on the device), stats)."""
+        self._need_navdyn("ssf_navdyn_blobs")
+        p, keep = self._navdyn_blob_params(blobs is not None, True, **kw)
+        host = np.zeros((NAVDYN_MAX_BLOBS, NAVDYN_BLOB_WORDS), np.int32) if blobs is None else None
+        st = SsfNavDynBlobStats()
+        self._ck(self.L.lib.ssf_navdyn_blobs(self.h, C.byref(p), self._dev_addr(depth), self._dev_addr(mask), self._dev_addr(label),
+                                             _ptr(host) if blobs is None else self._dev_addr(blobs), C.byref(st)), "ssf_navdyn_blobs")
+        stats = st.as_dict()
+        return dict(blobs=None if host is None else host[:stats["blobs_written"]].copy(), stats=stats)
+
+    def nav_live_dyn_steer(self, depth, state, goals, poses, tracker, steps_since=1, targets=None, motion=None, live=None, blobs=None, plan=None,
+                           steer=None):
+        """Motion mask, overlay, blobs, tracker, plan and rollouts among the movers, with nothing but the blob table and the command
+        leaving the device: nav_live_steer with the moving pixels taken OUT of the overlay (mask_mode 2: a mover is not stamped as a
+        wall where it stands now) and handed to the rollouts as predicted discs instead.  depth: host array in the input format or a
+        device tensor; tracker: a MoverTracker, which keeps the blob table from call to call; steps_since: the rollout steps since
+        the previous call; motion: motion_mask's params; live, blobs, plan, steer: the four calls' keywords (blobs' grid and camera
+        default to live's; steer's min_dist2 and allow_unknown to the plan's).  Returns a dict: 'motion', 'live', 'plan' (stats),
+        'blobs' (the table and stats), 'movers' (m x 6) and 'steer' (the per-pose outputs as nav_dyn_steer returns them, and stats)."""
+        import torch
+        self._need_navlive("ssf_navlive_overlay")
+        self._need_navplan("ssf_navplan_field")
+        self._need_navdyn("ssf_navdyn_rollouts")
+        live, bq, plan, sq = dict(live or {}), dict(blobs or {}), dict(plan or {}), dict(steer or {})
+        state = np.ascontiguousarray(state, np.int8)
+        if state.ndim != 2:
+            raise SsfError("state is a height x width array, got shape %s" % (state.shape,))
+        H, W = state.shape
+        poses = np.ascontiguousarray(poses, np.int32)
+        if poses.ndim != 2 or poses.shape[1] != 3 or poses.shape[0] < 1:
+            raise SsfError("poses are n x 3 (x, y, heading) in units, n >= 1, got shape %s" % (poses.shape,))
+        n = poses.shape[0]
+        dev = torch.device("cuda")
+        if not isinstance(depth, torch.Tensor):
+            depth = torch.from_numpy(np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32).view(
+                np.int16 if self.depth_format == "u16" else np.float32)).to(dev)
+        d_mask = torch.empty((self.H, self.W), dtype=torch.uint8, device=dev)
+        d_label = torch.empty((self.H, self.W), dtype=torch.int32, device=dev)
+        motion_stats = self.motion_mask_device(depth, mask=d_mask, label=d_label, params=motion)
+        d_state = torch.from_numpy(state).to(dev)
+        d_dist2 = torch.empty((H, W), dtype=torch.int32, device=dev)
+        d_cost = torch.empty((H, W), dtype=torch.int32, device=dev)       # (uint32 words)
+        live_stats = self.nav_live_device(depth, d_state, W, H, mask=d_mask, state_out=d_state, dist2=d_dist2, **dict(live, mask_mode=2))
+        for nm in ("grid_pose", "cam_pose", "res", "floor_max", "z_max", "fx", "fy", "cx", "cy", "cam_width", "cam_height", "t_min", "t_max"):
+            if nm in live:
+                bq.setdefault(nm, live[nm])
+        table = self.nav_dyn_blobs_device(depth, d_mask, d_label, width=W, height=H, **bq)
+        movers = tracker.update(table["blobs"], steps_since)
+        plan_stats = self.nav_plan_device(d_state, d_dist2, W, H, goals, None, cost=d_cost, **plan)
+        for nm in ("min_dist2", "allow_unknown"):
+            sq.setdefault(nm, plan.get(nm, 0))
+        _, rest = self._navdyn_params(0, sq)
+        T = min(max(self._navsteer_params(True, W, H, n, rest).n_steps, 0), 256)
+        d_poses = torch.from_numpy(poses).to(dev)
+        d_targets = None if targets is None else torch.from_numpy(np.ascontiguousarray(targets, np.int32)).to(dev)
+        d_movers = torch.from_numpy(movers).to(dev) if movers.shape[0] else None
+        o = {nm: torch.zeros(self._navsteer_shape(kind, tail, n, 1, T), dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
+             for nm, dt, kind, tail in NAVSTEER_OUTPUTS + NAVDYN_OUTPUTS if kind == "pose"}
+        steer_stats = self.nav_dyn_steer_device(d_state, d_dist2, W, H, d_poses, n, movers=d_movers, n_movers=movers.shape[0], cost=d_cost,
+                                                targets=d_targets, **dict(o, **sq))
+        got = {nm: a.cpu().numpy() for nm, a in o.items()}
+        got["best_traj"] = [got["best_traj"][i, :got["best_len"][i]].copy() for i in range(n)]
+        got["stats"] = steer_stats
+        return dict(motion=dict(stats=motion_stats), live=dict(stats=live_stats), plan=dict(stats=plan_stats), blobs=table, movers=movers, steer=got)
 
     # ---- rays cast through the model: the first disc each ray hits (include/ssf_raycast.h) ------------
     def _need_raycast(self, symbol):

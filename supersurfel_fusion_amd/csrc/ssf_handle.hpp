@@ -398,6 +398,16 @@ struct NavSteerWs {
     bool dirs_sent = false;                       // the table's upload has been enqueued (a call may fail between allocation and upload)
     unsigned char* io = nullptr; size_t io_bytes = 0;
 };
+// ssf_navdyn_blobs (ssf_navdyn.h, ssf_navdyn.hip: linked into libssf_hip_dyn.so only): per pixel the point (bx, by) of a contributing
+// pixel and, per label value, its compact slot (12 bytes a pixel); the per-label records (40 bytes, one per pixel at the most); the
+// sums; the staging buffer of host images.  The rollouts with movers use NavSteerWs and NavFootWs.  Allocated on first use; each
+// group is grown as a whole or not at all (DevBufs::grow).  Nothing here is read or written by the frame path.
+struct NavDynWs {
+    DevBufs bufs;
+    int2* pt = nullptr; int32_t* slot = nullptr; unsigned char* rec = nullptr; size_t pixels = 0;
+    unsigned long long* stats = nullptr;
+    unsigned char* img = nullptr; size_t img_bytes = 0;
+};
 // ssf_navfoot_layers and ssf_navfoot_rollouts (ssf_navfoot.h, ssf_navfoot.hip: linked into libssf_hip_foot.so only): the footprint's
 // table of spans as the layers kernel reads it (kept from call to call while the footprint is the same), the layers' sums and the staging buffer of a layers call with host arrays; per cell
 // the rollouts' packed (heading mask, d) word of 8 bytes.  The rollouts' keys, counts, direction table, sums and staging are
@@ -561,6 +571,7 @@ struct ssf_handle {
     NavSteerWs navsteer;                          // ssf_navsteer_rollouts (ssf_navsteer.h)
     NavFootWs navfoot;                            // ssf_navfoot_layers, ssf_navfoot_rollouts (ssf_navfoot.h)
     NavPoseWs navpose;                            // ssf_navpose_field (ssf_navpose.h)
+    NavDynWs navdyn;                              // ssf_navdyn_blobs (ssf_navdyn.h)
     RaycastWs raycast;                            // ssf_raycast (ssf_raycast.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense); the out-of-view
                                                   // compaction keeps rows and order but moves slots: who keeps slot numbers also watches n_recentres (RaycastWs)

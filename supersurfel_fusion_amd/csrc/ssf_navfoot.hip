@@ -103,29 +103,8 @@ __global__ __launch_bounds__(256) void k_navfoot_pack(size_t P, int min_dist2, i
                                                       uint2* __restrict__ pk) {
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
-    const int d = dist2[p];
-    const int dd = d < 0 ? 0 : (d > cap ? cap : d);
-    pk[p] = make_uint2(d >= min_dist2 ? mask[p] : 0u, (uint32_t)dd);
+    pk[p] = ns_foot_word(mask, dist2, p, min_dist2, cap);
 }
-
-// the footprint's cell test (step 3): the packed (mask, d) word in the grid under the bins a step sweeps
-struct NavFootCells {
-    const uint2* pk; int W, B, shift;
-    __device__ __forceinline__ uint32_t bin_bit(int h) const { return 1u << (((h + (1 << (shift - 1))) >> shift) & (B - 1)); }
-    __device__ __forceinline__ uint32_t need(int h, int w) const {
-        const int a = h + (1 << (shift - 1)), b = a + w;
-        const int lo = (a < b ? a : b) >> shift, hi = (a < b ? b : a) >> shift, n = hi - lo + 1;
-        const uint32_t all = B == 32 ? 0xFFFFFFFFu : (1u << B) - 1u;
-        if (n >= B) return all;
-        const unsigned long long run = ((1ull << n) - 1ull) << (lo & (B - 1));       // n < B <= 32 bits from a bin below B: below 2^63
-        return (uint32_t)(run | (run >> B)) & all;
-    }
-    __device__ __forceinline__ bool free(int ix, int iy, uint32_t need, int& d) const {
-        const uint2 u = pk[(size_t)iy * W + ix];
-        d = (int)u.y;
-        return (u.x & need) == need;
-    }
-};
 
 // ---- roll: one workgroup per (pose, 256 candidates) ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_navfoot_roll(NavSteerRule r, int B, int shift, const uint2* __restrict__ pk, const uint32_t* __restrict__ cost,
@@ -133,17 +112,7 @@ __global__ __launch_bounds__(256) void k_navfoot_roll(NavSteerRule r, int B, int
                                                       const uint32_t* __restrict__ dirs, unsigned long long* __restrict__ keys,
                                                       int32_t* __restrict__ n_adm, NavSteerCand out, unsigned long long* __restrict__ stats) {
     __shared__ uint32_t s_dir[NS_DIRS];                               // (S << 16) | (C & 0xFFFF)
-    const int t = threadIdx.x, pose = blockIdx.y;
-    const int px = poses[3 * (size_t)pose], py = poses[3 * (size_t)pose + 1], ph = poses[3 * (size_t)pose + 2] & 0xFFFF;
-    const int cx0 = px >> 10, cy0 = py >> 10;
-    const NavFootCells cells{pk, r.W, B, shift};
-    const bool inside = cx0 >= 0 && cx0 < r.W && cy0 >= 0 && cy0 < r.H;
-    const uint2 start = inside ? pk[(size_t)cy0 * r.W + cx0] : make_uint2(0u, 0u);
-    const bool start_ok = (start.x & cells.bin_bit(ph)) != 0;          // (the same for every thread)
-    if (start_ok)
-        for (int k = t; k < NS_DIRS; k += 256) s_dir[k] = dirs[k];
-    __syncthreads();
-    ns_roll_body(r, cells, start_ok, (int)start.y, false, px, py, ph, cx0, cy0, s_dir, cost, targets, keys, n_adm, out, stats);
+    ns_foot_roll(r, NsNoHook{}, s_dir, B, shift, pk, cost, poses, targets, dirs, keys, n_adm, out, stats);
 }
 
 // ---- pick: one lane per pose ----------------------------------------------------------------------------------------------------------
@@ -151,7 +120,7 @@ __global__ __launch_bounds__(256) void k_navfoot_pick(NavSteerRule r, int B, int
                                                       const uint32_t* __restrict__ dirs, const unsigned long long* __restrict__ keys,
                                                       const int32_t* __restrict__ n_adm, NavSteerPose out, unsigned long long* __restrict__ stats) {
     const NavFootCells cells{pk, r.W, B, shift};
-    ns_pick_body(r, cells, [&](int cx, int cy, int h) { return (pk[(size_t)cy * r.W + cx].x & cells.bin_bit(h)) != 0; }, poses, dirs, keys, n_adm, out,
+    ns_pick_body(r, cells, NsNoHook{}, [&](int cx, int cy, int h) { return (pk[(size_t)cy * r.W + cx].x & cells.bin_bit(h)) != 0; }, poses, dirs, keys, n_adm, out,
                  stats);
 }
 
@@ -159,12 +128,6 @@ __global__ __launch_bounds__(256) void k_navfoot_pick(NavSteerRule r, int B, int
 
 namespace {
 using namespace ssf;
-
-int navfoot_log2(int B) {
-    for (int k = 0; k <= 5; k++)
-        if (B == 1 << k) return k;
-    return -1;
-}
 
 // step 1: what the header's inequalities cover; lo[b][dy + 40], hi likewise, (1, 0) where empty.  nullptr: fine; else what is wrong
 struct NavFootSpans { int16_t lo[NF_BINS][NF_ROWS], hi[NF_BINS][NF_ROWS]; int reach; long long cells; };
@@ -203,13 +166,7 @@ const char* navfoot_spans(int front, int back, int left, int right, int pad, int
 struct NavFootRun {
     ssf_handle* h; int B, shift;
     int stage_cells(const NavSteerRule&) const { return 0; }
-    bool reserve(size_t P) {
-        NavFootWs& w = h->navfoot;
-        if (P <= w.pk_cells) return true;
-        if (!w.bufs.grow({{(void**)&w.pk, 8 * P}})) return false;
-        w.pk_cells = P;
-        return true;
-    }
+    bool reserve(size_t P) { return navfoot_reserve_pk(h, P); }
     int launch(hipStream_t st, const NavSteerRule& r, const void* mask, const int32_t* dist2, const uint32_t* cost, const int32_t* poses,
                const int32_t* targets, NavSteerWs& w, const NavSteerCand& cand, const NavSteerPose& pick) {
         const size_t P = (size_t)r.W * r.H;

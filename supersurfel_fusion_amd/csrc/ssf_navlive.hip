@@ -14,8 +14,7 @@
 //
 // This file is NOT one of the product library's objects, nor of the four older navigation libraries: it is linked with
 // libssf_hip_drive.so's objects into libssf_hip_live.so (csrc/Makefile), which is what a caller of the overlay loads.
-#include "ssf_navgrid.hpp"
-#include "../../include/ssf_input.h"
+#include "ssf_navlive.hpp"
 #include "../../include/ssf_navlive.h"
 
 namespace ssf {
@@ -26,23 +25,7 @@ enum { NL_VALID = 0, NL_STAMPING, NL_POINTS, NL_RAYS, NL_CARVING, NL_SAMPLES, NL
        NL_STATS = 12, NL_PAD = 16 };
 enum { NL_TW = 16, NL_TH = 16, NL_RUN = 16 };
 
-// the camera of the frame: pose (R row-major, t: camera-to-map), pinhole, image size, valid depths; the lattice of the rays
-struct NavLiveCam { float R[9], t[3]; float fx, fy, cx, cy; int W, H; float tmin, tmax; int stride, nu, nv; };
-
-template <int DF> __device__ __forceinline__ float navlive_load_depth(const void* __restrict__ p, size_t q, double scale) {
-    if (DF == SSF_DEPTH_U16_SCALED) return (float)((double)reinterpret_cast<const uint16_t*>(p)[q] * scale);
-    return reinterpret_cast<const float*>(p)[q];
-}
-// the cell in whose band the map-frame point S lies (ssf_navgrid.h steps 1 and 4, the band of step 5), or -1
-__device__ __forceinline__ int navlive_cell(const NavGrid& G, float Sx, float Sy, float Sz) {
-    const float dx = Sx - G.t[0], dy = Sy - G.t[1], dz = Sz - G.t[2];
-    const float* R = G.R;
-    const float Cx = (R[0] * dx + R[3] * dy) + R[6] * dz, Cy = (R[1] * dx + R[4] * dy) + R[7] * dz, z = (R[2] * dx + R[5] * dy) + R[8] * dz;
-    const float gx = Cx / G.res, gy = Cy / G.res;
-    if (!(gx >= 0.0f && gx < G.fW && gy >= 0.0f && gy < G.fH)) return -1;
-    if (!(z > G.floor_max && z <= G.zmax)) return -1;
-    return (int)gy * G.W + (int)gx;
-}
+// (the camera of the frame, the depth of a pixel and the cell of a point: ssf_navlive.hpp, shared with ssf_navdyn.hip)
 // four sums of a workgroup of 256 into stats[s0], .. stats[s3]: ALL threads call it
 __device__ __forceinline__ void navlive_block_sums(unsigned long long a, unsigned long long b, unsigned long long c, unsigned long long d,
                                                    unsigned long long (*red)[4], unsigned long long* __restrict__ stats, int s0, int s1, int s2, int s3) {
@@ -75,11 +58,9 @@ __global__ __launch_bounds__(256) void k_navlive_stamp(NavGrid G, NavLiveCam cam
         valid = isfinite(d) && d >= cam.tmin && d <= cam.tmax;
         stamping = valid && (mask_mode == 0 || (mask[p] != 0) == (mask_mode == 1));
         if (stamping) {
-            const float x = ((float)u - cam.cx) / cam.fx, y = ((float)v - cam.cy) / cam.fy;
-            const float px = x * d, py = y * d;
-            const float* R = cam.R;
-            c = navlive_cell(G, ((R[0] * px + R[1] * py) + R[2] * d) + cam.t[0], ((R[3] * px + R[4] * py) + R[5] * d) + cam.t[1],
-                             ((R[6] * px + R[7] * py) + R[8] * d) + cam.t[2]);
+            float Sx, Sy, Sz;
+            navlive_pixel_point(cam, u, v, d, Sx, Sy, Sz);
+            c = navlive_cell(G, Sx, Sy, Sz);
         }
     }
     s_cell[(t & (NL_TW - 1)) * (NL_TH + 1) + (t >> 4)] = c;
@@ -252,20 +233,13 @@ int ssf_navlive_overlay(ssf_handle* h, const ssf_navlive_params* p, const void* 
     if (std::isnan(p->floor_max) || std::isnan(p->z_max)) return refuse("floor_max or z_max is a NaN");
     // the camera and its lattice
     NavLiveCam cam{};
-    cam.fx = p->fx; cam.fy = p->fy; cam.cx = p->cx; cam.cy = p->cy; cam.W = p->cam_width; cam.H = p->cam_height;
-    if (cam.W == 0) { cam.fx = h->cfg.fx; cam.fy = h->cfg.fy; cam.cx = h->cfg.cx; cam.cy = h->cfg.cy; cam.W = h->cfg.width; cam.H = h->cfg.height; }
-    if (cam.W < 1 || cam.W > 8192 || cam.H < 1 || cam.H > 8192) return refuse("cam_width and cam_height must be 1..8192");
-    if (!std::isfinite(cam.fx) || !std::isfinite(cam.fy) || !(cam.fx > 0.0f) || !(cam.fy > 0.0f) || !std::isfinite(cam.cx) || !std::isfinite(cam.cy))
-        return refuse("fx and fy must be finite and > 0, cx and cy finite");
+    if (const char* what = navlive_pinhole(h, p->fx, p->fy, p->cx, p->cy, p->cam_width, p->cam_height, cam)) return refuse(what);
     if (p->stride < 1 || p->stride > 64) return refuse("stride must be 1..64");
     cam.stride = p->stride; cam.nu = cam.W / p->stride; cam.nv = cam.H / p->stride;
     if (cam.nu < 1 || cam.nv < 1) return refuse("the stride leaves no pixel lattice");
     if (!(p->hit_margin_cells >= 0.0f) || !std::isfinite(p->hit_margin_cells)) return refuse("hit_margin_cells must be finite and >= 0");
     if (p->min_seen < 1) return refuse("min_seen must be >= 1");
-    cam.tmin = p->t_min; cam.tmax = p->t_max;
-    if (cam.tmin == 0.0f && cam.tmax == 0.0f) { cam.tmin = h->cfg.range_min; cam.tmax = h->cfg.range_max; }
-    if (!std::isfinite(cam.tmin) || !std::isfinite(cam.tmax) || !(cam.tmin > 0.0f) || !(cam.tmax > cam.tmin))
-        return refuse("the range needs 0 < t_min < t_max, both finite");
+    if (const char* what = navlive_range(h, p->t_min, p->t_max, cam)) return refuse(what);
     if (p->mask_mode < 0 || p->mask_mode > 2) return refuse("mask_mode must be 0..2");
     if (p->mask_mode != 0 && !mask) return refuse("mask is NULL with mask_mode != 0");
     const int df = h->in_depth;
@@ -294,13 +268,9 @@ int ssf_navlive_overlay(ssf_handle* h, const ssf_navlive_params* p, const void* 
     }
     { int rc = model_at_rest(h, "ssf_navlive_overlay", "overlays no frame"); if (rc) return rc; }
 
-    float gpose[12], cpose[12];
-    if (p->grid_pose) std::memcpy(gpose, p->grid_pose, sizeof(gpose));
-    else { int rc = ssf_navgrid_default_pose(h, &g, gpose); if (rc) return rc; }
-    if (p->cam_pose) std::memcpy(cpose, p->cam_pose, sizeof(cpose)); else pose_to12(h->pose, cpose);
-    std::memcpy(cam.R, cpose, 9 * sizeof(float)); cam.t[0] = cpose[9]; cam.t[1] = cpose[10]; cam.t[2] = cpose[11];
+    float gpose[12];
     NavGrid G{};
-    std::memcpy(G.R, gpose, 9 * sizeof(float)); G.t[0] = gpose[9]; G.t[1] = gpose[10]; G.t[2] = gpose[11];
+    { int rc = navlive_frames(h, &g, p->grid_pose, p->cam_pose, G, cam, gpose); if (rc) return rc; }
     G.W = p->width; G.H = p->height; G.res = p->res; G.step = step; G.fW = (float)G.W; G.fH = (float)G.H;
     G.zmax = p->z_max; G.floor_max = p->floor_max;
 

@@ -28,8 +28,9 @@
 //            best_traj from the packed grid.
 // No device-wide barrier, no inline assembly; nothing depends on the order the hardware works in.
 // The step, the arc's walk, the score, the winner, the replay and the host side of the call live in ssf_navsteer_walk.hpp, generic
-// over the cell test, and are shared with ssf_navfoot.hip (include/ssf_navfoot.h); this file holds the disc's cell test (the packed
-// word, staged or not), the staging choice and the three kernels' frames.
+// over the cell test, and are shared with ssf_navfoot.hip (include/ssf_navfoot.h); and with
+// ssf_navdyn.hip (include/ssf_navdyn.h), and so do the disc's cell test (the packed word, staged or not) and its roll frame; this
+// file holds the staging choice, the three kernels and their launches.
 //
 // Bounds: a cell is read only after the test that it lies in the grid; a read of the staged window tests the window's box as well
 // and goes to the grid when outside (by the reach argument it never is).  Per-candidate arrays are written at pose * K + c with
@@ -49,58 +50,16 @@ __global__ __launch_bounds__(256) void k_navsteer_pack(size_t P, int min_dist2, 
                                                        const int32_t* __restrict__ dist2, uint32_t* __restrict__ pk) {
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
-    const int s = state[p], d = dist2[p];
-    const bool trav = (s == 0 || (allow_unknown && s == -1)) && d >= min_dist2;
-    const int dd = d < 0 ? 0 : (d > cap ? cap : d);
-    pk[p] = (trav ? (uint32_t)NS_TRAV : 0u) | (uint32_t)dd;
+    pk[p] = ns_disc_word(state[p], dist2[p], min_dist2, allow_unknown, cap);
 }
-
-// the disc's cell test (step 3): the packed word, from the staged window when the cell lies in it, else from the grid
-struct NavSteerCells {
-    const uint32_t* pk; const uint32_t* win; int W, x0, y0, ww, wh; bool staged;
-    __device__ __forceinline__ int need(int, int) const { return 0; }
-    __device__ __forceinline__ uint32_t word(int ix, int iy) const {
-        if (staged) {
-            const int lx = ix - x0, ly = iy - y0;
-            if ((unsigned)lx < (unsigned)ww && (unsigned)ly < (unsigned)wh) return win[ly * ww + lx];
-        }
-        return pk[(size_t)iy * W + ix];
-    }
-    __device__ __forceinline__ bool free(int ix, int iy, int, int& d) const {
-        const uint32_t u = word(ix, iy);
-        d = (int)(u & NS_D);
-        return (u & NS_TRAV) != 0;
-    }
-};
 
 // ---- roll: one workgroup per (pose, 256 candidates) (steps 4 to 7) ------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_navsteer_roll(NavSteerRule r, const uint32_t* __restrict__ pk, const uint32_t* __restrict__ cost,
                                                        const int32_t* __restrict__ poses, const int32_t* __restrict__ targets,
                                                        const uint32_t* __restrict__ dirs, unsigned long long* __restrict__ keys,
                                                        int32_t* __restrict__ n_adm, NavSteerCand out, unsigned long long* __restrict__ stats) {
-    extern __shared__ uint32_t s_win[];                               // the staged window, row-major, ww cells a row
     __shared__ uint32_t s_dir[NS_DIRS];                               // (S << 16) | (C & 0xFFFF)
-    const int t = threadIdx.x, pose = blockIdx.y;
-    const int px = poses[3 * (size_t)pose], py = poses[3 * (size_t)pose + 1], ph = poses[3 * (size_t)pose + 2] & 0xFFFF;
-    const int cx0 = px >> 10, cy0 = py >> 10;
-    const bool inside = cx0 >= 0 && cx0 < r.W && cy0 >= 0 && cy0 < r.H;
-    const uint32_t start = inside ? pk[(size_t)cy0 * r.W + cx0] : 0u;
-    const bool start_ok = (start & NS_TRAV) != 0;                     // (the same for every thread)
-    // the window of the pose, clipped to the grid
-    const int x0 = cx0 - r.R > 0 ? cx0 - r.R : 0, y0 = cy0 - r.R > 0 ? cy0 - r.R : 0;
-    const int x1 = cx0 + r.R < r.W - 1 ? cx0 + r.R : r.W - 1, y1 = cy0 + r.R < r.H - 1 ? cy0 + r.R : r.H - 1;
-    const int ww = x1 - x0 + 1, wh = y1 - y0 + 1;
-    const bool staged = start_ok && (long long)ww * wh <= r.stage_cells;
-    if (start_ok) {
-        for (int k = t; k < NS_DIRS; k += 256) s_dir[k] = dirs[k];
-        if (staged) {
-            const int n = ww * wh;
-            for (int i = t; i < n; i += 256) { const int ly = i / ww, lx = i - ly * ww; s_win[i] = pk[(size_t)(y0 + ly) * r.W + (x0 + lx)]; }
-        }
-    }
-    __syncthreads();
-    const NavSteerCells cells{pk, s_win, r.W, x0, y0, ww, wh, staged};
-    ns_roll_body(r, cells, start_ok, (int)(start & NS_D), staged, px, py, ph, cx0, cy0, s_dir, cost, targets, keys, n_adm, out, stats);
+    ns_disc_roll(r, NsNoHook{}, s_dir, pk, cost, poses, targets, dirs, keys, n_adm, out, stats);
 }
 
 // ---- pick: one lane per pose (steps 7 and 8) -----------------------------------------------------------------------------------------
@@ -108,7 +67,7 @@ __global__ __launch_bounds__(256) void k_navsteer_pick(NavSteerRule r, const uin
                                                        const uint32_t* __restrict__ dirs, const unsigned long long* __restrict__ keys,
                                                        const int32_t* __restrict__ n_adm, NavSteerPose out, unsigned long long* __restrict__ stats) {
     const NavSteerCells cells{pk, nullptr, r.W, 0, 0, 0, 0, false};
-    ns_pick_body(r, cells, [&](int cx, int cy, int) { return (pk[(size_t)cy * r.W + cx] & NS_TRAV) != 0; }, poses, dirs, keys, n_adm, out, stats);
+    ns_pick_body(r, cells, NsNoHook{}, [&](int cx, int cy, int) { return (pk[(size_t)cy * r.W + cx] & NS_TRAV) != 0; }, poses, dirs, keys, n_adm, out, stats);
 }
 
 static void launch_navsteer_pack(hipStream_t st, size_t P, const NavSteerRule& r, const int8_t* state, const int32_t* dist2, uint32_t* pk) {
@@ -118,12 +77,8 @@ static void launch_navsteer_pack(hipStream_t st, size_t P, const NavSteerRule& r
 static void launch_navsteer_roll(hipStream_t st, const NavSteerRule& r, const uint32_t* pk, const uint32_t* cost, const int32_t* poses, const int32_t* targets,
                                  const uint32_t* dirs, unsigned long long* keys, int32_t* n_adm, const NavSteerCand& out, unsigned long long* stats) {
     ScopedKernel sk("navsteer_roll", st);
-    // the largest clipped window of any pose, capped at what is staged (r.stage_cells): a pose whose window is larger walks the grid
-    const long long side = 2LL * r.R + 1;
-    const long long bound = std::min<long long>(side, r.W) * std::min<long long>(side, r.H);
-    const size_t lds = 4 * (size_t)std::min<long long>(bound, r.stage_cells);
-    hipLaunchKernelGGL(k_navsteer_roll, dim3((unsigned)((r.K + 255) / 256), (unsigned)r.n_poses), dim3(256), lds, st, r, pk, cost, poses, targets, dirs, keys,
-                       n_adm, out, stats);
+    hipLaunchKernelGGL(k_navsteer_roll, dim3((unsigned)((r.K + 255) / 256), (unsigned)r.n_poses), dim3(256), navsteer_window_lds(r), st, r, pk, cost, poses,
+                       targets, dirs, keys, n_adm, out, stats);
 }
 static void launch_navsteer_pick(hipStream_t st, const NavSteerRule& r, const uint32_t* pk, const int32_t* poses, const uint32_t* dirs,
                                  const unsigned long long* keys, const int32_t* n_adm, const NavSteerPose& out, unsigned long long* stats) {
@@ -133,24 +88,25 @@ static void launch_navsteer_pick(hipStream_t st, const NavSteerRule& r, const ui
 
 }  // namespace ssf
 
+// what is staged (the file's head: a measured choice); no output depends on it.  ssf_navdyn.hip's launch asks it as well: its roll
+// kernel holds the mover list (1.5 KiB) in static LDS on top of NS_STATIC_LDS, which makes `roomy` slightly optimistic for it (a choice
+// of speed, never of results) and must keep the largest staged window inside the 64 KiB a workgroup gets without opting in
+static_assert(4 * ssf::NS_LDS_CELLS + ssf::NS_STATIC_LDS + 4 * SSF_NAVDYN_MAX_MOVERS * SSF_NAVDYN_MOVER_WORDS <= 64 * 1024,
+              "the staged window, the roll kernel's static LDS and ssf_navdyn.hip's mover list no longer fit a workgroup's LDS");
+int navsteer_stage_cells(const ssf::NavSteerRule& r) {
+    using namespace ssf;
+    const long long side = 2LL * r.R + 1, bound = std::min<long long>(side, r.W) * std::min<long long>(side, r.H);
+    const long long bytes = 4 * std::min<long long>(bound, NS_LDS_CELLS) + NS_STATIC_LDS, wgs = (long long)((r.K + 255) / 256) * r.n_poses;
+    const bool roomy = bytes <= NS_LDS_FREE || wgs <= (long long)NS_CUS * (NS_CU_LDS / bytes);
+    return r.walk ? 0 : (roomy ? (int)NS_LDS_CELLS : (int)((NS_LDS_FREE - NS_STATIC_LDS) / 4));
+}
+
 namespace {
 // the disc's part of a call (navsteer_call, ssf_navsteer_walk.hpp): the staging choice, the packed grid, the three launches
 struct NavSteerRun {
     ssf_handle* h;
-    int stage_cells(const ssf::NavSteerRule& r) const {   // what is staged (the file's head: a measured choice); no output depends on it
-        using namespace ssf;
-        const long long side = 2LL * r.R + 1, bound = std::min<long long>(side, r.W) * std::min<long long>(side, r.H);
-        const long long bytes = 4 * std::min<long long>(bound, NS_LDS_CELLS) + NS_STATIC_LDS, wgs = (long long)((r.K + 255) / 256) * r.n_poses;
-        const bool roomy = bytes <= NS_LDS_FREE || wgs <= (long long)NS_CUS * (NS_CU_LDS / bytes);
-        return r.walk ? 0 : (roomy ? (int)NS_LDS_CELLS : (int)((NS_LDS_FREE - NS_STATIC_LDS) / 4));
-    }
-    bool reserve(size_t P) {
-        NavSteerWs& w = h->navsteer;
-        if (P <= w.cells) return true;
-        if (!w.bufs.grow({{(void**)&w.pk, 4 * P}})) return false;
-        w.cells = P;
-        return true;
-    }
+    int stage_cells(const ssf::NavSteerRule& r) const { return navsteer_stage_cells(r); }
+    bool reserve(size_t P) { return navsteer_reserve_pk(h, P); }
     int launch(hipStream_t st, const ssf::NavSteerRule& r, const void* state, const int32_t* dist2, const uint32_t* cost, const int32_t* poses,
                const int32_t* targets, NavSteerWs& w, const ssf::NavSteerCand& cand, const ssf::NavSteerPose& pick) {
         ssf::launch_navsteer_pack(st, (size_t)r.W * r.H, r, (const int8_t*)state, dist2, w.pk);

@@ -218,6 +218,10 @@ def plan_cells(pose, res, cam_t, goals_m):
 
 
 NAV_STEER_DT = 0.1                     # seconds per rollout step of --nav-steer
+NAV_FRAME_DT = 1.0 / 30.0              # seconds between two frames, for --nav-steer-movers' velocities (the sequences here are 30 Hz)
+# The tracker's steps_since is a whole number of rollout steps >= 1.  Grids fewer than three frames apart (--nav-grid-every 1 or 2) are
+# 0.33 or 0.67 of a step apart and count as one step, so their movers' velocities come out up to three times too small; from three
+# frames on the interval is rounded to the nearest step.  The replay is a demonstration: a control loop passes its own step count.
 
 
 def steer_pose(pose, res, cam_pose):
@@ -266,7 +270,12 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
     one nav-foot log line; the command is logged as without it.  With steer['poses'] = dict(turn_cost) as well, the rollouts' cost term
     is no longer the disc's field but the projection of the plan over (x, y, heading) for that body (include/ssf_navpose.h), from the
     plan's goal cells at any heading and the steer pose: <k>_pose_cost.npy (cell_cost), <k>_pose_bin.npy, <k>_pose_path.npy ((len, 3)
-    int32: ix, iy, bin) and one nav-pose log line with the start's status and cost and the stats"""
+    int32: ix, iy, bin) and one nav-pose log line with the start's status and cost and the stats.
+    With steer['movers'] = dict(tracker=a binding.MoverTracker, last=None) and a live layer, the rollouts steer among the frame's moving
+    objects (include/ssf_navdyn.h): the motion detector's mask keeps them OUT of the live layer (mask_mode 2), its labels and the depth
+    give their blobs in the grid frame, the tracker turns this table and the one of the grid before into movers (steps_since from
+    the frames between the two at NAV_FRAME_DT seconds each), and nav_dyn_steer / nav_dyn_foot_steer refuse the steps that meet
+    them: <k>_blobs.npy ((n, 8) int32), <k>_movers.npy ((n, 6) int32) and one nav-movers log line"""
     if carve_views is None:
         out = fusion.nav_grid(outputs=("state", "dist2"), res=res)
     else:
@@ -287,9 +296,22 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
     if carve_views is not None:
         np.save(os.path.join(grid_dir, name + "_seen.npy"), out["seen"])
     lv = None
+    movers = None
     if live is not None:
-        lv = fusion.nav_live(live["depth"], state, outputs=("state", "dist2"), grid_pose=pose, res=res, min_hits=int(live.get("min_hits", 4)),
-                             stride=int(live.get("stride", 4)))
+        mm = None
+        if steer is not None and steer.get("movers") is not None:
+            mm = fusion.motion_mask(live["depth"], outputs=("mask", "label"))
+            table = fusion.nav_dyn_blobs(live["depth"], mm["mask"], mm["label"], grid_pose=pose, width=state.shape[1], height=state.shape[0], res=res)
+            track = steer["movers"]
+            frames_since = 1 if track.get("last") is None else max(1, k - track["last"])
+            movers = track["tracker"].update(table["blobs"], max(1, int(round(frames_since * NAV_FRAME_DT / NAV_STEER_DT))))
+            track["last"] = k
+            np.save(os.path.join(grid_dir, name + "_blobs.npy"), table["blobs"])
+            np.save(os.path.join(grid_dir, name + "_movers.npy"), movers)
+            print("nav-movers %s: movers=%d pixels_masked=%d %s" % (name, len(movers), mm["stats"]["pixels_masked"],
+                                                                   " ".join("%s=%d" % (nm, n) for nm, n in table["stats"].items())))
+        lv = fusion.nav_live(live["depth"], state, mask=None if mm is None else mm["mask"], outputs=("state", "dist2"), grid_pose=pose, res=res,
+                             min_hits=int(live.get("min_hits", 4)), stride=int(live.get("stride", 4)), mask_mode=0 if mm is None else 2)
         np.save(os.path.join(grid_dir, name + "_live_state.npy"), lv["state"])
         np.save(os.path.join(grid_dir, name + "_live_dist2.npy"), lv["dist2"])
         print("nav-live %s: %s" % (name, " ".join("%s=%d" % (nm, v) for nm, v in lv["stats"].items() if nm != "pose")))
@@ -331,7 +353,10 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
                     print("nav-pose %s: headings=%d status=%d cost=%d path=%d %s" % (name, bins, int(pp["start_status"][0]), int(pp["start_cost"][0]),
                                                                                     len(pp["path"][0]), " ".join("%s=%d" % (nm, n) for nm, n in pp["stats"].items())))
                     kw["cost"] = pp["cell_cost"]
-                st = fusion.nav_foot_steer(lay["free_mask"], on["dist2"], at, bins, **kw)
+                st = fusion.nav_foot_steer(lay["free_mask"], on["dist2"], at, bins, **kw) if movers is None else \
+                    fusion.nav_dyn_foot_steer(lay["free_mask"], on["dist2"], at, bins, movers=movers, **kw)
+            elif movers is not None:
+                st = fusion.nav_dyn_steer(on["state"], on["dist2"], steer_pose(pose, res, fusion.get_pose()), movers=movers, **kw)
             else:
                 st = fusion.nav_steer(on["state"], on["dist2"], steer_pose(pose, res, fusion.get_pose()), **kw)
             np.save(os.path.join(grid_dir, name + "_steer_traj.npy"), st["best_traj"][0])
@@ -430,6 +455,10 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
         raise ValueError("nav_live needs nav_grid_dir")
     if nav_steer is not None and nav_plan is None:
         raise ValueError("nav_steer needs nav_plan")
+    if nav_steer is not None and nav_steer.get("movers") is not None:
+        if nav_live is None:
+            raise ValueError("nav_steer's movers need nav_live")
+        nav_steer = dict(nav_steer, movers=mover_tracker_of(nav_steer["movers"], nav_grid_res))      # (one tracker for the whole sequence)
     live_of = (lambda depth: dict(nav_live, depth=depth)) if nav_live is not None else (lambda depth: None)
     carve_views = (lambda: [r["pose"] for r in results]) if nav_grid_carve else (lambda: None)
     if odometry_prior:
@@ -683,6 +712,13 @@ def parse_args(argv=None):
     ap.add_argument("--nav-steer-footprint", type=float, nargs=4, default=None, metavar=("FRONT", "BACK", "LEFT", "RIGHT"),
                     help="with --nav-steer: the robot's body as a rectangle, metres from its centre; the rollouts test it at the headings they "
                          "sweep (include/ssf_navfoot.h) and <k>_foot_mask.npy holds its heading layers")
+    ap.add_argument("--nav-steer-movers", action="store_true",
+                    help="with --nav-steer and --nav-live: steer among the frame's moving objects (include/ssf_navdyn.h): the motion detector's "
+                         "pixels stay out of the live layer and go to the rollouts as predicted discs: <k>_blobs.npy, <k>_movers.npy and one "
+                         "nav-movers log line per grid")
+    ap.add_argument("--nav-steer-mover-inflate", type=float, default=None, metavar="R", help="metres added to every mover's radius: the robot's own (default 0.3)")
+    ap.add_argument("--nav-steer-mover-gate", type=float, default=None, metavar="G",
+                    help="the largest distance in metres between a blob and the blob of the grid before that it is taken to be (default 1.0)")
     ap.add_argument("--nav-steer-headings", type=int, default=None, metavar="B", help="heading bins of --nav-steer-footprint: 1, 2, 4, 8, 16 or 32 (default 16)")
     ap.add_argument("--nav-plan-poses", action="store_true",
                     help="with --nav-steer-footprint and --nav-plan-goal: plan over (x, y, heading) for that body (include/ssf_navpose.h) and score the "
@@ -750,6 +786,14 @@ def parse_args(argv=None):
         ap.error("--nav-steer-headings goes with --nav-steer-footprint")
     if a.nav_steer_headings is not None and a.nav_steer_headings not in (1, 2, 4, 8, 16, 32):
         ap.error("--nav-steer-headings is 1, 2, 4, 8, 16 or 32")
+    if a.nav_steer_movers and not (a.nav_steer and a.nav_live):
+        ap.error("--nav-steer-movers goes with --nav-steer and --nav-live")
+    if (a.nav_steer_mover_inflate is not None or a.nav_steer_mover_gate is not None) and not a.nav_steer_movers:
+        ap.error("--nav-steer-mover-inflate and --nav-steer-mover-gate go with --nav-steer-movers")
+    if a.nav_steer_mover_inflate is not None and not a.nav_steer_mover_inflate >= 0.0:
+        ap.error("--nav-steer-mover-inflate is >= 0")
+    if a.nav_steer_mover_gate is not None and not a.nav_steer_mover_gate > 0.0:
+        ap.error("--nav-steer-mover-gate is > 0")
     if a.nav_plan_poses and (a.nav_steer_footprint is None or not a.nav_plan_goal):
         ap.error("--nav-plan-poses goes with --nav-steer-footprint and --nav-plan-goal (its goals are cells, not the frontier)")
     if a.nav_plan_turn_cost is not None and not a.nav_plan_poses:
@@ -796,7 +840,17 @@ def nav_steer_of(a):
         steer.update(footprint=tuple(float(v) for v in a.nav_steer_footprint), headings=16 if a.nav_steer_headings is None else int(a.nav_steer_headings))
     if a.nav_plan_poses:
         steer.update(poses=dict(turn_cost=5 if a.nav_plan_turn_cost is None else int(a.nav_plan_turn_cost)))
+    if a.nav_steer_movers:
+        steer.update(movers=dict(inflate=0.3 if a.nav_steer_mover_inflate is None else float(a.nav_steer_mover_inflate),
+                                 gate=1.0 if a.nav_steer_mover_gate is None else float(a.nav_steer_mover_gate)))
     return steer
+
+
+def mover_tracker_of(movers, res):
+    """write_nav_grid's steer['movers'] from nav_steer_of's: the tracker with the gate and the inflation in sub-units of a grid of `res`"""
+    from . import binding
+    units = lambda metres: int(round(float(metres) / res * 1024.0))
+    return dict(tracker=binding.MoverTracker(gate=units(movers.get("gate", 1.0)), inflate=units(movers.get("inflate", 0.3))), last=None)
 
 
 def nav_frontiers_of(a):
@@ -809,10 +863,12 @@ def nav_frontiers_of(a):
 
 def library_of(a):
     """the name of binding's loader of the library that exports every entry point the parsed options ask for (the carve's, the plan's,
-    the regions', the waypoints', the live layer's, the commands', the footprint's and the pose plan's entry points: libraries of their
-    own, each holding the one before it)"""
+    the regions', the waypoints', the live layer's, the commands', the footprint's, the pose plan's and the movers' entry points: libraries
+    of their own, each holding the one before it)"""
     steer = nav_steer_of(a)
     if steer:
+        if steer.get("movers") is not None:
+            return "load_dyn"
         if steer.get("poses") is not None:
             return "load_pose"
         return "load_foot" if steer.get("footprint") is not None else "load_steer"
