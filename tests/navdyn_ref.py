@@ -42,9 +42,15 @@ def movers_ok(movers):
                 and (m[:, 4] <= MAX_R).all() and (m[:, 5] >= 0).all() and (m[:, 5] <= MAX_GROW).all())
 
 
-def rollouts(grid, dist2, cost, poses, targets, movers, c, B=None):
+WRONG_RULES = ("hit_le", "movers_first", "last_hit", "gap_uncommitted", "zero_based", "start_tested")
+
+
+def rollouts(grid, dist2, cost, poses, targets, movers, c, B=None, _wrong=None):
     """every output of ssf_navdyn_rollouts (B None: grid is state) or ssf_navdyn_foot_rollouts (B: the heading bins; grid is free_mask)
-    in the ABI's dtypes (best_traj entries past best_len are 0 here and unwritten there) and 'stats'.  c: params()"""
+    in the ABI's dtypes (best_traj entries past best_len are 0 here and unwritten there) and 'stats'.  c: params().
+    _wrong (tests/test_navdyn.py only): one of WRONG_RULES, a rule the header does NOT state, swapped in for the one it does, to show
+    on the CPU which scenes would tell the two apart"""
+    assert _wrong is None or _wrong in WRONG_RULES, _wrong
     grid = np.asarray(grid)
     H, W = grid.shape
     dist2 = np.asarray(dist2).astype(np.int64)
@@ -112,6 +118,11 @@ def rollouts(grid, dist2, cost, poses, targets, movers, c, B=None):
         hit, gap = np.full(K, -1, np.int64), np.full(K, cap, np.int64)
         traj = np.zeros((K, T + 1, 3), np.int64)
         traj[:, 0] = (px, py, ph)
+        if _wrong == "start_tested":                                    # (wrong: the start is tested like a step, against R_0)
+            for m in range(len(movers) - 1, -1, -1):
+                mx, my, _, _, mr, _ = (int(e) for e in movers[m])
+                if (px - mx) ** 2 + (py - my) ** 2 < mr * mr:
+                    hit[:], alive[:] = m, False
         for s in range(1, T + 1):                                       # s: the step being attempted, 1-based
             k = ((2 * h + w + 64) >> 7) & 1023
             nx, ny = x + ((v * _C[k] + 8192) >> 14), y + ((v * _S[k] + 8192) >> 14)
@@ -123,15 +134,24 @@ def rollouts(grid, dist2, cost, poses, targets, movers, c, B=None):
             step &= alive
             # the movers, after the static test: the smallest m with D2 < R_s^2 ends the rollout
             g = gap.copy()
+            at = s - 1 if _wrong == "zero_based" else s                  # (wrong: the movers of the step before)
             for m in range(len(movers) - 1, -1, -1):                    # (downwards, so that the smallest hitting m is written last)
                 mx, my, mvx, mvy, mr, mg = (int(e) for e in movers[m])
-                X, Y, Rs = mx + s * mvx, my + s * mvy, mr + s * mg
+                X, Y, Rs = mx + at * mvx, my + at * mvy, mr + at * mg
                 D2 = (nx - X) ** 2 + (ny - Y) ** 2
                 assert int(D2.max()) < 1 << 53 and Rs * Rs < 1 << 43
                 inside = step & (D2 < Rs * Rs)
+                if _wrong == "hit_le":                                  # (wrong: a touching disc hits)
+                    inside = step & (D2 <= Rs * Rs)
+                if _wrong == "movers_first":                            # (wrong: a step the static test refuses is still charged to a mover)
+                    inside = alive & (D2 < Rs * Rs)
+                if _wrong == "last_hit":                                # (wrong: downwards, the first one written stays: the largest m)
+                    inside &= hit < 0
                 hit = np.where(inside, m, hit)
                 for i in np.flatnonzero(step & ~inside & (D2 < (g + Rs) ** 2)):
                     g[i] = math.isqrt(int(D2[i])) - Rs
+            if _wrong == "gap_uncommitted":                             # (wrong: the gaps of a step that a mover refuses count as well)
+                gap = np.where(step, g, gap)
             step &= hit < 0
             alive &= step
             if not alive.any():
@@ -295,6 +315,34 @@ def hand_scene(r):
                 movers=np.array([(14848, 12800, 0, -256, r, 0)], np.int32), c=c)
 
 
+X0 = Y0 = 10 * SUB + 512                                                # hand_scene's pose
+# name -> (heading, movers, wall cells (ix, iy)) on hand_scene: the fast candidate advances exactly 512 a step along a heading that is
+# a multiple of a quarter turn, so D2 == R_s^2 can be met.  tests/test_navdyn.py states what each must give, by hand
+HAND_SCENES = {
+    "touch static": (0, [(X0 + 512 * 6 + 1000, Y0, 0, 0, 1000, 0)], ()),
+    "touch growing": (0, [(X0 + 2560 + 500, Y0, 0, 0, 0, 100)], ()),
+    "touch pythagorean": (0, [(X0 + 512 * 3 + 600, Y0 + 800, 0, 0, 1000, 0)], ()),
+    "touch quarter turn": (16384, [(X0, Y0 + 512 * 6 + 1000, 0, 0, 1000, 0)], ()),
+    # the mover walks towards the robot at 256 a step: the two close at 768 a step and touch at step 4; it touches the standing
+    # candidate at step 12, the last
+    "touch moving": (0, [(X0 + 768 * 4 + 700, Y0, -256, 0, 700, 0)], ()),
+    # the cell (13, 10) is a wall and lies inside the disc; the fast candidate's step 5 enters both: the static test answers
+    "wall inside a disc": (0, [(13 * SUB + 512, Y0, 0, 0, 800, 0)], ((13, 10),)),
+    # mover 1 refuses step 6; at that refused step mover 0 is nearer than it is at any committed step
+    "gap of a refused step": (0, [(X0 + 512 * 6, Y0 + 1300, 0, 0, 1000, 0), (X0 + 512 * 6 + 900, Y0, 0, 0, 1000, 0)], ()),
+}
+HAND_CASES = tuple(HAND_SCENES)
+
+
+def hand_made(name):
+    heading, movers, walls = HAND_SCENES[name]
+    s = hand_scene(0)
+    for ix, iy in walls:
+        s["state"][iy, ix] = 100
+    s["poses"] = np.array([sr.centre(10, 10, heading)], np.int32)
+    return _with(s, movers)
+
+
 def random_movers(W, H, m, seed, r_max=1500):
     """m movers inside and around a W x H grid, walking at up to half a cell a step"""
     rng = np.random.default_rng(seed)
@@ -303,7 +351,8 @@ def random_movers(W, H, m, seed, r_max=1500):
 
 
 # name -> (steering scene of navsteer_ref, keywords that override its lattice, mover list maker, dyn keywords).
-# Grids 1 x 1, 1 x 70, 37 x 53, 64 x 65, 97 x 33; K = 297 and 512; n_steps 1 and 256; n_poses 1 and 70
+# Grids 1 x 1, 1 x 70, 37 x 53, 64 x 65, 97 x 33; K = 297 and 512; n_steps 1 and 256; n_poses 1, 70 and 300.  A footprint's scene
+# carries its own (foot, B): B = 1, 4, 8, 16, 32
 K297 = dict(n_v=9, n_w=33)                                              # the default lattice: 297 candidates
 K512 = dict(n_v=8, n_w=64, v_min=-128, v_step=128, w_min=-2016, w_step=64)
 
@@ -382,18 +431,54 @@ def make_scene(name):
         return _with(s, [(x + 40 * SUB, y + 30 * SUB, 0, 0, 0, 4096)])
     if name == "cap 0":
         return _with(_grid_scene(37, 53, 4, 11, n_steps=24, mover_cap=0, mover_weight=1000, **K297), random_movers(37, 53, 8, 14))
+    if name == "300 poses K64":
+        # more poses than one pick workgroup holds: the second one's lanes replay their winners against the list in global memory
+        return _with(_grid_scene(37, 53, 300, 13, n_steps=12, n_v=4, n_w=16, v_min=128, v_step=128, w_min=-1920, w_step=256, mover_weight=5),
+                     random_movers(37, 53, 12, 16))
+    if name == "mixed walks":
+        return mixed_scene()
+    if name in HAND_SCENES:
+        return hand_made(name)
+    # the footprint's: (footprint, B) with the scene
     if name == "foot 37x53":
-        return _with(_grid_scene(37, 53, 8, 12, n_steps=24, mover_weight=3, **dict(K297, w_min=-8192, w_step=512)), random_movers(37, 53, 16, 15))
+        s = _with(_grid_scene(37, 53, 8, 12, n_steps=24, mover_weight=3, **dict(K297, w_min=-8192, w_step=512)), random_movers(37, 53, 16, 15))
+        return dict(s, foot=FOOT, B=16)
+    if name == "foot B1 point":
+        s = _with(_grid_scene(37, 53, 8, 14, n_steps=24, mover_weight=3, **dict(K297, w_min=-8192, w_step=512)), random_movers(37, 53, 16, 17))
+        return dict(s, foot=fr.POINT, B=1)
+    if name == "foot B32 K512 64 movers":
+        s = _with(_grid_scene(37, 53, 8, 15, n_steps=24, target_weight=1, mover_weight=7, mover_cap=3000, **K512), random_movers(37, 53, 64, 18))
+        return dict(s, foot=BODY, B=32)
+    if name == "foot 300 poses K257":
+        s = _with(_grid_scene(64, 65, 300, 16, n_steps=8, n_v=1, n_w=257, v_min=700, v_step=0, w_min=-2048, w_step=16), random_movers(64, 65, 12, 19))
+        return dict(s, foot=BODY, B=16)
+    if name == "foot T256":
+        s = _grid_scene(64, 65, 3, 17, n_steps=256, min_free_steps=4, mover_cap=65536, **dict(K297, v_step=16))
+        return dict(_with(s, random_movers(64, 65, 12, 20, r_max=2500)), foot=BODY, B=8)
+    if name == "foot 1x1 B4":
+        return dict(make_scene("1x1"), foot=fr.POINT, B=4)
     raise KeyError(name)
 
 
-FOOT = (2048, 1536, 1024, 1024, 0)                                       # the footprint of the "foot" scenes, with B = 16
-FOOT_B = 16
+def mixed_scene():
+    """navsteer_ref.mixed_scene (1281 workgroups, of which the launch stages the windows of up to 4056 cells and walks the others) among
+    ten movers, with 60 of its live poses: the others stand outside the grid, where they end at once but still count as workgroups"""
+    s = sr.mixed_scene()
+    live = 4 + 60
+    poses = s["poses"].copy()
+    poses[live:4 + sr.MIXED_LIVE] = [((-3 - k) * SUB, 5 * SUB, k) for k in range(4 + sr.MIXED_LIVE - live)]
+    c = dict(s["c"], **DYN_DEFAULTS)
+    return _with(dict(s, poses=poses, c=c), random_movers(78, 120, 10, 21, r_max=2500))
+
+
+FOOT = (2048, 1536, 1024, 1024, 0)                                       # the footprint of "foot 37x53", with B = 16
+BODY = (1536, 512, 512, 512, 0)                                          # a smaller body, for the scenes that set B themselves
 DISC_CASES = ("1x1", "1x70 K297 one mover", "37x53 K512 64 movers 70 poses", "64x65 K297 T256", "97x33 K512 T1", "r 0 never hits",
-              "two movers one step", "mover on the start", "int64 path", "grow 4096", "cap 0")
-FOOT_CASES = ("foot 37x53",)
+              "two movers one step", "mover on the start", "int64 path", "grow 4096", "cap 0", "300 poses K64")
+FOOT_CASES = ("foot 37x53", "foot B1 point", "foot B32 K512 64 movers", "foot 300 poses K257", "foot T256", "foot 1x1 B4")
 # the random lists: the reference alone must show a hit, an admissible candidate and a gap strictly between 0 and the cap
-GUARDED = ("37x53 K512 64 movers 70 poses", "64x65 K297 T256", "97x33 K512 T1", "foot 37x53")
+GUARDED = ("37x53 K512 64 movers 70 poses", "64x65 K297 T256", "97x33 K512 T1", "foot 37x53", "300 poses K64", "foot B1 point",
+           "foot B32 K512 64 movers", "foot 300 poses K257", "foot T256")
 _WANT = {}
 
 
@@ -407,20 +492,20 @@ def scene_inputs(name):
     def make():
         s = make_scene(name)
         if name in FOOT_CASES:
-            s["free_mask"] = fr.layers(s["state"], s["c"]["allow_unknown"], FOOT, FOOT_B)["free_mask"]
+            s["free_mask"] = fr.layers(s["state"], s["c"]["allow_unknown"], s["foot"], s["B"])["free_mask"]
         return s
     return cached(("in", name), make)
 
 
-def scene_reference(name):
+def scene_reference(name, _wrong=None):
     """rollouts() of a scene, computed once and shared (the callers leave it unchanged)"""
     def make():
         s = scene_inputs(name)
         c = s["c"]
         foot = name in FOOT_CASES
         return rollouts(s["free_mask"] if foot else s["state"], s["dist2"], s["cost"] if c["cost_weight"] else None, s["poses"],
-                        s["targets"] if c["target_weight"] else None, s["movers"], c, FOOT_B if foot else None)
-    return cached(("want", name), make)
+                        s["targets"] if c["target_weight"] else None, s["movers"], c, s["B"] if foot else None, _wrong=_wrong)
+    return cached(("want", name) if _wrong is None else ("want", name, _wrong), make)
 
 
 def not_vacuous(want, c):
@@ -470,13 +555,41 @@ def blob_scene(cw, ch, kind):
         label[:] = np.arange(cw * ch, dtype=np.int32).reshape(ch, cw)[::-1, ::-1]
         mask[:] = 1
         kw = dict(min_points=1, max_blobs=5)
+    elif kind == "blocks":
+        # blocks of 5 x 3 pixels, each labelled with its first pixel: a tile's 16 columns are no multiple of 5 and its 16 rows none of 3,
+        # so a tile holds many labels of several pixels each and most labels lie in two tiles or in four.  A grid wide enough for the whole
+        # surface; the band still cuts it.  Three pixels carry labels that are no pixel index (step B.1: not members)
+        v, u = np.mgrid[0:ch, 0:cw]
+        label[:] = (v // 3 * 3) * cw + u // 5 * 5
+        mask[:] = 1
+        c = lr.params(width=64, height=31, res=0.05, floor_max=-0.3, z_max=0.1, **cam)
+        for k, odd in enumerate((cw * ch, np.iinfo(np.int32).max, np.iinfo(np.int32).min)):
+            label[(ch // 2 + k) % ch, (cw // 2 + 3 * k) % cw] = odd
+        kw = dict(min_points=1, max_blobs=64)
     else:
         raise KeyError(kind)
     return dict(depth=d, mask=mask, label=label, cam_pose=pose, grid_pose=lr.grid_pose_at(), c=c, cam=cam, **kw)
 
 
+def blob_tiles(s):
+    """of a blob scene, on the restatement's own pixels: (labels with contributing pixels in two or more 16 x 16 tiles, tiles that hold
+    eight or more labels)"""
+    c = s["c"]
+    ch, cw = s["label"].shape
+    d = s["depth"]
+    member = (s["mask"] != 0) & (s["label"] >= 0) & (s["label"].astype(np.int64) < cw * ch)
+    contrib = member & lr.valid_pixels(d, c) & grid_points(d, s["cam_pose"], s["grid_pose"], c)[2]
+    tiles_of, labels_in = {}, {}
+    for v, u in np.argwhere(contrib):
+        L, t = int(s["label"][v, u]), (int(v) // 16, int(u) // 16)
+        tiles_of.setdefault(L, set()).add(t)
+        labels_in.setdefault(t, set()).add(L)
+    return sum(len(t) >= 2 for t in tiles_of.values()), sum(len(l) >= 8 for l in labels_in.values())
+
+
 BLOB_CAMERAS = ((1, 1), (17, 13), (160, 128))
 BLOB_KINDS = ("none", "one pixel", "columns", "many")
+BLOCK_CAMERAS = ((40, 24), (35, 19))                                     # the "blocks" kind's: neither side a multiple of 16
 
 
 def blob_reference(cw, ch, kind, fmt):

@@ -1,7 +1,8 @@
 """Steering among movers (include/ssf_navdyn.h) without a GPU: the rule by hand on the restatement (tests/navdyn_ref.py), the restatement
 without movers against the disc's and the footprint's, the tracker in Python against ssf.hpp's and the restatement's, the blobs'
 restatement by hand, who exports the entry points, the header on its own, the struct layouts of the binding, the refusals that need no
-device, replay.py's options, and guards that the scenes of the GPU file show what they are there to show."""
+device, replay.py's options, and guards that the scenes of the GPU file show what they are there to show: among them the touching
+discs by hand, and for six wrong rules (navdyn_ref.WRONG_RULES) a scene of the GPU file whose reference each of them changes."""
 import ctypes as C
 import os
 import re
@@ -260,6 +261,126 @@ def test_the_special_lists_show_what_they_are_there_to_show():
     assert (want["cand_min_gap"] == 0).all() and want["stats"]["poses_ok"] == 1
 
 
+def test_the_footprint_scenes_stand_at_the_edges_they_name():
+    """B = 1 and 32, 256 steps, 64 movers, one cell, and more poses than a pick workgroup holds with winners on both sides of it"""
+    got = {name: dr.scene_inputs(name) for name in dr.FOOT_CASES}
+    assert {s["B"] for s in got.values()} >= {1, 4, 8, 16, 32} and got["foot 37x53"]["foot"] == dr.FOOT and got["foot 37x53"]["B"] == 16
+    assert got["foot T256"]["c"]["n_steps"] == 256 and len(got["foot B32 K512 64 movers"]["movers"]) == dr.MAX_MOVERS
+    assert got["foot 1x1 B4"]["free_mask"].shape == (1, 1) and got["foot 1x1 B4"]["free_mask"][0, 0] == 15
+    want = dr.scene_reference("foot 1x1 B4")
+    assert want["stats"]["poses_ok"] == 1 and (want["cand_min_gap"] == 0).all()
+    want = dr.scene_reference("foot T256")
+    assert want["cand_free"].max() > 64                                   # a rollout that is still running long after the others ended
+    for name in ("foot 300 poses K257", "300 poses K64"):
+        want = dr.scene_reference(name)
+        ok = np.flatnonzero(want["pose_status"] == 0)
+        assert len(want["best"]) >= 300 and (ok < 256).any() and (ok >= 256).any(), name
+        assert len(np.unique(want["best_min_gap"][ok[ok < 256]])) > 2 and len(np.unique(want["best_min_gap"][ok[ok >= 256]])) > 2, name
+        assert (want["best_len"][ok[ok >= 256]] > 1).any(), name             # a winner past the first workgroup whose replay takes steps
+    assert dr.scene_reference("foot 300 poses K257")["stats"]["poses_ok"] > 256
+
+
+def test_the_mixed_scene_stages_some_windows_and_walks_the_others():
+    s, want = dr.scene_inputs("mixed walks"), dr.scene_reference("mixed walks")
+    assert sr.stage_cells(s["c"]) == 4056 and len(s["poses"]) == 1281 and len(s["movers"]) >= 8
+    assert want["stats"]["windows_staged"] > 0 and want["stats"]["windows_global"] > 0
+    assert dr.not_vacuous(want, s["c"]) == (True, True, True)
+    for q in (sr.MIXED_EDGE_STAGED, sr.MIXED_EDGE_WALKED, sr.MIXED_CORNER, sr.MIXED_CENTRAL):
+        assert want["pose_status"][q] == 0, q
+
+
+# ---- touching discs: the strict comparisons, by hand ---------------------------------------------------------------------------------
+def fast(want):
+    """(cand_free, cand_hit, cand_min_gap) of a hand-made scene's fast candidate (v = 512)"""
+    return tuple(int(want[nm][0, 1]) for nm in ("cand_free", "cand_hit", "cand_min_gap"))
+
+
+def test_a_touching_disc_does_not_hit_and_its_gap_is_zero():
+    """D2 == R_s^2 is free (step A.2 asks D2 >= R_s^2) with gap isqrt(D2) - R_s = 0; the step after it lies inside.  The fast candidate is at
+    (x0 + 512 s, y0) at step s, (x0, y0) = (10752, 10752); need = 2 + 512 / 128 = 6 of 12 steps"""
+    x0 = y0 = dr.X0
+    assert x0 == 10752
+    # static: the disc of radius 1000 at x0 + 4072: |dx| = 4072 - 512 s: 1000 at s = 6, 488 at s = 7
+    assert 4072 - 512 * 6 == 1000 and 4072 - 512 * 7 == 488 < 1000
+    want = dr.scene_reference("touch static")
+    assert fast(want) == (6, 0, 0) and want["cand_min_gap"][0, 0] == 4072 - 1000 == 3072 and want["cand_hit"][0, 0] == -1
+    assert want["cand_score"][0, 1] == (10 * 4096) >> 10 == 40 and want["best"].tolist() == [1] and want["best_min_gap"].tolist() == [0]
+    # growing: R_s = 100 s at x0 + 3060: |dx| = 3060 - 512 s: 500 = R_5 at s = 5; 12 < R_6 = 600 at s = 6
+    assert 3060 - 512 * 5 == 500 and abs(3060 - 512 * 6) == 12 < 600 and 3060 - 512 * 4 == 1012 > 400
+    want = dr.scene_reference("touch growing")
+    assert fast(want) == (5, 0, 0) and want["cand_min_gap"][0, 0] == 3060 - 100 * 12
+    # off the axis: (dx, dy) = (2136 - 512 s, 800): (600, 800) at s = 3, 600^2 + 800^2 = 1000^2; (88, 800) at s = 4
+    assert (2136 - 512 * 3, 600 ** 2 + 800 ** 2) == (600, 1000 ** 2) and 88 ** 2 + 800 ** 2 < 1000 ** 2 < 1112 ** 2 + 800 ** 2
+    want = dr.scene_reference("touch pythagorean")
+    assert fast(want) == (3, 0, 0)
+    # a quarter turn: the static case along +y
+    want = dr.scene_reference("touch quarter turn")
+    assert fast(want) == (6, 0, 0) and want["cand_min_gap"][0, 0] == 3072
+    assert want["cand_end"][0, 1].tolist() == [x0, y0 + 512 * 6, 16384]
+    # a mover that walks: X_s = x0 + 3772 - 256 s, the robot at x0 + 512 s: |dx| = 3772 - 768 s: 1468 at s = 3, 700 = R at s = 4, 68 at s = 5.
+    # The standing candidate sees |dx| = 3772 - 256 s: 700 at s = 12, the last step: all 12 steps free, gap 0
+    assert 3772 - 768 * 4 == 700 and abs(3772 - 768 * 5) == 68 < 700 and 3772 - 256 * 12 == 700
+    want = dr.scene_reference("touch moving")
+    assert fast(want) == (4, 0, 0)
+    assert (int(want["cand_free"][0, 0]), int(want["cand_hit"][0, 0]), int(want["cand_min_gap"][0, 0])) == (12, -1, 0)
+    assert want["best"].tolist() == [0] and want["best_min_gap"].tolist() == [0] and want["stats"]["hit_movers"] == 1
+
+
+def test_the_static_test_comes_first_and_a_refused_steps_gaps_do_not_count():
+    # the wall cell (13, 10) begins at x = 13312 = x0 + 512 * 5; the disc of radius 800 at its centre 13824: |dx| = 1024 at s = 4 (free,
+    # gap 224), 512 at s = 5: inside the disc AND in the wall: the rollout ended on the static test, cand_hit is -1
+    assert 13 * 1024 == dr.X0 + 512 * 5 and 13824 - (dr.X0 + 512 * 4) == 1024 and 13824 - (dr.X0 + 512 * 5) == 512 < 800
+    s, want = dr.scene_inputs("wall inside a disc"), dr.scene_reference("wall inside a disc")
+    assert s["state"][10, 13] == 100 and fast(want) == (4, -1, 224) and want["stats"]["hit_movers"] == 0
+    assert want["stats"]["collided"] == 1
+    # mover 1 (radius 1000 at x0 + 3972) refuses step 6 (|dx| = 900) after a gap of 1412 - 1000 at step 5; mover 0 (radius 1000 at
+    # (x0 + 3072, y0 + 1300)) is at distance 1300 at the refused step 6 and at isqrt(512^2 + 1300^2) = 1397 at step 5: the gap is 397
+    assert 3972 - 512 * 6 == 900 < 1000 < 3972 - 512 * 5 == 1412 and 1397 ** 2 <= 512 ** 2 + 1300 ** 2 < 1398 ** 2
+    want = dr.scene_reference("gap of a refused step")
+    assert fast(want) == (5, 1, 397)
+
+
+# ---- what the scenes are sensitive to ------------------------------------------------------------------------------------------------
+# the references of the scenes from before the wrong rules were added to the restatement: sha256 of every output's bytes and the stats
+DIGESTS = {"1x1": "4ee5cbb739ffbe73", "1x70 K297 one mover": "99b4d213c8b99c39", "37x53 K512 64 movers 70 poses": "512d41a123120328",
+           "64x65 K297 T256": "743fdddea12f54c6", "97x33 K512 T1": "4eaad3ea30eeb66e", "r 0 never hits": "24d8157c34df22ca",
+           "two movers one step": "4f51a47ad069b854", "mover on the start": "c9cac9b9eb542161", "int64 path": "d68e283b4552c9ac",
+           "grow 4096": "e1f79390230f6d1b", "cap 0": "772544cf20db27d9", "foot 37x53": "9dc1b33bfbc4c1f0"}
+# wrong rule -> (a scene of the GPU suite, an output of its reference that the rule changes)
+SENSITIVE = {"hit_le": ("touch static", "cand_free"), "movers_first": ("wall inside a disc", "cand_hit"), "last_hit": ("two movers one step", "cand_hit"),
+             "gap_uncommitted": ("gap of a refused step", "cand_min_gap"), "zero_based": ("touch moving", "cand_min_gap"),
+             "start_tested": ("mover on the start", "cand_free")}
+
+
+def test_the_default_rule_computes_what_it_computed():
+    import hashlib
+    import json
+    for name, told in DIGESTS.items():
+        want = dr.scene_reference(name)
+        h = hashlib.sha256()
+        for nm in dr.OUTPUTS:
+            h.update(np.ascontiguousarray(want[nm]).tobytes())
+        h.update(json.dumps(want["stats"], sort_keys=True).encode())
+        assert h.hexdigest()[:16] == told, name
+
+
+@pytest.mark.parametrize("rule", dr.WRONG_RULES)
+def test_every_wrong_rule_changes_an_output_of_a_scene_the_gpu_suite_runs(rule):
+    """a condition on the scenes: a kernel that followed the wrong rule would differ from the reference on the named scene's output"""
+    assert set(SENSITIVE) == set(dr.WRONG_RULES)
+    name, output = SENSITIVE[rule]
+    assert name in dr.DISC_CASES + dr.FOOT_CASES + dr.HAND_CASES
+    right, wrong = dr.scene_reference(name), dr.scene_reference(name, _wrong=rule)
+    assert (right[output] != wrong[output]).any(), (rule, name, output)
+    if rule == "hit_le":                                                  # every touching scene tells <= from <
+        for name in dr.HAND_CASES[:5]:
+            assert (dr.scene_reference(name)["cand_free"] != dr.scene_reference(name, _wrong=rule)["cand_free"]).any(), name
+    if rule == "movers_first":
+        assert wrong["cand_hit"][0, 1] == 0 and right["cand_hit"][0, 1] == -1 and (right["cand_free"] == wrong["cand_free"]).all()
+    if rule == "gap_uncommitted":
+        assert wrong["cand_min_gap"][0, 1] == 1300 - 1000
+
+
 # ---- the tracker -------------------------------------------------------------------------------------------------------------------------
 def test_the_tracker_by_hand():
     out = dr.tracker_case(0)
@@ -367,6 +488,26 @@ def test_the_blob_scenes_show_what_they_are_there_to_show(cam):
         assert (cols["blobs"][:, 4] ** 2 >= cols["blobs"][:, 5] ** 2 + cols["blobs"][:, 6] ** 2).all()
         first = s["label"][ch // 2] == cols["blobs"][np.argmin(cols["blobs"][:, 0]), 0]              # the stripe of the smallest label starts at
         assert first[0] and (cw < 160 or first[:20].all())                                          # column 0: 20 wide at 160, across a 16-pixel tile border
+
+
+def test_the_blocks_share_labels_between_tiles_and_all_are_reported():
+    """the "blocks" kind: several labels of several pixels each in a tile, most of them in two tiles or four, and every one written"""
+    for cw, ch in dr.BLOCK_CAMERAS:
+        assert cw % 16 and ch % 16
+        s, _, _, want = dr.blob_reference(cw, ch, "blocks", "f32")
+        st, n = want["stats"], want["blobs"][:, 1]
+        assert 20 <= st["labels_seen"] <= 64 and st["blobs_written"] == st["labels_seen"] == st["blobs_kept"], (cw, ch, st)
+        assert n.min() >= 1 and n.max() == 15 and len(set(n.tolist())) >= 4, n
+        assert st["pixels_member"] == cw * ch - 3                          # the three labels that are no pixel index
+        odd = s["label"][(s["label"] < 0) | (s["label"] >= cw * ch)]
+        assert sorted(odd.tolist()) == [-(1 << 31), cw * ch, (1 << 31) - 1] and (s["mask"] != 0).all()
+    s, _, _, want = dr.blob_reference(40, 24, "blocks", "f32")
+    shared, crowded = dr.blob_tiles(s)
+    assert shared >= 10 and crowded >= 4, (shared, crowded)
+    # one of the three pixels would contribute if its label were a pixel index: the member test decides it
+    as_member = np.where((s["label"] < 0) | (s["label"] >= 40 * 24), 0, s["label"]).astype(np.int32)
+    more = dr.blobs(s["depth"], s["mask"], as_member, s["grid_pose"], s["cam_pose"], s["c"], 1, 64)
+    assert more["stats"]["points_in_band"] > want["stats"]["points_in_band"]
 
 
 # ---- replay.py's options -------------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,11 @@
 ssf_navdyn_foot_rollouts and ssf_navdyn_blobs equals the restatement (tests/navdyn_ref.py) with ==, at the smallest shapes at which
 the kernels can go wrong (one cell, one row, grids that are no multiple of anything, K = 297 and 512, 1 and 256 steps, 1 and 70
 poses, 0 / 1 / 64 movers, the largest operands; cameras of 1 x 1, 17 x 13 and 160 x 128), through device pointers from the motion
-detector and the overlay to the command, and with the older calls beside them through the same handle."""
+detector and the overlay to the command, and with the older calls beside them through the same handle.
+The edges: the footprint at B = 1, 4 and 32, at 256 steps, with 64 movers, on one cell and through device pointers; 300 poses (two
+pick workgroups) for the disc and the footprint; one launch that stages some windows and walks the others; discs that touch
+(D2 == R_s^2: free, gap 0), a wall inside a disc (the static test answers), a refused step's gaps; blocks of labels that share tiles
+(cameras of 40 x 24 and 35 x 19), a large frame after a small one on one handle; a device mover list outside the header's bounds."""
 import os
 import re
 import subprocess
@@ -66,19 +70,22 @@ def steer(f, name, **more):
     c = s["c"]
     cost, targets = (s["cost"] if c["cost_weight"] else None), (s["targets"] if c["target_weight"] else None)
     if name in dr.FOOT_CASES:
-        return f.nav_dyn_foot_steer(s["free_mask"], s["dist2"], s["poses"], dr.FOOT_B, movers=s["movers"], cost=cost, targets=targets, outputs=dr.OUTPUTS,
+        return f.nav_dyn_foot_steer(s["free_mask"], s["dist2"], s["poses"], s["B"], movers=s["movers"], cost=cost, targets=targets, outputs=dr.OUTPUTS,
                                     **dict(call_kw(c), **more))
     return f.nav_dyn_steer(s["state"], s["dist2"], s["poses"], movers=s["movers"], cost=cost, targets=targets, outputs=dr.OUTPUTS, **dict(call_kw(c), **more))
 
 
 # ---- the rollouts ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", dr.DISC_CASES + dr.FOOT_CASES)
+@pytest.mark.parametrize("name", dr.DISC_CASES + dr.FOOT_CASES + dr.HAND_CASES)
 def test_the_rollouts_with_movers(name, fusion):
     want, c = dr.scene_reference(name), dr.scene_inputs(name)["c"]
     if name in dr.GUARDED:                                               # (on the restatement alone: the case is not vacuous)
         assert dr.not_vacuous(want, c) == (True, True, True), name
+    if c["n_poses"] > 256:                                               # winners on both sides of the first pick workgroup, of several gaps
+        ok = np.flatnonzero(want["pose_status"] == 0)
+        assert (ok < 256).any() and (ok >= 256).any() and len(np.unique(want["best_min_gap"][ok[ok >= 256]])) > 2, name
     same(steer(fusion, name), want, name)
-    if name in ("37x53 K512 64 movers 70 poses", "64x65 K297 T256"):     # the grid walked in place of the staged window: the same outputs
+    if name in ("37x53 K512 64 movers 70 poses", "64x65 K297 T256", "300 poses K64", "touch static"):     # the grid walked in place of the staged window: the same outputs
         same(steer(fusion, name, walk=1), want, name + " walk", stats=dr.STATS)
 
 
@@ -137,6 +144,93 @@ def test_one_output_alone_guard_bytes_and_two_calls_giving_the_same_bytes(fusion
         assert raws[0].tobytes() == raws[1].tobytes(), nm
 
 
+def on_device(s, keys, dev):
+    import torch
+    return {k: torch.from_numpy(s[k].view(np.int32) if s[k].dtype == np.uint32 else s[k]).to(dev) for k in keys}
+
+
+def test_one_footprint_output_alone_guard_bytes_and_two_calls_giving_the_same_bytes(fusion):
+    """the footprint's rollouts through device pointers (nav_dyn_steer_device with n_headings), B = 32, 64 movers: the twin of the
+    test above"""
+    import torch
+    dev = torch.device("cuda")
+    name = "foot B32 K512 64 movers"
+    s, want = dr.scene_inputs(name), dr.scene_reference(name)
+    c = s["c"]
+    gw, gh, n, K = c["width"], c["height"], c["n_poses"], c["n_v"] * c["n_w"]
+    assert s["B"] == 32 and c["cost_weight"] > 0 and c["target_weight"] > 0
+    d = on_device(s, ("free_mask", "dist2", "cost", "poses", "targets", "movers"), dev)
+    G, SENT = 256, 0x5A
+    for nm, words in (("cand_hit", n * K), ("cand_min_gap", n * K), ("best_min_gap", n)):
+        raws = []
+        for _ in range(2):
+            buf = torch.full((2 * G + 4 * words + 3,), SENT, dtype=torch.uint8, device=dev)
+            st = fusion.nav_dyn_steer_device(d["free_mask"], d["dist2"], gw, gh, d["poses"], n, movers=d["movers"], n_movers=len(s["movers"]),
+                                             n_headings=s["B"], cost=d["cost"], targets=d["targets"], **dict(call_kw(c), **{nm: buf.data_ptr() + G}))
+            raws.append(buf.cpu().numpy())
+            assert {k: st[k] for k in dr.STATS + sr.INFORMATIVE} == {k: want["stats"][k] for k in dr.STATS + sr.INFORMATIVE}
+        raw = raws[0]
+        assert (raw[G:G + 4 * words].view(np.int32).reshape(want[nm].shape) == want[nm]).all(), nm
+        assert (raw[:G] == SENT).all() and (raw[G + 4 * words:] == SENT).all(), nm
+        assert raws[0].tobytes() == raws[1].tobytes(), nm
+
+
+def test_a_launch_with_movers_that_stages_some_windows_and_walks_the_others(fusion):
+    """navsteer_ref.mixed_scene among ten movers: 1281 workgroups, of which one launch stages the windows of up to 4056 cells in LDS and
+    walks the others in the grid; both kinds test their steps against the list in LDS"""
+    name = "mixed walks"
+    s, want = dr.scene_inputs(name), dr.scene_reference(name)
+    assert want["stats"]["windows_staged"] > 0 and want["stats"]["windows_global"] > 0 and len(s["movers"]) >= 8     # (on the restatement alone)
+    assert want["stats"]["hit_movers"] > 0
+    got = steer(fusion, name)
+    same(got, want, name)
+    assert got["stats"]["windows_staged"] == want["stats"]["windows_staged"] and got["stats"]["windows_global"] == want["stats"]["windows_global"]
+    walked = steer(fusion, name, walk=1)
+    same(walked, want, name + " walk", stats=dr.STATS)
+    assert walked["stats"]["windows_staged"] == 0
+    assert walked["stats"]["windows_global"] == want["stats"]["windows_staged"] + want["stats"]["windows_global"]
+
+
+def test_a_device_mover_list_outside_the_bounds_touches_nothing_else(dyn_lib):
+    """a device list is not read by the host (ssf_navdyn.h: "change what is computed, never what is touched"): entries at INT32_MIN,
+    INT32_MAX and 1 << 30 in every field, every output inside sentinels.  Only what the header promises is asserted: no gap, no score"""
+    import torch
+    dev = torch.device("cuda")
+    f = handle(dyn_lib)
+    name = "37x53 K512 64 movers 70 poses"
+    s = dr.scene_inputs(name)
+    c = s["c"]
+    gw, gh, n, K, T = c["width"], c["height"], c["n_poses"], c["n_v"] * c["n_w"], c["n_steps"]
+    bad = s["movers"].copy()
+    odd = (sr.I32_MIN, sr.I32_MAX, 1 << 30)
+    for k, val in enumerate(odd):
+        for field in range(6):
+            bad[6 * k + field, field] = val                               # one field out of range, the others as they were
+        bad[18 + k] = val                                                 # all six
+    bad[21] = (sr.I32_MIN, sr.I32_MAX, sr.I32_MAX, sr.I32_MIN, 1 << 30, sr.I32_MAX)
+    assert len(bad) == dr.MAX_MOVERS and not dr.movers_ok(bad) and dr.movers_ok(bad[22:])
+    d = on_device(dict(s, movers=bad), ("state", "dist2", "cost", "poses", "targets", "movers"), dev)
+    known = binding.NAVSTEER_OUTPUTS + binding.NAVDYN_OUTPUTS
+    G, SENT = 256, 0x5A
+    bufs, ptrs = {}, {}
+    for nm, dt, kind, tail in known:
+        nbytes = int(np.prod(binding.Fusion._navsteer_shape(kind, tail, n, K, T))) * np.dtype(dt).itemsize
+        bufs[nm] = (torch.full((2 * G + nbytes,), SENT, dtype=torch.uint8, device=dev), nbytes)
+        ptrs[nm] = bufs[nm][0].data_ptr() + G
+    st = f.nav_dyn_steer_device(d["state"], d["dist2"], gw, gh, d["poses"], n, movers=d["movers"], n_movers=len(bad), cost=d["cost"], targets=d["targets"],
+                                **dict(call_kw(c), **ptrs))              # the call returns
+    got = {}
+    for nm, dt, kind, tail in known:
+        raw, nbytes = bufs[nm][0].cpu().numpy(), bufs[nm][1]
+        assert (raw[:G] == SENT).all() and (raw[G + nbytes:] == SENT).all(), nm
+        got[nm] = raw[G:G + nbytes].view(dt)
+    assert ((got["cand_free"] >= 0) & (got["cand_free"] <= T)).all()
+    assert ((got["cand_hit"] >= -1) & (got["cand_hit"] < len(bad))).all()
+    assert st["hit_movers"] == int((got["cand_hit"] >= 0).sum()) and st["collided"] == int((got["cand_free"] < T).sum())
+    same(steer(f, name), dr.scene_reference(name), "after the list out of bounds")
+    f.close()
+
+
 # ---- the blobs -------------------------------------------------------------------------------------------------------------------------
 def blob_kw(s):
     c = s["c"]
@@ -144,19 +238,40 @@ def blob_kw(s):
                 z_max=c["z_max"], min_points=s["min_points"], max_blobs=s["max_blobs"])
 
 
-@pytest.mark.parametrize("fmt", ["f32", "u16"])
-@pytest.mark.parametrize("kind", dr.BLOB_KINDS)
-@pytest.mark.parametrize("cam", dr.BLOB_CAMERAS)
+def same_blobs(got, want, what):
+    assert got["stats"] == want["stats"], (what, got["stats"], want["stats"])
+    assert got["blobs"].dtype == np.int32 and got["blobs"].shape == want["blobs"].shape and (got["blobs"] == want["blobs"]).all(), (
+        what, got["blobs"][:4].tolist(), want["blobs"][:4].tolist())
+
+
+# every kind at every camera of BLOB_CAMERAS (cam0 .. cam2), and the "blocks" at theirs (cam3, cam4)
+BLOB_CASES = [(k, cam, kind) for kind in dr.BLOB_KINDS for k, cam in enumerate(dr.BLOB_CAMERAS)] + \
+             [(len(dr.BLOB_CAMERAS) + k, cam, "blocks") for k, cam in enumerate(dr.BLOCK_CAMERAS)]
+
+
+@pytest.mark.parametrize("cam,kind,fmt", [pytest.param(cam, kind, fmt, id="cam%d-%s-%s" % (k, kind, fmt)) for fmt in ("f32", "u16") for k, cam, kind in BLOB_CASES])
 def test_the_blobs(cam, kind, fmt, dyn_lib):
     s, img, scale, want = dr.blob_reference(cam[0], cam[1], kind, fmt)
+    if kind == "blocks":                                                 # (on the restatement alone: every label is written)
+        assert 20 <= want["stats"]["labels_seen"] == want["stats"]["blobs_written"] <= 64
     f = handle(dyn_lib)
     if fmt == "u16":
         f.set_input_format("rgb8", "u16", scale)
     for direct in (0, 1):
-        got = f.nav_dyn_blobs(img, s["mask"], s["label"], direct=direct, **blob_kw(s))
-        assert got["stats"] == want["stats"], (cam, kind, fmt, direct, got["stats"], want["stats"])
-        assert got["blobs"].dtype == np.int32 and got["blobs"].shape == want["blobs"].shape and (got["blobs"] == want["blobs"]).all(), (
-            cam, kind, fmt, direct, got["blobs"][:4].tolist(), want["blobs"][:4].tolist())
+        same_blobs(f.nav_dyn_blobs(img, s["mask"], s["label"], direct=direct, **blob_kw(s)), want, (cam, kind, fmt, direct))
+    f.close()
+
+
+def test_the_blobs_after_a_smaller_frame_on_the_same_handle(dyn_lib):
+    """160 x 128, then 17 x 13, then 160 x 128 again with other labels, on one handle: the working buffers (the per-pixel points, the
+    slots, the records) are those of the first call, and a smaller frame leaves most of them as the larger one left them"""
+    f = handle(dyn_lib)
+    for direct in (0, 1):
+        for cam, kind in (((160, 128), "blocks"), ((17, 13), "blocks"), ((160, 128), "columns"), ((17, 13), "many"), ((160, 128), "many")):
+            s, img, scale, want = dr.blob_reference(cam[0], cam[1], kind, "f32")
+            same_blobs(f.nav_dyn_blobs(img, s["mask"], s["label"], direct=direct, **blob_kw(s)), want, (cam, kind, direct))
+    s, _, _, want = dr.blob_reference(160, 128, "blocks", "f32")
+    assert want["stats"]["labels_seen"] > 64 == want["stats"]["blobs_written"] and (want["blobs"][:, 1] == 15).all()
     f.close()
 
 
