@@ -4,8 +4,9 @@
 // ssf_navgrid_carve runs ssf_navgrid_build's own prep, fill and tile (ssf_navgrid.hpp), then per chunk of at most 2^20 rays
 //   * rays     k_navcarve_rays: one thread per ray: the pixel's direction through the view's pose, (O, D) in the map frame;
 //   * the hit  ssf_raycast itself, on the device buffers, with the identity pose (raycast_* kernels; its resident index is reused);
-//   * march    k_navcarve_march: one ray per wave, its samples over the lanes; the entries of a cell's band are counted into `seen`
-//              with integer atomics (order-free), merged in registers where neighbouring rays share their first cells;
+//   * march    k_navcarve_march: one ray per wave, its samples over the lanes (nav_march_ray, ssf_navgrid.hpp, shared with the live
+//              layer); the entries of a cell's band are counted into `seen` with integer atomics (order-free), merged in registers
+//              where neighbouring rays share their first cells;
 // and the cells kernel's carving sibling, with `seen` as one more input of the state.  Its working set is NavCarveWs (ssf_handle.hpp).
 //
 // This file is NOT one of the product library's objects: libssf_hip.so's exported symbols stay what they were.  It is linked,
@@ -44,36 +45,20 @@ __global__ __launch_bounds__(256) void k_navcarve_rays(NavCam cam, const float* 
     }
 }
 
-// the cell whose band sample m of a ray is accepted in (steps 5), or -1
-struct NavRay { float O[3], D[3]; };
-__device__ __forceinline__ int navcarve_cell(const NavGrid& G, const NavRay& r, int m) {
-    const float tm = (float)m * G.step;
-    const float dx = (r.O[0] + tm * r.D[0]) - G.t[0], dy = (r.O[1] + tm * r.D[1]) - G.t[1], dz = (r.O[2] + tm * r.D[2]) - G.t[2];
-    const float* R = G.R;
-    const float Cx = (R[0] * dx + R[3] * dy) + R[6] * dz, Cy = (R[1] * dx + R[4] * dy) + R[7] * dz, z = (R[2] * dx + R[5] * dy) + R[8] * dz;
-    const float gx = Cx / G.res, gy = Cy / G.res;
-    if (!(gx >= 0.0f && gx < G.fW && gy >= 0.0f && gy < G.fH)) return -1;
-    if (!(z > G.floor_max && z <= G.zmax)) return -1;
-    return (int)gy * G.W + (int)gx;
-}
-// march: ONE RAY PER WAVE, like k_raycast_march; a wave takes NC_RUN consecutive rays (neighbouring pixels of one view), its
-// lanes the samples m = lane, lane + 64, ...  The cell of sample m - 1 comes from the neighbouring lane (the same formula, so
-// the same bits).  Only entries reach `seen`, with an integer atomicAdd.  Neighbouring rays start in the same cell and stay
-// together for their first cells, and all of that would land on a few addresses: what a lane would add for sample m < 64 of
-// consecutive rays to one cell is merged in the lane's registers and issued as one atomic when the cell changes.
+// march: ONE RAY PER WAVE, like k_raycast_march; a wave takes NC_RUN consecutive rays (neighbouring pixels of one view) through
+// nav_march_ray (ssf_navgrid.hpp: steps 5 and 6).  The counters go out with per-wave atomics from lane 0.
 enum { NC_RUN = 16 };
 __global__ __launch_bounds__(256) void k_navcarve_march(NavGrid G, int n, const float* __restrict__ rays, const float* __restrict__ tt,
                                                         const int32_t* __restrict__ index, float margin, float tmax, int carve_misses,
                                                         uint32_t* __restrict__ seen, unsigned long long* __restrict__ stats) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    const int ln = lane();
     const long long first = (long long)wave * NC_RUN;
     const int r0 = (int)min(first, (long long)n), r1 = (int)min(first + NC_RUN, (long long)n);
     unsigned long long n_carving = 0, n_samples = 0, n_entries = 0, n_atomics = 0;       // the first two: the same in every lane
     int pend_cell = -1; uint32_t pend_n = 0u;
     for (int ray = r0; ray < r1; ray++) {
         const float* in = rays + 6 * (size_t)ray;
-        NavRay r;
+        NavMarchRay r;
 #pragma unroll
         for (int k = 0; k < 3; k++) { r.O[k] = in[k]; r.D[k] = in[3 + k]; }
         const bool valid = finite3(r.O[0], r.O[1], r.O[2]) && finite3(r.D[0], r.D[1], r.D[2]) && !(r.D[0] == 0.0f && r.D[1] == 0.0f && r.D[2] == 0.0f);
@@ -83,28 +68,11 @@ __global__ __launch_bounds__(256) void k_navcarve_march(NavGrid G, int n, const 
         const int M = t_end >= 0.0f ? (int)floorf(t_end / G.step) : -1;
         if (M < 0) continue;                                          // (wave-uniform)
         n_carving++; n_samples += (unsigned long long)(M + 1);
-        int carry = -1;                                               // the cell of the sample before this round's first
-        for (int base = 0; base <= M; base += 64) {
-            const int m = base + ln;
-            const int c = m <= M ? navcarve_cell(G, r, m) : -1;
-            int prev = __shfl_up(c, 1, 64);
-            if (ln == 0) prev = carry;
-            carry = __shfl(c, 63, 64);
-            if (c >= 0 && c != prev) {
-                n_entries++;
-                if (base == 0) {
-                    if (c == pend_cell) pend_n++;
-                    else {
-                        if (pend_n) { atomicAdd(&seen[pend_cell], pend_n); n_atomics++; }
-                        pend_cell = c; pend_n = 1u;
-                    }
-                } else { atomicAdd(&seen[c], 1u); n_atomics++; }
-            }
-        }
+        nav_march_ray(G, r, M, seen, pend_cell, pend_n, n_entries, n_atomics);
     }
     if (pend_n) { atomicAdd(&seen[pend_cell], pend_n); n_atomics++; }
     n_entries = wave_sum(n_entries); n_atomics = wave_sum(n_atomics);
-    if (ln == 0) {
+    if (lane() == 0) {
         if (n_carving) atomicAdd(&stats[NC_CARVING], n_carving);
         if (n_samples) atomicAdd(&stats[NC_SAMPLES], n_samples);
         if (n_entries) atomicAdd(&stats[NC_ENTRIES], n_entries);

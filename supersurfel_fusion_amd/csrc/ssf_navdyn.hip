@@ -158,7 +158,6 @@ template <int DF>
 __global__ __launch_bounds__(256) void k_navdyn_blob_seen(NavGrid G, NavLiveCam cam, const void* __restrict__ depth, double scale,
                                                           const uint8_t* __restrict__ mask, const int32_t* __restrict__ label, int2* __restrict__ pt,
                                                           int32_t* __restrict__ slot, unsigned long long* __restrict__ stats) {
-    __shared__ unsigned long long red[3][4];
     const int ntx = (cam.W + NB_TW - 1) / NB_TW;
     const int t = threadIdx.x;
     const int u = (int)(blockIdx.x % ntx) * NB_TW + (t & (NB_TW - 1)), v = (int)(blockIdx.x / ntx) * NB_TH + (t >> 4);
@@ -174,20 +173,13 @@ __global__ __launch_bounds__(256) void k_navdyn_blob_seen(NavGrid G, NavLiveCam 
             if (valid) {
                 float Sx, Sy, Sz, gx, gy;
                 navlive_pixel_point(cam, u, v, d, Sx, Sy, Sz);
-                band = navlive_grid_point(G, Sx, Sy, Sz, gx, gy);
+                band = nav_grid_point(G, Sx, Sy, Sz, gx, gy);
                 if (band) { q = make_int2((int)(gx * 1024.0f), (int)(gy * 1024.0f)); slot[L] = 1; }
             }
         }
         pt[p] = q;
     }
-    member = wave_sum(member); valid = wave_sum(valid); band = wave_sum(band);
-    const int wv = t >> 6;
-    if (lane() == 0) { red[0][wv] = member; red[1][wv] = valid; red[2][wv] = band; }
-    __syncthreads();
-    if (t < 3) {
-        const unsigned long long sum = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
-        if (sum) atomicAdd(&stats[NB_MEMBER + t], sum);
-    }
+    block_sums({member, valid, band}, stats, NB_MEMBER);
 }
 
 // one thread per label value: a marked label takes the next slot (slot[L] = slot + 1) and clears its record
@@ -343,7 +335,7 @@ int ssf_navdyn_foot_rollouts(ssf_handle* h, const ssf_navsteer_params* p, const 
                              const int32_t* dist2, const uint32_t* cost, const int32_t* poses, const int32_t* targets, const int32_t* movers,
                              const ssf_navsteer_out* out, const ssf_navdyn_out* dout, ssf_navsteer_stats* stats, ssf_navdyn_stats* dstats) {
     if (!h || !p) return SSF_ERR_INVALID_ARG;
-    const int lg = navfoot_log2(n_headings);
+    const int lg = nav_log2_bins(n_headings);
     if (lg < 0) { h->err = "ssf_navdyn_foot_rollouts: n_headings must be 1, 2, 4, 8, 16 or 32"; return SSF_ERR_INVALID_ARG; }
     NavSteerMovers mv{dp, movers, dout, dstats, nullptr, ssf_navdyn_out{}};
     NavDynFootRun run{h, &mv, n_headings, 16 - lg};

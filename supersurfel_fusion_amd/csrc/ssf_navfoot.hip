@@ -42,7 +42,6 @@ __global__ __launch_bounds__(256) void k_navfoot_layers(int W, int H, int allow_
                                                         const unsigned long long* __restrict__ masks, const uint32_t* __restrict__ row_bins,
                                                         uint32_t* __restrict__ mask, uint8_t* __restrict__ n_free, unsigned long long* __restrict__ stats) {
     __shared__ unsigned long long s_row[NF_SIDE][2];                  // the window's bit rows
-    __shared__ unsigned long long red[NF_STATS][4];
     const int t = threadIdx.x, wv = t >> 6, ln = t & 63;
     const int side = 32 + 2 * reach, nrow = 2 * reach + 1;
     const int gx0 = (int)blockIdx.x * 32 - reach, gy0 = (int)blockIdx.y * 32 - reach;
@@ -89,13 +88,7 @@ __global__ __launch_bounds__(256) void k_navfoot_layers(int W, int H, int allow_
         if (n_free) n_free[p] = (uint8_t)__popc(m);
         n_clear += own; n_all += m == all; n_some += m != 0u && m != all; n_none += m == 0u;
     }
-    n_clear = wave_sum(n_clear); n_all = wave_sum(n_all); n_some = wave_sum(n_some); n_none = wave_sum(n_none);
-    if (lane() == 0) { red[NF_CLEAR][wv] = n_clear; red[NF_ALL][wv] = n_all; red[NF_SOME][wv] = n_some; red[NF_NONE][wv] = n_none; }
-    __syncthreads();
-    if (t < NF_STATS) {
-        const unsigned long long sum = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
-        if (sum) atomicAdd(&stats[t], sum);
-    }
+    block_sums({n_clear, n_all, n_some, n_none}, stats, NF_CLEAR);
 }
 
 // ---- pack: one thread per cell (step 3's traversable, folded) --------------------------------------------------------------------------
@@ -136,7 +129,7 @@ const char* navfoot_spans(int front, int back, int left, int right, int pad, int
     for (int k = 0; k < 4; k++)
         if (sides[k] < 0 || sides[k] > SSF_NAVFOOT_MAX_SIDE) return "front, back, left and right must be 0..24576";
     if (pad < 0 || pad > SSF_NAVFOOT_MAX_PAD) return "pad must be 0..4096";
-    if (navfoot_log2(B) < 0) return "n_headings must be 1, 2, 4, 8, 16 or 32";
+    if (nav_log2_bins(B) < 0) return "n_headings must be 1, 2, 4, 8, 16 or 32";
     const NavSteerDirs& dirs = navsteer_dirs();
     const long long u_lo = -(long long)(back + pad) * 16384, u_hi = (long long)(front + pad) * 16384;
     const long long v_lo = -(long long)(right + pad) * 16384, v_hi = (long long)(left + pad) * 16384;
@@ -299,7 +292,7 @@ int ssf_navfoot_layers(ssf_handle* h, const ssf_navfoot_params* p, const int8_t*
 int ssf_navfoot_rollouts(ssf_handle* h, const ssf_navsteer_params* p, int n_headings, const uint32_t* free_mask, const int32_t* dist2,
                          const uint32_t* cost, const int32_t* poses, const int32_t* targets, const ssf_navsteer_out* out, ssf_navsteer_stats* stats) {
     if (!h || !p) return SSF_ERR_INVALID_ARG;
-    const int lg = navfoot_log2(n_headings);
+    const int lg = nav_log2_bins(n_headings);
     if (lg < 0) { h->err = "ssf_navfoot_rollouts: n_headings must be 1, 2, 4, 8, 16 or 32"; return SSF_ERR_INVALID_ARG; }
     NavFootRun run{h, n_headings, 16 - lg};
     return navsteer_call(h, "ssf_navfoot_rollouts", p, free_mask, 4, "free_mask", dist2, cost, poses, targets, out, stats, run);

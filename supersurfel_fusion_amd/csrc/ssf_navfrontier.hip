@@ -91,14 +91,6 @@ __device__ __forceinline__ void nf_unite(int32_t* parent, int a, int b) {
     }
 }
 
-// the workgroup's sum of v added to *dst (all 256 threads call it; red: four words of LDS that nothing else uses)
-__device__ __forceinline__ void nf_block_add(unsigned long long v, unsigned long long* red, unsigned long long* __restrict__ dst) {
-    v = wave_sum(v);
-    if (lane() == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) { const unsigned long long s = (red[0] + red[1]) + (red[2] + red[3]); if (s) atomicAdd(dst, s); }
-}
-
 // step 1 for a cell inside the grid
 __device__ __forceinline__ bool nf_member(const NavFrontierGrid& G, const NavFrontierRule& r, const int8_t* __restrict__ state,
                                           const int32_t* __restrict__ dist2, int x, int y) {
@@ -115,7 +107,6 @@ __global__ __launch_bounds__(256) void k_navfrontier_label(NavFrontierGrid G, Na
                                                            int32_t* __restrict__ label, unsigned long long* __restrict__ stats) {
     __shared__ int sp[NAV_CELLS];
     __shared__ uint8_t sm[NAV_CELLS];
-    __shared__ unsigned long long red[4];
     const int tx = blockIdx.x % G.ntx, ty = blockIdx.x / G.ntx, x0 = tx * NAV_TILE, y0 = ty * NAV_TILE;
     unsigned long long members = 0;
 #pragma unroll
@@ -146,7 +137,7 @@ __global__ __launch_bounds__(256) void k_navfrontier_label(NavFrontierGrid G, Na
         parent[p] = lr < 0 ? -1 : (int32_t)((size_t)(y0 + lr / NAV_TILE) * G.W + (x0 + lr % NAV_TILE));
         label[p] = lr < 0 ? -1 : (lr == i ? (int32_t)p : -2);
     }
-    nf_block_add(members, red, &stats[NF_MEMBERS]);
+    block_sums({members}, stats, NF_MEMBERS);
 }
 
 // ---- merge: one thread per cell on the high side of a tile border --------------------------------------------------------------------
@@ -276,7 +267,7 @@ __device__ __forceinline__ bool nf_kept(const NavFrontierRule& r, const NavFront
 __global__ __launch_bounds__(256) void k_navfrontier_keep(NavFrontierRule r, int n, const NavFrontierAcc* __restrict__ acc, uint32_t* __restrict__ blocks,
                                                           unsigned long long* __restrict__ stats) {
     __shared__ int part[4];
-    __shared__ unsigned long long red[3][4];
+    __shared__ unsigned long long red[4];
     const int id = blockIdx.x * 256 + threadIdx.x;
     bool kept = false;
     unsigned long long small = 0, unreached = 0, cells = 0;
@@ -286,14 +277,13 @@ __global__ __launch_bounds__(256) void k_navfrontier_keep(NavFrontierRule r, int
     }
     const int nk = block_count256(kept, part);
     if (threadIdx.x == 0) blocks[blockIdx.x] = (uint32_t)nk;
-    nf_block_add(small, red[0], &stats[NF_SMALL]);
-    nf_block_add(unreached, red[1], &stats[NF_UNREACHED]);
+    block_sums({small, unreached}, stats, NF_SMALL);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { const unsigned long long u = __shfl_xor(cells, o, 64); cells = u > cells ? u : cells; }
-    if (lane() == 0) red[2][threadIdx.x >> 6] = cells;
+    if (lane() == 0) red[threadIdx.x >> 6] = cells;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const unsigned long long a = red[2][0] > red[2][1] ? red[2][0] : red[2][1], b = red[2][2] > red[2][3] ? red[2][2] : red[2][3];
+        const unsigned long long a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
         atomicMax(&stats[NF_LARGEST], a > b ? a : b);
     }
 }

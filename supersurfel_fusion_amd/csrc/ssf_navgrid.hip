@@ -58,7 +58,6 @@ __device__ __forceinline__ int nav_lattice_count(int n1, int n2) {
 // y0 | y1 << 16 in cells (empty: x0 = 1 > x1 = 0)
 __global__ __launch_bounds__(256) void k_navgrid_prep(NavView nv, float4* __restrict__ rec, uint2* __restrict__ rbox,
                                                       uint32_t* __restrict__ tcnt, unsigned long long* __restrict__ stats) {
-    __shared__ unsigned long long red[2][4];
     __shared__ uint32_t hist[NAV_HIST];
     const NavGrid& G = nv.grid;
     const int ntiles = G.ntx * G.nty;
@@ -120,15 +119,10 @@ __global__ __launch_bounds__(256) void k_navgrid_prep(NavView nv, float4* __rest
         }
     }
     if ((int)s < nv.model.nslots) rbox[s] = box;
-    used = wave_sum(used); nsamp = wave_sum(nsamp);
-    if (lane() == 0) { red[0][threadIdx.x >> 6] = used; red[1][threadIdx.x >> 6] = nsamp; }
-    __syncthreads();
+    __syncthreads();                                                  // (hist is complete)
     if (use_hist)
         for (int t = threadIdx.x; t < ntiles; t += 256) { const uint32_t c = hist[t]; if (c) atomicAdd(&tcnt[t], c); }
-    if (threadIdx.x < 2) {
-        const unsigned long long sum = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
-        if (sum) atomicAdd(&stats[threadIdx.x == 0 ? NAV_ROWS : NAV_SAMPLES], sum);
-    }
+    block_sums({used, nsamp}, stats, NAV_ROWS);
 }
 
 // ---- fill: the (tile -> slot) lists -----------------------------------------------------------------------------------
@@ -170,7 +164,6 @@ __global__ __launch_bounds__(1024) void k_navgrid_tile(NavGrid G, int split, con
                                                        unsigned long long* __restrict__ stats) {
     __shared__ uint32_t cmin[NAV_CELLS], cmax[NAV_CELLS], cfloor[NAV_CELLS], cobst[NAV_CELLS];
     __shared__ float4 sr[4 * NAV_CHUNK];
-    __shared__ unsigned long long red[16];
     const int t = blockIdx.x / split, part = blockIdx.x - t * split, tx = t % G.ntx, ty = t / G.ntx;
     const int wv = threadIdx.x >> 6;
     const uint32_t beg = toff[t], end = toff[t + 1];
@@ -223,14 +216,7 @@ __global__ __launch_bounds__(1024) void k_navgrid_tile(NavGrid G, int split, con
         if (nfloor) atomicAdd(&acc.nfloor[p], nfloor);
         if (nobst) atomicAdd(&acc.nobst[p], nobst);
     }
-    accepted = wave_sum(accepted);
-    if (lane() == 0) red[wv] = accepted;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long sum = 0;
-        for (int w = 0; w < 16; w++) sum += red[w];
-        if (sum) atomicAdd(&stats[NAV_ACCEPTED], sum);
-    }
+    block_sums<1, 16>({accepted}, stats, NAV_ACCEPTED);
 }
 
 // ---- cells: one thread per cell (the body: ssf_navgrid.hpp) --------------------------------------------------------------------

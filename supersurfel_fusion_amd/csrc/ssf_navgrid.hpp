@@ -1,6 +1,7 @@
 // ssf_navgrid.hpp -- what ssf_navgrid.hip (ssf_navgrid_build, in the product library) shares with ssf_navcarve.hip
-// (ssf_navgrid_carve, include/ssf_navcarve.h): the kernels' view of a grid, the cells kernel's body, and the four parts of a
-// grid call.  Private to the library's own files: nothing here is exported.
+// (ssf_navgrid_carve, include/ssf_navcarve.h) and the live layer (ssf_navlive.hip, ssf_navdyn.hip): the kernels' view of a grid, the
+// cells kernel's body, the cell of a map-frame point and the march of a ray through the grid, and the four parts of a grid call.
+// Private to the library's own files: nothing here is exported.
 #pragma once
 #include "ssf_slots.hpp"
 #include "ssf_handle.hpp"
@@ -34,7 +35,6 @@ struct NavSeen { const uint32_t* seen; int min_seen; uint32_t* out; unsigned lon
 template <bool CARVE>
 __device__ __forceinline__ void navgrid_cells_body(const NavAcc& acc, size_t P, int min_hits, const NavOut& out, unsigned long long* __restrict__ stats,
                                                    const NavSeen& sn) {
-    __shared__ unsigned long long red[CARVE ? 5 : 3][4];
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     unsigned long long nfree = 0, nocc = 0, nunk = 0, nseen = 0, ncarved = 0;
     if (p < P) {
@@ -53,20 +53,58 @@ __device__ __forceinline__ void navgrid_cells_body(const NavAcc& acc, size_t P, 
         if (out.hits) { out.hits[2 * p] = nfloor; out.hits[2 * p + 1] = nobst; }
         if (out.state) out.state[p] = st;
     }
-    nfree = wave_sum(nfree); nocc = wave_sum(nocc); nunk = wave_sum(nunk);
-    if (lane() == 0) { red[0][threadIdx.x >> 6] = nfree; red[1][threadIdx.x >> 6] = nocc; red[2][threadIdx.x >> 6] = nunk; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const unsigned long long sum = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
-        if (sum) atomicAdd(&stats[NAV_FREE + threadIdx.x], sum);
-    }
-    if (CARVE) {
-        nseen = wave_sum(nseen); ncarved = wave_sum(ncarved);
-        if (lane() == 0) { red[3][threadIdx.x >> 6] = nseen; red[4][threadIdx.x >> 6] = ncarved; }
-        __syncthreads();
-        if (threadIdx.x >= 3 && threadIdx.x < 5) {
-            const unsigned long long sum = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
-            if (sum) atomicAdd(&sn.stats[NC_SEEN + (threadIdx.x - 3)], sum);
+    block_sums({nfree, nocc, nunk}, stats, NAV_FREE);
+    if (CARVE) block_sums({nseen, ncarved}, sn.stats, NC_SEEN);
+}
+
+// ---- rays through the grid: the march of the carve (ssf_navcarve.hip) and of the live layer (ssf_navlive.hip) -----------------
+// the map-frame point S in the grid frame (ssf_navgrid.h steps 1 and 4): true iff it lies in the grid and in the band of step 5;
+// (gx, gy): its position in cells
+__device__ __forceinline__ bool nav_grid_point(const NavGrid& G, float Sx, float Sy, float Sz, float& gx, float& gy) {
+    const float dx = Sx - G.t[0], dy = Sy - G.t[1], dz = Sz - G.t[2];
+    const float* R = G.R;
+    const float Cx = (R[0] * dx + R[3] * dy) + R[6] * dz, Cy = (R[1] * dx + R[4] * dy) + R[7] * dz, z = (R[2] * dx + R[5] * dy) + R[8] * dz;
+    gx = Cx / G.res; gy = Cy / G.res;
+    if (!(gx >= 0.0f && gx < G.fW && gy >= 0.0f && gy < G.fH)) return false;
+    return z > G.floor_max && z <= G.zmax;
+}
+// the cell in whose band the map-frame point S lies, or -1
+__device__ __forceinline__ int nav_cell(const NavGrid& G, float Sx, float Sy, float Sz) {
+    float gx, gy;
+    if (!nav_grid_point(G, Sx, Sy, Sz, gx, gy)) return -1;
+    return (int)gy * G.W + (int)gx;
+}
+// a ray in the map frame, and the cell in whose band its sample m is accepted, or -1
+struct NavMarchRay { float O[3], D[3]; };
+__device__ __forceinline__ int nav_sample_cell(const NavGrid& G, const NavMarchRay& r, int m) {
+    const float tm = (float)m * G.step;
+    return nav_cell(G, r.O[0] + tm * r.D[0], r.O[1] + tm * r.D[1], r.O[2] + tm * r.D[2]);
+}
+// The march of ONE RAY BY ONE WAVE: its samples m = 0 .. M over the lanes, m = lane, lane + 64, ...  The cell of sample m - 1 comes
+// from the neighbouring lane (the same formula, so the same bits), across rounds of 64 through `carry`.  Only entries -- a sample in a
+// cell's band whose predecessor was not -- reach `seen`, with an integer atomicAdd (order-free).  The rays a wave takes one after the
+// other are neighbouring pixels: they start in the same cell and stay together for their first cells, and all of that would land on a
+// few addresses.  So what a lane would add for a sample m < 64 of consecutive rays to one cell is merged in its registers (pend_cell,
+// pend_n: they live across the wave's rays) and issued as one atomic when the cell changes; the caller issues the last one.
+__device__ __forceinline__ void nav_march_ray(const NavGrid& G, const NavMarchRay& r, int M, uint32_t* seen, int& pend_cell, uint32_t& pend_n,
+                                              unsigned long long& n_entries, unsigned long long& n_atomics) {
+    const int ln = lane();
+    int carry = -1;                                                   // the cell of the sample before this round's first
+    for (int base = 0; base <= M; base += 64) {
+        const int m = base + ln;
+        const int c = m <= M ? nav_sample_cell(G, r, m) : -1;
+        int prev = __shfl_up(c, 1, 64);
+        if (ln == 0) prev = carry;
+        carry = __shfl(c, 63, 64);
+        if (c >= 0 && c != prev) {
+            n_entries++;
+            if (base == 0) {
+                if (c == pend_cell) pend_n++;
+                else {
+                    if (pend_n) { atomicAdd(&seen[pend_cell], pend_n); n_atomics++; }
+                    pend_cell = c; pend_n = 1u;
+                }
+            } else { atomicAdd(&seen[c], 1u); n_atomics++; }
         }
     }
 }
@@ -82,6 +120,11 @@ struct NavCall { const char* who; NavGrid G; float pose[12]; size_t P; unsigned 
 // how finish launches the cells kernel: ssf_navgrid.hip's own, or the carve's with `seen`
 typedef void (*NavCellsLaunch)(hipStream_t st, const ssf::NavGrid& G, const ssf::NavAcc& acc, const ssf::NavOut& out, unsigned long long* stats,
                                const ssf::NavSeen* sn);
+// log2 of a number of heading bins (1, 2, 4, .. 32), or -1: the footprint's layers, the pose plan's states
+inline int nav_log2_bins(int B) {
+    for (int lg = 0; lg <= 5; lg++) if (B == (1 << lg)) return lg;
+    return -1;
+}
 const char* navgrid_size_res(const ssf_navgrid_params* p);
 int navgrid_begin(ssf_handle* h, const ssf_navgrid_params* p, NavCall& c);
 int navgrid_reserve(ssf_handle* h, const ssf_navgrid_params* p, const NavCall& c, StagedIo& io);

@@ -5,7 +5,7 @@
 //             and come back column-major, so that a wave holds four runs of 16 vertically adjacent pixels: with an upright camera a
 //             pixel column of a wall lands in one cell, and a run of lanes with one cell issues ONE atomicAdd of the run's length.
 //             The result never depends on the merge: a rolled camera merges less and counts the same.
-//   * march   k_navlive_march: the carve's march (ssf_navcarve.hip) for a single-origin bundle: one ray per wave, its samples over
+//   * march   k_navlive_march: the carve's march (nav_march_ray, ssf_navgrid.hpp) for a single-origin bundle: one ray per wave, its samples over
 //             the lanes, NL_RUN consecutive lattice pixels per wave; the ray is made from the depth image in place (no ray buffer, no
 //             ray cast: the hit is the pixel's own depth).  Every ray starts in the camera's own cell: what a lane would add for a
 //             sample m < 64 of consecutive rays to one cell is merged in its registers, as in the carve.
@@ -21,24 +21,13 @@ namespace ssf {
 
 // the sums the host reads (the unknown cells are the rest of the grid).  Every workgroup adds to them, so each sum has a 128-byte line
 // of its own: sum k is word k * NL_PAD, and the additions to different sums do not queue behind one another
-enum { NL_VALID = 0, NL_STAMPING, NL_POINTS, NL_RAYS, NL_CARVING, NL_SAMPLES, NL_ENTRIES, NL_STAMPED, NL_OPENED, NL_FREE, NL_OCC, NL_ATOMICS,
-       NL_STATS = 12, NL_PAD = 16 };
+// (a kernel's sums are consecutive, as block_sums wants them: the stamp and the march count their atomics apart)
+enum { NL_VALID = 0, NL_STAMPING, NL_POINTS, NL_STAMP_ATOMICS, NL_CARVING, NL_SAMPLES, NL_ENTRIES, NL_MARCH_ATOMICS, NL_RAYS, NL_STAMPED, NL_OPENED,
+       NL_FREE, NL_OCC, NL_STATS = 13, NL_PAD = 16 };
 enum { NL_TW = 16, NL_TH = 16, NL_RUN = 16 };
 
-// (the camera of the frame, the depth of a pixel and the cell of a point: ssf_navlive.hpp, shared with ssf_navdyn.hip)
-// four sums of a workgroup of 256 into stats[s0], .. stats[s3]: ALL threads call it
-__device__ __forceinline__ void navlive_block_sums(unsigned long long a, unsigned long long b, unsigned long long c, unsigned long long d,
-                                                   unsigned long long (*red)[4], unsigned long long* __restrict__ stats, int s0, int s1, int s2, int s3) {
-    a = wave_sum(a); b = wave_sum(b); c = wave_sum(c); d = wave_sum(d);
-    const int wv = threadIdx.x >> 6;
-    if (lane() == 0) { red[0][wv] = a; red[1][wv] = b; red[2][wv] = c; red[3][wv] = d; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const unsigned long long sum = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
-        const int slot = threadIdx.x == 0 ? s0 : (threadIdx.x == 1 ? s1 : (threadIdx.x == 2 ? s2 : s3));
-        if (sum) atomicAdd(&stats[slot * NL_PAD], sum);
-    }
-}
+// (the camera of the frame and the depth of a pixel: ssf_navlive.hpp, shared with ssf_navdyn.hip; the cell of a point and the march of
+// a ray: ssf_navgrid.hpp, shared with the carve; the sums: block_sums, ssf_slots.hpp, with NL_PAD as its stride)
 
 // ---- stamp: steps 1 to 3 ---------------------------------------------------------------------------------------------------
 template <int DF>
@@ -46,7 +35,6 @@ __global__ __launch_bounds__(256) void k_navlive_stamp(NavGrid G, NavLiveCam cam
                                                        const uint8_t* __restrict__ mask, int mask_mode, uint32_t* __restrict__ hits,
                                                        unsigned long long* __restrict__ stats) {
     __shared__ int s_cell[NL_TW * (NL_TH + 1)];                       // column x at x * (NL_TH + 1): the transposing write spreads over the banks
-    __shared__ unsigned long long red[4][4];
     const int ntx = (cam.W + NL_TW - 1) / NL_TW;
     const int t = threadIdx.x;
     const int u = (int)(blockIdx.x % ntx) * NL_TW + (t & (NL_TW - 1)), v = (int)(blockIdx.x / ntx) * NL_TH + (t >> 4);
@@ -60,7 +48,7 @@ __global__ __launch_bounds__(256) void k_navlive_stamp(NavGrid G, NavLiveCam cam
         if (stamping) {
             float Sx, Sy, Sz;
             navlive_pixel_point(cam, u, v, d, Sx, Sy, Sz);
-            c = navlive_cell(G, Sx, Sy, Sz);
+            c = nav_cell(G, Sx, Sy, Sz);
         }
     }
     s_cell[(t & (NL_TW - 1)) * (NL_TH + 1) + (t >> 4)] = c;
@@ -78,19 +66,13 @@ __global__ __launch_bounds__(256) void k_navlive_stamp(NavGrid G, NavLiveCam cam
         atomicAdd(&hits[cc], (uint32_t)len);
         n_atomics = 1;
     }
-    navlive_block_sums(valid, stamping, c >= 0, n_atomics, red, stats, NL_VALID, NL_STAMPING, NL_POINTS, NL_ATOMICS);
+    block_sums({valid, stamping, c >= 0, n_atomics}, stats, NL_VALID, NL_PAD);
 }
 
 // ---- march: step 4 ---------------------------------------------------------------------------------------------------------
-struct NavLiveRay { float O[3], D[3]; };
-__device__ __forceinline__ int navlive_sample_cell(const NavGrid& G, const NavLiveRay& r, int m) {
-    const float tm = (float)m * G.step;
-    return navlive_cell(G, r.O[0] + tm * r.D[0], r.O[1] + tm * r.D[1], r.O[2] + tm * r.D[2]);
-}
 template <int DF>
 __global__ __launch_bounds__(256) void k_navlive_march(NavGrid G, NavLiveCam cam, const void* __restrict__ depth, double scale, float margin,
                                                        uint32_t* __restrict__ seen, unsigned long long* __restrict__ stats) {
-    __shared__ unsigned long long red[4][4];
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     const int ln = lane();
     const int n = cam.nu * cam.nv;
@@ -108,7 +90,7 @@ __global__ __launch_bounds__(256) void k_navlive_march(NavGrid G, NavLiveCam cam
         const float l = sqrtf((x * x + y * y) + 1.0f);
         const float dx = x / l, dy = y / l, dz = 1.0f / l;
         const float o = 0.0f;                                         // the camera-frame origin, through ssf_raycast.h step 1 as written
-        NavLiveRay r;
+        NavMarchRay r;
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const float a = cam.R[3 * k], b = cam.R[3 * k + 1], c = cam.R[3 * k + 2];
@@ -120,30 +102,12 @@ __global__ __launch_bounds__(256) void k_navlive_march(NavGrid G, NavLiveCam cam
         const int M = rvalid && t_end >= 0.0f ? (int)floorf(t_end / G.step) : -1;                  // <= 65535: the refusal of the corners
         if (M < 0) continue;
         n_carving++; n_samples += (unsigned long long)(M + 1);
-        int carry = -1;                                               // the cell of the sample before this round's first
-        for (int base = 0; base <= M; base += 64) {
-            const int m = base + ln;
-            const int c = m <= M ? navlive_sample_cell(G, r, m) : -1;
-            int prev = __shfl_up(c, 1, 64);
-            if (ln == 0) prev = carry;
-            carry = __shfl(c, 63, 64);
-            if (c >= 0 && c != prev) {
-                n_entries++;
-                if (base == 0) {
-                    if (c == pend_cell) pend_n++;
-                    else {
-                        if (pend_n) { atomicAdd(&seen[pend_cell], pend_n); n_atomics++; }
-                        pend_cell = c; pend_n = 1u;
-                    }
-                } else { atomicAdd(&seen[c], 1u); n_atomics++; }
-            }
-        }
+        nav_march_ray(G, r, M, seen, pend_cell, pend_n, n_entries, n_atomics);
     }
     if (pend_n) { atomicAdd(&seen[pend_cell], pend_n); n_atomics++; }
     // the sums of the workgroup's four waves (rays and samples: one lane speaks for its wave)
-    navlive_block_sums(ln == 0 ? n_carving : 0ull, ln == 0 ? n_samples : 0ull, n_entries, n_atomics, red, stats, NL_CARVING, NL_SAMPLES, NL_ENTRIES, NL_ATOMICS);
-    __syncthreads();                                                  // (red is used again)
-    navlive_block_sums(ln == 0 ? n_rays : 0ull, 0ull, 0ull, 0ull, red, stats, NL_RAYS, NL_RAYS, NL_RAYS, NL_RAYS);
+    block_sums({ln == 0 ? n_carving : 0ull, ln == 0 ? n_samples : 0ull, n_entries, n_atomics}, stats, NL_CARVING, NL_PAD);
+    block_sums({ln == 0 ? n_rays : 0ull}, stats, NL_RAYS, NL_PAD);
 }
 
 // ---- cells: step 5 and the cell stats; one thread per cell -------------------------------------------------------------------
@@ -152,7 +116,6 @@ struct NavLiveRule { int min_hits, min_seen, open_unknown; };
 __global__ __launch_bounds__(256) void k_navlive_cells(size_t P, NavLiveRule rule, const int8_t* state_in, const uint32_t* __restrict__ hits,
                                                        const uint32_t* __restrict__ seen, uint32_t* __restrict__ out_hits,
                                                        uint32_t* __restrict__ out_seen, int8_t* out_state, unsigned long long* __restrict__ stats) {
-    __shared__ unsigned long long red[4][4];
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     unsigned long long nstamped = 0, nopened = 0, nfree = 0, nocc = 0;
     if (p < P) {
@@ -167,7 +130,7 @@ __global__ __launch_bounds__(256) void k_navlive_cells(size_t P, NavLiveRule rul
         if (out_seen) out_seen[p] = ns;
         if (out_state) out_state[p] = st;
     }
-    navlive_block_sums(nstamped, nopened, nfree, nocc, red, stats, NL_STAMPED, NL_OPENED, NL_FREE, NL_OCC);
+    block_sums({nstamped, nopened, nfree, nocc}, stats, NL_STAMPED, NL_PAD);
 }
 
 static void launch_navlive_stamp(hipStream_t st, int df, const NavGrid& G, const NavLiveCam& cam, const void* depth, double scale, const uint8_t* mask,
@@ -324,7 +287,7 @@ int ssf_navlive_overlay(ssf_handle* h, const ssf_navlive_params* p, const void* 
         stats->rays = (int64_t)s[NL_RAYS]; stats->rays_carving = (int64_t)s[NL_CARVING]; stats->ray_samples = (int64_t)s[NL_SAMPLES];
         stats->ray_entries = (int64_t)s[NL_ENTRIES]; stats->cells_stamped = (int64_t)s[NL_STAMPED]; stats->cells_opened = (int64_t)s[NL_OPENED];
         stats->cells_free = (int64_t)s[NL_FREE]; stats->cells_occupied = (int64_t)s[NL_OCC]; stats->cells_unknown = (int64_t)P - (int64_t)s[NL_FREE] - (int64_t)s[NL_OCC];
-        stats->atomics = (int64_t)s[NL_ATOMICS];
+        stats->atomics = (int64_t)(s[NL_STAMP_ATOMICS] + s[NL_MARCH_ATOMICS]);
         std::memcpy(stats->pose, gpose, sizeof(gpose));
     }
     return SSF_OK;

@@ -1,6 +1,7 @@
 // ssf_navlive.hpp -- what ssf_navlive.hip (ssf_navlive_overlay) shares with ssf_navdyn.hip (ssf_navdyn_blobs, include/ssf_navdyn.h):
-// the camera of a depth frame, the depth of a pixel, the grid point of a map-frame point (include/ssf_navlive.h steps 1 and 2), and the
-// refusals for the camera and the depth range.  Private to the library's own files: nothing here is exported.
+// the camera of a depth frame, the depth of a pixel, the map-frame point of a pixel (include/ssf_navlive.h steps 1 and 2; its grid
+// point and cell: nav_grid_point and nav_cell, ssf_navgrid.hpp), and the refusals for the camera and the depth range.
+// Private to the library's own files: nothing here is exported.
 #pragma once
 #include "ssf_navgrid.hpp"
 #include "../../include/ssf_input.h"
@@ -13,22 +14,6 @@ struct NavLiveCam { float R[9], t[3]; float fx, fy, cx, cy; int W, H; float tmin
 template <int DF> __device__ __forceinline__ float navlive_load_depth(const void* __restrict__ p, size_t q, double scale) {
     if (DF == SSF_DEPTH_U16_SCALED) return (float)((double)reinterpret_cast<const uint16_t*>(p)[q] * scale);
     return reinterpret_cast<const float*>(p)[q];
-}
-// the map-frame point S in the grid frame (ssf_navgrid.h steps 1 and 4): true iff it lies in the grid and in the band of step 5;
-// (gx, gy): its position in cells
-__device__ __forceinline__ bool navlive_grid_point(const NavGrid& G, float Sx, float Sy, float Sz, float& gx, float& gy) {
-    const float dx = Sx - G.t[0], dy = Sy - G.t[1], dz = Sz - G.t[2];
-    const float* R = G.R;
-    const float Cx = (R[0] * dx + R[3] * dy) + R[6] * dz, Cy = (R[1] * dx + R[4] * dy) + R[7] * dz, z = (R[2] * dx + R[5] * dy) + R[8] * dz;
-    gx = Cx / G.res; gy = Cy / G.res;
-    if (!(gx >= 0.0f && gx < G.fW && gy >= 0.0f && gy < G.fH)) return false;
-    return z > G.floor_max && z <= G.zmax;
-}
-// the cell in whose band the map-frame point S lies, or -1
-__device__ __forceinline__ int navlive_cell(const NavGrid& G, float Sx, float Sy, float Sz) {
-    float gx, gy;
-    if (!navlive_grid_point(G, Sx, Sy, Sz, gx, gy)) return -1;
-    return (int)gy * G.W + (int)gx;
 }
 // the map-frame point of pixel (u, v) at depth d (ssf_navlive.h step 2)
 __device__ __forceinline__ void navlive_pixel_point(const NavLiveCam& cam, int u, int v, float d, float& Sx, float& Sy, float& Sz) {

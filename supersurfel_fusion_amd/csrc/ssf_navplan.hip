@@ -3,33 +3,25 @@
 // What is computed is pinned in include/ssf_navplan.h (the restatement: tests/navplan_ref.py).  ssf_navplan_field runs
 //   * init     k_navplan_init: one thread per cell: traversable and penalty packed into one word, the frontier, cost = INF (0 on a
 //              frontier goal); k_navplan_goals: one thread per goal entry: the goals at 0.  Both flag the 32 x 32 tiles that see a goal;
-//   * relax    k_navplan_relax, one launch per ROUND: one 256-thread workgroup per tile, which leaves at once when its tile is not
-//              flagged; otherwise it loads the tile's 34 x 34 window of cost and packed word into LDS, relaxes there until nothing
-//              changes, writes back the interior cells it lowered and flags, for the next round, the neighbour tiles whose window
-//              holds a lowered edge or corner cell.  The flags are two ping-pong arrays with the number of set words beside each;
-//              the host reads that number once per batch of rounds.  No device-wide barrier, no spinning kernel;
+//   * relax    k_navplan_relax, one launch per ROUND, one workgroup per flagged 32 x 32 tile on its 34 x 34 window of cost and packed
+//              word: the tile-round scheme of ssf_navfield.hpp, which also says why its racy reads are benign;
 //   * stats    k_navplan_stats: reached cells and the largest cost;
 //   * trace    k_navplan_trace: one wave per start, lanes 0..7 the eight moves, a wave minimum over (value, k).
 //
-// Why the racy reads are benign: a workgroup reads its window's rim from the interiors of neighbours that may be lowering them in
-// the same round.  Every value ever stored is the cost of a real path, values only decrease, and whoever lowers an edge cell flags
-// every tile that sees it for the next round (a launch boundary makes the stores visible).  So whichever value was read, the reader
-// runs again on the final one; when no tile is flagged, every tile is at its fixed point for the window it would load.  The field
-// is stored with plain aligned 32-bit stores, no atomics.
-//
 // This file is NOT one of the product library's objects.  It is linked, with all of them and the carve, into libssf_hip_nav.so.
-#include "ssf_navgrid.hpp"
+#include "ssf_navfield.hpp"
 #include "../../include/ssf_navplan.h"
 #include "../../include/ssf_navplan_testing.h"
 
 namespace ssf {
 
 enum { NP_WIN = NAV_TILE + 2, NP_WIN_CELLS = NP_WIN * NP_WIN };
-enum : uint32_t { NP_INF = 0xFFFFFFFFu, NP_TRAV = 0x80000000u };
+enum : uint32_t { NP_INF = NAVF_INF, NP_TRAV = 0x80000000u };
 // the sums: traversable cells, frontier cells, frontier goals, goal entries used / blocked / outside, reached cells, largest cost,
 // (round, tile) visits, the last round that worked + 1, the set words of the two flag arrays
 enum { NP_NTRAV = 0, NP_NFRONT = 1, NP_FGOALS = 2, NP_GUSED = 3, NP_GBLOCKED = 4, NP_GOUTSIDE = 5, NP_REACHED = 6, NP_MAXCOST = 7,
        NP_VISITS = 8, NP_ROUNDS = 9, NP_FLAGGED = 10, NP_STATS = 12 };
+constexpr NavFieldSums NP_SUMS{NP_VISITS, NP_ROUNDS, NP_FLAGGED};
 // the rounds launched between two looks at the flagged-tile count: 16 was the best or within 2 % of the best of 1, 4, 16, 64 on all
 // three grids of tools/navplan_probe.py (profiles/navplan.txt).  One workgroup per tile, idle ones included, stays the launch form:
 // with 256 tiles a round costs what its busiest tile costs (about 60 us), so a compacted list of flagged tiles was not built.
@@ -37,41 +29,6 @@ enum { NP_DEFAULT_BATCH = 16, NP_MAX_BATCH = 1024 };
 
 struct NavPlanGrid { int W, H, ntx, nty; };
 struct NavPlanRule { int min_dist2, soft_dist2, near_penalty, allow_unknown, frontier_goals; };
-
-// move k = 0..7: (+1,0), (0,+1), (-1,0), (0,-1), (+1,+1), (-1,+1), (-1,-1), (+1,-1); 10 along an axis, 14 across
-__device__ __forceinline__ int np_dx(int k) { return (int)((0x8246u >> (2 * k)) & 3u) - 1; }     // dx + 1 = 2 1 0 1 2 0 0 2
-__device__ __forceinline__ int np_dy(int k) { return (int)((0x0A19u >> (2 * k)) & 3u) - 1; }     // dy + 1 = 1 2 1 0 2 2 0 0
-__device__ __forceinline__ uint32_t np_w(int k) { return k < 4 ? 10u : 14u; }
-
-// flag tile t in `flags` (counted once, however many set it)
-__device__ __forceinline__ void np_flag(uint32_t* __restrict__ flags, unsigned long long* __restrict__ flagged, int t) {
-    if (flags[t] == 0u && atomicExch(&flags[t], 1u) == 0u) atomicAdd(flagged, 1ull);      // (a word only goes 0 -> 1 while it is being set)
-}
-// bit (sy + 1) * 3 + (sx + 1) for every tile offset (sx, sy) whose 34 x 34 window holds cell (lx, ly) of a tile (bit 4: the tile itself)
-__device__ __forceinline__ uint32_t np_seers(int lx, int ly) {
-    const int sx = lx == 0 ? -1 : (lx == NAV_TILE - 1 ? 1 : 0), sy = ly == 0 ? -1 : (ly == NAV_TILE - 1 ? 1 : 0);
-    uint32_t m = 1u << 4;
-    if (sx) m |= 1u << (3 + (sx + 1));
-    if (sy) m |= 1u << ((sy + 1) * 3 + 1);
-    if (sx && sy) m |= 1u << ((sy + 1) * 3 + (sx + 1));
-    return m;
-}
-__device__ __forceinline__ void np_flag_bit(const NavPlanGrid& G, int tx, int ty, int bit, uint32_t* __restrict__ flags, unsigned long long* __restrict__ flagged) {
-    const int nx = tx + bit % 3 - 1, ny = ty + bit / 3 - 1;
-    if (nx >= 0 && nx < G.ntx && ny >= 0 && ny < G.nty) np_flag(flags, flagged, ny * G.ntx + nx);
-}
-
-// three block sums into stats[first ..]: the block-sum pattern of navgrid_cells_body (ssf_navgrid.hpp); all 256 threads call it
-__device__ __forceinline__ void np_block_sums3(unsigned long long a, unsigned long long b, unsigned long long c, unsigned long long* __restrict__ stats, int first) {
-    __shared__ unsigned long long red[3][4];
-    a = wave_sum(a); b = wave_sum(b); c = wave_sum(c);
-    if (lane() == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; red[2][threadIdx.x >> 6] = c; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const unsigned long long sum = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
-        if (sum) atomicAdd(&stats[first + threadIdx.x], sum);
-    }
-}
 
 // ---- init: one thread per cell (steps 1, 2, 4 and the frontier's part of 5) ------------------------------------------------------
 __global__ __launch_bounds__(256) void k_navplan_init(NavPlanGrid G, NavPlanRule r, const int8_t* __restrict__ state, const int32_t* __restrict__ dist2,
@@ -83,21 +40,17 @@ __global__ __launch_bounds__(256) void k_navplan_init(NavPlanGrid G, NavPlanRule
         const int x = (int)(p % (size_t)G.W), y = (int)(p / (size_t)G.W);
         const int s = state[p], d = dist2[p];
         const bool trav = (s == 0 || (r.allow_unknown && s == -1)) && d >= r.min_dist2;
-        const int dc = d < 0 ? 0 : (d < r.soft_dist2 ? d : r.soft_dist2);
-        const uint32_t pen = r.soft_dist2 > 0 ? (uint32_t)(r.near_penalty * (r.soft_dist2 - dc) / r.soft_dist2) : 0u;
+        const uint32_t pen = navfield_penalty(d, r.soft_dist2, r.near_penalty);
         const bool fr = s == 0 && ((x > 0 && state[p - 1] == -1) || (x + 1 < G.W && state[p + 1] == -1) ||
                                    (y > 0 && state[p - G.W] == -1) || (y + 1 < G.H && state[p + G.W] == -1));
         const bool goal = r.frontier_goals && fr && trav;
         pk[p] = (trav ? (uint32_t)NP_TRAV : 0u) | pen;
         cost[p] = goal ? 0u : (uint32_t)NP_INF;
         frontier[p] = fr ? 1 : 0;
-        if (goal) {
-            const uint32_t m = np_seers(x & (NAV_TILE - 1), y & (NAV_TILE - 1));
-            for (int b = 0; b < 9; b++) if ((m >> b) & 1u) np_flag_bit(G, x >> NAV_TILE_SHIFT, y >> NAV_TILE_SHIFT, b, flags, &stats[NP_FLAGGED]);
-        }
+        if (goal) navfield_flag_seers<NAV_TILE>(G.ntx, G.nty, x, y, flags, &stats[NP_FLAGGED]);
         ntrav = trav; nfront = fr; ngoal = goal;
     }
-    np_block_sums3(ntrav, nfront, ngoal, stats, NP_NTRAV);
+    block_sums({ntrav, nfront, ngoal}, stats, NP_NTRAV);
 }
 
 // goals: one thread per entry of the caller's list (step 5); runs behind k_navplan_init, so its zeros stay
@@ -114,12 +67,11 @@ __global__ __launch_bounds__(256) void k_navplan_goals(NavPlanGrid G, const int3
             else {
                 used = 1;
                 cost[p] = 0u;
-                const uint32_t m = np_seers(x & (NAV_TILE - 1), y & (NAV_TILE - 1));
-                for (int b = 0; b < 9; b++) if ((m >> b) & 1u) np_flag_bit(G, x >> NAV_TILE_SHIFT, y >> NAV_TILE_SHIFT, b, flags, &stats[NP_FLAGGED]);
+                navfield_flag_seers<NAV_TILE>(G.ntx, G.nty, x, y, flags, &stats[NP_FLAGGED]);
             }
         }
     }
-    np_block_sums3(used, blocked, outside, stats, NP_GUSED);
+    block_sums({used, blocked, outside}, stats, NP_GUSED);
 }
 
 // ---- relax: one round; one workgroup per tile, gone at once when the tile is not flagged ------------------------------------------
@@ -130,9 +82,8 @@ __global__ __launch_bounds__(256) void k_navplan_relax(NavPlanGrid G, const uint
                                                        unsigned long long* __restrict__ stats, int cur, unsigned long long round) {
     __shared__ uint32_t sc[NP_WIN_CELLS], sp[NP_WIN_CELLS];
     __shared__ uint32_t seers;
-    const int t = blockIdx.x;
-    if (fcur[t] == 0u) return;                                        // (the same word for every thread: nobody clears it before the last barrier)
-    const int tx = t % G.ntx, ty = t / G.ntx;
+    if (!navfield_flagged(fcur)) return;
+    const int t = blockIdx.x, tx = t % G.ntx, ty = t / G.ntx;
     const int x0 = tx * NAV_TILE - 1, y0 = ty * NAV_TILE - 1;
     for (int i = threadIdx.x; i < NP_WIN_CELLS; i += 256) {
         const int gx = x0 + i % NP_WIN, gy = y0 + i / NP_WIN;
@@ -158,12 +109,12 @@ __global__ __launch_bounds__(256) void k_navplan_relax(NavPlanGrid G, const uint
             const bool right = sp[c + 1] & NP_TRAV, down = sp[c + NP_WIN] & NP_TRAV, left = sp[c - 1] & NP_TRAV, up = sp[c - NP_WIN] & NP_TRAV;
 #pragma unroll
             for (int k = 0; k < 8; k++) {
-                const int dx = np_dx(k), dy = np_dy(k), q = c + dy * NP_WIN + dx;
+                const int dx = navfield_dx(k), dy = navfield_dy(k), q = c + dy * NP_WIN + dx;
                 const uint32_t pq = sp[q];
                 bool ok = pq & NP_TRAV;
                 if (k >= 4) ok = ok && (dx > 0 ? right : left) && (dy > 0 ? down : up);
                 const uint32_t cq = sc[q];
-                if (ok && cq != NP_INF) { const uint32_t v = cq + np_w(k) + (pq & ~(uint32_t)NP_TRAV); best = v < best ? v : best; }
+                if (ok && cq != NP_INF) { const uint32_t v = cq + navfield_w(k) + (pq & ~(uint32_t)NP_TRAV); best = v < best ? v : best; }
             }
             if (best < have) { sc[c] = best; changed = 1; }
         }
@@ -176,39 +127,18 @@ __global__ __launch_bounds__(256) void k_navplan_relax(NavPlanGrid G, const uint
         const uint32_t now = sc[(ly + 1) * NP_WIN + lx + 1];
         if (now < old[j]) {                                           // (a lowered cell is traversable, so inside the grid)
             cost[(size_t)(y0 + 1 + ly) * G.W + (x0 + 1 + lx)] = now;
-            mine |= np_seers(lx, ly);
+            mine |= navfield_seers<NAV_TILE>(lx, ly);
         }
     }
-    mine &= ~(1u << 4);
-    if (mine) atomicOr(&seers, mine);
-    __syncthreads();
-    if (threadIdx.x < 9 && ((seers >> threadIdx.x) & 1u)) np_flag_bit(G, tx, ty, threadIdx.x, fnxt, &stats[NP_FLAGGED + (cur ^ 1)]);
-    if (threadIdx.x == 0) {
-        fcur[t] = 0u;
-        atomicAdd(&stats[NP_FLAGGED + cur], ~0ull);                   // (- 1)
-        atomicAdd(&stats[NP_VISITS], 1ull);
-        atomicMax(&stats[NP_ROUNDS], round + 1ull);
-    }
+    navfield_publish(G.ntx, G.nty, mine, &seers, fcur, fnxt, stats, NP_SUMS, cur, round);
 }
 
 // ---- stats: reached cells and the largest cost ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_navplan_stats(size_t P, const uint32_t* __restrict__ cost, unsigned long long* __restrict__ stats) {
-    __shared__ unsigned long long red[2][4];
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     const uint32_t c = p < P ? cost[p] : (uint32_t)NP_INF;
-    unsigned long long n = c != NP_INF, mx = c != NP_INF ? c : 0u;
-    n = wave_sum(n);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long u = __shfl_xor(mx, o, 64); mx = u > mx ? u : mx; }
-    if (lane() == 0) { red[0][threadIdx.x >> 6] = n; red[1][threadIdx.x >> 6] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long sum = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        if (sum) atomicAdd(&stats[NP_REACHED], sum);
-    } else if (threadIdx.x == 1) {
-        const unsigned long long a = red[1][0] > red[1][1] ? red[1][0] : red[1][1], b = red[1][2] > red[1][3] ? red[1][2] : red[1][3];
-        if ((a > b ? a : b) > 0ull) atomicMax(&stats[NP_MAXCOST], a > b ? a : b);
-    }
+    block_sums({c != NP_INF}, stats, NP_REACHED);
+    navfield_block_max(c != NP_INF ? c : 0u, &stats[NP_MAXCOST]);
 }
 
 // ---- trace: one wave per start (step 7) ------------------------------------------------------------------------------------------------
@@ -235,14 +165,14 @@ __global__ __launch_bounds__(256) void k_navplan_trace(NavPlanGrid G, const uint
             unsigned long long key = ~0ull;
             uint32_t cq = NP_INF;
             if (ln < 8) {
-                const int dx = np_dx(ln), dy = np_dy(ln), qx = x + dx, qy = y + dy;
+                const int dx = navfield_dx(ln), dy = navfield_dy(ln), qx = x + dx, qy = y + dy;
                 if (qx >= 0 && qx < G.W && qy >= 0 && qy < G.H) {
                     const uint32_t pq = pk[(size_t)qy * G.W + qx];
                     bool ok = pq & NP_TRAV;
                     if (ok && ln >= 4) ok = (pk[(size_t)y * G.W + qx] & NP_TRAV) && (pk[(size_t)qy * G.W + x] & NP_TRAV);
                     if (ok) {
                         cq = cost[(size_t)qy * G.W + qx];
-                        if (cq != NP_INF) key = ((unsigned long long)(cq + np_w(ln) + (pq & ~(uint32_t)NP_TRAV)) << 3) | (unsigned long long)ln;
+                        if (cq != NP_INF) key = ((unsigned long long)(cq + navfield_w(ln) + (pq & ~(uint32_t)NP_TRAV)) << 3) | (unsigned long long)ln;
                     }
                 }
             }
@@ -250,7 +180,7 @@ __global__ __launch_bounds__(256) void k_navplan_trace(NavPlanGrid G, const uint
             if (key == ~0ull) { status = 3; break; }                  // (not on a settled field: a cell of finite cost > 0 has such a neighbour)
             const int k = (int)(key & 7ull);
             c = __shfl(cq, k, 64);
-            x += np_dx(k); y += np_dy(k);
+            x += navfield_dx(k); y += navfield_dy(k);
         }
     }
     if (ln == 0) { start_cost[w] = c0; start_status[w] = status; path_len[w] = len; }
@@ -325,16 +255,11 @@ int ssf_navplan_field(ssf_handle* h, const ssf_navplan_params* p, const int8_t* 
     const size_t path_words = want_path ? (size_t)ns * (size_t)p->max_path * 2 : 0;
     // the working buffers
     NavPlanWs& w = h->navplan;
-    bool ok = true;
-    if (!w.stats) ok = w.bufs.grow({{(void**)&w.stats, NP_STATS * sizeof(unsigned long long)}, {(void**)&w.goals, 65536 * 2 * sizeof(int32_t)},
-                                    {(void**)&w.starts, 4096 * 2 * sizeof(int32_t)}, {(void**)&w.start_cost, 4096 * sizeof(uint32_t)},
-                                    {(void**)&w.start_status, 4096 * sizeof(int32_t)}, {(void**)&w.path_len, 4096 * sizeof(int32_t)}});
+    bool ok = navfield_reserve(w, NP_STATS, 2, tiles, dev ? 0 : path_words);
     if (ok && P > w.cells) {
         ok = w.bufs.grow({{(void**)&w.state, P}, {(void**)&w.dist2, 4 * P}, {(void**)&w.pk, 4 * P}, {(void**)&w.cost, 4 * P}, {(void**)&w.frontier, P}});
         if (ok) w.cells = P;
     }
-    if (ok && tiles > w.tiles) { ok = w.bufs.grow({{(void**)&w.flags, 2 * tiles * sizeof(uint32_t)}}); if (ok) w.tiles = tiles; }
-    if (ok && !dev && path_words > w.path_words) { ok = w.bufs.grow({{(void**)&w.path, path_words * sizeof(int32_t)}}); if (ok) w.path_words = path_words; }
     if (!ok) { h->err = "ssf_navplan_field: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
 
     hipStream_t st = h->stream;
@@ -352,17 +277,10 @@ int ssf_navplan_field(ssf_handle* h, const ssf_navplan_params* p, const int8_t* 
     launch_navplan_init(st, G, rule, d_state, d_dist2, w.pk, w.cost, w.frontier, w.flags, w.stats);
     HCK(hipGetLastError());
     if (p->n_goals > 0) { launch_navplan_goals(st, G, w.goals, p->n_goals, w.pk, w.cost, w.flags, w.stats); HCK(hipGetLastError()); }
-    // the rounds: round r reads the flags of array r & 1 and sets those of the other; the host looks once per batch
-    const int batch = w.round_batch > 0 ? w.round_batch : NP_DEFAULT_BATCH;
-    const long long limit = (long long)P + 2;
-    long long round = 0;
-    for (;;) {
-        unsigned long long flagged = 0;
-        HCK(hipMemcpyAsync(&flagged, w.stats + NP_FLAGGED + (round & 1), sizeof(flagged), hipMemcpyDeviceToHost, st));
-        { int rc = sync_collect(h); if (rc) return rc; }
-        if (flagged == 0) break;
-        if (round >= limit) { h->err = "ssf_navplan_field: the field did not converge"; return SSF_ERR_DEVICE; }
-        for (int i = 0; i < batch && round < limit; i++, round++) { launch_navplan_relax(st, G, w.pk, w.cost, w.flags, w.stats, round); HCK(hipGetLastError()); }
+    {                                                                 // the rounds, with the hook's batch
+        int rc = navfield_rounds(h, "ssf_navplan_field", w.stats, NP_FLAGGED, (long long)P + 2, w.round_batch > 0 ? w.round_batch : NP_DEFAULT_BATCH,
+                                 [&](long long round, int) { launch_navplan_relax(st, G, w.pk, w.cost, w.flags, w.stats, round); });
+        if (rc) return rc;
     }
     launch_navplan_stats(st, P, w.cost, w.stats);
     HCK(hipGetLastError());
@@ -374,23 +292,12 @@ int ssf_navplan_field(ssf_handle* h, const ssf_navplan_params* p, const int8_t* 
     // the outputs
     const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     unsigned long long s[NP_STATS];
-    int32_t lens[4096];                                               // (n_starts <= 4096)
     HCK(hipMemcpyAsync(s, w.stats, sizeof(s), hipMemcpyDeviceToHost, st));
     if (out->cost) HCK(hipMemcpyAsync(out->cost, w.cost, 4 * P, kind, st));
     if (out->frontier) HCK(hipMemcpyAsync(out->frontier, w.frontier, P, kind, st));
-    if (ns > 0) {
-        if (out->start_cost) HCK(hipMemcpyAsync(out->start_cost, w.start_cost, 4 * (size_t)ns, kind, st));
-        if (out->start_status) HCK(hipMemcpyAsync(out->start_status, w.start_status, 4 * (size_t)ns, kind, st));
-        if (out->path_len) HCK(hipMemcpyAsync(out->path_len, w.path_len, 4 * (size_t)ns, kind, st));
-        if (want_path && !dev) { HCK(hipMemcpyAsync(lens, w.path_len, 4 * (size_t)ns, hipMemcpyDeviceToHost, st)); }
-    }
-    { int rc = sync_collect(h); if (rc) return rc; }
-    if (want_path && !dev) {                                          // entries past path_len are not written: each path's cells, no more
-        for (int i = 0; i < ns; i++)
-            if (lens[i] > 0)
-                HCK(hipMemcpyAsync(out->path + (size_t)i * p->max_path * 2, w.path + (size_t)i * p->max_path * 2, 8 * (size_t)lens[i],
-                                   hipMemcpyDeviceToHost, st));
-        HCK(hipStreamSynchronize(st));
+    {
+        int rc = navfield_copy_out(h, w, ns, p->max_path, 2, kind, out->start_cost, out->start_status, out->path_len, want_path && !dev ? out->path : nullptr);
+        if (rc) return rc;
     }
     w.last_rounds = (long long)s[NP_ROUNDS]; w.last_visits = (long long)s[NP_VISITS];
     if (stats) {

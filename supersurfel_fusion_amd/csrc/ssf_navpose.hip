@@ -7,84 +7,42 @@
 //   * init     k_navpose_init: one thread per cell: the traversable bins and the penalty packed into one 8-byte word, the cell's B
 //              field entries set to the marker; k_navpose_goals: one thread per goal entry: the goal states at 0, and the flags of
 //              the 16 x 16-cell tiles whose window holds the goal's cell;
-//   * relax    k_navpose_relax, one launch per ROUND: one 256-thread workgroup per tile, which leaves at once when its tile is not
-//              flagged; otherwise it loads the tile's 18 x 18 window -- the packed word and all B layers of the field -- into LDS and
-//              sweeps there until a sweep stores nothing.  A thread owns one cell and walks its column of bins: per bin the moves of
-//              that bin from the same layer's neighbours, then the two rotations; an ascending sweep carries a lowered value round
-//              the column in one go, a descending sweep of rotations alone does the same the other way.  The column stays in LDS
-//              (no dynamically indexed register array, so no scratch).  What the thread lowered it writes back with plain 32-bit
-//              stores, and the workgroup flags, for the next round, the neighbour tiles whose window holds a lowered cell.  The flags
-//              are two ping-pong arrays with the number of set words beside each; the host reads that number once per batch of
-//              rounds.  No device-wide barrier, no spinning kernel, no atomics on the field;
+//   * relax    k_navpose_relax, one launch per ROUND, one workgroup per flagged tile: the tile-round scheme of ssf_navfield.hpp, which
+//              also says why its racy reads are benign.  The workgroup loads the tile's 18 x 18 window -- the packed word and all B
+//              layers of the field -- into LDS and sweeps there until a sweep stores nothing.  A thread owns one cell and walks its
+//              column of bins: per bin the moves of that bin from the same layer's neighbours, then the two rotations; an ascending
+//              sweep carries a lowered value round the column in one go, a descending sweep of rotations alone does the same the
+//              other way.  The column stays in LDS (no dynamically indexed register array, so no scratch).  Rotations stay inside a
+//              cell, so they add no reader outside the window;
 //   * stats    k_navpose_stats: one thread per cell: cell_cost, cell_bin, the reached states and cells, the largest cost;
 //   * trace    k_navpose_trace: one wave per start, lanes 0..9 the ten transitions, a wave minimum over (value, t).
-//
-// Why the racy reads are benign (ssf_navplan.hip's argument, with states for cells): a workgroup reads its window's rim from the
-// interiors of neighbours that may be lowering them in the same round.  Every value ever stored is the cost of a real sequence of
-// admissible transitions to a goal, values only fall, and whoever lowers a state of an edge cell flags every tile whose window holds
-// that cell for the next round (a launch boundary makes the stores visible).  So whichever value was read, the reader runs again on
-// the final one; when no tile is flagged, every tile is at its fixed point for the window it would load, and that fixed point is the
-// field: all weights are positive.  Rotations stay inside a cell, so they add no reader outside the window.
 //
 // LDS: (2 + B) * 324 words, 41.0 KiB + 2.5 KiB at B = 32, asked for per launch (dynamic), so a smaller B leaves room for more
 // workgroups.  It never passes the 64 KiB a workgroup gets without opting into more.
 //
 // This file is NOT one of the product library's objects.  It is linked, with all of them and the older navigation files, into
 // libssf_hip_pose.so.
-#include "ssf_navgrid.hpp"
+#include "ssf_navfield.hpp"
 #include "../../include/ssf_navpose.h"
 
 namespace ssf {
 
 enum { NQ_TILE = SSF_NAVPOSE_TILE, NQ_WIN = NQ_TILE + 2, NQ_WIN_CELLS = NQ_WIN * NQ_WIN };
-enum : uint32_t { NQ_INF = 0xFFFFFFFFu };
+enum : uint32_t { NQ_INF = NAVF_INF };
 // the sums: traversable states, goal entries used / blocked / outside, reached states, reached cells, largest cost, (round, tile)
 // visits, the last round that worked + 1, the set words of the two flag arrays
 enum { NQ_NTRAV = 0, NQ_GUSED = 1, NQ_GBLOCKED = 2, NQ_GOUTSIDE = 3, NQ_REACHED = 4, NQ_CELLS = 5, NQ_MAXCOST = 6, NQ_VISITS = 7, NQ_ROUNDS = 8,
        NQ_FLAGGED = 9, NQ_STATS = 12 };
+constexpr NavFieldSums NQ_SUMS{NQ_VISITS, NQ_ROUNDS, NQ_FLAGGED};
 static_assert((2 + SSF_NAVFOOT_MAX_HEADINGS) * NQ_WIN_CELLS * 4 <= 64 * 1024, "a workgroup's window must fit the LDS it gets without opting into more");
 
 struct NavPoseGrid { int W, H, B, ntx, nty; };
 struct NavPoseRule { int min_dist2, soft_dist2, near_penalty, reverse_cost, turn_cost; };
 struct NavPoseMoves { uint32_t m[SSF_NAVFOOT_MAX_HEADINGS / 2]; };        // bin b: bits 16 (b & 1) + 2 k: 0 none, 1 forward, 2 reverse
 
-// move k = 0..7 as in ssf_navplan.hip: (+1,0), (0,+1), (-1,0), (0,-1), (+1,+1), (-1,+1), (-1,-1), (+1,-1); 10 along an axis, 14 across
-__device__ __forceinline__ int nq_dx(int k) { return (int)((0x8246u >> (2 * k)) & 3u) - 1; }
-__device__ __forceinline__ int nq_dy(int k) { return (int)((0x0A19u >> (2 * k)) & 3u) - 1; }
-__device__ __forceinline__ uint32_t nq_w(int k) { return k < 4 ? 10u : 14u; }
+// (the moves k = 0..7 and their weights: ssf_navfield.hpp)
 __device__ __forceinline__ uint32_t nq_codes(const NavPoseMoves& mv, int b) { return (mv.m[b >> 1] >> (16 * (b & 1))) & 0xFFFFu; }
 
-__device__ __forceinline__ void nq_flag(uint32_t* __restrict__ flags, unsigned long long* __restrict__ flagged, int t) {
-    if (flags[t] == 0u && atomicExch(&flags[t], 1u) == 0u) atomicAdd(flagged, 1ull);      // (a word only goes 0 -> 1 while it is being set)
-}
-// bit (sy + 1) * 3 + (sx + 1) for every tile offset (sx, sy) whose 18 x 18 window holds cell (lx, ly) of a tile (bit 4: the tile itself)
-__device__ __forceinline__ uint32_t nq_seers(int lx, int ly) {
-    const int sx = lx == 0 ? -1 : (lx == NQ_TILE - 1 ? 1 : 0), sy = ly == 0 ? -1 : (ly == NQ_TILE - 1 ? 1 : 0);
-    uint32_t m = 1u << 4;
-    if (sx) m |= 1u << (3 + (sx + 1));
-    if (sy) m |= 1u << ((sy + 1) * 3 + 1);
-    if (sx && sy) m |= 1u << ((sy + 1) * 3 + (sx + 1));
-    return m;
-}
-__device__ __forceinline__ void nq_flag_bit(const NavPoseGrid& G, int tx, int ty, int bit, uint32_t* __restrict__ flags, unsigned long long* __restrict__ flagged) {
-    const int nx = tx + bit % 3 - 1, ny = ty + bit / 3 - 1;
-    if (nx >= 0 && nx < G.ntx && ny >= 0 && ny < G.nty) nq_flag(flags, flagged, ny * G.ntx + nx);
-}
-__device__ __forceinline__ void nq_flag_seers(const NavPoseGrid& G, int x, int y, uint32_t* __restrict__ flags, unsigned long long* __restrict__ flagged) {
-    const uint32_t m = nq_seers(x & (NQ_TILE - 1), y & (NQ_TILE - 1));
-    for (int b = 0; b < 9; b++) if ((m >> b) & 1u) nq_flag_bit(G, x / NQ_TILE, y / NQ_TILE, b, flags, flagged);
-}
-// three block sums into stats[first ..]; all 256 threads call it
-__device__ __forceinline__ void nq_block_sums3(unsigned long long a, unsigned long long b, unsigned long long c, unsigned long long* __restrict__ stats, int first) {
-    __shared__ unsigned long long red[3][4];
-    a = wave_sum(a); b = wave_sum(b); c = wave_sum(c);
-    if (lane() == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; red[2][threadIdx.x >> 6] = c; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const unsigned long long sum = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
-        if (sum) atomicAdd(&stats[first + threadIdx.x], sum);
-    }
-}
 
 // ---- init: one thread per cell (steps 1 and 2); the field set to the marker ---------------------------------------------------------
 __global__ __launch_bounds__(256) void k_navpose_init(NavPoseGrid G, NavPoseRule r, const uint32_t* __restrict__ mask, const int32_t* __restrict__ dist2,
@@ -95,13 +53,11 @@ __global__ __launch_bounds__(256) void k_navpose_init(NavPoseGrid G, NavPoseRule
         const int d = dist2[p];
         const uint32_t all = G.B == 32 ? 0xFFFFFFFFu : (1u << G.B) - 1u;
         const uint32_t tr = d >= r.min_dist2 ? mask[p] & all : 0u;
-        const int dc = d < 0 ? 0 : (d < r.soft_dist2 ? d : r.soft_dist2);
-        const uint32_t pen = r.soft_dist2 > 0 ? (uint32_t)(r.near_penalty * (r.soft_dist2 - dc) / r.soft_dist2) : 0u;
-        pk[p] = make_uint2(tr, pen);
+        pk[p] = make_uint2(tr, navfield_penalty(d, r.soft_dist2, r.near_penalty));
         for (int b = 0; b < G.B; b++) cost[(size_t)b * P + p] = NQ_INF;
         ntrav = (unsigned long long)__popc(tr);
     }
-    nq_block_sums3(ntrav, 0ull, 0ull, stats, NQ_NTRAV);               // (the two zeros add nothing to the goals' sums)
+    block_sums({ntrav}, stats, NQ_NTRAV);
 }
 
 // goals: one thread per entry of the caller's list (step 6); runs behind k_navpose_init
@@ -119,11 +75,11 @@ __global__ __launch_bounds__(256) void k_navpose_goals(NavPoseGrid G, const int3
             else {
                 used = 1;
                 for (int b = 0; b < G.B; b++) if ((sel >> b) & 1u) cost[(size_t)b * P + p] = 0u;
-                nq_flag_seers(G, x, y, flags, &stats[NQ_FLAGGED]);
+                navfield_flag_seers<NQ_TILE>(G.ntx, G.nty, x, y, flags, &stats[NQ_FLAGGED]);
             }
         }
     }
-    nq_block_sums3(used, blocked, outside, stats, NQ_GUSED);
+    block_sums({used, blocked, outside}, stats, NQ_GUSED);
 }
 
 // ---- relax: one round; one workgroup per tile, gone at once when the tile is not flagged ------------------------------------------
@@ -138,11 +94,10 @@ __global__ __launch_bounds__(256) void k_navpose_relax(NavPoseGrid G, NavPoseMov
     uint32_t* const sp = nq_lds + NQ_WIN_CELLS;                       // [324] the penalty
     uint32_t* const sc = nq_lds + 2 * NQ_WIN_CELLS;                   // [B][324] the field
     __shared__ uint32_t seers;
-    const int t = blockIdx.x;
-    if (fcur[t] == 0u) return;                                        // (the same word for every thread: nobody clears it before the last barrier)
+    if (!navfield_flagged(fcur)) return;
     const int B = G.B;
     const size_t P = (size_t)G.W * G.H;
-    const int tx = t % G.ntx, ty = t / G.ntx;
+    const int t = blockIdx.x, tx = t % G.ntx, ty = t / G.ntx;
     const int x0 = tx * NQ_TILE - 1, y0 = ty * NQ_TILE - 1;
     for (int i = threadIdx.x; i < NQ_WIN_CELLS; i += 256) {
         const int gx = x0 + i % NQ_WIN, gy = y0 + i / NQ_WIN;
@@ -167,10 +122,10 @@ __global__ __launch_bounds__(256) void k_navpose_relax(NavPoseGrid G, NavPoseMov
         const uint32_t right = sm[c + 1], down = sm[c + NQ_WIN], left = sm[c - 1], up = sm[c - NQ_WIN];
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            const int dx = nq_dx(k), dy = nq_dy(k), q = c + dy * NQ_WIN + dx;
+            const int dx = navfield_dx(k), dy = navfield_dy(k), q = c + dy * NQ_WIN + dx;
             uint32_t m = sm[q] & my;
             if (k >= 4) m &= (dx > 0 ? right : left) & (dy > 0 ? down : up);
-            okm[k] = m; add[k] = nq_w(k) + sp[q];
+            okm[k] = m; add[k] = navfield_w(k) + sp[q];
         }
     }
     uint32_t lowered = 0u;
@@ -187,7 +142,7 @@ __global__ __launch_bounds__(256) void k_navpose_relax(NavPoseGrid G, NavPoseMov
                     for (int k = 0; k < 8; k++) {
                         const uint32_t code = (codes >> (2 * k)) & 3u;
                         if (code && ((okm[k] >> b) & 1u)) {
-                            const uint32_t cq = sc[b * NQ_WIN_CELLS + c + nq_dy(k) * NQ_WIN + nq_dx(k)];
+                            const uint32_t cq = sc[b * NQ_WIN_CELLS + c + navfield_dy(k) * NQ_WIN + navfield_dx(k)];
                             if (cq != NQ_INF) { const uint32_t v = cq + add[k] + (code == 2u ? rev : 0u); best = v < best ? v : best; }
                         }
                     }
@@ -214,23 +169,13 @@ __global__ __launch_bounds__(256) void k_navpose_relax(NavPoseGrid G, NavPoseMov
     if (lowered) {                                                    // (a lowered state is traversable, so its cell is inside the grid)
         const size_t p = (size_t)(y0 + 1 + ly) * G.W + (x0 + 1 + lx);
         for (int b = 0; b < B; b++) if ((lowered >> b) & 1u) cost[(size_t)b * P + p] = sc[b * NQ_WIN_CELLS + c];
-        const uint32_t mine = nq_seers(lx, ly) & ~(1u << 4);
-        if (mine) atomicOr(&seers, mine);
     }
-    __syncthreads();
-    if (threadIdx.x < 9 && ((seers >> threadIdx.x) & 1u)) nq_flag_bit(G, tx, ty, threadIdx.x, fnxt, &stats[NQ_FLAGGED + (cur ^ 1)]);
-    if (threadIdx.x == 0) {
-        fcur[t] = 0u;
-        atomicAdd(&stats[NQ_FLAGGED + cur], ~0ull);                   // (- 1)
-        atomicAdd(&stats[NQ_VISITS], 1ull);
-        atomicMax(&stats[NQ_ROUNDS], round + 1ull);
-    }
+    navfield_publish(G.ntx, G.nty, lowered ? navfield_seers<NQ_TILE>(lx, ly) : 0u, &seers, fcur, fnxt, stats, NQ_SUMS, cur, round);
 }
 
 // ---- stats and projection: one thread per cell (steps 8 and 10) ---------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_navpose_stats(NavPoseGrid G, const uint32_t* __restrict__ cost, uint32_t* __restrict__ cell_cost,
                                                        uint8_t* __restrict__ cell_bin, unsigned long long* __restrict__ stats) {
-    __shared__ unsigned long long red[4];
     const size_t P = (size_t)G.W * G.H, p = (size_t)blockIdx.x * 256 + threadIdx.x;
     unsigned long long reached = 0, cells = 0, mx = 0;
     if (p < P) {
@@ -242,14 +187,8 @@ __global__ __launch_bounds__(256) void k_navpose_stats(NavPoseGrid G, const uint
         cell_cost[p] = best; cell_bin[p] = (uint8_t)bin;
         cells = reached != 0;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long u = __shfl_xor(mx, o, 64); mx = u > mx ? u : mx; }
-    if (lane() == 0) red[threadIdx.x >> 6] = mx;
-    nq_block_sums3(reached, cells, 0ull, stats, NQ_REACHED);          // (its barrier orders red as well; the zero adds nothing to NQ_MAXCOST)
-    if (threadIdx.x == 3) {
-        const unsigned long long a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
-        if ((a > b ? a : b) > 0ull) atomicMax(&stats[NQ_MAXCOST], a > b ? a : b);
-    }
+    block_sums({reached, cells}, stats, NQ_REACHED);
+    navfield_block_max(mx, &stats[NQ_MAXCOST]);
 }
 
 // ---- trace: one wave per start (step 9) -----------------------------------------------------------------------------------------------
@@ -280,14 +219,14 @@ __global__ __launch_bounds__(256) void k_navpose_trace(NavPoseGrid G, NavPoseMov
             uint32_t cq = NQ_INF;
             if (ln < 8) {
                 const uint32_t code = (nq_codes(mv, b) >> (2 * ln)) & 3u;
-                const int dx = nq_dx(ln), dy = nq_dy(ln), qx = x + dx, qy = y + dy;
+                const int dx = navfield_dx(ln), dy = navfield_dy(ln), qx = x + dx, qy = y + dy;
                 if (code && qx >= 0 && qx < G.W && qy >= 0 && qy < G.H) {
                     const uint2 pq = pk[(size_t)qy * G.W + qx];
                     bool ok = (pq.x >> b) & 1u;
                     if (ok && ln >= 4) ok = ((pk[(size_t)y * G.W + qx].x >> b) & 1u) && ((pk[(size_t)qy * G.W + x].x >> b) & 1u);
                     if (ok) {
                         cq = cost[(size_t)b * P + (size_t)qy * G.W + qx];
-                        if (cq != NQ_INF) key = ((unsigned long long)(cq + nq_w(ln) + pq.y + (code == 2u ? rev : 0u)) << 4) | (unsigned long long)ln;
+                        if (cq != NQ_INF) key = ((unsigned long long)(cq + navfield_w(ln) + pq.y + (code == 2u ? rev : 0u)) << 4) | (unsigned long long)ln;
                     }
                 }
             } else if (ln < 10 && B > 1) {
@@ -301,20 +240,16 @@ __global__ __launch_bounds__(256) void k_navpose_trace(NavPoseGrid G, NavPoseMov
             if (key == ~0ull) { status = 3; break; }                  // (not on a settled field: a state of finite cost > 0 has such a successor)
             const int k = (int)(key & 15ull);
             c = __shfl(cq, k, 64);
-            if (k < 8) { x += nq_dx(k); y += nq_dy(k); }
+            if (k < 8) { x += navfield_dx(k); y += navfield_dy(k); }
             else b = (k == 8 ? b + 1 : b - 1) & (B - 1);
         }
     }
     if (ln == 0) { start_cost[w] = c0; start_status[w] = status; path_len[w] = len; }
 }
 
-static int navpose_log2(int B) {
-    for (int lg = 0; lg <= 5; lg++) if (B == (1 << lg)) return lg;
-    return -1;
-}
 // the move table of the header's steps 3 and 5; nullptr when it is made, else what is wrong
 static const char* navpose_moves(int B, int move_tol, int allow_reverse, int8_t* out) {
-    if (navpose_log2(B) < 0) return "n_headings must be 1, 2, 4, 8, 16 or 32";
+    if (nav_log2_bins(B) < 0) return "n_headings must be 1, 2, 4, 8, 16 or 32";
     if (move_tol < 0 || move_tol > 256) return "move_tol must be 0..256";
     if (allow_reverse != 0 && allow_reverse != 1) return "allow_reverse must be 0 or 1";
     static const int A[8] = {0, 256, 512, 768, 128, 384, 640, 896};
@@ -350,7 +285,7 @@ int ssf_navpose_field(ssf_handle* h, const ssf_navpose_params* p, const uint32_t
     if (!free_mask || !dist2) return refuse("free_mask or dist2 is NULL");
     if (!out || (!out->cost && !out->cell_cost && !out->cell_bin && !out->start_cost && !out->start_status && !out->path_len && !out->path))
         return refuse("every output is NULL");
-    const int lg = navpose_log2(p->n_headings);
+    const int lg = nav_log2_bins(p->n_headings);
     if (lg < 0) return refuse("n_headings must be 1, 2, 4, 8, 16 or 32");
     if (p->width < 1 || p->width > 4096 || p->height < 1 || p->height > 4096) return refuse("the grid's size must be 1..4096 x 1..4096");
     const size_t P = (size_t)p->width * p->height, N = P * (size_t)p->n_headings;
@@ -390,17 +325,12 @@ int ssf_navpose_field(ssf_handle* h, const ssf_navpose_params* p, const uint32_t
     // the working buffers; a call with device arrays relaxes the caller's field and projects into the caller's arrays
     NavPoseWs& w = h->navpose;
     const bool own_cost = !(dev && out->cost);
-    bool ok = true;
-    if (!w.stats) ok = w.bufs.grow({{(void**)&w.stats, NQ_STATS * sizeof(unsigned long long)}, {(void**)&w.goals, 65536 * 3 * sizeof(int32_t)},
-                                    {(void**)&w.starts, 4096 * 3 * sizeof(int32_t)}, {(void**)&w.start_cost, 4096 * sizeof(uint32_t)},
-                                    {(void**)&w.start_status, 4096 * sizeof(int32_t)}, {(void**)&w.path_len, 4096 * sizeof(int32_t)}});
+    bool ok = navfield_reserve(w, NQ_STATS, 3, tiles, dev ? 0 : path_words);
     if (ok && P > w.cells) {
         ok = w.bufs.grow({{(void**)&w.mask, 4 * P}, {(void**)&w.dist2, 4 * P}, {(void**)&w.pk, 8 * P}, {(void**)&w.cell_cost, 4 * P}, {(void**)&w.cell_bin, P}});
         if (ok) w.cells = P;
     }
     if (ok && own_cost && N > w.states) { ok = w.bufs.grow({{(void**)&w.cost, 4 * N}}); if (ok) w.states = N; }
-    if (ok && tiles > w.tiles) { ok = w.bufs.grow({{(void**)&w.flags, 2 * tiles * sizeof(uint32_t)}}); if (ok) w.tiles = tiles; }
-    if (ok && !dev && path_words > w.path_words) { ok = w.bufs.grow({{(void**)&w.path, path_words * sizeof(int32_t)}}); if (ok) w.path_words = path_words; }
     if (!ok) { h->err = "ssf_navpose_field: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
 
     hipStream_t st = h->stream;
@@ -432,22 +362,14 @@ int ssf_navpose_field(ssf_handle* h, const ssf_navpose_params* p, const uint32_t
     HCK(hipGetLastError());
     // the rounds: round r reads the flags of array r & 1 and sets those of the other; the host looks once per batch
     const size_t lds = (size_t)(2 + B) * NQ_WIN_CELLS * sizeof(uint32_t);
-    const long long limit = (long long)N + 2;
-    long long round = 0;
-    for (;;) {
-        unsigned long long flagged = 0;
-        HCK(hipMemcpyAsync(&flagged, w.stats + NQ_FLAGGED + (round & 1), sizeof(flagged), hipMemcpyDeviceToHost, st));
-        { int rc = sync_collect(h); if (rc) return rc; }
-        if (flagged == 0) break;
-        if (round >= limit) { h->err = "ssf_navpose_field: the field did not converge"; return SSF_ERR_DEVICE; }
-        for (int i = 0; i < SSF_NAVPOSE_ROUND_BATCH && round < limit; i++, round++) {
+    {
+        int rc = navfield_rounds(h, "ssf_navpose_field", w.stats, NQ_FLAGGED, (long long)N + 2, SSF_NAVPOSE_ROUND_BATCH, [&](long long round, int cur) {
             ScopedKernel sk("navpose_relax", st);
-            const int cur = (int)(round & 1);
             hipLaunchKernelGGL(k_navpose_relax, dim3((unsigned)tiles), dim3(256), lds, st, G, mv, (uint32_t)p->reverse_cost, (uint32_t)p->turn_cost,
                                (const uint2*)d_pk, d_cost, w.flags + (size_t)cur * tiles, w.flags + (size_t)(cur ^ 1) * tiles, w.stats, cur,
                                (unsigned long long)round);
-            HCK(hipGetLastError());
-        }
+        });
+        if (rc) return rc;
     }
     {
         ScopedKernel sk("navpose_stats", st);
@@ -465,24 +387,13 @@ int ssf_navpose_field(ssf_handle* h, const ssf_navpose_params* p, const uint32_t
     // the outputs
     const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     unsigned long long s[NQ_STATS];
-    int32_t lens[4096];                                               // (n_starts <= 4096)
     HCK(hipMemcpyAsync(s, w.stats, sizeof(s), hipMemcpyDeviceToHost, st));
     if (out->cost && out->cost != d_cost) HCK(hipMemcpyAsync(out->cost, d_cost, 4 * N, kind, st));
     if (out->cell_cost && out->cell_cost != d_cell_cost) HCK(hipMemcpyAsync(out->cell_cost, d_cell_cost, 4 * P, kind, st));
     if (out->cell_bin && out->cell_bin != d_cell_bin) HCK(hipMemcpyAsync(out->cell_bin, d_cell_bin, P, kind, st));
-    if (ns > 0) {
-        if (out->start_cost) HCK(hipMemcpyAsync(out->start_cost, w.start_cost, 4 * (size_t)ns, kind, st));
-        if (out->start_status) HCK(hipMemcpyAsync(out->start_status, w.start_status, 4 * (size_t)ns, kind, st));
-        if (out->path_len) HCK(hipMemcpyAsync(out->path_len, w.path_len, 4 * (size_t)ns, kind, st));
-        if (want_path && !dev) { HCK(hipMemcpyAsync(lens, w.path_len, 4 * (size_t)ns, hipMemcpyDeviceToHost, st)); }
-    }
-    { int rc = sync_collect(h); if (rc) return rc; }
-    if (want_path && !dev) {                                          // entries past path_len are not written: each path's states, no more
-        for (int i = 0; i < ns; i++)
-            if (lens[i] > 0)
-                HCK(hipMemcpyAsync(out->path + (size_t)i * p->max_path * 3, w.path + (size_t)i * p->max_path * 3, 12 * (size_t)lens[i],
-                                   hipMemcpyDeviceToHost, st));
-        HCK(hipStreamSynchronize(st));
+    {
+        int rc = navfield_copy_out(h, w, ns, p->max_path, 3, kind, out->start_cost, out->start_status, out->path_len, want_path && !dev ? out->path : nullptr);
+        if (rc) return rc;
     }
     if (stats) {
         stats->states_traversable = (int64_t)s[NQ_NTRAV]; stats->states_reached = (int64_t)s[NQ_REACHED]; stats->cells_reached = (int64_t)s[NQ_CELLS];

@@ -98,7 +98,6 @@ __device__ __forceinline__ void ns_roll_body(const NavSteerRule& r, const Cells&
                                              const int32_t* __restrict__ targets, unsigned long long* __restrict__ keys, int32_t* __restrict__ n_adm,
                                              const NavSteerCand& out, unsigned long long* __restrict__ stats) {
     __shared__ unsigned long long s_key[4];
-    __shared__ unsigned long long red[4][4];
     const int t = threadIdx.x, pose = blockIdx.y;
     const int c = (int)blockIdx.x * 256 + t;
     unsigned long long key = ~0ull, n_ok = 0, n_coll = 0, n_steps = 0, n_hooked = 0;
@@ -141,13 +140,7 @@ __device__ __forceinline__ void ns_roll_body(const NavSteerRule& r, const Cells&
     }
     // the chunk's winner and sums
     key = wave_min64(key);
-    n_ok = wave_sum(n_ok); n_coll = wave_sum(n_coll); n_steps = wave_sum(n_steps);
-    const int wv = t >> 6;
-    if (lane() == 0) { s_key[wv] = key; red[0][wv] = n_ok; red[1][wv] = n_coll; red[2][wv] = n_steps; }
-    if constexpr (Hook::counts) {
-        n_hooked = wave_sum(n_hooked);
-        if (lane() == 0) red[3][wv] = n_hooked;
-    }
+    if (lane() == 0) s_key[t >> 6] = key;
     __syncthreads();
     if (t == 0) {
         const unsigned long long a = s_key[0] < s_key[1] ? s_key[0] : s_key[1], b = s_key[2] < s_key[3] ? s_key[2] : s_key[3];
@@ -155,16 +148,9 @@ __device__ __forceinline__ void ns_roll_body(const NavSteerRule& r, const Cells&
         if (m != ~0ull) atomicMin(&keys[pose], m);
         if (start_ok) atomicAdd(&stats[staged ? NS_STAGED : NS_GLOBAL], 1ull);
     }
-    if (t >= 1 && t < 4) {
-        const unsigned long long sum = (red[t - 1][0] + red[t - 1][1]) + (red[t - 1][2] + red[t - 1][3]);
-        if (sum) atomicAdd(&stats[NS_ADM + (t - 1)], sum);
-        if (t == 1 && sum) atomicAdd(&n_adm[pose], (int32_t)sum);
-    }
-    if constexpr (Hook::counts)
-        if (t == 4) {
-            const unsigned long long sum = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]);
-            if (sum) atomicAdd(&stats[NS_HOOKED], sum);
-        }
+    const unsigned long long sum = block_sums({n_ok, n_coll, n_steps}, stats, NS_ADM);
+    if (t == 0 && sum) atomicAdd(&n_adm[pose], (int32_t)sum);         // (thread 0 holds the first sum)
+    if constexpr (Hook::counts) block_sums({n_hooked}, stats, NS_HOOKED);
 }
 
 // steps 7 and 8 of one workgroup of 256, one lane per pose.  start(cx, cy, heading): the start cell's test (the cell is in the grid);
@@ -173,7 +159,6 @@ template <class Cells, class Hook, class Start>
 __device__ __forceinline__ void ns_pick_body(const NavSteerRule& r, const Cells& cells, Hook hook, Start start, const int32_t* __restrict__ poses,
                                              const uint32_t* __restrict__ dirs, const unsigned long long* __restrict__ keys,
                                              const int32_t* __restrict__ n_adm, const NavSteerPose& out, unsigned long long* __restrict__ stats) {
-    __shared__ unsigned long long red[4][4];
     const int pose = (int)blockIdx.x * 256 + threadIdx.x;
     unsigned long long n_ok = 0, n_blocked = 0, n_stuck = 0;
     if (pose < r.n_poses) {
@@ -208,14 +193,7 @@ __device__ __forceinline__ void ns_pick_body(const NavSteerRule& r, const Cells&
         hook.pick(pose, status == 0);
         n_ok = status == 0; n_blocked = status == 1 || status == 2; n_stuck = status == 3;
     }
-    n_ok = wave_sum(n_ok); n_blocked = wave_sum(n_blocked); n_stuck = wave_sum(n_stuck);
-    const int wv = threadIdx.x >> 6;
-    if (lane() == 0) { red[0][wv] = n_ok; red[1][wv] = n_blocked; red[2][wv] = n_stuck; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const unsigned long long sum = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
-        if (sum) atomicAdd(&stats[NS_OK + threadIdx.x], sum);
-    }
+    block_sums({n_ok, n_blocked, n_stuck}, stats, NS_OK);
 }
 
 // ---- the disc (ssf_navsteer.h step 3) ------------------------------------------------------------------------------------------------
@@ -361,12 +339,7 @@ inline bool navsteer_reserve_pk(ssf_handle* h, size_t P) {
     w.cells = P;
     return true;
 }
-// the footprint: log2 of a legal n_headings (else -1), and the 8-byte packed grid of h->navfoot
-inline int navfoot_log2(int B) {
-    for (int k = 0; k <= 5; k++)
-        if (B == 1 << k) return k;
-    return -1;
-}
+// the footprint: the 8-byte packed grid of h->navfoot (log2 of a legal n_headings: nav_log2_bins, ssf_navgrid.hpp)
 inline bool navfoot_reserve_pk(ssf_handle* h, size_t P) {
     NavFootWs& w = h->navfoot;
     if (P <= w.pk_cells) return true;

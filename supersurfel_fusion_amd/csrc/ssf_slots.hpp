@@ -71,6 +71,27 @@ __device__ __forceinline__ int block_rank256(bool mine, int* part) {
     return before;
 }
 
+// The sums of N counters over a workgroup of WAVES waves (256 threads unless told otherwise), added to stats[(first + k) * stride];
+// a sum of zero adds nothing, so an idle workgroup issues no atomic.  ALL threads call it, as with the two helpers above.  It owns
+// its LDS and opens with a barrier, so a kernel may call it more than once; a caller's own LDS is NOT ordered by its barriers.
+// Threads 0 .. N - 1 add in ONE atomic instruction (sums that share a cache line then cost one request, not N); thread k < N gets
+// sum k back, every other thread 0.  (Integers: no order can change the result.)
+template <int N, int WAVES = 4>
+__device__ __forceinline__ unsigned long long block_sums(const unsigned long long (&v)[N], unsigned long long* __restrict__ stats, int first, int stride = 1) {
+    __shared__ unsigned long long red[N][WAVES];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; k++) { const unsigned long long s = wave_sum(v[k]); if (lane() == 0) red[k][threadIdx.x >> 6] = s; }
+    __syncthreads();
+    unsigned long long mine = 0;
+    if (threadIdx.x < N) {
+#pragma unroll
+        for (int w = 0; w < WAVES; w++) mine += red[threadIdx.x][w];
+        if (mine) atomicAdd(&stats[(first + (int)threadIdx.x) * stride], mine);
+    }
+    return mine;
+}
+
 // the logical index ([visible | out-of-view], ssf_get_model's order) of slot s = blockIdx.x * 256 + threadIdx.x: slot order is
 // logical order, so a visible slot is its own index and an out-of-view slot's is n_visible + (live rows in front of it) =
 // bc[its block] (exclusive scan of the blocks' live counts) + its rank inside the block.  holds = slot_row's answer.  (The

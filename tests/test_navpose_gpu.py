@@ -149,6 +149,33 @@ def test_the_field_the_projection_and_the_paths(name, fusion):
     assert got["stats"]["rounds"] >= (1 if s["goals_used"] else 0) and got["stats"]["tile_visits"] >= got["stats"]["rounds"]
 
 
+def narrow_last_tile(h, w, B):
+    """dict(mask, dist2, goals, starts, kw, want): a free grid with a handful of fixed obstacle cells, the goal in the last column --
+    which is one cell wide at 17 and 33 columns -- and the start in the opposite corner; every move allowed, so B = 1 reaches it"""
+    def make():
+        state = np.zeros((h, w), np.int8)
+        for x, y in ((5, 3), (9, 9), (15, 8), (16, 2), (2, 15), (20, 7), (31, 12), (32, 3)):
+            if x < w and y < h: state[y, x] = 100
+        dist2 = ((7 * np.arange(w)[None, :] + 3 * np.arange(h)[:, None]) % 41).astype(np.int32)
+        mask = qr.point_mask(state, 0, B)
+        kw = dict(n_headings=B, move_tol=256, max_path=4096)
+        goals, starts = np.array([(w - 1, h - 1, -1)], np.int32), np.array([(512, 512, 0)], np.int32)
+        return dict(mask=mask, dist2=dist2, goals=goals, starts=starts, kw=kw, want=qr.plan(mask, dist2, goals, starts, **kw))
+    return qr.cached(("narrow last tile", h, w, B), make)
+
+
+@pytest.mark.parametrize("B", [1, 32])
+@pytest.mark.parametrize("h,w", [(1, 1), (17, 17), (16, 33)])
+def test_a_last_tile_column_or_row_one_cell_wide(h, w, B, fusion):
+    """the smallest grids at which the seers of a tile's edge cells and the flags of its neighbours can go wrong: the goal's tile is
+    one cell wide (17 x 17: and one cell high), so every round's news crosses a tile boundary at once"""
+    c = narrow_last_tile(h, w, B)
+    want = c["want"]
+    assert want["stats"]["goals_used"] == 1 and want["start_status"][0] == qr.STATUS_REACHED        # (no all-INF field passes)
+    assert want["path_len"][0] >= max(h, w) and want["stats"]["cells_reached"] == int(want["trav"].any(axis=0).sum())
+    same(fusion.nav_pose_plan(c["mask"], c["dist2"], c["goals"], c["starts"], **c["kw"]), want, (h, w, B))
+
+
 def test_a_serpentine_that_needs_more_rounds_than_one_batch(fusion):
     """one-cell corridors that cross the boundary between two tile columns once per lane: every crossing costs a round, so the field
     settles only in the host's second batch of rounds or later"""
