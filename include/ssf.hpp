@@ -34,6 +34,7 @@
 #include "ssf_navfoot.h"
 #include "ssf_navpose.h"
 #include "ssf_navdyn.h"
+#include "ssf_navmem.h"
 #include "ssf_raycast.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
@@ -373,6 +374,21 @@ struct LiveParams {
 struct LiveNavGrid : NavGrid {
     std::vector<uint32_t> live_hits, live_seen;
     ssf_navlive_stats live;
+};
+/* The caller's memory of the live layer (ssf_navmem.h; exported by libssf_hip_mem.so, linked INSTEAD of the other libraries -- a program
+ * that does not call the overlayDepthFrame overloads that take one links as before): per cell the marked height slices of the body's
+ * band, the tick of the last stamp and the tick at which the cell was last seen through.  The handle keeps nothing of it: the overloads
+ * read it, write it back and record the call's tick and stats.  It sizes itself to the grid of the first call; a grid of another size
+ * starts it afresh, and so does clear().  It lives in the grid's frame and does not scroll: keep the grid's pose, or clear it. */
+struct LiveMemory {
+    int slices = 16;                               /* 1..32 height slices of the band */
+    uint32_t max_mark_age = 0, max_seen_age = 0;   /* ticks after which a mark / a seen-through cell expires; 0 = never */
+    int width = 0, height = 0;
+    std::vector<uint32_t> marks, mark_tick, seen_tick;
+    uint32_t tick = 0;                             /* of the last update; 0 = none yet */
+    ssf_navmem_stats stats = ssf_navmem_stats();   /* of the last update */
+    std::vector<uint32_t> hit_bits, seen_bits;     /* the last frame's evidence per cell and slice */
+    void clear() { width = height = 0; marks.clear(); mark_tick.clear(); seen_tick.clear(); hit_bits.clear(); seen_bits.clear(); tick = 0; }
 };
 
 /* steerOnGrid (ssf_navsteer.h; exported by libssf_hip_steer.so, linked INSTEAD of the other libraries -- a program that does not call
@@ -999,7 +1015,91 @@ public:
         overlay_depth(g, q, d.ptr<float>(), n, mk, out);
     }
 #endif
+    /* ... into a layer that REMEMBERS (ssf_navmem.h): the frame marks height slices of the band in mem, the rays that see through a
+     * slice clear it, marks and seen-through cells older than mem's ages expire, and out is g -- the STATIC grid of every frame, the
+     * map's own, not an earlier out -- with the marked cells occupied and the seen-through cells opened.  tick: >= 1 and monotone (a
+     * frame counter).  q.min_seen and q.want_seen have no part in it; out.live_hits holds the frame's points per cell, out.live_seen
+     * stays empty (mem.seen_bits has the slices seen through), out.live the counts both calls share, mem.stats all of them. */
+    void overlayDepthFrame(const NavGrid& g, const LiveParams& q, const std::vector<float>& depth_m, const std::vector<uint8_t>& mask, LiveMemory& mem,
+                           uint32_t tick, LiveNavGrid& out) {
+        if (depth_u16_) throw std::logic_error("overlayDepthFrame: the input format is uint16 depth; pass the counts as std::vector<uint16_t>");
+        remember_depth(g, q, depth_m.data(), depth_m.size(), mask, mem, tick, out);
+    }
+    void overlayDepthFrame(const NavGrid& g, const LiveParams& q, const std::vector<uint16_t>& depth_counts, const std::vector<uint8_t>& mask,
+                           LiveMemory& mem, uint32_t tick, LiveNavGrid& out) {
+        if (!depth_u16_) throw std::logic_error("overlayDepthFrame(uint16_t depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+        remember_depth(g, q, depth_counts.data(), depth_counts.size(), mask, mem, tick, out);
+    }
+#if defined(CV_VERSION) && defined(CV_32FC1) && defined(CV_8UC1)
+    void overlayDepthFrame(const NavGrid& g, const LiveParams& q, const cv::Mat& depth_h, const cv::Mat& mask_h, LiveMemory& mem, uint32_t tick,
+                           LiveNavGrid& out) {
+        const cv::Mat d = depth_h.isContinuous() ? depth_h : depth_h.clone(), m = mask_h.isContinuous() ? mask_h : mask_h.clone();
+        const size_t n = (size_t)d.rows * (size_t)d.cols;
+        const bool masked = m.rows != 0 || m.cols != 0;
+        if (masked && (m.type() != CV_8UC1 || m.rows != d.rows || m.cols != d.cols)) throw std::invalid_argument("overlayDepthFrame: the mask must be CV_8UC1 of the depth image's size");
+        std::vector<uint8_t> mk;
+        if (masked) mk.assign(m.ptr<uint8_t>(), m.ptr<uint8_t>() + n);
+#ifdef CV_16UC1
+        if (d.type() == CV_16UC1) {
+            if (!depth_u16_) throw std::logic_error("overlayDepthFrame(CV_16UC1 depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
+            remember_depth(g, q, d.ptr<uint16_t>(), n, mk, mem, tick, out);
+            return;
+        }
+#endif
+        if (d.type() != CV_32FC1) throw std::invalid_argument("overlayDepthFrame: the depth image must be CV_32FC1 or CV_16UC1");
+        if (depth_u16_) throw std::logic_error("overlayDepthFrame: the input format is uint16 depth; pass a CV_16UC1 image");
+        remember_depth(g, q, d.ptr<float>(), n, mk, mem, tick, out);
+    }
+#endif
 private:
+    void remember_depth(const NavGrid& g, const LiveParams& q, const void* depth, size_t n_depth, const std::vector<uint8_t>& mask, LiveMemory& mem,
+                        uint32_t tick, LiveNavGrid& out) {
+        const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
+        if (n == 0 || g.state.size() != n) throw std::logic_error("overlayDepthFrame: the grid has no state (want_state)");
+        const size_t npix = q.width > 0 ? (size_t)q.width * (size_t)(q.height > 0 ? q.height : 0) : (size_t)width_ * (size_t)height_;
+        if (n_depth != npix) throw std::invalid_argument("overlayDepthFrame: the depth image must be width x height of the camera");
+        if (!mask.empty() && mask.size() != npix) throw std::invalid_argument("overlayDepthFrame: the mask must be width x height of the camera");
+        if (mem.width != g.width || mem.height != g.height || mem.marks.size() != n || mem.mark_tick.size() != n || mem.seen_tick.size() != n) {
+            mem.clear();
+            mem.width = g.width; mem.height = g.height;
+            mem.marks.assign(n, 0u); mem.mark_tick.assign(n, 0u); mem.seen_tick.assign(n, 0u);
+        }
+        ssf_navmem_params p;
+        check(ssf_navmem_default_params(need(), &p));
+        float cam[12];
+        if (q.cam_pose) { transform3_to_rt(*q.cam_pose, cam); p.cam_pose = cam; }
+        p.grid_pose = g.stats.pose; p.width = g.width; p.height = g.height; p.res = g.res;
+        p.floor_max = q.floor_max; p.z_max = q.z_max; p.max_dist_cells = q.max_dist_cells; p.unknown_is_obstacle = q.unknown_is_obstacle ? 1 : 0;
+        p.fx = q.fx; p.fy = q.fy; p.cx = q.cx; p.cy = q.cy; p.cam_width = q.width; p.cam_height = q.height; p.t_min = q.t_min; p.t_max = q.t_max;
+        p.mask_mode = q.mask_mode; p.min_hits = q.min_hits; p.stride = q.stride; p.hit_margin_cells = q.hit_margin_cells;
+        p.open_unknown = q.open_unknown ? 1 : 0; p.on_device = 0; p.frame_on_device = 0;
+        p.slices = mem.slices; p.tick = tick; p.max_mark_age = mem.max_mark_age; p.max_seen_age = mem.max_seen_age;
+        std::vector<int8_t> state(n);                             /* (g may be out itself) */
+        std::vector<uint32_t> hits(q.want_hits ? n : 0), hit_bits(n), seen_bits(n);
+        std::vector<int32_t> dist2(q.want_dist2 ? n : 0);
+        ssf_navmem_layer in;
+        in.marks = mem.marks.data(); in.mark_tick = mem.mark_tick.data(); in.seen_tick = mem.seen_tick.data();
+        ssf_navmem_out o;
+        o.marks = mem.marks.data(); o.mark_tick = mem.mark_tick.data(); o.seen_tick = mem.seen_tick.data();      /* the update in place */
+        o.live_hits = q.want_hits ? hits.data() : nullptr; o.hit_bits = hit_bits.data(); o.seen_bits = seen_bits.data();
+        o.state = state.data(); o.dist2 = q.want_dist2 ? dist2.data() : nullptr;
+        ssf_navmem_stats st;
+        check(ssf_navmem_update(need(), &p, depth, mask.empty() ? nullptr : mask.data(), g.state.data(), &in, &o, &st));
+        mem.tick = tick; mem.stats = st; mem.hit_bits.swap(hit_bits); mem.seen_bits.swap(seen_bits);
+        out.width = g.width; out.height = g.height; out.res = g.res;
+        out.zmin.clear(); out.zmax.clear(); out.hits.clear();
+        out.state.swap(state); out.dist2.swap(dist2); out.live_hits.swap(hits); out.live_seen.clear();
+        ssf_navlive_stats ls = ssf_navlive_stats();
+        ls.pixels_valid = st.pixels_valid; ls.pixels_stamping = st.pixels_stamping; ls.points_in_band = st.points_in_band; ls.rays = st.rays;
+        ls.rays_carving = st.rays_carving; ls.ray_samples = st.ray_samples; ls.cells_opened = st.cells_opened; ls.cells_free = st.cells_free;
+        ls.cells_occupied = st.cells_occupied; ls.cells_unknown = st.cells_unknown; ls.atomics = st.atomics;
+        std::copy(st.pose, st.pose + 12, ls.pose);
+        out.live = ls;
+        ssf_navgrid_stats gs = ssf_navgrid_stats();
+        gs.cells_free = st.cells_free; gs.cells_occupied = st.cells_occupied; gs.cells_unknown = st.cells_unknown;
+        std::copy(st.pose, st.pose + 12, gs.pose);
+        out.stats = gs;
+    }
     void overlay_depth(const NavGrid& g, const LiveParams& q, const void* depth, size_t n_depth, const std::vector<uint8_t>& mask, LiveNavGrid& out) {
         const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
         if (n == 0 || g.state.size() != n) throw std::logic_error("overlayDepthFrame: the grid has no state (want_state)");

@@ -41,6 +41,9 @@ POSE_LIB = os.path.join(_HERE, "csrc", "libssf_hip_pose.so")
 # pose's objects and steering among movers (include/ssf_navdyn.h): the one library of a robot that also drives among people.  None
 # of the nine libraries above exports the movers' entry points
 DYN_LIB = os.path.join(_HERE, "csrc", "libssf_hip_dyn.so")
+# dyn's objects and the live layer with memory (include/ssf_navmem.h): the one library of a robot whose live obstacles outlive their
+# time in view and are cleared when seen through.  None of the ten libraries above exports the memory's entry points
+MEM_LIB = os.path.join(_HERE, "csrc", "libssf_hip_mem.so")
 
 
 class SsfConfig(C.Structure):
@@ -155,6 +158,12 @@ NAVPATH_FORCED = 1 << 30             # bit 30 of a waypoint's index word: the se
 NAVLIVE_SYMBOLS = ["ssf_navlive_default_params", "ssf_navlive_overlay"]
 NAVLIVE_OUTPUTS = (("live_hits", np.uint32), ("live_seen", np.uint32), ("state", np.int8), ("dist2", np.int32))
 NAVLIVE_OUTPUT_NAMES = tuple(nm for nm, _ in NAVLIVE_OUTPUTS)
+# the live layer with memory (include/ssf_navmem.h): exported by libssf_hip_mem.so only (load_mem)
+NAVMEM_SYMBOLS = ["ssf_navmem_default_params", "ssf_navmem_update"]
+NAVMEM_LAYER_NAMES = ("marks", "mark_tick", "seen_tick")
+NAVMEM_OUTPUTS = (("marks", np.uint32), ("mark_tick", np.uint32), ("seen_tick", np.uint32), ("live_hits", np.uint32), ("hit_bits", np.uint32),
+                  ("seen_bits", np.uint32), ("state", np.int8), ("dist2", np.int32))
+NAVMEM_OUTPUT_NAMES = tuple(nm for nm, _ in NAVMEM_OUTPUTS)
 # the velocity commands (include/ssf_navsteer.h): exported by libssf_hip_steer.so only (load_steer)
 NAVSTEER_SYMBOLS = ["ssf_navsteer_rollouts", "ssf_navsteer_default_params", "ssf_navsteer_direction_table"]
 # (name, dtype, per pose or per candidate, trailing shape; 'T1' = n_steps + 1)
@@ -416,6 +425,40 @@ class SsfNavLiveStats(C.Structure):
     """ssf_navlive_stats (include/ssf_navlive.h)"""
     _fields_ = [(nm, C.c_int64) for nm in ("pixels_valid", "pixels_stamping", "points_in_band", "rays", "rays_carving", "ray_samples",
                                            "ray_entries", "cells_stamped", "cells_opened", "cells_free", "cells_occupied", "cells_unknown",
+                                           "atomics")] + [("pose", C.c_float * 12)]
+
+    def as_dict(self):
+        d = {nm: int(getattr(self, nm)) for nm, _ in self._fields_ if nm != "pose"}
+        d["pose"] = np.array(self.pose, np.float32)
+        return d
+
+
+class SsfNavMemParams(C.Structure):
+    """ssf_navmem_params (include/ssf_navmem.h)"""
+    _fields_ = [("grid_pose", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("res", C.c_float), ("floor_max", C.c_float),
+                ("z_max", C.c_float), ("max_dist_cells", C.c_int), ("unknown_is_obstacle", C.c_int), ("cam_pose", C.c_void_p),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("cam_width", C.c_int), ("cam_height", C.c_int),
+                ("t_min", C.c_float), ("t_max", C.c_float), ("mask_mode", C.c_int), ("min_hits", C.c_int), ("stride", C.c_int),
+                ("hit_margin_cells", C.c_float), ("open_unknown", C.c_int), ("slices", C.c_int), ("tick", C.c_uint32),
+                ("max_mark_age", C.c_uint32), ("max_seen_age", C.c_uint32), ("on_device", C.c_int),
+                ("frame_on_device", C.c_int)]
+
+
+class SsfNavMemLayer(C.Structure):
+    """ssf_navmem_layer (include/ssf_navmem.h)"""
+    _fields_ = [(nm, C.c_void_p) for nm in NAVMEM_LAYER_NAMES]
+
+
+class SsfNavMemOut(C.Structure):
+    """ssf_navmem_out (include/ssf_navmem.h)"""
+    _fields_ = [(nm, C.c_void_p) for nm in NAVMEM_OUTPUT_NAMES]
+
+
+class SsfNavMemStats(C.Structure):
+    """ssf_navmem_stats (include/ssf_navmem.h)"""
+    _fields_ = [(nm, C.c_int64) for nm in ("pixels_valid", "pixels_stamping", "points_in_band", "rays", "rays_carving", "ray_samples",
+                                           "cells_marked", "cells_newly_marked", "cells_cleared", "cells_expired", "bits_cleared",
+                                           "cells_remembered", "cells_opened", "cells_free", "cells_occupied", "cells_unknown",
                                            "atomics")] + [("pose", C.c_float * 12)]
 
     def as_dict(self):
@@ -735,6 +778,11 @@ class Library:
             L.ssf_navdyn_foot_rollouts.argtypes = [vp, sp, dp, C.c_int, vp, vp, vp, vp, vp, vp] + tail
             L.ssf_navdyn_default_blob_params.argtypes = [vp, C.POINTER(SsfNavDynBlobParams)]
             L.ssf_navdyn_blobs.argtypes = [vp, C.POINTER(SsfNavDynBlobParams), vp, vp, vp, vp, C.POINTER(SsfNavDynBlobStats)]
+        self.has_navmem = all(hasattr(L, nm) for nm in NAVMEM_SYMBOLS)
+        if self.has_navmem:
+            L.ssf_navmem_default_params.argtypes = [vp, C.POINTER(SsfNavMemParams)]
+            L.ssf_navmem_update.argtypes = [vp, C.POINTER(SsfNavMemParams), vp, vp, vp, C.POINTER(SsfNavMemLayer), C.POINTER(SsfNavMemOut),
+                                            C.POINTER(SsfNavMemStats)]
         self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
         if self.has_navgrid:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
@@ -946,6 +994,59 @@ def load_dyn():
     call nav_dyn_steer, nav_dyn_blobs or nav_live_dyn_steer on it.  Fails loudly when it has not been built."""
     import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
     return Library(DYN_LIB)
+
+
+def load_mem():
+    """Load libssf_hip_mem.so: dyn's objects (the product and every navigation call up to steering among movers) with the live layer
+    with memory linked in (include/ssf_navmem.h).  A handle belongs to the library that created it: create the Fusion from THIS library
+    to call nav_memory, nav_memory_plan or nav_memory_dyn_steer on it.  Fails loudly when it has not been built."""
+    import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
+    return Library(MEM_LIB)
+
+
+class LiveMemory:
+    """The caller's memory of the live layer (include/ssf_navmem.h): marks, mark_tick and seen_tick, each height x width uint32, as
+    numpy arrays (device=False) or torch tensors on the device, and the tick of the last update (0: none yet).  The handle keeps
+    nothing of it: Fusion.nav_memory and its siblings read it, write it back in place and advance the tick."""
+
+    def __init__(self, width, height, device=False):
+        self.width, self.height, self.device = int(width), int(height), bool(device)
+        if self.width < 1 or self.height < 1:
+            raise SsfError("LiveMemory needs width and height >= 1, got %d x %d" % (self.width, self.height))
+        if self.device:
+            import torch
+            zeros = lambda: torch.zeros((self.height, self.width), dtype=torch.int32, device=torch.device("cuda"))      # (u32 words)
+        else:
+            zeros = lambda: np.zeros((self.height, self.width), np.uint32)
+        self.marks, self.mark_tick, self.seen_tick = zeros(), zeros(), zeros()
+        self.tick = 0
+
+    def clear(self):
+        """forget everything: the three arrays to zero in place, the tick to 0"""
+        for a in self.arrays():
+            if self.device:
+                a.zero_()
+            else:
+                a[...] = 0
+        self.tick = 0
+
+    def arrays(self):
+        return (self.marks, self.mark_tick, self.seen_tick)
+
+    def numpy(self):
+        """dict of the three arrays as uint32 numpy arrays (copies of device tensors)"""
+        if self.device:
+            return {nm: a.cpu().numpy().view(np.uint32) for nm, a in zip(NAVMEM_LAYER_NAMES, self.arrays())}
+        return {nm: a.copy() for nm, a in zip(NAVMEM_LAYER_NAMES, self.arrays())}
+
+    def next_tick(self, tick=None):
+        """the tick of the next update: the caller's (it must not be 0), or the last one + 1 (modulo 2^32, skipping 0)"""
+        if tick is None:
+            tick = (self.tick + 1) & 0xFFFFFFFF or 1
+        tick = int(tick)
+        if not 1 <= tick <= 0xFFFFFFFF:
+            raise SsfError("a tick is 1 .. 2^32 - 1, got %d" % tick)
+        return tick
 
 
 class MoverTracker:
@@ -2164,7 +2265,7 @@ class Fusion:
         self._ck(self.L.lib.ssf_navlive_default_params(self.h, C.byref(p)), "ssf_navlive_default_params")
         return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm not in ("grid_pose", "cam_pose")}
 
-    def nav_live_plan(self, depth, state, goals, starts, waypoints=False, mask=None, live=None, plan=None, waypoint_params=None):
+    def nav_live_plan(self, depth, state, goals, starts, waypoints=False, mask=None, live=None, plan=None, waypoint_params=None, _overlay=None):
         """Overlay, plan and (waypoints=True) refine without the grid leaving the device: state (host, height x width int8) and the
         depth frame (host array in the input format, or a device tensor) are uploaded once, nav_live_device writes the live state and
         dist2 into device tensors, nav_plan_device plans on them and nav_waypoints_device reads its paths there.  live: the overlay's
@@ -2194,7 +2295,7 @@ class Fusion:
             mask = torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).to(dev)
         d_state = torch.from_numpy(state).to(dev)
         d_dist2 = torch.empty((H, W), dtype=torch.int32, device=dev)
-        live_stats = self.nav_live_device(depth, d_state, W, H, mask=mask, state_out=d_state, dist2=d_dist2, **live)
+        live_stats = (_overlay or self.nav_live_device)(depth, d_state, W, H, mask=mask, state_out=d_state, dist2=d_dist2, **live)      # (_overlay: nav_memory_plan's)
         mp = int(plan.setdefault("max_path", min(W * H, 1 << 20)))
         i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
         t = dict(start_cost=i32(n), start_status=i32(n), path_len=i32(n), path=i32(n, max(mp, 1), 2))
@@ -2215,6 +2316,146 @@ class Fusion:
             ref["stats"] = wp_stats
             res["waypoints"] = ref
         return res
+
+    # ---- the live layer with memory: height-sliced marks, ray clearing and decay (include/ssf_navmem.h) ----
+    def _need_navmem(self, symbol):
+        if not self.L.has_navmem:
+            raise SsfError("%s does not export %s: its live layer has no memory (include/ssf_navmem.h: libssf_hip_mem.so, binding.load_mem)"
+                           % (self.L.path, symbol))
+
+    def _navmem_params(self, on_device, frame_on_device, grid_pose=None, cam_pose=None, **kw):
+        """(SsfNavMemParams, the pose arrays it points into), as _navlive_params: the other keywords are fields of ssf_navmem_params by
+        name, each at ssf_navmem_default_params' value when missing."""
+        p = SsfNavMemParams()
+        self._ck(self.L.lib.ssf_navmem_default_params(self.h, C.byref(p)), "ssf_navmem_default_params")
+        keep = []
+        for nm, pose in (("grid_pose", grid_pose), ("cam_pose", cam_pose)):
+            if pose is not None:
+                keep.append(self._pose12(pose, nm))
+                setattr(p, nm, keep[-1].ctypes.data)
+        kinds = dict(p._fields_)
+        for nm, val in kw.items():
+            if nm not in kinds or nm in ("grid_pose", "cam_pose", "on_device", "frame_on_device"):
+                raise SsfError("unknown memory parameter %r" % nm)
+            if kinds[nm] is C.c_uint32 and not 0 <= int(val) <= 0xFFFFFFFF:
+                raise SsfError("%s is a uint32, got %r" % (nm, val))
+            setattr(p, nm, float(val) if kinds[nm] is C.c_float else int(val))
+        p.on_device, p.frame_on_device = int(bool(on_device)), int(bool(frame_on_device))
+        return p, keep
+
+    def _navmem_update(self, p, depth, mask, state_in, layer, ptrs):
+        st = SsfNavMemStats()
+        lay = SsfNavMemLayer(*layer) if layer is not None else None
+        out = SsfNavMemOut(*[ptrs.get(nm) for nm in NAVMEM_OUTPUT_NAMES])
+        self._ck(self.L.lib.ssf_navmem_update(self.h, C.byref(p), depth, mask, state_in, None if lay is None else C.byref(lay), C.byref(out),
+                                              C.byref(st)), "ssf_navmem_update")
+        return st.as_dict()
+
+    def nav_memory(self, depth, state, memory=None, mask=None, tick=None, outputs=NAVMEM_OUTPUT_NAMES, **kw):
+        """The depth frame stamped into the caller's sliced memory of the live layer (ssf_navmem_update), host arrays.  depth: H x W in
+        the handle's input format; state: height x width int8, the STATIC grid of every frame (nav_grid's or nav_grid_carve's); memory:
+        a LiveMemory of host arrays of that size -- read, updated in place and its tick advanced -- or None for a zero layer that is
+        not kept; tick: this update's (None = memory.tick + 1, or 1).  Returns a dict of the requested outputs -- marks, mark_tick,
+        seen_tick, live_hits, hit_bits, seen_bits (u32), state (i8), dist2 (i32), each height x width -- and 'stats'.  With a memory
+        the three layer arrays returned ARE the memory's.  Keywords: _navmem_params."""
+        self._need_navmem("ssf_navmem_update")
+        bad = [nm for nm in outputs if nm not in NAVMEM_OUTPUT_NAMES]
+        if bad:
+            raise SsfError("unknown memory outputs %s (known: %s)" % (bad, ", ".join(NAVMEM_OUTPUT_NAMES)))
+        state = np.ascontiguousarray(state, np.int8)
+        if state.ndim != 2:
+            raise SsfError("state is a height x width array, got shape %s" % (state.shape,))
+        for nm in ("width", "height"):
+            if nm in kw:
+                raise SsfError("nav_memory takes %s from state" % nm)
+        H, W = state.shape
+        if memory is not None and (memory.device or (memory.height, memory.width) != (H, W)):
+            raise SsfError("nav_memory takes a LiveMemory of host arrays of the state's size %d x %d" % (H, W))
+        tick = memory.next_tick(tick) if memory is not None else (1 if tick is None else int(tick))
+        p, keep = self._navmem_params(False, False, width=W, height=H, tick=tick, **kw)
+        cw, ch = (p.cam_width, p.cam_height) if p.cam_width else (self.W, self.H)
+        depth = np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32)
+        if depth.shape != (ch, cw):
+            raise SsfError("depth is %d x %d in the handle's input format, got shape %s" % (ch, cw, depth.shape))
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            if mask.shape != depth.shape:
+                raise SsfError("mask and depth are images of one shape, got %s and %s" % (mask.shape, depth.shape))
+        out = {nm: np.zeros((H, W), dt) for nm, dt in NAVMEM_OUTPUTS if nm in outputs}
+        layer = None
+        if memory is not None:
+            layer = [_ptr(a) for a in memory.arrays()]
+            out.update(zip(NAVMEM_LAYER_NAMES, memory.arrays()))          # the update in place, asked for or not
+        stats = self._navmem_update(p, _ptr(depth), _ptr(mask), _ptr(state), layer, {nm: _ptr(a) for nm, a in out.items()})
+        if memory is not None:
+            memory.tick = tick
+        out = {nm: a for nm, a in out.items() if nm in outputs}
+        out["stats"] = stats
+        return out
+
+    def nav_memory_device(self, depth, state, width, height, memory=None, mask=None, layer_in=None, marks=None, mark_tick=None, seen_tick=None,
+                          live_hits=None, hit_bits=None, seen_bits=None, state_out=None, dist2=None, frame_on_device=True, tick=None, **kw):
+        """ssf_navmem_update on device memory: state and each output are a contiguous torch tensor on the device or the device address
+        (int) of a buffer of the shape and dtype nav_memory works on (outputs may be None, not all; state_out may be `state` itself);
+        depth and mask likewise, or host arrays with frame_on_device=False.  memory: a LiveMemory(device=True), read, updated in place
+        and its tick advanced; or, without one, layer_in: None or three tensors / addresses (None = zero) and marks / mark_tick /
+        seen_tick: where the layer goes (each may be its own input).  Returns the stats dict."""
+        self._need_navmem("ssf_navmem_update")
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        if memory is not None:
+            if not memory.device or (memory.height, memory.width) != (int(height), int(width)):
+                raise SsfError("nav_memory_device takes a LiveMemory(device=True) of the grid's size %d x %d" % (height, width))
+            if layer_in is not None or marks is not None or mark_tick is not None or seen_tick is not None:
+                raise SsfError("nav_memory_device takes a LiveMemory or the layer's arrays, not both")
+            layer_in = memory.arrays()
+            marks, mark_tick, seen_tick = layer_in
+            tick = memory.next_tick(tick)
+        elif tick is None:
+            tick = 1
+        p, keep = self._navmem_params(True, frame_on_device, width=width, height=height, tick=tick, **kw)
+        if frame_on_device:
+            d, m = addr(depth), addr(mask)
+        else:
+            depth = np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32)
+            mask = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+            d, m = _ptr(depth), _ptr(mask)
+        layer = None if layer_in is None else [addr(a) for a in layer_in]
+        stats = self._navmem_update(p, d, m, addr(state), layer, dict(marks=addr(marks), mark_tick=addr(mark_tick), seen_tick=addr(seen_tick),
+                                                                      live_hits=addr(live_hits), hit_bits=addr(hit_bits), seen_bits=addr(seen_bits),
+                                                                      state=addr(state_out), dist2=addr(dist2)))
+        if memory is not None:
+            memory.tick = int(tick)
+        return stats
+
+    def nav_memory_default_params(self):
+        """ssf_navmem_default_params as a dict"""
+        self._need_navmem("ssf_navmem_default_params")
+        p = SsfNavMemParams()
+        self._ck(self.L.lib.ssf_navmem_default_params(self.h, C.byref(p)), "ssf_navmem_default_params")
+        return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm not in ("grid_pose", "cam_pose")}
+
+    def _navmem_overlay(self, memory, tick):
+        """nav_memory_device with `memory` in the place of nav_live_device in the chains below"""
+        self._need_navmem("ssf_navmem_update")
+        if not isinstance(memory, LiveMemory) or not memory.device:
+            raise SsfError("the chain keeps its grid on the device: it takes a LiveMemory(device=True)")
+        return lambda depth, state, W, H, **k: self.nav_memory_device(depth, state, W, H, memory=memory, tick=tick, **k)
+
+    def nav_memory_plan(self, depth, state, memory, goals, starts, waypoints=False, mask=None, tick=None, live=None, plan=None, waypoint_params=None):
+        """nav_live_plan with the memory in the overlay's place: update, plan and (waypoints=True) refine without the grid or the layer
+        leaving the device.  state: the STATIC grid (host, height x width int8), uploaded afresh every call; memory: a
+        LiveMemory(device=True), updated in place; live: the update's keywords (_navmem_params).  Returns nav_live_plan's dict ('live'
+        holds the update's state, dist2 and stats)."""
+        return self.nav_live_plan(depth, state, goals, starts, waypoints=waypoints, mask=mask, live=live, plan=plan, waypoint_params=waypoint_params,
+                                  _overlay=self._navmem_overlay(memory, tick))
+
+    def nav_memory_dyn_steer(self, depth, state, memory, goals, poses, tracker, steps_since=1, targets=None, tick=None, motion=None, live=None,
+                             blobs=None, plan=None, steer=None):
+        """nav_live_dyn_steer with the memory in the overlay's place: the moving pixels stay out of the stamp (mask_mode 2) but their rays
+        still clear, so a mover's trail is not remembered and what it walked away from is cleared behind it.  memory: a
+        LiveMemory(device=True), updated in place; live: the update's keywords (_navmem_params).  Returns nav_live_dyn_steer's dict."""
+        return self.nav_live_dyn_steer(depth, state, goals, poses, tracker, steps_since=steps_since, targets=targets, motion=motion, live=live,
+                                       blobs=blobs, plan=plan, steer=steer, _overlay=self._navmem_overlay(memory, tick))
 
     # ---- velocity commands on the navigation grid: rollouts scored on the device (include/ssf_navsteer.h) ----
     def _need_navsteer(self, symbol):
@@ -2867,7 +3108,7 @@ class Fusion:
         return dict(blobs=None if host is None else host[:stats["blobs_written"]].copy(), stats=stats)
 
     def nav_live_dyn_steer(self, depth, state, goals, poses, tracker, steps_since=1, targets=None, motion=None, live=None, blobs=None, plan=None,
-                           steer=None):
+                           steer=None, _overlay=None):
         """Motion mask, overlay, blobs, tracker, plan and rollouts among the movers, with nothing but the blob table and the command
         leaving the device: nav_live_steer with the moving pixels taken OUT of the overlay (mask_mode 2: a mover is not stamped as a
         wall where it stands now) and handed to the rollouts as predicted discs instead.  depth: host array in the input format or a
@@ -2898,7 +3139,7 @@ class Fusion:
         d_state = torch.from_numpy(state).to(dev)
         d_dist2 = torch.empty((H, W), dtype=torch.int32, device=dev)
         d_cost = torch.empty((H, W), dtype=torch.int32, device=dev)       # (uint32 words)
-        live_stats = self.nav_live_device(depth, d_state, W, H, mask=d_mask, state_out=d_state, dist2=d_dist2, **dict(live, mask_mode=2))
+        live_stats = (_overlay or self.nav_live_device)(depth, d_state, W, H, mask=d_mask, state_out=d_state, dist2=d_dist2, **dict(live, mask_mode=2))
         for nm in ("grid_pose", "cam_pose", "res", "floor_max", "z_max", "fx", "fy", "cx", "cy", "cam_width", "cam_height", "t_min", "t_max"):
             if nm in live:
                 bq.setdefault(nm, live[nm])

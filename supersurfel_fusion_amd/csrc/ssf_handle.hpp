@@ -408,6 +408,19 @@ struct NavDynWs {
     unsigned long long* stats = nullptr;
     unsigned char* img = nullptr; size_t img_bytes = 0;
 };
+// ssf_navmem_update (ssf_navmem.h, ssf_navmem.hip: linked into libssf_hip_mem.so only): per cell the points, the hit bits and the seen
+// bits of the frame (one more u32 plane than NavLiveWs: the hit bits beside the points), the column distances of the clearance and
+// the state when the caller did not ask for it (15 bytes); the sums; the staging buffer of host arrays.  The layer itself is the
+// caller's, never the handle's.  Allocated on first use; each group is grown as a whole or not at all (DevBufs::grow).  Nothing here
+// is read or written by the frame path.
+struct NavMemWs {
+    DevBufs bufs;
+    uint32_t* hits = nullptr; uint32_t* hit_bits = nullptr; uint32_t* seen_bits = nullptr; uint16_t* colg = nullptr; int8_t* state = nullptr;
+    size_t cells = 0;
+    unsigned long long* stats = nullptr;
+    unsigned char* img_in = nullptr; size_t img_in_bytes = 0;      // staged host inputs: depth, mask, state_in, the layer
+    unsigned char* img = nullptr; size_t img_bytes = 0;            // staged host outputs (a StagedIo holds eight arrays: two of them)
+};
 // ssf_navfoot_layers and ssf_navfoot_rollouts (ssf_navfoot.h, ssf_navfoot.hip: linked into libssf_hip_foot.so only): the footprint's
 // table of spans as the layers kernel reads it (kept from call to call while the footprint is the same), the layers' sums and the staging buffer of a layers call with host arrays; per cell
 // the rollouts' packed (heading mask, d) word of 8 bytes.  The rollouts' keys, counts, direction table, sums and staging are
@@ -575,6 +588,7 @@ struct ssf_handle {
     RaycastWs raycast;                            // ssf_raycast (ssf_raycast.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense); the out-of-view
                                                   // compaction keeps rows and order but moves slots: who keeps slot numbers also watches n_recentres (RaycastWs)
+    NavMemWs navmem;                              // ssf_navmem_update (ssf_navmem.h); last, so that no older member moves
 };
 
 #define HCK(call)                                                                                    \

@@ -259,7 +259,11 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
     int32: ix, iy, index into the path with bit 30 on a forced step, seg_min) and <k>_waypoints.json (stats, status, path_min).
     live (dict(depth=the depth image of the frame just processed, min_hits, stride)): that frame stamped onto the grid
     (include/ssf_navlive.h) from the tracked pose: <k>_live_state.npy and <k>_live_dist2.npy, and one log line with the stats; the
-    map's own grid, plan and regions above are written as without it.
+    map's own grid, plan and regions above are written as without it.  With live['memory'] = dict(forget=ticks, slices=n) the frame goes
+    into a height-sliced layer that remembers (include/ssf_navmem.h) instead: the tick is k + 1, marks and seen-through both expire
+    after `forget` ticks (0: never), the layer is kept in live['memory'] from grid to grid as long as the grid's frame and size stay
+    (it does not scroll), <k>_live_marks.npy, <k>_live_mark_tick.npy and <k>_live_seen_tick.npy are written as well, and the log
+    line starts with nav-memory.
     steer (dict(horizon=steps, speed=metres per second), with a plan only): the velocity command of include/ssf_navsteer.h from the
     tracked camera projected into the grid (steer_pose), over steer_lattice's candidates with steps of NAV_STEER_DT seconds, on the
     live layer's state and dist2 when there is one and the grid's otherwise, with the plan's field as the cost and the plan's
@@ -310,11 +314,28 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
             np.save(os.path.join(grid_dir, name + "_movers.npy"), movers)
             print("nav-movers %s: movers=%d pixels_masked=%d %s" % (name, len(movers), mm["stats"]["pixels_masked"],
                                                                    " ".join("%s=%d" % (nm, n) for nm, n in table["stats"].items())))
-        lv = fusion.nav_live(live["depth"], state, mask=None if mm is None else mm["mask"], outputs=("state", "dist2"), grid_pose=pose, res=res,
-                             min_hits=int(live.get("min_hits", 4)), stride=int(live.get("stride", 4)), mask_mode=0 if mm is None else 2)
+        lkw = dict(mask=None if mm is None else mm["mask"], grid_pose=pose, res=res, min_hits=int(live.get("min_hits", 4)),
+                   stride=int(live.get("stride", 4)), mask_mode=0 if mm is None else 2)
+        keep = live.get("memory")
+        if keep is None:
+            lv = fusion.nav_live(live["depth"], state, outputs=("state", "dist2"), **lkw)
+        else:
+            # the layer lives in the grid's frame and does not scroll (include/ssf_navmem.h): a grid of another frame or size starts afresh
+            mem = keep.get("layer")
+            fresh = mem is None or (mem.height, mem.width) != state.shape or not np.array_equal(keep.get("pose"), pose)
+            if fresh:
+                from .binding import LiveMemory
+                mem = keep["layer"] = LiveMemory(state.shape[1], state.shape[0])
+                keep["pose"] = np.array(pose, np.float32)
+            forget = int(keep.get("forget", 0))
+            lv = fusion.nav_memory(live["depth"], state, memory=mem, tick=k + 1, outputs=("state", "dist2"), slices=int(keep.get("slices", 16)),
+                                   max_mark_age=forget, max_seen_age=forget, **lkw)
+            for nm, a in zip(("marks", "mark_tick", "seen_tick"), mem.arrays()):
+                np.save(os.path.join(grid_dir, name + "_live_" + nm + ".npy"), a)
         np.save(os.path.join(grid_dir, name + "_live_state.npy"), lv["state"])
         np.save(os.path.join(grid_dir, name + "_live_dist2.npy"), lv["dist2"])
-        print("nav-live %s: %s" % (name, " ".join("%s=%d" % (nm, v) for nm, v in lv["stats"].items() if nm != "pose")))
+        print("%s %s: %s%s" % ("nav-live" if keep is None else "nav-memory", name, "" if keep is None else "tick=%d fresh=%d " % (k + 1, fresh),
+                               " ".join("%s=%d" % (nm, v) for nm, v in lv["stats"].items() if nm != "pose")))
     if plan is not None:
         import json
         start, goals = plan_cells(pose, res, fusion.get_pose()[9:12], plan.get("goals") or [])
@@ -428,7 +449,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     nav_grid_carve_stride, and <k>_seen.npy is written as well.  nav_plan (write_nav_grid's plan): the field, path and stats of a
     plan from the camera's cell are written next to each grid.  nav_frontiers (write_nav_grid's frontiers): the frontier regions
     of each grid, ranked from the camera's cell, are written next to it.  nav_live (dict(min_hits, stride)): the depth image of the
-    frame just processed is stamped onto each grid (write_nav_grid's live).  nav_waypoints (write_nav_grid's waypoints; needs nav_plan):
+    frame just processed is stamped onto each grid (write_nav_grid's live; with a 'memory' dict(forget, slices) into the layer that
+    remembers, one layer for the whole sequence).  nav_waypoints (write_nav_grid's waypoints; needs nav_plan):
     the plan's path reduced to waypoints is written next to it.  nav_steer (write_nav_grid's steer; needs nav_plan): the velocity command
     from the tracked camera's pose on each grid is logged and its arc written next to it.
     laser_scan_dir: after frames 0, laser_scan_every, 2 laser_scan_every, ... a planar scan of laser_scan_beams beams from the tracked
@@ -459,6 +481,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
         if nav_live is None:
             raise ValueError("nav_steer's movers need nav_live")
         nav_steer = dict(nav_steer, movers=mover_tracker_of(nav_steer["movers"], nav_grid_res))      # (one tracker for the whole sequence)
+    if nav_live is not None and nav_live.get("memory") is not None:
+        nav_live = dict(nav_live, memory=dict(nav_live["memory"]))            # (one layer for the whole sequence)
     live_of = (lambda depth: dict(nav_live, depth=depth)) if nav_live is not None else (lambda depth: None)
     carve_views = (lambda: [r["pose"] for r in results]) if nav_grid_carve else (lambda: None)
     if odometry_prior:
@@ -704,6 +728,13 @@ def parse_args(argv=None):
                          "obstacle layer); _live_state.npy and _live_dist2.npy are written next to the grid, and one log line with the stats")
     ap.add_argument("--nav-live-min-hits", type=int, default=None, metavar="N", help="points of the frame that make a cell occupied (default 4)")
     ap.add_argument("--nav-live-stride", type=int, default=None, metavar="S", help="pixel lattice of the see-through rays, 1..64 (default 4)")
+    ap.add_argument("--nav-live-memory", action="store_true",
+                    help="with --nav-live: the frame goes into a height-sliced live layer that remembers and is cleared when seen through "
+                         "(include/ssf_navmem.h; the tick is the frame index + 1); _live_marks.npy, _live_mark_tick.npy and _live_seen_tick.npy "
+                         "are written as well, and the log line starts with nav-memory")
+    ap.add_argument("--nav-live-forget", type=int, default=None, metavar="TICKS",
+                    help="with --nav-live-memory: marks and seen-through cells expire after this many frames without refreshment (default 0: never)")
+    ap.add_argument("--nav-live-slices", type=int, default=None, metavar="N", help="with --nav-live-memory: height slices of the obstacle band, 1..32 (default 16)")
     ap.add_argument("--nav-steer", action="store_true",
                     help="with --nav-plan-goal or --nav-plan-frontier: the velocity command from the tracked camera's pose on each grid, rolled out "
                          "and scored on the device (include/ssf_navsteer.h): one nav-steer log line and <k>_steer_traj.npy per grid")
@@ -770,6 +801,14 @@ def parse_args(argv=None):
         ap.error("--nav-live-min-hits is >= 1")
     if a.nav_live_stride is not None and not 1 <= a.nav_live_stride <= 64:
         ap.error("--nav-live-stride is 1..64")
+    if a.nav_live_memory and not a.nav_live:
+        ap.error("--nav-live-memory goes with --nav-live")
+    if (a.nav_live_forget is not None or a.nav_live_slices is not None) and not a.nav_live_memory:
+        ap.error("--nav-live-forget and --nav-live-slices go with --nav-live-memory")
+    if a.nav_live_forget is not None and not 0 <= a.nav_live_forget <= 0xFFFFFFFF:
+        ap.error("--nav-live-forget is 0..4294967295")
+    if a.nav_live_slices is not None and not 1 <= a.nav_live_slices <= 32:
+        ap.error("--nav-live-slices is 1..32")
     if a.nav_steer and not (a.nav_plan_goal or a.nav_plan_frontier):
         ap.error("--nav-steer goes with --nav-plan-goal or --nav-plan-frontier")
     if (a.nav_steer_horizon is not None or a.nav_steer_speed is not None) and not a.nav_steer:
@@ -828,7 +867,10 @@ def nav_live_of(a):
     """replay()'s nav_live from the parsed options, or None"""
     if not a.nav_live:
         return None
-    return dict(min_hits=4 if a.nav_live_min_hits is None else int(a.nav_live_min_hits), stride=4 if a.nav_live_stride is None else int(a.nav_live_stride))
+    live = dict(min_hits=4 if a.nav_live_min_hits is None else int(a.nav_live_min_hits), stride=4 if a.nav_live_stride is None else int(a.nav_live_stride))
+    if a.nav_live_memory:
+        live["memory"] = dict(forget=0 if a.nav_live_forget is None else int(a.nav_live_forget), slices=16 if a.nav_live_slices is None else int(a.nav_live_slices))
+    return live
 
 
 def nav_steer_of(a):
@@ -866,6 +908,8 @@ def library_of(a):
     the regions', the waypoints', the live layer's, the commands', the footprint's, the pose plan's and the movers' entry points: libraries
     of their own, each holding the one before it)"""
     steer = nav_steer_of(a)
+    if (nav_live_of(a) or {}).get("memory") is not None:
+        return "load_mem"                                                 # (the last of the chain: it holds whatever else is asked for)
     if steer:
         if steer.get("movers") is not None:
             return "load_dyn"
