@@ -997,22 +997,7 @@ public:
 #if defined(CV_VERSION) && defined(CV_32FC1) && defined(CV_8UC1)
     /* ... with the depth as CV_32FC1 (or, after setInputFormat, CV_16UC1) and the mask as CV_8UC1 (an empty Mat = no mask) */
     void overlayDepthFrame(const NavGrid& g, const LiveParams& q, const cv::Mat& depth_h, const cv::Mat& mask_h, LiveNavGrid& out) {
-        const cv::Mat d = depth_h.isContinuous() ? depth_h : depth_h.clone(), m = mask_h.isContinuous() ? mask_h : mask_h.clone();
-        const size_t n = (size_t)d.rows * (size_t)d.cols;
-        const bool masked = m.rows != 0 || m.cols != 0;
-        if (masked && (m.type() != CV_8UC1 || m.rows != d.rows || m.cols != d.cols)) throw std::invalid_argument("overlayDepthFrame: the mask must be CV_8UC1 of the depth image's size");
-        std::vector<uint8_t> mk;
-        if (masked) mk.assign(m.ptr<uint8_t>(), m.ptr<uint8_t>() + n);
-#ifdef CV_16UC1
-        if (d.type() == CV_16UC1) {
-            if (!depth_u16_) throw std::logic_error("overlayDepthFrame(CV_16UC1 depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
-            overlay_depth(g, q, d.ptr<uint16_t>(), n, mk, out);
-            return;
-        }
-#endif
-        if (d.type() != CV_32FC1) throw std::invalid_argument("overlayDepthFrame: the depth image must be CV_32FC1 or CV_16UC1");
-        if (depth_u16_) throw std::logic_error("overlayDepthFrame: the input format is uint16 depth; pass a CV_16UC1 image");
-        overlay_depth(g, q, d.ptr<float>(), n, mk, out);
+        with_depth_mats(depth_h, mask_h, [&](const void* d, size_t n, const std::vector<uint8_t>& mk) { overlay_depth(g, q, d, n, mk, out); });
     }
 #endif
     /* ... into a layer that REMEMBERS (ssf_navmem.h): the frame marks height slices of the band in mem, the rays that see through a
@@ -1033,6 +1018,12 @@ public:
 #if defined(CV_VERSION) && defined(CV_32FC1) && defined(CV_8UC1)
     void overlayDepthFrame(const NavGrid& g, const LiveParams& q, const cv::Mat& depth_h, const cv::Mat& mask_h, LiveMemory& mem, uint32_t tick,
                            LiveNavGrid& out) {
+        with_depth_mats(depth_h, mask_h, [&](const void* d, size_t n, const std::vector<uint8_t>& mk) { remember_depth(g, q, d, n, mk, mem, tick, out); });
+    }
+private:
+    /* the two overloads above: the images made continuous, their types checked against the input format, and f(depth as uint16_t* or
+     * float*, its pixels, the mask's bytes or none) */
+    template <class F> void with_depth_mats(const cv::Mat& depth_h, const cv::Mat& mask_h, F f) {
         const cv::Mat d = depth_h.isContinuous() ? depth_h : depth_h.clone(), m = mask_h.isContinuous() ? mask_h : mask_h.clone();
         const size_t n = (size_t)d.rows * (size_t)d.cols;
         const bool masked = m.rows != 0 || m.cols != 0;
@@ -1042,23 +1033,49 @@ public:
 #ifdef CV_16UC1
         if (d.type() == CV_16UC1) {
             if (!depth_u16_) throw std::logic_error("overlayDepthFrame(CV_16UC1 depth): call setInputFormat(..., SSF_DEPTH_U16_SCALED, scale) first");
-            remember_depth(g, q, d.ptr<uint16_t>(), n, mk, mem, tick, out);
+            f(d.ptr<uint16_t>(), n, mk);
             return;
         }
 #endif
         if (d.type() != CV_32FC1) throw std::invalid_argument("overlayDepthFrame: the depth image must be CV_32FC1 or CV_16UC1");
         if (depth_u16_) throw std::logic_error("overlayDepthFrame: the input format is uint16 depth; pass a CV_16UC1 image");
-        remember_depth(g, q, d.ptr<float>(), n, mk, mem, tick, out);
+        f(d.ptr<float>(), n, mk);
     }
 #endif
 private:
-    void remember_depth(const NavGrid& g, const LiveParams& q, const void* depth, size_t n_depth, const std::vector<uint8_t>& mask, LiveMemory& mem,
-                        uint32_t tick, LiveNavGrid& out) {
+    /* What overlay_depth and remember_depth share.  The checks: g has its state, depth and mask are images of q's camera; the cells */
+    size_t check_depth_frame(const NavGrid& g, const LiveParams& q, size_t n_depth, const std::vector<uint8_t>& mask) const {
         const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
         if (n == 0 || g.state.size() != n) throw std::logic_error("overlayDepthFrame: the grid has no state (want_state)");
         const size_t npix = q.width > 0 ? (size_t)q.width * (size_t)(q.height > 0 ? q.height : 0) : (size_t)width_ * (size_t)height_;
         if (n_depth != npix) throw std::invalid_argument("overlayDepthFrame: the depth image must be width x height of the camera");
         if (!mask.empty() && mask.size() != npix) throw std::invalid_argument("overlayDepthFrame: the mask must be width x height of the camera");
+        return n;
+    }
+    /* the fields that ssf_navlive_params and ssf_navmem_params share, host arrays; cam: 12 floats of the caller's for q.cam_pose */
+    template <class P> static void fill_frame_params(P& p, const NavGrid& g, const LiveParams& q, float* cam) {
+        if (q.cam_pose) { transform3_to_rt(*q.cam_pose, cam); p.cam_pose = cam; }
+        p.grid_pose = g.stats.pose; p.width = g.width; p.height = g.height; p.res = g.res;
+        p.floor_max = q.floor_max; p.z_max = q.z_max; p.max_dist_cells = q.max_dist_cells; p.unknown_is_obstacle = q.unknown_is_obstacle ? 1 : 0;
+        p.fx = q.fx; p.fy = q.fy; p.cx = q.cx; p.cy = q.cy; p.cam_width = q.width; p.cam_height = q.height; p.t_min = q.t_min; p.t_max = q.t_max;
+        p.mask_mode = q.mask_mode; p.min_hits = q.min_hits; p.stride = q.stride; p.hit_margin_cells = q.hit_margin_cells;
+        p.open_unknown = q.open_unknown ? 1 : 0; p.on_device = 0; p.frame_on_device = 0;
+    }
+    /* out as either call leaves it: g's size, the call's arrays (live_seen: the caller's), its stats as the live grid's and the grid's */
+    static void fill_live_grid(LiveNavGrid& out, const NavGrid& g, std::vector<int8_t>& state, std::vector<int32_t>& dist2, std::vector<uint32_t>& hits,
+                               const ssf_navlive_stats& st) {
+        out.width = g.width; out.height = g.height; out.res = g.res;
+        out.zmin.clear(); out.zmax.clear(); out.hits.clear();
+        out.state.swap(state); out.dist2.swap(dist2); out.live_hits.swap(hits);
+        out.live = st;
+        ssf_navgrid_stats gs = ssf_navgrid_stats();
+        gs.cells_free = st.cells_free; gs.cells_occupied = st.cells_occupied; gs.cells_unknown = st.cells_unknown;
+        std::copy(st.pose, st.pose + 12, gs.pose);
+        out.stats = gs;
+    }
+    void remember_depth(const NavGrid& g, const LiveParams& q, const void* depth, size_t n_depth, const std::vector<uint8_t>& mask, LiveMemory& mem,
+                        uint32_t tick, LiveNavGrid& out) {
+        const size_t n = check_depth_frame(g, q, n_depth, mask);
         if (mem.width != g.width || mem.height != g.height || mem.marks.size() != n || mem.mark_tick.size() != n || mem.seen_tick.size() != n) {
             mem.clear();
             mem.width = g.width; mem.height = g.height;
@@ -1067,12 +1084,7 @@ private:
         ssf_navmem_params p;
         check(ssf_navmem_default_params(need(), &p));
         float cam[12];
-        if (q.cam_pose) { transform3_to_rt(*q.cam_pose, cam); p.cam_pose = cam; }
-        p.grid_pose = g.stats.pose; p.width = g.width; p.height = g.height; p.res = g.res;
-        p.floor_max = q.floor_max; p.z_max = q.z_max; p.max_dist_cells = q.max_dist_cells; p.unknown_is_obstacle = q.unknown_is_obstacle ? 1 : 0;
-        p.fx = q.fx; p.fy = q.fy; p.cx = q.cx; p.cy = q.cy; p.cam_width = q.width; p.cam_height = q.height; p.t_min = q.t_min; p.t_max = q.t_max;
-        p.mask_mode = q.mask_mode; p.min_hits = q.min_hits; p.stride = q.stride; p.hit_margin_cells = q.hit_margin_cells;
-        p.open_unknown = q.open_unknown ? 1 : 0; p.on_device = 0; p.frame_on_device = 0;
+        fill_frame_params(p, g, q, cam);
         p.slices = mem.slices; p.tick = tick; p.max_mark_age = mem.max_mark_age; p.max_seen_age = mem.max_seen_age;
         std::vector<int8_t> state(n);                             /* (g may be out itself) */
         std::vector<uint32_t> hits(q.want_hits ? n : 0), hit_bits(n), seen_bits(n);
@@ -1086,35 +1098,21 @@ private:
         ssf_navmem_stats st;
         check(ssf_navmem_update(need(), &p, depth, mask.empty() ? nullptr : mask.data(), g.state.data(), &in, &o, &st));
         mem.tick = tick; mem.stats = st; mem.hit_bits.swap(hit_bits); mem.seen_bits.swap(seen_bits);
-        out.width = g.width; out.height = g.height; out.res = g.res;
-        out.zmin.clear(); out.zmax.clear(); out.hits.clear();
-        out.state.swap(state); out.dist2.swap(dist2); out.live_hits.swap(hits); out.live_seen.clear();
         ssf_navlive_stats ls = ssf_navlive_stats();
         ls.pixels_valid = st.pixels_valid; ls.pixels_stamping = st.pixels_stamping; ls.points_in_band = st.points_in_band; ls.rays = st.rays;
         ls.rays_carving = st.rays_carving; ls.ray_samples = st.ray_samples; ls.cells_opened = st.cells_opened; ls.cells_free = st.cells_free;
         ls.cells_occupied = st.cells_occupied; ls.cells_unknown = st.cells_unknown; ls.atomics = st.atomics;
         std::copy(st.pose, st.pose + 12, ls.pose);
-        out.live = ls;
-        ssf_navgrid_stats gs = ssf_navgrid_stats();
-        gs.cells_free = st.cells_free; gs.cells_occupied = st.cells_occupied; gs.cells_unknown = st.cells_unknown;
-        std::copy(st.pose, st.pose + 12, gs.pose);
-        out.stats = gs;
+        fill_live_grid(out, g, state, dist2, hits, ls);
+        out.live_seen.clear();
     }
     void overlay_depth(const NavGrid& g, const LiveParams& q, const void* depth, size_t n_depth, const std::vector<uint8_t>& mask, LiveNavGrid& out) {
-        const size_t n = (size_t)(g.width >= 1 && g.height >= 1 ? (size_t)g.width * (size_t)g.height : 0);
-        if (n == 0 || g.state.size() != n) throw std::logic_error("overlayDepthFrame: the grid has no state (want_state)");
-        const size_t npix = q.width > 0 ? (size_t)q.width * (size_t)(q.height > 0 ? q.height : 0) : (size_t)width_ * (size_t)height_;
-        if (n_depth != npix) throw std::invalid_argument("overlayDepthFrame: the depth image must be width x height of the camera");
-        if (!mask.empty() && mask.size() != npix) throw std::invalid_argument("overlayDepthFrame: the mask must be width x height of the camera");
+        const size_t n = check_depth_frame(g, q, n_depth, mask);
         ssf_navlive_params p;
         check(ssf_navlive_default_params(need(), &p));
         float cam[12];
-        if (q.cam_pose) { transform3_to_rt(*q.cam_pose, cam); p.cam_pose = cam; }
-        p.grid_pose = g.stats.pose; p.width = g.width; p.height = g.height; p.res = g.res;
-        p.floor_max = q.floor_max; p.z_max = q.z_max; p.max_dist_cells = q.max_dist_cells; p.unknown_is_obstacle = q.unknown_is_obstacle ? 1 : 0;
-        p.fx = q.fx; p.fy = q.fy; p.cx = q.cx; p.cy = q.cy; p.cam_width = q.width; p.cam_height = q.height; p.t_min = q.t_min; p.t_max = q.t_max;
-        p.mask_mode = q.mask_mode; p.min_hits = q.min_hits; p.stride = q.stride; p.hit_margin_cells = q.hit_margin_cells; p.min_seen = q.min_seen;
-        p.open_unknown = q.open_unknown ? 1 : 0; p.on_device = 0; p.frame_on_device = 0;
+        fill_frame_params(p, g, q, cam);
+        p.min_seen = q.min_seen;
         std::vector<int8_t> state(n);                             /* (g may be out itself) */
         std::vector<uint32_t> hits(q.want_hits ? n : 0), seen(q.want_seen ? n : 0);
         std::vector<int32_t> dist2(q.want_dist2 ? n : 0);
@@ -1123,14 +1121,8 @@ private:
         o.state = state.data(); o.dist2 = q.want_dist2 ? dist2.data() : nullptr;
         ssf_navlive_stats st;
         check(ssf_navlive_overlay(need(), &p, depth, mask.empty() ? nullptr : mask.data(), g.state.data(), &o, &st));
-        out.width = g.width; out.height = g.height; out.res = g.res;
-        out.zmin.clear(); out.zmax.clear(); out.hits.clear();
-        out.state.swap(state); out.dist2.swap(dist2); out.live_hits.swap(hits); out.live_seen.swap(seen);
-        out.live = st;
-        ssf_navgrid_stats gs = ssf_navgrid_stats();
-        gs.cells_free = st.cells_free; gs.cells_occupied = st.cells_occupied; gs.cells_unknown = st.cells_unknown;
-        std::copy(st.pose, st.pose + 12, gs.pose);
-        out.stats = gs;
+        fill_live_grid(out, g, state, dist2, hits, st);
+        out.live_seen.swap(seen);
     }
 public:
     /* Plan on a grid that buildNavGrid made (ssf_navplan.h), plain or carved: the cost-to-goal field over the cells a robot of

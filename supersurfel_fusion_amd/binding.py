@@ -2185,12 +2185,18 @@ class Fusion:
             raise SsfError("%s does not export %s: it overlays no depth frame (include/ssf_navlive.h: libssf_hip_live.so, binding.load_live)"
                            % (self.L.path, symbol))
 
-    def _navlive_params(self, on_device, frame_on_device, grid_pose=None, cam_pose=None, **kw):
-        """(SsfNavLiveParams, the pose arrays it points into).  grid_pose: grid-to-map, what the grid's stats returned as 'pose' (None =
-        nav_grid_default_pose now); cam_pose: camera-to-map (None = the handle's pose); the other keywords are fields of
-        ssf_navlive_params by name, each at ssf_navlive_default_params' value when missing."""
-        p = SsfNavLiveParams()
-        self._ck(self.L.lib.ssf_navlive_default_params(self.h, C.byref(p)), "ssf_navlive_default_params")
+    # what the calls that put a depth frame onto a grid share (nav_live*, nav_memory*): params, host checks, frame staging
+    def _frame_layer_defaults(self, struct, default_fn, as_dict=False):
+        """`struct` as the library's `default_fn` (a symbol's name) fills it; as_dict: its fields but the poses, what nav_*_default_params return"""
+        p = struct()
+        self._ck(getattr(self.L.lib, default_fn)(self.h, C.byref(p)), default_fn)
+        return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm not in ("grid_pose", "cam_pose")} if as_dict else p
+
+    def _frame_layer_params(self, struct, default_fn, what, on_device, frame_on_device, grid_pose=None, cam_pose=None, **kw):
+        """(struct, the pose arrays it points into).  grid_pose: grid-to-map, what the grid's stats returned as 'pose' (None =
+        nav_grid_default_pose now); cam_pose: camera-to-map (None = the handle's pose); the other keywords are fields of the struct by
+        name, each at default_fn's value when missing; what: how an error calls them ('overlay', 'memory')."""
+        p = self._frame_layer_defaults(struct, default_fn)
         keep = []
         for nm, pose in (("grid_pose", grid_pose), ("cam_pose", cam_pose)):
             if pose is not None:
@@ -2199,10 +2205,48 @@ class Fusion:
         kinds = dict(p._fields_)
         for nm, val in kw.items():
             if nm not in kinds or nm in ("grid_pose", "cam_pose", "on_device", "frame_on_device"):
-                raise SsfError("unknown overlay parameter %r" % nm)
+                raise SsfError("unknown %s parameter %r" % (what, nm))
+            if kinds[nm] is C.c_uint32 and not 0 <= int(val) <= 0xFFFFFFFF:
+                raise SsfError("%s is a uint32, got %r" % (nm, val))
             setattr(p, nm, float(val) if kinds[nm] is C.c_float else int(val))
         p.on_device, p.frame_on_device = int(bool(on_device)), int(bool(frame_on_device))
         return p, keep
+
+    def _frame_layer_host(self, who, make_params, depth, state, mask, kw):
+        """The host arrays of `who` (nav_live, nav_memory) checked: state 2-D int8, which fixes width and height; depth of the camera's
+        shape in the handle's input format; mask of depth's shape.  make_params(W, H) builds the call's params once the grid's size
+        is known.  Returns (p, keep, depth, state, mask)."""
+        state = np.ascontiguousarray(state, np.int8)
+        if state.ndim != 2:
+            raise SsfError("state is a height x width array, got shape %s" % (state.shape,))
+        for nm in ("width", "height"):
+            if nm in kw:
+                raise SsfError("%s takes %s from state" % (who, nm))
+        H, W = state.shape
+        p, keep = make_params(W, H)
+        cw, ch = (p.cam_width, p.cam_height) if p.cam_width else (self.W, self.H)
+        depth = np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32)
+        if depth.shape != (ch, cw):
+            raise SsfError("depth is %d x %d in the handle's input format, got shape %s" % (ch, cw, depth.shape))
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            if mask.shape != depth.shape:
+                raise SsfError("mask and depth are images of one shape, got %s and %s" % (mask.shape, depth.shape))
+        return p, keep, depth, state, mask
+
+    def _frame_layer_device(self, depth, mask, frame_on_device):
+        """(addr, depth, mask, keep) of a device call: addr(t) is the pointer of a tensor or a device address (None stays None);
+        depth and mask go through it, or, with frame_on_device false, are host arrays (kept alive in `keep`) and their pointers."""
+        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+        if frame_on_device:
+            return addr, addr(depth), addr(mask), ()
+        depth = np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32)
+        mask = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        return addr, _ptr(depth), _ptr(mask), (depth, mask)
+
+    def _navlive_params(self, on_device, frame_on_device, **kw):
+        """(SsfNavLiveParams, the pose arrays it points into): _frame_layer_params over ssf_navlive_params"""
+        return self._frame_layer_params(SsfNavLiveParams, "ssf_navlive_default_params", "overlay", on_device, frame_on_device, **kw)
 
     def _navlive_overlay(self, p, depth, mask, state_in, ptrs):
         st = SsfNavLiveStats()
@@ -2220,23 +2264,9 @@ class Fusion:
         bad = [nm for nm in outputs if nm not in NAVLIVE_OUTPUT_NAMES]
         if bad:
             raise SsfError("unknown overlay outputs %s (known: %s)" % (bad, ", ".join(NAVLIVE_OUTPUT_NAMES)))
-        state = np.ascontiguousarray(state, np.int8)
-        if state.ndim != 2:
-            raise SsfError("state is a height x width array, got shape %s" % (state.shape,))
-        for nm in ("width", "height"):
-            if nm in kw:
-                raise SsfError("nav_live takes %s from state" % nm)
-        H, W = state.shape
-        p, keep = self._navlive_params(False, False, width=W, height=H, **kw)
-        cw, ch = (p.cam_width, p.cam_height) if p.cam_width else (self.W, self.H)
-        depth = np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32)
-        if depth.shape != (ch, cw):
-            raise SsfError("depth is %d x %d in the handle's input format, got shape %s" % (ch, cw, depth.shape))
-        if mask is not None:
-            mask = np.ascontiguousarray(mask, np.uint8)
-            if mask.shape != depth.shape:
-                raise SsfError("mask and depth are images of one shape, got %s and %s" % (mask.shape, depth.shape))
-        out = {nm: np.zeros((H, W), dt) for nm, dt in NAVLIVE_OUTPUTS if nm in outputs}
+        p, keep, depth, state, mask = self._frame_layer_host(
+            "nav_live", lambda W, H: self._navlive_params(False, False, width=W, height=H, **kw), depth, state, mask, kw)
+        out = {nm: np.zeros(state.shape, dt) for nm, dt in NAVLIVE_OUTPUTS if nm in outputs}
         stats = self._navlive_overlay(p, _ptr(depth), _ptr(mask), _ptr(state), {nm: _ptr(a) for nm, a in out.items()})
         out["stats"] = stats
         return out
@@ -2248,22 +2278,14 @@ class Fusion:
         itself: the update in place); depth and mask likewise, or host arrays with frame_on_device=False.  Returns the stats dict."""
         self._need_navlive("ssf_navlive_overlay")
         p, keep = self._navlive_params(True, frame_on_device, width=width, height=height, **kw)
-        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
-        if frame_on_device:
-            d, m = addr(depth), addr(mask)
-        else:
-            depth = np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32)
-            mask = None if mask is None else np.ascontiguousarray(mask, np.uint8)
-            d, m = _ptr(depth), _ptr(mask)
+        addr, d, m, frame = self._frame_layer_device(depth, mask, frame_on_device)
         return self._navlive_overlay(p, d, m, addr(state), dict(live_hits=addr(live_hits), live_seen=addr(live_seen), state=addr(state_out),
                                                                 dist2=addr(dist2)))
 
     def nav_live_default_params(self):
         """ssf_navlive_default_params as a dict"""
         self._need_navlive("ssf_navlive_default_params")
-        p = SsfNavLiveParams()
-        self._ck(self.L.lib.ssf_navlive_default_params(self.h, C.byref(p)), "ssf_navlive_default_params")
-        return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm not in ("grid_pose", "cam_pose")}
+        return self._frame_layer_defaults(SsfNavLiveParams, "ssf_navlive_default_params", as_dict=True)
 
     def nav_live_plan(self, depth, state, goals, starts, waypoints=False, mask=None, live=None, plan=None, waypoint_params=None, _overlay=None):
         """Overlay, plan and (waypoints=True) refine without the grid leaving the device: state (host, height x width int8) and the
@@ -2323,25 +2345,9 @@ class Fusion:
             raise SsfError("%s does not export %s: its live layer has no memory (include/ssf_navmem.h: libssf_hip_mem.so, binding.load_mem)"
                            % (self.L.path, symbol))
 
-    def _navmem_params(self, on_device, frame_on_device, grid_pose=None, cam_pose=None, **kw):
-        """(SsfNavMemParams, the pose arrays it points into), as _navlive_params: the other keywords are fields of ssf_navmem_params by
-        name, each at ssf_navmem_default_params' value when missing."""
-        p = SsfNavMemParams()
-        self._ck(self.L.lib.ssf_navmem_default_params(self.h, C.byref(p)), "ssf_navmem_default_params")
-        keep = []
-        for nm, pose in (("grid_pose", grid_pose), ("cam_pose", cam_pose)):
-            if pose is not None:
-                keep.append(self._pose12(pose, nm))
-                setattr(p, nm, keep[-1].ctypes.data)
-        kinds = dict(p._fields_)
-        for nm, val in kw.items():
-            if nm not in kinds or nm in ("grid_pose", "cam_pose", "on_device", "frame_on_device"):
-                raise SsfError("unknown memory parameter %r" % nm)
-            if kinds[nm] is C.c_uint32 and not 0 <= int(val) <= 0xFFFFFFFF:
-                raise SsfError("%s is a uint32, got %r" % (nm, val))
-            setattr(p, nm, float(val) if kinds[nm] is C.c_float else int(val))
-        p.on_device, p.frame_on_device = int(bool(on_device)), int(bool(frame_on_device))
-        return p, keep
+    def _navmem_params(self, on_device, frame_on_device, **kw):
+        """(SsfNavMemParams, the pose arrays it points into): _frame_layer_params over ssf_navmem_params"""
+        return self._frame_layer_params(SsfNavMemParams, "ssf_navmem_default_params", "memory", on_device, frame_on_device, **kw)
 
     def _navmem_update(self, p, depth, mask, state_in, layer, ptrs):
         st = SsfNavMemStats()
@@ -2362,26 +2368,14 @@ class Fusion:
         bad = [nm for nm in outputs if nm not in NAVMEM_OUTPUT_NAMES]
         if bad:
             raise SsfError("unknown memory outputs %s (known: %s)" % (bad, ", ".join(NAVMEM_OUTPUT_NAMES)))
-        state = np.ascontiguousarray(state, np.int8)
-        if state.ndim != 2:
-            raise SsfError("state is a height x width array, got shape %s" % (state.shape,))
-        for nm in ("width", "height"):
-            if nm in kw:
-                raise SsfError("nav_memory takes %s from state" % nm)
-        H, W = state.shape
-        if memory is not None and (memory.device or (memory.height, memory.width) != (H, W)):
-            raise SsfError("nav_memory takes a LiveMemory of host arrays of the state's size %d x %d" % (H, W))
-        tick = memory.next_tick(tick) if memory is not None else (1 if tick is None else int(tick))
-        p, keep = self._navmem_params(False, False, width=W, height=H, tick=tick, **kw)
-        cw, ch = (p.cam_width, p.cam_height) if p.cam_width else (self.W, self.H)
-        depth = np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32)
-        if depth.shape != (ch, cw):
-            raise SsfError("depth is %d x %d in the handle's input format, got shape %s" % (ch, cw, depth.shape))
-        if mask is not None:
-            mask = np.ascontiguousarray(mask, np.uint8)
-            if mask.shape != depth.shape:
-                raise SsfError("mask and depth are images of one shape, got %s and %s" % (mask.shape, depth.shape))
-        out = {nm: np.zeros((H, W), dt) for nm, dt in NAVMEM_OUTPUTS if nm in outputs}
+        def make_params(W, H):
+            if memory is not None and (memory.device or (memory.height, memory.width) != (H, W)):
+                raise SsfError("nav_memory takes a LiveMemory of host arrays of the state's size %d x %d" % (H, W))
+            t = memory.next_tick(tick) if memory is not None else (1 if tick is None else int(tick))
+            return self._navmem_params(False, False, width=W, height=H, tick=t, **kw)
+        p, keep, depth, state, mask = self._frame_layer_host("nav_memory", make_params, depth, state, mask, kw)
+        tick = p.tick
+        out = {nm: np.zeros(state.shape, dt) for nm, dt in NAVMEM_OUTPUTS if nm in outputs}
         layer = None
         if memory is not None:
             layer = [_ptr(a) for a in memory.arrays()]
@@ -2401,7 +2395,6 @@ class Fusion:
         and its tick advanced; or, without one, layer_in: None or three tensors / addresses (None = zero) and marks / mark_tick /
         seen_tick: where the layer goes (each may be its own input).  Returns the stats dict."""
         self._need_navmem("ssf_navmem_update")
-        addr = lambda t: None if t is None else C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
         if memory is not None:
             if not memory.device or (memory.height, memory.width) != (int(height), int(width)):
                 raise SsfError("nav_memory_device takes a LiveMemory(device=True) of the grid's size %d x %d" % (height, width))
@@ -2413,12 +2406,7 @@ class Fusion:
         elif tick is None:
             tick = 1
         p, keep = self._navmem_params(True, frame_on_device, width=width, height=height, tick=tick, **kw)
-        if frame_on_device:
-            d, m = addr(depth), addr(mask)
-        else:
-            depth = np.ascontiguousarray(depth, np.uint16 if self.depth_format == "u16" else np.float32)
-            mask = None if mask is None else np.ascontiguousarray(mask, np.uint8)
-            d, m = _ptr(depth), _ptr(mask)
+        addr, d, m, frame = self._frame_layer_device(depth, mask, frame_on_device)
         layer = None if layer_in is None else [addr(a) for a in layer_in]
         stats = self._navmem_update(p, d, m, addr(state), layer, dict(marks=addr(marks), mark_tick=addr(mark_tick), seen_tick=addr(seen_tick),
                                                                       live_hits=addr(live_hits), hit_bits=addr(hit_bits), seen_bits=addr(seen_bits),
@@ -2430,9 +2418,7 @@ class Fusion:
     def nav_memory_default_params(self):
         """ssf_navmem_default_params as a dict"""
         self._need_navmem("ssf_navmem_default_params")
-        p = SsfNavMemParams()
-        self._ck(self.L.lib.ssf_navmem_default_params(self.h, C.byref(p)), "ssf_navmem_default_params")
-        return {nm: getattr(p, nm) for nm, _ in p._fields_ if nm not in ("grid_pose", "cam_pose")}
+        return self._frame_layer_defaults(SsfNavMemParams, "ssf_navmem_default_params", as_dict=True)
 
     def _navmem_overlay(self, memory, tick):
         """nav_memory_device with `memory` in the place of nav_live_device in the chains below"""

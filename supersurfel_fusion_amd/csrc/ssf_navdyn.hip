@@ -13,8 +13,8 @@
 //            multiply-add from the list in LDS needs none.  The square root is taken only where it lowers the running minimum:
 //            isqrt(D2) - R_s < g  <=>  D2 < (g + R_s)^2; then the f64 root, put right by one integer comparison each way.
 //            Movers are not culled per workgroup: see README (the probe's figures).
-//   * blobs  k_navdyn_blob_seen: a workgroup per 16 x 16 pixel tile, a thread per pixel (rows of 16 consecutive pixels: the loads of
-//            depth, mask and label coalesce): member, valid, point, (bx, by) into a per-pixel buffer, and a mark at the pixel's label.
+//   * blobs  k_navdyn_blob_seen: a workgroup per 16 x 16 pixel tile, a thread per pixel (the live layer's tile pixel, depth test and
+//            point, ssf_navlive.hpp, behind this kernel's own membership test): member, valid, point, (bx, by) into a per-pixel buffer, and a mark at the pixel's label.
 //            k_navdyn_blob_slots: a thread per label value: a marked label takes the next compact slot and clears its record.
 //            k_navdyn_blob_sum: a workgroup per tile again: the tile's contributing pixels are merged per slot in an LDS hash table of
 //            512 entries (a tile has at most 256 labels, so a probe always ends) with LDS atomics, and every occupied entry goes to
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void k_navdyn_foot_pick(NavSteerRule r, NavDyn
 
 // ---- the blobs -------------------------------------------------------------------------------------------------------------------------
 enum { NB_MEMBER = 0, NB_VALID = 1, NB_BAND = 2, NB_LABELS = 3, NB_STATS = 4 };
-enum { NB_TW = 16, NB_TH = 16, NB_HASH = 512 };
+enum { NB_HASH = 512 };                                               // (the tile: NL_TW x NL_TH, navlive_tile_pixel, ssf_navlive.hpp)
 // the record of a label (step B.3)
 struct NavDynBlobRec { unsigned long long sum_x, sum_y; int32_t label; uint32_t n; int32_t min_x, max_x, min_y, max_y; };
 static_assert(sizeof(NavDynBlobRec) == 40, "NavDynWs counts 40 bytes a record");
@@ -158,26 +158,23 @@ template <int DF>
 __global__ __launch_bounds__(256) void k_navdyn_blob_seen(NavGrid G, NavLiveCam cam, const void* __restrict__ depth, double scale,
                                                           const uint8_t* __restrict__ mask, const int32_t* __restrict__ label, int2* __restrict__ pt,
                                                           int32_t* __restrict__ slot, unsigned long long* __restrict__ stats) {
-    const int ntx = (cam.W + NB_TW - 1) / NB_TW;
-    const int t = threadIdx.x;
-    const int u = (int)(blockIdx.x % ntx) * NB_TW + (t & (NB_TW - 1)), v = (int)(blockIdx.x / ntx) * NB_TH + (t >> 4);
+    const NavTilePixel px = navlive_tile_pixel(cam.W, cam.H);
     unsigned long long member = 0, valid = 0, band = 0;
-    if (u < cam.W && v < cam.H) {
-        const size_t p = (size_t)v * cam.W + u;
-        const int L = label[p];
+    if (px.in) {
+        const int L = label[px.p];
         int2 q = make_int2(-1, -1);
-        member = mask[p] != 0 && L >= 0 && L < cam.W * cam.H;
+        member = mask[px.p] != 0 && L >= 0 && L < cam.W * cam.H;
         if (member) {
-            const float d = navlive_load_depth<DF>(depth, p, scale);
-            valid = isfinite(d) && d >= cam.tmin && d <= cam.tmax;
+            float d;
+            valid = navlive_pixel_depth<DF>(cam, depth, px.p, scale, d);
             if (valid) {
                 float Sx, Sy, Sz, gx, gy;
-                navlive_pixel_point(cam, u, v, d, Sx, Sy, Sz);
+                navlive_pixel_point(cam, px.u, px.v, d, Sx, Sy, Sz);
                 band = nav_grid_point(G, Sx, Sy, Sz, gx, gy);
                 if (band) { q = make_int2((int)(gx * 1024.0f), (int)(gy * 1024.0f)); slot[L] = 1; }
             }
         }
-        pt[p] = q;
+        pt[px.p] = q;
     }
     block_sums({member, valid, band}, stats, NB_MEMBER);
 }
@@ -203,15 +200,13 @@ __global__ __launch_bounds__(256) void k_navdyn_blob_sum(int W, int H, const int
                                                          const int32_t* __restrict__ slot, NavDynBlobRec* __restrict__ rec) {
     __shared__ int s_key[MERGE ? NB_HASH : 1];
     __shared__ NavDynBlobRec s_rec[MERGE ? NB_HASH : 1];
-    const int ntx = (W + NB_TW - 1) / NB_TW;
+    const NavTilePixel px = navlive_tile_pixel(W, H);
     const int t = threadIdx.x;
-    const int u = (int)(blockIdx.x % ntx) * NB_TW + (t & (NB_TW - 1)), v = (int)(blockIdx.x / ntx) * NB_TH + (t >> 4);
     int s = -1;
     int2 q = make_int2(-1, -1);
-    if (u < W && v < H) {
-        const size_t p = (size_t)v * W + u;
-        q = pt[p];
-        if (q.x >= 0) s = slot[label[p]] - 1;                         // (a contributing pixel: its label was checked and took a slot)
+    if (px.in) {
+        q = pt[px.p];
+        if (q.x >= 0) s = slot[label[px.p]] - 1;                      // (a contributing pixel: its label was checked and took a slot)
     }
     if (!MERGE) {
         if (s >= 0) navdyn_blob_add(rec + s, 1u, (unsigned long long)q.x, (unsigned long long)q.y, q.x, q.x, q.y, q.y);
@@ -376,8 +371,7 @@ int ssf_navdyn_blobs(ssf_handle* h, const ssf_navdyn_blob_params* p, const void*
 
     float gpose[12];
     NavGrid G{};
-    { int rc = navlive_frames(h, &g, p->grid_pose, p->cam_pose, G, cam, gpose); if (rc) return rc; }
-    G.W = p->width; G.H = p->height; G.res = p->res; G.fW = (float)G.W; G.fH = (float)G.H; G.zmax = p->z_max; G.floor_max = p->floor_max;
+    { int rc = navlive_frames(h, &g, p, 0.0f, G, cam, gpose); if (rc) return rc; }
 
     const size_t npix = (size_t)cam.W * cam.H;
     const void* d_depth = depth; const uint8_t* d_mask = mask; const int32_t* d_label = label;
@@ -398,16 +392,14 @@ int ssf_navdyn_blobs(ssf_handle* h, const ssf_navdyn_blob_params* p, const void*
     HCK(io.copy_in(st));
     HCK(hipMemsetAsync(w.stats, 0, NB_STATS * sizeof(unsigned long long), st));
     HCK(hipMemsetAsync(w.slot, 0, 4 * npix, st));
-    const unsigned tiles = (unsigned)(((cam.W + NB_TW - 1) / NB_TW) * ((cam.H + NB_TH - 1) / NB_TH));
+    const unsigned tiles = navlive_tiles(cam.W, cam.H);
     NavDynBlobRec* rec = (NavDynBlobRec*)w.rec;
     {
         ScopedKernel sk("navdyn_blob_seen", st);
-        if (df == SSF_DEPTH_U16_SCALED)
-            hipLaunchKernelGGL(k_navdyn_blob_seen<SSF_DEPTH_U16_SCALED>, dim3(tiles), dim3(256), 0, st, G, cam, d_depth, h->in_scale, d_mask, d_label, w.pt, w.slot,
+        navlive_by_depth_format(df, [&](auto DF) {
+            hipLaunchKernelGGL(k_navdyn_blob_seen<decltype(DF)::value>, dim3(tiles), dim3(256), 0, st, G, cam, d_depth, h->in_scale, d_mask, d_label, w.pt, w.slot,
                                w.stats);
-        else
-            hipLaunchKernelGGL(k_navdyn_blob_seen<SSF_DEPTH_F32_METRES>, dim3(tiles), dim3(256), 0, st, G, cam, d_depth, h->in_scale, d_mask, d_label, w.pt, w.slot,
-                               w.stats);
+        });
     }
     HCK(hipGetLastError());
     {

@@ -59,27 +59,31 @@ __device__ __forceinline__ void navgrid_cells_body(const NavAcc& acc, size_t P, 
 
 // ---- rays through the grid: the march of the carve (ssf_navcarve.hip) and of the live layer (ssf_navlive.hip) -----------------
 // the map-frame point S in the grid frame (ssf_navgrid.h steps 1 and 4): true iff it lies in the grid and in the band of step 5;
-// (gx, gy): its position in cells
-__device__ __forceinline__ bool nav_grid_point(const NavGrid& G, float Sx, float Sy, float Sz, float& gx, float& gy) {
+// (gx, gy): its position in cells; z: its height in the grid frame.  THE one place where a point meets the grid: the forms without
+// z, the cell and the memory's (cell, z) below all go through it
+__device__ __forceinline__ bool nav_grid_point(const NavGrid& G, float Sx, float Sy, float Sz, float& gx, float& gy, float& z) {
     const float dx = Sx - G.t[0], dy = Sy - G.t[1], dz = Sz - G.t[2];
     const float* R = G.R;
-    const float Cx = (R[0] * dx + R[3] * dy) + R[6] * dz, Cy = (R[1] * dx + R[4] * dy) + R[7] * dz, z = (R[2] * dx + R[5] * dy) + R[8] * dz;
-    gx = Cx / G.res; gy = Cy / G.res;
+    const float Cx = (R[0] * dx + R[3] * dy) + R[6] * dz, Cy = (R[1] * dx + R[4] * dy) + R[7] * dz, Cz = (R[2] * dx + R[5] * dy) + R[8] * dz;
+    gx = Cx / G.res; gy = Cy / G.res; z = Cz;
     if (!(gx >= 0.0f && gx < G.fW && gy >= 0.0f && gy < G.fH)) return false;
-    return z > G.floor_max && z <= G.zmax;
+    return Cz > G.floor_max && Cz <= G.zmax;
 }
-// the cell in whose band the map-frame point S lies, or -1
-__device__ __forceinline__ int nav_cell(const NavGrid& G, float Sx, float Sy, float Sz) {
+__device__ __forceinline__ bool nav_grid_point(const NavGrid& G, float Sx, float Sy, float Sz, float& gx, float& gy) { float z; return nav_grid_point(G, Sx, Sy, Sz, gx, gy, z); }
+// the cell in whose band the map-frame point S lies, or -1; z: as above (ssf_navmem.hip's slices)
+__device__ __forceinline__ int nav_cell(const NavGrid& G, float Sx, float Sy, float Sz, float& z) {
     float gx, gy;
-    if (!nav_grid_point(G, Sx, Sy, Sz, gx, gy)) return -1;
+    if (!nav_grid_point(G, Sx, Sy, Sz, gx, gy, z)) return -1;
     return (int)gy * G.W + (int)gx;
 }
-// a ray in the map frame, and the cell in whose band its sample m is accepted, or -1
+__device__ __forceinline__ int nav_cell(const NavGrid& G, float Sx, float Sy, float Sz) { float z; return nav_cell(G, Sx, Sy, Sz, z); }
+// a ray in the map frame, and the cell in whose band its sample m is accepted, or -1 (z: as above)
 struct NavMarchRay { float O[3], D[3]; };
-__device__ __forceinline__ int nav_sample_cell(const NavGrid& G, const NavMarchRay& r, int m) {
+__device__ __forceinline__ int nav_sample_cell(const NavGrid& G, const NavMarchRay& r, int m, float& z) {
     const float tm = (float)m * G.step;
-    return nav_cell(G, r.O[0] + tm * r.D[0], r.O[1] + tm * r.D[1], r.O[2] + tm * r.D[2]);
+    return nav_cell(G, r.O[0] + tm * r.D[0], r.O[1] + tm * r.D[1], r.O[2] + tm * r.D[2], z);
 }
+__device__ __forceinline__ int nav_sample_cell(const NavGrid& G, const NavMarchRay& r, int m) { float z; return nav_sample_cell(G, r, m, z); }
 // The march of ONE RAY BY ONE WAVE: its samples m = 0 .. M over the lanes, m = lane, lane + 64, ...  The cell of sample m - 1 comes
 // from the neighbouring lane (the same formula, so the same bits), across rounds of 64 through `carry`.  Only entries -- a sample in a
 // cell's band whose predecessor was not -- reach `seen`, with an integer atomicAdd (order-free).  The rays a wave takes one after the

@@ -2,12 +2,12 @@
 // obstacle band, cleared by the rays that see through a slice, aged by the caller's tick.
 //
 // What is computed is pinned, operation by operation, in include/ssf_navmem.h (the numpy restatement: tests/navmem_ref.py).
-//   * stamp   k_navmem_stamp: ssf_navlive.hip's tile -- a workgroup per 16 x 16 pixels, the cells through LDS and back column-major, so
-//             that a wave holds four runs of 16 vertically adjacent pixels -- which also carries the pixel's slice bit.  A run of lanes
-//             with one cell is found by the ballot of run heads; the run's bits are OR-ed down to its head (a segmented OR over the
-//             wave), and the head issues ONE atomicAdd of the run's length and ONE atomicOr of the run's bits.
-//   * march   k_navmem_march: one ray per wave, its samples over the lanes, NM_RUN consecutive lattice pixels per wave, the ray made
-//             from the depth image in place.  Every accepted sample yields (cell, bit); consecutive lanes in one cell are OR-reduced to
+//   * stamp   k_navmem_stamp: the overlay's tile (ssf_navlive.hpp: the tile pixel, its point, the transpose, the run heads -- the SAME
+//             code as k_navlive_stamp runs, not a copy) with a second LDS plane for the pixel's slice bit.  The run's bits are OR-ed
+//             down to its head (a segmented OR over the wave), and the head issues ONE atomicAdd of the run's length and ONE atomicOr
+//             of the run's bits.  The cell and the height come from one nav_grid_point (ssf_navgrid.hpp).
+//   * march   k_navmem_march: the overlay's rays (navlive_wave_rays, ssf_navlive.hpp: one ray per wave, NL_RUN consecutive lattice pixels
+//             per wave) with this file's march of a ray.  Every accepted sample yields (cell, bit); consecutive lanes in one cell are OR-reduced to
 //             their run head, what lane 63's run issued is carried into the next round of 64, and what consecutive rays give the first
 //             cells stays merged in registers (pend_cell, pend_bits).  A head issues an atomicOr whose value nobody reads.
 //   * cells   k_navmem_cells: one thread per cell: the layer, the state and the cell stats (steps 4 and 5);
@@ -25,34 +25,20 @@ namespace ssf {
 // of its own: sum k is word k * NM_PAD (a kernel's sums are consecutive, as block_sums wants them)
 enum { NM_VALID = 0, NM_STAMPING, NM_POINTS, NM_STAMP_ATOMICS, NM_CARVING, NM_SAMPLES, NM_MARCH_ATOMICS, NM_RAYS, NM_MARKED, NM_NEWLY, NM_CLEARED,
        NM_EXPIRED, NM_BITS, NM_REMEMBERED, NM_OPENED, NM_FREE, NM_OCC, NM_STATS = 17, NM_PAD = 16 };
-enum { NM_TW = 16, NM_TH = 16, NM_RUN = 16 };
 
 // the band cut into slices (ssf_navmem.h step 2)
 struct NavMemSlices { float floor_max, slice_h; int top; };          // top = slices - 1
 
-// nav_cell's sibling (ssf_navgrid.hpp: the same operations in the same order, so the same cell) that hands back the height z too
-__device__ __forceinline__ int navmem_cell_z(const NavGrid& G, float Sx, float Sy, float Sz, float& z) {
-    const float dx = Sx - G.t[0], dy = Sy - G.t[1], dz = Sz - G.t[2];
-    const float* R = G.R;
-    const float Cx = (R[0] * dx + R[3] * dy) + R[6] * dz, Cy = (R[1] * dx + R[4] * dy) + R[7] * dz;
-    z = (R[2] * dx + R[5] * dy) + R[8] * dz;
-    const float gx = Cx / G.res, gy = Cy / G.res;
-    if (!(gx >= 0.0f && gx < G.fW && gy >= 0.0f && gy < G.fH)) return -1;
-    if (!(z > G.floor_max && z <= G.zmax)) return -1;
-    return (int)gy * G.W + (int)gx;
-}
 // the bit of the slice that holds the band height z (z > floor_max, so the quotient is >= 0)
 __device__ __forceinline__ uint32_t navmem_slice_bit(const NavMemSlices& S, float z) {
     const float q = (z - S.floor_max) / S.slice_h;
     const int k = min(S.top, (int)floorf(q));
     return 1u << k;
 }
-// the OR of v over the lanes from this one to the end of its run; heads: the ballot of run heads (lane 0 is one).  len: the run's
-// lanes from this one on.  What a head gets is its whole run's.
-__device__ __forceinline__ uint32_t navmem_run_or(uint32_t v, unsigned long long heads, int& len) {
-    const int ln = lane();
-    const unsigned long long next = ln == 63 ? 0ull : heads >> (ln + 1);
-    len = next ? __builtin_ctzll(next) + 1 : 64 - ln;
+// the OR of v over the lanes from this one to the end of its run; heads: the ballot of run heads (nav_run_head, ssf_navlive.hpp).
+// What a head gets is its whole run's.
+__device__ __forceinline__ uint32_t navmem_run_or(uint32_t v, unsigned long long heads) {
+    const int len = nav_run_len(heads);
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const uint32_t o = __shfl_down(v, d, 64);
@@ -66,40 +52,25 @@ template <int DF>
 __global__ __launch_bounds__(256) void k_navmem_stamp(NavGrid G, NavLiveCam cam, NavMemSlices S, const void* __restrict__ depth, double scale,
                                                       const uint8_t* __restrict__ mask, int mask_mode, uint32_t* __restrict__ hits,
                                                       uint32_t* __restrict__ hit_bits, unsigned long long* __restrict__ stats) {
-    __shared__ int s_cell[NM_TW * (NM_TH + 1)];                       // column x at x * (NM_TH + 1): the transposing write spreads over the banks
-    __shared__ uint32_t s_bit[NM_TW * (NM_TH + 1)];
-    const int ntx = (cam.W + NM_TW - 1) / NM_TW;
-    const int t = threadIdx.x;
-    const int u = (int)(blockIdx.x % ntx) * NM_TW + (t & (NM_TW - 1)), v = (int)(blockIdx.x / ntx) * NM_TH + (t >> 4);
+    __shared__ int s_cell[NL_TILE_LDS];
+    __shared__ uint32_t s_bit[NL_TILE_LDS];
     int c = -1;
     uint32_t b = 0u;
-    bool valid = false, stamping = false;
-    if (u < cam.W && v < cam.H) {
-        const size_t p = (size_t)v * cam.W + u;
-        const float d = navlive_load_depth<DF>(depth, p, scale);
-        valid = isfinite(d) && d >= cam.tmin && d <= cam.tmax;
-        stamping = valid && (mask_mode == 0 || (mask[p] != 0) == (mask_mode == 1));
-        if (stamping) {
-            float Sx, Sy, Sz, z;
-            navlive_pixel_point(cam, u, v, d, Sx, Sy, Sz);
-            c = navmem_cell_z(G, Sx, Sy, Sz, z);
-            if (c >= 0) b = navmem_slice_bit(S, z);
-        }
+    bool valid, stamping;
+    float Sx, Sy, Sz, z;
+    if (navlive_tile_point<DF>(cam, depth, scale, mask, mask_mode, valid, stamping, Sx, Sy, Sz)) {
+        c = nav_cell(G, Sx, Sy, Sz, z);
+        if (c >= 0) b = navmem_slice_bit(S, z);
     }
-    const int w = (t & (NM_TW - 1)) * (NM_TH + 1) + (t >> 4);
+    const int w = navlive_tile_put(), r = navlive_tile_get();
     s_cell[w] = c; s_bit[w] = b;
     __syncthreads();
-    // thread t now holds pixel (x = t / 16, y = t % 16) of the tile: a lane's predecessor is the pixel above it
-    const int r = (t >> 4) * (NM_TH + 1) + (t & (NM_TH - 1));
     const int cc = s_cell[r];
-    const int ln = lane();
-    const int above = __shfl_up(cc, 1, 64);
-    const bool head = ln == 0 || cc != above;
-    int len;
-    const uint32_t bits = navmem_run_or(s_bit[r], __ballot(head), len);
-    unsigned long long n_atomics = 0;
+    unsigned long long heads, n_atomics = 0;
+    const bool head = nav_run_head(cc, heads);
+    const uint32_t bits = navmem_run_or(s_bit[r], heads);
     if (head && cc >= 0) {
-        atomicAdd(&hits[cc], (uint32_t)len);
+        atomicAdd(&hits[cc], (uint32_t)nav_run_len(heads));
         atomicOr(&hit_bits[cc], bits);
         n_atomics = 2;
     }
@@ -126,16 +97,13 @@ __device__ __forceinline__ void navmem_march_ray(const NavGrid& G, const NavMemS
         const int m = base + ln;
         int c = -1; uint32_t b = 0u;
         if (m <= M) {
-            const float tm = (float)m * G.step;
             float z;
-            c = navmem_cell_z(G, r.O[0] + tm * r.D[0], r.O[1] + tm * r.D[1], r.O[2] + tm * r.D[2], z);
+            c = nav_sample_cell(G, r, m, z);
             if (c >= 0) b = navmem_slice_bit(S, z);
         }
-        const int prev = __shfl_up(c, 1, 64);
-        const bool head = ln == 0 || c != prev;
-        const unsigned long long heads = __ballot(head);
-        int len;
-        const uint32_t bits = navmem_run_or(b, heads, len);
+        unsigned long long heads;
+        const bool head = nav_run_head(c, heads);
+        const uint32_t bits = navmem_run_or(b, heads);
         const bool covered = ln == 0 && c == carry_cell && (bits & ~carry_bits) == 0u;
         const int last_head = 63 - __builtin_clzll(heads);             // the head of the run that holds lane 63 (heads != 0: lane 0)
         carry_cell = __shfl(c, last_head, 64);
@@ -155,40 +123,15 @@ __device__ __forceinline__ void navmem_march_ray(const NavGrid& G, const NavMemS
 template <int DF>
 __global__ __launch_bounds__(256) void k_navmem_march(NavGrid G, NavLiveCam cam, NavMemSlices S, const void* __restrict__ depth, double scale, float margin,
                                                       uint32_t* __restrict__ seen, unsigned long long* __restrict__ stats) {
-    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    const int ln = lane();
-    const int n = cam.nu * cam.nv;
-    const long long first = (long long)wave * NM_RUN;
-    const int r0 = (int)min(first, (long long)n), r1 = (int)min(first + NM_RUN, (long long)n);
-    unsigned long long n_rays = 0, n_carving = 0, n_samples = 0, n_atomics = 0;                     // the first three: the same in every lane
+    unsigned long long n_atomics = 0;
     int pend_cell = -1; uint32_t pend_bits = 0u;
-    for (int ray = r0; ray < r1; ray++) {
-        const int i = ray % cam.nu, j = ray / cam.nu;
-        const int u = i * cam.stride + cam.stride / 2, v = j * cam.stride + cam.stride / 2;      // u < W, v < H: nu = W / stride
-        const float d = navlive_load_depth<DF>(depth, (size_t)v * cam.W + u, scale);
-        if (!(isfinite(d) && d >= cam.tmin && d <= cam.tmax)) continue;                          // (wave-uniform)
-        n_rays++;
-        const float x = ((float)u - cam.cx) / cam.fx, y = ((float)v - cam.cy) / cam.fy;
-        const float l = sqrtf((x * x + y * y) + 1.0f);
-        const float dx = x / l, dy = y / l, dz = 1.0f / l;
-        const float o = 0.0f;                                         // the camera-frame origin, through ssf_raycast.h step 1 as written
-        NavMarchRay r;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float a = cam.R[3 * k], b = cam.R[3 * k + 1], c = cam.R[3 * k + 2];
-            r.O[k] = ((a * o + b * o) + c * o) + cam.t[k];
-            r.D[k] = (a * dx + b * dy) + c * dz;
-        }
-        const bool rvalid = finite3(r.O[0], r.O[1], r.O[2]) && finite3(r.D[0], r.D[1], r.D[2]) && !(r.D[0] == 0.0f && r.D[1] == 0.0f && r.D[2] == 0.0f);
-        const float t_end = (d * l) - margin;
-        const int M = rvalid && t_end >= 0.0f ? (int)floorf(t_end / G.step) : -1;                  // <= 65535: the refusal of the corners
-        if (M < 0) continue;
-        n_carving++; n_samples += (unsigned long long)(M + 1);
+    const NavRayCounts n = navlive_wave_rays<DF>(G.step, cam, depth, scale, margin, [&](const NavMarchRay& r, int M) {
         navmem_march_ray(G, S, r, M, seen, pend_cell, pend_bits, n_atomics);
-    }
+    });
     if (pend_bits) navmem_or(seen, pend_cell, pend_bits, n_atomics);
     // the sums of the workgroup's four waves (rays and samples: one lane speaks for its wave)
-    block_sums({ln == 0 ? n_carving : 0ull, ln == 0 ? n_samples : 0ull, n_atomics, ln == 0 ? n_rays : 0ull}, stats, NM_CARVING, NM_PAD);
+    const bool one = lane() == 0;
+    block_sums({one ? n.carving : 0ull, one ? n.samples : 0ull, n_atomics, one ? n.rays : 0ull}, stats, NM_CARVING, NM_PAD);
 }
 
 // ---- cells: steps 4 and 5 and the cell stats; one thread per cell -------------------------------------------------------------
@@ -238,20 +181,17 @@ __global__ __launch_bounds__(256) void k_navmem_cells(size_t P, NavMemRule rule,
 static void launch_navmem_stamp(hipStream_t st, int df, const NavGrid& G, const NavLiveCam& cam, const NavMemSlices& S, const void* depth, double scale,
                                 const uint8_t* mask, int mask_mode, uint32_t* hits, uint32_t* hit_bits, unsigned long long* stats) {
     ScopedKernel sk("navmem_stamp", st);
-    const unsigned tiles = (unsigned)(((cam.W + NM_TW - 1) / NM_TW) * ((cam.H + NM_TH - 1) / NM_TH));
-    if (df == SSF_DEPTH_U16_SCALED)
-        hipLaunchKernelGGL(k_navmem_stamp<SSF_DEPTH_U16_SCALED>, dim3(tiles), dim3(256), 0, st, G, cam, S, depth, scale, mask, mask_mode, hits, hit_bits, stats);
-    else
-        hipLaunchKernelGGL(k_navmem_stamp<SSF_DEPTH_F32_METRES>, dim3(tiles), dim3(256), 0, st, G, cam, S, depth, scale, mask, mask_mode, hits, hit_bits, stats);
+    navlive_by_depth_format(df, [&](auto DF) {
+        hipLaunchKernelGGL(k_navmem_stamp<decltype(DF)::value>, dim3(navlive_tiles(cam.W, cam.H)), dim3(256), 0, st, G, cam, S, depth, scale, mask, mask_mode, hits,
+                           hit_bits, stats);
+    });
 }
 static void launch_navmem_march(hipStream_t st, int df, const NavGrid& G, const NavLiveCam& cam, const NavMemSlices& S, const void* depth, double scale,
                                 float margin, uint32_t* seen, unsigned long long* stats) {
     ScopedKernel sk("navmem_march", st);
-    const unsigned waves = (unsigned)((cam.nu * cam.nv + NM_RUN - 1) / NM_RUN);
-    if (df == SSF_DEPTH_U16_SCALED)
-        hipLaunchKernelGGL(k_navmem_march<SSF_DEPTH_U16_SCALED>, dim3((waves + 3) / 4), dim3(256), 0, st, G, cam, S, depth, scale, margin, seen, stats);
-    else
-        hipLaunchKernelGGL(k_navmem_march<SSF_DEPTH_F32_METRES>, dim3((waves + 3) / 4), dim3(256), 0, st, G, cam, S, depth, scale, margin, seen, stats);
+    navlive_by_depth_format(df, [&](auto DF) {
+        hipLaunchKernelGGL(k_navmem_march<decltype(DF)::value>, dim3(navlive_march_groups(cam)), dim3(256), 0, st, G, cam, S, depth, scale, margin, seen, stats);
+    });
 }
 static void launch_navmem_cells(hipStream_t st, size_t P, const NavMemRule& rule, const NavMemCellsIo& io, unsigned long long* stats) {
     ScopedKernel sk("navmem_cells", st);
@@ -260,22 +200,10 @@ static void launch_navmem_cells(hipStream_t st, size_t P, const NavMemRule& rule
 
 }  // namespace ssf
 
-// [a, a + na) and [b, b + nb) share a byte (a NULL array shares nothing)
-static bool navmem_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 extern "C" {
 int ssf_navmem_default_params(const ssf_handle* h, ssf_navmem_params* p) {
     if (!h || !p) return SSF_ERR_INVALID_ARG;
-    ssf_navgrid_params g;
-    { int rc = ssf_navgrid_default_params(h, &g); if (rc) return rc; }
-    std::memset(p, 0, sizeof(*p));
-    p->width = g.width; p->height = g.height; p->res = g.res; p->floor_max = g.floor_max; p->z_max = g.z_max;
-    p->max_dist_cells = g.max_dist_cells; p->unknown_is_obstacle = g.unknown_is_obstacle;
-    p->min_hits = 4; p->stride = 4; p->hit_margin_cells = 1.0f; p->open_unknown = 1;      // ssf_navlive_default_params'
+    { int rc = navlive_default_fields(h, p); if (rc) return rc; }
     p->slices = 16; p->tick = 1u; p->max_mark_age = 0u; p->max_seen_age = 0u;
     return SSF_OK;
 }
@@ -288,41 +216,19 @@ int ssf_navmem_update(ssf_handle* h, const ssf_navmem_params* p, const void* dep
     if (!state_in) return refuse("state_in is NULL");
     if (!out || (!out->marks && !out->mark_tick && !out->seen_tick && !out->live_hits && !out->hit_bits && !out->seen_bits && !out->state && !out->dist2))
         return refuse("every output is NULL");
-    // the grid
+    // the grid, the memory's own slices, the camera and its lattice (ssf_navlive.hpp: shared with ssf_navlive_overlay)
     ssf_navgrid_params g;
-    (void)ssf_navgrid_default_params(h, &g);
-    g.width = p->width; g.height = p->height; g.res = p->res;
-    if (const char* what = navgrid_size_res(&g)) return refuse(what);
-    if (p->max_dist_cells < 1 || p->max_dist_cells > 1024) return refuse("max_dist_cells must be 1..1024");
-    if (p->min_hits < 1) return refuse("min_hits must be >= 1");
-    // the slices
+    if (const char* what = navlive_refuse_grid(h, p, g)) return refuse(what);
     if (p->tick == 0u) return refuse("tick must be >= 1");
     if (p->slices < 1 || p->slices > 32) return refuse("slices must be 1..32");
     if (!std::isfinite(p->floor_max) || !std::isfinite(p->z_max)) return refuse("floor_max and z_max must be finite");
     if (!(p->z_max > p->floor_max)) return refuse("z_max must be > floor_max");
     const float slice_h = (p->z_max - p->floor_max) / (float)p->slices;
     if (!std::isfinite(slice_h) || !(slice_h > 0.0f)) return refuse("(z_max - floor_max) / slices must be finite and > 0");
-    // the camera and its lattice
     NavLiveCam cam{};
-    if (const char* what = navlive_pinhole(h, p->fx, p->fy, p->cx, p->cy, p->cam_width, p->cam_height, cam)) return refuse(what);
-    if (p->stride < 1 || p->stride > 64) return refuse("stride must be 1..64");
-    cam.stride = p->stride; cam.nu = cam.W / p->stride; cam.nv = cam.H / p->stride;
-    if (cam.nu < 1 || cam.nv < 1) return refuse("the stride leaves no pixel lattice");
-    if (!(p->hit_margin_cells >= 0.0f) || !std::isfinite(p->hit_margin_cells)) return refuse("hit_margin_cells must be finite and >= 0");
-    if (const char* what = navlive_range(h, p->t_min, p->t_max, cam)) return refuse(what);
-    if (p->mask_mode < 0 || p->mask_mode > 2) return refuse("mask_mode must be 0..2");
-    if (p->mask_mode != 0 && !mask) return refuse("mask is NULL with mask_mode != 0");
+    size_t bpp = 0;
+    if (const char* what = navlive_refuse_camera(h, p, depth, mask, nullptr, cam, bpp)) return refuse(what);
     const int df = h->in_depth;
-    const size_t bpp = df == SSF_DEPTH_U16_SCALED ? 2 : 4;
-    if (p->frame_on_device && (uintptr_t)depth % bpp) return refuse("the device depth pointer is not aligned for the input format");
-    // the sample index is bounded: l is largest at a corner of the image
-    const float step = p->res * 0.5f;
-    for (int k = 0; k < 4; k++) {
-        const int u = (k & 1) ? cam.W - 1 : 0, v = (k & 2) ? cam.H - 1 : 0;
-        const float x = ((float)u - cam.cx) / cam.fx, y = ((float)v - cam.cy) / cam.fy;
-        const float l = sqrtf((x * x + y * y) + 1.0f);
-        if (!((cam.tmax * l) / step <= 65535.0f)) return refuse("(t_max * l) / (res / 2) must be <= 65535 at the image's corners");
-    }
     const size_t P = (size_t)p->width * p->height, npix = (size_t)cam.W * cam.H;
     const bool dev = p->on_device != 0, fdev = p->frame_on_device != 0;
     const ssf_navmem_layer none{nullptr, nullptr, nullptr};
@@ -330,25 +236,18 @@ int ssf_navmem_update(ssf_handle* h, const ssf_navmem_params* p, const void* dep
     // overlaps: the outputs among themselves and with the inputs that live in the same memory; an output of the layer on its own
     // input and state == state_in are the update in place
     {
-        enum { N_OUT = 8, N_ALL = 14 };
-        const void* a[N_ALL] = {out->marks, out->mark_tick, out->seen_tick, out->live_hits, out->hit_bits, out->seen_bits, out->state, out->dist2,
-                                L.marks, L.mark_tick, L.seen_tick, state_in, depth, p->mask_mode ? mask : nullptr};
-        const size_t n[N_ALL] = {4 * P, 4 * P, 4 * P, 4 * P, 4 * P, 4 * P, P, 4 * P, 4 * P, 4 * P, 4 * P, P, bpp * npix, npix};
-        for (int i = 0; i < N_OUT; i++)
-            for (int j = i + 1; j < N_ALL; j++) {
-                if (j >= 12 && dev != fdev) continue;                 // (a host range and a device range are no overlap)
-                if (i < 3 && j == N_OUT + i && a[i] == a[j]) continue;
-                if (i == 6 && j == 11 && a[i] == a[j]) continue;
-                if (navmem_overlap(a[i], n[i], a[j], n[j])) return refuse("arrays overlap (only an output of the layer on its own input, and state == state_in, may)");
-            }
+        const void* a[14] = {out->marks, out->mark_tick, out->seen_tick, out->live_hits, out->hit_bits, out->seen_bits, out->state, out->dist2,
+                             L.marks, L.mark_tick, L.seen_tick, state_in, depth, p->mask_mode ? mask : nullptr};
+        const size_t n[14] = {4 * P, 4 * P, 4 * P, 4 * P, 4 * P, 4 * P, P, 4 * P, 4 * P, 4 * P, 4 * P, P, bpp * npix, npix};
+        const int may[4][2] = {{0, 8}, {1, 9}, {2, 10}, {6, 11}};
+        if (navlive_arrays_overlap(a, n, 14, 8, 12, dev != fdev, may, 4))
+            return refuse("arrays overlap (only an output of the layer on its own input, and state == state_in, may)");
     }
     { int rc = model_at_rest(h, "ssf_navmem_update", "updates no layer"); if (rc) return rc; }
 
     float gpose[12];
     NavGrid G{};
-    { int rc = navlive_frames(h, &g, p->grid_pose, p->cam_pose, G, cam, gpose); if (rc) return rc; }
-    G.W = p->width; G.H = p->height; G.res = p->res; G.step = step; G.fW = (float)G.W; G.fH = (float)G.H;
-    G.zmax = p->z_max; G.floor_max = p->floor_max;
+    { int rc = navlive_frames(h, &g, p, p->res * 0.5f, G, cam, gpose); if (rc) return rc; }
     const NavMemSlices S{p->floor_max, slice_h, p->slices - 1};
 
     // the arrays: host ones are staged on the device, the inputs in one buffer and the outputs in another
@@ -397,11 +296,10 @@ int ssf_navmem_update(ssf_handle* h, const ssf_navmem_params* p, const void* dep
         launch_navgrid_clearance(st, c.state, G.W, G.H, p->max_dist_cells, p->unknown_is_obstacle != 0, w.colg, o_dist2);
         HCK(hipGetLastError());
     }
-    unsigned long long padded[NM_STATS * NM_PAD], s[NM_STATS];
-    HCK(hipMemcpyAsync(padded, w.stats, sizeof(padded), hipMemcpyDeviceToHost, st));
+    NavPaddedSums<NM_STATS, NM_PAD> s;
+    HCK(s.fetch(w.stats, st));
     HCK(io.copy_out(st));
     { int rc = sync_collect(h); if (rc) return rc; }
-    for (int k = 0; k < NM_STATS; k++) s[k] = padded[k * NM_PAD];
     if (stats) {
         stats->pixels_valid = (int64_t)s[NM_VALID]; stats->pixels_stamping = (int64_t)s[NM_STAMPING]; stats->points_in_band = (int64_t)s[NM_POINTS];
         stats->rays = (int64_t)s[NM_RAYS]; stats->rays_carving = (int64_t)s[NM_CARVING]; stats->ray_samples = (int64_t)s[NM_SAMPLES];

@@ -397,6 +397,50 @@ def test_the_refusals(live_lib):
     f.close()
 
 
+def test_the_refusal_texts(live_lib):
+    """Every refusal of ssf_navlive_overlay by its exact ssf_last_error text (as the entry point's source had them before the refusals
+    it shares with ssf_navmem_update moved into one place), on the 8 x 4 grid and the handle-size image of test_the_refusals: a row
+    violates one parameter; the last four violate two, one on each side of the overlay's own checks (the NaN test of the band between
+    the grid and the camera, min_seen between the margin and the range), which pins the order.  All are refused before any kernel."""
+    f = handle(live_lib)
+    L, byref, vp = live_lib.lib, binding.C.byref, binding.C.c_void_p
+    dd, s8, o8 = np.ones((H, W), np.float32), np.zeros((4, 8), np.int8), np.zeros((4, 8), np.int32)
+    nan = float("nan")
+    cam = dict(cam_width=W, cam_height=H, fx=100.0, fy=100.0, cx=80.0, cy=64.0)
+    rows = [(dict(depth=None), "depth is NULL"), (dict(state_in=None), "state_in is NULL"), (dict(state=None), "every output is NULL"),
+            (dict(width=0), "the grid's size must be 1..4096 x 1..4096"), (dict(res=0.0), "res must be finite and > 0"),
+            (dict(max_dist_cells=0), "max_dist_cells must be 1..1024"), (dict(min_hits=0), "min_hits must be >= 1"),
+            (dict(floor_max=nan), "floor_max or z_max is a NaN"),
+            (dict(cam, cam_width=8193), "cam_width and cam_height must be 1..8192"),
+            (dict(cam, fx=-1.0), "fx and fy must be finite and > 0, cx and cy finite"), (dict(stride=0), "stride must be 1..64"),
+            (dict(cam, cam_width=13, cam_height=5, stride=8), "the stride leaves no pixel lattice"),
+            (dict(hit_margin_cells=-0.5), "hit_margin_cells must be finite and >= 0"), (dict(min_seen=0), "min_seen must be >= 1"),
+            (dict(t_min=3.0, t_max=2.0), "the range needs 0 < t_min < t_max, both finite"), (dict(mask_mode=3), "mask_mode must be 0..2"),
+            (dict(mask_mode=1), "mask is NULL with mask_mode != 0"),
+            (dict(frame_on_device=1, depth=dd.ctypes.data + 2), "the device depth pointer is not aligned for the input format"),
+            (dict(t_min=0.2, t_max=2000.0), "(t_max * l) / (res / 2) must be <= 65535 at the image's corners"),
+            (dict(dist2=o8.ctypes.data), "arrays overlap (only state == state_in may)"),
+            (dict(min_hits=0, floor_max=nan), "min_hits must be >= 1"), (dict(floor_max=nan, stride=0), "floor_max or z_max is a NaN"),
+            (dict(hit_margin_cells=-0.5, min_seen=0), "hit_margin_cells must be finite and >= 0"),
+            (dict(min_seen=0, t_min=3.0, t_max=2.0), "min_seen must be >= 1")]
+    for bad, text in rows:
+        p, out = binding.SsfNavLiveParams(), binding.SsfNavLiveOut()
+        assert L.ssf_navlive_default_params(f.h, byref(p)) == 0
+        p.width, p.height = 8, 4
+        arg = dict(depth=dd.ctypes.data, state_in=s8.ctypes.data, state=o8.ctypes.data, dist2=None)
+        for k, v in bad.items():
+            if k in arg:
+                arg[k] = v
+            else:
+                setattr(p, k, v)
+        out.state, out.dist2 = arg["state"], arg["dist2"]
+        rc = L.ssf_navlive_overlay(f.h, byref(p), vp(arg["depth"]), None, vp(arg["state_in"]), byref(out), None)
+        got = L.ssf_last_error(f.h).decode()
+        print(bad, rc, got)
+        assert rc == -1 and got == "ssf_navlive_overlay: " + text, (bad, rc, got)
+    f.close()
+
+
 def test_the_kernels_are_timed_under_profile(live_lib):
     f = handle(live_lib, profile=1)
     f.reset_kernel_times()

@@ -1,6 +1,6 @@
 """Per-kernel register / LDS / occupancy table of the product's device code (hipcc -Rpass-analysis=kernel-resource-usage).
 
-    python tools/kernel_resources.py [-DSSF_EXPERIMENTS ...] > profiles/kernel_resources_rNN.txt
+    python tools/kernel_resources.py [-DSSF_EXPERIMENTS ...] [ssf_navlive.hip ...] > profiles/kernel_resources_rNN.txt
 
 Also prints the number of 256-thread workgroups a CU admits by scalar registers (MI355X_MICROARCH.md, "Residency":
 min(8, floor(800 / (ceil(sgpr / 16) * 16 + 16)))) -- the API's occupancy answer is one too high for 81-96 / 97-112."""
@@ -22,11 +22,12 @@ def demangle(names):
 
 
 def main():
-    extra = sys.argv[1:]
+    extra = [a for a in sys.argv[1:] if not a.endswith(".hip")]
+    srcs = [a for a in sys.argv[1:] if a.endswith(".hip")]           # (names in csrc/: those files in the place of the product's)
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        for src in ("ssf_extract.hip", "ssf_track_fuse.hip", "ssf_upkeep.hip", "ssf_p2p.hip", "ssf_slots.hip", "ssf_render.hip", "ssf_query.hip", "ssf_navgrid.hip",
-                    "ssf_raycast.hip", "ssf_graph.hip", "ssf_graph_solve.hip", "ssf_keyframes.hip"):
+        for src in srcs or ("ssf_extract.hip", "ssf_track_fuse.hip", "ssf_upkeep.hip", "ssf_p2p.hip", "ssf_slots.hip", "ssf_render.hip", "ssf_query.hip",
+                            "ssf_navgrid.hip", "ssf_raycast.hip", "ssf_graph.hip", "ssf_graph_solve.hip", "ssf_keyframes.hip"):
             r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + extra + ["-c", src, "-o", os.path.join(tmp, src + ".o")],
                                cwd=CSRC, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
             for blk in re.split(r"remark: Function Name: ", r.stderr)[1:]:
