@@ -277,3 +277,107 @@ def case_reference(scene, fmt, stride):
         i = case_inputs(*key)
         _WANT[key] = overlay(i["depth"], None, i["state_in"], i["grid_pose"], i["cam_pose"], i["c"], fmt, i["depth_scale"])
     return _WANT[key]
+
+
+# ---- the parameter space of tests/test_navlive_gpu.py and tests/test_navmem_gpu.py ------------------------------------------------
+# One scene, one entry overridden at a time (and two combined rows): (overrides, the outputs the row must change against the base case
+# on the overlay, the same on the memory).  min_seen is the overlay's alone: a row of min_seen only has no memory side (None), a
+# combined row drops it there.  tests/test_navlive.py and tests/test_navmem.py check on the restatements that every row changes
+# its arrays, so that no row repeats the base case.
+PARAM_SCENE, PARAM_STRIDE, PARAM_FORMATS = "room rolled", 4, ("f32", "u16")
+_SEEN, _STATE, _DIST2, _HITS = ("live_seen",), ("state",), ("dist2",), ("live_hits",)
+PARAM_ROWS = tuple((dict(hit_margin_cells=m), _SEEN, ("seen_bits",)) for m in (0.0, 0.37, 2.5, 40.0)) + (
+    (dict(min_seen=2), _STATE, None), (dict(min_seen=9), _STATE, None),
+    (dict(open_unknown=0), _STATE, _STATE), (dict(unknown_is_obstacle=1), _DIST2, _DIST2),
+    (dict(min_hits=1), _STATE, _STATE), (dict(min_hits=64), _STATE, _STATE),
+    (dict(t_min=0.9, t_max=1.4), _HITS, _HITS), (dict(t_min=1.05, t_max=1.25), _HITS, _HITS), (dict(floor_max=-0.3, z_max=0.1), _HITS, _HITS),
+    (dict(max_dist_cells=1), _DIST2, _DIST2), (dict(max_dist_cells=40), _DIST2, _DIST2),
+    (dict(stride=3), _SEEN, ("seen_bits",)), (dict(stride=7), _SEEN, ("seen_bits",)), (dict(stride=64), _SEEN, ("seen_bits",)),
+    (dict(open_unknown=0, unknown_is_obstacle=1, hit_margin_cells=0.0), ("state", "dist2", "live_seen"), ("state", "dist2", "seen_bits")),
+    (dict(min_hits=64, min_seen=9, stride=7), ("state", "live_seen"), ("state", "seen_bits")))
+PARAM_IDS = tuple("-".join("%s=%s" % kv for kv in row[0].items()) for row in PARAM_ROWS)
+# The rows that do NOT change their array on this scene, by (id, format): the guard checks that they are exactly these, and that
+# another row of the same parameter changes it in that format.  Every valid depth of the scene lies in 0.99 .. 1.36 m, so the range
+# 0.9 .. 1.4 cuts nothing off: the range 1.05 .. 1.25, inside the scene's depths, cuts pixels off at both ends.  min_hits = 1 changes
+# the state of one cell in f32 and of none with the depths rounded to millimetres (min_hits = 64 changes two in both).
+PARAM_UNCHANGED = frozenset({("t_min=0.9-t_max=1.4", "f32"), ("t_min=0.9-t_max=1.4", "u16"), ("min_hits=1", "u16")})
+
+
+def param_inputs(fmt, over):
+    """case_inputs of the parameter space's scene with the keywords `over` in the place of the base case's"""
+    i = case_inputs(PARAM_SCENE, fmt, PARAM_STRIDE)
+    kw = dict(i["kw"], **over)
+    return dict(i, kw=kw, c=params(**kw))
+
+
+def param_reference(fmt, row):
+    """overlay() of row `row` of PARAM_ROWS (None: the base case), computed once and shared (the callers leave it unchanged)"""
+    key = ("param", fmt, row)
+    if key not in _WANT:
+        i = param_inputs(fmt, {} if row is None else PARAM_ROWS[row][0])
+        _WANT[key] = overlay(i["depth"], None, i["state_in"], i["grid_pose"], i["cam_pose"], i["c"], fmt, i["depth_scale"])
+    return _WANT[key]
+
+
+# ---- masks --------------------------------------------------------------------------------------------------------------------
+def modes_mask(W=160, H=128):
+    """the mask of the mask-mode tests: 40 % random, a solid band, values other than 1"""
+    mask = (np.random.default_rng(4).random((H, W)) < 0.4).astype(np.uint8) * 3
+    mask[:, 60:100] = 1
+    return mask
+
+
+# 37 x 29 at stride 3 on a 31 x 33 grid: partial 16 x 16 pixel tiles both ways (the mask must not be read outside the image), 12 x 9
+# lattice pixels with a remainder both ways, a mask of half the pixels with the value 200
+SMALL_W, SMALL_H, SMALL_STRIDE = 37, 29, 3
+SMALL_GRID = (31, 33, 0.05)
+SMALL_KW = dict(fx=60.0, fy=60.0, cx=0.5 * (SMALL_W - 1), cy=0.5 * (SMALL_H - 1), cam_width=SMALL_W, cam_height=SMALL_H, t_min=0.2, t_max=5.0,
+                width=SMALL_GRID[0], height=SMALL_GRID[1], res=SMALL_GRID[2], max_dist_cells=5, stride=SMALL_STRIDE, min_hits=3)
+
+
+def small_inputs(fmt):
+    """dict(depth (in the format), depth_scale, mask, state_in, cam_pose, grid_pose, kw) of the small image"""
+    gw, gh, _ = SMALL_GRID
+    d = noise_depth(SMALL_W, SMALL_H, 7 * SMALL_W + SMALL_H, lo=0.1, hi=1.6)
+    _, scale, image = dict((x[0], x) for x in scene_formats(d))[fmt]
+    mask = (np.random.default_rng(1).random((SMALL_H, SMALL_W)) < 0.5).astype(np.uint8) * 200
+    return dict(depth=image, depth_scale=scale, mask=mask, state_in=state_pattern(gw, gh, gw + SMALL_W), grid_pose=grid_pose_at(0.0, 0.0),
+                cam_pose=room_pose(yaw=8.0, roll=2.0, at=(0.8, 0.1, 0.35)), kw=dict(SMALL_KW))
+
+
+# ---- rays at the round edges ----------------------------------------------------------------------------------------------------
+# A 64 x 2 image at stride 1 along map +x over a 160 x 8 grid: 128 lattice pixels = eight waves of sixteen rays.  The depths rise by a
+# quarter cell a pixel, so that the rays of row 0 have 49 .. 80 samples and those of row 1 113 .. 144: the rounds of 64 samples end
+# inside both rows (64 | 65, 128 | 129).  Two pixels are invalid.  A tilted camera climbs or falls through the slices of the memory.
+EDGE_KW = dict(BOUNDARY, width=160, height=8, res=0.05, t_max=4.5, cam_width=64, cam_height=2, fx=2000.0, fy=2000.0, cx=31.5, cy=0.5)
+EDGE_TILTS = (5.0, -5.0, 0.0)
+EDGE_INVALID = ((0, 7), (1, 40))                                     # (v, u): a NaN and a 0
+EDGE_COUNTS = (64, 65, 128, 129)                                     # the sample counts on both sides of a round's end
+# With the depths as above a round ends between pixels 31 and 32 of a row, which is between two waves: every wave's rays have one
+# number of rounds.  Eight pixels further along the ramp the round ends in the middle of a wave, whose pending pair then lives
+# across rays of one round and of two (of two and of three).
+EDGE_SHIFTS = (0, 8)
+
+
+def edge_inputs(tilt, shift=0):
+    """dict(depth, state_in, grid_pose, cam_pose, kw) of the round-edge image, its ramp begun `shift` pixels later, seen by the
+    camera tilted by `tilt` degrees"""
+    u = np.arange(64, dtype=np.float64) + shift
+    d = np.stack([1.25 + 0.0125 * u, 2.85 + 0.0125 * u]).astype(f32)
+    d[EDGE_INVALID[0]] = np.nan
+    d[EDGE_INVALID[1]] = 0.0
+    return dict(depth=d, state_in=np.full((8, 160), -1, np.int8), grid_pose=nr.IDENTITY,
+                cam_pose=nr.pose_about(ncr.ALONG_X @ nr.rot("x", tilt), (0.0125, 0.2, 0.5)), kw=dict(EDGE_KW))
+
+
+def edge_ray_counts(tilt, run, shift=0):
+    """the sample count of each lattice pixel's ray (2 x 64, 0: no carving ray), each from a call of its own with every other pixel
+    invalid; run(depth, inputs) -> the stats of a restatement"""
+    i = edge_inputs(tilt, shift)
+    n = np.zeros((2, 64), np.int64)
+    for v in range(2):
+        for u in range(64):
+            d = np.zeros((2, 64), f32)
+            d[v, u] = i["depth"][v, u]
+            n[v, u] = run(d, i)["ray_samples"]
+    return n

@@ -289,3 +289,60 @@ def case_evidence(scene, fmt, stride):
         c = params(**i["kw"])
         _EV[key] = (i, evidence(i["depth"], None, i["grid_pose"], i["cam_pose"], c, fmt, i["depth_scale"]))
     return _EV[key]
+
+
+# ---- the parameter space, the masks and the round-edge rays (navlive_ref's inputs with the memory's fields) ------------------------------
+PARAM_SLICES, PARAM_LAYER_SEED = 5, 3
+PARAM_ROWS = tuple((k, {nm: v for nm, v in over.items() if nm != "min_seen"}, arrays)
+                   for k, (over, _, arrays) in enumerate(lr.PARAM_ROWS) if arrays is not None)          # (row of lr.PARAM_ROWS, overrides, arrays)
+PARAM_IDS = tuple(lr.PARAM_IDS[k].replace("-min_seen=9", "") for k, _, _ in PARAM_ROWS)
+# navlive_ref.PARAM_UNCHANGED's rows, and one more: a fifth of the random layer's cells are marked, so no cell lies further than the
+# default's 6 cells from an obstacle and a larger max_dist_cells caps nothing (max_dist_cells = 1 does)
+PARAM_UNCHANGED = lr.PARAM_UNCHANGED | {("max_dist_cells=40", "f32"), ("max_dist_cells=40", "u16")}
+
+
+def param_inputs(fmt, over):
+    """navlive_ref.param_inputs with the memory's fields and a random layer: dict(..., kw, c, layer)"""
+    i = lr.param_inputs(fmt, over)
+    kw = dict(i["kw"], slices=PARAM_SLICES, tick=GPU_TICK, **GPU_AGES)
+    c = params(**kw)
+    return dict(i, kw=kw, c=c, layer=random_layer(c["width"], c["height"], PARAM_LAYER_SEED, GPU_TICK, slices=PARAM_SLICES, **GPU_AGES))
+
+
+_WANT = {}
+
+
+def param_reference(fmt, row):
+    """update() of row `row` of PARAM_ROWS (None: the base case), computed once and shared (the callers leave it unchanged)"""
+    key = ("param", fmt, row)
+    if key not in _WANT:
+        i = param_inputs(fmt, {} if row is None else PARAM_ROWS[row][1])
+        _WANT[key] = update(i["depth"], None, i["state_in"], i["layer"], i["grid_pose"], i["cam_pose"], i["c"], fmt, i["depth_scale"])
+    return _WANT[key]
+
+
+def masked_inputs(fmt):
+    """the parameter space's base case at stride 8 with navlive_ref.modes_mask: the mask modes on the 160 x 128 image"""
+    i = lr.case_inputs(lr.PARAM_SCENE, fmt, 8)
+    kw = dict(i["kw"], slices=PARAM_SLICES, tick=GPU_TICK, **GPU_AGES)
+    c = params(**kw)
+    return dict(i, kw=kw, c=c, mask=lr.modes_mask(), layer=random_layer(c["width"], c["height"], PARAM_LAYER_SEED, GPU_TICK, slices=PARAM_SLICES, **GPU_AGES))
+
+
+SMALL_MEM = dict(slices=7, tick=9, max_mark_age=3, max_seen_age=2)
+
+
+def small_inputs(fmt):
+    """navlive_ref.small_inputs with the memory's fields and a random layer"""
+    i = lr.small_inputs(fmt)
+    gw, gh, _ = lr.SMALL_GRID
+    return dict(i, kw=dict(i["kw"], **SMALL_MEM), layer=random_layer(gw, gh, gw, 9, 3, 2, slices=7))
+
+
+EDGE_SLICES = 32
+
+
+def edge_inputs(tilt, shift=0):
+    """navlive_ref.edge_inputs with 32 slices"""
+    i = lr.edge_inputs(tilt, shift)
+    return dict(i, kw=dict(i["kw"], slices=EDGE_SLICES))

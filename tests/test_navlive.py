@@ -282,3 +282,110 @@ def test_no_scene_of_the_gpu_file_is_vacuous(scene, fmt, stride):
     assert int(got["live_hits"].max()) >= 64                             # contention inside a wave
     assert s["rays_carving"] > 0 and s["ray_entries"] > s["rays_carving"] and 0 < s["points_in_band"] <= s["pixels_stamping"]
     assert set(np.unique(i["state_in"])) - {-1, 0, 100}                  # foreign values of state_in are exercised
+
+
+# ---- the guards of the parameter space, the masks and the round-edge rays of the GPU file ------------------------------------------
+def changes(ref, unchanged, ids, rows_arrays, row, fmt):
+    """the governed arrays of a row against the base case: all differ, or -- a row listed as unchanged -- none does"""
+    base, got = ref(fmt, None), ref(fmt, row)
+    differ = [bool((got[a] != base[a]).any()) for a in rows_arrays[row]]
+    print(ids[row], fmt, {a: int((got[a] != base[a]).sum()) for a in rows_arrays[row]})
+    if (ids[row], fmt) in unchanged:
+        assert not any(differ), (ids[row], fmt, "is listed as a row that changes nothing")
+    else:
+        assert all(differ), (ids[row], fmt, "repeats the base case", rows_arrays[row], differ)
+
+
+def substitutes(unchanged, ids, overrides, changed):
+    """every row listed as unchanged names a row, and another row of the same parameter changes its array in that format"""
+    for name, fmt in unchanged:
+        over = overrides[ids.index(name)]
+        others = [k for k, o in enumerate(overrides) if set(o) == set(over) and (ids[k], fmt) not in unchanged]
+        assert others and all(changed(k, fmt) for k in others), (name, fmt)
+
+
+@pytest.mark.parametrize("fmt", lr.PARAM_FORMATS)
+@pytest.mark.parametrize("row", range(len(lr.PARAM_ROWS)), ids=lr.PARAM_IDS)
+def test_every_row_of_the_parameter_space_changes_its_arrays(row, fmt):
+    changes(lr.param_reference, lr.PARAM_UNCHANGED, lr.PARAM_IDS, [r[1] for r in lr.PARAM_ROWS], row, fmt)
+
+
+def test_the_parameter_space_is_the_one_that_was_asked_for():
+    over = [r[0] for r in lr.PARAM_ROWS]
+    assert [o["hit_margin_cells"] for o in over if set(o) == {"hit_margin_cells"}] == [0.0, 0.37, 2.5, 40.0]
+    assert [o["min_seen"] for o in over if set(o) == {"min_seen"}] == [2, 9] and [o["min_hits"] for o in over if set(o) == {"min_hits"}] == [1, 64]
+    assert [o["max_dist_cells"] for o in over if set(o) == {"max_dist_cells"}] == [1, 40] and [o["stride"] for o in over if set(o) == {"stride"}] == [3, 7, 64]
+    for o in (dict(open_unknown=0), dict(unknown_is_obstacle=1), dict(t_min=0.9, t_max=1.4), dict(floor_max=-0.3, z_max=0.1),
+              dict(open_unknown=0, unknown_is_obstacle=1, hit_margin_cells=0.0), dict(min_hits=64, min_seen=9, stride=7)):
+        assert o in over, o
+    assert (lr.PARAM_SCENE, lr.PARAM_STRIDE, lr.PARAM_FORMATS) == ("room rolled", 4, ("f32", "u16"))
+    assert all(160 % s or 128 % s for s in (3, 7, 64))                   # every stride of the rows leaves a remainder in the lattice
+    changed = lambda k, fmt: all((lr.param_reference(fmt, k)[a] != lr.param_reference(fmt, None)[a]).any() for a in lr.PARAM_ROWS[k][1])
+    substitutes(lr.PARAM_UNCHANGED, lr.PARAM_IDS, over, changed)
+    # what the base case's cell rule sees: cells on both sides of min_seen 2 and 9, and of min_hits 64
+    base = lr.param_reference("f32", None)
+    assert ((base["live_seen"] >= 1) & (base["live_seen"] < 9)).any() and (base["live_seen"] >= 9).any() and (base["live_hits"] >= 64).any()
+    # a margin of 40 cells is longer than every ray: none carves, and every pixel still counts as a ray
+    far = lr.param_reference("f32", lr.PARAM_IDS.index("hit_margin_cells=40.0"))["stats"]
+    assert far["rays_carving"] == 0 == far["ray_entries"] and far["rays"] == base["stats"]["rays"] > 0
+    # margin 0: rays reach the cells their own pixels stamp
+    zero = lr.param_reference("f32", lr.PARAM_IDS.index("hit_margin_cells=0.0"))
+    stamped = base["live_hits"] >= 4
+    assert (zero["live_hits"] == base["live_hits"]).all() and zero["live_seen"][stamped].sum() > base["live_seen"][stamped].sum() > 0
+
+
+@pytest.mark.parametrize("fmt", ["f32", "u16"])
+def test_the_mask_of_the_small_image_splits_its_pixels(fmt):
+    i = lr.small_inputs(fmt)
+    assert (i["depth"].shape, i["mask"].shape, i["state_in"].shape) == ((29, 37), (29, 37), (33, 31)) and set(np.unique(i["mask"])) == {0, 200}
+    assert 37 % 16 and 29 % 16 and 37 % 3 and 29 % 3                     # partial pixel tiles and a remainder in the lattice, both ways
+    run = lambda mode: lr.overlay(i["depth"], i["mask"], i["state_in"], i["grid_pose"], i["cam_pose"], lr.params(**dict(i["kw"], mask_mode=mode)),
+                                  fmt, i["depth_scale"])
+    all_, only, rest = run(0), run(1), run(2)
+    for got in (only, rest):
+        s = got["stats"]
+        assert 0 < s["pixels_stamping"] < s["pixels_valid"] and s["cells_stamped"] > 0 and 0 < s["points_in_band"] < all_["stats"]["points_in_band"]
+    assert only["stats"]["pixels_stamping"] + rest["stats"]["pixels_stamping"] == all_["stats"]["pixels_valid"] == (834 if fmt == "f32" else 835)
+    print(fmt, only["stats"], rest["stats"])
+    assert (only["stats"]["pixels_stamping"], rest["stats"]["pixels_stamping"]) == ((413, 421) if fmt == "f32" else (414, 421))
+    assert (only["state"] != rest["state"]).any() and (only["live_seen"] == rest["live_seen"]).all()
+
+
+def test_the_mask_modes_differ_on_the_large_image():
+    i = lr.case_inputs(lr.PARAM_SCENE, "f32", 8)
+    mask = lr.modes_mask()
+    assert set(np.unique(mask)) == {0, 1, 3} and (mask[:, 60:100] == 1).all() and 0.3 < (mask[:, :60] != 0).mean() < 0.5
+    got = [lr.overlay(i["depth"], mask, i["state_in"], i["grid_pose"], i["cam_pose"], lr.params(**dict(i["kw"], mask_mode=m))) for m in (0, 1, 2)]
+    assert all((a["live_hits"] != b["live_hits"]).any() for a, b in ((got[0], got[1]), (got[0], got[2]), (got[1], got[2])))
+
+
+@pytest.mark.parametrize("tilt", lr.EDGE_TILTS)
+def test_the_round_edge_rays_end_on_both_sides_of_a_round(tilt):
+    i = lr.edge_inputs(tilt)
+    c = lr.params(**i["kw"])
+    run = lambda d, i: lr.overlay(d, None, i["state_in"], i["grid_pose"], i["cam_pose"], c)
+    s = run(i["depth"], i)["stats"]
+    nu, nv = 64 // c["stride"], 2 // c["stride"]
+    assert (nu * nv, nu * nv // 16) == (128, 8)                           # eight waves of sixteen rays
+    assert (s["pixels_valid"], s["rays"], s["rays_carving"], s["ray_samples"]) == (126, 126, 126, 12167)
+    n = lr.edge_ray_counts(tilt, lambda d, i: run(d, i)["stats"])
+    assert n.sum() == s["ray_samples"] and [(v, u) for v, u in np.argwhere(n == 0)] == list(lr.EDGE_INVALID)
+    assert set(n[0]) - {0} == set(range(49, 81)) and set(n[1]) - {0} == set(range(113, 145))
+    for count in lr.EDGE_COUNTS:
+        assert (n == count).any(), count
+    # a wave's sixteen consecutive rays have eight or nine counts; a round ends between two waves (pixels 31 | 32 of either row)
+    waves = [set(n.ravel()[k:k + 16]) for k in range(0, 128, 16)]
+    assert all(len(w) >= 8 for w in waves) and 64 in waves[1] and 65 in waves[2] and 128 in waves[5] and 129 in waves[6]
+    assert s["ray_entries"] > 6000 and s["cells_opened"] > 100 and s["cells_stamped"] > 30
+
+
+@pytest.mark.parametrize("tilt", lr.EDGE_TILTS)
+def test_the_shifted_round_edge_rays_end_a_round_inside_a_wave(tilt):
+    i = lr.edge_inputs(tilt, 8)
+    c = lr.params(**i["kw"])
+    run = lambda d, i: lr.overlay(d, None, i["state_in"], i["grid_pose"], i["cam_pose"], c)
+    s = run(i["depth"], i)["stats"]
+    n = lr.edge_ray_counts(tilt, lambda d, i: run(d, i)["stats"], 8)
+    assert (s["rays_carving"], s["ray_samples"]) == (126, n.sum()) and float(np.nanmax(i["depth"])) < c["t_max"]
+    waves = [set(n.ravel()[k:k + 16]) for k in range(0, 128, 16)]
+    assert {64, 65} <= waves[1] and {128, 129} <= waves[5] and lr.EDGE_SHIFTS == (0, 8)

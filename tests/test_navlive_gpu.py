@@ -1,6 +1,7 @@
 """The live obstacle layer (include/ssf_navlive.h) on the GPU: every array and every exact stat of ssf_navlive_overlay equals the
 numpy restatement (tests/navlive_ref.py) with ==, on the scenes that tests/test_navlive.py guards against being vacuous, on the
-smallest images and grids at which the kernels take another path, on boundary cases with hand-written answers, through device
+smallest images and grids at which the kernels take another path, with every parameter off its default in turn, with masks off the
+full tile, with rays that end on both sides of a round of 64 samples, on boundary cases with hand-written answers, through device
 pointers, through nav_live_plan, replay.py and the C++ wrapper."""
 import os
 import re
@@ -116,6 +117,61 @@ def test_the_strides_on_one_scene(stride, fusion):
     assert got["stats"]["rays"] <= (W // stride) * (H // stride) and got["stats"]["rays_carving"] > 0
 
 
+# ---- the parameter space: one entry off its default at a time (tests/test_navlive.py guards that each row changes its arrays) -----
+@pytest.mark.parametrize("fmt", lr.PARAM_FORMATS)
+@pytest.mark.parametrize("row", [None] + list(range(len(lr.PARAM_ROWS))), ids=("base",) + lr.PARAM_IDS)
+def test_the_parameter_space(row, fmt, fusion, fusion_u16):
+    i = lr.param_inputs(fmt, {} if row is None else lr.PARAM_ROWS[row][0])
+    check(fusion_u16 if fmt == "u16" else fusion, "base" if row is None else lr.PARAM_IDS[row], i["depth"], i["state_in"], i["grid_pose"], i["cam_pose"],
+          i["kw"], fmt=fmt, scale=i["depth_scale"], want=lr.param_reference(fmt, row))
+
+
+# ---- masks off the full tile, in both formats and behind device pointers ----------------------------------------------------------
+@pytest.mark.parametrize("fmt", ["f32", "u16"])
+def test_the_mask_on_partial_pixel_tiles(fmt, fusion, fusion_u16):
+    """37 x 29 at stride 3: the threads of a partial tile that lie outside the image read no mask"""
+    i = lr.small_inputs(fmt)
+    f = fusion_u16 if fmt == "u16" else fusion
+    for mode in (1, 2):
+        got, _ = check(f, "37x29 mask_mode %d" % mode, i["depth"], i["state_in"], i["grid_pose"], i["cam_pose"], dict(i["kw"], mask_mode=mode),
+                       mask=i["mask"], fmt=fmt, scale=i["depth_scale"])
+        assert 0 < got["stats"]["pixels_stamping"] < got["stats"]["pixels_valid"] and got["stats"]["cells_stamped"] > 0
+
+
+def test_a_device_mask_inside_guard_bytes(fusion_u16):
+    """depth, mask and grid behind device pointers, mask_mode 2: the 37 x 29 mask starts at an odd address between sentinel bytes"""
+    import torch
+    dev = torch.device("cuda")
+    i = lr.small_inputs("u16")
+    kw = dict(i["kw"], mask_mode=2)
+    want = lr.overlay(i["depth"], i["mask"], i["state_in"], i["grid_pose"], i["cam_pose"], lr.params(**kw), "u16", i["depth_scale"])
+    gw, gh, G = kw["width"], kw["height"], 67
+    guarded = np.full(2 * G + i["mask"].size, 0xA5, np.uint8)
+    guarded[G:-G] = i["mask"].ravel()
+    d_mask = torch.from_numpy(guarded).to(dev)
+    d_depth, d_in = torch.from_numpy(i["depth"].view(np.int16)).to(dev), torch.from_numpy(i["state_in"]).to(dev)
+    out = dict(live_hits=torch.zeros((gh, gw), dtype=torch.int32, device=dev), live_seen=torch.zeros((gh, gw), dtype=torch.int32, device=dev),
+               state_out=torch.zeros((gh, gw), dtype=torch.int8, device=dev), dist2=torch.zeros((gh, gw), dtype=torch.int32, device=dev))
+    stats = fusion_u16.nav_live_device(d_depth, d_in, gw, gh, mask=d_mask.data_ptr() + G, grid_pose=i["grid_pose"], cam_pose=i["cam_pose"],
+                                       **dict(out, **call_kw(kw)))
+    got = dict(live_hits=out["live_hits"].cpu().numpy().view(np.uint32), live_seen=out["live_seen"].cpu().numpy().view(np.uint32),
+               state=out["state_out"].cpu().numpy(), dist2=out["dist2"].cpu().numpy(), stats=stats)
+    same(got, want, "device mask")
+    assert (d_mask.cpu().numpy() == guarded).all() and (d_in.cpu().numpy() == i["state_in"]).all()
+    assert 0 < stats["pixels_stamping"] < stats["pixels_valid"]
+
+
+# ---- rays longer than a round of 64 samples, sixteen to a wave ---------------------------------------------------------------------
+@pytest.mark.parametrize("shift", lr.EDGE_SHIFTS)
+@pytest.mark.parametrize("tilt", lr.EDGE_TILTS)
+def test_rays_that_end_on_both_sides_of_a_round_of_64_samples(tilt, shift, fusion):
+    """64 x 2 pixels at stride 1: eight waves of sixteen rays of 49 .. 80 and 113 .. 144 samples (tests/test_navlive.py recomputes them);
+    shifted, a round ends in the middle of a wave"""
+    i = lr.edge_inputs(tilt, shift)
+    got, _ = check(fusion, "round edges, tilt %g, shift %d" % (tilt, shift), i["depth"], i["state_in"], i["grid_pose"], i["cam_pose"], i["kw"])
+    assert (got["stats"]["rays_carving"], got["stats"]["ray_samples"]) == (126, 12167 if shift == 0 else 12671)
+
+
 # ---- specific cases ------------------------------------------------------------------------------------------------------------
 def test_every_point_in_one_cell(fusion):
     """the contention case: a constant depth and a lens so long that the whole image lands in one cell"""
@@ -165,8 +221,7 @@ def test_a_camera_outside_the_grid_and_a_pose_that_is_not_finite(fusion):
 
 def test_the_mask_modes(fusion):
     i = lr.case_inputs("room rolled", "f32", 8)
-    mask = (np.random.default_rng(4).random((H, W)) < 0.4).astype(np.uint8) * 3
-    mask[:, 60:100] = 1
+    mask = lr.modes_mask()                                               # 40 % random, a solid band, values other than 1
     seen = []
     for mode in (0, 1, 2):
         got, _ = check(fusion, "mask_mode %d" % mode, i["depth"], i["state_in"], i["grid_pose"], i["cam_pose"], dict(i["kw"], mask_mode=mode), mask=mask)
@@ -353,6 +408,20 @@ def test_the_refusals(live_lib):
         with refused:
             f.nav_live_device(d_depth, d_in, gw, gh, **dict(out, **base))
     f.nav_live_device(d_depth, d_in, gw, gh, state_out=d_in, **base)      # the one overlap that is the update in place
+    # the mask is one of the arrays only when it is read: an output on its first byte alone, on its last alone, and beside it
+    mbuf = torch.zeros(2 * P + W * H, dtype=torch.uint8, device=dev)
+    m = mbuf.data_ptr() + P
+    for ptr in (m - P + 1, m + W * H - 1, m):
+        with refused:
+            f.nav_live_device(d_depth, d_in, gw, gh, mask=m, state_out=ptr, **dict(base, mask_mode=2))
+        assert live_lib.lib.ssf_last_error(f.h).decode() == "ssf_navlive_overlay: arrays overlap (only state == state_in may)"
+    with refused:
+        f.nav_live_device(d_depth, d_in, gw, gh, mask=m, dist2=m + W * H - 4, **dict(base, mask_mode=1))
+    assert not mbuf.any()                                                # refused before any kernel
+    for ptr in (m - P, m + W * H):
+        f.nav_live_device(d_depth, d_in, gw, gh, mask=m, state_out=ptr, **dict(base, mask_mode=2))
+    for ptr in (m - P + 1, m + W * H - 1, m):
+        f.nav_live_device(d_depth, d_in, gw, gh, mask=m, state_out=ptr, **dict(base, mask_mode=0))
     # the C entry points themselves
     L, byref, vp = live_lib.lib, binding.C.byref, binding.C.c_void_p
     p, st = binding.SsfNavLiveParams(), binding.SsfNavLiveStats()

@@ -184,3 +184,126 @@ def test_the_random_layers_of_the_gpu_cases_exercise_every_branch():
         assert got["stats"]["cells_expired"] > 0 and got["stats"]["cells_remembered"] > 0
         assert int(got["hit_bits"].max()) < (1 << slices) and (slices == 1 or len(np.unique(got["seen_bits"])) > 2)
     assert all(v > 0 for v in seen.values()), seen
+
+
+# ---- the guards of the parameter space, the masks and the round-edge rays of the GPU file ------------------------------------------
+@pytest.mark.parametrize("fmt", lr.PARAM_FORMATS)
+@pytest.mark.parametrize("row", range(len(mr.PARAM_ROWS)), ids=mr.PARAM_IDS)
+def test_every_row_of_the_parameter_space_changes_its_arrays(row, fmt):
+    base, got = mr.param_reference(fmt, None), mr.param_reference(fmt, row)
+    arrays = mr.PARAM_ROWS[row][2]
+    differ = [bool((got[a] != base[a]).any()) for a in arrays]
+    print(mr.PARAM_IDS[row], fmt, {a: int((got[a] != base[a]).sum()) for a in arrays})
+    if (mr.PARAM_IDS[row], fmt) in mr.PARAM_UNCHANGED:
+        assert not any(differ), (mr.PARAM_IDS[row], fmt, "is listed as a row that changes nothing")
+    else:
+        assert all(differ), (mr.PARAM_IDS[row], fmt, "repeats the base case", arrays, differ)
+
+
+def test_the_parameter_space_is_the_overlays_without_min_seen():
+    over = [r[1] for r in mr.PARAM_ROWS]
+    assert over == [{k: v for k, v in r[0].items() if k != "min_seen"} for r in lr.PARAM_ROWS if set(r[0]) != {"min_seen"}]
+    assert len(over) == len(lr.PARAM_ROWS) - 2 == len(mr.PARAM_IDS) and dict(min_hits=64, stride=7) in over and not any("min_seen" in o for o in over)
+    changed = lambda k, fmt: all((mr.param_reference(fmt, k)[a] != mr.param_reference(fmt, None)[a]).any() for a in mr.PARAM_ROWS[k][2])
+    for name, fmt in mr.PARAM_UNCHANGED:                                 # another row of the same parameter changes its array in that format
+        o = over[mr.PARAM_IDS.index(name)]
+        others = [k for k, x in enumerate(over) if set(x) == set(o) and (mr.PARAM_IDS[k], fmt) not in mr.PARAM_UNCHANGED]
+        assert others and all(changed(k, fmt) for k in others), (name, fmt)
+    # the base case is random_case()'s kind: five slices, both ages on, a random layer with marks that expire and marks that stay
+    i = mr.param_inputs("f32", {})
+    assert (i["c"]["slices"], i["c"]["tick"], i["c"]["max_mark_age"], i["c"]["max_seen_age"]) == (5, mr.GPU_TICK, 40, 25)
+    base = mr.param_reference("f32", None)["stats"]
+    assert base["cells_expired"] > 0 and base["cells_remembered"] > 0 and base["cells_cleared"] > 0 and base["cells_opened"] > 0
+    # open_unknown = 0: no cell is opened, in cells whose seen_tick is not 0 -- the branch rule.open_unknown && st != 0
+    closed = mr.param_reference("f32", mr.PARAM_IDS.index("open_unknown=0"))
+    assert closed["stats"]["cells_opened"] == 0 and ((closed["seen_tick"] != 0) & (closed["state"] == -1)).sum() > 100
+    assert closed["stats"]["cells_remembered"] == base["cells_remembered"]
+    # margin 0: rays clear bits in the cells their own pixels mark (hit wins over seen: m = (m_in & ~sb) | hb)
+    zero = mr.param_reference("f32", mr.PARAM_IDS.index("hit_margin_cells=0.0"))
+    hb = np.where(zero["live_hits"] >= 4, zero["hit_bits"], 0)
+    assert ((hb & zero["seen_bits"]) != 0).sum() > 0 and ((zero["marks"] & hb) == hb).all()
+
+
+@pytest.mark.parametrize("fmt", ["f32", "u16"])
+def test_the_mask_modes_on_the_large_image(fmt):
+    i = mr.masked_inputs(fmt)
+    run = lambda mode: mr.update(i["depth"], i["mask"], i["state_in"], i["layer"], i["grid_pose"], i["cam_pose"], dict(i["c"], mask_mode=mode), fmt,
+                                 i["depth_scale"])
+    got = [run(m) for m in (0, 1, 2)]
+    assert (got[0]["live_hits"] == got[1]["live_hits"] + got[2]["live_hits"]).all() and (got[0]["hit_bits"] == got[1]["hit_bits"] | got[2]["hit_bits"]).all()
+    assert got[1]["stats"]["pixels_stamping"] + got[2]["stats"]["pixels_stamping"] == got[0]["stats"]["pixels_valid"]
+    for a, b in ((0, 1), (0, 2), (1, 2)):
+        assert (got[a]["live_hits"] != got[b]["live_hits"]).any() and (got[a]["seen_bits"] == got[b]["seen_bits"]).all()
+        assert (got[a]["seen_tick"] == got[b]["seen_tick"]).all()
+    assert (got[1]["marks"] != got[2]["marks"]).any() and (got[1]["hit_bits"] != got[2]["hit_bits"]).any()
+    assert all(0 < g["stats"]["pixels_stamping"] < got[0]["stats"]["pixels_valid"] and g["stats"]["cells_newly_marked"] > 0 for g in got[1:])
+
+
+@pytest.mark.parametrize("fmt", ["f32", "u16"])
+def test_the_mask_of_the_small_image_splits_its_pixels(fmt):
+    i = mr.small_inputs(fmt)
+    assert (i["depth"].shape, i["mask"].shape, i["state_in"].shape) == ((29, 37), (29, 37), (33, 31))
+    run = lambda mode: mr.update(i["depth"], i["mask"], i["state_in"], i["layer"], i["grid_pose"], i["cam_pose"],
+                                 mr.params(**dict(i["kw"], mask_mode=mode)), fmt, i["depth_scale"])
+    only, rest = run(1), run(2)
+    for got in (only, rest):
+        s = got["stats"]
+        print(fmt, s)
+        assert 0 < s["pixels_stamping"] < s["pixels_valid"] and s["cells_newly_marked"] > 0 and s["rays"] > 64
+    assert (only["stats"]["pixels_stamping"], rest["stats"]["pixels_stamping"], rest["stats"]["pixels_valid"]) == ((413, 421, 834) if fmt == "f32" else (414, 421, 835))
+    assert (only["marks"] != rest["marks"]).any() and (only["seen_bits"] == rest["seen_bits"]).all()
+
+
+@pytest.mark.parametrize("tilt", lr.EDGE_TILTS)
+def test_the_round_edge_rays_end_on_both_sides_of_a_round(tilt):
+    i = mr.edge_inputs(tilt)
+    c = mr.params(**i["kw"])
+    run = lambda d, i: mr.update(d, None, i["state_in"], None, i["grid_pose"], i["cam_pose"], c)
+    got = run(i["depth"], i)
+    s = got["stats"]
+    assert (s["pixels_valid"], s["rays"], s["rays_carving"], s["ray_samples"], c["slices"]) == (126, 126, 126, 12167, 32)
+    n = lr.edge_ray_counts(tilt, lambda d, i: run(d, i)["stats"])
+    assert n.sum() == s["ray_samples"] and [(v, u) for v, u in np.argwhere(n == 0)] == list(lr.EDGE_INVALID)
+    assert set(n[0]) - {0} == set(range(49, 81)) and set(n[1]) - {0} == set(range(113, 145))
+    for count in lr.EDGE_COUNTS:
+        assert (n == count).any(), count
+    # a tilted ray climbs or falls through the slices: a cell that continues over a round's end brings a new bit in most cells; the
+    # level camera's rays stay in one slice (and the two image rows in two), so a continued cell brings none
+    words = len(np.unique(got["seen_bits"]))
+    print(tilt, words)
+    assert (17 <= words <= 18) if tilt else words == 3
+    assert s["cells_marked"] > 30 and s["cells_opened"] > 100
+
+
+def test_a_camera_that_sees_nothing_only_ages_the_layer():
+    """the GPU file's camera outside the grid and its poses that are not finite, on the restatement: no hit, no seen bit, and a layer with
+    marks on both sides of the age"""
+    i, _ = mr.case_evidence("room straight", "f32", 4)
+    c = mr.params(**dict(i["kw"], slices=5, tick=mr.GPU_TICK, **mr.GPU_AGES))
+    layer = mr.random_layer(c["width"], c["height"], 3, mr.GPU_TICK, slices=5, **mr.GPU_AGES)
+    zero = np.zeros((c["height"], c["width"]), np.uint32)
+    aged = mr.cells_rule(zero, zero, zero, i["state_in"], layer, c)
+    assert aged["stats"]["cells_expired"] > 0 and aged["stats"]["cells_marked"] > 0 and (aged["seen_tick"] != layer["seen_tick"]).any()
+    poses = [lr.room_pose(at=(40.0, 0.0, -30.0))]
+    for k, bad in ((0, np.nan), (4, np.inf), (9, np.nan), (11, -np.inf)):
+        poses.append(i["cam_pose"].copy())
+        poses[-1][k] = bad
+    for pose in poses:
+        got = mr.update(i["depth"], None, i["state_in"], layer, i["grid_pose"], pose, c)
+        assert not got["live_hits"].any() and not got["hit_bits"].any() and not got["seen_bits"].any()
+        assert all((got[nm] == aged[nm]).all() for nm in mr.LAYER + ("state",)) and all(got["stats"][k] == n for k, n in aged["stats"].items())
+    assert got["stats"]["rays"] > 0 and mr.update(i["depth"], None, i["state_in"], layer, i["grid_pose"], poses[0], c)["stats"]["ray_samples"] > 0
+
+
+@pytest.mark.parametrize("tilt", lr.EDGE_TILTS)
+def test_the_shifted_round_edge_rays_end_a_round_inside_a_wave(tilt):
+    i = mr.edge_inputs(tilt, 8)
+    c = mr.params(**i["kw"])
+    run = lambda d, i: mr.update(d, None, i["state_in"], None, i["grid_pose"], i["cam_pose"], c)
+    got = run(i["depth"], i)
+    n = lr.edge_ray_counts(tilt, lambda d, i: run(d, i)["stats"], 8)
+    assert (got["stats"]["rays_carving"], got["stats"]["ray_samples"], c["slices"]) == (126, n.sum(), 32)
+    waves = [set(n.ravel()[k:k + 16]) for k in range(0, 128, 16)]
+    assert {64, 65} <= waves[1] and {128, 129} <= waves[5]
+    words = len(np.unique(got["seen_bits"]))
+    assert words > 12 if tilt else words == 3

@@ -1,6 +1,7 @@
 """The live layer with memory (include/ssf_navmem.h) on the GPU: every array and every exact stat of ssf_navmem_update equals the numpy
 restatement (tests/navmem_ref.py) with ==, on the scenes that tests/test_navmem.py guards against being vacuous, with zero and random
-layers, on the smallest images and grids at which the kernels take another path, on boundary cases with hand-written answers, through
+layers, on the smallest images and grids at which the kernels take another path, with every parameter off its default in turn, under the
+three mask modes, with rays that end on both sides of a round of 64 samples, on boundary cases with hand-written answers, through
 device pointers and in place, against the device's own ssf_navlive_overlay, and through nav_memory_plan and nav_memory_dyn_steer."""
 import numpy as np
 import pytest
@@ -126,6 +127,83 @@ def test_image_and_grid_shapes(fmt, fusion, fusion_u16):
     assert points > 0
 
 
+# ---- the parameter space: one entry off its default at a time (tests/test_navmem.py guards that each row changes its arrays) ------
+@pytest.mark.parametrize("fmt", lr.PARAM_FORMATS)
+@pytest.mark.parametrize("row", [None] + list(range(len(mr.PARAM_ROWS))), ids=("base",) + mr.PARAM_IDS)
+def test_the_parameter_space(row, fmt, fusion, fusion_u16):
+    i = mr.param_inputs(fmt, {} if row is None else mr.PARAM_ROWS[row][1])
+    got, _ = check(fusion_u16 if fmt == "u16" else fusion, "base" if row is None else mr.PARAM_IDS[row], i["depth"], i["state_in"], i["layer"], i["grid_pose"],
+                   i["cam_pose"], i["kw"], fmt=fmt, scale=i["depth_scale"], want=mr.param_reference(fmt, row))
+    assert got["stats"]["cells_opened"] > 0 or not i["c"]["open_unknown"]
+
+
+# ---- the mask: the three modes against the restatement, off the full tile, behind device pointers --------------------------------
+@pytest.mark.parametrize("fmt", ["f32", "u16"])
+def test_the_mask_modes(fmt, fusion, fusion_u16):
+    i = mr.masked_inputs(fmt)
+    f = fusion_u16 if fmt == "u16" else fusion
+    seen = []
+    for mode in (0, 1, 2):
+        got, _ = check(f, "mask_mode %d" % mode, i["depth"], i["state_in"], i["layer"], i["grid_pose"], i["cam_pose"], dict(i["kw"], mask_mode=mode),
+                       mask=i["mask"], fmt=fmt, scale=i["depth_scale"])
+        seen.append(got)                                                 # (each check has a memory of its own)
+    assert (seen[0]["live_hits"] == seen[1]["live_hits"] + seen[2]["live_hits"]).all()
+    for got in seen[1:]:                                                 # the rays do not consult the mask
+        assert (got["seen_bits"] == seen[0]["seen_bits"]).all() and (got["seen_tick"] == seen[0]["seen_tick"]).all()
+        assert all(got["stats"][k] == seen[0]["stats"][k] for k in ("pixels_valid", "rays", "rays_carving", "ray_samples"))
+    assert seen[1]["stats"]["pixels_stamping"] + seen[2]["stats"]["pixels_stamping"] == seen[0]["stats"]["pixels_valid"]
+
+
+@pytest.mark.parametrize("fmt", ["f32", "u16"])
+def test_the_mask_on_partial_pixel_tiles(fmt, fusion, fusion_u16):
+    """37 x 29 at stride 3: the threads of a partial tile that lie outside the image read no mask"""
+    i = mr.small_inputs(fmt)
+    f = fusion_u16 if fmt == "u16" else fusion
+    for mode in (1, 2):
+        got, _ = check(f, "37x29 mask_mode %d" % mode, i["depth"], i["state_in"], i["layer"], i["grid_pose"], i["cam_pose"], dict(i["kw"], mask_mode=mode),
+                       mask=i["mask"], fmt=fmt, scale=i["depth_scale"])
+        assert 0 < got["stats"]["pixels_stamping"] < got["stats"]["pixels_valid"] and got["stats"]["cells_newly_marked"] > 0
+
+
+def test_a_device_mask_inside_guard_bytes(fusion):
+    """depth, mask, grid and layer behind device pointers, mask_mode 2: the 37 x 29 mask starts at an odd address between sentinel bytes"""
+    import torch
+    dev = torch.device("cuda")
+    i = mr.small_inputs("f32")
+    kw = dict(i["kw"], mask_mode=2)
+    c = mr.params(**kw)
+    want = mr.update(i["depth"], i["mask"], i["state_in"], i["layer"], i["grid_pose"], i["cam_pose"], c)
+    gw, gh, G = c["width"], c["height"], 67
+    guarded = np.full(2 * G + i["mask"].size, 0xA5, np.uint8)
+    guarded[G:-G] = i["mask"].ravel()
+    d_mask = torch.from_numpy(guarded).to(dev)
+    d_depth, d_in = torch.from_numpy(i["depth"]).to(dev), torch.from_numpy(i["state_in"]).to(dev)
+    d_lay = [torch.from_numpy(i["layer"][nm].view(np.int32)).to(dev) for nm in mr.LAYER]
+    out = {nm: torch.zeros((gh, gw), dtype=torch.int8 if nm == "state" else torch.int32, device=dev) for nm in mr.OUTPUTS}
+    stats = fusion.nav_memory_device(d_depth, d_in, gw, gh, mask=d_mask.data_ptr() + G, layer_in=d_lay, grid_pose=i["grid_pose"], cam_pose=i["cam_pose"],
+                                     **dict({("state_out" if nm == "state" else nm): t for nm, t in out.items()}, **call_kw(kw)), tick=c["tick"])
+    got = {nm: t.cpu().numpy().view(want[nm].dtype) for nm, t in out.items()}
+    same(dict(got, stats=stats), want, "device mask")
+    assert (d_mask.cpu().numpy() == guarded).all() and (d_in.cpu().numpy() == i["state_in"]).all()
+    assert all((t.cpu().numpy().view(np.uint32) == i["layer"][nm]).all() for t, nm in zip(d_lay, mr.LAYER))
+    assert 0 < stats["pixels_stamping"] < stats["pixels_valid"]
+
+
+# ---- rays at the ends of a round of 64 samples, sixteen to a wave -----------------------------------------------------------------
+@pytest.mark.parametrize("shift", lr.EDGE_SHIFTS)
+@pytest.mark.parametrize("tilt", lr.EDGE_TILTS)
+def test_rays_that_end_on_both_sides_of_a_round_of_64_samples(tilt, shift, fusion):
+    """64 x 2 pixels at stride 1: eight waves of sixteen rays of 49 .. 80 and 113 .. 144 samples (tests/test_navmem.py recomputes them):
+    the pending pair merges across the rays of a wave while the carry crosses the rounds of each; tilted, a continued cell brings a new
+    bit in most cells, level it brings none.  Shifted, a round ends in the middle of a wave: its pending pair lives across rays of one
+    round and of two"""
+    i = mr.edge_inputs(tilt, shift)
+    got, _ = check(fusion, "round edges, tilt %g, shift %d" % (tilt, shift), i["depth"], i["state_in"], None, i["grid_pose"], i["cam_pose"], i["kw"])
+    assert (got["stats"]["rays_carving"], got["stats"]["ray_samples"]) == (126, 12167 if shift == 0 else 12671)
+    words = len(np.unique(got["seen_bits"]))
+    assert words > 12 if tilt else words == 3
+
+
 def test_the_boundary_cases(fusion):
     for name, d, at, kw, want in mr.boundary_cases():
         kw = dict(lr.BOUNDARY, **kw)
@@ -229,6 +307,55 @@ def test_without_a_valid_pixel_the_layer_is_a_fixed_point(fusion):
     got, _ = check(fusion, "no valid pixel", np.zeros((H, W), np.float32), i["state_in"], layer, i["grid_pose"], i["cam_pose"], kw)
     for nm in mr.LAYER:
         assert (got[nm] == layer[nm]).all(), nm
+
+
+# ---- the handle's defaults and cameras that see nothing ----------------------------------------------------------------------------
+def test_the_default_frame_and_camera_are_the_handles(mem_lib):
+    """grid_pose None = nav_grid_default_pose now, cam_pose None = the tracked pose, cam_width 0 = cfg's camera, t = cfg's range"""
+    f = handle(mem_lib)
+    rgb, depth = util.frame(0, W, H)
+    f.process_frame(rgb, depth)
+    K = util.synthetic.intrinsics(W, H)
+    kw = dict(width=65, height=64, res=0.1, max_dist_cells=7, stride=8, slices=9, tick=mr.GPU_TICK, **mr.GPU_AGES)
+    c = mr.params(cfg_camera=K, **kw)
+    grid_pose = nr.default_pose(f.get_pose(), c)
+    state_in = np.full((64, 65), -1, np.int8)
+    layer = mr.random_layer(65, 64, 5, mr.GPU_TICK, slices=9, **mr.GPU_AGES)
+    want = mr.update(depth, None, state_in, layer, grid_pose, f.get_pose(), c)
+    mem = host_memory(layer, 65, 64, mr.GPU_TICK)
+    got = f.nav_memory(depth, state_in, memory=mem, **call_kw(kw))
+    same(got, want, "defaults")
+    assert (got["stats"]["pose"] == grid_pose).all() and (f.nav_grid_default_pose(width=65, height=64, res=0.1) == grid_pose).all()
+    assert got["stats"]["points_in_band"] > 0 and got["stats"]["ray_samples"] > 0 and got["stats"]["bits_cleared"] > 0 and mem.tick == mr.GPU_TICK
+    f.close()
+
+
+def test_a_camera_outside_the_grid_and_a_pose_that_is_not_finite(fusion):
+    """no point and no sample reaches the grid: only ageing changes the layer"""
+    i, _ = mr.case_evidence("room straight", "f32", 4)
+    kw = dict(i["kw"], slices=5, tick=mr.GPU_TICK, **mr.GPU_AGES)
+    c = mr.params(**kw)
+    layer = mr.random_layer(c["width"], c["height"], 3, mr.GPU_TICK, slices=5, **mr.GPU_AGES)
+    zero = np.zeros((c["height"], c["width"]), np.uint32)
+    aged = mr.cells_rule(zero, zero, zero, i["state_in"], layer, c)
+
+    def only_ageing(got, what):
+        assert not got["live_hits"].any() and not got["hit_bits"].any() and not got["seen_bits"].any(), what
+        assert all((got[nm] == aged[nm]).all() for nm in mr.LAYER + ("state",)), what
+        s = got["stats"]
+        assert all(s[k] == n for k, n in aged["stats"].items()), (what, s, aged["stats"])
+        assert s["cells_expired"] > 0 and s["cells_cleared"] == 0 == s["bits_cleared"] == s["cells_newly_marked"] and s["pixels_valid"] > 0 and s["rays"] > 0, what
+    got, _ = check(fusion, "outside", i["depth"], i["state_in"], layer, i["grid_pose"], lr.room_pose(at=(40.0, 0.0, -30.0)), kw)
+    only_ageing(got, "outside")
+    assert got["stats"]["points_in_band"] == 0 and got["stats"]["rays_carving"] > 0 and got["stats"]["ray_samples"] > 0
+    for k, bad in ((0, np.nan), (4, np.inf), (9, np.nan), (11, -np.inf)):
+        pose = i["cam_pose"].copy()
+        pose[k] = bad
+        got, _ = check(fusion, "pose[%d] = %s" % (k, bad), i["depth"], i["state_in"], layer, i["grid_pose"], pose, kw)
+        only_ageing(got, "pose[%d] = %s" % (k, bad))
+        assert got["stats"]["rays_carving"] == 0 == got["stats"]["ray_samples"] == got["stats"]["points_in_band"] or k == 0
+    got, _ = check(fusion, "after the poses", i["depth"], i["state_in"], layer, i["grid_pose"], i["cam_pose"], kw)
+    assert got["stats"]["cells_newly_marked"] > 0 and got["stats"]["bits_cleared"] > 0
 
 
 # ---- pointers and outputs --------------------------------------------------------------------------------------------------------
@@ -362,6 +489,21 @@ def test_the_refusals(mem_lib):
         with refused:
             f.nav_memory_device(d_depth, d_in, gw, gh, **dict(out, **base))
     f.nav_memory_device(d_depth, d_in, gw, gh, layer_in=lay, marks=lay[0], mark_tick=lay[1], seen_tick=lay[2], state_out=d_in, **base)      # in place
+    # the mask is one of the arrays only when it is read: an output on its first byte alone, on its last alone, and beside it
+    mbuf = torch.zeros(2 * P + W * H, dtype=torch.uint8, device=dev)
+    m = mbuf.data_ptr() + P
+    for ptr in (m - P + 1, m + W * H - 1, m):
+        with refused:
+            f.nav_memory_device(d_depth, d_in, gw, gh, mask=m, state_out=ptr, **dict(base, mask_mode=2))
+        assert mem_lib.lib.ssf_last_error(f.h).decode() == ("ssf_navmem_update: arrays overlap (only an output of the layer on its own input, and "
+                                                            "state == state_in, may)")
+    with refused:
+        f.nav_memory_device(d_depth, d_in, gw, gh, mask=m, seen_bits=m + W * H - 4, **dict(base, mask_mode=1))
+    assert not mbuf.any()                                                # refused before any kernel
+    for ptr in (m - P, m + W * H):
+        f.nav_memory_device(d_depth, d_in, gw, gh, mask=m, state_out=ptr, **dict(base, mask_mode=2))
+    for ptr in (m - P + 1, m + W * H - 1, m):
+        f.nav_memory_device(d_depth, d_in, gw, gh, mask=m, state_out=ptr, **dict(base, mask_mode=0))
     with pytest.raises(binding.SsfError, match="LiveMemory"):
         f.nav_memory_device(d_depth, d_in, gw, gh, memory=binding.LiveMemory(gw, gh), dist2=a, **base)
     with pytest.raises(binding.SsfError, match="LiveMemory"):
