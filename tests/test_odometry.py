@@ -1,7 +1,9 @@
 """Dense RGB-D odometry (include/ssf_odometry.h) without a GPU: who exports the entry points, the header on its own, the struct
 layouts of the binding, the C++ surface, replay.py's option, and the numpy restatement the GPU tests compare against
 (tests/odometry_ref.py): known answers of the pyramid, the range and format rules, the mask, the record of a frame against itself,
-the header's overflow argument evaluated at 1280 x 960, and the recovery of known motions on synthetic and real frames."""
+the header's overflow argument evaluated at 1280 x 960, the recovery of known motions on synthetic and real frames, and, for every
+input of tests/test_odometry_edges_gpu.py (tests/odometry_cases.py), that the restatement's output on it has the property the input
+was built for."""
 import ctypes as C
 import functools
 import os
@@ -10,8 +12,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import odometry_cases as oc
 import odometry_ref as orf
 from conftest import ROOT
+from odometry_cases import exact_frame
 from supersurfel_fusion_amd import binding, replay, synthetic
 
 INCLUDE = os.path.join(ROOT, "include")
@@ -250,14 +254,6 @@ def test_uint16_depth_is_scaled_in_double_and_rounded_once():
     assert got.dtype == f32 and got[0].tolist() == [float(f32(float(x) * 0.0002)) for x in v[0]]
 
 
-def exact_frame(W=64, H=48, seed=0):
-    """a frame whose warp at the identity is exact: power-of-two focal length and depths, half-integer principal point"""
-    rng = np.random.default_rng(seed)
-    rgb = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
-    depth = rng.choice(np.array([0, 0.5, 1, 2, 4], f32), (H, W)).astype(f32)
-    return rgb, depth, (64.0, 64.0, W / 2 - 0.5, H / 2 - 0.5)
-
-
 def test_a_frame_against_itself_at_the_identity_has_no_residual():
     rgb, depth, K = exact_frame()
     pyr = orf.pyramid(rgb, depth, K)
@@ -368,3 +364,217 @@ def test_the_prior_composition_is_the_f32_product_of_the_two_poses():
     assert np.array_equal(orf.compose(orf.IDENTITY12, r), r)
     T = orf.from12(r)
     assert np.abs(orf.mat4_lmul(orf.invert(T), T) - np.eye(4)).max() < 1e-7
+
+
+# ---- the inputs of tests/test_odometry_edges_gpu.py (tests/odometry_cases.py): each is shown to reach what it is there for ------
+def test_644x410_has_six_levels_four_odd_reductions_and_more_pixels_than_the_launch_has_threads():
+    W, H = oc.BIG
+    assert W * H == 264040 > oc.MAX_BLOCKS * oc.BLOCK and -(-W * H // oc.BLOCK) == 1032
+    assert orf.level_sizes(W, H) == oc.BIG_SIZES and len(oc.BIG_SIZES) == orf.MAX_LEVELS
+    assert sum(1 for w, h in oc.BIG_SIZES[:-1] if w % 2 or h % 2) == 4
+    W3, H3 = oc.THREE_TRIPS
+    assert 2 * oc.MAX_BLOCKS * oc.BLOCK < W3 * H3 < 3 * oc.MAX_BLOCKS * oc.BLOCK
+    assert [orf.level_sizes(w, h) for w, h, _ in oc.ODD] == [s for _, _, s in oc.ODD]
+    for _, _, sizes in oc.ODD:                                           # every reduction but the first starts from an odd width or height
+        assert all(w % 2 or h % 2 for w, h in sizes[1:-1]) and len(sizes) >= 3
+
+
+def test_the_644x410_record_at_the_identity_has_more_than_half_of_every_level():
+    W, H = oc.BIG
+    ref, cur = oc.pyramid(0, W, H), oc.pyramid(1, W, H)
+    p = orf.params(levels=6)
+    counts = [int(orf.record(ref[l], cur[l], orf.IDENTITY12, p)[28]) for l in range(6)]
+    assert all(2 * n > lv["W"] * lv["H"] for n, lv in zip(counts, ref)), counts
+    assert counts[0] == 197048 and counts[5] == 200 and ref[5]["W"] * ref[5]["H"] == 240
+    for l in (4, 5):
+        assert np.array_equal(orf.record(ref[l], cur[l], oc.transform("small"), p), orf.record(ref[l], cur[l], oc.transform("small"), p, exact=True))
+    assert 0 < int(orf.record(ref[5], cur[5], oc.transform("behind"), p)[28]) < counts[5]
+
+
+def test_the_second_trip_of_644x410_has_pixels_of_its_own_and_the_two_masks_share_out_the_record():
+    W, H = oc.BIG
+    head, tail = oc.trip_masks(W, H)
+    assert head.sum() == oc.MAX_BLOCKS * oc.BLOCK and tail.sum() == 1896 and not (head & tail).any() and (head | tail).all()
+    assert head.ravel()[:oc.MAX_BLOCKS * oc.BLOCK].all()
+    cur = oc.pyramid(1, W, H)[0]
+    p = orf.params(levels=6)
+    second, first, full = (orf.record(py[0], cur, orf.IDENTITY12, p) for py in (oc.masked_pyramid(0), oc.masked_pyramid(1), oc.pyramid(0, W, H)))
+    assert second[28] == 936 >= 500 and first[28] == full[28] - 936
+    assert np.array_equal(first + second, full)
+    ys, xs = np.nonzero(oc.masked_pyramid(0)[0]["D"])
+    assert (ys * W + xs).min() >= oc.MAX_BLOCKS * oc.BLOCK
+
+
+def test_1024x513_has_pixels_in_the_record_from_all_three_trips():
+    W, H = oc.THREE_TRIPS
+    ref, cur = oc.pyramid(0, W, H)[0], oc.pyramid(1, W, H)[0]
+    n = oc.MAX_BLOCKS * oc.BLOCK
+    assert 2 * n == W * (H - 1)                                          # the third trip is exactly the last row
+    counts = {}
+    for trip, (lo, hi) in enumerate(((0, n), (n, 2 * n), (2 * n, W * H))):
+        only = dict(ref, D=np.where((np.arange(W * H) >= lo) & (np.arange(W * H) < hi), ref["D"].ravel(), f32(0)).reshape(H, W))
+        for nm, T in oc.three_trip_transforms():
+            counts[(trip, nm)] = int(orf.record(only, cur, T, orf.params())[28])
+    print(counts)
+    assert counts[(0, "small")] > n // 2 and counts[(1, "small")] > n // 2 and counts[(0, "up")] > n // 2 and counts[(1, "up")] > n // 2
+    assert counts[(2, "small")] == 0 and counts[(2, "up")] > W // 4      # (a quarter of the row: depth holes and the residual gate take the rest)
+
+
+def test_the_dropped_column_of_an_odd_level_reaches_no_coarser_level_but_that_levels_gradients():
+    """101 x 63 drops level 0's last column at once; 102 and 202 are even, so there the first dropped column is level 1's (51 and
+    101 wide), made of level 0's last two"""
+    assert [oc.first_odd_level(W) for W, _ in oc.DROPPED] == [(0, 100), (1, 100), (1, 200)]
+    for W, H in oc.DROPPED:
+        rgb, depth = oc.frame(0, W, H)
+        rgb2, depth2, l = oc.dropped_column_changed(rgb, depth)
+        assert (rgb2 != rgb).any(axis=(0, 2)).sum() == (depth2 != depth).any(axis=0).sum() == 1 << l
+        a, b = orf.pyramid(rgb, depth, oc.K4(W, H)), orf.pyramid(rgb2, depth2, oc.K4(W, H))
+        assert len(a) > l + 1 and a[l]["W"] % 2 == 1
+        for x, y in zip(a[l + 1:], b[l + 1:]):
+            assert all(np.array_equal(x[nm], y[nm]) for nm in ("I", "D", "gx", "gy"))
+        for k, (x, y) in enumerate(zip(a[:l + 1], b[:l + 1])):
+            c = 1 << (l - k)                                             # columns of level k behind the dropped one
+            assert (x["I"][:, -c:] != y["I"][:, -c:]).all() and np.array_equal(x["I"][:, :-c], y["I"][:, :-c])
+            assert (x["D"][:, -c:] != y["D"][:, -c:]).any() and np.array_equal(x["D"][:, :-c], y["D"][:, :-c])
+            assert (x["gx"][:, -c - 1:] != y["gx"][:, -c - 1:]).any(axis=0)[[0, -1]].all() and np.array_equal(x["gx"][:, :-c - 1], y["gx"][:, :-c - 1])
+            assert (x["gy"][:, -c:] != y["gy"][:, -c:]).any() and np.array_equal(x["gy"][:, :-c], y["gy"][:, :-c])
+
+
+def test_the_odd_shapes_records_have_pixels_on_every_level_and_levels_6_is_clamped(oracle_lib):
+    for W, H, sizes in oc.ODD:
+        ref, cur = oc.pyramid(0, W, H), oc.pyramid(1, W, H)
+        L = len(sizes)
+        assert len(ref) == L == (3 if W == 102 else 4)
+        for l in range(L):
+            n = {nm: int(orf.record(ref[l], cur[l], T, orf.params(levels=6))[28]) for nm, T in oc.transforms()}
+            assert 2 * n["identity"] > sizes[l][0] * sizes[l][1] and 0 < n["behind"] < n["mostly out"] < n["identity"] and n["none left"] == 0
+        res = orf.estimate(ref, cur, orf.params(levels=6), oracle_lib)[1]
+        assert res["levels"] == L and all(res["iters"][:L]) and res["iters"][L:] == [0] * (6 - L) and res["valid"] == 1
+
+
+def test_the_planted_u16_counts_fall_on_both_sides_of_both_ends_of_the_range():
+    W, H = oc.EDGE_SHAPE
+    counts, planted = oc.u16_counts(oc.frame(0, W, H)[1])
+    assert counts.dtype == np.uint16 and counts[0, :len(planted)].tolist() == planted and planted[:2] == [0, 65535]
+    d = orf.convert_depth(np.array(planted, np.uint16), oc.U16_SCALE)
+    ok = orf.valid_depth(d).tolist()
+    lo, hi = orf.RANGE
+    assert ok[0] is False and ok[1] is False and d[1] > hi
+    assert ok[2:6].count(True) >= 1 and ok[2:6].count(False) >= 1 and ok[2:6] == sorted(ok[2:6])           # below range_min, then inside
+    assert ok[6:10].count(True) >= 1 and ok[6:10].count(False) >= 1 and ok[6:10] == sorted(ok[6:10], reverse=True)
+    assert d[2] < lo <= d[5] and d[6] <= hi < d[9]
+    # random alpha bytes, and the four orders name the same image
+    rgb = oc.frame(0, W, H)[0]
+    want = orf.intensity(rgb)
+    for fmt in ("rgb8", "bgr8", "rgba8", "bgra8"):
+        c = oc.colour_as(rgb, fmt)
+        assert c.shape[2] == (4 if fmt.endswith("a8") else 3) and np.array_equal(orf.intensity(c, fmt[:-1]), want)
+        assert not fmt.endswith("a8") or len(np.unique(c[..., 3])) > 200
+    assert not np.array_equal(orf.intensity(oc.colour_as(rgb, "bgra8"), "rgba"), want)                          # (r and b swapped shows)
+
+
+def test_each_planted_depth_block_reduces_to_what_the_header_promises(oracle_lib):
+    rgb, depth, blocks = oc.planted_depth_frame()
+    lo, hi = orf.RANGE
+    flat = np.concatenate([np.array(v, f32) for _, v, _ in blocks])
+    for special in (lo, np.nextafter(lo, f32(0)), hi, np.nextafter(hi, f32(np.inf)), f32(-1), f32(1e-42)):
+        assert (flat == special).any(), special
+    assert np.isnan(flat).any() and np.isposinf(flat).any() and np.isneginf(flat).any() and (flat == 0).any()
+    assert np.signbit(flat[flat == 0]).any() and not np.signbit(flat[flat == 0]).all() and 0 < f32(1e-42) < np.finfo(f32).tiny
+    pyr = orf.pyramid(rgb, depth, oc.K4(64, 48))
+    kinds = set()
+    for (x, y), vals, want in blocks:
+        assert x % 2 == 0 and y % 2 == 0 and np.array_equal(depth[y:y + 2, x:x + 2].ravel(), np.array(vals, f32), equal_nan=True)
+        nvalid = int(orf.valid_depth(np.array(vals, f32)).sum())
+        got = pyr[1]["D"][y // 2, x // 2]
+        assert got == want and not np.signbit(got), ((x, y), got, want)
+        assert want == (min(v for v in vals if orf.valid_depth(np.array([v], f32))[0]) if nvalid else 0)
+        kinds.add(min(nvalid, 2))
+    assert kinds == {0, 1, 2}
+    for lv in pyr:
+        assert np.isfinite(lv["D"]).all() and not np.signbit(lv["D"]).any()
+    for T in (orf.IDENTITY12, oc.transform("small")):
+        assert orf.record(pyr[0], pyr[0], T, orf.params())[28] > 64 * 48 // 2
+    rel, res = orf.estimate(pyr, pyr, orf.params(levels=3), oracle_lib, init12=oc.transform("small"))
+    assert np.isfinite(rel).all() and res["valid"] == 1 and sum(res["iters"]) > 3
+
+
+def test_a_narrower_range_takes_pixels_out_of_the_pyramid_and_out_of_the_warp():
+    W, H = oc.EDGE_SHAPE
+    wide, narrow = [oc.pyramid(k, W, H) for k in (0, 1)], [oc.pyramid(k, W, H, oc.NARROW) for k in (0, 1)]
+    assert 0 < (narrow[0][0]["D"] != 0).sum() < (wide[0][0]["D"] != 0).sum()
+    for nm in ("small", "behind"):
+        T = oc.transform(nm)
+        n_wide = orf.record(wide[0][0], wide[1][0], T, orf.params())[28]
+        n_narrow = orf.record(narrow[0][0], narrow[1][0], T, orf.params(), rng=oc.NARROW)[28]
+        assert 0 < n_narrow < n_wide
+    # the gate on Y.z with the same (narrow) pyramids: 1.5 m backwards puts warped depths below 0.6 m that stay above 0.2 m
+    assert n_narrow < orf.record(narrow[0][0], narrow[1][0], oc.transform("behind"), orf.params(), rng=orf.RANGE)[28]
+
+
+def test_the_border_shifts_count_exactly_the_pixels_whose_target_has_four_neighbours():
+    rgb, depth, K = oc.border_frame()
+    assert (depth == 1).all() and K == oc.EXACT_K
+    lv = orf.pyramid(rgb, depth, K)[0]
+    p = orf.params(r_max=1.0)
+    want = {(-1, 0): 63 * 47, (0, 0): 63 * 47, (1, 0): 62 * 47, (62, 0): 1 * 47, (0, -1): 63 * 47, (0, 46): 63 * 1}
+    assert list(want) == oc.BORDER_SHIFTS
+    for (kx, ky), n in want.items():
+        assert oc.border_count(kx, ky) == n
+        q, got, _, r, _ = orf.terms(lv, lv, oc.shift12(kx, ky), p)
+        assert got == n == orf.record(lv, lv, oc.shift12(kx, ky), p)[28], (kx, ky, got, n)
+        # the warp is exact: the residual is the difference of two pixels of the image
+        ys, xs = np.mgrid[0:48, 0:64]
+        inside = (xs + kx >= 0) & (xs + kx <= 62) & (ys + ky >= 0) & (ys + ky <= 46)
+        assert np.array_equal(r, (lv["I"][(ys + ky)[inside], (xs + kx)[inside]] - lv["I"][inside]))
+    # one pixel further and nothing is left; the gate is strict: a target ON the last column is out
+    assert orf.record(lv, lv, oc.shift12(63, 0), p)[28] == 0 and orf.record(lv, lv, oc.shift12(0, 47), p)[28] == 0
+
+
+def test_every_parameter_edge_ends_the_restatements_loop_as_recorded(oracle_lib):
+    W, H = oc.EDGE_SHAPE
+    ref, cur = oc.pyramid(0, W, H), oc.pyramid(1, W, H)
+    res = {nm: orf.estimate(ref, cur, orf.params(levels=3, **kw), oracle_lib) for nm, kw in oc.PARAM_EDGES}
+    plain = orf.estimate(ref, cur, orf.params(levels=3), oracle_lib)
+    r = res["huber=0"][1]
+    assert (r["reason"], r["iters"][:3], r["mean_sq_residual"], r["valid"]) == ("converged", [1, 1, 1], 0.0, 1) and r["pixels"] > 0
+    r = res["r_max=0"][1]
+    assert (r["reason"], r["iters"][:3], r["valid"]) == ("too_few_pixels", [0, 0, 1], 0) and 0 < r["pixels"] < max(1, int(f32(0.05) * f32(25 * 15)))
+    assert (res["tol=0"][1]["reason"], res["tol=0"][1]["iters"][:3]) == ("max_iterations", [4, 6, 8])
+    assert (res["iters 2 0 3"][1]["reason"], res["iters 2 0 3"][1]["iters"][:3]) == ("max_iterations", [2, 0, 3])
+    assert (res["iters 0 0 3"][1]["reason"], res["iters 0 0 3"][1]["iters"][:3]) == ("max_iterations", [0, 0, 3])
+    r = res["max_rotation=0"]
+    assert (r[1]["reason"], r[1]["valid"]) == ("motion_gate", 0) and np.array_equal(r[0], plain[0]) and plain[1]["valid"] == 1
+    assert max(1, int(f32(1e-9) * f32(W * H))) == 1 and res["min_pixel_share tiny"][1]["valid"] == 1
+    r = res["huber above r_max"][1]
+    assert r["valid"] == 1 and 0 < r["pixels"] < plain[1]["pixels"] and r["mean_sq_residual"] < f32(0.05) ** 2
+
+
+def test_a_few_reference_pixels_give_rank_deficient_but_finite_steps(oracle_lib):
+    W, H = oc.EDGE_SHAPE
+    rgb, depth = oc.frame(0, W, H)
+    cur = oc.pyramid(1, W, H)
+    p = orf.params(levels=1, min_pixel_share=0.0)
+    reasons = set()
+    for n in (1, 3, 5, 7):
+        ref = orf.pyramid(rgb, depth, oc.K4(W, H), mask=oc.few_pixel_mask(n))
+        assert (ref[0]["D"] != 0).sum() == n
+        rec = orf.record(ref[0], cur[0], orf.IDENTITY12, p)
+        assert rec[28] == n and rec[:21].any()                                        # (each pixel adds one row of J: fewer than six up to n = 5)
+        rel, res = orf.estimate(ref, cur, p, oracle_lib)
+        assert np.isfinite(rel).all() and res["reason"] != "degenerate"
+        reasons.add(res["reason"])
+    assert len(reasons) >= 2
+
+
+def test_the_small_checkerboard_gives_the_largest_words_this_shape_can():
+    W, H = oc.EDGE_SHAPE
+    rgb, neg, depth = oc.checkerboard()
+    ref, cur = orf.pyramid(rgb, depth, oc.K4(W, H))[0], orf.pyramid(neg, depth, oc.K4(W, H))[0]
+    assert abs(ref["gx"]).max() > 0.49 and abs(ref["gy"]).max() > 0.49
+    p = orf.params(r_max=2.0, huber=2.0)
+    rec = orf.record(ref, cur, orf.IDENTITY12, p)
+    assert rec[28] == 6161 and max(int(v).bit_length() for v in rec) == 49
+    assert np.array_equal(rec, orf.record(ref, cur, orf.IDENTITY12, p, exact=True))
+    q, _, _, r, w = orf.terms(ref, cur, orf.IDENTITY12, p)
+    assert abs(r).max() > 0.9 and (w == 1).all() and 2 ** 35 <= abs(q).max() < orf.CLAMP

@@ -10,7 +10,8 @@ import pytest
 
 import odometry_ref as orf
 import util
-from supersurfel_fusion_amd import binding, synthetic
+from odometry_cases import K4, transforms, true_rel12             # (shared with tests/test_odometry_edges_gpu.py and the CPU conditions)
+from supersurfel_fusion_amd import binding
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(64, 48, 2), (100, 60, 3), (160, 128, 3)]
@@ -20,11 +21,6 @@ HOLES = 0.25
 
 def handle(lib, W, H, **kw):
     return binding.Fusion(lib, util.make_cfg(lib, W, H, **kw))
-
-
-def K4(W, H):
-    K = synthetic.intrinsics(W, H)
-    return tuple(f32(K[k]) for k in ("fx", "fy", "cx", "cy"))
 
 
 @functools.lru_cache(maxsize=None)
@@ -38,28 +34,12 @@ def ref_pyramid(k, W, H):
     return orf.pyramid(rgb, depth, K4(W, H))
 
 
-def pose12(R, t):
-    return synthetic.pose12(R, t)
-
-
 def to_device(a):
     import torch
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    a = np.array(a, order="C")                                                          # (a copy: the cached frames are read-only)
+    t = torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).cuda()       # (the same bytes: only the address is passed on)
     torch.cuda.synchronize()
     return t
-
-
-def true_rel12(k):
-    R, t = orf.true_rel(synthetic.orbit_pose(k), synthetic.orbit_pose(k + 1))
-    return pose12(R, t)
-
-
-def transforms():
-    """reference camera -> current camera: the identity, a small motion, most pixels out of the image, none left (everything
-    beyond range_max), the nearer part of the scene behind the camera (1.5 m backwards)"""
-    return [("identity", orf.IDENTITY12), ("small", pose12(synthetic.rot_y(0.01) @ synthetic.rot_x(-0.004), [0.01, -0.003, -0.005])),
-            ("mostly out", pose12(synthetic.rot_y(0.75), [0.0, 0.0, 0.0])), ("none left", pose12(np.eye(3), [0.0, 0.0, 10.0])),
-            ("behind", pose12(synthetic.rot_y(0.05), [0.0, 0.0, -1.5]))]
 
 
 def assert_pyramid(f, which, ref, what):
@@ -278,6 +258,16 @@ def test_the_refusals(product_lib):
                  lambda: f.odometry_track_device(d_rgb, d_depth.data_ptr() + 2)):
         with pytest.raises(binding.SsfError, match=r"\(-1\)"):
             call()
+    # a device colour pointer of a 4-byte format not aligned to 4 bytes (k_odo_pyramid_base loads the pixel as one uint32_t)
+    q = handle(product_lib, W, H)
+    q.set_input_format("rgba8", "f32")
+    d_rgba, d_ok = to_device(np.zeros(H * W * 4 + 4, np.uint8)), to_device(depth)
+    q.odometry_set_reference_device(d_rgba, d_ok)
+    for off in (1, 2, 3):
+        for call in (lambda: q.odometry_estimate_device(d_rgba.data_ptr() + off, d_ok), lambda: q.odometry_set_reference_device(d_rgba.data_ptr() + off, d_ok),
+                     lambda: q.odometry_track_device(d_rgba.data_ptr() + off, d_ok)):
+            with pytest.raises(binding.SsfError, match=r"\(-1\)"):
+                call()
     # the handle keeps working
     assert f.odometry_estimate(*util.frame(1, W, H))[1]["valid"] == 1
     # frames pending in the extract pipeline
