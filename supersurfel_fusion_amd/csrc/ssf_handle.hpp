@@ -246,7 +246,9 @@ struct MotionWs {
     unsigned char* din = nullptr;                                 // a host depth image, uploaded in the input format (4 P)
     float* m = nullptr; float* d32 = nullptr;                     // model depth (rendered or uploaded); the frame's depth in metres
     uint8_t* cls = nullptr; int32_t* parent = nullptr; int32_t* label = nullptr;
-    uint2* cnt = nullptr;                                         // (seed, unknown) pixels: of a tile's component at its local root, then of the component at its root
+    // (seed, unknown) pixels: of a tile's component at its local root, then of the component at its root.  A word that is no local
+    // root's is never written and must never be read: k_motion_roots reads cnt[p] only where label[p] >= 0, k_motion_decide only cnt[label[p]]
+    uint2* cnt = nullptr;
     uint8_t* mask = nullptr; uint8_t* last = nullptr;
     unsigned long long* stats = nullptr;                          // ssf_motion_stats' five counts
     size_t pixels = 0;

@@ -4,35 +4,26 @@
 //   * classify  k_motion_classify: one thread per pixel.  Reads the depth once, converting the input format where it loads it,
 //               and the model depth; writes the class and the f32 depth the later phases read.  Seed and unknown pixels are
 //               counted per workgroup (ballots), one 64-bit atomic each.
-//   * label     k_motion_label: one 256-thread workgroup per 32 x 32 tile, four pixels per thread.  Union-find in LDS over the
-//               tile's links (left and up neighbour of every pixel, atomicMin on the parent word).  A tile's row-major order is
-//               the image's restricted to it, so a local root is the smallest image index of its local component.  Per local
-//               component the seed / unknown pixels are counted in LDS; parent[p] = the local root's image index, cnt[p] =
-//               the counts at a local root and (0, 0) everywhere else -- a non-zero cnt[p] IS the mark of a local root.
-//   * merge     k_motion_merge: one thread per pixel pair across a tile border (vertical borders, then horizontal ones):
-//               union-find on the global parent array.  atomicMin is the only write, and it is only ever applied to a node that
-//               a walk ended at (a local root), with the other walk's end as its value; when the node had meanwhile been hung
-//               elsewhere the atomic returns that older parent and the thread goes on uniting IT with the other side, so no
-//               link is ever lost.  Every read of a parent is an agent-scope load (other workgroups, on any XCD, lower parents
-//               in the same launch); a stale read only names an older ancestor, and the decision is taken on the value the
-//               atomic returns.  Nothing is compressed here: re-pointing a node while other threads still unite can cut a set.
-//   * flatten   two launches, parent read-only in both.  k_motion_roots: one thread per pixel, only the local roots (non-zero
-//               cnt) work: label[p] = the root their walk ends at; a local root that is not the component's root adds its
-//               counts to the root's (integer atomics: one pair per (tile, local component), never one per pixel).
-//               k_motion_flatten: every other member pixel takes the label of its local root, parent[p], which the merge
-//               never rewrites for a pixel that is no local root; a pixel that is no member gets -1.
+//   * label, merge, flatten (k_motion_roots, k_motion_flatten): the connected components of the members under the link rule of
+//               step 3 with 4-connectivity, by the labeller of ssf_ccl.hpp: its scheme, its marks in parent and label between the
+//               phases and the argument why it ends and loses no link are stated there.  What is motion's own: the link test on
+//               the depths, and the counts.  k_motion_label counts the seed / unknown pixels per local component in LDS and
+//               writes them to cnt at the local root, and nowhere else; in k_motion_roots a local root that is not the
+//               component's root adds its counts to the root's (integer atomics: one pair per (tile, local component), never
+//               one per pixel).
 //   * decide    k_motion_decide: one thread per pixel: the component's counts at cnt[label[p]], the rule of step 5, the mask
 //               byte; components (label[p] == p), dynamic components and masked pixels are counted per workgroup.
-// The root of a set is its smallest index by construction (links go from the larger root to the smaller), so labels, counts and
-// the mask do not depend on scheduling.  The phases are separate launches: no workgroup ever waits for another.  The host reads
-// the five counts once, at the end.  Nothing here writes to the handle's stores, counters or scratch: the working set is
-// MotionWs (ssf_handle.hpp); the model depth of ssf_motion_mask is drawn by ssf_render_model itself.
-#include "ssf_slots.hpp"
+// The root of a set is its smallest index, so labels, counts and the mask do not depend on scheduling.  The phases are separate
+// launches: no workgroup ever waits for another.  The host reads the five counts once, at the end.  Nothing here writes to the
+// handle's stores, counters or scratch: the working set is MotionWs (ssf_handle.hpp); the model depth of ssf_motion_mask is drawn
+// by ssf_render_model itself.
+#include "ssf_ccl.hpp"
 #include "ssf_handle.hpp"
 
 namespace ssf {
 
 enum { MT_W = 32, MT_H = 32, MT_P = MT_W * MT_H };              // the label tile; 256 threads, MT_P / 256 pixels each
+static_assert(MT_W == CCL_TILE && MT_H == CCL_TILE, "the label tile is ssf_ccl.hpp's");
 enum { MST_SEED = 0, MST_UNKNOWN, MST_COMP, MST_DYN, MST_MASKED, MST_WORDS };
 
 struct MotionArgs {
@@ -72,42 +63,9 @@ __global__ __launch_bounds__(256) void k_motion_classify(MotionArgs a, const voi
     if (threadIdx.x == 1 && nu) atomicAdd(&stats[MST_UNKNOWN], (unsigned long long)nu);
 }
 
-// ---- union-find: in LDS (label) and in global memory (merge, flatten) -------------------------------------------------------
-// The invariant of every loop below: parent[i] <= i, and a parent only ever decreases (atomicMin is the only write).  A walk
-// i -> parent[i] therefore visits strictly decreasing indices >= 0 and ends at an i with parent[i] == i, whatever other threads do.
-__device__ __forceinline__ int lds_find(const volatile int* sp, int i) {
-    for (int g; (g = sp[i]) != i;) i = g;             // strictly decreasing: ends
-    return i;
-}
-__device__ __forceinline__ void lds_unite(int* sp, int a, int b) {
-    for (;;) {                                        // max(a, b) strictly decreases from one round to the next: ends
-        a = lds_find(sp, a); b = lds_find(sp, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(&sp[a], b);
-        if (old == a) return;                         // a was a root and now hangs under b < a
-        a = old;                                      // another thread hung a under old < a first: now unite old and b
-    }
-}
-__device__ __forceinline__ int g_load(const int32_t* q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int g_find(const int32_t* parent, int i) {
-    for (int g; (g = g_load(&parent[i])) != i;) i = g;       // strictly decreasing: ends
-    return i;
-}
-__device__ __forceinline__ void g_unite(int32_t* parent, int a, int b) {
-    for (;;) {                                        // max(a, b) strictly decreases from one round to the next: ends
-        a = g_find(parent, a); b = g_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(&parent[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-// ---- label: one workgroup per tile ---------------------------------------------------------------------------------------
+// ---- label: one workgroup per tile (ssf_ccl.hpp's tile body; the link test is motion_linked on the LDS depths) ---------------------
 __global__ __launch_bounds__(256) void k_motion_label(MotionArgs a, const float* __restrict__ d32, const uint8_t* __restrict__ cls,
-                                                      int32_t* __restrict__ parent, uint2* __restrict__ cnt) {
+                                                      int32_t* __restrict__ parent, int32_t* __restrict__ label, uint2* __restrict__ cnt) {
     __shared__ float sd[MT_P];
     __shared__ int sp[MT_P];
     __shared__ uint32_t scs[MT_P], scu[MT_P];
@@ -120,79 +78,47 @@ __global__ __launch_bounds__(256) void k_motion_label(MotionArgs a, const float*
         const size_t p = (size_t)y * a.W + x;
         sc[i] = in ? cls[p] : (uint8_t)SSF_MOTION_INVALID;
         sd[i] = in ? d32[p] : 0.0f;
-        sp[i] = i; scs[i] = 0u; scu[i] = 0u;
+        scs[i] = 0u; scu[i] = 0u;
     }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < MT_P / 256; k++) {
-        const int i = k * 256 + threadIdx.x;
-        if (!motion_member(sc[i])) continue;
-        if ((i % MT_W) > 0 && motion_member(sc[i - 1]) && motion_linked(a, sd[i], sd[i - 1])) lds_unite(sp, i, i - 1);
-        if (i >= MT_W && motion_member(sc[i - MT_W]) && motion_linked(a, sd[i], sd[i - MT_W])) lds_unite(sp, i, i - MT_W);
-    }
-    __syncthreads();
     int root[MT_P / 256];
+    ccl_tile_label(sp, false, [&](int i) { return motion_member(sc[i]); }, [&](int i, int j) { return motion_linked(a, sd[i], sd[j]); }, root);
 #pragma unroll
-    for (int k = 0; k < MT_P / 256; k++) {
-        const int i = k * 256 + threadIdx.x;
-        root[k] = -1;
-        if (!motion_member(sc[i])) continue;
-        root[k] = lds_find(sp, i);                     // (no writer any more)
-        atomicAdd(sc[i] == SSF_MOTION_SEED ? &scs[root[k]] : &scu[root[k]], 1u);
-    }
+    for (int k = 0; k < MT_P / 256; k++)
+        if (root[k] >= 0) atomicAdd(sc[k * 256 + threadIdx.x] == SSF_MOTION_SEED ? &scs[root[k]] : &scu[root[k]], 1u);
     __syncthreads();
+    ccl_tile_store(a.W, a.H, x0, y0, root, parent, label);
 #pragma unroll
-    for (int k = 0; k < MT_P / 256; k++) {
-        const int i = k * 256 + threadIdx.x, x = x0 + (i % MT_W), y = y0 + (i / MT_W);
-        if (x >= a.W || y >= a.H) continue;
-        const size_t p = (size_t)y * a.W + x;
-        const int r = root[k];
-        parent[p] = r < 0 ? (int32_t)p : (int32_t)((size_t)(y0 + r / MT_W) * a.W + (x0 + r % MT_W));
-        cnt[p] = r == i ? make_uint2(scs[i], scu[i]) : make_uint2(0u, 0u);
+    for (int k = 0; k < MT_P / 256; k++) {                 // the counts, at the local roots only (members: inside the image)
+        const int i = k * 256 + threadIdx.x;
+        if (root[k] == i) cnt[ccl_image_index(a.W, x0, y0, i)] = make_uint2(scs[i], scu[i]);
     }
 }
 
-// ---- merge: one thread per pixel pair across a tile border -------------------------------------------------------------
-// pairs [0, nv): (x = bx * MT_W, y) with its left neighbour, bx = 1 .. ntx - 1; pairs [nv, nv + nh): (x, y = by * MT_H) with its
-// upper neighbour, by = 1 .. nty - 1
-__global__ __launch_bounds__(256) void k_motion_merge(MotionArgs a, const float* __restrict__ d32, const uint8_t* __restrict__ cls,
-                                                      int32_t* __restrict__ parent) {
-    const long long nv = (long long)(a.ntx - 1) * a.H, nh = (long long)(a.nty - 1) * a.W;
-    long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= nv + nh) return;
-    size_t p, q;
-    if (t < nv) { const int x = (int)(t / a.H + 1) * MT_W, y = (int)(t % a.H); p = (size_t)y * a.W + x; q = p - 1; }
-    else { t -= nv; const int y = (int)(t / a.W + 1) * MT_H, x = (int)(t % a.W); p = (size_t)y * a.W + x; q = p - a.W; }
-    if (!motion_member(cls[p]) || !motion_member(cls[q]) || !motion_linked(a, d32[p], d32[q])) return;
-    g_unite(parent, (int)p, (int)q);
+// ---- merge: one thread per pixel on the high side of a tile border, united with its neighbour across it ---------------------------
+__global__ __launch_bounds__(256) void k_motion_merge(MotionArgs a, const float* __restrict__ d32, int32_t* parent) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= ccl_border_threads(a.W, a.H, a.ntx, a.nty)) return;
+    ccl_merge(parent, a.W, a.H, a.ntx, t, false, [&](int p, int q) { return motion_linked(a, d32[p], d32[q]); });
 }
 
 // ---- flatten: the local roots walk to their root, then every other member takes its local root's label ----------------------
 __global__ __launch_bounds__(256) void k_motion_roots(MotionArgs a, const int32_t* __restrict__ parent, int32_t* __restrict__ label,
                                                       uint2* __restrict__ cnt) {
     const size_t P = (size_t)a.W * a.H, p = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;
-    const uint2 c = cnt[p];
-    if ((c.x | c.y) == 0u) return;                     // no local root (a local component holds at least its root: never 0, 0)
-    int i = (int)p;
-    for (int g; (g = parent[i]) != i;) i = g;          // parent[i] <= i, read-only in this launch: strictly decreasing, ends
+    if (p >= P || !ccl_is_local_root(label, p)) return;
+    const int i = ccl_walk(parent, (int)p);
     label[p] = i;
-    // (the root's own words only receive additions, and the only thread that reads them here is the root's, which adds nothing)
+    // a local root that is not the component's root adds its counts to the root's (the root's own words only receive additions,
+    // and the only thread that reads them here is the root's, which adds nothing)
     if (i != (int)p) {
+        const uint2 c = cnt[p];
         if (c.x) atomicAdd(&cnt[i].x, c.x);
         if (c.y) atomicAdd(&cnt[i].y, c.y);
     }
 }
-// (k_motion_roots has added to the roots' words of cnt, but a root is a local root too -- non-zero before and after -- so
-// "non-zero" still tells the local roots from the other pixels)
-__global__ __launch_bounds__(256) void k_motion_flatten(MotionArgs a, const uint8_t* __restrict__ cls, const int32_t* __restrict__ parent,
-                                                        const uint2* __restrict__ cnt, int32_t* __restrict__ label) {
+__global__ __launch_bounds__(256) void k_motion_flatten(MotionArgs a, const int32_t* __restrict__ parent, int32_t* __restrict__ label) {
     const size_t P = (size_t)a.W * a.H, p = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;
-    if (!motion_member(cls[p])) { label[p] = -1; return; }
-    const uint2 c = cnt[p];
-    if ((c.x | c.y) != 0u) return;                     // a local root: k_motion_roots wrote its label
-    label[p] = label[parent[p]];                       // parent[p] = its local root (written by k_motion_label, never by the merge)
+    if (p < P) ccl_flatten(parent, label, p, label[p]);
 }
 
 // ---- decide: one thread per pixel ----------------------------------------------------------------------------------------
@@ -226,20 +152,20 @@ static void launch_motion_classify(hipStream_t st, const MotionArgs& a, const vo
     else
         hipLaunchKernelGGL(k_motion_classify<SSF_DEPTH_F32_METRES>, dim3(nb), dim3(256), 0, st, a, depth, scale, model, d32, cls, stats);
 }
-static void launch_motion_label(hipStream_t st, const MotionArgs& a, const float* d32, const uint8_t* cls, int32_t* parent, uint2* cnt) {
+static void launch_motion_label(hipStream_t st, const MotionArgs& a, const float* d32, const uint8_t* cls, int32_t* parent, int32_t* label, uint2* cnt) {
     ScopedKernel sk("motion_label", st);
-    hipLaunchKernelGGL(k_motion_label, dim3(a.ntx * a.nty), dim3(256), 0, st, a, d32, cls, parent, cnt);
+    hipLaunchKernelGGL(k_motion_label, dim3(a.ntx * a.nty), dim3(256), 0, st, a, d32, cls, parent, label, cnt);
 }
-static void launch_motion_merge(hipStream_t st, const MotionArgs& a, const float* d32, const uint8_t* cls, int32_t* parent) {
+static void launch_motion_merge(hipStream_t st, const MotionArgs& a, const float* d32, int32_t* parent) {
     ScopedKernel sk("motion_merge", st);
-    const long long n = (long long)(a.ntx - 1) * a.H + (long long)(a.nty - 1) * a.W;
-    if (n > 0) hipLaunchKernelGGL(k_motion_merge, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, d32, cls, parent);
+    const long long n = ccl_border_threads(a.W, a.H, a.ntx, a.nty);
+    if (n > 0) hipLaunchKernelGGL(k_motion_merge, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, d32, parent);
 }
-static void launch_motion_flatten(hipStream_t st, const MotionArgs& a, const uint8_t* cls, const int32_t* parent, int32_t* label, uint2* cnt) {
+static void launch_motion_flatten(hipStream_t st, const MotionArgs& a, const int32_t* parent, int32_t* label, uint2* cnt) {
     ScopedKernel sk("motion_flatten", st);
     const unsigned nb = (unsigned)(((size_t)a.W * a.H + 255) / 256);
     hipLaunchKernelGGL(k_motion_roots, dim3(nb), dim3(256), 0, st, a, parent, label, cnt);
-    hipLaunchKernelGGL(k_motion_flatten, dim3(nb), dim3(256), 0, st, a, cls, parent, cnt, label);
+    hipLaunchKernelGGL(k_motion_flatten, dim3(nb), dim3(256), 0, st, a, parent, label);
 }
 static void launch_motion_decide(hipStream_t st, const MotionArgs& a, const int32_t* label, const uint2* cnt, uint8_t* mask,
                                  unsigned long long* stats) {
@@ -296,9 +222,9 @@ static int motion_run(ssf_handle* h, const MotionArgs& a, const void* depth, int
     if (!on_device) { HCK(hipMemcpyAsync(w.din, depth, motion_depth_bpp(h) * P, hipMemcpyHostToDevice, st)); d_depth = w.din; }
     HCK(hipMemsetAsync(w.stats, 0, MST_WORDS * sizeof(unsigned long long), st));
     launch_motion_classify(st, a, d_depth, h->in_depth, h->in_scale, d_model, w.d32, w.cls, w.stats);
-    launch_motion_label(st, a, w.d32, w.cls, w.parent, w.cnt);
-    launch_motion_merge(st, a, w.d32, w.cls, w.parent);
-    launch_motion_flatten(st, a, w.cls, w.parent, w.label, w.cnt);
+    launch_motion_label(st, a, w.d32, w.cls, w.parent, w.label, w.cnt);
+    launch_motion_merge(st, a, w.d32, w.parent);
+    launch_motion_flatten(st, a, w.parent, w.label, w.cnt);
     launch_motion_decide(st, a, w.label, w.cnt, w.mask, w.stats);
     HCK(hipGetLastError());
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;

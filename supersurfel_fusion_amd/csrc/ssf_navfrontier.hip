@@ -2,21 +2,12 @@
 // summed per region, with the gain of a look from each region's representative.
 //
 // What is computed is pinned in include/ssf_navfrontier.h (the restatement: tests/navfrontier_ref.py).  ssf_navfrontier_regions runs
-//   * label     k_navfrontier_label: one 256-thread workgroup per 32 x 32 tile, four cells per thread.  The members (step 1), then a
-//               union-find in LDS over the tile's links (left and up neighbour; with connectivity 8 the two upper diagonals as well;
-//               atomicMin on the parent word).  parent[p] = the local root's grid index (-1: no member); label[p] = p at a local
-//               root, -2 at any other member, -1 elsewhere.  A tile's row-major order is the grid's restricted to it, so a local
-//               root is the smallest grid index of its local component;
-//   * merge     k_navfrontier_merge: one thread per cell on the high side of a tile border, united with the one cell (connectivity
-//               4) or the three cells (8: the diagonal pairs along the edge, which at a tile corner are the corner's diagonal pairs)
-//               that face it across the border.  The rules are ssf_motion.hip's: atomicMin is the only write and is only ever
-//               applied to a node that a walk ended at, with the other walk's end as its value; when that node had meanwhile been
-//               hung elsewhere the atomic returns the older parent and the thread goes on uniting IT.  Parents are read with
-//               agent-scope loads; nothing is compressed while others unite;
-//   * flatten   k_navfrontier_roots: the local roots walk to their root (label[p] = the root, the region's label) and the roots of
-//               every 256 cells are counted; the slot code's scan turns the counts into offsets; k_navfrontier_flatten: every
-//               other member takes its local root's label, and a root, whose parent word nobody needs any more, keeps the running
-//               index of its region there as -2 - index (ascending grid index = ascending label);
+//   * label, merge, flatten (k_navfrontier_roots, k_navfrontier_flatten): the members (step 1) and their connected components, with
+//               connectivity 4 or 8 and membership as the only link rule, by the labeller of ssf_ccl.hpp: its scheme, its marks in
+//               parent and label between the phases and the argument why it ends and loses no link are stated there.  What is the
+//               frontier's own: members and merged pairs are counted; k_navfrontier_roots counts the roots of every 256 cells, the
+//               slot code's scan turns the counts into offsets, and in k_navfrontier_flatten a root, whose parent word nobody needs
+//               any more, keeps the running index of its region there as -2 - index (ascending grid index = ascending label);
 //   * sums      the host reads the number of regions and grows the accumulators (NavFrontierAcc, one per region FOUND).
 //               k_navfrontier_sums: one workgroup per tile again.  A member adds itself in LDS to the slot of the cell its parent
 //               word names when that cell lies in the same tile (its local root, or for a local root the root it was hung under),
@@ -33,15 +24,16 @@
 // maxima do not depend on arrival order, and the table is in label order: nothing here depends on scheduling.  The phases are
 // separate launches: no workgroup ever waits for another.
 //
-// The union-find helpers restate ssf_motion.hip's (that file is left as it is: its kernels' code stays what it was).
 // This file is NOT one of the product library's objects.  It is linked, with all of them, the carve and the plan, into
 // libssf_hip_explore.so.
 #include "ssf_navgrid.hpp"
+#include "ssf_ccl.hpp"
 #include "../../include/ssf_navfrontier.h"
 #include <algorithm>
 
 namespace ssf {
 
+static_assert(NAV_TILE == CCL_TILE, "the label tile is ssf_ccl.hpp's");
 enum : uint32_t { NF_INF = 0xFFFFFFFFu };
 enum { NF_GAIN_WORDS = (257 * 257 + 31) / 32 };                   // the window's bitmap at R = 128
 // the sums: members, pairs the merge looked at, regions found / too small / unreached / kept, the largest region
@@ -57,39 +49,6 @@ struct NavFrontierAcc {
 };
 static_assert(sizeof(NavFrontierAcc) == 56, "NavFrontierAcc");
 static_assert(sizeof(ssf_navfrontier_region) == 56, "ssf_navfrontier_region");
-
-// ---- union-find: in LDS (label) and in global memory (merge), as in ssf_motion.hip ----------------------------------------------
-// The invariant of every loop below: parent[i] <= i, and a parent only ever decreases (atomicMin is the only write).  A walk
-// i -> parent[i] therefore visits strictly decreasing indices >= 0 and ends at an i with parent[i] == i, whatever other threads do.
-__device__ __forceinline__ int nf_lds_find(const volatile int* sp, int i) {
-    for (int g; (g = sp[i]) != i;) i = g;
-    return i;
-}
-__device__ __forceinline__ void nf_lds_unite(int* sp, int a, int b) {
-    for (;;) {                                        // max(a, b) strictly decreases from one round to the next: ends
-        a = nf_lds_find(sp, a); b = nf_lds_find(sp, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(&sp[a], b);
-        if (old == a) return;                         // a was a root and now hangs under b < a
-        a = old;                                      // another thread hung a under old < a first: now unite old and b
-    }
-}
-__device__ __forceinline__ int nf_load(const int32_t* q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int nf_find(const int32_t* parent, int i) {
-    for (int g; (g = nf_load(&parent[i])) != i;) i = g;
-    return i;
-}
-__device__ __forceinline__ void nf_unite(int32_t* parent, int a, int b) {
-    for (;;) {
-        a = nf_find(parent, a); b = nf_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(&parent[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
 
 // step 1 for a cell inside the grid
 __device__ __forceinline__ bool nf_member(const NavFrontierGrid& G, const NavFrontierRule& r, const int8_t* __restrict__ state,
@@ -113,63 +72,19 @@ __global__ __launch_bounds__(256) void k_navfrontier_label(NavFrontierGrid G, Na
     for (int k = 0; k < NAV_CELLS / 256; k++) {
         const int i = k * 256 + threadIdx.x, x = x0 + (i % NAV_TILE), y = y0 + (i / NAV_TILE);
         const bool m = x < G.W && y < G.H && nf_member(G, r, state, dist2, x, y);
-        sm[i] = m; sp[i] = i; members += m;
+        sm[i] = m; members += m;
     }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NAV_CELLS / 256; k++) {
-        const int i = k * 256 + threadIdx.x, lx = i % NAV_TILE;
-        if (!sm[i]) continue;
-        if (lx > 0 && sm[i - 1]) nf_lds_unite(sp, i, i - 1);
-        if (i >= NAV_TILE) {
-            if (sm[i - NAV_TILE]) nf_lds_unite(sp, i, i - NAV_TILE);
-            if (r.conn8 && lx > 0 && sm[i - NAV_TILE - 1]) nf_lds_unite(sp, i, i - NAV_TILE - 1);
-            if (r.conn8 && lx + 1 < NAV_TILE && sm[i - NAV_TILE + 1]) nf_lds_unite(sp, i, i - NAV_TILE + 1);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NAV_CELLS / 256; k++) {
-        const int i = k * 256 + threadIdx.x, x = x0 + (i % NAV_TILE), y = y0 + (i / NAV_TILE);
-        if (x >= G.W || y >= G.H) continue;
-        const size_t p = (size_t)y * G.W + x;
-        const int lr = sm[i] ? nf_lds_find(sp, i) : -1;                // (no writer any more)
-        parent[p] = lr < 0 ? -1 : (int32_t)((size_t)(y0 + lr / NAV_TILE) * G.W + (x0 + lr % NAV_TILE));
-        label[p] = lr < 0 ? -1 : (lr == i ? (int32_t)p : -2);
-    }
+    int root[NAV_CELLS / 256];
+    ccl_tile_label(sp, r.conn8 != 0, [&](int i) { return sm[i] != 0; }, [](int, int) { return true; }, root);
+    ccl_tile_store(G.W, G.H, x0, y0, root, parent, label);
     block_sums({members}, stats, NF_MEMBERS);
 }
 
-// ---- merge: one thread per cell on the high side of a tile border --------------------------------------------------------------------
-// cells [0, nv): (x = bx * 32, y), bx = 1 .. ntx - 1, with (x - 1, y) and, connectivity 8, (x - 1, y - 1) and (x - 1, y + 1);
-// cells [nv, nv + nh): (x, y = by * 32), by = 1 .. nty - 1, with (x, y - 1) and, connectivity 8, (x - 1, y - 1) and (x + 1, y - 1).
-// A diagonal pair across a tile corner is met from both lists; uniting twice is harmless.  A member's parent word is >= 0 for good,
-// any other cell's is -1 for good, so the membership test needs no care about the unions going on.
-__device__ __forceinline__ int nf_merge_pair(int32_t* parent, int p, int q) {
-    if (nf_load(&parent[q]) < 0) return 0;
-    nf_unite(parent, p, q);
-    return 1;
-}
+// ---- merge: one thread per cell on the high side of a tile border; the pairs whose two cells are members are counted -------------------
 __global__ __launch_bounds__(256) void k_navfrontier_merge(NavFrontierGrid G, int conn8, int32_t* parent, unsigned long long* __restrict__ stats) {
-    const long long nv = (long long)(G.ntx - 1) * G.H, nh = (long long)(G.nty - 1) * G.W;
-    long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     unsigned long long pairs = 0;
-    if (t < nv) {
-        const int x = (int)(t / G.H + 1) * NAV_TILE, y = (int)(t % G.H), p = y * G.W + x;
-        if (nf_load(&parent[p]) >= 0) {
-            pairs += nf_merge_pair(parent, p, p - 1);
-            if (conn8 && y > 0) pairs += nf_merge_pair(parent, p, p - G.W - 1);
-            if (conn8 && y + 1 < G.H) pairs += nf_merge_pair(parent, p, p + G.W - 1);
-        }
-    } else if (t < nv + nh) {
-        t -= nv;
-        const int y = (int)(t / G.W + 1) * NAV_TILE, x = (int)(t % G.W), p = y * G.W + x;
-        if (nf_load(&parent[p]) >= 0) {
-            pairs += nf_merge_pair(parent, p, p - G.W);
-            if (conn8 && x > 0) pairs += nf_merge_pair(parent, p, p - G.W - 1);
-            if (conn8 && x + 1 < G.W) pairs += nf_merge_pair(parent, p, p - G.W + 1);
-        }
-    }
+    if (t < ccl_border_threads(G.W, G.H, G.ntx, G.nty)) pairs = ccl_merge(parent, G.W, G.H, G.ntx, t, conn8 != 0, [](int, int) { return true; });
     pairs = wave_sum(pairs);
     if (lane() == 0 && pairs) atomicAdd(&stats[NF_PAIRS], pairs);
 }
@@ -180,17 +95,15 @@ __global__ __launch_bounds__(256) void k_navfrontier_roots(size_t P, const int32
     __shared__ int part[4];
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     bool root = false;
-    if (p < P && label[p] >= 0) {                                     // a local root
-        int i = (int)p;
-        for (int g; (g = parent[i]) != i;) i = g;                     // parent[i] <= i, read-only in this launch: strictly decreasing, ends
+    if (p < P && ccl_is_local_root(label, p)) {
+        const int i = ccl_walk(parent, (int)p);
         label[p] = i;
         root = i == (int)p;
     }
     const int n = block_count256(root, part);
     if (threadIdx.x == 0) blocks[blockIdx.x] = (uint32_t)n;
 }
-// label[parent[p]] is a local root's word: written by k_navfrontier_roots, by nobody here.  A root's parent word is read by nobody
-// here (a cell that is no local root reads its own), so the root may keep its region's index there
+// A root's parent word is read by nobody here (a cell that is no local root reads its own), so the root may keep its region's index there
 __global__ __launch_bounds__(256) void k_navfrontier_flatten(size_t P, int32_t* __restrict__ parent, int32_t* __restrict__ label,
                                                              const uint32_t* __restrict__ blocks) {
     __shared__ int part[4];
@@ -198,7 +111,7 @@ __global__ __launch_bounds__(256) void k_navfrontier_flatten(size_t P, int32_t* 
     bool root = false;
     if (p < P) {
         const int32_t l = label[p];
-        if (l == -2) label[p] = label[parent[p]];
+        ccl_flatten(parent, label, p, l);
         root = l == (int32_t)p;
     }
     const int rank = block_rank256(root, part);
@@ -363,7 +276,7 @@ static void launch_navfrontier_label(hipStream_t st, const NavFrontierGrid& G, c
 }
 static void launch_navfrontier_merge(hipStream_t st, const NavFrontierGrid& G, int conn8, int32_t* parent, unsigned long long* stats) {
     ScopedKernel sk("navfrontier_merge", st);
-    const long long n = (long long)(G.ntx - 1) * G.H + (long long)(G.nty - 1) * G.W;
+    const long long n = ccl_border_threads(G.W, G.H, G.ntx, G.nty);
     if (n > 0) hipLaunchKernelGGL(k_navfrontier_merge, dim3(nf_blocks((size_t)n)), dim3(256), 0, st, G, conn8, parent, stats);
 }
 static void launch_navfrontier_flatten(hipStream_t st, size_t P, int32_t* parent, int32_t* label, uint32_t* blocks, unsigned long long* stats) {

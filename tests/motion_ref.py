@@ -296,6 +296,22 @@ def cases(W, H, seed=0):
     return out
 
 
+# the tile grids cases()' shapes do not have: one row of tiles (only vertical borders), one column (only horizontal ones), a single
+# tile (no merge launch), and a last tile one cell wide
+TILE_SHAPES = [(70, 24), (24, 70), (24, 24), (33, 33)]
+
+
+def tile_cases(W, H, seed=0):
+    """(name, depth, model, params) of the patterns that stress the labelling, every component counted (min_seeds = 1)"""
+    rng = np.random.default_rng(seed)
+    sa, sb = spirals(W, H)
+    mem = rng.random((H, W)) < 0.62
+    patterns = [("serpentine", serpentine(W, H), None), ("comb", comb(W, H), None), ("cross", cross(W, H), None),
+                ("checkerboard", checkerboard(W, H), None), ("full", np.ones((H, W), bool), None), ("spirals", sa | sb, sa),
+                ("random", mem, rng.random((H, W)) < 0.3)]
+    return [(name,) + from_pattern(member, seed_px) + (dict(min_seeds=1),) for name, member, seed_px in patterns]
+
+
 # ---- the end-to-end scene: the synthetic room with a box pasted in front of it -----------------------------------------
 def box_rect(W, H):
     """(y0, y1, x0, x1) of the pasted box"""

@@ -173,6 +173,18 @@ def test_the_union_find_form_equals_the_flood_fill_on_every_adversarial_image(W,
         assert ((a["label"] >= 0) == member).all() and (a["label"][member] <= np.arange(W * H).reshape(H, W)[member]).all()
 
 
+@pytest.mark.parametrize("W,H", mr.TILE_SHAPES)
+def test_the_two_forms_agree_on_the_tile_grids_the_other_shapes_miss(W, H):
+    """one row of tiles, one column, a single tile, a last tile one cell wide: the references of the GPU test of the same shapes"""
+    comps = {}
+    for case in mr.tile_cases(W, H):
+        a = run(case, W, H)
+        mr.assert_same(a, run(case, W, H, "bfs"), case[0])
+        comps[case[0]] = a["stats"]["n_components"]
+    comps.pop("random")                                            # (no known answer: the two forms agreeing is its check)
+    assert comps == dict(serpentine=1, comb=1, cross=1, full=1, spirals=2, checkerboard=(W * H + 1) // 2), comps
+
+
 @pytest.mark.parametrize("W,H", SHAPES)
 def test_known_answers_of_the_adversarial_images(W, H):
     st = {c[0]: run(c, W, H)["stats"] for c in cases(W, H)}

@@ -76,6 +76,14 @@ def test_hand_built_images_against_the_restatement(W, H, product_lib):
     mr.assert_same(only, reference(W, H, name), "label alone")
 
 
+@pytest.mark.parametrize("W,H", mr.TILE_SHAPES)
+def test_the_tile_grids_the_other_shapes_miss(W, H, product_lib):
+    """one row of tiles, one column, a single tile (no merge launch), a last tile one cell wide"""
+    f = handle(product_lib, W, H)
+    for name, d, m, kw in mr.tile_cases(W, H):
+        mr.assert_same(f.motion_segment(d, m, params=kw), mr.segment(d, m, **dict(mr.default_params(W, H), **kw)), name)
+
+
 @pytest.mark.parametrize("W,H", SHAPES)
 def test_uint16_depth_through_the_input_format(W, H, product_lib):
     f = handle(product_lib, W, H)
