@@ -24,6 +24,21 @@ long long ssf_resident_icp_frames(ssf_handle* h);
  * frame before (pipelined frames, ssf_tuner_state [0] = 1) */
 long long ssf_resident_icp_ahead_frames(ssf_handle* h);
 
+/* The tile-sorted copy of the visible rows (ssf_debug_set_bin_min_rows moves its threshold).
+ * ssf_tile_copy_frames: frames whose tracking made the copy since the handle was created; -1 for NULL. */
+long long ssf_tile_copy_frames(ssf_handle* h);
+/* Test read-out of the sort itself: sorts the handle's visible rows (n_visible of ssf_get_counts) by the 32 x 32 pixel tile they
+ * project to under T12 (R row-major, then t: ps = R pos + t), in the copy's own buffers (allocated on first use, as a frame's copy
+ * does), waits, and copies out
+ *   records   12 * n_visible floats: one 48-byte record per row -- (position, confidence) (Lab, the row's index in the visible
+ *             array as integer bits) (normal = orientation row 2, 0.0f); bin after bin, the order inside a bin is arbitrary
+ *   totals    nbins = ceil(W / 32) * ceil(H / 32) + 1 words: rows per bin (the last bin: rows that project nowhere)
+ *   lab_src   nullable, 3 * n_visible floats: the stored Lab of the visible rows in array order
+ * No frame streams what it leaves.  SSF_ERR_INVALID_ARG for a NULL h, T12, records or totals; SSF_ERR_STATE with frames pending,
+ * on a sharded handle, and for a frame of more than 4096 bins (which never makes the copy).  With no visible rows nothing is
+ * launched and totals are zeros. */
+int ssf_debug_tile_copy(ssf_handle* h, const float* T12, float* records, uint32_t* totals, float* lab_src);
+
 #ifdef __cplusplus
 }
 #endif

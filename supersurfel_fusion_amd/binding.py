@@ -197,8 +197,10 @@ RAYCAST_SYMBOLS = ["ssf_raycast_default_params", "ssf_raycast"]
 RAYCAST_OUTPUTS = (("t", np.float32, ()), ("index", np.int32, ()), ("point", np.float32, (3,)), ("normal", np.float32, (3,)),
                    ("color", np.float32, (3,)))
 RAYCAST_OUTPUT_NAMES = tuple(nm for nm, _, _ in RAYCAST_OUTPUTS)
-# the track stage's test hook and counter of the resident ICP launch (include/ssf_track.h): HIP product only, not part of ssf.h
-TRACK_SYMBOLS = ["ssf_debug_set_resident_icp_max_rows", "ssf_resident_icp_frames", "ssf_resident_icp_ahead_frames"]
+# the track stage's test hooks and counters -- the resident ICP launch, the tile-sorted copy (include/ssf_track.h): HIP product only,
+# not part of ssf.h
+TRACK_SYMBOLS = ["ssf_debug_set_resident_icp_max_rows", "ssf_resident_icp_frames", "ssf_resident_icp_ahead_frames",
+                 "ssf_tile_copy_frames", "ssf_debug_tile_copy"]
 # the geometric moving-object detector (include/ssf_motion.h): exported by the HIP product only, not part of ssf.h (ABI_SYMBOLS)
 MOTION_SYMBOLS = ["ssf_motion_default_params", "ssf_motion_segment", "ssf_motion_mask", "ssf_process_frame_motion", "ssf_get_motion_mask"]
 # dense RGB-D odometry, the pose prior of the library's own (include/ssf_odometry.h): HIP product only, not part of ssf.h
@@ -795,6 +797,9 @@ class Library:
             L.ssf_resident_icp_frames.restype = C.c_longlong
             L.ssf_resident_icp_ahead_frames.argtypes = [vp]
             L.ssf_resident_icp_ahead_frames.restype = C.c_longlong
+            L.ssf_tile_copy_frames.argtypes = [vp]
+            L.ssf_tile_copy_frames.restype = C.c_longlong
+            L.ssf_debug_tile_copy.argtypes = [vp, vp, vp, vp, vp]
         self.has_motion = all(hasattr(L, nm) for nm in MOTION_SYMBOLS)
         if self.has_motion:
             mp, ms = C.POINTER(SsfMotionParams), C.POINTER(SsfMotionStats)
@@ -3546,6 +3551,26 @@ class Fusion:
         if not self.L.has_track:
             raise SsfError("this library has no resident ICP launch (include/ssf_track.h: HIP product only)")
         return int(self.L.lib.ssf_resident_icp_ahead_frames(self.h))
+
+    def tile_copy_frames(self):
+        """frames whose tracking made the tile-sorted copy of the visible rows since the handle was created"""
+        if not self.L.has_track:
+            raise SsfError("this library has no tile-sorted copy (include/ssf_track.h: HIP product only)")
+        return int(self.L.lib.ssf_tile_copy_frames(self.h))
+
+    def debug_tile_copy(self, T12):
+        """ssf_debug_tile_copy: the visible rows sorted by the tile they project to under T12 (12 floats: R row-major, then t).
+        Returns dict(records: n_visible x 12 float32 (position, confidence | Lab, row index as integer bits | normal, 0), totals:
+        uint32 rows per bin, ceil(W / 32) * ceil(H / 32) + 1 of them, lab_src: n_visible x 3 float32, the stored Lab in array order)"""
+        if not self.L.has_track:
+            raise SsfError("this library has no tile-sorted copy (include/ssf_track.h: HIP product only)")
+        T12 = np.ascontiguousarray(T12, np.float32).reshape(-1)
+        assert T12.size == 12, T12.size
+        n = self.counts()["n_visible"]
+        records, lab_src = np.zeros((max(n, 1), 12), np.float32)[:n], np.zeros((max(n, 1), 3), np.float32)[:n]
+        totals = np.zeros(((self.W + 31) // 32) * ((self.H + 31) // 32) + 1, np.uint32)
+        self._ck(self.L.lib.ssf_debug_tile_copy(self.h, _ptr(T12), _ptr(records), _ptr(totals), _ptr(lab_src)), "ssf_debug_tile_copy")
+        return dict(records=records, totals=totals, lab_src=lab_src)
 
     def set_shard(self, id_offset, global_n_model, global_n_visible):
         self._ck(self.L.lib.ssf_stage_set_shard(self.h, id_offset, global_n_model, global_n_visible), "ssf_stage_set_shard")

@@ -137,6 +137,7 @@ struct TileCopy {
     SurfelSoA rows{};                             // rows.pos: one 48-byte record per row (k_bin_scatter); the other streams stay null
     int32_t* d_idx = nullptr; uint32_t* d_count = nullptr; uint32_t* d_cursor = nullptr;       // launch_match's flag "sorted records" | bin_buffer_words each
     bool valid = false; int min_rows = SSF_BIN_MIN_ROWS_DEFAULT;      // min_rows: visible rows from which a frame's tracking makes the copy (< 0: never)
+    long long frames = 0;                         // frames whose tracking made the copy (ssf_tile_copy_frames)
     int make_if_large(ssf_handle* h);             // (ssf_host.hip) the frame's copy, if it wants one: on first use the buffers, then launch_bin_rows
     void drop() { valid = false; }
 };

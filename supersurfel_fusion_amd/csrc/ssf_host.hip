@@ -1111,16 +1111,21 @@ static void icp_chain_reset(ssf_handle* h) {
 // what the steps share: entry time, end of the ICP loop, the frame's number inside a sequence (debug marks) | the stage split is
 // timed (costs an event synchronise: opt-in) | no record has come back yet | the launch made ahead
 struct TrackFrame { double t_a = 0.0, t_b = 0.0; int kf = -1; bool timing = false, first_it = true; IcpWaiter w; };
+// The tile-sorted copy's buffers, on first use (48 B per row of capacity; d_idx: only the flag "this is the sorted copy" of
+// launch_match).  Shared by the frame's copy and the read-out ssf_debug_tile_copy.
+static int tile_copy_buffers(ssf_handle* h, TileCopy& b) {
+    if (b.d_idx) return SSF_OK;
+    const size_t N = (size_t)h->cfg.nb_supersurfels_max, bw = bin_buffer_words(h->cam, N);
+    const bool ok = bw && dalloc(h, &b.rows.pos, 12 * N) && dalloc(h, &b.d_idx, 1) && dalloc(h, &b.d_count, bw) && dalloc(h, &b.d_cursor, bw);
+    if (!ok) { h->err = "allocation of the tile-sorted copy failed"; return SSF_ERR_DEVICE; }
+    return SSF_OK;
+}
 // The tile-copy step of a frame (after icp_begin, which dropped the last copy).  A large visible set: its ICP / association fields
 // once more, sorted by the image tile they project to under the frame's initial transform (ssf_track_fuse.hip, k_bin_*): the
 // iterations and the association stream that copy.  The decision: a frame that iterates, on a single shard, min_rows visible rows or more.
 int TileCopy::make_if_large(ssf_handle* h) {
     if (!(h->icp.active && min_rows >= 0 && h->n_visible >= min_rows && h->n_visible > 0 && single_shard_alone(h) && bin_buffer_words(h->cam, 1) != 0)) return SSF_OK;
-    if (!d_idx) {                              // first use: the copy's buffers (48 B per row of capacity; d_idx: only the flag "this is the sorted copy" of launch_match)
-        const size_t N = (size_t)h->cfg.nb_supersurfels_max, bw = bin_buffer_words(h->cam, N);
-        const bool ok = bw && dalloc(h, &rows.pos, 12 * N) && dalloc(h, &d_idx, 1) && dalloc(h, &d_count, bw) && dalloc(h, &d_cursor, bw);
-        if (!ok) { h->err = "allocation of the tile-sorted copy failed"; return SSF_ERR_DEVICE; }
-    }
+    { const int rc = tile_copy_buffers(h, *this); if (rc) return rc; }
     Rt T0; T0.R = h->icp.R_init; T0.t = h->icp.t_init;
     // In front of the loop, on the track stream.  (Measured and removed, round 6: the sort on a stream of its own beside the
     // frame's first two iterations, the launch made ahead for iteration 3 the first to wait for it -- 2 003-2 026 frames/s at
@@ -1128,7 +1133,7 @@ int TileCopy::make_if_large(ssf_handle* h) {
     // places while they wait for the host's word, and the sort's three launches queue behind them.  profiles/config3_sorted_rows_r06.txt)
     launch_bin_rows(h->stream, h->cam, h->model[h->mcur], h->n_visible, T0, d_count, d_cursor, rows);
     HCK(hipGetLastError());
-    valid = true;
+    valid = true; frames++;
     return SSF_OK;
 }
 // chained launches (single GPU, kernels not individually timed): while iteration i runs, iteration i + 1 is
@@ -1918,6 +1923,31 @@ int ssf_debug_set_bin_min_rows(ssf_handle* h, int n) {
     h->bins.min_rows = bin_buffer_words(h->cam, 1) == 0 ? -1 : n;
     return SSF_OK;
 }
+// test read-out: the sort itself.  launch_bin_rows over the visible array under the transform T12 (R row-major, then t) into the
+// copy's own buffers, then to the host: the 48-byte records, the bin totals (the first nbins words of `cursor`) and the stored Lab
+// stream of the visible rows in array order (no other read-out returns its bits).  The copy stays invalid: no frame streams it.
+int ssf_debug_tile_copy(ssf_handle* h, const float* T12, float* records, uint32_t* totals, float* lab_src) {
+    if (!h || !T12 || !records || !totals) return SSF_ERR_INVALID_ARG;
+    if (!h->pending.empty()) { h->err = "frames are pending in the extract pipeline"; return SSF_ERR_STATE; }
+    if (!single_shard_alone(h)) { h->err = "the tile-sorted copy is made on a single shard only"; return SSF_ERR_STATE; }
+    const size_t nbins = bin_buffer_words(h->cam, 0);          // (no rows: the bin totals alone)
+    if (bin_buffer_words(h->cam, 1) == 0) { h->err = "the frame is too fine for the tile-sorted copy"; return SSF_ERR_STATE; }
+    const size_t n = (size_t)h->n_visible;
+    if (n == 0) { std::memset(totals, 0, nbins * sizeof(uint32_t)); return SSF_OK; }
+    { const int rc = tile_copy_buffers(h, h->bins); if (rc) return rc; }
+    h->bins.drop();
+    Rt T; T.R = m3(v3(T12[0], T12[1], T12[2]), v3(T12[3], T12[4], T12[5]), v3(T12[6], T12[7], T12[8])); T.t = v3(T12[9], T12[10], T12[11]);
+    const SurfelSoA& M = h->model[h->mcur];
+    launch_bin_rows(h->stream, h->cam, M, (int)n, T, h->bins.d_count, h->bins.d_cursor, h->bins.rows);
+    HCK(hipGetLastError());
+    HCK(hipMemcpyAsync(records, h->bins.rows.pos, 48 * n, hipMemcpyDeviceToHost, h->stream));
+    HCK(hipMemcpyAsync(totals, h->bins.d_cursor, nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (lab_src) HCK(hipMemcpyAsync(lab_src, M.lab, 12 * n, hipMemcpyDeviceToHost, h->stream));
+    HCK(hipStreamSynchronize(h->stream));
+    return SSF_OK;
+}
+// frames whose tracking made the tile-sorted copy since the handle was created
+long long ssf_tile_copy_frames(ssf_handle* h) { return h ? h->bins.frames : -1; }
 // visible rows up to which a frame's ICP loop and association run in ONE resident launch (default and ceiling: 262 144, every
 // workgroup of it must hold a place at once; 0: never)
 int ssf_debug_set_resident_icp_max_rows(ssf_handle* h, int n) {
