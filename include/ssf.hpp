@@ -35,6 +35,7 @@
 #include "ssf_navpose.h"
 #include "ssf_navdyn.h"
 #include "ssf_navmem.h"
+#include "ssf_navfloor.h"
 #include "ssf_raycast.h"
 #include "ssf_motion.h"
 #include "ssf_odometry.h"
@@ -266,6 +267,33 @@ struct NavGrid {
     std::vector<int8_t> state;                     /* nav_msgs/OccupancyGrid's values: 100 occupied, 0 free, -1 unknown */
     std::vector<int32_t> dist2;                    /* squared distance in cells to the nearest obstacle cell, capped at max_dist_cells^2 */
     ssf_navgrid_stats stats;
+};
+/* fitFloor (ssf_navfloor.h; exported by libssf_hip_floor.so, linked INSTEAD of the other libraries -- a program that does not call
+ * it links as before: the inline member leaves no reference behind): the floor plane of the map, fitted on the device, as the frame and
+ * bands of a navigation grid.  The members start at ssf_navfloor_default_params' values; origin nullptr = the camera position. */
+struct FloorParams {
+    float3 up = float3{0.f, -1.f, 0.f};            /* up hint in the map frame (the first camera's y points down) */
+    const float3* origin = nullptr;                /* positions are taken relative to it; the pose's multiples of res count from it */
+    float tilt_cos = 0.8f, align_cos = 0.95f, height_res = 0.02f;
+    int min_rows = 32, floor_share256 = 64, refine_iters = 3;
+    float first_dist = 0.15f, inlier_dist = 0.05f, min_conf = 0.f;
+    int32_t t_init_min = -2147483647 - 1, t_init_max = 2147483647, t_last_min = -2147483647 - 1, t_last_max = 2147483647;
+    bool visible_only = false;
+    int width = 512, height = 512; float res = 0.05f;      /* the grid the pose is centred and snapped for */
+    float below = 0.5f, step = 0.2f, body_height = 1.5f;   /* the bands about the floor: z_min = -below, floor_max = step, z_max = body_height */
+    bool want_histograms = false;
+};
+/* what fitFloor found: fit is the C result (status, plane, counts, rounds, pose, bands); pose is fit.pose as a Transform3 */
+struct FloorFit {
+    ssf_navfloor_fit_result fit;
+    Transform3 pose;
+    std::vector<uint32_t> dir_hist, height_hist;   /* with want_histograms: 31 x 31 and 2048 */
+    bool ok() const { return fit.status == SSF_NAVFLOOR_OK; }
+    /* the frame, the bands and the size of the fit into a grid's parameters; g.pose points into this object */
+    void applyTo(NavGridParams& g) const {
+        g.pose = &pose; g.z_min = fit.z_min; g.floor_max = fit.floor_max; g.z_max = fit.z_max;
+        g.width = fit.width; g.height = fit.height; g.res = fit.res;
+    }
 };
 /* buildNavGrid with views (ssf_navcarve.h; exported by libssf_hip_navcarve.so, linked INSTEAD of libssf_hip.so -- a program that
  * does not call it links against libssf_hip.so as before: the inline member leaves no reference behind): the grid with free space carved along camera rays.  The
@@ -940,6 +968,33 @@ public:
     }
     void buildNavGrid(const NavGridParams& g, const CarveParams& c, const std::vector<std::array<float, 12> >& views, CarvedNavGrid& out) {
         buildNavGrid(g, c, views.empty() ? nullptr : views[0].data(), (int)views.size(), out);
+    }
+    /* The floor plane of the map, fitted on the device (ssf_navfloor.h): the lowest large set of rows whose normals agree with the up
+     * hint and whose heights agree.  A status other than SSF_NAVFLOOR_OK is no error: out.fit says how far the fit came. */
+    void fitFloor(const FloorParams& f, FloorFit& out) {
+        ssf_navfloor_params p;
+        check(ssf_navfloor_default_params(need(), &p));
+        float o[3];
+        p.up[0] = f.up.x; p.up[1] = f.up.y; p.up[2] = f.up.z;
+        if (f.origin) { o[0] = f.origin->x; o[1] = f.origin->y; o[2] = f.origin->z; p.origin = o; }
+        p.tilt_cos = f.tilt_cos; p.align_cos = f.align_cos; p.height_res = f.height_res;
+        p.min_rows = f.min_rows; p.floor_share256 = f.floor_share256; p.refine_iters = f.refine_iters;
+        p.first_dist = f.first_dist; p.inlier_dist = f.inlier_dist; p.min_conf = f.min_conf;
+        p.t_init_min = f.t_init_min; p.t_init_max = f.t_init_max; p.t_last_min = f.t_last_min; p.t_last_max = f.t_last_max;
+        p.visible_only = f.visible_only ? 1 : 0;
+        p.width = f.width; p.height = f.height; p.res = f.res; p.below = f.below; p.step = f.step; p.body_height = f.body_height;
+        out.dir_hist.assign(f.want_histograms ? SSF_NAVFLOOR_DIR_BINS * SSF_NAVFLOOR_DIR_BINS : 0, 0u);
+        out.height_hist.assign(f.want_histograms ? SSF_NAVFLOOR_HEIGHT_BINS : 0, 0u);
+        const ssf_navfloor_out o2 = {f.want_histograms ? out.dir_hist.data() : nullptr, f.want_histograms ? out.height_hist.data() : nullptr};
+        check(ssf_navfloor_fit(need(), &p, &o2, &out.fit));
+        out.pose = transform3_from_rt(out.fit.pose);
+    }
+    /* The fit, then the grid in its frame and bands: g's pose, bands, size and res are replaced by the fit's (f's width, height and
+     * res), everything else of g holds. */
+    void buildNavGridOnFloor(const FloorParams& f, NavGridParams g, FloorFit& fit, NavGrid& out) {
+        fitFloor(f, fit);
+        fit.applyTo(g);
+        buildNavGrid(g, out);
     }
 private:
     /* the C parameters of a grid call (v: room for the pose), out's vectors sized, and the output pointers into them */

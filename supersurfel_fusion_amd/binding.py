@@ -44,6 +44,9 @@ DYN_LIB = os.path.join(_HERE, "csrc", "libssf_hip_dyn.so")
 # dyn's objects and the live layer with memory (include/ssf_navmem.h): the one library of a robot whose live obstacles outlive their
 # time in view and are cleared when seen through.  None of the ten libraries above exports the memory's entry points
 MEM_LIB = os.path.join(_HERE, "csrc", "libssf_hip_mem.so")
+# mem's objects and the fitted floor plane (include/ssf_navfloor.h): the one library of a robot that also finds the grid's frame and
+# bands in its map.  None of the eleven libraries above exports the fit's entry points
+FLOOR_LIB = os.path.join(_HERE, "csrc", "libssf_hip_floor.so")
 
 
 class SsfConfig(C.Structure):
@@ -164,6 +167,10 @@ NAVMEM_LAYER_NAMES = ("marks", "mark_tick", "seen_tick")
 NAVMEM_OUTPUTS = (("marks", np.uint32), ("mark_tick", np.uint32), ("seen_tick", np.uint32), ("live_hits", np.uint32), ("hit_bits", np.uint32),
                   ("seen_bits", np.uint32), ("state", np.int8), ("dist2", np.int32))
 NAVMEM_OUTPUT_NAMES = tuple(nm for nm, _ in NAVMEM_OUTPUTS)
+# the fitted floor plane (include/ssf_navfloor.h): exported by libssf_hip_floor.so only (load_floor)
+NAVFLOOR_SYMBOLS = ["ssf_navfloor_default_params", "ssf_navfloor_fit"]
+NAVFLOOR_STATUS = ("ok", "no_floor", "degenerate")
+NAVFLOOR_DIR_BINS, NAVFLOOR_HEIGHT_BINS, NAVFLOOR_MAX_ROUNDS = 31, 2048, 8
 # the velocity commands (include/ssf_navsteer.h): exported by libssf_hip_steer.so only (load_steer)
 NAVSTEER_SYMBOLS = ["ssf_navsteer_rollouts", "ssf_navsteer_default_params", "ssf_navsteer_direction_table"]
 # (name, dtype, per pose or per candidate, trailing shape; 'T1' = n_steps + 1)
@@ -466,6 +473,43 @@ class SsfNavMemStats(C.Structure):
     def as_dict(self):
         d = {nm: int(getattr(self, nm)) for nm, _ in self._fields_ if nm != "pose"}
         d["pose"] = np.array(self.pose, np.float32)
+        return d
+
+
+class SsfNavFloorParams(C.Structure):
+    """ssf_navfloor_params (include/ssf_navfloor.h)"""
+    _fields_ = [("origin", C.c_void_p), ("up", C.c_float * 3), ("tilt_cos", C.c_float), ("align_cos", C.c_float), ("height_res", C.c_float),
+                ("min_rows", C.c_int), ("floor_share256", C.c_int), ("refine_iters", C.c_int), ("first_dist", C.c_float), ("inlier_dist", C.c_float),
+                ("min_conf", C.c_float), ("t_init_min", C.c_int32), ("t_init_max", C.c_int32), ("t_last_min", C.c_int32), ("t_last_max", C.c_int32),
+                ("visible_only", C.c_int), ("width", C.c_int), ("height", C.c_int), ("res", C.c_float), ("below", C.c_float), ("step", C.c_float),
+                ("body_height", C.c_float)]
+
+
+class SsfNavFloorOut(C.Structure):
+    """ssf_navfloor_out (include/ssf_navfloor.h)"""
+    _fields_ = [("dir_hist", C.c_void_p), ("height_hist", C.c_void_p)]
+
+
+class SsfNavFloorFitResult(C.Structure):
+    """ssf_navfloor_fit_result (include/ssf_navfloor.h)"""
+    _fields_ = [("status", C.c_int), ("rounds", C.c_int), ("normal", C.c_float * 3), ("d", C.c_float), ("origin", C.c_float * 3),
+                ("camera_height", C.c_float), ("rows_used", C.c_int64), ("candidates", C.c_int64), ("direction_rows", C.c_int64),
+                ("aligned", C.c_int64), ("height_out_of_range", C.c_int64), ("height_rows", C.c_int64), ("dir_bin", C.c_int * 2),
+                ("height_bin", C.c_int), ("reserved", C.c_int), ("inliers", C.c_int64 * 8), ("rms", C.c_float * 8), ("sums", (C.c_int64 * 10) * 8),
+                ("pose", C.c_float * 12), ("z_min", C.c_float), ("floor_max", C.c_float), ("z_max", C.c_float), ("width", C.c_int),
+                ("height", C.c_int), ("res", C.c_float)]
+
+    def as_dict(self):
+        d = {nm: int(getattr(self, nm)) for nm in ("status", "rounds", "rows_used", "candidates", "direction_rows", "aligned", "height_out_of_range",
+                                                   "height_rows", "height_bin", "width", "height")}
+        for nm in ("d", "camera_height", "z_min", "floor_max", "z_max", "res"):
+            d[nm] = np.float32(getattr(self, nm))
+        for nm in ("normal", "origin", "rms", "pose"):
+            d[nm] = np.array(getattr(self, nm), np.float32)
+        d["dir_bin"] = (int(self.dir_bin[0]), int(self.dir_bin[1]))
+        d["inliers"] = [int(v) for v in self.inliers]
+        d["sums"] = np.array([[int(v) for v in row] for row in self.sums], np.int64)
+        d["status_name"] = NAVFLOOR_STATUS[self.status]
         return d
 
 
@@ -785,6 +829,10 @@ class Library:
             L.ssf_navmem_default_params.argtypes = [vp, C.POINTER(SsfNavMemParams)]
             L.ssf_navmem_update.argtypes = [vp, C.POINTER(SsfNavMemParams), vp, vp, vp, C.POINTER(SsfNavMemLayer), C.POINTER(SsfNavMemOut),
                                             C.POINTER(SsfNavMemStats)]
+        self.has_navfloor = all(hasattr(L, nm) for nm in NAVFLOOR_SYMBOLS)
+        if self.has_navfloor:
+            L.ssf_navfloor_default_params.argtypes = [vp, C.POINTER(SsfNavFloorParams)]
+            L.ssf_navfloor_fit.argtypes = [vp, C.POINTER(SsfNavFloorParams), C.POINTER(SsfNavFloorOut), C.POINTER(SsfNavFloorFitResult)]
         self.has_navgrid = all(hasattr(L, nm) for nm in NAVGRID_SYMBOLS)
         if self.has_navgrid:
             L.ssf_navgrid_default_params.argtypes = [vp, C.POINTER(SsfNavGridParams)]
@@ -1007,6 +1055,14 @@ def load_mem():
     to call nav_memory, nav_memory_plan or nav_memory_dyn_steer on it.  Fails loudly when it has not been built."""
     import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
     return Library(MEM_LIB)
+
+
+def load_floor():
+    """Load libssf_hip_floor.so: mem's objects (the product and every navigation call up to the live layer with memory) with the fitted
+    floor plane linked in (include/ssf_navfloor.h).  A handle belongs to the library that created it: create the Fusion from THIS
+    library to call nav_floor or nav_floor_grid on it.  Fails loudly when it has not been built."""
+    import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
+    return Library(FLOOR_LIB)
 
 
 class LiveMemory:
@@ -1741,6 +1797,80 @@ class Fusion:
         pose = np.zeros(12, np.float32)
         self._ck(self.L.lib.ssf_navgrid_default_pose(self.h, C.byref(p), _ptr(pose)), "ssf_navgrid_default_pose")
         return pose
+
+    # ---- the fitted floor plane: the grid's own frame and bands (include/ssf_navfloor.h) ------
+    def _need_navfloor(self, symbol):
+        if not self.L.has_navfloor:
+            raise SsfError("%s does not export %s: it fits no floor plane (include/ssf_navfloor.h: libssf_hip_floor.so, binding.load_floor)"
+                           % (self.L.path, symbol))
+
+    def _navfloor_params(self, up=None, origin=None, t_init=None, t_last=None, visible_only=False, **kw):
+        """(SsfNavFloorParams, the origin array it points into).  up: 3 floats (None = (0, -1, 0)); origin: 3 floats in the map frame
+        (None = the camera position); t_init / t_last: (min, max) of stamps.x / stamps.y (None = any); the other keywords are fields of
+        ssf_navfloor_params, each at ssf_navfloor_default_params' value when missing."""
+        p = SsfNavFloorParams()
+        self._ck(self.L.lib.ssf_navfloor_default_params(self.h, C.byref(p)), "ssf_navfloor_default_params")
+        keep = None
+        if up is not None:
+            up = np.asarray(up, np.float32).ravel()
+            if up.size != 3:
+                raise SsfError("an up hint is 3 floats, got %d" % up.size)
+            p.up[0], p.up[1], p.up[2] = float(up[0]), float(up[1]), float(up[2])
+        if origin is not None:
+            keep = np.ascontiguousarray(np.asarray(origin, np.float32).ravel())
+            if keep.size != 3:
+                raise SsfError("an origin is 3 floats, got %d" % keep.size)
+            p.origin = keep.ctypes.data
+        if t_init is not None:
+            p.t_init_min, p.t_init_max = int(t_init[0]), int(t_init[1])
+        if t_last is not None:
+            p.t_last_min, p.t_last_max = int(t_last[0]), int(t_last[1])
+        kinds = dict(p._fields_)
+        for nm, v in kw.items():
+            if nm not in kinds or nm in ("origin", "up", "visible_only") or nm.startswith("t_"):
+                raise SsfError("unknown floor fit parameter %r" % nm)
+            setattr(p, nm, float(v) if kinds[nm] is C.c_float else int(v))
+        p.visible_only = int(bool(visible_only))
+        return p, keep
+
+    def nav_floor(self, histograms=True, **kw):
+        """The floor plane of the model (ssf_navfloor_fit): dict of the result -- status (and status_name), the plane normal . (c -
+        origin) = d, camera_height, the exact counts, the winners, per round inliers / rms / sums, pose and the three bands -- with
+        'dir_hist' (31 x 31 u32) and 'height_hist' (2048 u32) unless histograms is False, and 'grid' = dict(pose, z_min, floor_max, z_max,
+        width, height, res): what nav_grid, nav_grid_carve and the live calls take where they take those keywords.  Keywords:
+        _navfloor_params."""
+        self._need_navfloor("ssf_navfloor_fit")
+        p, keep = self._navfloor_params(**kw)
+        res = SsfNavFloorFitResult()
+        dh, hh = np.zeros((NAVFLOOR_DIR_BINS, NAVFLOOR_DIR_BINS), np.uint32), np.zeros(NAVFLOOR_HEIGHT_BINS, np.uint32)
+        out = SsfNavFloorOut(_ptr(dh), _ptr(hh)) if histograms else SsfNavFloorOut(None, None)
+        self._ck(self.L.lib.ssf_navfloor_fit(self.h, C.byref(p), C.byref(out), C.byref(res)), "ssf_navfloor_fit")
+        d = res.as_dict()
+        if histograms:
+            d["dir_hist"], d["height_hist"] = dh, hh
+        d["grid"] = dict(pose=d["pose"].copy(), z_min=float(d["z_min"]), floor_max=float(d["floor_max"]), z_max=float(d["z_max"]), width=d["width"],
+                         height=d["height"], res=float(d["res"]))
+        return d
+
+    def nav_floor_default_params(self):
+        """ssf_navfloor_default_params as a dict"""
+        self._need_navfloor("ssf_navfloor_default_params")
+        p = SsfNavFloorParams()
+        self._ck(self.L.lib.ssf_navfloor_default_params(self.h, C.byref(p)), "ssf_navfloor_default_params")
+        d = {nm: getattr(p, nm) for nm, _ in p._fields_ if nm not in ("origin", "up")}
+        d["up"] = tuple(float(v) for v in p.up)
+        return d
+
+    def nav_floor_grid(self, outputs=NAVGRID_OUTPUT_NAMES, floor=None, **grid_kw):
+        """The fit, then the navigation grid in its frame and bands: dict(floor = nav_floor's dict, grid = nav_grid's).  floor: the fit's
+        keywords (width, height and res come from grid_kw); grid_kw: nav_grid's other keywords (no pose, no bands: they are the fit's)."""
+        self._need_navfloor("ssf_navfloor_fit")
+        bad = [nm for nm in ("pose", "z_min", "z_max", "floor_max") if nm in grid_kw]
+        if bad:
+            raise SsfError("nav_floor_grid takes %s from the fit" % ", ".join(bad))
+        size = {nm: grid_kw.pop(nm) for nm in ("width", "height", "res") if nm in grid_kw}
+        fit = self.nav_floor(histograms=False, **dict(floor or {}, **size))
+        return dict(floor=fit, grid=self.nav_grid(outputs=outputs, **dict(grid_kw, **fit["grid"])))
 
     # ---- the navigation grid with free space carved along camera rays (include/ssf_navcarve.h) ------
     def _need_navcarve(self, symbol):

@@ -424,6 +424,15 @@ struct NavMemWs {
     unsigned char* img_in = nullptr; size_t img_in_bytes = 0;      // staged host inputs: depth, mask, state_in, the layer
     unsigned char* img = nullptr; size_t img_bytes = 0;            // staged host outputs (a StagedIo holds eight arrays: two of them)
 };
+// ssf_navfloor_fit (ssf_navfloor.h, ssf_navfloor.hip: linked into libssf_hip_floor.so only): per slot the 32-byte candidate record; the
+// sums (rows, candidates, the record cursor, the direction's four words, the height's two, ten per round); the two histograms.
+// Allocated on first use; each group is grown as a whole or not at all (DevBufs::grow).  Nothing here is read or written by the
+// frame path.
+struct NavFloorWs {
+    DevBufs bufs;
+    float4* rec = nullptr; size_t slots = 0;
+    unsigned long long* stats = nullptr; uint32_t* hist = nullptr;
+};
 // ssf_navfoot_layers and ssf_navfoot_rollouts (ssf_navfoot.h, ssf_navfoot.hip: linked into libssf_hip_foot.so only): the footprint's
 // table of spans as the layers kernel reads it (kept from call to call while the footprint is the same), the layers' sums and the staging buffer of a layers call with host arrays; per cell
 // the rollouts' packed (heading mask, d) word of 8 bytes.  The rollouts' keys, counts, direction table, sums and staging are
@@ -591,7 +600,8 @@ struct ssf_handle {
     RaycastWs raycast;                            // ssf_raycast (ssf_raycast.h)
     unsigned long long model_gen = 0;             // bumped by whatever rewrites model rows or their order (a fuse, store_from_dense); the out-of-view
                                                   // compaction keeps rows and order but moves slots: who keeps slot numbers also watches n_recentres (RaycastWs)
-    NavMemWs navmem;                              // ssf_navmem_update (ssf_navmem.h); last, so that no older member moves
+    NavMemWs navmem;                              // ssf_navmem_update (ssf_navmem.h); behind the older members, so that none of them moves
+    NavFloorWs navfloor;                          // ssf_navfloor_fit (ssf_navfloor.h); last, for the same reason
 };
 
 #define HCK(call)                                                                                    \

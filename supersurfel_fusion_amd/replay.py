@@ -241,7 +241,8 @@ def steer_lattice(speed, res):
     return dict(n_v=9, v_min=0, v_step=top // 8) if top >= 8 else dict(n_v=1, v_min=top, v_step=0)
 
 
-def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, plan=None, frontiers=None, waypoints=None, live=None, steer=None):
+def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, plan=None, frontiers=None, waypoints=None, live=None, steer=None,
+                   fit_floor=None):
     """the navigation grid of the map, built on the device (include/ssf_navgrid.h) at the default size and frame (floor-aligned
     about the tracked camera) with cells of `res` metres: grid_dir/<k as %06d>.pgm -- the state in map_server's convention (205
     unknown, 254 free, 0 occupied; the image's top row is the grid's last) --, <k>.yaml beside it (map_server's keys; origin = the
@@ -279,11 +280,28 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
     objects (include/ssf_navdyn.h): the motion detector's mask keeps them OUT of the live layer (mask_mode 2), its labels and the depth
     give their blobs in the grid frame, the tracker turns this table and the one of the grid before into movers (steps_since from
     the frames between the two at NAV_FRAME_DT seconds each), and nav_dyn_steer / nav_dyn_foot_steer refuse the steps that meet
-    them: <k>_blobs.npy ((n, 8) int32), <k>_movers.npy ((n, 6) int32) and one nav-movers log line"""
+    them: <k>_blobs.npy ((n, 8) int32), <k>_movers.npy ((n, 6) int32) and one nav-movers log line.
+    fit_floor (dict(up=(X, Y, Z) or None)): the grid is built in the frame and bands of a floor plane fitted to the map just before it
+    (include/ssf_navfloor.h) instead of the default ones, the live layer takes the same frame and bands, and the plane and the fit's
+    counts go into <k>_floor.json with one nav-floor log line"""
+    gkw = dict(res=res)
+    if fit_floor is not None:
+        import json
+        fit = fusion.nav_floor(histograms=False, res=res, up=fit_floor.get("up"))
+        gkw = dict(fit["grid"])
+        os.makedirs(grid_dir, exist_ok=True)
+        with open(os.path.join(grid_dir, "%06d_floor.json" % k), "w") as f:
+            json.dump(dict({nm: fit[nm] for nm in ("status", "status_name", "rounds", "rows_used", "candidates", "direction_rows", "aligned",
+                                                   "height_out_of_range", "height_rows", "height_bin", "inliers")},
+                           normal=[float(v) for v in fit["normal"]], d=float(fit["d"]), origin=[float(v) for v in fit["origin"]],
+                           camera_height=float(fit["camera_height"]), dir_bin=list(fit["dir_bin"]), rms=[float(v) for v in fit["rms"]],
+                           z_min=gkw["z_min"], floor_max=gkw["floor_max"], z_max=gkw["z_max"]), f, sort_keys=True)
+        print("nav-floor %06d: status=%s rounds=%d camera_height=%.3f candidates=%d inliers=%d" % (k, fit["status_name"], fit["rounds"],
+              float(fit["camera_height"]), fit["candidates"], fit["inliers"][max(0, fit["rounds"] - 1)]))
     if carve_views is None:
-        out = fusion.nav_grid(outputs=("state", "dist2"), res=res)
+        out = fusion.nav_grid(outputs=("state", "dist2"), **gkw)
     else:
-        out = fusion.nav_grid_carve(thin_views(carve_views), outputs=("state", "dist2", "seen"), carve=dict(stride=carve_stride), res=res)
+        out = fusion.nav_grid_carve(thin_views(carve_views), outputs=("state", "dist2", "seen"), carve=dict(stride=carve_stride), **gkw)
     state, pose = out["state"], out["stats"]["pose"]
     os.makedirs(grid_dir, exist_ok=True)
     name = "%06d" % k
@@ -316,6 +334,8 @@ def write_nav_grid(fusion, grid_dir, k, res, carve_views=None, carve_stride=8, p
                                                                    " ".join("%s=%d" % (nm, n) for nm, n in table["stats"].items())))
         lkw = dict(mask=None if mm is None else mm["mask"], grid_pose=pose, res=res, min_hits=int(live.get("min_hits", 4)),
                    stride=int(live.get("stride", 4)), mask_mode=0 if mm is None else 2)
+        if fit_floor is not None:
+            lkw.update(floor_max=gkw["floor_max"], z_max=gkw["z_max"])
         keep = live.get("memory")
         if keep is None:
             lv = fusion.nav_live(live["depth"], state, outputs=("state", "dist2"), **lkw)
@@ -433,7 +453,8 @@ def write_laser_scan(fusion, scan_dir, k, beams):
 def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, mask_dir=None, render_dir=None, render_every=30,
            keyframes=None, keyframe_log=None, local_cloud_dir=None, local_cloud_radius=2.0, local_cloud_every=30, detect_motion=False,
            motion_mask_dir=None, odometry_prior=False, nav_grid_dir=None, nav_grid_every=30, nav_grid_res=0.05,
-           nav_grid_carve=False, nav_grid_carve_stride=8, nav_plan=None, nav_frontiers=None, nav_waypoints=None, nav_live=None, nav_steer=None, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360):
+           nav_grid_carve=False, nav_grid_carve_stride=8, nav_plan=None, nav_frontiers=None, nav_waypoints=None, nav_live=None, nav_steer=None, laser_scan_dir=None, laser_scan_every=30, laser_scan_beams=360,
+           nav_fit_floor=None):
     """frames: iterable of (stamp, rgb u8 HxWx3, depth HxW in the handle's input format: f32 metres by default).  Returns (lines, results).
     pipelined: decode / submit ahead while earlier frames are tracked and fused (ssf_submit_frame /
     ssf_process_submitted, for handles created with pipeline_depth / extract_batch > 0 / 1); the trajectory is the
@@ -452,7 +473,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
     frame just processed is stamped onto each grid (write_nav_grid's live; with a 'memory' dict(forget, slices) into the layer that
     remembers, one layer for the whole sequence).  nav_waypoints (write_nav_grid's waypoints; needs nav_plan):
     the plan's path reduced to waypoints is written next to it.  nav_steer (write_nav_grid's steer; needs nav_plan): the velocity command
-    from the tracked camera's pose on each grid is logged and its arc written next to it.
+    from the tracked camera's pose on each grid is logged and its arc written next to it.  nav_fit_floor (write_nav_grid's fit_floor):
+    every grid is built in the frame of a floor plane fitted just before it.
     laser_scan_dir: after frames 0, laser_scan_every, 2 laser_scan_every, ... a planar scan of laser_scan_beams beams from the tracked
     pose is written (write_laser_scan, numbered by frame); pipelined, submission pauses as for a render.
     keyframes: a dict of ssf_keyframes_params fields ({} = the defaults): the keyframe database is configured and
@@ -477,6 +499,8 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
         raise ValueError("nav_live needs nav_grid_dir")
     if nav_steer is not None and nav_plan is None:
         raise ValueError("nav_steer needs nav_plan")
+    if nav_fit_floor is not None and not nav_grid_dir:
+        raise ValueError("nav_fit_floor needs nav_grid_dir")
     if nav_steer is not None and nav_steer.get("movers") is not None:
         if nav_live is None:
             raise ValueError("nav_steer's movers need nav_live")
@@ -535,7 +559,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
                 write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan, nav_frontiers,
-                               nav_waypoints, live_of(depth), nav_steer)
+                               nav_waypoints, live_of(depth), nav_steer, nav_fit_floor)
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     else:
@@ -568,7 +592,7 @@ def replay(fusion, frames, out_path=None, export_model=None, pipelined=False, ma
                 write_local_cloud(fusion, local_cloud_dir, len(lines) - 1, local_cloud_radius)
             if nav_grid_dir and (len(lines) - 1) % nav_grid_every == 0:
                 write_nav_grid(fusion, nav_grid_dir, len(lines) - 1, nav_grid_res, carve_views(), nav_grid_carve_stride, nav_plan, nav_frontiers,
-                               nav_waypoints, live_of(last_depth), nav_steer)
+                               nav_waypoints, live_of(last_depth), nav_steer, nav_fit_floor)
             if laser_scan_dir and (len(lines) - 1) % laser_scan_every == 0:
                 write_laser_scan(fusion, laser_scan_dir, len(lines) - 1, laser_scan_beams)
     if out_path:
@@ -701,6 +725,11 @@ def parse_args(argv=None):
                          "(map_server's convention), .yaml and _dist2.npy (squared clearance in cells)")
     ap.add_argument("--nav-grid-every", type=int, default=30, metavar="K")
     ap.add_argument("--nav-grid-res", type=float, default=0.05, metavar="R", help="metres per cell (default 0.05)")
+    ap.add_argument("--nav-grid-fit-floor", action="store_true",
+                    help="with --nav-grid-dir: every grid is built in the frame and bands of a floor plane fitted to the map just before it "
+                         "(include/ssf_navfloor.h); the plane and the fit's counts go into _floor.json next to the grid")
+    ap.add_argument("--nav-floor-up", nargs=3, type=float, default=None, metavar=("X", "Y", "Z"),
+                    help="with --nav-grid-fit-floor: the up hint in the map frame (default 0 -1 0: the first camera's y points down)")
     ap.add_argument("--nav-grid-carve", action="store_true",
                     help="with --nav-grid-dir: carve free space along the rays of the poses estimated so far (at most 256, evenly thinned); "
                          "the files show the carved state, and _seen.npy (ray entries per cell) is written as well")
@@ -779,6 +808,12 @@ def parse_args(argv=None):
         ap.error("--motion-mask-dir needs --detect-motion")
     if a.nav_grid_carve and not a.nav_grid_dir:
         ap.error("--nav-grid-carve needs --nav-grid-dir")
+    if a.nav_grid_fit_floor and not a.nav_grid_dir:
+        ap.error("--nav-grid-fit-floor needs --nav-grid-dir")
+    if a.nav_floor_up is not None and not a.nav_grid_fit_floor:
+        ap.error("--nav-floor-up goes with --nav-grid-fit-floor")
+    if a.nav_floor_up is not None and not any(a.nav_floor_up):
+        ap.error("--nav-floor-up is not zero")
     if (a.nav_plan_goal or a.nav_plan_frontier) and not a.nav_grid_dir:
         ap.error("--nav-plan-goal and --nav-plan-frontier need --nav-grid-dir")
     if a.nav_plan_radius < 0.0 or (a.nav_plan_radius > 0.0 and not (a.nav_plan_goal or a.nav_plan_frontier)):
@@ -903,13 +938,22 @@ def nav_frontiers_of(a):
                 gain_radius=0 if a.nav_frontier_gain_radius is None else int(a.nav_frontier_gain_radius))
 
 
+def nav_fit_floor_of(a):
+    """replay()'s nav_fit_floor from the parsed options, or None"""
+    if not a.nav_grid_fit_floor:
+        return None
+    return dict(up=None if a.nav_floor_up is None else tuple(float(v) for v in a.nav_floor_up))
+
+
 def library_of(a):
     """the name of binding's loader of the library that exports every entry point the parsed options ask for (the carve's, the plan's,
     the regions', the waypoints', the live layer's, the commands', the footprint's, the pose plan's and the movers' entry points: libraries
     of their own, each holding the one before it)"""
+    if nav_fit_floor_of(a) is not None:
+        return "load_floor"                                               # (the last of the chain: it holds whatever else is asked for)
     steer = nav_steer_of(a)
     if (nav_live_of(a) or {}).get("memory") is not None:
-        return "load_mem"                                                 # (the last of the chain: it holds whatever else is asked for)
+        return "load_mem"                                                 # (it holds whatever else is asked for without the fit)
     if steer:
         if steer.get("movers") is not None:
             return "load_dyn"
@@ -946,7 +990,7 @@ def main(argv=None):
                         nav_grid_res=a.nav_grid_res, nav_grid_carve=a.nav_grid_carve, nav_grid_carve_stride=a.nav_grid_carve_stride, nav_plan=plan,
                         nav_frontiers=frontiers, nav_waypoints=waypoints, nav_live=live, nav_steer=steer,
                         laser_scan_dir=a.laser_scan_dir, laser_scan_every=a.laser_scan_every,
-                        laser_scan_beams=a.laser_scan_beams)
+                        laser_scan_beams=a.laser_scan_beams, nav_fit_floor=nav_fit_floor_of(a))
     if a.keyframes and not a.keyframe_log:
         print("\n".join(f.keyframe_lines))
     print("%d frames -> %s ; %d supersurfels" % (len(lines), a.out, res[-1]["n_model"] if res else 0))
