@@ -170,18 +170,21 @@ struct DevBufs {
 // The host arrays of one call, carried through a staging buffer on the device: every array is declared ONCE, with its bytes and
 // the kernel argument that points at it (on declaration: the caller's own pointer).  reserve grows the buffer when the call needs
 // more and points every argument at its item's place (nullptr for a NULL array: not produced); copy_in / copy_out enqueue the
-// copies of the inputs / outputs.  The offsets are StageLayout's (ssf_stage_layout.hpp).
+// copies of the inputs / outputs, in the order of declaration; an inout item is in both.  The offsets are StageLayout's
+// (ssf_stage_layout.hpp).
 struct StagedIo {
     StageLayout lay;
     void** arg[StageLayout::MAX_ITEMS];
-    unsigned inputs = 0;                                          // bit i: item i is read by the device (host -> device)
-    void add(const void* host, size_t bytes, void** dev, bool in) {
+    static_assert(StageLayout::MAX_ITEMS <= 32, "inputs and outputs hold a bit per item");
+    unsigned inputs = 0, outputs = 0;                             // bit i: item i is read (host -> device) / written (device -> host) by the device
+    void add(const void* host, size_t bytes, void** dev, bool in, bool out) {
         const int i = lay.add(host, bytes);
         assert(i >= 0);                                           // (more items than StageLayout::MAX_ITEMS: raise it)
-        arg[i] = dev; if (in) inputs |= 1u << i;
+        arg[i] = dev; if (in) inputs |= 1u << i; if (out) outputs |= 1u << i;
     }
-    template <typename T> void out(T* host, size_t bytes, T** dev) { add(host, bytes, (void**)dev, false); }
-    template <typename T> void in(const T* host, size_t bytes, const T** dev) { add(host, bytes, (void**)dev, true); }
+    template <typename T> void out(T* host, size_t bytes, T** dev) { add(host, bytes, (void**)dev, false, true); }
+    template <typename T> void in(const T* host, size_t bytes, const T** dev) { add(host, bytes, (void**)dev, true, false); }
+    template <typename T> void inout(T* host, size_t bytes, T** dev) { add(host, bytes, (void**)dev, true, true); }
     size_t need() const { return lay.total; }
     // *buf holds *have bytes: grown to cap (>= need(), the caller's growth rule) when need() does not fit
     bool reserve(DevBufs& bufs, unsigned char** buf, size_t* have, size_t cap) {
@@ -192,7 +195,7 @@ struct StagedIo {
     hipError_t copy(hipStream_t st, bool in) const {
         for (int i = 0; i < lay.n; i++) {
             const StageLayout::Item& it = lay.item[i];
-            if (!it.host || ((inputs >> i) & 1u) != (in ? 1u : 0u)) continue;
+            if (!it.host || !(((in ? inputs : outputs) >> i) & 1u)) continue;
             const hipError_t e = in ? hipMemcpyAsync(*arg[i], it.host, it.bytes, hipMemcpyHostToDevice, st)
                                     : hipMemcpyAsync(const_cast<void*>(it.host), *arg[i], it.bytes, hipMemcpyDeviceToHost, st);
             if (e != hipSuccess) return e;
@@ -343,42 +346,45 @@ struct NavCarveWs {
     uint32_t* seen = nullptr; size_t cells = 0;
     int chunk_rays = 0; long long last_chunks = 0, last_atomics = 0;
 };
-// ssf_navplan_field (ssf_navplan.h, ssf_navplan.hip: linked into libssf_hip_nav.so only): per cell the grid as the call got it (state,
-// dist2: the copy of host arrays), the packed (traversable, penalty) word, the cost and the frontier; per 32 x 32-cell tile the two
-// ping-pong flag words; the goals (65536 pairs) and starts (4096 pairs) with the starts' results; the paths of a call with host
-// outputs; the sums.  Allocated on first use; each group is grown as a whole or not at all (DevBufs::grow).  round_batch: the test
-// hook (0 = the default); last_*: what the last call did.  Nothing here is read or written by the frame path.
+// ssf_navplan_field (ssf_navplan.h, ssf_navplan.hip: linked into libssf_hip_nav.so only): per cell the packed (traversable, penalty)
+// word, the cost and the frontier; per 32 x 32-cell tile the two ping-pong flag words; the goals (65536 pairs) and starts (4096 pairs)
+// with the starts' results; the paths of a call with host outputs and the staging buffer of its host grid (state, dist2); the sums.
+// Allocated on first use; each group is grown as a whole or not at all (DevBufs::grow).  round_batch: the test hook (0 = the
+// default); last_*: what the last call did.  Nothing here is read or written by the frame path.
 struct NavPlanWs {
     DevBufs bufs;
-    int8_t* state = nullptr; int32_t* dist2 = nullptr; uint32_t* pk = nullptr; uint32_t* cost = nullptr; uint8_t* frontier = nullptr; size_t cells = 0;
+    uint32_t* pk = nullptr; uint32_t* cost = nullptr; uint8_t* frontier = nullptr; size_t cells = 0;
+    unsigned char* io = nullptr; size_t io_bytes = 0;
     uint32_t* flags = nullptr; size_t tiles = 0;
     int32_t* goals = nullptr; int32_t* starts = nullptr; uint32_t* start_cost = nullptr; int32_t* start_status = nullptr; int32_t* path_len = nullptr;
     unsigned long long* stats = nullptr;
     int32_t* path = nullptr; size_t path_words = 0;
     int round_batch = 0; long long last_rounds = 0, last_visits = 0;
 };
-// ssf_navfrontier_regions (ssf_navfrontier.h, ssf_navfrontier.hip: linked into libssf_hip_explore.so only): per cell the grid and the
-// cost field as the call got them (the copies of host arrays), the union-find's parent word and the label; per 256 cells and per 256
-// regions (+ 1) the counts that are scanned into offsets; per region found the accumulators (acc: NavFrontierAcc, ssf_navfrontier.hip);
-// the table (65536 records) and the sums.  Allocated on first use; each group is grown as a whole or not at all (DevBufs::grow).
+// ssf_navfrontier_regions (ssf_navfrontier.h, ssf_navfrontier.hip: linked into libssf_hip_explore.so only): per cell the union-find's
+// parent word and the label; per 256 cells and per 256 regions (+ 1) the counts that are scanned into offsets; per region found the
+// accumulators (acc: NavFrontierAcc, ssf_navfrontier.hip); the table (65536 records) and the sums; the staging buffer of a call with
+// host arrays (state, dist2, cost).  Allocated on first use; each group is grown as a whole or not at all (DevBufs::grow).
 // Nothing here is read or written by the frame path.
 struct NavFrontierWs {
     DevBufs bufs;
-    int8_t* state = nullptr; int32_t* dist2 = nullptr; uint32_t* cost = nullptr; int32_t* parent = nullptr; int32_t* label = nullptr;
+    int32_t* parent = nullptr; int32_t* label = nullptr;
     uint32_t* cell_blocks = nullptr; size_t cells = 0;
+    unsigned char* io = nullptr; size_t io_bytes = 0;
     void* acc = nullptr; uint32_t* region_blocks = nullptr; size_t regions = 0;
     void* table = nullptr; unsigned long long* stats = nullptr;
 };
-// ssf_navpath_waypoints (ssf_navpath.h, ssf_navpath.hip: linked into libssf_hip_drive.so only): per cell the grid as the call got it
-// (the copies of host arrays) and the packed (traversable, d) word; per path (4096) the length, status, waypoint count and minimum;
-// the paths and the waypoints of a call with host arrays; the sums.  Allocated on first use; each group is grown as a whole or not
-// at all (DevBufs::grow).  Nothing here is read or written by the frame path.
+// ssf_navpath_waypoints (ssf_navpath.h, ssf_navpath.hip: linked into libssf_hip_drive.so only): per cell the packed (traversable, d)
+// word; per path (4096) the status, waypoint count and minimum; the paths and the waypoints of a call with host arrays and the
+// staging buffer of its whole-array inputs (state, dist2, path_len); the sums.  Allocated on first use; each group is grown as a
+// whole or not at all (DevBufs::grow).  Nothing here is read or written by the frame path.
 struct NavPathWs {
     DevBufs bufs;
-    int8_t* state = nullptr; int32_t* dist2 = nullptr; uint32_t* pk = nullptr; size_t cells = 0;
-    int32_t* path_len = nullptr; int32_t* status = nullptr; int32_t* n_wp = nullptr; int32_t* path_min = nullptr; unsigned long long* stats = nullptr;
+    uint32_t* pk = nullptr; size_t cells = 0;
+    int32_t* status = nullptr; int32_t* n_wp = nullptr; int32_t* path_min = nullptr; unsigned long long* stats = nullptr;
     int32_t* path = nullptr; size_t path_words = 0;
     int32_t* wp = nullptr; size_t wp_words = 0;
+    unsigned char* io = nullptr; size_t io_bytes = 0;
 };
 // ssf_navlive_overlay (ssf_navlive.h, ssf_navlive.hip: linked into libssf_hip_live.so only): per cell the points and the ray entries of
 // the frame, the column distances of the clearance and the state when the caller did not ask for it (11 bytes); the sums; the staging
@@ -421,8 +427,7 @@ struct NavMemWs {
     uint32_t* hits = nullptr; uint32_t* hit_bits = nullptr; uint32_t* seen_bits = nullptr; uint16_t* colg = nullptr; int8_t* state = nullptr;
     size_t cells = 0;
     unsigned long long* stats = nullptr;
-    unsigned char* img_in = nullptr; size_t img_in_bytes = 0;      // staged host inputs: depth, mask, state_in, the layer
-    unsigned char* img = nullptr; size_t img_bytes = 0;            // staged host outputs (a StagedIo holds eight arrays: two of them)
+    unsigned char* img = nullptr; size_t img_bytes = 0;            // staged host arrays: depth, mask, state_in, the layer, the outputs
 };
 // ssf_navfloor_fit (ssf_navfloor.h, ssf_navfloor.hip: linked into libssf_hip_floor.so only): per slot the 32-byte candidate record; the
 // sums (rows, candidates, the record cursor, the direction's four words, the height's two, ten per round); the two histograms.
@@ -448,15 +453,16 @@ struct NavFootWs {
     unsigned char* io = nullptr; size_t io_bytes = 0;
     unsigned long long* pk = nullptr; size_t pk_cells = 0;
 };
-// ssf_navpose_field (ssf_navpose.h, ssf_navpose.hip: linked into libssf_hip_pose.so only): per cell the mask and dist2 as the call got
-// them (the copies of host arrays), the packed (traversable bins, penalty) word of 8 bytes, the projection (cell_cost, cell_bin); per
-// state the cost; per 16 x 16-cell tile the two ping-pong flag words; the goals (65536 triples) and starts (4096 triples) with the
-// starts' results; the paths of a call with host outputs; the sums.  Allocated on first use; each group is grown as a whole or not at
+// ssf_navpose_field (ssf_navpose.h, ssf_navpose.hip: linked into libssf_hip_pose.so only): per cell the packed (traversable bins,
+// penalty) word of 8 bytes and the projection (cell_cost, cell_bin); per state the cost; per 16 x 16-cell tile the two ping-pong flag
+// words; the goals (65536 triples) and starts (4096 triples) with the starts' results; the paths of a call with host outputs and the
+// staging buffer of its host grid (free_mask, dist2); the sums.  Allocated on first use; each group is grown as a whole or not at
 // all (DevBufs::grow).  Nothing here is read or written by the frame path.
 struct NavPoseWs {
     DevBufs bufs;
-    uint32_t* mask = nullptr; int32_t* dist2 = nullptr; unsigned long long* pk = nullptr; uint32_t* cell_cost = nullptr; uint8_t* cell_bin = nullptr;
+    unsigned long long* pk = nullptr; uint32_t* cell_cost = nullptr; uint8_t* cell_bin = nullptr;
     size_t cells = 0;
+    unsigned char* io = nullptr; size_t io_bytes = 0;
     uint32_t* cost = nullptr; size_t states = 0;
     uint32_t* flags = nullptr; size_t tiles = 0;
     int32_t* goals = nullptr; int32_t* starts = nullptr; uint32_t* start_cost = nullptr; int32_t* start_status = nullptr; int32_t* path_len = nullptr;

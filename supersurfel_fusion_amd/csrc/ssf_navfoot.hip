@@ -250,16 +250,14 @@ int ssf_navfoot_layers(ssf_handle* h, const ssf_navfoot_params* p, const int8_t*
             for (int dx = sp.lo[b][k]; dx <= sp.hi[b][k]; dx++) table[((size_t)b * nrow + r) * 2 + ((dx + reach) >> 6)] |= 1ull << ((dx + reach) & 63);
             if (sp.lo[b][k] <= sp.hi[b][k]) row_bins[r] |= 1u << b;
         }
-    // the arrays of a call with host pointers, each at a 256-byte boundary of one staging buffer
-    const size_t off_mask = (P + 255) & ~(size_t)255, off_n = off_mask + (out->free_mask ? (4 * P + 255) & ~(size_t)255 : 0);
-    const size_t need = dev ? 0 : off_n + (out->n_free ? (P + 255) & ~(size_t)255 : 0);
+    // the arrays of a call with host pointers are staged on the device
+    const int8_t* d_state = state; uint32_t* d_mask = out->free_mask; uint8_t* d_n = out->n_free;
+    StagedIo io;
+    if (!dev) { io.in(state, P, &d_state); io.out(out->free_mask, 4 * P, &d_mask); io.out(out->n_free, P, &d_n); }
     bool ok = true;
     if (!w.stats) ok = w.bufs.grow({{(void**)&w.stats, NF_STATS * sizeof(unsigned long long)}, {(void**)&w.table, NF_TABLE_BYTES}});
-    if (ok && need > w.io_bytes) { ok = w.bufs.grow({{(void**)&w.io, need}}); if (ok) w.io_bytes = need; }
+    if (ok) ok = io.reserve(w.bufs, &w.io, &w.io_bytes, io.need());
     if (!ok) { h->err = "ssf_navfoot_layers: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
-    const int8_t* d_state = dev ? state : (const int8_t*)w.io;
-    uint32_t* d_mask = dev ? out->free_mask : (out->free_mask ? (uint32_t*)(w.io + off_mask) : nullptr);
-    uint8_t* d_n = dev ? out->n_free : (out->n_free ? (uint8_t*)(w.io + off_n) : nullptr);
 
     TimerScope ts(h);
     if (!kept) {
@@ -268,7 +266,7 @@ int ssf_navfoot_layers(ssf_handle* h, const ssf_navfoot_params* p, const int8_t*
         HCK(hipMemcpyAsync((unsigned char*)w.table + NF_MASK_WORDS * 8, row_bins, (size_t)nrow * 4, hipMemcpyHostToDevice, st));
         std::memcpy(w.key, key, sizeof(key)); w.reach = sp.reach; w.cells = sp.cells; w.table_valid = true;
     }
-    if (!dev) HCK(hipMemcpyAsync(w.io, state, P, hipMemcpyHostToDevice, st));
+    HCK(io.copy_in(st));
     HCK(hipMemsetAsync(w.stats, 0, NF_STATS * sizeof(unsigned long long), st));
     {
         ScopedKernel sk("navfoot_layers", st);
@@ -279,8 +277,7 @@ int ssf_navfoot_layers(ssf_handle* h, const ssf_navfoot_params* p, const int8_t*
     HCK(hipGetLastError());
     unsigned long long s[NF_STATS];
     HCK(hipMemcpyAsync(s, w.stats, sizeof(s), hipMemcpyDeviceToHost, st));
-    if (!dev && out->free_mask) HCK(hipMemcpyAsync(out->free_mask, d_mask, 4 * P, hipMemcpyDeviceToHost, st));
-    if (!dev && out->n_free) HCK(hipMemcpyAsync(out->n_free, d_n, P, hipMemcpyDeviceToHost, st));
+    HCK(io.copy_out(st));
     { int rc = sync_collect(h); if (rc) return rc; }
     if (stats) {
         stats->cells_clear = (int64_t)s[NF_CLEAR]; stats->cells_all = (int64_t)s[NF_ALL]; stats->cells_some = (int64_t)s[NF_SOME];

@@ -345,25 +345,23 @@ int ssf_navfrontier_regions(ssf_handle* h, const ssf_navfrontier_params* p, cons
     const NavFrontierRule rule{p->connectivity == 8, p->traversable_only != 0, p->min_dist2, p->min_cells, p->reachable_only != 0, p->max_regions};
     const size_t P = (size_t)G.W * G.H, nb = (P + 255) / 256;
     const bool dev = p->on_device != 0, use_dist2 = rule.trav_only != 0;
-    // the working buffers
+    // the working buffers; host arrays are staged on the device
     NavFrontierWs& w = h->navfrontier;
+    const int8_t* d_state = state; const int32_t* d_dist2 = use_dist2 ? dist2 : nullptr; const uint32_t* d_cost = cost;
+    StagedIo io;
+    if (!dev) { io.in(state, P, &d_state); io.in(d_dist2, 4 * P, &d_dist2); io.in(cost, 4 * P, &d_cost); }
     bool ok = true;
     if (!w.stats) ok = w.bufs.grow({{(void**)&w.stats, NF_STATS * sizeof(unsigned long long)}, {&w.table, 65536 * sizeof(ssf_navfrontier_region)}});
     if (ok && P > w.cells) {
-        ok = w.bufs.grow({{(void**)&w.state, P}, {(void**)&w.dist2, 4 * P}, {(void**)&w.cost, 4 * P}, {(void**)&w.parent, 4 * P}, {(void**)&w.label, 4 * P},
-                          {(void**)&w.cell_blocks, (nb + 1) * sizeof(uint32_t)}});
+        ok = w.bufs.grow({{(void**)&w.parent, 4 * P}, {(void**)&w.label, 4 * P}, {(void**)&w.cell_blocks, (nb + 1) * sizeof(uint32_t)}});
         if (ok) w.cells = P;
     }
+    if (ok) ok = io.reserve(w.bufs, &w.io, &w.io_bytes, io.need());
     if (!ok) { h->err = "ssf_navfrontier_regions: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
 
     hipStream_t st = h->stream;
     TimerScope ts(h);
-    const int8_t* d_state = state; const int32_t* d_dist2 = use_dist2 ? dist2 : nullptr; const uint32_t* d_cost = cost;
-    if (!dev) {
-        HCK(hipMemcpyAsync(w.state, state, P, hipMemcpyHostToDevice, st)); d_state = w.state;
-        if (use_dist2) { HCK(hipMemcpyAsync(w.dist2, dist2, 4 * P, hipMemcpyHostToDevice, st)); d_dist2 = w.dist2; }
-        if (cost) { HCK(hipMemcpyAsync(w.cost, cost, 4 * P, hipMemcpyHostToDevice, st)); d_cost = w.cost; }
-    }
+    HCK(io.copy_in(st));
     HCK(hipMemsetAsync(w.stats, 0, NF_STATS * sizeof(unsigned long long), st));
     launch_navfrontier_label(st, G, rule, d_state, d_dist2, w.parent, w.label, w.stats);
     HCK(hipGetLastError());

@@ -250,17 +250,17 @@ int ssf_navmem_update(ssf_handle* h, const ssf_navmem_params* p, const void* dep
     { int rc = navlive_frames(h, &g, p, p->res * 0.5f, G, cam, gpose); if (rc) return rc; }
     const NavMemSlices S{p->floor_max, slice_h, p->slices - 1};
 
-    // the arrays: host ones are staged on the device, the inputs in one buffer and the outputs in another
+    // the arrays: host ones are staged on the device
     const void* d_depth = depth; const uint8_t* d_mask = p->mask_mode ? mask : nullptr;
     NavMemCellsIo c{};
     c.state_in = state_in; c.marks_in = L.marks; c.mark_tick_in = L.mark_tick; c.seen_tick_in = L.seen_tick;
     c.marks = out->marks; c.mark_tick = out->mark_tick; c.seen_tick = out->seen_tick; c.out_hits = out->live_hits; c.out_hit_bits = out->hit_bits;
     c.out_seen_bits = out->seen_bits; c.state = out->state;
     int32_t* o_dist2 = out->dist2;
-    StagedIo in, io;
-    if (!fdev) { in.in(depth, bpp * npix, &d_depth); in.in(d_mask, npix, &d_mask); }
+    StagedIo io;
+    if (!fdev) { io.in(depth, bpp * npix, &d_depth); io.in(d_mask, npix, &d_mask); }
     if (!dev) {
-        in.in(state_in, P, &c.state_in); in.in(L.marks, 4 * P, &c.marks_in); in.in(L.mark_tick, 4 * P, &c.mark_tick_in); in.in(L.seen_tick, 4 * P, &c.seen_tick_in);
+        io.in(state_in, P, &c.state_in); io.in(L.marks, 4 * P, &c.marks_in); io.in(L.mark_tick, 4 * P, &c.mark_tick_in); io.in(L.seen_tick, 4 * P, &c.seen_tick_in);
         io.out(out->marks, 4 * P, &c.marks); io.out(out->mark_tick, 4 * P, &c.mark_tick); io.out(out->seen_tick, 4 * P, &c.seen_tick);
         io.out(out->live_hits, 4 * P, &c.out_hits); io.out(out->hit_bits, 4 * P, &c.out_hit_bits); io.out(out->seen_bits, 4 * P, &c.out_seen_bits);
         io.out(out->state, P, &c.state); io.out(out->dist2, 4 * P, &o_dist2);
@@ -272,14 +272,13 @@ int ssf_navmem_update(ssf_handle* h, const ssf_navmem_params* p, const void* dep
         ok = w.bufs.grow({{(void**)&w.hits, 4 * P}, {(void**)&w.hit_bits, 4 * P}, {(void**)&w.seen_bits, 4 * P}, {(void**)&w.colg, 2 * P}, {(void**)&w.state, P}});
         if (ok) w.cells = P;
     }
-    if (ok) ok = in.reserve(w.bufs, &w.img_in, &w.img_in_bytes, in.need());
     if (ok) ok = io.reserve(w.bufs, &w.img, &w.img_bytes, io.need());
     if (!ok) { h->err = "ssf_navmem_update: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
     c.hits = w.hits; c.hit_bits = w.hit_bits; c.seen_bits = w.seen_bits;
 
     hipStream_t st = h->stream;
     TimerScope ts(h);
-    HCK(in.copy_in(st));
+    HCK(io.copy_in(st));
     HCK(hipMemsetAsync(w.stats, 0, NM_STATS * NM_PAD * sizeof(unsigned long long), st));
     HCK(hipMemsetAsync(w.hits, 0, 4 * P, st));
     HCK(hipMemsetAsync(w.hit_bits, 0, 4 * P, st));

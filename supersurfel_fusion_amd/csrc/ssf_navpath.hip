@@ -244,33 +244,30 @@ int ssf_navpath_waypoints(ssf_handle* h, const ssf_navpath_params* p, const int8
     const int np = p->n_paths;
     const bool dev = p->on_device != 0;
     const size_t path_words = (size_t)np * (size_t)p->max_path * 2, wp_words = out->waypoints ? (size_t)np * (size_t)p->max_waypoints * 4 : 0;
-    // the working buffers
+    // the working buffers; the whole-array inputs of a host caller are staged on the device
     NavPathWs& w = h->navpath;
+    const int8_t* d_state = state; const int32_t* d_dist2 = dist2; const int32_t* d_path = path; const int32_t* d_len = path_len;
+    StagedIo io;
+    if (!dev) { io.in(state, P, &d_state); io.in(dist2, 4 * P, &d_dist2); io.in(path_len, 4 * (size_t)np, &d_len); }
     bool ok = true;
-    if (!w.stats) ok = w.bufs.grow({{(void**)&w.stats, NW_STATS * sizeof(unsigned long long)}, {(void**)&w.path_len, 4096 * sizeof(int32_t)},
-                                    {(void**)&w.status, 4096 * sizeof(int32_t)}, {(void**)&w.n_wp, 4096 * sizeof(int32_t)},
-                                    {(void**)&w.path_min, 4096 * sizeof(int32_t)}});
-    if (ok && P > w.cells) {
-        ok = w.bufs.grow({{(void**)&w.state, P}, {(void**)&w.dist2, 4 * P}, {(void**)&w.pk, 4 * P}});
-        if (ok) w.cells = P;
-    }
+    if (!w.stats) ok = w.bufs.grow({{(void**)&w.stats, NW_STATS * sizeof(unsigned long long)}, {(void**)&w.status, 4096 * sizeof(int32_t)},
+                                    {(void**)&w.n_wp, 4096 * sizeof(int32_t)}, {(void**)&w.path_min, 4096 * sizeof(int32_t)}});
+    if (ok && P > w.cells) { ok = w.bufs.grow({{(void**)&w.pk, 4 * P}}); if (ok) w.cells = P; }
+    if (ok) ok = io.reserve(w.bufs, &w.io, &w.io_bytes, io.need());
     if (ok && !dev && path_words > w.path_words) { ok = w.bufs.grow({{(void**)&w.path, path_words * sizeof(int32_t)}}); if (ok) w.path_words = path_words; }
     if (ok && !dev && wp_words > w.wp_words) { ok = w.bufs.grow({{(void**)&w.wp, wp_words * sizeof(int32_t)}}); if (ok) w.wp_words = wp_words; }
     if (!ok) { h->err = "ssf_navpath_waypoints: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
 
     hipStream_t st = h->stream;
     TimerScope ts(h);
-    const int8_t* d_state = state; const int32_t* d_dist2 = dist2; const int32_t* d_path = path; const int32_t* d_len = path_len;
+    HCK(io.copy_in(st));
     if (!dev) {
-        HCK(hipMemcpyAsync(w.state, state, P, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(w.dist2, dist2, 4 * P, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(w.path_len, path_len, 4 * (size_t)np, hipMemcpyHostToDevice, st));
         for (int i = 0; i < np; i++) {                                // entries past path_len are not read: each path's cells, no more
             const int L = path_len[i];
             if (L > 0 && L <= p->max_path)
                 HCK(hipMemcpyAsync(w.path + (size_t)i * p->max_path * 2, path + (size_t)i * p->max_path * 2, 8 * (size_t)L, hipMemcpyHostToDevice, st));
         }
-        d_state = w.state; d_dist2 = w.dist2; d_path = w.path; d_len = w.path_len;
+        d_path = w.path;
     }
     HCK(hipMemsetAsync(w.stats, 0, NW_STATS * sizeof(unsigned long long), st));
     launch_navpath_pack(st, P, rule, d_state, d_dist2, w.pk);

@@ -253,23 +253,22 @@ int ssf_navplan_field(ssf_handle* h, const ssf_navplan_params* p, const int8_t* 
     const int ns = p->n_starts;
     const bool dev = p->on_device != 0, want_path = out->path && ns > 0 && p->max_path > 0;
     const size_t path_words = want_path ? (size_t)ns * (size_t)p->max_path * 2 : 0;
-    // the working buffers
+    // the working buffers; a host grid is staged on the device
     NavPlanWs& w = h->navplan;
+    const int8_t* d_state = state; const int32_t* d_dist2 = dist2;
+    StagedIo io;
+    if (!dev) { io.in(state, P, &d_state); io.in(dist2, 4 * P, &d_dist2); }
     bool ok = navfield_reserve(w, NP_STATS, 2, tiles, dev ? 0 : path_words);
     if (ok && P > w.cells) {
-        ok = w.bufs.grow({{(void**)&w.state, P}, {(void**)&w.dist2, 4 * P}, {(void**)&w.pk, 4 * P}, {(void**)&w.cost, 4 * P}, {(void**)&w.frontier, P}});
+        ok = w.bufs.grow({{(void**)&w.pk, 4 * P}, {(void**)&w.cost, 4 * P}, {(void**)&w.frontier, P}});
         if (ok) w.cells = P;
     }
+    if (ok) ok = io.reserve(w.bufs, &w.io, &w.io_bytes, io.need());
     if (!ok) { h->err = "ssf_navplan_field: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
 
     hipStream_t st = h->stream;
     TimerScope ts(h);
-    const int8_t* d_state = state; const int32_t* d_dist2 = dist2;
-    if (!dev) {
-        HCK(hipMemcpyAsync(w.state, state, P, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(w.dist2, dist2, 4 * P, hipMemcpyHostToDevice, st));
-        d_state = w.state; d_dist2 = w.dist2;
-    }
+    HCK(io.copy_in(st));
     if (p->n_goals > 0) HCK(hipMemcpyAsync(w.goals, p->goals, 2 * sizeof(int32_t) * (size_t)p->n_goals, hipMemcpyHostToDevice, st));
     if (ns > 0) HCK(hipMemcpyAsync(w.starts, p->starts, 2 * sizeof(int32_t) * (size_t)ns, hipMemcpyHostToDevice, st));
     HCK(hipMemsetAsync(w.stats, 0, NP_STATS * sizeof(unsigned long long), st));

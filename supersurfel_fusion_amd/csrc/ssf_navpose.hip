@@ -322,25 +322,25 @@ int ssf_navpose_field(ssf_handle* h, const ssf_navpose_params* p, const uint32_t
     const int ns = p->n_starts;
     const bool dev = p->on_device != 0, want_path = out->path && ns > 0 && p->max_path > 0;
     const size_t path_words = want_path ? (size_t)ns * (size_t)p->max_path * 3 : 0;
-    // the working buffers; a call with device arrays relaxes the caller's field and projects into the caller's arrays
+    // the working buffers; a call with device arrays relaxes the caller's field and projects into the caller's arrays, a host grid
+    // is staged on the device
     NavPoseWs& w = h->navpose;
     const bool own_cost = !(dev && out->cost);
+    const uint32_t* d_mask = free_mask; const int32_t* d_dist2 = dist2;
+    StagedIo io;
+    if (!dev) { io.in(free_mask, 4 * P, &d_mask); io.in(dist2, 4 * P, &d_dist2); }
     bool ok = navfield_reserve(w, NQ_STATS, 3, tiles, dev ? 0 : path_words);
     if (ok && P > w.cells) {
-        ok = w.bufs.grow({{(void**)&w.mask, 4 * P}, {(void**)&w.dist2, 4 * P}, {(void**)&w.pk, 8 * P}, {(void**)&w.cell_cost, 4 * P}, {(void**)&w.cell_bin, P}});
+        ok = w.bufs.grow({{(void**)&w.pk, 8 * P}, {(void**)&w.cell_cost, 4 * P}, {(void**)&w.cell_bin, P}});
         if (ok) w.cells = P;
     }
     if (ok && own_cost && N > w.states) { ok = w.bufs.grow({{(void**)&w.cost, 4 * N}}); if (ok) w.states = N; }
+    if (ok) ok = io.reserve(w.bufs, &w.io, &w.io_bytes, io.need());
     if (!ok) { h->err = "ssf_navpose_field: allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
 
     hipStream_t st = h->stream;
     TimerScope ts(h);
-    const uint32_t* d_mask = free_mask; const int32_t* d_dist2 = dist2;
-    if (!dev) {
-        HCK(hipMemcpyAsync(w.mask, free_mask, 4 * P, hipMemcpyHostToDevice, st));
-        HCK(hipMemcpyAsync(w.dist2, dist2, 4 * P, hipMemcpyHostToDevice, st));
-        d_mask = w.mask; d_dist2 = w.dist2;
-    }
+    HCK(io.copy_in(st));
     uint32_t* d_cost = own_cost ? w.cost : out->cost;
     uint32_t* d_cell_cost = dev && out->cell_cost ? out->cell_cost : w.cell_cost;
     uint8_t* d_cell_bin = dev && out->cell_bin ? out->cell_bin : w.cell_bin;

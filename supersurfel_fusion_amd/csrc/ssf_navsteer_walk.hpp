@@ -424,37 +424,26 @@ int navsteer_call(ssf_handle* h, const char* who, const ssf_navsteer_params* p, 
     const uint32_t* use_cost = r.wc > 0 ? cost : nullptr;
     const int32_t* use_targets = r.wt > 0 ? targets : nullptr;
 
-    // the arrays of a call with host pointers, each at a 256-byte boundary of one staging buffer.  best_traj goes in as well as out:
-    // entries past best_len keep what the caller had there
-    struct Item { const void* host; size_t bytes; void** arg; bool in, outp; size_t off; };
+    // the arrays of a call with host pointers are staged on the device.  best_traj goes in as well as out: entries past best_len
+    // keep what the caller had there
     const void* d_grid = grid; const int32_t* d_dist2 = dist2; const uint32_t* d_cost = use_cost; const int32_t* d_poses = poses;
     const int32_t* d_targets = use_targets;
     ssf_navsteer_out o{};
     if (out) o = *out;
     if (mv) { mv->d_movers = mv->movers; mv->o = ssf_navdyn_out{}; if (mv->out) mv->o = *mv->out; }
-    Item items[21];
-    int n_items = 0;
-    size_t need = 0;
+    StagedIo io;
     if (!dev) {
-        auto add = [&](const void* host, size_t bytes, void** arg, bool in, bool outp) {
-            if (!host) return;
-            items[n_items++] = Item{host, bytes, arg, in, outp, need};
-            need += (bytes + 255) & ~(size_t)255;
-        };
-        add(grid, grid_bytes * P, (void**)&d_grid, true, false); add(dist2, 4 * P, (void**)&d_dist2, true, false);
-        add(use_cost, 4 * P, (void**)&d_cost, true, false);
-        add(poses, 12 * np, (void**)&d_poses, true, false); add(use_targets, 8 * np, (void**)&d_targets, true, false);
-        add(o.best, 4 * np, (void**)&o.best, false, true); add(o.best_cmd, 8 * np, (void**)&o.best_cmd, false, true);
-        add(o.best_score, 8 * np, (void**)&o.best_score, false, true); add(o.n_admissible, 4 * np, (void**)&o.n_admissible, false, true);
-        add(o.pose_status, 4 * np, (void**)&o.pose_status, false, true); add(o.best_len, 4 * np, (void**)&o.best_len, false, true);
-        add(o.best_traj, 4 * traj, (void**)&o.best_traj, true, true);
-        add(o.cand_free, 4 * NK, (void**)&o.cand_free, false, true); add(o.cand_min_d, 4 * NK, (void**)&o.cand_min_d, false, true);
-        add(o.cand_end, 12 * NK, (void**)&o.cand_end, false, true); add(o.cand_end_cost, 4 * NK, (void**)&o.cand_end_cost, false, true);
-        add(o.cand_score, 8 * NK, (void**)&o.cand_score, false, true);
+        io.in(grid, grid_bytes * P, &d_grid); io.in(dist2, 4 * P, &d_dist2); io.in(use_cost, 4 * P, &d_cost);
+        io.in(poses, 12 * np, &d_poses); io.in(use_targets, 8 * np, &d_targets);
+        io.out(o.best, 4 * np, &o.best); io.out(o.best_cmd, 8 * np, &o.best_cmd); io.out(o.best_score, 8 * np, &o.best_score);
+        io.out(o.n_admissible, 4 * np, &o.n_admissible); io.out(o.pose_status, 4 * np, &o.pose_status); io.out(o.best_len, 4 * np, &o.best_len);
+        io.inout(o.best_traj, 4 * traj, &o.best_traj);
+        io.out(o.cand_free, 4 * NK, &o.cand_free); io.out(o.cand_min_d, 4 * NK, &o.cand_min_d); io.out(o.cand_end, 12 * NK, &o.cand_end);
+        io.out(o.cand_end_cost, 4 * NK, &o.cand_end_cost); io.out(o.cand_score, 8 * NK, &o.cand_score);
         if (mv) {
-            add(mv->movers, 24 * (size_t)mv->p->n_movers, (void**)&mv->d_movers, true, false);
-            add(mv->o.cand_hit, 4 * NK, (void**)&mv->o.cand_hit, false, true); add(mv->o.cand_min_gap, 4 * NK, (void**)&mv->o.cand_min_gap, false, true);
-            add(mv->o.best_min_gap, 4 * np, (void**)&mv->o.best_min_gap, false, true);
+            io.in(mv->movers, 24 * (size_t)mv->p->n_movers, &mv->d_movers);
+            io.out(mv->o.cand_hit, 4 * NK, &mv->o.cand_hit); io.out(mv->o.cand_min_gap, 4 * NK, &mv->o.cand_min_gap);
+            io.out(mv->o.best_min_gap, 4 * np, &mv->o.best_min_gap);
         }
     }
     // the working buffers
@@ -465,9 +454,8 @@ int navsteer_call(ssf_handle* h, const char* who, const ssf_navsteer_params* p, 
                           {(void**)&w.n_adm, 4096 * sizeof(int32_t)}, {(void**)&w.dirs, NS_DIRS * sizeof(uint32_t)}});
     }
     if (ok) ok = run.reserve(P);
-    if (ok && need > w.io_bytes) { ok = w.bufs.grow({{(void**)&w.io, need}}); if (ok) w.io_bytes = need; }
+    if (ok) ok = io.reserve(w.bufs, &w.io, &w.io_bytes, io.need());
     if (!ok) { h->err = std::string(who) + ": allocation of the working buffers failed"; return SSF_ERR_DEVICE; }
-    for (int k = 0; k < n_items; k++) *items[k].arg = w.io + items[k].off;
 
     hipStream_t st = h->stream;
     TimerScope ts(h);
@@ -475,8 +463,7 @@ int navsteer_call(ssf_handle* h, const char* who, const ssf_navsteer_params* p, 
         HCK(hipMemcpyAsync(w.dirs, navsteer_dirs().packed, NS_DIRS * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         w.dirs_sent = true;
     }
-    for (int k = 0; k < n_items; k++)
-        if (const Item& it = items[k]; it.in) HCK(hipMemcpyAsync(*it.arg, it.host, it.bytes, hipMemcpyHostToDevice, st));
+    HCK(io.copy_in(st));
     // (the sums of a call without movers are the eight words they were: its fill and its copy are the ones the older libraries issue)
     const size_t n_sums = mv ? NS_STATS : NS_HOOKED;
     HCK(hipMemsetAsync(w.stats, 0, n_sums * sizeof(unsigned long long), st));
@@ -487,8 +474,7 @@ int navsteer_call(ssf_handle* h, const char* who, const ssf_navsteer_params* p, 
     { int rc = run.launch(st, r, d_grid, d_dist2, d_cost, d_poses, d_targets, w, cand, pick); if (rc) return rc; }
     unsigned long long s[NS_STATS] = {};
     HCK(hipMemcpyAsync(s, w.stats, n_sums * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    for (int k = 0; k < n_items; k++)
-        if (const Item& it = items[k]; it.outp) HCK(hipMemcpyAsync(const_cast<void*>(it.host), *it.arg, it.bytes, hipMemcpyDeviceToHost, st));
+    HCK(io.copy_out(st));
     { int rc = sync_collect(h); if (rc) return rc; }
     if (stats) {
         stats->poses_ok = (int64_t)s[NS_OK]; stats->poses_blocked = (int64_t)s[NS_BLOCKED]; stats->poses_stuck = (int64_t)s[NS_STUCK];

@@ -8,7 +8,7 @@ namespace ssf {
 // Items in the order they were added.  An item with a host array starts on a multiple of 256 bytes behind the one before it; an
 // item without one (a NULL output) takes no space.  total = the bytes the buffer needs.
 struct StageLayout {
-    enum { MAX_ITEMS = 8 };
+    enum { MAX_ITEMS = 24 };                                      // (the rollouts with movers declare 21)
     struct Item { const void* host; size_t bytes, off; };
     Item item[MAX_ITEMS];
     int n = 0;

@@ -17,7 +17,9 @@ struct Decl { bool present; size_t bytes; };
 
 static void check(const char* what, const std::vector<Decl>& decl) {
     static const char host_byte = 0;                        // any non-null address: the layout never reads through it
-    std::vector<unsigned char> buf(256 * (decl.size() + 1) + 4096);
+    size_t room = 0;                                        // the restatement's total: what a caller would allocate, and no more
+    for (const Decl& d : decl) room += d.present ? (d.bytes + 255) / 256 * 256 : 0;
+    std::vector<unsigned char> buf(room);
     ssf::StageLayout lay;
     for (size_t i = 0; i < decl.size(); i++) EXPECT(lay.add(decl[i].present ? &host_byte : nullptr, decl[i].bytes) == (int)i);
     EXPECT(lay.n == (int)decl.size());
@@ -29,6 +31,7 @@ static void check(const char* what, const std::vector<Decl>& decl) {
         if (!p) continue;
         const size_t off = (size_t)(p - buf.data());
         EXPECT(off % 256 == 0);
+        EXPECT(off == sum);                                 // the restatement: the aligned sizes of the present items before it
         EXPECT(off >= end_prev);                            // behind everything before it (the items come in order)
         EXPECT(off + decl[i].bytes <= lay.total);
         EXPECT(off + decl[i].bytes <= buf.size());
@@ -51,7 +54,21 @@ int main() {
     check("a null between two", {{true, 300}, {false, 300}, {true, 300}});
     check("an input, then outputs", {{true, 24 * 7}, {true, 4 * 7}, {false, 4 * 7}, {true, 12 * 7}, {false, 12 * 7}, {true, 12 * 7}});
     check("eight items", {{true, 12}, {true, 12}, {false, 8}, {true, 36}, {true, 24}, {false, 8}, {true, 4}, {true, 4}});
-    {   // a ninth item is refused and changes nothing
+    // more than eight: the 21 arrays of a rollouts call with movers on a 37 x 19 grid (703 cells), 5 poses, 35 candidates each and
+    // 9 steps, with cost, targets, three of the outputs and one of the movers' outputs NULL
+    {
+        const size_t P = 37 * 19, np = 5, NK = 5 * 35, traj = 5 * (9 + 1) * 3;
+        check("a rollouts call", {{true, P}, {true, 4 * P}, {false, 4 * P}, {true, 12 * np}, {false, 8 * np},
+                                  {true, 4 * np}, {true, 8 * np}, {false, 8 * np}, {true, 4 * np}, {true, 4 * np}, {true, 4 * np}, {true, 4 * traj},
+                                  {true, 4 * NK}, {false, 4 * NK}, {true, 12 * NK}, {false, 4 * NK}, {true, 8 * NK},
+                                  {true, 24 * 3}, {true, 4 * NK}, {false, 4 * NK}, {true, 4 * np}});
+    }
+    {
+        std::vector<Decl> all((size_t)ssf::StageLayout::MAX_ITEMS);
+        for (size_t i = 0; i < all.size(); i++) all[i] = Decl{i % 5 != 3, 100 * i + 1};
+        check("every item, every fifth NULL", all);
+    }
+    {   // one item more than MAX_ITEMS is refused and changes nothing
         const char* what = "full";
         static const char host_byte = 0;
         ssf::StageLayout lay;

@@ -471,6 +471,57 @@ def mixed_scene():
     return _with(dict(s, poses=poses, c=c), random_movers(78, 120, 10, 21, r_max=2500))
 
 
+def staging_scene(W, H, n_poses):
+    """the scene of the tests of a call's host arrays, for the four rollouts: a lattice of 21 candidates over 10 steps among three
+    movers on a W x H floor, with a cost, targets and the small body (on one cell: the point) at 8 bins.  From 8 x 8 cells on the floor is walled in, with a
+    pillar in the middle and one unknown cell; the first pose then faces the wall from two cells away, so that its winner stops
+    before the horizon, and the first mover stands in the way of the second pose"""
+    def make():
+        c = params(width=W, height=H, n_poses=n_poses, n_steps=10, n_v=3, n_w=7, v_min=0, v_step=384, w_min=-3072, w_step=1024, min_free_steps=1,
+                   brake_div=0, target_weight=1, mover_weight=3)
+        state = np.zeros((H, W), np.int8)
+        room = W >= 8 and H >= 8
+        if room:
+            state[0, :] = state[-1, :] = state[:, 0] = state[:, -1] = 100
+            state[H // 2 - 1:H // 2 + 1, W // 2:W // 2 + 2] = 100
+            state[H - 2, 1] = -1
+        dist2 = sr.clearance(state)
+        cost = sr.field(state, dist2, (W - 3, 2) if room else (0, 0), c)
+        rng = np.random.default_rng(40 + W + H)
+        poses = [sr.centre(2, H // 2, 32768), sr.centre(W // 4, H // 4 + 1, 0), sr.centre(W - 3, H - 3, 16384 + 65536), (-5, 700, 0)] if room else \
+                [sr.centre(0, 0, 0), (1023, 0, 16384), (0, 1023, 65535), (-1, 0, 0)]
+        while len(poses) < n_poses:
+            poses.append((int(rng.integers(0, W * SUB)), int(rng.integers(0, H * SUB)), int(rng.integers(-TURN, 2 * TURN))))
+        poses = np.array(poses[:n_poses], np.int32)
+        targets = np.stack([rng.integers(0, W * SUB, n_poses), rng.integers(0, H * SUB, n_poses)], axis=1).astype(np.int32)
+        x, y, _ = sr.centre(W // 4, H // 4 + 1) if room else (512, 900, 0)
+        movers = np.vstack([[(x + (3 * SUB if room else 0), y, -128 if room else 0, -64, 600, 8)], random_movers(W, H, 2, 41)])
+        foot = BODY if room else fr.POINT                               # (the body does not fit on a floor of one cell)
+        s = dict(_with(dict(state=state, dist2=dist2, cost=cost, poses=poses, targets=targets, c=c), movers), foot=foot, B=8)
+        s["layers"] = fr.layers(state, 0, foot, 8)                       # (what ssf_navfoot_layers makes of the floor: tests/test_navfoot_gpu.py)
+        s["free_mask"] = s["layers"]["free_mask"]
+        return s
+    return cached(("staging", W, H, n_poses), make)
+
+
+def staging_reference(W, H, n_poses, kind):
+    """the restatement's answer to staging_scene: kind 'disc' (navsteer_ref), 'foot' (navfoot_ref), 'dyn' or 'dyn foot' (this file)"""
+    def make():
+        s = staging_scene(W, H, n_poses)
+        if kind == "disc":
+            return sr.rollouts(s["state"], s["dist2"], s["cost"], s["poses"], s["targets"], steer_params(s["c"]))
+        if kind == "foot":
+            return fr.rollouts(s["free_mask"], s["B"], s["dist2"], s["cost"], s["poses"], s["targets"], steer_params(s["c"]))
+        return rollouts(s["free_mask"] if kind == "dyn foot" else s["state"], s["dist2"], s["cost"], s["poses"], s["targets"], s["movers"], s["c"],
+                        s["B"] if kind == "dyn foot" else None)
+    return cached(("staging want", W, H, n_poses, kind), make)
+
+
+def steer_params(c):
+    """c without the movers' two parameters: what the calls of ssf_navsteer.h and ssf_navfoot.h take"""
+    return {k: v for k, v in c.items() if k not in DYN_DEFAULTS}
+
+
 FOOT = (2048, 1536, 1024, 1024, 0)                                       # the footprint of "foot 37x53", with B = 16
 BODY = (1536, 512, 512, 512, 0)                                          # a smaller body, for the scenes that set B themselves
 DISC_CASES = ("1x1", "1x70 K297 one mover", "37x53 K512 64 movers 70 poses", "64x65 K297 T256", "97x33 K512 T1", "r 0 never hits",

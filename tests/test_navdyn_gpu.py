@@ -175,6 +175,67 @@ def test_one_footprint_output_alone_guard_bytes_and_two_calls_giving_the_same_by
         assert raws[0].tobytes() == raws[1].tobytes(), nm
 
 
+# ---- the staging of host arrays: the 21 arrays of a call with movers ----------------------------------------------------------------
+FILL = util.GUARD_WORD
+KINDS = ("dyn", "dyn foot")
+
+
+@pytest.mark.parametrize("w,h", [(37, 19), (1, 1)])
+@pytest.mark.parametrize("kind", KINDS)
+def test_host_arrays_whose_items_all_start_at_rounded_offsets(kind, w, h, fusion):
+    """703 cells and one cell: neither P nor 4 P is a multiple of 256, so every array behind the first sits at a rounded offset of the
+    staging buffer.  Host arrays, device pointers and the restatement agree on every output and exact stat"""
+    s, want = dr.staging_scene(w, h, 5), dr.staging_reference(w, h, 5, kind)
+    host, hs = util.rollouts_host(fusion, kind, s, dr.OUTPUTS)
+    dev, ds = util.rollouts_device(fusion, kind, s, dr.OUTPUTS)
+    util.rollouts_same(host, want, "host %d x %d" % (w, h), FILL)
+    util.rollouts_same(dev, want, "device %d x %d" % (w, h), FILL)
+    assert all(host[nm].tobytes() == dev[nm].tobytes() for nm in dr.OUTPUTS)
+    assert {k: hs[k] for k in dr.STATS} == {k: ds[k] for k in dr.STATS} == {k: want["stats"][k] for k in dr.STATS}
+    assert want["stats"]["hit_movers"] > 0 and (w == 1 or ((want["pose_status"] == 0).sum() >= 3 and want["stats"]["collided"] > 0))
+
+
+@pytest.mark.parametrize("name", dr.OUTPUTS)
+@pytest.mark.parametrize("kind", KINDS)
+def test_one_host_output_alone_between_guard_bytes(kind, name, fusion):
+    """37 x 19, host arrays: each of the 15 outputs on its own, all others NULL, equals the same array of the call that asks for all
+    of them, and the 256 bytes on either side of the caller's array are untouched"""
+    s = dr.staging_scene(37, 19, 5)
+    every, stats = dr.cached(("staging host", kind), lambda: util.rollouts_host(fusion, kind, s, dr.OUTPUTS))
+    util.rollouts_same(every, dr.staging_reference(37, 19, 5, kind), "every output", FILL)
+    alone, st = util.rollouts_host(fusion, kind, s, (name,))
+    assert alone[name].tobytes() == every[name].tobytes() and {k: st[k] for k in dr.STATS} == {k: stats[k] for k in dr.STATS}, name
+
+
+def test_best_traj_goes_in_as_well_as_out(fusion):
+    """host arrays: best_traj is staged in both directions, so the entries past best_len, which the kernel does not write, come back
+    as the caller's 0x5A5A5A5A and not as what the staging buffer held.  The first pose's winner stops at the wall after two steps"""
+    s, want = dr.staging_scene(37, 19, 5), dr.staging_reference(37, 19, 5, "dyn")
+    T1 = s["c"]["n_steps"] + 1
+    assert want["pose_status"][0] == 0 and 1 < want["best_len"][0] < T1 and (want["best_len"] == T1).any() and (want["best_len"] == 0).any()
+    util.rollouts_host(fusion, "dyn", s, ("cand_end",))                 # (the place of best_len and best_traj then holds other bytes)
+    got, _ = util.rollouts_host(fusion, "dyn", s, ("best_traj", "best_len"))
+    assert (got["best_len"] == want["best_len"]).all()
+    util.rollouts_same(got, want, "best_traj", FILL)
+    assert sum(int((got["best_traj"][q, n:] == FILL).sum()) for q, n in enumerate(want["best_len"])) == 3 * int((T1 - want["best_len"]).sum()) > 0
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_the_staging_buffer_grows_and_is_used_again(kind, dyn_lib):
+    """one handle: 8 x 8 with one pose, 37 x 19 with five, 8 x 8 with one again.  Each call gives what a handle that has made no
+    other call gives"""
+    f = handle(dyn_lib)
+    for w, h, n in ((8, 8, 1), (37, 19, 5), (8, 8, 1)):
+        s = dr.staging_scene(w, h, n)
+        got, gs = util.rollouts_host(f, kind, s, dr.OUTPUTS)
+        fresh = handle(dyn_lib)
+        want, ws = util.rollouts_host(fresh, kind, s, dr.OUTPUTS)
+        fresh.close()
+        assert all(got[nm].tobytes() == want[nm].tobytes() for nm in dr.OUTPUTS) and {k: gs[k] for k in dr.STATS} == {k: ws[k] for k in dr.STATS}, (w, h, n)
+        util.rollouts_same(got, dr.staging_reference(w, h, n, kind), (w, h, n), FILL)
+    f.close()
+
+
 def test_a_launch_with_movers_that_stages_some_windows_and_walks_the_others(fusion):
     """navsteer_ref.mixed_scene among ten movers: 1281 workgroups, of which one launch stages the windows of up to 4056 cells in LDS and
     walks the others in the grid; both kinds test their steps against the list in LDS"""

@@ -5,6 +5,7 @@ device pointers fed by the overlay and the plan, through nav_live_foot_steer, an
 import numpy as np
 import pytest
 
+import navdyn_ref as dr
 import navfoot_ref as fr
 import navlive_ref as lr
 import navplan_ref as pr
@@ -281,6 +282,74 @@ def test_two_chunks_and_one_lane_and_300_poses(fusion):
     assert s["candidates"] == 300 * 257 and s["poses_ok"] > 100 and s["poses_blocked"] > 10 and s["collided"] > 0 and (got["best"] > 0).any()
     assert s["windows_global"] == 2 * (s["poses_ok"] + s["poses_stuck"])
     assert got["pose_status"][4] == 1 and got["pose_status"][5] == 1 and got["pose_status"][6] == 0 and got["pose_status"][7] == 0
+
+
+# ---- the staging of host arrays ----------------------------------------------------------------------------------------------------
+FILL = util.GUARD_WORD
+
+
+def layers_host(f, s, names):
+    """ssf_navfoot_layers on staging_scene's floor with host arrays, the outputs `names` alone between guard bytes: (name -> array, stats)"""
+    h, w = s["state"].shape
+    out = {nm: util.guarded((h, w), np.uint32 if nm == "free_mask" else np.uint8) for nm in names}
+    ptr = lambda nm: binding._ptr(out[nm][0]) if nm in out else None
+    stats = f._navfoot_layers(f._navfoot_params(False, w, h, foot_kw(s["foot"], s["B"])), binding._ptr(s["state"]), ptr("free_mask"), ptr("n_free"))
+    assert all(intact() for _, intact in out.values()), names
+    return {nm: a for nm, (a, _) in out.items()}, stats
+
+
+@pytest.mark.parametrize("w,h", [(37, 19), (1, 1)])
+def test_host_arrays_whose_items_all_start_at_rounded_offsets(w, h, fusion):
+    """703 cells and one cell: neither P nor 4 P is a multiple of 256, so every array behind the first sits at a rounded offset of the
+    staging buffer.  Host arrays, device pointers and the restatement agree, for the layers and for the rollouts over them"""
+    import torch
+    s = dr.staging_scene(w, h, 5)
+    want = s["layers"]
+    got, stats = layers_host(fusion, s, ("free_mask", "n_free"))
+    d_mask, d_n = torch.zeros((h, w), dtype=torch.int32, device="cuda"), torch.zeros((h, w), dtype=torch.uint8, device="cuda")
+    dev_stats = fusion.nav_foot_device(torch.from_numpy(s["state"]).to("cuda"), w, h, free_mask=d_mask, n_free=d_n, **foot_kw(s["foot"], s["B"]))
+    for nm, d in (("free_mask", d_mask.cpu().numpy().view(np.uint32)), ("n_free", d_n.cpu().numpy())):
+        assert got[nm].dtype == want[nm].dtype and (got[nm] == want[nm]).all() and (d == want[nm]).all(), (w, h, nm)
+    assert stats == dev_stats == want["stats"] and (w == 1 or want["stats"]["cells_some"] > 0)
+    want = dr.staging_reference(w, h, 5, "foot")
+    host, hs = util.rollouts_host(fusion, "foot", s, sr.OUTPUTS)
+    dev, ds = util.rollouts_device(fusion, "foot", s, sr.OUTPUTS)
+    util.rollouts_same(host, want, "host %d x %d" % (w, h), FILL)
+    util.rollouts_same(dev, want, "device %d x %d" % (w, h), FILL)
+    assert all(host[nm].tobytes() == dev[nm].tobytes() for nm in sr.OUTPUTS)
+    assert {k: hs[k] for k in sr.STATS} == {k: ds[k] for k in sr.STATS} == {k: want["stats"][k] for k in sr.STATS}
+    assert w == 1 or ((want["pose_status"] == 0).sum() >= 3 and want["stats"]["collided"] > 0 and (want["pose_status"] == 1).any())
+
+
+@pytest.mark.parametrize("name", ("free_mask", "n_free") + sr.OUTPUTS)
+def test_one_host_output_alone_between_guard_bytes(name, fusion):
+    """37 x 19, host arrays: every output of the layers and of the rollouts on its own, all others NULL, equals the same array of the
+    call that asks for all of them, and the 256 bytes on either side of the caller's array are untouched"""
+    s = dr.staging_scene(37, 19, 5)
+    if name in ("free_mask", "n_free"):
+        alone, st = layers_host(fusion, s, (name,))
+        assert (alone[name] == s["layers"][name]).all() and st == s["layers"]["stats"]
+        return
+    every, stats = dr.cached(("staging host", "foot"), lambda: util.rollouts_host(fusion, "foot", s, sr.OUTPUTS))
+    util.rollouts_same(every, dr.staging_reference(37, 19, 5, "foot"), "every output", FILL)
+    alone, st = util.rollouts_host(fusion, "foot", s, (name,))
+    assert alone[name].tobytes() == every[name].tobytes() and {k: st[k] for k in sr.STATS} == {k: stats[k] for k in sr.STATS}, name
+
+
+def test_the_staging_buffers_grow_and_are_used_again(foot_lib):
+    """one handle: 8 x 8 with one pose, 37 x 19 with five, 8 x 8 with one again, the layers and the rollouts.  Each call gives what a
+    handle that has made no other call gives"""
+    f = handle(foot_lib)
+    for w, h, n in ((8, 8, 1), (37, 19, 5), (8, 8, 1)):
+        s = dr.staging_scene(w, h, n)
+        fresh = handle(foot_lib)
+        (lay, ls), (want, ws) = layers_host(f, s, ("free_mask", "n_free")), layers_host(fresh, s, ("free_mask", "n_free"))
+        assert all(lay[nm].tobytes() == want[nm].tobytes() == s["layers"][nm].tobytes() for nm in lay) and ls == ws == s["layers"]["stats"], (w, h, n)
+        (got, gs), (want, ws) = util.rollouts_host(f, "foot", s, sr.OUTPUTS), util.rollouts_host(fresh, "foot", s, sr.OUTPUTS)
+        fresh.close()
+        assert all(got[nm].tobytes() == want[nm].tobytes() for nm in sr.OUTPUTS) and {k: gs[k] for k in sr.STATS} == {k: ws[k] for k in sr.STATS}, (w, h, n)
+        util.rollouts_same(got, dr.staging_reference(w, h, n, "foot"), (w, h, n), FILL)
+    f.close()
 
 
 # ---- the chain -------------------------------------------------------------------------------------------------------------------------

@@ -283,6 +283,96 @@ def test_device_tensors_give_the_same_bits(fusion):
     assert (s_dev.cpu().numpy() == state).all() and (c_dev.cpu().numpy().view(np.uint32) == cost).all()      # the inputs are read only
 
 
+# ---- the staging of host arrays ------------------------------------------------------------------------------------------------
+FILL = util.GUARD_WORD
+OUTPUTS = ("region", "regions", "order")
+_STAGING = {}
+
+
+def staging_case(h, w):
+    """dict(state, dist2, cost, kw, want): a random grid and cost field under every filter, with a gain; the restatement's answer,
+    computed once and shared"""
+    if (h, w) not in _STAGING:
+        state, dist2 = fr.random_grid(h, w, 300 + h + w)
+        cost = fr.random_cost(h, w, 11 + h)
+        kw = dict(min_cells=2, reachable_only=1, traversable_only=1, min_dist2=2, gain_radius=3, gain_weight=2, max_regions=64)
+        _STAGING[h, w] = dict(state=state, dist2=dist2, cost=cost, kw=kw, want=fr.frontiers(state, dist2, cost, **kw))
+    return _STAGING[h, w]
+
+
+def frontiers_host(f, c, names):
+    """ssf_navfrontier_regions with host arrays, the outputs `names` alone, each between guard bytes and filled with them: (name ->
+    array, stats)"""
+    C = binding.C
+    (h, w), n = c["state"].shape, c["kw"]["max_regions"]
+    shapes = dict(region=((h, w), np.int32), regions=((n,), binding.NAVFRONTIER_REGION_DTYPE), order=((n,), np.int32))
+    out = {nm: util.guarded(*shapes[nm]) for nm in names}
+    p, st = f._navfrontier_params(False, w, h, c["kw"]), binding.SsfNavFrontierStats()
+    o = binding.SsfNavFrontierOut(*[binding._ptr(out[nm][0]) if nm in out else None for nm in OUTPUTS])
+    f._ck(f.L.lib.ssf_navfrontier_regions(f.h, C.byref(p), binding._ptr(c["state"]), binding._ptr(c["dist2"]), binding._ptr(c["cost"]), C.byref(o), C.byref(st)),
+          "ssf_navfrontier_regions")
+    assert all(intact() for _, intact in out.values()), names
+    return {nm: a for nm, (a, _) in out.items()}, st.as_dict()
+
+
+def frontiers_same(got, stats, want, what):
+    """every array of got equals the restatement's; the table and the order up to regions_written, and past it they hold the fill"""
+    k = want["stats"]["regions_written"]
+    cut = {nm: (a if nm == "region" else a[:k]) for nm, a in got.items()}
+    if "region" in cut:
+        assert (cut["region"] == want["region"]).all(), what
+    if "regions" in cut:
+        table = fr.as_records(want["regions"], binding.NAVFRONTIER_REGION_DTYPE)
+        assert len(table) == k and all((cut["regions"][nm] == table[nm]).all() for nm in fr.FIELDS), what
+        assert (got["regions"][k:].view(np.uint8) == util.GUARD_FILL).all(), what
+    if "order" in cut:
+        assert (cut["order"] == want["order"]).all() and (got["order"][k:] == FILL).all(), what
+    assert {nm: stats[nm] for nm in fr.STATS} == {nm: want["stats"][nm] for nm in fr.STATS}, what
+
+
+@pytest.mark.parametrize("h,w", [(19, 37), (1, 1)])
+def test_host_arrays_whose_items_all_start_at_rounded_offsets(h, w, fusion):
+    """703 cells and one cell: neither P nor 4 P is a multiple of 256, so dist2 and cost sit at rounded offsets of the staging buffer.
+    Host arrays, device pointers and the restatement agree"""
+    import torch
+    c = staging_case(h, w)
+    host, hs = frontiers_host(fusion, c, OUTPUTS)
+    frontiers_same(host, hs, c["want"], "host %d x %d" % (h, w))
+    region = torch.full((h, w), -7, dtype=torch.int32, device="cuda")
+    dev = fusion.nav_frontiers_device(torch.from_numpy(c["state"]).to("cuda"), w, h, torch.from_numpy(c["dist2"]).to("cuda"),
+                                      torch.from_numpy(c["cost"].view(np.int32)).to("cuda"), region, **c["kw"])
+    k = hs["regions_written"]
+    assert (region.cpu().numpy() == host["region"]).all() and dev["regions"].tobytes() == host["regions"][:k].tobytes() and (dev["order"] == host["order"][:k]).all()
+    assert {nm: dev["stats"][nm] for nm in fr.STATS} == {nm: hs[nm] for nm in fr.STATS}
+    assert h == 1 or (k >= 2 and c["want"]["stats"]["regions_small"] + c["want"]["stats"]["regions_unreached"] >= 1 and (c["want"]["region"] >= 0).any())
+
+
+@pytest.mark.parametrize("name", OUTPUTS)
+def test_one_host_output_alone_between_guard_bytes(name, fusion):
+    """19 x 37, host arrays: every output on its own, all others NULL, equals the same array of the call that asks for all three, and
+    the 256 bytes on either side of the caller's array are untouched"""
+    c = staging_case(19, 37)
+    if "every" not in c:
+        c["every"] = frontiers_host(fusion, c, OUTPUTS)
+    every, stats = c["every"]
+    frontiers_same(every, stats, c["want"], "every output")
+    alone, st = frontiers_host(fusion, c, (name,))
+    assert alone[name].tobytes() == every[name].tobytes() and {k: st[k] for k in fr.STATS} == {k: stats[k] for k in fr.STATS}, name
+
+
+def test_the_staging_buffer_grows_and_is_used_again(explore_lib):
+    """one handle: 8 x 8, 19 x 37, 8 x 8 again.  Each call gives what a handle that has made no other call gives"""
+    f = handle(explore_lib)
+    for h, w in ((8, 8), (19, 37), (8, 8)):
+        c = staging_case(h, w)
+        fresh = handle(explore_lib)
+        (got, gs), (want, ws) = frontiers_host(f, c, OUTPUTS), frontiers_host(fresh, c, OUTPUTS)
+        fresh.close()
+        assert all(got[nm].tobytes() == want[nm].tobytes() for nm in got) and {k: gs[k] for k in fr.STATS} == {k: ws[k] for k in fr.STATS}, (h, w)
+        frontiers_same(got, gs, c["want"], (h, w))
+    f.close()
+
+
 # ---- where to go next ----------------------------------------------------------------------------------------------------------------
 def test_nav_explore_equals_the_three_reference_calls_chained(fusion):
     state, dist2, robot = fr.room()

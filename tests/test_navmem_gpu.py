@@ -420,6 +420,99 @@ def test_device_pointers_in_place_and_out_of_place(fusion_u16):
     assert all((lay[nm] == before[nm]).all() for nm in mr.LAYER)
 
 
+# ---- the staging of host arrays: twelve in one buffer ----------------------------------------------------------------------------
+_STAGING = {}
+
+
+def staging_case(gw, gh):
+    """dict(depth, state_in, layer, grid_pose, cam_pose, kw, want): test_image_and_grid_shapes' noise frame of 37 x 29 pixels over a
+    grid of gw x gh cells that holds the camera, with a random layer and both ages; the restatement's answer, computed once and shared"""
+    if (gw, gh) not in _STAGING:
+        w, h = 37, 29
+        res, corner = (0.05, (0.0, 0.0)) if gw >= 31 else (0.25, (0.0, 0.0)) if gw >= 8 else (0.5, (0.6, 0.3))
+        kw = dict(fx=60.0, fy=60.0, cx=0.5 * (w - 1), cy=0.5 * (h - 1), cam_width=w, cam_height=h, t_min=0.2, t_max=5.0, width=gw, height=gh, res=res,
+                  max_dist_cells=5, stride=3, min_hits=3, slices=7, tick=9, max_mark_age=3, max_seen_age=2)
+        c = dict(depth=lr.noise_depth(w, h, 7 * w + h, lo=0.1, hi=1.6), state_in=lr.state_pattern(gw, gh, gw + w), layer=mr.random_layer(gw, gh, gw, 9, 3, 2, slices=7),
+                 grid_pose=lr.grid_pose_at(*corner), cam_pose=lr.room_pose(yaw=8.0, roll=2.0, at=(0.8, 0.1, 0.35)), kw=kw)
+        c["want"] = mr.update(c["depth"], None, c["state_in"], c["layer"], c["grid_pose"], c["cam_pose"], mr.params(**kw))
+        _STAGING[gw, gh] = c
+    return _STAGING[gw, gh]
+
+
+def memory_host(f, c, names, in_place=False):
+    """ssf_navmem_update with host arrays, the outputs `names` alone, each between guard bytes and filled with them; in_place: the
+    layer's outputs are its inputs and state is state_in, whatever `names` says of them.  Returns (name -> array, stats)"""
+    gw, gh = c["kw"]["width"], c["kw"]["height"]
+    out = {nm: util.guarded((gh, gw), dt) for nm, dt in binding.NAVMEM_OUTPUTS if nm in names or (in_place and nm in mr.LAYER + ("state",))}
+    ins = {nm: c["layer"][nm].copy() for nm in mr.LAYER}
+    ins["state"] = c["state_in"].copy()
+    if in_place:
+        for nm in ins:
+            out[nm][0][...] = ins[nm]
+        ins = {nm: out[nm][0] for nm in ins}
+    p, keep = f._navmem_params(False, False, width=gw, height=gh, grid_pose=c["grid_pose"], cam_pose=c["cam_pose"], tick=c["kw"]["tick"], **call_kw(c["kw"]))
+    stats = f._navmem_update(p, binding._ptr(c["depth"]), None, binding._ptr(ins["state"]), [binding._ptr(ins[nm]) for nm in mr.LAYER],
+                             {nm: binding._ptr(a) for nm, (a, _) in out.items()})
+    assert all(intact() for _, intact in out.values()), names
+    assert in_place or ((ins["state"] == c["state_in"]).all() and all((ins[nm] == c["layer"][nm]).all() for nm in mr.LAYER)), "an input was written"
+    return {nm: a for nm, (a, _) in out.items()}, stats
+
+
+@pytest.mark.parametrize("gw,gh", [(37, 19), (1, 1)])
+def test_host_arrays_whose_items_all_start_at_rounded_offsets(gw, gh, fusion):
+    """703 cells and one cell, a frame of 37 x 29 pixels: neither P nor 4 P nor 4 times the pixels is a multiple of 256, so each of the
+    twelve arrays behind the first sits at a rounded offset of the one staging buffer.  Host arrays, device pointers and the
+    restatement agree"""
+    import torch
+    c = staging_case(gw, gh)
+    host, hs = memory_host(fusion, c, mr.OUTPUTS)
+    same(dict(host, stats=hs), c["want"], "host %d x %d" % (gw, gh))
+    t = {nm: torch.full((gh, gw), 0x5A, dtype=torch.int8 if dt is np.int8 else torch.int32, device="cuda") for nm, dt in binding.NAVMEM_OUTPUTS}
+    up = lambda a: torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to("cuda")
+    ds = fusion.nav_memory_device(up(c["depth"]), up(c["state_in"]), gw, gh, layer_in=[up(c["layer"][nm]) for nm in mr.LAYER], grid_pose=c["grid_pose"],
+                                  cam_pose=c["cam_pose"], tick=c["kw"]["tick"], **dict({("state_out" if nm == "state" else nm): a for nm, a in t.items()}, **call_kw(c["kw"])))
+    assert all(host[nm].tobytes() == t[nm].cpu().numpy().tobytes() for nm in mr.OUTPUTS) and {k: hs[k] for k in mr.STATS} == {k: ds[k] for k in mr.STATS}
+    s = c["want"]["stats"]
+    assert s["rays"] > 64 and (gw == 1 or (s["points_in_band"] > 0 and s["cells_remembered"] > 0 and s["cells_expired"] > 0))
+
+
+@pytest.mark.parametrize("name", mr.OUTPUTS)
+def test_one_host_output_alone_between_guard_bytes(name, fusion):
+    """37 x 19, host arrays: each of the eight outputs on its own, all others NULL, equals the same array of the call that asks for
+    all of them, and the 256 bytes on either side of the caller's array are untouched"""
+    c = staging_case(37, 19)
+    if "every" not in c:
+        c["every"] = memory_host(fusion, c, mr.OUTPUTS)
+    every, stats = c["every"]
+    same(dict(every, stats=stats), c["want"], "every output")
+    alone, st = memory_host(fusion, c, (name,))
+    assert alone[name].tobytes() == every[name].tobytes() and {k: st[k] for k in mr.STATS} == {k: stats[k] for k in mr.STATS}, name
+
+
+def test_host_arrays_updated_in_place(fusion):
+    """37 x 19, host arrays: the layer's three outputs are its inputs and state is state_in.  Each pair is two items of the staging
+    buffer, so the update reads what the caller had and the caller gets what a call out of place gives"""
+    c = staging_case(37, 19)
+    got, stats = memory_host(fusion, c, mr.OUTPUTS, in_place=True)
+    same(dict(got, stats=stats), c["want"], "in place")
+    few, stats = memory_host(fusion, c, ("dist2",), in_place=True)        # the other five NULL
+    same(dict(few, stats=stats), c["want"], "in place, dist2", outputs=mr.LAYER + ("state", "dist2"))
+    assert (c["want"]["state"] != c["state_in"]).any() and any((c["want"][nm] != c["layer"][nm]).any() for nm in mr.LAYER)
+
+
+def test_the_staging_buffer_grows_and_is_used_again(mem_lib):
+    """one handle: 8 x 8, 37 x 19, 8 x 8 again.  Each call gives what a handle that has made no other call gives"""
+    f = handle(mem_lib)
+    for gw, gh in ((8, 8), (37, 19), (8, 8)):
+        c = staging_case(gw, gh)
+        fresh = handle(mem_lib)
+        (got, gs), (want, ws) = memory_host(f, c, mr.OUTPUTS), memory_host(fresh, c, mr.OUTPUTS)
+        fresh.close()
+        assert all(got[nm].tobytes() == want[nm].tobytes() for nm in mr.OUTPUTS) and {k: gs[k] for k in mr.STATS} == {k: ws[k] for k in mr.STATS}, (gw, gh)
+        same(dict(got, stats=gs), c["want"], (gw, gh))
+    f.close()
+
+
 def test_a_call_between_two_frames_changes_no_later_result(mem_lib):
     import torch
     A, B = handle(mem_lib), handle(mem_lib)

@@ -276,6 +276,91 @@ def test_device_tensors_give_the_same_bits(fusion):
     assert (t2.cpu().numpy() == host["path_min"]).all()
 
 
+# ---- the staging of the host grid and the lengths -----------------------------------------------------------------------------
+FILL = util.GUARD_WORD
+_STAGING = {}
+
+
+def staging_case(h, w):
+    """dict(state, dist2, path, lens, kw, want): five paths of the plan's restatement on a random grid, one with a length of 0 and one
+    with a length past max_path among them, refined with a kept clearance; the restatement's answer, computed once and shared"""
+    if (h, w) not in _STAGING:
+        state, dist2 = pr.random_grid(h, w, 600 + h + w, obstacles=0.12, unknown=0.05)
+        goal = (w // 2, h // 2)
+        state[goal[1], goal[0]] = 0
+        plan = pr.plan(state, dist2, [goal], some_starts(h, w, 5, 3 * h + w), max_path=h * w, allow_unknown=1)
+        path, lens = wr.pack_paths(plan["path"] + [plan["path"][0][:0], plan["path"][0]])
+        lens[-1] = path.shape[1] + 1
+        kw = dict(allow_unknown=1, keep_clearance=1, clearance_cap=10, los_dist2=1, lookahead=50, max_waypoints=max(1, path.shape[1] // 2))
+        _STAGING[h, w] = dict(state=state, dist2=dist2, path=path, lens=lens, kw=kw, want=wr.waypoints(state, dist2, path, lens, **kw))
+    return _STAGING[h, w]
+
+
+def waypoints_host(f, c, names):
+    """ssf_navpath_waypoints with host arrays, the outputs `names` alone, each between guard bytes and filled with them: (name ->
+    array, stats)"""
+    (h, w), (n, mp, _), mw = c["state"].shape, c["path"].shape, c["kw"]["max_waypoints"]
+    shapes = dict(n_waypoints=(n,), status=(n,), waypoints=(n, mw, 4), path_min=(n,))
+    out = {nm: util.guarded(shapes[nm], np.int32) for nm in names}
+    stats = f._navpath_waypoints(f._navpath_params(False, w, h, n, mp, c["kw"]), binding._ptr(c["state"]), binding._ptr(c["dist2"]), binding._ptr(c["path"]),
+                                 binding._ptr(c["lens"]), {nm: binding._ptr(a) for nm, (a, _) in out.items()})
+    assert all(intact() for _, intact in out.values()), names
+    return {nm: a for nm, (a, _) in out.items()}, stats
+
+
+def waypoints_same(got, want, what):
+    """every array of got equals the restatement's; a path's waypoints up to their count, and past it they hold the fill"""
+    for nm, a in got.items():
+        if nm != "waypoints":
+            assert (a == want[nm]).all(), (what, nm, a.tolist(), want[nm].tolist())
+            continue
+        for i, wp in enumerate(want["waypoints"]):
+            assert (a[i, :len(wp)] == wp).all() and (a[i, len(wp):] == FILL).all(), (what, nm, i)
+
+
+@pytest.mark.parametrize("h,w", [(19, 37), (1, 1)])
+def test_host_arrays_whose_items_all_start_at_rounded_offsets(h, w, fusion):
+    """703 cells and one cell: neither P nor 4 P is a multiple of 256, so dist2 and the lengths sit at rounded offsets of the staging
+    buffer.  Host arrays, device pointers and the restatement agree"""
+    import torch
+    c = staging_case(h, w)
+    host, hs = waypoints_host(fusion, c, binding.NAVPATH_OUTPUT_NAMES)
+    waypoints_same(host, c["want"], "host %d x %d" % (h, w))
+    t = {nm: torch.full(a.shape, FILL, dtype=torch.int32, device="cuda") for nm, a in host.items()}
+    d = [torch.from_numpy(c[k]).to("cuda") for k in ("state", "dist2", "path", "lens")]
+    ds = fusion.nav_waypoints_device(d[0], d[1], w, h, d[2], d[3], len(c["lens"]), c["path"].shape[1], **dict(t, **c["kw"]))
+    assert all(host[nm].tobytes() == t[nm].cpu().numpy().tobytes() for nm in host)
+    assert {k: hs[k] for k in wr.STATS} == {k: ds[k] for k in wr.STATS} == {k: c["want"]["stats"][k] for k in wr.STATS}
+    s = c["want"]["stats"]
+    assert s["paths_bad"] == 1 and (h == 1 or (s["paths_ok"] == 6 and s["waypoints"] > 12 and s["cells_in"] > 40))
+
+
+@pytest.mark.parametrize("name", binding.NAVPATH_OUTPUT_NAMES)
+def test_one_host_output_alone_between_guard_bytes(name, fusion):
+    """19 x 37, host arrays: every output on its own, all others NULL, equals the same array of the call that asks for all four, and
+    the 256 bytes on either side of the caller's array are untouched"""
+    c = staging_case(19, 37)
+    if "every" not in c:
+        c["every"] = waypoints_host(fusion, c, binding.NAVPATH_OUTPUT_NAMES)
+    every, stats = c["every"]
+    waypoints_same(every, c["want"], "every output")
+    alone, st = waypoints_host(fusion, c, (name,))
+    assert alone[name].tobytes() == every[name].tobytes() and {k: st[k] for k in wr.STATS} == {k: stats[k] for k in wr.STATS}, name
+
+
+def test_the_staging_buffer_grows_and_is_used_again(drive_lib):
+    """one handle: 8 x 8, 19 x 37, 8 x 8 again.  Each call gives what a handle that has made no other call gives"""
+    f = handle(drive_lib)
+    for h, w in ((8, 8), (19, 37), (8, 8)):
+        c = staging_case(h, w)
+        fresh = handle(drive_lib)
+        (got, gs), (want, ws) = waypoints_host(f, c, binding.NAVPATH_OUTPUT_NAMES), waypoints_host(fresh, c, binding.NAVPATH_OUTPUT_NAMES)
+        fresh.close()
+        assert all(got[nm].tobytes() == want[nm].tobytes() for nm in got) and {k: gs[k] for k in wr.STATS} == {k: ws[k] for k in wr.STATS}, (h, w)
+        waypoints_same(got, c["want"], (h, w))
+    f.close()
+
+
 def test_plan_and_refine_without_leaving_the_device(fusion):
     state, dist2 = pr.random_grid(64, 64, 23, obstacles=0.15)
     state[5, 5] = 0

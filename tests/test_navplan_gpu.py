@@ -286,6 +286,87 @@ def test_device_tensors_give_the_same_bits(fusion):
     assert (t2.cpu().numpy().view(np.uint32) == host["cost"]).all()
 
 
+# ---- the staging of a host grid -----------------------------------------------------------------------------------------------
+FILL = util.GUARD_WORD
+_STAGING = {}
+
+
+def staging_case(h, w):
+    """dict(state, dist2, goals, starts, kw, want): a random grid with unknown cells, goals in two corners, five
+    starts; the restatement's answer, computed once and shared"""
+    if (h, w) not in _STAGING:
+        state, dist2 = pr.random_grid(h, w, 900 + h + w, obstacles=0.15, unknown=0.1)
+        state[0, 0] = state[h - 1, w - 1] = 0
+        goals, starts = [(0, 0), (w - 1, h - 1)], some_starts(h, w, 5, 7 * h + w)
+        kw = dict(soft_dist2=30, near_penalty=40, max_path=h * w)
+        _STAGING[h, w] = dict(state=state, dist2=dist2, goals=goals, starts=starts, kw=kw, want=pr.plan(state, dist2, goals, starts, **kw))
+    return _STAGING[h, w]
+
+
+def plan_host(f, c, names):
+    """ssf_navplan_field with host arrays, the outputs `names` alone, each between guard bytes and filled with them: (name -> array, stats)"""
+    (h, w), n, mp = c["state"].shape, len(c["starts"]), c["kw"]["max_path"]
+    shapes = dict(cost=((h, w), np.uint32), frontier=((h, w), np.uint8), start_cost=((n,), np.uint32), start_status=((n,), np.int32),
+                  path_len=((n,), np.int32), path=((n, mp, 2), np.int32))
+    out = {nm: util.guarded(*shapes[nm]) for nm in names}
+    p, keep = f._navplan_params(False, w, h, c["goals"], c["starts"], c["kw"])
+    stats = f._navplan_field(p, binding._ptr(c["state"]), binding._ptr(c["dist2"]), {nm: binding._ptr(a) for nm, (a, _) in out.items()})
+    assert all(intact() for _, intact in out.values()), names
+    return {nm: a for nm, (a, _) in out.items()}, stats
+
+
+def plan_same(got, want, what):
+    """every array of got equals the restatement's; a path up to its length, and past it it holds the fill"""
+    for nm, a in got.items():
+        if nm != "path":
+            assert a.dtype == want[nm].dtype and (a == want[nm]).all(), (what, nm)
+            continue
+        for i, cells in enumerate(want["path"]):
+            assert (a[i, :len(cells)] == cells).all() and (a[i, len(cells):] == FILL).all(), (what, nm, i)
+
+
+@pytest.mark.parametrize("h,w", [(19, 37), (1, 1)])
+def test_a_host_grid_whose_arrays_start_at_rounded_offsets(h, w, fusion):
+    """703 cells and one cell: neither P nor 4 P is a multiple of 256, so dist2 sits at a rounded offset of the staging buffer.  Host
+    arrays, device pointers and the restatement agree"""
+    import torch
+    c = staging_case(h, w)
+    host, hs = plan_host(fusion, c, binding.NAVPLAN_OUTPUT_NAMES)
+    plan_same(host, c["want"], "host %d x %d" % (h, w))
+    t = {nm: torch.full(a.shape, util.GUARD_FILL, dtype=torch.uint8, device="cuda") if a.dtype == np.uint8 else torch.full(a.shape, FILL, dtype=torch.int32, device="cuda")
+         for nm, a in host.items()}
+    ds = fusion.nav_plan_device(torch.from_numpy(c["state"]).to("cuda"), torch.from_numpy(c["dist2"]).to("cuda"), w, h, c["goals"], c["starts"], **dict(t, **c["kw"]))
+    assert all(host[nm].tobytes() == t[nm].cpu().numpy().tobytes() for nm in host)
+    assert {k: hs[k] for k in pr.STATS} == {k: ds[k] for k in pr.STATS} == {k: c["want"]["stats"][k] for k in pr.STATS}
+    assert h == 1 or (c["want"]["stats"]["cells_reached"] > 100 and c["want"]["stats"]["frontier_cells"] > 0 and (c["want"]["path_len"] > 10).any())
+
+
+@pytest.mark.parametrize("name", binding.NAVPLAN_OUTPUT_NAMES)
+def test_one_host_output_alone_between_guard_bytes(name, fusion):
+    """19 x 37, host arrays: every output on its own, all others NULL, equals the same array of the call that asks for all six, and
+    the 256 bytes on either side of the caller's array are untouched"""
+    c = staging_case(19, 37)
+    if "every" not in c:
+        c["every"] = plan_host(fusion, c, binding.NAVPLAN_OUTPUT_NAMES)
+    every, stats = c["every"]
+    plan_same(every, c["want"], "every output")
+    alone, st = plan_host(fusion, c, (name,))
+    assert alone[name].tobytes() == every[name].tobytes() and {k: st[k] for k in pr.STATS} == {k: stats[k] for k in pr.STATS}, name
+
+
+def test_the_staging_buffer_grows_and_is_used_again(nav_lib):
+    """one handle: 8 x 8, 19 x 37, 8 x 8 again.  Each call gives what a handle that has made no other call gives"""
+    f = handle(nav_lib)
+    for h, w in ((8, 8), (19, 37), (8, 8)):
+        c = staging_case(h, w)
+        fresh = handle(nav_lib)
+        (got, gs), (want, ws) = plan_host(f, c, binding.NAVPLAN_OUTPUT_NAMES), plan_host(fresh, c, binding.NAVPLAN_OUTPUT_NAMES)
+        fresh.close()
+        assert all(got[nm].tobytes() == want[nm].tobytes() for nm in got) and {k: gs[k] for k in pr.STATS} == {k: ws[k] for k in pr.STATS}, (h, w)
+        plan_same(got, c["want"], (h, w))
+    f.close()
+
+
 def test_plan_from_the_carved_map_without_the_grid_leaving_the_device(fusion):
     f = fusion
     m, n, pose, gkw, views, ckw = nc.wall_scene()

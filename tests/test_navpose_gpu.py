@@ -234,6 +234,88 @@ def test_the_five_statuses_and_the_paths_lengths(fusion):
     assert sorted(got) == ["start_status", "stats"] and got["start_status"].tolist() == st
 
 
+# ---- the staging of a host grid --------------------------------------------------------------------------------------------------------
+FILL = util.GUARD_WORD
+
+
+def staging_case(h, w):
+    """dict(mask, dist2, goals, starts, kw, want): a floor with a few obstacles, the small body at 8 bins (on one cell: the point), two
+    goals and five starts; the restatement's answer, computed once and shared"""
+    def make():
+        state, dist2 = grid(h, w, "few", 700 + h + w)
+        state[h // 2, w // 2] = 0
+        mask = fr.layers(state, 0, SMALL, 8)["free_mask"] if min(h, w) >= 8 else qr.point_mask(state, 0, 8)
+        kw = dict(n_headings=8, soft_dist2=30, near_penalty=40, max_path=256)
+        rng = np.random.default_rng(h * w)
+        goals = np.array([(w // 2, h // 2, -1), (w - 1, 0, 2), (w, 0, 0)], np.int32)
+        starts = np.stack([rng.integers(0, w * 1024, 5), rng.integers(0, h * 1024, 5), rng.integers(-70000, 140000, 5)], axis=1).astype(np.int32)
+        return dict(mask=mask, dist2=dist2, goals=goals, starts=starts, kw=kw, want=qr.plan(mask, dist2, goals, starts, **kw))
+    return qr.cached(("staging", h, w), make)
+
+
+def pose_host(f, c, names):
+    """ssf_navpose_field with host arrays, the outputs `names` alone, each between guard bytes and filled with them: (name -> array, stats)"""
+    (h, w), n, mp, B = c["mask"].shape, len(c["starts"]), c["kw"]["max_path"], c["kw"]["n_headings"]
+    shapes = dict(cost=((B, h, w), np.uint32), cell_cost=((h, w), np.uint32), cell_bin=((h, w), np.uint8), start_cost=((n,), np.uint32),
+                  start_status=((n,), np.int32), path_len=((n,), np.int32), path=((n, mp, 3), np.int32))
+    out = {nm: util.guarded(*shapes[nm]) for nm in names}
+    p, keep = f._navpose_params(False, w, h, c["goals"], c["starts"], c["kw"])
+    stats = f._navpose_field(p, binding._ptr(c["mask"]), binding._ptr(c["dist2"]), {nm: binding._ptr(a) for nm, (a, _) in out.items()})
+    assert all(intact() for _, intact in out.values()), names
+    return {nm: a for nm, (a, _) in out.items()}, stats
+
+
+def pose_same(got, want, what):
+    """every array of got equals the restatement's; a path up to its length, and past it it holds the fill"""
+    for nm, a in got.items():
+        if nm != "path":
+            assert a.dtype == want[nm].dtype and a.shape == want[nm].shape and (a == want[nm]).all(), (what, nm)
+            continue
+        for i, states in enumerate(want["path"]):
+            assert (a[i, :len(states)] == states).all() and (a[i, len(states):] == FILL).all(), (what, nm, i)
+
+
+@pytest.mark.parametrize("h,w", [(19, 37), (1, 1)])
+def test_a_host_grid_whose_arrays_start_at_rounded_offsets(h, w, fusion):
+    """703 cells and one cell: 4 P is no multiple of 256, so dist2 sits at a rounded offset of the staging buffer.  Host arrays,
+    device pointers and the restatement agree"""
+    import torch
+    c = staging_case(h, w)
+    host, hs = pose_host(fusion, c, binding.NAVPOSE_OUTPUT_NAMES)
+    pose_same(host, c["want"], "host %d x %d" % (h, w))
+    t = {nm: torch.full(a.shape, util.GUARD_FILL, dtype=torch.uint8, device="cuda") if a.dtype == np.uint8 else torch.full(a.shape, FILL, dtype=torch.int32, device="cuda")
+         for nm, a in host.items()}
+    ds = fusion.nav_pose_plan_device(torch.from_numpy(c["mask"].view(np.int32)).to("cuda"), torch.from_numpy(c["dist2"]).to("cuda"), w, h, c["goals"], c["starts"],
+                                     **dict(t, **c["kw"]))
+    assert all(host[nm].tobytes() == t[nm].cpu().numpy().tobytes() for nm in host)
+    assert {k: hs[k] for k in qr.STATS} == {k: ds[k] for k in qr.STATS} == c["want"]["stats"]
+    assert h == 1 or (c["want"]["stats"]["states_reached"] > 1000 and (c["want"]["path_len"] > 1).any() and c["want"]["stats"]["goals_outside"] == 1)
+
+
+@pytest.mark.parametrize("name", binding.NAVPOSE_OUTPUT_NAMES)
+def test_one_host_output_alone_between_guard_bytes(name, fusion):
+    """19 x 37, host arrays: every output on its own, all others NULL, equals the same array of the call that asks for all seven, and
+    the 256 bytes on either side of the caller's array are untouched"""
+    c = staging_case(19, 37)
+    every, stats = qr.cached("staging every", lambda: pose_host(fusion, c, binding.NAVPOSE_OUTPUT_NAMES))
+    pose_same(every, c["want"], "every output")
+    alone, st = pose_host(fusion, c, (name,))
+    assert alone[name].tobytes() == every[name].tobytes() and {k: st[k] for k in qr.STATS} == {k: stats[k] for k in qr.STATS}, name
+
+
+def test_the_staging_buffer_grows_and_is_used_again(pose_lib):
+    """one handle: 8 x 8, 19 x 37, 8 x 8 again.  Each call gives what a handle that has made no other call gives"""
+    f = handle(pose_lib)
+    for h, w in ((8, 8), (19, 37), (8, 8)):
+        c = staging_case(h, w)
+        fresh = handle(pose_lib)
+        (got, gs), (want, ws) = pose_host(f, c, binding.NAVPOSE_OUTPUT_NAMES), pose_host(fresh, c, binding.NAVPOSE_OUTPUT_NAMES)
+        fresh.close()
+        assert all(got[nm].tobytes() == want[nm].tobytes() for nm in got) and {k: gs[k] for k in qr.STATS} == {k: ws[k] for k in qr.STATS}, (h, w)
+        pose_same(got, c["want"], (h, w))
+    f.close()
+
+
 # ---- device pointers -------------------------------------------------------------------------------------------------------------------
 def overlay_scene():
     """a depth frame over a free floor (tests/navlive_ref.py's room): what the overlay, the layers and the pose plan make of it is steered on"""

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import navdyn_ref as dr
 import navlive_ref as lr
 import navplan_ref as pr
 import navsteer_ref as sr
@@ -232,6 +233,63 @@ def test_entries_of_best_traj_past_best_len_are_not_written(steer_lib, fusion):
     assert (blen == want["best_len"]).all() and (blen < T + 1).any() and (blen == 0).any()
     for q in range(n):
         assert (traj[q, :blen[q]] == want["best_traj"][q, :blen[q]]).all() and (traj[q, blen[q]:] == SENT).all(), q
+
+
+# ---- the staging of host arrays ----------------------------------------------------------------------------------------------------
+same_arrays, FILL = util.rollouts_same, util.GUARD_WORD
+
+
+@pytest.mark.parametrize("w,h", [(37, 19), (1, 1)])
+def test_host_arrays_whose_items_all_start_at_rounded_offsets(w, h, fusion):
+    """703 cells and one cell: neither P nor 4 P is a multiple of 256, so every array behind the first sits at a rounded offset of the
+    staging buffer.  Host arrays, device pointers and the restatement agree on every output and exact stat"""
+    s, want = dr.staging_scene(w, h, 5), dr.staging_reference(w, h, 5, "disc")
+    host, hs = util.rollouts_host(fusion, "disc", s, sr.OUTPUTS)
+    dev, ds = util.rollouts_device(fusion, "disc", s, sr.OUTPUTS)
+    same_arrays(host, want, "host %d x %d" % (w, h), FILL)
+    same_arrays(dev, want, "device %d x %d" % (w, h), FILL)
+    assert all(host[nm].tobytes() == dev[nm].tobytes() for nm in sr.OUTPUTS)
+    assert {k: hs[k] for k in sr.STATS} == {k: ds[k] for k in sr.STATS} == {k: want["stats"][k] for k in sr.STATS}
+    assert w == 1 or ((want["pose_status"] == 0).sum() >= 3 and want["stats"]["collided"] > 0 and (want["pose_status"] == 1).any())
+
+
+@pytest.mark.parametrize("name", sr.OUTPUTS)
+def test_one_host_output_alone_between_guard_bytes(name, fusion):
+    """37 x 19, host arrays: every output on its own, all others NULL, equals the same array of the call that asks for all twelve,
+    and the 256 bytes on either side of the caller's array are untouched"""
+    s = dr.staging_scene(37, 19, 5)
+    every, stats = dr.cached(("staging host", "disc"), lambda: util.rollouts_host(fusion, "disc", s, sr.OUTPUTS))
+    same_arrays(every, dr.staging_reference(37, 19, 5, "disc"), "every output", FILL)
+    alone, st = util.rollouts_host(fusion, "disc", s, (name,))
+    assert alone[name].tobytes() == every[name].tobytes() and {k: st[k] for k in sr.STATS} == {k: stats[k] for k in sr.STATS}, name
+
+
+def test_best_traj_goes_in_as_well_as_out(fusion):
+    """host arrays: best_traj is staged in both directions, so the entries past best_len, which the kernel does not write, come back
+    as the caller's 0x5A5A5A5A and not as what the staging buffer held.  The first pose's winner stops at the wall after two steps"""
+    s, want = dr.staging_scene(37, 19, 5), dr.staging_reference(37, 19, 5, "disc")
+    T1 = s["c"]["n_steps"] + 1
+    assert want["pose_status"][0] == 0 and 1 < want["best_len"][0] < T1 and (want["best_len"] == T1).any() and (want["best_len"] == 0).any()
+    util.rollouts_host(fusion, "disc", s, ("cand_end",))                # (the place of best_len and best_traj then holds other bytes)
+    got, _ = util.rollouts_host(fusion, "disc", s, ("best_traj", "best_len"))
+    assert (got["best_len"] == want["best_len"]).all()
+    same_arrays(got, want, "best_traj", FILL)
+    assert sum(int((got["best_traj"][q, n:] == FILL).sum()) for q, n in enumerate(want["best_len"])) == 3 * int((T1 - want["best_len"]).sum()) > 0
+
+
+def test_the_staging_buffer_grows_and_is_used_again(steer_lib):
+    """one handle: 8 x 8 with one pose, 37 x 19 with five, 8 x 8 with one again.  Each call gives what a handle that has made no
+    other call gives"""
+    f = handle(steer_lib)
+    for w, h, n in ((8, 8, 1), (37, 19, 5), (8, 8, 1)):
+        s = dr.staging_scene(w, h, n)
+        got, gs = util.rollouts_host(f, "disc", s, sr.OUTPUTS)
+        fresh = handle(steer_lib)
+        want, ws = util.rollouts_host(fresh, "disc", s, sr.OUTPUTS)
+        fresh.close()
+        assert all(got[nm].tobytes() == want[nm].tobytes() for nm in sr.OUTPUTS) and {k: gs[k] for k in sr.STATS} == {k: ws[k] for k in sr.STATS}, (w, h, n)
+        same_arrays(got, dr.staging_reference(w, h, n, "disc"), (w, h, n), FILL)
+    f.close()
 
 
 # ---- through the binding ----------------------------------------------------------------------------------------------------------

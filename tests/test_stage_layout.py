@@ -1,6 +1,9 @@
 """The offsets of a call's host arrays in the staging buffer (csrc/ssf_stage_layout.hpp, used by StagedIo in ssf_handle.hpp for
-ssf_render_model, ssf_query_rows, ssf_navgrid_build and ssf_raycast): tests/cpp/stage_layout_smoke.cpp, a program of its own over
-the part that includes no HIP header, built with the address and undefined-behaviour sanitizers and run as a process."""
+ssf_render_model, ssf_query_rows, ssf_raycast, ssf_navgrid_build, ssf_navgrid_carve, ssf_navlive_overlay, ssf_navmem_update,
+ssf_navdyn_blobs, ssf_navplan_field, ssf_navpose_field, ssf_navfrontier_regions, ssf_navpath_waypoints, ssf_navfoot_layers and the
+four rollouts: ssf_navsteer_rollouts, ssf_navfoot_rollouts, ssf_navdyn_rollouts, ssf_navdyn_foot_rollouts):
+tests/cpp/stage_layout_smoke.cpp, a program of its own over the part that includes no HIP header, built with the address and
+undefined-behaviour sanitizers and run as a process."""
 import os
 import subprocess
 

@@ -76,6 +76,81 @@ def same_result(ra, rb):
     assert_same_bits(ra["pose"], rb["pose"], "result pose")
 
 
+GUARD_FILL, GUARD_WORD = 0x5A, 0x5A5A5A5A                                # util.guarded's byte, and four of them as a 32-bit word
+
+
+def guarded(shape, dtype):
+    """(array, intact): a host array of `shape` between two runs of 256 guard bytes in one buffer, every byte of all three 0x5A (a
+    32-bit word: 0x5A5A5A5A); intact() tells whether both guards still hold that"""
+    n = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
+    raw = np.full(256 + n + 256, GUARD_FILL, np.uint8)
+    return raw[256:256 + n].view(dtype).reshape(shape), lambda: bool((raw[:256] == GUARD_FILL).all() and (raw[256 + n:] == GUARD_FILL).all())
+
+
+# ---- the four rollouts on navdyn_ref.staging_scene, for the tests of a call's host arrays (test_navsteer_gpu.py, test_navfoot_gpu.py,
+# test_navdyn_gpu.py).  kind: 'disc' (ssf_navsteer_rollouts), 'foot' (ssf_navfoot_rollouts), 'dyn' (ssf_navdyn_rollouts), 'dyn foot'
+# (ssf_navdyn_foot_rollouts) ------------------------------------------------------------------------------------------------------
+def rollouts_outputs(kind):
+    """(name, dtype, per pose or candidate, trailing shape) of every output array of the call"""
+    return binding.NAVSTEER_OUTPUTS + (binding.NAVDYN_OUTPUTS if "dyn" in kind else ())
+
+
+def rollouts_shape(s, name):
+    c = s["c"]
+    _, dt, per, tail = [o for o in rollouts_outputs("dyn") if o[0] == name][0]
+    return binding.Fusion._navsteer_shape(per, tail, c["n_poses"], c["n_v"] * c["n_w"], c["n_steps"]), dt
+
+
+def rollouts_call(f, kind, s, inputs, outputs, on_device):
+    """the C call of `kind` on scene s: inputs (grid, dist2, cost, poses, targets, movers) and outputs (name -> pointer; the others
+    are NULL) are pointers of the memory on_device tells; returns the stats"""
+    c = s["c"]
+    kw = {k: v for k, v in c.items() if k not in ("width", "height", "n_poses")}
+    B = s["B"] if "foot" in kind else None
+    if "dyn" in kind:
+        dp, kw = f._navdyn_params(len(s["movers"]), kw)
+        return f._navdyn_rollouts(f._navsteer_params(on_device, c["width"], c["height"], c["n_poses"], kw), dp, *inputs, outputs, B)
+    kw = {k: v for k, v in kw.items() if k not in ("mover_cap", "mover_weight")}
+    return f._navsteer_rollouts(f._navsteer_params(on_device, c["width"], c["height"], c["n_poses"], kw), *inputs[:5], outputs, B)
+
+
+def rollouts_inputs(kind, s):
+    return [s["free_mask"] if "foot" in kind else s["state"], s["dist2"], s["cost"], s["poses"], s["targets"], s["movers"]]
+
+
+def rollouts_host(f, kind, s, names):
+    """the call with host arrays, the outputs `names` alone, each between guard bytes and filled with them before the call: (name ->
+    array, stats).  The guards are checked here"""
+    out = {nm: guarded(*rollouts_shape(s, nm)) for nm in names}
+    stats = rollouts_call(f, kind, s, [binding._ptr(np.ascontiguousarray(a)) for a in rollouts_inputs(kind, s)], {nm: binding._ptr(a) for nm, (a, _) in out.items()}, False)
+    for nm, (_, intact) in out.items():
+        assert intact(), (kind, nm, "the guard bytes around the caller's array")
+    return {nm: a for nm, (a, _) in out.items()}, stats
+
+
+def rollouts_device(f, kind, s, names):
+    """the call with device pointers: (name -> array, copied back, filled with 0x5A bytes before the call; stats)"""
+    import ctypes as C
+    import torch
+    dev = torch.device("cuda")
+    ins = [torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev) for a in rollouts_inputs(kind, s)]
+    out = {nm: torch.full((max(1, int(np.prod(rollouts_shape(s, nm)[0])) * np.dtype(rollouts_shape(s, nm)[1]).itemsize),), GUARD_FILL, dtype=torch.uint8, device=dev)
+           for nm in names}
+    stats = rollouts_call(f, kind, s, [C.c_void_p(t.data_ptr()) for t in ins], {nm: C.c_void_p(t.data_ptr()) for nm, t in out.items()}, True)
+    return {nm: t.cpu().numpy().view(rollouts_shape(s, nm)[1]).reshape(rollouts_shape(s, nm)[0]) for nm, t in out.items()}, stats
+
+
+def rollouts_same(got, want, what, fill=None):
+    """every array of got (name -> array, uncut) equals the restatement's; best_traj up to best_len, and past it (fill given) it holds
+    what it held before the call"""
+    for nm, a in got.items():
+        if nm != "best_traj":
+            assert a.dtype == want[nm].dtype and a.shape == want[nm].shape and (a == want[nm]).all(), (what, nm)
+            continue
+        for q, n in enumerate(want["best_len"]):
+            assert (a[q, :n] == want[nm][q, :n]).all() and (fill is None or (a[q, n:] == fill).all()), (what, nm, q)
+
+
 def device_to_host(ptr, shape, dtype):
     """copy a raw device pointer (ssf_get_model_device) to a numpy array through the HIP runtime already in the process"""
     import ctypes as C
