@@ -70,6 +70,7 @@
  * inner_check < 1.  SSF_ERR_STATE: frames pending, a sharded handle, a missing or stale graph, m >= 2^20 (the counting sorts' key
  * range), no solve yet (get_transforms / apply_solved).  SSF_ERR_CAPACITY: capacity < m.  SSF_ERR_DEVICE: a working buffer could
  * not be allocated (buffers are allocated on first use and grown as a whole or not at all; the handle keeps working).
+ * A call refused with SSF_ERR_INVALID_ARG or SSF_ERR_STATE touches nothing: the transforms of the last solve stay as they were.
  *
  * All calls are synchronous and run on the handle's stream.  Kernel time appears in ssf_get_kernel_times under profile = 1 as
  * graph_solve.  Only the HIP product library exports these functions; the ABI version of ssf.h is unchanged.

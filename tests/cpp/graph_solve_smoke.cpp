@@ -1,7 +1,8 @@
 // The graph-optimisation surface of include/ssf.hpp (getGraphEdges, optimiseGraphSparse, getGraphTransforms, applyGraphToModel)
 // on frames read from a file: graph_solve_smoke W H n frames.bin fx fy cx cy.  The constraints are the node positions themselves:
-// the earlier half pinned, the later half shifted.  Prints sizes, the result record and FNV-1a hashes; the GPU test repeats the
-// calls through the Python binding and compares the lines.
+// the earlier half pinned, the later half shifted; solved twice, once through ssf_graph_solve itself with no result record.
+// Prints sizes, the result record and FNV-1a hashes; the GPU test repeats the calls through the Python binding and compares
+// the lines.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -41,6 +42,14 @@ int main(int argc, char** argv) {
         for (int k = m / 2; k < m; k++) { dst[(size_t)k].x += 0.01f; dst[(size_t)k].z -= 0.02f; }
         ssf_graph_solve_params p = SupersurfelFusion::defaultGraphSolveParams();
         p.max_outer = 3;
+        // first the C entry point without a result record, the stop rule read after every iteration; its line is printed last
+        ssf_graph_solve_params p1 = p;
+        p1.inner_check = 1;
+        if (ssf_graph_solve(a.handle(), &p1, reinterpret_cast<const float*>(g.data()), t0.data(), reinterpret_cast<const float*>(dst.data()),
+                            m, nullptr) != SSF_OK) { std::printf("ssf_graph_solve without a result record failed\n"); return 1; }
+        std::vector<Mat33> R1; std::vector<float3> t1;
+        a.getGraphTransforms(R1, t1);
+        const unsigned long long every_1 = fnv(t1.data(), 12 * t1.size(), fnv(R1.data(), 36 * R1.size()));
         const ssf_graph_solve_result r = a.optimiseGraphSparse(g, t0, dst, p);
         std::printf("solve outer=%d inner=%d,%d,%d end=%d energy %016llx\n", r.outer, r.inner[0], r.inner[1], r.inner[2], r.inner_end,
                     fnv(&r.e_before, 5 * sizeof(double)));
@@ -53,6 +62,7 @@ int main(int argc, char** argv) {
         bool stale = false;
         try { a.getGraphTransforms(R, t); } catch (const std::runtime_error&) { stale = true; }
         std::printf("stale_after_apply %d\n", stale ? 1 : 0);
+        std::printf("no_record_check_every_1 transforms %016llx\n", every_1);
     } catch (const std::exception& e) { std::printf("exception %s\n", e.what()); return 1; }
     return 0;
 }

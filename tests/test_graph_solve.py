@@ -1,6 +1,10 @@
 """The numpy restatement of include/ssf_graph_solve.h (tests/graph_solve_ref.py) under test, so that the GPU tests compare against
 something proven: its J, J^T and diagonal against finite differences of its own residuals, the identity, a rigid motion, and its
-result against an independent Gauss-Newton with a sparse direct solve."""
+result against an independent Gauss-Newton with a sparse direct solve.  Last, EDGE_CASES: the inputs with which
+tests/test_graph_solve_edges_gpu.py drives the device through every inner-loop ending, chunk shape, block boundary and the sort's
+third pass; here the restatement alone is shown to reach each of them."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -167,3 +171,108 @@ def test_condition_the_last_inner_loop_ends_by_tolerance(name):
     c = loop_case(**GPU_CASES[name])
     res = gs.solve(c["npos"], c["nt0"], c["look"], c["src"], c["t_init"], c["dst"])[2]
     assert res["inner_end"] == gs.END_TOL and max(res["inner"]) < gs.DEFAULTS["max_inner"], res
+
+
+# ---- edge cases ---------------------------------------------------------------------------------------------------------------
+# What tests/test_graph_solve_edges_gpu.py solves on the device: loop_case arguments, solver parameters, the ending that the last
+# inner loop must reach, and how the constraints are replaced ("pins": dst = src; "hub": one point a thousand times).  The tests
+# below prove on the restatement alone that each entry reaches its ending, iteration pattern and sizes.
+LATE = dict(n=300, stride=10, look=4, n_con=20)                      # m = 30
+ROOM = dict(n=3000, stride=10, look=6)                               # m = 300
+BLOCKS = dict(max_outer=3, max_inner=48)
+EDGE_CASES = {
+    # rho underflows to zero after about 1500 iterations: a breakdown 50 iterations into a chunk, some 200 frozen launches after it
+    "late_breakdown": dict(case=LATE, params=dict(inner_tol=0.0, max_inner=6000, inner_check=300, max_outer=2, damping=0.5),
+                           end=gs.END_BREAKDOWN),
+    "breakdown_at_0": dict(case=ROOM, params=dict(w_con=1e307, max_outer=2), end=gs.END_BREAKDOWN),      # p.q overflows to +inf
+    "pins": dict(case=LATE, params={}, end=gs.END_ZERO, variant="pins"),
+    "no_energy": dict(case=ROOM, params=dict(w_rot=0.0, w_reg=0.0, w_con=0.0), end=gs.END_ZERO),
+    "check_every_1": dict(case=ROOM, params=dict(inner_check=1, max_outer=2), end=gs.END_TOL),
+    "check_beyond_max": dict(case=LATE, params=dict(inner_check=5, max_inner=3, max_outer=64, outer_tol=0.0), end=gs.END_MAX_INNER),
+    "hist_cap": dict(case=ROOM, params=dict(inner_check=300, max_inner=600, inner_tol=0.0, max_outer=1), end=gs.END_MAX_INNER),
+    # constraints alone: the touched nodes fit them exactly (a few CG iterations, by tolerance), the others have D == 0 and stay
+    "no_rot_no_reg": dict(case=LATE, params=dict(w_rot=0.0, w_reg=0.0, max_outer=3, max_inner=64), end=gs.END_TOL),
+    "m256": dict(case=dict(n=2560, stride=10, look=6, n_con=257), params=BLOCKS, end=gs.END_MAX_INNER),
+    "m257": dict(case=dict(n=2561, stride=10, look=6, n_con=256), params=BLOCKS, end=gs.END_MAX_INNER),
+    "nc513": dict(case=dict(n=2561, stride=10, look=6, n_con=513), params=BLOCKS, end=gs.END_MAX_INNER),
+    "three_passes": dict(case=dict(n=66000, stride=1, look=6, n_con=300), params=dict(max_outer=2, max_inner=8, inner_check=4),
+                         end=gs.END_MAX_INNER),
+    "one_hub": dict(case=LATE, params=BLOCKS, end=gs.END_MAX_INNER, variant="hub"),
+}
+HUB = 1000
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(name):
+    """loop_case of the entry with its variant applied; shared between the tests, so nobody writes into it"""
+    e = EDGE_CASES[name]
+    c = loop_case(**e["case"])
+    if e.get("variant") == "pins":
+        c["dst"] = c["src"].copy()
+    elif e.get("variant") == "hub":
+        c["src"] = np.repeat(c["src"][:1], HUB, axis=0)
+        c["t_init"] = np.repeat(c["t_init"][:1], HUB)
+        c["dst"] = (c["src"] + np.random.default_rng(77).normal(0.0, 0.01, (HUB, 3)).astype(f32)).astype(f32)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def edge_solution(name):
+    """(Problem, rotations, translations, result) of the restatement for the entry, computed once for every test that needs it"""
+    c = edge_case(name)
+    P = gs.Problem(c["npos"], c["nt0"], c["look"], c["src"], c["t_init"], c["dst"], **EDGE_CASES[name]["params"])
+    return (P,) + P.solve()
+
+
+def is_identity(R, t):
+    return bool((R == np.tile(np.eye(3, dtype=f32).ravel(), (len(R), 1))).all() and (t == 0).all())
+
+
+@pytest.mark.parametrize("name", sorted(EDGE_CASES))
+def test_edge_case_reaches_what_it_is_named_for(name):
+    e = EDGE_CASES[name]
+    P, R, t, res = edge_solution(name)
+    p = P.p
+    print(name, "m %d n_con %d" % (P.m, P.nc), {k: res[k] for k in ("outer", "inner", "inner_end", "e_before", "e_after")})
+    assert res["inner_end"] == e["end"], res
+    assert len(res["inner"]) == res["outer"] <= p["max_outer"]
+    in_deg, con_deg = np.diff(P.in_off), np.diff(P.con_off)
+    if name == "late_breakdown":
+        assert P.m == 30 and res["outer"] == 2
+        for it in res["inner"]:                                      # past the history's length, and inside a chunk of host reads
+            assert it > 256 and it % 300 not in (0, 256), res
+        assert np.isfinite(R).all() and np.isfinite(t).all()
+        assert not is_identity(R, t)                                 # delta survived the breakdown
+    elif name == "breakdown_at_0":
+        assert res["outer"] == 1 and res["inner"] == [0] and is_identity(R, t)
+        x = np.zeros((P.m, 12), f64); x[:, 0] = x[:, 4] = x[:, 8] = 1.0
+        b = -P.Jt(x, P.residuals(x))
+        with np.errstate(all="ignore"):
+            z = np.where(P.diag(x) > 0, b / P.diag(x), 0.0)
+            assert P.dot(b, z) > 0 and P.dot(z, P.Jt(x, P.J(x, z))) == np.inf          # rho_0 > 0, p.q = +inf
+    elif name == "pins":
+        assert res["outer"] == 1 and res["inner"] == [0] and res["e_before"] == 0.0 and is_identity(R, t)
+    elif name == "no_energy":
+        assert res["outer"] == 1 and res["inner"] == [0] and is_identity(R, t)
+    elif name == "check_every_1":
+        assert res["outer"] == 2 and any(it % 16 for it in res["inner"]), res
+    elif name == "check_beyond_max":
+        assert res["outer"] == 64 and res["inner"] == [3] * 64
+    elif name == "hist_cap":
+        assert res["inner"] == [600]
+    elif name == "no_rot_no_reg":
+        assert (con_deg == 0).any()                                  # nodes that no constraint touches: D == 0 rows, z = 0
+        x = np.zeros((P.m, 12), f64); x[:, 0] = x[:, 4] = x[:, 8] = 1.0
+        D = P.diag(x)
+        assert (D[con_deg == 0] == 0).all() and (D[con_deg > 0] > 0).any()
+        assert not is_identity(R, t)
+    elif name in ("m256", "m257", "nc513"):
+        assert (P.m, P.nc) == {"m256": (256, 257), "m257": (257, 256), "nc513": (257, 513)}[name]
+        assert (in_deg == 0).any()                                   # an empty run in the list of edges that point at a node
+    elif name == "three_passes":
+        assert P.m == 66000 and P.nc == 300
+        assert P.edges.max() >= 65536 and P.idx4.max() >= 65536      # keys whose bits 16-19 the third pass sorts
+    elif name == "one_hub":
+        assert con_deg.max() >= HUB and P.nc == HUB
+    else:
+        raise AssertionError("no check written for " + name)

@@ -20,12 +20,13 @@ W, H = tg.W, tg.H
 SHORT = dict(max_outer=3, max_inner=48)          # constructed cases: a few steps are enough to compare every kernel's bits
 
 
-def solve_and_check(f, look, src, t0, dst, what, **params):
+def solve_and_check(f, look, src, t0, dst, what, ref=None, **params):
+    """ref: the restatement's (rotations, translations, result) of exactly these inputs, where a test has them already"""
     npos, nt0, _ = f.graph_nodes()
     assert np.array_equal(f.graph_edges(), gs.edges_of(npos, nt0, look)), what + " edges"
     res = f.graph_solve(src, t0, dst, **params)
     R, t = f.graph_transforms()
-    Rr, tr, rr = gs.solve(npos, nt0, look, src, t0, dst, **params)
+    Rr, tr, rr = ref if ref is not None else gs.solve(npos, nt0, look, src, t0, dst, **params)
     print(what, res)
     assert (res["outer"], res["inner"], res["inner_end"]) == (rr["outer"], rr["inner"], rr["inner_end"]), (what, res, rr)
     for k in ("e_before", "e_after", "e_rot", "e_reg", "e_con"):
@@ -268,6 +269,8 @@ def test_graph_solve_smoke_cpp_agrees_with_the_python_mirror(product_lib, tmp_pa
     assert lines[0] == "graph nodes=%d edges %016x" % (m, tg.fnv(f.graph_edges()))
     dst = gp.copy()
     dst[m // 2:, 0] += f32(0.01); dst[m // 2:, 2] -= f32(0.02)
+    f.graph_solve(gp, gt, dst, max_outer=3, inner_check=1)           # the smoke's first solve: no result record there
+    every_1 = tg.fnv(*f.graph_transforms())
     res = f.graph_solve(gp, gt, dst, max_outer=3)
     inner = (res["inner"] + [0, 0, 0])[:3]
     en = np.array([res[k] for k in ("e_before", "e_after", "e_rot", "e_reg", "e_con")], f64)
@@ -278,3 +281,4 @@ def test_graph_solve_smoke_cpp_agrees_with_the_python_mirror(product_lib, tmp_pa
     model = f.get_model()
     assert lines[3] == "model %d %016x" % (len(model["confidences"]), tg.fnv(model["positions"]))
     assert lines[4] == "stale_after_apply 1"
+    assert lines[5] == "no_record_check_every_1 transforms %016x" % every_1
